@@ -3,7 +3,10 @@
 
 Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N > 1 launched as
 ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`` (one rank per GPU).
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  Such a plain run sets up, runs W warm-up steps and ~0.5 s more of the same workload,
+times exactly K steps once (`ms_per_step` = that time / K), writes the last step's logits with ``--dump-outputs DIR``
+and prints the line.  Everything else below (the drop-in figures, roofline, other precisions and sizes, parity, the
+training and MaxViT legs, the CPU baseline) runs only with ``--full``, which prints the long line first.
 
 Workload = BASELINE.json configs[1]: ConvNeXt-pico multi-modal (mm_ConvNeXt) bf16 inference on a
 batch of 1024 synthetic alerts per GPU (63x63x3 triplet + 25 metadata scalars each), inputs
@@ -39,6 +42,12 @@ def parse_args():
     ap.add_argument("--pipeline-depth", type=int, default=3,
                     help="batches in flight on alternating HIP streams in the timed loop (btsbot_amd.ScoreStream); "
                          "1 = plain model(...) calls on one stream")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (drop-in calls, roofline, parity, other precisions "
+                         "and sizes, training and MaxViT legs, CPU baseline); the options below apply to --full runs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the logits of the last timed step as DIR/logits.npy (float32; "
+                         "rank r > 0: logits_rank<r>.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-legs", action="store_true",
                     help="skip the f16 / f32 precision legs and the parity object (profiling runs)")
@@ -343,6 +352,7 @@ def maxvit_leg(dev, rank, world, dist, fence, args):
 
 WARM_SECONDS = 0.5     # every timed region is preceded by at least this much of its own workload (clocks, caches)
 BLOCKS = 7             # the K-step block is timed this many times; the MEDIAN block is reported
+FULL_LEG_STEPS = 1000  # --full: a secondary leg times blocks of at most this many steps, whatever --steps the headline has
 
 
 def timed_blocks(run, steps, warmup, fence, dist, dev, blocks=BLOCKS, warm_seconds=WARM_SECONDS):
@@ -379,6 +389,80 @@ def timed_blocks(run, steps, warmup, fence, dist, dev, blocks=BLOCKS, warm_secon
         times.append(el)
     times.sort()
     return times[len(times) // 2], times, last
+
+
+def timed_steps(run, steps, warmup, fence, dist, dev, warm_seconds=WARM_SECONDS):
+    """The headline's timing: `warmup` untimed steps, then >= warm_seconds of the workload in chunks of at most
+    max(warmup, 1) steps (never a whole `steps` block: the time outside the timed steps stays small whatever `steps`
+    is), then ONE timed region of exactly `steps` steps, bracketed by barrier + synchronize on both sides and reduced
+    with MAX over the ranks.  Returns (seconds, last output)."""
+    last = None
+    if warmup > 0:
+        last = run(warmup)
+    fence()
+    chunk = max(1, min(steps, warmup))
+    t_end = time.perf_counter() + warm_seconds
+    while True:
+        go = time.perf_counter() < t_end
+        if dist is not None:   # every rank must run the same number of chunks: `run` may contain collectives
+            g = torch.tensor([1.0 if go else 0.0], device=dev)
+            dist.all_reduce(g, op=dist.ReduceOp.MIN)
+            go = g.item() > 0.5
+        if not go:
+            break
+        last = run(chunk)
+        torch.cuda.synchronize(dev)
+    fence()
+    t0 = time.perf_counter()
+    last = run(steps)
+    fence()
+    el = time.perf_counter() - t0
+    if dist is not None:
+        t = torch.tensor([el], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        el = t.item()
+    return el, last
+
+
+def dump_outputs(out_dir, rank, **arrays):
+    """--dump-outputs: the tensors the timed path handed its caller in its last step, as float32 .npy files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), t.detach().float().cpu().numpy())
+
+
+def headline_line(args, world, elapsed, depth):
+    """The contract's fields, the same in a plain and in a --full run."""
+    total_alerts = args.batch * world * args.steps
+    return {
+        "metric": METRIC,
+        "value": round(total_alerts / elapsed, 1),
+        "unit": "alerts/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": args.precision,
+        "data": "synthetic",
+        "config": {
+            "workload": "BASELINE.json configs[1]: ConvNeXt-pico multi-modal (mm_ConvNeXt) "
+                        f"{args.precision} inference, batch={args.batch} synthetic triplets per GPU, "
+                        "inputs resident in HBM, logits+scores out",
+            "per_gpu_batch": args.batch, "global_batch": args.batch * world,
+            "precision": args.precision, "weights": "seeded random, layer-scale ~1",
+            "parallelism": f"{world} independent replicas, batch-sharded, no collective",
+            "pipeline_depth": depth,
+            "api": ("btsbot_amd.ScoreStream (the library's scoring loop: consecutive batches on alternating HIP "
+                    "streams)" if depth > 1 else "drop-in model(image_input=, metadata_input=) calls"),
+        },
+        "timing": {"blocks": 1, "steps_per_block": args.steps, "reported": "one timed block of --steps steps",
+                   "gpu_warm_seconds_before_timing": WARM_SECONDS},
+    }
 
 
 def maxvit_train_leg(dev, rank, world, dist, fence, args):
@@ -795,8 +879,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
+    steps2 = min(args.steps, FULL_LEG_STEPS)    # the --full legs' steps per block
+
     def timed(run):
-        return timed_blocks(run, args.steps, args.warmup, fence, dist, dev)
+        return timed_blocks(run, steps2, args.warmup, fence, dist, dev)
 
     def run_serial(n):
         o = None
@@ -804,10 +890,11 @@ def main():
             o = step()
         return o
 
-    # one stream, one model(...) call after the other
-    serial_elapsed, serial_blocks, out = timed(run_serial)
-    elapsed, blocks_s = serial_elapsed, serial_blocks
+    pipelined_elapsed = None
     if args.pipeline_depth > 1:
+        if args.full:
+            # one stream, one model(...) call after the other (the drop-in figures of the --full line)
+            serial_elapsed = timed(run_serial)[0] * args.steps / steps2     # (seconds per K steps)
         # the scoring loop as the library runs it over a sequence of batches: consecutive batches on alternating HIP
         # streams (btsbot_amd.ScoreStream), every batch a full pass of the same kernels, all K finished inside the
         # timed region
@@ -820,25 +907,35 @@ def main():
                 pass
             return o
 
-        pipelined_elapsed, pipelined_blocks, out = timed(run_pipelined)
+        pipelined_elapsed, out = timed_steps(run_pipelined, args.steps, args.warmup, fence, dist, dev)
         del scorer
         # The headline is ALWAYS the library's scoring loop (ScoreStream), never the better of the two: two HIP streams
         # only overlap when the runtime gives them different hardware queues; where it does not (seen once in ~20
         # processes) the pipelined loop is the slower one and the line says so (`pipelined_slower_than_serial`).
         headline_depth = args.pipeline_depth
-        elapsed, blocks_s = pipelined_elapsed, pipelined_blocks
+        elapsed = pipelined_elapsed
     else:
-        pipelined_elapsed, headline_depth = None, 1
+        serial_elapsed, out = timed_steps(run_serial, args.steps, args.warmup, fence, dist, dev)
+        elapsed, headline_depth = serial_elapsed, 1
     if not os.environ.get("BTSBOT_AMD_S0_DIAG"):
         assert torch.isfinite(out).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, logits=out)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline_line(args, world, elapsed, headline_depth)), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- roofline leg: same K steps, every launch bracketed by HIP events on the launch stream
     t_end = time.perf_counter() + WARM_SECONDS
     while time.perf_counter() < t_end:
-        run_serial(args.steps)
+        run_serial(steps2)
         torch.cuda.synchronize(dev)
     model.set_profile(True)
-    prof_steps = max(args.steps, 100)       # >= 100 launches per kernel behind the averages
+    prof_steps = max(steps2, 100)           # >= 100 launches per kernel behind the averages
     for _ in range(prof_steps):
         step()
     prof = model.collect_profile()
@@ -859,12 +956,12 @@ def main():
             if prec == args.precision:
                 continue
             try:
-                legs[prec] = precision_leg(prec, dev, img, meta, max(5, args.steps // (5 if prec == "f32" else 1)),
+                legs[prec] = precision_leg(prec, dev, img, meta, max(5, steps2 // (5 if prec == "f32" else 1)),
                                            3, fence, dist, world, with_parity=(rank == 0))
             except Exception as e:   # noqa: BLE001
                 legs[prec] = {"error": f"{type(e).__name__}: {e}"}
         try:
-            legs["convnext_nano"] = nano_leg(args.precision, dev, img, meta, max(5, args.steps // 2), 3, fence, dist, world,
+            legs["convnext_nano"] = nano_leg(args.precision, dev, img, meta, max(5, steps2 // 2), 3, fence, dist, world,
                                              with_parity=(rank == 0))
         except Exception as e:   # noqa: BLE001
             legs["convnext_nano"] = {"error": f"{type(e).__name__}: {e}"}
@@ -875,11 +972,11 @@ def main():
         try:
             big_img, big_meta, _ = synthetic_batch(8192, seed=3 + rank)
             big_img, big_meta = big_img.to(dev), big_meta.to(dev)
-            leg = precision_leg_on(model, big_img, big_meta, max(5, args.steps // 5), 2, fence, dist, world)
+            leg = precision_leg_on(model, big_img, big_meta, max(5, steps2 // 5), 2, fence, dist, world)
             leg["workload"] = "BASELINE.json configs[4] batch size (8192 alerts per call) at %s, serial calls" % args.precision
             legs["batch8192"] = leg
             if args.precision != "fp8":
-                legs["fp8"] = precision_leg("fp8", dev, img, meta, args.steps, 3, fence, dist, world, with_parity=(rank == 0))
+                legs["fp8"] = precision_leg("fp8", dev, img, meta, steps2, 3, fence, dist, world, with_parity=(rank == 0))
                 with warnings.catch_warnings():
                     warnings.simplefilter("ignore")
                     m8 = btsbot_amd.mm_ConvNeXt(CONFIG, precision="fp8")
@@ -894,7 +991,7 @@ def main():
                         pass
                     return o
 
-                n8 = max(6, args.steps // 8)
+                n8 = max(6, steps2 // 8)
                 e8, _, _ = timed_blocks(run8, n8, 2, fence, dist, dev, blocks=5, warm_seconds=0.3)
                 legs["fp8_batch8192"] = dict(
                     value=round(8192 * world * n8 / e8, 1), unit="alerts/s", steps=n8, ms_per_step=round(1e3 * e8 / n8, 4),
@@ -1015,37 +1112,13 @@ def main():
         achieved = fam_flop / (fam_ms * 1e-3) / 1e12
         lowest = min(per_kernel, key=lambda k: per_kernel[k]["frac"])
         total_alerts = args.batch * world * args.steps
-        line = {
-            "metric": METRIC,
-            "value": round(total_alerts / elapsed, 1),
-            "unit": "alerts/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": args.precision,
-            "data": "synthetic",
-            "config": {
-                "workload": "BASELINE.json configs[1]: ConvNeXt-pico multi-modal (mm_ConvNeXt) "
-                            f"{args.precision} inference, batch={args.batch} synthetic triplets per GPU, "
-                            "inputs resident in HBM, logits+scores out",
-                "per_gpu_batch": args.batch, "global_batch": args.batch * world,
-                "precision": args.precision, "weights": "seeded random, layer-scale ~1",
-                "parallelism": f"{world} independent replicas, batch-sharded, no collective",
-                "pipeline_depth": headline_depth,
-                "drop_in_value": round(total_alerts / serial_elapsed, 1),
-                "drop_in_ms_per_step": round(1e3 * serial_elapsed / args.steps, 4),
-                "drop_in_api": "plain model(image_input=, metadata_input=) calls on one stream "
-                               "(/root/reference/btsbot/inference_example.py:84)",
-                "api": ("btsbot_amd.ScoreStream (the library's scoring loop: consecutive batches on alternating HIP "
-                        "streams)" if headline_depth > 1 else "drop-in model(image_input=, metadata_input=) calls"),
-            },
-            "timing": {"blocks": len(blocks_s), "steps_per_block": args.steps, "reported": "median block",
-                       "block_ms_per_step": [round(1e3 * b / args.steps, 4) for b in blocks_s],
-                       "gpu_warm_seconds_before_timing": WARM_SECONDS},
+        line = headline_line(args, world, elapsed, headline_depth)
+        line["config"].update(
+            drop_in_value=round(total_alerts / serial_elapsed, 1),
+            drop_in_ms_per_step=round(1e3 * serial_elapsed / args.steps, 4),
+            drop_in_api="plain model(image_input=, metadata_input=) calls on one stream (the reference's "
+                        "inference_example.py:84)")
+        line.update({
             "pipelined": None if pipelined_elapsed is None else {
                 "note": f"btsbot_amd.ScoreStream(depth={args.pipeline_depth}) API: the K steps as consecutive batches on "
                         "alternating HIP streams (not the reference's call signature)",
@@ -1070,7 +1143,7 @@ def main():
             "kernels": kernels,
             "flop_per_alert": 133701376 + 210000,
             "whole_net_tflops": round((133701376 + 210000) * total_alerts / elapsed / 1e12, 2),
-        }
+        })
         if parity is not None:
             line["parity"] = parity
         if legs:

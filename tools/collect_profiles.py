@@ -29,7 +29,7 @@ def family(k):
 
 
 fa, wa = agg(F, "FETCH_SIZE"), agg(W, "WRITE_SIZE")
-out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --steps 5 "
+out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 5 "
                  "--warmup 2 --no-cpu-baseline --train-steps 0",
        "correction": "bytes = 2*FETCH_SIZE*1024 + WRITE_SIZE*1024 (gfx950 FETCH_SIZE reads 1/2: tools/pmc_calib, "
                      "0.500 on dword, dwordx4 and the stem gather; WRITE_SIZE exact)",

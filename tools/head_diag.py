@@ -2,7 +2,7 @@
 import os, sys, subprocess, json
 for diag in (0, 1, 2, 4, 8, 16, 31):
     env = dict(os.environ, BTSBOT_AMD_HEAD_DIAG=str(diag), BTSBOT_AMD_S0_DIAG="0")
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "10", "--warmup", "3", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "10", "--warmup", "3", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True)
     try:
         d = json.loads(r.stdout)

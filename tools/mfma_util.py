@@ -2,10 +2,10 @@
 
   rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU \
             SQ_INSTS_VALU_MFMA_MOPS_BF16 GRBM_GUI_ACTIVE --kernel-trace --output-format csv \
-            -d gpurun_out/mfma -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --train-steps 0 \
+            -d <trace dir> -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --train-steps 0 \
             --maxvit-steps 1 --maxvit-batch 256
 
-  python tools/mfma_util.py gpurun_out/mfma profiles/r01_mfma_util.json
+  python tools/mfma_util.py <trace dir> profiles/r01_mfma_util.json
 
 Per kernel symbol (sums over its dispatches):
   mfma_busy      = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs * GRBM_GUI_ACTIVE / 8)

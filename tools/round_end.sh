@@ -11,7 +11,7 @@ PROF="--pipeline-depth 1 --no-extra-legs"   # profiled runs: one stream, so a ke
 if [ "$PHASE" != profile ]; then
 timeout -k 10 700 python -m pytest tests -q -m gpu -x > $O/pytest_gpu.log 2>&1 &&
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 &&
-( time timeout -k 10 400 python bench.py ) > $O/bench_default.log 2>&1 &&
+( time timeout -k 10 400 python bench.py --full ) > $O/bench_default.log 2>&1 &&
 timeout -k 10 120 python tools/nano_bench.py 1024 bf16 > $O/nano.log 2>&1 &&
 timeout -k 10 120 python tools/stamps_nano.py > $O/stamps_nano.log 2>&1 &&
 timeout -k 10 120 python tools/stamps.py 1024 > $O/stamps.log 2>&1 &&
@@ -27,11 +27,11 @@ echo "measure rc=$?" > $O/chain_measure.log
 tail -3 $O/pytest_gpu.log; head -1 $O/nano.log; cat $O/train_ab.log; tail -2 $O/smoke.log; tail -5 $O/bench_default.log | cut -c1-400; cat $O/chain_measure.log
 fi
 if [ "$PHASE" = measure ]; then exit 0; fi
-timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --steps 50 --warmup 10 --no-cpu-baseline --train-steps 0 --maxvit-train-steps 0 $PROF > $O/trace.log 2>&1 &&
-timeout -k 10 200 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --train-steps 0 --maxvit-train-steps 0 $PROF > $O/pmc_fetch.log 2>&1 &&
-timeout -k 10 200 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --train-steps 0 --maxvit-train-steps 0 $PROF > $O/pmc_write.log 2>&1 &&
-timeout -k 10 200 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU_MFMA_MOPS_BF16 GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/mfma -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --train-steps 0 --maxvit-steps 1 --maxvit-batch 256 --maxvit-train-steps 0 $PROF > $O/mfma.log 2>&1 &&
-timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/train_trace -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --train-steps 20 --maxvit-steps 0 --maxvit-train-steps 0 $PROF > $O/train_trace.log 2>&1
+timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --train-steps 0 --maxvit-train-steps 0 $PROF > $O/trace.log 2>&1 &&
+timeout -k 10 200 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --train-steps 0 --maxvit-train-steps 0 $PROF > $O/pmc_fetch.log 2>&1 &&
+timeout -k 10 200 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --train-steps 0 --maxvit-train-steps 0 $PROF > $O/pmc_write.log 2>&1 &&
+timeout -k 10 200 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU_MFMA_MOPS_BF16 GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/mfma -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --train-steps 0 --maxvit-steps 1 --maxvit-batch 256 --maxvit-train-steps 0 $PROF > $O/mfma.log 2>&1 &&
+timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/train_trace -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --train-steps 20 --maxvit-steps 0 --maxvit-train-steps 0 $PROF > $O/train_trace.log 2>&1
 rc=$?
 if [ $rc = 0 ]; then
 timeout -k 10 200 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch_train -- python3 tools/train_bench.py 1024 bf16 5 > $O/pmc_fetch_train.log 2>&1 &&

@@ -3,7 +3,7 @@ import os, sys, subprocess, json
 batch = sys.argv[1] if len(sys.argv) > 1 else "1024"
 for diag in (0, 64, 51, 115):
     env = dict(os.environ, BTSBOT_AMD_S0_DIAG=str(diag))
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--batch", batch],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--batch", batch],
                          env=env, capture_output=True, text=True)
     try:
         d = json.loads(r.stdout)

@@ -743,6 +743,16 @@ extern "C" int btsbot_set_option(btsbot_handle h, const char* key, int value) {
     }
     return BTSBOT_OK;
   }
+  if (strcmp(key, "query_maxvit_split") == 0) {
+    // a query: BTSBOT_OK when the MaxViT inference forward runs its matrix products on split operands (gemm_x2.hip)
+    if (!(h->has_image && h->is_maxvit && maxvit_split(h))) {
+      btsbot_set_error("query_maxvit_split: this handle's %s", h->has_image && h->is_maxvit
+                                                                  ? "MaxViT GEMMs run on the operand type of its precision"
+                                                                  : "image branch is not MaxViT");
+      return BTSBOT_ERR_STATE;
+    }
+    return BTSBOT_OK;
+  }
   if (strcmp(key, "exchange") == 0) {
     if (value != 0 && value != 1) {
       btsbot_set_error("set_option: exchange is 0 (one all-reduce per span) or 1 (reduce-scatter + all-gather), got %d", value);
@@ -1814,6 +1824,21 @@ extern "C" int btsbot_op_gemm(int prec, int epi, const void* X, const void* W, c
       K < 1 || (epi == EPI_RESID && (gamma == nullptr || resid == nullptr))) {
     btsbot_set_error("op_gemm: invalid argument");
     return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (prec == BTSBOT_F16X2) {   // fp32 X and W: W split into its f16 head and remainder planes here, stream-ordered
+    hipStream_t st = (hipStream_t)stream;
+    if (M == 0) return BTSBOT_OK;
+    void* wsplit = nullptr;
+    HIP_TRY(hipMallocAsync(&wsplit, (size_t)N * K * 4, st));
+    const float* w = reinterpret_cast<const float*>(W);
+    int s = launch_cast(BTSBOT_F16, w, wsplit, (int64_t)N * K, st);
+    if (s == BTSBOT_OK)
+      s = launch_rowscale_cast_lo(w, nullptr, reinterpret_cast<f16_t*>(wsplit) + (size_t)N * K, N, K, st);
+    if (s == BTSBOT_OK)
+      s = launch_gemm_x2(epi, reinterpret_cast<const float*>(X), wsplit, bias, gamma, resid, reinterpret_cast<float*>(out),
+                         M, N, K, st);
+    HIP_TRY(hipFreeAsync(wsplit, st));
+    return s;
   }
   return launch_gemm(prec, epi, X, W, bias, gamma, resid, out, M, N, K, (hipStream_t)stream);
 }

@@ -259,6 +259,16 @@ int launch_gemm(int prec, int epi, const void* X, const void* W, const float* bi
 int launch_gemm_gated(int prec, const void* X, const float* gate, int rows_per_alert, const void* W,
                       const float* resid, float* out, int M, int N, int K, hipStream_t st);
 
+// split-operand form (gemm_x2.hip, the MaxViT forward of an f16x2 handle): X fp32 [M][K], W the packed f16 head plane
+// [N][K] followed by the remainder plane; out fp32 for every epilogue (EPI_GELU / RESID / BIAS / SILU / BIAS_T, resid may
+// alias out); K % 8 == 0, N % 4 == 0
+int launch_gemm_x2(int epi, const float* X, const void* W, const float* bias, const float* gamma, const float* resid,
+                   float* out, int M, int N, int K, hipStream_t st);
+// ... and launch_gemm_gated's form: out = resid + (X[m][k] * gate[m / rows_per_alert][k]) . W^T, the product split after
+// the gate
+int launch_gemm_x2_gated(const float* X, const float* gate, int rows_per_alert, const void* W, const float* resid,
+                         float* out, int M, int N, int K, hipStream_t st);
+
 // pipelined LDS-DMA variant for the 16-bit modes (gemm2.hip); launch_gemm dispatches to it
 bool gemm2_supported(int prec, int M, int N, int K);
 int launch_gemm2(int prec, int epi, const void* X, const void* W, const float* bias,

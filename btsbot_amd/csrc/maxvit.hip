@@ -146,6 +146,8 @@ int maxvit_build_tables(btsbot_ctx* h, size_t* extra_cursor) {
   mv->p_stem2 = mv_bump(cur, (size_t)64 * 288 * esz);
   mv->p_zero = mv_bump(cur, 2048 * 4);
   mv->p_one = mv_bump(cur, 2048 * 4);
+  mv->x2 = h->x2;
+  if (mv->x2) mv->p_x2_tmp = mv_bump(cur, (size_t)64 * 288 * 4);
   int cin = 64, hw = 112;
   for (int i = 0; i < 4; ++i) {
     for (int j = 0; j < MV_DEPTHS[i]; ++j) {
@@ -201,6 +203,8 @@ void maxvit_free(btsbot_ctx* h) {
   h->mv = nullptr;
 }
 
+bool maxvit_split(const btsbot_ctx* h) { return h->mv != nullptr && h->mv->x2; }
+
 #define MTRY(call)                  \
   do {                              \
     int _s = (call);                \
@@ -214,6 +218,19 @@ static int fold_bn(btsbot_ctx* h, const BnPk& b, int n, hipStream_t st) {
                         reinterpret_cast<float*>(h->extra + b.p_shift), n, st);
 }
 
+// a GEMM filter image: the operand type's copy of in[r][c] * rowscale[r] (rowscale may be NULL), or in an f16x2 handle
+// its f16 heads followed by the f16 remainders of the same fp32 product
+static int mv_pack_filter(const MaxVit* mv, int prec, const float* in, const float* rowscale, void* out, int rows,
+                          int cols, hipStream_t st) {
+  if (mv->x2) {
+    if (rowscale != nullptr) MTRY(launch_rowscale_cast(BTSBOT_F16, in, rowscale, out, rows, cols, st));
+    else MTRY(launch_cast(BTSBOT_F16, in, out, (int64_t)rows * cols, st));
+    return launch_rowscale_cast_lo(in, rowscale, reinterpret_cast<f16_t*>(out) + (size_t)rows * cols, rows, cols, st);
+  }
+  if (rowscale != nullptr) return launch_rowscale_cast(prec, in, rowscale, out, rows, cols, st);
+  return launch_cast(prec, in, out, (int64_t)rows * cols, st);
+}
+
 int maxvit_pack(btsbot_ctx* h, hipStream_t st) {
   MaxVit* mv = h->mv;
   const int prec = h->cfg.precision;
@@ -221,28 +238,36 @@ int maxvit_pack(btsbot_ctx* h, hipStream_t st) {
   unsigned char* ex = h->extra;
   auto F = [&](size_t off) { return reinterpret_cast<float*>(ex + off); };
   MTRY(fold_bn(h, mv->stem_bn, 32, st));
-  MTRY(launch_mv_pack_stem1(prec, m + mv->stem1_w, F(mv->stem_bn.p_scale), ex + mv->p_stem1, st));
-  MTRY(launch_mv_pack_conv3(prec, m + mv->stem2_w, ex + mv->p_stem2, 64, 32, st));
+  if (mv->x2) {   // the stem images in fp32 first (BatchNorm folded, im2col order), then split
+    float* tmp = F(mv->p_x2_tmp);
+    MTRY(launch_mv_pack_stem1(BTSBOT_F32, m + mv->stem1_w, F(mv->stem_bn.p_scale), tmp, st));
+    MTRY(mv_pack_filter(mv, prec, tmp, nullptr, ex + mv->p_stem1, 32, 32, st));
+    MTRY(launch_mv_pack_conv3(BTSBOT_F32, m + mv->stem2_w, tmp, 64, 32, st));
+    MTRY(mv_pack_filter(mv, prec, tmp, nullptr, ex + mv->p_stem2, 64, 288, st));
+  } else {
+    MTRY(launch_mv_pack_stem1(prec, m + mv->stem1_w, F(mv->stem_bn.p_scale), ex + mv->p_stem1, st));
+    MTRY(launch_mv_pack_conv3(prec, m + mv->stem2_w, ex + mv->p_stem2, 64, 32, st));
+  }
   MTRY(launch_mv_fill(F(mv->p_zero), 0.f, 2048, st));
   MTRY(launch_mv_fill(F(mv->p_one), 1.f, 2048, st));
   for (const MvBlock& b : mv->blocks) {
-    if (b.sc_w >= 0) MTRY(launch_cast(prec, m + b.sc_w, ex + b.p_sc, (int64_t)b.c * b.cin, st));
+    if (b.sc_w >= 0) MTRY(mv_pack_filter(mv, prec, m + b.sc_w, nullptr, ex + b.p_sc, b.c, b.cin, st));
     MTRY(fold_bn(h, b.pre, b.cin, st));
     MTRY(fold_bn(h, b.n1, b.mid, st));
     MTRY(fold_bn(h, b.n2, b.mid, st));
     // conv1_1x1 followed by BN1: W' = diag(s1) W, b' = b s1 + t1
-    MTRY(launch_rowscale_cast(prec, m + b.c1_w, F(b.n1.p_scale), ex + b.p_c1, b.mid, b.cin, st));
+    MTRY(mv_pack_filter(mv, prec, m + b.c1_w, F(b.n1.p_scale), ex + b.p_c1, b.mid, b.cin, st));
     MTRY(launch_mv_fold_bias(m + b.c1_b, F(b.n1.p_scale), F(b.n1.p_shift), F(b.p_c1b), b.mid, st));
     MTRY(launch_mv_pack_dw(m + b.c2_w, F(b.n2.p_scale), F(b.p_dw), b.mid, st));
     MTRY(launch_mv_fold_bias(m + b.c2_b, F(b.n2.p_scale), F(b.n2.p_shift), F(b.p_dwb), b.mid, st));
-    MTRY(launch_cast(prec, m + b.c3_w, ex + b.p_c3, (int64_t)b.c * b.mid, st));
+    MTRY(mv_pack_filter(mv, prec, m + b.c3_w, nullptr, ex + b.p_c3, b.c, b.mid, st));
     MTRY(launch_transpose_f32(m + b.se2_w, F(b.p_se2t), b.mid, b.rd, st));
     for (const AttnPk& a : b.attn) {
       const int c = b.c;
-      MTRY(launch_cast(prec, m + a.qkv_w, ex + a.p_qkv, (int64_t)3 * c * c, st));
-      MTRY(launch_cast(prec, m + a.proj_w, ex + a.p_proj, (int64_t)c * c, st));
-      MTRY(launch_cast(prec, m + a.fc1_w, ex + a.p_fc1, (int64_t)4 * c * c, st));
-      MTRY(launch_cast(prec, m + a.fc2_w, ex + a.p_fc2, (int64_t)4 * c * c, st));
+      MTRY(mv_pack_filter(mv, prec, m + a.qkv_w, nullptr, ex + a.p_qkv, 3 * c, c, st));
+      MTRY(mv_pack_filter(mv, prec, m + a.proj_w, nullptr, ex + a.p_proj, c, c, st));
+      MTRY(mv_pack_filter(mv, prec, m + a.fc1_w, nullptr, ex + a.p_fc1, 4 * c, c, st));
+      MTRY(mv_pack_filter(mv, prec, m + a.fc2_w, nullptr, ex + a.p_fc2, c, 4 * c, st));
       MTRY(launch_mv_pack_relbias(m + a.rel, F(a.p_bias), c / 32, st));
       MTRY(launch_mv_pack_relbias64(m + a.rel, F(a.p_bias64), c / 32, st));
       if (a.fused) MTRY(launch_pack_fused_mlp(prec, c, m + a.fc1_w, m + a.fc2_w, ex + a.p_fused, st));
@@ -292,9 +317,12 @@ size_t maxvit_ws_bytes(const btsbot_ctx* h, int chunk) {
   return total;
 }
 
-// GEMM dispatch of the MaxViT schedule: the LDS-free streaming kernel where it applies (K = 64 / 128)
+// GEMM dispatch of the MaxViT schedule: an f16x2 handle's products on split operands (fp32 maps in and out)
 static int mv_gemm(const MaxVit* mv, int prec, int epi, const void* X, const void* W, const float* bias,
                    const float* gamma, const float* resid, void* out, int M, int N, int K, hipStream_t st) {
+  if (mv->x2)
+    return launch_gemm_x2(epi, reinterpret_cast<const float*>(X), W, bias, gamma, resid, reinterpret_cast<float*>(out),
+                          M, N, K, st);
   return launch_gemm(prec, epi, X, W, bias, gamma, resid, out, M, N, K, st);
 }
 
@@ -343,8 +371,8 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
   } else {
     MTRY(mv_timed(h, CAT_MV_STEM, st, [&] { return launch_mv_resize_im2col(prec, img, Bb, nb, st); }));
     MTRY(mv_timed(h, CAT_MV_G_STEM, st, [&] {
-      return launch_gemm(prec, EPI_SILU, Bb, ex + mv->p_stem1, F(mv->stem_bn.p_shift), nullptr, nullptr,
-                         Cc, M0, 32, 32, st);
+      return mv_gemm(mv, prec, EPI_SILU, Bb, ex + mv->p_stem1, F(mv->stem_bn.p_shift), nullptr, nullptr,
+                     Cc, M0, 32, 32, st);
     }));
   }
   if (prec != BTSBOT_F32 && !mv->stem_im2col) {
@@ -361,8 +389,8 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
   } else {
     MTRY(mv_timed(h, CAT_MV_STEM, st, [&] { return launch_mv_im2col3(prec, Cc, A, nb, 112, 32, st); }));
     MTRY(mv_timed(h, CAT_MV_G_STEM, st, [&] {
-      return launch_gemm(prec, EPI_BIAS, A, ex + mv->p_stem2, zero, nullptr, nullptr, x, M0, 64, 288,
-                         st);
+      return mv_gemm(mv, prec, EPI_BIAS, A, ex + mv->p_stem2, zero, nullptr, nullptr, x, M0, 64, 288,
+                     st);
     }));
   }
   if (h->debug && h->taps[0])
@@ -467,6 +495,9 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
       }));
     } else {
       MTRY(mv_timed(h, CAT_MV_G_CONV3, st, [&] {
+        if (mv->x2)
+          return launch_gemm_x2_gated(reinterpret_cast<const float*>(m2b), gate, hw2, ex + b.p_c3, resid, dst, Mo, b.c,
+                                      b.mid, st);
         return launch_gemm_gated(prec, m2b, gate, hw2, ex + b.p_c3, resid, dst, Mo, b.c, b.mid, st);
       }));
     }
@@ -589,8 +620,8 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
                            4 * c, c, st);
       }));
       MTRY(mv_timed(h, CAT_MV_G_FC2, st, [&] {
-        return launch_gemm(prec, EPI_RESID, Bb, ex + a.p_fc2, m + a.fc2_b, one, x, x, Mo, c, 4 * c,
-                           st);
+        return mv_gemm(mv, prec, EPI_RESID, Bb, ex + a.p_fc2, m + a.fc2_b, one, x, x, Mo, c, 4 * c,
+                       st);
       }));
     }
     // debug taps: output of the last block of every stage

@@ -32,6 +32,10 @@ struct MaxVit {
   int64_t stem1_w, stem2_w, norm_w, norm_b;
   BnPk stem_bn;
   size_t p_stem1, p_stem2, p_zero, p_one;
+  // f16x2 handles: every GEMM of the forward runs on split operands (gemm_x2.hip); its filter images hold the f16 head plane
+  // followed by the remainder plane (the same 4 bytes per element as the fp32 images), p_x2_tmp stages the fp32 stem filters
+  bool x2 = false;
+  size_t p_x2_tmp = 0;
   std::vector<MvBlock> blocks;
   // workspace offsets (bytes) for the current reservation
   size_t o_x, o_x2, o_a, o_b, o_c, o_d, o_e, o_gate, o_feat, o_part, o_sescr, o_wg;

@@ -20,14 +20,22 @@ def _stream(t):
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
-def gemm(x, w, bias, epi="bias", gamma=None, resid=None, precision="f32"):
-    """epi in {'gelu','resid','bias'}; x [M,K], w [N,K] in the precision's dtype."""
-    dt = _DT[precision]
+_EPI = {"gelu": 0, "resid": 1, "bias": 2, "silu": 6, "bias_t": 7}
+
+
+def gemm(x, w, bias, epi="bias", gamma=None, resid=None, precision="f32", out=None):
+    """epi in {'gelu','resid','bias','silu','bias_t'}; x [M,K], w [N,K] in the precision's dtype ('f16x2': fp32 x and
+    w, w split into f16 head + remainder inside, every output fp32).  'gelu' / 'silu' / 'bias_t' write the precision's
+    dtype, 'resid' / 'bias' fp32.  out: the output tensor (for 'resid' it may be resid itself: in place)."""
+    dt = torch.float32 if precision == "f16x2" else _DT[precision]
     assert x.dtype == dt and w.dtype == dt and x.is_contiguous() and w.is_contiguous()
     M, K = x.shape
     N = w.shape[0]
-    e = {"gelu": 0, "resid": 1, "bias": 2}[epi]
-    out = torch.empty(M, N, dtype=dt if e == 0 else torch.float32, device=x.device)
+    e = _EPI[epi]
+    odt = dt if epi in ("gelu", "silu", "bias_t") else torch.float32
+    if out is None:
+        out = torch.empty(M, N, dtype=odt, device=x.device)
+    assert out.dtype == odt and out.shape == (M, N) and out.is_contiguous()
     with torch.cuda.device(x.device):
         _lib.check(_lib.lib().btsbot_op_gemm(_lib.PRECISION[precision], e, _p(x), _p(w), _p(bias),
                                              _p(gamma), _p(resid), _p(out), M, N, K, _stream(x)),

@@ -249,7 +249,12 @@ int btsbot_allreduce_grads(btsbot_handle h, void* nccl_comm, float* grads, int n
  *   "query_side_apart" (a query; `value` ignored): BTSBOT_OK when the second stream of btsbot_backward() and the
  *   exchange stream of btsbot_allreduce_grads() were each measured on a hardware pipe of their own, BTSBOT_ERR_STATE
  *   (and a warning on stderr at the time) when none of eight candidates was: two queues of one pipe take turns of ~50 us,
- *   a 1024-alert step then takes 5-7 ms instead of 2.6. */
+ *   a 1024-alert step then takes 5-7 ms instead of 2.6.
+ *   "query_maxvit_split" (a query; `value` ignored): BTSBOT_OK when the handle's MaxViT image branch runs the matrix
+ *   products of its inference forward on split operands -- a BTSBOT_F16X2 handle: fp32 maps split into f16 head +
+ *   remainder, three f16 MFMAs per product, the filters packed as head and remainder planes; attention, depthwise,
+ *   squeeze-excite, LayerNorm and elementwise kernels stay fp32 --, BTSBOT_ERR_STATE for every other handle
+ *   (other precisions, ConvNeXt branches, no image branch). */
 int btsbot_set_option(btsbot_handle h, const char* key, int value);
 
 /* Validation aid with no reference counterpart: when on, forward() keeps fp32 copies of the stem and
@@ -275,7 +280,11 @@ int64_t btsbot_read_tap(btsbot_handle h, const char* name, float* dst, int64_t c
 /* K4/K5/K6: out = epi(X[M,K] . W[N,K]^T + bias[N]) on MFMA.  Replaces conv2d 1x1 (+gelu) /
  * conv2d 1x1 + layer-scale + residual / conv2d 2x2 s2 on pre-gathered patches.
  *   epi 0: out (prec) = gelu(acc + bias)         epi 1: out (f32) = resid + gamma * (acc + bias)
- *   epi 2: out (f32) = acc + bias.   K % (16/sizeof(prec)) == 0, N % 4 == 0.                    */
+ *   epi 2: out (f32) = acc + bias.   K % (16/sizeof(prec)) == 0, N % 4 == 0.
+ *   epi 6: out (prec) = silu(acc + bias)        epi 7: out (prec) = acc + bias
+ *   prec BTSBOT_F16X2: X and W are f32; W is split into f16 head + remainder planes inside the call (a stream-ordered
+ *   scratch of N*K*4 bytes), X in registers, three f16 MFMAs per product; every output is f32 (epi 0, 1, 2, 6, 7),
+ *   K % 8 == 0, N % 4 == 0. */
 int btsbot_op_gemm(int prec, int epi, const void* X, const void* W, const float* bias,
                    const float* gamma, const float* resid, void* out, int M, int N, int K,
                    void* stream);

@@ -259,8 +259,7 @@ extern "C" int btsbot_create(const btsbot_config* cfg, btsbot_handle* out) {
   if (cfg->precision == BTSBOT_F16X2) {   // kernels without a split-operand form run the fp32 schedule
     h->x2 = true;
     h->cfg.precision = BTSBOT_F32;
-    const char* tp = getenv("BTSBOT_AMD_X2_TAIL_F16");
-    h->x2_tail_plain = tp != nullptr && tp[0] == '1';
+    h->x2_tail_plain = env_on("BTSBOT_AMD_X2_TAIL_F16");
   }
   const int w = cfg->wiring;
   h->has_image = (w != BTSBOT_UM_NN);
@@ -326,60 +325,39 @@ extern "C" int btsbot_create(const btsbot_config* cfg, btsbot_handle* out) {
     h->comb_dims[3] = 1;
   }
   build_tables(h);
-  const char* nf = getenv("BTSBOT_AMD_NO_FUSED_MLP");
-  h->use_fused = !(nf != nullptr && nf[0] == '1');
-  const char* ns = getenv("BTSBOT_AMD_NO_STAGE0");
-  h->use_stage0 = !(ns != nullptr && ns[0] == '1');
-  const char* n1 = getenv("BTSBOT_AMD_NO_STAGE1");
-  h->use_stage1 = !(n1 != nullptr && n1[0] == '1');
-  const char* n2 = getenv("BTSBOT_AMD_NO_STAGE2");
-  h->use_s2 = !(n2 != nullptr && n2[0] == '1');
+  h->use_fused = !env_on("BTSBOT_AMD_NO_FUSED_MLP");
+  h->use_stage0 = !env_on("BTSBOT_AMD_NO_STAGE0");
+  h->use_stage1 = !env_on("BTSBOT_AMD_NO_STAGE1");
+  h->use_s2 = !env_on("BTSBOT_AMD_NO_STAGE2");
   h->use_s2p = h->use_s2;
-  {
-    const char* nh = getenv("BTSBOT_AMD_NO_HEAD16");
-    h->use_head16 = !(nh != nullptr && nh[0] == '1');
-  }
-  {
-    const char* n3 = getenv("BTSBOT_AMD_NO_S3");
-    h->use_s3 = !(n3 != nullptr && n3[0] == '1');
-    const char* ndl = getenv("BTSBOT_AMD_NO_DWLN");
-    h->use_dwln = !(ndl != nullptr && ndl[0] == '1');
-    const char* mbc = getenv("BTSBOT_AMD_MLP_BWD_C");
-    const char* nmb = getenv("BTSBOT_AMD_NO_MLP_BWD");
-    h->mlp_bwd_only = nmb != nullptr && nmb[0] == '1' ? -1 : mbc != nullptr ? atoi(mbc) : 0;
-    // (default since its operand images come out of the re-pack's job table: with a dozen launches of their own queued in
-    //  front of the forward's join the kernel LOST 30 us per step; now 2.549-2.560 against 2.565-2.581 ms)
-    const char* ns2m = getenv("BTSBOT_AMD_NO_S2MLP");
-    h->s2mlp = !(ns2m != nullptr && ns2m[0] == '1');
-    const char* fpb = getenv("BTSBOT_AMD_FORK_PER_BLOCK");
-    h->fork_per_block = fpb != nullptr && fpb[0] == '1';
-    const char* nwb = getenv("BTSBOT_AMD_NO_WGRAD_BATCH");
-    h->wgrad_batch = !(nwb != nullptr && nwb[0] == '1');
-    const char* nss = getenv("BTSBOT_AMD_NO_SIDE_STREAM");
-    h->use_side = !(nss != nullptr && nss[0] == '1');
-    // stage 2's training forward through stage2p_kernel's keeping form (ctx.h): on wherever its backward runs the 3x3
-    // kernel that recomputes the depthwise output (dw3ln_bwd_kernel: use_dwln and not BTSBOT_AMD_DW3_OLD)
-    const char* nst = getenv("BTSBOT_AMD_NO_S2P_TRAIN");
-    h->s2p_train = h->stage2p && h->cfg.dims[2] == 256 && h->use_s2p && !h->x2 && !h->fp8 && h->use_dwln && dw3_bwd_active(3, 256) &&
-                   (h->cfg.precision == BTSBOT_BF16 || h->cfg.precision == BTSBOT_F16) && !(nst != nullptr && nst[0] == '1');
-    const char* ns0t = getenv("BTSBOT_AMD_NO_S0_TRAIN");
-    h->s0_train = h->stage0 && h->use_stage0 && !h->x2 && !h->fp8 &&
-                  (h->cfg.precision == BTSBOT_BF16 || h->cfg.precision == BTSBOT_F16) && !(ns0t != nullptr && ns0t[0] == '1');
-    // stage 1 likewise -- by default in the f16 mode only.  In bf16 it is worth 45 us of a 2.6 ms step and holds every
-    // gradient bound, but the 50-step trajectory test (loss curve against the fp32 recipe, bounds = 2 x what the per-op
-    // forward measured) then uses 0.40 / 0.98 / 1.02 of its band in three runs (stage 0 alone: 0.66-0.72; the parameter
-    // drift stays 3.3-3.8 % either way): BTSBOT_AMD_S1_TRAIN=1 opts in.
-    const char* ns1t = getenv("BTSBOT_AMD_NO_S1_TRAIN");
-    const char* ys1t = getenv("BTSBOT_AMD_S1_TRAIN");
-    h->s1_train = h->stage1 && h->use_stage1 && !h->x2 && !h->fp8 &&
-                  (h->cfg.precision == BTSBOT_F16 || (h->cfg.precision == BTSBOT_BF16 && ys1t != nullptr && ys1t[0] == '1')) &&
-                  !(ns1t != nullptr && ns1t[0] == '1');
-    const char* ns16 = getenv("BTSBOT_AMD_NO_STEM16");
-    h->use_stem16 = !(ns16 != nullptr && ns16[0] == '1');
-    const char* det = getenv("BTSBOT_AMD_DETERMINISTIC");
-    // (the deterministic reductions cover the ConvNeXt training step only: same rule as btsbot_set_option)
-    h->deterministic = det != nullptr && det[0] == '1' && !h->is_maxvit;
-  }
+  h->use_head16 = !env_on("BTSBOT_AMD_NO_HEAD16");
+  h->s0_diag = env_int("BTSBOT_AMD_S0_DIAG", 0);
+  h->s2p_diag = env_int("BTSBOT_AMD_S2P_DIAG", 0);
+  h->use_s3 = !env_on("BTSBOT_AMD_NO_S3");
+  h->use_dwln = !env_on("BTSBOT_AMD_NO_DWLN");
+  h->mlp_bwd_only = env_on("BTSBOT_AMD_NO_MLP_BWD") ? -1 : env_int("BTSBOT_AMD_MLP_BWD_C", 0);
+  // (default since its operand images come out of the re-pack's job table: with a dozen launches of their own queued in
+  //  front of the forward's join the kernel LOST 30 us per step; now 2.549-2.560 against 2.565-2.581 ms)
+  h->s2mlp = !env_on("BTSBOT_AMD_NO_S2MLP");
+  h->fork_per_block = env_on("BTSBOT_AMD_FORK_PER_BLOCK");
+  h->wgrad_batch = !env_on("BTSBOT_AMD_NO_WGRAD_BATCH");
+  h->use_side = !env_on("BTSBOT_AMD_NO_SIDE_STREAM");
+  // stage 2's training forward through stage2p_kernel's keeping form (ctx.h): on wherever its backward runs the 3x3
+  // kernel that recomputes the depthwise output (dw3ln_bwd_kernel: use_dwln and not BTSBOT_AMD_DW3_OLD)
+  h->s2p_train = h->stage2p && h->cfg.dims[2] == 256 && h->use_s2p && !h->x2 && !h->fp8 && h->use_dwln && dw3_bwd_active(3, 256) &&
+                 (h->cfg.precision == BTSBOT_BF16 || h->cfg.precision == BTSBOT_F16) && !env_on("BTSBOT_AMD_NO_S2P_TRAIN");
+  h->s0_train = h->stage0 && h->use_stage0 && !h->x2 && !h->fp8 &&
+                (h->cfg.precision == BTSBOT_BF16 || h->cfg.precision == BTSBOT_F16) && !env_on("BTSBOT_AMD_NO_S0_TRAIN");
+  // stage 1 likewise -- by default in the f16 mode only.  In bf16 it is worth 45 us of a 2.6 ms step and holds every
+  // gradient bound, but the 50-step trajectory test (loss curve against the fp32 recipe, bounds = 2 x what the per-op
+  // forward measured) then uses 0.40 / 0.98 / 1.02 of its band in three runs (stage 0 alone: 0.66-0.72; the parameter
+  // drift stays 3.3-3.8 % either way): BTSBOT_AMD_S1_TRAIN=1 opts in.
+  h->s1_train = h->stage1 && h->use_stage1 && !h->x2 && !h->fp8 &&
+                (h->cfg.precision == BTSBOT_F16 || (h->cfg.precision == BTSBOT_BF16 && env_on("BTSBOT_AMD_S1_TRAIN"))) &&
+                !env_on("BTSBOT_AMD_NO_S1_TRAIN");
+  h->use_stem16 = !env_on("BTSBOT_AMD_NO_STEM16");
+  // (the deterministic reductions cover the ConvNeXt training step only: same rule as btsbot_set_option)
+  h->deterministic = env_on("BTSBOT_AMD_DETERMINISTIC") && !h->is_maxvit;
   *out = h;
   return BTSBOT_OK;
 }
@@ -493,10 +471,7 @@ static int pack_impl(btsbot_handle h, const float* master, void* stream, bool tr
   // The plain element maps (casts, transposes, the downsample re-orderings) run as ONE launch over a job
   // table built on the first pack of each kind: mirror and extra never move, so the table is static.
   // BTSBOT_AMD_PACK_UNBATCHED=1 keeps one launch per operand (A/B and parity).
-  static const bool unbatched = [] {
-    const char* e = getenv("BTSBOT_AMD_PACK_UNBATCHED");
-    return e != nullptr && e[0] == '1';
-  }();
+  static const bool unbatched = env_on("BTSBOT_AMD_PACK_UNBATCHED");
   const int kind = train_only ? 1 : 0;
   std::vector<PackJob> jobs, jobs_early;
   const bool build = !unbatched && h->pack_jobs[kind] == nullptr;
@@ -886,6 +861,11 @@ template <typename F> static int timed(btsbot_ctx* h, int cat, hipStream_t st, F
   return BTSBOT_OK;
 }
 
+// a stage kernel's per-workgroup wall-clock region: nullptr without a stamp buffer or when `grid` workgroups do not fit
+static unsigned long long* stamp_wgt(const btsbot_ctx* h, size_t off, int max_wg, int grid) {
+  return h->stamps != nullptr && grid <= max_wg ? h->stamps + off : nullptr;
+}
+
 // image branch of one chunk; *feat_out = [nb][dims[3]] fp32 features inside the workspace
 static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st,
                           float** feat_out) {
@@ -899,44 +879,15 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
   if (h->has_image) {
     const bool s0 = h->stage0 && h->use_stage0;
     if (s0) {
-      Stage0Args a;
-      memset(&a, 0, sizeof(a));
+      Stage0Args a = stage0_args(h, false);
       a.img = img;
-      a.stem_w = h->extra + (h->x2 ? h->p_x2_stem : h->p_stem16);
-      a.stem_w_lo = h->x2 ? h->extra + h->p_x2_stemlo : nullptr;
-      a.stem_b = m + h->stem_b;
-      a.stem_lnw = m + h->stem_lnw;
-      a.stem_lnb = m + h->stem_lnb;
-      for (int j = 0; j < 2; ++j) {
-        const BlockPk& b = h->blocks[0][j];
-        a.blk[j].dw_w = reinterpret_cast<const float*>(h->extra + b.p_dw);
-        a.blk[j].dw_b = m + b.dw_b;
-        a.blk[j].ln_w = m + b.ln_w;
-        a.blk[j].ln_b = m + b.ln_b;
-        a.blk[j].b1 = m + b.fc1_b;
-        a.blk[j].b2 = m + b.fc2_b;
-        a.blk[j].gamma = m + b.gamma;
-        a.blk[j].w1 = h->extra + (h->x2 ? b.p_x2_w1 : b.p_fc1);
-        a.blk[j].w2g = h->extra + (h->x2 ? b.p_x2_w2g : b.p_fc2g);
-        a.blk[j].w1_lo = h->x2 ? h->extra + b.p_x2_w1lo : nullptr;
-        a.blk[j].w2g_lo = h->x2 ? h->extra + b.p_x2_w2glo : nullptr;
-        a.blk[j].par = h->extra + b.p_s0par;
-      }
-      a.ds_lnw = m + h->down[1].ln_w;
-      a.ds_lnb = m + h->down[1].ln_b;
-      a.ds_w = h->extra + (h->x2 ? h->down[1].p_x2_w : h->down[1].p_w);
-      a.ds_w_lo = h->x2 ? h->extra + h->down[1].p_x2_wlo : nullptr;
-      a.ds_b = m + h->down[1].b;
       a.out = x;
       a.tap_stem = h->debug ? h->taps[0] : nullptr;
       a.tap_stage = h->debug ? h->taps[1] : nullptr;
       a.B = nb;
-      {
-        const char* dg = getenv("BTSBOT_AMD_S0_DIAG");
-        a.diag = dg != nullptr ? atoi(dg) : 0;
-      }
-      a.stamps = h->stamps;
-      a.wgt = h->stamps ? h->stamps + 32 : nullptr;
+      a.diag = h->s0_diag;
+      a.stamps = h->stamps ? h->stamps + STAMP_S0 : nullptr;
+      a.wgt = stamp_wgt(h, STAMP_S0_WG, STAMP_S0_MAX_WG, nb);
       TRY(timed(h, CAT_STAGE0, st, [&] {
         return launch_stage0b(h->prec_s01(), a, st);
       }));
@@ -972,38 +923,15 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
       }
       down_done = false;
       if (i == 1 && s1) {
-        Stage1Args a;
-        memset(&a, 0, sizeof(a));
+        Stage1Args a = stage1_args(h, false);
         a.x_in = x;
-        for (int j = 0; j < 2; ++j) {
-          const BlockPk& b = h->blocks[1][j];
-          a.blk[j].dw_w = reinterpret_cast<const float*>(h->extra + b.p_dw);
-          a.blk[j].dw_b = m + b.dw_b;
-          a.blk[j].ln_w = m + b.ln_w;
-          a.blk[j].ln_b = m + b.ln_b;
-            a.blk[j].b1 = m + b.fc1_b;
-          a.blk[j].b2 = m + b.fc2_b;
-          a.blk[j].gamma = m + b.gamma;
-          a.blk[j].w1 = h->extra + (h->x2 ? b.p_x2_w1 : b.p_fc1);
-          a.blk[j].w2g = h->extra + (h->x2 ? b.p_x2_w2g : b.p_fc2g);
-          a.blk[j].w1_lo = h->x2 ? h->extra + b.p_x2_w1lo : nullptr;
-          a.blk[j].w2g_lo = h->x2 ? h->extra + b.p_x2_w2glo : nullptr;
-          a.blk[j].par = h->extra + b.p_s0par;
-        }
-        a.ds_lnw = m + h->down[2].ln_w;
-        a.ds_lnb = m + h->down[2].ln_b;
-        a.ds_w = h->extra + h->down[2].p_wp;
-        a.ds_b = m + h->down[2].b;
         a.out = x2;
         a.scratch = x2 + (((size_t)nb * 9 * c.dims[2] + 63) / 64) * 64;   // behind the output rows (x2 holds 225 * 64 floats per alert)
         a.tap_stage = h->debug ? h->taps[2] : nullptr;
         a.B = nb;
-        {
-          const char* dg = getenv("BTSBOT_AMD_S0_DIAG");
-          a.diag = dg != nullptr ? atoi(dg) : 0;
-        }
-        a.stamps = h->stamps ? h->stamps + 16 : nullptr;
-        a.wgt = h->stamps ? h->stamps + 32 + 2 * 4096 : nullptr;
+        a.diag = h->s0_diag;
+        a.stamps = h->stamps ? h->stamps + STAMP_S1 : nullptr;
+        a.wgt = stamp_wgt(h, STAMP_S1_WG, STAMP_S1_MAX_WG, (nb + 1) / 2);
         TRY(timed(h, CAT_STAGE1, st, [&] {
           return launch_stage1b(h->prec_s01(), a, st);
         }));
@@ -1015,37 +943,13 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
       }
       if (i == 2 && h->stage2p && h->use_s2p) {
         // every block of the 3x3 stage and the last downsample in one launch: x [nb][9][256] -> x2 [nb][512]
-        Stage2pArgs a;
-        memset(&a, 0, sizeof(a));
+        Stage2pArgs a = stage2p_args(h, false);
         a.x_in = x;
-        a.depth = (int)h->blocks[2].size();
-        for (int j = 0; j < a.depth; ++j) {
-          const BlockPk& b = h->blocks[2][j];
-          a.blk[j].dw_w = reinterpret_cast<const float*>(h->extra + b.p_dw);
-          a.blk[j].dw_b = m + b.dw_b;
-          a.blk[j].ln_w = m + b.ln_w;
-          a.blk[j].ln_b = m + b.ln_b;
-          a.blk[j].b1 = m + b.fc1_b;
-          a.blk[j].b2 = m + b.fc2_b;
-          a.blk[j].gamma = m + b.gamma;
-          a.blk[j].w1p = h->extra + b.p_w1p;
-          a.blk[j].w2p = h->extra + b.p_w2p;
-          a.blk[j].scales = h->fp8 ? reinterpret_cast<const float*>(h->extra + b.p_scales) : nullptr;
-        }
-        a.ds_lnw = m + h->down[3].ln_w;
-        a.ds_lnb = m + h->down[3].ln_b;
-        a.ds_wp = h->extra + h->down[3].p_wp;
-        a.ds_b = m + h->down[3].b;
         a.out = x2;
         a.tap_stage = h->debug ? h->taps[3] : nullptr;
         a.B = nb;
-        a.cw = c.dims[2];
-        a.alerts_hint = h->s2p_alerts_hint;
-        {
-          const char* dg = getenv("BTSBOT_AMD_S2P_DIAG");
-          a.diag = dg != nullptr ? atoi(dg) : 0;
-        }
-        a.stamps = h->stamps ? h->stamps + 32 + 16384 : nullptr;
+        a.diag = h->s2p_diag;
+        a.stamps = h->stamps ? h->stamps + STAMP_S2 : nullptr;
         TRY(timed(h, CAT_STAGE2, st, [&] { return launch_stage2p(h->prec_tail(), a, st); }));
         float* t = x;
         x = x2;
@@ -1055,26 +959,11 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
       }
       if (i == 3 && hw == 1 && h->stage3 && h->use_s3) {
         // the 1x1 stage: two launches per block, x updated in place
-        Stage3Args a;
-        memset(&a, 0, sizeof(a));
+        Stage3Args a = stage3_args(h);
         a.x = x;
-        a.depth = (int)h->blocks[3].size();
-        for (int j = 0; j < a.depth; ++j) {
-          const BlockPk& b = h->blocks[3][j];
-          a.blk[j].dw_c = reinterpret_cast<const float*>(h->extra + b.p_dw) + 24 * ch;   // tap-major [49][C]: the centre row
-          a.blk[j].dw_b = m + b.dw_b;
-          a.blk[j].ln_w = m + b.ln_w;
-          a.blk[j].ln_b = m + b.ln_b;
-          a.blk[j].w1p = h->extra + b.p_w1p;
-          a.blk[j].b1 = m + b.fc1_b;
-          a.blk[j].w2p = h->extra + b.p_w2p;
-          a.blk[j].b2 = m + b.fc2_b;
-          a.blk[j].gamma = m + b.gamma;
-          a.blk[j].scales = h->fp8 ? reinterpret_cast<const float*>(h->extra + b.p_scales) : nullptr;
-        }
         a.hfrag = hb;
         a.B = nb;
-        a.stamps = h->stamps ? h->stamps + 32 + 16384 + 64 : nullptr;
+        a.stamps = h->stamps ? h->stamps + STAMP_S3 : nullptr;
         for (int j = 0; j < a.depth; ++j) {
           TRY(timed(h, CAT_S3FC1, st, [&] { return launch_stage3(h->prec_tail(), ch, a, j, 0, st); }));
           TRY(timed(h, CAT_S3FC2, st, [&] { return launch_stage3(h->prec_tail(), ch, a, j, 1, st); }));
@@ -1142,7 +1031,7 @@ static int forward_chunk(btsbot_ctx* h, const float* img, const float* meta, flo
     g.logits = logits;
     g.scores = scores;
     g.B = nb;
-    g.stamps = h->stamps ? h->stamps + 32 + 16384 + 64 + 1500 : nullptr;
+    g.stamps = h->stamps ? h->stamps + STAMP_HEAD16 : nullptr;
     TRY(timed(h, CAT_HEAD16, st, [&] { return launch_head16(h->prec_head(), g, st); }));
     h->last_chunk = nb;
     return BTSBOT_OK;
@@ -1177,10 +1066,7 @@ static int forward_chunk(btsbot_ctx* h, const float* img, const float* meta, flo
   a.logits = logits;
   a.scores = scores;
   a.B = nb;
-  {
-    const char* dg = getenv("BTSBOT_AMD_HEAD_DIAG");
-    a.diag = dg != nullptr ? atoi(dg) : 0;
-  }
+  a.diag = env_int("BTSBOT_AMD_HEAD_DIAG", 0);
   TRY(timed(h, CAT_HEAD, st, [&] { return launch_head(a, st); }));
   h->last_chunk = nb;
   return BTSBOT_OK;
@@ -1346,10 +1232,7 @@ extern "C" int btsbot_forward_train(btsbot_handle h, const float* triplets, cons
       // the metadata branch reads nothing of the image branch: its three launches go to the side stream (behind the
       // re-pack queued there) and run beside the backbone instead of in the chain behind it
       hipStream_t sd = st;
-      static const bool meta_inline = [] {
-        const char* e = getenv("BTSBOT_AMD_NO_META_SIDE");   // 1: the metadata branch in the chain, behind the backbone (A/B)
-        return e != nullptr && e[0] == '1';
-      }();
+      static const bool meta_inline = env_on("BTSBOT_AMD_NO_META_SIDE");   // 1: the metadata branch in the chain, behind the backbone (A/B)
       if (h->has_meta && h->side != nullptr && !meta_inline) {
         TRY(side_fork(h, st, &sd));
         TRY(head_train_meta_forward(h, h->tcache, meta, batch, meta_mask, master_arena, sd));
@@ -1525,7 +1408,8 @@ int time_candidate(hipStream_t cand, hipEvent_t ev, const hipStream_t* busy, int
 int pick_apart_stream(btsbot_ctx* h, const hipStream_t* busy, int nbusy, const char* role, hipStream_t* out, bool* apart_out) {
   StreamPile pile;
   HIP_TRY(hipEventCreateWithFlags(&pile.ev, hipEventDisableTiming));
-  const bool debug = getenv("BTSBOT_AMD_DEBUG_SIDE") != nullptr;
+  // (presence-only switch, any value: the two defaults agree only when the variable is set)
+  const bool debug = env_int("BTSBOT_AMD_DEBUG_SIDE", 0) == env_int("BTSBOT_AMD_DEBUG_SIDE", 1);
   hipStream_t chosen = nullptr;
   bool apart = false;
   for (int attempt = 0; attempt < 8 && chosen == nullptr; ++attempt) {

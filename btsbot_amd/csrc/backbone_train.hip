@@ -147,6 +147,12 @@ BBCache carve_bb(const btsbot_ctx* h, unsigned char* base, int B) {
   return k;
 }
 
+// the training forward of a batch of B alerts runs stage 2 through stage2p_kernel's keeping form, which does not keep the
+// blocks' depthwise outputs (BlkBuf::d).  Up to two rounds of one workgroup (5 alerts) per CU: 2.50 against 2.57 ms per
+// 1024-alert step; at 4096 alerts the per-op GEMMs (36 864 rows: full tiles, full rounds) are as fast or faster (7.95
+// against 8.00 ms), so large batches keep them
+bool s2_kept(const btsbot_ctx* h, int B) { return h->s2p_train && B <= 2560; }
+
 #define TRYB(call)                  \
   do {                              \
     int _s = (call);                \
@@ -175,32 +181,12 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
     // backward reads of them is written on its way (stage0.h).  It needs this step's operand images at once: the
     // re-pack queued behind the previous optimiser step runs under the mask draws and whatever precedes this call
     TRYB(pack_sync_early(h, st));
-    Stage0Args a;
-    memset(&a, 0, sizeof(a));
+    Stage0Args a = stage0_args(h, true);
     a.img = img;
-    a.stem_w = h->extra + h->p_stem16;
-    a.stem_b = m + h->stem_b;
-    a.stem_lnw = m + h->stem_lnw;
-    a.stem_lnb = m + h->stem_lnb;
     for (int j = 0; j < 2; ++j) {
-      const BlockPk& b = h->blocks[0][j];
-      a.blk[j].dw_w = reinterpret_cast<const float*>(h->extra + b.p_dw);
-      a.blk[j].dw_b = m + b.dw_b;
-      a.blk[j].ln_w = m + b.ln_w;
-      a.blk[j].ln_b = m + b.ln_b;
-      a.blk[j].b1 = m + b.fc1_b;
-      a.blk[j].b2 = m + b.fc2_b;
-      a.blk[j].gamma = m + b.gamma;
-      a.blk[j].w1 = h->extra + b.p_fc1;
-      a.blk[j].w2g = h->extra + b.p_fc2g;
-      a.blk[j].par = h->extra + b.p_s0par_t;
       a.keep_d[j] = k.blk[0][j].d;
       a.keep_xn[j] = k.blk[0][j].xn;
     }
-    a.ds_lnw = m + h->down[1].ln_w;
-    a.ds_lnb = m + h->down[1].ln_b;
-    a.ds_w = h->extra + h->down[1].p_w;
-    a.ds_b = m + h->down[1].b;
     a.out = stage_in(1);
     a.keep_stem_pre = k.stem_pre;
     a.tap_stem = k.blk[0][0].xin;
@@ -217,10 +203,7 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
                      B, c.dims[0], st, k.stem_pre));
   TRYB(pack_sync(h, st));   // the operand images of this step (packed on the side stream while the stem ran)
   const bool s1t = h->s1_train && h->blocks[1].size() == 2 && h->mlp_fused(c.dims[1]) && h->use_dwln;
-  // stage 2 through stage2p_kernel's keeping form up to two rounds of one workgroup (5 alerts) per CU: 2.50 against 2.57 ms
-  // per 1024-alert step; at 4096 alerts the per-op GEMMs (36 864 rows: full tiles, full rounds) are as fast or faster
-  // (7.95 against 8.00 ms), so large batches keep them
-  const bool s2t = h->s2p_train && B <= 2560;
+  const bool s2t = s2_kept(h, B);
   for (int i = s0t ? 1 : 0; i < 4; ++i) {
     const int ch = c.dims[i], hw = STAGE_HW[i], rows = B * hw * hw;
     if (i > 0 && !(i == 3 && s2t) && !(i == 1 && s0t) && !(i == 2 && s1t)) {
@@ -234,28 +217,12 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
     if (i == 1 && s1t) {
       // stage 1 + the second downsample as one launch of stage1b's keeping form: block 0's input is its x_in, block 1's
       // input the residual copy the kernel parks between the blocks anyway
-      Stage1Args a;
-      memset(&a, 0, sizeof(a));
+      Stage1Args a = stage1_args(h, true);
       a.x_in = stage_in(1);
       for (int j = 0; j < 2; ++j) {
-        const BlockPk& b = h->blocks[1][j];
-        a.blk[j].dw_w = reinterpret_cast<const float*>(h->extra + b.p_dw);
-        a.blk[j].dw_b = m + b.dw_b;
-        a.blk[j].ln_w = m + b.ln_w;
-        a.blk[j].ln_b = m + b.ln_b;
-        a.blk[j].b1 = m + b.fc1_b;
-        a.blk[j].b2 = m + b.fc2_b;
-        a.blk[j].gamma = m + b.gamma;
-        a.blk[j].w1 = h->extra + b.p_fc1;
-        a.blk[j].w2g = h->extra + b.p_fc2g;
-        a.blk[j].par = h->extra + b.p_s0par_t;
         a.keep_d[j] = k.blk[1][j].d;
         a.keep_xn[j] = k.blk[1][j].xn;
       }
-      a.ds_lnw = m + h->down[2].ln_w;
-      a.ds_lnb = m + h->down[2].ln_b;
-      a.ds_w = h->extra + h->down[2].p_wp;
-      a.ds_b = m + h->down[2].b;
       a.out = stage_in(2);
       a.scratch = k.blk[1][1].xin;
       a.tap_stage = k.xs[1];
@@ -270,39 +237,21 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
       // the downsample's patch rows -- on its way.  Replaces 6 x (dw3_ln + two GEMMs) + ln_patch + GEMM.  The depthwise
       // output is not kept: dw3ln_bwd_kernel recomputes it (block 0's buffer for it takes the copy of the stage input the
       // kernel writes for every block alike).
-      Stage2pArgs a;
-      memset(&a, 0, sizeof(a));
-      a.cw = c.dims[2];
+      Stage2pArgs a = stage2p_args(h, true);
       a.x_in = stage_in(2);
-      a.depth = (int)nblk;
       for (size_t j = 0; j < nblk; ++j) {
-        const BlockPk& b = h->blocks[2][j];
         const BlkBuf& sb = k.blk[2][j];
-        a.blk[j].dw_w = reinterpret_cast<const float*>(h->extra + b.p_dw);
-        a.blk[j].dw_b = m + b.dw_b;
-        a.blk[j].ln_w = m + b.ln_w;
-        a.blk[j].ln_b = m + b.ln_b;
-        a.blk[j].b1 = m + b.fc1_b;
-        a.blk[j].b2 = m + b.fc2_b;
-        a.blk[j].gamma = m + b.gamma;
-        a.blk[j].w1p = h->extra + b.p_w1p;
-        a.blk[j].w2p = h->extra + b.p_w2p;
         a.keep[j].xin = j == 0 ? sb.d : sb.xin;
         a.keep[j].xn = sb.xn;
         a.keep[j].a = sb.a;
         a.keep[j].hh = sb.h;
       }
-      a.ds_lnw = m + h->down[3].ln_w;
-      a.ds_lnb = m + h->down[3].ln_b;
-      a.ds_wp = h->extra + h->down[3].p_wp;
-      a.ds_b = m + h->down[3].b;
       a.out = stage_in(3);
       a.tap_stage = k.xs[2];
       a.ds_patches = k.patches[3];
       a.B = B;
       a.train = 1;
-      a.alerts_hint = h->s2p_alerts_hint;
-      a.stamps = h->stamps ? h->stamps + 32 + 16384 : nullptr;   // (tools/stamps_train.py)
+      a.stamps = h->stamps ? h->stamps + STAMP_S2 : nullptr;   // (tools/stamps_train.py)
       TRYB(launch_stage2p(c.precision, a, st));
       continue;
     }
@@ -356,6 +305,7 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
   const float* m = h->mirror;
   const int prec = c.precision;
   BBCache k = carve_bb(h, h->bbcache, B);
+  const bool s2t = s2_kept(h, B);
   float* dy = k.dyA;
   float* dxn = k.dyB;
   TRYB(launch_copy_f32(dy, dfeat, (size_t)B * c.dims[3], st));
@@ -436,6 +386,12 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
         btsbot_set_error("backward: the fused MLP backward of a %d-channel block needs dwln_bwd_kernel behind it", ch);
         return BTSBOT_ERR_STATE;
       }
+      // (3x3 maps: dw3ln_bwd_kernel recomputes the depthwise output; every other branch reads the one the forward kept)
+      const bool dw3 = s.dwpart != nullptr && adjacent && dw3_bwd_active(hw, ch);
+      if (i == 2 && s2t && !dw3) {
+        btsbot_set_error("backward: stage 2's keeping-form forward kept no depthwise output, but block %d's backward reads it", j);
+        return BTSBOT_ERR_STATE;
+      }
       if (s.fpart != nullptr) {
         // ---- da, dxn = da W1 and both filter gradients of the MLP in one launch (a recomputed from xn; da, g only on chip)
         TRYB(launch_mlp_bwd(prec, ch, s.xn, s.dyT, h->extra + b.p_fc1, h->extra + b.p_fc2t, m + b.fc1_b, dxn, s.fpart,
@@ -458,7 +414,7 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
       }
       void* nxt = fold_cast ? next_dyT(i, j) : nullptr;
       // (the partial rows follow the arena's layout of conv_dw.weight | conv_dw.bias | norm.weight | norm.bias)
-      if (s.dwpart != nullptr && adjacent && dw3_bwd_active(hw, ch)) {
+      if (dw3) {
         // ---- 3x3 maps: the same in their own kernel (d recomputed from x_in; compact rows, reduced by launch_dw3_rows)
         TRYB(launch_dw3ln_bwd(m + b.dw_b, dxn, m + b.ln_w, s.xin, wdw, dy, nxt, prec, s.dwpart, B, st, planes,
                               (size_t)rows * ch));

@@ -766,10 +766,7 @@ int wgrad_f32(const void* Dv, const void* Av, float* out, int M, int N, int K, i
   const float* D = reinterpret_cast<const float*>(Dv);
   const float* A = reinterpret_cast<const float*>(Av);
   if (cs_done != nullptr) *cs_done = false;
-  static const bool old_form = [] {   // BTSBOT_AMD_WGRAD_F32_OLD=1: the 64 x 64 kernel for every shape (A/B timing, parity)
-    const char* e = getenv("BTSBOT_AMD_WGRAD_F32_OLD");
-    return e != nullptr && e[0] == '1';
-  }();
+  static const bool old_form = env_on("BTSBOT_AMD_WGRAD_F32_OLD");   // 1: the 64 x 64 kernel for every shape (A/B timing, parity)
   const bool aligned = ((reinterpret_cast<uintptr_t>(D) | reinterpret_cast<uintptr_t>(A)) & 15) == 0;
   if (!old_form && aligned && N % 64 == 0 && K % 64 == 0) {
     // (deterministic mode: the column sums keep their own launch with its fixed-order reduction)
@@ -1105,8 +1102,8 @@ int launch_ln_bwd(const float* d, const float* dxn, const float* g, float* dd, f
                   float* dbeta, long rows, int C, hipStream_t st, void* out16, int prec16, int patch_hw) {
   if (rows <= 0) return BTSBOT_OK;
   static const long cap = [] {
-    const char* e = getenv("BTSBOT_AMD_LNBWD_BLOCKS");   // tuning knob: workgroups (= same-address atomics per channel;
-    const long v = e ? atol(e) : 0;                      //  measured per step: 256 4.64 ms, 384/512 4.58, 1024 4.70, 2048 5.02)
+    const long v = env_int("BTSBOT_AMD_LNBWD_BLOCKS", 0);   // tuning knob: workgroups (= same-address atomics per channel;
+                                                            //  measured per step: 256 4.64 ms, 384/512 4.58, 1024 4.70, 2048 5.02)
     return v >= 1 ? v : 512;
   }();
   long blocks = (rows + 3) / 4;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/btsbot_hip.h"
 
@@ -62,6 +63,17 @@ struct DevOnce {
   bool need() const { return ((mask.load(std::memory_order_relaxed) >> dev()) & 1ULL) == 0; }
   void done() { mask.fetch_or(1ULL << dev(), std::memory_order_relaxed); }
 };
+
+// Developer switches (BTSBOT_AMD_*): on when the variable is set and its value starts with '1'; integer knobs read
+// atoi(value), `dflt` when the variable is not set (each caller keeps its own range check)
+inline bool env_on(const char* name) {
+  const char* e = getenv(name);
+  return e != nullptr && e[0] == '1';
+}
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e != nullptr ? atoi(e) : dflt;
+}
 
 // ---------------------------------------------------------------------------------------
 // error plumbing (no exception crosses the ABI)

@@ -50,6 +50,32 @@ const char* const CAT_NAMES[NCAT] = {"stem_kernel",       "dwconv_ln_kernel", "g
                                      "mv_se_kernel", "mv_ln_kernel", "mv_attn_kernel", "mv_streamed_mlp", "mv_partition"};
 constexpr size_t PROF_MAX_LAUNCHES = 16384;
 
+// Regions of the developer timestamp buffer (btsbot_debug_stamps; include/btsbot_hip.h lists them): offsets and sizes in
+// uint64 entries.  Phase clocks come from one workgroup of a launch; a per-workgroup region holds [grid][2] start / end
+// wall clocks and is passed only when the launch's grid fits (stamp_wgt in api.hip).
+constexpr size_t STAMP_TOTAL = 32 + 16384 + 64 + 2048;       // 18528
+constexpr size_t STAMP_S0 = 0, STAMP_S0_N = 16;               // stage 0 phases (stage0b.hip)
+constexpr size_t STAMP_S1 = 16, STAMP_S1_N = 16;              // stage 1 phases (stage1b.hip)
+constexpr size_t STAMP_S0_WG = 32, STAMP_S0_WG_N = 8192;      // stage 0 per workgroup: 4096 workgroups of one alert
+constexpr size_t STAMP_S1_WG = 8224, STAMP_S1_WG_N = 8192;    // stage 1 per workgroup in [0, 4096): 2048 workgroups of two
+                                                              // alerts; its loop clocks at [4096, 4112) (stage1b.hip)
+constexpr int STAMP_S0_MAX_WG = 4096, STAMP_S1_MAX_WG = 2048;
+constexpr size_t STAMP_S2 = 16416, STAMP_S2_N = 64;           // stage 2 phases (stage2p.hip)
+constexpr size_t STAMP_S3 = 16480, STAMP_S3_N = 16;           // stage 3 phases (stage3.hip)
+constexpr size_t STAMP_HEAD16 = 17980, STAMP_HEAD16_N = 16;   // head16.hip
+constexpr size_t STAMP_MV_PART = 32, STAMP_MV_PART_N = 64;    // MaxViT handles: mv_part_kernel, 32 for C = 256, then 32
+                                                              // for C = 128; over stage 0's per-workgroup region, which
+                                                              // only ConvNeXt handles write
+constexpr bool stamp_fits(size_t off, size_t n) { return off + n <= STAMP_TOTAL; }
+static_assert(stamp_fits(STAMP_S0, STAMP_S0_N) && stamp_fits(STAMP_S1, STAMP_S1_N) &&
+                  stamp_fits(STAMP_S0_WG, STAMP_S0_WG_N) && stamp_fits(STAMP_S1_WG, STAMP_S1_WG_N) &&
+                  stamp_fits(STAMP_S2, STAMP_S2_N) && stamp_fits(STAMP_S3, STAMP_S3_N) &&
+                  stamp_fits(STAMP_HEAD16, STAMP_HEAD16_N) && stamp_fits(STAMP_MV_PART, STAMP_MV_PART_N),
+              "a stamp region runs past the documented buffer");
+static_assert(2 * STAMP_S0_MAX_WG <= STAMP_S0_WG_N && 2 * STAMP_S1_MAX_WG <= 4096 &&
+                  STAMP_MV_PART + STAMP_MV_PART_N <= STAMP_S0_WG + STAMP_S0_WG_N,
+              "a stamp region does not hold what is written into it");
+
 struct MaxVit;   // maxvit.hip
 struct SidePick {
   hipStream_t caller, side;
@@ -198,7 +224,8 @@ struct btsbot_ctx {
                            // BTSBOT_AMD_NO_WGRAD_BATCH=1: one launch per GEMM behind each block (A/B timing, parity tests)
   bool use_side = true;    // BTSBOT_AMD_NO_SIDE_STREAM=1: the whole backward on the caller's stream (A/B timing)
 
-  unsigned long long* stamps = nullptr;   // 32 phase timestamps: [0..15] stage 0, [16..31] stage 1
+  unsigned long long* stamps = nullptr;   // btsbot_debug_stamps: STAMP_TOTAL entries, regions STAMP_* above
+  int s0_diag = 0, s2p_diag = 0;          // BTSBOT_AMD_S0_DIAG / _S2P_DIAG: Stage0Args::diag / Stage2pArgs::diag of inference
   bool debug = false;
   float* taps[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   int last_chunk = 0;
@@ -216,3 +243,15 @@ int side_join(btsbot_ctx* h, hipStream_t st);
 
 int pack_sync(btsbot_ctx* h, hipStream_t st);   // api.hip
 int pack_sync_early(btsbot_ctx* h, hipStream_t st);   // api.hip: only what stage0b_kernel reads (else = pack_sync)
+
+// stage_args.hip: the argument blocks of the ConvNeXt stage kernels with every parameter pointer the handle holds
+// filled in, everything else zero.  keep: the keeping form of the training forward (bf16 / f16: stage-0 / stage-1
+// parameter images with f16 taps, no split-mode remainder planes, no fp8 scales).
+struct Stage0Args;
+struct Stage1Args;
+struct Stage2pArgs;
+struct Stage3Args;
+Stage0Args stage0_args(const btsbot_ctx* h, bool keep);
+Stage1Args stage1_args(const btsbot_ctx* h, bool keep);
+Stage2pArgs stage2p_args(const btsbot_ctx* h, bool keep);
+Stage3Args stage3_args(const btsbot_ctx* h);

@@ -116,28 +116,16 @@ int maxvit_build_tables(btsbot_ctx* h, size_t* extra_cursor) {
   const int esz = h->esz();
   MaxVit* mv = new MaxVit();
   h->mv = mv;
-  {
-    const char* e = getenv("BTSBOT_AMD_MV_ATTN_VALU");
-    mv->attn_valu = e != nullptr && e[0] == '1';
-    const char* d = getenv("BTSBOT_AMD_MV_DW_PLAIN");
-    mv->dw_plain = d != nullptr && d[0] == '1';
-    const char* s2 = getenv("BTSBOT_AMD_MV_STEM_IM2COL");
-    mv->stem_im2col = s2 != nullptr && s2[0] == '1';
-    const char* gg = getenv("BTSBOT_AMD_MV_GATED_GEMM");
-    mv->gated_gemm = gg != nullptr && gg[0] == '1';
-    const char* nf = getenv("BTSBOT_AMD_MV_NO_FRONT");
-    mv->no_front = nf != nullptr && nf[0] == '1';
-    const char* lf = getenv("BTSBOT_AMD_MV_NO_LN_FUSE");
-    mv->no_ln_fuse = lf != nullptr && lf[0] == '1';
-    const char* ab = getenv("BTSBOT_AMD_MV_NO_ATTN_BLOCK");
-    mv->no_attn_block = ab != nullptr && ab[0] == '1';
-    const char* u = getenv("BTSBOT_AMD_MV_MLP_UNFUSED");
-    mv->mlp_unfused = u != nullptr && u[0] == '1';
-    const char* na = getenv("BTSBOT_AMD_MV_NO_PART");
-    mv->no_part = na != nullptr && na[0] == '1';
-    const char* ns = getenv("BTSBOT_AMD_MV_NO_SMLP");
-    mv->no_smlp = ns != nullptr && ns[0] == '1';
-  }
+  mv->attn_valu = env_on("BTSBOT_AMD_MV_ATTN_VALU");
+  mv->dw_plain = env_on("BTSBOT_AMD_MV_DW_PLAIN");
+  mv->stem_im2col = env_on("BTSBOT_AMD_MV_STEM_IM2COL");
+  mv->gated_gemm = env_on("BTSBOT_AMD_MV_GATED_GEMM");
+  mv->no_front = env_on("BTSBOT_AMD_MV_NO_FRONT");
+  mv->no_ln_fuse = env_on("BTSBOT_AMD_MV_NO_LN_FUSE");
+  mv->no_attn_block = env_on("BTSBOT_AMD_MV_NO_ATTN_BLOCK");
+  mv->mlp_unfused = env_on("BTSBOT_AMD_MV_MLP_UNFUSED");
+  mv->no_part = env_on("BTSBOT_AMD_MV_NO_PART");
+  mv->no_smlp = env_on("BTSBOT_AMD_MV_NO_SMLP");
   char buf[96];
   mv->stem1_w = mv_add(h, "stem.conv1.weight", {32, 3, 3, 3});
   mv->stem_bn = add_bn(h, "stem.norm1.", 32, cur);
@@ -522,7 +510,7 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
         pw.wprojp = ex + a.p_projp;
         pw.bproj = m + a.proj_b;
         pw.biasl = F(a.p_biasl);
-        pw.stamps = h->stamps ? h->stamps + 20000 + (c == 256 ? 0 : 32) : nullptr;
+        pw.stamps = h->stamps ? h->stamps + STAMP_MV_PART + (c == 256 ? 0 : 32) : nullptr;
         pw.ln2w = m + a.n2w;
         pw.ln2b = m + a.n2b;
         pw.w1p = ex + a.p_w1p;

@@ -261,11 +261,15 @@ int btsbot_set_option(btsbot_handle h, const char* key, int value);
  * stage outputs (call before btsbot_reserve()). */
 int btsbot_set_debug(btsbot_handle h, int on);
 
-/* Developer aid: when non-NULL, workgroup 0 of the stage megakernels stores the shader clock at its
- * phase boundaries into device_buffer32[0..31] (uint64), and every workgroup its start / end on the
- * 100 MHz wall clock into [32 + 2*wg] (stage 0) and [32 + 8192 + 2*wg] (stage 1), and the stage-2
- * front kernel its phase clocks into [32 + 16384 ..+63] and per-workgroup wall clocks behind them: the
- * buffer holds 32 + 16384 + 64 + 2048 entries and the batch must not exceed 4096 alerts while it is installed. */
+/* Developer aid: when non-NULL, the forward's kernels store clocks into device_buffer32, a device buffer of
+ * 32 + 16384 + 64 + 2048 = 18528 uint64 entries.  Phase clocks (shader clock) come from one workgroup of each
+ * kernel; the per-workgroup regions hold every workgroup's start / end on the 100 MHz wall clock:
+ *     [0, 16)            stage 0 phases                [16, 32)         stage 1 phases
+ *     [32 + 2 wg]        stage 0 per workgroup (one alert each; left out for chunks above 4096 alerts)
+ *     [8224 + 2 wg]      stage 1 per workgroup (two alerts each; likewise), its loop clocks at [12320, 12336)
+ *     [16416, 16480)     stage 2 phases                [16480, 16496)   stage 3 phases
+ *     [17980, 17996)     head16 phases
+ *     [32, 96)           MaxViT handles: the partition kernel's phases, C = 256 then C = 128 (32 each) */
 int btsbot_debug_stamps(btsbot_handle h, unsigned long long* device_buffer32);
 
 /* Debug/validation tap: copy an intermediate of the LAST forward chunk to `dst` (fp32).

@@ -113,6 +113,8 @@ class _HipModel(nn.Module):
         self._reserved = 0
         self._reserved_train = 0
         self._reserved_image = False
+        if getattr(self, "_split_training", False):   # (re-applied: it must precede the new handle's first pack)
+            _lib.check(_lib.lib().btsbot_set_option(self._handle.ptr, b"train_split", 1), "btsbot_set_option(train_split)")
 
     def _build_parameters(self):
         h = self._handle
@@ -207,12 +209,32 @@ class _HipModel(nn.Module):
             raise ValueError(f"unknown precision {precision!r}")
         if _lib.PRECISION[precision] != _lib.PRECISION[self._precision]:
             self._precision = precision
+            self._split_training = False   # (an f16x2-only mode)
             self._new_handle()
         return self
 
     @property
     def precision(self) -> str:
         return self._precision
+
+    def set_split_training(self, on: bool = True):
+        """f16x2 models with a ConvNeXt image branch: run the training step's 1x1 / downsample matrix products (forward,
+        input and filter gradients) on split f16 operands -- three f16 MFMAs per product, gradient operands scaled by a
+        power of two per tensor first -- instead of the exact-fp32 MFMA.  Inference is unchanged.  Re-creates the
+        handle (the option changes its packed-operand layout); set_precision() to another mode clears it."""
+        on = bool(on)
+        if on and (_lib.PRECISION[self._precision] != _lib.PRECISION["f16x2"] or self._table is None
+                   or "maxvit" in self._wiring.lower() or self._wiring == "um_nn"):
+            raise ValueError(f"btsbot_amd: split training needs precision 'f16x2' and a ConvNeXt image branch "
+                             f"(this model: {self._wiring}, {self._precision!r})")
+        if on != getattr(self, "_split_training", False):
+            self._split_training = on
+            self._new_handle()
+        return self
+
+    @property
+    def split_training(self) -> bool:
+        return getattr(self, "_split_training", False)
 
     def mark_weights_dirty(self):
         """Call after modifying parameters through ``.data`` (in-place ops on the parameters

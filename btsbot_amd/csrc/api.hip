@@ -368,6 +368,7 @@ extern "C" int btsbot_destroy(btsbot_handle h) {
   if (h->extra) (void)hipFree(h->extra);
   for (void* t : h->pack_jobs)
     if (t) (void)hipFree(t);
+  if (h->split_jobs) (void)hipFree(h->split_jobs);
   if (h->ws && h->ws_owned) (void)hipFree(h->ws);
   if (h->tcache) (void)hipFree(h->tcache);
   if (h->bbcache) (void)hipFree(h->bbcache);
@@ -639,6 +640,32 @@ static int pack_impl(btsbot_handle h, const float* master, void* stream, bool tr
     TRY(launch_pack_down_split(m + h->down[1].w, h->extra + h->down[1].p_x2_w, h->extra + h->down[1].p_x2_wlo, c.dims[1],
                                c.dims[0], st));
   }
+  if (convnext && h->train_split && h->train_packs) {
+    // split training: the f16 head + remainder planes of the fp32 images packed above (same stream: behind them), one launch
+    if (h->split_jobs == nullptr) {
+      std::vector<SplitJob> sj;
+      auto add = [&](size_t src, size_t dst, long n) {
+        sj.push_back(SplitJob{reinterpret_cast<const float*>(h->extra + src), h->extra + dst, n});
+      };
+      for (int i = 0; i < 4; ++i) {
+        const long ch = c.dims[i];
+        if (i > 0) {
+          add(h->down[i].p_w, h->down[i].p_s_w, ch * c.dims[i - 1] * 4);
+          add(h->down[i].p_wt, h->down[i].p_s_wt, ch * c.dims[i - 1] * 4);
+        }
+        for (const BlockPk& b : h->blocks[i]) {
+          add(b.p_fc1, b.p_s_fc1, 4 * ch * ch);
+          add(b.p_fc2, b.p_s_fc2, 4 * ch * ch);
+          add(b.p_fc1t, b.p_s_fc1t, 4 * ch * ch);
+          add(b.p_fc2t, b.p_s_fc2t, 4 * ch * ch);
+        }
+      }
+      HIP_TRY(hipMalloc(&h->split_jobs, sj.size() * sizeof(SplitJob)));
+      HIP_TRY(hipMemcpy(h->split_jobs, sj.data(), sj.size() * sizeof(SplitJob), hipMemcpyHostToDevice));
+      h->split_njobs = (int)sj.size();
+    }
+    TRY(launch_split_jobs(reinterpret_cast<const SplitJob*>(h->split_jobs), h->split_njobs, st));
+  }
   if (convnext && h->stage1 && (!train_only || h->s1_train))
     TRY(launch_pack_frag32(h->prec_s01(), m + h->down[2].w, h->extra + h->down[2].p_wp, c.dims[2], c.dims[1], st));
   if (convnext && h->stage2p && (!train_only || (h->s2p_train && unbatched)))
@@ -703,6 +730,51 @@ extern "C" int btsbot_set_option(btsbot_handle h, const char* key, int value) {
       return BTSBOT_ERR_STATE;
     }
     h->deterministic = value == 1;
+    return BTSBOT_OK;
+  }
+  if (strcmp(key, "train_split") == 0) {
+    if (value != 0 && value != 1) {
+      btsbot_set_error("set_option: train_split is 0 or 1, got %d", value);
+      return BTSBOT_ERR_INVALID_ARG;
+    }
+    if (!h->x2 || !h->has_image || h->is_maxvit) {
+      btsbot_set_error("set_option: train_split needs a BTSBOT_F16X2 handle with a ConvNeXt image branch (this one: %s)",
+                       !h->x2 ? "another precision" : !h->has_image ? "no image branch" : "a MaxViT image branch");
+      return BTSBOT_ERR_INVALID_ARG;
+    }
+    if (h->mirror != nullptr || h->tcache != nullptr) {
+      btsbot_set_error("set_option: train_split changes the packed-operand layout: set it before the first "
+                       "btsbot_pack_params* / btsbot_reserve_train()");
+      return BTSBOT_ERR_STATE;
+    }
+    if (value == 1 && h->blocks[0][0].p_s_fc1 == 0) {   // the split planes' slots, behind everything else in `extra`
+      size_t cur = h->extra_bytes;
+      for (int i = 0; i < 4; ++i) {
+        const size_t ch = h->cfg.dims[i];
+        if (i > 0) {
+          const size_t n = ch * h->cfg.dims[i - 1] * 4;
+          h->down[i].p_s_w = bump(cur, n * 4);
+          h->down[i].p_s_wt = bump(cur, n * 4);
+        }
+        for (BlockPk& b : h->blocks[i]) {
+          b.p_s_fc1 = bump(cur, 4 * ch * ch * 4);
+          b.p_s_fc2 = bump(cur, 4 * ch * ch * 4);
+          b.p_s_fc1t = bump(cur, 4 * ch * ch * 4);
+          b.p_s_fc2t = bump(cur, 4 * ch * ch * 4);
+        }
+      }
+      h->extra_bytes = cur;
+    }
+    h->train_split = value == 1;
+    return BTSBOT_OK;
+  }
+  if (strcmp(key, "query_train_split") == 0) {
+    // a query: BTSBOT_OK when the training step's matrix products run on split operands
+    if (!h->train_split) {
+      btsbot_set_error("query_train_split: this handle's training products run on %s",
+                       h->x2 ? "the fp32 MFMA (train_split is off)" : "the operand type of its precision");
+      return BTSBOT_ERR_STATE;
+    }
     return BTSBOT_OK;
   }
   if (strcmp(key, "query_side_apart") == 0) {
@@ -1709,22 +1781,67 @@ extern "C" int btsbot_op_gemm(int prec, int epi, const void* X, const void* W, c
     btsbot_set_error("op_gemm: invalid argument");
     return BTSBOT_ERR_INVALID_ARG;
   }
+  if ((epi == EPI_GELU_SAVE || epi == EPI_DGELU) && resid == nullptr) {   // (every precision: the pre-activation's buffer)
+    btsbot_set_error("op_gemm: this epilogue needs resid (the pre-activation)");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
   if (prec == BTSBOT_F16X2) {   // fp32 X and W: W split into its f16 head and remainder planes here, stream-ordered
     hipStream_t st = (hipStream_t)stream;
     if (M == 0) return BTSBOT_OK;
+    // (the training epilogues whose X is a gradient: X's largest magnitude sets its power-of-two scale, as in the step)
+    const bool grad_x = epi == EPI_DGELU || epi == EPI_PLAIN;
     void* wsplit = nullptr;
-    HIP_TRY(hipMallocAsync(&wsplit, (size_t)N * K * 4, st));
+    HIP_TRY(hipMallocAsync(&wsplit, (size_t)N * K * 4 + AMAX_WORDS * 4, st));
+    unsigned* xamax = grad_x ? reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(wsplit) + (size_t)N * K * 4) : nullptr;
     const float* w = reinterpret_cast<const float*>(W);
     int s = launch_cast(BTSBOT_F16, w, wsplit, (int64_t)N * K, st);
     if (s == BTSBOT_OK)
       s = launch_rowscale_cast_lo(w, nullptr, reinterpret_cast<f16_t*>(wsplit) + (size_t)N * K, N, K, st);
+    if (s == BTSBOT_OK && grad_x) {
+      if (hipMemsetAsync(xamax, 0, AMAX_WORDS * 4, st) != hipSuccess) s = BTSBOT_ERR_HIP;
+      if (s == BTSBOT_OK) s = launch_copy_amax(reinterpret_cast<const float*>(X), nullptr, (long)M * K, xamax, st);
+    }
     if (s == BTSBOT_OK)
-      s = launch_gemm_x2(epi, reinterpret_cast<const float*>(X), wsplit, bias, gamma, resid, reinterpret_cast<float*>(out),
-                         M, N, K, st);
+      s = launch_gemm_x2_train(epi, reinterpret_cast<const float*>(X), wsplit, bias, gamma, resid,
+                               reinterpret_cast<float*>(out), M, N, K, xamax, nullptr, st);
     HIP_TRY(hipFreeAsync(wsplit, st));
     return s;
   }
   return launch_gemm(prec, epi, X, W, bias, gamma, resid, out, M, N, K, (hipStream_t)stream);
+}
+
+extern "C" int btsbot_op_wgrad(int prec, const float* D, const float* A, float* out, float* colsum, int M, int N, int K,
+                               void* stream) {
+  if (D == nullptr || A == nullptr || out == nullptr || M < 0 || N < 1 || K < 1) {
+    btsbot_set_error("op_wgrad: invalid argument");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (M == 0) return BTSBOT_OK;
+  if (prec == BTSBOT_F32) return launch_wgrad_cs_f32(D, A, out, colsum, M, N, K, K, st);
+  if (prec != BTSBOT_F16X2) {
+    btsbot_set_error("op_wgrad: precision %d (BTSBOT_F32 or BTSBOT_F16X2)", prec);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  // split operands as in the split training step's stem: the largest magnitudes of D and of A set their power-of-two
+  // scales (for an O(1) A, as the other products of the step have, the scale changes nothing but the exponents); slice
+  // partials + fixed-order sum
+  if ((N & 15) || (K & 15)) {
+    btsbot_set_error("op_wgrad: N=%d K=%d must be multiples of 16", N, K);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  const size_t part_floats = (size_t)16 << 20;
+  void* scratch = nullptr;
+  HIP_TRY(hipMallocAsync(&scratch, part_floats * 4 + 2 * AMAX_WORDS * 4, st));
+  float* part = reinterpret_cast<float*>(scratch);
+  unsigned* damax = reinterpret_cast<unsigned*>(part + part_floats);
+  unsigned* aamax = damax + AMAX_WORDS;
+  int s = hipMemsetAsync(damax, 0, 2 * AMAX_WORDS * 4, st) == hipSuccess ? BTSBOT_OK : BTSBOT_ERR_HIP;
+  if (s == BTSBOT_OK) s = launch_copy_amax(D, nullptr, (long)M * N, damax, st);
+  if (s == BTSBOT_OK) s = launch_copy_amax(A, nullptr, (long)M * K, aamax, st);
+  if (s == BTSBOT_OK) s = launch_wgrad_x2(D, A, out, colsum, M, N, K, K, damax, aamax, st, part, part_floats, nullptr);
+  HIP_TRY(hipFreeAsync(scratch, st));
+  return s;
 }
 
 extern "C" int btsbot_op_dwconv_ln(int prec, const float* x, const float* w, const float* bias,

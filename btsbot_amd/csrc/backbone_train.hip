@@ -10,6 +10,10 @@
 //     kept per stage : the stage output (input of the next downsample), the 2x2 patch matrix
 //     kept once      : the stem convolution's output before its LayerNorm (fp32)
 // Everything else (LN statistics) is recomputed in the backward.
+// Split training (BTSBOT_F16X2 + "train_split", fp32 schedule otherwise): the blocks' fc1 / fc2 products and the
+// downsamples' -- forward, input gradients and filter gradients -- on split operands (gemm_x2.hip, wgrad_x2.hip).  The
+// gradient operands (dy of a block or downsample, da) carry the largest magnitude the kernel that wrote them recorded;
+// the products scale them by a power of two from it before the split (common.h: split_exp).
 #include <string.h>
 
 #include "ctx.h"
@@ -57,6 +61,9 @@ struct BBCache {
   float* wpart;             // fp32 2 x WPART_FLOATS: slice partials of the filter-gradient GEMMs (wgrad.hip)
   void* stem_patches;       // [B*225][48] operand type
   float* stem_pre;          // [B*225][C0] fp32
+  unsigned* amax;           // split training: the largest magnitudes (float bits) of the gradient operands, or nullptr:
+  int namax;                // [2 b] dy, [2 b + 1] da of block b (in schedule order), [2 nblocks + i] dy of downsample i
+                            // (i = 1..3), [2 nblocks] the stem's dy, [2 nblocks + 4] the stem's patches
   size_t total;
 };
 
@@ -143,6 +150,8 @@ BBCache carve_bb(const btsbot_ctx* h, unsigned char* base, int B) {
   k.wpart = reinterpret_cast<float*>(take(2 * WPART_FLOATS * 4));   // two GEMMs' partial tiles at a time
   k.stem_patches = take((size_t)B * 225 * 48 * esz);
   k.stem_pre = reinterpret_cast<float*>(take((size_t)B * 225 * c.dims[0] * 4));
+  k.namax = 2 * (c.depths[0] + c.depths[1] + c.depths[2] + c.depths[3]) + 5;
+  k.amax = h->train_split ? reinterpret_cast<unsigned*>(take((size_t)k.namax * AMAX_WORDS * 4)) : nullptr;
   k.total = cur;
   return k;
 }
@@ -210,6 +219,10 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
       const int cin = c.dims[i - 1];
       TRYB(launch_ln_patch(c.precision, k.xs[i - 1], m + h->down[i].ln_w, m + h->down[i].ln_b,
                            k.patches[i], B, STAGE_HW[i - 1], cin, st));
+      if (h->train_split)
+        TRYB(launch_gemm_x2_train(EPI_BIAS, reinterpret_cast<const float*>(k.patches[i]), h->extra + h->down[i].p_s_w,
+                                  m + h->down[i].b, nullptr, nullptr, stage_in(i), rows, ch, 4 * cin, nullptr, nullptr, st));
+      else
       TRYB(launch_gemm(c.precision, EPI_BIAS, k.patches[i], h->extra + h->down[i].p_w,
                        m + h->down[i].b, nullptr, nullptr, stage_in(i), rows, ch, 4 * cin, st));
     }
@@ -267,6 +280,14 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
                               rows, st, nullptr, nullptr, nullptr, 0, s.xin));
         continue;
       }
+      if (h->train_split) {   // (split training: the activations enter the products unscaled, as in inference)
+        TRYB(launch_gemm_x2_train(EPI_GELU_SAVE, reinterpret_cast<const float*>(s.xn), h->extra + b.p_s_fc1, m + b.fc1_b,
+                                  nullptr, reinterpret_cast<const float*>(s.a), reinterpret_cast<float*>(s.h), rows, 4 * ch,
+                                  ch, nullptr, nullptr, st));
+        TRYB(launch_gemm_x2_train(EPI_RESID, reinterpret_cast<const float*>(s.h), h->extra + b.p_s_fc2, m + b.fc2_b,
+                                  m + b.gamma, s.xin, xout, rows, ch, 4 * ch, nullptr, nullptr, st));
+        continue;
+      }
       TRYB(launch_gemm(c.precision, EPI_GELU_SAVE, s.xn, h->extra + b.p_fc1, m + b.fc1_b, nullptr,
                        reinterpret_cast<const float*>(s.a), s.h, rows, 4 * ch, ch, st));
       TRYB(launch_gemm(c.precision, EPI_RESID, s.h, h->extra + b.p_fc2, m + b.fc2_b, m + b.gamma,
@@ -297,6 +318,15 @@ static int wgrad_cs(int prec, const void* D, const void* A, float* out, float* c
     return launch_wgrad16(prec, D, A, out, cs, M, N, K, ldo, st, part, WPART_FLOATS, defer);
   }
   return launch_wgrad_cs_f32(reinterpret_cast<const float*>(D), reinterpret_cast<const float*>(A), out, cs, M, N, K, ldo, st);
+}
+
+// the same on split operands (split training): D's scale from its largest magnitude (damax's record); the column sum in
+// fp32 on the unscaled D, inside the same launch
+static int wgrad_cs_x2(const void* D, const void* A, const unsigned* damax, float* out, float* cs, int M, int N, int K,
+                       int ldo, hipStream_t st, float* part, WgradReduceJob* defer = nullptr, const unsigned* aamax = nullptr) {
+  const float* d = reinterpret_cast<const float*>(D);
+  return launch_wgrad_x2(d, reinterpret_cast<const float*>(A), out, cs, M, N, K, ldo, damax, aamax, st, part, WPART_FLOATS,
+                         defer);
 }
 
 int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat, float* grads,
@@ -351,6 +381,14 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
     float* z0 = k.fS0 != nullptr ? k.fS0 : k.S;
     TRYB(launch_fill0(z0, (size_t)((k.G + k.g_floats) - z0), st));
   }
+  const bool sp = h->train_split;
+  if (sp) TRYB(launch_fill0(reinterpret_cast<float*>(k.amax), (size_t)k.namax * AMAX_WORDS, st));
+  auto amax_rec = [&](int slot) { return k.amax + (size_t)slot * AMAX_WORDS; };
+  auto blk_amax = [&](int i, int j) {   // dy slot of block (i, j); its da slot follows
+    int b = j;
+    for (int q = 0; q < i; ++q) b += c.depths[q];
+    return 2 * b;
+  };
   // (deterministic mode: the per-GEMM launches with their fixed-order column sums)
   const bool batching = k.gb_floats > 0 && det_alloc(0) == nullptr;
   if (batching) TRYB(launch_fill0(k.gb0, k.gb_floats, st));
@@ -375,7 +413,11 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
       const BlkBuf& s = k.blk[i][j];
       const float* wdw = reinterpret_cast<const float*>(h->extra + b.p_dw);
       const bool batched = batching && s.Gb != nullptr && s.fpart == nullptr && nbj + 2 <= 16;
-      if (!dyT_ready)
+      unsigned* am_dy = sp ? amax_rec(blk_amax(i, j)) : nullptr;
+      unsigned* am_da = sp ? amax_rec(blk_amax(i, j) + 1) : nullptr;
+      if (sp)   // (split training: the fp32 copy also records dy's largest magnitude)
+        TRYB(launch_copy_amax(dy, reinterpret_cast<float*>(s.dyT), (long)rows * ch, am_dy, st));
+      else if (!dyT_ready)
         TRYB(launch_scale_cast(prec, dy, nullptr, s.dyT, (long)rows * ch, ch, st));
       dyT_ready = false;
       WgradReduceJob red[2];
@@ -401,6 +443,14 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
         // ---- 256 channels: da = (dy (diag(gamma) W2)) * gelu'(a) and dxn = da W1 in one launch (s2mlp_bwd.hip)
         TRYB(launch_s2mlp_bwd(prec, s.dyT, s.a, h->extra + b.p_w2tp, h->extra + b.p_w1tp, s.da, dxn, rows, st));
         if (!batched || h->fork_per_block) TRYB(fork());
+      } else if (sp) {
+        // ---- split training: the two products below on split operands (dy, da scaled by their own powers of two)
+        TRYB(launch_gemm_x2_train(EPI_DGELU, reinterpret_cast<const float*>(s.dyT), h->extra + b.p_s_fc2t, nullptr, nullptr,
+                                  reinterpret_cast<const float*>(s.a), reinterpret_cast<float*>(s.da), rows, H, ch, am_dy,
+                                  am_da, st));
+        TRYB(fork());
+        TRYB(launch_gemm_x2_train(EPI_PLAIN, reinterpret_cast<const float*>(s.da), h->extra + b.p_s_fc1t, nullptr, nullptr,
+                                  nullptr, dxn, rows, ch, H, am_da, nullptr, st));
       } else {
       // ---- da = (dy (diag(gamma) W2)) * gelu'(a)     (gamma is folded into the packed W2^T)
       TRYB(launch_gemm(prec, EPI_DGELU, s.dyT, h->extra + b.p_fc2t, nullptr, nullptr,
@@ -446,7 +496,11 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
         dyT_ready = nxt != nullptr;
         continue;
       }
-      if (s.fpart == nullptr) {
+      if (sp) {
+        TRYB(wgrad_cs_x2(s.dyT, s.h, am_dy, k.G, k.S, rows, ch, H, H, sd, k.wpart, &red[0]));
+        TRYB(wgrad_cs_x2(s.da, s.xn, am_da, grads + b.fc1_w, grads + b.fc1_b, rows, H, ch, ch, sd, k.wpart + WPART_FLOATS,
+                         &red[1]));
+      } else if (s.fpart == nullptr) {
       TRYB(wgrad_cs(prec, s.dyT, s.h, k.G, k.S, rows, ch, H, H, sd, k.wpart, &red[0]));
       TRYB(wgrad_cs(prec, s.da, s.xn, grads + b.fc1_w, grads + b.fc1_b, rows, H, ch, ch, sd, k.wpart + WPART_FLOATS,
                     &red[1]));
@@ -480,11 +534,18 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
       const int cin = c.dims[i - 1], hwp = STAGE_HW[i - 1];
       const long prow = (long)B * hwp * hwp;
       void* dyT = k.dyT_down[i];
-      if (!dyT_ready)
+      unsigned* am_dn = sp ? amax_rec(k.namax - 5 + i) : nullptr;
+      if (sp)
+        TRYB(launch_copy_amax(dy, reinterpret_cast<float*>(dyT), (long)rows * ch, am_dn, st));
+      else if (!dyT_ready)
         TRYB(launch_scale_cast(prec, dy, nullptr, dyT, (long)rows * ch, ch, st));
       dyT_ready = false;
       TRYB(fork());
       if (nbj > 0) TRYB(stage_batch());
+      if (sp)
+        TRYB(launch_gemm_x2_train(EPI_PLAIN, reinterpret_cast<const float*>(dyT), h->extra + h->down[i].p_s_wt, nullptr,
+                                  nullptr, nullptr, k.dpat, rows, 4 * cin, ch, am_dn, nullptr, st));
+      else
       TRYB(launch_gemm(prec, EPI_PLAIN, dyT, h->extra + h->down[i].p_wt, nullptr, nullptr,
                        nullptr, k.dpat, rows, 4 * cin, ch, st));
       // LN backward per input pixel (x_prev = stage i-1 output), its incoming gradient gathered from the patch matrix
@@ -495,6 +556,9 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
                          grads + h->down[i].ln_b, prow, cin, st, nxt16, prec, hwp));
       dyT_ready = nxt16 != nullptr;
       // (side work queued behind the chain's launches, as in the blocks)
+      if (sp)
+        TRYB(wgrad_cs_x2(dyT, k.patches[i], am_dn, k.G, grads + h->down[i].b, rows, ch, 4 * cin, 4 * cin, sd, k.wpart));
+      else
       TRYB(wgrad_cs(prec, dyT, k.patches[i], k.G, grads + h->down[i].b, rows, ch, 4 * cin, 4 * cin, sd, k.wpart));
       TRYB(launch_unpack_down_grad(k.G, grads + h->down[i].w, ch, cin, sd));
     }
@@ -511,10 +575,22 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
     const int c0 = c.dims[0], rows = B * 225;
     TRYB(launch_ln_bwd(k.stem_pre, dy, m + h->stem_lnw, dxn, grads + h->stem_lnw,
                        grads + h->stem_lnb, rows, c0, st, fold_cast ? k.dyT_stem : nullptr, prec));
+    if (sp) {
+      // (split training: the stem's filter gradient on split operands too -- its fp32 kernel meets through atomics; the
+      //  patches are raw pixel values, scaled like the gradient)
+      unsigned* am = amax_rec(k.namax - 5);
+      TRYB(launch_copy_amax(dxn, reinterpret_cast<float*>(k.dyT_stem), (long)rows * c0, am, st));
+      TRYB(fork());
+      TRYB(launch_copy_amax(reinterpret_cast<const float*>(k.stem_patches), nullptr, (long)rows * 48, amax_rec(k.namax - 1),
+                            sd));
+      TRYB(wgrad_cs_x2(k.dyT_stem, k.stem_patches, am, grads + h->stem_w, grads + h->stem_b, rows, c0, 48, 48, sd,
+                       k.wpart, nullptr, amax_rec(k.namax - 1)));
+    } else {
     if (!fold_cast) TRYB(launch_scale_cast(prec, dxn, nullptr, k.dyT_stem, (long)rows * c0, c0, st));
     TRYB(fork());
     TRYB(wgrad_cs(prec, k.dyT_stem, k.stem_patches, grads + h->stem_w, grads + h->stem_b, rows, c0, 48, 48,
                   sd, k.wpart));
+    }
   }
   TRYB(join());
   if (h->n_buckets == 3 && h->bucket_fine) HIP_TRY(hipEventRecord(h->bucket_ev[2], st));

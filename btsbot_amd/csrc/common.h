@@ -37,6 +37,36 @@ __device__ __forceinline__ h2x8 split8(const float (&v)[8]) {
   }
   return o;
 }
+// Gradient operands of the split training products (btsbot_set_option "train_split") are small -- the BCE mean's 1/B and
+// the backbone shrink them -- and split naively their heads would be f16 subnormals.  They enter the products scaled by
+// 2^e, one e per tensor, chosen from the tensor's largest magnitude (the bits of a non-negative float, collected with
+// atomicMax by the kernel that writes the tensor) so that it lands in [2^14, 2^15); an all-zero tensor (or none) keeps
+// e = 0.  Both scalings are powers of two: applying and undoing them is exact.
+// A tensor's record is AMAX_WORDS words: AMAX_SUB running maxima on separate cache lines, so that the waves of a large
+// launch do not all queue at one address (one line: a copy of stage 0's dy took 4x as long as without the record).
+constexpr int AMAX_SUB = 16, AMAX_STRIDE = 32, AMAX_WORDS = AMAX_SUB * AMAX_STRIDE;
+__device__ __forceinline__ int split_exp(const unsigned* amax) {
+  if (amax == nullptr) return 0;
+  unsigned m = 0;
+#pragma unroll
+  for (int i = 0; i < AMAX_SUB; ++i) m = max(m, amax[i * AMAX_STRIDE]);
+  const float a = __uint_as_float(m);
+  if (!(a > 0.f) || !(a <= 3.0e38f)) return 0;
+  int ex;
+  (void)frexpf(a, &ex);   // a in [2^(ex-1), 2^ex)
+  const int e = 15 - ex;
+  return e < -100 ? -100 : e > 100 ? 100 : e;
+}
+// 64-lane max of a non-negative float's bits, then one vector atomic per wave (every lane of the wave must call it)
+__device__ __forceinline__ void wave_amax(unsigned* amax, float v) {
+  unsigned b = __float_as_uint(fabsf(v));
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const unsigned t = (unsigned)__shfl_xor((int)b, o);
+    b = t > b ? t : b;
+  }
+  if ((threadIdx.x & 63) == 0 && b != 0u) atomicMax(amax + (blockIdx.x % AMAX_SUB) * AMAX_STRIDE, b);
+}
 __device__ __forceinline__ h2x4 split4(const float (&v)[4]) {
   h2x4 o;
 #pragma unroll
@@ -397,6 +427,25 @@ struct WgradBatchJob {
 int launch_wgrad16_batched(int prec, const WgradBatchJob* jobs, int njobs, float* part, size_t part_floats, int target_wg,
                            hipStream_t st);
 int launch_colsum(int prec, const void* in, float* out, int M, int N, hipStream_t st);  // out[n] += ...
+// ---- split training products (BTSBOT_F16X2 handles with "train_split"; gemm_x2.hip / wgrad_x2.hip)
+// launch_gemm_x2 with every epilogue, the training ones included (EPI_GELU_SAVE / EPI_DGELU / EPI_PLAIN: gemm.hip's fp32
+// semantics).  xamax (optional): X's largest magnitude (split_exp) -- X enters scaled by 2^e, the epilogue undoes it;
+// oamax (optional, EPI_DGELU): receives the largest magnitude of what the launch writes
+int launch_gemm_x2_train(int epi, const float* X, const void* W, const float* bias, const float* gamma, const float* resid,
+                         float* out, int M, int N, int K, const unsigned* xamax, unsigned* oamax, hipStream_t st);
+// out[n][k] += sum_m D[m][n] A[m][k] and (colsum != nullptr) colsum[n] += sum_m D[m][n] (fp32 sums of the unscaled D,
+// fixed-order in deterministic mode) on split operands (D, A fp32 pixel-major; D scaled by 2^split_exp(damax) before the
+// split, undone on the slice partials; aamax, optional: A likewise -- the stem's patches are raw pixel values).  N, K
+// multiples of 16.  part / part_floats / defer as for launch_wgrad16; with part the slices never meet through atomics
+// (a single slice still goes through the partial tiles).
+int launch_wgrad_x2(const float* D, const float* A, float* out, float* colsum, int M, int N, int K, int ldo, const unsigned* damax,
+                    const unsigned* aamax, hipStream_t st, float* part, size_t part_floats, WgradReduceJob* defer);
+// out = in (fp32 copy; out may be nullptr) and amax's record (AMAX_WORDS words) takes in's largest magnitude (n a multiple
+// of 4, 16-byte aligned)
+int launch_copy_amax(const float* in, float* out, long n, unsigned* amax, hipStream_t st);
+// f16 head / remainder planes of fp32 images: for each job, dst[0, n) = f16(src), dst[n, 2n) = f16(src - f16(src))
+struct SplitJob { const float* src; void* dst; long n; };
+int launch_split_jobs(const SplitJob* jobs_dev, int njobs, hipStream_t st);
 // fp32 mode: out[n][k] += sum_m D[m][n] A[m][k] and (cs != nullptr) cs[n] += sum_m D[m][n] (backward.hip)
 int launch_wgrad_cs_f32(const float* D, const float* A, float* out, float* cs, int M, int N, int K, int ldo, hipStream_t st);
 int launch_rowscale_cast(int prec, const float* in, const float* rowscale, void* out, int rows,

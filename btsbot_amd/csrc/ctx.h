@@ -25,6 +25,9 @@ struct BlockPk {  // per ConvNeXt block: master offsets + packed offsets (bytes 
   size_t p_x2_w1lo = 0, p_x2_w2glo = 0;   // ... and their f16 remainders, same layouts
   size_t p_fc1t, p_fc2t;   // for the dgrad GEMMs: W1^T [C][4C], (diag(gamma) W2)^T [4C][C]
   size_t p_w1tp = 0, p_w2tp = 0;   // 256-channel blocks, training: the same two as MFMA A fragments (s2mlp_bwd.hip)
+  // split training ("train_split"): p_fc1 / p_fc2 / p_fc1t / p_fc2t as f16 head + remainder planes, [n] heads then [n]
+  // remainders (slots of their own: the per-op inference forward of the split mode reads the fp32 p_fc1 / p_fc2)
+  size_t p_s_fc1 = 0, p_s_fc2 = 0, p_s_fc1t = 0, p_s_fc2t = 0;
   bool fused;
 };
 struct DownPk {
@@ -33,6 +36,7 @@ struct DownPk {
   size_t p_wp = 0;         // stage2p.hip: the filter as MFMA A fragments
   size_t p_scale = 0;      // fp8 mode: {S, 1/S} of it
   size_t p_x2_w = 0, p_x2_wlo = 0;   // split mode, stage0b's downsample: the filter's f16 heads / remainders, [Cout][q][Cin]
+  size_t p_s_w = 0, p_s_wt = 0;      // split training: p_w / p_wt as f16 head + remainder planes (BlockPk::p_s_fc1)
 };
 
 constexpr int STAGE_HW[4] = {15, 7, 3, 1};
@@ -155,6 +159,11 @@ struct btsbot_ctx {
   int64_t img_floats = 0;     // master-arena floats [0, img_floats) belong to the image branch
   const float* t_img = nullptr;   // triplets of the last training forward (stem backward re-reads them)
   bool train_packs = false;   // also pack the dgrad transposes (set by btsbot_reserve_train)
+  // btsbot_set_option("train_split"), BTSBOT_F16X2 ConvNeXt handles: the training step's 1x1 / downsample products (forward,
+  // input gradients, filter gradients) run on split operands (gemm_x2.hip, wgrad_x2.hip) instead of the fp32 MFMA
+  bool train_split = false;
+  void* split_jobs = nullptr;   // ... the re-pack's SplitJob table (device), built on the first training pack
+  int split_njobs = 0;
   bool bb_saved = false;      // the last training forward kept the image-branch activations
   // training cache (head_train.hip): activations of the last training-mode forward
   float* tcache = nullptr;

@@ -1,4 +1,4 @@
-// Split-operand GEMM (BTSBOT_F16X2) for the MaxViT inference forward (gfx950).
+// Split-operand GEMM (BTSBOT_F16X2) for the MaxViT inference forward and the split ConvNeXt training step (gfx950).
 //
 //   out[m][n] = epi( sum_k X[m][k] * W[n][k] + bias[n] )
 //
@@ -7,6 +7,10 @@
 // Every value enters the products as head + remainder, and each product is lo*hi + hi*lo + hi*hi on
 // v_mfma_f32_16x16x32_f16 with fp32 accumulation, small terms first: an fp32-class result at the
 // f16 matrix rate.  The epilogues are the fp32 ones of gemm.hip (exact erf GELU, expf SiLU), output always fp32.
+// Training (btsbot_set_option "train_split"): the forward's GELU_SAVE and the input-gradient products' DGELU / PLAIN.
+// Their X is a gradient there: it enters scaled by 2^e (common.h: split_exp of its largest magnitude) so that its heads
+// stay normal f16 values, and the epilogue multiplies the accumulator by 2^-e; DGELU also reports its output's largest
+// magnitude, the scale of the products that read it next.
 //
 // Tiling: 256 threads = 4 waves, workgroup tile TM x TN, K tile = 64.  X is read global -> registers as 16-byte
 // vectors (two per 8-column chunk), split in registers (the MBConv squeeze-excite gate applied to the fp32 value
@@ -35,7 +39,8 @@ template <int TM, int TN, int WM, int WN, int EPI, bool GATED>
 __global__ __launch_bounds__(256) void gemm_x2_kernel(const float* __restrict__ X, const f16_t* __restrict__ W,
                                                       const float* __restrict__ bias, const float* __restrict__ gamma,
                                                       const float* resid, float* out, int M, int N, int K,
-                                                      const float* __restrict__ gate, int rows_per_alert) {
+                                                      const float* __restrict__ gate, int rows_per_alert,
+                                                      const unsigned* __restrict__ xamax, unsigned* oamax) {
   constexpr int WTM = TM / WM, WTN = TN / WN;
   constexpr int MI = WTM / 16, NI = WTN / 16;
   constexpr int XCH = TM * 8 / 256, WCH = TN * 8 / 256;   // 8-element chunks per thread and K tile
@@ -51,6 +56,8 @@ __global__ __launch_bounds__(256) void gemm_x2_kernel(const float* __restrict__ 
   const int wm = wave / WN, wn = wave % WN;
   const int m0 = blockIdx.x * TM, n0 = blockIdx.y * TN;
   const f16_t* Wlo = W + (size_t)N * K;
+  const int xe = split_exp(xamax);
+  const float xs = ldexpf(1.f, xe), xu = ldexpf(1.f, -xe);   // exact powers of two (|xe| <= 100)
 
   float4 xr[XCH][2];
   float4 gr[GATED ? XCH : 1][2];
@@ -91,6 +98,10 @@ __global__ __launch_bounds__(256) void gemm_x2_kernel(const float* __restrict__ 
                             gr[i][1].x, gr[i][1].y, gr[i][1].z, gr[i][1].w};
 #pragma unroll
         for (int q = 0; q < 8; ++q) v[q] *= g[q];
+      }
+      if (xe != 0) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] *= xs;
       }
       const h2x8 s = split8(v);
       const int o = swz(row, kc);
@@ -158,13 +169,15 @@ __global__ __launch_bounds__(256) void gemm_x2_kernel(const float* __restrict__ 
     }
   __syncthreads();
   const int j = tid % SL, n = n0 + 4 * j;
-  if (n >= N) return;
+  const bool live = n < N;
+  constexpr bool NOBIAS = GATED || EPI == EPI_DGELU || EPI == EPI_PLAIN;
   float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (!GATED) bv = *reinterpret_cast<const float4*>(bias + n);
+  if (!NOBIAS && live) bv = *reinterpret_cast<const float4*>(bias + n);
   float4 gv = make_float4(1.f, 1.f, 1.f, 1.f);
-  if (EPI == EPI_RESID && !GATED) gv = *reinterpret_cast<const float4*>(gamma + n);
+  if (EPI == EPI_RESID && !GATED && live) gv = *reinterpret_cast<const float4*>(gamma + n);
+  float omax = 0.f;
 #pragma unroll 4
-  for (int r = tid / SL; r < TM; r += 256 / SL) {
+  for (int r = tid / SL; r < TM && live; r += 256 / SL) {
     const int m = m0 + r;
     if (m >= M) break;
     const float4 a = *reinterpret_cast<const float4*>(T + r * TN + ((j ^ (r & XM)) << 2));
@@ -180,19 +193,32 @@ __global__ __launch_bounds__(256) void gemm_x2_kernel(const float* __restrict__ 
       v.y = rv.y + gv.y * (a.y + bv.y);
       v.z = rv.z + gv.z * (a.z + bv.z);
       v.w = rv.w + gv.w * (a.w + bv.w);
+    } else if (EPI == EPI_GELU_SAVE) {   // the fp32 pre-activation to resid, its GELU to out (gemm.hip)
+      const float4 pre = make_float4(a.x + bv.x, a.y + bv.y, a.z + bv.z, a.w + bv.w);
+      *reinterpret_cast<float4*>(const_cast<float*>(resid) + o) = pre;
+      v = make_float4(gelu_erf(pre.x), gelu_erf(pre.y), gelu_erf(pre.z), gelu_erf(pre.w));
+    } else if (EPI == EPI_DGELU) {      // out = acc * gelu'(pre), pre = the saved fp32 pre-activation
+      const float4 pre = *reinterpret_cast<const float4*>(resid + o);
+      v = make_float4(a.x * xu * gelu_grad(pre.x), a.y * xu * gelu_grad(pre.y), a.z * xu * gelu_grad(pre.z),
+                      a.w * xu * gelu_grad(pre.w));
+      omax = fmaxf(omax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+    } else if (EPI == EPI_PLAIN) {
+      v = make_float4(a.x * xu, a.y * xu, a.z * xu, a.w * xu);
     } else {   // EPI_BIAS, EPI_BIAS_T
       v = make_float4(a.x + bv.x, a.y + bv.y, a.z + bv.z, a.w + bv.w);
     }
     *reinterpret_cast<float4*>(out + o) = v;
   }
+  if (EPI == EPI_DGELU && oamax != nullptr) wave_amax(oamax, omax);   // (every lane of every wave gets here)
 }
 
 template <int TM, int TN, int WM, int WN, int EPI, bool GATED>
 int launch_tile(const float* x, const f16_t* w, const float* bias, const float* gamma, const float* resid, float* out,
-                int M, int N, int K, const float* gate, int rpa, hipStream_t st) {
+                int M, int N, int K, const float* gate, int rpa, hipStream_t st, const unsigned* xamax = nullptr,
+                unsigned* oamax = nullptr) {
   dim3 grid((M + TM - 1) / TM, (N + TN - 1) / TN);
   hipLaunchKernelGGL((gemm_x2_kernel<TM, TN, WM, WN, EPI, GATED>), grid, dim3(256), 0, st, x, w, bias, gamma, resid,
-                     out, M, N, K, gate, rpa);
+                     out, M, N, K, gate, rpa, xamax, oamax);
   LAUNCH_CHECK();
   return BTSBOT_OK;
 }
@@ -201,15 +227,16 @@ int launch_tile(const float* x, const f16_t* w, const float* bias, const float* 
 // narrow filters (stem, shortcut, stage-0 qkv-less GEMMs), 64 x 64 for the short late-stage maps.
 template <int EPI, bool GATED>
 int launch_shape(const float* x, const f16_t* w, const float* bias, const float* gamma, const float* resid, float* out,
-                 int M, int N, int K, const float* gate, int rpa, hipStream_t st) {
+                 int M, int N, int K, const float* gate, int rpa, hipStream_t st, const unsigned* xa = nullptr,
+                 unsigned* oa = nullptr) {
   const long wg128 = (long)((M + 127) / 128) * ((N + 127) / 128);
   const long wg12864 = (long)((M + 127) / 128) * ((N + 63) / 64);
-  if (N <= 32) return launch_tile<128, 32, 4, 1, EPI, GATED>(x, w, bias, gamma, resid, out, M, N, K, gate, rpa, st);
+  if (N <= 32) return launch_tile<128, 32, 4, 1, EPI, GATED>(x, w, bias, gamma, resid, out, M, N, K, gate, rpa, st, xa, oa);
   if (N >= 128 && wg128 >= 512)
-    return launch_tile<128, 128, 2, 2, EPI, GATED>(x, w, bias, gamma, resid, out, M, N, K, gate, rpa, st);
+    return launch_tile<128, 128, 2, 2, EPI, GATED>(x, w, bias, gamma, resid, out, M, N, K, gate, rpa, st, xa, oa);
   if (wg12864 >= 512 || N < 64)
-    return launch_tile<128, 64, 4, 1, EPI, GATED>(x, w, bias, gamma, resid, out, M, N, K, gate, rpa, st);
-  return launch_tile<64, 64, 2, 2, EPI, GATED>(x, w, bias, gamma, resid, out, M, N, K, gate, rpa, st);
+    return launch_tile<128, 64, 4, 1, EPI, GATED>(x, w, bias, gamma, resid, out, M, N, K, gate, rpa, st, xa, oa);
+  return launch_tile<64, 64, 2, 2, EPI, GATED>(x, w, bias, gamma, resid, out, M, N, K, gate, rpa, st, xa, oa);
 }
 
 int check_shape(const char* who, int M, int N, int K) {
@@ -228,11 +255,23 @@ int check_shape(const char* who, int M, int N, int K) {
 
 int launch_gemm_x2(int epi, const float* X, const void* W, const float* bias, const float* gamma, const float* resid,
                    float* out, int M, int N, int K, hipStream_t st) {
+  if (epi == EPI_GELU_SAVE || epi == EPI_DGELU || epi == EPI_PLAIN) {
+    btsbot_set_error("launch_gemm_x2: epilogue %d is a training one (launch_gemm_x2_train)", epi);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  return launch_gemm_x2_train(epi, X, W, bias, gamma, resid, out, M, N, K, nullptr, nullptr, st);
+}
+
+int launch_gemm_x2_train(int epi, const float* X, const void* W, const float* bias, const float* gamma, const float* resid,
+                         float* out, int M, int N, int K, const unsigned* xa, unsigned* oa, hipStream_t st) {
   if (M <= 0) return BTSBOT_OK;
   const int s = check_shape("launch_gemm_x2", M, N, K);
   if (s != BTSBOT_OK) return s;
   const f16_t* w = reinterpret_cast<const f16_t*>(W);
   switch (epi) {
+    case EPI_GELU_SAVE: return launch_shape<EPI_GELU_SAVE, false>(X, w, bias, gamma, resid, out, M, N, K, nullptr, 1, st);
+    case EPI_DGELU: return launch_shape<EPI_DGELU, false>(X, w, bias, gamma, resid, out, M, N, K, nullptr, 1, st, xa, oa);
+    case EPI_PLAIN: return launch_shape<EPI_PLAIN, false>(X, w, bias, gamma, resid, out, M, N, K, nullptr, 1, st, xa);
     case EPI_GELU: return launch_shape<EPI_GELU, false>(X, w, bias, gamma, resid, out, M, N, K, nullptr, 1, st);
     case EPI_RESID: return launch_shape<EPI_RESID, false>(X, w, bias, gamma, resid, out, M, N, K, nullptr, 1, st);
     case EPI_BIAS: return launch_shape<EPI_BIAS, false>(X, w, bias, gamma, resid, out, M, N, K, nullptr, 1, st);

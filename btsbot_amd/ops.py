@@ -20,19 +20,32 @@ def _stream(t):
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
-_EPI = {"gelu": 0, "resid": 1, "bias": 2, "silu": 6, "bias_t": 7}
+_EPI = {"gelu": 0, "resid": 1, "bias": 2, "gelu_save": 3, "dgelu": 4, "plain": 5, "silu": 6, "bias_t": 7}
 
 
 def gemm(x, w, bias, epi="bias", gamma=None, resid=None, precision="f32", out=None):
-    """epi in {'gelu','resid','bias','silu','bias_t'}; x [M,K], w [N,K] in the precision's dtype ('f16x2': fp32 x and
-    w, w split into f16 head + remainder inside, every output fp32).  'gelu' / 'silu' / 'bias_t' write the precision's
-    dtype, 'resid' / 'bias' fp32.  out: the output tensor (for 'resid' it may be resid itself: in place)."""
+    """epi in {'gelu','resid','bias','silu','bias_t'} and the training ones {'gelu_save','dgelu','plain'}; x [M,K],
+    w [N,K] in the precision's dtype ('f16x2': fp32 x and w, w split into f16 head + remainder inside, every output
+    fp32).  'gelu' / 'silu' / 'bias_t' write the precision's dtype, 'resid' / 'bias' and the training epilogues fp32.
+    'gelu_save': resid <- acc + bias (the pre-activation), out = gelu(resid); 'dgelu': out = acc * gelu'(resid);
+    'plain': out = acc ('dgelu' / 'plain' read no bias: None is fine).  The training epilogues take precision 'f32' or
+    'f16x2' only; every tensor of theirs is fp32, and 'gelu_save' / 'dgelu' need resid.  out: the output tensor (for
+    'resid' it may be resid itself: in place)."""
+    train_epi = epi in ("gelu_save", "dgelu", "plain")
+    if train_epi and precision not in ("f32", "f16x2"):
+        raise ValueError(f"ops.gemm: the training epilogue {epi!r} takes precision 'f32' or 'f16x2', got {precision!r}")
     dt = torch.float32 if precision == "f16x2" else _DT[precision]
     assert x.dtype == dt and w.dtype == dt and x.is_contiguous() and w.is_contiguous()
     M, K = x.shape
     N = w.shape[0]
     e = _EPI[epi]
-    odt = dt if epi in ("gelu", "silu", "bias_t") else torch.float32
+    if epi in ("gelu_save", "dgelu"):
+        if resid is None:
+            raise ValueError(f"ops.gemm: {epi!r} needs resid (the fp32 pre-activation [M, N])")
+        assert resid.dtype == torch.float32 and resid.shape == (M, N) and resid.is_contiguous()
+    if bias is None and epi in ("dgelu", "plain"):
+        bias = torch.zeros(N, dtype=torch.float32, device=x.device)
+    odt = torch.float32 if train_epi else dt if epi in ("gelu", "silu", "bias_t") else torch.float32
     if out is None:
         out = torch.empty(M, N, dtype=odt, device=x.device)
     assert out.dtype == odt and out.shape == (M, N) and out.is_contiguous()
@@ -40,6 +53,26 @@ def gemm(x, w, bias, epi="bias", gamma=None, resid=None, precision="f32", out=No
         _lib.check(_lib.lib().btsbot_op_gemm(_lib.PRECISION[precision], e, _p(x), _p(w), _p(bias),
                                              _p(gamma), _p(resid), _p(out), M, N, K, _stream(x)),
                    "btsbot_op_gemm")
+    return out
+
+
+def wgrad(d, a, out=None, colsum=None, precision="f32"):
+    """Filter gradient of a 1x1 convolution: out[n][k] += sum_m d[m][n] a[m][k] (and colsum[n] += sum_m d[m][n] when
+    colsum is given).  d [M,N], a [M,K] fp32; out [N,K] fp32 (zeros when None).  precision 'f32' (the fp32 training
+    kernel) or 'f16x2' (the split training form: N, K multiples of 16)."""
+    assert precision in ("f32", "f16x2"), precision
+    assert d.dtype == torch.float32 and a.dtype == torch.float32 and d.is_contiguous() and a.is_contiguous()
+    M, N = d.shape
+    K = a.shape[1]
+    assert a.shape[0] == M
+    if out is None:
+        out = torch.zeros(N, K, dtype=torch.float32, device=d.device)
+    assert out.dtype == torch.float32 and out.shape == (N, K) and out.is_contiguous()
+    if colsum is not None:
+        assert colsum.dtype == torch.float32 and colsum.shape == (N,) and colsum.is_contiguous()
+    with torch.cuda.device(d.device):
+        _lib.check(_lib.lib().btsbot_op_wgrad(_lib.PRECISION[precision], _p(d), _p(a), _p(out), _p(colsum), M, N, K,
+                                              _stream(d)), "btsbot_op_wgrad")
     return out
 
 

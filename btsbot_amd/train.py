@@ -273,7 +273,7 @@ def fit(trainer: Trainer, train_set, val_images, val_metadata, val_labels, model
 
 
 def run_training(config: dict, data_base_dir: str = "", run_name: str = "testing", device="cuda",
-                 precision: str = "bf16", models_root: str = "models"):
+                 precision: str = "bf16", models_root: str = "models", split_training: bool = False):
     """train.py:75-440 (``run_training(config)``) on this framework, minus WandB and the diagnostic figure: seeds,
     the split files (``data.load_split``), the model by name with the frozen_fusion freezing rule
     (train.py:224-236), AdamW(lr, betas=(beta_1, beta_2)) under the warm-up + cosine schedule, BCE with
@@ -282,7 +282,9 @@ def run_training(config: dict, data_base_dir: str = "", run_name: str = "testing
     launched by torchrun) every rank trains its contiguous shard of each global batch and the gradients meet in one
     all-reduce per step; rank 0 writes the files.  Config keys are the reference's: model_name, epochs,
     batch_size, learning_rate, warmup_epochs, beta_1, beta_2, patience, random_seed, train_data_version, N_max,
-    metadata_cols, data_aug_*, plus the model's own.  Returns (history dict, model_dir)."""
+    metadata_cols, data_aug_*, plus the model's own.  split_training: precision 'f16x2' with a ConvNeXt image branch
+    only -- the training step's matrix products on split f16 operands (``set_split_training``).  Returns (history dict,
+    model_dir)."""
     import numpy as np
     import torch.distributed as dist
     from . import architectures
@@ -306,7 +308,10 @@ def run_training(config: dict, data_base_dir: str = "", run_name: str = "testing
         model_type = getattr(architectures, model_name)
     except AttributeError:
         raise ValueError(f"Could not find model of name {model_name}") from None
-    model = model_type(config, precision=precision).to(dev).train()
+    model = model_type(config, precision=precision)
+    if split_training:
+        model.set_split_training(True)
+    model = model.to(dev).train()
     if model_name == "frozen_fusion":                      # only the combined head is trained
         for p in list(model.image_branch.parameters()) + list(model.meta_branch.parameters()):
             p.requires_grad = False

@@ -49,7 +49,9 @@ def main():
     ap.add_argument("--alerts", type=int, default=4096)
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--batch-size", type=int, default=256)
-    ap.add_argument("--precision", default="bf16", choices=["f32", "bf16", "f16"])
+    ap.add_argument("--precision", default="bf16", choices=["f32", "bf16", "f16", "f16x2"])
+    ap.add_argument("--split-training", action="store_true",
+                    help="f16x2 with a ConvNeXt image branch: train on split f16 operands (fp32-class gradients)")
     ap.add_argument("--data-base-dir", default=None)
     args = ap.parse_args()
 
@@ -84,7 +86,8 @@ def main():
                   epochs=args.epochs, batch_size=args.batch_size, learning_rate=1e-3, warmup_epochs=1,
                   beta_1=0.9, beta_2=0.999, patience=5, random_seed=2)
     hist, model_dir = run_training(config, data_base_dir=base, run_name="example", device=dev,
-                                   precision=args.precision, models_root=os.path.join(base, "models"))
+                                   precision=args.precision, models_root=os.path.join(base, "models"),
+                                   split_training=args.split_training)
     if rank == 0:
         for e, (tl, ta, vl, va) in enumerate(zip(hist["train_loss"], hist["train_accuracy"], hist["val_loss"],
                                                  hist["val_accuracy"])):

@@ -76,8 +76,11 @@ enum btsbot_precision {
   BTSBOT_F16X2 = 4 /* split operands: every MFMA operand of the pointwise / downsample convolutions is an f16
                       head plus an f16 remainder (x = hi + lo, 22 significant bits), a product is three
                       v_mfma_f32_*_f16 (hi*hi + hi*lo + lo*hi) -- scores within 1e-4 of the fp32 reference at
-                      the 16-bit matrix rate; kernels without a split form run the fp32 schedule.  Inference
-                      only: the training entry points behave as BTSBOT_F32 */
+                      the 16-bit matrix rate; kernels without a split form run the fp32 schedule.  The
+                      training entry points behave as BTSBOT_F32, unless a ConvNeXt handle opts in with
+                      btsbot_set_option(h, "train_split", 1): its training step then runs the blocks' and
+                      downsamples' matrix products (forward, input and filter gradients) on split operands,
+                      gradient operands scaled by a power of two per tensor first */
 };
 
 typedef struct btsbot_config {
@@ -254,7 +257,17 @@ int btsbot_allreduce_grads(btsbot_handle h, void* nccl_comm, float* grads, int n
  *   products of its inference forward on split operands -- a BTSBOT_F16X2 handle: fp32 maps split into f16 head +
  *   remainder, three f16 MFMAs per product, the filters packed as head and remainder planes; attention, depthwise,
  *   squeeze-excite, LayerNorm and elementwise kernels stay fp32 --, BTSBOT_ERR_STATE for every other handle
- *   (other precisions, ConvNeXt branches, no image branch). */
+ *   (other precisions, ConvNeXt branches, no image branch).
+ *   "train_split" (BTSBOT_F16X2 handles with a ConvNeXt image branch; BTSBOT_ERR_INVALID_ARG for every other handle;
+ *   set before the first btsbot_pack_params* / btsbot_reserve_train, BTSBOT_ERR_STATE after -- it adds packed-operand
+ *   slots): 1 = the training step's 1x1 / downsample products -- fc1 / fc2 / downsample forward, their input gradients
+ *   and their filter gradients -- run on split operands (three f16 MFMAs per product) instead of the fp32 MFMA.  Every
+ *   gradient operand is scaled by 2^e before the split, e per tensor from its largest magnitude (chosen on the device,
+ *   into [2^14, 2^15)) and undone exactly in the fp32 epilogue / slice reduction.  The stem's filter gradient runs split
+ *   too (its raw-pixel patches scaled the same way); the stem's forward convolution, depthwise, LayerNorm, heads, loss
+ *   and optimiser stay fp32; inference is unchanged.  0 (default): the fp32 training schedule.
+ *   "query_train_split" (a query; `value` ignored): BTSBOT_OK when the handle's training products run split,
+ *   BTSBOT_ERR_STATE otherwise. */
 int btsbot_set_option(btsbot_handle h, const char* key, int value);
 
 /* Validation aid with no reference counterpart: when on, forward() keeps fp32 copies of the stem and
@@ -292,6 +305,17 @@ int64_t btsbot_read_tap(btsbot_handle h, const char* name, float* dst, int64_t c
 int btsbot_op_gemm(int prec, int epi, const void* X, const void* W, const float* bias,
                    const float* gamma, const float* resid, void* out, int M, int N, int K,
                    void* stream);
+/*   The training epilogues (fp32 X, W and outputs in BTSBOT_F32; BTSBOT_F16X2 takes them as well):
+ *   epi 3: resid (f32) = acc + bias, out = gelu(resid)      epi 4: out = acc * gelu'(resid)      epi 5: out = acc
+ *   (BTSBOT_F16X2, epi 4 / 5: X is a gradient -- scaled by a power of two from its largest magnitude before the split,
+ *   as in the split training step). */
+/* Filter gradient of a 1x1 convolution: out[n][k] += sum_m D[m][n] A[m][k], colsum[n] += sum_m D[m][n] (colsum may be
+ * NULL).  D [M][N], A [M][K] fp32, pixel-major; out [N][K] fp32.  prec BTSBOT_F32: the fp32 training kernel;
+ * BTSBOT_F16X2: the split form of the split training step (N, K multiples of 16; D and A each scaled by a power of two
+ * from its largest magnitude, as the step's stem does; slice partials added in a fixed order; a stream-ordered scratch
+ * of 64 MB). */
+int btsbot_op_wgrad(int prec, const float* D, const float* A, float* out, float* colsum, int M, int N, int K,
+                    void* stream);
 /* K2+K3: depthwise 7x7 p3 + bias + LayerNorm(C, eps 1e-6).  x [B,HW,HW,C] f32 NHWC ->
  * xn [B,HW,HW,C] (prec).  w_tap_major is [49][C] f32.  (C,HW) in {(64,15),(128,7),(256,3),(512,1),
  * (80,15),(160,7),(320,3),(640,1)}.  Arithmetic: fp32 FMAs on the fp32 map, two-pass variance -- EXCEPT the 15x15 maps

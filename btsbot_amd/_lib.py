@@ -28,6 +28,7 @@ SYMBOLS = [
     "btsbot_set_profile", "btsbot_profile_categories", "btsbot_profile_category_name",
     "btsbot_profile_collect",
     "btsbot_op_gemm", "btsbot_op_dwconv_ln", "btsbot_op_stem", "btsbot_op_ln_patch", "btsbot_op_wgrad",
+    "btsbot_op_gemm_gated", "btsbot_op_gemm_resid_ln",
     "btsbot_reserve_train", "btsbot_forward_train", "btsbot_backward", "btsbot_debug_stamps",
     "btsbot_grad_buckets", "btsbot_wait_grad_bucket", "btsbot_allreduce_grads", "btsbot_use_workspace", "btsbot_set_option",
     "btsbot_augment", "btsbot_eval_metrics", "btsbot_prep_triplets",
@@ -110,6 +111,10 @@ def lib() -> C.CDLL:
     L.btsbot_op_gemm.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     L.btsbot_op_wgrad.restype = i32
     L.btsbot_op_wgrad.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, vp]
+    L.btsbot_op_gemm_gated.restype = i32
+    L.btsbot_op_gemm_gated.argtypes = [i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp]
+    L.btsbot_op_gemm_resid_ln.restype = i32
+    L.btsbot_op_gemm_resid_ln.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.btsbot_op_dwconv_ln.restype = i32
     L.btsbot_op_dwconv_ln.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     L.btsbot_op_stem.restype = i32

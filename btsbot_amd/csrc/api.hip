@@ -1810,17 +1810,32 @@ extern "C" int btsbot_op_gemm(int prec, int epi, const void* X, const void* W, c
   return launch_gemm(prec, epi, X, W, bias, gamma, resid, out, M, N, K, (hipStream_t)stream);
 }
 
-extern "C" int btsbot_op_wgrad(int prec, const float* D, const float* A, float* out, float* colsum, int M, int N, int K,
+extern "C" int btsbot_op_wgrad(int prec, const void* Dv, const void* Av, float* out, float* colsum, int M, int N, int K,
                                void* stream) {
-  if (D == nullptr || A == nullptr || out == nullptr || M < 0 || N < 1 || K < 1) {
+  if (Dv == nullptr || Av == nullptr || out == nullptr || M < 0 || N < 1 || K < 1) {
     btsbot_set_error("op_wgrad: invalid argument");
     return BTSBOT_ERR_INVALID_ARG;
   }
   hipStream_t st = (hipStream_t)stream;
   if (M == 0) return BTSBOT_OK;
+  if (prec == BTSBOT_BF16 || prec == BTSBOT_F16) {
+    // 16-bit D and A, the training step's form: slice partials in a stream-ordered scratch + the two-pass reduction
+    if ((N & 7) || (K & 7) || ((uintptr_t)Dv & 15) || ((uintptr_t)Av & 15)) {
+      btsbot_set_error("op_wgrad: N=%d K=%d must be multiples of 8 and D, A 16-byte aligned", N, K);
+      return BTSBOT_ERR_INVALID_ARG;
+    }
+    const size_t part_floats = (size_t)16 << 20;
+    void* part = nullptr;
+    HIP_TRY(hipMallocAsync(&part, part_floats * 4, st));
+    const int s = launch_wgrad16(prec, Dv, Av, out, colsum, M, N, K, K, st, reinterpret_cast<float*>(part), part_floats);
+    HIP_TRY(hipFreeAsync(part, st));
+    return s;
+  }
+  const float* D = reinterpret_cast<const float*>(Dv);
+  const float* A = reinterpret_cast<const float*>(Av);
   if (prec == BTSBOT_F32) return launch_wgrad_cs_f32(D, A, out, colsum, M, N, K, K, st);
   if (prec != BTSBOT_F16X2) {
-    btsbot_set_error("op_wgrad: precision %d (BTSBOT_F32 or BTSBOT_F16X2)", prec);
+    btsbot_set_error("op_wgrad: precision %d (BTSBOT_F32, BTSBOT_BF16, BTSBOT_F16 or BTSBOT_F16X2)", prec);
     return BTSBOT_ERR_INVALID_ARG;
   }
   // split operands as in the split training step's stem: the largest magnitudes of D and of A set their power-of-two
@@ -1841,6 +1856,53 @@ extern "C" int btsbot_op_wgrad(int prec, const float* D, const float* A, float* 
   if (s == BTSBOT_OK) s = launch_copy_amax(A, nullptr, (long)M * K, aamax, st);
   if (s == BTSBOT_OK) s = launch_wgrad_x2(D, A, out, colsum, M, N, K, K, damax, aamax, st, part, part_floats, nullptr);
   HIP_TRY(hipFreeAsync(scratch, st));
+  return s;
+}
+
+extern "C" int btsbot_op_gemm_gated(int prec, const void* X, const float* gate, int rows_per_alert, const void* W,
+                                    const float* resid, float* out, int M, int N, int K, void* stream) {
+  if (X == nullptr || gate == nullptr || W == nullptr || resid == nullptr || out == nullptr || M < 0 || N < 1 ||
+      K < 1 || rows_per_alert < 1) {
+    btsbot_set_error("op_gemm_gated: invalid argument");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (M == 0) return BTSBOT_OK;
+  if (prec != BTSBOT_F16X2)
+    return launch_gemm_gated(prec, X, gate, rows_per_alert, W, resid, out, M, N, K, st);
+  // fp32 X and W: W split into its f16 head and remainder planes here, stream-ordered (as btsbot_op_gemm does)
+  void* wsplit = nullptr;
+  HIP_TRY(hipMallocAsync(&wsplit, (size_t)N * K * 4, st));
+  const float* w = reinterpret_cast<const float*>(W);
+  int s = launch_cast(BTSBOT_F16, w, wsplit, (int64_t)N * K, st);
+  if (s == BTSBOT_OK) s = launch_rowscale_cast_lo(w, nullptr, reinterpret_cast<f16_t*>(wsplit) + (size_t)N * K, N, K, st);
+  if (s == BTSBOT_OK)
+    s = launch_gemm_x2_gated(reinterpret_cast<const float*>(X), gate, rows_per_alert, wsplit, resid, out, M, N, K, st);
+  HIP_TRY(hipFreeAsync(wsplit, st));
+  return s;
+}
+
+extern "C" int btsbot_op_gemm_resid_ln(int prec, const void* X, const void* W, const float* resid, float* out, int batch,
+                                       int M, int N, int K, const float* ln_w, const float* ln_b, void* ln_out,
+                                       void* stream) {
+  if (X == nullptr || W == nullptr || resid == nullptr || out == nullptr || batch < 1 || M < 1 || N < 1 || K < 1 ||
+      (ln_out != nullptr && (ln_w == nullptr || ln_b == nullptr))) {
+    btsbot_set_error("op_gemm_resid_ln: invalid argument");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // the kernel reads a bias and a layer scale; this form has neither: zeros and ones, stream-ordered
+  void* ones = nullptr;
+  HIP_TRY(hipMallocAsync(&ones, (size_t)N * 8, st));
+  float* zero_bias = reinterpret_cast<float*>(ones);
+  float* one_gamma = zero_bias + N;
+  int s = BTSBOT_OK;
+  if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(zero_bias), 0, N, st) != hipSuccess ||
+      hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(one_gamma), 0x3f800000, N, st) != hipSuccess)   // 1.0f
+    s = BTSBOT_ERR_HIP;
+  if (s == BTSBOT_OK)
+    s = launch_gemm2_batched_resid(prec, X, W, zero_bias, one_gamma, resid, out, batch, M, N, K, st, ln_w, ln_b, ln_out);
+  HIP_TRY(hipFreeAsync(ones, st));
   return s;
 }
 

@@ -58,10 +58,12 @@ def gemm(x, w, bias, epi="bias", gamma=None, resid=None, precision="f32", out=No
 
 def wgrad(d, a, out=None, colsum=None, precision="f32"):
     """Filter gradient of a 1x1 convolution: out[n][k] += sum_m d[m][n] a[m][k] (and colsum[n] += sum_m d[m][n] when
-    colsum is given).  d [M,N], a [M,K] fp32; out [N,K] fp32 (zeros when None).  precision 'f32' (the fp32 training
-    kernel) or 'f16x2' (the split training form: N, K multiples of 16)."""
-    assert precision in ("f32", "f16x2"), precision
-    assert d.dtype == torch.float32 and a.dtype == torch.float32 and d.is_contiguous() and a.is_contiguous()
+    colsum is given).  d [M,N], a [M,K] in the precision's dtype (fp32 for 'f16x2'); out [N,K] fp32 (zeros when None).
+    precision 'f32' (the fp32 training kernel), 'bf16' / 'f16' (the 16-bit training kernel: N, K multiples of 8) or
+    'f16x2' (the split training form: N, K multiples of 16)."""
+    assert precision in ("f32", "bf16", "f16", "f16x2"), precision
+    dt = torch.float32 if precision == "f16x2" else _DT[precision]
+    assert d.dtype == dt and a.dtype == dt and d.is_contiguous() and a.is_contiguous()
     M, N = d.shape
     K = a.shape[1]
     assert a.shape[0] == M
@@ -74,6 +76,47 @@ def wgrad(d, a, out=None, colsum=None, precision="f32"):
         _lib.check(_lib.lib().btsbot_op_wgrad(_lib.PRECISION[precision], _p(d), _p(a), _p(out), _p(colsum), M, N, K,
                                               _stream(d)), "btsbot_op_wgrad")
     return out
+
+
+def gemm_gated(x, gate, rows_per_alert, w, resid, precision="f32", out=None):
+    """out (fp32) = resid + (x[m][k] * gate[m // rows_per_alert][k]) @ w^T: the squeeze-excite gated 1x1 convolution of
+    a MaxViT MBConv block.  x [M,K], w [N,K] in the precision's dtype (fp32 for 'f16x2'); gate [ceil(M / rows), K] and
+    resid [M,N] fp32.  out may be resid itself (in place)."""
+    dt = torch.float32 if precision == "f16x2" else _DT[precision]
+    assert x.dtype == dt and w.dtype == dt and x.is_contiguous() and w.is_contiguous()
+    M, K = x.shape
+    N = w.shape[0]
+    assert gate.dtype == torch.float32 and gate.is_contiguous() and gate.shape == ((M + rows_per_alert - 1) // rows_per_alert, K)
+    assert resid.dtype == torch.float32 and resid.shape == (M, N) and resid.is_contiguous()
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.shape == (M, N) and out.is_contiguous()
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().btsbot_op_gemm_gated(_lib.PRECISION[precision], _p(x), _p(gate), rows_per_alert, _p(w),
+                                                   _p(resid), _p(out), M, N, K, _stream(x)), "btsbot_op_gemm_gated")
+    return out
+
+
+def gemm_resid_ln(x, w, resid, ln_w=None, ln_b=None, precision="bf16", out=None):
+    """The batched residual GEMM of the 16-bit MaxViT forward: out[b] (fp32) = resid[b] + x[b] @ w[b]^T for x [B,M,K],
+    w [B,N,K] ('bf16' / 'f16'), resid [B,M,N] fp32 (out may be resid itself).  With ln_w / ln_b (N 64 or 128) it also
+    returns LayerNorm_N(out) * ln_w + ln_b (eps 1e-6) in the precision's dtype: (out, ln_out); else out."""
+    dt = _DT[precision]
+    assert precision in ("bf16", "f16") and x.dtype == dt and w.dtype == dt and x.is_contiguous() and w.is_contiguous()
+    B, M, K = x.shape
+    N = w.shape[1]
+    assert w.shape == (B, N, K) and resid.dtype == torch.float32 and resid.shape == (B, M, N) and resid.is_contiguous()
+    if out is None:
+        out = torch.empty(B, M, N, dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.shape == (B, M, N) and out.is_contiguous()
+    ln_out = None
+    if ln_w is not None:
+        ln_out = torch.empty(B, M, N, dtype=dt, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().btsbot_op_gemm_resid_ln(_lib.PRECISION[precision], _p(x), _p(w), _p(resid), _p(out), B, M,
+                                                      N, K, _p(ln_w), _p(ln_b), _p(ln_out), _stream(x)),
+                   "btsbot_op_gemm_resid_ln")
+    return out if ln_out is None else (out, ln_out)
 
 
 def dwconv_ln(x, w, bias, ln_w, ln_b, precision="f32"):

@@ -310,12 +310,28 @@ int btsbot_op_gemm(int prec, int epi, const void* X, const void* W, const float*
  *   (BTSBOT_F16X2, epi 4 / 5: X is a gradient -- scaled by a power of two from its largest magnitude before the split,
  *   as in the split training step). */
 /* Filter gradient of a 1x1 convolution: out[n][k] += sum_m D[m][n] A[m][k], colsum[n] += sum_m D[m][n] (colsum may be
- * NULL).  D [M][N], A [M][K] fp32, pixel-major; out [N][K] fp32.  prec BTSBOT_F32: the fp32 training kernel;
+ * NULL).  D [M][N], A [M][K] pixel-major, fp32 unless said otherwise; out [N][K] fp32.  prec BTSBOT_F32: the fp32
+ * training kernel; BTSBOT_BF16 / BTSBOT_F16: D and A of that type, the 16-bit training step's kernel (N, K multiples
+ * of 8, D and A 16-byte aligned; slice partials in a stream-ordered scratch of 64 MB, then the two-pass reduction);
  * BTSBOT_F16X2: the split form of the split training step (N, K multiples of 16; D and A each scaled by a power of two
  * from its largest magnitude, as the step's stem does; slice partials added in a fixed order; a stream-ordered scratch
  * of 64 MB). */
-int btsbot_op_wgrad(int prec, const float* D, const float* A, float* out, float* colsum, int M, int N, int K,
+int btsbot_op_wgrad(int prec, const void* D, const void* A, float* out, float* colsum, int M, int N, int K,
                     void* stream);
+/* MaxViT MBConv's last 1x1 convolution with the squeeze-excite gate folded into its A operand:
+ *   out (f32) [M,N] = resid + (X[m][k] * gate[m / rows_per_alert][k]) . W[N,K]^T      (in place allowed)
+ * X, W prec-typed (BTSBOT_F16X2: fp32, W split into f16 head + remainder planes inside the call, as btsbot_op_gemm);
+ * gate [ceil(M / rows_per_alert)][K] f32.  In the 16-bit modes X * gate is rounded to prec before the product.
+ * K % (16/sizeof(prec)) == 0 (8 for BTSBOT_F16X2), N % 4 == 0. */
+int btsbot_op_gemm_gated(int prec, const void* X, const float* gate, int rows_per_alert, const void* W,
+                         const float* resid, float* out, int M, int N, int K, void* stream);
+/* The batched residual GEMM of the 16-bit MaxViT forward (prec BTSBOT_BF16 / BTSBOT_F16), `batch` problems of M rows:
+ *   out_b (f32) [M,N] = resid_b + X_b[M,K] . W_b[N,K]^T      (problem b at X + b*M*K, W + b*N*K, resid / out + b*M*N;
+ *                                                           in place allowed)
+ * and, with ln_out != NULL, the next LayerNorm fused: ln_out_b (prec) = LayerNorm_N(out_b row) * ln_w + ln_b, eps 1e-6
+ * (N 64 or 128).  K % 64 == 0, N % 64 == 0. */
+int btsbot_op_gemm_resid_ln(int prec, const void* X, const void* W, const float* resid, float* out, int batch, int M,
+                            int N, int K, const float* ln_w, const float* ln_b, void* ln_out, void* stream);
 /* K2+K3: depthwise 7x7 p3 + bias + LayerNorm(C, eps 1e-6).  x [B,HW,HW,C] f32 NHWC ->
  * xn [B,HW,HW,C] (prec).  w_tap_major is [49][C] f32.  (C,HW) in {(64,15),(128,7),(256,3),(512,1),
  * (80,15),(160,7),(320,3),(640,1)}.  Arithmetic: fp32 FMAs on the fp32 map, two-pass variance -- EXCEPT the 15x15 maps

@@ -56,19 +56,11 @@ int64_t add_param(btsbot_ctx* h, const std::string& name, std::initializer_list<
   return r.off;
 }
 
-size_t bump(size_t& cur, size_t bytes) {
-  const size_t o = cur;
-  cur += (bytes + 255) / 256 * 256;
-  return o;
-}
-
 int build_tables(btsbot_ctx* h) {
   const btsbot_config& c = h->cfg;
-  size_t cur = 0;
-  const int esz = h->esz();
   char buf[96];
   if (h->has_image && h->is_maxvit) {
-    maxvit_build_tables(h, &cur);
+    maxvit_build_tables(h, &h->extra_fixed);   // (its operand images too; every other handle's: pack.hip)
   } else if (h->has_image) {
     const int c0 = c.dims[0];
     h->stem_w = add_param(h, "stem.0.weight", {c0, 3, 4, 4});
@@ -76,11 +68,6 @@ int build_tables(btsbot_ctx* h) {
     h->stem_lnw = add_param(h, "stem.1.weight", {c0});
     h->stem_lnb = add_param(h, "stem.1.bias", {c0});
     h->stage0 = stage0_supported(h->prec_s01(), c0) && c.depths[0] == 2;
-    h->p_stem16 = bump(cur, (size_t)c0 * 48 * esz);   // stem filter in the operand type
-    if (h->x2 && h->stage0) {
-      h->p_x2_stem = bump(cur, (size_t)c0 * 48 * 2);
-      h->p_x2_stemlo = bump(cur, (size_t)c0 * 48 * 2);
-    }
     h->stage1 = stage1_supported(h->prec_s01(), c.dims[1], c.dims[2]) && c.depths[1] == 2;
     h->stage2p = stage2p_supported(h->prec_tail(), c.dims[2], c.dims[3], c.depths[2]);
     h->stage3 = stage3_supported(h->prec_tail(), c.dims[3], c.depths[3]);
@@ -95,16 +82,6 @@ int build_tables(btsbot_ctx* h) {
         h->down[i].ln_b = add_param(h, p + "0.bias", {cin});
         h->down[i].w = add_param(h, p + "1.weight", {ch, cin, 2, 2});
         h->down[i].b = add_param(h, p + "1.bias", {ch});
-        h->down[i].p_w = bump(cur, (size_t)ch * cin * 4 * esz);
-        h->down[i].p_wt = bump(cur, (size_t)ch * cin * 4 * esz);
-        if ((i == 3 && h->stage2p) || (i == 2 && h->stage1)) {
-          h->down[i].p_wp = bump(cur, (size_t)ch * cin * 4 * esz);
-          h->down[i].p_scale = bump(cur, 64);
-        }
-        if (i == 1 && h->x2 && h->stage0) {
-          h->down[i].p_x2_w = bump(cur, (size_t)ch * cin * 4 * 2);
-          h->down[i].p_x2_wlo = bump(cur, (size_t)ch * cin * 4 * 2);
-        }
       }
       for (int j = 0; j < c.depths[i]; ++j) {
         snprintf(buf, sizeof buf, "stages.%d.blocks.%d.", i, j);
@@ -119,33 +96,7 @@ int build_tables(btsbot_ctx* h) {
         b.fc1_b = add_param(h, p + "mlp.fc1.bias", {4 * ch});
         b.fc2_w = add_param(h, p + "mlp.fc2.weight", {ch, 4 * ch, 1, 1});
         b.fc2_b = add_param(h, p + "mlp.fc2.bias", {ch});
-        b.p_dw = bump(cur, (size_t)49 * ch * 4);
-        b.p_fc1 = bump(cur, (size_t)4 * ch * ch * esz);
-        b.p_fc2 = bump(cur, (size_t)4 * ch * ch * esz);
-        b.p_fc2g = bump(cur, (size_t)4 * ch * ch * esz);
-        b.p_s0par = (i == 0 && ch == 64) ? bump(cur, s0par_bytes())
-                    : (i == 1 && ch == 128 && (c.precision != BTSBOT_F32 || h->x2)) ? bump(cur, s1par_bytes()) : 0;
-        if (!h->x2 && s2mlp_bwd_supported(c.precision, ch)) {
-          b.p_w1tp = bump(cur, (size_t)4 * ch * ch * 2);
-          b.p_w2tp = bump(cur, (size_t)4 * ch * ch * 2);
-        }
-        if (!h->x2 && c.precision != BTSBOT_F32 && ((i == 0 && ch == 64) || (i == 1 && ch == 128)))
-          b.p_s0par_t = bump(cur, i == 0 ? s0par_bytes() : s1par_bytes());
-        if (h->x2 && ((i == 0 && h->stage0) || (i == 1 && h->stage1))) {
-          b.p_x2_w1 = bump(cur, (size_t)4 * ch * ch * 2);
-          b.p_x2_w2g = bump(cur, (size_t)4 * ch * ch * 2);
-          b.p_x2_w1lo = bump(cur, (size_t)4 * ch * ch * 2);
-          b.p_x2_w2glo = bump(cur, (size_t)4 * ch * ch * 2);
-        }
-        if ((i == 2 && h->stage2p) || (i == 3 && h->stage3)) {
-          b.p_w1p = bump(cur, (size_t)4 * ch * ch * esz);
-          b.p_w2p = bump(cur, (size_t)4 * ch * ch * esz);
-          b.p_scales = bump(cur, 64);
-        }
-        b.p_fc1t = bump(cur, (size_t)4 * ch * ch * esz);
-        b.p_fc2t = bump(cur, (size_t)4 * ch * ch * esz);
         b.fused = fused_mlp_supported(c.precision, ch);
-        b.p_fused = b.fused ? bump(cur, fused_mlp_packed_bytes(ch)) : 0;
         h->blocks[i].push_back(b);
       }
     }
@@ -164,28 +115,15 @@ int build_tables(btsbot_ctx* h) {
     h->m1_b = add_param(h, "meta.1.bias", {c.meta_fc1});
     h->m2_w = add_param(h, "meta.4.weight", {c.meta_fc2, c.meta_fc1});
     h->m2_b = add_param(h, "meta.4.bias", {c.meta_fc2});
-    h->p_m1 = bump(cur, (size_t)c.meta_fc1 * c.n_meta * 4);
-    h->p_m2 = bump(cur, (size_t)c.meta_fc2 * c.meta_fc1 * 4);
-    h->p_bn_scale = bump(cur, (size_t)c.n_meta * 4);
-    h->p_bn_shift = bump(cur, (size_t)c.n_meta * 4);
   }
   for (int i = 0; i < h->n_comb; ++i) {
     snprintf(buf, sizeof buf, "comb.%d.", i);
     std::string p(buf);
     h->comb_w[i] = add_param(h, p + "weight", {h->comb_dims[i + 1], h->comb_dims[i]});
     h->comb_b[i] = add_param(h, p + "bias", {h->comb_dims[i + 1]});
-    h->p_comb[i] = bump(cur, (size_t)h->comb_dims[i + 1] * h->comb_dims[i] * 4);
   }
   h->head16 = head16_supported(h->prec_head(), h->has_image ? c.dims[3] : 0, h->has_meta ? c.n_meta : 0, c.meta_fc1, c.meta_fc2,
                                h->n_comb, h->comb_dims);
-  if (h->head16) {
-    if (h->has_meta) {
-      h->p_m1h = bump(cur, head16_packed_bytes(c.meta_fc1, c.n_meta));
-      h->p_m2h = bump(cur, head16_packed_bytes(c.meta_fc2, c.meta_fc1));
-    }
-    for (int i = 0; i < h->n_comb; ++i) h->p_combh[i] = bump(cur, head16_packed_bytes(h->comb_dims[i + 1], h->comb_dims[i]));
-  }
-  h->extra_bytes = cur;
   // gradient buckets, in the order the backward pass completes them
   if (h->has_image && !h->is_maxvit) {
     const int64_t s3 = h->down[3].ln_w, s2 = h->down[2].ln_w;
@@ -358,6 +296,10 @@ extern "C" int btsbot_create(const btsbot_config* cfg, btsbot_handle* out) {
   h->use_stem16 = !env_on("BTSBOT_AMD_NO_STEM16");
   // (the deterministic reductions cover the ConvNeXt training step only: same rule as btsbot_set_option)
   h->deterministic = env_on("BTSBOT_AMD_DETERMINISTIC") && !h->is_maxvit;
+  if (pack_layout(h) != BTSBOT_OK) {
+    delete h;
+    return BTSBOT_ERR_STATE;
+  }
   *out = h;
   return BTSBOT_OK;
 }
@@ -366,9 +308,7 @@ extern "C" int btsbot_destroy(btsbot_handle h) {
   if (h == nullptr) return BTSBOT_OK;
   if (h->mirror) (void)hipFree(h->mirror);
   if (h->extra) (void)hipFree(h->extra);
-  for (void* t : h->pack_jobs)
-    if (t) (void)hipFree(t);
-  if (h->split_jobs) (void)hipFree(h->split_jobs);
+  pack_release(h);
   if (h->ws && h->ws_owned) (void)hipFree(h->ws);
   if (h->tcache) (void)hipFree(h->tcache);
   if (h->bbcache) (void)hipFree(h->bbcache);
@@ -382,7 +322,6 @@ extern "C" int btsbot_destroy(btsbot_handle h) {
   for (hipEvent_t e : h->bucket_ev)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->side_ev) (void)hipEventDestroy(e);
-  if (h->pack_early_ev) (void)hipEventDestroy(h->pack_early_ev);
   bool side_cached = false;
   for (const SidePick& p : h->side_cache) {
     side_cached = side_cached || p.side == h->side;
@@ -419,274 +358,12 @@ extern "C" int btsbot_param_info_at(btsbot_handle h, int index, btsbot_param_inf
     if (_s != BTSBOT_OK) return _s; \
   } while (0)
 
-static int pack_impl(btsbot_handle h, const float* master, void* stream, bool train_only);
-int side_fork(btsbot_ctx* h, hipStream_t st, hipStream_t* sd);
-int side_join(btsbot_ctx* h, hipStream_t st);
-int pack_sync(btsbot_ctx* h, hipStream_t st) {
-  if (!h->pack_on_side) return BTSBOT_OK;
-  h->pack_on_side = false;
-  h->pack_early = false;
-  return side_join(h, st);
-}
-// `st` waits for the stem / stage-0 operand images only (the re-pack queues them first and records an event behind them);
-// the rest of the re-pack runs on under the stage-0 megakernel and pack_sync() joins it in front of stage 1
-int pack_sync_early(btsbot_ctx* h, hipStream_t st) {
-  if (!h->pack_on_side) return BTSBOT_OK;
-  if (!h->pack_early) return pack_sync(h, st);
-  HIP_TRY(hipStreamWaitEvent(st, h->pack_early_ev, 0));
-  return BTSBOT_OK;
-}
-
 extern "C" int btsbot_pack_params(btsbot_handle h, const float* master, void* stream) {
-  return pack_impl(h, master, stream, false);
+  return pack_params(h, master, (hipStream_t)stream, false);
 }
 
 extern "C" int btsbot_pack_params_train(btsbot_handle h, const float* master, void* stream) {
-  return pack_impl(h, master, stream, true);
-}
-
-// train_only: skip the operand images only the fused inference kernels read (gamma-scaled fc2 filters and
-// their chunk-major form, the megakernels' parameter images, the fused-MLP image): the per-op training
-// schedule (backbone_train.hip) and the backward never touch them, and they are re-packed after every
-// optimiser step
-static int pack_impl(btsbot_handle h, const float* master, void* stream, bool train_only) {
-  if (h == nullptr || master == nullptr) {
-    btsbot_set_error("pack_params: NULL argument");
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const btsbot_config& c = h->cfg;
-  if (h->mirror == nullptr) {  // first pack on this handle: allocate the operand arenas
-    HIP_TRY(hipMalloc(&h->mirror, (size_t)h->total_floats * 4));
-    HIP_TRY(hipMalloc(&h->extra, h->extra_bytes > 0 ? h->extra_bytes : 256));
-  }
-  TRY(pack_sync(h, st));   // (a pack nobody consumed yet still reads the mirror on the side stream)
-  TRY(launch_copy_f32(h->mirror, master, (size_t)h->total_floats, st));
-  const float* m = h->mirror;
-  if (train_only && h->has_image && !h->is_maxvit && h->use_side && h->side != nullptr) {
-    hipStream_t sp = st;
-    TRY(side_fork(h, st, &sp));   // behind the mirror copy
-    st = sp;
-    h->pack_on_side = true;
-  }
-  // The plain element maps (casts, transposes, the downsample re-orderings) run as ONE launch over a job
-  // table built on the first pack of each kind: mirror and extra never move, so the table is static.
-  // BTSBOT_AMD_PACK_UNBATCHED=1 keeps one launch per operand (A/B and parity).
-  static const bool unbatched = env_on("BTSBOT_AMD_PACK_UNBATCHED");
-  const int kind = train_only ? 1 : 0;
-  std::vector<PackJob> jobs, jobs_early;
-  const bool build = !unbatched && h->pack_jobs[kind] == nullptr;
-  // training re-pack with the stage-0 megakernel in the forward (s0_train): the jobs it reads go into a table of their
-  // own that is launched first ([2]); `early_now` marks them while the tables are built
-  const bool split = train_only && h->s0_train && !unbatched && h->has_image && !h->is_maxvit;
-  bool early_now = false;
-  int status = BTSBOT_OK;
-  auto job = [&](int op, const float* src, const float* scale, void* dst, int R, int Cc) {
-    if (status != BTSBOT_OK) return;
-    if (!unbatched) {
-      if (build) (split && early_now ? jobs_early : jobs).push_back(PackJob{src, scale, dst, R, Cc, op, 0});
-      return;
-    }
-    switch (op) {
-      case PACK_CAST: status = launch_cast(c.precision, src, dst, R, st); break;
-      case PACK_TRANSPOSE_F32: status = launch_transpose_f32(src, reinterpret_cast<float*>(dst), R, Cc, st); break;
-      case PACK_TRANSPOSE_CAST: status = launch_transpose_cast(c.precision, src, scale, dst, R, Cc, st); break;
-      case PACK_DOWN: status = launch_pack_down(c.precision, src, dst, R, Cc, st); break;
-      case PACK_TFRAG: break;   // (unbatched: launch_pack_frag16 behind the transposes, below)
-      case PACK_FRAG:
-      case PACK_FRAG_DOWN: break;   // (unbatched: launch_pack_s2p, below)
-      default: status = launch_pack_down_t(c.precision, src, dst, R, Cc, st);
-    }
-  };
-  const bool convnext = h->has_image && !h->is_maxvit;
-  if (convnext) {
-    early_now = true;
-    if (h->stage0 || h->train_packs)
-      job(PACK_CAST, m + h->stem_w, nullptr, h->extra + h->p_stem16, c.dims[0] * 48, 1);
-    for (int i = 0; i < 4; ++i) {
-      const int ch = c.dims[i];
-      early_now = i <= 1;
-      if (i > 0) {
-        if (train_only && i == 3 && h->s2p_train)
-          job(PACK_FRAG_DOWN, m + h->down[i].w, nullptr, h->extra + h->down[i].p_wp, ch, c.dims[i - 1]);
-        job(PACK_DOWN, m + h->down[i].w, nullptr, h->extra + h->down[i].p_w, ch, c.dims[i - 1]);
-        early_now = false;   // (stage 1's own jobs and the dgrad transposes are not read by the stage-0 kernel)
-        if (h->train_packs)
-          job(PACK_DOWN_T, m + h->down[i].w, nullptr, h->extra + h->down[i].p_wt, ch, c.dims[i - 1]);
-      }
-      for (const BlockPk& b : h->blocks[i]) {
-        early_now = i == 0;
-        job(PACK_TRANSPOSE_F32, m + b.dw_w, nullptr, h->extra + b.p_dw, ch, 49);
-        // (training re-pack with stage 2's forward through stage2p_kernel: its filters as MFMA fragments ride in the table,
-        //  beside the row-major images the per-op forward reads -- large batches take that one, backbone_train.hip)
-        const bool s2frag = train_only && i == 2 && h->s2p_train;
-        job(PACK_CAST, m + b.fc1_w, nullptr, h->extra + b.p_fc1, 4 * ch * ch, 1);
-        early_now = false;
-        job(PACK_CAST, m + b.fc2_w, nullptr, h->extra + b.p_fc2, 4 * ch * ch, 1);
-        if (s2frag) {
-          job(PACK_FRAG, m + b.fc1_w, nullptr, h->extra + b.p_w1p, 4 * ch, ch);
-          job(PACK_FRAG, m + b.fc2_w, m + b.gamma, h->extra + b.p_w2p, ch, 4 * ch);
-        }
-        if (h->train_packs) {   // W1^T [C][4C] and (diag(gamma) W2)^T [4C][C] for the dgrad GEMMs
-          job(PACK_TRANSPOSE_CAST, m + b.fc1_w, nullptr, h->extra + b.p_fc1t, 4 * ch, ch);
-          job(PACK_TRANSPOSE_CAST, m + b.fc2_w, m + b.gamma, h->extra + b.p_fc2t, ch, 4 * ch);
-          if (b.p_w1tp != 0 && h->s2mlp) {   // the same two as MFMA A fragments for s2mlp_bwd_kernel
-            job(PACK_TFRAG, m + b.fc1_w, nullptr, h->extra + b.p_w1tp, 4 * ch, ch);
-            job(PACK_TFRAG, m + b.fc2_w, m + b.gamma, h->extra + b.p_w2tp, ch, 4 * ch);
-          }
-        }
-      }
-    }
-  }
-  if (h->has_meta) {
-    job(PACK_TRANSPOSE_F32, m + h->m1_w, nullptr, h->extra + h->p_m1, c.meta_fc1, c.n_meta);
-    job(PACK_TRANSPOSE_F32, m + h->m2_w, nullptr, h->extra + h->p_m2, c.meta_fc2, c.meta_fc1);
-  }
-  for (int i = 0; i < h->n_comb; ++i)
-    job(PACK_TRANSPOSE_F32, m + h->comb_w[i], nullptr, h->extra + h->p_comb[i], h->comb_dims[i + 1],
-        h->comb_dims[i]);
-  early_now = false;
-  TRY(status);
-  auto upload = [&](std::vector<PackJob>& v, int slot) -> int {
-    if (v.empty()) return BTSBOT_OK;
-    int nb = 0;
-    for (PackJob& j : v) {
-      j.blk0 = nb;
-      nb += pack_job_blocks(j);
-    }
-    HIP_TRY(hipMalloc(&h->pack_jobs[slot], v.size() * sizeof(PackJob)));
-    HIP_TRY(hipMemcpy(h->pack_jobs[slot], v.data(), v.size() * sizeof(PackJob), hipMemcpyHostToDevice));
-    h->pack_njobs[slot] = (int)v.size();
-    h->pack_blocks[slot] = nb;
-    return BTSBOT_OK;
-  };
-  if (build) {
-    TRY(upload(jobs, kind));
-    if (split) TRY(upload(jobs_early, 2));
-  }
-  h->pack_early = false;
-  if (split && h->pack_jobs[2] != nullptr) {
-    // what the stage-0 megakernel reads, first: its table, then the stage-0 blocks' gamma-scaled fc2 filters and parameter
-    // images (they read the tap-major taps the table wrote), then the event pack_sync_early() waits for
-    TRY(launch_pack_jobs(c.precision, reinterpret_cast<const PackJob*>(h->pack_jobs[2]), h->pack_njobs[2], h->pack_blocks[2], st));
-    for (const BlockPk& b : h->blocks[0]) {
-      const int ch = c.dims[0];
-      TRY(launch_rowscale_cast(c.precision, m + b.fc2_w, m + b.gamma, h->extra + b.p_fc2g, ch, 4 * ch, st));
-      TRY(launch_pack_s0par(BTSBOT_F16, reinterpret_cast<const float*>(h->extra + b.p_dw), m + b.dw_b, m + b.ln_w, m + b.ln_b,
-                            m + b.fc1_b, m + b.fc2_b, m + b.gamma, h->extra + b.p_s0par_t, st));
-    }
-    if (h->pack_early_ev == nullptr) HIP_TRY(hipEventCreateWithFlags(&h->pack_early_ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(h->pack_early_ev, st));
-    h->pack_early = true;
-  }
-  if (!unbatched)
-    TRY(launch_pack_jobs(c.precision, reinterpret_cast<const PackJob*>(h->pack_jobs[kind]), h->pack_njobs[kind],
-                         h->pack_blocks[kind], st));
-  // ... then the images that read the packed taps or have maps of their own
-  if (h->has_image && h->is_maxvit) {
-    TRY(maxvit_pack(h, st));
-  } else if (h->has_image) {
-    for (int i = 0; i < 4; ++i) {
-      const int ch = c.dims[i];
-      for (const BlockPk& b : h->blocks[i]) {
-        if (!train_only || (i == 0 && h->s0_train && !h->pack_early) || (i == 1 && h->s1_train))
-          TRY(launch_rowscale_cast(c.precision, m + b.fc2_w, m + b.gamma, h->extra + b.p_fc2g, ch,
-                                   4 * ch, st));
-        if (i == 2 && h->stage2p && (!train_only || (h->s2p_train && unbatched))) {
-          float* sc = reinterpret_cast<float*>(h->extra + b.p_scales);
-          TRY(launch_pack_s2p(h->prec_tail(), m + b.fc1_w, nullptr, h->extra + b.p_w1p, 4 * ch, ch, 0, 0, sc, st));
-          TRY(launch_pack_s2p(h->prec_tail(), m + b.fc2_w, m + b.gamma, h->extra + b.p_w2p, ch, 4 * ch, 0, 0, sc + 2, st));
-        }
-        if (i == 3 && h->stage3 && !train_only) {
-          float* sc = reinterpret_cast<float*>(h->extra + b.p_scales);
-          TRY(launch_pack_s3(h->prec_tail(), m + b.fc1_w, nullptr, h->extra + b.p_w1p, 4 * ch, ch, 1, sc, st));
-          TRY(launch_pack_s3(h->prec_tail(), m + b.fc2_w, m + b.gamma, h->extra + b.p_w2p, ch, 4 * ch, 0, sc + 2, st));
-        }
-        if (i == 1 && ch == 128 && (c.precision != BTSBOT_F32 || (h->x2 && h->stage1)) && !train_only)
-          TRY(launch_pack_s1par(h->prec_s01(), reinterpret_cast<const float*>(h->extra + b.p_dw),
-                                m + b.dw_b, m + b.ln_w, m + b.ln_b, h->extra + b.p_s0par, st));
-        if (i == 0 && ch == 64 && (c.precision != BTSBOT_F32 || (h->x2 && h->stage0)) && !train_only)   // (after the tap-major transpose above: same stream)
-          TRY(launch_pack_s0par(h->prec_s01(), reinterpret_cast<const float*>(h->extra + b.p_dw), m + b.dw_b,
-                                m + b.ln_w, m + b.ln_b, m + b.fc1_b, m + b.fc2_b, m + b.gamma,
-                                h->extra + b.p_s0par, st));
-        // (the unbatched re-pack only: the job table writes these itself)
-        if (b.p_w1tp != 0 && h->train_packs && h->s2mlp && unbatched) {
-          TRY(launch_pack_frag16(h->extra + b.p_fc2t, h->extra + b.p_w2tp, 4 * ch, ch, st));
-          TRY(launch_pack_frag16(h->extra + b.p_fc1t, h->extra + b.p_w1tp, ch, 4 * ch, st));
-        }
-        // the keeping forms' images (f16 taps), in the full pack too: the first training forward follows one
-        if (i == 1 && b.p_s0par_t != 0 && h->s1_train && h->train_packs)
-          TRY(launch_pack_s1par(BTSBOT_F16, reinterpret_cast<const float*>(h->extra + b.p_dw), m + b.dw_b, m + b.ln_w, m + b.ln_b,
-                                h->extra + b.p_s0par_t, st));
-        if (i == 0 && b.p_s0par_t != 0 && h->s0_train && h->train_packs && !h->pack_early)
-          TRY(launch_pack_s0par(BTSBOT_F16, reinterpret_cast<const float*>(h->extra + b.p_dw), m + b.dw_b, m + b.ln_w, m + b.ln_b,
-                                m + b.fc1_b, m + b.fc2_b, m + b.gamma, h->extra + b.p_s0par_t, st));
-        if (b.p_x2_w1 != 0 && !train_only) {   // split mode, stages 0-1: the pointwise filters as f16 heads + remainders
-          TRY(launch_cast(BTSBOT_F16, m + b.fc1_w, h->extra + b.p_x2_w1, (int64_t)4 * ch * ch, st));
-          TRY(launch_rowscale_cast(BTSBOT_F16, m + b.fc2_w, m + b.gamma, h->extra + b.p_x2_w2g, ch, 4 * ch, st));
-          TRY(launch_rowscale_cast_lo(m + b.fc1_w, nullptr, h->extra + b.p_x2_w1lo, 4 * ch, ch, st));
-          TRY(launch_rowscale_cast_lo(m + b.fc2_w, m + b.gamma, h->extra + b.p_x2_w2glo, ch, 4 * ch, st));
-        }
-        // (the training forward of the blocks whose backward is mlp_bwd_kernel runs the fused MLP too)
-        if (b.fused && (!train_only || h->mlp_fused(ch)))
-          TRY(launch_pack_fused_mlp(c.precision, ch, m + b.fc1_w, m + b.fc2_w,
-                                    h->extra + b.p_fused, st));
-      }
-    }
-  }
-  if (convnext && h->x2 && h->stage0 && !train_only) {
-    TRY(launch_cast(BTSBOT_F16, m + h->stem_w, h->extra + h->p_x2_stem, (int64_t)c.dims[0] * 48, st));
-    TRY(launch_rowscale_cast_lo(m + h->stem_w, nullptr, h->extra + h->p_x2_stemlo, c.dims[0], 48, st));
-    TRY(launch_pack_down_split(m + h->down[1].w, h->extra + h->down[1].p_x2_w, h->extra + h->down[1].p_x2_wlo, c.dims[1],
-                               c.dims[0], st));
-  }
-  if (convnext && h->train_split && h->train_packs) {
-    // split training: the f16 head + remainder planes of the fp32 images packed above (same stream: behind them), one launch
-    if (h->split_jobs == nullptr) {
-      std::vector<SplitJob> sj;
-      auto add = [&](size_t src, size_t dst, long n) {
-        sj.push_back(SplitJob{reinterpret_cast<const float*>(h->extra + src), h->extra + dst, n});
-      };
-      for (int i = 0; i < 4; ++i) {
-        const long ch = c.dims[i];
-        if (i > 0) {
-          add(h->down[i].p_w, h->down[i].p_s_w, ch * c.dims[i - 1] * 4);
-          add(h->down[i].p_wt, h->down[i].p_s_wt, ch * c.dims[i - 1] * 4);
-        }
-        for (const BlockPk& b : h->blocks[i]) {
-          add(b.p_fc1, b.p_s_fc1, 4 * ch * ch);
-          add(b.p_fc2, b.p_s_fc2, 4 * ch * ch);
-          add(b.p_fc1t, b.p_s_fc1t, 4 * ch * ch);
-          add(b.p_fc2t, b.p_s_fc2t, 4 * ch * ch);
-        }
-      }
-      HIP_TRY(hipMalloc(&h->split_jobs, sj.size() * sizeof(SplitJob)));
-      HIP_TRY(hipMemcpy(h->split_jobs, sj.data(), sj.size() * sizeof(SplitJob), hipMemcpyHostToDevice));
-      h->split_njobs = (int)sj.size();
-    }
-    TRY(launch_split_jobs(reinterpret_cast<const SplitJob*>(h->split_jobs), h->split_njobs, st));
-  }
-  if (convnext && h->stage1 && (!train_only || h->s1_train))
-    TRY(launch_pack_frag32(h->prec_s01(), m + h->down[2].w, h->extra + h->down[2].p_wp, c.dims[2], c.dims[1], st));
-  if (convnext && h->stage2p && (!train_only || (h->s2p_train && unbatched)))
-    TRY(launch_pack_s2p(h->prec_down3(), m + h->down[3].w, nullptr, h->extra + h->down[3].p_wp, c.dims[3], 4 * c.dims[2], 1,
-                        c.dims[2], nullptr, st));
-  if (h->head16 && !train_only) {
-    if (h->has_meta) {
-      TRY(launch_pack_h16(h->prec_head(), m + h->m1_w, h->extra + h->p_m1h, c.meta_fc1, c.n_meta, st));
-      TRY(launch_pack_h16(h->prec_head(), m + h->m2_w, h->extra + h->p_m2h, c.meta_fc2, c.meta_fc1, st));
-    }
-    for (int i = 0; i < h->n_comb; ++i)
-      TRY(launch_pack_h16(h->prec_head(), m + h->comb_w[i], h->extra + h->p_combh[i], h->comb_dims[i + 1], h->comb_dims[i], st));
-  }
-  if (h->has_meta) {
-    TRY(launch_bn_fold(m + h->bn_w, m + h->bn_b, m + h->bn_rm, m + h->bn_rv,
-                       reinterpret_cast<float*>(h->extra + h->p_bn_scale),
-                       reinterpret_cast<float*>(h->extra + h->p_bn_shift), c.n_meta, st));
-  }
-  h->packed = true;
-  h->packed_full = !train_only || !h->has_image || h->is_maxvit;
-  return BTSBOT_OK;
+  return pack_params(h, master, (hipStream_t)stream, true);
 }
 
 extern "C" int64_t btsbot_workspace_bytes(btsbot_handle h, int max_chunk) {
@@ -747,26 +424,8 @@ extern "C" int btsbot_set_option(btsbot_handle h, const char* key, int value) {
                        "btsbot_pack_params* / btsbot_reserve_train()");
       return BTSBOT_ERR_STATE;
     }
-    if (value == 1 && h->blocks[0][0].p_s_fc1 == 0) {   // the split planes' slots, behind everything else in `extra`
-      size_t cur = h->extra_bytes;
-      for (int i = 0; i < 4; ++i) {
-        const size_t ch = h->cfg.dims[i];
-        if (i > 0) {
-          const size_t n = ch * h->cfg.dims[i - 1] * 4;
-          h->down[i].p_s_w = bump(cur, n * 4);
-          h->down[i].p_s_wt = bump(cur, n * 4);
-        }
-        for (BlockPk& b : h->blocks[i]) {
-          b.p_s_fc1 = bump(cur, 4 * ch * ch * 4);
-          b.p_s_fc2 = bump(cur, 4 * ch * ch * 4);
-          b.p_s_fc1t = bump(cur, 4 * ch * ch * 4);
-          b.p_s_fc2t = bump(cur, 4 * ch * ch * 4);
-        }
-      }
-      h->extra_bytes = cur;
-    }
     h->train_split = value == 1;
-    return BTSBOT_OK;
+    return pack_layout(h);   // (the split planes are images of their own)
   }
   if (strcmp(key, "query_train_split") == 0) {
     // a query: BTSBOT_OK when the training step's matrix products run on split operands
@@ -951,7 +610,8 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
   if (h->has_image) {
     const bool s0 = h->stage0 && h->use_stage0;
     if (s0) {
-      Stage0Args a = stage0_args(h, false);
+      Stage0Args a;
+      TRY(stage0_args(h, false, &a));
       a.img = img;
       a.out = x;
       a.tap_stem = h->debug ? h->taps[0] : nullptr;
@@ -986,7 +646,7 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
                                  STAGE_HW[i - 1], cin, st);
         }));
         TRY(timed(h, CAT_DOWN, st, [&] {
-          return launch_gemm(c.precision, EPI_BIAS, xn, h->extra + h->down[i].p_w,
+          return launch_gemm(c.precision, EPI_BIAS, xn, IMG(h, h->down[i].p_w),
                              m + h->down[i].b, nullptr, nullptr, x2, rows, ch, 4 * cin, st);
         }));
         float* t = x;
@@ -995,7 +655,8 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
       }
       down_done = false;
       if (i == 1 && s1) {
-        Stage1Args a = stage1_args(h, false);
+        Stage1Args a;
+        TRY(stage1_args(h, false, &a));
         a.x_in = x;
         a.out = x2;
         a.scratch = x2 + (((size_t)nb * 9 * c.dims[2] + 63) / 64) * 64;   // behind the output rows (x2 holds 225 * 64 floats per alert)
@@ -1015,7 +676,8 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
       }
       if (i == 2 && h->stage2p && h->use_s2p) {
         // every block of the 3x3 stage and the last downsample in one launch: x [nb][9][256] -> x2 [nb][512]
-        Stage2pArgs a = stage2p_args(h, false);
+        Stage2pArgs a;
+        TRY(stage2p_args(h, false, &a));
         a.x_in = x;
         a.out = x2;
         a.tap_stage = h->debug ? h->taps[3] : nullptr;
@@ -1031,7 +693,8 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
       }
       if (i == 3 && hw == 1 && h->stage3 && h->use_s3) {
         // the 1x1 stage: two launches per block, x updated in place
-        Stage3Args a = stage3_args(h);
+        Stage3Args a;
+        TRY(stage3_args(h, &a));
         a.x = x;
         a.hfrag = hb;
         a.B = nb;
@@ -1046,23 +709,22 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
       }
       for (const BlockPk& b : h->blocks[i]) {
         TRY(timed(h, CAT_DWLN, st, [&] {
-          return launch_dwconv_ln(c.precision, x,
-                                  reinterpret_cast<const float*>(h->extra + b.p_dw), m + b.dw_b,
-                                  m + b.ln_w, m + b.ln_b, xn, nb, hw, ch, st);
+          return launch_dwconv_ln(c.precision, x, IMG_F32(h, b.p_dw), m + b.dw_b, m + b.ln_w, m + b.ln_b, xn, nb, hw,
+                                  ch, st);
         }));
         if (b.fused && h->use_fused) {
           TRY(timed(h, CAT_FUSED, st, [&] {
-            return launch_fused_mlp(c.precision, ch, xn, h->extra + b.p_fused, m + b.fc1_b,
+            return launch_fused_mlp(c.precision, ch, xn, IMG(h, b.p_fused), m + b.fc1_b,
                                     m + b.fc2_b, m + b.gamma, x, rows, st);
           }));
           continue;
         }
         TRY(timed(h, CAT_FC1, st, [&] {
-          return launch_gemm(c.precision, EPI_GELU, xn, h->extra + b.p_fc1, m + b.fc1_b, nullptr,
+          return launch_gemm(c.precision, EPI_GELU, xn, IMG(h, b.p_fc1), m + b.fc1_b, nullptr,
                              nullptr, hb, rows, 4 * ch, ch, st);
         }));
         TRY(timed(h, CAT_FC2, st, [&] {
-          return launch_gemm(c.precision, EPI_RESID, hb, h->extra + b.p_fc2, m + b.fc2_b,
+          return launch_gemm(c.precision, EPI_RESID, hb, IMG(h, b.p_fc2), m + b.fc2_b,
                              m + b.gamma, x, x, rows, ch, 4 * ch, st);
         }));
       }
@@ -1091,14 +753,14 @@ static int forward_chunk(btsbot_ctx* h, const float* img, const float* meta, flo
     if (h->has_meta) {
       g.meta = meta;
       g.n_meta = c.n_meta;
-      g.bn_scale = reinterpret_cast<const float*>(h->extra + h->p_bn_scale);
-      g.bn_shift = reinterpret_cast<const float*>(h->extra + h->p_bn_shift);
-      g.m1 = H16Layer{h->extra + h->p_m1h, m + h->m1_b, c.n_meta, c.meta_fc1, h->act};
-      g.m2 = H16Layer{h->extra + h->p_m2h, m + h->m2_b, c.meta_fc1, c.meta_fc2, h->meta_trailing_act ? h->act : ACT_NONE};
+      g.bn_scale = IMG_F32(h, h->p_bn_scale);
+      g.bn_shift = IMG_F32(h, h->p_bn_shift);
+      g.m1 = H16Layer{IMG(h, h->p_m1h), m + h->m1_b, c.n_meta, c.meta_fc1, h->act};
+      g.m2 = H16Layer{IMG(h, h->p_m2h), m + h->m2_b, c.meta_fc1, c.meta_fc2, h->meta_trailing_act ? h->act : ACT_NONE};
     }
     g.n_layers = h->n_comb;
     for (int i = 0; i < h->n_comb; ++i)
-      g.comb[i] = H16Layer{h->extra + h->p_combh[i], m + h->comb_b[i], h->comb_dims[i], h->comb_dims[i + 1],
+      g.comb[i] = H16Layer{IMG(h, h->p_combh[i]), m + h->comb_b[i], h->comb_dims[i], h->comb_dims[i + 1],
                            i + 1 < h->n_comb ? h->act : ACT_NONE};
     g.logits = logits;
     g.scores = scores;
@@ -1119,11 +781,11 @@ static int forward_chunk(btsbot_ctx* h, const float* img, const float* meta, flo
     a.n_meta = c.n_meta;
     a.f1 = c.meta_fc1;
     a.f2 = c.meta_fc2;
-    a.bn_scale = reinterpret_cast<const float*>(h->extra + h->p_bn_scale);
-    a.bn_shift = reinterpret_cast<const float*>(h->extra + h->p_bn_shift);
-    a.m1_wt = reinterpret_cast<const float*>(h->extra + h->p_m1);
+    a.bn_scale = IMG_F32(h, h->p_bn_scale);
+    a.bn_shift = IMG_F32(h, h->p_bn_shift);
+    a.m1_wt = IMG_F32(h, h->p_m1);
     a.m1_b = m + h->m1_b;
-    a.m2_wt = reinterpret_cast<const float*>(h->extra + h->p_m2);
+    a.m2_wt = IMG_F32(h, h->p_m2);
     a.m2_b = m + h->m2_b;
     a.meta_act = h->act;
     a.meta_trailing_act = h->meta_trailing_act;
@@ -1131,7 +793,7 @@ static int forward_chunk(btsbot_ctx* h, const float* img, const float* meta, flo
   a.n_layers = h->n_comb;
   for (int i = 0; i <= h->n_comb; ++i) a.dims[i] = h->comb_dims[i];
   for (int i = 0; i < h->n_comb; ++i) {
-    a.wt[i] = reinterpret_cast<const float*>(h->extra + h->p_comb[i]);
+    a.wt[i] = IMG_F32(h, h->p_comb[i]);
     a.b[i] = m + h->comb_b[i];
   }
   a.comb_act = h->act;
@@ -1237,15 +899,7 @@ extern "C" int btsbot_reserve_train(btsbot_handle h, int max_batch, int with_ima
     h->bbcache_batch = max_batch;
     if (!h->train_packs && !h->is_maxvit) {      // the dgrad transposes must be packed too from now on
       h->train_packs = true;
-      h->packed = false;
-      for (int kd = 0; kd < 3; ++kd) {   // the job tables were built without the transposes: rebuild on the next pack
-        if (h->pack_jobs[kd]) {
-          HIP_TRY(hipDeviceSynchronize());
-          (void)hipFree(h->pack_jobs[kd]);
-        }
-        h->pack_jobs[kd] = nullptr;
-        h->pack_njobs[kd] = h->pack_blocks[kd] = 0;
-      }
+      TRY(pack_invalidate(h));   // (the job tables were built without the transposes)
     }
   }
   h->train_batch = 0;

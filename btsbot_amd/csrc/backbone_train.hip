@@ -190,7 +190,8 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
     // backward reads of them is written on its way (stage0.h).  It needs this step's operand images at once: the
     // re-pack queued behind the previous optimiser step runs under the mask draws and whatever precedes this call
     TRYB(pack_sync_early(h, st));
-    Stage0Args a = stage0_args(h, true);
+    Stage0Args a;
+    TRYB(stage0_args(h, true, &a));
     a.img = img;
     for (int j = 0; j < 2; ++j) {
       a.keep_d[j] = k.blk[0][j].d;
@@ -220,17 +221,18 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
       TRYB(launch_ln_patch(c.precision, k.xs[i - 1], m + h->down[i].ln_w, m + h->down[i].ln_b,
                            k.patches[i], B, STAGE_HW[i - 1], cin, st));
       if (h->train_split)
-        TRYB(launch_gemm_x2_train(EPI_BIAS, reinterpret_cast<const float*>(k.patches[i]), h->extra + h->down[i].p_s_w,
+        TRYB(launch_gemm_x2_train(EPI_BIAS, reinterpret_cast<const float*>(k.patches[i]), IMG(h, h->down[i].p_s_w),
                                   m + h->down[i].b, nullptr, nullptr, stage_in(i), rows, ch, 4 * cin, nullptr, nullptr, st));
       else
-      TRYB(launch_gemm(c.precision, EPI_BIAS, k.patches[i], h->extra + h->down[i].p_w,
+      TRYB(launch_gemm(c.precision, EPI_BIAS, k.patches[i], IMG(h, h->down[i].p_w),
                        m + h->down[i].b, nullptr, nullptr, stage_in(i), rows, ch, 4 * cin, st));
     }
     const size_t nblk = h->blocks[i].size();
     if (i == 1 && s1t) {
       // stage 1 + the second downsample as one launch of stage1b's keeping form: block 0's input is its x_in, block 1's
       // input the residual copy the kernel parks between the blocks anyway
-      Stage1Args a = stage1_args(h, true);
+      Stage1Args a;
+      TRYB(stage1_args(h, true, &a));
       a.x_in = stage_in(1);
       for (int j = 0; j < 2; ++j) {
         a.keep_d[j] = k.blk[1][j].d;
@@ -250,7 +252,8 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
       // the downsample's patch rows -- on its way.  Replaces 6 x (dw3_ln + two GEMMs) + ln_patch + GEMM.  The depthwise
       // output is not kept: dw3ln_bwd_kernel recomputes it (block 0's buffer for it takes the copy of the stage input the
       // kernel writes for every block alike).
-      Stage2pArgs a = stage2p_args(h, true);
+      Stage2pArgs a;
+      TRYB(stage2p_args(h, true, &a));
       a.x_in = stage_in(2);
       for (size_t j = 0; j < nblk; ++j) {
         const BlkBuf& sb = k.blk[2][j];
@@ -272,25 +275,25 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
       const BlockPk& b = h->blocks[i][j];
       const BlkBuf& s = k.blk[i][j];
       float* xout = j + 1 < nblk ? k.blk[i][j + 1].xin : k.xs[i];
-      TRYB(launch_dwconv_ln(c.precision, s.xin, reinterpret_cast<const float*>(h->extra + b.p_dw),
+      TRYB(launch_dwconv_ln(c.precision, s.xin, IMG_F32(h, b.p_dw),
                             m + b.dw_b, m + b.ln_w, m + b.ln_b, s.xn, B, hw, ch, st, s.d));
       if (s.fpart != nullptr) {
         // the block's backward recomputes fc1 (mlp_bwd.hip): neither the pre-activation nor the GELU output is kept
-        TRYB(launch_fused_mlp(c.precision, ch, s.xn, h->extra + b.p_fused, m + b.fc1_b, m + b.fc2_b, m + b.gamma, xout,
+        TRYB(launch_fused_mlp(c.precision, ch, s.xn, IMG(h, b.p_fused), m + b.fc1_b, m + b.fc2_b, m + b.gamma, xout,
                               rows, st, nullptr, nullptr, nullptr, 0, s.xin));
         continue;
       }
       if (h->train_split) {   // (split training: the activations enter the products unscaled, as in inference)
-        TRYB(launch_gemm_x2_train(EPI_GELU_SAVE, reinterpret_cast<const float*>(s.xn), h->extra + b.p_s_fc1, m + b.fc1_b,
+        TRYB(launch_gemm_x2_train(EPI_GELU_SAVE, reinterpret_cast<const float*>(s.xn), IMG(h, b.p_s_fc1), m + b.fc1_b,
                                   nullptr, reinterpret_cast<const float*>(s.a), reinterpret_cast<float*>(s.h), rows, 4 * ch,
                                   ch, nullptr, nullptr, st));
-        TRYB(launch_gemm_x2_train(EPI_RESID, reinterpret_cast<const float*>(s.h), h->extra + b.p_s_fc2, m + b.fc2_b,
+        TRYB(launch_gemm_x2_train(EPI_RESID, reinterpret_cast<const float*>(s.h), IMG(h, b.p_s_fc2), m + b.fc2_b,
                                   m + b.gamma, s.xin, xout, rows, ch, 4 * ch, nullptr, nullptr, st));
         continue;
       }
-      TRYB(launch_gemm(c.precision, EPI_GELU_SAVE, s.xn, h->extra + b.p_fc1, m + b.fc1_b, nullptr,
+      TRYB(launch_gemm(c.precision, EPI_GELU_SAVE, s.xn, IMG(h, b.p_fc1), m + b.fc1_b, nullptr,
                        reinterpret_cast<const float*>(s.a), s.h, rows, 4 * ch, ch, st));
-      TRYB(launch_gemm(c.precision, EPI_RESID, s.h, h->extra + b.p_fc2, m + b.fc2_b, m + b.gamma,
+      TRYB(launch_gemm(c.precision, EPI_RESID, s.h, IMG(h, b.p_fc2), m + b.fc2_b, m + b.gamma,
                        s.xin, xout, rows, ch, 4 * ch, st));
     }
   }
@@ -411,7 +414,7 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
     for (int j = (int)h->blocks[i].size() - 1; j >= 0; --j) {
       const BlockPk& b = h->blocks[i][j];
       const BlkBuf& s = k.blk[i][j];
-      const float* wdw = reinterpret_cast<const float*>(h->extra + b.p_dw);
+      const float* wdw = IMG_F32(h, b.p_dw);
       const bool batched = batching && s.Gb != nullptr && s.fpart == nullptr && nbj + 2 <= 16;
       unsigned* am_dy = sp ? amax_rec(blk_amax(i, j)) : nullptr;
       unsigned* am_da = sp ? amax_rec(blk_amax(i, j) + 1) : nullptr;
@@ -436,30 +439,30 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
       }
       if (s.fpart != nullptr) {
         // ---- da, dxn = da W1 and both filter gradients of the MLP in one launch (a recomputed from xn; da, g only on chip)
-        TRYB(launch_mlp_bwd(prec, ch, s.xn, s.dyT, h->extra + b.p_fc1, h->extra + b.p_fc2t, m + b.fc1_b, dxn, s.fpart,
+        TRYB(launch_mlp_bwd(prec, ch, s.xn, s.dyT, IMG(h, b.p_fc1), IMG(h, b.p_fc2t), m + b.fc1_b, dxn, s.fpart,
                             k.G, s.fS, grads + b.fc1_w, grads + b.fc1_b, rows, st, red));
         TRYB(fork());
       } else if (h->s2mlp && b.p_w1tp != 0 && s2mlp_bwd_supported(prec, ch)) {
         // ---- 256 channels: da = (dy (diag(gamma) W2)) * gelu'(a) and dxn = da W1 in one launch (s2mlp_bwd.hip)
-        TRYB(launch_s2mlp_bwd(prec, s.dyT, s.a, h->extra + b.p_w2tp, h->extra + b.p_w1tp, s.da, dxn, rows, st));
+        TRYB(launch_s2mlp_bwd(prec, s.dyT, s.a, IMG(h, b.p_w2tp), IMG(h, b.p_w1tp), s.da, dxn, rows, st));
         if (!batched || h->fork_per_block) TRYB(fork());
       } else if (sp) {
         // ---- split training: the two products below on split operands (dy, da scaled by their own powers of two)
-        TRYB(launch_gemm_x2_train(EPI_DGELU, reinterpret_cast<const float*>(s.dyT), h->extra + b.p_s_fc2t, nullptr, nullptr,
+        TRYB(launch_gemm_x2_train(EPI_DGELU, reinterpret_cast<const float*>(s.dyT), IMG(h, b.p_s_fc2t), nullptr, nullptr,
                                   reinterpret_cast<const float*>(s.a), reinterpret_cast<float*>(s.da), rows, H, ch, am_dy,
                                   am_da, st));
         TRYB(fork());
-        TRYB(launch_gemm_x2_train(EPI_PLAIN, reinterpret_cast<const float*>(s.da), h->extra + b.p_s_fc1t, nullptr, nullptr,
+        TRYB(launch_gemm_x2_train(EPI_PLAIN, reinterpret_cast<const float*>(s.da), IMG(h, b.p_s_fc1t), nullptr, nullptr,
                                   nullptr, dxn, rows, ch, H, am_da, nullptr, st));
       } else {
       // ---- da = (dy (diag(gamma) W2)) * gelu'(a)     (gamma is folded into the packed W2^T)
-      TRYB(launch_gemm(prec, EPI_DGELU, s.dyT, h->extra + b.p_fc2t, nullptr, nullptr,
+      TRYB(launch_gemm(prec, EPI_DGELU, s.dyT, IMG(h, b.p_fc2t), nullptr, nullptr,
                        reinterpret_cast<const float*>(s.a), s.da, rows, H, ch, st));
       // the side stream may start once da exists; its work is queued below, behind the chain's (a block whose GEMMs wait
       // for the stage's batch has nothing for it yet)
       if (!batched || h->fork_per_block) TRYB(fork());
       // ---- dxn = da W1, then the LayerNorm backward on the depthwise output d = dwconv(x_in) + bias the forward kept
-      TRYB(launch_gemm(prec, EPI_PLAIN, s.da, h->extra + b.p_fc1t, nullptr, nullptr, nullptr, dxn,
+      TRYB(launch_gemm(prec, EPI_PLAIN, s.da, IMG(h, b.p_fc1t), nullptr, nullptr, nullptr, dxn,
                        rows, ch, H, st));
       }
       void* nxt = fold_cast ? next_dyT(i, j) : nullptr;
@@ -543,10 +546,10 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
       TRYB(fork());
       if (nbj > 0) TRYB(stage_batch());
       if (sp)
-        TRYB(launch_gemm_x2_train(EPI_PLAIN, reinterpret_cast<const float*>(dyT), h->extra + h->down[i].p_s_wt, nullptr,
+        TRYB(launch_gemm_x2_train(EPI_PLAIN, reinterpret_cast<const float*>(dyT), IMG(h, h->down[i].p_s_wt), nullptr,
                                   nullptr, nullptr, k.dpat, rows, 4 * cin, ch, am_dn, nullptr, st));
       else
-      TRYB(launch_gemm(prec, EPI_PLAIN, dyT, h->extra + h->down[i].p_wt, nullptr, nullptr,
+      TRYB(launch_gemm(prec, EPI_PLAIN, dyT, IMG(h, h->down[i].p_wt), nullptr, nullptr,
                        nullptr, k.dpat, rows, 4 * cin, ch, st));
       // LN backward per input pixel (x_prev = stage i-1 output), its incoming gradient gathered from the patch matrix
       // (was an unpatch launch); result is the new dy, in the 16-bit modes also as the operand of stage i-1's last

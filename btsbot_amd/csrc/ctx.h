@@ -1,5 +1,6 @@
 // Internal: the handle behind btsbot_handle (shared by api.hip and head_train.hip).
 #pragma once
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -13,17 +14,17 @@ struct ParamRec {
   int is_buffer;
 };
 
-struct BlockPk {  // per ConvNeXt block: master offsets + packed offsets (bytes into `extra`)
+struct BlockPk {  // per ConvNeXt block: master offsets + packed offsets (bytes into `extra`; 0: no such image, pack.hip)
   int64_t gamma, dw_w, dw_b, ln_w, ln_b, fc1_w, fc1_b, fc2_w, fc2_b;
-  size_t p_dw, p_fc1, p_fc2, p_fused;
-  size_t p_s0par;          // stage-0 / stage-1 blocks: parameter image for stage0b.hip / stage1b.hip
+  size_t p_dw = 0, p_fc1 = 0, p_fc2 = 0, p_fused = 0;
+  size_t p_s0par = 0;      // stage-0 / stage-1 blocks: parameter image for stage0b.hip / stage1b.hip
   size_t p_s0par_t = 0;    // ... for their keeping forms (training forward): the same image with f16 taps in every mode
-  size_t p_fc2g;           // diag(gamma) W2 in the operand type (megakernels fold the layer scale)
+  size_t p_fc2g = 0;       // diag(gamma) W2 in the operand type (megakernels fold the layer scale)
   size_t p_w1p = 0, p_w2p = 0;   // stage2p.hip / stage3.hip: fc1 / gamma * fc2 filters as MFMA A fragments
   size_t p_scales = 0;           // fp8 mode: {S1, 1/S1, S2, 1/S2} of those two
   size_t p_x2_w1 = 0, p_x2_w2g = 0;   // split mode, stages 0-1: fc1 / gamma * fc2 filters, f16 heads (stage0b / stage1b)
   size_t p_x2_w1lo = 0, p_x2_w2glo = 0;   // ... and their f16 remainders, same layouts
-  size_t p_fc1t, p_fc2t;   // for the dgrad GEMMs: W1^T [C][4C], (diag(gamma) W2)^T [4C][C]
+  size_t p_fc1t = 0, p_fc2t = 0;   // for the dgrad GEMMs: W1^T [C][4C], (diag(gamma) W2)^T [4C][C]
   size_t p_w1tp = 0, p_w2tp = 0;   // 256-channel blocks, training: the same two as MFMA A fragments (s2mlp_bwd.hip)
   // split training ("train_split"): p_fc1 / p_fc2 / p_fc1t / p_fc2t as f16 head + remainder planes, [n] heads then [n]
   // remainders (slots of their own: the per-op inference forward of the split mode reads the fp32 p_fc1 / p_fc2)
@@ -32,9 +33,8 @@ struct BlockPk {  // per ConvNeXt block: master offsets + packed offsets (bytes 
 };
 struct DownPk {
   int64_t ln_w, ln_b, w, b;
-  size_t p_w, p_wt;        // p_wt: [4*Cin][Cout] transpose of the packed filter (dgrad)
-  size_t p_wp = 0;         // stage2p.hip: the filter as MFMA A fragments
-  size_t p_scale = 0;      // fp8 mode: {S, 1/S} of it
+  size_t p_w = 0, p_wt = 0;   // p_wt: [4*Cin][Cout] transpose of the packed filter (dgrad)
+  size_t p_wp = 0;         // stage2p.hip / stage1b.hip: the filter as MFMA A fragments
   size_t p_x2_w = 0, p_x2_wlo = 0;   // split mode, stage0b's downsample: the filter's f16 heads / remainders, [Cout][q][Cin]
   size_t p_s_w = 0, p_s_wt = 0;      // split training: p_w / p_wt as f16 head + remainder planes (BlockPk::p_s_fc1)
 };
@@ -80,6 +80,25 @@ static_assert(2 * STAMP_S0_MAX_WG <= STAMP_S0_WG_N && 2 * STAMP_S1_MAX_WG <= 409
                   STAMP_MV_PART + STAMP_MV_PART_N <= STAMP_S0_WG + STAMP_S0_WG_N,
               "a stamp region does not hold what is written into it");
 
+// One packed operand image of a ConvNeXt / metadata / fusion handle (pack.hip: image_walk() lists them, pack_layout()
+// reserves them, pack_params() writes them).
+enum { IN_FULL = 1, IN_TRAIN = 2 };   // btsbot_pack_params() / the training re-pack btsbot_pack_params_train()
+struct ImageEntry {
+  const char* name;
+  size_t* slot;           // the BlockPk / DownPk / btsbot_ctx field that holds its offset into `extra`
+  size_t bytes;           // 0: another writer of a slot an entry in front reserved
+  unsigned when;          // which packs write it (0: reserved only, e.g. the dgrad transposes before btsbot_reserve_train)
+  bool early;             // training re-pack: stage0b_kernel's keeping form reads it -- written in front of pack_early_ev
+  const size_t* reads;    // the packed image it is made from, listed in front of it (nullptr: made from the mirror)
+  int op;                 // >= 0: a PackJob of the batch table (common.h: PACK_*), src / scale = master offsets (-1: none)
+  int64_t src, scale;
+  int R, Cc;
+  long split_n;           // > 0: the f16 head + remainder planes of the split_n floats of *reads (SplitJob)
+  // a dedicated packer; with op >= 0 the job's single-operand launch where the generic one does not fit.  None of the
+  // three: written by the entry in front (a packer with two outputs)
+  std::function<int(hipStream_t)> launch;
+};
+
 struct MaxVit;   // maxvit.hip
 struct SidePick {
   hipStream_t caller, side;
@@ -104,7 +123,7 @@ struct btsbot_ctx {
   DownPk down[4];
   int64_t bn_w, bn_b, bn_rm, bn_rv, m1_w, m1_b, m2_w, m2_b;
   int64_t comb_w[3], comb_b[3];
-  size_t p_m1, p_m2, p_comb[3], p_bn_scale, p_bn_shift, p_stem16 = 0;
+  size_t p_m1 = 0, p_m2 = 0, p_comb[3] = {0, 0, 0}, p_bn_scale = 0, p_bn_shift = 0, p_stem16 = 0;
   size_t p_x2_stem = 0, p_x2_stemlo = 0;    // split mode: the stem filter's f16 heads / remainders (stage0b)
   int prec_head() const { return x2 ? BTSBOT_F16 : cfg.precision; }   // head16.hip splits its operands in every mode
   int prec_s01() const { return x2 ? BTSBOT_F16X2 : cfg.precision; }   // operand mode of stage0b.hip / stage1b.hip
@@ -115,8 +134,11 @@ struct btsbot_ctx {
 
   // device memory
   float* mirror = nullptr;          // fp32 copy of the master arena (same offsets)
-  unsigned char* extra = nullptr;   // transformed operands
-  void* pack_jobs[3] = {nullptr, nullptr, nullptr};   // device tables of PackJob: [0] full pack, [1] training re-pack,
+  unsigned char* extra = nullptr;   // transformed operands; offset 0 is reserved: a slot of 0 is an image that was never laid out
+  unsigned char* image(size_t slot) const { return slot != 0 ? extra + slot : nullptr; }   // readers: IMG() below
+  std::vector<ImageEntry> images;   // pack.hip
+  size_t extra_fixed = 256;         // where they start: behind offset 0 and a MaxViT branch's images (maxvit_build_tables)
+  void* pack_jobs[3] = {nullptr, nullptr, nullptr};   // (pack.hip) device tables of PackJob: [0] full pack, [1] training re-pack,
   int pack_njobs[3] = {0, 0, 0}, pack_blocks[3] = {0, 0, 0};   // [2] the part of [1] the stage-0 megakernel reads (s0_train)
   hipEvent_t pack_early_ev = nullptr;   // recorded behind that part and the stage-0 parameter images (pack_sync_early)
   bool pack_early = false;              // the running re-pack recorded it
@@ -250,8 +272,32 @@ int pick_apart_stream(btsbot_ctx* h, const hipStream_t* busy, int nbusy, const c
 int side_fork(btsbot_ctx* h, hipStream_t st, hipStream_t* sd);
 int side_join(btsbot_ctx* h, hipStream_t st);
 
-int pack_sync(btsbot_ctx* h, hipStream_t st);   // api.hip
-int pack_sync_early(btsbot_ctx* h, hipStream_t st);   // api.hip: only what stage0b_kernel reads (else = pack_sync)
+// h->extra + slot for a reader or a packer.  An image the layout never reserved ends the calling function (or lambda)
+// with BTSBOT_ERR_STATE and its name, in front of the launch it was meant for.
+#define IMG(h, slot)                                                                            \
+  ({                                                                                            \
+    unsigned char* img_ = (h)->image(slot);                                                     \
+    if (img_ == nullptr) {                                                                      \
+      btsbot_set_error("the packed operand image %s does not exist on this handle", #slot);   \
+      return (int)BTSBOT_ERR_STATE;                                                              \
+    }                                                                                           \
+    img_;                                                                                       \
+  })
+#define IMG_F32(h, slot) reinterpret_cast<const float*>(IMG(h, slot))
+
+inline size_t bump(size_t& cur, size_t bytes) {
+  const size_t o = cur;
+  cur += (bytes + 255) / 256 * 256;
+  return o;
+}
+
+// pack.hip
+int pack_layout(btsbot_ctx* h);       // lists the images, reserves their slots behind extra_fixed, sets extra_bytes
+int pack_params(btsbot_ctx* h, const float* master, hipStream_t st, bool train_only);
+int pack_invalidate(btsbot_ctx* h);   // a flag the image list reads has changed (train_packs): new list, new job tables
+void pack_release(btsbot_ctx* h);     // btsbot_destroy
+int pack_sync(btsbot_ctx* h, hipStream_t st);
+int pack_sync_early(btsbot_ctx* h, hipStream_t st);   // only what stage0b_kernel reads (else = pack_sync)
 
 // stage_args.hip: the argument blocks of the ConvNeXt stage kernels with every parameter pointer the handle holds
 // filled in, everything else zero.  keep: the keeping form of the training forward (bf16 / f16: stage-0 / stage-1
@@ -260,7 +306,7 @@ struct Stage0Args;
 struct Stage1Args;
 struct Stage2pArgs;
 struct Stage3Args;
-Stage0Args stage0_args(const btsbot_ctx* h, bool keep);
-Stage1Args stage1_args(const btsbot_ctx* h, bool keep);
-Stage2pArgs stage2p_args(const btsbot_ctx* h, bool keep);
-Stage3Args stage3_args(const btsbot_ctx* h);
+int stage0_args(const btsbot_ctx* h, bool keep, Stage0Args* out);
+int stage1_args(const btsbot_ctx* h, bool keep, Stage1Args* out);
+int stage2p_args(const btsbot_ctx* h, bool keep, Stage2pArgs* out);
+int stage3_args(const btsbot_ctx* h, Stage3Args* out);

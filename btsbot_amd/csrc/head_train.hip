@@ -428,12 +428,12 @@ int head_train_meta_forward(btsbot_ctx* h, float* cache, const float* meta, int 
   LAUNCH_CHECK();
   const float ks1 = c.meta_dropout < 1.f ? 1.f / (1.f - c.meta_dropout) : 0.f;
   hipLaunchKernelGGL(lin_fwd_kernel, g1((long)M * c.meta_fc1), dim3(256), 0, st, p.x1, c.n_meta,
-                     reinterpret_cast<const float*>(h->extra + h->p_m1), m + h->m1_b, p.a1, p.h1,
+                     IMG_F32(h, h->p_m1), m + h->m1_b, p.a1, p.h1,
                      c.meta_fc1, M, c.meta_fc1, c.n_meta, h->act,
                      c.meta_dropout > 0.f ? meta_mask : nullptr, ks1);
   LAUNCH_CHECK();
   hipLaunchKernelGGL(lin_fwd_kernel, g1((long)M * c.meta_fc2), dim3(256), 0, st, p.h1,
-                     c.meta_fc1, reinterpret_cast<const float*>(h->extra + h->p_m2), m + h->m2_b,
+                     c.meta_fc1, IMG_F32(h, h->p_m2), m + h->m2_b,
                      p.a2, p.z + F, zd, M, c.meta_fc2, c.meta_fc1,
                      h->meta_trailing_act ? h->act : ACT_NONE, nullptr, 1.f);
   LAUNCH_CHECK();
@@ -471,7 +471,7 @@ int head_train_forward(btsbot_ctx* h, float* cache, const float* meta, float* lo
                          last ? ACT_NONE : h->act, drop ? comb_mask : nullptr, ksc);
     } else {
       hipLaunchKernelGGL(lin_fwd_kernel, g1((long)M * N), dim3(256), 0, st, in, ldi,
-                         reinterpret_cast<const float*>(h->extra + h->p_comb[i]), m + h->comb_b[i],
+                         IMG_F32(h, h->p_comb[i]), m + h->comb_b[i],
                          p.pre[i], p.actv[i], N, M, N, K, last ? ACT_NONE : h->act,
                          drop ? comb_mask : nullptr, ksc);
     }
@@ -507,7 +507,7 @@ int head_train_backward(btsbot_ctx* h, float* cache, const float* dlogits, float
     if (i == 0 && !want_dz) break;
     float* din = p.dbuf[i];
     if (wide_layer(M, K, N, N)) {   // din[m][k] = sum_n dout[m][n] Wt[k][n]
-      TRY_RET(launch_gemm(BTSBOT_F32, EPI_PLAIN, dout[i], h->extra + h->p_comb[i], nullptr, nullptr, nullptr, din, M, K,
+      TRY_RET(launch_gemm(BTSBOT_F32, EPI_PLAIN, dout[i], IMG(h, h->p_comb[i]), nullptr, nullptr, nullptr, din, M, K,
                           N, st));
     } else {
       hipLaunchKernelGGL(lin_bwd_in_kernel, g1((long)M * K), dim3(256), 0, st, dout[i], m + h->comb_w[i],

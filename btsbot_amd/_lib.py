@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("BTSBOT_AMD_LIB") or os.path.join(_HERE, "libbtsbot_hi
 ABI_VERSION = 1
 
 OK = 0
+ERR_INVALID_ARG = -1
+ERR_STATE = -5
 WIRING = {"mm_ConvNeXt": 0, "ConvNeXt": 1, "frozen_fusion": 2, "um_nn": 3, "mm_MaxViT": 4,
           "MaxViT": 5, "frozen_fusion_MaxViT": 6}
 PRECISION = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1, "f16": 2, "fp16": 2,

@@ -236,6 +236,14 @@ class _HipModel(nn.Module):
     def split_training(self) -> bool:
         return getattr(self, "_split_training", False)
 
+    def schedule_flag(self, field: str) -> bool:
+        """Whether decision ``field`` of the handle's resolved kernel schedule is on (``btsbot_set_option
+        "query_schedule:<field>"``; the fields are listed in csrc/schedule.h).  Unknown fields raise."""
+        rc = _lib.lib().btsbot_set_option(self._handle.ptr, f"query_schedule:{field}".encode(), 0)
+        if rc not in (_lib.OK, _lib.ERR_STATE):
+            raise ValueError(f"btsbot_amd: no schedule field {field!r}")
+        return rc == _lib.OK
+
     def mark_weights_dirty(self):
         """Call after modifying parameters through ``.data`` (in-place ops on the parameters
         themselves, ``load_state_dict`` and optimisers are tracked automatically)."""

@@ -67,10 +67,6 @@ int build_tables(btsbot_ctx* h) {
     h->stem_b = add_param(h, "stem.0.bias", {c0});
     h->stem_lnw = add_param(h, "stem.1.weight", {c0});
     h->stem_lnb = add_param(h, "stem.1.bias", {c0});
-    h->stage0 = stage0_supported(h->prec_s01(), c0) && c.depths[0] == 2;
-    h->stage1 = stage1_supported(h->prec_s01(), c.dims[1], c.dims[2]) && c.depths[1] == 2;
-    h->stage2p = stage2p_supported(h->prec_tail(), c.dims[2], c.dims[3], c.depths[2]);
-    h->stage3 = stage3_supported(h->prec_tail(), c.dims[3], c.depths[3]);
     h->blocks.resize(4);
     for (int i = 0; i < 4; ++i) {
       const int ch = c.dims[i];
@@ -96,7 +92,6 @@ int build_tables(btsbot_ctx* h) {
         b.fc1_b = add_param(h, p + "mlp.fc1.bias", {4 * ch});
         b.fc2_w = add_param(h, p + "mlp.fc2.weight", {ch, 4 * ch, 1, 1});
         b.fc2_b = add_param(h, p + "mlp.fc2.bias", {ch});
-        b.fused = fused_mlp_supported(c.precision, ch);
         h->blocks[i].push_back(b);
       }
     }
@@ -122,8 +117,6 @@ int build_tables(btsbot_ctx* h) {
     h->comb_w[i] = add_param(h, p + "weight", {h->comb_dims[i + 1], h->comb_dims[i]});
     h->comb_b[i] = add_param(h, p + "bias", {h->comb_dims[i + 1]});
   }
-  h->head16 = head16_supported(h->prec_head(), h->has_image ? c.dims[3] : 0, h->has_meta ? c.n_meta : 0, c.meta_fc1, c.meta_fc2,
-                               h->n_comb, h->comb_dims);
   // gradient buckets, in the order the backward pass completes them
   if (h->has_image && !h->is_maxvit) {
     const int64_t s3 = h->down[3].ln_w, s2 = h->down[2].ln_w;
@@ -162,7 +155,7 @@ void ws_layout(const btsbot_ctx* h, int chunk, size_t* ox, size_t* ox2, size_t* 
     *ox2 = bump(cur, x_el * chunk * 4);
     *oxn = bump(cur, xn_el * chunk * h->esz());
     size_t h_bytes = h_el * chunk * h->esz();
-    if (h->stage3) {   // stage3.hip keeps GELU(fc1) in fragment order, alerts rounded up to its 64-row tiles
+    if (h->sched.stage3) {   // stage3.hip keeps GELU(fc1) in fragment order, alerts rounded up to its 64-row tiles
       const size_t s3 = stage3_hfrag_bytes(h->prec_tail(), c.dims[3], chunk);
       h_bytes = s3 > h_bytes ? s3 : h_bytes;
     }
@@ -190,6 +183,7 @@ extern "C" int btsbot_create(const btsbot_config* cfg, btsbot_handle* out) {
   }
   btsbot_ctx* h = new btsbot_ctx();
   h->cfg = *cfg;
+  read_handle_switches(h);
   if (cfg->precision == BTSBOT_FP8) {   // everything but the fragment-streaming stages reads the bf16 schedule
     h->fp8 = true;
     h->cfg.precision = BTSBOT_BF16;
@@ -197,7 +191,7 @@ extern "C" int btsbot_create(const btsbot_config* cfg, btsbot_handle* out) {
   if (cfg->precision == BTSBOT_F16X2) {   // kernels without a split-operand form run the fp32 schedule
     h->x2 = true;
     h->cfg.precision = BTSBOT_F32;
-    h->x2_tail_plain = env_on("BTSBOT_AMD_X2_TAIL_F16");
+    h->x2_tail_plain = h->sw[SW_X2_TAIL_F16] == 1;
   }
   const int w = cfg->wiring;
   h->has_image = (w != BTSBOT_UM_NN);
@@ -263,39 +257,7 @@ extern "C" int btsbot_create(const btsbot_config* cfg, btsbot_handle* out) {
     h->comb_dims[3] = 1;
   }
   build_tables(h);
-  h->use_fused = !env_on("BTSBOT_AMD_NO_FUSED_MLP");
-  h->use_stage0 = !env_on("BTSBOT_AMD_NO_STAGE0");
-  h->use_stage1 = !env_on("BTSBOT_AMD_NO_STAGE1");
-  h->use_s2 = !env_on("BTSBOT_AMD_NO_STAGE2");
-  h->use_s2p = h->use_s2;
-  h->use_head16 = !env_on("BTSBOT_AMD_NO_HEAD16");
-  h->s0_diag = env_int("BTSBOT_AMD_S0_DIAG", 0);
-  h->s2p_diag = env_int("BTSBOT_AMD_S2P_DIAG", 0);
-  h->use_s3 = !env_on("BTSBOT_AMD_NO_S3");
-  h->use_dwln = !env_on("BTSBOT_AMD_NO_DWLN");
-  h->mlp_bwd_only = env_on("BTSBOT_AMD_NO_MLP_BWD") ? -1 : env_int("BTSBOT_AMD_MLP_BWD_C", 0);
-  // (default since its operand images come out of the re-pack's job table: with a dozen launches of their own queued in
-  //  front of the forward's join the kernel LOST 30 us per step; now 2.549-2.560 against 2.565-2.581 ms)
-  h->s2mlp = !env_on("BTSBOT_AMD_NO_S2MLP");
-  h->fork_per_block = env_on("BTSBOT_AMD_FORK_PER_BLOCK");
-  h->wgrad_batch = !env_on("BTSBOT_AMD_NO_WGRAD_BATCH");
-  h->use_side = !env_on("BTSBOT_AMD_NO_SIDE_STREAM");
-  // stage 2's training forward through stage2p_kernel's keeping form (ctx.h): on wherever its backward runs the 3x3
-  // kernel that recomputes the depthwise output (dw3ln_bwd_kernel: use_dwln and not BTSBOT_AMD_DW3_OLD)
-  h->s2p_train = h->stage2p && h->cfg.dims[2] == 256 && h->use_s2p && !h->x2 && !h->fp8 && h->use_dwln && dw3_bwd_active(3, 256) &&
-                 (h->cfg.precision == BTSBOT_BF16 || h->cfg.precision == BTSBOT_F16) && !env_on("BTSBOT_AMD_NO_S2P_TRAIN");
-  h->s0_train = h->stage0 && h->use_stage0 && !h->x2 && !h->fp8 &&
-                (h->cfg.precision == BTSBOT_BF16 || h->cfg.precision == BTSBOT_F16) && !env_on("BTSBOT_AMD_NO_S0_TRAIN");
-  // stage 1 likewise -- by default in the f16 mode only.  In bf16 it is worth 45 us of a 2.6 ms step and holds every
-  // gradient bound, but the 50-step trajectory test (loss curve against the fp32 recipe, bounds = 2 x what the per-op
-  // forward measured) then uses 0.40 / 0.98 / 1.02 of its band in three runs (stage 0 alone: 0.66-0.72; the parameter
-  // drift stays 3.3-3.8 % either way): BTSBOT_AMD_S1_TRAIN=1 opts in.
-  h->s1_train = h->stage1 && h->use_stage1 && !h->x2 && !h->fp8 &&
-                (h->cfg.precision == BTSBOT_F16 || (h->cfg.precision == BTSBOT_BF16 && env_on("BTSBOT_AMD_S1_TRAIN"))) &&
-                !env_on("BTSBOT_AMD_NO_S1_TRAIN");
-  h->use_stem16 = !env_on("BTSBOT_AMD_NO_STEM16");
-  // (the deterministic reductions cover the ConvNeXt training step only: same rule as btsbot_set_option)
-  h->deterministic = env_on("BTSBOT_AMD_DETERMINISTIC") && !h->is_maxvit;
+  resolve_schedule(h);
   if (pack_layout(h) != BTSBOT_OK) {
     delete h;
     return BTSBOT_ERR_STATE;
@@ -406,7 +368,8 @@ extern "C" int btsbot_set_option(btsbot_handle h, const char* key, int value) {
                        "backward still meets through atomics");
       return BTSBOT_ERR_STATE;
     }
-    h->deterministic = value == 1;
+    h->opt_deterministic = value == 1;
+    resolve_schedule(h);
     return BTSBOT_OK;
   }
   if (strcmp(key, "train_split") == 0) {
@@ -424,12 +387,13 @@ extern "C" int btsbot_set_option(btsbot_handle h, const char* key, int value) {
                        "btsbot_pack_params* / btsbot_reserve_train()");
       return BTSBOT_ERR_STATE;
     }
-    h->train_split = value == 1;
+    h->opt_train_split = value == 1;
+    resolve_schedule(h);
     return pack_layout(h);   // (the split planes are images of their own)
   }
   if (strcmp(key, "query_train_split") == 0) {
     // a query: BTSBOT_OK when the training step's matrix products run on split operands
-    if (!h->train_split) {
+    if (!h->sched.train_split) {
       btsbot_set_error("query_train_split: this handle's training products run on %s",
                        h->x2 ? "the fp32 MFMA (train_split is off)" : "the operand type of its precision");
       return BTSBOT_ERR_STATE;
@@ -451,7 +415,7 @@ extern "C" int btsbot_set_option(btsbot_handle h, const char* key, int value) {
   }
   if (strcmp(key, "query_maxvit_split") == 0) {
     // a query: BTSBOT_OK when the MaxViT inference forward runs its matrix products on split operands (gemm_x2.hip)
-    if (!(h->has_image && h->is_maxvit && maxvit_split(h))) {
+    if (!h->sched.maxvit_split) {
       btsbot_set_error("query_maxvit_split: this handle's %s", h->has_image && h->is_maxvit
                                                                   ? "MaxViT GEMMs run on the operand type of its precision"
                                                                   : "image branch is not MaxViT");
@@ -459,6 +423,7 @@ extern "C" int btsbot_set_option(btsbot_handle h, const char* key, int value) {
     }
     return BTSBOT_OK;
   }
+  if (strncmp(key, "query_schedule:", 15) == 0) return query_schedule(h, key + 15);
   if (strcmp(key, "exchange") == 0) {
     if (value != 0 && value != 1) {
       btsbot_set_error("set_option: exchange is 0 (one all-reduce per span) or 1 (reduce-scatter + all-gather), got %d", value);
@@ -608,8 +573,8 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
   void* hb = h->ws + h->o_h;
   if (h->is_maxvit) return maxvit_chunk(h, img, nb, st, feat_out);
   if (h->has_image) {
-    const bool s0 = h->stage0 && h->use_stage0;
-    if (s0) {
+    const Schedule& sc = h->sched;
+    if (sc.stage0) {
       Stage0Args a;
       TRY(stage0_args(h, false, &a));
       a.img = img;
@@ -617,7 +582,7 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
       a.tap_stem = h->debug ? h->taps[0] : nullptr;
       a.tap_stage = h->debug ? h->taps[1] : nullptr;
       a.B = nb;
-      a.diag = h->s0_diag;
+      a.diag = sc.s0_diag;
       a.stamps = h->stamps ? h->stamps + STAMP_S0 : nullptr;
       a.wgt = stamp_wgt(h, STAMP_S0_WG, STAMP_S0_MAX_WG, nb);
       TRY(timed(h, CAT_STAGE0, st, [&] {
@@ -625,7 +590,7 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
       }));
     } else {
       TRY(timed(h, CAT_STEM, st, [&] {
-        if (h->use_stem16 && !h->x2 && stem16_supported(c.precision, c.dims[0]))
+        if (sc.stem16)
           return launch_stem16(c.precision, img, m + h->stem_w, m + h->stem_b, m + h->stem_lnw, m + h->stem_lnb, x, nb,
                                c.dims[0], st);
         return launch_stem(img, m + h->stem_w, m + h->stem_b, m + h->stem_lnw, m + h->stem_lnb, x,
@@ -635,9 +600,8 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
         HIP_TRY(hipMemcpyAsync(h->taps[0], x, (size_t)nb * 225 * c.dims[0] * 4,
                                hipMemcpyDeviceToDevice, st));
     }
-    const bool s1 = h->stage1 && h->use_stage1;
-    bool down_done = s0;      // the previous stage's kernel already applied stage i's downsample
-    for (int i = s0 ? 1 : 0; i < 4; ++i) {
+    bool down_done = sc.stage0;      // the previous stage's kernel already applied stage i's downsample
+    for (int i = sc.stage0 ? 1 : 0; i < 4; ++i) {
       const int ch = c.dims[i], hw = STAGE_HW[i], rows = nb * hw * hw;
       if (i > 0 && !down_done) {
         const int cin = c.dims[i - 1];
@@ -654,7 +618,7 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
         x2 = t;
       }
       down_done = false;
-      if (i == 1 && s1) {
+      if (i == 1 && sc.stage1) {
         Stage1Args a;
         TRY(stage1_args(h, false, &a));
         a.x_in = x;
@@ -662,7 +626,7 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
         a.scratch = x2 + (((size_t)nb * 9 * c.dims[2] + 63) / 64) * 64;   // behind the output rows (x2 holds 225 * 64 floats per alert)
         a.tap_stage = h->debug ? h->taps[2] : nullptr;
         a.B = nb;
-        a.diag = h->s0_diag;
+        a.diag = sc.s0_diag;
         a.stamps = h->stamps ? h->stamps + STAMP_S1 : nullptr;
         a.wgt = stamp_wgt(h, STAMP_S1_WG, STAMP_S1_MAX_WG, (nb + 1) / 2);
         TRY(timed(h, CAT_STAGE1, st, [&] {
@@ -674,7 +638,7 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
         down_done = true;
         continue;
       }
-      if (i == 2 && h->stage2p && h->use_s2p) {
+      if (i == 2 && sc.stage2p) {
         // every block of the 3x3 stage and the last downsample in one launch: x [nb][9][256] -> x2 [nb][512]
         Stage2pArgs a;
         TRY(stage2p_args(h, false, &a));
@@ -682,7 +646,7 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
         a.out = x2;
         a.tap_stage = h->debug ? h->taps[3] : nullptr;
         a.B = nb;
-        a.diag = h->s2p_diag;
+        a.diag = sc.s2p_diag;
         a.stamps = h->stamps ? h->stamps + STAMP_S2 : nullptr;
         TRY(timed(h, CAT_STAGE2, st, [&] { return launch_stage2p(h->prec_tail(), a, st); }));
         float* t = x;
@@ -691,7 +655,7 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
         down_done = true;
         continue;
       }
-      if (i == 3 && hw == 1 && h->stage3 && h->use_s3) {
+      if (i == 3 && hw == 1 && sc.stage3) {
         // the 1x1 stage: two launches per block, x updated in place
         Stage3Args a;
         TRY(stage3_args(h, &a));
@@ -712,7 +676,7 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
           return launch_dwconv_ln(c.precision, x, IMG_F32(h, b.p_dw), m + b.dw_b, m + b.ln_w, m + b.ln_b, xn, nb, hw,
                                   ch, st);
         }));
-        if (b.fused && h->use_fused) {
+        if (sc.fused_mlp[i]) {
           TRY(timed(h, CAT_FUSED, st, [&] {
             return launch_fused_mlp(c.precision, ch, xn, IMG(h, b.p_fused), m + b.fc1_b,
                                     m + b.fc2_b, m + b.gamma, x, rows, st);
@@ -743,7 +707,7 @@ static int forward_chunk(btsbot_ctx* h, const float* img, const float* meta, flo
   const float* m = h->mirror;
   float* x = nullptr;
   if (h->has_image) TRY(backbone_chunk(h, img, nb, st, &x));
-  if (h->head16 && h->use_head16) {
+  if (h->sched.head16) {
     Head16Args g;
     memset(&g, 0, sizeof(g));
     g.feat = h->has_image ? x : nullptr;
@@ -800,7 +764,7 @@ static int forward_chunk(btsbot_ctx* h, const float* img, const float* meta, flo
   a.logits = logits;
   a.scores = scores;
   a.B = nb;
-  a.diag = env_int("BTSBOT_AMD_HEAD_DIAG", 0);
+  a.diag = h->sched.head_diag;
   TRY(timed(h, CAT_HEAD, st, [&] { return launch_head(a, st); }));
   h->last_chunk = nb;
   return BTSBOT_OK;
@@ -872,7 +836,7 @@ extern "C" int btsbot_reserve_train(btsbot_handle h, int max_batch, int with_ima
   // (MaxViT: with_image_grads = 1 trains the branch -- BatchNorm2d batch statistics, maxvit_train.hip; = 0 serves heads
   //  over a frozen, eval-mode branch with the inference kernels)
   const bool want_bb = with_image_grads && h->has_image;
-  if (h->deterministic) {   // partial rows of the batch reductions (common.h: det_add), sized by the batch: 256 KB per alert,
+  if (h->sched.deterministic) {   // partial rows of the batch reductions (common.h: det_add), sized by the batch: 256 KB per alert,
     const size_t want = std::max((size_t)16 << 20, (size_t)max_batch << 16);   // at least 64 MB (what a step of <= 256 alerts takes)
     if (h->det_scratch == nullptr || h->det_floats < want) {
       HIP_TRY(hipDeviceSynchronize());
@@ -897,8 +861,9 @@ extern "C" int btsbot_reserve_train(btsbot_handle h, int max_batch, int with_ima
     h->bbcache = nullptr;
     HIP_TRY(hipMalloc(&h->bbcache, h->is_maxvit ? maxvit_train_cache_bytes(h, max_batch) : bb_cache_bytes(h, max_batch)));
     h->bbcache_batch = max_batch;
-    if (!h->train_packs && !h->is_maxvit) {      // the dgrad transposes must be packed too from now on
-      h->train_packs = true;
+    if (!h->opt_train_packs && !h->is_maxvit) {      // the dgrad transposes must be packed too from now on
+      h->opt_train_packs = true;
+      resolve_schedule(h);
       TRY(pack_invalidate(h));   // (the job tables were built without the transposes)
     }
   }
@@ -958,8 +923,7 @@ extern "C" int btsbot_forward_train(btsbot_handle h, const float* triplets, cons
       // the metadata branch reads nothing of the image branch: its three launches go to the side stream (behind the
       // re-pack queued there) and run beside the backbone instead of in the chain behind it
       hipStream_t sd = st;
-      static const bool meta_inline = env_on("BTSBOT_AMD_NO_META_SIDE");   // 1: the metadata branch in the chain, behind the backbone (A/B)
-      if (h->has_meta && h->side != nullptr && !meta_inline) {
+      if (h->has_meta && h->side != nullptr && h->sched.meta_side) {
         TRY(side_fork(h, st, &sd));
         TRY(head_train_meta_forward(h, h->tcache, meta, batch, meta_mask, master_arena, sd));
         meta_on_side = sd != st;
@@ -1007,7 +971,7 @@ extern "C" int btsbot_backward(btsbot_handle h, const float* dlogits, float* gra
     btsbot_set_error("backward: image-branch gradients need forward_train(keep_image_activations=1)");
     return BTSBOT_ERR_STATE;
   }
-  if (h->deterministic && need_img) {
+  if (h->sched.deterministic && need_img) {
     // checked BEFORE anything is launched or any handle state moves: the scratch of the fixed-order reductions is sized
     // by the batch at btsbot_reserve_train() (256 KB per alert, at least 64 MB)
     const size_t want = std::max((size_t)16 << 20, (size_t)h->train_batch << 16);
@@ -1021,7 +985,7 @@ extern "C" int btsbot_backward(btsbot_handle h, const float* dlogits, float* gra
     TRY(launch_fill0(grad_arena, (size_t)h->img_floats, st));
   for (int i = 0; i < h->n_buckets; ++i)
     if (h->bucket_ev[i] == nullptr) HIP_TRY(hipEventCreateWithFlags(&h->bucket_ev[i], hipEventDisableTiming));
-  if (h->use_side && (h->side == nullptr || h->side_for != st)) {
+  if (h->sched.side_stream && (h->side == nullptr || h->side_for != st)) {
     // the caller changed streams: the side stream chosen against the old one may share the new one's pipe.  Whatever the
     // old pair still holds is ordered in front of this call by the join below (the new caller stream waits for it)
     hipStream_t old = h->side;
@@ -1037,7 +1001,7 @@ extern "C" int btsbot_backward(btsbot_handle h, const float* dlogits, float* gra
   h->side_used = 0;
   // deterministic mode: the launchers below take their partial rows from this scratch (fixed-order reductions)
   struct DetScope {
-    explicit DetScope(btsbot_ctx* c) { det_begin(c->deterministic ? c->det_scratch : nullptr, c->det_floats); }
+    explicit DetScope(btsbot_ctx* c) { det_begin(c->sched.deterministic ? c->det_scratch : nullptr, c->det_floats); }
     ~DetScope() { det_end(); }
   } det_scope(h);
   // (the paths that record every bucket at their end anyway always do; the ConvNeXt backward forks for them on demand)
@@ -1134,8 +1098,7 @@ int time_candidate(hipStream_t cand, hipEvent_t ev, const hipStream_t* busy, int
 int pick_apart_stream(btsbot_ctx* h, const hipStream_t* busy, int nbusy, const char* role, hipStream_t* out, bool* apart_out) {
   StreamPile pile;
   HIP_TRY(hipEventCreateWithFlags(&pile.ev, hipEventDisableTiming));
-  // (presence-only switch, any value: the two defaults agree only when the variable is set)
-  const bool debug = env_int("BTSBOT_AMD_DEBUG_SIDE", 0) == env_int("BTSBOT_AMD_DEBUG_SIDE", 1);
+  const bool debug = switch_set(SW_DEBUG_SIDE);
   hipStream_t chosen = nullptr;
   bool apart = false;
   for (int attempt = 0; attempt < 8 && chosen == nullptr; ++attempt) {
@@ -1204,7 +1167,7 @@ static int side_event(btsbot_ctx* h, hipEvent_t* e) {
 
 int side_fork(btsbot_ctx* h, hipStream_t st, hipStream_t* sd) {
   *sd = st;
-  if (!h->use_side || h->side == nullptr) return BTSBOT_OK;
+  if (!h->sched.side_stream || h->side == nullptr) return BTSBOT_OK;
   hipEvent_t e;
   TRY(side_event(h, &e));
   HIP_TRY(hipEventRecord(e, st));
@@ -1214,7 +1177,7 @@ int side_fork(btsbot_ctx* h, hipStream_t st, hipStream_t* sd) {
 }
 
 int side_join(btsbot_ctx* h, hipStream_t st) {
-  if (!h->use_side || h->side == nullptr) return BTSBOT_OK;
+  if (!h->sched.side_stream || h->side == nullptr) return BTSBOT_OK;
   hipEvent_t e;
   TRY(side_event(h, &e));
   HIP_TRY(hipEventRecord(e, h->side));

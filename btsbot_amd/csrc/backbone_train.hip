@@ -72,6 +72,7 @@ size_t al(size_t n) { return (n + 255) / 256 * 256; }
 // carve the cache for a batch of B alerts; base == nullptr only measures
 BBCache carve_bb(const btsbot_ctx* h, unsigned char* base, int B) {
   const btsbot_config& c = h->cfg;
+  const Schedule& sc = h->sched;
   const size_t esz = h->esz();
   BBCache k;
   size_t cur = 0;
@@ -89,20 +90,20 @@ BBCache carve_bb(const btsbot_ctx* h, unsigned char* base, int B) {
     if (i > 0 && rows * 4 * c.dims[i - 1] > maxpat) maxpat = rows * 4 * c.dims[i - 1];
     // (stage 2 under stage2p_kernel's keeping form: room for 9 more alerts behind the batch -- the kernel stores the rows
     //  of a ragged last workgroup and of its pad columns unconditionally, stage2p.hip)
-    const size_t prows = i == 2 && h->s2p_train ? rows + 9 * 9 : rows;
+    const size_t prows = i == 2 && sc.s2_keep ? rows + 9 * 9 : rows;
     for (int j = 0; j < c.depths[i]; ++j) {
       BlkBuf b;
       b.xin = reinterpret_cast<float*>(take(prows * ch * 4));
       b.d = reinterpret_cast<float*>(take(prows * ch * 4));
       b.xn = take(prows * ch * esz);
-      const bool keep4c = !h->mlp_fused((int)ch);   // fused blocks keep nothing 4C-wide (mlp_bwd.hip recomputes fc1)
+      const bool keep4c = !sc.mlp_bwd[i];   // fused blocks keep nothing 4C-wide (mlp_bwd.hip recomputes fc1)
       b.a = keep4c ? take(prows * 4 * ch * esz) : nullptr;
       b.h = keep4c ? take(prows * 4 * ch * esz) : nullptr;
       b.dyT = take(rows * ch * esz);
       b.da = keep4c ? take((rows + 48) * 4 * ch * esz) : nullptr;   // (+ 48 rows: s2mlp_bwd_kernel's last workgroup stores its dead rows too)
-      b.dwrows = h->use_dwln && dwln_bwd_supported(STAGE_HW[i], (int)ch) ? dwln_bwd_rows(STAGE_HW[i], (int)ch, B) : 0;
+      b.dwrows = sc.dwln && dwln_bwd_supported(STAGE_HW[i], (int)ch) ? dwln_bwd_rows(STAGE_HW[i], (int)ch, B) : 0;
       b.dwpart = b.dwrows ? reinterpret_cast<float*>(take((size_t)b.dwrows * 52 * ch * 4)) : nullptr;
-      b.fpart = h->mlp_fused((int)ch) ? reinterpret_cast<float*>(take(mlp_bwd_part_floats((int)ch, (int)rows) * 4))
+      b.fpart = sc.mlp_bwd[i] ? reinterpret_cast<float*>(take(mlp_bwd_part_floats((int)ch, (int)rows) * 4))
                                       : nullptr;
       b.fS = nullptr;
       b.Gb = b.Sb = nullptr;
@@ -110,7 +111,7 @@ BBCache carve_bb(const btsbot_ctx* h, unsigned char* base, int B) {
     }
     k.dyT_down[i] = i > 0 ? take(rows * ch * esz) : nullptr;
     if (rows * ch > maxrc) maxrc = rows * ch;
-    if (h->mlp_fused((int)ch) && rows * ch * mlp_bwd_planes((int)ch) > maxplanes) maxplanes = rows * ch * mlp_bwd_planes((int)ch);
+    if (sc.mlp_bwd[i] && rows * ch * mlp_bwd_planes((int)ch) > maxplanes) maxplanes = rows * ch * mlp_bwd_planes((int)ch);
     if (4 * ch * ch > maxc4c) maxc4c = 4 * ch * ch;
     if (i > 0 && 4 * ch * c.dims[i - 1] > maxc4c) maxc4c = 4 * ch * c.dims[i - 1];
   }
@@ -137,7 +138,7 @@ BBCache carve_bb(const btsbot_ctx* h, unsigned char* base, int B) {
     const size_t start = cur;
     for (int i = 0; i < 4; ++i) {
       const size_t ch = c.dims[i];
-      if (!h->wgrad_batch || h->mlp_fused((int)ch) || (ch & 127) != 0 || c.precision == BTSBOT_F32) continue;
+      if (!sc.wgrad_batch || sc.mlp_bwd[i] || (ch & 127) != 0 || c.precision == BTSBOT_F32) continue;
       for (auto& b : k.blk[i]) {
         b.Gb = reinterpret_cast<float*>(take(4 * ch * ch * 4));
         b.Sb = reinterpret_cast<float*>(take(ch * 4));
@@ -151,22 +152,57 @@ BBCache carve_bb(const btsbot_ctx* h, unsigned char* base, int B) {
   k.stem_patches = take((size_t)B * 225 * 48 * esz);
   k.stem_pre = reinterpret_cast<float*>(take((size_t)B * 225 * c.dims[0] * 4));
   k.namax = 2 * (c.depths[0] + c.depths[1] + c.depths[2] + c.depths[3]) + 5;
-  k.amax = h->train_split ? reinterpret_cast<unsigned*>(take((size_t)k.namax * AMAX_WORDS * 4)) : nullptr;
+  k.amax = sc.train_split ? reinterpret_cast<unsigned*>(take((size_t)k.namax * AMAX_WORDS * 4)) : nullptr;
   k.total = cur;
   return k;
 }
-
-// the training forward of a batch of B alerts runs stage 2 through stage2p_kernel's keeping form, which does not keep the
-// blocks' depthwise outputs (BlkBuf::d).  Up to two rounds of one workgroup (5 alerts) per CU: 2.50 against 2.57 ms per
-// 1024-alert step; at 4096 alerts the per-op GEMMs (36 864 rows: full tiles, full rounds) are as fast or faster (7.95
-// against 8.00 ms), so large batches keep them
-bool s2_kept(const btsbot_ctx* h, int B) { return h->s2p_train && B <= 2560; }
 
 #define TRYB(call)                  \
   do {                              \
     int _s = (call);                \
     if (_s != BTSBOT_OK) return _s; \
   } while (0)
+
+// One 1x1 / downsample product of the training step, out = epi(A W^T): under train_split on split operands -- W's split
+// planes at slot `sw`, a gradient operand A scaled by its amax record, amax_out the record of a gradient it writes
+// (gemm_x2.hip) -- else in the handle's operand type with the packed filter at slot `w`
+int train_gemm(const btsbot_ctx* h, int epi, const void* A, size_t w, size_t sw, const float* bias, const float* scale,
+               const float* aux, void* out, int M, int N, int K, const unsigned* amax_a, unsigned* amax_out, hipStream_t st) {
+  const bool sp = h->sched.train_split;
+  const unsigned char* W = h->image(sp ? sw : w);
+  if (W == nullptr) {
+    btsbot_set_error("training step: the %s filter image of a %d x %d product does not exist on this handle", sp ? "split" : "packed",
+                     N, K);
+    return BTSBOT_ERR_STATE;
+  }
+  if (sp)
+    return launch_gemm_x2_train(epi, reinterpret_cast<const float*>(A), W, bias, scale, aux, reinterpret_cast<float*>(out), M, N,
+                                K, amax_a, amax_out, st);
+  return launch_gemm(h->cfg.precision, epi, A, W, bias, scale, aux, out, M, N, K, st);
+}
+
+// One filter gradient: out[n][k] += sum_m D[m][n] A[m][k] and cs[n] += sum_m D[m][n].  Under train_split on split
+// operands (wgrad_x2.hip): D scaled by its amax record (A by `aamax`, if it has one), the column sum in fp32 on the
+// unscaled D inside the same launch; else D and A in the handle's operand type
+int train_wgrad(const btsbot_ctx* h, const void* D, const void* A, const unsigned* damax, const unsigned* aamax, float* out,
+                float* cs, int M, int N, int K, int ldo, hipStream_t st, float* part = nullptr, WgradReduceJob* defer = nullptr) {
+  const int prec = h->cfg.precision;
+  if (h->sched.train_split)
+    return launch_wgrad_x2(reinterpret_cast<const float*>(D), reinterpret_cast<const float*>(A), out, cs, M, N, K, ldo, damax,
+                           aamax, st, part, WPART_FLOATS, defer);
+  if (defer != nullptr) defer->nsl = 0;
+  if (prec != BTSBOT_F32) {
+    // (deterministic mode: the column sum as a launch of its own -- inside the filter-gradient GEMM its slices meet
+    //  through atomics; launch_colsum writes partial rows and adds them in a fixed order)
+    float* probe = det_alloc(0);
+    if (probe != nullptr && cs != nullptr) {
+      const int rc = launch_wgrad16(prec, D, A, out, nullptr, M, N, K, ldo, st, part, WPART_FLOATS, defer);
+      return rc != BTSBOT_OK ? rc : launch_colsum(prec, D, cs, M, N, st);
+    }
+    return launch_wgrad16(prec, D, A, out, cs, M, N, K, ldo, st, part, WPART_FLOATS, defer);
+  }
+  return launch_wgrad_cs_f32(reinterpret_cast<const float*>(D), reinterpret_cast<const float*>(A), out, cs, M, N, K, ldo, st);
+}
 
 }  // namespace
 
@@ -177,6 +213,7 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
                            float** feat_out) {
   const btsbot_config& c = h->cfg;
   const float* m = h->mirror;
+  const Schedule& sc = h->sched;
   BBCache k = carve_bb(h, h->bbcache, B);
   // A block's input is kept for its backward.  Instead of copying it aside, every producer writes
   // straight into the buffer its consumer keeps: the stem / downsample into block 0's xin, block j's
@@ -184,8 +221,7 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
   auto stage_in = [&](int i) { return h->blocks[i].empty() ? k.xs[i] : k.blk[i][0].xin; };
   // (the pre-LayerNorm output is kept for the backward; 16-bit modes: the matrix-pipe stem, which like stem_kernel reads
   //  nothing packed -- the operand re-pack of this step runs on the side stream meanwhile)
-  const bool s0t = h->s0_train && h->blocks[0].size() == 2 && h->mlp_fused(c.dims[0]) && h->use_dwln;
-  if (s0t) {
+  if (sc.s0_keep) {
     // stem + stage 0 + the first downsample as one launch of the inference megakernel's keeping form: every buffer the
     // backward reads of them is written on its way (stage0.h).  It needs this step's operand images at once: the
     // re-pack queued behind the previous optimiser step runs under the mask draws and whatever precedes this call
@@ -205,27 +241,23 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
     a.keep_patches = k.patches[1];
     a.B = B;
     TRYB(launch_stage0b(c.precision, a, st));
-  } else if (h->use_stem16 && stem16_supported(c.precision, c.dims[0]))
+  } else if (sc.stem16)
     TRYB(launch_stem16(c.precision, img, m + h->stem_w, m + h->stem_b, m + h->stem_lnw, m + h->stem_lnb, stage_in(0), B,
                        c.dims[0], st, k.stem_pre));
   else
     TRYB(launch_stem(img, m + h->stem_w, m + h->stem_b, m + h->stem_lnw, m + h->stem_lnb, stage_in(0),
                      B, c.dims[0], st, k.stem_pre));
   TRYB(pack_sync(h, st));   // the operand images of this step (packed on the side stream while the stem ran)
-  const bool s1t = h->s1_train && h->blocks[1].size() == 2 && h->mlp_fused(c.dims[1]) && h->use_dwln;
-  const bool s2t = s2_kept(h, B);
+  // (stage 2's form does not keep the blocks' depthwise outputs, BlkBuf::d)
+  const bool s0t = sc.s0_keep, s1t = sc.s1_keep, s2t = sc.s2_kept(B);
   for (int i = s0t ? 1 : 0; i < 4; ++i) {
     const int ch = c.dims[i], hw = STAGE_HW[i], rows = B * hw * hw;
     if (i > 0 && !(i == 3 && s2t) && !(i == 1 && s0t) && !(i == 2 && s1t)) {
       const int cin = c.dims[i - 1];
       TRYB(launch_ln_patch(c.precision, k.xs[i - 1], m + h->down[i].ln_w, m + h->down[i].ln_b,
                            k.patches[i], B, STAGE_HW[i - 1], cin, st));
-      if (h->train_split)
-        TRYB(launch_gemm_x2_train(EPI_BIAS, reinterpret_cast<const float*>(k.patches[i]), IMG(h, h->down[i].p_s_w),
-                                  m + h->down[i].b, nullptr, nullptr, stage_in(i), rows, ch, 4 * cin, nullptr, nullptr, st));
-      else
-      TRYB(launch_gemm(c.precision, EPI_BIAS, k.patches[i], IMG(h, h->down[i].p_w),
-                       m + h->down[i].b, nullptr, nullptr, stage_in(i), rows, ch, 4 * cin, st));
+      TRYB(train_gemm(h, EPI_BIAS, k.patches[i], h->down[i].p_w, h->down[i].p_s_w, m + h->down[i].b, nullptr, nullptr,
+                      stage_in(i), rows, ch, 4 * cin, nullptr, nullptr, st));
     }
     const size_t nblk = h->blocks[i].size();
     if (i == 1 && s1t) {
@@ -283,18 +315,11 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
                               rows, st, nullptr, nullptr, nullptr, 0, s.xin));
         continue;
       }
-      if (h->train_split) {   // (split training: the activations enter the products unscaled, as in inference)
-        TRYB(launch_gemm_x2_train(EPI_GELU_SAVE, reinterpret_cast<const float*>(s.xn), IMG(h, b.p_s_fc1), m + b.fc1_b,
-                                  nullptr, reinterpret_cast<const float*>(s.a), reinterpret_cast<float*>(s.h), rows, 4 * ch,
-                                  ch, nullptr, nullptr, st));
-        TRYB(launch_gemm_x2_train(EPI_RESID, reinterpret_cast<const float*>(s.h), IMG(h, b.p_s_fc2), m + b.fc2_b,
-                                  m + b.gamma, s.xin, xout, rows, ch, 4 * ch, nullptr, nullptr, st));
-        continue;
-      }
-      TRYB(launch_gemm(c.precision, EPI_GELU_SAVE, s.xn, IMG(h, b.p_fc1), m + b.fc1_b, nullptr,
-                       reinterpret_cast<const float*>(s.a), s.h, rows, 4 * ch, ch, st));
-      TRYB(launch_gemm(c.precision, EPI_RESID, s.h, IMG(h, b.p_fc2), m + b.fc2_b, m + b.gamma,
-                       s.xin, xout, rows, ch, 4 * ch, st));
+      // (split training: the activations enter the products unscaled, as in inference)
+      TRYB(train_gemm(h, EPI_GELU_SAVE, s.xn, b.p_fc1, b.p_s_fc1, m + b.fc1_b, nullptr, reinterpret_cast<const float*>(s.a), s.h,
+                      rows, 4 * ch, ch, nullptr, nullptr, st));
+      TRYB(train_gemm(h, EPI_RESID, s.h, b.p_fc2, b.p_s_fc2, m + b.fc2_b, m + b.gamma, s.xin, xout, rows, ch, 4 * ch, nullptr,
+                      nullptr, st));
     }
   }
   *feat_out = k.xs[3];
@@ -306,39 +331,14 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
 // (before the head LayerNorm, which the caller has already differentiated).  Gradients are
 // ACCUMULATED (atomics) into `grads` (master-arena layout): the caller zeroes the image-branch
 // range first.
-// out[n][k] += sum_m D[m][n] A[m][k] and cs[n] += sum_m D[m][n]; D and A in the mode's operand type
-static int wgrad_cs(int prec, const void* D, const void* A, float* out, float* cs, int M, int N,
-                    int K, int ldo, hipStream_t st, float* part = nullptr, WgradReduceJob* defer = nullptr) {
-  if (defer != nullptr) defer->nsl = 0;
-  if (prec != BTSBOT_F32) {
-    // (deterministic mode: the column sum as a launch of its own -- inside the filter-gradient GEMM its slices meet
-    //  through atomics; launch_colsum writes partial rows and adds them in a fixed order)
-    float* probe = det_alloc(0);
-    if (probe != nullptr && cs != nullptr) {
-      const int rc = launch_wgrad16(prec, D, A, out, nullptr, M, N, K, ldo, st, part, WPART_FLOATS, defer);
-      return rc != BTSBOT_OK ? rc : launch_colsum(prec, D, cs, M, N, st);
-    }
-    return launch_wgrad16(prec, D, A, out, cs, M, N, K, ldo, st, part, WPART_FLOATS, defer);
-  }
-  return launch_wgrad_cs_f32(reinterpret_cast<const float*>(D), reinterpret_cast<const float*>(A), out, cs, M, N, K, ldo, st);
-}
-
-// the same on split operands (split training): D's scale from its largest magnitude (damax's record); the column sum in
-// fp32 on the unscaled D, inside the same launch
-static int wgrad_cs_x2(const void* D, const void* A, const unsigned* damax, float* out, float* cs, int M, int N, int K,
-                       int ldo, hipStream_t st, float* part, WgradReduceJob* defer = nullptr, const unsigned* aamax = nullptr) {
-  const float* d = reinterpret_cast<const float*>(D);
-  return launch_wgrad_x2(d, reinterpret_cast<const float*>(A), out, cs, M, N, K, ldo, damax, aamax, st, part, WPART_FLOATS,
-                         defer);
-}
-
 int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat, float* grads,
                             int B, hipStream_t st) {
   const btsbot_config& c = h->cfg;
   const float* m = h->mirror;
   const int prec = c.precision;
+  const Schedule& sc = h->sched;
   BBCache k = carve_bb(h, h->bbcache, B);
-  const bool s2t = s2_kept(h, B);
+  const bool s2t = sc.s2_kept(B);
   float* dy = k.dyA;
   float* dxn = k.dyB;
   TRYB(launch_copy_f32(dy, dfeat, (size_t)B * c.dims[3], st));
@@ -384,7 +384,7 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
     float* z0 = k.fS0 != nullptr ? k.fS0 : k.S;
     TRYB(launch_fill0(z0, (size_t)((k.G + k.g_floats) - z0), st));
   }
-  const bool sp = h->train_split;
+  const bool sp = sc.train_split;
   if (sp) TRYB(launch_fill0(reinterpret_cast<float*>(k.amax), (size_t)k.namax * AMAX_WORDS, st));
   auto amax_rec = [&](int slot) { return k.amax + (size_t)slot * AMAX_WORDS; };
   auto blk_amax = [&](int i, int j) {   // dy slot of block (i, j); its da slot follows
@@ -404,7 +404,7 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
   // (at the end of the chain it was 36 us of the step's tail)
   // (no fork of its own: it reads the caller's triplets, which the forward already read on this stream, and the side
   //  stream has the head's backward in front of it, queued behind a fork a few launches ago)
-  if (h->use_side && h->side != nullptr) sd = h->side;
+  if (sc.side_stream && h->side != nullptr) sd = h->side;
   TRYB(launch_stem_im2col(prec, img, k.stem_patches, B, sd));
   bool dyT_ready = false;
   for (int i = 3; i >= 0; --i) {
@@ -442,28 +442,21 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
         TRYB(launch_mlp_bwd(prec, ch, s.xn, s.dyT, IMG(h, b.p_fc1), IMG(h, b.p_fc2t), m + b.fc1_b, dxn, s.fpart,
                             k.G, s.fS, grads + b.fc1_w, grads + b.fc1_b, rows, st, red));
         TRYB(fork());
-      } else if (h->s2mlp && b.p_w1tp != 0 && s2mlp_bwd_supported(prec, ch)) {
+      } else if (sc.s2mlp && b.p_w1tp != 0 && s2mlp_bwd_supported(prec, ch)) {
         // ---- 256 channels: da = (dy (diag(gamma) W2)) * gelu'(a) and dxn = da W1 in one launch (s2mlp_bwd.hip)
         TRYB(launch_s2mlp_bwd(prec, s.dyT, s.a, IMG(h, b.p_w2tp), IMG(h, b.p_w1tp), s.da, dxn, rows, st));
-        if (!batched || h->fork_per_block) TRYB(fork());
-      } else if (sp) {
-        // ---- split training: the two products below on split operands (dy, da scaled by their own powers of two)
-        TRYB(launch_gemm_x2_train(EPI_DGELU, reinterpret_cast<const float*>(s.dyT), IMG(h, b.p_s_fc2t), nullptr, nullptr,
-                                  reinterpret_cast<const float*>(s.a), reinterpret_cast<float*>(s.da), rows, H, ch, am_dy,
-                                  am_da, st));
-        TRYB(fork());
-        TRYB(launch_gemm_x2_train(EPI_PLAIN, reinterpret_cast<const float*>(s.da), IMG(h, b.p_s_fc1t), nullptr, nullptr,
-                                  nullptr, dxn, rows, ch, H, am_da, nullptr, st));
+        if (!batched || sc.fork_per_block) TRYB(fork());
       } else {
-      // ---- da = (dy (diag(gamma) W2)) * gelu'(a)     (gamma is folded into the packed W2^T)
-      TRYB(launch_gemm(prec, EPI_DGELU, s.dyT, IMG(h, b.p_fc2t), nullptr, nullptr,
-                       reinterpret_cast<const float*>(s.a), s.da, rows, H, ch, st));
-      // the side stream may start once da exists; its work is queued below, behind the chain's (a block whose GEMMs wait
-      // for the stage's batch has nothing for it yet)
-      if (!batched || h->fork_per_block) TRYB(fork());
-      // ---- dxn = da W1, then the LayerNorm backward on the depthwise output d = dwconv(x_in) + bias the forward kept
-      TRYB(launch_gemm(prec, EPI_PLAIN, s.da, IMG(h, b.p_fc1t), nullptr, nullptr, nullptr, dxn,
-                       rows, ch, H, st));
+        // ---- da = (dy (diag(gamma) W2)) * gelu'(a)     (gamma is folded into the packed W2^T; split training: dy, da
+        //      scaled by their own powers of two)
+        TRYB(train_gemm(h, EPI_DGELU, s.dyT, b.p_fc2t, b.p_s_fc2t, nullptr, nullptr, reinterpret_cast<const float*>(s.a), s.da,
+                        rows, H, ch, am_dy, am_da, st));
+        // the side stream may start once da exists; its work is queued below, behind the chain's (a block whose GEMMs wait
+        // for the stage's batch has nothing for it yet; split training batches none)
+        if (!batched || sc.fork_per_block) TRYB(fork());
+        // ---- dxn = da W1, then the LayerNorm backward on the depthwise output d = dwconv(x_in) + bias the forward kept
+        TRYB(train_gemm(h, EPI_PLAIN, s.da, b.p_fc1t, b.p_s_fc1t, nullptr, nullptr, nullptr, dxn, rows, ch, H, am_da, nullptr,
+                        st));
       }
       void* nxt = fold_cast ? next_dyT(i, j) : nullptr;
       // (the partial rows follow the arena's layout of conv_dw.weight | conv_dw.bias | norm.weight | norm.bias)
@@ -476,7 +469,7 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
         // ---- LayerNorm backward, depthwise filter gradient and dx = dy + conv_flipped(dd) in one launch
         TRYB(launch_dwln_bwd(s.d, dxn, m + b.ln_w, s.xin, wdw, dy, nxt, prec, s.dwpart, B, hw, ch, st, planes, (size_t)rows * ch));
         TRYB(add_pend(s.dwpart, grads + b.dw_w, s.dwrows, 52 * ch));
-      } else if (hw == 1 && h->use_dwln && ch <= 640) {
+      } else if (hw == 1 && sc.dwln && ch <= 640) {
         // ---- 1x1 maps: the same three steps per (alert, channel) in one launch
         TRYB(launch_ln_dw1_bwd(s.d, dxn, m + b.ln_w, s.xin, wdw, dy, nxt, prec, grads + b.ln_w, grads + b.ln_b,
                                grads + b.dw_w, grads + b.dw_b, rows, ch, st));
@@ -499,14 +492,10 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
         dyT_ready = nxt != nullptr;
         continue;
       }
-      if (sp) {
-        TRYB(wgrad_cs_x2(s.dyT, s.h, am_dy, k.G, k.S, rows, ch, H, H, sd, k.wpart, &red[0]));
-        TRYB(wgrad_cs_x2(s.da, s.xn, am_da, grads + b.fc1_w, grads + b.fc1_b, rows, H, ch, ch, sd, k.wpart + WPART_FLOATS,
-                         &red[1]));
-      } else if (s.fpart == nullptr) {
-      TRYB(wgrad_cs(prec, s.dyT, s.h, k.G, k.S, rows, ch, H, H, sd, k.wpart, &red[0]));
-      TRYB(wgrad_cs(prec, s.da, s.xn, grads + b.fc1_w, grads + b.fc1_b, rows, H, ch, ch, sd, k.wpart + WPART_FLOATS,
-                    &red[1]));
+      if (s.fpart == nullptr) {
+        TRYB(train_wgrad(h, s.dyT, s.h, am_dy, nullptr, k.G, k.S, rows, ch, H, H, sd, k.wpart, &red[0]));
+        TRYB(train_wgrad(h, s.da, s.xn, am_da, nullptr, grads + b.fc1_w, grads + b.fc1_b, rows, H, ch, ch, sd,
+                         k.wpart + WPART_FLOATS, &red[1]));
       }
       TRYB(launch_wgrad_reduce(red, 2, sd));
       TRYB(launch_fc2_grads(k.G, s.fpart != nullptr ? s.fS : k.S, m + b.fc2_w, m + b.fc2_b, m + b.gamma, grads + b.fc2_w,
@@ -528,7 +517,7 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
       return BTSBOT_OK;
     };
     // (with a downsample in front of the stage the batch shares that one's fork)
-    if (nbj > 0 && (i == 0 || h->fork_per_block)) {
+    if (nbj > 0 && (i == 0 || sc.fork_per_block)) {
       TRYB(fork());
       TRYB(stage_batch());
     }
@@ -545,12 +534,8 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
       dyT_ready = false;
       TRYB(fork());
       if (nbj > 0) TRYB(stage_batch());
-      if (sp)
-        TRYB(launch_gemm_x2_train(EPI_PLAIN, reinterpret_cast<const float*>(dyT), IMG(h, h->down[i].p_s_wt), nullptr,
-                                  nullptr, nullptr, k.dpat, rows, 4 * cin, ch, am_dn, nullptr, st));
-      else
-      TRYB(launch_gemm(prec, EPI_PLAIN, dyT, IMG(h, h->down[i].p_wt), nullptr, nullptr,
-                       nullptr, k.dpat, rows, 4 * cin, ch, st));
+      TRYB(train_gemm(h, EPI_PLAIN, dyT, h->down[i].p_wt, h->down[i].p_s_wt, nullptr, nullptr, nullptr, k.dpat, rows, 4 * cin,
+                      ch, am_dn, nullptr, st));
       // LN backward per input pixel (x_prev = stage i-1 output), its incoming gradient gathered from the patch matrix
       // (was an unpatch launch); result is the new dy, in the 16-bit modes also as the operand of stage i-1's last
       // block (was a cast launch)
@@ -559,10 +544,7 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
                          grads + h->down[i].ln_b, prow, cin, st, nxt16, prec, hwp));
       dyT_ready = nxt16 != nullptr;
       // (side work queued behind the chain's launches, as in the blocks)
-      if (sp)
-        TRYB(wgrad_cs_x2(dyT, k.patches[i], am_dn, k.G, grads + h->down[i].b, rows, ch, 4 * cin, 4 * cin, sd, k.wpart));
-      else
-      TRYB(wgrad_cs(prec, dyT, k.patches[i], k.G, grads + h->down[i].b, rows, ch, 4 * cin, 4 * cin, sd, k.wpart));
+      TRYB(train_wgrad(h, dyT, k.patches[i], am_dn, nullptr, k.G, grads + h->down[i].b, rows, ch, 4 * cin, 4 * cin, sd, k.wpart));
       TRYB(launch_unpack_down_grad(k.G, grads + h->down[i].w, ch, cin, sd));
     }
     // every gradient of stages.i.* (and, for i = 3, of the heads) is queued: bucket 3 - i is complete once the
@@ -578,22 +560,17 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
     const int c0 = c.dims[0], rows = B * 225;
     TRYB(launch_ln_bwd(k.stem_pre, dy, m + h->stem_lnw, dxn, grads + h->stem_lnw,
                        grads + h->stem_lnb, rows, c0, st, fold_cast ? k.dyT_stem : nullptr, prec));
-    if (sp) {
-      // (split training: the stem's filter gradient on split operands too -- its fp32 kernel meets through atomics; the
-      //  patches are raw pixel values, scaled like the gradient)
-      unsigned* am = amax_rec(k.namax - 5);
+    // (split training: the stem's filter gradient on split operands too -- its fp32 kernel meets through atomics; the
+    //  patches are raw pixel values, scaled like the gradient)
+    unsigned* am = sp ? amax_rec(k.namax - 5) : nullptr;
+    unsigned* am_pat = sp ? amax_rec(k.namax - 1) : nullptr;
+    if (sp)
       TRYB(launch_copy_amax(dxn, reinterpret_cast<float*>(k.dyT_stem), (long)rows * c0, am, st));
-      TRYB(fork());
-      TRYB(launch_copy_amax(reinterpret_cast<const float*>(k.stem_patches), nullptr, (long)rows * 48, amax_rec(k.namax - 1),
-                            sd));
-      TRYB(wgrad_cs_x2(k.dyT_stem, k.stem_patches, am, grads + h->stem_w, grads + h->stem_b, rows, c0, 48, 48, sd,
-                       k.wpart, nullptr, amax_rec(k.namax - 1)));
-    } else {
-    if (!fold_cast) TRYB(launch_scale_cast(prec, dxn, nullptr, k.dyT_stem, (long)rows * c0, c0, st));
+    else if (!fold_cast)
+      TRYB(launch_scale_cast(prec, dxn, nullptr, k.dyT_stem, (long)rows * c0, c0, st));
     TRYB(fork());
-    TRYB(wgrad_cs(prec, k.dyT_stem, k.stem_patches, grads + h->stem_w, grads + h->stem_b, rows, c0, 48, 48,
-                  sd, k.wpart));
-    }
+    if (sp) TRYB(launch_copy_amax(reinterpret_cast<const float*>(k.stem_patches), nullptr, (long)rows * 48, am_pat, sd));
+    TRYB(train_wgrad(h, k.dyT_stem, k.stem_patches, am, am_pat, grads + h->stem_w, grads + h->stem_b, rows, c0, 48, 48, sd, k.wpart));
   }
   TRYB(join());
   if (h->n_buckets == 3 && h->bucket_fine) HIP_TRY(hipEventRecord(h->bucket_ev[2], st));

@@ -766,7 +766,7 @@ int wgrad_f32(const void* Dv, const void* Av, float* out, int M, int N, int K, i
   const float* D = reinterpret_cast<const float*>(Dv);
   const float* A = reinterpret_cast<const float*>(Av);
   if (cs_done != nullptr) *cs_done = false;
-  static const bool old_form = env_on("BTSBOT_AMD_WGRAD_F32_OLD");   // 1: the 64 x 64 kernel for every shape (A/B timing, parity)
+  static const bool old_form = switch_on(SW_WGRAD_F32_OLD);   // 1: the 64 x 64 kernel for every shape (A/B timing, parity)
   const bool aligned = ((reinterpret_cast<uintptr_t>(D) | reinterpret_cast<uintptr_t>(A)) & 15) == 0;
   if (!old_form && aligned && N % 64 == 0 && K % 64 == 0) {
     // (deterministic mode: the column sums keep their own launch with its fixed-order reduction)
@@ -1102,7 +1102,7 @@ int launch_ln_bwd(const float* d, const float* dxn, const float* g, float* dd, f
                   float* dbeta, long rows, int C, hipStream_t st, void* out16, int prec16, int patch_hw) {
   if (rows <= 0) return BTSBOT_OK;
   static const long cap = [] {
-    const long v = env_int("BTSBOT_AMD_LNBWD_BLOCKS", 0);   // tuning knob: workgroups (= same-address atomics per channel;
+    const long v = switch_int(SW_LNBWD_BLOCKS, 0);   // tuning knob: workgroups (= same-address atomics per channel;
                                                             //  measured per step: 256 4.64 ms, 384/512 4.58, 1024 4.70, 2048 5.02)
     return v >= 1 ? v : 512;
   }();

@@ -94,16 +94,7 @@ struct DevOnce {
   void done() { mask.fetch_or(1ULL << dev(), std::memory_order_relaxed); }
 };
 
-// Developer switches (BTSBOT_AMD_*): on when the variable is set and its value starts with '1'; integer knobs read
-// atoi(value), `dflt` when the variable is not set (each caller keeps its own range check)
-inline bool env_on(const char* name) {
-  const char* e = getenv(name);
-  return e != nullptr && e[0] == '1';
-}
-inline int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e != nullptr ? atoi(e) : dflt;
-}
+#include "schedule.h"   // the developer switches (BTSBOT_AMD_*): switch_on() / switch_int()
 
 // ---------------------------------------------------------------------------------------
 // error plumbing (no exception crosses the ABI)

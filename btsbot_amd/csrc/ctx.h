@@ -29,7 +29,6 @@ struct BlockPk {  // per ConvNeXt block: master offsets + packed offsets (bytes 
   // split training ("train_split"): p_fc1 / p_fc2 / p_fc1t / p_fc2t as f16 head + remainder planes, [n] heads then [n]
   // remainders (slots of their own: the per-op inference forward of the split mode reads the fp32 p_fc1 / p_fc2)
   size_t p_s_fc1 = 0, p_s_fc2 = 0, p_s_fc1t = 0, p_s_fc2t = 0;
-  bool fused;
 };
 struct DownPk {
   int64_t ln_w, ln_b, w, b;
@@ -128,9 +127,16 @@ struct btsbot_ctx {
   int prec_head() const { return x2 ? BTSBOT_F16 : cfg.precision; }   // head16.hip splits its operands in every mode
   int prec_s01() const { return x2 ? BTSBOT_F16X2 : cfg.precision; }   // operand mode of stage0b.hip / stage1b.hip
   size_t p_m1h = 0, p_m2h = 0, p_combh[3] = {0, 0, 0};   // head16.hip: the Linear filters as split A fragments
-  bool head16 = false;     // the 16-bit modes run the head on the matrix pipe (head16.hip)
-  bool use_head16 = true;  // BTSBOT_AMD_NO_HEAD16=1: the fp32 VALU head (head.hip) instead
-  bool stage0 = false;     // stem + stage 0 + first downsample as one kernel
+
+  // which kernel runs what (schedule.h): sw = the HANDLE-scope switches as btsbot_create found them (INT_MIN: not set),
+  // opt_* = what btsbot_set_option / btsbot_reserve_train asked for; resolve_schedule() makes `sched` of them
+  int sw[SW_COUNT];
+  bool opt_deterministic = false;   // btsbot_set_option("deterministic") / BTSBOT_AMD_DETERMINISTIC=1
+  // btsbot_set_option("train_split"), BTSBOT_F16X2 ConvNeXt handles: the training step's 1x1 / downsample products (forward,
+  // input gradients, filter gradients) run on split operands (gemm_x2.hip, wgrad_x2.hip) instead of the fp32 MFMA
+  bool opt_train_split = false;
+  bool opt_train_packs = false;     // also pack the dgrad transposes (set by btsbot_reserve_train)
+  Schedule sched;
 
   // device memory
   float* mirror = nullptr;          // fp32 copy of the master arena (same offsets)
@@ -139,7 +145,7 @@ struct btsbot_ctx {
   std::vector<ImageEntry> images;   // pack.hip
   size_t extra_fixed = 256;         // where they start: behind offset 0 and a MaxViT branch's images (maxvit_build_tables)
   void* pack_jobs[3] = {nullptr, nullptr, nullptr};   // (pack.hip) device tables of PackJob: [0] full pack, [1] training re-pack,
-  int pack_njobs[3] = {0, 0, 0}, pack_blocks[3] = {0, 0, 0};   // [2] the part of [1] the stage-0 megakernel reads (s0_train)
+  int pack_njobs[3] = {0, 0, 0}, pack_blocks[3] = {0, 0, 0};   // [2] the part of [1] the stage-0 megakernel reads (s0_keep)
   hipEvent_t pack_early_ev = nullptr;   // recorded behind that part and the stage-0 parameter images (pack_sync_early)
   bool pack_early = false;              // the running re-pack recorded it
   size_t extra_bytes = 0;
@@ -157,34 +163,19 @@ struct btsbot_ctx {
   std::vector<int> prof_cat;
   size_t prof_used = 0;
 
-  bool use_s2 = true;      // BTSBOT_AMD_NO_STAGE2=1: the per-op launches (dwconv_ln + fc1 / fc2 GEMMs) for stage 2
   int s2p_alerts_hint = 0; // btsbot_set_option("stage2p_alerts"): 0 = by rounds, 4 / 7 forced
-  bool use_s2p = true;     // (= use_s2: stage2p.hip is the stage-2 kernel)
-  bool stage2p = false;    // stage 2 + the last downsample as one persistent kernel
   bool fp8 = false;        // created with BTSBOT_FP8: cfg.precision reads BTSBOT_BF16, stages 2-3 run fp8 operands
   bool x2 = false;         // created with BTSBOT_F16X2: cfg.precision reads BTSBOT_F32 (the schedule of every kernel without
                            // a split-operand form), the kernels that have one run it
-  // (x2_tail_plain: developer experiment BTSBOT_AMD_X2_TAIL_F16=1 -- the split mode with stages 2-3 on plain f16 operands:
-  //  what does the mode's error owe to which stage?)
-  bool x2_tail_plain = false;
+  bool x2_tail_plain = false;   // BTSBOT_AMD_X2_TAIL_F16 (schedule.h)
   int prec_tail() const { return fp8 ? BTSBOT_FP8 : x2 ? (x2_tail_plain ? BTSBOT_F16 : BTSBOT_F16X2) : cfg.precision; }   // operand mode of stage2p.hip / stage3.hip
   int prec_down3() const { return x2 ? (x2_tail_plain ? BTSBOT_F16 : BTSBOT_F16X2) : cfg.precision; }   // ... of the last downsample inside stage2p.hip
-  bool stage3 = false;     // stage3.hip: the 1x1 stage as two fragment-streaming launches per block
-  bool use_s3 = true;      // BTSBOT_AMD_NO_S3=1: dwconv_ln + the generic GEMMs instead
-  bool use_fused = true;   // BTSBOT_AMD_NO_FUSED_MLP=1 keeps the two-GEMM path (A/B timing)
-  bool stage1 = false;     // stage 1 + second downsample as one kernel
-  bool use_stage0 = true;
-  bool use_stage1 = true;  // BTSBOT_AMD_NO_STAGE1=1 likewise for stage 1  // BTSBOT_AMD_NO_STAGE0=1 keeps the per-op schedule for stage 0
   // image-branch training cache (backbone_train.hip)
   unsigned char* bbcache = nullptr;
   int bbcache_batch = 0;
   int64_t img_floats = 0;     // master-arena floats [0, img_floats) belong to the image branch
   const float* t_img = nullptr;   // triplets of the last training forward (stem backward re-reads them)
-  bool train_packs = false;   // also pack the dgrad transposes (set by btsbot_reserve_train)
-  // btsbot_set_option("train_split"), BTSBOT_F16X2 ConvNeXt handles: the training step's 1x1 / downsample products (forward,
-  // input gradients, filter gradients) run on split operands (gemm_x2.hip, wgrad_x2.hip) instead of the fp32 MFMA
-  bool train_split = false;
-  void* split_jobs = nullptr;   // ... the re-pack's SplitJob table (device), built on the first training pack
+  void* split_jobs = nullptr;   // split training: the re-pack's SplitJob table (device), built on the first training pack
   int split_njobs = 0;
   bool bb_saved = false;      // the last training forward kept the image-branch activations
   // training cache (head_train.hip): activations of the last training-mode forward
@@ -205,19 +196,7 @@ struct btsbot_ctx {
   bool bucket_waits_seen = false, bucket_fine = false;
   bool meta_join_pending = false;   // the metadata branch's training forward sits on the side stream and `st` has not joined it yet
   hipStream_t xchg = nullptr;        // btsbot_allreduce_grads: the stream its collectives run on
-  // Training forward of stage 2 + the last downsample as ONE launch of stage2p_kernel's keeping form (16-bit modes, 256
-  // channels; needs the 3x3 LayerNorm / depthwise backward kernel, which recomputes the depthwise output the form does
-  // not keep).  BTSBOT_AMD_NO_S2P_TRAIN=1: the per-op launches (A/B timing, parity tests).
-  bool s2p_train = false;
-  // Training forward of stem + stage 0 + first downsample as ONE launch of the inference megakernel's keeping form
-  // (stage0b.hip, KEEP) instead of stem16 + 2 x (dwconv_ln + fused_mlp) + ln_patch + GEMM (16-bit modes).
-  // BTSBOT_AMD_NO_S0_TRAIN=1: the per-op launches (A/B timing, parity tests).
-  bool s0_train = false;
-  bool s1_train = false;             // likewise stage 1 + the second downsample (stage1b.hip, KEEP): default in the f16 mode,
-                                     // BTSBOT_AMD_S1_TRAIN=1 in bf16 (api.hip says why), BTSBOT_AMD_NO_S1_TRAIN=1 switches it off
-  bool use_stem16 = true;            // BTSBOT_AMD_NO_STEM16=1: the fp32 VALU stem in the 16-bit modes too (A/B, parity)
-  bool deterministic = false;        // btsbot_set_option("deterministic") / BTSBOT_AMD_DETERMINISTIC=1: fixed-order batch reductions
-  float* det_scratch = nullptr;      // ... their partial rows (sized at btsbot_reserve_train)
+  float* det_scratch = nullptr;      // deterministic mode: the partial rows of its reductions (sized at btsbot_reserve_train)
   size_t det_floats = 0;
   int exchange_mode = 0;             // btsbot_set_option("exchange"): 0 all-reduce per span, 1 reduce-scatter + all-gather
   const float* last_grad_arena = nullptr;   // what the last btsbot_backward() wrote (the bucket events belong to it)
@@ -236,27 +215,8 @@ struct btsbot_ctx {
   // first kernel of the training forward (the stem reads the fp32 mirror only).  Every consumer of the operand images
   // calls pack_sync() first.
   bool pack_on_side = false;
-  bool use_dwln = true;    // BTSBOT_AMD_NO_DWLN=1: LayerNorm / depthwise backward as three launches (A/B timing)
-  // widths whose block MLP runs fused in the training step (fused_mlp forward that keeps nothing 4C-wide + mlp_bwd_kernel):
-  // 64 and 128.  BTSBOT_AMD_MLP_BWD_C=64 / =128 restricts it to one width, BTSBOT_AMD_NO_MLP_BWD=1 switches it off (A/B
-  // runs and tests).  The 128-channel form hands dxn over as four addend planes which only dwln_bwd_kernel reads, so it
-  // is tied to that kernel (BTSBOT_AMD_NO_DWLN keeps stage 1 unfused).
-  int mlp_bwd_only = 0;
-  bool mlp_fused(int ch) const {
-    return mlp_bwd_only >= 0 && (mlp_bwd_only == 0 || mlp_bwd_only == ch) && use_fused && (ch == 64 || use_dwln) &&
-           mlp_bwd_supported(cfg.precision, ch) && fused_mlp_supported(cfg.precision, ch);
-  }
-  bool s2mlp = true;       // 256-channel blocks: da and dxn of the MLP backward as one launch (s2mlp_bwd.hip) instead of two tiled
-                           // GEMMs; BTSBOT_AMD_NO_S2MLP=1: the GEMMs (A/B timing, parity tests)
-  bool fork_per_block = false;   // BTSBOT_AMD_FORK_PER_BLOCK=1: the blocks of a batched stage fork the side stream one by one, as
-                                 // before the batch existed (A/B timing)
-  bool wgrad_batch = true; // stages whose blocks run the unfused MLP backward (256 / 512 channels): their 2 x depth filter-gradient
-                           // GEMMs as ONE launch + one slice reduction at the end of the stage's chain (wgrad.hip);
-                           // BTSBOT_AMD_NO_WGRAD_BATCH=1: one launch per GEMM behind each block (A/B timing, parity tests)
-  bool use_side = true;    // BTSBOT_AMD_NO_SIDE_STREAM=1: the whole backward on the caller's stream (A/B timing)
 
   unsigned long long* stamps = nullptr;   // btsbot_debug_stamps: STAMP_TOTAL entries, regions STAMP_* above
-  int s0_diag = 0, s2p_diag = 0;          // BTSBOT_AMD_S0_DIAG / _S2P_DIAG: Stage0Args::diag / Stage2pArgs::diag of inference
   bool debug = false;
   float* taps[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   int last_chunk = 0;
@@ -294,7 +254,7 @@ inline size_t bump(size_t& cur, size_t bytes) {
 // pack.hip
 int pack_layout(btsbot_ctx* h);       // lists the images, reserves their slots behind extra_fixed, sets extra_bytes
 int pack_params(btsbot_ctx* h, const float* master, hipStream_t st, bool train_only);
-int pack_invalidate(btsbot_ctx* h);   // a flag the image list reads has changed (train_packs): new list, new job tables
+int pack_invalidate(btsbot_ctx* h);   // a schedule field the image list reads has changed (train_packs): new list, new job tables
 void pack_release(btsbot_ctx* h);     // btsbot_destroy
 int pack_sync(btsbot_ctx* h, hipStream_t st);
 int pack_sync_early(btsbot_ctx* h, hipStream_t st);   // only what stage0b_kernel reads (else = pack_sync)

@@ -282,7 +282,7 @@ int launch_dw15_t(const float* x, const float* wdw, const float* bdw, const floa
 }  // namespace
 
 bool dw15_supported(int prec, int C) {
-  static const bool off = env_on("BTSBOT_AMD_NO_DW15");   // 1: the 15x15 depthwise + LayerNorm stays on the per-tap kernel (A/B)
+  static const bool off = switch_on(SW_NO_DW15);   // 1: the 15x15 depthwise + LayerNorm stays on the per-tap kernel (A/B)
   return !off && (prec == BTSBOT_BF16 || prec == BTSBOT_F16) && (C == 64 || C == 80);
 }
 

@@ -379,7 +379,7 @@ __global__ __launch_bounds__(256) void dw3_rows_kernel(const float* __restrict__
 // workgroups of the 3x3 kernel: at most 512 (up to three fit a CU), each a whole number of alerts
 int dw3_ga(int B) {
   static const int wgs = [] {
-    const int v = env_int("BTSBOT_AMD_DW3_WGS", 0);   // tuning knob
+    const int v = switch_int(SW_DW3_WGS, 0);   // tuning knob
     return v >= 1 ? v : 512;
   }();
   const int per = (B + wgs - 1) / wgs;
@@ -387,7 +387,7 @@ int dw3_ga(int B) {
 }
 int dw3_grid(int B) { return (B + dw3_ga(B) - 1) / dw3_ga(B); }
 bool dw3_old() {
-  static const bool v = env_on("BTSBOT_AMD_DW3_OLD");   // 1: the general kernel on the 3x3 maps too (A/B timing)
+  static const bool v = switch_on(SW_DW3_OLD);   // 1: the general kernel on the 3x3 maps too (A/B timing)
   return v;
 }
 

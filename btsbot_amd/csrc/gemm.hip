@@ -310,8 +310,8 @@ int launch_gemm(int prec, int epi, const void* X, const void* W, const float* bi
     btsbot_set_error("launch_gemm: grid too large (M=%d N=%d)", M, N);
     return BTSBOT_ERR_INVALID_ARG;
   }
-  static const bool v1_only = env_on("BTSBOT_AMD_GEMM_V1");   // A/B switch for timing
-  static const bool train_v1 = env_on("BTSBOT_AMD_TRAIN_GEMM_V1");   // A/B: training epilogues on the register-staged kernel
+  static const bool v1_only = switch_on(SW_GEMM_V1);   // A/B switch for timing
+  static const bool train_v1 = switch_on(SW_TRAIN_GEMM_V1);   // A/B: training epilogues on the register-staged kernel
   const bool train_epi = epi == EPI_GELU_SAVE || epi == EPI_DGELU || epi == EPI_PLAIN;
   if (!v1_only && !(train_epi && train_v1) && gemm2_supported(prec, M, N, K))
     return launch_gemm2(prec, epi, X, W, bias, gamma, resid, out, M, N, K, st);

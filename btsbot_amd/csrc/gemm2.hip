@@ -306,7 +306,7 @@ int launch_tile2(const T* x, const T* w, const float* bias, const float* gamma,
                  const float* resid, void* out, int M, int N, int K, hipStream_t st, int batch = 1,
                  long bsX = 0, long bsW = 0, long bsO = 0, const float* ln_w = nullptr,
                  const float* ln_b = nullptr, void* ln_out = nullptr) {
-  static const bool no_pre = env_on("BTSBOT_AMD_GEMM2_NO_PREFETCH");
+  static const bool no_pre = switch_on(SW_GEMM2_NO_PREFETCH);
   if constexpr (EPI == EPI_RESID || EPI == EPI_DGELU) {
     if (!no_pre)
       return launch_tile2p<T, TM, TN, WM, WN, EPI, NSLOT, true>(x, w, bias, gamma, resid, out, M, N, K, st, batch,
@@ -324,8 +324,8 @@ int launch_typed2(const void* X, const void* W, const float* bias, const float* 
   const long wg128 = (long)((M + 127) / 128) * ((N + 127) / 128);
   // K == 64 is a single k-tile: a one-slot ring halves (thirds) the LDS per workgroup, so twice (three
   // times) as many workgroups share a CU and cover each other's load -> MFMA -> store chain
-  static const bool one_slot = !env_on("BTSBOT_AMD_GEMM2_NO_1SLOT");
-  static const bool tm64 = env_on("BTSBOT_AMD_GEMM2_TM64");   // A/B: 64x128 tiles, 3-slot ring (72 KB: two workgroups per CU, two k-tiles in flight each)
+  static const bool one_slot = !switch_on(SW_GEMM2_NO_1SLOT);
+  static const bool tm64 = switch_on(SW_GEMM2_TM64);   // A/B: 64x128 tiles, 3-slot ring (72 KB: two workgroups per CU, two k-tiles in flight each)
   // long reductions on big problems (MaxViT fc2 / conv3 at C >= 256: K >= 1024) run 7 % faster on 64x128 tiles
   // with a 3-slot ring (two workgroups per CU, two k-tiles in flight each); the short-K shapes lose 15 % there
   if (N >= 128 && wg128 >= 512 && (K >= 1024 || (tm64 && K >= 128)))

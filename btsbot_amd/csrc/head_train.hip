@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void act_fwd_kernel(const float* __restrict__ 
 // as one thread per output walking K) goes through gemm.hip's exact-fp32 MFMA GEMM: both operands are K-contiguous as
 // stored ([N][K] filter for the forward, the packed transpose [K][N] for the input gradient).
 static bool wide_layer(int M, int N, int K, int ldi) {
-  static const bool off = env_on("BTSBOT_AMD_HEAD_NO_GEMM");   // 1: every head layer on the per-output kernels (A/B)
+  static const bool off = switch_on(SW_HEAD_NO_GEMM);   // 1: every head layer on the per-output kernels (A/B)
   return !off && ldi == K && K % 4 == 0 && N % 4 == 0 && (long)M * N * K >= (1L << 24);
 }
 

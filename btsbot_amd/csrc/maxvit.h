@@ -12,7 +12,6 @@ int maxvit_pack(btsbot_ctx* h, hipStream_t st);                          // mirr
 size_t maxvit_ws_bytes(const btsbot_ctx* h, int chunk);
 int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float** feat_out);
 void maxvit_free(btsbot_ctx* h);
-bool maxvit_split(const btsbot_ctx* h);   // the forward's GEMMs run on split operands (f16x2 handles, gemm_x2.hip)
 // ---- training of the branch (maxvit_train.hip): BatchNorm2d batch statistics forward, backward of every layer; an
 //      fp32 engine whatever the handle's operand mode.  cache = h->bbcache, sized by maxvit_train_cache_bytes(B)
 size_t maxvit_train_cache_bytes(const btsbot_ctx* h, int B);

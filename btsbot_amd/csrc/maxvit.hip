@@ -116,16 +116,6 @@ int maxvit_build_tables(btsbot_ctx* h, size_t* extra_cursor) {
   const int esz = h->esz();
   MaxVit* mv = new MaxVit();
   h->mv = mv;
-  mv->attn_valu = env_on("BTSBOT_AMD_MV_ATTN_VALU");
-  mv->dw_plain = env_on("BTSBOT_AMD_MV_DW_PLAIN");
-  mv->stem_im2col = env_on("BTSBOT_AMD_MV_STEM_IM2COL");
-  mv->gated_gemm = env_on("BTSBOT_AMD_MV_GATED_GEMM");
-  mv->no_front = env_on("BTSBOT_AMD_MV_NO_FRONT");
-  mv->no_ln_fuse = env_on("BTSBOT_AMD_MV_NO_LN_FUSE");
-  mv->no_attn_block = env_on("BTSBOT_AMD_MV_NO_ATTN_BLOCK");
-  mv->mlp_unfused = env_on("BTSBOT_AMD_MV_MLP_UNFUSED");
-  mv->no_part = env_on("BTSBOT_AMD_MV_NO_PART");
-  mv->no_smlp = env_on("BTSBOT_AMD_MV_NO_SMLP");
   char buf[96];
   mv->stem1_w = mv_add(h, "stem.conv1.weight", {32, 3, 3, 3});
   mv->stem_bn = add_bn(h, "stem.norm1.", 32, cur);
@@ -190,8 +180,6 @@ void maxvit_free(btsbot_ctx* h) {
   delete h->mv;
   h->mv = nullptr;
 }
-
-bool maxvit_split(const btsbot_ctx* h) { return h->mv != nullptr && h->mv->x2; }
 
 #define MTRY(call)                  \
   do {                              \
@@ -306,9 +294,9 @@ size_t maxvit_ws_bytes(const btsbot_ctx* h, int chunk) {
 }
 
 // GEMM dispatch of the MaxViT schedule: an f16x2 handle's products on split operands (fp32 maps in and out)
-static int mv_gemm(const MaxVit* mv, int prec, int epi, const void* X, const void* W, const float* bias,
+static int mv_gemm(const btsbot_ctx* h, int prec, int epi, const void* X, const void* W, const float* bias,
                    const float* gamma, const float* resid, void* out, int M, int N, int K, hipStream_t st) {
-  if (mv->x2)
+  if (h->sched.maxvit_split)
     return launch_gemm_x2(epi, reinterpret_cast<const float*>(X), W, bias, gamma, resid, reinterpret_cast<float*>(out),
                           M, N, K, st);
   return launch_gemm(prec, epi, X, W, bias, gamma, resid, out, M, N, K, st);
@@ -328,6 +316,7 @@ template <typename F> static int mv_timed(btsbot_ctx* h, int cat, hipStream_t st
 
 int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float** feat_out) {
   MaxVit* mv = h->mv;
+  const Schedule& sc = h->sched;
   const int prec = h->cfg.precision;
   const float* m = h->mirror;
   unsigned char* ex = h->extra;
@@ -352,18 +341,18 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
   bool xn_ready = false, pool_ready = false, next_xn_ready = false;
   // ---- stem: resize + conv3x3 s2 (+BN, SiLU) + conv3x3 s1, both as im2col GEMMs
   const int M0 = nb * 12544;
-  if (prec != BTSBOT_F32 && !mv->stem_im2col) {
+  if (prec != BTSBOT_F32 && !sc.mv_stem_im2col) {
     MTRY(mv_timed(h, CAT_MV_STEM, st, [&] {
       return launch_mv_stem1(prec, img, ex + mv->p_stem1, F(mv->stem_bn.p_shift), Cc, nb, st);
     }));
   } else {
     MTRY(mv_timed(h, CAT_MV_STEM, st, [&] { return launch_mv_resize_im2col(prec, img, Bb, nb, st); }));
     MTRY(mv_timed(h, CAT_MV_G_STEM, st, [&] {
-      return mv_gemm(mv, prec, EPI_SILU, Bb, ex + mv->p_stem1, F(mv->stem_bn.p_shift), nullptr, nullptr,
+      return mv_gemm(h, prec, EPI_SILU, Bb, ex + mv->p_stem1, F(mv->stem_bn.p_shift), nullptr, nullptr,
                      Cc, M0, 32, 32, st);
     }));
   }
-  if (prec != BTSBOT_F32 && !mv->stem_im2col) {
+  if (prec != BTSBOT_F32 && !sc.mv_stem_im2col) {
     // (writes block 0's pre-norm + cast into the conv1 im2col buffer, which is free by now)
     const MvBlock& b0 = mv->blocks[0];
     // (without debug taps nobody needs the fp32 stem map itself: block 0's shortcut only wants its 2x2
@@ -377,7 +366,7 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
   } else {
     MTRY(mv_timed(h, CAT_MV_STEM, st, [&] { return launch_mv_im2col3(prec, Cc, A, nb, 112, 32, st); }));
     MTRY(mv_timed(h, CAT_MV_G_STEM, st, [&] {
-      return mv_gemm(mv, prec, EPI_BIAS, A, ex + mv->p_stem2, zero, nullptr, nullptr, x, M0, 64, 288,
+      return mv_gemm(h, prec, EPI_BIAS, A, ex + mv->p_stem2, zero, nullptr, nullptr, x, M0, 64, 288,
                      st);
     }));
   }
@@ -398,7 +387,7 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
           return launch_mv_avgpool2(prec, x, E, 1, nb, b.hin, b.cin, st);
         }));
         MTRY(mv_timed(h, CAT_MV_G_SC, st, [&] {
-          return mv_gemm(mv, prec, EPI_BIAS, E, ex + b.p_sc, zero, nullptr, nullptr, x2, Mo, b.c,
+          return mv_gemm(h, prec, EPI_BIAS, E, ex + b.p_sc, zero, nullptr, nullptr, x2, Mo, b.c,
                              b.cin, st);
         }));
       } else if (!(bi == 0 && pool_ready)) {
@@ -421,7 +410,7 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
     }
     const float inv_hw = 1.0f / (float)(b.hout * b.hout);
     void* m2b = Bb;      // where the gated-conv input (depthwise output) lives
-    const bool front = !mv->no_front && mv_mbconv_front_supported(prec, b.hin, b.cin, b.mid, b.stride);
+    const bool front = !sc.mv_no_front && mv_mbconv_front_supported(prec, b.hin, b.cin, b.mid, b.stride);
     if (front) {
       // wide stages: conv1 + depthwise + pool partials in one kernel, the expanded map stays on-chip
       m2b = A;
@@ -435,10 +424,10 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
       }));
     } else {
     MTRY(mv_timed(h, CAT_MV_G_CONV1, st, [&] {
-      return mv_gemm(mv, prec, EPI_SILU, c1_in, ex + b.p_c1, F(b.p_c1b), nullptr, nullptr, A, Min, b.mid,
+      return mv_gemm(h, prec, EPI_SILU, c1_in, ex + b.p_c1, F(b.p_c1b), nullptr, nullptr, A, Min, b.mid,
                          b.cin, st);
     }));
-    if (prec != BTSBOT_F32 && !mv->dw_plain) {
+    if (prec != BTSBOT_F32 && !sc.mv_dw_plain) {
       // depthwise conv with the squeeze-excite pool fused (partial sums per workgroup, no second pass)
       MTRY(mv_timed(h, CAT_MV_DW, st, [&] {
         return launch_mv_dw3s(prec, A, F(b.p_dw), F(b.p_dwb), Bb, part, nb, b.hin, b.mid, b.stride, st);
@@ -461,10 +450,10 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
     // wide stages (C = 64 / 128): the LayerNorm that follows a residual GEMM is computed in that GEMM's
     // epilogue (the staged output tile holds whole rows)
     // (a block whose partition halves run as mv_part_kernel normalises its rows there: nobody reads a fused LayerNorm copy)
-    const bool part_blk = b.attn[0].part && !mv->no_part;
-    const bool ln_fuse = prec != BTSBOT_F32 && !mv->no_ln_fuse && (b.c == 64 || b.c == 128) && !part_blk;
+    const bool part_blk = b.attn[0].part && !sc.mv_no_part;
+    const bool ln_fuse = prec != BTSBOT_F32 && !sc.mv_no_ln_fuse && (b.c == 64 || b.c == 128) && !part_blk;
     bool ln1_done = false, ln1_grid_done = false;
-    if (prec != BTSBOT_F32 && !mv->gated_gemm && (size_t)b.c * b.mid * 4 <= (size_t)hw2 * b.mid) {
+    if (prec != BTSBOT_F32 && !sc.mv_gated_gemm && (size_t)b.c * b.mid * 4 <= (size_t)hw2 * b.mid) {
       // wide stages: per-alert filters W3 diag(g_b) (a fraction of the map's size) + batched LDS-DMA GEMM
       MTRY(mv_timed(h, CAT_MV_SE, st, [&] {
         return launch_mv_scale_w(prec, m + b.c3_w, gate, wg, nb, b.c, b.mid, st);
@@ -475,7 +464,7 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
                                           ln_fuse ? m + b.attn[0].n1b : nullptr, ln_fuse ? Cc : nullptr);
       }));
       ln1_done = ln_fuse;
-    } else if (prec != BTSBOT_F32 && !mv->gated_gemm) {
+    } else if (prec != BTSBOT_F32 && !sc.mv_gated_gemm) {
       // narrow stages: the map is small -- gate it in place, then the plain LDS-DMA GEMM
       MTRY(mv_timed(h, CAT_MV_SE, st, [&] { return launch_mv_gate(prec, m2b, gate, nb, hw2, b.mid, st); }));
       MTRY(mv_timed(h, CAT_MV_G_CONV3, st, [&] {
@@ -483,7 +472,7 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
       }));
     } else {
       MTRY(mv_timed(h, CAT_MV_G_CONV3, st, [&] {
-        if (mv->x2)
+        if (sc.maxvit_split)
           return launch_gemm_x2_gated(reinterpret_cast<const float*>(m2b), gate, hw2, ex + b.p_c3, resid, dst, Mo, b.c,
                                       b.mid, st);
         return launch_gemm_gated(prec, m2b, gate, hw2, ex + b.p_c3, resid, dst, Mo, b.c, b.mid, st);
@@ -531,7 +520,7 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
           return launch_mv_ln(prec, x, m + a.n1w, m + a.n1b, Cc, (long)Mo, c, st);
         }));
       }
-      if (!mv->no_attn_block && mv_attn_block_supported(prec, c)) {
+      if (!sc.mv_no_attn_block && mv_attn_block_supported(prec, c)) {
         // C = 64: qkv, attention, proj, residual and LN2 in one kernel (qkv never reaches HBM)
         MTRY(mv_timed(h, CAT_MV_ABLK, st, [&] {
           return launch_mv_attn_block(prec, Cc, x, Cc, ex + a.p_qkv, m + a.qkv_b, ex + a.p_proj, m + a.proj_b,
@@ -539,11 +528,11 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
         }));
       } else {
       MTRY(mv_timed(h, CAT_MV_G_QKV, st, [&] {
-        return mv_gemm(mv, prec, EPI_BIAS_T, Cc, ex + a.p_qkv, m + a.qkv_b, nullptr, nullptr, D, Mo,
+        return mv_gemm(h, prec, EPI_BIAS_T, Cc, ex + a.p_qkv, m + a.qkv_b, nullptr, nullptr, D, Mo,
                            3 * c, c, st);
       }));
       MTRY(mv_timed(h, CAT_MV_ATTN, st, [&] {
-        if (prec != BTSBOT_F32 && !mv->attn_valu)
+        if (prec != BTSBOT_F32 && !sc.mv_attn_valu)
           return launch_mv_attn_mfma(prec, D, F(a.p_bias64), E, nb, b.hout, c, g, st);
         return launch_mv_attn(prec, D, F(a.p_bias), E, nb, b.hout, c, g, st);
       }));
@@ -554,16 +543,16 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
         }));
       } else {
         MTRY(mv_timed(h, CAT_MV_G_PROJ, st, [&] {
-          return mv_gemm(mv, prec, EPI_RESID, E, ex + a.p_proj, m + a.proj_b, one, x, x, Mo, c, c, st);
+          return mv_gemm(h, prec, EPI_RESID, E, ex + a.p_proj, m + a.proj_b, one, x, x, Mo, c, c, st);
         }));
-        if (!(a.smlp && !mv->no_smlp))   // (the streamed MLP below normalises its rows itself)
+        if (!(a.smlp && !sc.mv_no_smlp))   // (the streamed MLP below normalises its rows itself)
           MTRY(mv_timed(h, CAT_MV_LN, st, [&] {
             return launch_mv_ln(prec, x, m + a.n2w, m + a.n2b, Cc, (long)Mo, c, st);
           }));
       }
       }
       }   // (part_blk)
-      if (a.fused && !mv->mlp_unfused) {   // C = 64 / 128: fc1 -> GELU -> fc2 -> +x with the hidden on-chip
+      if (a.fused && !sc.mv_mlp_unfused) {   // C = 64 / 128: fc1 -> GELU -> fc2 -> +x with the hidden on-chip
         // ... and the next consumer's normalised copy of x from the same registers: the grid attention's
         // LN1 after the window attention's MLP, the next block's pre-norm BatchNorm after the grid one's.
         // (the kernel reads its input Cc completely before any row is written? no: rows are independent
@@ -587,7 +576,7 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
         if (post == 2) next_xn_ready = true;
         continue;
       }
-      if (a.smlp && !mv->no_smlp) {
+      if (a.smlp && !sc.mv_no_smlp) {
         // C = 256: norm2 -> fc1 -> GELU -> fc2 -> + x as ONE launch of stage2p_kernel's row-tile form: 64 rows resident per
         // workgroup, both filters streamed past them as packed MFMA fragments, the 1024-wide hidden rows never leave the CU
         // (unfused: a LayerNorm launch and two GEMMs that write and re-read 4 KB per row)
@@ -604,11 +593,11 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
         continue;
       }
       MTRY(mv_timed(h, CAT_MV_G_FC1, st, [&] {
-        return mv_gemm(mv, prec, EPI_GELU, Cc, ex + a.p_fc1, m + a.fc1_b, nullptr, nullptr, Bb, Mo,
+        return mv_gemm(h, prec, EPI_GELU, Cc, ex + a.p_fc1, m + a.fc1_b, nullptr, nullptr, Bb, Mo,
                            4 * c, c, st);
       }));
       MTRY(mv_timed(h, CAT_MV_G_FC2, st, [&] {
-        return mv_gemm(mv, prec, EPI_RESID, Bb, ex + a.p_fc2, m + a.fc2_b, one, x, x, Mo, c, 4 * c,
+        return mv_gemm(h, prec, EPI_RESID, Bb, ex + a.p_fc2, m + a.fc2_b, one, x, x, Mo, c, 4 * c,
                        st);
       }));
     }

@@ -41,17 +41,5 @@ struct MaxVit {
   size_t o_x, o_x2, o_a, o_b, o_c, o_d, o_e, o_gate, o_feat, o_part, o_sescr, o_wg;
   // training, 16-bit modes: (fp32 GEMM input of the forward, its kept 16-bit copy) in call order (maxvit_train.hip)
   std::vector<std::pair<const float*, void*>> xkept;
-  bool no_part = false;     // BTSBOT_AMD_MV_NO_PART=1: the partition blocks of C = 64 / 128 / 256 launch by launch (A/B, parity tests)
-  bool no_smlp = false;     // BTSBOT_AMD_MV_NO_SMLP=1: the 256-channel MLPs as LayerNorm + two GEMMs (A/B, parity tests)
-  bool mlp_unfused = false; // BTSBOT_AMD_MV_MLP_UNFUSED=1: fc1 / fc2 GEMM pair also where the fused MLP kernel applies
-  bool stem_im2col = false; // BTSBOT_AMD_MV_STEM_IM2COL=1: im2col + GEMM for the second stem conv in the 16-bit modes too
-                            // (measured slower than gemm2 on these shapes: opt-in, kept as the record)
-  bool gated_gemm = false;  // BTSBOT_AMD_MV_GATED_GEMM=1: register-staged gated GEMM for every conv3 (f32 mode's path)
-  bool no_front = false;    // BTSBOT_AMD_MV_NO_FRONT=1: conv1 GEMM + depthwise kernel instead of the fused MBConv front
-  bool no_ln_fuse = false;  // BTSBOT_AMD_MV_NO_LN_FUSE=1: separate LayerNorm launches everywhere
-  bool no_attn_block = false;  // BTSBOT_AMD_MV_NO_ATTN_BLOCK=1: qkv GEMM + attention + proj GEMM at C = 64 too
-                            // for the K = 128 / 256 wide-N shapes (measured 20-25 % slower than gemm2: opt-in)
-  bool dw_plain = false;    // BTSBOT_AMD_MV_DW_PLAIN=1: per-pixel depthwise kernel + separate pool pass
-  bool attn_valu = false;   // BTSBOT_AMD_MV_ATTN_VALU=1: the one-query-per-lane kernel in the 16-bit modes too
 };
 

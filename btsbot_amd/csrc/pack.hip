@@ -389,14 +389,16 @@ namespace {
 
 // Every packed image of the handle, in the order the packs write them: stem, then per stage the downsample and the
 // blocks, the split-training planes, metadata, fusion, head16.  THE place that decides that an image exists (an entry
-// with bytes) and which packs write it (`when`); the flags it reads are fixed from btsbot_create on, except train_split
-// (btsbot_set_option, before the first pack) and train_packs (btsbot_reserve_train: pack_invalidate()), which only
-// changes `when`.  An entry comes behind the image it reads.
+// with bytes) and which packs write it (`when`), from the handle's resolved schedule (schedule.h): a stage kernel's images
+// exist where that kernel runs.  The schedule is fixed from btsbot_create on, except train_split (btsbot_set_option,
+// before the first pack) and train_packs (btsbot_reserve_train: pack_invalidate()), which only changes `when`.  An entry
+// comes behind the image it reads.
 void image_walk(btsbot_ctx* h) {
   const btsbot_config& c = h->cfg;
   const size_t esz = h->esz();
   const int prec = c.precision;
-  const bool tp = h->train_packs;
+  const Schedule& sc = h->sched;
+  const bool tp = sc.train_packs;
   const unsigned F = IN_FULL, FT = IN_FULL | IN_TRAIN, if_tp = tp ? FT : 0;
   std::vector<ImageEntry>& v = h->images;
   v.clear();
@@ -416,11 +418,11 @@ void image_walk(btsbot_ctx* h) {
   };
   if (h->has_image && !h->is_maxvit) {
     const int c0 = c.dims[0];
-    const bool x2_s0 = h->x2 && h->stage0;
+    const bool x2_s0 = h->x2 && sc.stage0;
     // what stage0b_kernel's keeping form reads goes first in the training re-pack
-    const bool early = h->s0_train;
+    const bool early = sc.s0_keep;
     // stem filter in the operand type
-    job("p_stem16", &h->p_stem16, (size_t)c0 * 48 * esz, h->stage0 || tp ? FT : 0, early, PACK_CAST, h->stem_w, -1, c0 * 48, 1);
+    job("p_stem16", &h->p_stem16, (size_t)c0 * 48 * esz, sc.stage0 || tp ? FT : 0, early, PACK_CAST, h->stem_w, -1, c0 * 48, 1);
     if (x2_s0) {   // split mode: its f16 heads / remainders
       own("p_x2_stem", &h->p_x2_stem, (size_t)c0 * 48 * 2, F, false, nullptr, [=](hipStream_t st) {
         return launch_cast(BTSBOT_F16, h->mirror + h->stem_w, IMG(h, h->p_x2_stem), (int64_t)c0 * 48, st);
@@ -437,19 +439,19 @@ void image_walk(btsbot_ctx* h) {
         const int cin = c.dims[i - 1];
         const size_t n = (size_t)ch * cin * 4;
         // (training re-pack with stage 2's forward through stage2p_kernel: the last downsample's fragments ride in the table)
-        if (i == 3 && h->stage2p)
-          job("down.p_wp", &d->p_wp, n * esz, h->s2p_train ? IN_TRAIN : 0, false, PACK_FRAG_DOWN, d->w, -1, ch, cin).launch =
+        if (i == 3 && sc.stage2p)
+          job("down.p_wp", &d->p_wp, n * esz, sc.s2_keep ? IN_TRAIN : 0, false, PACK_FRAG_DOWN, d->w, -1, ch, cin).launch =
               [=](hipStream_t st) {
                 return launch_pack_s2p(h->prec_down3(), h->mirror + d->w, nullptr, IMG(h, d->p_wp), ch, 4 * cin, 1, cin, nullptr, st);
               };
         job("down.p_w", &d->p_w, n * esz, FT, early && i == 1, PACK_DOWN, d->w, -1, ch, cin);
         job("down.p_wt", &d->p_wt, n * esz, if_tp, false, PACK_DOWN_T, d->w, -1, ch, cin);
-        if (i == 3 && h->stage2p)   // ... and stage2p.hip's own packer writes them in the full pack
+        if (i == 3 && sc.stage2p)   // ... and stage2p.hip's own packer writes them in the full pack
           own("down.p_wp", &d->p_wp, 0, F, false, nullptr, [=](hipStream_t st) {
             return launch_pack_s2p(h->prec_down3(), h->mirror + d->w, nullptr, IMG(h, d->p_wp), ch, 4 * cin, 1, cin, nullptr, st);
           });
-        if (i == 2 && h->stage1)
-          own("down.p_wp", &d->p_wp, n * esz, h->s1_train ? FT : F, false, nullptr, [=](hipStream_t st) {
+        if (i == 2 && sc.stage1)
+          own("down.p_wp", &d->p_wp, n * esz, sc.s1_keep ? FT : F, false, nullptr, [=](hipStream_t st) {
             return launch_pack_frag32(h->prec_s01(), h->mirror + d->w, IMG(h, d->p_wp), ch, cin, st);
           });
         if (i == 1 && x2_s0) {   // split mode, stage0b's downsample: heads and remainders from one launch
@@ -461,16 +463,15 @@ void image_walk(btsbot_ctx* h) {
       }
       for (BlockPk& blk : h->blocks[i]) {
         BlockPk* b = &blk;
-        const bool s0 = i == 0 && ch == 64, s1 = i == 1 && ch == 128;
         const bool b_early = early && i == 0;
         job("p_dw", &b->p_dw, (size_t)49 * ch * 4, FT, b_early, PACK_TRANSPOSE_F32, b->dw_w, -1, ch, 49);
         job("p_fc1", &b->p_fc1, wb * esz, FT, b_early, PACK_CAST, b->fc1_w, -1, 4 * ch * ch, 1);
         job("p_fc2", &b->p_fc2, wb * esz, FT, false, PACK_CAST, b->fc2_w, -1, 4 * ch * ch, 1);
-        const bool frag = (i == 2 && h->stage2p) || (i == 3 && h->stage3);   // stage2p.hip / stage3.hip: filters as MFMA A fragments
-        if (i == 2 && h->stage2p) {
+        const bool frag = (i == 2 && sc.stage2p) || (i == 3 && sc.stage3);   // stage2p.hip / stage3.hip: filters as MFMA A fragments
+        if (i == 2 && sc.stage2p) {
           // (training re-pack with stage 2's forward through stage2p_kernel: its filters as MFMA fragments ride in the table,
           //  beside the row-major images the per-op forward reads -- large batches take that one, backbone_train.hip)
-          const unsigned t = h->s2p_train ? IN_TRAIN : 0;
+          const unsigned t = sc.s2_keep ? IN_TRAIN : 0;
           job("p_w1p", &b->p_w1p, wb * esz, t, false, PACK_FRAG, b->fc1_w, -1, 4 * ch, ch).launch = [=](hipStream_t st) {
             return launch_pack_s2p(h->prec_tail(), h->mirror + b->fc1_w, nullptr, IMG(h, b->p_w1p), 4 * ch, ch, 0, 0,
                                    reinterpret_cast<float*>(IMG(h, b->p_scales)), st);
@@ -484,7 +485,7 @@ void image_walk(btsbot_ctx* h) {
         job("p_fc1t", &b->p_fc1t, wb * esz, if_tp, false, PACK_TRANSPOSE_CAST, b->fc1_w, -1, 4 * ch, ch);
         job("p_fc2t", &b->p_fc2t, wb * esz, if_tp, false, PACK_TRANSPOSE_CAST, b->fc2_w, b->gamma, ch, 4 * ch);
         if (!h->x2 && s2mlp_bwd_supported(prec, ch)) {   // the same two as MFMA A fragments for s2mlp_bwd_kernel
-          const unsigned t = tp && h->s2mlp ? FT : 0;
+          const unsigned t = tp && sc.s2mlp ? FT : 0;
           ImageEntry& e1 = job("p_w1tp", &b->p_w1tp, wb * 2, t, false, PACK_TFRAG, b->fc1_w, -1, 4 * ch, ch);
           e1.reads = &b->p_fc1t;   // (the single-operand launch; the table's job reads the mirror)
           e1.launch = [=](hipStream_t st) { return launch_pack_frag16(IMG(h, b->p_fc1t), IMG(h, b->p_w1tp), ch, 4 * ch, st); };
@@ -494,7 +495,7 @@ void image_walk(btsbot_ctx* h) {
         }
         // diag(gamma) W2 in the operand type (the megakernels fold the layer scale); the training re-pack writes it for
         // the stages whose forward is a keeping form
-        own("p_fc2g", &b->p_fc2g, wb * esz, F | ((i == 0 && h->s0_train) || (i == 1 && h->s1_train) ? IN_TRAIN : 0), b_early, nullptr,
+        own("p_fc2g", &b->p_fc2g, wb * esz, F | ((i == 0 && sc.s0_keep) || (i == 1 && sc.s1_keep) ? IN_TRAIN : 0), b_early, nullptr,
             [=](hipStream_t st) {
               return launch_rowscale_cast(h->cfg.precision, h->mirror + b->fc2_w, h->mirror + b->gamma, IMG(h, b->p_fc2g), ch, 4 * ch, st);
             });
@@ -515,30 +516,30 @@ void image_walk(btsbot_ctx* h) {
           });
         }
         // the parameter images of stage0b.hip / stage1b.hip (they read the tap-major taps) ...
-        if (s1 && (prec != BTSBOT_F32 || (h->x2 && h->stage1)))
+        if (i == 1 && sc.stage1)
           own("p_s0par", &b->p_s0par, s1par_bytes(), F, false, &b->p_dw, [=](hipStream_t st) {
             const float* m = h->mirror;
             return launch_pack_s1par(h->prec_s01(), IMG_F32(h, b->p_dw), m + b->dw_b, m + b->ln_w, m + b->ln_b, IMG(h, b->p_s0par), st);
           });
-        if (s0 && (prec != BTSBOT_F32 || (h->x2 && h->stage0)))
+        if (i == 0 && sc.stage0)
           own("p_s0par", &b->p_s0par, s0par_bytes(), F, false, &b->p_dw, [=](hipStream_t st) {
             const float* m = h->mirror;
             return launch_pack_s0par(h->prec_s01(), IMG_F32(h, b->p_dw), m + b->dw_b, m + b->ln_w, m + b->ln_b, m + b->fc1_b,
                                      m + b->fc2_b, m + b->gamma, IMG(h, b->p_s0par), st);
           });
         // ... and of their keeping forms (f16 taps in every mode), in the full pack too: the first training forward follows one
-        if (!h->x2 && prec != BTSBOT_F32 && s1)
-          own("p_s0par_t", &b->p_s0par_t, s1par_bytes(), h->s1_train && tp ? FT : 0, false, &b->p_dw, [=](hipStream_t st) {
+        if (i == 1 && sc.s1_keep)
+          own("p_s0par_t", &b->p_s0par_t, s1par_bytes(), if_tp, false, &b->p_dw, [=](hipStream_t st) {
             const float* m = h->mirror;
             return launch_pack_s1par(BTSBOT_F16, IMG_F32(h, b->p_dw), m + b->dw_b, m + b->ln_w, m + b->ln_b, IMG(h, b->p_s0par_t), st);
           });
-        if (!h->x2 && prec != BTSBOT_F32 && s0)
-          own("p_s0par_t", &b->p_s0par_t, s0par_bytes(), h->s0_train && tp ? FT : 0, b_early, &b->p_dw, [=](hipStream_t st) {
+        if (i == 0 && sc.s0_keep)
+          own("p_s0par_t", &b->p_s0par_t, s0par_bytes(), if_tp, b_early, &b->p_dw, [=](hipStream_t st) {
             const float* m = h->mirror;
             return launch_pack_s0par(BTSBOT_F16, IMG_F32(h, b->p_dw), m + b->dw_b, m + b->ln_w, m + b->ln_b, m + b->fc1_b,
                                      m + b->fc2_b, m + b->gamma, IMG(h, b->p_s0par_t), st);
           });
-        if (h->x2 && ((i == 0 && h->stage0) || (i == 1 && h->stage1))) {   // split mode, stages 0-1: the pointwise filters as f16 heads + remainders
+        if (h->x2 && ((i == 0 && sc.stage0) || (i == 1 && sc.stage1))) {   // split mode, stages 0-1: the pointwise filters as f16 heads + remainders
           own("p_x2_w1", &b->p_x2_w1, wb * 2, F, false, nullptr, [=](hipStream_t st) {
             return launch_cast(BTSBOT_F16, h->mirror + b->fc1_w, IMG(h, b->p_x2_w1), (int64_t)4 * ch * ch, st);
           });
@@ -553,14 +554,14 @@ void image_walk(btsbot_ctx* h) {
           });
         }
         // (the training forward of the blocks whose backward is mlp_bwd_kernel runs the fused MLP too)
-        if (b->fused)
-          own("p_fused", &b->p_fused, fused_mlp_packed_bytes(ch), h->mlp_fused(ch) ? FT : F, false, nullptr, [=](hipStream_t st) {
+        if (sc.fused_mlp[i])
+          own("p_fused", &b->p_fused, fused_mlp_packed_bytes(ch), sc.mlp_bwd[i] ? FT : F, false, nullptr, [=](hipStream_t st) {
             return launch_pack_fused_mlp(h->cfg.precision, ch, h->mirror + b->fc1_w, h->mirror + b->fc2_w, IMG(h, b->p_fused), st);
           });
       }
     }
     // split training ("train_split"): the f16 head + remainder planes of the fp32 images above, one launch behind them
-    if (h->train_split)
+    if (sc.train_split)
       for (int i = 0; i < 4; ++i) {
         const long ch = c.dims[i];
         if (i > 0) {
@@ -582,7 +583,7 @@ void image_walk(btsbot_ctx* h) {
   for (int i = 0; i < h->n_comb; ++i)
     job("p_comb", &h->p_comb[i], (size_t)h->comb_dims[i + 1] * h->comb_dims[i] * 4, FT, false, PACK_TRANSPOSE_F32, h->comb_w[i], -1,
         h->comb_dims[i + 1], h->comb_dims[i]);
-  if (h->head16) {   // head16.hip: the Linear filters as split A fragments
+  if (sc.head16) {   // head16.hip: the Linear filters as split A fragments
     auto h16 = [&](const char* name, size_t* slot, int64_t w, int N, int K) {
       own(name, slot, head16_packed_bytes(N, K), F, false, nullptr,
           [=](hipStream_t st) { return launch_pack_h16(h->prec_head(), h->mirror + w, IMG(h, *slot), N, K, st); });
@@ -743,7 +744,7 @@ int pack_params(btsbot_ctx* h, const float* master, hipStream_t st, bool train_o
   }
   TRY(pack_sync(h, st));   // (a pack nobody consumed yet still reads the mirror on the side stream)
   TRY(launch_copy_f32(h->mirror, master, (size_t)h->total_floats, st));
-  if (train_only && h->has_image && !h->is_maxvit && h->use_side && h->side != nullptr) {
+  if (train_only && h->has_image && !h->is_maxvit && h->sched.side_stream && h->side != nullptr) {
     hipStream_t sp = st;
     TRY(side_fork(h, st, &sp));   // behind the mirror copy
     st = sp;
@@ -752,11 +753,11 @@ int pack_params(btsbot_ctx* h, const float* master, hipStream_t st, bool train_o
   // The plain element maps (casts, transposes, the downsample re-orderings) run as ONE launch over a job
   // table built on the first pack of each kind: mirror and extra never move, so the table is static.
   // BTSBOT_AMD_PACK_UNBATCHED=1 keeps one launch per operand (A/B and parity).
-  static const bool unbatched = env_on("BTSBOT_AMD_PACK_UNBATCHED");
+  static const bool unbatched = switch_on(SW_PACK_UNBATCHED);
   const int kind = train_only ? 1 : 0;
   const unsigned bit = train_only ? IN_TRAIN : IN_FULL;
   if (!unbatched && h->pack_jobs[kind] == nullptr) TRY(build_job_tables(h, kind));
-  // training re-pack with the stage-0 megakernel in the forward (s0_train): what it reads first -- its table, then the
+  // training re-pack with the stage-0 megakernel in the forward (s0_keep): what it reads first -- its table, then the
   // stage-0 blocks' gamma-scaled fc2 filters and parameter images (they read the tap-major taps the table wrote), then the
   // event pack_sync_early() waits for
   const bool early = train_only && !unbatched && h->pack_jobs[2] != nullptr;

@@ -264,7 +264,7 @@ int launch_s2mlp_bwd(int prec, const void* dy, const void* a, const void* w2tp, 
     return BTSBOT_ERR_INVALID_ARG;
   }
   static const int rw = [] {
-    const int v = env_int("BTSBOT_AMD_S2MLP_ROWS", 0);   // tuning knob: pixel rows per workgroup (<= 48)
+    const int v = switch_int(SW_S2MLP_ROWS, 0);   // tuning knob: pixel rows per workgroup (<= 48)
     return v >= 16 && v <= NCOL ? v : 45;
   }();
   S2MlpBwdArgs g{dy, a, w2tp, w1tp, da, dxn, R, rw};

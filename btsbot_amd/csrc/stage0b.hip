@@ -807,7 +807,7 @@ template <typename T, bool X2 = false, int WPS = 2, bool KEEP = false> int launc
   static DevOnce attr_set;
   // (BTSBOT_AMD_S0_ONE_WG=1: developer probe -- the LDS request padded so that ONE workgroup fits a CU: how the kernel's
   //  time scales from one to two waves per SIMD says what two more would buy)
-  static const int pad = env_on("BTSBOT_AMD_S0_ONE_WG") && !X2 ? 90 * 1024 - S0L<X2>::LDS_BYTES : 0;
+  static const int pad = switch_on(SW_S0_ONE_WG) && !X2 ? 90 * 1024 - S0L<X2>::LDS_BYTES : 0;
   const int LDS_BYTES = S0L<X2>::LDS_BYTES + pad;
   if (attr_set.need()) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),

@@ -929,7 +929,7 @@ template <typename T, bool X2 = false, int WPS = 2, bool KEEP = false> int launc
   auto kern = stage1b_kernel<T, X2, WPS, KEEP>;
   static DevOnce attr_set;
   // (BTSBOT_AMD_S1_ONE_WG=1: the same probe as stage0b.hip's)
-  static const int pad = env_on("BTSBOT_AMD_S1_ONE_WG") && !X2 ? 90 * 1024 - S1L<X2>::LDS_BYTES : 0;
+  static const int pad = switch_on(SW_S1_ONE_WG) && !X2 ? 90 * 1024 - S1L<X2>::LDS_BYTES : 0;
   const int LDS_BYTES = S1L<X2>::LDS_BYTES + pad;
   if (attr_set.need()) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),

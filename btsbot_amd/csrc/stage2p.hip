@@ -1008,7 +1008,7 @@ int launch_pack_s2p(int prec, const float* src, const float* rowscale, void* dst
 // 7 alerts per workgroup when that takes fewer rounds of one workgroup per CU than 4 (256 CUs): the kernel's time per
 // round does not depend on the alerts resident -- the filter stream bounds it
 int stage2p_alerts_per_workgroup(int B, int hint) {
-  static const int forced = env_int("BTSBOT_AMD_S2P_G", 0);
+  static const int forced = switch_int(SW_S2P_G, 0);
   if (forced == 4 || forced == 5 || forced == 7) return forced;
   // the caller's hint (btsbot_set_option): a scoring loop that keeps several forwards in flight on different streams
   // asks for 7 at every batch size -- at 1024 alerts the kernel then occupies 147 CUs instead of 256 for 116 instead of

@@ -530,7 +530,7 @@ template <typename T, int C, int MB> int launch_tm(const Stage3Args& a, int j, i
 // registers each: narrow tiles only.)
 template <typename T, int C> int launch_t(const Stage3Args& a, int j, int phase, hipStream_t st) {
   if constexpr (S3M<T>::ESZ <= 2) {
-    static const int forced = env_int("BTSBOT_AMD_S3_TILES", 0);   // BTSBOT_AMD_S3_TILES=1 / 2: always narrow / always wide (A/B timing, parity)
+    static const int forced = switch_int(SW_S3_TILES, 0);   // BTSBOT_AMD_S3_TILES=1 / 2: always narrow / always wide (A/B timing, parity)
     const bool wide = forced == 2 || (forced != 1 && C == 640 && S3M<T>::ESZ == 2);
     if (wide) return launch_tm<T, C, 2>(a, j, phase, st);
   }

@@ -397,14 +397,14 @@ int wgrad2_launch(const void* D, const void* A, float* out, float* colsum, int M
   // x 256-512 rows all land within 1.5 % of each other); atomic form (every slice ends in TN x TK fp32 atomics: fewer, longer
   // slices win): ~384 workgroups, at least 512 rows.  Measured per 1024-alert step: 4.59 ms vs 4.67 ms.
   static const int env_rows = [] {
-    const int v = env_int("BTSBOT_AMD_WGRAD_MIN_ROWS", 0);   // tuning knob (overrides both defaults)
+    const int v = switch_int(SW_WGRAD_MIN_ROWS, 0);   // tuning knob (overrides both defaults)
     return v >= 32 ? v : 0;
   }();
   static const int env_wg = [] {
-    const int v = env_int("BTSBOT_AMD_WGRAD_WGS", 0);        // tuning knob (overrides both defaults)
+    const int v = switch_int(SW_WGRAD_WGS, 0);        // tuning knob (overrides both defaults)
     return v >= 1 ? v : 0;
   }();
-  static const bool atomic_only = env_on("BTSBOT_AMD_WGRAD_ATOMIC");   // 1: every slice adds its tile with fp32 atomics (A/B)
+  static const bool atomic_only = switch_on(SW_WGRAD_ATOMIC);   // 1: every slice adds its tile with fp32 atomics (A/B)
   int nsl = 1, mslice = M;
   auto slices = [&](int min_rows, int target_wg) {
     nsl = (target_wg + gx * gy - 1) / (gx * gy);
@@ -456,7 +456,7 @@ int launch_wgrad_reduce(const WgradReduceJob* jobs, int njobs, hipStream_t st) {
   if (n == 1) a.j[1] = a.j[0];
   {
     // the 16-byte form wherever the outputs allow it (every arena tensor does: 16-byte aligned, K a multiple of 4)
-    static const bool old_form = env_on("BTSBOT_AMD_WGRAD_REDUCE1");   // 1: the one-thread-per-output kernels (A/B)
+    static const bool old_form = switch_on(SW_WGRAD_REDUCE1);   // 1: the one-thread-per-output kernels (A/B)
     bool ok = !old_form;
     for (int i = 0; i < n; ++i)
       ok = ok && (a.j[i].K % 4 == 0) && (a.j[i].TK % 4 == 0) && (a.j[i].ldo % 4 == 0) &&

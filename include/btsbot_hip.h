@@ -267,7 +267,10 @@ int btsbot_allreduce_grads(btsbot_handle h, void* nccl_comm, float* grads, int n
  *   too (its raw-pixel patches scaled the same way); the stem's forward convolution, depthwise, LayerNorm, heads, loss
  *   and optimiser stay fp32; inference is unchanged.  0 (default): the fp32 training schedule.
  *   "query_train_split" (a query; `value` ignored): BTSBOT_OK when the handle's training products run split,
- *   BTSBOT_ERR_STATE otherwise. */
+ *   BTSBOT_ERR_STATE otherwise.
+ *   "query_schedule:<field>" (a query; `value` ignored): BTSBOT_OK when that decision of the handle's resolved kernel
+ *   schedule is on (fields and the BTSBOT_AMD_* switches behind them: csrc/schedule.h), BTSBOT_ERR_STATE when it is off,
+ *   BTSBOT_ERR_INVALID_ARG for an unknown field. */
 int btsbot_set_option(btsbot_handle h, const char* key, int value);
 
 /* Validation aid with no reference counterpart: when on, forward() keeps fp32 copies of the stem and

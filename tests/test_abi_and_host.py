@@ -263,3 +263,84 @@ def test_score_stream_host_checks():
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         btsbot_amd.ScoreStream(m.eval(), depth=2)
     assert m._init_config["meta_fc1_neurons"] == cfg["meta_fc1_neurons"]
+
+
+# ---- the switch table (csrc/schedule.h) and the schedule a handle resolves from it -------------------------------------
+_CSRC = os.path.join(ROOT, "btsbot_amd", "csrc")
+# BTSBOT_AMD_* variables the Python package and the test suite read themselves: not the C library's
+_PYTHON_SIDE = {"LIB", "CHUNK", "MV_CHUNK", "PRECISION", "EXCHANGE", "EAGER_REPACK", "S2P_HINT", "TEST_CHILD"}
+
+
+def _switch_table():
+    text = open(os.path.join(_CSRC, "schedule.h")).read()
+    rows = re.findall(r'^\s*X\((\w+), (ON|INT), (HANDLE|PROCESS), "', text, re.M)
+    names = [r[0] for r in rows]
+    assert len(names) > 40 and len(set(names)) == len(names)     # every variable declared exactly once
+    return {r[0]: r[1:] for r in rows}
+
+
+def test_environment_is_read_through_the_switch_table_only():
+    """Outside schedule.h / schedule.hip (and common.h, which includes the table) no file of csrc/ reads the environment or
+    spells a BTSBOT_AMD_ variable as a string: launchers ask the table by enumerator."""
+    offenders = []
+    for f in sorted(os.listdir(_CSRC)):
+        if not f.endswith((".hip", ".h")) or f in ("schedule.h", "schedule.hip", "common.h"):
+            continue
+        for n, line in enumerate(open(os.path.join(_CSRC, f)), 1):
+            if re.search(r'env_on\(|env_int\(|getenv\(|"[^"]*BTSBOT_AMD_', line.split("//")[0]):
+                offenders.append(f"{f}:{n}: {line.strip()}")
+    assert not offenders, "\n".join(offenders)
+    assert "getenv(" not in open(os.path.join(_CSRC, "common.h")).read()
+
+
+def test_every_documented_switch_is_in_the_table():
+    """Each BTSBOT_AMD_* name the header, DESIGN.md section 4c's neighbourhood, bench.py, the tests and the tools use is a
+    row of the table, or one of the variables Python reads (an explicit list)."""
+    table = _switch_table()
+    files = [os.path.join(ROOT, "include", "btsbot_hip.h"), os.path.join(ROOT, "DESIGN.md"), os.path.join(ROOT, "bench.py")]
+    for d in ("tests", "tools"):
+        files += [os.path.join(ROOT, d, f) for f in sorted(os.listdir(os.path.join(ROOT, d))) if f.endswith(".py")]
+    unknown = {}
+    for path in files:
+        for name in re.findall(r"BTSBOT_AMD_([A-Z0-9_]*[A-Z0-9])(?![A-Z0-9_])", open(path).read()):
+            if name not in table and name not in _PYTHON_SIDE:
+                unknown.setdefault(name, os.path.relpath(path, ROOT))
+    assert not unknown, unknown
+    assert not _PYTHON_SIDE & set(table)
+
+
+def test_query_schedule_reports_what_the_switches_resolve_to(monkeypatch):
+    """btsbot_set_option "query_schedule:<field>" (model.schedule_flag): handle-scope switches are read when the handle is
+    created; a switch that vetoes a form shows in every decision that depends on it; unknown fields are an error."""
+    kind, cfg = CONFIGS["mm_pico"]
+    m = _build(kind, cfg, precision="bf16")
+    on = ("stage0", "stage1", "stage2p", "stage3", "head16", "stem16", "fused_mlp0", "fused_mlp1", "s0_keep", "s2_keep",
+          "mlp_bwd0", "mlp_bwd1", "dwln", "s2mlp", "wgrad_batch", "side_stream", "meta_side")
+    off = ("fused_mlp2", "fused_mlp3", "s1_keep", "mlp_bwd2", "mlp_bwd3", "fork_per_block", "deterministic", "train_split",
+           "train_packs", "maxvit_split", "mv_no_part")
+    for f in on:
+        assert m.schedule_flag(f), f
+    for f in off:
+        assert not m.schedule_flag(f), f
+    assert _build(kind, cfg, precision="f16").schedule_flag("s1_keep")
+    f32 = _build(kind, cfg, precision="f32")
+    assert not any(f32.schedule_flag(f) for f in ("stage0", "stage3", "head16", "stem16", "s0_keep", "s2_keep", "mlp_bwd0"))
+    with pytest.raises(ValueError):
+        m.schedule_flag("stage4")
+    with pytest.raises(ValueError):
+        m.schedule_flag("mlp_bwd4")
+    rc = _lib.lib().btsbot_set_option(m._handle.ptr, b"query_schedule:nonsense", 0)
+    assert rc == _lib.ERR_INVALID_ARG and b"nonsense" in _lib.lib().btsbot_last_error()
+    # the 128-channel fused backward needs dwln_bwd_kernel, and both keeping forms need their stage's fused backward
+    monkeypatch.setenv("BTSBOT_AMD_NO_DWLN", "1")
+    v = _build(kind, cfg, precision="bf16")
+    assert v.schedule_flag("mlp_bwd0") and not any(v.schedule_flag(f) for f in ("dwln", "mlp_bwd1", "s0_keep", "s2_keep"))
+    assert m.schedule_flag("dwln")                          # (an existing handle keeps what it read at create)
+    monkeypatch.delenv("BTSBOT_AMD_NO_DWLN")
+    monkeypatch.setenv("BTSBOT_AMD_NO_MLP_BWD", "1")
+    v = _build(kind, cfg, precision="bf16")
+    assert not any(v.schedule_flag(f) for f in ("mlp_bwd0", "mlp_bwd1", "s0_keep")) and v.schedule_flag("s2_keep")
+    monkeypatch.delenv("BTSBOT_AMD_NO_MLP_BWD")
+    monkeypatch.setenv("BTSBOT_AMD_NO_STAGE2", "1")
+    v = _build(kind, cfg, precision="bf16")
+    assert not v.schedule_flag("stage2p") and not v.schedule_flag("s2_keep") and v.schedule_flag("s0_keep")

@@ -397,6 +397,11 @@ def test_adamw_kernel(cuda):
         assert np.allclose(p.cpu().numpy(), g["traj"][s], rtol=2e-6, atol=1e-7)
 
 
+# the schedule field (csrc/schedule.h, model.schedule_flag) each switch below turns off
+_SWITCH_FIELD = {"BTSBOT_AMD_NO_STAGE2": "stage2p", "BTSBOT_AMD_NO_STAGE0": "stage0", "BTSBOT_AMD_NO_STAGE1": "stage1",
+                 "BTSBOT_AMD_NO_S3": "stage3", "BTSBOT_AMD_NO_HEAD16": "head16", "BTSBOT_AMD_NO_STEM16": "stem16"}
+
+
 @pytest.mark.parametrize("env", ["BTSBOT_AMD_NO_STAGE2", "BTSBOT_AMD_NO_STAGE0", "BTSBOT_AMD_NO_STAGE1", "BTSBOT_AMD_NO_S3",
                                  "BTSBOT_AMD_NO_HEAD16", "BTSBOT_AMD_NO_STAGE0,BTSBOT_AMD_NO_STEM16"])
 @pytest.mark.parametrize("prec", ["bf16", "f16", "f16x2"])
@@ -411,6 +416,11 @@ def test_alternative_schedules_match_oracle(cuda, monkeypatch, env, prec):
     img, meta, _ = synthetic_batch(21, seed=5)
     ref = _oracle(kind, cfg, sd, img, meta)
     m = build_model(kind, cfg, sd, cuda, prec)
+    # the switch took effect on this handle: the form it names is off, every other stage form still on
+    off = {_SWITCH_FIELD[e] for e in env.split(",")}
+    for field in ("stage0", "stage1", "stage2p", "stage3", "head16"):
+        assert m.schedule_flag(field) == (field not in off), (env, field)
+    assert m.schedule_flag("stem16") == (prec != "f16x2" and "stem16" not in off), env
     _check(run_model(kind, m, img.to(cuda), meta.to(cuda)), ref, prec)
 
 
@@ -535,6 +545,9 @@ def test_maxvit_alternative_kernels_match_oracle(cuda, monkeypatch, envs, prec):
     img, meta, _ = synthetic_batch(3, seed=2)
     ref = _mv_oracle(kind, cfg, sd, img, meta)
     m = build_model(kind, cfg, sd, cuda, prec)
+    # exactly the switches of this case are on in the handle's schedule
+    for sw in {e for t in _MV_SWITCHES for e in t}:
+        assert m.schedule_flag(sw.replace("BTSBOT_AMD_", "").lower()) == (sw in envs), (envs, sw)
     _check(run_model(kind, m, img.to(cuda), meta.to(cuda)), ref, prec)
 
 

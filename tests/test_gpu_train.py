@@ -134,7 +134,8 @@ def test_full_backward_alternative_schedules(cuda, monkeypatch, env):
     """The same gradients with the whole backward on one stream, and with the LayerNorm / depthwise backward as three
     launches instead of dwln_bwd_kernel (the switches are read when the handle is created)."""
     monkeypatch.setenv(env, "1")
-    _full_backward(cuda, "mm_pico")
+    field = {"BTSBOT_AMD_NO_SIDE_STREAM": "side_stream", "BTSBOT_AMD_NO_DWLN": "dwln"}[env]
+    _full_backward(cuda, "mm_pico", schedule={f: f != field for f in ("side_stream", "dwln")})
 
 
 def test_fused_layernorm_depthwise_backward_with_several_alerts_per_workgroup(cuda, monkeypatch):
@@ -147,8 +148,9 @@ def test_fused_layernorm_depthwise_backward_with_several_alerts_per_workgroup(cu
     img, meta, labels = synthetic_batch(B, seed=4)
     masks = {k: v.to(torch.uint8) for k, v in _masks(kind, cfg, B, seed=9).items()}
 
-    def grads():
+    def grads(dwln):
         m = build_model(kind, cfg, sd, cuda, "f32").train()
+        assert m.schedule_flag("dwln") == dwln
         m._forced_masks = masks
         logits = m(image_input=img.to(cuda), metadata_input=meta.to(cuda))
         loss = torch.nn.BCEWithLogitsLoss(pos_weight=torch.tensor([2.0], device=cuda))(
@@ -156,9 +158,9 @@ def test_fused_layernorm_depthwise_backward_with_several_alerts_per_workgroup(cu
         loss.backward()
         return {k: p.grad.detach().cpu().double() for k, p in m.named_parameters()}
 
-    fused = grads()
+    fused = grads(True)
     monkeypatch.setenv("BTSBOT_AMD_NO_DWLN", "1")
-    plain = grads()
+    plain = grads(False)
     worst = 0.0
     for k, b in plain.items():
         scale = max(b.abs().max().item(), 1e-7)
@@ -198,7 +200,7 @@ def test_gradient_buckets_are_complete_when_their_events_fire(cuda):
                 assert snap.abs().max().item() > 0, b
 
 
-def _full_backward(cuda, name):
+def _full_backward(cuda, name, schedule=None):
     """Every parameter trainable (train.py:233-236): gradients of the whole model -- stem, every
     ConvNeXt block (layer-scale, depthwise, LayerNorm, fc1, fc2), downsamples, head LayerNorm,
     metadata branch, fusion head -- against torch autograd through the fp32 CPU oracle.
@@ -211,6 +213,8 @@ def _full_backward(cuda, name):
         {"comb": (torch.rand(B, cfg["fc2_neurons"], generator=torch.Generator().manual_seed(9))
                   >= cfg["dropout"]).float()}
     m = build_model(kind, cfg, sd, cuda, "f32").train()
+    for field, on in (schedule or {}).items():   # the handle under test resolved the schedule the caller's switches ask for
+        assert m.schedule_flag(field) == on, field
     m._forced_masks = {k: v.to(torch.uint8) for k, v in masks.items()}
     trainable = [k for k, p in m.named_parameters()]
     if kind == "ConvNeXt":
@@ -359,6 +363,15 @@ def test_full_backward_16bit(cuda, monkeypatch, prec, bound, mlp):
     img, meta, labels = synthetic_batch(B, seed=4)
     masks = _masks(kind, cfg, B, seed=9)
     m = build_model(kind, cfg, sd, cuda, prec).train()
+    # the schedule this handle resolved is the case's: the default (stage 1's keeping form in f16 only) but for what
+    # the case's switches turn off or on
+    want = {"mlp_bwd0": mlp != "unfused", "mlp_bwd1": mlp not in ("unfused", "stage0_only"),
+            "s0_keep": mlp not in ("unfused", "per_op_forward"),
+            "s1_keep": (prec == "f16" or mlp == "stage1_keeping_kernel") and mlp not in ("unfused", "stage0_only", "per_op_forward"),
+            "s2_keep": mlp != "stage2_per_op", "s2mlp": mlp != "stage2_two_gemms", "fork_per_block": mlp == "fork_per_block",
+            "mlp_bwd2": False, "mlp_bwd3": False, "dwln": True, "wgrad_batch": True, "side_stream": True}
+    for field, on in want.items():
+        assert m.schedule_flag(field) == on, (prec, mlp, field)
     m._forced_masks = {k: v.to(torch.uint8) for k, v in masks.items()}
     trainable = [k for k, p in m.named_parameters()]
     logits = m(image_input=img.to(cuda), metadata_input=meta.to(cuda))

@@ -34,7 +34,9 @@ SYMBOLS = [
     "btsbot_reserve_train", "btsbot_forward_train", "btsbot_backward", "btsbot_debug_stamps",
     "btsbot_grad_buckets", "btsbot_wait_grad_bucket", "btsbot_allreduce_grads", "btsbot_use_workspace", "btsbot_set_option",
     "btsbot_augment", "btsbot_eval_metrics", "btsbot_prep_triplets",
+    "btsbot_embed_width", "btsbot_forward_embed",
 ]
+EMBEDDING = {"features": 0, "hidden": 1}   # enum btsbot_embedding
 
 
 class Config(C.Structure):
@@ -97,6 +99,10 @@ def lib() -> C.CDLL:
     L.btsbot_reserve.argtypes = [vp, i32]
     L.btsbot_forward.restype = i32
     L.btsbot_forward.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_uint64, vp]
+    L.btsbot_embed_width.restype = i32
+    L.btsbot_embed_width.argtypes = [vp, i32]
+    L.btsbot_forward_embed.restype = i32
+    L.btsbot_forward_embed.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp]
     L.btsbot_set_debug.restype = i32
     L.btsbot_set_debug.argtypes = [vp, i32]
     L.btsbot_read_tap.restype = i64

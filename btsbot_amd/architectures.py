@@ -20,6 +20,7 @@ VGG-like CNNs, out of scope per SURVEY.md section 2).
 from __future__ import annotations
 
 import ctypes as C
+import inspect
 import json
 import math
 import os
@@ -332,6 +333,55 @@ class _HipModel(nn.Module):
         if want_scores:
             return logits, scores.view(batch, 1)
         return logits
+
+    # -- embeddings ---------------------------------------------------------------------------
+    def embedding_dim(self, layer: str = "features") -> int:
+        """Width of ``embed(..., layer=layer)`` (``btsbot_embed_width``; no GPU needed)."""
+        if layer not in _lib.EMBEDDING:
+            raise ValueError(f"btsbot_amd: unknown embedding layer {layer!r} (have {sorted(_lib.EMBEDDING)})")
+        return _lib.check(_lib.lib().btsbot_embed_width(self._handle.ptr, _lib.EMBEDDING[layer]), "btsbot_embed_width")
+
+    def _bind_inputs(self, args, kwargs):
+        """(image, metadata) from the arguments of this model's own ``forward``."""
+        try:
+            given = inspect.signature(self.forward).bind(*args, **kwargs).arguments
+        except TypeError as e:
+            raise TypeError(f"btsbot_amd.{type(self).__name__}.embed takes the inputs of forward(): {e}") from None
+        if "input_data" in given:
+            return (given["input_data"], None) if self._table is not None else (None, given["input_data"])
+        return given["image_input"], given["metadata_input"]
+
+    def embed(self, *inputs, layer: str = "features", return_logits: bool = False, **kw_inputs):
+        """The model's representation of every alert, fp32 ``[B, embedding_dim(layer)]``, from the same launch that
+        scores it (``btsbot_forward_embed``).  ``layer="features"``: the input row of the first fusion / head Linear
+        -- the image feature (pooled, after the head LayerNorm where the wiring has one) followed by the metadata
+        branch's output: what ``frozen_fusion.remove_branch_head`` (architectures.py:298-320) leaves of a trained
+        branch; ``layer="hidden"``: the input row of the last Linear.  Takes the inputs ``forward`` takes
+        (``image_input=`` / ``metadata_input=``, or ``input_data=``).  ``return_logits=True`` returns
+        ``(embedding, logits [B, 1])``, the logits bit-identical to ``model(...)``.  Eval mode only (batch statistics
+        and dropout leave the vector ill-defined in train mode: RuntimeError); not differentiable."""
+        if layer not in _lib.EMBEDDING:
+            raise ValueError(f"btsbot_amd: unknown embedding layer {layer!r} (have {sorted(_lib.EMBEDDING)})")
+        if self.training:
+            raise RuntimeError("btsbot_amd: embed() is defined in eval mode only (BatchNorm batch statistics and "
+                               "dropout make the vector depend on the batch and the draw); call model.eval() first")
+        image, meta = self._bind_inputs(inputs, kw_inputs)
+        image, meta, batch, dev = self._check_inputs(image, meta)
+        width = self.embedding_dim(layer)
+        emb = torch.empty(batch, width, dtype=torch.float32, device=dev)
+        logits = torch.empty(batch, dtype=torch.float32, device=dev)
+        if batch > 0:
+            with torch.cuda.device(dev):
+                L, stream = self._prepare(dev, batch)
+                ptr = C.c_void_p(emb.data_ptr())
+                _lib.check(L.btsbot_forward_embed(
+                    self._handle.ptr,
+                    C.c_void_p(image.data_ptr() if image is not None else 0),
+                    C.c_void_p(meta.data_ptr() if meta is not None else 0),
+                    C.c_void_p(logits.data_ptr()), C.c_void_p(0),
+                    ptr if layer == "features" else C.c_void_p(0), ptr if layer == "hidden" else C.c_void_p(0),
+                    batch, C.c_void_p(stream)), "btsbot_forward_embed")
+        return (emb, logits.view(batch, 1)) if return_logits else emb
 
     # -- training mode ------------------------------------------------------------------------
     def _slot_groups(self):

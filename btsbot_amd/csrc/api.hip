@@ -701,8 +701,9 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
   return BTSBOT_OK;
 }
 
+// `features` / `hidden`: the embedding outputs of btsbot_forward_embed (nullptr: the scoring call)
 static int forward_chunk(btsbot_ctx* h, const float* img, const float* meta, float* logits,
-                         float* scores, int nb, hipStream_t st) {
+                         float* scores, float* features, float* hidden, int nb, hipStream_t st) {
   const btsbot_config& c = h->cfg;
   const float* m = h->mirror;
   float* x = nullptr;
@@ -728,6 +729,8 @@ static int forward_chunk(btsbot_ctx* h, const float* img, const float* meta, flo
                            i + 1 < h->n_comb ? h->act : ACT_NONE};
     g.logits = logits;
     g.scores = scores;
+    g.features = features;
+    g.hidden = hidden;
     g.B = nb;
     g.stamps = h->stamps ? h->stamps + STAMP_HEAD16 : nullptr;
     TRY(timed(h, CAT_HEAD16, st, [&] { return launch_head16(h->prec_head(), g, st); }));
@@ -763,6 +766,8 @@ static int forward_chunk(btsbot_ctx* h, const float* img, const float* meta, flo
   a.comb_act = h->act;
   a.logits = logits;
   a.scores = scores;
+  a.features = features;
+  a.hidden = hidden;
   a.B = nb;
   a.diag = h->sched.head_diag;
   TRY(timed(h, CAT_HEAD, st, [&] { return launch_head(a, st); }));
@@ -770,44 +775,66 @@ static int forward_chunk(btsbot_ctx* h, const float* img, const float* meta, flo
   return BTSBOT_OK;
 }
 
-extern "C" int btsbot_forward(btsbot_handle h, const float* triplets, const float* meta,
-                              float* logits, float* scores, int batch, int training,
-                              uint64_t dropout_seed, void* stream) {
-  (void)dropout_seed;
+// btsbot_forward and btsbot_forward_embed: preconditions, chunking and stream rules in one place
+static int forward_all(btsbot_ctx* h, const char* who, const float* triplets, const float* meta, float* logits,
+                       float* scores, float* features, float* hidden, int batch, void* stream) {
   if (h == nullptr || logits == nullptr || batch < 0) {
-    btsbot_set_error("forward: NULL handle/logits or negative batch");
+    btsbot_set_error("%s: NULL handle/logits or negative batch", who);
     return BTSBOT_ERR_INVALID_ARG;
   }
   if (!h->packed || !h->packed_full) {
-    btsbot_set_error(h->packed ? "forward: the last pack was btsbot_pack_params_train(); call "
+    btsbot_set_error(h->packed ? "%s: the last pack was btsbot_pack_params_train(); call "
                                  "btsbot_pack_params() before an inference forward"
-                               : "forward: btsbot_pack_params() has not been called");
+                               : "%s: btsbot_pack_params() has not been called", who);
     return BTSBOT_ERR_STATE;
   }
   if ((h->has_image && triplets == nullptr) || (h->has_meta && meta == nullptr)) {
-    btsbot_set_error("forward: this wiring needs %s input",
+    btsbot_set_error("%s: this wiring needs %s input", who,
                      h->has_image && triplets == nullptr ? "image" : "metadata");
     return BTSBOT_ERR_INVALID_ARG;
   }
-  if (training) {
-    btsbot_set_error("forward: for training mode call btsbot_forward_train() (explicit dropout "
-                     "keep-masks, BatchNorm batch statistics)");
-    return BTSBOT_ERR_STATE;
-  }
   if (batch == 0) return BTSBOT_OK;
   if (h->ws == nullptr || h->max_chunk < 1) {
-    btsbot_set_error("forward: btsbot_reserve() has not been called");
+    btsbot_set_error("%s: btsbot_reserve() has not been called", who);
     return BTSBOT_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
   TRY(pack_sync(h, st));
+  const size_t wf = h->comb_dims[0], wh = h->comb_dims[h->n_comb - 1];   // btsbot_embed_width
   for (int b0 = 0; b0 < batch; b0 += h->max_chunk) {
     const int nb = batch - b0 < h->max_chunk ? batch - b0 : h->max_chunk;
     TRY(forward_chunk(h, triplets ? triplets + (size_t)b0 * 3 * 63 * 63 : nullptr,
                       meta ? meta + (size_t)b0 * h->cfg.n_meta : nullptr, logits + b0,
-                      scores ? scores + b0 : nullptr, nb, st));
+                      scores ? scores + b0 : nullptr, features ? features + b0 * wf : nullptr,
+                      hidden ? hidden + b0 * wh : nullptr, nb, st));
   }
   return BTSBOT_OK;
+}
+
+extern "C" int btsbot_forward(btsbot_handle h, const float* triplets, const float* meta,
+                              float* logits, float* scores, int batch, int training,
+                              uint64_t dropout_seed, void* stream) {
+  (void)dropout_seed;
+  if (h != nullptr && logits != nullptr && batch >= 0 && training) {
+    TRY(forward_all(h, "forward", triplets, meta, logits, scores, nullptr, nullptr, 0, stream));   // (its other refusals first)
+    btsbot_set_error("forward: for training mode call btsbot_forward_train() (explicit dropout "
+                     "keep-masks, BatchNorm batch statistics)");
+    return BTSBOT_ERR_STATE;
+  }
+  return forward_all(h, "forward", triplets, meta, logits, scores, nullptr, nullptr, batch, stream);
+}
+
+extern "C" int btsbot_embed_width(btsbot_handle h, int which) {
+  if (h == nullptr || (which != BTSBOT_EMBED_FEATURES && which != BTSBOT_EMBED_HIDDEN)) {
+    btsbot_set_error("embed_width: NULL handle or unknown embedding %d", which);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  return which == BTSBOT_EMBED_FEATURES ? h->comb_dims[0] : h->comb_dims[h->n_comb - 1];
+}
+
+extern "C" int btsbot_forward_embed(btsbot_handle h, const float* triplets, const float* meta, float* logits,
+                                    float* scores, float* features, float* hidden, int batch, void* stream) {
+  return forward_all(h, "forward_embed", triplets, meta, logits, scores, features, hidden, batch, stream);
 }
 
 // ---------------------------------------------------------------------------------------

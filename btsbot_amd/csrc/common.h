@@ -520,6 +520,9 @@ struct HeadArgs {
   int comb_act;
   float* logits;
   float* scores;  // may be nullptr
+  // embedding outputs (btsbot_forward_embed), each may be nullptr; row-contiguous fp32, rows b >= B are never written
+  float* features;  // [B][dims[0]]: the concat row z, the input of the first fusion layer
+  float* hidden;    // [B][dims[n_layers - 1]]: the input of the last layer (= features when n_layers == 1)
   int B;
   int diag;       // timing diagnostics (BTSBOT_AMD_HEAD_DIAG): 1 skip feature LN, 2 skip metadata
                   // branch, 4 skip fusion layer 0, 8 skip fusion layers 1.., 16 skip all K loops

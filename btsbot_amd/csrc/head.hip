@@ -1,6 +1,8 @@
 // Fused classifier heads (fp32): optional head LayerNorm on the 1x1 image feature, metadata branch
 // (BatchNorm1d folded to scale/shift -> Linear -> act -> Linear [-> act]), concat (image first, then
-// metadata), fusion MLP, logits + sigmoid scores -- one kernel, nothing but the logits leaves the CU.
+// metadata), fusion MLP, logits + sigmoid scores -- one kernel; the logits leave the CU and, where the caller asks
+// for them (btsbot_forward_embed), the two embedding rows: `features`, the concat row, and `hidden`, the input of
+// the last layer.
 //
 // Reference wiring: /root/reference/btsbot/architectures.py:146-171 (mm_ConvNeXt, GELU),
 // :109-122 (ConvNeXt head), :282-293 (um_nn, ReLU), :299-313,358-372 (frozen_fusion, ReLU, metadata
@@ -108,6 +110,37 @@ __device__ __forceinline__ void dense(const float* in, int K, const float* __res
     dense_t<1>(in, K, wt, bias, N, act, outp, part);
 }
 
+// Embedding output: v[n][HG] (k-major LDS rows) -> dst[b0 + g][n] for the `rows` live alerts of the workgroup (the
+// padded alerts of the last workgroup hold duplicates of alert B - 1 and are never written).  A lane owns 4
+// consecutive k of one alert and stores them as one float4; a wave's 64 lanes are 8 alerts x 8 quads, 128
+// contiguous bytes per alert row.  The four reads of a lane are ds_read_b32 at dwords 32 q + 8 j + g (32 banks, 32
+// lanes per group): taken in the order j every quad of an alert would meet on one bank (4-way), so quad q starts at
+// j = q & 3 -- the group's 8 alerts x 4 quads then cover the 32 banks once -- and the lane turns its four values
+// back.  Widths that are not a multiple of 4, or a destination off 16 bytes, take dword stores, k along the lanes.
+__device__ __forceinline__ void store_rows(const float* v, int n, float* __restrict__ dst, int b0, int rows) {
+  static_assert(HG == 8, "store_rows: 8 alerts per k");
+  if ((n & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+    const int nq = n >> 2;
+    for (int i = threadIdx.x; i < HG * nq; i += HNT) {
+      const int g = i & (HG - 1), q = i >> 3, rot = q & 3;
+      float t[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t[j] = v[(4 * q + ((j + rot) & 3)) * HG + g];   // t[j] = element (j + rot) & 3
+      float4 o;
+      o.x = rot == 0 ? t[0] : rot == 1 ? t[3] : rot == 2 ? t[2] : t[1];
+      o.y = rot == 0 ? t[1] : rot == 1 ? t[0] : rot == 2 ? t[3] : t[2];
+      o.z = rot == 0 ? t[2] : rot == 1 ? t[1] : rot == 2 ? t[0] : t[3];
+      o.w = rot == 0 ? t[3] : rot == 1 ? t[2] : rot == 2 ? t[1] : t[0];
+      if (g < rows) *reinterpret_cast<float4*>(dst + (size_t)(b0 + g) * n + 4 * q) = o;
+    }
+  } else {
+    for (int i = threadIdx.x; i < rows * n; i += HNT) {
+      const int g = i / n, k = i - g * n;
+      dst[(size_t)(b0 + g) * n + k] = v[k * HG + g];
+    }
+  }
+}
+
 __global__ __launch_bounds__(HNT) void head_kernel(HeadArgs a) {
   static_assert(HG == 8, "dense() reads the 8 alerts of a k as two float4");
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -168,11 +201,14 @@ __global__ __launch_bounds__(HNT) void head_kernel(HeadArgs a) {
           z + a.feat_dim * HG, part, a.diag & 16);
   }
   __syncthreads();
+  const int live = min(HG, a.B - b0);   // alerts of this workgroup that exist
+  if (a.features != nullptr) store_rows(z, zd, a.features, b0, live);
   // ---- fusion MLP
   const float* in = z;
   float* bufs[2] = {t0, t1};
   for (int i = 0; i < a.n_layers; ++i) {
     float* o = bufs[i & 1];
+    if (a.hidden != nullptr && i + 1 == a.n_layers) store_rows(in, a.dims[i], a.hidden, b0, live);
     if ((i == 0 && (a.diag & 4)) || (i > 0 && (a.diag & 8))) { in = o; continue; }
     dense(in, a.dims[i], a.wt[i], a.b[i], a.dims[i + 1],
           i + 1 < a.n_layers ? a.comb_act : ACT_NONE, o, part, a.diag & 16);
@@ -189,6 +225,10 @@ __global__ __launch_bounds__(HNT) void head_kernel(HeadArgs a) {
 }  // namespace
 
 int launch_head(const HeadArgs& a, hipStream_t st) {
+  if (a.diag != 0 && (a.features != nullptr || a.hidden != nullptr)) {
+    btsbot_set_error("head: embedding outputs with the timing diagnostics on (diag %d skips the layers that make them)", a.diag);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
   if (a.B <= 0) return BTSBOT_OK;
   int maxw = a.f1 > a.n_meta ? a.f1 : a.n_meta;
   for (int i = 1; i <= a.n_layers; ++i) maxw = a.dims[i] > maxw ? a.dims[i] : maxw;

@@ -26,6 +26,8 @@ struct Head16Args {
   H16Layer comb[3];
   float* logits;
   float* scores;        // may be nullptr
+  float* features;      // embedding outputs as in HeadArgs (common.h): [B][feat_dim + m2.N] fp32, or nullptr
+  float* hidden;        // [B][comb[n_layers - 1].K] fp32, or nullptr
   int B;
   unsigned long long* stamps;     // optional: workgroup 0 / thread 0 stores the shader clock per phase
   int pitch_z, pitch_t, zwidth;   // LDS row pitches / concat width (filled in by launch_head16)

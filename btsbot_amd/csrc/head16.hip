@@ -1,7 +1,7 @@
 // Fused classifier heads on the matrix pipe (gfx950, the 16-bit modes): optional head LayerNorm on the 1x1 image
 // feature, metadata branch (BatchNorm1d folded to scale/shift -> Linear -> act -> Linear [-> act]), concat (image
-// first, then metadata), fusion MLP, logits + sigmoid scores -- one launch, 16 alerts per workgroup, nothing but the
-// logits leaves the CU.  Same wirings as head.hip (which stays the fp32 mode's head):
+// first, then metadata), fusion MLP, logits + sigmoid scores -- one launch, 16 alerts per workgroup; the logits leave
+// the CU and, on request, the two embedding rows (store_rows16).  Same wirings as head.hip (which stays the fp32 mode's head):
 // /root/reference/btsbot/architectures.py:146-171 (mm_ConvNeXt, GELU), :109-122 (ConvNeXt head), :282-293 (um_nn,
 // ReLU), :299-313,358-372 (frozen_fusion); sigmoid: inference_example.py:91.
 //
@@ -193,6 +193,37 @@ __device__ __forceinline__ void dense16(const Rows& in, const H16Layer& L, const
   }
 }
 
+// Embedding output: columns 0 .. n of an activation buffer -> dst[b0 + g][0 .. n] fp32, hi + lo added back (what the
+// next layer's three products see), for the alerts that exist (the last workgroup's rows past B hold duplicates of
+// alert B - 1 and are never written).  The LDS rows are alert-major already: a lane takes 4 consecutive columns of
+// one alert (two 8-byte reads, consecutive lanes consecutive addresses) and stores one float4, a wave 1 KB of a row.
+// Widths that are not a multiple of 4, or a destination off 16 bytes, take one column per lane and dword stores.
+template <typename T>
+__device__ __forceinline__ void store_rows16(const Rows& in, int n, float* __restrict__ dst, int b0, int B) {
+  typedef T __attribute__((ext_vector_type(4))) T4;
+  const int rows = min(HA, B - b0);
+  if ((n & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+    const int nq = n >> 2;
+    for (int i = threadIdx.x; i < rows * nq; i += HNT) {
+      const int g = i / nq, q = i - g * nq;
+      const unsigned char* p = in.hi + g * in.pitch + q * 8;
+      const T4 h = *reinterpret_cast<const T4*>(p), l = *reinterpret_cast<const T4*>(p + HA * in.pitch);
+      float4 o;
+      o.x = (float)h[0] + (float)l[0];
+      o.y = (float)h[1] + (float)l[1];
+      o.z = (float)h[2] + (float)l[2];
+      o.w = (float)h[3] + (float)l[3];
+      *reinterpret_cast<float4*>(dst + (size_t)(b0 + g) * n + 4 * q) = o;
+    }
+  } else {
+    for (int i = threadIdx.x; i < rows * n; i += HNT) {
+      const int g = i / n, k = i - g * n;
+      const unsigned char* p = in.hi + g * in.pitch + k * 2;
+      dst[(size_t)(b0 + g) * n + k] = (float)*reinterpret_cast<const T*>(p) + (float)*reinterpret_cast<const T*>(p + HA * in.pitch);
+    }
+  }
+}
+
 template <typename T> __global__ __launch_bounds__(HNT) void head16_kernel(Head16Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -296,6 +327,17 @@ template <typename T> __global__ __launch_bounds__(HNT) void head16_kernel(Head1
   for (int si = 0; si < a.n_steps; ++si) {
     const H16Step st = a.steps[si];
     const bool last = si + 1 == a.n_steps;
+    if (a.features != nullptr || a.hidden != nullptr) {
+      // embedding outputs: z is complete in front of the first fusion layer (the metadata branch's second layer wrote
+      // its columns, the barrier behind it has passed), `hidden` is the last layer's input; neither buffer is written
+      // by the step that follows.  One copy of the store code, like the layers.
+#pragma unroll 1
+      for (int w = 0; w < 2; ++w) {
+        float* dst = w == 0 ? a.features : a.hidden;
+        if (dst == nullptr || !(w == 0 ? si == a.n_steps - a.n_layers : last)) continue;
+        store_rows16<T>(w == 0 ? z : buf(st.in_buf), w == 0 ? a.zwidth : st.L.K, dst, b0, a.B);
+      }
+    }
     // K-split partial tiles (1 KB each) go to whichever of the three buffers the layer neither reads nor writes
     const Rows rb = buf(st.red_buf);
     dense16<T>(buf(st.in_buf), st.L, buf(st.out_buf), st.col0, reinterpret_cast<float*>(rb.hi),

@@ -53,9 +53,14 @@ if _S2P_HINT not in (0, 4, 5, 7):   # (the library would reject the value and th
 
 
 class ScoreStream:
-    def __init__(self, model, depth: int = 3, inputs_ready: bool = False):
+    def __init__(self, model, depth: int = 3, inputs_ready: bool = False, embed=None):
+        """embed: None (results are the logits), or "features" / "hidden": every result is ``(logits, embedding)``,
+        the embedding row of ``model.embed(..., layer=embed)`` from the same launch that scores the batch."""
         if depth < 1:
             raise ValueError("depth must be >= 1")
+        if embed is not None and embed not in _lib.EMBEDDING:
+            raise ValueError(f"embed must be None or one of {sorted(_lib.EMBEDDING)}, got {embed!r}")
+        self.embed = embed
         if model.training:
             raise RuntimeError("ScoreStream scores with an eval-mode model; call model.eval() first")
         dev = next(model.parameters()).device
@@ -106,7 +111,11 @@ class ScoreStream:
             _lib.check(_lib.lib().btsbot_set_option(m._handle.ptr, b"stage2p_alerts", _S2P_HINT), "btsbot_set_option")
         with torch.cuda.stream(side), torch.no_grad():
             try:
-                out = m(*inputs)
+                if self.embed is None:
+                    out = m(*inputs)
+                else:
+                    emb, logits = m.embed(*inputs, layer=self.embed, return_logits=True)
+                    out = (logits, emb)
             finally:
                 if hinted:
                     _lib.lib().btsbot_set_option(m._handle.ptr, b"stage2p_alerts", 0)
@@ -114,14 +123,15 @@ class ScoreStream:
             done.record(side)
         return out, done, inputs
 
-    def result(self, ticket) -> torch.Tensor:
-        """The batch's logits; returns once the batch has finished on the GPU (host-side wait), so the tensor is valid
-        on every stream."""
+    def result(self, ticket):
+        """The batch's logits -- with ``embed`` set, ``(logits, embedding)`` --; returns once the batch has finished on
+        the GPU (host-side wait), so the tensors are valid on every stream."""
         out, done, _inputs = ticket
         done.synchronize()
         # `out` was allocated while a side stream was current: tell the allocator that the caller's stream uses it too,
         # or the block could be handed to a later forward on that side stream while a caller-stream kernel still reads it
-        out.record_stream(torch.cuda.current_stream(self.device))
+        for t in (out if isinstance(out, tuple) else (out,)):
+            t.record_stream(torch.cuda.current_stream(self.device))
         return out
 
     def map(self, batches: Iterable[Tuple[torch.Tensor, ...]], lag: int = 16) -> Iterator[torch.Tensor]:

@@ -272,8 +272,40 @@ def fit(trainer: Trainer, train_set, val_images, val_metadata, val_labels, model
     return out
 
 
+def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, stem: str, batch_size: int = 1024,
+                     device="cuda", layer: str = "features") -> str:
+    """The embedding step at the end of a run (train.py:449-469, whose helper module the reference does not ship): load
+    ``model_dir/best_model.pth`` into ``model``, embed every alert of the test split -- of the validation split when
+    there are no test files -- through ``ScoreStream(embed=layer)`` and write ``{stem}.npy`` (fp32 [N, width], rows in
+    the candidate file's order) and, when that file has a ``candid`` column, ``{stem}.csv`` with it.  The 2-D
+    projection the reference makes of these rows (UMAP) is the caller's business.  Returns the .npy path."""
+    import numpy as np
+    from .data import load_split
+    from .pipeline import ScoreStream
+    from .to_HF import strip_module_prefix
+    dev = torch.device(device)
+    state = torch.load(os.path.join(model_dir, "best_model.pth"), map_location="cpu")
+    model.load_state_dict(strip_module_prefix(state), strict=True)
+    model = model.to(dev).eval()
+    try:
+        images, metadata, _labels, cand = load_split(data_base_dir, config, "test")
+    except FileNotFoundError:
+        images, metadata, _labels, cand = load_split(data_base_dir, config, "val")
+    parts = [t for t in (images, metadata) if t is not None]      # forward's own argument order
+    n = parts[0].shape[0]
+    batches = (tuple(t[i:i + batch_size].to(dev) for t in parts) for i in range(0, n, batch_size))
+    rows = [emb.cpu() for _logits, emb in ScoreStream(model, embed=layer).map(batches)]
+    out = torch.cat(rows).numpy() if rows else np.zeros((0, model.embedding_dim(layer)), dtype=np.float32)
+    os.makedirs(os.path.dirname(stem) or ".", exist_ok=True)
+    np.save(stem + ".npy", out)
+    if "candid" in cand.columns:
+        cand[["candid"]].to_csv(stem + ".csv", index=False)
+    return stem + ".npy"
+
+
 def run_training(config: dict, data_base_dir: str = "", run_name: str = "testing", device="cuda",
-                 precision: str = "bf16", models_root: str = "models", split_training: bool = False):
+                 precision: str = "bf16", models_root: str = "models", split_training: bool = False,
+                 embeddings_root: str = "embeddings"):
     """train.py:75-440 (``run_training(config)``) on this framework, minus WandB and the diagnostic figure: seeds,
     the split files (``data.load_split``), the model by name with the frozen_fusion freezing rule
     (train.py:224-236), AdamW(lr, betas=(beta_1, beta_2)) under the warm-up + cosine schedule, BCE with
@@ -283,8 +315,10 @@ def run_training(config: dict, data_base_dir: str = "", run_name: str = "testing
     all-reduce per step; rank 0 writes the files.  Config keys are the reference's: model_name, epochs,
     batch_size, learning_rate, warmup_epochs, beta_1, beta_2, patience, random_seed, train_data_version, N_max,
     metadata_cols, data_aug_*, plus the model's own.  split_training: precision 'f16x2' with a ConvNeXt image branch
-    only -- the training step's matrix products on split f16 operands (``set_split_training``).  Returns (history dict,
-    model_dir)."""
+    only -- the training step's matrix products on split f16 operands (``set_split_training``).
+    ``config['generate_embeddings']`` (train.py:449-469): after the best checkpoint is chosen, ``write_embeddings``
+    leaves ``{embeddings_root}/{model_name}_{run_name}.npy`` (+ ``.csv``); a failure there is printed and the run
+    still returns, as in the reference.  Returns (history dict, model_dir)."""
     import numpy as np
     import torch.distributed as dist
     from . import architectures
@@ -330,4 +364,14 @@ def run_training(config: dict, data_base_dir: str = "", run_name: str = "testing
     model_dir = os.path.join(models_root, f"{model_name}_{version}{n_str}_{dev.type}", run_name) + "/"
     hist = fit(trainer, train_set, vimg, vmeta, vlab, model_dir, epochs=epochs, patience=patience,
                val_batch_size=batch_size, config=config)
+    if config.get("generate_embeddings", False) and rank == 0:
+        try:
+            hist["embeddings_file"] = write_embeddings(model, config, data_base_dir, model_dir,
+                                                       os.path.join(embeddings_root, f"{model_name}_{run_name}"),
+                                                       batch_size=batch_size, device=dev)
+        except Exception as e:                             # train.py:466-469
+            import traceback
+            print("Error generating embeddings", e)
+            print(traceback.format_exc())
+            print("Skipping embedding generation.")
     return hist, model_dir

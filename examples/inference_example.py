@@ -40,6 +40,8 @@ def parse_args():
     p.add_argument("--precision", type=str, default=None, choices=[None, "f32", "bf16", "f16", "fp8"])
     p.add_argument("--all-batches", action="store_true",
                    help="score the whole file, not just its first batch, through btsbot.ScoreStream (two batches in flight)")
+    p.add_argument("--embeddings", type=str, default=None, metavar="PATH",
+                   help="also write the model's feature embedding of every alert of the file to PATH (.npy, fp32 [N, width])")
     p.add_argument("--random-weights", action="store_true",
                    help="no checkpoint: seeded random weights of the chosen architecture")
     return p.parse_args()
@@ -90,6 +92,20 @@ def run_all_batches(model, multi_modal: bool, data_dir: str, device="cuda"):
     return scores
 
 
+def write_embeddings(model, multi_modal: bool, data_dir: str, out_path: str, device="cuda"):
+    """The `features` row of every alert of the file (model.embed through btsbot.ScoreStream), saved as fp32 [N, width]."""
+    cand = pd.read_csv(os.path.join(data_dir, "usage_candidates.csv"), index_col=None)
+    triplets = np.load(os.path.join(data_dir, "usage_triplets.npy"), mmap_mode="r")
+    images, metadata, labels = prepare_inputs(cand, triplets, multi_modal)
+    ds = DeviceDataset(images, metadata, labels, batch_size=64, device=device, shuffle=False,
+                       drop_last=False, augment=False, check_nan=False)
+    scorer = btsbot.ScoreStream(model.to(device).eval(), depth=2, embed="features")
+    emb = torch.cat([e for _logits, e in scorer.map(batch[:-1] for batch in ds)]).cpu().numpy()
+    np.save(out_path, emb)
+    print(f"{emb.shape[0]} embeddings of width {emb.shape[1]} written to {out_path}")
+    return emb
+
+
 def random_model(architecture: str, multi_modal: bool, precision):
     cfg = dict(pretrained=False, train_data_version="v11", metadata_cols=METADATA_COLS,
                meta_fc1_neurons=128, meta_fc2_neurons=128, meta_dropout=0.25, comb_fc1_neurons=128,
@@ -115,3 +131,5 @@ if __name__ == "__main__":
         run_all_batches(model, args.multi_modal, args.data_dir)
     else:
         run_inference(model, args.multi_modal, args.data_dir)
+    if args.embeddings:
+        write_embeddings(model, args.multi_modal, args.data_dir, args.embeddings)

@@ -163,6 +163,27 @@ int btsbot_forward(btsbot_handle h, const float* triplets_nchw, const float* met
                    float* logits, float* scores, int batch, int training,
                    uint64_t dropout_seed, void* stream);
 
+/* Embedding outputs (eval mode): the model's learned representation of every alert next to its logit.
+ * Replaces: frozen_fusion.remove_branch_head (architectures.py:298-320) / the embedding step at the end of a run
+ * (train.py:449-469).
+ *   BTSBOT_EMBED_FEATURES  the input row of the first fusion / head Linear: the image feature (after the global pool
+ *                          and, where the wiring has one, the head LayerNorm) followed by the metadata branch's output
+ *                          (after its trailing activation where the wiring has one: not in the frozen_fusion wirings,
+ *                          whose branch the reference strips of it); dims[3] + meta_fc2 wide, or whichever half exists
+ *   BTSBOT_EMBED_HIDDEN    the input row of the last Linear (-> 1), after its activation, dropout as identity:
+ *                          comb_fc2 wide; for BTSBOT_UM_NN the same row as the features
+ * btsbot_embed_width() is the width in floats (negative: unknown `which`); it touches no device.
+ * btsbot_forward_embed() is btsbot_forward(training = 0) -- same preconditions, internal chunks and stream rules,
+ * bit-identical logits -- that also writes the rows: `features` / `hidden` are device buffers of [batch][width] fp32,
+ * row-contiguous, each may be NULL (as may `scores`; with both NULL this IS the scoring call).  Nothing is
+ * allocated, synchronised or copied to the host.  The rows come from the head kernel's own on-chip buffers: in the
+ * 16-bit modes they are the split 16-bit operands added back, i.e. the values the next layer multiplies. */
+enum btsbot_embedding { BTSBOT_EMBED_FEATURES = 0, BTSBOT_EMBED_HIDDEN = 1 };
+int btsbot_embed_width(btsbot_handle h, int which);
+int btsbot_forward_embed(btsbot_handle h, const float* triplets_nchw, const float* meta,
+                         float* logits, float* scores, float* features, float* hidden,
+                         int batch, void* stream);
+
 /* Training-mode forward: replaces model(...) under model.train() (train.py:510).  The image branch
  * is identical to inference (ConvNeXt has no BatchNorm / dropout, drop-path 0); the metadata
  * BatchNorm1d uses the statistics of THIS batch and, when master_arena is non-NULL, updates

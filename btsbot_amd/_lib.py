@@ -31,6 +31,8 @@ SYMBOLS = [
     "btsbot_profile_collect",
     "btsbot_op_gemm", "btsbot_op_dwconv_ln", "btsbot_op_stem", "btsbot_op_ln_patch", "btsbot_op_wgrad",
     "btsbot_op_gemm_gated", "btsbot_op_gemm_resid_ln",
+    "btsbot_op_mv_attn", "btsbot_op_mv_attn_block", "btsbot_op_mv_part", "btsbot_op_mv_dw3", "btsbot_op_mv_dw3_groups",
+    "btsbot_op_mv_mbconv_front", "btsbot_op_mv_mbconv_front_tiles", "btsbot_op_mv_se", "btsbot_op_mv_stem",
     "btsbot_reserve_train", "btsbot_forward_train", "btsbot_backward", "btsbot_debug_stamps",
     "btsbot_grad_buckets", "btsbot_wait_grad_bucket", "btsbot_allreduce_grads", "btsbot_use_workspace", "btsbot_set_option",
     "btsbot_augment", "btsbot_eval_metrics", "btsbot_prep_triplets",
@@ -129,6 +131,24 @@ def lib() -> C.CDLL:
     L.btsbot_op_stem.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp]
     L.btsbot_op_ln_patch.restype = i32
     L.btsbot_op_ln_patch.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, vp]
+    L.btsbot_op_mv_attn.restype = i32
+    L.btsbot_op_mv_attn.argtypes = [i32, i32, vp, vp, vp, i32, i32, i32, i32, vp]
+    L.btsbot_op_mv_attn_block.restype = i32
+    L.btsbot_op_mv_attn_block.argtypes = [i32] + [vp] * 10 + [i32, i32, i32, vp]
+    L.btsbot_op_mv_part.restype = i32
+    L.btsbot_op_mv_part.argtypes = [i32] + [vp] * 17 + [i32, i32, i32, i32, vp]
+    L.btsbot_op_mv_dw3.restype = i32
+    L.btsbot_op_mv_dw3.argtypes = [i32, i32] + [vp] * 6 + [i32, i32, i32, i32, vp]
+    L.btsbot_op_mv_dw3_groups.restype = i32
+    L.btsbot_op_mv_dw3_groups.argtypes = [i32, i32, i32]
+    L.btsbot_op_mv_mbconv_front.restype = i32
+    L.btsbot_op_mv_mbconv_front.argtypes = [i32] + [vp] * 8 + [i32, i32, i32, i32, i32, vp]
+    L.btsbot_op_mv_mbconv_front_tiles.restype = i32
+    L.btsbot_op_mv_mbconv_front_tiles.argtypes = [i32, i32]
+    L.btsbot_op_mv_se.restype = i32
+    L.btsbot_op_mv_se.argtypes = [i32] + [vp] * 6 + [i32, i32, i32, i32, f32, vp]
+    L.btsbot_op_mv_stem.restype = i32
+    L.btsbot_op_mv_stem.argtypes = [i32] + [vp] * 6 + [i32] + [vp] * 3 + [i32, vp]
     L.btsbot_debug_stamps.restype = i32
     L.btsbot_debug_stamps.argtypes = [vp, vp]
     L.btsbot_reserve_train.restype = i32

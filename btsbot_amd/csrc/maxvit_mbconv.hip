@@ -213,7 +213,12 @@ __global__ __launch_bounds__(256) void mv_mbconv_front_kernel(const T* __restric
         T8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          o[e] = (T)silu_fast(acc[e / 2][e & 1]);
+          // the pool sums the stored activation: the fp32 value is made opaque, or hipcc rounds the f16 copy it sums
+          // straight from the product (v_fma_mixlo_f16) and the copy it stores from the fp32 result, and the two differ
+          // by an f16 ulp where the second rounding lands on a tie
+          float sv = silu_fast(acc[e / 2][e & 1]);
+          asm("" : "+v"(sv));
+          o[e] = (T)sv;
           psum[e] += (float)o[e];
         }
         const long orow = (b * Ho + ty * G::TO + oy) * Ho + tx * G::TO + ox;

@@ -280,8 +280,13 @@ __global__ __launch_bounds__(256) void mv_dw3s_kernel(const T* __restrict__ in,
       T8 o;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        o[e] = (T)silu_fast(acc[p][e]);
-        psum[e] += (float)o[e];          // the pool sees the rounded activations, like the separate pass
+        // the pool sees the rounded activations, like the separate pass.  (The fp32 value is made opaque: hipcc
+        // otherwise rounds the f16 copy it sums straight from the product, v_fma_mixlo_f16, and the copy it stores from
+        // the fp32 result -- two values that differ by an f16 ulp where the second rounding lands on a tie.)
+        float sv = silu_fast(acc[p][e]);
+        asm("" : "+v"(sv));
+        o[e] = (T)sv;
+        psum[e] += (float)o[e];
       }
       *reinterpret_cast<T8*>(orow + (long)p * C) = o;
     }

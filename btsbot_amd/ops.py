@@ -150,3 +150,156 @@ def ln_patch(x, ln_w, ln_b, precision="f32"):
                                                  _p(out), B, HW, Cin, _stream(x)),
                    "btsbot_op_ln_patch")
     return out
+
+
+# ---- the MaxViT branch's kernels one at a time (btsbot_op_mv_*): parameters fp32 in the state-dict layout, activations
+# NHWC pixel rows; grid_mode 0 = 7x7 windows, 1 = the 7x7 dilated grid
+def _f32(*ts):
+    for t in ts:
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous()), "fp32 contiguous parameters"
+
+
+def mv_attn(qkv, table, B, H, grid_mode, impl=0, precision="f32", out=None):
+    """qkv [B*H*H, 3C] (channel order [head][q|k|v][32]), table [169, C/32] fp32 -> out [B*H*H, C].  impl 0: the
+    per-query kernel ('f32' / 'bf16' / 'f16'); impl 1: the MFMA kernel ('bf16' / 'f16')."""
+    dt = _DT[precision]
+    assert qkv.dtype == dt and qkv.is_contiguous() and qkv.shape[0] == B * H * H
+    Cc = qkv.shape[1] // 3
+    _f32(table)
+    assert table.shape == (169, Cc // 32)
+    if out is None:
+        out = torch.empty(B * H * H, Cc, dtype=dt, device=qkv.device)
+    assert out.dtype == dt and out.shape == (B * H * H, Cc) and out.is_contiguous()
+    with torch.cuda.device(qkv.device):
+        _lib.check(_lib.lib().btsbot_op_mv_attn(_lib.PRECISION[precision], impl, _p(qkv), _p(table), _p(out), B, H, Cc,
+                                                grid_mode, _stream(qkv)), "btsbot_op_mv_attn")
+    return out
+
+
+def mv_attn_block(xn, x, p, B, H, grid_mode, precision="bf16", xn2=None):
+    """C = 64: x (fp32, in place) += proj(attention(qkv(xn))), returns xn2 = LayerNorm2(x) in the precision's dtype.
+    p: dict with qkv_w [192,64], qkv_b, proj_w [64,64], proj_b, table [169,2], ln2_w, ln2_b (fp32)."""
+    dt = _DT[precision]
+    assert xn.dtype == dt and xn.is_contiguous() and xn.shape == (B * H * H, 64)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.shape == (B * H * H, 64)
+    ks = ("qkv_w", "qkv_b", "proj_w", "proj_b", "table", "ln2_w", "ln2_b")
+    _f32(*(p[k] for k in ks))
+    if xn2 is None:
+        xn2 = torch.empty_like(xn)
+    assert xn2.dtype == dt and xn2.shape == xn.shape and xn2.is_contiguous()
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().btsbot_op_mv_attn_block(_lib.PRECISION[precision], _p(xn), _p(x), _p(xn2),
+                                                      *(_p(p[k]) for k in ks), B, H, grid_mode, _stream(x)),
+                   "btsbot_op_mv_attn_block")
+    return xn2
+
+
+def mv_part(x, p, B, H, grid_mode, precision="bf16", mlp=True, post=None, post_out=None):
+    """C in {64, 128, 256}: x [B*H*H, C] fp32 in place, x += proj(attention(qkv(LN1(x)))) and with mlp
+    x += fc2(gelu(fc1(LN2(x)))).  p: dict with ln1_w, ln1_b, qkv_w, qkv_b, proj_w, proj_b, table and (mlp) ln2_w,
+    ln2_b, fc1_w, fc1_b, fc2_w, fc2_b.  post = (scale [C], shift [C]): also returns post_out = x * scale + shift in
+    the precision's dtype."""
+    dt = _DT[precision]
+    Cc = x.shape[1]
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.shape == (B * H * H, Cc)
+    ka = ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "table")
+    km = ("ln2_w", "ln2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")
+    args = [p[k] for k in ka] + [p[k] if mlp else None for k in km]
+    _f32(*args)
+    ps = pb = None
+    if post is not None:
+        ps, pb = post
+        _f32(ps, pb)
+        if post_out is None:
+            post_out = torch.empty(B * H * H, Cc, dtype=dt, device=x.device)
+        assert post_out.dtype == dt and post_out.shape == x.shape and post_out.is_contiguous()
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().btsbot_op_mv_part(_lib.PRECISION[precision], _p(x), *(_p(a) for a in args), _p(ps), _p(pb),
+                                                _p(post_out), B, H, Cc, grid_mode, _stream(x)), "btsbot_op_mv_part")
+    return post_out
+
+
+def mv_dw3_groups(H, C, stride):
+    return _lib.check(_lib.lib().btsbot_op_mv_dw3_groups(H, C, stride), "btsbot_op_mv_dw3_groups")
+
+
+def mv_dw3(x, w, scale, bias, stride, impl=0, precision="f32", out=None, part=None):
+    """x [B,H,H,C] -> silu(dw3x3_s(x, w [C,1,3,3]) * scale + bias) [B,H/s,H/s,C].  impl 1 ('bf16' / 'f16') also fills
+    part [B, mv_dw3_groups(H, C, s), C] fp32, the squeeze-excite pool's partial sums, and returns (out, part)."""
+    dt = _DT[precision]
+    B, H, _, Cc = x.shape
+    assert x.dtype == dt and x.is_contiguous()
+    _f32(w, scale, bias)
+    Ho = H // stride
+    if out is None:
+        out = torch.empty(B, Ho, Ho, Cc, dtype=dt, device=x.device)
+    assert out.dtype == dt and out.numel() == B * Ho * Ho * Cc and out.is_contiguous()
+    if impl == 1 and part is None:
+        part = torch.empty(B, mv_dw3_groups(H, Cc, stride), Cc, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().btsbot_op_mv_dw3(_lib.PRECISION[precision], impl, _p(x), _p(w), _p(scale), _p(bias),
+                                               _p(out), _p(part), B, H, Cc, stride, _stream(x)), "btsbot_op_mv_dw3")
+    return out if impl == 0 else (out, part)
+
+
+def mv_mbconv_front_tiles(H, stride):
+    return _lib.check(_lib.lib().btsbot_op_mv_mbconv_front_tiles(H, stride), "btsbot_op_mv_mbconv_front_tiles")
+
+
+def mv_mbconv_front(xn, conv1_w, b1, dw_w, dw_scale, b2, stride, precision="bf16", m2=None, part=None):
+    """xn [B,H,H,CIN] -> m2 [B,H/s,H/s,MID] = silu(dw3x3_s(silu(xn . conv1_w^T + b1)) * dw_scale + b2) and the pool's
+    per-tile partial sums part [B, tiles, MID] fp32: (m2, part)."""
+    dt = _DT[precision]
+    B, H, _, CIN = xn.shape
+    MID = conv1_w.shape[0]
+    assert xn.dtype == dt and xn.is_contiguous()
+    _f32(conv1_w, b1, dw_w, dw_scale, b2)
+    Ho = H // stride
+    if m2 is None:
+        m2 = torch.empty(B, Ho, Ho, MID, dtype=dt, device=xn.device)
+    if part is None:
+        part = torch.empty(B, mv_mbconv_front_tiles(H, stride), MID, dtype=torch.float32, device=xn.device)
+    with torch.cuda.device(xn.device):
+        _lib.check(_lib.lib().btsbot_op_mv_mbconv_front(_lib.PRECISION[precision], _p(xn), _p(conv1_w), _p(b1), _p(dw_w),
+                                                        _p(dw_scale), _p(b2), _p(m2), _p(part), B, H, CIN, MID, stride,
+                                                        _stream(xn)), "btsbot_op_mv_mbconv_front")
+    return m2, part
+
+
+def mv_se(y, fc1_w, fc1_b, fc2_w, fc2_b, inv_count, precision="f32", gate=None):
+    """gate [B,C] fp32 = sigmoid(fc2(silu(fc1(inv_count * y.sum(1))))): y [B,HW,C] a 16-bit map, or ('f32') rows of
+    partial sums.  fc1_w [RD,C], fc2_w [C,RD]."""
+    B, HW, Cc = y.shape
+    RD = fc1_w.shape[0]
+    assert y.dtype == _DT[precision] and y.is_contiguous()
+    _f32(fc1_w, fc1_b, fc2_w, fc2_b)
+    assert fc1_w.numel() == RD * Cc and fc2_w.numel() == RD * Cc
+    if gate is None:
+        gate = torch.empty(B, Cc, dtype=torch.float32, device=y.device)
+    with torch.cuda.device(y.device):
+        _lib.check(_lib.lib().btsbot_op_mv_se(_lib.PRECISION[precision], _p(y), _p(fc1_w), _p(fc1_b), _p(fc2_w), _p(fc2_b),
+                                              _p(gate), B, HW, Cc, RD, float(inv_count), _stream(y)), "btsbot_op_mv_se")
+    return gate
+
+
+def mv_stem(img, conv1_w, bn_scale, bn_shift, conv2_w, precision="bf16", pooled=False, pre=None, out=None, xn=None):
+    """img [B,3,63,63] fp32 -> the stem's fp32 output map [B,112,112,64] (pooled: its 2x2 average pool [B,56,56,64]);
+    pre = (scale [64], shift [64]): also xn [B,112,112,64] = map * scale + shift in the precision's dtype: (out, xn)."""
+    B = img.shape[0]
+    assert img.dtype == torch.float32 and img.is_contiguous() and img.shape[1:] == (3, 63, 63)
+    _f32(conv1_w, bn_scale, bn_shift, conv2_w)
+    hw = 56 if pooled else 112
+    if out is None:
+        out = torch.empty(B, hw, hw, 64, dtype=torch.float32, device=img.device)
+    assert out.dtype == torch.float32 and out.numel() == B * hw * hw * 64 and out.is_contiguous()
+    ps = pb = None
+    if pre is not None:
+        ps, pb = pre
+        _f32(ps, pb)
+        if xn is None:
+            xn = torch.empty(B, 112, 112, 64, dtype=_DT[precision], device=img.device)
+    with torch.cuda.device(img.device):
+        _lib.check(_lib.lib().btsbot_op_mv_stem(_lib.PRECISION[precision], _p(img), _p(conv1_w), _p(bn_scale), _p(bn_shift),
+                                                _p(conv2_w), _p(out), int(pooled), _p(xn), _p(ps), _p(pb), B,
+                                                _stream(img)), "btsbot_op_mv_stem")
+    return out if pre is None else (out, xn)

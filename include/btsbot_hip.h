@@ -375,6 +375,59 @@ int btsbot_op_stem(const float* img, const float* w, const float* bias, const fl
 int btsbot_op_ln_patch(int prec, const float* x, const float* ln_w, const float* ln_b,
                        void* patches, int B, int HW, int Cin, void* stream);
 
+/* The MaxViT branch's hand-written kernels one at a time.  Parameters are fp32 in the state-dict layout (timm's
+ * names); every call builds the kernel's operand images in a stream-ordered scratch with the pack kernels the handle
+ * uses, runs the kernel and releases the scratch on `stream`.  T = the type of `prec`.  Activations are NHWC pixel
+ * rows [B*H*H, C]; a partition is the 7x7 window (grid_mode 0) or the 7x7 dilated grid (grid_mode 1) of an H x H map,
+ * H a multiple of 7.  What a kernel cannot run comes back as BTSBOT_ERR_INVALID_ARG with a message.
+ *
+ * Multi-head attention inside the partitions: qkv [B*H*H, 3C] T, channel order [head][q|k|v][32]; table [169][C/32]
+ * f32 = attn.rel_pos.relative_position_bias_table; out [B*H*H, C] T.  impl 0: the per-query kernel (BTSBOT_F32 /
+ * BF16 / F16), impl 1: the MFMA kernel (BF16 / F16). */
+int btsbot_op_mv_attn(int prec, int impl, const void* qkv, const float* table, void* out, int B, int H, int C,
+                      int grid_mode, void* stream);
+/* C = 64, BF16 / F16: x (f32, in place) += proj(attention(qkv(xn))), xn2 (T) = LayerNorm(x) * ln2_w + ln2_b (eps
+ * 1e-6).  xn [B*H*H, 64] T is norm1's output; qkv_w [192][64], proj_w [64][64]; xn2 may alias xn. */
+int btsbot_op_mv_attn_block(int prec, const void* xn, float* x, void* xn2, const float* qkv_w, const float* qkv_b,
+                            const float* proj_w, const float* proj_b, const float* table, const float* ln2_w,
+                            const float* ln2_b, int B, int H, int grid_mode, void* stream);
+/* C in {64, 128, 256}, BF16 / F16: a partition block in one launch, x [B*H*H, C] f32 in place:
+ *   x += proj(attention(qkv(LayerNorm1(x))));  with fc1_w != NULL also  x += fc2(gelu(fc1(LayerNorm2(x)))).
+ * ln2_w .. fc2_b are all given or all NULL (the attention half alone).  post_out != NULL: also
+ * post_out [B*H*H, C] T = x * post_s[c] + post_b[c] (the next block's pre-norm BatchNorm copy). */
+int btsbot_op_mv_part(int prec, float* x, const float* ln1_w, const float* ln1_b, const float* qkv_w,
+                      const float* qkv_b, const float* proj_w, const float* proj_b, const float* table,
+                      const float* ln2_w, const float* ln2_b, const float* fc1_w, const float* fc1_b,
+                      const float* fc2_w, const float* fc2_b, const float* post_s, const float* post_b,
+                      void* post_out, int B, int H, int C, int grid_mode, void* stream);
+/* Depthwise 3x3 p1 (stride 1 / 2) + per-channel scale + bias + SiLU: in [B,H,H,C] T -> out [B,H/s,H/s,C] T =
+ * silu(conv(in, w) * scale[c] + bias[c]); w [C][1][3][3].  impl 0: one thread per output vector (F32 / BF16 / F16,
+ * part unused).  impl 1 (BF16 / F16; C/8 divides 256 or equals it, H/s a multiple of 7): strips of 7 outputs, and the
+ * squeeze-excite pool as partial sums part [B][btsbot_op_mv_dw3_groups(H, C, s)][C] f32 of the rounded outputs. */
+int btsbot_op_mv_dw3(int prec, int impl, const void* in, const float* w, const float* scale, const float* bias,
+                     void* out, float* part, int B, int H, int C, int stride, void* stream);
+int btsbot_op_mv_dw3_groups(int H, int C, int stride);
+/* MBConv's front half in one kernel (BF16 / F16, CIN = 64, MID a multiple of 64, output maps >= 28x28 in whole
+ * tiles): m2 [B,H/s,H/s,MID] T = silu(dw3x3_s(m1) * dw_scale + b2), m1 = T(silu(xn . conv1_w^T + b1));
+ * xn [B,H,H,CIN] T, conv1_w [MID][CIN], dw_w [MID][1][3][3]; part [B][btsbot_op_mv_mbconv_front_tiles(H, s)][MID]
+ * f32 = per-tile sums of the rounded m2. */
+int btsbot_op_mv_mbconv_front(int prec, const void* xn, const float* conv1_w, const float* b1, const float* dw_w,
+                              const float* dw_scale, const float* b2, void* m2, float* part, int B, int H, int CIN,
+                              int MID, int stride, void* stream);
+int btsbot_op_mv_mbconv_front_tiles(int H, int stride);
+/* Squeeze-excite gate: gate [B][C] f32 = sigmoid(fc2(silu(fc1(inv_count * sum_r y[b][r][:])))); y [B][HW][C] is a
+ * BF16 / F16 map, or BTSBOT_F32 rows of partial sums with HW = their count; fc1_w [RD][C], fc2_w [C][RD]. */
+int btsbot_op_mv_se(int prec, const void* y, const float* fc1_w, const float* fc1_b, const float* fc2_w,
+                    const float* fc2_b, float* gate, int B, int HW, int C, int RD, float inv_count, void* stream);
+/* The stem in the 16-bit modes: bilinear 63 -> 224 (align_corners = False), conv 3x3 s2 (3 -> 32) * bn_scale +
+ * bn_shift, SiLU (a T map), conv 3x3 s1 (32 -> 64).  img [B,3,63,63] f32; conv1_w [32][3][3][3], conv2_w [64][32][3][3];
+ * out f32 = the map [B,112,112,64], or with pooled = 1 its 2x2 average pool [B,56,56,64]; xn != NULL: also
+ * xn [B,112,112,64] T = map * pre_scale[c] + pre_shift[c] (the full-resolution map also with pooled = 1: the handle's
+ * own form, which pools `out` for the first block's shortcut and keeps xn for its conv1). */
+int btsbot_op_mv_stem(int prec, const float* img, const float* conv1_w, const float* bn_scale, const float* bn_shift,
+                      const float* conv2_w, float* out, int pooled, void* xn, const float* pre_scale,
+                      const float* pre_shift, int B, void* stream);
+
 /* Measurement aid with no reference counterpart (bench.py's roofline leg): when on, every kernel
  * launch of forward() is bracketed by two HIP events recorded on the launch stream;
  * profile_collect() waits for them and returns, per kernel family (profile_category_name), the

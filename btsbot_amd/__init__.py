@@ -21,6 +21,7 @@ from . import from_HF
 from . import to_HF
 from . import data
 from . import val
+from . import alert_utils
 from .architectures import (
     MaxViT,
     ConvNeXt,
@@ -34,9 +35,11 @@ from .architectures import (
 from .from_HF import download_HF_model, load_HF_model
 from .synthetic import METADATA_COLS, synthetic_batch
 from .pipeline import ScoreStream
+from .alert_utils import CUSTOM_COLS, alert_features, make_metadata
 
 __all__ = [
-    "__version__", "architectures", "from_HF", "to_HF", "data", "val",
+    "__version__", "architectures", "from_HF", "to_HF", "data", "val", "alert_utils",
     "MaxViT", "ConvNeXt", "mm_MaxViT", "mm_ConvNeXt", "mm_cnn", "um_cnn", "um_nn", "frozen_fusion",
     "download_HF_model", "load_HF_model", "METADATA_COLS", "synthetic_batch", "ScoreStream",
+    "CUSTOM_COLS", "alert_features", "make_metadata",
 ]

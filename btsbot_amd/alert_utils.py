@@ -1,17 +1,29 @@
-"""Alert -> triplet preprocessing (/root/reference/btsbot/alert_utils.py:110-196).
+"""Alert packets -> model inputs (the reference's alert_utils.py: make_triplet :110-196, prep_alerts :333-441).
 
-``make_triplet`` there gunzips and FITS-decodes the three stamps of an alert on the host (astropy),
+    triplets, drop = make_triplets(alerts, device="cuda")                       # image_input    [N,3,63,63]
+    meta = make_metadata(alerts, metadata_cols, new_drb=drb, device="cuda")     # metadata_input [N,len(cols)]
+    scores = torch.sigmoid(model(image_input=triplets[~drop], metadata_input=meta[~drop]))
+
+Images.  ``make_triplet`` there gunzips and FITS-decodes the three stamps of an alert on the host (astropy),
 then masks NaNs, L2-normalises, flags corrupted stamps and pads to 63x63.  Here the decoding is a
 dependency-free host step (``decode_stamp``: gzip + the primary HDU of a FITS image -- ZTF cutouts are
 single-HDU BITPIX = -32 images) and everything after it is one kernel (``btsbot_prep_triplets``) over a
 whole night's batch, writing the float32 NCHW tensor the classifier consumes
 (inference_example.py:62-64) without the float64 NHWC detour.
 
-    triplets, drop = make_triplets(alerts, device="cuda")          # alert packets as the reference takes them
-    # or, from stamps decoded elsewhere:
+    # from stamps decoded elsewhere:
     raw, shapes = stack_stamps(list_of_(science, template, difference)_arrays)
     triplets, drop = prep_triplets(raw.cuda(), shapes.cuda())
-    scores = torch.sigmoid(model(image_input=triplets[~drop], metadata_input=meta[~drop]))
+
+Metadata.  Six of the 25 columns the shipped multi-modal configurations read (``age``, ``days_since_peak``,
+``days_to_peak``, ``peakmag_so_far``, ``maxmag_so_far``, ``nnotdet``) are not packet fields: ``prep_alerts`` there
+derives them (and ``peakmag``, ``maxmag``) per object from the light curve so far, in a pandas loop that is quadratic
+per object.  Here they are ``CUSTOM_COLS``, one kernel over the whole batch (``btsbot_alert_features``) behind a
+stable device sort of the object ids; ``make_metadata`` adds the packet fields and orders the columns.
+
+    feats = alert_features(object_id, jd, magpsf, jdstarthist, ncovhist, ndethist)   # device tensors -> [N,8] float32
+
+Alerts of one object with equal ``jd`` are ordered by input position (the reference's unstable sort leaves that open).
 """
 from __future__ import annotations
 
@@ -126,3 +138,120 @@ def prep_triplets(raw: torch.Tensor, shapes: Optional[torch.Tensor] = None,
             C.c_void_p(out.data_ptr()), C.c_void_p(drop.data_ptr()), b, int(normalize),
             C.c_void_p(st)), "btsbot_prep_triplets")
     return out, drop.bool()
+
+
+# ---- metadata: the custom columns of prep_alerts (alert_utils.py:333-441) -----------------------------
+# the columns of alert_features(), in its output order
+CUSTOM_COLS = ("peakmag", "maxmag", "peakmag_so_far", "maxmag_so_far", "age", "days_since_peak", "days_to_peak",
+               "nnotdet")
+# alerts per LDS tile of btsbot_alert_features (TILE in csrc/alert_features.hip): objects of up to 64 alerts take one
+# wave, up to FEATURE_TILE one workgroup with the object resident in LDS, larger ones stream through the tile
+FEATURE_TILE = 1024
+_FEATURE_INPUTS = ("jd", "magpsf", "jdstarthist", "ncovhist", "ndethist")
+
+
+def _group_by_object(object_id: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(perm int32 [n], seg_offsets int32 [n + 1]) for btsbot_alert_features, on the device and without a host
+    sync.  Grouping is plumbing: a stable sort keeps input order inside an object, and object k's run starts where k
+    run heads lie to the left.  The number of objects would cost a sync, so the kernel is given n possibly empty
+    objects: the offsets past the last object all equal n."""
+    n, dev = object_id.shape[0], object_id.device
+    ids, perm = torch.sort(object_id.to(torch.int64), stable=True)
+    run = torch.zeros(n, dtype=torch.int64, device=dev)
+    run[1:] = torch.cumsum(ids[1:] != ids[:-1], 0)
+    offsets = torch.searchsorted(run, torch.arange(n + 1, device=dev))
+    return perm.to(torch.int32), offsets.to(torch.int32)
+
+
+def alert_features(object_id: torch.Tensor, jd: torch.Tensor, magpsf: torch.Tensor, jdstarthist: torch.Tensor,
+                   ncovhist: torch.Tensor, ndethist: torch.Tensor) -> torch.Tensor:
+    """CUSTOM_COLS of N alerts as float32 [N, 8] on the inputs' device, rows in input order.
+
+    object_id: any integers (equal = same object); jd, magpsf, jdstarthist are taken as float64, ncovhist, ndethist as
+    int32.  With O(i) the alerts of i's object and P(i) those of them up to and including i in (jd, input position)
+    order: peakmag / maxmag = min / max magpsf over O(i), *_so_far over P(i); age = jd - first, days_since_peak = jd -
+    jdpk, days_to_peak = jdpk - first with first = min(jdstarthist[i], min jd over O(i)) and jdpk the jd of the
+    earliest alert of P(i) at peakmag_so_far; nnotdet = ncovhist - ndethist.  NaN magpsf are skipped (all NaN: NaN); a
+    NaN jdstarthist gives NaN age and days_to_peak.  jd must be finite (not checked: that would be a host sync).
+    Everything is compared and subtracted in float64 and rounded to float32 once.  No host synchronisation."""
+    if object_id.device.type != "cuda":
+        raise RuntimeError("btsbot_amd.alert_utils.alert_features runs on the GPU; there is no CPU "
+                           f"fallback (object_id is on {object_id.device})")
+    dev = object_id.device
+    n = object_id.shape[0]
+    cols = (jd, magpsf, jdstarthist, ncovhist, ndethist)
+    for name, t in zip(("object_id",) + _FEATURE_INPUTS, (object_id,) + cols):
+        if t.dim() != 1 or t.shape[0] != n:
+            raise ValueError(f"{name} must be [{n}], got {tuple(t.shape)}")
+    if object_id.dtype.is_floating_point or object_id.dtype == torch.bool:
+        raise ValueError(f"object_id must be an integer tensor, got {object_id.dtype}")
+    jd, magpsf, jdstarthist = (t.to(device=dev, dtype=torch.float64).contiguous() for t in cols[:3])
+    ncovhist, ndethist = (t.to(device=dev, dtype=torch.int32).contiguous() for t in cols[3:])
+    out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    perm, offsets = _group_by_object(object_id)
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.lib().btsbot_alert_features(
+            C.c_void_p(perm.data_ptr()), C.c_void_p(offsets.data_ptr()), n, n,
+            C.c_void_p(jd.data_ptr()), C.c_void_p(magpsf.data_ptr()), C.c_void_p(jdstarthist.data_ptr()),
+            C.c_void_p(ncovhist.data_ptr()), C.c_void_p(ndethist.data_ptr()), C.c_void_p(out.data_ptr()),
+            C.c_void_p(st)), "btsbot_alert_features")
+    return out
+
+
+def make_metadata(alerts, metadata_cols: Sequence[str], new_drb=None, device="cuda") -> torch.Tensor:
+    """metadata_input [N, len(metadata_cols)] float32 on ``device`` for alert packets as prep_alerts
+    (alert_utils.py:333-441) takes them, columns in the order of ``metadata_cols``.
+
+    Each alert's row is ``alert["candidate"] | alert.get("classifications", {})``.  A column is, in this order of
+    precedence (the order in which prep_alerts overwrites the frame): one of CUSTOM_COLS, computed on the device from
+    objectId / jd / magpsf / jdstarthist / ncovhist / ndethist; ``"new_drb"`` when ``new_drb`` (one score per alert,
+    the caller's, as it is an argument of prep_alerts) is given; a packet field (of any alert: absent elsewhere = NaN,
+    as in a DataFrame; None = NaN).  Anything else raises KeyError naming the column, before any device work."""
+    alerts = list(alerts)
+    cols = list(metadata_cols)
+    n = len(alerts)
+    rows = [a["candidate"] | a.get("classifications", {}) for a in alerts]
+    fields = set().union(*rows) if rows else set()
+    custom = [c for c in cols if c in CUSTOM_COLS]
+    if new_drb is not None:
+        new_drb = np.asarray(new_drb, dtype=np.float64).reshape(-1)
+        if new_drb.shape[0] != n:
+            raise ValueError(f"new_drb has {new_drb.shape[0]} scores for {n} alerts")
+    for c in cols:
+        if n and c not in CUSTOM_COLS and not (c == "new_drb" and new_drb is not None) and c not in fields:
+            raise KeyError(c)
+    for c in (_FEATURE_INPUTS if custom and n else ()):
+        if c not in fields:
+            raise KeyError(c)
+
+    def column(name, dtype=np.float64):
+        vals = [r.get(name) for r in rows]
+        return np.array([np.nan if v is None else v for v in vals], dtype=dtype)
+
+    host = np.zeros((n, len(cols)), dtype=np.float32)
+    for k, c in enumerate(cols):
+        if c in CUSTOM_COLS:
+            continue
+        host[:, k] = new_drb if (c == "new_drb" and new_drb is not None) else column(c)
+    if custom and n:
+        ids = {}
+        object_id = np.array([ids.setdefault(a["objectId"], len(ids)) for a in alerts], dtype=np.int64)
+        jd = column("jd")
+        if not np.isfinite(jd).all():
+            raise ValueError("make_metadata: every alert needs a finite candidate.jd")
+        try:
+            ncov, ndet = column("ncovhist", np.int32), column("ndethist", np.int32)
+        except ValueError:
+            raise ValueError("make_metadata: every alert needs integer ncovhist and ndethist") from None
+        feats_in = [torch.from_numpy(x).to(device) for x in
+                    (object_id, jd, column("magpsf"), column("jdstarthist"), ncov, ndet)]
+    out = torch.from_numpy(host).to(device)
+    if custom and n:
+        feats = alert_features(*feats_in)
+        dst = torch.tensor([k for k, c in enumerate(cols) if c in CUSTOM_COLS], device=out.device)
+        src = torch.tensor([CUSTOM_COLS.index(c) for c in cols if c in CUSTOM_COLS], device=out.device)
+        out[:, dst] = feats[:, src]
+    return out

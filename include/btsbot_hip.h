@@ -470,6 +470,22 @@ int btsbot_augment(const float* src, const int64_t* index, const uint8_t* ops, f
 int btsbot_prep_triplets(const float* raw, const int* shapes, float* triplets, uint8_t* drop, int batch,
                          int normalize, void* stream);
 
+/* Replaces: the custom metadata columns of prep_alerts (alert_utils.py:333-441) for a batch of n_alerts alerts that
+ * the caller has grouped by object: perm int32 [n_alerts] lists alert indices object by object, in input order inside
+ * an object; object k owns perm[seg_offsets[k] .. seg_offsets[k+1]) (seg_offsets int32 [n_objects + 1], ascending from
+ * 0 to n_alerts; empty objects are allowed, so n_objects may be an upper bound whose surplus offsets all equal
+ * n_alerts).  perm and seg_offsets are trusted device data: they are read on the device and never validated on the
+ * host (the kernel clamps offsets to [0, n_alerts] and skips perm entries outside it, nothing more).
+ * With O(i) the alerts of i's object and P(i) those of them with (jd, index) <= (jd[i], i), out8 float32
+ * [n_alerts][8] (16-byte aligned, input order) = { min, max of magpsf over O(i); min, max of magpsf over P(i);
+ * age = jd[i] - first; days_since_peak = jd[i] - jdpk; days_to_peak = jdpk - first; ncovhist[i] - ndethist[i] },
+ * first = min(jdstarthist[i], min jd over O(i)) (NaN if jdstarthist[i] is), jdpk = the jd of the earliest alert of
+ * P(i) at P(i)'s minimum magpsf.  NaN magpsf are skipped; jd must be finite.  Compared and subtracted in float64,
+ * rounded once.  One launch on `stream`, no host synchronisation; n_alerts == 0 launches nothing. */
+int btsbot_alert_features(const int32_t* perm, const int32_t* seg_offsets, int n_alerts, int n_objects,
+                          const double* jd, const double* magpsf, const double* jdstarthist,
+                          const int32_t* ncovhist, const int32_t* ndethist, float* out8, void* stream);
+
 /* Replaces: the epoch / validation metrics of val.py:159-168 and train.py:550-558 -- out2[0] += sum_i of
  * BCEWithLogitsLoss(pos_weight) terms over n logits, out2[1] += number of alerts whose sigmoid(z) > 0.5
  * agrees with the label (caller zeroes out2 and divides by n). */

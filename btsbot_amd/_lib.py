@@ -36,6 +36,7 @@ SYMBOLS = [
     "btsbot_reserve_train", "btsbot_forward_train", "btsbot_backward", "btsbot_debug_stamps",
     "btsbot_grad_buckets", "btsbot_wait_grad_bucket", "btsbot_allreduce_grads", "btsbot_use_workspace", "btsbot_set_option",
     "btsbot_augment", "btsbot_eval_metrics", "btsbot_prep_triplets", "btsbot_alert_features",
+    "btsbot_policy_eval",
     "btsbot_embed_width", "btsbot_forward_embed",
 ]
 EMBEDDING = {"features": 0, "hidden": 1}   # enum btsbot_embedding
@@ -177,6 +178,8 @@ def lib() -> C.CDLL:
     L.btsbot_prep_triplets.argtypes = [vp, vp, vp, vp, i32, i32, vp]
     L.btsbot_alert_features.restype = i32
     L.btsbot_alert_features.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.btsbot_policy_eval.restype = i32
+    L.btsbot_policy_eval.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_double), i32, vp, vp, vp, vp]
     L.btsbot_eval_metrics.restype = i32
     L.btsbot_eval_metrics.argtypes = [vp, vp, f32, i64, vp, vp]
     if L.btsbot_abi_version() != ABI_VERSION:

@@ -216,13 +216,18 @@ def train_epoch(trainer: Trainer, dataset, epoch_metrics: bool = True):
 
 
 def fit(trainer: Trainer, train_set, val_images, val_metadata, val_labels, model_dir: str,
-        epochs: int, patience: int = 10, val_batch_size: int = 1024, config: Optional[dict] = None):
+        epochs: int, patience: int = 10, val_batch_size: int = 1024, config: Optional[dict] = None,
+        val_cand=None):
     """The epoch loop of train.py:303-352 on the device: per epoch ``train_epoch`` -> ``latest_model.pth`` ->
     validation pass (val.py's loop, on the live model instead of re-instantiating it from the file) ->
     scheduler step -> ``best_model.pth`` when the validation loss improved by at least 0.5 % ->
     early stopping after ``patience`` epochs without improvement.  Checkpoints are state dicts only, like
     the reference's (no optimiser state); ``report.json`` carries ``config`` for
-    to_HF.prep_config, the history and the best epoch's alert-level ``val_summary``.  Returns the run history dict (train/val loss and accuracy per epoch)."""
+    to_HF.prep_config, the history and the best epoch's alert-level ``val_summary``.  ``val_cand``: the validation
+    split's candidate table (a dict or DataFrame with ``objectId``, ``jd``, ``magpsf`` per validation alert, optionally
+    ``junk``, ``save_time``, ``trigger_time``); with it ``val_summary`` gains the per-source ``"policy_performance"``
+    (``val.policy_performance``, val.py:381-614), without it the summary is the alert-level one alone.  Returns the run
+    history dict (train/val loss and accuracy per epoch)."""
     import json
     import os
     import numpy as np
@@ -259,10 +264,13 @@ def fit(trainer: Trainer, train_set, val_images, val_metadata, val_labels, model
             if since >= patience:                                    # train.py:350-352
                 break
     out = {k: v[:done].tolist() for k, v in hist.items()}
-    # the alert-level numbers of the reference's val_summary (val.py:178-218 -> utils.make_report) for the best epoch;
-    # its figure and the per-source policy metrics need the candidate table and stay out of scope
+    # the alert-level numbers of the reference's val_summary (val.py:178-218 -> utils.make_report) for the best epoch,
+    # and the per-source policy metrics (val.py:381-614) when the candidate table is at hand; its figure stays out of scope
     from .val import alert_summary
     summary = alert_summary(best_raw_preds, best_val_labels) if best_raw_preds is not None else {}
+    if val_cand is not None and best_raw_preds is not None:
+        summary["policy_performance"] = policy_summary(val_cand, best_raw_preds, best_val_labels,
+                                                       next(trainer.model.parameters()).device)
     if main:
         with open(os.path.join(model_dir, "report.json"), "w") as f:
             json.dump({"train_config": dict(config or {}), "Training history": out, "val_summary": summary}, f,
@@ -270,6 +278,27 @@ def fit(trainer: Trainer, train_set, val_images, val_metadata, val_labels, model
     out["best_raw_preds"], out["best_val_labels"] = best_raw_preds, best_val_labels
     out["val_summary"] = summary
     return out
+
+
+def policy_summary(cand, raw_preds, labels, device="cuda") -> dict:
+    """``val.policy_performance`` for a candidate table: ``cand["objectId"]`` (names or integers), ``cand["jd"]``,
+    ``cand["magpsf"]``, one row per alert in the order of ``raw_preds`` / ``labels``; the optional columns ``junk``,
+    ``save_time`` and ``trigger_time`` are passed on when the table has them."""
+    import numpy as np
+    from .val import policy_performance
+    _, ids = np.unique(np.asarray(cand["objectId"]), return_inverse=True)
+    n = len(ids)
+    raw_preds, labels = np.asarray(raw_preds).reshape(-1), np.asarray(labels).reshape(-1)
+    if len(raw_preds) != n or len(labels) != n:
+        raise ValueError(f"the candidate table has {n} rows for {len(raw_preds)} scores and {len(labels)} labels")
+    dev = torch.device(device)
+    extra = {k: torch.as_tensor(np.asarray(cand[k], dtype=bool if k == "junk" else np.float64)).to(dev)
+             for k in ("junk", "save_time", "trigger_time") if k in cand}
+    return policy_performance(torch.as_tensor(ids.astype(np.int64)).to(dev),
+                              torch.as_tensor(np.asarray(cand["jd"], dtype=np.float64)).to(dev),
+                              torch.as_tensor(np.asarray(cand["magpsf"], dtype=np.float64)).to(dev),
+                              torch.as_tensor(labels.astype(np.int64)).to(dev),
+                              torch.as_tensor(raw_preds.astype(np.float32)).to(dev), **extra)
 
 
 def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, stem: str, batch_size: int = 1024,
@@ -310,7 +339,8 @@ def run_training(config: dict, data_base_dir: str = "", run_name: str = "testing
     the split files (``data.load_split``), the model by name with the frozen_fusion freezing rule
     (train.py:224-236), AdamW(lr, betas=(beta_1, beta_2)) under the warm-up + cosine schedule, BCE with
     pos_weight = N_neg / N_pos of the training split (train.py:211-212), the epoch loop with latest / best
-    checkpoints and early stopping (``fit``), and the report.  Under ``torch.distributed`` (one process per GPU,
+    checkpoints and early stopping (``fit``), and the report, whose ``val_summary`` carries the per-source ``policy_performance`` when the validation
+    split's candidate table has ``objectId``, ``jd`` and ``magpsf`` columns.  Under ``torch.distributed`` (one process per GPU,
     launched by torchrun) every rank trains its contiguous shard of each global batch and the gradients meet in one
     all-reduce per step; rank 0 writes the files.  Config keys are the reference's: model_name, epochs,
     batch_size, learning_rate, warmup_epochs, beta_1, beta_2, patience, random_seed, train_data_version, N_max,
@@ -337,7 +367,9 @@ def run_training(config: dict, data_base_dir: str = "", run_name: str = "testing
     torch.manual_seed(seed)
     torch.cuda.manual_seed_all(seed)
     timg, tmeta, tlab, _ = load_split(data_base_dir, config, "train")
-    vimg, vmeta, vlab, _ = load_split(data_base_dir, config, "val")
+    vimg, vmeta, vlab, vcand = load_split(data_base_dir, config, "val")
+    if not all(c in vcand.columns for c in ("objectId", "jd", "magpsf")):   # no light curves: the alert-level summary alone
+        vcand = None
     try:
         model_type = getattr(architectures, model_name)
     except AttributeError:
@@ -363,7 +395,7 @@ def run_training(config: dict, data_base_dir: str = "", run_name: str = "testing
                       warmup_epochs=warmup)
     model_dir = os.path.join(models_root, f"{model_name}_{version}{n_str}_{dev.type}", run_name) + "/"
     hist = fit(trainer, train_set, vimg, vmeta, vlab, model_dir, epochs=epochs, patience=patience,
-               val_batch_size=batch_size, config=config)
+               val_batch_size=batch_size, config=config, val_cand=vcand)
     if config.get("generate_embeddings", False) and rank == 0:
         try:
             hist["embeddings_file"] = write_embeddings(model, config, data_base_dir, model_dir,

@@ -40,6 +40,12 @@ def write_split(base, split, n, seed):
             img.permute(0, 2, 3, 1).contiguous().numpy().astype(np.float64))          # NHWC float64, as on disk
     df = pd.DataFrame(meta.numpy(), columns=METADATA_COLS)
     df["label"] = label
+    # light curves for the per-source policy metrics: about six alerts per object over two months (magpsf is a
+    # metadata column already); an object's label is its first alert's, as in the reference
+    rng = np.random.default_rng(seed)
+    obj = rng.integers(0, max(n // 6, 1), n)
+    df["objectId"] = [f"ZTF21{k:07d}" for k in obj]
+    df["jd"] = 2459300.5 + rng.uniform(0, 60, n)
     df.to_csv(os.path.join(base, "data", f"{split}_cand_v11_N100.csv"), index=False)
 
 
@@ -92,7 +98,10 @@ def main():
         for e, (tl, ta, vl, va) in enumerate(zip(hist["train_loss"], hist["train_accuracy"], hist["val_loss"],
                                                  hist["val_accuracy"])):
             print(f"epoch {e + 1}: train loss {tl:.4f} acc {ta:.3f} | val loss {vl:.4f} acc {va:.3f}")
-        print("val_summary:", {k: round(v, 4) if isinstance(v, float) else v for k, v in hist["val_summary"].items()})
+        print("val_summary:", {k: round(v, 4) if isinstance(v, float) else v for k, v in hist["val_summary"].items()
+                               if k != "policy_performance"})
+        for name, perf in hist["val_summary"].get("policy_performance", {}).items():     # per source, val.py:381-614
+            print(f"policy {name}: (recall, precision) = ({perf['policy_recall']:.3f}, {perf['policy_precision']:.3f})")
         cfg = to_HF.prep_config(model_dir)                  # report.json -> train_config.json
         to_HF.prep_model(model_dir, cfg)                    # best_model.pth -> pytorch_model.bin
         train_lab = pd.read_csv(os.path.join(base, "data", "train_cand_v11_N100.csv"))["label"].values

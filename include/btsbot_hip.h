@@ -486,6 +486,22 @@ int btsbot_alert_features(const int32_t* perm, const int32_t* seg_offsets, int n
                           const double* jd, const double* magpsf, const double* jdstarthist,
                           const int32_t* ncovhist, const int32_t* ndethist, float* out8, void* stream);
 
+/* Replaces: the per-object loop of the policy metrics in diagnostic_fig (val.py:454-500) for a batch of n_alerts alerts
+ * grouped by object exactly as for btsbot_alert_features (perm, seg_offsets, n_objects may be an upper bound with empty
+ * objects; trusted device data, clamped, never validated on the host).  policies is a HOST array [n_policies][4] =
+ * (thr, cut, k, gate; gate NaN = none), 1 <= n_policies <= 16 per launch, k an integer >= 1.  With P(i) the alerts of
+ * i's object with (jd, index) <= (jd[i], i), a policy fires at alert i when at least k alerts j of P(i) have
+ * (double)raw_pred[j] > thr and magpsf[j] < cut, and (without a gate, or) min magpsf over P(i) <= gate; NaN magpsf are
+ * never valid and are skipped by the minimum.  Per object and policy: obj_pred int32 [n_objects][n_policies] = 1 when the
+ * policy fires at any alert; obj_trigger double [n_objects][n_policies][2] = (jd, magpsf) of the (jd, index)-earliest
+ * alert it fires at, (-1, -1) when never.  obj_info double [n_objects][3] = (number of alerts, label of the object's
+ * first alert in input order (-1: empty object), min magpsf over the object (NaN: none)).  Compared in float64.  One
+ * launch on `stream`, no host synchronisation; n_alerts == 0 launches nothing. */
+int btsbot_policy_eval(const int32_t* perm, const int32_t* seg_offsets, int n_alerts, int n_objects,
+                       const double* jd, const double* magpsf, const float* raw_pred, const int32_t* label,
+                       const double* policies, int n_policies, int32_t* obj_pred, double* obj_trigger,
+                       double* obj_info, void* stream);
+
 /* Replaces: the epoch / validation metrics of val.py:159-168 and train.py:550-558 -- out2[0] += sum_i of
  * BCEWithLogitsLoss(pos_weight) terms over n logits, out2[1] += number of alerts whose sigmoid(z) > 0.5
  * agrees with the label (caller zeroes out2 and divides by n). */

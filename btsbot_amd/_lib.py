@@ -33,6 +33,11 @@ SYMBOLS = [
     "btsbot_op_gemm_gated", "btsbot_op_gemm_resid_ln",
     "btsbot_op_mv_attn", "btsbot_op_mv_attn_block", "btsbot_op_mv_part", "btsbot_op_mv_dw3", "btsbot_op_mv_dw3_groups",
     "btsbot_op_mv_mbconv_front", "btsbot_op_mv_mbconv_front_tiles", "btsbot_op_mv_se", "btsbot_op_mv_stem",
+    "btsbot_op_mvt_bn_row_blocks", "btsbot_op_mvt_dw3_bwd_w_row_blocks", "btsbot_op_mvt_attn_bwd_groups_per_head",
+    "btsbot_op_mvt_bn_fwd", "btsbot_op_mvt_bn_bwd", "btsbot_op_mvt_dw3_fwd", "btsbot_op_mvt_dw3_bwd_in",
+    "btsbot_op_mvt_dw3_bwd_w", "btsbot_op_mvt_attn_bwd", "btsbot_op_mvt_se_fwd", "btsbot_op_mvt_se_bwd",
+    "btsbot_op_mvt_avgpool2_bwd", "btsbot_op_mvt_col2im3", "btsbot_op_mvt_unpack_conv3_grad", "btsbot_op_mvt_gelu_fwd",
+    "btsbot_op_mvt_gelu_bwd", "btsbot_op_mvt_bcast_set",
     "btsbot_reserve_train", "btsbot_forward_train", "btsbot_backward", "btsbot_debug_stamps",
     "btsbot_grad_buckets", "btsbot_wait_grad_bucket", "btsbot_allreduce_grads", "btsbot_use_workspace", "btsbot_set_option",
     "btsbot_augment", "btsbot_eval_metrics", "btsbot_prep_triplets", "btsbot_alert_features",
@@ -150,6 +155,17 @@ def lib() -> C.CDLL:
     L.btsbot_op_mv_se.argtypes = [i32] + [vp] * 6 + [i32, i32, i32, i32, f32, vp]
     L.btsbot_op_mv_stem.restype = i32
     L.btsbot_op_mv_stem.argtypes = [i32] + [vp] * 6 + [i32] + [vp] * 3 + [i32, vp]
+    for name, args in (("bn_row_blocks", [i64]), ("dw3_bwd_w_row_blocks", [i64]), ("attn_bwd_groups_per_head", [i64, i32]),
+                       ("bn_fwd", [vp] * 7 + [i64, i32, i32, vp]), ("bn_bwd", [vp] * 8 + [i64, i32, i32, i32, vp]),
+                       ("dw3_fwd", [vp] * 4 + [i32] * 4 + [vp]), ("dw3_bwd_in", [vp] * 3 + [i32] * 4 + [vp]),
+                       ("dw3_bwd_w", [vp] * 4 + [i32] * 4 + [vp]), ("attn_bwd", [vp] * 5 + [i32] * 4 + [vp]),
+                       ("se_fwd", [vp] * 10 + [i32] * 4 + [vp]), ("se_bwd", [vp] * 13 + [i32] * 4 + [vp]),
+                       ("avgpool2_bwd", [vp, vp] + [i32] * 4 + [vp]), ("col2im3", [vp, vp] + [i32] * 3 + [vp]),
+                       ("unpack_conv3_grad", [vp, vp] + [i32] * 3 + [vp]), ("gelu_fwd", [vp, vp, i64, vp]),
+                       ("gelu_bwd", [vp, vp, i64, vp]), ("bcast_set", [vp, vp, i32, i32, i32, f32, vp])):
+        fn = getattr(L, "btsbot_op_mvt_" + name)
+        fn.restype = i32
+        fn.argtypes = args
     L.btsbot_debug_stamps.restype = i32
     L.btsbot_debug_stamps.argtypes = [vp, vp]
     L.btsbot_reserve_train.restype = i32

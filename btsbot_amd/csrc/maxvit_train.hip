@@ -615,6 +615,152 @@ __global__ __launch_bounds__(64) void mv_attn_bwd_kernel(const float* __restrict
   }
 }
 
+// ---- launchers: every kernel's launch with its grid arithmetic, on plain pointers and sizes.  The engine below and the
+// op-level entry points at the end of this file (btsbot_op_mvt_*, one kernel group at a time for the tests) run the same
+// ones.  Row blocks (gridDim.y) of the BatchNorm reductions over M rows, and of dw3_bwd_w over npix output pixels:
+inline unsigned bn_row_blocks(long M) { return (unsigned)(M / 256 > 256 ? 256 : (M / 256 > 0 ? M / 256 : 1)); }
+inline unsigned dw3_bwd_w_row_blocks(long npix) { return (unsigned)(npix / 64 > 256 ? 256 : (npix / 64 > 0 ? npix / 64 : 1)); }
+// attention backward: three workgroups fit a CU (LDS): 768 x 4 of them walk the units, each for one head
+inline long attn_bwd_groups_per_head(long units, int heads) { return units < 3072 / heads ? units : 3072 / heads; }
+
+// BatchNorm2d, training mode: batch statistics of x [M][C] into stat (mean | rstd), running statistics updated (or
+// nullptr), y = act(...);  sums0 / sums: two zeroed slots of 2C floats
+int launch_bn_train(const float* x, const float* w, const float* b, float* stat, float* sums0, float* sums, float* run_mean,
+                    float* run_var, float* y, long M, int C, int act, hipStream_t st) {
+  const dim3 grid((C + 63) / 64, bn_row_blocks(M));
+  hipLaunchKernelGGL(col_moments_kernel, grid, dim3(256), 0, st, x, (const float*)nullptr, sums0, M, C);
+  hipLaunchKernelGGL(bn_mean_kernel, dim3(nblk(C)), dim3(256), 0, st, sums0, stat, M, C);
+  hipLaunchKernelGGL(col_moments_kernel, grid, dim3(256), 0, st, x, (const float*)stat, sums, M, C);
+  hipLaunchKernelGGL(bn_finish_kernel, dim3(nblk(C)), dim3(256), 0, st, sums, stat, run_mean, run_var, M, C);
+  hipLaunchKernelGGL(bn_apply_kernel, dim3(nblk(M * C / 4)), dim3(256), 0, st, x, stat, w, b, y, M * C / 4, C, act);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+// ... and its backward: dy = gradient w.r.t. the layer's output (behind the activation), dx (+)= gradient w.r.t. x (dx may
+// be dy), dw / db += ;  sums: one zeroed slot
+int launch_bn_train_bwd(const float* x, const float* dy, const float* stat, const float* w, const float* b, float* sums,
+                        float* dx, float* dw, float* db, long M, int C, int act, int accumulate, hipStream_t st) {
+  const dim3 grid((C + 63) / 64, bn_row_blocks(M));
+  hipLaunchKernelGGL(bn_bwd_sums_kernel, grid, dim3(256), 0, st, x, dy, stat, w, b, sums, M, C, act);
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nblk(M * C / 4)), dim3(256), 0, st, x, dy, stat, w, b, (const float*)sums, dx,
+                     dw, db, M, C, act, accumulate);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+// depthwise 3x3 on packed taps w9 [9][C] (launch_mv_pack_dw)
+int launch_dw3_fwd(const float* in, const float* w9, const float* bias, float* out, int B, int H, int C, int s, hipStream_t st) {
+  const long Mo = (long)B * (H / s) * (H / s);
+  hipLaunchKernelGGL(dw3_fwd_kernel, dim3(nblk(Mo * C / 4)), dim3(256), 0, st, in, w9, bias, out, B, H, C, s);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+int launch_dw3_bwd_in(const float* dout, const float* w9, float* din, int B, int H, int C, int s, hipStream_t st) {
+  const long Min = (long)B * H * H;
+  hipLaunchKernelGGL(dw3_bwd_in_kernel, dim3(nblk(Min * C / 4)), dim3(256), 0, st, dout, w9, din, B, H, C, s);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+// filter / bias gradients: tap-major into the scratch g9 [10][C] (zeroed here), then added into the master layout dw [C][1][3][3]
+int launch_dw3_bwd_w(const float* in, const float* dout, float* g9, float* dw, float* dbias, int B, int H, int C, int s,
+                     hipStream_t st) {
+  HIP_TRY(hipMemsetAsync(g9, 0, (size_t)10 * C * 4, st));
+  const long npix = (long)B * (H / s) * (H / s);
+  const dim3 grid((C + 63) / 64, dw3_bwd_w_row_blocks(npix));
+  hipLaunchKernelGGL(dw3_bwd_w_kernel, grid, dim3(256), 0, st, in, dout, g9, dbias, B, H, C, s);
+  hipLaunchKernelGGL(unpack_dw_grad_kernel, dim3(nblk(9L * C)), dim3(256), 0, st, (const float*)g9, dw, C);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+// attention backward of one layer: dqkv written, dtable [169][heads] += ;  dbias: scratch [32][2401], the gradient of the
+// bias [heads <= 16][49][49] in its first half, the bias image bias_t in its second
+int launch_attn_bwd(const float* qkv, const float* table, const float* dout, float* dqkv, float* dbias, float* dtable, int B,
+                    int H, int C, int grid_mode, hipStream_t st) {
+  const int heads = C / 32;
+  HIP_TRY(hipMemsetAsync(dbias, 0, (size_t)heads * 2401 * 4, st));
+  VTRY(launch_mv_pack_relbias(table, dbias + 16 * 2401, heads, st));
+  const long units = (long)B * (H / 7) * (H / 7);
+  const long per_head = attn_bwd_groups_per_head(units, heads);
+  hipLaunchKernelGGL(mv_attn_bwd_kernel, dim3((unsigned)(per_head * heads)), dim3(64), 0, st, qkv, (const float*)(dbias + 16 * 2401),
+                     dout, dqkv, dbias, H, C, grid_mode, (int)units);
+  hipLaunchKernelGGL(relbias_grad_kernel, dim3(nblk(169 * heads)), dim3(256), 0, st, (const float*)dbias, dtable, heads);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+// y[b][p][c] = a[b][p][c] * g[b][c]   (y may be a)
+int launch_gate_mul(const float* a, const float* g, float* y, int B, int P, int C, hipStream_t st) {
+  const long n4 = (long)B * P * C / 4;
+  hipLaunchKernelGGL(gate_mul_kernel, dim3(nblk(n4)), dim3(256), 0, st, a, g, y, P, C, n4);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+// squeeze-excite of a2 [B][P][C]: pool = mean_p a2, r = silu(rpre = fc1 pool), gate = sigmoid(fc2 r), gated = a2 * gate
+int launch_se_fwd(const float* a2, const float* w1, const float* b1, const float* w2, const float* b2, float* pool, float* rpre,
+                  float* r, float* gate, float* gated, int B, int P, int C, int RD, hipStream_t st) {
+  hipLaunchKernelGGL(alert_colsum_kernel, dim3((C + 63) / 64, B), dim3(256), 0, st, a2, (const float*)nullptr, pool, P, C,
+                     1.0f / (float)P);
+  hipLaunchKernelGGL(lin_fwd_small_kernel, dim3(nblk((long)B * RD)), dim3(256), 0, st, (const float*)pool, w1, b1, rpre, r, B, C,
+                     RD, 1);
+  hipLaunchKernelGGL(lin_fwd_small_kernel, dim3(nblk((long)B * C)), dim3(256), 0, st, (const float*)r, w2, b2, (float*)nullptr,
+                     gate, B, RD, C, 2);
+  return launch_gate_mul(a2, gate, gated, B, P, C, st);
+}
+// ... and its backward, in place: d [B][P][C] holds d(gated) and leaves as d(a2);  dg[b][c] = sum_p d(gated) a2,
+// d(a2) = d(gated) g + the pooled path;  dw1 / db1 / dw2 / db2 += ;  dgate, dpool, dgpre [B][C] and dr [B][RD]: scratch
+int launch_se_bwd(float* d, const float* a2, const float* pool, const float* rpre, const float* r, const float* gate,
+                  const float* w1, const float* w2, float* dw1, float* db1, float* dw2, float* db2, float* dgate, float* dr,
+                  float* dpool, float* dgpre, int B, int P, int C, int RD, hipStream_t st) {
+  hipLaunchKernelGGL(alert_colsum_kernel, dim3((C + 63) / 64, B), dim3(256), 0, st, (const float*)d, a2, dgate, P, C, 1.0f);
+  VTRY(launch_gate_mul(d, gate, d, B, P, C, st));                                   // d(a2) = d(gated) * g, in place
+  hipLaunchKernelGGL(act_bwd_small_kernel, dim3(nblk((long)B * C)), dim3(256), 0, st, (const float*)dgate, gate, dgpre, B * C, 2);
+  hipLaunchKernelGGL(lin_bwd_w_small_kernel, dim3(nblk((long)C * RD)), dim3(256), 0, st, (const float*)dgpre, r, dw2, db2, B, RD,
+                     C);
+  hipLaunchKernelGGL(lin_bwd_in_small_kernel, dim3(nblk((long)B * RD)), dim3(256), 0, st, (const float*)dgpre, w2, dr, B, RD, C);
+  hipLaunchKernelGGL(act_bwd_small_kernel, dim3(nblk((long)B * RD)), dim3(256), 0, st, (const float*)dr, rpre, dr, B * RD, 1);
+  hipLaunchKernelGGL(lin_bwd_w_small_kernel, dim3(nblk((long)RD * C)), dim3(256), 0, st, (const float*)dr, pool, dw1, db1, B, C,
+                     RD);
+  hipLaunchKernelGGL(lin_bwd_in_small_kernel, dim3(nblk((long)B * C)), dim3(256), 0, st, (const float*)dr, w1, dpool, B, C, RD);
+  const long n = (long)B * P * C;
+  hipLaunchKernelGGL(bcast_add_kernel, dim3(nblk(n)), dim3(256), 0, st, d, (const float*)dpool, P, C, n, 1.0f / (float)P);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+int launch_bcast_set(float* d, const float* v, int B, int P, int C, float scale, hipStream_t st) {
+  const long n = (long)B * P * C;
+  hipLaunchKernelGGL(bcast_set_kernel, dim3(nblk(n)), dim3(256), 0, st, d, v, P, C, n, scale);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+int launch_avgpool2_bwd(const float* g, float* dx, int B, int H, int C, int accumulate, hipStream_t st) {
+  hipLaunchKernelGGL(avgpool2_bwd_kernel, dim3(nblk((long)B * H * H * C)), dim3(256), 0, st, g, dx, B, H, C, accumulate);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+int launch_add(float* a, const float* b, long n4, hipStream_t st) {   // a += b, n4 = count / 4
+  hipLaunchKernelGGL(add_kernel, dim3(nblk(n4)), dim3(256), 0, st, a, b, n4);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+int launch_gelu_fwd(const float* pre, float* out, long n4, hipStream_t st) {
+  hipLaunchKernelGGL(gelu_fwd_kernel, dim3(nblk(n4)), dim3(256), 0, st, pre, out, n4);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+int launch_gelu_bwd(const float* pre, float* d, long n4, hipStream_t st) {
+  hipLaunchKernelGGL(gelu_bwd_kernel, dim3(nblk(n4)), dim3(256), 0, st, pre, d, n4);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+int launch_col2im3(const float* dcol, float* din, int B, int H, int C, hipStream_t st) {
+  hipLaunchKernelGGL(col2im3_kernel, dim3(nblk((long)B * H * H * C)), dim3(256), 0, st, dcol, din, B, H, C);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+int launch_unpack_conv3_grad(const float* gp, float* g, int O, int C, int ldp, hipStream_t st) {
+  hipLaunchKernelGGL(unpack_conv3_grad_kernel, dim3(nblk((long)O * C * 9)), dim3(256), 0, st, gp, g, O, C, ldp);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
 // ---- the engine's cache: every activation the backward needs, carved from one allocation -------------------------
 constexpr size_t MVT_WPART_FLOATS = (size_t)16 << 20;
 constexpr int MVT_SUM_SLOTS = 96;   // BatchNorm reduction slots per pass: 2 per layer forward (34 layers), 1 backward
@@ -741,37 +887,25 @@ struct MvtSums {
 static int bn_train(const btsbot_ctx* h, const float* x, const BnPk& bn, float* stat, MvtSums& arena, float* y, long M, int C,
                     int act, float* master, hipStream_t st) {
   const float* m = h->mirror;
-  const dim3 grid((C + 63) / 64, (unsigned)(M / 256 > 256 ? 256 : (M / 256 > 0 ? M / 256 : 1)));
   float* sums0 = arena.take();
   float* sums = arena.take();
   if (sums == nullptr) {
     btsbot_set_error("maxvit_train: out of BatchNorm reduction slots");
     return BTSBOT_ERR_STATE;
   }
-  hipLaunchKernelGGL(col_moments_kernel, grid, dim3(256), 0, st, x, (const float*)nullptr, sums0, M, C);
-  hipLaunchKernelGGL(bn_mean_kernel, dim3(nblk(C)), dim3(256), 0, st, sums0, stat, M, C);
-  hipLaunchKernelGGL(col_moments_kernel, grid, dim3(256), 0, st, x, (const float*)stat, sums, M, C);
-  hipLaunchKernelGGL(bn_finish_kernel, dim3(nblk(C)), dim3(256), 0, st, sums, stat, master ? master + bn.rm : nullptr,
-                     master ? master + bn.rv : nullptr, M, C);
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(nblk(M * C / 4)), dim3(256), 0, st, x, stat, m + bn.w, m + bn.b, y, M * C / 4, C, act);
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
+  return launch_bn_train(x, m + bn.w, m + bn.b, stat, sums0, sums, master ? master + bn.rm : nullptr,
+                         master ? master + bn.rv : nullptr, y, M, C, act, st);
 }
 // ... and its backward: dy = gradient w.r.t. the layer's output (behind the activation), dx (+)= gradient w.r.t. x
 static int bn_train_bwd(const btsbot_ctx* h, const float* x, const float* dy, const BnPk& bn, const float* stat, MvtSums& arena,
                         float* dx, float* grads, long M, int C, int act, int accumulate, hipStream_t st) {
   const float* m = h->mirror;
-  const dim3 grid((C + 63) / 64, (unsigned)(M / 256 > 256 ? 256 : (M / 256 > 0 ? M / 256 : 1)));
   float* sums = arena.take();
   if (sums == nullptr) {
     btsbot_set_error("maxvit_train: out of BatchNorm reduction slots");
     return BTSBOT_ERR_STATE;
   }
-  hipLaunchKernelGGL(bn_bwd_sums_kernel, grid, dim3(256), 0, st, x, dy, stat, m + bn.w, m + bn.b, sums, M, C, act);
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nblk(M * C / 4)), dim3(256), 0, st, x, dy, stat, m + bn.w, m + bn.b,
-                     (const float*)sums, dx, grads + bn.w, grads + bn.b, M, C, act, accumulate);
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
+  return launch_bn_train_bwd(x, dy, stat, m + bn.w, m + bn.b, sums, dx, grads + bn.w, grads + bn.b, M, C, act, accumulate, st);
 }
 
 int maxvit_train_forward(btsbot_ctx* h, const float* img, int B, float* master, hipStream_t st, float** feat_out) {
@@ -864,18 +998,11 @@ int maxvit_train_forward(btsbot_ctx* h, const float* img, int B, float* master, 
     VTRY(gemm(a.a0, m + b.c1_w, m + b.c1_b, a.c1, Min, b.mid, b.cin));
     VTRY(bn_train(h, a.c1, b.n1, a.st1, sums_arena, a.a1, Min, b.mid, 1, master, st));
     VTRY(launch_mv_pack_dw(m + b.c2_w, one, k.g9, b.mid, st));
-    hipLaunchKernelGGL(dw3_fwd_kernel, dim3(nblk(Mo * b.mid / 4)), dim3(256), 0, st, a.a1, k.g9, m + b.c2_b, a.d2, B, b.hin,
-                       b.mid, b.stride);
+    VTRY(launch_dw3_fwd(a.a1, k.g9, m + b.c2_b, a.d2, B, b.hin, b.mid, b.stride, st));
     VTRY(bn_train(h, a.d2, b.n2, a.st2, sums_arena, a.a2, Mo, b.mid, 1, master, st));
     // squeeze-excite
-    hipLaunchKernelGGL(alert_colsum_kernel, dim3((b.mid + 63) / 64, B), dim3(256), 0, st, a.a2, (const float*)nullptr,
-                       a.sepool, hw2, b.mid, 1.0f / (float)hw2);
-    hipLaunchKernelGGL(lin_fwd_small_kernel, dim3(nblk((long)B * b.rd)), dim3(256), 0, st, a.sepool, m + b.se1_w,
-                       m + b.se1_b, a.rpre, a.r, B, b.mid, b.rd, 1);
-    hipLaunchKernelGGL(lin_fwd_small_kernel, dim3(nblk((long)B * b.mid)), dim3(256), 0, st, a.r, m + b.se2_w, m + b.se2_b,
-                       (float*)nullptr, a.g, B, b.rd, b.mid, 2);
-    hipLaunchKernelGGL(gate_mul_kernel, dim3(nblk(Mo * b.mid / 4)), dim3(256), 0, st, a.a2, a.g, k.dA, hw2, b.mid, Mo * b.mid / 4);
-    LAUNCH_CHECK();
+    VTRY(launch_se_fwd(a.a2, m + b.se1_w, m + b.se1_b, m + b.se2_w, m + b.se2_b, a.sepool, a.rpre, a.r, a.g, k.dA, B, hw2, b.mid,
+                       b.rd, st));
     VTRY(gemm_resid(k.dA, m + b.c3_w, nullptr, sc, a.y, Mo, b.c, b.mid));
     const float* yin = a.y;
     for (int g = 0; g < 2; ++g) {
@@ -889,8 +1016,7 @@ int maxvit_train_forward(btsbot_ctx* h, const float* img, int B, float* master, 
       VTRY(gemm_resid(t.o, m + p.proj_w, m + p.proj_b, yin, t.y1, Mo, c, c));
       VTRY(launch_mv_ln(BTSBOT_F32, t.y1, m + p.n2w, m + p.n2b, t.n2, Mo, c, st));
       VTRY(gemm(t.n2, m + p.fc1_w, m + p.fc1_b, t.f1, Mo, 4 * c, c));
-      hipLaunchKernelGGL(gelu_fwd_kernel, dim3(nblk(Mo * c)), dim3(256), 0, st, t.f1, t.gl, Mo * c);
-      LAUNCH_CHECK();
+      VTRY(launch_gelu_fwd(t.f1, t.gl, Mo * c, st));
       VTRY(gemm_resid(t.gl, m + p.fc2_w, m + p.fc2_b, t.y1, t.y2, Mo, c, 4 * c));
       yin = t.y2;
     }
@@ -954,9 +1080,7 @@ int maxvit_train_backward(btsbot_ctx* h, const float* img, const float* dfeat, f
   float* dy = k.dA;         // gradient w.r.t. the current map [rows][C]
   float* dt = k.dB;         // second map
   {
-    const long n = (long)B * 49 * 512;
-    hipLaunchKernelGGL(bcast_set_kernel, dim3(nblk(n)), dim3(256), 0, st, k.xn_final, dfeat, 49, 512, n, 1.0f / 49.0f);
-    LAUNCH_CHECK();
+    VTRY(launch_bcast_set(k.xn_final, dfeat, B, 49, 512, 1.0f / 49.0f, st));
     VTRY(launch_ln_bwd(k.xfin, k.xn_final, m + mv->norm_w, dy, grads + mv->norm_w, grads + mv->norm_b, (long)B * 49, 512, st));
   }
   for (int bi = (int)mv->blocks.size() - 1; bi >= 0; --bi) {
@@ -972,39 +1096,24 @@ int maxvit_train_backward(btsbot_ctx* h, const float* img, const float* dfeat, f
       // y2 = y1 + gl W2^T + b2
       VTRY(wgrad(dy, t.gl, grads + p.fc2_w, grads + p.fc2_b, Mo, c, 4 * c));
       VTRY(dgrad(dy, m + p.fc2_w, dt, Mo, c, 4 * c));                       // d(gl) [Mo][4c]
-      hipLaunchKernelGGL(gelu_bwd_kernel, dim3(nblk(Mo * c)), dim3(256), 0, st, t.f1, dt, Mo * c);
-      LAUNCH_CHECK();
+      VTRY(launch_gelu_bwd(t.f1, dt, Mo * c, st));
       VTRY(wgrad(dt, t.n2, grads + p.fc1_w, grads + p.fc1_b, Mo, 4 * c, c));
       VTRY(dgrad(dt, m + p.fc1_w, k.dC, Mo, 4 * c, c));                     // d(n2) [Mo][c]
       VTRY(launch_ln_bwd(t.y1, k.dC, m + p.n2w, dt, grads + p.n2w, grads + p.n2b, Mo, c, st));
-      hipLaunchKernelGGL(add_kernel, dim3(nblk(Mo * c / 4)), dim3(256), 0, st, dy, dt, Mo * c / 4);   // dy = d(y1)
-      LAUNCH_CHECK();
+      VTRY(launch_add(dy, dt, Mo * c / 4, st));   // dy = d(y1)
       // y1 = yin + o Wp^T + bp
       VTRY(wgrad(dy, t.o, grads + p.proj_w, grads + p.proj_b, Mo, c, c));
       VTRY(dgrad(dy, m + p.proj_w, dt, Mo, c, c));                          // d(o) [Mo][c]
-      const int heads = c / 32;
-      HIP_TRY(hipMemsetAsync(k.dbias, 0, (size_t)heads * 2401 * 4, st));
-      VTRY(launch_mv_pack_relbias(m + p.rel, k.dbias + 16 * 2401, heads, st));   // (bias_t in the slot's second half)
-      {
-        // three workgroups fit a CU (LDS): 768 x 4 of them walk the units, each for one head
-        const long units = (long)B * (b.hout / 7) * (b.hout / 7);
-        const long per_head = units < 3072 / heads ? units : 3072 / heads;
-        hipLaunchKernelGGL(mv_attn_bwd_kernel, dim3((unsigned)(per_head * heads)), dim3(64), 0, st, t.qkv, k.dbias + 16 * 2401,
-                           dt, k.dC, k.dbias, b.hout, c, g, (int)units);
-        hipLaunchKernelGGL(relbias_grad_kernel, dim3(nblk(169 * heads)), dim3(256), 0, st, k.dbias, grads + p.rel, heads);
-        LAUNCH_CHECK();
-      }
+      VTRY(launch_attn_bwd(t.qkv, m + p.rel, dt, k.dC, k.dbias, grads + p.rel, B, b.hout, c, g, st));   // d(qkv) [Mo][3c]
       VTRY(wgrad(k.dC, t.n1, grads + p.qkv_w, grads + p.qkv_b, Mo, 3 * c, c));
       VTRY(dgrad(k.dC, m + p.qkv_w, dt, Mo, 3 * c, c));                     // d(n1) [Mo][c]
       VTRY(launch_ln_bwd(yin, dt, m + p.n1w, k.dC, grads + p.n1w, grads + p.n1b, Mo, c, st));
-      hipLaunchKernelGGL(add_kernel, dim3(nblk(Mo * c / 4)), dim3(256), 0, st, dy, k.dC, Mo * c / 4);   // dy = d(yin)
-      LAUNCH_CHECK();
+      VTRY(launch_add(dy, k.dC, Mo * c / 4, st));   // dy = d(yin)
     }
     // ---- MBConv: y = sc + (a2 * g) W3^T;  dy = d(loss)/d(y) [Mo][c]
     float* dx = dt;           // gradient w.r.t. the block's input [Min][cin], accumulated from three paths
     // a3 = a2 * g (recomputed), d(a3) = dy W3
-    hipLaunchKernelGGL(gate_mul_kernel, dim3(nblk(Mo * b.mid / 4)), dim3(256), 0, st, a.a2, a.g, k.dC, hw2, b.mid, Mo * b.mid / 4);
-    LAUNCH_CHECK();
+    VTRY(launch_gate_mul(a.a2, a.g, k.dC, B, hw2, b.mid, st));
     VTRY(wgrad(dy, k.dC, grads + b.c3_w, nullptr, Mo, c, b.mid));
     VTRY(dgrad(dy, m + b.c3_w, k.dC, Mo, c, b.mid));                        // d(a3) [Mo][mid]
     // squeeze-excite: dg[b][c] = sum_p d(a3) a2; d(a2) = d(a3) g (+ the pooled path below)
@@ -1012,41 +1121,14 @@ int maxvit_train_backward(btsbot_ctx* h, const float* img, const float* dfeat, f
     float* dr = k.dsmall + (size_t)B * 2048;    // [B][rd] and scratch
     float* dpool = k.dsmall + (size_t)B * 2048 * 2;
     float* dgpre = k.dsmall + (size_t)B * 2048 * 3;
-    hipLaunchKernelGGL(alert_colsum_kernel, dim3((b.mid + 63) / 64, B), dim3(256), 0, st, (const float*)k.dC,
-                       (const float*)a.a2, dgate, hw2, b.mid, 1.0f);
-    hipLaunchKernelGGL(gate_mul_kernel, dim3(nblk(Mo * b.mid / 4)), dim3(256), 0, st, (const float*)k.dC, a.g, k.dC, hw2, b.mid,
-                       Mo * b.mid / 4);                                           // d(a2) = d(a3) * g, in place
-    hipLaunchKernelGGL(act_bwd_small_kernel, dim3(nblk((long)B * b.mid)), dim3(256), 0, st, (const float*)dgate,
-                       (const float*)a.g, dgpre, B * b.mid, 2);
-    hipLaunchKernelGGL(lin_bwd_w_small_kernel, dim3(nblk((long)b.mid * b.rd)), dim3(256), 0, st, (const float*)dgpre,
-                       (const float*)a.r, grads + b.se2_w, grads + b.se2_b, B, b.rd, b.mid);
-    hipLaunchKernelGGL(lin_bwd_in_small_kernel, dim3(nblk((long)B * b.rd)), dim3(256), 0, st, (const float*)dgpre,
-                       m + b.se2_w, dr, B, b.rd, b.mid);
-    hipLaunchKernelGGL(act_bwd_small_kernel, dim3(nblk((long)B * b.rd)), dim3(256), 0, st, (const float*)dr,
-                       (const float*)a.rpre, dr, B * b.rd, 1);
-    hipLaunchKernelGGL(lin_bwd_w_small_kernel, dim3(nblk((long)b.rd * b.mid)), dim3(256), 0, st, (const float*)dr,
-                       (const float*)a.sepool, grads + b.se1_w, grads + b.se1_b, B, b.mid, b.rd);
-    hipLaunchKernelGGL(lin_bwd_in_small_kernel, dim3(nblk((long)B * b.mid)), dim3(256), 0, st, (const float*)dr, m + b.se1_w,
-                       dpool, B, b.mid, b.rd);
-    hipLaunchKernelGGL(bcast_add_kernel, dim3(nblk(Mo * b.mid)), dim3(256), 0, st, k.dC, (const float*)dpool, hw2, b.mid,
-                       Mo * b.mid, 1.0f / (float)hw2);
-    LAUNCH_CHECK();
+    VTRY(launch_se_bwd(k.dC, a.a2, a.sepool, a.rpre, a.r, a.g, m + b.se1_w, m + b.se2_w, grads + b.se1_w, grads + b.se1_b,
+                       grads + b.se2_w, grads + b.se2_b, dgate, dr, dpool, dgpre, B, hw2, b.mid, b.rd, st));
     // BN2 + SiLU: d(d2) in place of d(a2)
     VTRY(bn_train_bwd(h, a.d2, k.dC, b.n2, a.st2, sums_arena, k.dC, grads, Mo, b.mid, 1, 0, st));
     // depthwise 3x3: filter / bias gradients (tap-major, then into the master layout), input gradient d(a1) [Min][mid]
-    HIP_TRY(hipMemsetAsync(k.g9, 0, (size_t)10 * b.mid * 4, st));
-    {
-      const long npix = Mo;
-      const dim3 grid((b.mid + 63) / 64, (unsigned)(npix / 64 > 256 ? 256 : (npix / 64 > 0 ? npix / 64 : 1)));
-      hipLaunchKernelGGL(dw3_bwd_w_kernel, grid, dim3(256), 0, st, (const float*)a.a1, (const float*)k.dC, k.g9,
-                         grads + b.c2_b, B, b.hin, b.mid, b.stride);
-      hipLaunchKernelGGL(unpack_dw_grad_kernel, dim3(nblk(9L * b.mid)), dim3(256), 0, st, (const float*)k.g9, grads + b.c2_w,
-                         b.mid);
-      VTRY(launch_mv_pack_dw(m + b.c2_w, F(mv->p_one), k.g9, b.mid, st));
-      hipLaunchKernelGGL(dw3_bwd_in_kernel, dim3(nblk(Min * b.mid / 4)), dim3(256), 0, st, (const float*)k.dC, (const float*)k.g9,
-                         dx, B, b.hin, b.mid, b.stride);
-      LAUNCH_CHECK();
-    }
+    VTRY(launch_dw3_bwd_w(a.a1, k.dC, k.g9, grads + b.c2_w, grads + b.c2_b, B, b.hin, b.mid, b.stride, st));
+    VTRY(launch_mv_pack_dw(m + b.c2_w, F(mv->p_one), k.g9, b.mid, st));
+    VTRY(launch_dw3_bwd_in(k.dC, k.g9, dx, B, b.hin, b.mid, b.stride, st));
     // BN1 + SiLU: d(c1) in place; conv1 1x1
     VTRY(bn_train_bwd(h, a.c1, dx, b.n1, a.st1, sums_arena, dx, grads, Min, b.mid, 1, 0, st));
     VTRY(wgrad(dx, a.a0, grads + b.c1_w, grads + b.c1_b, Min, b.mid, b.cin));
@@ -1055,17 +1137,14 @@ int maxvit_train_backward(btsbot_ctx* h, const float* img, const float* dfeat, f
     VTRY(bn_train_bwd(h, a.xin, k.dC, b.pre, a.st_pre, sums_arena, dx, grads, Min, b.cin, 0, 0, st));
     // ... plus the shortcut's: dy through identity | avgpool2 | avgpool2 . Wsc
     if (b.stride == 1) {
-      hipLaunchKernelGGL(add_kernel, dim3(nblk(Min * b.cin / 4)), dim3(256), 0, st, dx, (const float*)dy, Min * b.cin / 4);
+      VTRY(launch_add(dx, dy, Min * b.cin / 4, st));
     } else if (b.sc_w >= 0) {
       VTRY(wgrad(dy, a.pool_in, grads + b.sc_w, nullptr, Mo, c, b.cin));
       VTRY(dgrad(dy, m + b.sc_w, k.dC, Mo, c, b.cin));
-      hipLaunchKernelGGL(avgpool2_bwd_kernel, dim3(nblk(Min * b.cin)), dim3(256), 0, st, (const float*)k.dC, dx, B, b.hin,
-                         b.cin, 1);
+      VTRY(launch_avgpool2_bwd(k.dC, dx, B, b.hin, b.cin, 1, st));
     } else {
-      hipLaunchKernelGGL(avgpool2_bwd_kernel, dim3(nblk(Min * b.cin)), dim3(256), 0, st, (const float*)dy, dx, B, b.hin, b.cin,
-                         1);
+      VTRY(launch_avgpool2_bwd(dy, dx, B, b.hin, b.cin, 1, st));
     }
-    LAUNCH_CHECK();
     float* tswap = dy;       // dx becomes the next (earlier) block's dy
     dy = dx;
     dt = tswap;
@@ -1076,19 +1155,255 @@ int maxvit_train_backward(btsbot_ctx* h, const float* img, const float* dfeat, f
     VTRY(launch_mv_im2col3(BTSBOT_F32, k.a1s, k.dC, B, 112, 32, st));
     HIP_TRY(hipMemsetAsync(k.gconv, 0, (size_t)64 * 288 * 4, st));
     VTRY(wgrad(dy, k.dC, k.gconv, nullptr, M0, 64, 288));
-    hipLaunchKernelGGL(unpack_conv3_grad_kernel, dim3(nblk(64 * 32 * 9)), dim3(256), 0, st, (const float*)k.gconv,
-                       grads + mv->stem2_w, 64, 32, 288);
-    LAUNCH_CHECK();
+    VTRY(launch_unpack_conv3_grad(k.gconv, grads + mv->stem2_w, 64, 32, 288, st));
     VTRY(dgrad(dy, k.w2p, k.dC, M0, 64, 288));                              // d(col2) [M0][288]
-    hipLaunchKernelGGL(col2im3_kernel, dim3(nblk(M0 * 32)), dim3(256), 0, st, (const float*)k.dC, dt, B, 112, 32);
-    LAUNCH_CHECK();
+    VTRY(launch_col2im3(k.dC, dt, B, 112, 32, st));
     VTRY(bn_train_bwd(h, k.y1, dt, mv->stem_bn, k.st_stem, sums_arena, dt, grads, M0, 32, 1, 0, st));
     HIP_TRY(hipMemsetAsync(k.gconv, 0, (size_t)32 * 32 * 4, st));
     VTRY(wgrad(dt, k.col1, k.gconv, nullptr, M0, 32, 32));
-    hipLaunchKernelGGL(unpack_conv3_grad_kernel, dim3(nblk(32 * 3 * 9)), dim3(256), 0, st, (const float*)k.gconv,
-                       grads + mv->stem1_w, 32, 3, 32);
-    LAUNCH_CHECK();
+    VTRY(launch_unpack_conv3_grad(k.gconv, grads + mv->stem1_w, 32, 3, 32, st));
   }
   for (int i = 0; i < h->n_buckets; ++i) HIP_TRY(hipEventRecord(h->bucket_ev[i], st));
   return BTSBOT_OK;
+}
+
+// ---- op-level entry points (include/btsbot_hip.h, btsbot_op_mvt_*): the launchers above, one kernel group at a time,
+// on the caller's tensors and a stream-ordered scratch
+namespace {
+
+struct MvtScratch {   // (api.hip's OpScratch: offsets reserved first, one allocation, released behind the work on `st`)
+  hipStream_t st;
+  unsigned char* base = nullptr;
+  size_t total = 0;
+  explicit MvtScratch(hipStream_t s) : st(s) {}
+  ~MvtScratch() {
+    if (base != nullptr) (void)hipFreeAsync(base, st);
+  }
+  size_t reserve(size_t floats) {
+    const size_t o = total;
+    total += (floats * 4 + 255) / 256 * 256;
+    return o;
+  }
+  int alloc() {
+    if (hipMallocAsync(reinterpret_cast<void**>(&base), total ? total : 256, st) == hipSuccess) return BTSBOT_OK;
+    btsbot_set_error("op_mvt: hipMallocAsync of %zu scratch bytes failed", total);
+    return BTSBOT_ERR_HIP;
+  }
+  float* at(size_t off) const { return reinterpret_cast<float*>(base + off); }
+};
+
+int mvt_bad(const char* who, const char* what) {
+  btsbot_set_error("%s: %s", who, what);
+  return BTSBOT_ERR_INVALID_ARG;
+}
+// the depthwise ops' shape rule: C a multiple of 4, stride 1 or 2 dividing H
+int mvt_dw3_shape(const char* who, int B, int H, int C, int stride) {
+  if (B < 0 || H < 1 || C < 4 || C % 4 != 0 || (stride != 1 && stride != 2) || H % stride != 0) {
+    btsbot_set_error("%s: bad shape B=%d H=%d C=%d stride=%d (C a multiple of 4, stride 1 or 2 dividing H)", who, B, H, C, stride);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  return BTSBOT_OK;
+}
+// taps [9][C] of w [C][1][3][3] as the engine packs them (scale = 1)
+int mvt_pack_taps(const float* w, float* ones, float* w9, int C, hipStream_t st) {
+  VTRY(launch_mv_fill(ones, 1.0f, C, st));
+  return launch_mv_pack_dw(w, ones, w9, C, st);
+}
+
+}  // namespace
+
+extern "C" int btsbot_op_mvt_bn_row_blocks(int64_t M) {
+  if (M < 1) return mvt_bad("op_mvt_bn_row_blocks", "M < 1");
+  return (int)bn_row_blocks((long)M);
+}
+extern "C" int btsbot_op_mvt_dw3_bwd_w_row_blocks(int64_t npix) {
+  if (npix < 1) return mvt_bad("op_mvt_dw3_bwd_w_row_blocks", "npix < 1");
+  return (int)dw3_bwd_w_row_blocks((long)npix);
+}
+extern "C" int btsbot_op_mvt_attn_bwd_groups_per_head(int64_t units, int heads) {
+  if (units < 1 || units > 0x7fffffffL || heads < 1 || heads > 16) return mvt_bad("op_mvt_attn_bwd_groups_per_head", "units < 1 or heads outside 1..16");
+  return (int)attn_bwd_groups_per_head((long)units, heads);
+}
+
+extern "C" int btsbot_op_mvt_bn_fwd(const float* x, const float* w, const float* b, float* run_mean, float* run_var, float* y,
+                                    float* stat, int64_t M, int C, int act, void* stream) {
+  if (x == nullptr || w == nullptr || b == nullptr || y == nullptr || stat == nullptr || (run_mean == nullptr) != (run_var == nullptr))
+    return mvt_bad("op_mvt_bn_fwd", "null pointer (run_mean and run_var: both or neither)");
+  if (M < 1 || C < 4 || C % 4 != 0 || (act != 0 && act != 1)) {
+    btsbot_set_error("op_mvt_bn_fwd: bad shape M=%lld C=%d act=%d (C a multiple of 4, act 0 or 1)", (long long)M, C, act);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  MvtScratch sc(st);
+  const size_t o0 = sc.reserve(2 * (size_t)C), o1 = sc.reserve(2 * (size_t)C);
+  VTRY(sc.alloc());
+  HIP_TRY(hipMemsetAsync(sc.base, 0, sc.total, st));
+  return launch_bn_train(x, w, b, stat, sc.at(o0), sc.at(o1), run_mean, run_var, y, (long)M, C, act, st);
+}
+
+extern "C" int btsbot_op_mvt_bn_bwd(const float* x, const float* dy, const float* stat, const float* w, const float* b, float* dx,
+                                    float* dw, float* db, int64_t M, int C, int act, int accumulate, void* stream) {
+  if (x == nullptr || dy == nullptr || stat == nullptr || w == nullptr || b == nullptr || dx == nullptr || dw == nullptr ||
+      db == nullptr)
+    return mvt_bad("op_mvt_bn_bwd", "null pointer");
+  if (M < 1 || C < 4 || C % 4 != 0 || (act != 0 && act != 1) || (accumulate != 0 && accumulate != 1)) {
+    btsbot_set_error("op_mvt_bn_bwd: bad shape M=%lld C=%d act=%d accumulate=%d (C a multiple of 4, flags 0 or 1)", (long long)M, C,
+                     act, accumulate);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  MvtScratch sc(st);
+  const size_t o = sc.reserve(2 * (size_t)C);
+  VTRY(sc.alloc());
+  HIP_TRY(hipMemsetAsync(sc.base, 0, sc.total, st));
+  return launch_bn_train_bwd(x, dy, stat, w, b, sc.at(o), dx, dw, db, (long)M, C, act, accumulate, st);
+}
+
+extern "C" int btsbot_op_mvt_dw3_fwd(const float* in, const float* w, const float* bias, float* out, int B, int H, int C,
+                                     int stride, void* stream) {
+  if (in == nullptr || w == nullptr || bias == nullptr || out == nullptr) return mvt_bad("op_mvt_dw3_fwd", "null pointer");
+  VTRY(mvt_dw3_shape("op_mvt_dw3_fwd", B, H, C, stride));
+  if (B == 0) return BTSBOT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  MvtScratch sc(st);
+  const size_t o1 = sc.reserve(C), o9 = sc.reserve(9 * (size_t)C);
+  VTRY(sc.alloc());
+  VTRY(mvt_pack_taps(w, sc.at(o1), sc.at(o9), C, st));
+  return launch_dw3_fwd(in, sc.at(o9), bias, out, B, H, C, stride, st);
+}
+
+extern "C" int btsbot_op_mvt_dw3_bwd_in(const float* dout, const float* w, float* din, int B, int H, int C, int stride,
+                                        void* stream) {
+  if (dout == nullptr || w == nullptr || din == nullptr) return mvt_bad("op_mvt_dw3_bwd_in", "null pointer");
+  VTRY(mvt_dw3_shape("op_mvt_dw3_bwd_in", B, H, C, stride));
+  if (B == 0) return BTSBOT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  MvtScratch sc(st);
+  const size_t o1 = sc.reserve(C), o9 = sc.reserve(9 * (size_t)C);
+  VTRY(sc.alloc());
+  VTRY(mvt_pack_taps(w, sc.at(o1), sc.at(o9), C, st));
+  return launch_dw3_bwd_in(dout, sc.at(o9), din, B, H, C, stride, st);
+}
+
+extern "C" int btsbot_op_mvt_dw3_bwd_w(const float* in, const float* dout, float* dw, float* dbias, int B, int H, int C,
+                                       int stride, void* stream) {
+  if (in == nullptr || dout == nullptr || dw == nullptr || dbias == nullptr) return mvt_bad("op_mvt_dw3_bwd_w", "null pointer");
+  VTRY(mvt_dw3_shape("op_mvt_dw3_bwd_w", B, H, C, stride));
+  if (B == 0) return BTSBOT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  MvtScratch sc(st);
+  const size_t o = sc.reserve(10 * (size_t)C);
+  VTRY(sc.alloc());
+  return launch_dw3_bwd_w(in, dout, sc.at(o), dw, dbias, B, H, C, stride, st);
+}
+
+extern "C" int btsbot_op_mvt_attn_bwd(const float* qkv, const float* table, const float* dout, float* dqkv, float* dtable, int B,
+                                      int H, int C, int grid_mode, void* stream) {
+  if (qkv == nullptr || table == nullptr || dout == nullptr || dqkv == nullptr || dtable == nullptr)
+    return mvt_bad("op_mvt_attn_bwd", "null pointer");
+  if (B < 0 || H < 7 || H % 7 != 0 || C < 32 || C % 32 != 0 || C / 32 > 16 || (grid_mode != 0 && grid_mode != 1)) {
+    btsbot_set_error("op_mvt_attn_bwd: bad shape B=%d H=%d C=%d grid_mode=%d (H a multiple of 7, C of 32, at most 16 heads)", B, H,
+                     C, grid_mode);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if ((long)B * (H / 7) * (H / 7) > 0x7fffffffL) return mvt_bad("op_mvt_attn_bwd", "too many (alert, partition) units");
+  if (B == 0) return BTSBOT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  MvtScratch sc(st);
+  const size_t o = sc.reserve((size_t)32 * 2401);
+  VTRY(sc.alloc());
+  return launch_attn_bwd(qkv, table, dout, dqkv, sc.at(o), dtable, B, H, C, grid_mode, st);
+}
+
+// (the small dense kernels index [B][C] and [RD][C] with an int)
+static int mvt_se_shape(const char* who, int B, int P, int C, int RD) {
+  if (B < 0 || P < 1 || C < 4 || C % 4 != 0 || RD < 1 || (long)B * C > 0x7fffffffL || (long)RD * C > 0x7fffffffL) {
+    btsbot_set_error("%s: bad shape B=%d P=%d C=%d RD=%d (C a multiple of 4)", who, B, P, C, RD);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  return BTSBOT_OK;
+}
+
+extern "C" int btsbot_op_mvt_se_fwd(const float* a2, const float* fc1_w, const float* fc1_b, const float* fc2_w,
+                                    const float* fc2_b, float* pool, float* rpre, float* r, float* gate, float* gated, int B,
+                                    int P, int C, int RD, void* stream) {
+  if (a2 == nullptr || fc1_w == nullptr || fc1_b == nullptr || fc2_w == nullptr || fc2_b == nullptr || pool == nullptr ||
+      rpre == nullptr || r == nullptr || gate == nullptr || gated == nullptr)
+    return mvt_bad("op_mvt_se_fwd", "null pointer");
+  VTRY(mvt_se_shape("op_mvt_se_fwd", B, P, C, RD));
+  if (B == 0) return BTSBOT_OK;
+  return launch_se_fwd(a2, fc1_w, fc1_b, fc2_w, fc2_b, pool, rpre, r, gate, gated, B, P, C, RD, (hipStream_t)stream);
+}
+
+extern "C" int btsbot_op_mvt_se_bwd(const float* d_gated, const float* a2, const float* pool, const float* rpre, const float* r,
+                                    const float* gate, const float* fc1_w, const float* fc2_w, float* d_a2, float* d_fc1_w,
+                                    float* d_fc1_b, float* d_fc2_w, float* d_fc2_b, int B, int P, int C, int RD, void* stream) {
+  if (d_gated == nullptr || a2 == nullptr || pool == nullptr || rpre == nullptr || r == nullptr || gate == nullptr ||
+      fc1_w == nullptr || fc2_w == nullptr || d_a2 == nullptr || d_fc1_w == nullptr || d_fc1_b == nullptr || d_fc2_w == nullptr ||
+      d_fc2_b == nullptr)
+    return mvt_bad("op_mvt_se_bwd", "null pointer");
+  VTRY(mvt_se_shape("op_mvt_se_bwd", B, P, C, RD));
+  if (B == 0) return BTSBOT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  MvtScratch sc(st);
+  const size_t bc = (size_t)B * C;
+  const size_t o_dgate = sc.reserve(bc), o_dr = sc.reserve((size_t)B * RD), o_dpool = sc.reserve(bc), o_dgpre = sc.reserve(bc);
+  VTRY(sc.alloc());
+  // (the engine's chain runs in place on d(gated))
+  if (d_a2 != d_gated) HIP_TRY(hipMemcpyAsync(d_a2, d_gated, (size_t)B * P * C * 4, hipMemcpyDeviceToDevice, st));
+  return launch_se_bwd(d_a2, a2, pool, rpre, r, gate, fc1_w, fc2_w, d_fc1_w, d_fc1_b, d_fc2_w, d_fc2_b, sc.at(o_dgate), sc.at(o_dr),
+                       sc.at(o_dpool), sc.at(o_dgpre), B, P, C, RD, st);
+}
+
+extern "C" int btsbot_op_mvt_avgpool2_bwd(const float* g, float* dx, int B, int H, int C, int accumulate, void* stream) {
+  if (g == nullptr || dx == nullptr) return mvt_bad("op_mvt_avgpool2_bwd", "null pointer");
+  if (B < 0 || H < 2 || H % 2 != 0 || C < 1 || (accumulate != 0 && accumulate != 1)) {
+    btsbot_set_error("op_mvt_avgpool2_bwd: bad shape B=%d H=%d C=%d accumulate=%d (H even)", B, H, C, accumulate);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (B == 0) return BTSBOT_OK;
+  return launch_avgpool2_bwd(g, dx, B, H, C, accumulate, (hipStream_t)stream);
+}
+
+extern "C" int btsbot_op_mvt_col2im3(const float* dcol, float* din, int B, int H, int C, void* stream) {
+  if (dcol == nullptr || din == nullptr) return mvt_bad("op_mvt_col2im3", "null pointer");
+  if (B < 0 || H < 1 || C < 1) {
+    btsbot_set_error("op_mvt_col2im3: bad shape B=%d H=%d C=%d", B, H, C);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (B == 0) return BTSBOT_OK;
+  return launch_col2im3(dcol, din, B, H, C, (hipStream_t)stream);
+}
+
+extern "C" int btsbot_op_mvt_unpack_conv3_grad(const float* gp, float* g, int O, int C, int ldp, void* stream) {
+  if (gp == nullptr || g == nullptr) return mvt_bad("op_mvt_unpack_conv3_grad", "null pointer");
+  if (O < 1 || C < 1 || ldp < 9 * C || (long)O * C * 9 > 0x7fffffffL) {
+    btsbot_set_error("op_mvt_unpack_conv3_grad: bad shape O=%d C=%d ldp=%d (ldp >= 9 C)", O, C, ldp);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  return launch_unpack_conv3_grad(gp, g, O, C, ldp, (hipStream_t)stream);
+}
+
+extern "C" int btsbot_op_mvt_gelu_fwd(const float* pre, float* out, int64_t n, void* stream) {
+  if (pre == nullptr || out == nullptr) return mvt_bad("op_mvt_gelu_fwd", "null pointer");
+  if (n < 0 || n % 4 != 0) return mvt_bad("op_mvt_gelu_fwd", "n is not a multiple of 4");
+  if (n == 0) return BTSBOT_OK;
+  return launch_gelu_fwd(pre, out, (long)(n / 4), (hipStream_t)stream);
+}
+
+extern "C" int btsbot_op_mvt_gelu_bwd(const float* pre, float* d, int64_t n, void* stream) {
+  if (pre == nullptr || d == nullptr) return mvt_bad("op_mvt_gelu_bwd", "null pointer");
+  if (n < 0 || n % 4 != 0) return mvt_bad("op_mvt_gelu_bwd", "n is not a multiple of 4");
+  if (n == 0) return BTSBOT_OK;
+  return launch_gelu_bwd(pre, d, (long)(n / 4), (hipStream_t)stream);
+}
+
+extern "C" int btsbot_op_mvt_bcast_set(const float* v, float* d, int B, int P, int C, float scale, void* stream) {
+  if (v == nullptr || d == nullptr) return mvt_bad("op_mvt_bcast_set", "null pointer");
+  if (B < 0 || P < 1 || C < 1) {
+    btsbot_set_error("op_mvt_bcast_set: bad shape B=%d P=%d C=%d", B, P, C);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (B == 0) return BTSBOT_OK;
+  return launch_bcast_set(d, v, B, P, C, scale, (hipStream_t)stream);
 }

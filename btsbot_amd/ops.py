@@ -303,3 +303,175 @@ def mv_stem(img, conv1_w, bn_scale, bn_shift, conv2_w, precision="bf16", pooled=
                                                 _p(conv2_w), _p(out), int(pooled), _p(xn), _p(ps), _p(pb), B,
                                                 _stream(img)), "btsbot_op_mv_stem")
     return out if pre is None else (out, xn)
+
+
+# ---- the MaxViT TRAINING kernels one at a time (btsbot_op_mvt_*, maxvit_train.hip): everything fp32; outputs given by
+# the caller are used as they are ("+=" ones are added to), the others are allocated here
+def _f32t(t, shape=None, numel=None):
+    assert t.dtype == torch.float32 and t.is_contiguous(), "fp32 contiguous tensors"
+    assert shape is None or tuple(t.shape) == tuple(shape), (tuple(t.shape), tuple(shape))
+    assert numel is None or t.numel() == numel, (t.numel(), numel)
+    return t
+
+
+def _new(out, shape, like):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    n = 1
+    for s in shape:
+        n *= s
+    return _f32t(out, numel=n)
+
+
+def _mvt(name, t, *args):
+    with torch.cuda.device(t.device):
+        _lib.check(getattr(_lib.lib(), "btsbot_op_mvt_" + name)(*args, _stream(t)), "btsbot_op_mvt_" + name)
+
+
+def mvt_bn_row_blocks(M):
+    """gridDim.y of the BatchNorm reductions over M rows."""
+    return _lib.check(_lib.lib().btsbot_op_mvt_bn_row_blocks(M), "btsbot_op_mvt_bn_row_blocks")
+
+
+def mvt_dw3_bwd_w_row_blocks(npix):
+    """gridDim.y of the depthwise filter gradient over npix output pixels."""
+    return _lib.check(_lib.lib().btsbot_op_mvt_dw3_bwd_w_row_blocks(npix), "btsbot_op_mvt_dw3_bwd_w_row_blocks")
+
+
+def mvt_attn_bwd_groups_per_head(units, heads):
+    """Workgroups per head of the attention backward for `units` (alert, partition) pairs."""
+    return _lib.check(_lib.lib().btsbot_op_mvt_attn_bwd_groups_per_head(units, heads),
+                      "btsbot_op_mvt_attn_bwd_groups_per_head")
+
+
+def mvt_bn_fwd(x, w, b, run_mean, run_var, act, y=None, stat=None):
+    """BatchNorm2d on batch statistics of x [M,C]: -> (y = act(xhat w + b), stat [2C] = mean | rstd); run_mean /
+    run_var [C] are updated in place (both None: left out).  act 0 none, 1 SiLU."""
+    M, Cc = x.shape
+    _f32t(x), _f32t(w, (Cc,)), _f32t(b, (Cc,))
+    for r in (run_mean, run_var):
+        assert r is None or _f32t(r, (Cc,)) is r
+    y, stat = _new(y, (M, Cc), x), _new(stat, (2 * Cc,), x)
+    _mvt("bn_fwd", x, _p(x), _p(w), _p(b), _p(run_mean), _p(run_var), _p(y), _p(stat), M, Cc, act)
+    return y, stat
+
+
+def mvt_bn_bwd(x, dy, stat, w, b, act, accumulate, dx, dw, db):
+    """Backward of mvt_bn_fwd: dx [M,C] written (accumulate 0) or added to (1) -- it may be dy itself; dw, db [C] += ."""
+    M, Cc = x.shape
+    _f32t(x), _f32t(dy, numel=M * Cc), _f32t(stat, (2 * Cc,)), _f32t(w, (Cc,)), _f32t(b, (Cc,))
+    _f32t(dx, numel=M * Cc), _f32t(dw, (Cc,)), _f32t(db, (Cc,))
+    _mvt("bn_bwd", x, _p(x), _p(dy), _p(stat), _p(w), _p(b), _p(dx), _p(dw), _p(db), M, Cc, act, int(accumulate))
+    return dx
+
+
+def mvt_dw3_fwd(x, w, bias, stride, out=None):
+    """x [B,H,H,C] -> dw3x3_s(x, w [C,1,3,3]) + bias [B,H/s,H/s,C]."""
+    B, H, _, Cc = x.shape
+    _f32t(x), _f32t(w, (Cc, 1, 3, 3)), _f32t(bias, (Cc,))
+    Ho = H // max(stride, 1)
+    out = _new(out, (B, Ho, Ho, Cc), x)
+    _mvt("dw3_fwd", x, _p(x), _p(w), _p(bias), _p(out), B, H, Cc, stride)
+    return out
+
+
+def mvt_dw3_bwd_in(dout, w, H, stride, din=None):
+    """dout [B,H/s,H/s,C] -> the gradient of mvt_dw3_fwd's input [B,H,H,C]."""
+    B, Cc = dout.shape[0], dout.shape[3]
+    _f32t(dout), _f32t(w, (Cc, 1, 3, 3))
+    din = _new(din, (B, H, H, Cc), dout)
+    _mvt("dw3_bwd_in", dout, _p(dout), _p(w), _p(din), B, H, Cc, stride)
+    return din
+
+
+def mvt_dw3_bwd_w(x, dout, stride, dw, dbias):
+    """dw [C,1,3,3] += the filter gradient, dbias [C] += the bias gradient of mvt_dw3_fwd."""
+    B, H, _, Cc = x.shape
+    _f32t(x), _f32t(dout), _f32t(dw, numel=9 * Cc), _f32t(dbias, (Cc,))
+    _mvt("dw3_bwd_w", x, _p(x), _p(dout), _p(dw), _p(dbias), B, H, Cc, stride)
+    return dw, dbias
+
+
+def mvt_attn_bwd(qkv, table, dout, B, H, grid_mode, dtable, dqkv=None):
+    """Backward of mv_attn in fp32: qkv [B*H*H, 3C], table [169, C/32], dout [B*H*H, C] -> dqkv (written); dtable += ."""
+    N = B * H * H
+    Cc = qkv.shape[1] // 3
+    _f32t(qkv, (N, 3 * Cc)), _f32t(table, (169, Cc // 32)), _f32t(dout, (N, Cc)), _f32t(dtable, numel=169 * (Cc // 32))
+    dqkv = _new(dqkv, (N, 3 * Cc), qkv)
+    _mvt("attn_bwd", qkv, _p(qkv), _p(table), _p(dout), _p(dqkv), _p(dtable), B, H, Cc, grid_mode)
+    return dqkv
+
+
+def mvt_se_fwd(a2, fc1_w, fc1_b, fc2_w, fc2_b, out=None):
+    """a2 [B,P,C], fc1_w [RD,C], fc2_w [C,RD] -> (pool [B,C], rpre [B,RD], r [B,RD], gate [B,C], gated [B,P,C]);
+    out: the five tensors, given."""
+    B, P, Cc = a2.shape
+    RD = fc1_w.shape[0]
+    _f32t(a2), _f32t(fc1_w, (RD, Cc)), _f32t(fc1_b, (RD,)), _f32t(fc2_w, (Cc, RD)), _f32t(fc2_b, (Cc,))
+    shapes = ((B, Cc), (B, RD), (B, RD), (B, Cc), (B, P, Cc))
+    out = [_new(o, s, a2) for o, s in zip(out or (None,) * 5, shapes)]
+    _mvt("se_fwd", a2, _p(a2), _p(fc1_w), _p(fc1_b), _p(fc2_w), _p(fc2_b), *(_p(o) for o in out), B, P, Cc, RD)
+    return tuple(out)
+
+
+def mvt_se_bwd(d_gated, a2, pool, rpre, r, gate, fc1_w, fc2_w, d_fc1_w, d_fc1_b, d_fc2_w, d_fc2_b, d_a2=None):
+    """Backward of mvt_se_fwd from d_gated [B,P,C]: -> d_a2 (written); the four parameter gradients += ."""
+    B, P, Cc = a2.shape
+    RD = fc1_w.shape[0]
+    _f32t(d_gated, numel=B * P * Cc), _f32t(a2), _f32t(pool, (B, Cc)), _f32t(rpre, (B, RD)), _f32t(r, (B, RD))
+    _f32t(gate, (B, Cc)), _f32t(fc1_w, (RD, Cc)), _f32t(fc2_w, (Cc, RD))
+    _f32t(d_fc1_w, numel=RD * Cc), _f32t(d_fc1_b, (RD,)), _f32t(d_fc2_w, numel=RD * Cc), _f32t(d_fc2_b, (Cc,))
+    d_a2 = _new(d_a2, (B, P, Cc), a2)
+    _mvt("se_bwd", a2, _p(d_gated), _p(a2), _p(pool), _p(rpre), _p(r), _p(gate), _p(fc1_w), _p(fc2_w), _p(d_a2),
+         _p(d_fc1_w), _p(d_fc1_b), _p(d_fc2_w), _p(d_fc2_b), B, P, Cc, RD)
+    return d_a2
+
+
+def mvt_avgpool2_bwd(g, dx, accumulate):
+    """dx [B,H,H,C] (+)= 0.25 g [B,H/2,H/2,C]."""
+    B, H, _, Cc = dx.shape
+    _f32t(g, (B, H // 2, H // 2, Cc)), _f32t(dx)
+    _mvt("avgpool2_bwd", g, _p(g), _p(dx), B, H, Cc, int(accumulate))
+    return dx
+
+
+def mvt_col2im3(dcol, din=None):
+    """dcol [B,H,H,9C] (tap-major) -> din [B,H,H,C]: the input gradient of a 3x3 s1 p1 im2col."""
+    B, H, _, C9 = dcol.shape
+    _f32t(dcol)
+    assert C9 % 9 == 0
+    din = _new(din, (B, H, H, C9 // 9), dcol)
+    _mvt("col2im3", dcol, _p(dcol), _p(din), B, H, C9 // 9)
+    return din
+
+
+def mvt_unpack_conv3_grad(gp, g):
+    """g [O,C,3,3] += gp [O,ldp], packed (ky*3+kx)*C + c."""
+    O, Cc = g.shape[0], g.shape[1]
+    _f32t(gp), _f32t(g, (O, Cc, 3, 3))
+    assert gp.shape[0] == O
+    _mvt("unpack_conv3_grad", gp, _p(gp), _p(g), O, Cc, gp.shape[1])
+    return g
+
+
+def mvt_gelu_fwd(pre, out=None):
+    _f32t(pre)
+    out = _new(out, tuple(pre.shape), pre)
+    _mvt("gelu_fwd", pre, _p(pre), _p(out), pre.numel())
+    return out
+
+
+def mvt_gelu_bwd(pre, d):
+    """d *= gelu'(pre), in place."""
+    _f32t(pre), _f32t(d, numel=pre.numel())
+    _mvt("gelu_bwd", pre, _p(pre), _p(d), pre.numel())
+    return d
+
+
+def mvt_bcast_set(v, P, scale, out=None):
+    """v [B,C] -> [B,P,C] = v * scale."""
+    B, Cc = v.shape
+    _f32t(v)
+    out = _new(out, (B, P, Cc), v)
+    _mvt("bcast_set", v, _p(v), _p(out), B, P, Cc, float(scale))
+    return out

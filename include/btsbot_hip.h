@@ -428,6 +428,57 @@ int btsbot_op_mv_stem(int prec, const float* img, const float* conv1_w, const fl
                       const float* conv2_w, float* out, int pooled, void* xn, const float* pre_scale,
                       const float* pre_shift, int B, void* stream);
 
+/* The MaxViT TRAINING kernels (maxvit_train.hip) one at a time.  Everything is fp32; parameters are in the state-dict
+ * layout; activations are NHWC rows.  Every call runs the launcher the training engine itself runs (same kernels, same
+ * grid arithmetic) on a stream-ordered scratch of its own.  "+=" outputs are added to, the others written.  What a
+ * kernel cannot run (a null pointer, C not a multiple of 4, H not a multiple of 7 for attention or of the stride,
+ * more than 16 heads, a stride other than 1 or 2) comes back as BTSBOT_ERR_INVALID_ARG with a message.
+ *
+ * The launchers' grid decisions: row blocks (gridDim.y) of the BatchNorm reductions over M rows, row blocks of the
+ * depthwise filter gradient over npix output pixels, workgroups per head of the attention backward for `units`
+ * (alert, partition) pairs. */
+int btsbot_op_mvt_bn_row_blocks(int64_t M);
+int btsbot_op_mvt_dw3_bwd_w_row_blocks(int64_t npix);
+int btsbot_op_mvt_attn_bwd_groups_per_head(int64_t units, int heads);
+/* BatchNorm2d on batch statistics (eps 1e-5): y [M][C] = act(xhat * w + b), act 0 none / 1 SiLU; stat [2C] = mean |
+ * rstd; run_mean / run_var (both or neither) updated in place with momentum 0.1 and the unbiased variance. */
+int btsbot_op_mvt_bn_fwd(const float* x, const float* w, const float* b, float* run_mean, float* run_var, float* y,
+                         float* stat, int64_t M, int C, int act, void* stream);
+/* ... and its backward: dy is the gradient behind the activation; dx = (accumulate ? dx : 0) + gradient (dx may be
+ * dy); dw [C] += , db [C] += . */
+int btsbot_op_mvt_bn_bwd(const float* x, const float* dy, const float* stat, const float* w, const float* b, float* dx,
+                         float* dw, float* db, int64_t M, int C, int act, int accumulate, void* stream);
+/* Depthwise 3x3 p1, stride 1 / 2, w [C][1][3][3]: out [B,H/s,H/s,C] = conv(in [B,H,H,C]) + bias; the input gradient
+ * din [B,H,H,C] of dout [B,H/s,H/s,C]; the filter gradient dw [C][1][3][3] += and dbias [C] += . */
+int btsbot_op_mvt_dw3_fwd(const float* in, const float* w, const float* bias, float* out, int B, int H, int C,
+                          int stride, void* stream);
+int btsbot_op_mvt_dw3_bwd_in(const float* dout, const float* w, float* din, int B, int H, int C, int stride,
+                             void* stream);
+int btsbot_op_mvt_dw3_bwd_w(const float* in, const float* dout, float* dw, float* dbias, int B, int H, int C,
+                            int stride, void* stream);
+/* Backward of btsbot_op_mv_attn (fp32): qkv [B*H*H, 3C], table [169][C/32], dout [B*H*H, C] -> dqkv [B*H*H, 3C]
+ * written, dtable [169][C/32] += . */
+int btsbot_op_mvt_attn_bwd(const float* qkv, const float* table, const float* dout, float* dqkv, float* dtable, int B,
+                           int H, int C, int grid_mode, void* stream);
+/* Squeeze-excite of a2 [B][P][C], fc1_w [RD][C], fc2_w [C][RD]: pool [B][C] = mean over P, rpre [B][RD] = fc1(pool),
+ * r = silu(rpre), gate [B][C] = sigmoid(fc2(r)), gated [B][P][C] = a2 * gate.  Backward: d_a2 [B][P][C] written from
+ * d_gated; d_fc1_w, d_fc1_b, d_fc2_w, d_fc2_b += . */
+int btsbot_op_mvt_se_fwd(const float* a2, const float* fc1_w, const float* fc1_b, const float* fc2_w,
+                         const float* fc2_b, float* pool, float* rpre, float* r, float* gate, float* gated, int B, int P,
+                         int C, int RD, void* stream);
+int btsbot_op_mvt_se_bwd(const float* d_gated, const float* a2, const float* pool, const float* rpre, const float* r,
+                         const float* gate, const float* fc1_w, const float* fc2_w, float* d_a2, float* d_fc1_w,
+                         float* d_fc1_b, float* d_fc2_w, float* d_fc2_b, int B, int P, int C, int RD, void* stream);
+/* dx [B,H,H,C] (+)= 0.25 g [B,H/2,H/2,C];  din [B,H,H,C] = col2im of dcol [B,H,H,9C] (3x3 s1 p1, tap-major);
+ * g [O][C][3][3] += gp [O][ldp] (packed (ky*3+kx)*C + c);  out = gelu(pre), d *= gelu'(pre) (erf form, n a multiple
+ * of 4);  d [B][P][C] = v [B][C] * scale. */
+int btsbot_op_mvt_avgpool2_bwd(const float* g, float* dx, int B, int H, int C, int accumulate, void* stream);
+int btsbot_op_mvt_col2im3(const float* dcol, float* din, int B, int H, int C, void* stream);
+int btsbot_op_mvt_unpack_conv3_grad(const float* gp, float* g, int O, int C, int ldp, void* stream);
+int btsbot_op_mvt_gelu_fwd(const float* pre, float* out, int64_t n, void* stream);
+int btsbot_op_mvt_gelu_bwd(const float* pre, float* d, int64_t n, void* stream);
+int btsbot_op_mvt_bcast_set(const float* v, float* d, int B, int P, int C, float scale, void* stream);
+
 /* Measurement aid with no reference counterpart (bench.py's roofline leg): when on, every kernel
  * launch of forward() is bracketed by two HIP events recorded on the launch stream;
  * profile_collect() waits for them and returns, per kernel family (profile_category_name), the

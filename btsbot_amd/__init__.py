@@ -37,11 +37,12 @@ from .synthetic import METADATA_COLS, synthetic_batch
 from .pipeline import ScoreStream
 from .alert_utils import CUSTOM_COLS, alert_features, make_metadata
 from .val import REFERENCE_POLICIES, policy_eval, policy_performance
+from .triggers import TriggerState
 
 __all__ = [
     "__version__", "architectures", "from_HF", "to_HF", "data", "val", "alert_utils",
     "MaxViT", "ConvNeXt", "mm_MaxViT", "mm_ConvNeXt", "mm_cnn", "um_cnn", "um_nn", "frozen_fusion",
     "download_HF_model", "load_HF_model", "METADATA_COLS", "synthetic_batch", "ScoreStream",
     "CUSTOM_COLS", "alert_features", "make_metadata",
-    "REFERENCE_POLICIES", "policy_eval", "policy_performance",
+    "REFERENCE_POLICIES", "policy_eval", "policy_performance", "triggers", "TriggerState",
 ]

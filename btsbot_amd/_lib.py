@@ -41,7 +41,7 @@ SYMBOLS = [
     "btsbot_reserve_train", "btsbot_forward_train", "btsbot_backward", "btsbot_debug_stamps",
     "btsbot_grad_buckets", "btsbot_wait_grad_bucket", "btsbot_allreduce_grads", "btsbot_use_workspace", "btsbot_set_option",
     "btsbot_augment", "btsbot_eval_metrics", "btsbot_prep_triplets", "btsbot_alert_features",
-    "btsbot_policy_eval",
+    "btsbot_policy_eval", "btsbot_trigger_reset", "btsbot_trigger_update", "btsbot_trigger_load",
     "btsbot_embed_width", "btsbot_forward_embed",
 ]
 EMBEDDING = {"features": 0, "hidden": 1}   # enum btsbot_embedding
@@ -62,6 +62,17 @@ class ParamInfo(C.Structure):
     _fields_ = [
         ("name", C.c_char * 96), ("offset", C.c_int64), ("numel", C.c_int64),
         ("ndim", C.c_int32), ("shape", C.c_int32 * 4), ("is_buffer", C.c_int32),
+    ]
+
+
+TRIGGER_COUNTER_ROWS = 16   # BTSBOT_TRIGGER_COUNTER_ROWS
+
+
+class TriggerTable(C.Structure):   # struct btsbot_trigger_table
+    _fields_ = [
+        ("key", C.c_void_p), ("n_alerts", C.c_void_p), ("min_magpsf", C.c_void_p), ("last_jd", C.c_void_p),
+        ("count", C.c_void_p), ("trigger", C.c_void_p), ("counters", C.c_void_p),
+        ("capacity", C.c_int32), ("n_policies", C.c_int32),
     ]
 
 
@@ -196,6 +207,13 @@ def lib() -> C.CDLL:
     L.btsbot_alert_features.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.btsbot_policy_eval.restype = i32
     L.btsbot_policy_eval.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_double), i32, vp, vp, vp, vp]
+    L.btsbot_trigger_reset.restype = i32
+    L.btsbot_trigger_reset.argtypes = [C.POINTER(TriggerTable), vp]
+    L.btsbot_trigger_update.restype = i32
+    L.btsbot_trigger_update.argtypes = [C.POINTER(TriggerTable), C.POINTER(C.c_double), vp, vp, i32, i32, vp, vp, vp, vp, vp,
+                                        vp, vp]
+    L.btsbot_trigger_load.restype = i32
+    L.btsbot_trigger_load.argtypes = [C.POINTER(TriggerTable), i32, vp, vp, vp, vp, vp, vp, vp]
     L.btsbot_eval_metrics.restype = i32
     L.btsbot_eval_metrics.argtypes = [vp, vp, f32, i64, vp, vp]
     if L.btsbot_abi_version() != ABI_VERSION:

@@ -150,13 +150,20 @@ FEATURE_TILE = 1024
 _FEATURE_INPUTS = ("jd", "magpsf", "jdstarthist", "ncovhist", "ndethist")
 
 
-def _group_by_object(object_id: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+def _group_by_object(object_id: torch.Tensor,
+                     then_by: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(perm int32 [n], seg_offsets int32 [n + 1]) for btsbot_alert_features, on the device and without a host
     sync.  Grouping is plumbing: a stable sort keeps input order inside an object, and object k's run starts where k
     run heads lie to the left.  The number of objects would cost a sync, so the kernel is given n possibly empty
-    objects: the offsets past the last object all equal n."""
+    objects: the offsets past the last object all equal n.  With ``then_by`` (btsbot_trigger_update: jd) an object's
+    run is ordered by (then_by, input position): two stable sorts, the minor key first."""
     n, dev = object_id.shape[0], object_id.device
-    ids, perm = torch.sort(object_id.to(torch.int64), stable=True)
+    if then_by is None:
+        ids, perm = torch.sort(object_id.to(torch.int64), stable=True)
+    else:
+        minor = torch.sort(then_by, stable=True).indices
+        ids, major = torch.sort(object_id.to(torch.int64)[minor], stable=True)
+        perm = minor[major]
     run = torch.zeros(n, dtype=torch.int64, device=dev)
     run[1:] = torch.cumsum(ids[1:] != ids[:-1], 0)
     offsets = torch.searchsorted(run, torch.arange(n + 1, device=dev))

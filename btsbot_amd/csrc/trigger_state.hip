@@ -1,0 +1,357 @@
+// btsbot_trigger_update / _reset / _load: the policies of policy_eval.hip for a live stream.  policy_eval answers "does
+// (thr, cut, k, gate) fire on this object, and at which alert first" for a finished split; here the per-object history is
+// a record in a hash table on the device, and one launch per scored batch advances the records and says which alerts a
+// policy fires at NOW.  A policy is monotone along a light curve (it counts valid alerts so far and asks whether anything
+// so far was at or below the gate), so the record is a complete summary: the final state of a time-ordered stream cut
+// into batches anywhere equals policy_eval on the whole, bit for bit -- every output is a count or a copy of an input.
+//
+// Record of one object (struct btsbot_trigger_table: one array per field, `capacity` slots, capacity a power of two):
+//   key        int64   the object id; BTSBOT_TRIGGER_FREE (INT64_MIN) = free slot, which is why that id is reserved
+//   n_alerts   int32   alerts taken
+//   min_magpsf double  NaN skipped; NaN until a magnitude is seen
+//   last_jd    double  the largest jd seen; -inf before
+//   count      int32 [n_policies]      valid alerts so far
+//   trigger    double [n_policies][2]  (jd, magpsf) of the alert the policy fired at; (-1, -1) until it has
+// "min_magpsf <= gate" is the bright flag of every gated policy, so no flag is stored.
+//
+// Find or claim: slot = mix64(id) & (capacity - 1), linear probing with wrap-around, at most `capacity` probes; a free
+// slot is claimed with a 64-bit atomicCAS on key (a vector global atomic).  A key never changes once set, so a plain read
+// that sees another object's id may move on, and one that sees "free" is settled by the CAS.  btsbot_trigger_reset writes
+// the empty record into every slot, so a claim initialises nothing and needs no ordering beyond the CAS; the runs of one
+// launch are distinct objects, so a slot's payload has one owner per launch (payloads of earlier launches are visible
+// through stream order).  A run that finds no slot (table full) and a run of the reserved id are dropped.
+//
+// Update: one wave per run (run = one object's alerts of this batch, in the order of perm: (jd, input position)), one
+// alert per lane, 64 alerts per step.  What the rule needs at alert l is a prefix over lanes <= l, and each is a ballot
+// away:  count so far = carry + popcount(ballot(valid_q) & lanes <= l);  bright so far = carry min <= gate, or
+// ballot(mag <= gate_q) & lanes <= l is not empty;  the firing alert is the lowest set lane of ballot(fires_q) unless the
+// policy has fired before.  Late alerts (jd below the largest jd seen before them) take an exclusive prefix maximum, six
+// shuffles.  Counts, the minimum, the maximum and the fired mask are wave-uniform and carried from the slot into the
+// first step, from step to step, and back into the slot.  Every fired / dropped element is written by its own alert's
+// lane, once.  No LDS; four runs per workgroup; an empty run (the batch is handed over as n possibly empty runs, so that
+// the number of objects costs no host read) ends after reading its two offsets.
+#include "common.h"
+
+#include <climits>
+#include <cmath>
+
+namespace {
+
+constexpr int WG = 256, RUNS_PER_WG = WG / 64;
+constexpr int MAXP = 16;   // policies per table
+constexpr long long FREE_KEY = LLONG_MIN;
+// counters: BTSBOT_TRIGGER_COUNTER_ROWS rows of 8 int64 (one cache line each) whose column sums are the counters; a
+// workgroup adds to row blockIdx.x % rows, so the waves of a large launch do not all queue at one address
+enum { C_OBJECTS = 0, C_TAKEN = 1, C_DROPPED = 2, C_LATE = 3, C_LOAD_PRESENT = 4, C_LOAD_NO_SLOT = 5 };
+constexpr int C_ROWS = BTSBOT_TRIGGER_COUNTER_ROWS, C_STRIDE = 8;
+
+struct Policies {
+  double thr[MAXP], cut[MAXP], gate[MAXP];
+  int k[MAXP];
+  int n;
+};
+
+struct Batch {
+  const int32_t* perm;
+  const int64_t* id;
+  const double* jd;
+  const double* mag;
+  const float* raw;
+  uint8_t* fired;
+  uint8_t* dropped;
+  int n_alerts;
+};
+
+__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {   // splitmix64's finaliser
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+__device__ __forceinline__ void count(const btsbot_trigger_table& t, int which, long long by) {
+  if (by != 0)
+    atomicAdd((unsigned long long*)(t.counters + (blockIdx.x % C_ROWS) * C_STRIDE + which), (unsigned long long)by);
+}
+
+// the slot of `id` (never FREE_KEY), claimed when the id is new; -1: no free slot within `capacity` probes
+__device__ int find_or_claim(const btsbot_trigger_table& t, long long id, bool& claimed) {
+  claimed = false;
+  const unsigned mask = (unsigned)t.capacity - 1u;
+  unsigned idx = (unsigned)mix64((unsigned long long)id) & mask;
+  for (int probe = 0; probe < t.capacity; ++probe, idx = (idx + 1u) & mask) {
+    long long k = __atomic_load_n((const long long*)(t.key + idx), __ATOMIC_RELAXED);
+    if (k == FREE_KEY) {
+      k = (long long)atomicCAS((unsigned long long*)(t.key + idx), (unsigned long long)FREE_KEY, (unsigned long long)id);
+      if (k == FREE_KEY) {
+        claimed = true;
+        return (int)idx;
+      }
+    }
+    if (k == id) return (int)idx;
+  }
+  return -1;
+}
+
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v = fmin(v, __shfl_xor(v, d));
+  return v;
+}
+
+template <int NP>
+__global__ __launch_bounds__(WG) void trigger_update_kernel(btsbot_trigger_table t, Policies pol, Batch in,
+                                                            const int32_t* __restrict__ seg_offsets, int n_runs) {
+  const int lane = threadIdx.x & 63;
+  const long run = (long)blockIdx.x * RUNS_PER_WG + (threadIdx.x >> 6);
+  if (run >= n_runs) return;
+  int s = seg_offsets[run], e = seg_offsets[run + 1];
+  s = s < 0 ? 0 : s > in.n_alerts ? in.n_alerts : s;
+  e = e < 0 ? 0 : e > in.n_alerts ? in.n_alerts : e;
+  if (e <= s) return;
+  const int np = t.n_policies;
+  const unsigned long long le = ~0ull >> (63 - lane);   // lanes <= this one
+
+  // ---- the run's object and its slot (lane 0 probes, every lane learns the answer)
+  int slot = -1;
+  {
+    const int a0 = in.perm[s];
+    long long id = FREE_KEY;
+    if ((unsigned)a0 < (unsigned)in.n_alerts) id = in.id[a0];
+    if (lane == 0 && id != FREE_KEY) {
+      bool claimed;
+      slot = find_or_claim(t, id, claimed);
+      if (claimed) count(t, C_OBJECTS, 1);
+    }
+    slot = __shfl(slot, 0);
+  }
+  if (slot < 0) {   // table full, or the reserved id: the run changes nothing
+    int n_dropped = 0;
+    for (int p = s + lane; p < e; p += 64) {
+      const int a = in.perm[p];
+      if ((unsigned)a >= (unsigned)in.n_alerts) continue;
+      in.dropped[a] = 1;
+      for (int q = 0; q < np; ++q) in.fired[(long)a * np + q] = 0;
+      ++n_dropped;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) n_dropped += __shfl_xor(n_dropped, d);
+    if (lane == 0) count(t, C_DROPPED, n_dropped);
+    return;
+  }
+
+  // ---- the record so far (wave-uniform)
+  int n_seen = t.n_alerts[slot];
+  double lo = t.min_magpsf[slot], last = t.last_jd[slot];
+  int cnt[NP];
+  unsigned done = 0;   // policies that have fired
+#pragma unroll
+  for (int q = 0; q < NP; ++q) {
+    cnt[q] = q < np ? t.count[(long)slot * np + q] : 0;
+    if (q < np && t.trigger[((long)slot * np + q) * 2] >= 0.0) done |= 1u << q;
+  }
+  int n_late = 0, n_taken = 0;
+
+  for (int b0 = s; b0 < e; b0 += 64) {
+    const int p = b0 + lane;
+    int a = p < e ? in.perm[p] : -1;
+    if ((unsigned)a >= (unsigned)in.n_alerts) a = -1;
+    const bool on = a >= 0;
+    const double jd = on ? in.jd[a] : -__builtin_inf();
+    const double mag = on ? in.mag[a] : __builtin_nan("");
+    const double score = on ? (double)in.raw[a] : 0.0;
+    n_taken += __popcll(__ballot(on));
+
+    // late: jd below the largest jd seen before this alert (the slot's, the earlier steps', the lower lanes')
+    double upto = jd;   // inclusive prefix maximum
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const double o = __shfl_up(upto, d);
+      if (lane >= d) upto = fmax(upto, o);
+    }
+    double before = __shfl_up(upto, 1);
+    before = lane == 0 ? last : fmax(before, last);
+    n_late += __popcll(__ballot(on && jd < before));
+    last = fmax(last, __shfl(upto, 63));
+
+    unsigned mine = 0;   // policies that fire at this lane's alert
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+      if (q < np) {   // (wave-uniform)
+        const unsigned long long valid = __ballot(on && score > pol.thr[q] && mag < pol.cut[q]);
+        const double g = pol.gate[q];
+        const unsigned long long bright_at = __ballot(on && mag <= g);
+        const bool bright = g != g || lo <= g || (bright_at & le) != 0;
+        const int so_far = cnt[q] + __popcll(valid & le);
+        const unsigned long long fires = __ballot(on && so_far >= pol.k[q] && bright);
+        if (fires != 0 && !((done >> q) & 1u)) {
+          done |= 1u << q;
+          if (lane == __ffsll((long long)fires) - 1) {
+            mine |= 1u << q;
+            double* tr = t.trigger + ((long)slot * np + q) * 2;
+            tr[0] = jd;
+            tr[1] = mag;
+          }
+        }
+        cnt[q] += __popcll(valid);
+      }
+    }
+    if (on) {
+      in.dropped[a] = 0;
+      for (int q = 0; q < np; ++q) in.fired[(long)a * np + q] = (uint8_t)((mine >> q) & 1u);
+    }
+
+    // the minimum joins the carry after the policies have used the carry of the steps before
+    const bool has = mag == mag;
+    const double step_lo = wave_min(has ? mag : __builtin_inf());
+    if (__ballot(has) != 0) lo = fmin(lo, step_lo);   // (fmin skips a NaN carry)
+  }
+
+  if (lane == 0) {
+    t.n_alerts[slot] = n_seen + n_taken;
+    t.min_magpsf[slot] = lo;
+    t.last_jd[slot] = last;
+    count(t, C_TAKEN, n_taken);
+    count(t, C_LATE, n_late);
+  }
+#pragma unroll
+  for (int q = 0; q < NP; ++q)
+    if (lane == q && q < np) t.count[(long)slot * np + q] = cnt[q];
+}
+
+__global__ __launch_bounds__(WG) void trigger_reset_kernel(btsbot_trigger_table t) {
+  const long stride = (long)gridDim.x * WG;
+  const long i0 = (long)blockIdx.x * WG + threadIdx.x;
+  for (long i = i0; i < t.capacity; i += stride) {
+    t.key[i] = FREE_KEY;
+    t.n_alerts[i] = 0;
+    t.min_magpsf[i] = __builtin_nan("");
+    t.last_jd[i] = -__builtin_inf();
+  }
+  const long cells = (long)t.capacity * t.n_policies;
+  for (long i = i0; i < cells; i += stride) {
+    t.count[i] = 0;
+    t.trigger[2 * i] = -1.0;
+    t.trigger[2 * i + 1] = -1.0;
+  }
+  if (i0 < C_ROWS * C_STRIDE) t.counters[i0] = 0;
+}
+
+__global__ __launch_bounds__(WG) void trigger_load_kernel(btsbot_trigger_table t, int m, const int64_t* __restrict__ id,
+                                                          const int32_t* __restrict__ n_alerts,
+                                                          const double* __restrict__ min_magpsf,
+                                                          const double* __restrict__ last_jd,
+                                                          const int32_t* __restrict__ cnt,
+                                                          const double* __restrict__ trigger) {
+  const long r = (long)blockIdx.x * WG + threadIdx.x;
+  if (r >= m) return;
+  const long long oid = id[r];
+  bool claimed = false;
+  const int slot = oid == FREE_KEY ? -1 : find_or_claim(t, oid, claimed);
+  if (slot < 0) {
+    count(t, C_LOAD_NO_SLOT, 1);
+    return;
+  }
+  if (!claimed) {   // in the table already, or twice in this record set: the first writer keeps the slot
+    count(t, C_LOAD_PRESENT, 1);
+    return;
+  }
+  count(t, C_OBJECTS, 1);
+  t.n_alerts[slot] = n_alerts[r];
+  t.min_magpsf[slot] = min_magpsf[r];
+  t.last_jd[slot] = last_jd[r];
+  const int np = t.n_policies;
+  for (int q = 0; q < np; ++q) {
+    t.count[(long)slot * np + q] = cnt[r * np + q];
+    t.trigger[((long)slot * np + q) * 2] = trigger[(r * np + q) * 2];
+    t.trigger[((long)slot * np + q) * 2 + 1] = trigger[(r * np + q) * 2 + 1];
+  }
+}
+
+// NULL arrays, a capacity that is no power of two, n_policies outside 1..16
+bool table_ok(const char* who, const btsbot_trigger_table* t) {
+  if (t == nullptr || t->key == nullptr || t->n_alerts == nullptr || t->min_magpsf == nullptr || t->last_jd == nullptr ||
+      t->count == nullptr || t->trigger == nullptr || t->counters == nullptr) {
+    btsbot_set_error("%s: NULL table or NULL table array", who);
+    return false;
+  }
+  if (t->capacity < 1 || (t->capacity & (t->capacity - 1)) != 0) {
+    btsbot_set_error("%s: capacity must be a power of two, got %d", who, t->capacity);
+    return false;
+  }
+  if (t->n_policies < 1 || t->n_policies > MAXP) {
+    btsbot_set_error("%s: n_policies must be 1..%d, got %d", who, MAXP, t->n_policies);
+    return false;
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" int btsbot_trigger_reset(const btsbot_trigger_table* table, void* stream) {
+  if (!table_ok("trigger_reset", table)) return BTSBOT_ERR_INVALID_ARG;
+  const long cells = (long)table->capacity * table->n_policies;
+  const long blocks = (cells + WG - 1) / WG;
+  hipLaunchKernelGGL(trigger_reset_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(WG), 0,
+                     (hipStream_t)stream, *table);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+extern "C" int btsbot_trigger_update(const btsbot_trigger_table* table, const double* policies, const int32_t* perm,
+                                     const int32_t* seg_offsets, int n_alerts, int n_runs, const int64_t* object_id,
+                                     const double* jd, const double* magpsf, const float* raw_pred, uint8_t* fired,
+                                     uint8_t* dropped, void* stream) {
+  if (!table_ok("trigger_update", table)) return BTSBOT_ERR_INVALID_ARG;
+  if (policies == nullptr || perm == nullptr || seg_offsets == nullptr || object_id == nullptr || jd == nullptr ||
+      magpsf == nullptr || raw_pred == nullptr || fired == nullptr || dropped == nullptr || n_alerts < 0 || n_runs < 0) {
+    btsbot_set_error("trigger_update: NULL argument or negative n_alerts / n_runs");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  Policies pol;
+  pol.n = table->n_policies;
+  for (int q = 0; q < MAXP; ++q) {
+    const bool used = q < pol.n;
+    const double k = used ? policies[4 * q + 2] : 1.0;
+    if (!(k >= 1.0) || k != std::floor(k)) {
+      btsbot_set_error("trigger_update: policy %d: k must be an integer >= 1, got %g", q, k);
+      return BTSBOT_ERR_INVALID_ARG;
+    }
+    pol.thr[q] = used ? policies[4 * q] : 0.0;
+    pol.cut[q] = used ? policies[4 * q + 1] : 0.0;
+    pol.gate[q] = used ? policies[4 * q + 3] : 0.0;
+    pol.k[q] = k > (double)INT_MAX ? INT_MAX : (int)k;   // (more than a record can count: never fires)
+  }
+  if (n_alerts == 0) return BTSBOT_OK;
+  if (n_runs == 0) {
+    btsbot_set_error("trigger_update: %d alerts in 0 runs", n_alerts);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  const Batch in{perm, object_id, jd, magpsf, raw_pred, fired, dropped, n_alerts};
+  const unsigned blocks = (unsigned)(((long)n_runs + RUNS_PER_WG - 1) / RUNS_PER_WG);
+  if (pol.n <= 4)
+    hipLaunchKernelGGL(trigger_update_kernel<4>, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, *table, pol, in,
+                       seg_offsets, n_runs);
+  else
+    hipLaunchKernelGGL(trigger_update_kernel<MAXP>, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, *table, pol, in,
+                       seg_offsets, n_runs);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+extern "C" int btsbot_trigger_load(const btsbot_trigger_table* table, int n_records, const int64_t* object_id,
+                                   const int32_t* n_alerts, const double* min_magpsf, const double* last_jd,
+                                   const int32_t* count, const double* trigger, void* stream) {
+  if (!table_ok("trigger_load", table)) return BTSBOT_ERR_INVALID_ARG;
+  if (object_id == nullptr || n_alerts == nullptr || min_magpsf == nullptr || last_jd == nullptr || count == nullptr ||
+      trigger == nullptr || n_records < 0) {
+    btsbot_set_error("trigger_load: NULL argument or negative n_records");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (n_records == 0) return BTSBOT_OK;
+  hipLaunchKernelGGL(trigger_load_kernel, dim3((unsigned)((n_records + WG - 1) / WG)), dim3(WG), 0, (hipStream_t)stream,
+                     *table, n_records, object_id, n_alerts, min_magpsf, last_jd, count, trigger);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}

@@ -1,0 +1,193 @@
+"""Streaming policy triggers: which objects does a scanning policy fire on NOW.
+
+``val.policy_eval`` answers "does (thr, cut, k, gate) fire on this object, and at which alert first" for a finished
+split.  A live stream ends at a tensor of scores batch after batch; ``TriggerState`` keeps, per object and in a hash table
+on the device, the few numbers that summarise its history for a fixed set of policies (``btsbot_trigger_update``,
+csrc/trigger_state.hip), and one launch per scored batch advances them and marks the alerts a policy fires at:
+
+    state = TriggerState(REFERENCE_POLICIES, capacity=1 << 20)
+    for object_id, jd, magpsf, triplets, metadata in nights:
+        scores = stream.score(triplets, metadata)
+        new = state.new_triggers(object_id, jd, magpsf, scores)      # object_id, policy, trigger_jd, trigger_mag, alert
+
+The cost of a batch follows the batch, not the history.  Cut a time-ordered stream into batches anywhere: ``export()``
+then equals ``val.policy_eval`` over the whole stream bit for bit (every output is a count or a copy of an input).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Mapping
+
+import torch
+
+from . import _lib
+from .alert_utils import _group_by_object
+from .val import POLICIES_PER_LAUNCH, REFERENCE_POLICIES, _policy_table
+
+RESERVED_ID = -(1 << 63)          # BTSBOT_TRIGGER_FREE: the free-slot marker, the one id a state cannot hold
+_COUNTERS = ("objects", "taken", "dropped", "late")
+_RECORD = ("object_id", "n_alerts", "min_magpsf", "last_jd", "count", "trigger_jd", "trigger_mag")
+
+
+def _ptr(t: torch.Tensor) -> C.c_void_p:
+    return C.c_void_p(t.data_ptr())
+
+
+class TriggerState:
+    """Per-object policy state on one GPU.
+
+    policies: name -> (thr, cut, k, gate or None) as for ``val.policy_eval``, 1..16 of them, fixed for the life of the
+    state; capacity: slots of the table, a power of two (an object takes one slot for good: there is no eviction).  Per
+    object id (any int64 but ``RESERVED_ID``) the state holds n_alerts, min_magpsf (NaN skipped), last_jd (the largest jd
+    seen) and per policy the count of valid alerts and (trigger_jd, trigger_mag), (-1, -1) until the policy has fired.
+
+    Calls on one state must be ordered by the caller's streams: concurrent ``update`` calls are undefined."""
+
+    def __init__(self, policies: Mapping = REFERENCE_POLICIES, capacity: int = 1 << 20, device="cuda"):
+        table = _policy_table(policies)
+        if table.shape[0] > POLICIES_PER_LAUNCH:
+            raise ValueError(f"a TriggerState holds 1..{POLICIES_PER_LAUNCH} policies, got {table.shape[0]}")
+        for name, row in zip(policies, table.tolist()):
+            if not row[2] >= 1 or row[2] != int(row[2]):
+                raise ValueError(f"policy {name!r}: k must be an integer >= 1, got {row[2]!r}")
+        if not isinstance(capacity, int) or capacity < 1 or capacity & (capacity - 1) or capacity > 1 << 30:
+            raise ValueError(f"capacity must be a power of two (at most 2^30), got {capacity!r}")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError(f"btsbot_amd.TriggerState runs on the GPU; there is no CPU fallback (device is {dev})")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.policies = dict(policies)
+        self.capacity, self.device = capacity, dev
+        self._policy_rows = table.contiguous()                               # host, float64 [n_pol, 4]
+        npol = self.n_policies = table.shape[0]
+        self._key = torch.empty(capacity, dtype=torch.int64, device=dev)
+        self._n = torch.empty(capacity, dtype=torch.int32, device=dev)
+        self._min = torch.empty(capacity, dtype=torch.float64, device=dev)
+        self._last = torch.empty(capacity, dtype=torch.float64, device=dev)
+        self._count = torch.empty((capacity, npol), dtype=torch.int32, device=dev)
+        self._trig = torch.empty((capacity, npol, 2), dtype=torch.float64, device=dev)
+        self._counters = torch.empty((_lib.TRIGGER_COUNTER_ROWS, 8), dtype=torch.int64, device=dev)
+        self._table = _lib.TriggerTable(*(t.data_ptr() for t in (self._key, self._n, self._min, self._last, self._count,
+                                                                 self._trig, self._counters)), capacity, npol)
+        self.reset()
+
+    def _stream(self) -> C.c_void_p:
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def reset(self) -> None:
+        """Forget every object and zero the counters (one launch, no host synchronisation)."""
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().btsbot_trigger_reset(C.byref(self._table), self._stream()), "btsbot_trigger_reset")
+
+    def update(self, object_id: torch.Tensor, jd: torch.Tensor, magpsf: torch.Tensor,
+               raw_preds: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """One batch of [n] device tensors into the state; jd and magpsf are taken as float64, raw_preds as float32 and
+        compared as that value widened to float64, as in ``val.policy_eval``.
+
+        Batches are taken in call order; inside a batch an object's alerts are taken in (jd, input position) order, so the
+        batches of a time-sorted stream are taken exactly in ``policy_eval``'s order.  Alert i of object o: n_alerts += 1;
+        i is *late* (counted, and taken all the same, in arrival order) when jd < last_jd; last_jd = max(last_jd, jd);
+        min_magpsf takes magpsf unless it is NaN; per policy count += (raw > thr and magpsf < cut) (a NaN magpsf is never
+        valid); a policy that has not fired yet fires at i when count >= k and (without a gate, or) min_magpsf <= gate.
+        jd must be >= 0 and finite (not checked).
+
+        Returns ``fired`` bool [n, n_pol] (the policy fires at this alert: at most once per object and policy over the
+        life of the state) and ``dropped`` bool [n]: alerts of an object that found no free slot (table full; objects
+        already in the table keep being updated) and alerts with ``RESERVED_ID`` change nothing and are counted.
+
+        No host synchronisation: two stable sorts, the offsets and one launch are queued on the current stream, and
+        nothing on this path reads a device value on the host (no ``.item()``, ``.cpu()``, ``nonzero``)."""
+        cols = (object_id, jd, magpsf, raw_preds)
+        names = ("object_id", "jd", "magpsf", "raw_preds")
+        for name, t in zip(names, cols):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+        if object_id.device.type != "cuda":
+            raise RuntimeError("btsbot_amd.TriggerState.update runs on the GPU; there is no CPU "
+                               f"fallback (object_id is on {object_id.device})")
+        n = object_id.shape[0] if object_id.dim() == 1 else -1
+        for name, t in zip(names, cols):
+            if t.dim() != 1 or t.shape[0] != n:
+                raise ValueError(f"{name} must be [{max(n, 0)}], got {tuple(t.shape)}")
+        if object_id.dtype.is_floating_point or object_id.dtype == torch.bool:
+            raise ValueError(f"object_id must be an integer tensor, got {object_id.dtype}")
+        dev = self.device
+        if object_id.device != dev:
+            raise ValueError(f"object_id is on {object_id.device}, the state on {dev}")
+        ids = object_id.to(torch.int64).contiguous()
+        jd, magpsf = (t.to(device=dev, dtype=torch.float64).contiguous() for t in (jd, magpsf))
+        raw = raw_preds.to(device=dev, dtype=torch.float32).contiguous()
+        fired = torch.empty((n, self.n_policies), dtype=torch.uint8, device=dev)        # the kernel writes every element
+        dropped = torch.empty(n, dtype=torch.uint8, device=dev)
+        if n:
+            perm, offsets = _group_by_object(ids, then_by=jd)
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().btsbot_trigger_update(
+                    C.byref(self._table), C.cast(C.c_void_p(self._policy_rows.data_ptr()), C.POINTER(C.c_double)),
+                    _ptr(perm), _ptr(offsets), n, n, _ptr(ids), _ptr(jd), _ptr(magpsf), _ptr(raw), _ptr(fired),
+                    _ptr(dropped), self._stream()), "btsbot_trigger_update")
+        return {"fired": fired.view(torch.bool), "dropped": dropped.view(torch.bool)}
+
+    def new_triggers(self, object_id: torch.Tensor, jd: torch.Tensor, magpsf: torch.Tensor,
+                     raw_preds: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """``update``, then the batch's triggers as tensors of equal length, ordered by (alert, policy): ``object_id``,
+        ``policy`` (index into the state's policies), ``trigger_jd``, ``trigger_mag`` and ``alert`` (the row of the batch).
+        One host read (the number of triggers)."""
+        fired = self.update(object_id, jd, magpsf, raw_preds)["fired"]
+        where = fired.nonzero()                                                          # the one host read
+        row, pol = where[:, 0], where[:, 1]
+        return {"object_id": object_id[row].to(torch.int64), "policy": pol,
+                "trigger_jd": jd.to(device=self.device, dtype=torch.float64)[row],
+                "trigger_mag": magpsf.to(device=self.device, dtype=torch.float64)[row], "alert": row}
+
+    def export(self) -> Dict[str, torch.Tensor]:
+        """The objects held, in ascending id order: ``object_id``, ``n_alerts`` (int64), ``min_magpsf``, ``last_jd``,
+        ``count`` int32 [n_obj, n_pol], ``pred`` int32 (``trigger_jd >= 0``), ``trigger_jd``, ``trigger_mag`` float64
+        [n_obj, n_pol]; where the names are ``val.policy_eval``'s, so are shapes and dtypes.  One host read."""
+        slots = (self._key != RESERVED_ID).nonzero()[:, 0]                               # the one host read
+        slots = slots[torch.argsort(self._key[slots])]
+        trig = self._trig[slots]
+        return {"object_id": self._key[slots], "n_alerts": self._n[slots].to(torch.int64), "min_magpsf": self._min[slots],
+                "last_jd": self._last[slots], "count": self._count[slots], "pred": (trig[:, :, 0] >= 0).to(torch.int32),
+                "trigger_jd": trig[:, :, 0].contiguous(), "trigger_mag": trig[:, :, 1].contiguous()}
+
+    @classmethod
+    def from_export(cls, records: Mapping, policies: Mapping = REFERENCE_POLICIES, capacity: int = 1 << 20,
+                    device="cuda") -> "TriggerState":
+        """A state holding ``records`` (what ``export()`` returned, tensors or arrays; ``pred`` is not needed): a service
+        restart, or a move to a larger table.  ``policies`` must be the exporting state's.  Raises ValueError when an id
+        comes twice, is ``RESERVED_ID``, or the records do not fit the capacity."""
+        state = cls(policies, capacity, device)
+        dev, npol = state.device, state.n_policies
+        missing = [k for k in _RECORD if k not in records]
+        if missing:
+            raise ValueError(f"records lack {missing}")
+        ids = torch.as_tensor(records["object_id"]).to(device=dev, dtype=torch.int64).contiguous()
+        m = ids.shape[0] if ids.dim() == 1 else -1
+        n_alerts = torch.as_tensor(records["n_alerts"]).to(device=dev, dtype=torch.int32).contiguous()
+        lo, last = (torch.as_tensor(records[k]).to(device=dev, dtype=torch.float64).contiguous()
+                    for k in ("min_magpsf", "last_jd"))
+        count = torch.as_tensor(records["count"]).to(device=dev, dtype=torch.int32).contiguous()
+        trig = torch.stack([torch.as_tensor(records[k]).to(device=dev, dtype=torch.float64)
+                            for k in ("trigger_jd", "trigger_mag")], dim=-1).contiguous()
+        for name, t, shape in (("object_id", ids, (m,)), ("n_alerts", n_alerts, (m,)), ("min_magpsf", lo, (m,)),
+                               ("last_jd", last, (m,)), ("count", count, (m, npol)),
+                               ("trigger_jd / trigger_mag", trig, (m, npol, 2))):
+            if m < 0 or tuple(t.shape) != shape:
+                raise ValueError(f"records[{name!r}] must be {list(shape)} for {npol} policies, got {list(t.shape)}")
+        if m:
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().btsbot_trigger_load(
+                    C.byref(state._table), m, _ptr(ids), _ptr(n_alerts), _ptr(lo), _ptr(last), _ptr(count), _ptr(trig),
+                    state._stream()), "btsbot_trigger_load")
+            present, no_slot = state._counters.sum(0)[4:6].tolist()                      # the one host read
+            if present or no_slot:
+                raise ValueError(f"from_export: {present} records carry an id that came before, {no_slot} found no slot "
+                                 f"in a table of {capacity} (or carry the reserved id)")
+        return state
+
+    def counters(self) -> Dict[str, int]:
+        """``objects`` held, alerts ``taken``, alerts ``dropped``, ``late`` alerts since the state was made or reset (a
+        loaded record counts as an object, its alerts were taken elsewhere).  One host read."""
+        return dict(zip(_COUNTERS, self._counters.sum(0)[:4].tolist()))

@@ -553,6 +553,60 @@ int btsbot_policy_eval(const int32_t* perm, const int32_t* seg_offsets, int n_al
                        const double* policies, int n_policies, int32_t* obj_pred, double* obj_trigger,
                        double* obj_info, void* stream);
 
+/* ---- streaming policy triggers: the rule of btsbot_policy_eval with the per-object history kept on the device ---- */
+
+/* A table of per-object records, one array per field, in CALLER-OWNED device memory (the entry points below never
+ * allocate, synchronise or copy to the host).  Open addressing: an object lives at the first slot at or after
+ * hash(id) & (capacity - 1), wrapping round, whose key is its id.  The struct itself is host memory, passed by pointer
+ * and read before the call returns.
+ * counters: BTSBOT_TRIGGER_COUNTER_ROWS rows of 8 int64; the COLUMN SUMS are { objects held, alerts taken, alerts
+ * dropped, late alerts, records btsbot_trigger_load found present already, records it found no slot for, 0, 0 }. */
+#define BTSBOT_TRIGGER_FREE INT64_MIN     /* key of a free slot: the one object id a table cannot hold             */
+#define BTSBOT_TRIGGER_COUNTER_ROWS 16
+typedef struct btsbot_trigger_table {
+  int64_t* key;         /* [capacity]                 object id, BTSBOT_TRIGGER_FREE = free                        */
+  int32_t* n_alerts;    /* [capacity]                 alerts taken                                                 */
+  double* min_magpsf;   /* [capacity]                 NaN skipped; NaN until a magnitude is seen                   */
+  double* last_jd;      /* [capacity]                 the largest jd seen; -inf before                             */
+  int32_t* count;       /* [capacity][n_policies]     valid alerts so far                                          */
+  double* trigger;      /* [capacity][n_policies][2]  (jd, magpsf) of the alert the policy fired at; (-1, -1)      */
+  int64_t* counters;    /* [BTSBOT_TRIGGER_COUNTER_ROWS][8]                                                        */
+  int32_t capacity;     /* slots: a power of two                                                                   */
+  int32_t n_policies;   /* 1..16, fixed for the life of the table                                                  */
+} btsbot_trigger_table;
+
+/* Writes the empty record (free, 0, NaN, -inf, counts 0, triggers -1) into every slot and zeroes the counters.  A new
+ * table must be reset before its first use.  One launch on `stream`. */
+int btsbot_trigger_reset(const btsbot_trigger_table* table, void* stream);
+
+/* One batch of n_alerts scored alerts into the table.  policies is a HOST array [table->n_policies][4] as for
+ * btsbot_policy_eval (the same for every call on a table).  perm int32 [n_alerts] lists the alert indices sorted by
+ * (object id, jd, input position); run r (one object's alerts of this batch) owns perm[seg_offsets[r] ..
+ * seg_offsets[r+1]) (seg_offsets int32 [n_runs + 1]; empty runs are allowed, so n_runs may be an upper bound whose
+ * surplus offsets all equal n_alerts; trusted device data, clamped, never validated on the host).  A run's slot is found,
+ * or claimed with a 64-bit compare-and-swap on key; then its alerts are taken in perm's order.  Alert i: n_alerts += 1;
+ * i is LATE (counted, and taken all the same) when jd[i] < last_jd; last_jd = max(last_jd, jd[i]); min_magpsf takes
+ * magpsf[i] unless that is NaN; per policy count += ((double)raw_pred[i] > thr and magpsf[i] < cut); a policy that has
+ * not fired yet fires at i when count >= k and (without a gate, or) min_magpsf <= gate: trigger = (jd[i], magpsf[i])
+ * and fired[i][policy] = 1.  A policy fires at most once per object over the life of the table (jd must be >= 0).
+ * A run that finds no free slot within `capacity` probes, and a run of the id BTSBOT_TRIGGER_FREE, is DROPPED: its
+ * alerts get dropped[i] = 1, change nothing and are counted.  fired uint8 [n_alerts][n_policies] and dropped uint8
+ * [n_alerts] are written in full, every element by one writer.  Two updates of one table must be ordered (same stream,
+ * or events): concurrent updates are undefined.  One launch on `stream`, no host synchronisation; n_alerts == 0
+ * launches nothing. */
+int btsbot_trigger_update(const btsbot_trigger_table* table, const double* policies, const int32_t* perm,
+                          const int32_t* seg_offsets, int n_alerts, int n_runs, const int64_t* object_id,
+                          const double* jd, const double* magpsf, const float* raw_pred, uint8_t* fired,
+                          uint8_t* dropped, void* stream);
+
+/* Inserts n_records exported records (the fields of the table, record-major: count int32 [n_records][n_policies],
+ * trigger double [n_records][n_policies][2]) with the same find-or-claim.  A record whose id is in the table already,
+ * or twice in the set, is not written and counted in counters column 4; one that finds no slot (or carries
+ * BTSBOT_TRIGGER_FREE) in column 5: the caller reads the counters to learn of either.  One launch on `stream`. */
+int btsbot_trigger_load(const btsbot_trigger_table* table, int n_records, const int64_t* object_id,
+                        const int32_t* n_alerts, const double* min_magpsf, const double* last_jd,
+                        const int32_t* count, const double* trigger, void* stream);
+
 /* Replaces: the epoch / validation metrics of val.py:159-168 and train.py:550-558 -- out2[0] += sum_i of
  * BCEWithLogitsLoss(pos_weight) terms over n logits, out2[1] += number of alerts whose sigmoid(z) > 0.5
  * agrees with the label (caller zeroes out2 and divides by n). */

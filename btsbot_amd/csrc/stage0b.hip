@@ -3,22 +3,25 @@
 //   stem (conv 4x4 s4 + LN)  ->  2 x [ dwconv 7x7 + LN -> fc1 -> GELU -> fc2 -> layer-scale -> +x ]
 //                            ->  downsample (LN + conv 2x2 s2)  ->  [49][128] f32
 //
-// (timm ConvNeXt stem / stages[0] / stages[1].downsample, reached from
-// /root/reference/btsbot/architectures.py:108,132) -- cut so that TWO workgroups share a CU:
+// (timm ConvNeXt stem / stages[0] / stages[1].downsample) -- cut so that TWO workgroups share a CU:
 // a single 512-thread workgroup per CU (the first layout of this kernel, rounds 1-2, no longer in the tree) runs its
 // phases in lockstep (depthwise = VALU + LDS, MLP = MFMA + VALU, parameter fetches = latency) and nothing overlaps; two independent
 // 256-thread workgroups drift apart and fill each other's stalls, at the same 2 waves per SIMD
 // that the f32 VALU needs for its full rate (tools/unit/valu_rate.hip).
 //
 // What had to shrink to fit 80 KB of LDS and 4 waves per workgroup:
-//   * ONE 16-bit map image ([256 px][64 ch], 144-byte rows).  The depthwise phase keeps its LN
-//     outputs in registers until every wave has finished reading the image, then overwrites it;
-//     the MLP reads that as its MFMA B operand and writes the new x back at its end.
-//   * the pointwise filters stream through a 4-slot ring of 8 KB chunks (32 hidden units: W1 rows
+//   * ONE image region.  The depthwise phase reads it as the planar 16-bit map (lane = channel) and leaves its
+//     outputs in registers; once every wave has finished reading, they go back as an fp32 [225 px][64 ch] image
+//     (272-byte rows) -- the one transpose between the depthwise layout (lane = channel, registers = pixels) and
+//     the MLP's (lane = pixel).  Each lane reads its own pixel's channels back in fc1's k order, does the LayerNorm
+//     in registers (in-lane sums + one exchange with lane ^ 32, as the stem's and the downsample's) and holds the
+//     MFMA B operand: no cross-wave reduction, no 16-bit LayerNorm image.  The MLP writes the new x back at its end;
+//   * the pointwise filters stream through a 3-slot ring of 8 KB chunks (32 hidden units: W1 rows
 //     + W2 columns) by LDS-DMA straight from the plain row-major 16-bit filters -- the per-lane
 //     source address does the re-arrangement (XOR swizzles for conflict-free ds_read_b128, and the
 //     W1 rows of a chunk in bit-2/bit-3-swapped order so that the fc1 accumulator of a lane IS the
-//     fc2 B operand in plain k order);
+//     fc2 B operand in plain k order).  Slots 0 and 1, which receive chunks 0 and 1 during the depthwise phase, lie
+//     behind the image; slot 2 overlays the image's tail, which is dead before chunk 2 is requested;
 //   * layer scale is folded into the fc2 filter (gamma * W2, packed once), so fc2 accumulates
 //     straight into the fp32 residual registers: no second accumulator tile;
 //   * a wave owns 64 pixels (2 column blocks of the 32x32 MFMA): residual = 64 registers.
@@ -68,7 +71,6 @@ static_assert(256 * PITCH <= C * 800, "the [pixel][channel] image overlays the p
 constexpr int PL_ROWS = 22, PL_XQ = PL_ROWS * 8, PL_CH = 800;
 constexpr int PLB = C * PL_CH;                    // 51200 (the [pixel][channel] image overlays it)
 constexpr int CHUNKB = 8192, NCH = HID / 32, NSLOT = 3;
-constexpr int RINGB = NSLOT * CHUNKB;             // 24576
 // per-block parameter image in HBM (launch_pack_s0par):
 //   Toeplitz taps, operand type: [r = ky * 3 + (rb + 1)][channel][i][k] = W[channel][ky][4 rb + k - i + 3] (0 outside
 //   the 7 taps): the A operand of the 4x4x4 MFMA that maps input columns 4 (xb + rb) + k to outputs 4 xb + i;
@@ -79,18 +81,29 @@ static_assert(PF_B2 + C == PF_FLOATS, "parameter image layout");
 constexpr int PARB = TW_BYTES + PF_FLOATS * 4;    // 45056
 // split mode (BTSBOT_F16X2): the taps' f16 remainders follow their heads, the fp32 part comes last
 constexpr int PARB_X2 = 2 * TW_BYTES + PF_FLOATS * 4;
-// LDS layout.  Split mode (X2): a second planar image behind the first (the f16 remainders of the map the depthwise phase
-// reads) and chunks of twice the size (the filters' remainders behind their heads) -- 154,880 bytes, one workgroup per CU.
+// the fp32 [pixel][channel] image between the depthwise phase and the LayerNorm: 225 rows of 68 dwords, so the rows of
+// lanes i = 0..15 start at banks 4 i (ds_read_b128 without conflicts); a transposing store (16 channels x 4 rows, 15
+// pixels apart) is 2-way, which a ds_write_b32 does not pay for
+constexpr int LNP = 4 * C + 16;                   // 272
+constexpr int LNIMGB = P * LNP;                   // 61200
+static_assert(LNIMGB % 16 == 0 && PLB + CHUNKB <= LNIMGB, "ring slot 2 inside the image's tail, behind the planar image");
+// LDS layout: the image region (planar image, fp32 image, the downsample's 16-bit map: never live together), ring
+// slots 0 and 1 behind it, slot 2 over the fp32 image's tail at byte 51200 (zero_planar() never touches it), then the
+// block's fp32 words.  Split mode (X2): a second planar image behind the first (the f16 remainders of the map the
+// depthwise phase reads; the fp32 image fits inside the two) and chunks of twice the size (the filters' remainders
+// behind their heads), all three slots behind the images -- 153,344 bytes, one workgroup per CU.
 template <bool X2> struct S0L {
   static constexpr int PLANES = X2 ? 2 : 1;
   static constexpr int CHB = X2 ? 2 * CHUNKB : CHUNKB;     // bytes of a ring slot
-  static constexpr int OFF_RING = PLANES * PLB;
-  static constexpr int OFF_B1 = OFF_RING + NSLOT * CHB;    // 256 + 64 floats: this block's fc1 bias, gamma*b2
-  static constexpr int OFF_ST = OFF_B1 + (HID + C) * 4;    // LayerNorm (rstd, -mean * rstd) per padded pixel slot: 2 x 256 floats
-  static constexpr int LDS_BYTES = OFF_ST + 2 * 256 * 4;   // 79104 (two workgroups per CU) / 154880
+  static constexpr int OFF_RING = X2 ? PLANES * PLB : LNIMGB;
+  static constexpr int OFF_SLOT2 = X2 ? OFF_RING + 2 * CHB : PLB;
+  static constexpr int OFF_B1 = OFF_RING + (X2 ? NSLOT : 2) * CHB;   // 256 + 3 x 64 floats: this block's fc1 bias, gamma*b2, LN weight, LN bias
+  static constexpr int LDS_BYTES = OFF_B1 + (HID + 3 * C) * 4;       // 79376 (two workgroups per CU) / 153344
+  static __device__ __forceinline__ int slot(int s) { return s == 2 ? OFF_SLOT2 : OFF_RING + s * CHB; }
 };
 static_assert(S0L<false>::LDS_BYTES <= 81920, "two workgroups per CU");
 static_assert(S0L<true>::LDS_BYTES <= 160 * 1024, "one workgroup per CU");
+static_assert(LNIMGB <= S0L<true>::OFF_RING && LNIMGB <= S0L<false>::OFF_RING, "the fp32 image in front of ring slots 0 and 1");
 constexpr float LN_EPS = 1e-6f;
 
 #define SB_STAMP(i)                                                                \
@@ -110,14 +123,6 @@ template <int N> __device__ __forceinline__ void wait_vm() {
 }
 __device__ __forceinline__ int swz4(int row) {   // F[(row >> 2) & 3], F = {0,3,2,1}
   return (4 - ((row >> 2) & 3)) & 3;
-}
-__device__ __forceinline__ float swap_add32(float a, float b) {
-  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float swap_add16(float a, float b) {
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 // LayerNorm over the 64 channels of this lane's pixel (x[2][16] here + the partner lane ^ 32)
 __device__ __forceinline__ void ln_regs(const f32x16 (&x)[CT], const float* __restrict__ w,
@@ -201,34 +206,6 @@ __device__ __forceinline__ void regs_to_tap(const f32x16 (&x)[CT], float* tap, i
           make_float4(x[ct][4 * qd], x[ct][4 * qd + 1], x[ct][4 * qd + 2], x[ct][4 * qd + 3]);
 }
 
-template <int CTRL> __device__ __forceinline__ float dpp_mov(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-
-// Transposing sum over the 16 blocks (lane bits 2..5) of 64 values per lane (SQ: of their squares): level by
-// level the lanes of a pair split the values between them, so 32 + 16 + 8 + 4 adds instead of 4 x 64.
-// out[0..3] = the 16-lane totals of values 16 (lane >> 4) + 4 ((lane >> 2) & 3) + 0..3.
-template <bool SQ> __device__ __forceinline__ void block_reduce64(const float (&v)[64], int lane, float (&out)[4]) {
-  float w[32];
-#pragma unroll
-  for (int n = 0; n < 32; ++n)
-    w[n] = SQ ? swap_add32(v[n] * v[n], v[n + 32] * v[n + 32]) : swap_add32(v[n], v[n + 32]);
-#pragma unroll
-  for (int n = 0; n < 16; ++n) w[n] = swap_add16(w[n], w[n + 16]);
-  const bool b3 = (lane & 8) != 0, b2 = (lane & 4) != 0;
-#pragma unroll
-  for (int n = 0; n < 8; ++n) {
-    const float own = b3 ? w[n + 8] : w[n], send = b3 ? w[n] : w[n + 8];
-    w[n] = own + dpp_mov<0x128>(send);                       // row_ror:8 = lane ^ 8
-  }
-#pragma unroll
-  for (int n = 0; n < 4; ++n) {
-    const float own = b2 ? w[n + 4] : w[n], send = b2 ? w[n] : w[n + 4];
-    const float lo = dpp_mov<0x124>(send), hi = dpp_mov<0x12C>(send);   // row_ror:4 / :12 = lane - 4 / lane + 4
-    out[n] = own + (b2 ? lo : hi);
-  }
-}
-
 // X2 (BTSBOT_F16X2, T = f16): the LayerNorm outputs and the hidden activations go to the matrix pipe as f16 head +
 // f16 remainder (two products per k-step against the f16 filters), the depthwise taps likewise (two 4x4x4 products per
 // tap fragment against the f16 map), the downsample with both operands split (three products).  What stays plain f16
@@ -247,17 +224,14 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
   using DT = typename std::conditional<KEEP, f16_t, T>::type;
   using frag4 = typename SBM<DT>::frag4;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* map = smem;     // [pixel][channel] image (MLP operand, downsample input)
-  unsigned char* pl = smem;      // planar image (depthwise operand): same bytes, never live together
+  unsigned char* map = smem;     // 16-bit [pixel][channel] image (downsample input)
+  unsigned char* pl = smem;      // planar image (depthwise operand) and the fp32 [pixel][channel] image: same bytes, never live together
   using L = S0L<X2>;
-  constexpr int CHB = L::CHB;
   constexpr int PLO = X2 ? PLB : 0;                  // split mode: the planar image of the remainders
-  unsigned char* ring = smem + L::OFF_RING;
   float* b1s = reinterpret_cast<float*>(smem + L::OFF_B1);
   float* b2s = b1s + HID;
-  float* part = reinterpret_cast<float*>(ring + 2 * CHB);      // LayerNorm partial sums [2][4 waves][256 slots]:
-                                                               // ring slot 2 is idle until the MLP's first chunk
-  float* st = reinterpret_cast<float*>(smem + L::OFF_ST);
+  float* lnws = b2s + C;         // this block's LayerNorm weight and bias
+  float* lnbs = lnws + C;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 31, h = lane >> 5;
@@ -271,7 +245,6 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
   }
   // depthwise roles: lane = (block b = channel 16 wave + b, row offset j)
   const int dj = lane & 3, dch = wave * 16 + (lane >> 2);
-  const int dyb = lane >> 4, dxb = (lane >> 2) & 3;   // where this lane's LayerNorm sums end up
 
   SB_STAMP(0);
   // a block's Toeplitz taps (16 channels x 4 rows x 21 fragments per wave, lane-linear 8-byte loads) and its
@@ -289,8 +262,8 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
     }
     const float* pf = reinterpret_cast<const float*>(bk.par + (X2 ? 2 : 1) * TW_BYTES);
     dwbias = pf[PF_DWB + dch];
-    lng = pf[PF_LNW + dch];
-    lnb2 = pf[PF_LNB + dch];
+    lng = pf[PF_LNW + (tid & 63)];
+    lnb2 = pf[PF_LNB + (tid & 63)];
     b1v = pf[PF_B1 + tid];
     b2v = pf[PF_B2 + (tid & 63)];
   };
@@ -367,9 +340,13 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
   for (int j = 0; j < 2; ++j) {
     const Stage0Blk& bk = a.blk[j];
     SB_STAMP(2 + 5 * j);
-    __syncthreads();   // planar image complete (stem / previous MLP); ring free; b1s / st idle
+    __syncthreads();   // planar image complete (stem / previous MLP); ring free; the block's fp32 words idle
     b1s[tid] = b1v;
-    if (tid < C) b2s[tid] = b2v;
+    if (tid < C) {
+      b2s[tid] = b2v;
+      lnws[tid] = lng;
+      lnbs[tid] = lnb2;
+    }
 
     // ---- pointwise filters: chunk = 32 hidden units = 8 pieces of 1 KiB, 2 per wave.
     //      pieces 0..3: W1 rows (LDS row m <- hidden unit 32*ch + swap23(m)), 128-byte rows,
@@ -400,13 +377,13 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
 #pragma unroll
       for (int i = 0; i < 2; ++i)
         __builtin_amdgcn_global_load_lds((gptr_t)(wsrc[i] + (size_t)ch * wstep0),
-                                         (lptr_t)(ring + (ch % NSLOT) * CHB + (wave * 2 + i) * 1024),
+                                         (lptr_t)(smem + L::slot(ch % NSLOT) + (wave * 2 + i) * 1024),
                                          16, 0, 0);
       if (X2) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
           __builtin_amdgcn_global_load_lds((gptr_t)(wsrcl[i] + (size_t)ch * wstep0),
-                                           (lptr_t)(ring + (ch % NSLOT) * CHB + CHUNKB + (wave * 2 + i) * 1024),
+                                           (lptr_t)(smem + L::slot(ch % NSLOT) + CHUNKB + (wave * 2 + i) * 1024),
                                            16, 0, 0);
       }
     };
@@ -500,84 +477,82 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
           }
     }
     SB_STAMP(4 + 5 * j);   // depthwise done
-    // ---- LayerNorm over the 64 channels of a pixel: 16 blocks of this wave (transposing lane reduction), then
-    //      the 4 waves through LDS; single-pass variance
+    // ---- the one transpose: the depthwise outputs (lane = channel, registers = pixels) as fp32 into the
+    //      [pixel][channel] image, which overlays the planar image that other waves may still be reading
+    __syncthreads();   // nobody reads the planar image any more
     {
-      float s1[4], s2[4];
-#ifdef S0_EXP_NOLNRED
-      for (int i = 0; i < 4; ++i) { s1[i] = v[i]; s2[i] = v[i + 4] * v[i + 4] + 1.f; }
-#else
-      block_reduce64<false>(v, lane, s1);
-      block_reduce64<true>(v, lane, s2);
-#endif
-      const int slot = (4 * dyb + dj) * 16 + 4 * dxb;
-      *reinterpret_cast<float4*>(part + wave * 256 + slot) = make_float4(s1[0], s1[1], s1[2], s1[3]);
-      *reinterpret_cast<float4*>(part + 1024 + wave * 256 + slot) = make_float4(s2[0], s2[1], s2[2], s2[3]);
-    }
-    if (j == 0) SB_STAMP(14);
-    __syncthreads();   // partial sums complete; nobody reads the planar image any more
-    if (j == 0) SB_STAMP(15);
-    {
-      const float t1 = part[tid] + part[256 + tid] + part[512 + tid] + part[768 + tid];
-      const float t2 = part[1024 + tid] + part[1280 + tid] + part[1536 + tid] + part[1792 + tid];
-      const float mean = t1 * (1.0f / C);
-      const float rstd = rsqrtf(fmaxf(t2 * (1.0f / C) - mean * mean, 0.0f) + LN_EPS);
-      st[tid] = rstd;
-      st[256 + tid] = -mean * rstd;
-    }
-    __syncthreads();
-    // the LayerNorm output into the [pixel][channel] image: its f16 values, or (split mode, second pass through the same
-    // bytes) their f16 remainders
-    auto write_ln = [&](bool lo_pass) {
-      T* mo = reinterpret_cast<T*>(map) + dch;
+      float* dst = reinterpret_cast<float*>(smem + dj * HW * LNP) + dch;
 #pragma unroll
       for (int yb = 0; yb < 4; ++yb)
 #pragma unroll
-        for (int xb = 0; xb < 4; ++xb) {
-          const int slot = (4 * yb + dj) * 16 + 4 * xb;
-          const float4 r4 = *reinterpret_cast<const float4*>(st + slot);
-          const float4 m4 = *reinterpret_cast<const float4*>(st + 256 + slot);
-          const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w};
-          if (yb < 3 || dj < 3) {   // row 15 is padding
+        for (int xb = 0; xb < 4; ++xb)
+          if (yb < 3 || dj < 3) {   // row 15 is padding (and lies behind the image)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
               if (xb == 3 && i == 3) continue;   // column 15 is padding
-              const float y = fmaf(fmaf(v[yb * 16 + xb * 4 + i], rr[i], mm[i]), lng, lnb2);
-              const T yh = (T)y;
-              mo[((4 * yb + dj) * HW + 4 * xb + i) * (PITCH / 2)] = lo_pass ? (T)(y - (float)yh) : yh;
+              dst[(4 * yb * HW + 4 * xb + i) * (LNP / 4)] = v[yb * 16 + xb * 4 + i];
             }
           }
-        }
-    };
-    write_ln(false);
-    SB_STAMP(5 + 5 * j);
-    __syncthreads();   // LN image complete
-    if (KEEP) {   // the LayerNorm output rows, 16-byte pieces (8 per pixel row), before the image is cleared in the MLP
-      unsigned char* dst = reinterpret_cast<unsigned char*>(a.keep_xn[j]) + (size_t)alert * P * C * 2;
-      for (int i = tid; i < P * 8; i += 256) {
-        const int p = i >> 3, c16 = i & 7;
-        *reinterpret_cast<uint4*>(dst + (size_t)p * C * 2 + 16 * c16) = *reinterpret_cast<const uint4*>(map + p * PITCH + 16 * c16);
-      }
     }
+    if (j == 0) SB_STAMP(14);
+    __syncthreads();   // fp32 image complete
+    if (j == 0) SB_STAMP(15);
 
-    // ---- fc1 -> GELU -> fc2 over 8 chunks; fc2 accumulates into x (gamma is in the filter)
+    // ---- LayerNorm in registers -> fc1 -> GELU -> fc2 over 8 chunks; fc2 accumulates into x (gamma is in the filter)
     {
+      // this lane's pixel, 32 of its 64 channels per column block in fc1's k order (k-step ks: channels 16 ks + 8 h
+      // + 0..7); the partner lane ^ 32 holds the other 32: two-pass statistics as ln_regs(); the normalised value is
+      // rounded once to the operand type (split mode: its f16 remainder from the same fp32 value)
       frag xf[2][4], xfl[X2 ? 2 : 1][4];
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+      for (int t = 0; t < 2; ++t) {
+        // (lanes of the dead pixel slots 225..255 read the last row: their values are never used)
+        const unsigned char* row = smem + (live[t] ? pix[t] : P - 1) * LNP + h * 32;
+        float xv[32];
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
-          xf[t][ks] = *reinterpret_cast<const frag*>(map + pix[t] * PITCH + ks * 32 + h * 16);
-      if (X2) {   // the remainders through the same image bytes
-        __syncthreads();
-        write_ln(true);
-        __syncthreads();
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
+          for (int q = 0; q < 2; ++q) {
+            const float4 r4 = *reinterpret_cast<const float4*>(row + ks * 64 + q * 16);
+            xv[ks * 8 + q * 4 + 0] = r4.x;
+            xv[ks * 8 + q * 4 + 1] = r4.y;
+            xv[ks * 8 + q * 4 + 2] = r4.z;
+            xv[ks * 8 + q * 4 + 3] = r4.w;
+          }
+        float s = 0.f;
 #pragma unroll
-          for (int ks = 0; ks < 4; ++ks)
-            xfl[t][ks] = *reinterpret_cast<const frag*>(map + pix[t] * PITCH + ks * 32 + h * 16);
+        for (int n = 0; n < 32; ++n) s += xv[n];
+        s += __shfl_xor(s, 32, 64);
+        const float mean = s * (1.0f / C);
+        float q2 = 0.f;
+#pragma unroll
+        for (int n = 0; n < 32; ++n) {
+          xv[n] -= mean;
+          q2 += xv[n] * xv[n];
+        }
+        q2 += __shfl_xor(q2, 32, 64);
+        const float rstd = rsqrtf(q2 * (1.0f / C) + LN_EPS);
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+#pragma unroll
+          for (int q = 0; q < 2; ++q) {
+            const float4 w4 = *reinterpret_cast<const float4*>(lnws + ks * 16 + h * 8 + q * 4);
+            const float4 b4 = *reinterpret_cast<const float4*>(lnbs + ks * 16 + h * 8 + q * 4);
+            const float ww[4] = {w4.x, w4.y, w4.z, w4.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float y = xv[ks * 8 + q * 4 + e] * rstd * ww[e] + bb[e];
+              const T yh = (T)y;
+              xf[t][ks][q * 4 + e] = yh;
+              if (X2) xfl[t][ks][q * 4 + e] = (T)(y - (float)yh);
+            }
+          }
+          if (KEEP && live[t])   // the LayerNorm output for the backward: this lane's 16-byte piece of the pixel's row
+            *reinterpret_cast<frag*>(reinterpret_cast<unsigned char*>(a.keep_xn[j]) +
+                                     ((size_t)alert * P + pix[t]) * C * 2 + ks * 32 + h * 16) = xf[t][ks];
+        }
       }
+      SB_STAMP(5 + 5 * j);   // LN done: every B operand of the MLP is in registers
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
@@ -605,10 +580,10 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
         // chunks this ring keeps ahead (the chunk time then IS the DMA latency, ~2k cycles for ~1k of work)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();   // chunk ch has landed for everyone; chunk ch-1 is read out
-        // the LN image is dead once every wave holds its xf: clear it for the next block's planar image
-        // (whose padding must read as zero) while the matrix pipe works
+        // the fp32 image is dead once every wave holds its xf (ch == 0: ring slot 2, in its tail, may be filled):
+        // clear it for the next block's planar image (whose padding must read as zero) while the matrix pipe works
         if (ch == 1 && j == 0) zero_planar();
-        const unsigned char* w1s = ring + (ch % NSLOT) * CHB;
+        const unsigned char* w1s = smem + L::slot(ch % NSLOT);
         const unsigned char* w2s = w1s + 4096;
         frag a1[4], a2[CT][2], a1l[X2 ? 4 : 1], a2l[X2 ? CT : 1][2];
 #pragma unroll
@@ -709,10 +684,10 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
     frag af[16], afl[X2 ? 16 : 1];
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) af[ks] = *reinterpret_cast<const frag*>(dw + ks * 16);
-    // (every wave loaded its xf from the last block's LN image before that MLP's second barrier)
-    constexpr int MAPB = 256 * PITCH;   // split mode: the remainder image follows (into the filter ring's bytes)
-    static_assert(2 * MAPB <= L::OFF_B1, "two [pixel][channel] images in front of the bias words");
-    if (X2) __syncthreads();            // ... which every wave must have read out
+    // (every wave loaded its xf from the last block's fp32 image before that MLP's first barrier; chunks 5..7, which
+    //  other waves may still be reading, lie at or behind byte 51200)
+    constexpr int MAPB = 256 * PITCH;   // split mode: the remainder image follows (into the second planar image's bytes)
+    static_assert(MAPB <= PLB && 2 * MAPB <= S0L<true>::OFF_RING, "the 16-bit [pixel][channel] image(s) in front of every ring slot");
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       f32x16 xn[CT];
@@ -825,7 +800,7 @@ template <typename T, bool X2 = false, int WPS = 2, bool KEEP = false> int launc
 // ---- this translation unit (stage0x.hip) holds only the split-operand instantiation: co-compiled instantiations of
 //      one kernel template share the register allocator's context and move each other's spills
 int launch_stage0b_x2(const Stage0Args& a, hipStream_t st) {
-  // (one workgroup per CU -- the two planar images and the doubled filter ring take 155 KB of LDS -- with 512 registers)
+  // (one workgroup per CU -- the two planar images and the doubled filter ring take 153 KB of LDS -- with 512 registers)
   return launch_stage0b_t<f16_t, true, 1>(a, st);
 }
 int launch_pack_s0par_x2(const float* taps, const float* dw_b, const float* ln_w, const float* ln_b, const float* b1,

@@ -15,7 +15,7 @@
 //     8-byte bank slots.  Rows outside the map are one shared zero row (per-lane row offsets), column 7 of
 //     the second quad is kept zero.  Wave = 2 channel groups x both alerts: 224 MFMAs, 88 reads per block
 //     (the VALU form this replaces: 25k cycles per block, 2 x 49 x 7 FMAs per lane plus conversions);
-//   * LayerNorm: transposing lane reduction over the 16 blocks, the 4 waves meet through LDS (stage0b.hip);
+//   * LayerNorm: transposing lane reduction over the 16 blocks, the 4 waves meet through LDS (as in dw15.hip);
 //     its 16-bit output is the MLP's B operand image, in ring slots 0..1 until the MLP has loaded it;
 //   * pointwise filters: chunks of 32 hidden units (8 KB of W1 rows + 8 KB of gamma*W2 columns) through two
 //     3-slot LDS-DMA rings straight from the plain row-major filters (waves 0, 1 load W1, waves 2, 3 load W2); the

@@ -19,14 +19,14 @@ _lib.check(_lib.lib().btsbot_debug_stamps(m._handle.ptr, C.c_void_p(buf.data_ptr
 run_model(kind, m, img, meta)
 torch.cuda.synchronize()
 t = buf.cpu().tolist()
-names = ["start", "stem/input", "b0 filters touched", "b0 DMA issued", "b0 depthwise done", "b0 DMA landed", "b0 MLP done",
-         "b1 filters touched", "b1 DMA issued", "b1 depthwise done", "b1 DMA landed", "b1 MLP done", "ds LN done", "end"]
+names = ["start", "stem/input", "b0 filters touched", "b0 DMA issued", "b0 depthwise done", "b0 LN done", "b0 MLP done",
+         "b1 filters touched", "b1 DMA issued", "b1 depthwise done", "b1 LN done", "b1 MLP done", "ds LN done", "end"]
 for base, tag in ((0, "stage0"), (16, "stage1")):
     print(tag, "total cycles", t[base + 13] - t[base])
     for i in range(1, 14):
         print(f"   {names[i]:22s} +{t[base + i] - t[base + i - 1]:8d}")
 
-print("   stage0 b0 LN detail: reductions", t[14] - t[4], " barrier", t[15] - t[14], " combine + normalise + write", t[5] - t[15])
+print("   stage0 b0 LN detail: barrier + transposing fp32 stores", t[14] - t[4], " barrier", t[15] - t[14], " row reads + LayerNorm in registers", t[5] - t[15])
 import numpy as np
 for off, tag, n in ((32, "stage0", B), (32 + 8192, "stage1", (B + 1) // 2)):
     w = np.array(t[off:off + 2 * n]).reshape(n, 2)

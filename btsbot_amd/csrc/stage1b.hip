@@ -15,15 +15,29 @@
 //     8-byte bank slots.  Rows outside the map are one shared zero row (per-lane row offsets), column 7 of
 //     the second quad is kept zero.  Wave = 2 channel groups x both alerts: 224 MFMAs, 88 reads per block
 //     (the VALU form this replaces: 25k cycles per block, 2 x 49 x 7 FMAs per lane plus conversions);
-//   * LayerNorm: transposing lane reduction over the 16 blocks, the 4 waves meet through LDS (as in dw15.hip);
-//     its 16-bit output is the MLP's B operand image, in ring slots 0..1 until the MLP has loaded it;
+//   * LayerNorm: ONE transpose -- behind a barrier that ends every wave's reads of the planar image the depthwise outputs
+//     (lane = channel, registers = pixels) go to LDS as fp32 [98 px][128 ch] with a 528-byte pitch (row p starts at bank
+//     4 p), behind a second barrier each lane reads its own pixel's 64 channels in fc1's k order and normalises them in
+//     registers (two-pass fp32 statistics, one __shfl_xor(.., 32) per sum), rounds once to the operand type and holds the
+//     MLP's B operand xf (stage0b.hip).  The image lies in bytes that are dead in that phase: ring slots 0, 1
+//     [0, 32768) and the head of the planar image [32768, 51744).  Every ring slot but W2 slot 0 lies inside it, so
+//     the first filter chunks are requested behind the barrier that ends the row reads, under the LayerNorm arithmetic;
 //   * pointwise filters: chunks of 32 hidden units (8 KB of W1 rows + 8 KB of gamma*W2 columns) through two
 //     3-slot LDS-DMA rings straight from the plain row-major filters (waves 0, 1 load W1, waves 2, 3 load W2); the
 //     per-lane source address applies the bank swizzles and the bit-2/bit-3 row swap that makes the fc1 accumulator
 //     the fc2 B operand in plain k order (stage0b.hip); fc2 accumulates into the residual registers.  The rings
-//     live in the planar image's and the LN image's bytes (dead by then).  The chunk loop is software-pipelined
+//     live in the planar image's and the fp32 LN image's bytes (dead by then).  The chunk loop is software-pipelined
 //     inside the wave: W1 fragments and the fc1 bias of chunk ch+1 are in registers before step ch starts, its fc1
 //     MFMAs issue between the GELUs of chunk ch, chunk ch's fc2 MFMAs between the second half's GELUs.
+//
+// LDS (bytes; split mode in brackets):
+//   [0, 32768)             ring slots 0, 1: W2 slots 1, 2 | the last downsample's 16-bit map(s)
+//   [32768, 67584)         planar image  [.. 102400): two]; its head doubles as W1 slots 0, 1, 2 and W2 slot 0 (4 x 8 KB
+//                          [4 x 16 KB])
+//   [0, 51744)             fp32 LN image [98][528 B], over both of the above
+//   [102400, 135168)       split mode only: W2 slots 1, 2
+//   OFF_B1   67584 [135168]  fc1 bias [512] | gamma*b2 [128], fp32
+//   OFF_LNW  70144 [137728]  LN weight [128] | LN bias [128], fp32;  end 71168 [138752]
 #include "common.h"
 #include "stage0.h"
 #include <type_traits>
@@ -65,21 +79,25 @@ constexpr int MAPB = NPX * PITCH;                 // 26656: lives in ring slots 
 constexpr int CHUNKB = 16384, HALFB = CHUNKB / 2, NCH = HID / 32, NSLOT = 3;
 // planar image of the depthwise phase: [alert][x quad 0..1][row 0..6, 7 = zeros][channel, pitch 136][4 x]
 constexpr int PL_ROW = 136 * 8, PL_XQ = 8 * PL_ROW, PL_AL = 2 * PL_XQ, PLB = G * PL_AL;   // 1088, 8704, 17408, 34816
-constexpr int OFF_PL = 2 * CHUNKB;                // ring slots 0, 1 | planar image = ring slot 2 + 18 KB
+constexpr int OFF_PL = 2 * CHUNKB;                // ring slots 0, 1 | planar image (its first 32 KB: W1 slots 0..2, W2 slot 0)
 // Split mode (X2): a second planar image behind the first (the remainders of the map the depthwise phase reads), ring slots of
 // twice the size (a filter piece's remainders 8 KB behind its heads): the W1 slots and W2 slot 0 (64 KB) lie in the two
 // planar images, W2 slots 1, 2 in a region of their own -- 142,848 bytes, one workgroup per CU.
+// fp32 [pixel][channel] image of the depthwise outputs (the block LayerNorm's input), from byte 0 over ring slots 0, 1 and
+// the head of the planar image -- all dead between the depthwise phase and the MLP.  Pitch 132 words: row p starts at
+// bank 4 p, a lane's 16-byte reads of its own row are conflict-free.
+constexpr int LNP = 4 * C + 16;                   // 528
 template <bool X2> struct S1L {
   static constexpr int PLANES = X2 ? 2 : 1;
   static constexpr int SLB = X2 ? 2 * HALFB : HALFB;            // bytes of a W1 / W2 ring slot
   static constexpr int OFF_W2X = OFF_PL + PLANES * PLB;         // X2 only: W2 slots 1, 2
   static constexpr int OFF_B1 = OFF_W2X + (X2 ? 2 * SLB : 0);   // 512 floats fc1 bias + 128 floats gamma*b2
-  static constexpr int OFF_PART = OFF_B1 + (HID + C) * 4;       // LayerNorm partial sums [2][4 waves][128 slots]
-  static constexpr int OFF_ST = OFF_PART + 2 * 4 * 128 * 4;     // (rstd, -mean * rstd) per padded pixel slot [2][128]
-  static constexpr int LDS_BYTES = OFF_ST + 2 * 128 * 4;        // 75264: two workgroups per CU / 142848
+  static constexpr int OFF_LNW = OFF_B1 + (HID + C) * 4;        // LayerNorm weight [128] | bias [128], fp32
+  static constexpr int LDS_BYTES = OFF_LNW + 2 * C * 4;         // 71168: two workgroups per CU / 138752
   static_assert(4 * SLB <= PLANES * PLB, "W1 slots + W2 slot 0 inside the planar images");
+  static_assert(NPX * LNP <= OFF_PL + PLB && NPX * LNP <= OFF_B1, "the fp32 image lies in ring slots 0, 1 + the planar image");
 };
-static_assert(MAPB <= 2 * CHUNKB && S1L<false>::LDS_BYTES <= 80 * 1024 && S1L<true>::LDS_BYTES <= 160 * 1024, "LDS layout");
+static_assert(MAPB <= 2 * CHUNKB && S1L<false>::LDS_BYTES <= 75264 && S1L<true>::LDS_BYTES <= 160 * 1024, "LDS layout");
 constexpr float LN_EPS = 1e-6f;
 // per-block parameter image in HBM (launch_pack_s1par): Toeplitz taps in the operand type
 //   [r = ky * 3 + (rb + 1)][channel][i][k] = W[channel][ky][4 rb + k - i + 3]   (0 outside the 7 taps)
@@ -102,38 +120,6 @@ template <int N> __device__ __forceinline__ void wait_vm() {
 __device__ __forceinline__ int swz4(int row) {   // F[(row >> 2) & 3], F = {0,3,2,1}
   return (4 - ((row >> 2) & 3)) & 3;
 }
-__device__ __forceinline__ float swap_add32(float a, float b) {
-  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float swap_add16(float a, float b) {
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-template <int CTRL> __device__ __forceinline__ float dpp_mov(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-// Transposing sum over the 16 blocks (lane bits 2..5) of 32 values per lane: out[0..1] = the 16-lane totals of
-// values 16 (lane >> 5) + 8 ((lane >> 4) & 1) + 4 ((lane >> 3) & 1) + 2 ((lane >> 2) & 1) + 0..1  (stage0b.hip)
-__device__ __forceinline__ void block_reduce32(float (&w)[32], int lane, float (&out)[2]) {
-#pragma unroll
-  for (int n = 0; n < 16; ++n) w[n] = swap_add32(w[n], w[n + 16]);
-#pragma unroll
-  for (int n = 0; n < 8; ++n) w[n] = swap_add16(w[n], w[n + 8]);
-  const bool b3 = (lane & 8) != 0, b2 = (lane & 4) != 0;
-#pragma unroll
-  for (int n = 0; n < 4; ++n) {
-    const float own = b3 ? w[n + 4] : w[n], send = b3 ? w[n] : w[n + 4];
-    w[n] = own + dpp_mov<0x128>(send);                       // row_ror:8 = lane ^ 8
-  }
-#pragma unroll
-  for (int n = 0; n < 2; ++n) {
-    const float own = b2 ? w[n + 2] : w[n], send = b2 ? w[n] : w[n + 2];
-    const float lo = dpp_mov<0x124>(send), hi = dpp_mov<0x12C>(send);   // row_ror:4 / :12 = lane - 4 / lane + 4
-    out[n] = own + (b2 ? lo : hi);
-  }
-}
-
 // LayerNorm over the 128 channels of this lane's pixel (x[4][16] here + the partner lane ^ 32)
 __device__ __forceinline__ void ln_regs(const f32x16 (&x)[CT], const float* __restrict__ w,
                                         const float* __restrict__ b, int h, f32x16 (&y)[CT]) {
@@ -222,18 +208,18 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
   using DT = typename std::conditional<KEEP, f16_t, T>::type;
   using frag4 = typename SCM<DT>::frag4;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* pl = smem + OFF_PL;                 // planar image; its first 16 KB double as ring slot 2
-  unsigned char* stg = smem;                         // LN image [98][PITCH] in ring slots 0..1
+  unsigned char* pl = smem + OFF_PL;                 // planar image; its first 24 KB double as the W1 ring
+  unsigned char* stg = smem;                         // the last downsample's 16-bit image [98][PITCH] in ring slots 0..1
   using L = S1L<X2>;
   constexpr int SLB = L::SLB;
   constexpr int PLO = X2 ? PLB : 0;                  // split mode: the planar image of the remainders
   float* b1s = reinterpret_cast<float*>(smem + L::OFF_B1);
   float* b2s = b1s + HID;
-  float* part = reinterpret_cast<float*>(smem + L::OFF_PART);
-  float* st = reinterpret_cast<float*>(smem + L::OFF_ST);
+  float* lnws = reinterpret_cast<float*>(smem + L::OFF_LNW);
+  float* lnbs = lnws + C;
   // filter rings, 3 slots of 8 KB each (split mode: 16 KB, the remainders behind the heads): the W1 slots and W2 slot 0
-  // lie in the planar image(s) (dead once the depthwise phase is over, so the first chunk is requested under the
-  // LayerNorm), W2 slots 1, 2 in the LN image's bytes (split mode: in a region of their own)
+  // lie in the planar image(s), W2 slots 1, 2 in ring slots 0, 1 (split mode: in a region of their own); all but W2
+  // slot 0 overlap the fp32 LayerNorm image, so the first request follows the barrier that ends its row reads
   auto w1slot = [&](int sl) { return pl + sl * SLB; };
   auto w2slot = [&](int sl) { return sl == 0 ? pl + 3 * SLB : (X2 ? smem + L::OFF_W2X : smem) + (sl - 1) * SLB; };
 
@@ -246,6 +232,8 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
   const bool live = p < nal * PA;
   const bool inmap = p < NPX;
   const int pm = inmap ? p : 0;                      // row to read for slots beyond the image
+  // this lane's row of the fp32 LayerNorm image, its half's 32 bytes of every k-step
+  const int lnrow = pm * LNP + h * 32;
   SC_STAMP(0);
   // what the live writes never touch and the depthwise products read: the zero rows and column 7
   auto zero_pads = [&]() {
@@ -312,19 +300,16 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
       for (int r = 0; r < TW_R; ++r) twl[r] = __builtin_bit_cast(frag4, twsrc[TW_BYTES / 8 + r * 512]);
     }
     const float* pf = reinterpret_cast<const float*>(bk.par + (X2 ? 2 : 1) * TW_BYTES);
-    float dwbias[2], lng[2], lnb2[2];
+    float dwbias[2];
 #pragma unroll
-    for (int gi = 0; gi < 2; ++gi) {
-      const int c = 16 * (2 * wave + gi) + db;
-      dwbias[gi] = pf[c];
-      lng[gi] = pf[C + c];
-      lnb2[gi] = pf[2 * C + c];
-    }
+    for (int gi = 0; gi < 2; ++gi) dwbias[gi] = pf[16 * (2 * wave + gi) + db];
+    const float lnv = pf[C + tid];   // LN weight [128] | LN bias [128]
     SC_STAMP(2 + 5 * j);
     __syncthreads();   // planar image complete (input / previous MLP + zero pads); ring slots 0, 1 free
     b1s[tid] = b1v0;
     b1s[256 + tid] = b1v1;
     if (tid < C) b2s[tid] = b2v;
+    lnws[tid] = lnv;
 
     // ---- pointwise filters: chunk = 32 hidden units = 16 pieces of 1 KiB, 4 per wave.
     //      pieces 0..7 : W1 rows (LDS row m <- hidden unit 32*ch + swap23(m)), 256-byte rows,
@@ -493,116 +478,101 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
         }
     }
     SC_STAMP(4 + 5 * j);   // depthwise done
-    // ---- LayerNorm over the 128 channels of a pixel: this wave's 2 groups in the lane, its 16 blocks by the
-    //      transposing lane reduction, the 4 waves through LDS; single-pass variance
+    // ---- the one transpose: the depthwise outputs (lane = channel, registers = pixels) as fp32 into the
+    //      [pixel][channel] image, which overlays the planar image that other waves may still be reading
+    __syncthreads();   // nobody reads the planar image any more
     {
-      float o1[2], o2[2];
-      {
-        float s1[32];
+      unsigned char* dst = smem + dj * (HW * LNP) + (32 * wave + db) * 4;
 #pragma unroll
-        for (int al = 0; al < G; ++al)
-#pragma unroll
-          for (int n = 0; n < 16; ++n) s1[al * 16 + n] = v[0][al][n] + v[1][al][n];
-        block_reduce32(s1, ln, o1);
-      }
-      {
-        float s2[32];
-#pragma unroll
-        for (int al = 0; al < G; ++al)
-#pragma unroll
-          for (int n = 0; n < 16; ++n) s2[al * 16 + n] = fmaf(v[0][al][n], v[0][al][n], v[1][al][n] * v[1][al][n]);
-        block_reduce32(s2, ln, o2);
-      }
-      // padded pixel slot [alert][row 0..7][column 0..7] of this lane's two totals
-      const int slot = (ln >> 5) * 64 + (4 * ((ln >> 4) & 1) + dj) * 8 + 4 * ((ln >> 3) & 1) + 2 * ((ln >> 2) & 1);
-      *reinterpret_cast<float2*>(part + wave * 128 + slot) = make_float2(o1[0], o1[1]);
-      *reinterpret_cast<float2*>(part + 512 + wave * 128 + slot) = make_float2(o2[0], o2[1]);
-    }
-    __syncthreads();   // partial sums complete; nobody reads the planar image any more
-    if (tid < 128) {
-      const float t1 = part[tid] + part[128 + tid] + part[256 + tid] + part[384 + tid];
-      const float t2 = part[512 + tid] + part[640 + tid] + part[768 + tid] + part[896 + tid];
-      const float mean = t1 * (1.0f / C);
-      const float rstd = rsqrtf(fmaxf(t2 * (1.0f / C) - mean * mean, 0.0f) + LN_EPS);
-      st[tid] = rstd;
-      st[128 + tid] = -mean * rstd;
-    }
-    __syncthreads();
-    // the LayerNorm output into the [pixel][channel] image: its f16 values, or (split mode, second pass through the same
-    // bytes) their f16 remainders
-    auto write_ln = [&](bool lo_pass) {
-#pragma unroll
-      for (int gi = 0; gi < 2; ++gi) {
-        T* mo = reinterpret_cast<T*>(stg) + 16 * (2 * wave + gi) + db;
+      for (int gi = 0; gi < 2; ++gi)
 #pragma unroll
         for (int al = 0; al < G; ++al)
 #pragma unroll
           for (int yb = 0; yb < 2; ++yb)
 #pragma unroll
-            for (int xb = 0; xb < 2; ++xb) {
-              const int slot = al * 64 + (4 * yb + dj) * 8 + 4 * xb;
-              const float4 r4 = *reinterpret_cast<const float4*>(st + slot);
-              const float4 m4 = *reinterpret_cast<const float4*>(st + 128 + slot);
-              const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w};
+            for (int xb = 0; xb < 2; ++xb)
               if (yb < 1 || dj < 3) {   // row 7 is padding
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                   if (xb == 1 && i == 3) continue;   // column 7 is padding
-                  const float y = fmaf(fmaf(v[gi][al][yb * 8 + xb * 4 + i], rr[i], mm[i]), lng[gi], lnb2[gi]);
-                  const T yh = (T)y;
-                  mo[(al * PA + (4 * yb + dj) * HW + 4 * xb + i) * (PITCH / 2)] = lo_pass ? (T)(y - (float)yh) : yh;
+                  const int col = 4 * xb + i, ofs = (al * PA + 4 * yb * HW + col) * LNP + gi * 64;
+                  *reinterpret_cast<float*>(dst + ofs) = v[gi][al][yb * 8 + xb * 4 + i];
                 }
               }
-            }
-      }
-    };
-    write_ln(false);
-    __syncthreads();   // LN image complete
-    if (KEEP) {   // the LayerNorm output rows, 16-byte pieces (16 per pixel row), before the ring takes the image's bytes
-      unsigned char* dst = reinterpret_cast<unsigned char*>(a.keep_xn[j]) + (size_t)a0 * PA * C * 2;
-      for (int i = tid; i < nal * PA * 16; i += 256) {
-        const int pp = i >> 4, c16 = i & 15;
-        *reinterpret_cast<uint4*>(dst + (size_t)pp * C * 2 + 16 * c16) = *reinterpret_cast<const uint4*>(stg + pp * PITCH + 16 * c16);
-      }
     }
-    issue(0);          // chunk 0 lives in slot 2 = the (dead) planar image's first 16 KB
-    SC_STAMP(5 + 5 * j);
+    __syncthreads();   // fp32 image complete
 
-    // ---- fc1 -> GELU -> fc2 over 16 chunks, software-pipelined inside the wave: step ch issues chunk ch+1's fc1 MFMAs
-    //      between the GELUs of chunk ch (one element per MFMA: ~7 VALU instructions pass while the matrix pipe
+    // ---- LayerNorm in registers -> fc1 -> GELU -> fc2 over 16 chunks, software-pipelined inside the wave: step ch issues
+    //      chunk ch+1's fc1 MFMAs between the GELUs of chunk ch (one element per MFMA: ~7 VALU instructions pass while the matrix pipe
     //      works on a 32-cycle product), then chunk ch's fc2 MFMAs between the second half's GELUs.  Without this a
     //      wave runs LDS reads -> 8 dependent MFMAs -> 120 VALU -> 8 MFMAs strictly one after the other (2.9k cycles per
     //      chunk).  No pipe is saturated now (MFMA 20 % busy, LDS array 31 %, VALU active in 21 % of wave-cycles): a
     //      step is ~2k cycles of which ~0.5k are barrier, fragment-read issue and LDS-DMA issue.  fc2 accumulates into x
     //      (gamma is in the filter).
-    load_x(j == 0 ? xsrc : xscr, x);
     {
+      // this lane's pixel, 64 of its 128 channels in fc1's k order (k-step ks: channels 16 ks + 8 h + 0..7); the partner
+      // lane ^ 32 holds the other 64: two-pass statistics as ln_regs(); the normalised value is rounded once to the operand
+      // type (split mode: its f16 remainder from the same fp32 value).  (LDS words are read as 16-bit vectors while an
+      // LDS-DMA may be in flight, see bias_acc.)
+      auto lds4 = [](const void* q) { return __builtin_bit_cast(f32x4, *reinterpret_cast<const bf16x8*>(q)); };
       frag xf[KS1], xfl[X2 ? KS1 : 1];
+      float xv[64];
 #pragma unroll
       for (int ks = 0; ks < KS1; ++ks)
-        xf[ks] = *reinterpret_cast<const frag*>(stg + pm * PITCH + ks * 32 + h * 16);
-      if (X2) {   // the remainders through the same image bytes
-        __syncthreads();
-        write_ln(true);
-        __syncthreads();
 #pragma unroll
-        for (int ks = 0; ks < KS1; ++ks)
-          xfl[ks] = *reinterpret_cast<const frag*>(stg + pm * PITCH + ks * 32 + h * 16);
-      }
+        for (int q = 0; q < 2; ++q) {
+          const f32x4 r4 = lds4(smem + lnrow + ks * 64 + q * 16);
 #pragma unroll
-      for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-          const float4 bv = *reinterpret_cast<const float4*>(b2s + ct * 32 + 8 * qd + 4 * h);
-          x[ct][4 * qd + 0] += bv.x;
-          x[ct][4 * qd + 1] += bv.y;
-          x[ct][4 * qd + 2] += bv.z;
-          x[ct][4 * qd + 3] += bv.w;
+          for (int e = 0; e < 4; ++e) xv[ks * 8 + q * 4 + e] = r4[e];
         }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // xf is in registers
-      __syncthreads();   // ... everyone's: the LN image's bytes may take the W2 ring's slots 1, 2
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this lane's row is in registers
+      __builtin_amdgcn_s_barrier();   // ... everyone's: the image's bytes may take the rings' other slots
+      issue(0);
       issue(1);
       if (w1wave) issue(2);
+      float s = 0.f;
+#pragma unroll
+      for (int n = 0; n < 64; ++n) s += xv[n];
+      s += __shfl_xor(s, 32, 64);
+      const float mean = s * (1.0f / C);
+      float q2 = 0.f;
+#pragma unroll
+      for (int n = 0; n < 64; ++n) {
+        xv[n] -= mean;
+        q2 += xv[n] * xv[n];
+      }
+      q2 += __shfl_xor(q2, 32, 64);
+      const float rstd = rsqrtf(q2 * (1.0f / C) + LN_EPS);
+#pragma unroll
+      for (int ks = 0; ks < KS1; ++ks) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const f32x4 w4 = lds4(lnws + ks * 16 + h * 8 + q * 4), b4 = lds4(lnbs + ks * 16 + h * 8 + q * 4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float y = xv[ks * 8 + q * 4 + e] * rstd * w4[e] + b4[e];
+            const T yh = (T)y;
+            xf[ks][q * 4 + e] = yh;
+            if (X2) xfl[X2 ? ks : 0][q * 4 + e] = (T)(y - (float)yh);
+          }
+        }
+        if (KEEP && live)   // the LayerNorm output for the backward: this lane's 16-byte piece of the pixel's row
+          *reinterpret_cast<frag*>(reinterpret_cast<unsigned char*>(a.keep_xn[j]) + ((size_t)a0 * PA + p) * C * 2 + ks * 32 +
+                                   h * 16) = xf[ks];
+      }
+      SC_STAMP(5 + 5 * j);   // LN done: every B operand of the MLP is in registers
+      // the residual, requested behind the filter requests in this wave's VM order (its 64 registers next to the row's 64
+      // spill) and not touched before the prologue has waited for all of them: first used by step 0's fc2
+      float4 xt[4 * CT];
+      __builtin_amdgcn_sched_barrier(0);
+      {
+        const float* src = j == 0 ? xsrc : xscr;
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+          for (int qd = 0; qd < 4; ++qd) xt[4 * ct + qd] = *reinterpret_cast<const float4*>(src + ct * 32 + 8 * qd + 4 * h);
+      }
+      __builtin_amdgcn_sched_barrier(0);
       // fc1 bias of chunk k into an accumulator: row (r&3) + 8(r>>2) + 4h holds hidden unit
       // 32k + (r&3) + 4((r>>2)&1) + 8h + 16(r>>3).  (Read as 16-bit vectors like the filter fragments: behind an LDS
       // read of float type hipcc waits vmcnt(0) while an LDS-DMA is in flight -- its type-based alias test takes the
@@ -637,7 +607,11 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
       f32x16 hacc[2];
       frag a1[KS1];
       {   // prologue: chunk 0's fc1, then the operands of step 0
-        wait_vm<X2 ? 8 : 4>();   // W1(0) (and x) landed; at most this wave's youngest group is still out
+        // VM order of a wave: W1 waves W1(0), W1(1), W1(2), 16 loads of x; W2 waves W2(0), W2(1), x: chunk 0 has landed
+        // once no more than W2(1) + x are out.  (Whatever else the wave issues behind chunk 0 -- the keeping forms' 8
+        // keep_xn stores, a spill store of hipcc's -- counts in vmcnt on gfx9 as well and is younger than chunk 0, so it
+        // only makes this wait stricter: the count is an upper bound and must not be tightened to the loads listed here.)
+        wait_vm<(X2 ? 8 : 4) + 16>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         bias_acc(0, hacc[0]);
@@ -651,11 +625,28 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
           hacc[0] = SCM<T>::run(a1[ks], xf[ks], hacc[0]);
         }
         __builtin_amdgcn_sched_barrier(0);
-        wait_vm<0>();   // W1(1), W1(2) / W2(1)
+        wait_vm<0>();   // W1(1), W1(2) / W2(1), x
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();   // ... for everyone, and W1 slot 0 is read out
+        __builtin_amdgcn_s_barrier();   // ... for everyone, and chunk 0's W1 slot is read out
         bias_acc(1, hacc[1]);
         read_a1(1, a1);
+        // x = residual + gamma*b2 (its first use in front of the next request: behind it hipcc's own wait for the
+        // residual would drain that request too)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+          for (int qd = 0; qd < 4; ++qd) {
+            const f32x4 bv = lds4(b2s + ct * 32 + 8 * qd + 4 * h);
+            const float4 v4 = xt[4 * ct + qd];
+            x[ct][4 * qd + 0] = (live ? v4.x : 0.f) + bv[0];
+            x[ct][4 * qd + 1] = (live ? v4.y : 0.f) + bv[1];
+            x[ct][4 * qd + 2] = (live ? v4.z : 0.f) + bv[2];
+            x[ct][4 * qd + 3] = (live ? v4.w : 0.f) + bv[3];
+          }
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) asm volatile("" : "+v"(x[ct]));
+        __builtin_amdgcn_sched_barrier(0);
         if (w1wave) issue(3);
       }
       // one step: hc = fc1 of chunk ch (complete), hn = bias of chunk ch + 1 <- fc1 of chunk ch + 1; hc <- bias of ch + 2
@@ -762,7 +753,7 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
         for (int i = 0; i < 16; ++i) a.wgt[4096 + i] = lts[i];
 #endif
       wait_vm<0>();   // the wrapped reloads: nothing may land in the ring once its bytes are reused
-      if (j == 0) {      // next block's depthwise operand; chunk 15 (slot 2 = the same bytes) must be read out first
+      if (j == 0) {      // next block's depthwise operand; chunk 15 (W1 slot 0 = the planar image's first 8 KB) must be read out first
         __syncthreads();
         zero_pads();
         if (inmap) regs_to_planar<DT, PLO, KEEP && !std::is_same<T, f16_t>::value>(x, pl, p, h);

@@ -38,6 +38,7 @@ from .pipeline import ScoreStream
 from .alert_utils import CUSTOM_COLS, alert_features, make_metadata
 from .val import REFERENCE_POLICIES, policy_eval, policy_performance
 from .triggers import TriggerState
+from .features import FeatureState
 
 __all__ = [
     "__version__", "architectures", "from_HF", "to_HF", "data", "val", "alert_utils",
@@ -45,4 +46,5 @@ __all__ = [
     "download_HF_model", "load_HF_model", "METADATA_COLS", "synthetic_batch", "ScoreStream",
     "CUSTOM_COLS", "alert_features", "make_metadata",
     "REFERENCE_POLICIES", "policy_eval", "policy_performance", "triggers", "TriggerState",
+    "features", "FeatureState",
 ]

@@ -42,6 +42,7 @@ SYMBOLS = [
     "btsbot_grad_buckets", "btsbot_wait_grad_bucket", "btsbot_allreduce_grads", "btsbot_use_workspace", "btsbot_set_option",
     "btsbot_augment", "btsbot_eval_metrics", "btsbot_prep_triplets", "btsbot_alert_features",
     "btsbot_policy_eval", "btsbot_trigger_reset", "btsbot_trigger_update", "btsbot_trigger_load",
+    "btsbot_feature_reset", "btsbot_feature_update", "btsbot_feature_load",
     "btsbot_embed_width", "btsbot_forward_embed",
 ]
 EMBEDDING = {"features": 0, "hidden": 1}   # enum btsbot_embedding
@@ -73,6 +74,14 @@ class TriggerTable(C.Structure):   # struct btsbot_trigger_table
         ("key", C.c_void_p), ("n_alerts", C.c_void_p), ("min_magpsf", C.c_void_p), ("last_jd", C.c_void_p),
         ("count", C.c_void_p), ("trigger", C.c_void_p), ("counters", C.c_void_p),
         ("capacity", C.c_int32), ("n_policies", C.c_int32),
+    ]
+
+
+class FeatureTable(C.Structure):   # struct btsbot_feature_table
+    _fields_ = [
+        ("key", C.c_void_p), ("n_alerts", C.c_void_p), ("first_jd", C.c_void_p), ("last_jd", C.c_void_p),
+        ("peak_mag", C.c_void_p), ("peak_jd", C.c_void_p), ("max_mag", C.c_void_p), ("counters", C.c_void_p),
+        ("capacity", C.c_int32),
     ]
 
 
@@ -214,6 +223,12 @@ def lib() -> C.CDLL:
                                         vp, vp]
     L.btsbot_trigger_load.restype = i32
     L.btsbot_trigger_load.argtypes = [C.POINTER(TriggerTable), i32, vp, vp, vp, vp, vp, vp, vp]
+    L.btsbot_feature_reset.restype = i32
+    L.btsbot_feature_reset.argtypes = [C.POINTER(FeatureTable), vp]
+    L.btsbot_feature_update.restype = i32
+    L.btsbot_feature_update.argtypes = [C.POINTER(FeatureTable), vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.btsbot_feature_load.restype = i32
+    L.btsbot_feature_load.argtypes = [C.POINTER(FeatureTable), i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.btsbot_eval_metrics.restype = i32
     L.btsbot_eval_metrics.argtypes = [vp, vp, f32, i64, vp, vp]
     if L.btsbot_abi_version() != ABI_VERSION:

@@ -24,6 +24,9 @@ stable device sort of the object ids; ``make_metadata`` adds the packet fields a
     feats = alert_features(object_id, jd, magpsf, jdstarthist, ncovhist, ndethist)   # device tensors -> [N,8] float32
 
 Alerts of one object with equal ``jd`` are ordered by input position (the reference's unstable sort leaves that open).
+
+On a live stream a call holds only tonight's alerts of each object: ``make_metadata(..., state=FeatureState(...))``
+continues the light curves from a per-object state on the device (features.py), keyed by ``object_keys(objectId)``.
 """
 from __future__ import annotations
 
@@ -208,7 +211,50 @@ def alert_features(object_id: torch.Tensor, jd: torch.Tensor, magpsf: torch.Tens
     return out
 
 
-def make_metadata(alerts, metadata_cols: Sequence[str], new_drb=None, device="cuda") -> torch.Tensor:
+_ZTF_LETTERS = 7
+_ZTF_YEAR = 26 ** _ZTF_LETTERS
+
+
+def object_keys(names) -> np.ndarray:
+    """A stable int64 id per ``objectId`` string, so that one object keeps its slot in a ``FeatureState`` or
+    ``TriggerState`` across calls (and across processes).  ``ZTF`` + two digits + seven letters a-z encodes exactly and
+    reversibly as yy * 26**7 + the letters read as a base-26 number (``object_names`` inverts it); any other string
+    becomes -(1 + h % (2**63 - 1)) with h the 8-byte blake2b digest of its UTF-8 bytes read as an unsigned big-endian
+    integer: negative, so it cannot collide with a ZTF code, and never the states' reserved id -2**63."""
+    import hashlib
+    out = np.empty(len(names), dtype=np.int64)
+    for i, name in enumerate(names):
+        name = str(name)
+        tail = name[5:]
+        if (len(name) == 5 + _ZTF_LETTERS and name.startswith("ZTF") and name[3:5].isascii() and name[3:5].isdigit()
+                and all("a" <= c <= "z" for c in tail)):
+            code = 0
+            for c in tail:
+                code = code * 26 + (ord(c) - ord("a"))
+            out[i] = int(name[3:5]) * _ZTF_YEAR + code
+        else:
+            h = int.from_bytes(hashlib.blake2b(name.encode("utf-8"), digest_size=8).digest(), "big")
+            out[i] = -(1 + h % (2 ** 63 - 1))
+    return out
+
+
+def object_names(keys) -> list:
+    """The ZTF names of ``object_keys``' exact codes; a key outside 0 .. 100 * 26**7 - 1 (a hashed name) raises
+    ValueError."""
+    names = []
+    for key in np.asarray(keys, dtype=np.int64).reshape(-1).tolist():
+        if not 0 <= key < 100 * _ZTF_YEAR:
+            raise ValueError(f"{key} is not the code of a ZTF name")
+        yy, code = divmod(key, _ZTF_YEAR)
+        letters = []
+        for _ in range(_ZTF_LETTERS):
+            code, r = divmod(code, 26)
+            letters.append(chr(ord("a") + r))
+        names.append(f"ZTF{yy:02d}" + "".join(reversed(letters)))
+    return names
+
+
+def make_metadata(alerts, metadata_cols: Sequence[str], new_drb=None, device="cuda", state=None) -> torch.Tensor:
     """metadata_input [N, len(metadata_cols)] float32 on ``device`` for alert packets as prep_alerts
     (alert_utils.py:333-441) takes them, columns in the order of ``metadata_cols``.
 
@@ -216,7 +262,13 @@ def make_metadata(alerts, metadata_cols: Sequence[str], new_drb=None, device="cu
     precedence (the order in which prep_alerts overwrites the frame): one of CUSTOM_COLS, computed on the device from
     objectId / jd / magpsf / jdstarthist / ncovhist / ndethist; ``"new_drb"`` when ``new_drb`` (one score per alert,
     the caller's, as it is an argument of prep_alerts) is given; a packet field (of any alert: absent elsewhere = NaN,
-    as in a DataFrame; None = NaN).  Anything else raises KeyError naming the column, before any device work."""
+    as in a DataFrame; None = NaN).  Anything else raises KeyError naming the column, before any device work.
+
+    state: a ``FeatureState`` on ``device``.  Without one the custom columns come from ``alert_features`` over the alerts
+    of this call.  With one they come from ``state.update`` on ``object_keys`` of the packets' objectIds, so they continue
+    each object's light curve from the calls before: the six causal columns are what one call over the whole stream
+    would give, ``peakmag`` / ``maxmag`` are the so-far values, and the rows of alerts the state dropped (table full)
+    carry NaN in every custom column."""
     alerts = list(alerts)
     cols = list(metadata_cols)
     n = len(alerts)
@@ -244,8 +296,11 @@ def make_metadata(alerts, metadata_cols: Sequence[str], new_drb=None, device="cu
             continue
         host[:, k] = new_drb if (c == "new_drb" and new_drb is not None) else column(c)
     if custom and n:
-        ids = {}
-        object_id = np.array([ids.setdefault(a["objectId"], len(ids)) for a in alerts], dtype=np.int64)
+        if state is None:
+            ids = {}
+            object_id = np.array([ids.setdefault(a["objectId"], len(ids)) for a in alerts], dtype=np.int64)
+        else:
+            object_id = object_keys([a["objectId"] for a in alerts])
         jd = column("jd")
         if not np.isfinite(jd).all():
             raise ValueError("make_metadata: every alert needs a finite candidate.jd")
@@ -257,7 +312,7 @@ def make_metadata(alerts, metadata_cols: Sequence[str], new_drb=None, device="cu
                     (object_id, jd, column("magpsf"), column("jdstarthist"), ncov, ndet)]
     out = torch.from_numpy(host).to(device)
     if custom and n:
-        feats = alert_features(*feats_in)
+        feats = alert_features(*feats_in) if state is None else state.update(*feats_in)["features"]
         dst = torch.tensor([k for k, c in enumerate(cols) if c in CUSTOM_COLS], device=out.device)
         src = torch.tensor([CUSTOM_COLS.index(c) for c in cols if c in CUSTOM_COLS], device=out.device)
         out[:, dst] = feats[:, src]

@@ -14,12 +14,11 @@
 //   trigger    double [n_policies][2]  (jd, magpsf) of the alert the policy fired at; (-1, -1) until it has
 // "min_magpsf <= gate" is the bright flag of every gated policy, so no flag is stored.
 //
-// Find or claim: slot = mix64(id) & (capacity - 1), linear probing with wrap-around, at most `capacity` probes; a free
-// slot is claimed with a 64-bit atomicCAS on key (a vector global atomic).  A key never changes once set, so a plain read
-// that sees another object's id may move on, and one that sees "free" is settled by the CAS.  btsbot_trigger_reset writes
-// the empty record into every slot, so a claim initialises nothing and needs no ordering beyond the CAS; the runs of one
-// launch are distinct objects, so a slot's payload has one owner per launch (payloads of earlier launches are visible
-// through stream order).  A run that finds no slot (table full) and a run of the reserved id are dropped.
+// Find or claim (object_table.h, shared with feature_state.hip): an object lives at the first slot at or after
+// mix64(id) & (capacity - 1) whose key is its id; a free slot is claimed with a 64-bit atomicCAS on key.
+// btsbot_trigger_reset writes the empty record into every slot, so a claim initialises nothing; the runs of one launch are
+// distinct objects, so a slot's payload has one owner per launch (payloads of earlier launches are visible through stream
+// order).  A run that finds no slot (table full) and a run of the reserved id are dropped.
 //
 // Update: one wave per run (run = one object's alerts of this batch, in the order of perm: (jd, input position)), one
 // alert per lane, 64 alerts per step.  What the rule needs at alert l is a prefix over lanes <= l, and each is a ballot
@@ -31,6 +30,7 @@
 // lane, once.  No LDS; four runs per workgroup; an empty run (the batch is handed over as n possibly empty runs, so that
 // the number of objects costs no host read) ends after reading its two offsets.
 #include "common.h"
+#include "object_table.h"
 
 #include <climits>
 #include <cmath>
@@ -39,7 +39,7 @@ namespace {
 
 constexpr int WG = 256, RUNS_PER_WG = WG / 64;
 constexpr int MAXP = 16;   // policies per table
-constexpr long long FREE_KEY = LLONG_MIN;
+using object_table::FREE_KEY;
 // counters: BTSBOT_TRIGGER_COUNTER_ROWS rows of 8 int64 (one cache line each) whose column sums are the counters; a
 // workgroup adds to row blockIdx.x % rows, so the waves of a large launch do not all queue at one address
 enum { C_OBJECTS = 0, C_TAKEN = 1, C_DROPPED = 2, C_LATE = 3, C_LOAD_PRESENT = 4, C_LOAD_NO_SLOT = 5 };
@@ -62,36 +62,14 @@ struct Batch {
   int n_alerts;
 };
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {   // splitmix64's finaliser
-  x ^= x >> 30;
-  x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27;
-  x *= 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 __device__ __forceinline__ void count(const btsbot_trigger_table& t, int which, long long by) {
   if (by != 0)
     atomicAdd((unsigned long long*)(t.counters + (blockIdx.x % C_ROWS) * C_STRIDE + which), (unsigned long long)by);
 }
 
 // the slot of `id` (never FREE_KEY), claimed when the id is new; -1: no free slot within `capacity` probes
-__device__ int find_or_claim(const btsbot_trigger_table& t, long long id, bool& claimed) {
-  claimed = false;
-  const unsigned mask = (unsigned)t.capacity - 1u;
-  unsigned idx = (unsigned)mix64((unsigned long long)id) & mask;
-  for (int probe = 0; probe < t.capacity; ++probe, idx = (idx + 1u) & mask) {
-    long long k = __atomic_load_n((const long long*)(t.key + idx), __ATOMIC_RELAXED);
-    if (k == FREE_KEY) {
-      k = (long long)atomicCAS((unsigned long long*)(t.key + idx), (unsigned long long)FREE_KEY, (unsigned long long)id);
-      if (k == FREE_KEY) {
-        claimed = true;
-        return (int)idx;
-      }
-    }
-    if (k == id) return (int)idx;
-  }
-  return -1;
+__device__ __forceinline__ int find_or_claim(const btsbot_trigger_table& t, long long id, bool& claimed) {
+  return object_table::find_or_claim(t.key, t.capacity, id, claimed);
 }
 
 __device__ __forceinline__ double wave_min(double v) {

@@ -607,6 +607,56 @@ int btsbot_trigger_load(const btsbot_trigger_table* table, int n_records, const 
                         const int32_t* n_alerts, const double* min_magpsf, const double* last_jd,
                         const int32_t* count, const double* trigger, void* stream);
 
+/* ---- streaming light-curve features: the columns of btsbot_alert_features with the per-object history on the device ---- */
+
+/* A table of per-object light-curve records, laid out and addressed like btsbot_trigger_table (one array per field in
+ * CALLER-OWNED device memory, open addressing with the same hash, BTSBOT_TRIGGER_FREE = free slot and reserved id; the
+ * struct itself is host memory, read before the call returns).  counters: BTSBOT_TRIGGER_COUNTER_ROWS rows of 8 int64
+ * with the trigger table's columns: the COLUMN SUMS are { objects held, alerts taken, alerts dropped, late alerts,
+ * records btsbot_feature_load found present already, records it found no slot for, 0, 0 }. */
+typedef struct btsbot_feature_table {
+  int64_t* key;         /* [capacity]  object id, BTSBOT_TRIGGER_FREE = free                                       */
+  int32_t* n_alerts;    /* [capacity]  alerts taken                                                                */
+  double* first_jd;     /* [capacity]  the smallest jd seen; +inf before                                           */
+  double* last_jd;      /* [capacity]  the largest jd seen; -inf before                                            */
+  double* peak_mag;     /* [capacity]  the smallest magpsf seen, NaN skipped; NaN until a magnitude is seen        */
+  double* peak_jd;      /* [capacity]  the jd peak_mag was first reached at; NaN with peak_mag                     */
+  double* max_mag;      /* [capacity]  the largest magpsf seen, NaN skipped; NaN until a magnitude is seen         */
+  int64_t* counters;    /* [BTSBOT_TRIGGER_COUNTER_ROWS][8]                                                        */
+  int32_t capacity;     /* slots: a power of two                                                                   */
+} btsbot_feature_table;
+
+/* Writes the empty record (free, 0, +inf, -inf, NaN, NaN, NaN) into every slot and zeroes the counters.  A new table must
+ * be reset before its first use.  One launch on `stream`. */
+int btsbot_feature_reset(const btsbot_feature_table* table, void* stream);
+
+/* One batch of n_alerts alerts into the table and their rows out of it.  perm, seg_offsets, n_runs: the grouping of
+ * btsbot_trigger_update (alert indices sorted by (object id, jd, input position); empty runs allowed; trusted device
+ * data, clamped, never validated on the host).  A run's slot is found, or claimed with a 64-bit compare-and-swap on key;
+ * then its alerts are taken in perm's order.  Alert i: n_alerts += 1; i is LATE (counted, and taken all the same) when
+ * jd[i] < last_jd; first_jd = min(first_jd, jd[i]); last_jd = max(last_jd, jd[i]); a magpsf[i] that is not NaN replaces
+ * (peak_mag, peak_jd) when it is lower, or equal with a lower jd, and max_mag when it is higher.  Then out8 float32
+ * [n_alerts][8] (16-byte aligned, input order), from the record as it stands after i = { peak_mag, max_mag, peak_mag,
+ * max_mag, jd[i] - first, jd[i] - peak_jd, peak_jd - first, ncovhist[i] - ndethist[i] } with first = min(jdstarthist[i],
+ * first_jd) (NaN if jdstarthist[i] is): columns 2-7 of btsbot_alert_features for a time-ordered stream; columns 0-1
+ * repeat the so-far values (the whole-curve values are the table's peak_mag / max_mag at the end of the stream).
+ * Compared and subtracted in float64, rounded once.  jd must be finite.
+ * A run that finds no free slot within `capacity` probes, and a run of the id BTSBOT_TRIGGER_FREE, is DROPPED: its
+ * alerts get dropped[i] = 1 and an all-NaN row, change nothing and are counted.  out8 and dropped uint8 [n_alerts] are
+ * written in full, every element by one writer.  Two updates of one table must be ordered (same stream, or events).  One
+ * launch on `stream`, no host synchronisation; n_alerts == 0 launches nothing. */
+int btsbot_feature_update(const btsbot_feature_table* table, const int32_t* perm, const int32_t* seg_offsets,
+                          int n_alerts, int n_runs, const int64_t* object_id, const double* jd, const double* magpsf,
+                          const double* jdstarthist, const int32_t* ncovhist, const int32_t* ndethist, float* out8,
+                          uint8_t* dropped, void* stream);
+
+/* Inserts n_records exported records (the fields of the table) with the same find-or-claim.  A record whose id is in
+ * the table already, or twice in the set, is not written and counted in counters column 4; one that finds no slot (or
+ * carries BTSBOT_TRIGGER_FREE) in column 5: the caller reads the counters to learn of either.  One launch on `stream`. */
+int btsbot_feature_load(const btsbot_feature_table* table, int n_records, const int64_t* object_id,
+                        const int32_t* n_alerts, const double* first_jd, const double* last_jd, const double* peak_mag,
+                        const double* peak_jd, const double* max_mag, void* stream);
+
 /* Replaces: the epoch / validation metrics of val.py:159-168 and train.py:550-558 -- out2[0] += sum_i of
  * BCEWithLogitsLoss(pos_weight) terms over n logits, out2[1] += number of alerts whose sigmoid(z) > 0.5
  * agrees with the label (caller zeroes out2 and divides by n). */

@@ -15,31 +15,22 @@
 //   peak_jd   double  the jd peak_mag was first reached at: the (magpsf, jd, taking order) minimum; NaN with peak_mag
 //   max_mag   double  the largest magpsf seen, NaN skipped; NaN until a magnitude is seen
 //
-// Find or claim: object_table.h, as in trigger_state.hip.  btsbot_feature_reset writes the empty record into every slot,
-// so a claim initialises nothing; the runs of one launch are distinct objects, so a slot's payload has one owner per
-// launch (payloads of earlier launches are visible through stream order).  A run that finds no slot (table full) and a
-// run of the reserved id are dropped: all-NaN rows, dropped = 1, nothing changes in the table.
+// The table, the walk over a grouped batch (one wave per run, one alert per lane, 64 alerts per step), the dropped runs,
+// the late scan, the counters and the load protocol are object_table.h's, shared with trigger_state.hip.  A dropped run's
+// alerts get all-NaN rows.
 //
-// Update: trigger_update_kernel's shape -- one wave per run (run = one object's alerts of this batch, in the order of
-// perm: (jd, input position)), one alert per lane, 64 alerts per step, four runs per workgroup, no LDS.  What the rule
-// needs at alert l is the record after the alerts of lanes <= l: an inclusive prefix minimum of jd, an inclusive prefix
-// maximum of magpsf and the inclusive prefix (magpsf, jd, lane) minimum, NaN magnitudes skipped -- shuffle scans of six
-// steps each (the lower lane wins a tie, which is the taking order), then combined with the carry, which is older than
-// every lane.  Late alerts take the exclusive prefix maximum of jd, as in trigger_update_kernel.  The record is wave-uniform
-// and carried from the slot into the first step, from step to step (lane 63's prefix is the step's total: lanes past the
-// run's end hold the neutral element) and back into the slot.  Every row and dropped byte is written by its own alert's
-// lane, once, the row as two float4 stores.  An empty run ends after reading its two offsets.
+// Update, what is particular to light curves: what the rule needs at alert l is the record after the alerts of lanes
+// <= l: an inclusive prefix minimum of jd, an inclusive prefix maximum of magpsf and the inclusive prefix (magpsf, jd,
+// lane) minimum, NaN magnitudes skipped -- shuffle scans of six steps each (the lower lane wins a tie, which is the taking
+// order), then combined with the carry, which is older than every lane.  From step to step lane 63's prefix is the
+// step's total: lanes past the run's end hold the neutral element.  Every row is written by its own alert's lane, once,
+// as two float4 stores.
 #include "common.h"
 #include "object_table.h"
 
 namespace {
 
-constexpr int WG = 256, RUNS_PER_WG = WG / 64;
-using object_table::FREE_KEY;
-// counters: the layout of the trigger table's (BTSBOT_TRIGGER_COUNTER_ROWS rows of 8 int64 whose column sums are the
-// counters; a workgroup adds to row blockIdx.x % rows)
-enum { C_OBJECTS = 0, C_TAKEN = 1, C_DROPPED = 2, C_LATE = 3, C_LOAD_PRESENT = 4, C_LOAD_NO_SLOT = 5 };
-constexpr int C_ROWS = BTSBOT_TRIGGER_COUNTER_ROWS, C_STRIDE = 8;
+using namespace object_table;
 
 struct Batch {
   const int32_t* perm;
@@ -53,11 +44,6 @@ struct Batch {
   uint8_t* dropped;
   int n_alerts;
 };
-
-__device__ __forceinline__ void count(const btsbot_feature_table& t, int which, long long by) {
-  if (by != 0)
-    atomicAdd((unsigned long long*)(t.counters + (blockIdx.x % C_ROWS) * C_STRIDE + which), (unsigned long long)by);
-}
 
 // the older maximum `o` against the younger `v`, NaN = none: v replaces o when it is higher
 __device__ __forceinline__ double keep_max(double o, double v) { return (o == o && !(v > o)) ? o : v; }
@@ -76,39 +62,16 @@ __global__ __launch_bounds__(WG) void feature_update_kernel(btsbot_feature_table
   const int lane = threadIdx.x & 63;
   const long run = (long)blockIdx.x * RUNS_PER_WG + (threadIdx.x >> 6);
   if (run >= n_runs) return;
-  int s = seg_offsets[run], e = seg_offsets[run + 1];
-  s = s < 0 ? 0 : s > in.n_alerts ? in.n_alerts : s;
-  e = e < 0 ? 0 : e > in.n_alerts ? in.n_alerts : e;
-  if (e <= s) return;
-
-  // ---- the run's object and its slot (lane 0 probes, every lane learns the answer)
-  int slot = -1;
-  {
-    const int a0 = in.perm[s];
-    long long id = FREE_KEY;
-    if ((unsigned)a0 < (unsigned)in.n_alerts) id = in.id[a0];
-    if (lane == 0 && id != FREE_KEY) {
-      bool claimed;
-      slot = object_table::find_or_claim(t.key, t.capacity, id, claimed);
-      if (claimed) count(t, C_OBJECTS, 1);
-    }
-    slot = __shfl(slot, 0);
-  }
-  if (slot < 0) {   // table full, or the reserved id: the run changes nothing
-    const float nan = __builtin_nanf("");
-    int n_dropped = 0;
-    for (int p = s + lane; p < e; p += 64) {
-      const int a = in.perm[p];
-      if ((unsigned)a >= (unsigned)in.n_alerts) continue;
-      in.dropped[a] = 1;
-      float4* o = reinterpret_cast<float4*>(in.out + (long)a * 8);
+  const Run r = open_run(seg_offsets, run, in.perm, in.id, in.n_alerts, t.key, t.capacity, t.counters);
+  if (r.e <= r.s) return;
+  const int slot = r.slot;
+  if (slot < 0) {   // table full, or the reserved id
+    drop_run(r.s, r.e, in.perm, in.n_alerts, in.dropped, t.counters, [out = in.out](int a) {
+      const float nan = __builtin_nanf("");
+      float4* o = reinterpret_cast<float4*>(out + (long)a * 8);
       o[0] = make_float4(nan, nan, nan, nan);
       o[1] = make_float4(nan, nan, nan, nan);
-      ++n_dropped;
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) n_dropped += __shfl_xor(n_dropped, d);
-    if (lane == 0) count(t, C_DROPPED, n_dropped);
+    });
     return;
   }
 
@@ -118,26 +81,12 @@ __global__ __launch_bounds__(WG) void feature_update_kernel(btsbot_feature_table
   double pk = t.peak_mag[slot], pkjd = t.peak_jd[slot], mx = t.max_mag[slot];
   int n_late = 0, n_taken = 0;
 
-  for (int b0 = s; b0 < e; b0 += 64) {
-    const int p = b0 + lane;
-    int a = p < e ? in.perm[p] : -1;
-    if ((unsigned)a >= (unsigned)in.n_alerts) a = -1;
-    const bool on = a >= 0;
+  for (int b0 = r.s; b0 < r.e; b0 += 64) {
+    bool on;
+    const int a = step_alert(in.perm, b0, r.e, in.n_alerts, on, n_taken);
     const double jd = on ? in.jd[a] : 0.0;
     const double mag = on ? in.mag[a] : __builtin_nan("");
-    n_taken += __popcll(__ballot(on));
-
-    // late: jd below the largest jd seen before this alert (the slot's, the earlier steps', the lower lanes')
-    double upto = on ? jd : -__builtin_inf();   // inclusive prefix maximum
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const double o = __shfl_up(upto, d);
-      if (lane >= d) upto = fmax(upto, o);
-    }
-    double before = __shfl_up(upto, 1);
-    before = lane == 0 ? last : fmax(before, last);
-    n_late += __popcll(__ballot(on && jd < before));
-    last = fmax(last, __shfl(upto, 63));
+    n_late += late_step(on, jd, last);
 
     // the record after this lane's alert: three inclusive prefixes, then the carry
     double lo = on ? jd : __builtin_inf();      // first_jd
@@ -180,8 +129,8 @@ __global__ __launch_bounds__(WG) void feature_update_kernel(btsbot_feature_table
     t.peak_mag[slot] = pk;
     t.peak_jd[slot] = pkjd;
     t.max_mag[slot] = mx;
-    count(t, C_TAKEN, n_taken);
-    count(t, C_LATE, n_late);
+    count(t.counters, C_TAKEN, n_taken);
+    count(t.counters, C_LATE, n_late);
   }
 }
 
@@ -213,18 +162,8 @@ struct Records {
 __global__ __launch_bounds__(WG) void feature_load_kernel(btsbot_feature_table t, int m, Records rec) {
   const long r = (long)blockIdx.x * WG + threadIdx.x;
   if (r >= m) return;
-  const long long oid = rec.id[r];
-  bool claimed = false;
-  const int slot = oid == FREE_KEY ? -1 : object_table::find_or_claim(t.key, t.capacity, oid, claimed);
-  if (slot < 0) {
-    count(t, C_LOAD_NO_SLOT, 1);
-    return;
-  }
-  if (!claimed) {   // in the table already, or twice in this record set: the first writer keeps the slot
-    count(t, C_LOAD_PRESENT, 1);
-    return;
-  }
-  count(t, C_OBJECTS, 1);
+  const int slot = load_claim(t.key, t.capacity, t.counters, rec.id[r]);
+  if (slot < 0) return;
   t.n_alerts[slot] = rec.n_alerts[r];
   t.first_jd[slot] = rec.first_jd[r];
   t.last_jd[slot] = rec.last_jd[r];
@@ -235,25 +174,17 @@ __global__ __launch_bounds__(WG) void feature_load_kernel(btsbot_feature_table t
 
 // NULL arrays, a capacity that is no power of two
 bool table_ok(const char* who, const btsbot_feature_table* t) {
-  if (t == nullptr || t->key == nullptr || t->n_alerts == nullptr || t->first_jd == nullptr || t->last_jd == nullptr ||
-      t->peak_mag == nullptr || t->peak_jd == nullptr || t->max_mag == nullptr || t->counters == nullptr) {
-    btsbot_set_error("%s: NULL table or NULL table array", who);
-    return false;
-  }
-  if (t->capacity < 1 || (t->capacity & (t->capacity - 1)) != 0) {
-    btsbot_set_error("%s: capacity must be a power of two, got %d", who, t->capacity);
-    return false;
-  }
-  return true;
+  using T = btsbot_feature_table;
+  return common_table_ok(who, t, &T::key, &T::n_alerts, &T::first_jd, &T::last_jd, &T::peak_mag, &T::peak_jd, &T::max_mag,
+                         &T::counters);
 }
 
 }  // namespace
 
 extern "C" int btsbot_feature_reset(const btsbot_feature_table* table, void* stream) {
   if (!table_ok("feature_reset", table)) return BTSBOT_ERR_INVALID_ARG;
-  const long blocks = ((long)table->capacity + WG - 1) / WG;
-  hipLaunchKernelGGL(feature_reset_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(WG), 0,
-                     (hipStream_t)stream, *table);
+  hipLaunchKernelGGL(feature_reset_kernel, dim3(blocks_strided(table->capacity)), dim3(WG), 0, (hipStream_t)stream,
+                     *table);
   LAUNCH_CHECK();
   return BTSBOT_OK;
 }
@@ -279,9 +210,8 @@ extern "C" int btsbot_feature_update(const btsbot_feature_table* table, const in
     return BTSBOT_ERR_INVALID_ARG;
   }
   const Batch in{perm, object_id, jd, magpsf, jdstarthist, ncovhist, ndethist, out8, dropped, n_alerts};
-  const unsigned blocks = (unsigned)(((long)n_runs + RUNS_PER_WG - 1) / RUNS_PER_WG);
-  hipLaunchKernelGGL(feature_update_kernel, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, *table, in, seg_offsets,
-                     n_runs);
+  hipLaunchKernelGGL(feature_update_kernel, dim3(blocks_per_run(n_runs)), dim3(WG), 0, (hipStream_t)stream, *table, in,
+                     seg_offsets, n_runs);
   LAUNCH_CHECK();
   return BTSBOT_OK;
 }
@@ -297,7 +227,7 @@ extern "C" int btsbot_feature_load(const btsbot_feature_table* table, int n_reco
   }
   if (n_records == 0) return BTSBOT_OK;
   const Records rec{object_id, n_alerts, first_jd, last_jd, peak_mag, peak_jd, max_mag};
-  hipLaunchKernelGGL(feature_load_kernel, dim3((unsigned)((n_records + WG - 1) / WG)), dim3(WG), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(feature_load_kernel, dim3(blocks_per_record(n_records)), dim3(WG), 0, (hipStream_t)stream,
                      *table, n_records, rec);
   LAUNCH_CHECK();
   return BTSBOT_OK;

@@ -14,21 +14,15 @@
 //   trigger    double [n_policies][2]  (jd, magpsf) of the alert the policy fired at; (-1, -1) until it has
 // "min_magpsf <= gate" is the bright flag of every gated policy, so no flag is stored.
 //
-// Find or claim (object_table.h, shared with feature_state.hip): an object lives at the first slot at or after
-// mix64(id) & (capacity - 1) whose key is its id; a free slot is claimed with a 64-bit atomicCAS on key.
-// btsbot_trigger_reset writes the empty record into every slot, so a claim initialises nothing; the runs of one launch are
-// distinct objects, so a slot's payload has one owner per launch (payloads of earlier launches are visible through stream
-// order).  A run that finds no slot (table full) and a run of the reserved id are dropped.
+// The table, the walk over a grouped batch (one wave per run, one alert per lane, 64 alerts per step), the dropped runs,
+// the late scan, the counters and the load protocol are object_table.h's, shared with feature_state.hip.  A dropped run's
+// alerts get fired = 0.
 //
-// Update: one wave per run (run = one object's alerts of this batch, in the order of perm: (jd, input position)), one
-// alert per lane, 64 alerts per step.  What the rule needs at alert l is a prefix over lanes <= l, and each is a ballot
-// away:  count so far = carry + popcount(ballot(valid_q) & lanes <= l);  bright so far = carry min <= gate, or
+// Update, what is particular to policies: what the rule needs at alert l is a prefix over lanes <= l, and each is a
+// ballot away:  count so far = carry + popcount(ballot(valid_q) & lanes <= l);  bright so far = carry min <= gate, or
 // ballot(mag <= gate_q) & lanes <= l is not empty;  the firing alert is the lowest set lane of ballot(fires_q) unless the
-// policy has fired before.  Late alerts (jd below the largest jd seen before them) take an exclusive prefix maximum, six
-// shuffles.  Counts, the minimum, the maximum and the fired mask are wave-uniform and carried from the slot into the
-// first step, from step to step, and back into the slot.  Every fired / dropped element is written by its own alert's
-// lane, once.  No LDS; four runs per workgroup; an empty run (the batch is handed over as n possibly empty runs, so that
-// the number of objects costs no host read) ends after reading its two offsets.
+// policy has fired before.  Counts, the minimum and the fired mask are wave-uniform and carried like the rest of the
+// record.  Every fired element is written by its own alert's lane, once.
 #include "common.h"
 #include "object_table.h"
 
@@ -37,13 +31,8 @@
 
 namespace {
 
-constexpr int WG = 256, RUNS_PER_WG = WG / 64;
 constexpr int MAXP = 16;   // policies per table
-using object_table::FREE_KEY;
-// counters: BTSBOT_TRIGGER_COUNTER_ROWS rows of 8 int64 (one cache line each) whose column sums are the counters; a
-// workgroup adds to row blockIdx.x % rows, so the waves of a large launch do not all queue at one address
-enum { C_OBJECTS = 0, C_TAKEN = 1, C_DROPPED = 2, C_LATE = 3, C_LOAD_PRESENT = 4, C_LOAD_NO_SLOT = 5 };
-constexpr int C_ROWS = BTSBOT_TRIGGER_COUNTER_ROWS, C_STRIDE = 8;
+using namespace object_table;
 
 struct Policies {
   double thr[MAXP], cut[MAXP], gate[MAXP];
@@ -62,16 +51,6 @@ struct Batch {
   int n_alerts;
 };
 
-__device__ __forceinline__ void count(const btsbot_trigger_table& t, int which, long long by) {
-  if (by != 0)
-    atomicAdd((unsigned long long*)(t.counters + (blockIdx.x % C_ROWS) * C_STRIDE + which), (unsigned long long)by);
-}
-
-// the slot of `id` (never FREE_KEY), claimed when the id is new; -1: no free slot within `capacity` probes
-__device__ __forceinline__ int find_or_claim(const btsbot_trigger_table& t, long long id, bool& claimed) {
-  return object_table::find_or_claim(t.key, t.capacity, id, claimed);
-}
-
 __device__ __forceinline__ double wave_min(double v) {
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) v = fmin(v, __shfl_xor(v, d));
@@ -84,38 +63,14 @@ __global__ __launch_bounds__(WG) void trigger_update_kernel(btsbot_trigger_table
   const int lane = threadIdx.x & 63;
   const long run = (long)blockIdx.x * RUNS_PER_WG + (threadIdx.x >> 6);
   if (run >= n_runs) return;
-  int s = seg_offsets[run], e = seg_offsets[run + 1];
-  s = s < 0 ? 0 : s > in.n_alerts ? in.n_alerts : s;
-  e = e < 0 ? 0 : e > in.n_alerts ? in.n_alerts : e;
-  if (e <= s) return;
-  const int np = t.n_policies;
+  const Run r = open_run(seg_offsets, run, in.perm, in.id, in.n_alerts, t.key, t.capacity, t.counters);
+  if (r.e <= r.s) return;
+  const int np = t.n_policies, slot = r.slot;
   const unsigned long long le = ~0ull >> (63 - lane);   // lanes <= this one
-
-  // ---- the run's object and its slot (lane 0 probes, every lane learns the answer)
-  int slot = -1;
-  {
-    const int a0 = in.perm[s];
-    long long id = FREE_KEY;
-    if ((unsigned)a0 < (unsigned)in.n_alerts) id = in.id[a0];
-    if (lane == 0 && id != FREE_KEY) {
-      bool claimed;
-      slot = find_or_claim(t, id, claimed);
-      if (claimed) count(t, C_OBJECTS, 1);
-    }
-    slot = __shfl(slot, 0);
-  }
-  if (slot < 0) {   // table full, or the reserved id: the run changes nothing
-    int n_dropped = 0;
-    for (int p = s + lane; p < e; p += 64) {
-      const int a = in.perm[p];
-      if ((unsigned)a >= (unsigned)in.n_alerts) continue;
-      in.dropped[a] = 1;
-      for (int q = 0; q < np; ++q) in.fired[(long)a * np + q] = 0;
-      ++n_dropped;
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) n_dropped += __shfl_xor(n_dropped, d);
-    if (lane == 0) count(t, C_DROPPED, n_dropped);
+  if (slot < 0) {   // table full, or the reserved id
+    drop_run(r.s, r.e, in.perm, in.n_alerts, in.dropped, t.counters, [fired = in.fired, np](int a) {
+      for (int q = 0; q < np; ++q) fired[(long)a * np + q] = 0;
+    });
     return;
   }
 
@@ -131,27 +86,13 @@ __global__ __launch_bounds__(WG) void trigger_update_kernel(btsbot_trigger_table
   }
   int n_late = 0, n_taken = 0;
 
-  for (int b0 = s; b0 < e; b0 += 64) {
-    const int p = b0 + lane;
-    int a = p < e ? in.perm[p] : -1;
-    if ((unsigned)a >= (unsigned)in.n_alerts) a = -1;
-    const bool on = a >= 0;
-    const double jd = on ? in.jd[a] : -__builtin_inf();
+  for (int b0 = r.s; b0 < r.e; b0 += 64) {
+    bool on;
+    const int a = step_alert(in.perm, b0, r.e, in.n_alerts, on, n_taken);
+    const double jd = on ? in.jd[a] : 0.0;
     const double mag = on ? in.mag[a] : __builtin_nan("");
     const double score = on ? (double)in.raw[a] : 0.0;
-    n_taken += __popcll(__ballot(on));
-
-    // late: jd below the largest jd seen before this alert (the slot's, the earlier steps', the lower lanes')
-    double upto = jd;   // inclusive prefix maximum
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const double o = __shfl_up(upto, d);
-      if (lane >= d) upto = fmax(upto, o);
-    }
-    double before = __shfl_up(upto, 1);
-    before = lane == 0 ? last : fmax(before, last);
-    n_late += __popcll(__ballot(on && jd < before));
-    last = fmax(last, __shfl(upto, 63));
+    n_late += late_step(on, jd, last);
 
     unsigned mine = 0;   // policies that fire at this lane's alert
 #pragma unroll
@@ -190,8 +131,8 @@ __global__ __launch_bounds__(WG) void trigger_update_kernel(btsbot_trigger_table
     t.n_alerts[slot] = n_seen + n_taken;
     t.min_magpsf[slot] = lo;
     t.last_jd[slot] = last;
-    count(t, C_TAKEN, n_taken);
-    count(t, C_LATE, n_late);
+    count(t.counters, C_TAKEN, n_taken);
+    count(t.counters, C_LATE, n_late);
   }
 #pragma unroll
   for (int q = 0; q < NP; ++q)
@@ -224,18 +165,8 @@ __global__ __launch_bounds__(WG) void trigger_load_kernel(btsbot_trigger_table t
                                                           const double* __restrict__ trigger) {
   const long r = (long)blockIdx.x * WG + threadIdx.x;
   if (r >= m) return;
-  const long long oid = id[r];
-  bool claimed = false;
-  const int slot = oid == FREE_KEY ? -1 : find_or_claim(t, oid, claimed);
-  if (slot < 0) {
-    count(t, C_LOAD_NO_SLOT, 1);
-    return;
-  }
-  if (!claimed) {   // in the table already, or twice in this record set: the first writer keeps the slot
-    count(t, C_LOAD_PRESENT, 1);
-    return;
-  }
-  count(t, C_OBJECTS, 1);
+  const int slot = load_claim(t.key, t.capacity, t.counters, id[r]);
+  if (slot < 0) return;
   t.n_alerts[slot] = n_alerts[r];
   t.min_magpsf[slot] = min_magpsf[r];
   t.last_jd[slot] = last_jd[r];
@@ -249,15 +180,9 @@ __global__ __launch_bounds__(WG) void trigger_load_kernel(btsbot_trigger_table t
 
 // NULL arrays, a capacity that is no power of two, n_policies outside 1..16
 bool table_ok(const char* who, const btsbot_trigger_table* t) {
-  if (t == nullptr || t->key == nullptr || t->n_alerts == nullptr || t->min_magpsf == nullptr || t->last_jd == nullptr ||
-      t->count == nullptr || t->trigger == nullptr || t->counters == nullptr) {
-    btsbot_set_error("%s: NULL table or NULL table array", who);
+  using T = btsbot_trigger_table;
+  if (!common_table_ok(who, t, &T::key, &T::n_alerts, &T::min_magpsf, &T::last_jd, &T::count, &T::trigger, &T::counters))
     return false;
-  }
-  if (t->capacity < 1 || (t->capacity & (t->capacity - 1)) != 0) {
-    btsbot_set_error("%s: capacity must be a power of two, got %d", who, t->capacity);
-    return false;
-  }
   if (t->n_policies < 1 || t->n_policies > MAXP) {
     btsbot_set_error("%s: n_policies must be 1..%d, got %d", who, MAXP, t->n_policies);
     return false;
@@ -270,9 +195,7 @@ bool table_ok(const char* who, const btsbot_trigger_table* t) {
 extern "C" int btsbot_trigger_reset(const btsbot_trigger_table* table, void* stream) {
   if (!table_ok("trigger_reset", table)) return BTSBOT_ERR_INVALID_ARG;
   const long cells = (long)table->capacity * table->n_policies;
-  const long blocks = (cells + WG - 1) / WG;
-  hipLaunchKernelGGL(trigger_reset_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(WG), 0,
-                     (hipStream_t)stream, *table);
+  hipLaunchKernelGGL(trigger_reset_kernel, dim3(blocks_strided(cells)), dim3(WG), 0, (hipStream_t)stream, *table);
   LAUNCH_CHECK();
   return BTSBOT_OK;
 }
@@ -307,7 +230,7 @@ extern "C" int btsbot_trigger_update(const btsbot_trigger_table* table, const do
     return BTSBOT_ERR_INVALID_ARG;
   }
   const Batch in{perm, object_id, jd, magpsf, raw_pred, fired, dropped, n_alerts};
-  const unsigned blocks = (unsigned)(((long)n_runs + RUNS_PER_WG - 1) / RUNS_PER_WG);
+  const unsigned blocks = blocks_per_run(n_runs);
   if (pol.n <= 4)
     hipLaunchKernelGGL(trigger_update_kernel<4>, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, *table, pol, in,
                        seg_offsets, n_runs);
@@ -328,7 +251,7 @@ extern "C" int btsbot_trigger_load(const btsbot_trigger_table* table, int n_reco
     return BTSBOT_ERR_INVALID_ARG;
   }
   if (n_records == 0) return BTSBOT_OK;
-  hipLaunchKernelGGL(trigger_load_kernel, dim3((unsigned)((n_records + WG - 1) / WG)), dim3(WG), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(trigger_load_kernel, dim3(blocks_per_record(n_records)), dim3(WG), 0, (hipStream_t)stream,
                      *table, n_records, object_id, n_alerts, min_magpsf, last_jd, count, trigger);
   LAUNCH_CHECK();
   return BTSBOT_OK;

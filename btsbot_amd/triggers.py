@@ -21,19 +21,13 @@ from typing import Dict, Mapping
 import torch
 
 from . import _lib
-from .alert_utils import _group_by_object
+from ._object_state import RESERVED_ID, ObjectState, _ptr   # noqa: F401  (RESERVED_ID: part of this module's names)
 from .val import POLICIES_PER_LAUNCH, REFERENCE_POLICIES, _policy_table
 
-RESERVED_ID = -(1 << 63)          # BTSBOT_TRIGGER_FREE: the free-slot marker, the one id a state cannot hold
-_COUNTERS = ("objects", "taken", "dropped", "late")
 _RECORD = ("object_id", "n_alerts", "min_magpsf", "last_jd", "count", "trigger_jd", "trigger_mag")
 
 
-def _ptr(t: torch.Tensor) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr())
-
-
-class TriggerState:
+class TriggerState(ObjectState):
     """Per-object policy state on one GPU.
 
     policies: name -> (thr, cut, k, gate or None) as for ``val.policy_eval``, 1..16 of them, fixed for the life of the
@@ -42,6 +36,7 @@ class TriggerState:
     seen) and per policy the count of valid alerts and (trigger_jd, trigger_mag), (-1, -1) until the policy has fired.
 
     Calls on one state must be ordered by the caller's streams: concurrent ``update`` calls are undefined."""
+    _RESET = "btsbot_trigger_reset"
 
     def __init__(self, policies: Mapping = REFERENCE_POLICIES, capacity: int = 1 << 20, device="cuda"):
         table = _policy_table(policies)
@@ -50,35 +45,18 @@ class TriggerState:
         for name, row in zip(policies, table.tolist()):
             if not row[2] >= 1 or row[2] != int(row[2]):
                 raise ValueError(f"policy {name!r}: k must be an integer >= 1, got {row[2]!r}")
-        if not isinstance(capacity, int) or capacity < 1 or capacity & (capacity - 1) or capacity > 1 << 30:
-            raise ValueError(f"capacity must be a power of two (at most 2^30), got {capacity!r}")
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"btsbot_amd.TriggerState runs on the GPU; there is no CPU fallback (device is {dev})")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        super().__init__(capacity, device)
+        dev = self.device
         self.policies = dict(policies)
-        self.capacity, self.device = capacity, dev
         self._policy_rows = table.contiguous()                               # host, float64 [n_pol, 4]
         npol = self.n_policies = table.shape[0]
-        self._key = torch.empty(capacity, dtype=torch.int64, device=dev)
-        self._n = torch.empty(capacity, dtype=torch.int32, device=dev)
         self._min = torch.empty(capacity, dtype=torch.float64, device=dev)
         self._last = torch.empty(capacity, dtype=torch.float64, device=dev)
         self._count = torch.empty((capacity, npol), dtype=torch.int32, device=dev)
         self._trig = torch.empty((capacity, npol, 2), dtype=torch.float64, device=dev)
-        self._counters = torch.empty((_lib.TRIGGER_COUNTER_ROWS, 8), dtype=torch.int64, device=dev)
         self._table = _lib.TriggerTable(*(t.data_ptr() for t in (self._key, self._n, self._min, self._last, self._count,
                                                                  self._trig, self._counters)), capacity, npol)
         self.reset()
-
-    def _stream(self) -> C.c_void_p:
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def reset(self) -> None:
-        """Forget every object and zero the counters (one launch, no host synchronisation)."""
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().btsbot_trigger_reset(C.byref(self._table), self._stream()), "btsbot_trigger_reset")
 
     def update(self, object_id: torch.Tensor, jd: torch.Tensor, magpsf: torch.Tensor,
                raw_preds: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -98,35 +76,18 @@ class TriggerState:
 
         No host synchronisation: two stable sorts, the offsets and one launch are queued on the current stream, and
         nothing on this path reads a device value on the host (no ``.item()``, ``.cpu()``, ``nonzero``)."""
-        cols = (object_id, jd, magpsf, raw_preds)
-        names = ("object_id", "jd", "magpsf", "raw_preds")
-        for name, t in zip(names, cols):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
-        if object_id.device.type != "cuda":
-            raise RuntimeError("btsbot_amd.TriggerState.update runs on the GPU; there is no CPU "
-                               f"fallback (object_id is on {object_id.device})")
-        n = object_id.shape[0] if object_id.dim() == 1 else -1
-        for name, t in zip(names, cols):
-            if t.dim() != 1 or t.shape[0] != n:
-                raise ValueError(f"{name} must be [{max(n, 0)}], got {tuple(t.shape)}")
-        if object_id.dtype.is_floating_point or object_id.dtype == torch.bool:
-            raise ValueError(f"object_id must be an integer tensor, got {object_id.dtype}")
+        n = self._check_batch(("object_id", "jd", "magpsf", "raw_preds"), (object_id, jd, magpsf, raw_preds))
         dev = self.device
-        if object_id.device != dev:
-            raise ValueError(f"object_id is on {object_id.device}, the state on {dev}")
         ids = object_id.to(torch.int64).contiguous()
         jd, magpsf = (t.to(device=dev, dtype=torch.float64).contiguous() for t in (jd, magpsf))
         raw = raw_preds.to(device=dev, dtype=torch.float32).contiguous()
         fired = torch.empty((n, self.n_policies), dtype=torch.uint8, device=dev)        # the kernel writes every element
         dropped = torch.empty(n, dtype=torch.uint8, device=dev)
         if n:
-            perm, offsets = _group_by_object(ids, then_by=jd)
-            with torch.cuda.device(dev):
-                _lib.check(_lib.lib().btsbot_trigger_update(
-                    C.byref(self._table), C.cast(C.c_void_p(self._policy_rows.data_ptr()), C.POINTER(C.c_double)),
-                    _ptr(perm), _ptr(offsets), n, n, _ptr(ids), _ptr(jd), _ptr(magpsf), _ptr(raw), _ptr(fired),
-                    _ptr(dropped), self._stream()), "btsbot_trigger_update")
+            perm, offsets = self._runs(ids, jd)
+            self._call("btsbot_trigger_update", C.cast(C.c_void_p(self._policy_rows.data_ptr()), C.POINTER(C.c_double)),
+                       _ptr(perm), _ptr(offsets), n, n, _ptr(ids), _ptr(jd), _ptr(magpsf), _ptr(raw), _ptr(fired),
+                       _ptr(dropped))
         return {"fired": fired.view(torch.bool), "dropped": dropped.view(torch.bool)}
 
     def new_triggers(self, object_id: torch.Tensor, jd: torch.Tensor, magpsf: torch.Tensor,
@@ -145,8 +106,7 @@ class TriggerState:
         """The objects held, in ascending id order: ``object_id``, ``n_alerts`` (int64), ``min_magpsf``, ``last_jd``,
         ``count`` int32 [n_obj, n_pol], ``pred`` int32 (``trigger_jd >= 0``), ``trigger_jd``, ``trigger_mag`` float64
         [n_obj, n_pol]; where the names are ``val.policy_eval``'s, so are shapes and dtypes.  One host read."""
-        slots = (self._key != RESERVED_ID).nonzero()[:, 0]                               # the one host read
-        slots = slots[torch.argsort(self._key[slots])]
+        slots = self._held_slots()
         trig = self._trig[slots]
         return {"object_id": self._key[slots], "n_alerts": self._n[slots].to(torch.int64), "min_magpsf": self._min[slots],
                 "last_jd": self._last[slots], "count": self._count[slots], "pred": (trig[:, :, 0] >= 0).to(torch.int32),
@@ -160,9 +120,7 @@ class TriggerState:
         comes twice, is ``RESERVED_ID``, or the records do not fit the capacity."""
         state = cls(policies, capacity, device)
         dev, npol = state.device, state.n_policies
-        missing = [k for k in _RECORD if k not in records]
-        if missing:
-            raise ValueError(f"records lack {missing}")
+        state._require(records, _RECORD)
         ids = torch.as_tensor(records["object_id"]).to(device=dev, dtype=torch.int64).contiguous()
         m = ids.shape[0] if ids.dim() == 1 else -1
         n_alerts = torch.as_tensor(records["n_alerts"]).to(device=dev, dtype=torch.int32).contiguous()
@@ -171,23 +129,7 @@ class TriggerState:
         count = torch.as_tensor(records["count"]).to(device=dev, dtype=torch.int32).contiguous()
         trig = torch.stack([torch.as_tensor(records[k]).to(device=dev, dtype=torch.float64)
                             for k in ("trigger_jd", "trigger_mag")], dim=-1).contiguous()
-        for name, t, shape in (("object_id", ids, (m,)), ("n_alerts", n_alerts, (m,)), ("min_magpsf", lo, (m,)),
-                               ("last_jd", last, (m,)), ("count", count, (m, npol)),
-                               ("trigger_jd / trigger_mag", trig, (m, npol, 2))):
-            if m < 0 or tuple(t.shape) != shape:
-                raise ValueError(f"records[{name!r}] must be {list(shape)} for {npol} policies, got {list(t.shape)}")
-        if m:
-            with torch.cuda.device(dev):
-                _lib.check(_lib.lib().btsbot_trigger_load(
-                    C.byref(state._table), m, _ptr(ids), _ptr(n_alerts), _ptr(lo), _ptr(last), _ptr(count), _ptr(trig),
-                    state._stream()), "btsbot_trigger_load")
-            present, no_slot = state._counters.sum(0)[4:6].tolist()                      # the one host read
-            if present or no_slot:
-                raise ValueError(f"from_export: {present} records carry an id that came before, {no_slot} found no slot "
-                                 f"in a table of {capacity} (or carry the reserved id)")
+        fields = (("object_id", ids, (m,)), ("n_alerts", n_alerts, (m,)), ("min_magpsf", lo, (m,)),
+                  ("last_jd", last, (m,)), ("count", count, (m, npol)), ("trigger_jd / trigger_mag", trig, (m, npol, 2)))
+        state._load("btsbot_trigger_load", m, fields, lambda shape: f"{list(shape)} for {npol} policies")
         return state
-
-    def counters(self) -> Dict[str, int]:
-        """``objects`` held, alerts ``taken``, alerts ``dropped``, ``late`` alerts since the state was made or reset (a
-        loaded record counts as an object, its alerts were taken elsewhere).  One host read."""
-        return dict(zip(_COUNTERS, self._counters.sum(0)[:4].tolist()))

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from test_alert_features_host import GOLDEN, restate
-from test_trigger_host import CHUNKS, RESERVED_ID, same_arrays
+from test_trigger_host import CHUNKS, RESERVED_ID, StreamRestatement, same_arrays
 
 NAMES = ("object_id", "jd", "magpsf", "jdstarthist", "ncovhist", "ndethist")
 EXPORTED = ("object_id", "n_alerts", "first_jd", "last_jd", "peakmag", "peak_jd", "maxmag")
@@ -168,6 +168,78 @@ def test_full_state_and_reserved_id_drop_alerts():
     assert state.counters() == dict(objects=2, taken=3, dropped=2, late=0)
     assert np.isnan(feats[dropped]).all() and list(feats[~dropped, 4]) == [1.0, 2.0, 4.0]
     assert list(feats[~dropped, 5]) == [0.0, 0.0, 3.0] and list(feats[~dropped, 7]) == [7.0] * 3
+
+
+# ---- what TriggerState and FeatureState share: the table, the drop rule, the late rule, the counters -----------------
+SHARED_CAPACITY = 8
+SHARED_EXPORT = ("object_id", "n_alerts", "last_jd")
+TRIGGER_NAMES = ("object_id", "jd", "magpsf", "raw_preds")
+
+
+def shared_batches():
+    """Five batches (the columns of both states' update) that reach every branch the two states share, for a table of
+    SHARED_CAPACITY slots and 12 distinct objects:
+      0  objects of 1, 63, 64, 65 and 129 alerts (the carry crosses no, one and two 64-alert steps), shuffled, some NaN magpsf
+      1  the empty batch
+      2  three more objects (the table is full from here on) and two alerts of the reserved id (dropped)
+      3  earlier epochs of two held objects, one run of 65: every one late against the slot's last_jd; and four new
+         objects, which find no slot (dropped)
+      4  70 alerts of a held object shuffled inside, their epochs on both sides of its last_jd: late and timely alerts in one
+         step; a new object again (dropped again)"""
+    from test_gpu_alert_features import _objects
+    rng = np.random.default_rng(41)
+
+    def with_scores(rows):
+        rows = {k: rows[k] for k in NAMES}
+        rows["raw_preds"] = rng.uniform(0, 1, len(rows["jd"])).astype(np.float32)
+        return rows
+
+    def alerts(ids, jd):
+        n = len(ids)
+        ndet = rng.integers(1, 50, n).astype(np.int32)
+        order = rng.permutation(n)
+        rows = dict(object_id=np.asarray(ids, dtype=np.int64), jd=np.asarray(jd, dtype=np.float64),
+                    magpsf=np.round(rng.uniform(17.5, 20.5, n), 2), jdstarthist=np.full(n, 2458990.5), ndethist=ndet,
+                    ncovhist=(ndet + rng.integers(0, 2000, n)).astype(np.int32))
+        return with_scores({k: v[order] for k, v in rows.items()})
+
+    first = _objects([1, 63, 64, 65, 129], seed=31)                     # ids 1000, 1007, 1014, 1021, 1028
+    first["magpsf"][::9] = np.nan
+    held63, held129 = 1007, 1028
+    lo = {o: first["jd"][first["object_id"] == o].min() for o in (held63, held129)}
+    hi129 = first["jd"][first["object_id"] == held129].max()
+    empty = {k: v[:0] for k, v in with_scores(first).items()}
+    more = alerts([2000, 2001, 2002, 2000, 2001, 2002, RESERVED_ID, RESERVED_ID], 2459400.5 + rng.uniform(0, 9, 8))
+    new = [3000, 3001, 3002, 3003]
+    earlier = alerts([held63] * 65 + [held129] * 3 + new * 2,
+                     np.concatenate([lo[held63] - rng.uniform(1, 50, 65), lo[held129] - rng.uniform(1, 50, 3),
+                                     2459400.5 + rng.uniform(0, 9, 8)]))
+    around = alerts([held129] * 70 + [3000], np.concatenate([hi129 + rng.uniform(-30, 30, 70), [2459420.5]]))
+    around["magpsf"][::8] = np.nan
+    return [with_scores(first), empty, more, earlier, around]
+
+
+def test_both_restatements_agree_on_what_the_states_share():
+    """The batches of tests/test_gpu_object_states.py through both restatements: counters, dropped flags and the exported
+    object_id, n_alerts and last_jd agree after every batch, and the batches do reach the branches they are meant to."""
+    trig, feat = StreamRestatement(capacity=SHARED_CAPACITY), FeatureStreamRestatement(capacity=SHARED_CAPACITY)
+    seen, lates = [], []
+    for b in shared_batches():
+        _, td = trig.update(*(b[k] for k in TRIGGER_NAMES))
+        _, fd = feat.update(*(b[k] for k in NAMES))
+        assert np.array_equal(td, fd) and trig.counters() == feat.counters()
+        diff = same_arrays(trig.export(), feat.export(), SHARED_EXPORT)
+        assert diff is None, diff
+        seen.append((len(b["jd"]), int(td.sum()), np.array_equal(td, b["object_id"] == RESERVED_ID)))
+        lates.append(trig.late)
+    assert seen[0] == (322, 0, True) and seen[1] == (0, 0, True) and seen[2] == (8, 2, True)
+    assert seen[3][:2] == (76, 8) and seen[4][:2] == (71, 1)
+    assert lates[:3] == [0, 0, 0] and lates[3] == 68 and 0 < lates[4] - lates[3] < 70
+    got = trig.counters()
+    assert got["objects"] == SHARED_CAPACITY and got["dropped"] == 11 and got["taken"] == 322 + 6 + 68 + 70
+    every = np.concatenate([b["object_id"] for b in shared_batches()])
+    assert len(np.unique(every)) == 12 + 1 and sorted(trig.export()["n_alerts"]) == [1, 2, 2, 2, 64, 65, 128, 202]
+    assert sum(int(np.isnan(b["magpsf"]).sum()) for b in shared_batches()) > 0
 
 
 # ---- the C entry points, argument checks only (they return before any HIP call) ------------------------------------

@@ -42,7 +42,7 @@ SYMBOLS = [
     "btsbot_grad_buckets", "btsbot_wait_grad_bucket", "btsbot_allreduce_grads", "btsbot_use_workspace", "btsbot_set_option",
     "btsbot_augment", "btsbot_eval_metrics", "btsbot_prep_triplets", "btsbot_alert_features",
     "btsbot_policy_eval", "btsbot_trigger_reset", "btsbot_trigger_update", "btsbot_trigger_load",
-    "btsbot_feature_reset", "btsbot_feature_update", "btsbot_feature_load",
+    "btsbot_trigger_rehash", "btsbot_feature_reset", "btsbot_feature_update", "btsbot_feature_load", "btsbot_feature_rehash",
     "btsbot_embed_width", "btsbot_forward_embed",
 ]
 EMBEDDING = {"features": 0, "hidden": 1}   # enum btsbot_embedding
@@ -223,12 +223,16 @@ def lib() -> C.CDLL:
                                         vp, vp]
     L.btsbot_trigger_load.restype = i32
     L.btsbot_trigger_load.argtypes = [C.POINTER(TriggerTable), i32, vp, vp, vp, vp, vp, vp, vp]
+    L.btsbot_trigger_rehash.restype = i32
+    L.btsbot_trigger_rehash.argtypes = [C.POINTER(TriggerTable), C.POINTER(TriggerTable), C.c_double, vp]
     L.btsbot_feature_reset.restype = i32
     L.btsbot_feature_reset.argtypes = [C.POINTER(FeatureTable), vp]
     L.btsbot_feature_update.restype = i32
     L.btsbot_feature_update.argtypes = [C.POINTER(FeatureTable), vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.btsbot_feature_load.restype = i32
     L.btsbot_feature_load.argtypes = [C.POINTER(FeatureTable), i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.btsbot_feature_rehash.restype = i32
+    L.btsbot_feature_rehash.argtypes = [C.POINTER(FeatureTable), C.POINTER(FeatureTable), C.c_double, vp]
     L.btsbot_eval_metrics.restype = i32
     L.btsbot_eval_metrics.argtypes = [vp, vp, f32, i64, vp, vp]
     if L.btsbot_abi_version() != ABI_VERSION:

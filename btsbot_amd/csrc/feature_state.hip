@@ -1,4 +1,4 @@
-// btsbot_feature_update / _reset / _load: the light-curve columns of alert_features.hip for a live stream.
+// btsbot_feature_update / _reset / _load / _rehash: the light-curve columns of alert_features.hip for a live stream.
 // alert_features answers "what are peakmag_so_far, maxmag_so_far, age, days_since_peak, days_to_peak of this alert" from
 // the alerts of its object that are in the same call; here the object's history is a record in a hash table on the
 // device, and one launch per batch advances the records and writes the batch's rows.  The six columns a model reads are
@@ -172,6 +172,20 @@ __global__ __launch_bounds__(WG) void feature_load_kernel(btsbot_feature_table t
   t.max_mag[slot] = rec.max_mag[r];
 }
 
+// The survivors of src (last_jd >= keep_from, or NaN) into the freshly reset dst: object_table.h's rehash_walk.
+__global__ __launch_bounds__(WG) void feature_rehash_kernel(btsbot_feature_table src, btsbot_feature_table dst,
+                                                            double keep_from) {
+  rehash_walk(src.key, src.last_jd, src.capacity, src.counters, dst.key, dst.capacity, dst.counters, keep_from,
+              [src, dst](long i, int slot) {
+                dst.n_alerts[slot] = src.n_alerts[i];
+                dst.first_jd[slot] = src.first_jd[i];
+                dst.last_jd[slot] = src.last_jd[i];
+                dst.peak_mag[slot] = src.peak_mag[i];
+                dst.peak_jd[slot] = src.peak_jd[i];
+                dst.max_mag[slot] = src.max_mag[i];
+              });
+}
+
 // NULL arrays, a capacity that is no power of two
 bool table_ok(const char* who, const btsbot_feature_table* t) {
   using T = btsbot_feature_table;
@@ -229,6 +243,16 @@ extern "C" int btsbot_feature_load(const btsbot_feature_table* table, int n_reco
   const Records rec{object_id, n_alerts, first_jd, last_jd, peak_mag, peak_jd, max_mag};
   hipLaunchKernelGGL(feature_load_kernel, dim3(blocks_per_record(n_records)), dim3(WG), 0, (hipStream_t)stream,
                      *table, n_records, rec);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+extern "C" int btsbot_feature_rehash(const btsbot_feature_table* src, const btsbot_feature_table* dst, double keep_from_jd,
+                                     void* stream) {
+  if (!table_ok("feature_rehash", src) || !table_ok("feature_rehash", dst) || !rehash_ok("feature_rehash", src, dst))
+    return BTSBOT_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(feature_rehash_kernel, dim3(blocks_strided(src->capacity)), dim3(WG), 0, (hipStream_t)stream, *src,
+                     *dst, keep_from_jd);
   LAUNCH_CHECK();
   return BTSBOT_OK;
 }

@@ -23,6 +23,12 @@
 //
 // Load: one thread per record, the same find-or-claim; the first writer keeps a slot (load_claim).
 //
+// Rehash (retention: expire, resize): nothing is ever deleted in place -- a linear-probing chain with a hole in it loses
+// the objects behind the hole, and a tombstone would be a key that changes.  The survivors of one table are inserted
+// into a second, freshly reset one, of any capacity, with the same find-or-claim (rehash_walk): one thread per source
+// slot in a grid-stride loop, key and last_jd read coalesced, the record copied by the thread that claimed its slot.
+// The source is only read, so a rehash that does not fit leaves it whole.
+//
 // Counters: C_ROWS rows of C_STRIDE int64 (one cache line each) whose column sums are the counters; a workgroup adds to
 // row blockIdx.x % C_ROWS, so the waves of a large launch do not all queue at one address.
 #pragma once
@@ -34,7 +40,16 @@ namespace object_table {
 
 constexpr long long FREE_KEY = LLONG_MIN;   // BTSBOT_TRIGGER_FREE: the key of a free slot, the one id a table cannot hold
 constexpr int WG = 256, RUNS_PER_WG = WG / 64;
-enum { C_OBJECTS = 0, C_TAKEN = 1, C_DROPPED = 2, C_LATE = 3, C_LOAD_PRESENT = 4, C_LOAD_NO_SLOT = 5 };
+enum {
+  C_OBJECTS = 0,
+  C_TAKEN = 1,
+  C_DROPPED = 2,
+  C_LATE = 3,
+  C_LOAD_PRESENT = 4,
+  C_LOAD_NO_SLOT = 5,
+  C_EXPIRED = 6,        // objects a rehash left behind
+  C_MOVE_NO_SLOT = 7    // survivors a rehash found no slot for (a smaller destination)
+};
 constexpr int C_ROWS = BTSBOT_TRIGGER_COUNTER_ROWS, C_STRIDE = 8;
 
 __device__ __forceinline__ void count(int64_t* counters, int which, long long by) {
@@ -160,6 +175,57 @@ __device__ __forceinline__ int load_claim(int64_t* key, int capacity, int64_t* c
   return slot;
 }
 
+// The sweep of a rehash: source slot i is free (nothing), expired (last_jd < keep_from, written in exactly this form: a
+// NaN last_jd is kept, a NaN or -inf keep_from expires nothing, +inf everything whose last_jd is a number) or a survivor,
+// which claims a slot of the destination and has copy(i, slot) move its record.  Source keys are distinct and the
+// destination was reset, so a survivor claims or finds no slot; one that finds its id there already (a destination that
+// was not reset) is counted with those that found none and overwrites nothing.  Each thread counts in registers, each
+// wave adds its three sums once.  Destination counters: objects = survivors moved, C_EXPIRED, C_MOVE_NO_SLOT, and the
+// source's taken, dropped, late and expired entries added row by row, so the column sums go on across the rehash.
+template <class Copy>
+__device__ __forceinline__ void rehash_walk(const int64_t* __restrict__ src_key, const double* __restrict__ src_last_jd,
+                                            int src_capacity, const int64_t* __restrict__ src_counters,
+                                            int64_t* dst_key, int dst_capacity, int64_t* dst_counters, double keep_from,
+                                            Copy copy) {
+  const long stride = (long)gridDim.x * WG;
+  const long i0 = (long)blockIdx.x * WG + threadIdx.x;
+  int n_moved = 0, n_expired = 0, n_no_slot = 0;
+  for (long i = i0; i < src_capacity; i += stride) {
+    const long long id = src_key[i];
+    const double last = src_last_jd[i];
+    if (id == FREE_KEY) continue;
+    if (last < keep_from) {
+      ++n_expired;
+      continue;
+    }
+    bool claimed;
+    const int slot = find_or_claim(dst_key, dst_capacity, id, claimed);
+    if (slot < 0 || !claimed) {
+      ++n_no_slot;
+      continue;
+    }
+    copy(i, slot);
+    ++n_moved;
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    n_moved += __shfl_xor(n_moved, d);
+    n_expired += __shfl_xor(n_expired, d);
+    n_no_slot += __shfl_xor(n_no_slot, d);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    count(dst_counters, C_OBJECTS, n_moved);
+    count(dst_counters, C_EXPIRED, n_expired);
+    count(dst_counters, C_MOVE_NO_SLOT, n_no_slot);
+  }
+  if (i0 < C_ROWS * C_STRIDE) {   // (the first workgroup; atomic, because the waves above add to C_EXPIRED too)
+    const int column = (int)(i0 % C_STRIDE);
+    const long long carried = src_counters[i0];
+    if ((column == C_TAKEN || column == C_DROPPED || column == C_LATE || column == C_EXPIRED) && carried != 0)
+      atomicAdd((unsigned long long*)(dst_counters + i0), (unsigned long long)carried);
+  }
+}
+
 // ---- host side
 // a table and each of the named arrays of it is there, and its capacity is a power of two
 template <class Table, class... Array>
@@ -170,6 +236,16 @@ bool common_table_ok(const char* who, const Table* t, Array* Table::*... arrays)
   }
   if (t->capacity < 1 || (t->capacity & (t->capacity - 1)) != 0) {
     btsbot_set_error("%s: capacity must be a power of two, got %d", who, t->capacity);
+    return false;
+  }
+  return true;
+}
+
+// what a rehash asks beyond two good tables: two different ones
+template <class Table>
+bool rehash_ok(const char* who, const Table* src, const Table* dst) {
+  if (src->key == dst->key) {
+    btsbot_set_error("%s: src and dst share the key array (a rehash is never in place)", who);
     return false;
   }
   return true;

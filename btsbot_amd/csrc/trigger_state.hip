@@ -1,4 +1,4 @@
-// btsbot_trigger_update / _reset / _load: the policies of policy_eval.hip for a live stream.  policy_eval answers "does
+// btsbot_trigger_update / _reset / _load / _rehash: the policies of policy_eval.hip for a live stream.  policy_eval answers "does
 // (thr, cut, k, gate) fire on this object, and at which alert first" for a finished split; here the per-object history is
 // a record in a hash table on the device, and one launch per scored batch advances the records and says which alerts a
 // policy fires at NOW.  A policy is monotone along a light curve (it counts valid alerts so far and asks whether anything
@@ -178,6 +178,24 @@ __global__ __launch_bounds__(WG) void trigger_load_kernel(btsbot_trigger_table t
   }
 }
 
+// The survivors of src (last_jd >= keep_from, or NaN) into the freshly reset dst, each with all its n_policies counts and
+// trigger pairs: object_table.h's rehash_walk.
+__global__ __launch_bounds__(WG) void trigger_rehash_kernel(btsbot_trigger_table src, btsbot_trigger_table dst,
+                                                            double keep_from) {
+  rehash_walk(src.key, src.last_jd, src.capacity, src.counters, dst.key, dst.capacity, dst.counters, keep_from,
+              [src, dst](long i, int slot) {
+                dst.n_alerts[slot] = src.n_alerts[i];
+                dst.min_magpsf[slot] = src.min_magpsf[i];
+                dst.last_jd[slot] = src.last_jd[i];
+                const int np = src.n_policies;
+                for (int q = 0; q < np; ++q) {
+                  dst.count[(long)slot * np + q] = src.count[i * np + q];
+                  dst.trigger[((long)slot * np + q) * 2] = src.trigger[(i * np + q) * 2];
+                  dst.trigger[((long)slot * np + q) * 2 + 1] = src.trigger[(i * np + q) * 2 + 1];
+                }
+              });
+}
+
 // NULL arrays, a capacity that is no power of two, n_policies outside 1..16
 bool table_ok(const char* who, const btsbot_trigger_table* t) {
   using T = btsbot_trigger_table;
@@ -253,6 +271,20 @@ extern "C" int btsbot_trigger_load(const btsbot_trigger_table* table, int n_reco
   if (n_records == 0) return BTSBOT_OK;
   hipLaunchKernelGGL(trigger_load_kernel, dim3(blocks_per_record(n_records)), dim3(WG), 0, (hipStream_t)stream,
                      *table, n_records, object_id, n_alerts, min_magpsf, last_jd, count, trigger);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+extern "C" int btsbot_trigger_rehash(const btsbot_trigger_table* src, const btsbot_trigger_table* dst, double keep_from_jd,
+                                     void* stream) {
+  if (!table_ok("trigger_rehash", src) || !table_ok("trigger_rehash", dst) || !rehash_ok("trigger_rehash", src, dst))
+    return BTSBOT_ERR_INVALID_ARG;
+  if (src->n_policies != dst->n_policies) {
+    btsbot_set_error("trigger_rehash: n_policies differs: src %d, dst %d", src->n_policies, dst->n_policies);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  hipLaunchKernelGGL(trigger_rehash_kernel, dim3(blocks_strided(src->capacity)), dim3(WG), 0, (hipStream_t)stream, *src,
+                     *dst, keep_from_jd);
   LAUNCH_CHECK();
   return BTSBOT_OK;
 }

@@ -32,21 +32,22 @@ _RECORD = ("object_id", "n_alerts", "first_jd", "last_jd", "peakmag", "peak_jd",
 class FeatureState(ObjectState):
     """Per-object light-curve state on one GPU.
 
-    capacity: slots of the table, a power of two (an object takes one slot for good: there is no eviction).  Per object
+    capacity: slots of the table, a power of two (an object keeps its slot until ``expire`` forgets it; ``resize`` moves
+    the records to a table of another size; an object that comes back after it was expired is a new object: its
+    ``*_so_far`` and peak columns start again, ``age`` still follows the packet's jdstarthist).  Per object
     id (any int64 but ``RESERVED_ID``) the state holds n_alerts, first_jd and last_jd (the smallest and largest jd seen),
     peakmag (the smallest magpsf seen, NaN skipped) with peak_jd (the jd it was first reached at) and maxmag.
 
     Calls on one state must be ordered by the caller's streams: concurrent ``update`` calls are undefined."""
-    _RESET = "btsbot_feature_reset"
+    _RESET, _REHASH = "btsbot_feature_reset", "btsbot_feature_rehash"
+    _ARRAYS = ("_key", "_n", "_first", "_last", "_peak", "_peak_jd", "_max", "_counters")
 
     def __init__(self, capacity: int = 1 << 20, device="cuda"):
         super().__init__(capacity, device)
-        dev = self.device
-        self._first, self._last, self._peak, self._peak_jd, self._max = (
-            torch.empty(capacity, dtype=torch.float64, device=dev) for _ in range(5))
-        self._table = _lib.FeatureTable(*(t.data_ptr() for t in (self._key, self._n, self._first, self._last, self._peak,
-                                                                 self._peak_jd, self._max, self._counters)), capacity)
-        self.reset()
+
+    def _allocate(self, capacity: int):
+        arrays = self._empty(capacity, [((), torch.float64)] * 5)
+        return arrays, _lib.FeatureTable(*(t.data_ptr() for t in arrays), capacity)
 
     def update(self, object_id: torch.Tensor, jd: torch.Tensor, magpsf: torch.Tensor, jdstarthist: torch.Tensor,
                ncovhist: torch.Tensor, ndethist: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -87,10 +88,12 @@ class FeatureState(ObjectState):
         """The objects held, in ascending id order: ``object_id``, ``n_alerts`` (int64), ``first_jd``, ``last_jd``,
         ``peakmag``, ``peak_jd``, ``maxmag`` (float64).  At the end of a stream ``peakmag`` / ``maxmag`` are columns 0-1 of
         ``alert_features`` over the whole of it.  One host read."""
-        slots = self._held_slots()
-        return {"object_id": self._key[slots], "n_alerts": self._n[slots].to(torch.int64), "first_jd": self._first[slots],
-                "last_jd": self._last[slots], "peakmag": self._peak[slots], "peak_jd": self._peak_jd[slots],
-                "maxmag": self._max[slots]}
+        return self._records(self._installed()[1], self._held_slots())
+
+    def _records(self, arrays, slots):
+        out = {"object_id": arrays[0][slots], "n_alerts": arrays[1][slots].to(torch.int64)}
+        out.update((name, t[slots]) for name, t in zip(_RECORD[2:], arrays[2:7]))
+        return out
 
     @classmethod
     def from_export(cls, records: Mapping, capacity: int = 1 << 20, device="cuda") -> "FeatureState":

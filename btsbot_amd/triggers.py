@@ -31,12 +31,15 @@ class TriggerState(ObjectState):
     """Per-object policy state on one GPU.
 
     policies: name -> (thr, cut, k, gate or None) as for ``val.policy_eval``, 1..16 of them, fixed for the life of the
-    state; capacity: slots of the table, a power of two (an object takes one slot for good: there is no eviction).  Per
-    object id (any int64 but ``RESERVED_ID``) the state holds n_alerts, min_magpsf (NaN skipped), last_jd (the largest jd
-    seen) and per policy the count of valid alerts and (trigger_jd, trigger_mag), (-1, -1) until the policy has fired.
+    state; capacity: slots of the table, a power of two (an object keeps its slot until ``expire`` forgets it; ``resize``
+    moves the records to a table of another size; an object that comes back after it was expired is a new object, on
+    which the policies may fire again).  Per object id (any int64 but ``RESERVED_ID``) the state holds n_alerts,
+    min_magpsf (NaN skipped), last_jd (the largest jd seen) and per policy the count of valid alerts and (trigger_jd,
+    trigger_mag), (-1, -1) until the policy has fired.
 
     Calls on one state must be ordered by the caller's streams: concurrent ``update`` calls are undefined."""
-    _RESET = "btsbot_trigger_reset"
+    _RESET, _REHASH = "btsbot_trigger_reset", "btsbot_trigger_rehash"
+    _ARRAYS = ("_key", "_n", "_min", "_last", "_count", "_trig", "_counters")
 
     def __init__(self, policies: Mapping = REFERENCE_POLICIES, capacity: int = 1 << 20, device="cuda"):
         table = _policy_table(policies)
@@ -45,18 +48,15 @@ class TriggerState(ObjectState):
         for name, row in zip(policies, table.tolist()):
             if not row[2] >= 1 or row[2] != int(row[2]):
                 raise ValueError(f"policy {name!r}: k must be an integer >= 1, got {row[2]!r}")
-        super().__init__(capacity, device)
-        dev = self.device
         self.policies = dict(policies)
         self._policy_rows = table.contiguous()                               # host, float64 [n_pol, 4]
-        npol = self.n_policies = table.shape[0]
-        self._min = torch.empty(capacity, dtype=torch.float64, device=dev)
-        self._last = torch.empty(capacity, dtype=torch.float64, device=dev)
-        self._count = torch.empty((capacity, npol), dtype=torch.int32, device=dev)
-        self._trig = torch.empty((capacity, npol, 2), dtype=torch.float64, device=dev)
-        self._table = _lib.TriggerTable(*(t.data_ptr() for t in (self._key, self._n, self._min, self._last, self._count,
-                                                                 self._trig, self._counters)), capacity, npol)
-        self.reset()
+        self.n_policies = table.shape[0]
+        super().__init__(capacity, device)
+
+    def _allocate(self, capacity: int):
+        npol, f64 = self.n_policies, torch.float64
+        arrays = self._empty(capacity, (((), f64), ((), f64), ((npol,), torch.int32), ((npol, 2), f64)))
+        return arrays, _lib.TriggerTable(*(t.data_ptr() for t in arrays), capacity, npol)
 
     def update(self, object_id: torch.Tensor, jd: torch.Tensor, magpsf: torch.Tensor,
                raw_preds: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -106,10 +106,13 @@ class TriggerState(ObjectState):
         """The objects held, in ascending id order: ``object_id``, ``n_alerts`` (int64), ``min_magpsf``, ``last_jd``,
         ``count`` int32 [n_obj, n_pol], ``pred`` int32 (``trigger_jd >= 0``), ``trigger_jd``, ``trigger_mag`` float64
         [n_obj, n_pol]; where the names are ``val.policy_eval``'s, so are shapes and dtypes.  One host read."""
-        slots = self._held_slots()
-        trig = self._trig[slots]
-        return {"object_id": self._key[slots], "n_alerts": self._n[slots].to(torch.int64), "min_magpsf": self._min[slots],
-                "last_jd": self._last[slots], "count": self._count[slots], "pred": (trig[:, :, 0] >= 0).to(torch.int32),
+        return self._records(self._installed()[1], self._held_slots())
+
+    def _records(self, arrays, slots):
+        key, n, lo, last, count, trig, _ = arrays
+        trig = trig[slots]
+        return {"object_id": key[slots], "n_alerts": n[slots].to(torch.int64), "min_magpsf": lo[slots],
+                "last_jd": last[slots], "count": count[slots], "pred": (trig[:, :, 0] >= 0).to(torch.int32),
                 "trigger_jd": trig[:, :, 0].contiguous(), "trigger_mag": trig[:, :, 1].contiguous()}
 
     @classmethod

@@ -9,7 +9,12 @@ alerts; a seeded ``mm_ConvNeXt`` scores them through ``btsbot.ScoreStream``; ``b
 the end the rows of all nights are compared with ``btsbot.alert_features`` over the whole stream -- the only way to the
 same metadata without the state, at a cost that grows with the history -- and ``export()`` with its whole-curve columns.
 
-    python examples/stream_features_example.py [--alerts 4096] [--nights 16] [--precision f16]
+With ``--retain-days D`` both states forget, every night, the objects they have not seen for D days (``expire``: on the
+device, no host synchronisation), which is what keeps a long-running service's tables from filling up.  An object that
+comes back after that is a new object, so the comparison with the whole stream is not made; the numbers of objects
+expired are printed instead.
+
+    python examples/stream_features_example.py [--alerts 4096] [--nights 16] [--precision f16] [--retain-days 5]
 """
 import argparse
 import os
@@ -37,6 +42,8 @@ def main():
     p.add_argument("--nights", type=int, default=16)
     p.add_argument("--precision", type=str, default="f16", choices=["f32", "bf16", "f16", "f16x2"])
     p.add_argument("--batch", type=int, default=256, help="alerts per forward")
+    p.add_argument("--retain-days", type=float, default=None,
+                   help="every night, expire the objects not seen for this many days from both states")
     args = p.parse_args()
     dev = torch.device("cuda:0")
 
@@ -63,6 +70,9 @@ def main():
     night = torch.floor(jd - 2459000.5).long()
     seen_rows, seen_feats = [], []
     for k in range(int(night.max().item()) + 1):
+        if args.retain_days is not None:
+            feats.expire(2459000.5 + k - args.retain_days)
+            state.expire(2459000.5 + k - args.retain_days)
         rows = (night == k).nonzero()[:, 0]
         if rows.numel() == 0:
             continue
@@ -81,6 +91,10 @@ def main():
 
     print("feature counters:", feats.counters())
     print("trigger counters:", state.counters())
+    if args.retain_days is not None:
+        print(f"expired after {args.retain_days:g} quiet days: {feats.n_expired()} objects from the feature state, "
+              f"{state.n_expired()} from the trigger state (an object that came back was made afresh)")
+        return
     rows, got = torch.cat(seen_rows), torch.cat(seen_feats)
     want = btsbot.alert_features(object_id, jd, magpsf, jdstarthist, ncovhist, ndethist)
     if not same(got[:, 2:], want[rows][:, 2:]):

@@ -560,7 +560,8 @@ int btsbot_policy_eval(const int32_t* perm, const int32_t* seg_offsets, int n_al
  * hash(id) & (capacity - 1), wrapping round, whose key is its id.  The struct itself is host memory, passed by pointer
  * and read before the call returns.
  * counters: BTSBOT_TRIGGER_COUNTER_ROWS rows of 8 int64; the COLUMN SUMS are { objects held, alerts taken, alerts
- * dropped, late alerts, records btsbot_trigger_load found present already, records it found no slot for, 0, 0 }. */
+ * dropped, late alerts, records btsbot_trigger_load found present already, records it found no slot for, objects
+ * btsbot_trigger_rehash expired, survivors it found no slot for }. */
 #define BTSBOT_TRIGGER_FREE INT64_MIN     /* key of a free slot: the one object id a table cannot hold             */
 #define BTSBOT_TRIGGER_COUNTER_ROWS 16
 typedef struct btsbot_trigger_table {
@@ -607,13 +608,29 @@ int btsbot_trigger_load(const btsbot_trigger_table* table, int n_records, const 
                         const int32_t* n_alerts, const double* min_magpsf, const double* last_jd,
                         const int32_t* count, const double* trigger, void* stream);
 
+/* Retention: the objects of src whose last_jd is not below keep_from_jd (a record is EXPIRED when last_jd < keep_from_jd,
+ * in exactly this form: a NaN last_jd is kept, a NaN or -inf keep_from_jd expires nothing, +inf every record whose
+ * last_jd is a number) are inserted, whole, into dst with the same find-or-claim; dst may have any capacity, so this
+ * is also the way to a larger or smaller table.  Nothing is deleted in place: src is only read.  dst MUST HAVE BEEN
+ * RESET by the caller (btsbot_trigger_reset, ordered before this call) and must share no array with src; its n_policies
+ * must be src's.  Afterwards dst's counters column 0 is the number of survivors moved, column 6 the number of objects
+ * expired plus src's column 6, column 7 the number of survivors that found no slot (only a smaller dst can run out; the
+ * caller reads the counters to learn of it, and src is still whole), and columns 1-3 (taken, dropped, late) are src's,
+ * carried over row by row.  An object that comes back after it was expired is a new object: its policies may fire again.
+ * Ordered with the updates of both tables like two updates (same stream, or events).  One launch on `stream`, no
+ * allocation, no host synchronisation.  BTSBOT_ERR_INVALID_ARG before any launch: a NULL table or table array, a
+ * capacity that is no power of two, src and dst sharing `key`, n_policies differing. */
+int btsbot_trigger_rehash(const btsbot_trigger_table* src, const btsbot_trigger_table* dst, double keep_from_jd,
+                          void* stream);
+
 /* ---- streaming light-curve features: the columns of btsbot_alert_features with the per-object history on the device ---- */
 
 /* A table of per-object light-curve records, laid out and addressed like btsbot_trigger_table (one array per field in
  * CALLER-OWNED device memory, open addressing with the same hash, BTSBOT_TRIGGER_FREE = free slot and reserved id; the
  * struct itself is host memory, read before the call returns).  counters: BTSBOT_TRIGGER_COUNTER_ROWS rows of 8 int64
  * with the trigger table's columns: the COLUMN SUMS are { objects held, alerts taken, alerts dropped, late alerts,
- * records btsbot_feature_load found present already, records it found no slot for, 0, 0 }. */
+ * records btsbot_feature_load found present already, records it found no slot for, objects btsbot_feature_rehash
+ * expired, survivors it found no slot for }. */
 typedef struct btsbot_feature_table {
   int64_t* key;         /* [capacity]  object id, BTSBOT_TRIGGER_FREE = free                                       */
   int32_t* n_alerts;    /* [capacity]  alerts taken                                                                */
@@ -656,6 +673,16 @@ int btsbot_feature_update(const btsbot_feature_table* table, const int32_t* perm
 int btsbot_feature_load(const btsbot_feature_table* table, int n_records, const int64_t* object_id,
                         const int32_t* n_alerts, const double* first_jd, const double* last_jd, const double* peak_mag,
                         const double* peak_jd, const double* max_mag, void* stream);
+
+/* Retention, as btsbot_trigger_rehash: the records of src with last_jd >= keep_from_jd (or NaN) into dst, which MUST
+ * HAVE BEEN RESET by the caller (btsbot_feature_reset) and shares no array with src; any capacity.  src is only read.
+ * dst's counters: column 0 survivors moved, column 6 objects expired (plus src's), column 7 survivors that found no
+ * slot, columns 1-3 carried over from src.  An object that comes back after it was expired is a new object: its
+ * so-far and peak columns start again (age still follows the packet's jdstarthist).  One launch on `stream`, no
+ * allocation, no host synchronisation.  BTSBOT_ERR_INVALID_ARG before any launch: a NULL table or table array, a
+ * capacity that is no power of two, src and dst sharing `key`. */
+int btsbot_feature_rehash(const btsbot_feature_table* src, const btsbot_feature_table* dst, double keep_from_jd,
+                          void* stream);
 
 /* Replaces: the epoch / validation metrics of val.py:159-168 and train.py:550-558 -- out2[0] += sum_i of
  * BCEWithLogitsLoss(pos_weight) terms over n logits, out2[1] += number of alerts whose sigmoid(z) > 0.5

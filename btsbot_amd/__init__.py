@@ -22,6 +22,7 @@ from . import to_HF
 from . import data
 from . import val
 from . import alert_utils
+from . import splits
 from .architectures import (
     MaxViT,
     ConvNeXt,
@@ -39,6 +40,8 @@ from .alert_utils import CUSTOM_COLS, alert_features, make_metadata
 from .val import REFERENCE_POLICIES, policy_eval, policy_performance
 from .triggers import TriggerState
 from .features import FeatureState
+from .splits import (SOURCE_SETS, SPLIT_NAMES, create_subset, cut_set_and_assign_splits, cuts_suffix, label_set,
+                     merge_sets_across_split, split_labels, subsample_data, subset_mask)
 
 __all__ = [
     "__version__", "architectures", "from_HF", "to_HF", "data", "val", "alert_utils",
@@ -47,4 +50,6 @@ __all__ = [
     "CUSTOM_COLS", "alert_features", "make_metadata",
     "REFERENCE_POLICIES", "policy_eval", "policy_performance", "triggers", "TriggerState",
     "features", "FeatureState",
+    "splits", "SPLIT_NAMES", "SOURCE_SETS", "label_set", "split_labels", "subset_mask", "cuts_suffix",
+    "cut_set_and_assign_splits", "merge_sets_across_split", "create_subset", "subsample_data",
 ]

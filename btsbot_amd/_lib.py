@@ -41,6 +41,7 @@ SYMBOLS = [
     "btsbot_reserve_train", "btsbot_forward_train", "btsbot_backward", "btsbot_debug_stamps",
     "btsbot_grad_buckets", "btsbot_wait_grad_bucket", "btsbot_allreduce_grads", "btsbot_use_workspace", "btsbot_set_option",
     "btsbot_augment", "btsbot_eval_metrics", "btsbot_prep_triplets", "btsbot_alert_features",
+    "btsbot_split_labels",
     "btsbot_policy_eval", "btsbot_trigger_reset", "btsbot_trigger_update", "btsbot_trigger_load",
     "btsbot_trigger_rehash", "btsbot_feature_reset", "btsbot_feature_update", "btsbot_feature_load", "btsbot_feature_rehash",
     "btsbot_embed_width", "btsbot_forward_embed",
@@ -214,6 +215,8 @@ def lib() -> C.CDLL:
     L.btsbot_prep_triplets.argtypes = [vp, vp, vp, vp, i32, i32, vp]
     L.btsbot_alert_features.restype = i32
     L.btsbot_alert_features.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.btsbot_split_labels.restype = i32
+    L.btsbot_split_labels.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.btsbot_policy_eval.restype = i32
     L.btsbot_policy_eval.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_double), i32, vp, vp, vp, vp]
     L.btsbot_trigger_reset.restype = i32

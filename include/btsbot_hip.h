@@ -553,6 +553,25 @@ int btsbot_policy_eval(const int32_t* perm, const int32_t* seg_offsets, int n_al
                        const double* policies, int n_policies, int32_t* obj_pred, double* obj_trigger,
                        double* obj_info, void* stream);
 
+/* Replaces: the per-object loops of cut_set_and_assign_splits and create_subset (query_data/train_val_test_split.py:
+ * 123-140, 211-231) for a table of n_alerts alerts grouped by object exactly as for btsbot_alert_features (perm,
+ * seg_offsets, n_objects may be an upper bound with empty objects; trusted device data, clamped, perm entries outside
+ * [0, n_alerts) skipped, never validated on the host).  With O(i) the alerts of i's object, one row per alert in input
+ * order, each written by one thread:
+ *   pos int32       the alerts of O(i) with a smaller index (i's position in the object, in table order)
+ *   size int32      |O(i)|
+ *   first_row int32 the smallest index of O(i) (the row of the object's first appearance)
+ *   later int32     the alerts j of O(i) with (jd[j], j) > (jd[i], i): per object a permutation of 0 .. size - 1.  A
+ *                   NaN jd counts as later than every finite jd; NaN jd among themselves are ordered by index
+ *   is_rise uint8   jd[i] <= jd[m], m the lowest index of O(i) at O(i)'s minimum non-NaN magpsf (ties of the minimum go
+ *                   to the lowest row, not the lowest jd); 0 when every magpsf of the object is NaN, or jd[i] or jd[m] is
+ *   peakmag double  that minimum, NaN if none
+ * Compared in float64 (compare-and-select), nothing is rounded.  One launch on `stream`, no atomics, no host
+ * synchronisation; n_alerts == 0 launches nothing. */
+int btsbot_split_labels(const int32_t* perm, const int32_t* seg_offsets, int n_alerts, int n_objects, const double* jd,
+                        const double* magpsf, int32_t* pos, int32_t* size, int32_t* first_row, int32_t* later,
+                        uint8_t* is_rise, double* peakmag, void* stream);
+
 /* ---- streaming policy triggers: the rule of btsbot_policy_eval with the per-object history kept on the device ---- */
 
 /* A table of per-object records, one array per field, in CALLER-OWNED device memory (the entry points below never

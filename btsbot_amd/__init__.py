@@ -36,7 +36,7 @@ from .architectures import (
 from .from_HF import download_HF_model, load_HF_model
 from .synthetic import METADATA_COLS, synthetic_batch
 from .pipeline import ScoreStream
-from .alert_utils import CUSTOM_COLS, alert_features, make_metadata
+from .alert_utils import CUSTOM_COLS, alert_features, decode_stamps_device, make_metadata, make_triplets
 from .val import REFERENCE_POLICIES, policy_eval, policy_performance
 from .triggers import TriggerState
 from .features import FeatureState
@@ -47,7 +47,7 @@ __all__ = [
     "__version__", "architectures", "from_HF", "to_HF", "data", "val", "alert_utils",
     "MaxViT", "ConvNeXt", "mm_MaxViT", "mm_ConvNeXt", "mm_cnn", "um_cnn", "um_nn", "frozen_fusion",
     "download_HF_model", "load_HF_model", "METADATA_COLS", "synthetic_batch", "ScoreStream",
-    "CUSTOM_COLS", "alert_features", "make_metadata",
+    "CUSTOM_COLS", "alert_features", "make_metadata", "make_triplets", "decode_stamps_device",
     "REFERENCE_POLICIES", "policy_eval", "policy_performance", "triggers", "TriggerState",
     "features", "FeatureState",
     "splits", "SPLIT_NAMES", "SOURCE_SETS", "label_set", "split_labels", "subset_mask", "cuts_suffix",

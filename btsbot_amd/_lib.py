@@ -41,12 +41,16 @@ SYMBOLS = [
     "btsbot_reserve_train", "btsbot_forward_train", "btsbot_backward", "btsbot_debug_stamps",
     "btsbot_grad_buckets", "btsbot_wait_grad_bucket", "btsbot_allreduce_grads", "btsbot_use_workspace", "btsbot_set_option",
     "btsbot_augment", "btsbot_eval_metrics", "btsbot_prep_triplets", "btsbot_alert_features",
-    "btsbot_split_labels",
+    "btsbot_split_labels", "btsbot_decode_stamps_workspace", "btsbot_decode_stamps",
     "btsbot_policy_eval", "btsbot_trigger_reset", "btsbot_trigger_update", "btsbot_trigger_load",
     "btsbot_trigger_rehash", "btsbot_feature_reset", "btsbot_feature_update", "btsbot_feature_load", "btsbot_feature_rehash",
     "btsbot_embed_width", "btsbot_forward_embed",
 ]
 EMBEDDING = {"features": 0, "hidden": 1}   # enum btsbot_embedding
+# enum btsbot_stamp_status: what btsbot_decode_stamps says of each stamp
+STAMP_STATUS = {"OK": 0, "BAD_GZIP": 1, "BAD_DEFLATE": 2, "TOO_LARGE": 3, "BAD_TRAILER": 4, "BAD_FITS": 5,
+                "UNSUPPORTED": 6}
+STAMP_CAP = 28800   # BTSBOT_STAMP_CAP
 
 
 class Config(C.Structure):
@@ -217,6 +221,10 @@ def lib() -> C.CDLL:
     L.btsbot_alert_features.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.btsbot_split_labels.restype = i32
     L.btsbot_split_labels.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.btsbot_decode_stamps_workspace.restype = i64
+    L.btsbot_decode_stamps_workspace.argtypes = [i32]
+    L.btsbot_decode_stamps.restype = i32
+    L.btsbot_decode_stamps.argtypes = [vp, vp, i32, vp, vp, vp, vp, i64, vp]
     L.btsbot_policy_eval.restype = i32
     L.btsbot_policy_eval.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_double), i32, vp, vp, vp, vp]
     L.btsbot_trigger_reset.restype = i32

@@ -5,11 +5,12 @@
     scores = torch.sigmoid(model(image_input=triplets[~drop], metadata_input=meta[~drop]))
 
 Images.  ``make_triplet`` there gunzips and FITS-decodes the three stamps of an alert on the host (astropy),
-then masks NaNs, L2-normalises, flags corrupted stamps and pads to 63x63.  Here the decoding is a
+then masks NaNs, L2-normalises, flags corrupted stamps and pads to 63x63.  Here the decoding is by default a
 dependency-free host step (``decode_stamp``: gzip + the primary HDU of a FITS image -- ZTF cutouts are
 single-HDU BITPIX = -32 images) and everything after it is one kernel (``btsbot_prep_triplets``) over a
 whole night's batch, writing the float32 NCHW tensor the classifier consumes
-(inference_example.py:62-64) without the float64 NHWC detour.
+(inference_example.py:62-64) without the float64 NHWC detour.  ``make_triplets(..., decode="device")`` runs the
+decoding on the GPU as well (``decode_stamps_device``: one upload, one launch of ``btsbot_decode_stamps``).
 
     # from stamps decoded elsewhere:
     raw, shapes = stack_stamps(list_of_(science, template, difference)_arrays)
@@ -91,11 +92,102 @@ def decode_alert(alert) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     return tuple(decode_stamp(alert[f"cutout{c}"]["stampData"]) for c in ("Science", "Template", "Difference"))
 
 
-def make_triplets(alerts, device="cuda", normalize: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
-    """make_triplet (alert_utils.py:110-196) over a batch of alert packets: host decode, then the arithmetic
-    on ``device`` in one launch.  Returns (triplets [B,3,63,63] float32 NCHW, drop [B] bool)."""
-    raw, shapes = stack_stamps([decode_alert(a) for a in alerts])
-    return prep_triplets(raw.to(device), shapes.to(device), normalize)
+_STAMP_KEYS = ("cutoutScience", "cutoutTemplate", "cutoutDifference")
+STAMP_STATUS = _lib.STAMP_STATUS
+
+
+def _cuda_device(device, what: str) -> torch.device:
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"btsbot_amd.alert_utils.{what} runs on the GPU; there is no CPU fallback (device is {dev})")
+    return dev
+
+
+def decode_stamps_device(stamps, device="cuda") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``stampData`` fields (a sequence of bytes-like objects) -> (raw [n,63,63] float32, shapes [n,2] int32 = (h, w),
+    status [n] uint8) on ``device``: gunzip and FITS decode of the whole batch in one launch (``btsbot_decode_stamps``).
+
+    raw holds each image in native float32 in the top-left h x w corner, zero elsewhere -- ``stack_stamps``' layout, so
+    ``raw.view(-1, 3, 63, 63)`` / ``shapes.view(-1, 3, 2)`` go straight into ``prep_triplets``.  ``status`` is one of
+    ``STAMP_STATUS`` per stamp; a stamp with a non-zero status has an all-zero image and shape (0, 0).  The device decodes
+    a single gzip member (stored, fixed and dynamic deflate blocks) that inflates to at most 28,800 bytes and holds a
+    FITS primary image with SIMPLE = T, NAXIS = 2, BITPIX = -32, axes of 1 .. 63, no BSCALE / BZERO; anything else that is
+    well formed is ``UNSUPPORTED`` and left to ``decode_stamp``.  Unlike ``gzip.decompress`` it does not verify the CRC32
+    of the gzip trailer (it does verify ISIZE).
+
+    One ``b"".join``, one upload (offsets and bytes in one buffer), one launch; nothing is read back."""
+    dev = _cuda_device(device, "decode_stamps_device")
+    stamps = list(stamps)
+    for i, s in enumerate(stamps):
+        if not isinstance(s, (bytes, bytearray, memoryview)):
+            raise TypeError(f"stamps[{i}] must be bytes-like, got {type(s).__name__}")
+    n = len(stamps)
+    if n >= 2 ** 31:
+        raise ValueError(f"{n} stamps in one call: more than an int32 counts")
+    raw = torch.empty((n, 63, 63), dtype=torch.float32, device=dev)
+    shapes = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    if n == 0:
+        return raw, shapes, status
+    blob = b"".join(stamps)
+    head = 8 * (n + 1)
+    host = np.empty(head + len(blob), dtype=np.uint8)
+    offsets = host[:head].view(np.int64)
+    offsets[0] = 0
+    np.cumsum([len(s) for s in stamps], out=offsets[1:])
+    host[head:] = np.frombuffer(blob, dtype=np.uint8)
+    buf = torch.from_numpy(host).to(dev)
+    L = _lib.lib()
+    ws_bytes = _lib.check(L.btsbot_decode_stamps_workspace(n), "btsbot_decode_stamps_workspace")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.btsbot_decode_stamps(
+            C.c_void_p(buf.data_ptr() + head), C.c_void_p(buf.data_ptr()), n, C.c_void_p(raw.data_ptr()),
+            C.c_void_p(shapes.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(ws.data_ptr()), ws_bytes,
+            C.c_void_p(st)), "btsbot_decode_stamps")
+    return raw, shapes, status
+
+
+def make_triplets(alerts, device="cuda", normalize: bool = True, decode: str = "host", fallback: Optional[str] = "host",
+                  return_status: bool = False):
+    """make_triplet (alert_utils.py:110-196) over a batch of alert packets: the decode, then the arithmetic on
+    ``device`` in one launch.  Returns (triplets [B,3,63,63] float32 NCHW, drop [B] bool).
+
+    decode="host" (the default): ``decode_stamp`` per stamp in a Python loop.  decode="device": the three ``stampData``
+    fields of every alert go through ``decode_stamps_device`` (its docstring names what the device decodes and that it
+    does not verify the gzip CRC32).  Then ``fallback`` says what becomes of a stamp whose status is not 0:
+      "host"  one host read of the statuses; those stamps are decoded by ``decode_stamp`` and patched in before
+              ``prep_triplets``, so the result is the host path's and errors surface as they do there;
+      None    no host synchronisation at all: the alert comes back with ``drop = True``.
+    return_status=True adds a third value, the uint8 [B,3] statuses of the device decode (zeros for decode="host")."""
+    if decode not in ("host", "device"):
+        raise ValueError(f"decode must be 'host' or 'device', got {decode!r}")
+    if fallback not in ("host", None):
+        raise ValueError(f"fallback must be 'host' or None, got {fallback!r}")
+    if decode == "host":
+        raw, shapes = stack_stamps([decode_alert(a) for a in alerts])
+        out = prep_triplets(raw.to(device), shapes.to(device), normalize)
+        if return_status:
+            out += (torch.zeros((raw.shape[0], 3), dtype=torch.uint8, device=out[0].device),)
+        return out
+    stamps = [a[k]["stampData"] for a in alerts for k in _STAMP_KEYS]
+    raw, shapes, status = decode_stamps_device(stamps, device)
+    if fallback == "host":
+        for i in torch.nonzero(status.cpu()).reshape(-1).tolist():
+            stamp = decode_stamp(stamps[i])
+            h, w = stamp.shape
+            if h > 63 or w > 63:
+                raise ValueError(f"stamp larger than 63x63: {stamp.shape}")
+            frame = np.zeros((63, 63), dtype=np.float32)
+            frame[:h, :w] = stamp
+            raw[i] = torch.from_numpy(frame).to(raw.device)
+            shapes[i] = torch.tensor([h, w], dtype=torch.int32).to(raw.device)
+    status = status.view(-1, 3)
+    triplets, drop = prep_triplets(raw.view(-1, 3, 63, 63), shapes.view(-1, 3, 2), normalize)
+    if fallback is None:
+        drop = drop | (status != 0).any(dim=1)
+    return (triplets, drop, status) if return_status else (triplets, drop)
 
 
 def stack_stamps(alerts: Sequence[Sequence[np.ndarray]]) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -521,6 +521,39 @@ int btsbot_augment(const float* src, const int64_t* index, const uint8_t* ops, f
 int btsbot_prep_triplets(const float* raw, const int* shapes, float* triplets, uint8_t* drop, int batch,
                          int normalize, void* stream);
 
+/* Replaces: the gunzip + FITS decode in front of make_triplet (alert_utils.py:139-145), for a whole batch in one
+ * launch: stamp s is the `stampData` bytes blob[offsets[s] .. offsets[s+1]) (blob, offsets: device memory; offsets
+ * int64 [n_stamps + 1], non-decreasing, trusted; any byte alignment), a gzip member around a single-HDU FITS image.
+ * raw [n_stamps][63][63] f32 receives the image, big-endian samples swapped to native order (bit patterns kept), in the
+ * top-left h x w corner and zero elsewhere; shapes int32 [n_stamps][2] = (h, w); status uint8 [n_stamps] one of
+ * enum btsbot_stamp_status.  With n_stamps = 3 * batch these are btsbot_prep_triplets' raw and shapes.  A stamp with a
+ * non-zero status gets an all-zero image and shape (0, 0).
+ * Decoded on the device: one gzip member (FEXTRA / FNAME / FCOMMENT / FHCRC skipped, reserved flags refused) of stored,
+ * fixed and dynamic deflate blocks -- exactly the code-length sets zlib accepts -- inflating to at most
+ * BTSBOT_STAMP_CAP bytes, with ISIZE equal to the bytes produced; then a FITS primary header with SIMPLE = T,
+ * NAXIS = 2, BITPIX = -32, 1 <= NAXIS1, NAXIS2 <= 63, no BSCALE / BZERO card, and the whole data unit present.
+ * NOT as gzip.decompress: the CRC32 is not verified.  Anything else that is well formed -- bytes after the first member
+ * (multi-member files), other BITPIX, scaled data, larger axes, a header value the strict integer parser does not read
+ * -- is BTSBOT_STAMP_UNSUPPORTED: the caller's host path decodes it.
+ * workspace: btsbot_decode_stamps_workspace(n_stamps) bytes of device memory, 4-byte aligned, the caller's; contents
+ * do not matter before and are scratch afterwards.  One launch on `stream`; nothing allocates, synchronises or copies
+ * to the host; n_stamps == 0 launches nothing.  BTSBOT_ERR_INVALID_ARG before any HIP call: a NULL pointer, a negative
+ * n_stamps, a workspace that is too small or misaligned.  A negative length offsets[s+1] - offsets[s] is
+ * BTSBOT_STAMP_BAD_GZIP for that stamp. */
+#define BTSBOT_STAMP_CAP 28800   /* four 2880-byte header blocks + the data unit of a 63 x 63 float32 image */
+enum btsbot_stamp_status {
+  BTSBOT_STAMP_OK = 0,
+  BTSBOT_STAMP_BAD_GZIP = 1,     /* magic, method, reserved flags, or a header longer than the stamp          */
+  BTSBOT_STAMP_BAD_DEFLATE = 2,  /* the deflate stream breaks a rule or ends early                            */
+  BTSBOT_STAMP_TOO_LARGE = 3,    /* inflates to more than BTSBOT_STAMP_CAP bytes                              */
+  BTSBOT_STAMP_BAD_TRAILER = 4,  /* no 8-byte trailer, or ISIZE is not the number of bytes produced           */
+  BTSBOT_STAMP_BAD_FITS = 5,     /* no END card in the output, or the data unit is shorter than the header says */
+  BTSBOT_STAMP_UNSUPPORTED = 6   /* well formed, outside what the device decodes                              */
+};
+int64_t btsbot_decode_stamps_workspace(int n_stamps);
+int btsbot_decode_stamps(const uint8_t* blob, const int64_t* offsets, int n_stamps, float* raw, int32_t* shapes,
+                         uint8_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Replaces: the custom metadata columns of prep_alerts (alert_utils.py:333-441) for a batch of n_alerts alerts that
  * the caller has grouped by object: perm int32 [n_alerts] lists alert indices object by object, in input order inside
  * an object; object k owns perm[seg_offsets[k] .. seg_offsets[k+1]) (seg_offsets int32 [n_objects + 1], ascending from

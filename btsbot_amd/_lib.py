@@ -38,6 +38,9 @@ SYMBOLS = [
     "btsbot_op_mvt_dw3_bwd_w", "btsbot_op_mvt_attn_bwd", "btsbot_op_mvt_se_fwd", "btsbot_op_mvt_se_bwd",
     "btsbot_op_mvt_avgpool2_bwd", "btsbot_op_mvt_col2im3", "btsbot_op_mvt_unpack_conv3_grad", "btsbot_op_mvt_gelu_fwd",
     "btsbot_op_mvt_gelu_bwd", "btsbot_op_mvt_bcast_set",
+    "btsbot_op_cnt_dwln_bwd_rows", "btsbot_op_cnt_dw3ln_bwd_rows", "btsbot_op_cnt_dwln_bwd", "btsbot_op_cnt_dw3ln_bwd",
+    "btsbot_op_cnt_ln_bwd", "btsbot_op_cnt_ln_dw1_bwd", "btsbot_op_cnt_dw_plain", "btsbot_op_cnt_dw_wgrad",
+    "btsbot_op_cnt_colsum_f32",
     "btsbot_reserve_train", "btsbot_forward_train", "btsbot_backward", "btsbot_debug_stamps",
     "btsbot_grad_buckets", "btsbot_wait_grad_bucket", "btsbot_allreduce_grads", "btsbot_use_workspace", "btsbot_set_option",
     "btsbot_augment", "btsbot_eval_metrics", "btsbot_prep_triplets", "btsbot_alert_features",
@@ -189,6 +192,16 @@ def lib() -> C.CDLL:
                        ("unpack_conv3_grad", [vp, vp] + [i32] * 3 + [vp]), ("gelu_fwd", [vp, vp, i64, vp]),
                        ("gelu_bwd", [vp, vp, i64, vp]), ("bcast_set", [vp, vp, i32, i32, i32, f32, vp])):
         fn = getattr(L, "btsbot_op_mvt_" + name)
+        fn.restype = i32
+        fn.argtypes = args
+    for name, args in (("dwln_bwd_rows", [i32] * 3), ("dw3ln_bwd_rows", [i32]),
+                       ("dwln_bwd", [vp] * 7 + [i32, vp] + [i32] * 4 + [i64, vp]),
+                       ("dw3ln_bwd", [vp] * 7 + [i32, vp] + [i32] * 4 + [i64, vp]),
+                       ("ln_bwd", [vp] * 6 + [i64, i32, vp, i32, i32, vp]),
+                       ("ln_dw1_bwd", [vp] * 7 + [i32] + [vp] * 4 + [i64, i32, vp]),
+                       ("dw_plain", [vp, vp, i32, vp, vp, vp, vp] + [i32] * 4 + [vp]),
+                       ("dw_wgrad", [vp] * 4 + [i32] * 3 + [vp]), ("colsum_f32", [vp, vp, i32, i32, vp])):
+        fn = getattr(L, "btsbot_op_cnt_" + name)
         fn.restype = i32
         fn.argtypes = args
     L.btsbot_debug_stamps.restype = i32

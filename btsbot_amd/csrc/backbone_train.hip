@@ -468,7 +468,7 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
       } else if (s.dwpart != nullptr && adjacent) {
         // ---- LayerNorm backward, depthwise filter gradient and dx = dy + conv_flipped(dd) in one launch
         TRYB(launch_dwln_bwd(s.d, dxn, m + b.ln_w, s.xin, wdw, dy, nxt, prec, s.dwpart, B, hw, ch, st, planes, (size_t)rows * ch));
-        TRYB(add_pend(s.dwpart, grads + b.dw_w, s.dwrows, 52 * ch));
+        TRYB(add_pend(s.dwpart, grads + b.dw_w, dwln_bwd_grid(hw, ch, B), 52 * ch));
       } else if (hw == 1 && sc.dwln && ch <= 640) {
         // ---- 1x1 maps: the same three steps per (alert, channel) in one launch
         TRYB(launch_ln_dw1_bwd(s.d, dxn, m + b.ln_w, s.xin, wdw, dy, nxt, prec, grads + b.ln_w, grads + b.ln_b,

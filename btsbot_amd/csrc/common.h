@@ -468,7 +468,8 @@ int launch_ln_dw1_bwd(const float* d, const float* dxn, const float* g, const fl
                       void* out16, int prec16, float* dg, float* dbeta, float* dw, float* dbias, long rows, int C,
                       hipStream_t st);
 bool dwln_bwd_supported(int HW, int C);
-int dwln_bwd_rows(int HW, int C, int B);   // partial rows (52 * C floats each) one launch writes
+int dwln_bwd_rows(int HW, int C, int B);   // partial rows (52 * C floats each) to keep room for
+int dwln_bwd_grid(int HW, int C, int B);   // ... and those launch_dwln_bwd writes: the rows of the column sum behind it
 // (d == nullptr: the depthwise output is recomputed from x_in, the taps and the depthwise bias dwb)
 int launch_dwln_bwd(const float* d, const float* dxn, const float* g, const float* xin, const float* w, float* dy,
                     void* out16, int prec16, float* partials, int B, int HW, int C, hipStream_t st, int nplanes = 1,

@@ -422,16 +422,25 @@ int dwln_launch(const float* d, const float* dxn, const float* g, const float* x
 // the (map, width) pairs of convnext_pico's stages 0-2; everything else keeps the three-kernel form
 bool dwln_bwd_supported(int HW, int C) { return (HW == 15 && C == 64) || (HW == 7 && C == 128) || (HW == 3 && C == 256); }
 
-// partial rows one launch writes for a batch of B alerts (each 52 * C floats)
-int dwln_bwd_rows(int HW, int C, int B) {
+// partial rows (each 52 * C floats) launch_dwln_bwd WRITES for a batch of B alerts: its workgroups.  The column sum
+// behind it covers exactly these, never dwln_bwd_rows() of them: from B = 257 on the 3x3 kernel has more workgroups than
+// the general one, and the rows past the general kernel's are scratch that no launch has written
+int dwln_bwd_grid(int HW, int C, int B) {
   if (B <= 0) return 0;
   if (HW == 15 && C == 64) return DwlnCfg<15, 64, 512, 1>::grid(B);
   if (HW == 7 && C == 128) return DwlnCfg<7, 128, 512, 1>::grid(B);
-  if (HW == 3 && C == 256) {   // (room for either kernel's rows: BTSBOT_AMD_DW3_OLD=1 runs the general one; the deterministic mode keeps the 3x3 kernel and adds its rows in one slice)
-    const int r0 = DwlnCfg<3, 256, 512, 4>::grid(B), r1 = dw3_grid(B);
+  if (HW == 3 && C == 256) return DwlnCfg<3, 256, 512, 4>::grid(B);
+  return 0;
+}
+
+// partial rows to keep room for (each 52 * C floats)
+int dwln_bwd_rows(int HW, int C, int B) {
+  const int r0 = dwln_bwd_grid(HW, C, B);
+  if (HW == 3 && C == 256 && B > 0) {   // (room for either kernel's rows: BTSBOT_AMD_DW3_OLD=1 runs the general one; the deterministic mode keeps the 3x3 kernel and adds its rows in one slice)
+    const int r1 = dw3_grid(B);
     return r0 > r1 ? r0 : r1;
   }
-  return 0;
+  return r0;
 }
 
 // w: taps [49][C].  partials: dwln_bwd_rows() x 52 * C floats; row = [C][49] depthwise filter | [C] depthwise bias |

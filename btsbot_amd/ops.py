@@ -475,3 +475,105 @@ def mvt_bcast_set(v, P, scale, out=None):
     out = _new(out, (B, P, Cc), v)
     _mvt("bcast_set", v, _p(v), _p(out), B, P, Cc, float(scale))
     return out
+
+
+# ---- the ConvNeXt training step's LayerNorm / depthwise backward kernels one at a time (btsbot_op_cnt_*,
+# cn_bwd_ops.hip): everything fp32, NHWC rows; w = taps [49, C].  Every output is the caller's tensor: the "+=" ones
+# are added to, the "=" ones written (include/btsbot_hip.h states which is which).  out16: None, or a bf16 / f16
+# tensor that receives the rounded copy of the fp32 output.
+def _cnt(name, t, *args):
+    with torch.cuda.device(t.device):
+        _lib.check(getattr(_lib.lib(), "btsbot_op_cnt_" + name)(*args, _stream(t)), "btsbot_op_cnt_" + name)
+
+
+def _o16(out16, numel):
+    if out16 is None:
+        return _p(None), 0
+    assert out16.dtype in (torch.bfloat16, torch.float16) and out16.is_contiguous() and out16.numel() == numel
+    return _p(out16), _lib.PRECISION["bf16" if out16.dtype == torch.bfloat16 else "f16"]
+
+
+def cnt_dwln_bwd_rows(HW, C, B):
+    """Partial rows (= workgroups) of one dwln_bwd launch over B alerts."""
+    return _lib.check(_lib.lib().btsbot_op_cnt_dwln_bwd_rows(HW, C, B), "btsbot_op_cnt_dwln_bwd_rows")
+
+
+def cnt_dw3ln_bwd_rows(B):
+    """Partial rows (= workgroups) of one dw3ln_bwd launch over B alerts."""
+    return _lib.check(_lib.lib().btsbot_op_cnt_dw3ln_bwd_rows(B), "btsbot_op_cnt_dw3ln_bwd_rows")
+
+
+def _cnt_fused(name, first, dxn, g, xin, w, dy, arena, out16):
+    B, HW, _, Cc = xin.shape
+    n = B * HW * HW * Cc
+    planes = dxn.numel() // max(n, 1)
+    _f32t(dxn, numel=planes * n), _f32t(g, (Cc,)), _f32t(xin), _f32t(w, (49, Cc)), _f32t(dy, numel=n)
+    _f32t(arena, numel=52 * Cc)
+    p16, prec16 = _o16(out16, n)
+    _cnt(name, xin, _p(first), _p(dxn), _p(g), _p(xin), _p(w), _p(dy), p16, prec16, _p(arena), B, HW, Cc, planes, n)
+    return dy
+
+
+def cnt_dwln_bwd(d, dxn, g, xin, w, dy, arena, out16=None):
+    """xin, d, dy [B,HW,HW,C]; dxn [planes,B,HW,HW,C] (or one plane); dy += ; arena [52 C] = [C,49] | [C] | [C] | [C] += ."""
+    _f32t(d, numel=xin.numel())
+    return _cnt_fused("dwln_bwd", d, dxn, g, xin, w, dy, arena, out16)
+
+
+def cnt_dw3ln_bwd(dwb, dxn, g, xin, w, dy, arena, out16=None):
+    """The 3x3 x 256 kernel: as cnt_dwln_bwd with dwb [C] = conv_dw.bias in place of d."""
+    _f32t(dwb, (xin.shape[3],))
+    return _cnt_fused("dw3ln_bwd", dwb, dxn, g, xin, w, dy, arena, out16)
+
+
+def cnt_ln_bwd(d, dxn, g, dd, dg, dbeta, out16=None, patch_hw=0):
+    """d [rows, C]; dxn [rows, C] (dd may be dxn) or, with patch_hw, the patch matrix [rows / 4-ish, 4 C]; dd = ;
+    dg, dbeta [C] += ."""
+    rows, Cc = d.shape
+    _f32t(d), _f32t(dxn), _f32t(g, (Cc,)), _f32t(dd, numel=rows * Cc), _f32t(dg, (Cc,)), _f32t(dbeta, (Cc,))
+    if patch_hw == 0:
+        assert dxn.numel() == rows * Cc
+    else:
+        assert dxn.numel() == rows // (patch_hw * patch_hw) * (patch_hw // 2) ** 2 * 4 * Cc
+    p16, prec16 = _o16(out16, rows * Cc)
+    _cnt("ln_bwd", d, _p(d), _p(dxn), _p(g), _p(dd), _p(dg), _p(dbeta), rows, Cc, p16, prec16, patch_hw)
+    return dd
+
+
+def cnt_ln_dw1_bwd(d, dxn, g, xin, w, dy, dg, dbeta, dw, dbias, out16=None):
+    """1x1 maps: d, dxn, xin, dy [rows, C]; dy += ; dg, dbeta, dbias [C] += ; dw [C, 49]: tap 24 += ."""
+    rows, Cc = d.shape
+    for t in (d, dxn, xin, dy):
+        _f32t(t, numel=rows * Cc)
+    _f32t(g, (Cc,)), _f32t(w, (49, Cc)), _f32t(dg, (Cc,)), _f32t(dbeta, (Cc,)), _f32t(dw, (Cc, 49)), _f32t(dbias, (Cc,))
+    p16, prec16 = _o16(out16, rows * Cc)
+    _cnt("ln_dw1_bwd", d, _p(d), _p(dxn), _p(g), _p(xin), _p(w), _p(dy), p16, prec16, _p(dg), _p(dbeta), _p(dw), _p(dbias),
+         rows, Cc)
+    return dy
+
+
+def cnt_dw_plain(x, w, flip, bias, addend, out, out16=None):
+    """x, out [B,HW,HW,C]; out = conv(x, taps, flipped when flip) + bias + addend (each may be None; addend may be out)."""
+    B, HW, _, Cc = x.shape
+    _f32t(x), _f32t(w, (49, Cc)), _f32t(out, numel=x.numel())
+    assert bias is None or _f32t(bias, (Cc,)) is bias
+    assert addend is None or _f32t(addend, numel=x.numel()) is addend
+    p16, prec16 = _o16(out16, x.numel())
+    _cnt("dw_plain", x, _p(x), _p(w), int(flip), _p(bias), _p(addend), _p(out), p16, prec16, B, HW, Cc)
+    return out
+
+
+def cnt_dw_wgrad(x, dd, dw, dbias):
+    """x, dd [B,HW,HW,C]; dw [C,49] += , dbias [C] += (dbias directly behind dw in memory, or the call is refused)."""
+    B, HW, _, Cc = x.shape
+    _f32t(x), _f32t(dd, numel=x.numel()), _f32t(dw, numel=49 * Cc), _f32t(dbias, (Cc,))
+    _cnt("dw_wgrad", x, _p(x), _p(dd), _p(dw), _p(dbias), B, HW, Cc)
+    return dw, dbias
+
+
+def cnt_colsum_f32(rows, out):
+    """out [N] += the column sums of rows [M, N]."""
+    M, N = rows.shape
+    _f32t(rows), _f32t(out, (N,))
+    _cnt("colsum_f32", rows, _p(rows), _p(out), M, N)
+    return out

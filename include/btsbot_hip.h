@@ -479,6 +479,55 @@ int btsbot_op_mvt_gelu_fwd(const float* pre, float* out, int64_t n, void* stream
 int btsbot_op_mvt_gelu_bwd(const float* pre, float* d, int64_t n, void* stream);
 int btsbot_op_mvt_bcast_set(const float* v, float* d, int B, int P, int C, float scale, void* stream);
 
+/* The LayerNorm / depthwise backward kernels of the ConvNeXt TRAINING step (dwln_bwd.hip, backward.hip) one at a time.
+ * Everything is fp32; activations are NHWC rows [B][HW*HW][C]; w = the depthwise taps [49][C] (tap-major, as the
+ * engine packs conv_dw.weight); the LayerNorm eps is 1e-6.  Every call runs the launcher the training engine itself
+ * runs (same kernels, same grid arithmetic) on the caller's stream, with a stream-ordered scratch of its own for the
+ * partial rows.  A null pointer, B or rows < 0, or a shape the launcher has no kernel for comes back as
+ * BTSBOT_ERR_INVALID_ARG with a message, before anything is allocated or launched; B = 0 launches nothing.
+ * out16 (may be NULL): the same values as the fp32 output next to it, rounded to prec16 = BTSBOT_BF16 / BTSBOT_F16;
+ * WRITTEN.  The accumulation contract of every other output is stated per entry point: "+=" outputs are added to
+ * (the caller zeroes the gradient arena once per step), "=" outputs are written.
+ *
+ * The launchers' grid decisions: partial rows (= workgroups) of one dwln_bwd / dw3ln_bwd launch over B alerts; a
+ * workgroup of dwln_bwd owns ceil(B / rows) consecutive alerts, the last one what is left. */
+int btsbot_op_cnt_dwln_bwd_rows(int HW, int C, int B);
+int btsbot_op_cnt_dw3ln_bwd_rows(int B);
+/* LayerNorm backward, depthwise filter gradient and depthwise input gradient of a block in one kernel, then the column
+ * sum of its partial rows: (HW, C) = (15, 64), (7, 128) or (3, 256).  d = the kept depthwise output, xin = the block's
+ * input, g = norm.weight, dxn = the gradient of the LayerNorm output as `nplanes` addend planes pstride floats apart.
+ *   dy    += conv(dd, flipped taps)      (dd = LN'(d) . sum of planes never leaves the chip)
+ *   arena += [C][49] conv_dw.weight | [C] conv_dw.bias | [C] norm.weight | [C] norm.bias gradients */
+int btsbot_op_cnt_dwln_bwd(const float* d, const float* dxn, const float* g, const float* xin, const float* w, float* dy,
+                           void* out16, int prec16, float* arena, int B, int HW, int C, int nplanes, int64_t pstride,
+                           void* stream);
+/* The same for 3x3 maps of 256 channels in their own kernel, which recomputes d from xin, the taps and dwb =
+ * conv_dw.bias, then the reduction of its compact rows.  dy += ; arena += as above, where of the 49 taps per channel
+ * only the central 5x5 (the ones that meet a 3x3 map) are touched at all. */
+int btsbot_op_cnt_dw3ln_bwd(const float* dwb, const float* dxn, const float* g, const float* xin, const float* w, float* dy,
+                            void* out16, int prec16, float* arena, int B, int HW, int C, int nplanes, int64_t pstride,
+                            void* stream);
+/* LayerNorm backward over the C <= 640 channels of each of `rows` rows: dd = (written; it may be dxn itself when
+ * patch_hw = 0), dg [C] += , dbeta [C] += .  patch_hw != 0: dxn is the gradient of a 2x2 / stride-2 downsample's patch
+ * matrix [B (patch_hw/2)^2][4 C] for input maps of side patch_hw (rows = B patch_hw^2); every input pixel gathers its
+ * slice, an odd last row and column get dd = 0 and add nothing to dg / dbeta. */
+int btsbot_op_cnt_ln_bwd(const float* d, const float* dxn, const float* g, float* dd, float* dg, float* dbeta, int64_t rows,
+                         int C, void* out16, int prec16, int patch_hw, void* stream);
+/* 1x1 maps (C <= 640): LayerNorm backward and both depthwise gradients per (alert, channel) in one kernel.
+ * dy += dd * w[24];  dg [C] += ;  dbeta [C] += ;  dw [C][49]: tap 24 += , the other 48 untouched;  dbias [C] += . */
+int btsbot_op_cnt_ln_dw1_bwd(const float* d, const float* dxn, const float* g, const float* xin, const float* w, float* dy,
+                             void* out16, int prec16, float* dg, float* dbeta, float* dw, float* dbias, int64_t rows, int C,
+                             void* stream);
+/* Depthwise 7x7 p3 on maps of side HW = 15, 7, 3 or 1 (C a multiple of 4):
+ * out = conv(x, flip ? flipped taps : taps) [+ bias] [+ addend]  (written; addend may be out itself). */
+int btsbot_op_cnt_dw_plain(const float* x, const float* w, int flip, const float* bias, const float* addend, float* out,
+                           void* out16, int prec16, int B, int HW, int C, void* stream);
+/* Depthwise filter gradient (same shapes): dw [C][49] += sum dd[p] x[p + delta_t], dbias [C] += sum dd; dbias must be
+ * dw + 49 C, as in the arena (one column sum covers both), anything else is refused. */
+int btsbot_op_cnt_dw_wgrad(const float* x, const float* dd, float* dw, float* dbias, int B, int HW, int C, void* stream);
+/* out [N] += the column sums of in [M][N] (fp32): what folds partial rows into the arena. */
+int btsbot_op_cnt_colsum_f32(const float* in, float* out, int M, int N, void* stream);
+
 /* Measurement aid with no reference counterpart (bench.py's roofline leg): when on, every kernel
  * launch of forward() is bracketed by two HIP events recorded on the launch stream;
  * profile_collect() waits for them and returns, per kernel family (profile_category_name), the

@@ -38,6 +38,8 @@ from .synthetic import METADATA_COLS, synthetic_batch
 from .pipeline import ScoreStream
 from .alert_utils import CUSTOM_COLS, alert_features, decode_stamps_device, make_metadata, make_triplets
 from .val import REFERENCE_POLICIES, policy_eval, policy_performance
+from . import diagnostics
+from .diagnostics import alert_histograms, diagnostic_data, diagnostic_fig, draw_diagnostic_fig, roc_points
 from .triggers import TriggerState
 from .features import FeatureState
 from .splits import (SOURCE_SETS, SPLIT_NAMES, create_subset, cut_set_and_assign_splits, cuts_suffix, label_set,
@@ -49,6 +51,7 @@ __all__ = [
     "download_HF_model", "load_HF_model", "METADATA_COLS", "synthetic_batch", "ScoreStream",
     "CUSTOM_COLS", "alert_features", "make_metadata", "make_triplets", "decode_stamps_device",
     "REFERENCE_POLICIES", "policy_eval", "policy_performance", "triggers", "TriggerState",
+    "diagnostics", "alert_histograms", "roc_points", "diagnostic_data", "diagnostic_fig", "draw_diagnostic_fig",
     "features", "FeatureState",
     "splits", "SPLIT_NAMES", "SOURCE_SETS", "label_set", "split_labels", "subset_mask", "cuts_suffix",
     "cut_set_and_assign_splits", "merge_sets_across_split", "create_subset", "subsample_data",

@@ -45,7 +45,7 @@ SYMBOLS = [
     "btsbot_grad_buckets", "btsbot_wait_grad_bucket", "btsbot_allreduce_grads", "btsbot_use_workspace", "btsbot_set_option",
     "btsbot_augment", "btsbot_eval_metrics", "btsbot_prep_triplets", "btsbot_alert_features",
     "btsbot_split_labels", "btsbot_decode_stamps_workspace", "btsbot_decode_stamps",
-    "btsbot_policy_eval", "btsbot_trigger_reset", "btsbot_trigger_update", "btsbot_trigger_load",
+    "btsbot_policy_eval", "btsbot_alert_histograms", "btsbot_trigger_reset", "btsbot_trigger_update", "btsbot_trigger_load",
     "btsbot_trigger_rehash", "btsbot_feature_reset", "btsbot_feature_update", "btsbot_feature_load", "btsbot_feature_rehash",
     "btsbot_embed_width", "btsbot_forward_embed",
 ]
@@ -240,6 +240,9 @@ def lib() -> C.CDLL:
     L.btsbot_decode_stamps.argtypes = [vp, vp, i32, vp, vp, vp, vp, i64, vp]
     L.btsbot_policy_eval.restype = i32
     L.btsbot_policy_eval.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_double), i32, vp, vp, vp, vp]
+    L.btsbot_alert_histograms.restype = i32
+    L.btsbot_alert_histograms.argtypes = [vp, vp, vp, i64, C.POINTER(C.c_double), i32, C.POINTER(C.c_double), i32,
+                                          C.POINTER(C.c_double), i32, vp, vp]
     L.btsbot_trigger_reset.restype = i32
     L.btsbot_trigger_reset.argtypes = [C.POINTER(TriggerTable), vp]
     L.btsbot_trigger_update.restype = i32

@@ -217,7 +217,7 @@ def train_epoch(trainer: Trainer, dataset, epoch_metrics: bool = True):
 
 def fit(trainer: Trainer, train_set, val_images, val_metadata, val_labels, model_dir: str,
         epochs: int, patience: int = 10, val_batch_size: int = 1024, config: Optional[dict] = None,
-        val_cand=None):
+        val_cand=None, diagnostic: bool = False, run_name: str = "diagnostic"):
     """The epoch loop of train.py:303-352 on the device: per epoch ``train_epoch`` -> ``latest_model.pth`` ->
     validation pass (val.py's loop, on the live model instead of re-instantiating it from the file) ->
     scheduler step -> ``best_model.pth`` when the validation loss improved by at least 0.5 % ->
@@ -226,8 +226,11 @@ def fit(trainer: Trainer, train_set, val_images, val_metadata, val_labels, model
     to_HF.prep_config, the history and the best epoch's alert-level ``val_summary``.  ``val_cand``: the validation
     split's candidate table (a dict or DataFrame with ``objectId``, ``jd``, ``magpsf`` per validation alert, optionally
     ``junk``, ``save_time``, ``trigger_time``); with it ``val_summary`` gains the per-source ``"policy_performance"``
-    (``val.policy_performance``, val.py:381-614), without it the summary is the alert-level one alone.  Returns the run
-    history dict (train/val loss and accuracy per epoch)."""
+    (``val.policy_performance``, val.py:381-614), without it the summary is the alert-level one alone.  ``diagnostic`` (with
+    ``val_cand``): rank 0 also writes ``diagnostic.json`` -- ``diagnostics.diagnostic_data`` for the best epoch, the data
+    of the reference's twelve-panel figure (val.py:173-682) -- and, where matplotlib is installed, the figure itself as
+    ``{run_name}.pdf``; ``report.json`` and the return value are the same with and without.  Returns the run history
+    dict (train/val loss and accuracy per epoch)."""
     import json
     import os
     import numpy as np
@@ -265,7 +268,7 @@ def fit(trainer: Trainer, train_set, val_images, val_metadata, val_labels, model
                 break
     out = {k: v[:done].tolist() for k, v in hist.items()}
     # the alert-level numbers of the reference's val_summary (val.py:178-218 -> utils.make_report) for the best epoch,
-    # and the per-source policy metrics (val.py:381-614) when the candidate table is at hand; its figure stays out of scope
+    # and the per-source policy metrics (val.py:381-614) when the candidate table is at hand
     from .val import alert_summary
     summary = alert_summary(best_raw_preds, best_val_labels) if best_raw_preds is not None else {}
     if val_cand is not None and best_raw_preds is not None:
@@ -275,6 +278,15 @@ def fit(trainer: Trainer, train_set, val_images, val_metadata, val_labels, model
         with open(os.path.join(model_dir, "report.json"), "w") as f:
             json.dump({"train_config": dict(config or {}), "Training history": out, "val_summary": summary}, f,
                       indent=2)
+        if diagnostic and val_cand is not None and best_raw_preds is not None:
+            from .diagnostics import cand_diagnostic_data, save_diagnostic_fig
+            curves = {"loss": out["train_loss"], "val_loss": out["val_loss"], "accuracy": out["train_accuracy"],
+                      "val_accuracy": out["val_accuracy"]}
+            data = cand_diagnostic_data(val_cand, best_raw_preds, best_val_labels, history=curves,
+                                        device=next(trainer.model.parameters()).device)
+            with open(os.path.join(model_dir, "diagnostic.json"), "w") as f:
+                json.dump(data, f)
+            save_diagnostic_fig(data, model_dir, os.path.join(model_dir, f"{run_name}.pdf"))
     out["best_raw_preds"], out["best_val_labels"] = best_raw_preds, best_val_labels
     out["val_summary"] = summary
     return out
@@ -334,8 +346,8 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
 
 def run_training(config: dict, data_base_dir: str = "", run_name: str = "testing", device="cuda",
                  precision: str = "bf16", models_root: str = "models", split_training: bool = False,
-                 embeddings_root: str = "embeddings"):
-    """train.py:75-440 (``run_training(config)``) on this framework, minus WandB and the diagnostic figure: seeds,
+                 embeddings_root: str = "embeddings", diagnostic_fig: bool = False):
+    """train.py:75-440 (``run_training(config)``) on this framework, minus WandB: seeds,
     the split files (``data.load_split``), the model by name with the frozen_fusion freezing rule
     (train.py:224-236), AdamW(lr, betas=(beta_1, beta_2)) under the warm-up + cosine schedule, BCE with
     pos_weight = N_neg / N_pos of the training split (train.py:211-212), the epoch loop with latest / best
@@ -348,7 +360,9 @@ def run_training(config: dict, data_base_dir: str = "", run_name: str = "testing
     only -- the training step's matrix products on split f16 operands (``set_split_training``).
     ``config['generate_embeddings']`` (train.py:449-469): after the best checkpoint is chosen, ``write_embeddings``
     leaves ``{embeddings_root}/{model_name}_{run_name}.npy`` (+ ``.csv``); a failure there is printed and the run
-    still returns, as in the reference.  Returns (history dict, model_dir)."""
+    still returns, as in the reference.  ``diagnostic_fig`` (train.py:378, off by default): when the validation table
+    has the light-curve columns, rank 0 leaves ``diagnostic.json`` and, with matplotlib, ``{run_name}.pdf`` in the model
+    directory (``fit``'s ``diagnostic``).  Returns (history dict, model_dir)."""
     import numpy as np
     import torch.distributed as dist
     from . import architectures
@@ -395,7 +409,8 @@ def run_training(config: dict, data_base_dir: str = "", run_name: str = "testing
                       warmup_epochs=warmup)
     model_dir = os.path.join(models_root, f"{model_name}_{version}{n_str}_{dev.type}", run_name) + "/"
     hist = fit(trainer, train_set, vimg, vmeta, vlab, model_dir, epochs=epochs, patience=patience,
-               val_batch_size=batch_size, config=config, val_cand=vcand)
+               val_batch_size=batch_size, config=config, val_cand=vcand, diagnostic=diagnostic_fig,
+               run_name=run_name)
     if config.get("generate_embeddings", False) and rank == 0:
         try:
             hist["embeddings_file"] = write_embeddings(model, config, data_base_dir, model_dir,

@@ -75,6 +75,11 @@ def alert_summary(raw_preds, labels) -> dict:
     ``bts_acc`` / ``notbts_acc`` / ``bal_acc``, ``alert_precision`` / ``alert_recall`` (-999.0 when there is no true
     positive or no true negative, as there) and ``roc_auc`` (area under sklearn's ``roc_curve``: the rank statistic
     with tied scores sharing their average rank).  Everything is reduced on the tensors' device; one host read."""
+    return _alert_summary_dict(_alert_summary_device(raw_preds, labels).cpu().tolist())   # the one host read
+
+
+def _alert_summary_device(raw_preds, labels) -> torch.Tensor:
+    """The seven sums ``alert_summary`` is made of, float64 on the inputs' device; nothing is read."""
     p = torch.as_tensor(raw_preds).reshape(-1).to(torch.float64)
     y = torch.as_tensor(labels, device=p.device).reshape(-1).to(torch.float64)
     if p.numel() != y.numel():
@@ -92,7 +97,10 @@ def alert_summary(raw_preds, labels) -> dict:
     avg_rank = (last - (cnt.to(torch.float64) - 1) / 2)[inv]
     n_pos, n_neg = y.sum(), (1 - y).sum()
     rank_sum = (avg_rank * y[order]).sum()
-    vals = torch.stack([tp, tn, fp, fn, n_pos, n_neg, rank_sum]).to(torch.float64).cpu().tolist()
+    return torch.stack([tp, tn, fp, fn, n_pos, n_neg, rank_sum]).to(torch.float64)
+
+
+def _alert_summary_dict(vals) -> dict:
     tp, tn, fp, fn, n_pos, n_neg, rank_sum = vals
     nan = float("nan")
     bts_acc = tp / (tp + fn) if tp + fn > 0 else nan
@@ -265,6 +273,15 @@ def policy_performance(object_id: torch.Tensor, jd: torch.Tensor, magpsf: torch.
     a TP or without a TN every figure is -999.0 and the binned lists are [-999.0], as there.
 
     Everything is reduced on the device over the kernel's object slots; ONE host read at the end."""
+    names, rows, _ = _policy_performance_device(object_id, jd, magpsf, label, raw_preds, policies, junk, save_time,
+                                                trigger_time)
+    return _policy_performance_dict(names, rows.cpu().tolist())                           # the one host read
+
+
+def _policy_performance_device(object_id, jd, magpsf, label, raw_preds, policies, junk, save_time, trigger_time):
+    """``policy_performance`` up to its host read: the policy names, one float64 row of counts and medians per policy on
+    the device, and per object slot and policy the ``save_dt`` that median is taken over (NaN where there is none; None
+    without ``save_time``)."""
     columns = (("junk", junk, torch.bool), ("save_time", save_time, torch.float64),
                ("trigger_time", trigger_time, torch.float64))
     for name, t, _ in columns:                                        # before any device work
@@ -294,7 +311,7 @@ def policy_performance(object_id: torch.Tensor, jd: torch.Tensor, magpsf: torch.
     counts = [m.sum(0).to(torch.float64)[:, None] for m in (tp, fp, fn, tn)]
     counts += [(m[:, :, None] & onehot[:, None, :]).sum(0).to(torch.float64) for m in (tp, fp, fn)]
     tjd = slots["trigger_jd"]
-    meds = []
+    meds, save_dt = [], None
     for t, upper in ((per_row.get("save_time"), None), (per_row.get("trigger_time"), 1e10)):
         if t is None:
             meds.append(torch.full((len(names), 1), float("nan"), dtype=torch.float64, device=dev))
@@ -303,8 +320,14 @@ def policy_performance(object_id: torch.Tensor, jd: torch.Tensor, magpsf: torch.
         if upper is not None:
             ok &= t < upper
         dt = torch.where(tp & ok[:, None] & (tjd > 0), tjd - t[:, None], torch.full_like(tjd, float("nan")))
+        if upper is None:
+            save_dt = dt
         meds.append(_median_columns(dt)[:, None])
-    rows = torch.cat(counts + meds, dim=1).cpu().tolist()                                 # the one host read
+    return names, torch.cat(counts + meds, dim=1), save_dt
+
+
+def _policy_performance_dict(names, rows) -> dict:
+    nb = len(PEAKMAG_BINS) - 1
     nan = float("nan")
     out = {}
     for name, row in zip(names, rows):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A whole training run on the MI355X-native package, in the shapes the reference's train.py works with.
 
-    python examples/train_example.py [--model mm_ConvNeXt|um_nn|ConvNeXt] [--alerts 4096] [--epochs 3]
+    python examples/train_example.py [--model mm_ConvNeXt|um_nn|ConvNeXt] [--alerts 4096] [--epochs 3] [--diagnostic]
     torchrun --standalone --local-addr 127.0.0.1 --nproc-per-node 2 examples/train_example.py   # one rank per GPU
 
 It writes a synthetic split in the reference's on-disk layout (``data/{train,val}_cand_v11_N100.csv`` +
@@ -46,6 +46,8 @@ def write_split(base, split, n, seed):
     obj = rng.integers(0, max(n // 6, 1), n)
     df["objectId"] = [f"ZTF21{k:07d}" for k in obj]
     df["jd"] = 2459300.5 + rng.uniform(0, 60, n)
+    # when the human scanners saved the object (trues.csv in the reference): some day of its two months, per object
+    df["save_time"] = (2459300.5 + rng.uniform(5, 55, max(n // 6, 1)))[obj]
     df.to_csv(os.path.join(base, "data", f"{split}_cand_v11_N100.csv"), index=False)
 
 
@@ -59,6 +61,9 @@ def main():
     ap.add_argument("--split-training", action="store_true",
                     help="f16x2 with a ConvNeXt image branch: train on split f16 operands (fp32-class gradients)")
     ap.add_argument("--data-base-dir", default=None)
+    ap.add_argument("--diagnostic", action="store_true",
+                    help="also leave diagnostic.json (the data of the reference's twelve-panel figure) and, with "
+                         "matplotlib installed, example.pdf in the model directory")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -93,7 +98,7 @@ def main():
                   beta_1=0.9, beta_2=0.999, patience=5, random_seed=2)
     hist, model_dir = run_training(config, data_base_dir=base, run_name="example", device=dev,
                                    precision=args.precision, models_root=os.path.join(base, "models"),
-                                   split_training=args.split_training)
+                                   split_training=args.split_training, diagnostic_fig=args.diagnostic)
     if rank == 0:
         for e, (tl, ta, vl, va) in enumerate(zip(hist["train_loss"], hist["train_accuracy"], hist["val_loss"],
                                                  hist["val_accuracy"])):

@@ -635,6 +635,28 @@ int btsbot_policy_eval(const int32_t* perm, const int32_t* seg_offsets, int n_al
                        const double* policies, int n_policies, int32_t* obj_pred, double* obj_trigger,
                        double* obj_info, void* stream);
 
+/* Replaces: the alert-level counts behind the reference's diagnostic figure (val.py:185-379 inside diagnostic_fig: the
+ * hist2d of score against magnitude with its two marginal histograms, np.histogram of magpsf per TP / FP / TN / FN, the
+ * confusion matrix) for a whole split in one launch.
+ * magpsf double [n], raw float [n] (the sigmoid scores, compared as the float32 value widened to float64), label int32
+ * [n] (0 = negative, anything else positive; not checked): device pointers.  mag_edges [n_mag + 1], score_edges
+ * [n_score + 1], class_edges [n_class + 1]: HOST arrays of float64 bin edges, finite and strictly increasing, read before
+ * the call returns and compared exactly as passed.  Bin i holds edges[i] <= x < edges[i+1], the last bin also
+ * x == edges[n]; any other x, NaN included, is in no bin (numpy's rule).  pred = raw > 0.5 (a NaN score predicts 0).
+ * out int64 (device), ADDED INTO -- the caller zeroes it before the first call -- in this order:
+ *   joint [n_mag][n_score]   alerts with magpsf in mag bin i AND score in score bin j
+ *   mag   [n_mag]            alerts per mag bin, whatever the score (not a row sum of joint)
+ *   score [n_score]          alerts per score bin, whatever the magnitude
+ *   cls   [4][n_class]       magpsf over class_edges per class, rows TP, FP, TN, FN
+ *   total [4]                every alert, by class, whatever its magnitude
+ * n_mag, n_score, n_class in 1..64, n_mag * n_score <= 4096, 0 <= n <= 2^38; BTSBOT_ERR_INVALID_ARG before any launch
+ * otherwise (also: a NULL pointer, an edge table that is not finite and strictly increasing).  One launch on `stream`,
+ * no allocation, no host synchronisation; n == 0 launches nothing.  Integer sums: the result does not depend on the
+ * order in which the workgroups add. */
+int btsbot_alert_histograms(const double* magpsf, const float* raw, const int32_t* label, int64_t n,
+                            const double* mag_edges, int n_mag, const double* score_edges, int n_score,
+                            const double* class_edges, int n_class, int64_t* out, void* stream);
+
 /* Replaces: the per-object loops of cut_set_and_assign_splits and create_subset (query_data/train_val_test_split.py:
  * 123-140, 211-231) for a table of n_alerts alerts grouped by object exactly as for btsbot_alert_features (perm,
  * seg_offsets, n_objects may be an upper bound with empty objects; trusted device data, clamped, perm entries outside

@@ -24,10 +24,16 @@
 //   * fc1's B operand is the LayerNorm output ([pixel][channel] in LDS, re-read per chunk: the registers it would
 //     take are the second fragment set); its result goes through GELU into a double-buffered [pixel][hidden]
 //     LDS image that is fc2's B operand: one barrier per chunk;
-//   * depthwise + LayerNorm: the map goes to LDS in fp32, thread = (channel, alert pair) applies the central
-//     5 x 5 taps (all a 3 x 3 map can touch) in place, wave = pixel normalises (two wave reductions);
+//   * depthwise + LayerNorm: the map goes to LDS in fp32 -- [9 G live pixel rows][C + 4]: the four floats of padding
+//     put the eight rows a 16-byte accumulator store is served in on eight different bank slots (Shp<>::XLP); nothing
+//     clears the map, every row is rewritten from the accumulators before it is read -- thread = (channel, alert pair)
+//     applies the central 5 x 5 taps (all a 3 x 3 map can touch) in place, half wave = pixel normalises;
 //   * the downsample's 4 MB-per-launch GEMM (M = alerts) runs here as 16-column products with 4 live columns:
-//     wasteful on the matrix pipe, free in time -- it is the 1 MB filter stream that bounds it.
+//     wasteful on the matrix pipe, free in time -- it is the 1 MB filter stream that bounds it, a whole output tile
+//     (32 KB per wave) in flight; its LayerNorm normalises only the four pixels of a map that the 2 x 2 stride-2
+//     convolution reads.
+// LDS (bf16 / f16, 256 channels): G = 4: 95,296 B, G = 5: 104,656 B, G = 7: 141,296 B (row-tile form: 142,336 B);
+// split operands: 149,056 B (G = 4), 158,416 B (G = 5); 320 channels, G = 5: 129,488 B; training forward: + 55,296 B.
 #include <string.h>
 #include <type_traits>
 
@@ -183,7 +189,16 @@ constexpr int CHUNK = 128;                            // hidden units per fc1 / 
 template <int CW> struct Shp {
   static constexpr int C = CW, HID = 4 * CW, NCHUNK = HID / CHUNK;
   static constexpr int CO = 2 * CW, KD = 4 * CW, KSD = KD / 32;   // downsample: 512 outputs, K = 1024 (640, 1280)
-  static constexpr int XLP = CW;                                   // fp32 map: floats per pixel row
+  // fp32 map: floats per pixel row.  The accumulators reach it as ds_write_b128 with lane = (pixel row 16 n + (lane & 15),
+  // channels c0 + 4 (lane >> 4) ..): the eight lanes a store is served by hold eight consecutive rows at ONE channel
+  // offset, a pitch apart, and a store's bank is (a / 4) mod 32.  A pitch of C floats (0 mod 128 bytes) put all eight on
+  // the same four banks; 16 bytes (mod 128) give each its own 16-byte slot of the 128-byte bank row (1040; 1296 bytes).
+  // The map's readers do not care: the depthwise reads have lane = channel, the LayerNorm reads one row per half wave.
+  // (320 channels, the shared tiles' read-add: a ds_read_b128 group holds rows at two neighbouring channel quads, slot =
+  //  row + quad (mod 16) with this pitch: one slot of each group is taken twice, 5 cycles for 4.  32 bytes (mod 256)
+  //  would free the read and make every store 2-way; the stores are the many.)
+  static constexpr int XLP = CW + 4;
+  static_assert(XLP * 4 % 128 == 16, "map pitch: the eight rows of a store group on eight 16-byte slots");
   static constexpr int NTILE = CW / 16, MF = NTILE / NW, NX = NTILE - MF * NW;   // row tiles; per wave; shared by wave pairs
   static_assert(NX == 0 || 2 * NX == NW, "the tiles left over are shared by wave pairs");
   // 16-bit LN image: bytes per pixel row, 32 (mod 256) -- see below (544; 800)
@@ -197,22 +212,25 @@ template <int CW> struct Shp {
 // cycles were conflicts, SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.50.)  fp8 reads 8 bytes per lane in two groups
 // of 32 lanes: 16 bytes apart is the bijection there.
 constexpr int HP2 = CHUNK * 2 + 32;                   // hidden image: bytes per pixel row (288)
-constexpr int OFF_XL = 0;                             // [NCOL][256] f32 (rows >= NPX stay zero)
-template <typename T, int G, int CW = 256> struct Lds {
-  static constexpr int NCOL = Geo<G>::NCOL;
+constexpr int OFF_XL = 0;                             // [NPX][XLP] f32: the live rows only (nothing reads a row >= NPX)
+template <typename T, int G, int CW = 256, int ROWS = 0> struct Lds {
+  static constexpr int NCOL = Geo<G>::NCOL, NPX = ROWS > 0 ? ROWS : Geo<G>::NPX;
   static constexpr int XLP = Shp<CW>::XLP, XNP2 = Shp<CW>::XNP2, HID = Shp<CW>::HID;
-  static constexpr int OFF_XN = OFF_XL + NCOL * XLP * 4;      // G = 4: 49152
+  static constexpr int OFF_XN = OFF_XL + NPX * XLP * 4;       // G = 4: 37440 (a multiple of 16: the images keep their alignment)
   static constexpr int XN_PLANE = NCOL * XNP2, H_PLANE = NCOL * HP2;   // 26112, 13824 (the split mode has two planes of each)
   static constexpr int NPL = MP<T>::SPLIT ? 2 : 1;
   static constexpr int H_IMG = NPL * H_PLANE;                 // one hidden image (two of them)
   static constexpr int OFF_H = OFF_XN + NPL * XN_PLANE;
   static constexpr int OFF_B1 = OFF_H + 2 * H_IMG;            // fc1 bias [1024] f32
-  static constexpr int BYTES = OFF_B1 + HID * 4;              // G = 4: 104704 (split: 160768); G = 7: 141312
+  static constexpr int BYTES = OFF_B1 + HID * 4;              // G = 4: 95296 (split: 149056); G = 5: 104656; G = 7: 141296
   // training forward: two more hidden-sized images (the rounded fc1 pre-activation of a chunk, kept for the backward)
   static constexpr int OFF_A = BYTES;
   static constexpr int BYTES_TRAIN = BYTES + 2 * H_IMG;
 };
 static_assert(Lds<f16x2_t, 4>::BYTES <= 160 * 1024 && Lds<bf16_t, 7>::BYTES <= 160 * 1024, "the images fit one CU");
+static_assert(Lds<bf16_t, 4>::BYTES == 95296 && Lds<bf16_t, 5>::BYTES == 104656 && Lds<bf16_t, 7>::BYTES == 141296 &&
+              Lds<bf16_t, 7, 256, 64>::BYTES == 142336 && Lds<f16x2_t, 5>::BYTES == 158416 && Lds<bf16_t, 5, 320>::BYTES == 129488,
+              "the byte counts the comments give");
 constexpr float LN_EPS = 1e-6f;
 #ifndef XRES_TRAIN
 #define XRES_TRAIN 1
@@ -275,7 +293,7 @@ __global__ __launch_bounds__(NT, 2) void stage2p_kernel(Stage2pArgs a) {
   constexpr int C = SH::C, HID = SH::HID, NCHUNK = SH::NCHUNK, CO = SH::CO, KSD = SH::KSD, XLP = SH::XLP;
   constexpr int MF = SH::MF, NX = SH::NX;
   static_assert(NX == 0 || (TRAIN == 0 && !MP<T>::SPLIT && MP<T>::ESZ == 2), "320 channels: 16-bit inference only");
-  using LD = Lds<T, G, CW>;
+  using LD = Lds<T, G, CW, ROWS>;
   constexpr bool RM = ROWS > 0;
   static_assert(!RM || (TRAIN == 0 && ROWS == Geo<G>::NCOL && CW == 256), "row-tile form: inference, whole column blocks");
   constexpr int NPX = RM ? ROWS : Geo<G>::NPX, NCOL = Geo<G>::NCOL, NB = Geo<G>::NB;
@@ -317,7 +335,8 @@ __global__ __launch_bounds__(NT, 2) void stage2p_kernel(Stage2pArgs a) {
     reinterpret_cast<unsigned*>(xn + NPX * XNP)[i] = 0u;
     if (MP<T>::SPLIT) reinterpret_cast<unsigned*>(xn + XN_PLANE + NPX * XNP)[i] = 0u;
   }
-  for (int i = tid; i < NCOL * XLP; i += NT) xl[i] = 0.f;
+  // (the fp32 map is not cleared: every row below NPX is written from the accumulators before each phase that reads it --
+  //  absent alerts carry zeros there -- and no phase touches a row at or above NPX)
 
   // ---- residual stream: this wave's 32 channels x 48 pixels, acc[m][n][r] = x[16 n + col][32 wave + 16 m + 4 kg + r]
   f32x4 acc[MF][NB], accx[NB];
@@ -336,7 +355,6 @@ __global__ __launch_bounds__(NT, 2) void stage2p_kernel(Stage2pArgs a) {
     accx[n] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (NX > 0 && xlead && p < nlive) accx[n] = *reinterpret_cast<const f32x4*>(a.x_in + (row0 + p) * C + cx0);
   }
-  __syncthreads();   // zero fill done before the first map is written
 
   // this wave's fragment streams: fc1 tile (8 ch + wave) of a chunk: 8 KiB contiguous; fc2 tiles 2 wave, 2 wave + 1:
   // 2 x 4 KiB.  ONE register set, refilled in place: the slot a product has just read is requested again at once with
@@ -771,6 +789,15 @@ __global__ __launch_bounds__(NT, 2) void stage2p_kernel(Stage2pArgs a) {
   }
 
   S2P_STAMP(56);
+  // The thread's indices once more, from a value hipcc cannot trace to the ones above: what the rest of the kernel derives
+  // from them (the lane's byte offsets into the stage output, the downsample's filter and its result, 64-bit) was
+  // otherwise computed in the prologue and carried through the whole block loop -- in scratch, spilled there and reloaded
+  // here (3 to 19 registers by instantiation).  The rest of the kernel is the body of a lambda so that the names can be
+  // the same; it keeps the kernel's indentation.
+  int tid_end = threadIdx.x;
+  asm volatile("" : "+v"(tid_end));
+  [&](const int tid) {
+  const int lane = tid & 63, wave = tid >> 6, col = lane & 15, kg = lane >> 4;
   // ---- stage output (validation copy), then the downsample: LN per pixel + conv 2x2 s2 on pixels 0, 1, 3, 4
 #pragma unroll
   for (int m = 0; m < MF; ++m) {
@@ -810,24 +837,43 @@ __global__ __launch_bounds__(NT, 2) void stage2p_kernel(Stage2pArgs a) {
   using fragd = typename MP<TD>::frag;
   constexpr int XND = SH::XNP2 * MP<TD>::ESZ / 2;
   {
-    // (320 channels: a lane's fifth channel is 256 + lane)
+    // Only the rows the convolution reads -- pixels 0, 1, 3, 4 of each 3x3 map, 4 G of the 9 G -- in the block LayerNorm's
+    // form: half wave = pixel (two rows per wave trip), lane = 8 channels (320 channels: and 256 + 2 (lane & 31) + {0, 1}).
+    // The sums are associated as a whole wave with 4 (+ 1) channels per lane adds them -- each quad (with its fifth
+    // channel) on its own, then the two quads, which is that butterfly's first step, then half_sum, which is the rest of it.
     constexpr int CXD = C > 256 ? 256 : 0;
-    const f32x4 lw = *reinterpret_cast<const f32x4*>(a.ds_lnw + 4 * lane);
-    const f32x4 lb = *reinterpret_cast<const f32x4*>(a.ds_lnb + 4 * lane);
-    const float lwx = a.ds_lnw[CXD + lane], lbx = a.ds_lnb[CXD + lane];
-    for (int p = wave; p < NPX; p += NW) {
-      const f32x4 d = *reinterpret_cast<const f32x4*>(xl + p * XLP + 4 * lane);
-      const float dx = C > 256 ? xl[p * XLP + CXD + lane] : 0.f;
-      const float mean = wave_sum(d[0] + d[1] + d[2] + d[3] + dx) * (1.0f / C);
-      const f32x4 e = d - mean;
-      const float ex = C > 256 ? dx - mean : 0.f;
-      const float var = wave_sum(e[0] * e[0] + e[1] * e[1] + e[2] * e[2] + e[3] * e[3] + ex * ex) * (1.0f / C);
+    const int hl = lane & 31;
+    const f32x4 lw = *reinterpret_cast<const f32x4*>(a.ds_lnw + 8 * hl), lw2 = *reinterpret_cast<const f32x4*>(a.ds_lnw + 8 * hl + 4);
+    const f32x4 lb = *reinterpret_cast<const f32x4*>(a.ds_lnb + 8 * hl), lb2 = *reinterpret_cast<const f32x4*>(a.ds_lnb + 8 * hl + 4);
+    const float2 lwx = *reinterpret_cast<const float2*>(a.ds_lnw + CXD + 2 * hl), lbx = *reinterpret_cast<const float2*>(a.ds_lnb + CXD + 2 * hl);
+    for (int r = 2 * wave + (lane >> 5); r < 4 * G; r += 2 * NW) {
+      const int q = r & 3, p = 9 * (r >> 2) + 3 * (q >> 1) + (q & 1);
+      const f32x4 d0 = *reinterpret_cast<const f32x4*>(xl + p * XLP + 8 * hl);
+      const f32x4 d1 = *reinterpret_cast<const f32x4*>(xl + p * XLP + 8 * hl + 4);
+      float2 dx = make_float2(0.f, 0.f);
+      if (C > 256) dx = *reinterpret_cast<const float2*>(xl + p * XLP + CXD + 2 * hl);
+      const float s0 = d0[0] + d0[1] + d0[2] + d0[3] + dx.x, s1 = d1[0] + d1[1] + d1[2] + d1[3] + dx.y;
+      const float mean = half_sum(s0 + s1) * (1.0f / C);
+      const f32x4 e0 = d0 - mean, e1 = d1 - mean;
+      const float ex0 = C > 256 ? dx.x - mean : 0.f, ex1 = C > 256 ? dx.y - mean : 0.f;
+      const float q0 = e0[0] * e0[0] + e0[1] * e0[1] + e0[2] * e0[2] + e0[3] * e0[3] + ex0 * ex0;
+      const float q1 = e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2] + e1[3] * e1[3] + ex1 * ex1;
+      const float var = half_sum(q0 + q1) * (1.0f / C);
       const float rstd = rsqrtf(var + LN_EPS);
-      float y[4];
+      float y[8];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) y[i] = e[i] * rstd * lw[i] + lb[i];
-      MP<TD>::template st4<XN_PLANE>(xn + p * XND + 4 * MP<TD>::ESZ * lane, y);
-      if constexpr (C > 256) *reinterpret_cast<TD*>(xn + p * XND + (CXD + lane) * MP<TD>::ESZ) = (TD)(ex * rstd * lwx + lbx);
+      for (int i = 0; i < 4; ++i) {
+        y[i] = e0[i] * rstd * lw[i] + lb[i];
+        y[4 + i] = e1[i] * rstd * lw2[i] + lb2[i];
+      }
+      MP<TD>::template st8<XN_PLANE>(xn + p * XND + 8 * MP<TD>::ESZ * hl, y);
+      if constexpr (C > 256) {
+        typedef TD pair_t __attribute__((ext_vector_type(2)));
+        pair_t yx;
+        yx[0] = (TD)(ex0 * rstd * lwx.x + lbx.x);
+        yx[1] = (TD)(ex1 * rstd * lwx.y + lbx.y);
+        *reinterpret_cast<pair_t*>(xn + p * XND + (CXD + 2 * hl) * MP<TD>::ESZ) = yx;
+      }
     }
   }
   __syncthreads();
@@ -846,34 +892,55 @@ __global__ __launch_bounds__(NT, 2) void stage2p_kernel(Stage2pArgs a) {
     // out[alert][co] = b[co] + sum_k Wd[co][k] patch[alert][k],  k = (2 ky + kx) * 256 + c  ->  pixel 3 ky + kx.
     // Column = alert (4 live of 16); wave w: output tiles 4 w .. 4 w + 3 (16 channels each), 32 k-steps.
     const int al = col < G ? col : 0;
-    // this wave's 4 (5) tiles x 32 (40) k-steps = 128 (200) fragments, contiguous in memory (tile-major): a ring of 16 (20) in flight
+    // this wave's 4 (5) tiles x 32 (40) k-steps = 128 (200) fragments, contiguous in memory (tile-major): a ring of one whole
+    // tile, 32 (40) fragments, in flight -- the residual accumulators, the LayerNorm fragments and both block streams are
+    // dead here, so unlike the chunk loop this one has the registers (split: 8 fragments of 8 registers)
     constexpr int TPW = CO / 16 / NW, KSC = C / 32;
     const size_t fd0 = (size_t)(TPW * wave) * KSD;
-    constexpr int RING = MP<TD>::SPLIT ? 8 : C == 256 ? 16 : 20, NSTEP = TPW * KSD;
+    constexpr int RING = MP<TD>::SPLIT ? 8 : KSD, NSTEP = TPW * KSD;
     static_assert(KSD % RING == 0, "a tile's k-steps are whole ring rounds");
     constexpr int RPT = KSD / RING;   // ring rounds per tile
     fragd wq[RING];
 #pragma unroll
     for (int i = 0; i < RING; ++i) wq[i] = MP<TD>::gld(a.ds_wp, fd0 + i, lane);
     f32x4 o = *reinterpret_cast<const f32x4*>(a.ds_b + 16 * (TPW * wave) + 4 * kg);
-#pragma unroll 1
-    for (int g = 0; g < NSTEP / RING; ++g) {
+    constexpr int NR = NSTEP / RING;
+    // B fragment of k-step s of a tile: pixel 3 ky + kx of the column's alert, 32 channels
+    auto bfrag = [&](int s) {
+      const int q = s / KSC, pq = 3 * (q >> 1) + (q & 1);
+      return MP<TD>::template ld8<XN_PLANE>(xn + (9 * al + pq) * XND + (32 * (s - q * KSC) + 8 * kg) * MP<TD>::ESZ);
+    };
+    // One ring round.  B fragments are read two steps ahead into three register sets and every step ends at a scheduling
+    // barrier: left alone hipcc hoists a whole round's LDS reads above its first product (128 registers next to the
+    // ring's 128).  The refills are unconditional -- the last round, which has none, is a call of its own -- and the next
+    // tile's bias is requested in front of them, so the wait for it at the tile's end is a counted one.
+    auto round = [&](int g, auto LASTR) {
+      constexpr bool lastr = decltype(LASTR)::value;
+      // (s from the round's position in its tile: `s == KSD - 1` below is then false at compile time for every i but the last)
+      const int tq = g / RPT, s0 = (g - tq * RPT) * RING, tile = TPW * wave + tq;
+      const f32x4 onext = *reinterpret_cast<const f32x4*>(a.ds_b + 16 * (tq + 1 < TPW ? tile + 1 : tile) + 4 * kg);
+      fragd bf[3];
+      bf[0] = bfrag(s0);
+      bf[1] = bfrag(s0 + 1);
 #pragma unroll
       for (int i = 0; i < RING; ++i) {
-        // (s from the round's position in its tile: `s == KSD - 1` below is then false at compile time for every i but the last)
-        const int st = g * RING + i, tq = g / RPT, s = (g - tq * RPT) * RING + i, tile = TPW * wave + tq;
-        const int q = s / KSC, pq = 3 * (q >> 1) + (q & 1);
-        const fragd bf = MP<TD>::template ld8<XN_PLANE>(xn + (9 * al + pq) * XND + (32 * (s - q * KSC) + 8 * kg) * MP<TD>::ESZ);
-        o = MP<TD>::run(wq[i], bf, o);
-        if (st + RING < NSTEP) wq[i] = MP<TD>::gld(a.ds_wp, fd0 + st + RING, lane);
+        const int s = s0 + i;
+        if (i + 2 < RING) bf[(i + 2) % 3] = bfrag(s + 2);
+        o = MP<TD>::run(wq[i], bf[i % 3], o);
+        if (!lastr) wq[i] = MP<TD>::gld(a.ds_wp, fd0 + (size_t)(g + 1) * RING + i, lane);
         if (i == RING - 1 && s == KSD - 1) {   // tile finished (every KSD steps = RPT ring rounds)
           if (col < G && alert0 + col < a.B)
             *reinterpret_cast<f32x4*>(a.out + (size_t)(alert0 + col) * CO + 16 * tile + 4 * kg) = o;
-          if (st + 1 < NSTEP) o = *reinterpret_cast<const f32x4*>(a.ds_b + 16 * (tile + 1) + 4 * kg);
+          o = onext;
         }
+        __builtin_amdgcn_sched_barrier(0);
       }
-    }
+    };
+#pragma unroll 1
+    for (int g = 0; g < NR - 1; ++g) round(g, std::false_type{});
+    round(NR - 1, std::true_type{});
   }
+  }(tid_end);
   S2P_STAMP(58);
 }
 
@@ -953,7 +1020,7 @@ __global__ void pack_frag_fp8_kernel(const float* __restrict__ w, const float* _
 
 template <typename T, int G = S2P_ALERTS, int TRAIN = 0, int CW = 256, int ROWS = 0> int launch_stage2p_t(const Stage2pArgs& a, hipStream_t st) {
   auto kern = stage2p_kernel<T, G, TRAIN, CW, ROWS>;
-  constexpr int lds_bytes = TRAIN == 1 ? Lds<T, G, CW>::BYTES_TRAIN : Lds<T, G, CW>::BYTES;
+  constexpr int lds_bytes = TRAIN == 1 ? Lds<T, G, CW, ROWS>::BYTES_TRAIN : Lds<T, G, CW, ROWS>::BYTES;
   static_assert(lds_bytes <= 160 * 1024, "the images fit one CU");
   static DevOnce attr_set;
   if (attr_set.need()) {

@@ -44,7 +44,7 @@ if any(ls):
     print("stage1 loop stamps (steps 6, 7):", [ls[i + 1] - ls[i] for i in range(15)])
 s2 = t[32 + 16384:32 + 16384 + 64]
 print("stage2p (workgroup 0) total cycles", s2[58] - s2[0])
-print(f"   prologue (zero fill, x load)    +{s2[1] - s2[0]:8d}")
+print(f"   prologue (pad rows, x load)     +{s2[1] - s2[0]:8d}")
 for j in range(6):
     b = 1 + 8 * j
     nxt = s2[1 + 8 * (j + 1)] if j < 5 else s2[56]

@@ -10,34 +10,13 @@
 // and alerts.  Reductions over the batch use fp32 atomics into the (pre-zeroed) gradient arena.
 #include <stdlib.h>
 
-#include "common.h"
+#include "mfma.h"
 
 namespace {
 
-constexpr float LN_EPS = 1e-6f;
 
-template <typename T> struct Mw;
-template <> struct Mw<float> {
-  using frag = float;
-  static constexpr int KR = 4;   // reduction depth per MFMA
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct Mw<bf16_t> {
-  using frag = bf16x8;
-  static constexpr int KR = 32;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct Mw<f16_t> {
-  using frag = f16x8;
-  static constexpr int KR = 32;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-  }
-};
+template <typename T> struct Mw : Mfma<T> { static constexpr int KR = 32; };   // reduction depth per MFMA
+template <> struct Mw<float> : Mfma<float> { static constexpr int KR = 4; };
 
 // ---------------------------------------------------------------------------------------
 // wgrad: out[n][k] += sum_m D[m][n] * A[m][k]   (D: [M][N], A: [M][K], both row-major, type T)
@@ -96,7 +75,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const T* __restrict__ D,
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = MM::run(af[i], bf[j], acc[i][j]);
+        for (int j = 0; j < 2; ++j) acc[i][j] = MM::m16(af[i], bf[j], acc[i][j]);
     }
     __syncthreads();
   }
@@ -120,7 +99,6 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const T* __restrict__ D,
 // next stage's loads in flight under the current stage's products (registers -> the other LDS buffer, one barrier per
 // stage).  Both operands are reduction-major in memory, which is what the 32x32x2 fragments want: lane l reads element
 // [m + (l >> 5)][base + (l & 31)] -- 32 consecutive floats per half wave.  N % TN == K % TK == 0 (the launcher picks).
-typedef __attribute__((ext_vector_type(16))) float f32x16w;
 template <int TN, int TK>
 __global__ __launch_bounds__(64 * (TN / 64) * (TK / 64)) void wgrad_f32_kernel(const float* __restrict__ D,
                                                                                 const float* __restrict__ A,
@@ -140,7 +118,7 @@ __global__ __launch_bounds__(64 * (TN / 64) * (TK / 64)) void wgrad_f32_kernel(c
   const int n0 = blockIdx.x * TN, k0 = blockIdx.y * TK;
   const int mbeg = blockIdx.z * mslice, mend = min(M, mbeg + mslice);
   const int l31 = lane & 31, lh = lane >> 5;
-  f32x16w acc[2][2];
+  f32x16 acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll

@@ -16,6 +16,7 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(4))) _Float16 f16x4v;
 typedef __attribute__((ext_vector_type(2))) _Float16 f16x2v;
+constexpr float LN_EPS = 1e-6f;   // the LayerNorms of both networks
 // split operands: 8 / 4 / 2 values as f16 head + f16 remainder (the remainder of a value below ~2^-13 is an f16
 // subnormal: the matrix pipe takes subnormal f16 operands as they are, kernels are built with the default
 // denormal mode)
@@ -239,6 +240,24 @@ __device__ __forceinline__ float wave_sum(float v) {
   w = v;
   asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(v), "+v"(w));
   return v + w;
+}
+
+// the halves / the 16-lane rows of two values meet in one swap (gfx950)
+__device__ __forceinline__ float swap_add32(float a, float b) {
+  // a' = {a.lo, b.lo}, b' = {a.hi, b.hi}; a'+b': lanes 0-31 total of a, lanes 32-63 total of b
+  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float swap_add16(float a, float b) {
+  // odd 16-lane rows of a swap with even rows of b; a'+b': even rows total of a, odd rows of b
+  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+__device__ __forceinline__ double lane_bcast(double v, int k) {   // k wave-uniform
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), k);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), k);
+  return __hiloint2double(hi, lo);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -11,7 +11,6 @@
 
 namespace {
 
-constexpr float LN_EPS = 1e-6f;
 
 // ---------------------------------------------------------------------------------------
 // "transposing" wave reduction: each lane brings NV partial values; two swap-and-add steps
@@ -20,17 +19,6 @@ constexpr float LN_EPS = 1e-6f;
 // Afterwards v[j], j < NV/4, holds the 64-lane total of value index (lane>>4)*(NV/4) + j.
 // (A select-based variant makes hipcc index the value array dynamically: 16-way cndmask chains.)
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ float swap_add32(float a, float b) {
-  // a' = {a.lo, b.lo}, b' = {a.hi, b.hi}; a'+b': lanes 0-31 total of a, lanes 32-63 total of b
-  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float swap_add16(float a, float b) {
-  // odd 16-lane rows of a swap with even rows of b; a'+b': even rows total of a, odd rows of b
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
 template <int NV> __device__ __forceinline__ void treduce(float (&v)[NV]) {
   static_assert(NV == 4 || NV == 8 || NV == 16, "treduce");
 #pragma unroll

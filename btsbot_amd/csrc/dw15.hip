@@ -12,37 +12,13 @@
 //   * the normalised rows leave through a [pixel][channel] LDS image (overlays the planar one) as 16-byte pieces.
 // Workgroup = C / 16 waves, one alert at a time (two workgroups per CU).
 // The map enters the products rounded to the operand type (as in the fused stage-0 kernel); sums and LayerNorm are fp32.
-#include "common.h"
+#include "mfma.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-template <typename T> struct D4;
-template <> struct D4<bf16_t> {
-  static __device__ __forceinline__ f32x4 run(s16x4 a, s16x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct D4<f16_t> {
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  static __device__ __forceinline__ f32x4 run(s16x4 a, s16x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(h4, a), __builtin_bit_cast(h4, b), c, 0, 0, 0);
-  }
-};
-
 constexpr int HW = 15, P = 225;
 constexpr int PL_ROWS = 22, PL_XQ = PL_ROWS * 8, PL_CH = 800;   // (stage0b.hip: the channel stride is 4 mod 32 entries)
-constexpr float LN_EPS = 1e-6f;
 
-__device__ __forceinline__ float swap_add32(float a, float b) {
-  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float swap_add16(float a, float b) {
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
 template <int CTRL> __device__ __forceinline__ float dpp_mov(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
@@ -193,7 +169,7 @@ __global__ __launch_bounds__(L15<C>::NT * L15<C>::TEAMS, L15<C>::TEAMS == 2 ? 3 
             for (int xb = 0; xb < 4; ++xb) {
               const int q = xb + rbi - 1;
               if (q < 0 || q > 3) continue;
-              acc[yb][xb] = D4<T>::run(tw[ky * 3 + rbi], bq[s & 1][q], acc[yb][xb]);
+              acc[yb][xb] = MfmaRaw<T>::m4(tw[ky * 3 + rbi], bq[s & 1][q], acc[yb][xb]);
             }
         }
       }

@@ -20,7 +20,6 @@
 
 namespace {
 
-constexpr float LN_EPS = 1e-6f;
 
 template <int HW, int C, int NT, int NA>
 __global__ __launch_bounds__(NT) void dwln_bwd_kernel(const float* __restrict__ d, const float* __restrict__ dxn,

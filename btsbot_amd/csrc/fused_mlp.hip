@@ -21,25 +21,9 @@
 // barrier per chunk); for C = 64 the whole block's filters stay resident and the tile loop runs
 // barrier-free.  The packed filter image in HBM is byte-identical to the LDS image (row padding
 // included: 16 B per W1 row, 80-byte W2 rows), so staging is a flat 16-byte copy.
-#include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-template <typename T> struct M32;
-template <> struct M32<bf16_t> {
-  using frag = bf16x8;
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct M32<f16_t> {
-  using frag = f16x8;
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
 
 template <int C> struct FusedGeom {
   static constexpr int CP = (C + 31) / 32 * 32;         // GEMM2's output rows: C rounded up to whole 32-row tiles
@@ -63,7 +47,7 @@ __global__ __launch_bounds__(512, C <= 64 ? 4 : 2) void fused_mlp_kernel(
   // xres: where the residual rows are read (the training forward keeps a block's input); x itself when omitted
   using G = FusedGeom<C>;
   if (xres == nullptr) xres = x;
-  using frag = typename M32<T>::frag;
+  using frag = typename Mfma<T>::frag;
   constexpr int KS1 = C / 16;   // k-steps of GEMM1
   constexpr int CT = G::CP / 32;   // 32-channel output tiles of GEMM2 (the last one ragged when C % 32 != 0)
   static_assert(C % 16 == 0 && (4 * C) % 32 == 0 && G::NSUB % G::SUBS == 0, "geometry");
@@ -169,7 +153,7 @@ __global__ __launch_bounds__(512, C <= 64 ? 4 : 2) void fused_mlp_kernel(
 #pragma unroll
         for (int ks = 0; ks < KS1; ++ks) {
           const frag a = *reinterpret_cast<const frag*>(w1s + lr * G::W1ROW + ks * 32 + h * 16);
-          hacc = M32<T>::run(a, xf[ks], hacc);
+          hacc = Mfma<T>::m32(a, xf[ks], hacc);
         }
         // ---- bias + GELU; register r <-> hidden unit (r&3) + 8(r>>2) + 4h of this sub-chunk
         const float* bp = b1s + (chunk * G::SUBS + sub) * 32 + 4 * h;
@@ -193,7 +177,7 @@ __global__ __launch_bounds__(512, C <= 64 ? 4 : 2) void fused_mlp_kernel(
           for (int s = 0; s < 2; ++s) {
             const frag a = *reinterpret_cast<const frag*>(w2s + (ct * 32 + lr) * G::W2ROW +
                                                           s * 32 + h * 16);
-            yacc[ct] = M32<T>::run(a, hf[s], yacc[ct]);
+            yacc[ct] = Mfma<T>::m32(a, hf[s], yacc[ct]);
           }
         }
       }

@@ -15,36 +15,19 @@
 // the epilogue writes 8/16-byte vectors.
 #include <stdlib.h>
 
-#include "common.h"
+#include "mfma.h"
 
 namespace {
 
 constexpr int LDS_STRIDE = 144;  // bytes per staged row: 128 data + 16 pad
 
-template <typename T> struct Mma;
-template <> struct Mma<float> {
-  using frag = float;
+template <typename T> struct Mma : Mfma<T> {
+  static constexpr int KSTEP_BYTES = 64;  // 32 elements per v_mfma_f32_16x16x32
+  static constexpr int LANE_BYTES = 16;
+};
+template <> struct Mma<float> : Mfma<float> {
   static constexpr int KSTEP_BYTES = 16;  // 4 floats per v_mfma_f32_16x16x4_f32
   static constexpr int LANE_BYTES = 4;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct Mma<bf16_t> {
-  using frag = bf16x8;
-  static constexpr int KSTEP_BYTES = 64;  // 32 bf16 per v_mfma_f32_16x16x32_bf16
-  static constexpr int LANE_BYTES = 16;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct Mma<f16_t> {
-  using frag = f16x8;
-  static constexpr int KSTEP_BYTES = 64;
-  static constexpr int LANE_BYTES = 16;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-  }
 };
 
 template <typename T, int TM, int TN, int WM, int WN, int EPI, bool GATED = false>
@@ -144,7 +127,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const T* __restrict__ X,
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = MM::run(afr[ni], bfr[mi], acc[ni][mi]);
+        for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = MM::m16(afr[ni], bfr[mi], acc[ni][mi]);
     }
     __syncthreads();
   }

@@ -16,26 +16,9 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-template <typename T> struct Mma2;
-template <> struct Mma2<bf16_t> {
-  using frag = bf16x8;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct Mma2<f16_t> {
-  using frag = f16x8;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-  }
-};
 
 template <int N> __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -51,7 +34,7 @@ __global__ __launch_bounds__(256) void gemm2_kernel(const T* __restrict__ X,
                                                     const float* __restrict__ ln_w = nullptr,
                                                     const float* __restrict__ ln_b = nullptr,
                                                     T* __restrict__ ln_out = nullptr) {
-  using MM = Mma2<T>;
+  using MM = Mfma<T>;
   // batched form (gridDim.z > 1): problem z reads X + z*bsX, W + z*bsW and writes out/resid + z*bsO
   X += blockIdx.z * bsX;
   W += blockIdx.z * bsW;
@@ -163,7 +146,7 @@ __global__ __launch_bounds__(256) void gemm2_kernel(const T* __restrict__ X,
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = MM::run(afr[ni], bfr[mi], acc[ni][mi]);
+        for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = MM::m16(afr[ni], bfr[mi], acc[ni][mi]);
     }
   }
   __syncthreads();  // ring is idle from here on (no LDS-DMA in flight: last wait was vmcnt(0))

@@ -15,25 +15,10 @@
 // layer's rows.  16 alerts per workgroup rather than 32: the chain's length is instructions per wave, not FLOPs.
 // (Single f16 filters with split activations were tried: frozen_fusion's unnormalised features put the bf16 mode's
 //  score error at 3.3e-3 against 2e-3 with the filters' remainder kept.)
-#include "common.h"
+#include "mfma.h"
 #include "head16.h"
 
 namespace {
-
-
-template <typename T> struct HM;
-template <> struct HM<bf16_t> {
-  using frag = bf16x8;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct HM<f16_t> {
-  using frag = f16x8;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-  }
-};
 
 #define H_STAMP(i)                                                                         \
   do {                                                                                     \
@@ -78,7 +63,7 @@ __device__ __forceinline__ void dense16(const Rows& in, const H16Layer& L, const
                                         float* logits, float* scores, int b0, int B, unsigned long long* stamps) {
 #define D_STAMP(i) do { if (stamps != nullptr && col0 != 0 && blockIdx.x == 0 && threadIdx.x == 0) stamps[i] = clock64(); } while (0)
   D_STAMP(10);
-  using frag = typename HM<T>::frag;
+  using frag = typename Mfma<T>::frag;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lc = lane & 15, q = lane >> 4;
   const int KS = kpad(L.K) / 32, tiles = rup(L.N, 16) / 16;
   int split = 1;
@@ -134,9 +119,9 @@ __device__ __forceinline__ void dense16(const Rows& in, const H16Layer& L, const
       }
 #pragma unroll
       for (int j = 0; j < KGRAN; ++j) {
-        acc = HM<T>::run(ah[j], xh[j], acc);
-        acc1 = HM<T>::run(al[j], xh[j], acc1);
-        acc2 = HM<T>::run(ah[j], xl[j], acc2);
+        acc = Mfma<T>::m16(ah[j], xh[j], acc);
+        acc1 = Mfma<T>::m16(al[j], xh[j], acc1);
+        acc2 = Mfma<T>::m16(ah[j], xl[j], acc2);
       }
 #pragma unroll
       for (int j = 0; j < KGRAN; ++j) {

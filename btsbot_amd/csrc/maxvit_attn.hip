@@ -18,25 +18,9 @@
 // LDS: 64 rows x 96 B per wave (the 96-byte pitch makes the transposed reads conflict-free); rows 49..63
 // are zeroed once so that padded keys contribute exact zeros.
 #include "maxvit.h"
+#include "mfma.h"
 
 namespace {
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-
-template <typename T> struct AM;
-template <> struct AM<bf16_t> {
-  using frag = bf16x8;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct AM<f16_t> {
-  using frag = f16x8;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-  }
-};
 
 constexpr int VPITCH = 96;
 
@@ -45,7 +29,7 @@ __global__ __launch_bounds__(256) void mv_attn_mfma_kernel(const T* __restrict__
                                                            const float* __restrict__ bias64,
                                                            T* __restrict__ out, int H, int C,
                                                            int grid_mode, int units, int upw) {
-  using frag = typename AM<T>::frag;
+  using frag = typename Mfma<T>::frag;
   __shared__ __attribute__((aligned(16))) unsigned char vsm[4][64 * VPITCH];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l15 = lane & 15, g = lane >> 4;
@@ -100,7 +84,7 @@ __global__ __launch_bounds__(256) void mv_attn_mfma_kernel(const T* __restrict__
     for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
       for (int it = 0; it < 4; ++it)
-        s[jt][it] = AM<T>::run(kf[jt], qf[it], f32x4{0.f, 0.f, 0.f, 0.f});
+        s[jt][it] = Mfma<T>::m16(kf[jt], qf[it], f32x4{0.f, 0.f, 0.f, 0.f});
     // ---- softmax over the keys of each query (unnormalised; 1/sum goes onto O)
     float inv[4];
 #pragma unroll
@@ -160,8 +144,8 @@ __global__ __launch_bounds__(256) void mv_attn_mfma_kernel(const T* __restrict__
         }
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
-        f32x4 acc = AM<T>::run(vf[dt][0], pf[0], f32x4{0.f, 0.f, 0.f, 0.f});
-        o[dt][it] = AM<T>::run(vf[dt][1], pf[1], acc);
+        f32x4 acc = Mfma<T>::m16(vf[dt][0], pf[0], f32x4{0.f, 0.f, 0.f, 0.f});
+        o[dt][it] = Mfma<T>::m16(vf[dt][1], pf[1], acc);
       }
     }
     // ---- store: lane owns d = dt*16 + 4g .. +3 of query it*16 + l15
@@ -246,7 +230,7 @@ __global__ __launch_bounds__(256, 2) void mv_stem2_kernel(const T* __restrict__ 
   // ([B,56,56,64] f32 -- the first MBConv block's shortcut is the only consumer of the fp32 map) instead of
   // the full map [B,112,112,64]: the horizontal neighbour comes from the adjacent lane (quad_perm [1,0,3,2]),
   // the vertical one from the pair's first row, summed in avg_pool2d's order ((a+b)+c)+d.
-  using frag = typename AM<T>::frag;
+  using frag = typename Mfma<T>::frag;
   const int lane = threadIdx.x & 63, l15 = lane & 15, g = lane >> 4;
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
   frag wf[4][9];
@@ -300,7 +284,7 @@ __global__ __launch_bounds__(256, 2) void mv_stem2_kernel(const T* __restrict__ 
 #pragma unroll
           for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
-            for (int mt = 0; mt < 4; ++mt) acc[mt] = AM<T>::run(wf[mt][ky * 3 + kx], xf[sub + ky][kx], acc[mt]);
+            for (int mt = 0; mt < 4; ++mt) acc[mt] = Mfma<T>::m16(wf[mt][ky * 3 + kx], xf[sub + ky][kx], acc[mt]);
         const long po = ((b * 112 + y) * 112 + x) * 64 + 4 * g;
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {

@@ -21,25 +21,9 @@
 // Workgroups are persistent over partitions (filters stay in LDS).  Tokens 49..63 of the padded tile repeat
 // token 48 and are masked as keys / never stored as queries.
 #include "maxvit.h"
+#include "mfma.h"
 
 namespace {
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-
-template <typename T> struct BM;
-template <> struct BM<bf16_t> {
-  using frag = bf16x8;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct BM<f16_t> {
-  using frag = f16x8;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-  }
-};
 
 constexpr int C = 64, C3 = 192;
 constexpr int IPITCH = 416;                 // bytes per token row of the qkv image (192 x 2 + 32)
@@ -51,7 +35,7 @@ __global__ __launch_bounds__(256, 2) void mv_attn_block64_kernel(
     const float* __restrict__ bqkv, const T* __restrict__ wproj, const float* __restrict__ bproj,
     const float* __restrict__ bias64, const float* __restrict__ ln_w, const float* __restrict__ ln_b,
     int H, int grid_mode, int units) {
-  using frag = typename BM<T>::frag;
+  using frag = typename Mfma<T>::frag;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* img = smem;                              // [64][IPITCH]
   unsigned char* wq = smem + 64 * IPITCH;                 // [192][WPITCH]
@@ -114,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void mv_attn_block64_kernel(
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
           const frag a = *reinterpret_cast<const frag*>(wq + (ct * 16 + l15) * WPITCH + ks * 64 + g * 16);
-          acc = BM<T>::run(a, xf[ks], acc);
+          acc = Mfma<T>::m16(a, xf[ks], acc);
         }
         const float4 bv = *reinterpret_cast<const float4*>(bqkv + ct * 16 + 4 * g);
         T4 v;
@@ -145,7 +129,7 @@ __global__ __launch_bounds__(256, 2) void mv_attn_block64_kernel(
 #pragma unroll
       for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
-        for (int q = 0; q < 2; ++q) s[jt][q] = BM<T>::run(kf[jt], qf[q], f32x4{0.f, 0.f, 0.f, 0.f});
+        for (int q = 0; q < 2; ++q) s[jt][q] = Mfma<T>::m16(kf[jt], qf[q], f32x4{0.f, 0.f, 0.f, 0.f});
       float inv[2];
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
@@ -203,8 +187,8 @@ __global__ __launch_bounds__(256, 2) void mv_attn_block64_kernel(
           }
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
-          f32x4 acc = BM<T>::run(vf[dt][0], pf[0], f32x4{0.f, 0.f, 0.f, 0.f});
-          acc = BM<T>::run(vf[dt][1], pf[1], acc);
+          f32x4 acc = Mfma<T>::m16(vf[dt][0], pf[0], f32x4{0.f, 0.f, 0.f, 0.f});
+          acc = Mfma<T>::m16(vf[dt][1], pf[1], acc);
           // O[token (it0+q)*16 + l15][head*32 + dt*16 + 4g .. +3] -> this head's (dead) Q columns
           T4 v;
 #pragma unroll
@@ -228,7 +212,7 @@ __global__ __launch_bounds__(256, 2) void mv_attn_block64_kernel(
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
           const frag a = *reinterpret_cast<const frag*>(wp + (ct * 16 + l15) * WPITCH + ks * 64 + g * 16);
-          acc = BM<T>::run(a, of[ks], acc);
+          acc = Mfma<T>::m16(a, of[ks], acc);
         }
         const int c = ct * 16 + 4 * g;
         const float4 bv = *reinterpret_cast<const float4*>(bproj + c);

@@ -17,22 +17,9 @@
 // so m1 never leaves the CU.  Tiles: stride 2 -> 7x7 outputs (15x15 halo = 15 MFMA pixel tiles), stride 1 ->
 // 14x14 outputs (16x16 halo = 16 pixel tiles exactly); halo recompute costs 15 % / 30 % more conv1 work.
 #include "maxvit.h"
+#include "mfma.h"
 
 namespace {
-
-template <typename T> struct FM;
-template <> struct FM<bf16_t> {
-  using frag = bf16x8;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct FM<f16_t> {
-  using frag = f16x8;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-  }
-};
 
 template <int STRIDE> struct Geo {
   static constexpr int TO = STRIDE == 2 ? 7 : 14;          // output tile side
@@ -55,7 +42,7 @@ __global__ __launch_bounds__(256) void mv_mbconv_front_kernel(const T* __restric
                                                               T* __restrict__ m2,
                                                               float* __restrict__ part, int H, int MID) {
   using G = Geo<STRIDE>;
-  using frag = typename FM<T>::frag;
+  using frag = typename Mfma<T>::frag;
   constexpr int KS = CIN / 32;
   constexpr int XPITCH = CIN * 2 + 16;    // bytes per pixel row of the input halo image
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -151,7 +138,7 @@ __global__ __launch_bounds__(256) void mv_mbconv_front_kernel(const T* __restric
       for (int mt = 0; mt < 4; ++mt) {
         f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) acc = FM<T>::run(wf[mt][ks], xf[ks], acc);
+        for (int ks = 0; ks < KS; ++ks) acc = Mfma<T>::m16(wf[mt][ks], xf[ks], acc);
         typedef T __attribute__((ext_vector_type(4))) T4;
         T4 v;
         // (a factor, not a branch: straight-line code lets the next tile's MFMAs issue under this one's SiLU; the

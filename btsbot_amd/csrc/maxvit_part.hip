@@ -31,28 +31,11 @@
 //   phase 6  rows back to x (tokens 49..63 of the padded tile repeat token 48, are masked as keys and never stored); behind
 //            a block's grid half also the next block's pre-norm copy (T)(x * s + t) (post_out)
 #include "maxvit.h"
+#include "mfma.h"
 
 namespace {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-
-template <typename T> struct PM;
-template <> struct PM<bf16_t> {
-  using frag = bf16x8;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct PM<f16_t> {
-  using frag = f16x8;
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-  }
-};
-
 constexpr int NB = 4;
-constexpr float LN_EPS = 1e-6f;
 
 // sum over the wave's four 16-lane rows (the lanes that share lane & 15); every lane ends with the total.  The rows meet
 // through v_permlane16_swap / v_permlane32_swap as in common.h's wave_sum (inline asm for the reason given there).
@@ -125,7 +108,7 @@ __global__ __launch_bounds__(PG<C_>::NT, 2) void mv_part_kernel(PartArgs a) {
   using P = PG<C_>;
   constexpr int C = C_, HEADS = P::HEADS, PARTS = P::PARTS, KS = P::KS, QT = P::QT, NCHQ = P::NCHQ, HT = P::HT;
   constexpr int NCHM = P::NCHM, IP = P::IP, XNP = P::XNP, NTOK = P::NTOK, HCH = P::HCH, HP = P::HP, KF = P::KF;
-  using frag = typename PM<T>::frag;
+  using frag = typename Mfma<T>::frag;
   typedef T __attribute__((ext_vector_type(4))) T4;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, kg = lane >> 4;
@@ -287,7 +270,7 @@ __global__ __launch_bounds__(PG<C_>::NT, 2) void mv_part_kernel(PartArgs a) {
 #pragma unroll
         for (int q = 0; q < QT; ++q) {
 #pragma unroll
-          for (int n = 0; n < NB; ++n) hacc[q][n] = PM<T>::run(a1[q][s], xb[s & 1][n], hacc[q][n]);
+          for (int n = 0; n < NB; ++n) hacc[q][n] = Mfma<T>::m16(a1[q][s], xb[s & 1][n], hacc[q][n]);
           a1[q][s] = wq[(size_t)(((nch * HEADS + wo) * QT + q) * KS + s) * 64];
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -351,7 +334,7 @@ __global__ __launch_bounds__(PG<C_>::NT, 2) void mv_part_kernel(PartArgs a) {
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
-          for (int q = 0; q < 2; ++q) s[jt][q] = PM<T>::run(kf[jt], qf[q], f32x4{0.f, 0.f, 0.f, 0.f});
+          for (int q = 0; q < 2; ++q) s[jt][q] = Mfma<T>::m16(kf[jt], qf[q], f32x4{0.f, 0.f, 0.f, 0.f});
         float inv[2];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -394,8 +377,8 @@ __global__ __launch_bounds__(PG<C_>::NT, 2) void mv_part_kernel(PartArgs a) {
             }
 #pragma unroll
           for (int dt = 0; dt < 2; ++dt) {
-            f32x4 o = PM<T>::run(vf[dt][0], pf[0], f32x4{0.f, 0.f, 0.f, 0.f});
-            o = PM<T>::run(vf[dt][1], pf[1], o);
+            f32x4 o = Mfma<T>::m16(vf[dt][0], pf[0], f32x4{0.f, 0.f, 0.f, 0.f});
+            o = Mfma<T>::m16(vf[dt][1], pf[1], o);
             // O[token (it0 + q) * 16 + col][head * 32 + dt * 16 + 4 kg ..] -> this head's (dead) Q columns of that token
             T4 v;
 #pragma unroll
@@ -431,7 +414,7 @@ __global__ __launch_bounds__(PG<C_>::NT, 2) void mv_part_kernel(PartArgs a) {
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
-          for (int n = 0; n < NB; ++n) acc[m][n] = PM<T>::run(a2[m][s], of[s & 1][n], acc[m][n]);
+          for (int n = 0; n < NB; ++n) acc[m][n] = Mfma<T>::m16(a2[m][s], of[s & 1][n], acc[m][n]);
       }
     }
     PT_STAMP(7);
@@ -479,7 +462,7 @@ __global__ __launch_bounds__(PG<C_>::NT, 2) void mv_part_kernel(PartArgs a) {
 #pragma unroll
             for (int q = 0; q < HT; ++q) {
 #pragma unroll
-              for (int n = 0; n < NB; ++n) hacc[q][n] = PM<T>::run(f1[q][s], xb[s & 1][n], hacc[q][n]);
+              for (int n = 0; n < NB; ++n) hacc[q][n] = Mfma<T>::m16(f1[q][s], xb[s & 1][n], hacc[q][n]);
               f1[q][s] = w1[(size_t)(((nch * HEADS + wo) * HT + q) * KS + s) * 64];
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -511,7 +494,7 @@ __global__ __launch_bounds__(PG<C_>::NT, 2) void mv_part_kernel(PartArgs a) {
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
-              for (int n = 0; n < NB; ++n) acc[m][n] = PM<T>::run(f2[m][s], hf[s & 1][n], acc[m][n]);
+              for (int n = 0; n < NB; ++n) acc[m][n] = Mfma<T>::m16(f2[m][s], hf[s & 1][n], acc[m][n]);
           }
         }
         if (ch < 2) PT_STAMP(11 + 3 * ch);
@@ -576,7 +559,7 @@ static_assert(2 * LDS_BYTES <= 160 * 1024 && 64 * IP <= A_BYTES, "two workgroups
 template <typename T, bool MLP>
 __global__ __launch_bounds__(p64::NT, 2) void mv_part64_kernel(PartArgs a) {
   using namespace p64;
-  using frag = typename PM<T>::frag;
+  using frag = typename Mfma<T>::frag;
   typedef T __attribute__((ext_vector_type(4))) T4;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* img = smem + OFF_A;
@@ -730,7 +713,7 @@ __global__ __launch_bounds__(p64::NT, 2) void mv_part64_kernel(PartArgs a) {
         for (int n = 0; n < NB; ++n) {
           f32x4 hacc = bv;
 #pragma unroll
-          for (int s = 0; s < KS; ++s) hacc = PM<T>::run(fq[q][s], xb[s][n], hacc);
+          for (int s = 0; s < KS; ++s) hacc = Mfma<T>::m16(fq[q][s], xb[s][n], hacc);
           T4 v;
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = (T)hacc[r];
@@ -772,7 +755,7 @@ __global__ __launch_bounds__(p64::NT, 2) void mv_part64_kernel(PartArgs a) {
 #pragma unroll
       for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
-        for (int q = 0; q < 2; ++q) sc[jt][q] = PM<T>::run(kf[jt], qf[q], f32x4{0.f, 0.f, 0.f, 0.f});
+        for (int q = 0; q < 2; ++q) sc[jt][q] = Mfma<T>::m16(kf[jt], qf[q], f32x4{0.f, 0.f, 0.f, 0.f});
       float inv[2];
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
@@ -809,8 +792,8 @@ __global__ __launch_bounds__(p64::NT, 2) void mv_part64_kernel(PartArgs a) {
           }
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
-          f32x4 o = PM<T>::run(vf[dt][0], pf[0], f32x4{0.f, 0.f, 0.f, 0.f});
-          o = PM<T>::run(vf[dt][1], pf[1], o);
+          f32x4 o = Mfma<T>::m16(vf[dt][0], pf[0], f32x4{0.f, 0.f, 0.f, 0.f});
+          o = Mfma<T>::m16(vf[dt][1], pf[1], o);
           T4 v;
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = (T)(o[r] * inv[q]);
@@ -829,7 +812,7 @@ __global__ __launch_bounds__(p64::NT, 2) void mv_part64_kernel(PartArgs a) {
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
           const frag of = *reinterpret_cast<const frag*>(img + (16 * n + col) * IP + (s * 96 + 8 * kg) * 2);
-          acc[n] = PM<T>::run(fp[s], of, acc[n]);
+          acc[n] = Mfma<T>::m16(fp[s], of, acc[n]);
         }
       }
     }
@@ -850,7 +833,7 @@ __global__ __launch_bounds__(p64::NT, 2) void mv_part64_kernel(PartArgs a) {
           for (int n = 0; n < NB; ++n) {
             f32x4 hacc = bv;
 #pragma unroll
-            for (int s = 0; s < KS; ++s) hacc = PM<T>::run(f1[q][s], xb[s][n], hacc);
+            for (int s = 0; s < KS; ++s) hacc = Mfma<T>::m16(f1[q][s], xb[s][n], hacc);
             T4 v;
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = (T)gelu_for<T>(hacc[r]);
@@ -868,7 +851,7 @@ __global__ __launch_bounds__(p64::NT, 2) void mv_part64_kernel(PartArgs a) {
 #pragma unroll
           for (int n = 0; n < NB; ++n) {
             const frag hf = *reinterpret_cast<const frag*>(hid + (16 * n + col) * HPP + (32 * s + 8 * kg) * 2);
-            acc[n] = PM<T>::run(f2[s], hf, acc[n]);
+            acc[n] = Mfma<T>::m16(f2[s], hf, acc[n]);
           }
       }
     }

@@ -35,7 +35,7 @@
 // GELU(1) | C(1)).  Measured and what bounds it: DESIGN.md section 5b, profiles/r03_mlp_bwd_kernel.txt.
 #include <stdlib.h>
 
-#include "common.h"
+#include "mfma.h"
 
 #ifndef MLP_BWD_STAMP
 #define MLP_BWD_STAMP 0   // development only: per-phase s_memtime stamps of the 4th tile of workgroup 0 (into `stamps`)
@@ -57,34 +57,11 @@ __device__ unsigned long long mlp_bwd_stamps[8 * 16];
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 
-template <typename T> struct MB;
-template <> struct MB<bf16_t> {
-  static constexpr int DEG = GeluDeg<bf16_t>::value;
-  static __device__ __forceinline__ f32x16 m32(s16x8 a, s16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ f32x4 m16(s16x8 a, s16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ short cvt(float v) { return __builtin_bit_cast(short, (bf16_t)v); }
-  static __device__ __forceinline__ float tofloat(unsigned short v) { return __builtin_bit_cast(float, (unsigned)v << 16); }
-};
-template <> struct MB<f16_t> {
-  static constexpr int DEG = GeluDeg<f16_t>::value;
-  static __device__ __forceinline__ f32x16 m32(s16x8 a, s16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ f32x4 m16(s16x8 a, s16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ short cvt(float v) { return __builtin_bit_cast(short, (f16_t)v); }
-  static __device__ __forceinline__ float tofloat(unsigned short v) { return (float)__builtin_bit_cast(f16_t, v); }
+template <typename T> struct MB : MfmaRaw<T> {
+  static constexpr int DEG = GeluDeg<T>::value;
+  static __device__ __forceinline__ short cvt(float v) { return __builtin_bit_cast(short, (T)v); }
 };
 
 // gelu_poly and its derivative from one exponential (common.h: gelu_poly / gelu_poly_grad)
@@ -367,7 +344,7 @@ __global__ __launch_bounds__(64 * NW) void mlp_bwd_kernel(const T* __restrict__ 
     MB_STAMP(5);
 #pragma unroll
     for (int r = 0; r < G::TR / SGRP; ++r)
-      ssum += M::tofloat(*reinterpret_cast<const unsigned short*>(Y + (srg + SGRP * r) * PX + scol * 2));
+      ssum += bits_to_f32<T>(*reinterpret_cast<const unsigned short*>(Y + (srg + SGRP * r) * PX + scol * 2));
     __builtin_amdgcn_sched_barrier(0);   // (keeps the wait for the fetched rows down here)
     if (dxn_late && tprev >= 0) dxn_tile(tprev, sm + G::OFF_DA + (p ^ 1) * G::DAB);
     MB_STAMP(6);

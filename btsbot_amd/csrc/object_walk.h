@@ -41,12 +41,6 @@ __device__ __forceinline__ int load_alert(const In& in, int p, bool inside, doub
   return a;
 }
 
-__device__ __forceinline__ double lane_bcast(double v, int k) {   // k wave-uniform
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), k);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), k);
-  return __hiloint2double(hi, lo);
-}
-
 // the body of a kernel launched with WG threads and ceil(n_objects / OBJ_PER_WG) workgroups
 template <class Acc, class In>
 __device__ __forceinline__ void walk(const In& in, const int32_t* __restrict__ seg_offsets, int n_objects) {

@@ -158,12 +158,6 @@ __device__ __forceinline__ int load_alert(const Inputs& in, const Policies& pol,
   return a;
 }
 
-__device__ __forceinline__ double lane_bcast(double v, int k) {   // k wave-uniform
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), k);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), k);
-  return __hiloint2double(hi, lo);
-}
-
 template <int NP>
 __global__ __launch_bounds__(WG) void policy_eval_kernel(Inputs in, Policies pol, const int32_t* __restrict__ seg_offsets,
                                                          int n_objects) {

@@ -20,25 +20,9 @@
 // test_full_backward_16bit[*-stage2_two_gemms]; the default cases run this kernel in both 16-bit modes).
 #include <stdlib.h>
 
-#include "common.h"
+#include "mfma.h"
 
 namespace {
-
-template <typename T> struct SM;
-template <> struct SM<bf16_t> {
-  typedef bf16_t frag __attribute__((ext_vector_type(8)));
-  typedef bf16_t quad __attribute__((ext_vector_type(4)));
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct SM<f16_t> {
-  typedef f16_t frag __attribute__((ext_vector_type(8)));
-  typedef f16_t quad __attribute__((ext_vector_type(4)));
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-  }
-};
 
 // da leaves through buffer stores (scalar descriptor, 32-bit lane offset, scalar chunk offset), as whole 256-byte row pieces
 // out of its LDS image one step behind: stage2p.hip's keeping form says why (scattered quads: 64 separate 8-byte writes per
@@ -71,8 +55,8 @@ struct S2MlpBwdArgs {
 
 template <typename T>
 __global__ __launch_bounds__(NT, 2) void s2mlp_bwd_kernel(S2MlpBwdArgs a) {
-  using frag = typename SM<T>::frag;
-  using quad = typename SM<T>::quad;
+  using frag = typename Mfma<T>::frag;
+  typedef T quad __attribute__((ext_vector_type(4)));
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* yi = smem + OFF_Y;
   unsigned char* hb = smem + OFF_H;
@@ -161,7 +145,7 @@ __global__ __launch_bounds__(NT, 2) void s2mlp_bwd_kernel(S2MlpBwdArgs a) {
           yb[(s + 1) & 1][n] = *reinterpret_cast<const frag*>(yi + (16 * n + col) * YP + (32 * (s + 1) + 8 * kg) * 2);
       }
 #pragma unroll
-      for (int n = 0; n < NB; ++n) t[n] = SM<T>::run(a1[s], yb[s & 1][n], t[n]);
+      for (int n = 0; n < NB; ++n) t[n] = Mfma<T>::m16(a1[s], yb[s & 1][n], t[n]);
       a1[s] = w2f[(size_t)((nch * NW + wave) * KS1 + s) * 64];
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -186,7 +170,7 @@ __global__ __launch_bounds__(NT, 2) void s2mlp_bwd_kernel(S2MlpBwdArgs a) {
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
-          for (int n = 0; n < NB; ++n) acc[m][n] = SM<T>::run(a2[m][s], hbf[s & 1][n], acc[m][n]);
+          for (int n = 0; n < NB; ++n) acc[m][n] = Mfma<T>::m16(a2[m][s], hbf[s & 1][n], acc[m][n]);
       }
       if (s < KS2) {   // refill with THIS chunk's fragments (used in the next step)
         a2[0][s] = w1f[(size_t)((2 * wave) * KH + ch * KS2 + s) * 64];
@@ -217,7 +201,7 @@ __global__ __launch_bounds__(NT, 2) void s2mlp_bwd_kernel(S2MlpBwdArgs a) {
 #pragma unroll
       for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int n = 0; n < NB; ++n) acc[m][n] = SM<T>::run(a2[m][s], hbf[n], acc[m][n]);
+        for (int n = 0; n < NB; ++n) acc[m][n] = Mfma<T>::m16(a2[m][s], hbf[n], acc[m][n]);
     }
   }
   // dxn: lane holds channels 32 wave + 16 m + 4 kg + 0..3 of pixel 16 n + col

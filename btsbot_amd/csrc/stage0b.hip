@@ -27,42 +27,14 @@
 //   * a wave owns 64 pixels (2 column blocks of the 32x32 MFMA): residual = 64 registers.
 #include <type_traits>
 
-#include "common.h"
 #include "stage0.h"
+#include "stage_regs.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-template <typename T> struct SBM;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-template <> struct SBM<bf16_t> {
-  using frag = bf16x8;
-  using frag4 = s16x4;
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-  // 16 independent 4x4x4 products (one per channel): lane = (block, row of A / column of B and D)
-  static __device__ __forceinline__ f32x4 run4(frag4 a, frag4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct SBM<f16_t> {
-  using frag = f16x8;
-  using frag4 = f16x4;
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ f32x4 run4(frag4 a, frag4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_4x4x4f16(a, b, c, 0, 0, 0);
-  }
-};
-
 constexpr int C = 64, HW = 15, P = 225, CT = 2, HID = 256;
 constexpr int PITCH = 2 * C + 16;                 // [pixel][channel] image: 144 bytes per pixel row
+static_assert(C == StageRegs<CT>::C && PITCH == StageRegs<CT>::PITCH, "ln_regs / regs_to_map derive both from CT");
 static_assert(256 * PITCH <= C * 800, "the [pixel][channel] image overlays the planar one");
 // planar image for the depthwise phase: [channel][x quad 0..3][row -3..18][4 x] in the operand type.
 // 8-byte entries (4 consecutive x of one row); 22 rows of a quad are contiguous, so the four lanes j of a
@@ -104,7 +76,6 @@ template <bool X2> struct S0L {
 static_assert(S0L<false>::LDS_BYTES <= 81920, "two workgroups per CU");
 static_assert(S0L<true>::LDS_BYTES <= 160 * 1024, "one workgroup per CU");
 static_assert(LNIMGB <= S0L<true>::OFF_RING && LNIMGB <= S0L<false>::OFF_RING, "the fp32 image in front of ring slots 0 and 1");
-constexpr float LN_EPS = 1e-6f;
 
 #define SB_STAMP(i)                                                                \
   do {                                                                             \
@@ -117,65 +88,6 @@ constexpr float LN_EPS = 1e-6f;
   } while (0)
 
 struct __attribute__((packed, aligned(4))) f4u { float v[4]; };
-
-template <int N> __device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ int swz4(int row) {   // F[(row >> 2) & 3], F = {0,3,2,1}
-  return (4 - ((row >> 2) & 3)) & 3;
-}
-// LayerNorm over the 64 channels of this lane's pixel (x[2][16] here + the partner lane ^ 32)
-__device__ __forceinline__ void ln_regs(const f32x16 (&x)[CT], const float* __restrict__ w,
-                                        const float* __restrict__ b, int h, f32x16 (&y)[CT]) {
-  float s = 0.f;
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s += x[ct][r];
-  s += __shfl_xor(s, 32, 64);
-  const float mean = s * (1.0f / C);
-  float q = 0.f;
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float d = x[ct][r] - mean;
-      q += d * d;
-    }
-  q += __shfl_xor(q, 32, 64);
-  const float rstd = rsqrtf(q * (1.0f / C) + LN_EPS);
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      const int c = ct * 32 + 8 * qd + 4 * h;
-      const float4 wv = *reinterpret_cast<const float4*>(w + c);
-      const float4 bv = *reinterpret_cast<const float4*>(b + c);
-      y[ct][4 * qd + 0] = (x[ct][4 * qd + 0] - mean) * rstd * wv.x + bv.x;
-      y[ct][4 * qd + 1] = (x[ct][4 * qd + 1] - mean) * rstd * wv.y + bv.y;
-      y[ct][4 * qd + 2] = (x[ct][4 * qd + 2] - mean) * rstd * wv.z + bv.z;
-      y[ct][4 * qd + 3] = (x[ct][4 * qd + 3] - mean) * rstd * wv.w + bv.w;
-    }
-}
-
-// LOPLANE > 0: also the values' f16 remainders, LOPLANE bytes behind (split mode)
-template <typename T, int LOPLANE = 0>
-__device__ __forceinline__ void regs_to_map(const f32x16 (&x)[CT], unsigned char* map, int p, int h) {
-  typedef T T4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      T4 v, w;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[e] = (T)x[ct][4 * qd + e];
-        if (LOPLANE > 0) w[e] = (T)(x[ct][4 * qd + e] - (float)v[e]);
-      }
-      *reinterpret_cast<T4*>(map + p * PITCH + (ct * 32 + 8 * qd + 4 * h) * 2) = v;
-      if (LOPLANE > 0) *reinterpret_cast<T4*>(map + LOPLANE + p * PITCH + (ct * 32 + 8 * qd + 4 * h) * 2) = w;
-    }
-}
 
 // this lane's pixel (32 of its 64 channels: rows (r & 3) + 8 (r >> 2) + 4 h of column block ct) into the planar
 // image; the zero padding around the 15x15 map is never touched
@@ -216,13 +128,13 @@ __device__ __forceinline__ void regs_to_tap(const f32x16 (&x)[CT], float* tap, i
 // KEEP: the training forward (Stage0Args::keep_*): the same kernel plus the copies the backward reads
 template <typename T, bool X2, int WPS = 2, bool KEEP = false>
 __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
-  using frag = typename SBM<T>::frag;
+  using frag = typename Mfma<T>::frag;
   // the depthwise phase's operand type: the training forward reads map and taps as f16 in the bf16 mode too -- the
   // map is the fp32 residual stream, and its rounding to bf16 in front of 49 products moved a 50-step bf16 training
   // run ten times further from the fp32 recipe than the per-op forward's fp32 convolution (test_16bit_training_follows_
   // the_fp32_recipe: worst loss difference 4.0e-2 against 4.0e-3); f16 keeps 11 bits of it
   using DT = typename std::conditional<KEEP, f16_t, T>::type;
-  using frag4 = typename SBM<DT>::frag4;
+  using frag4 = typename Mfma<DT>::frag4;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* map = smem;     // 16-bit [pixel][channel] image (downsample input)
   unsigned char* pl = smem;      // planar image (depthwise operand) and the fp32 [pixel][channel] image: same bytes, never live together
@@ -320,10 +232,10 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
           if (X2) {
-            x[t][ct] = SBM<T>::run(afl[ci][ct], bf, x[t][ct]);
-            x[t][ct] = SBM<T>::run(af[ci][ct], bfl, x[t][ct]);
+            x[t][ct] = Mfma<T>::m32(afl[ci][ct], bf, x[t][ct]);
+            x[t][ct] = Mfma<T>::m32(af[ci][ct], bfl, x[t][ct]);
           }
-          x[t][ct] = SBM<T>::run(af[ci][ct], bf, x[t][ct]);
+          x[t][ct] = Mfma<T>::m32(af[ci][ct], bf, x[t][ct]);
         }
       }
       if (KEEP && live[t]) regs_to_tap(x[t], a.keep_stem_pre + ((size_t)alert * P + pix[t]) * C, h);
@@ -446,10 +358,10 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
               const int q = xb + rbi - 1;
               if (q < 0 || q > 3) continue;
               if (X2) {   // remainders first (small terms into the accumulator before the large one)
-                acc[yb][xb] = SBM<DT>::run4(twl[ky * 3 + rbi], bq[s & 1][q], acc[yb][xb]);
-                acc[yb][xb] = SBM<DT>::run4(tw[ky * 3 + rbi], bql[X2 ? s & 1 : 0][X2 ? q : 0], acc[yb][xb]);
+                acc[yb][xb] = Mfma<DT>::m4(twl[ky * 3 + rbi], bq[s & 1][q], acc[yb][xb]);
+                acc[yb][xb] = Mfma<DT>::m4(tw[ky * 3 + rbi], bql[X2 ? s & 1 : 0][X2 ? q : 0], acc[yb][xb]);
               }
-              acc[yb][xb] = SBM<DT>::run4(tw[ky * 3 + rbi], bq[s & 1][q], acc[yb][xb]);
+              acc[yb][xb] = Mfma<DT>::m4(tw[ky * 3 + rbi], bq[s & 1][q], acc[yb][xb]);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -622,10 +534,10 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
 #pragma unroll
           for (int ks = 0; ks < 4; ++ks) {
             if (X2) {
-              hacc[t] = SBM<T>::run(a1l[ks], xf[t][ks], hacc[t]);
-              hacc[t] = SBM<T>::run(a1[ks], xfl[t][ks], hacc[t]);
+              hacc[t] = Mfma<T>::m32(a1l[ks], xf[t][ks], hacc[t]);
+              hacc[t] = Mfma<T>::m32(a1[ks], xfl[t][ks], hacc[t]);
             }
-            hacc[t] = SBM<T>::run(a1[ks], xf[t][ks], hacc[t]);
+            hacc[t] = Mfma<T>::m32(a1[ks], xf[t][ks], hacc[t]);
           }
         }
         // (issued here, not at the barrier: an LDS-DMA holds the issuing wave ~90 cycles per
@@ -650,10 +562,10 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
               if (X2) {
-                x[t][ct] = SBM<T>::run(a2l[ct][s2], hf, x[t][ct]);
-                x[t][ct] = SBM<T>::run(a2[ct][s2], hfl, x[t][ct]);
+                x[t][ct] = Mfma<T>::m32(a2l[ct][s2], hf, x[t][ct]);
+                x[t][ct] = Mfma<T>::m32(a2[ct][s2], hfl, x[t][ct]);
               }
-              x[t][ct] = SBM<T>::run(a2[ct][s2], hf, x[t][ct]);
+              x[t][ct] = Mfma<T>::m32(a2[ct][s2], hf, x[t][ct]);
             }
           }
         }
@@ -732,10 +644,10 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
         const frag bf = *reinterpret_cast<const frag*>(map + pin * PITCH + (ks & 3) * 32 + h * 16);
         if (X2) {
           const frag bfl = *reinterpret_cast<const frag*>(map + MAPB + pin * PITCH + (ks & 3) * 32 + h * 16);
-          acc = SBM<T>::run(afl[ks], bf, acc);
-          acc = SBM<T>::run(af[ks], bfl, acc);
+          acc = Mfma<T>::m32(afl[ks], bf, acc);
+          acc = Mfma<T>::m32(af[ks], bfl, acc);
         }
-        acc = SBM<T>::run(af[ks], bf, acc);
+        acc = Mfma<T>::m32(af[ks], bf, acc);
       }
       if (olive) {
         float* dst = a.out + ((size_t)alert * 49 + o) * 128 + wave * 32 + 4 * h;

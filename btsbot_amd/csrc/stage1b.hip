@@ -38,43 +38,16 @@
 //   [102400, 135168)       split mode only: W2 slots 1, 2
 //   OFF_B1   67584 [135168]  fc1 bias [512] | gamma*b2 [128], fp32
 //   OFF_LNW  70144 [137728]  LN weight [128] | LN bias [128], fp32;  end 71168 [138752]
-#include "common.h"
 #include "stage0.h"
+#include "stage_regs.h"
 #include <type_traits>
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-template <typename T> struct SCM;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-template <> struct SCM<bf16_t> {
-  using frag = bf16x8;
-  using frag4 = s16x4;
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ f32x4 run4(frag4 a, frag4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct SCM<f16_t> {
-  using frag = f16x8;
-  using frag4 = f16x4;
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ f32x4 run4(frag4 a, frag4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_4x4x4f16(a, b, c, 0, 0, 0);
-  }
-};
-
 constexpr int C = 128, HW = 7, PA = 49, G = 2, NPX = G * PA, CT = 4, HID = 512, KS1 = 8;
 constexpr int CN = 256, PO = 9;                   // downsample: output channels, pixels per alert
 constexpr int PITCH = 2 * C + 16;                 // [pixel][channel] image: 272 bytes per pixel row
+static_assert(C == StageRegs<CT>::C && PITCH == StageRegs<CT>::PITCH, "ln_regs / regs_to_map derive both from CT");
 constexpr int MAPB = NPX * PITCH;                 // 26656: lives in ring slots 0..1
 constexpr int CHUNKB = 16384, HALFB = CHUNKB / 2, NCH = HID / 32, NSLOT = 3;
 // planar image of the depthwise phase: [alert][x quad 0..1][row 0..6, 7 = zeros][channel, pitch 136][4 x]
@@ -98,7 +71,6 @@ template <bool X2> struct S1L {
   static_assert(NPX * LNP <= OFF_PL + PLB && NPX * LNP <= OFF_B1, "the fp32 image lies in ring slots 0, 1 + the planar image");
 };
 static_assert(MAPB <= 2 * CHUNKB && S1L<false>::LDS_BYTES <= 75264 && S1L<true>::LDS_BYTES <= 160 * 1024, "LDS layout");
-constexpr float LN_EPS = 1e-6f;
 // per-block parameter image in HBM (launch_pack_s1par): Toeplitz taps in the operand type
 //   [r = ky * 3 + (rb + 1)][channel][i][k] = W[channel][ky][4 rb + k - i + 3]   (0 outside the 7 taps)
 // then fp32: dw bias [128] | LN weight [128] | LN bias [128]
@@ -113,65 +85,6 @@ constexpr int PARB_X2 = 2 * TW_BYTES + 3 * C * 4;
     if (a.wgt != nullptr && threadIdx.x == 0 && ((i) == 0 || (i) == 13))           \
       a.wgt[2 * blockIdx.x + ((i) == 13)] = wall_clock64();                        \
   } while (0)
-
-template <int N> __device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ int swz4(int row) {   // F[(row >> 2) & 3], F = {0,3,2,1}
-  return (4 - ((row >> 2) & 3)) & 3;
-}
-// LayerNorm over the 128 channels of this lane's pixel (x[4][16] here + the partner lane ^ 32)
-__device__ __forceinline__ void ln_regs(const f32x16 (&x)[CT], const float* __restrict__ w,
-                                        const float* __restrict__ b, int h, f32x16 (&y)[CT]) {
-  float s = 0.f;
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s += x[ct][r];
-  s += __shfl_xor(s, 32, 64);
-  const float mean = s * (1.0f / C);
-  float q = 0.f;
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float d = x[ct][r] - mean;
-      q += d * d;
-    }
-  q += __shfl_xor(q, 32, 64);
-  const float rstd = rsqrtf(q * (1.0f / C) + LN_EPS);
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      const int c = ct * 32 + 8 * qd + 4 * h;
-      const float4 wv = *reinterpret_cast<const float4*>(w + c);
-      const float4 bv = *reinterpret_cast<const float4*>(b + c);
-      y[ct][4 * qd + 0] = (x[ct][4 * qd + 0] - mean) * rstd * wv.x + bv.x;
-      y[ct][4 * qd + 1] = (x[ct][4 * qd + 1] - mean) * rstd * wv.y + bv.y;
-      y[ct][4 * qd + 2] = (x[ct][4 * qd + 2] - mean) * rstd * wv.z + bv.z;
-      y[ct][4 * qd + 3] = (x[ct][4 * qd + 3] - mean) * rstd * wv.w + bv.w;
-    }
-}
-
-// LOPLANE > 0: also the values' f16 remainders, LOPLANE bytes behind (split mode)
-template <typename T, int LOPLANE = 0>
-__device__ __forceinline__ void regs_to_map(const f32x16 (&x)[CT], unsigned char* map, int p, int h) {
-  typedef T __attribute__((ext_vector_type(4))) T4;
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      T4 v, w;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[e] = (T)x[ct][4 * qd + e];
-        if (LOPLANE > 0) w[e] = (T)(x[ct][4 * qd + e] - (float)v[e]);
-      }
-      *reinterpret_cast<T4*>(map + p * PITCH + (ct * 32 + 8 * qd + 4 * h) * 2) = v;
-      if (LOPLANE > 0) *reinterpret_cast<T4*>(map + LOPLANE + p * PITCH + (ct * 32 + 8 * qd + 4 * h) * 2) = w;
-    }
-}
 
 // this lane's pixel (64 of its 128 channels: rows (r & 3) + 8 (r >> 2) + 4 h of column block ct) into the planar
 // image; p = alert * 49 + y * 7 + x
@@ -200,13 +113,13 @@ __device__ __forceinline__ void regs_to_planar(const f32x16 (&x)[CT], unsigned c
 // KEEP: the training forward (Stage1Args::keep_*): the same kernel plus the copies the backward reads
 template <typename T, bool X2, int WPS = 2, bool KEEP = false>
 __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
-  using frag = typename SCM<T>::frag;
+  using frag = typename Mfma<T>::frag;
   // the depthwise phase's operand type: the training forward reads map and taps as f16 in the bf16 mode too -- the
   // map is the fp32 residual stream, and its rounding to bf16 in front of 49 products moved a 50-step bf16 training
   // run ten times further from the fp32 recipe than the per-op forward's fp32 convolution (test_16bit_training_follows_
   // the_fp32_recipe: worst loss difference 4.0e-2 against 4.0e-3); f16 keeps 11 bits of it
   using DT = typename std::conditional<KEEP, f16_t, T>::type;
-  using frag4 = typename SCM<DT>::frag4;
+  using frag4 = typename Mfma<DT>::frag4;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* pl = smem + OFF_PL;                 // planar image; its first 24 KB double as the W1 ring
   unsigned char* stg = smem;                         // the last downsample's 16-bit image [98][PITCH] in ring slots 0..1
@@ -439,10 +352,10 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
                 const int q = xb + rbi - 1;
                 if (q < 0 || q > 1) continue;
                 if (X2) {   // remainders first
-                  acc[al][yb][xb] = SCM<DT>::run4(twl[ky * 3 + rbi], bq[sx & 1][al][q], acc[al][yb][xb]);
-                  acc[al][yb][xb] = SCM<DT>::run4(tw[ky * 3 + rbi], bql[X2 ? sx & 1 : 0][al][X2 ? q : 0], acc[al][yb][xb]);
+                  acc[al][yb][xb] = Mfma<DT>::m4(twl[ky * 3 + rbi], bq[sx & 1][al][q], acc[al][yb][xb]);
+                  acc[al][yb][xb] = Mfma<DT>::m4(tw[ky * 3 + rbi], bql[X2 ? sx & 1 : 0][al][X2 ? q : 0], acc[al][yb][xb]);
                 }
-                acc[al][yb][xb] = SCM<DT>::run4(tw[ky * 3 + rbi], bq[sx & 1][al][q], acc[al][yb][xb]);
+                acc[al][yb][xb] = Mfma<DT>::m4(tw[ky * 3 + rbi], bq[sx & 1][al][q], acc[al][yb][xb]);
               }
           }
         __builtin_amdgcn_sched_barrier(0);
@@ -619,10 +532,10 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
 #pragma unroll
         for (int ks = 0; ks < KS1; ++ks) {
           if (X2) {
-            hacc[0] = SCM<T>::run(a1l[ks], xf[ks], hacc[0]);
-            hacc[0] = SCM<T>::run(a1[ks], xfl[ks], hacc[0]);
+            hacc[0] = Mfma<T>::m32(a1l[ks], xf[ks], hacc[0]);
+            hacc[0] = Mfma<T>::m32(a1[ks], xfl[ks], hacc[0]);
           }
-          hacc[0] = SCM<T>::run(a1[ks], xf[ks], hacc[0]);
+          hacc[0] = Mfma<T>::m32(a1[ks], xf[ks], hacc[0]);
         }
         __builtin_amdgcn_sched_barrier(0);
         wait_vm<0>();   // W1(1), W1(2) / W2(1), x
@@ -681,10 +594,10 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
         for (int r = 0; r < 8; ++r) {
           if (!LAST) {
             if (X2) {
-              hn = SCM<T>::run(a1l[r], xf[r], hn);
-              hn = SCM<T>::run(a1[r], xfl[r], hn);
+              hn = Mfma<T>::m32(a1l[r], xf[r], hn);
+              hn = Mfma<T>::m32(a1[r], xfl[r], hn);
             }
-            hn = SCM<T>::run(a1[r], xf[r], hn);
+            hn = Mfma<T>::m32(a1[r], xf[r], hn);
           }
 #ifdef S1_EXP_NOGELU
           g[r] = hc[r];
@@ -708,10 +621,10 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
           if (X2) {
-            x[ct] = SCM<T>::run(a2l[ct][0], hf, x[ct]);
-            x[ct] = SCM<T>::run(a2[ct][0], hfl, x[ct]);
+            x[ct] = Mfma<T>::m32(a2l[ct][0], hf, x[ct]);
+            x[ct] = Mfma<T>::m32(a2[ct][0], hfl, x[ct]);
           }
-          x[ct] = SCM<T>::run(a2[ct][0], hf, x[ct]);
+          x[ct] = Mfma<T>::m32(a2[ct][0], hf, x[ct]);
 #ifdef S1_EXP_NOGELU
           g[8 + 2 * ct] = hc[8 + 2 * ct];
           g[9 + 2 * ct] = hc[9 + 2 * ct];
@@ -731,10 +644,10 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
           if (X2) {
-            x[ct] = SCM<T>::run(a2l[ct][1], hf, x[ct]);
-            x[ct] = SCM<T>::run(a2[ct][1], hfl, x[ct]);
+            x[ct] = Mfma<T>::m32(a2l[ct][1], hf, x[ct]);
+            x[ct] = Mfma<T>::m32(a2[ct][1], hfl, x[ct]);
           }
-          x[ct] = SCM<T>::run(a2[ct][1], hf, x[ct]);
+          x[ct] = Mfma<T>::m32(a2[ct][1], hf, x[ct]);
         }
         LS(7);
       };
@@ -847,10 +760,10 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
         const frag bf = *reinterpret_cast<const frag*>(stg + pin * PITCH + (ks & 7) * 32 + h * 16);
         if (X2) {
           const frag bfl = *reinterpret_cast<const frag*>(stg + MAPB + pin * PITCH + (ks & 7) * 32 + h * 16);
-          acc = SCM<T>::run(wql[i], bf, acc);
-          acc = SCM<T>::run(wq[i], bfl, acc);
+          acc = Mfma<T>::m32(wql[i], bf, acc);
+          acc = Mfma<T>::m32(wq[i], bfl, acc);
         }
-        acc = SCM<T>::run(wq[i], bf, acc);
+        acc = Mfma<T>::m32(wq[i], bf, acc);
         if (stp + RING < NSTEP) {
           wq[i] = *fsrc(stp + RING);
           if (X2) wql[i] = fsrc(stp + RING)[64];

@@ -37,18 +37,18 @@
 #include <string.h>
 #include <type_traits>
 
-#include "common.h"
+#include "mfma.h"
 #include "stage2p.h"
 #include "stage3.h"
 
 namespace {
 
-// operand traits: fragment (8 elements per lane), element size, MFMA, conversions from fp32
-template <typename T> struct MP;
+// operand traits: fragment (8 elements per lane), element size, MFMA, conversions from fp32; the primary template is
+// the 16-bit modes' (bf16_t, f16_t)
 // Besides the arithmetic a trait says where a fragment lies: gld = fragment number f of a packed array in HBM (64 lanes
 // x 8 values); ld8 / st8 / st4 = 8 / 8 / 4 consecutive values of an operand image in LDS at byte address p of its
 // first (for the split mode: only) plane.  PLANE = byte distance of the split mode's remainder plane.
-template <typename T> struct MP16 {
+template <typename T> struct MP {
   static constexpr int ESZ = 2;
   static constexpr int KSTEP = 32;        // k per MFMA; a lane holds KSTEP / 4 consecutive values of its row / column
   static constexpr bool SPLIT = false;
@@ -79,16 +79,7 @@ template <typename T> struct MP16 {
     for (int j = 0; j < 4; ++j) o[j] = (T)v[j];
     return o;
   }
-};
-template <> struct MP<bf16_t> : MP16<bf16_t> {
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct MP<f16_t> : MP16<f16_t> {
-  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-  }
+  static __device__ __forceinline__ f32x4 run(frag a, frag b, f32x4 c) { return Mfma<T>::m16(a, b, c); }
 };
 // split operands (BTSBOT_F16X2): value = f16 head + f16 remainder, product = lo*hi + hi*lo + hi*hi on the f16 MFMA.
 // LDS images keep the 16-bit geometry for the heads and a second plane of the same geometry for the remainders (so
@@ -231,7 +222,6 @@ static_assert(Lds<f16x2_t, 4>::BYTES <= 160 * 1024 && Lds<bf16_t, 7>::BYTES <= 1
 static_assert(Lds<bf16_t, 4>::BYTES == 95296 && Lds<bf16_t, 5>::BYTES == 104656 && Lds<bf16_t, 7>::BYTES == 141296 &&
               Lds<bf16_t, 7, 256, 64>::BYTES == 142336 && Lds<f16x2_t, 5>::BYTES == 158416 && Lds<bf16_t, 5, 320>::BYTES == 129488,
               "the byte counts the comments give");
-constexpr float LN_EPS = 1e-6f;
 #ifndef XRES_TRAIN
 #define XRES_TRAIN 1
 #endif

@@ -19,20 +19,18 @@
 //  same-address device-scope atomics, or cooperative_groups' grid.sync() -- against ~3 us for a kernel boundary.)
 #include <stdlib.h>
 
-#include "common.h"
+#include "mfma.h"
 #include "stage3.h"
 #include <type_traits>
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-// operand traits: fragment type (8 elements per lane), element size, MFMA, and the conversions from fp32
-template <typename T> struct S3M;
+// operand traits: fragment type (8 elements per lane), element size, MFMA, and the conversions from fp32; the primary
+// template is the 16-bit modes' (bf16_t, f16_t)
 // Every trait also says how a fragment lies in memory: ldg / stg = fragment number f of a packed fragment array in HBM
 // (64 lanes x 8 values), lds_ld8 / lds_st2 = values c .. c + 7 / c, c + 1 of an operand row in LDS (`plane` = the
 // row's width in values; only the split mode, which keeps a row's remainders `plane` values behind its heads, uses it).
-template <typename T> struct S3M16 {
+template <typename T> struct S3M {
   static constexpr int ESZ = 2;
   static constexpr int KSTEP = 16;        // k per MFMA; a lane holds KSTEP / 2 consecutive values of its row / column
   static constexpr bool MX = false;
@@ -63,16 +61,7 @@ template <typename T> struct S3M16 {
     for (int j = 0; j < 8; ++j) o[j] = (T)v[j];
     return o;
   }
-};
-template <> struct S3M<bf16_t> : S3M16<bf16_t> {
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct S3M<f16_t> : S3M16<f16_t> {
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
+  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) { return Mfma<T>::m32(a, b, c); }
 };
 // fp8 (OCP e4m3) on the block-scaled MFMA v_mfma_scale_f32_32x32x64_f8f6f4: 64 k per instruction, twice the bf16 rate
 // per clock (stage2p.hip has the 16x16x128 form and the note on the scales, both the constant 2^0 here too).  A lane
@@ -172,7 +161,6 @@ template <> struct GeluOf<fp8_t> { using type = bf16_t; };
 constexpr int NT = 512;           // threads per workgroup (8 waves)
 constexpr int M1 = 32, N1 = 256;  // fc1 tile: alerts x hidden units
 constexpr int M2 = 64, N2 = 32;   // fc2 tile: alerts x channels
-constexpr float LN_EPS = 1e-6f;
 constexpr int RED_BYTES = 8 * 2 * 4 * 64 * 16;   // fc2: 8 K slices x 2 alert blocks x 4 quads x 64 lanes x float4
 
 // MB = 32-alert row blocks per workgroup (1; 2 at C = 640, where 32 x 10 tiles would be 320 workgroups = two rounds of the

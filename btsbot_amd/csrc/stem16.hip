@@ -10,35 +10,19 @@
 //   * B = 4 x 4 input pixels per (lane, input channel): two unaligned 16-byte loads, converted in registers;
 //   * LayerNorm over the lane's 16 CT values + its partner lane's (lane ^ 32), fp32; NHWC fp32 rows out
 //     (+ optionally the pre-LayerNorm rows the training backward keeps).
-#include "common.h"
+#include "mfma.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 constexpr int HW = 15, P = 225;
-constexpr float LN_EPS = 1e-6f;
 struct __attribute__((packed, aligned(4))) f4u { float v[4]; };
-
-template <typename T> struct SM;
-template <> struct SM<bf16_t> {
-  using frag = bf16x8;
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct SM<f16_t> {
-  using frag = f16x8;
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
 
 template <typename T, int C0>
 __global__ __launch_bounds__(256) void stem16_kernel(const float* __restrict__ img, const float* __restrict__ w,
                                                      const float* __restrict__ bias, const float* __restrict__ lnw,
                                                      const float* __restrict__ lnb, float* __restrict__ out,
                                                      float* __restrict__ pre_out, int B) {
-  using frag = typename SM<T>::frag;
+  using frag = typename Mfma<T>::frag;
   constexpr int CT = (C0 + 31) / 32;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 31, h = lane >> 5;
@@ -91,7 +75,7 @@ __global__ __launch_bounds__(256) void stem16_kernel(const float* __restrict__ i
         bf[4 + e] = (T)v1.v[e];
       }
 #pragma unroll
-      for (int ct = 0; ct < CT; ++ct) x[ct] = SM<T>::run(af[ci][ct], bf, x[ct]);
+      for (int ct = 0; ct < CT; ++ct) x[ct] = Mfma<T>::m32(af[ci][ct], bf, x[ct]);
     }
     float* po = pre_out != nullptr ? pre_out + ((size_t)alert * P + pc) * C0 : nullptr;
     if (po != nullptr && live) {

@@ -18,46 +18,11 @@
 // /root/reference/btsbot/train.py:526.
 #include <stdlib.h>
 
-#include "common.h"
+#include "mfma.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
-template <typename T> struct W2M;
-template <> struct W2M<bf16_t> {
-  static __device__ __forceinline__ f32x16 run(s16x8 a, s16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
-                                                   __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ float tofloat(unsigned short v) {
-    return __builtin_bit_cast(float, (unsigned)v << 16);
-  }
-};
-template <> struct W2M<f16_t> {
-  static __device__ __forceinline__ f32x16 run(s16x8 a, s16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a),
-                                                  __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ float tofloat(unsigned short v) {
-    return (float)__builtin_bit_cast(f16_t, v);
-  }
-};
-
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-
-// lane's 8 reduction-consecutive elements (rows r0 + 8h .. +7) of column c0 + (lane & 31)
-__device__ __forceinline__ s16x8 tr_frag(const unsigned char* tile, int pitchb, int r0, int c0,
-                                         int lane) {
-  const int h = lane >> 5, g1 = (lane >> 4) & 1, q = (lane >> 2) & 3, p = lane & 3;
-  const unsigned char* a = tile + (r0 + 8 * h + q) * pitchb + (c0 + 16 * g1 + 4 * p) * 2;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(a));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(a + 4 * pitchb));
-  return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 
 constexpr int TM = 64;   // reduction rows per LDS tile
 
@@ -144,14 +109,14 @@ __device__ __forceinline__ void wgrad2_body(const T* __restrict__ D, const T* __
 #pragma unroll
       for (int i = 0; i < FN; ++i)
 #pragma unroll
-        for (int j = 0; j < FK; ++j) acc[i][j] = W2M<T>::run(af[i], bf[j], acc[i][j]);
+        for (int j = 0; j < FK; ++j) acc[i][j] = MfmaRaw<T>::m32(af[i], bf[j], acc[i][j]);
     }
     if (do_sum) {   // thread = (column, row group); rows rg, rg + G, ...
       constexpr int G = 256 / TN;
       const int col = tid % TN, rg = tid / TN;
 #pragma unroll
       for (int r = 0; r < TM / G; ++r)
-        csum += W2M<T>::tofloat(
+        csum += bits_to_f32<T>(
             *reinterpret_cast<const unsigned short*>(ds + (rg + G * r) * PN + col * 2));
     }
     if (more) stash((t + 1) & 1);

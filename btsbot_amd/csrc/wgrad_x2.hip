@@ -14,7 +14,7 @@
 // flight while the current one is multiplied (register-staged, one LDS image set: 4 images of 64 rows).  Slices leave as
 // dense partial tiles, 2^-e applied (exact), and wgrad_reduce_kernel adds them in a fixed order -- no atomics whenever the
 // caller lends the scratch, a single slice included.
-#include "common.h"
+#include "mfma.h"
 
 namespace {
 
@@ -24,25 +24,7 @@ namespace {
     if (_s != BTSBOT_OK) return _s; \
   } while (0)
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-
 constexpr int TM = 64;   // reduction rows per LDS tile
-
-// lane's 8 reduction-consecutive elements (rows r0 + 8h .. +7) of column c0 + (lane & 31) (wgrad.hip)
-__device__ __forceinline__ s16x8 tr_frag(const unsigned char* tile, int pitchb, int r0, int c0, int lane) {
-  const int h = lane >> 5, g1 = (lane >> 4) & 1, q = (lane >> 2) & 3, p = lane & 3;
-  const unsigned char* a = tile + (r0 + 8 * h + q) * pitchb + (c0 + 16 * g1 + 4 * p) * 2;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(a));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(a + 4 * pitchb));
-  return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
-__device__ __forceinline__ f32x16 mma(s16x8 a, s16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 
 // 4 fp32 values (times s) -> f16 heads and remainders at row r, 4-column chunk cc of the two images
 __device__ __forceinline__ void put4(unsigned char* hi, unsigned char* lo, int off, float4 v, float s) {
@@ -150,9 +132,9 @@ __global__ __launch_bounds__(256) void wgrad_x2_kernel(const float* __restrict__
       for (int i = 0; i < FN; ++i)
 #pragma unroll
         for (int j = 0; j < FK; ++j) {
-          acc[i][j] = mma(afl[i], bfh[j], acc[i][j]);
-          acc[i][j] = mma(afh[i], bfl[j], acc[i][j]);
-          acc[i][j] = mma(afh[i], bfh[j], acc[i][j]);
+          acc[i][j] = MfmaRaw<f16_t>::m32(afl[i], bfh[j], acc[i][j]);
+          acc[i][j] = MfmaRaw<f16_t>::m32(afh[i], bfl[j], acc[i][j]);
+          acc[i][j] = MfmaRaw<f16_t>::m32(afh[i], bfh[j], acc[i][j]);
         }
     }
     __syncthreads();

@@ -352,6 +352,17 @@ extern "C" int btsbot_set_option(btsbot_handle h, const char* key, int value) {
       return BTSBOT_ERR_INVALID_ARG;
     }
     h->s2p_alerts_hint = value;
+    resolve_schedule(h);
+    return BTSBOT_OK;
+  }
+  if (strcmp(key, "forwards_in_flight") == 0) {
+    // every handle takes it; what it changes is the schedule's business (s2p_g7, s3_wide: 16-bit ConvNeXt tails)
+    if (value != 0 && value != 1) {
+      btsbot_set_error("set_option: forwards_in_flight is 0 or 1, got %d", value);
+      return BTSBOT_ERR_INVALID_ARG;
+    }
+    h->opt_forwards_in_flight = value == 1;
+    resolve_schedule(h);
     return BTSBOT_OK;
   }
   if (strcmp(key, "deterministic") == 0) {
@@ -664,8 +675,8 @@ static int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t s
         a.B = nb;
         a.stamps = h->stamps ? h->stamps + STAMP_S3 : nullptr;
         for (int j = 0; j < a.depth; ++j) {
-          TRY(timed(h, CAT_S3FC1, st, [&] { return launch_stage3(h->prec_tail(), ch, a, j, 0, st); }));
-          TRY(timed(h, CAT_S3FC2, st, [&] { return launch_stage3(h->prec_tail(), ch, a, j, 1, st); }));
+          TRY(timed(h, CAT_S3FC1, st, [&] { return launch_stage3(h->prec_tail(), ch, a, j, 0, sc.s3_wide, st); }));
+          TRY(timed(h, CAT_S3FC2, st, [&] { return launch_stage3(h->prec_tail(), ch, a, j, 1, sc.s3_wide, st); }));
         }
         if (h->debug)
           HIP_TRY(hipMemcpyAsync(h->taps[4], x, (size_t)rows * ch * 4, hipMemcpyDeviceToDevice, st));

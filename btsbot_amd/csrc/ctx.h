@@ -164,6 +164,7 @@ struct btsbot_ctx {
   size_t prof_used = 0;
 
   int s2p_alerts_hint = 0; // btsbot_set_option("stage2p_alerts"): 0 = by rounds, 4 / 7 forced
+  bool opt_forwards_in_flight = false;   // btsbot_set_option("forwards_in_flight"): other forwards run beside this handle's
   bool fp8 = false;        // created with BTSBOT_FP8: cfg.precision reads BTSBOT_BF16, stages 2-3 run fp8 operands
   bool x2 = false;         // created with BTSBOT_F16X2: cfg.precision reads BTSBOT_F32 (the schedule of every kernel without
                            // a split-operand form), the kernels that have one run it

@@ -64,7 +64,7 @@
   X(S0_ONE_WG, ON, PROCESS, "stage0b_kernel padded to one workgroup per CU")                                            \
   X(S1_ONE_WG, ON, PROCESS, "stage1b_kernel padded to one workgroup per CU")                                            \
   X(S2P_G, INT, PROCESS, "stage2p_kernel: 4 / 5 / 7 alerts per workgroup at every batch size")                          \
-  X(S3_TILES, INT, PROCESS, "stage3.hip: 1 always narrow, 2 always wide tiles")                                         \
+  X(S3_TILES, INT, PROCESS, "stage3.hip: 1 always narrow, 2 always wide tiles (whatever forwards_in_flight says)")      \
   X(S2MLP_ROWS, INT, PROCESS, "s2mlp_bwd_kernel: pixel rows per workgroup (16..48, default 45)")
 
 enum Switch {
@@ -89,6 +89,8 @@ bool switch_set(Switch s);   // present at all, whatever its value
   X(stage1)       /* stage 1 + second downsample as one kernel (stage1b.hip) */                                        \
   X(stage2p)      /* stage 2 + last downsample as one persistent kernel (stage2p.hip) */                               \
   X(stage3)       /* the 1x1 stage as two fragment-streaming launches per block (stage3.hip) */                        \
+  X(s2p_g7)       /* stage2p keeps 7 alerts per workgroup at every batch size (options below) */                       \
+  X(s3_wide)      /* stage3.hip on 64-alert fc1 / 64-channel fc2 tiles: half the workgroups (options below) */         \
   X(head16)       /* the head on the matrix pipe (head16.hip); off: the fp32 head (head.hip) */                        \
   X(stem16)       /* a stem launched on its own is the matrix-pipe one (stem16.hip) */                                 \
   /* training step of the ConvNeXt branch */                                                                           \
@@ -114,6 +116,14 @@ bool switch_set(Switch s);   // present at all, whatever its value
   X(fused_mlp)    /* inference: the stage's per-op blocks run fused_mlp_kernel */                                      \
   X(mlp_bwd)      /* training: its blocks run the fused MLP forward that keeps nothing 4C-wide + mlp_bwd_kernel */
 
+// Options a caller sets per handle (btsbot_set_option) that the schedule reads besides the switches:
+//   option               values       decides
+//   "deterministic"      0 | 1        deterministic
+//   "train_split"        0 | 1        train_split
+//   "stage2p_alerts"     0, 4, 5, 7   s2p_alerts (0: forwards_in_flight's choice, else the kernel's by rounds), s2p_g7
+//   "forwards_in_flight" 0 | 1        other forwards run beside this handle's: forms that hold fewer CUs per launch --
+//                                     s2p_alerts = 7 unless "stage2p_alerts" is given; s3_wide at 512 channels in the
+//                                     bf16 / f16 / fp8 modes (split operands: 8 registers per fragment, narrow only)
 struct Schedule {
 #define X(f) bool f = false;
   BTSBOT_SCHEDULE_FLAGS(X)
@@ -125,6 +135,7 @@ struct Schedule {
   // per-op GEMMs (36 864 rows: full tiles, full rounds) are as fast or faster (7.95 against 8.00 ms)
   int s2_keep_max_batch = 0;
   int s0_diag = 0, s2p_diag = 0, head_diag = 0;
+  int s2p_alerts = 0;   // Stage2pArgs::alerts_hint: 0 = the kernel picks 5 or 7 by rounds; 4 / 5 / 7 at every batch size
   bool s2_kept(int B) const { return s2_keep && B <= s2_keep_max_batch; }
 };
 

@@ -84,6 +84,20 @@ void resolve_schedule(btsbot_ctx* h) {
     s.stage1 = !on(SW_NO_STAGE1) && stage1_supported(h->prec_s01(), c.dims[1], c.dims[2]) && c.depths[1] == 2;
     s.stage2p = !on(SW_NO_STAGE2) && stage2p_supported(h->prec_tail(), c.dims[2], c.dims[3], c.depths[2]);
     s.stage3 = !on(SW_NO_S3) && stage3_supported(h->prec_tail(), c.dims[3], c.depths[3]);
+    // stage 2's alerts per workgroup: the caller's number wins, then the overlap hint (7: 147 workgroups at 1024 alerts,
+    // the other streams' kernels take the remaining CUs), else the kernel's own choice by rounds
+    s.s2p_alerts = h->s2p_alerts_hint != 0 ? h->s2p_alerts_hint : h->opt_forwards_in_flight ? 7 : 0;
+    s.s2p_g7 = s.stage2p && s.s2p_alerts == 7 && h->prec_tail() != BTSBOT_F16X2;   // (split planes of 7 do not fit the LDS: 5)
+    // stage 3's tiles.  Wide (64 alerts / 64 channels, half the workgroups, twice the rows per filter fragment): at 640
+    // channels always -- 160 workgroups are one round of the chip, 320 two --, at 512 only while other forwards are in
+    // flight: a lone forward gains nothing from the CUs given back (2.255 against 2.265 ms per 8192 alerts).  The split
+    // mode's fragments are 8 registers each: narrow tiles only; fp8 at 640 channels stays narrow unless forced
+    {
+      const int tail = h->prec_tail(), forced = switch_int(SW_S3_TILES, 0);
+      const bool can = tail == BTSBOT_BF16 || tail == BTSBOT_F16 || tail == BTSBOT_FP8;
+      const bool pick = (c.dims[3] == 640 && tail != BTSBOT_FP8) || (c.dims[3] == 512 && h->opt_forwards_in_flight);
+      s.s3_wide = s.stage3 && can && (forced == 2 || (forced != 1 && pick));
+    }
     s.stem16 = !on(SW_NO_STEM16) && stem16_supported(prec, c.dims[0]);
     s.s0_diag = num(SW_S0_DIAG, 0);
     s.s2p_diag = num(SW_S2P_DIAG, 0);

@@ -28,7 +28,8 @@ struct Stage3Args {
 bool stage3_supported(int prec, int c3, int depth);
 size_t stage3_hfrag_bytes(int prec, int c3, int B);
 // phase 0: centre tap + LN + fc1 + GELU of block `block` (x -> hfrag); phase 1: fc2 + layer scale + residual (in place)
-int launch_stage3(int prec, int c3, const Stage3Args& a, int block, int phase, hipStream_t st);
+// wide: 64-alert fc1 / 64-channel fc2 tiles (Schedule::s3_wide; not in the split mode), same sums per row
+int launch_stage3(int prec, int c3, const Stage3Args& a, int block, int phase, bool wide, hipStream_t st);
 // fp32 [rows][K] (x rowscale[row]) -> A fragments of 32 rows x 16 k; swap23: tile row r holds source row swap23(r)
 // fp8: `scale` (device, 2 floats) receives {S, 1/S}, S = the power of two that puts max |w| just below 240
 int launch_pack_s3(int prec, const float* src, const float* rowscale, void* dst, int rows, int K, int swap23,

@@ -13,6 +13,8 @@
 //           units of its alert = exactly fc2's B fragment: h leaves as [alert block][k-step][lane][8], 1 KiB per store.
 //   s3_fc2  tile = 64 alerts x 32 channels, the 8 waves split K = 4C; A (gamma * W2) and B (h) fragments are all
 //           requested up front (48 per wave); the partial tiles meet in LDS, + gamma * b2 + x, in place.
+//   wide tiles (launch_t below): fc1 64 alerts x 256 hidden units, fc2 64 alerts x 64 channels -- half the workgroups, a
+//           filter fragment serves twice the rows; every row's sums are the narrow form's, in the same order.
 // Bound: what one CU can pull through its TA port, ~64 B/clk: 320 KB per fc1 tile, 384 KB per fc2 tile = 5k / 6k
 // cycles, behind one MALL round trip (the L2s start every kernel empty); algorithmic FLOPs 2 x 2.1 GFLOP per block.
 // (One cooperative launch for the whole stage was tried: a grid-wide barrier costs 8-20 us on this part -- 256
@@ -197,6 +199,17 @@ __device__ __forceinline__ void fc1_tile(const Stage3Args& a, const Stage3Blk& b
     lw[i] = *reinterpret_cast<const float2*>(bk.ln_w + c);
     lb[i] = *reinterpret_cast<const float2*>(bk.ln_b + c);
   }
+  // MB = 2: the fc1 bias (the accumulator's start value) is requested here too.  Loads return in order, so asked for behind
+  // the filter fragments it holds the first product back until the whole filter has arrived: with eight rows per wave in
+  // front of the barrier that wait was 5.2k cycles of the workgroup's 19.9k (2.9k with the request here; s3_fc1 12.2 -> 11.8
+  // us at 1024 alerts).  With four rows (MB = 1) the kernel measured the same either way (9.47 / 9.53 us): left as it was
+  constexpr bool B1_PRE = MB == 2;
+  const float* b1p = bk.b1 + 32 * ht + 8 * h;
+  float4 b1v[4];
+  if constexpr (B1_PRE) {
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) b1v[qd] = *reinterpret_cast<const float4*>(b1p + 4 * (qd & 1) + 16 * (qd >> 1));
+  }
   // ---- the wave's filter fragments, a quarter in front of each row's LayerNorm: the requests queue at the TA port
   //      (a wave cannot run ahead of its own unissued loads) while the VALU works on the row before
   const size_t wf0 = (size_t)ht * KS;      // this wave's first filter fragment
@@ -239,18 +252,15 @@ __device__ __forceinline__ void fc1_tile(const Stage3Args& a, const Stage3Blk& b
   constexpr bool F8 = std::is_same<T, fp8_t>::value;
   const float s1 = F8 ? bk.scales[0] : 1.0f, is1 = F8 ? bk.scales[1] : 1.0f;
   f32x16 acc[MB];
-  {
-    const float* bp = bk.b1 + 32 * ht + 8 * h;
 #pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      const float4 bv = *reinterpret_cast<const float4*>(bp + 4 * (qd & 1) + 16 * (qd >> 1));
+  for (int qd = 0; qd < 4; ++qd) {
+    const float4 bv = B1_PRE ? b1v[qd] : *reinterpret_cast<const float4*>(b1p + 4 * (qd & 1) + 16 * (qd >> 1));
 #pragma unroll
-      for (int mb = 0; mb < MB; ++mb) {
-        acc[mb][4 * qd + 0] = bv.x * s1;
-        acc[mb][4 * qd + 1] = bv.y * s1;
-        acc[mb][4 * qd + 2] = bv.z * s1;
-        acc[mb][4 * qd + 3] = bv.w * s1;
-      }
+    for (int mb = 0; mb < MB; ++mb) {
+      acc[mb][4 * qd + 0] = bv.x * s1;
+      acc[mb][4 * qd + 1] = bv.y * s1;
+      acc[mb][4 * qd + 2] = bv.z * s1;
+      acc[mb][4 * qd + 3] = bv.w * s1;
     }
   }
   __syncthreads();
@@ -316,15 +326,19 @@ __device__ __forceinline__ void fc2_tile(const Stage3Args& a, const Stage3Blk& b
   }
   // the epilogue's operands (this thread's four residual values, layer scale, bias) are requested behind the fragments:
   // asked for only after the K slices had met in LDS they were one more exposed memory round trip per launch (~2.5k cycles
-  // of the workgroup's 14.7k).  (One channel tile per workgroup only: with two the fragments leave no registers for them.)
-  constexpr bool EPI_PRE = NC == 1;
-  float4 xv_pre = make_float4(0.f, 0.f, 0.f, 0.f), g_pre = xv_pre, b_pre = xv_pre;
-  if constexpr (EPI_PRE) {
+  // of the workgroup's 14.7k).  12 registers per channel tile, held through the k loop: every instantiation stays below
+  // 256 VGPRs without scratch (-Rpass-analysis=kernel-resource-usage; the largest, two tiles at 640 channels: 244).
+  float4 xv_pre[NC], g_pre[NC], b_pre[NC];
+  {
     const int q = tid, t = q >> 8, qd = (q >> 6) & 3, ln = q & 63;
-    const int al = m0 + 32 * t + (ln & 31), c = 32 * ct + 8 * qd + 4 * (ln >> 5);
-    xv_pre = *reinterpret_cast<const float4*>(a.x + (size_t)(al < a.B ? al : a.B - 1) * C + c);
-    g_pre = *reinterpret_cast<const float4*>(bk.gamma + c);
-    b_pre = *reinterpret_cast<const float4*>(bk.b2 + c);
+    const int al = m0 + 32 * t + (ln & 31);
+#pragma unroll
+    for (int nc = 0; nc < NC; ++nc) {
+      const int c = 32 * (ct * NC + nc) + 8 * qd + 4 * (ln >> 5);
+      xv_pre[nc] = *reinterpret_cast<const float4*>(a.x + (size_t)(al < a.B ? al : a.B - 1) * C + c);
+      g_pre[nc] = *reinterpret_cast<const float4*>(bk.gamma + c);
+      b_pre[nc] = *reinterpret_cast<const float4*>(bk.b2 + c);
+    }
   }
   __builtin_amdgcn_sched_barrier(0);   // (left alone, hipcc sinks the loads to their MFMAs: ~10 in flight instead of 48)
   f32x16 acc[NC][2];
@@ -379,9 +393,7 @@ __device__ __forceinline__ void fc2_tile(const Stage3Args& a, const Stage3Blk& b
     }
     if (al < a.B) {
       float* xp = a.x + (size_t)al * C + c;
-      const float4 xv = EPI_PRE ? xv_pre : *reinterpret_cast<const float4*>(xp);
-      const float4 g = EPI_PRE ? g_pre : *reinterpret_cast<const float4*>(bk.gamma + c);
-      const float4 b = EPI_PRE ? b_pre : *reinterpret_cast<const float4*>(bk.b2 + c);
+      const float4 xv = xv_pre[nc], g = g_pre[nc], b = b_pre[nc];
       *reinterpret_cast<float4*>(xp) = make_float4(xv.x + fmaf(g.x, b.x, s.x), xv.y + fmaf(g.y, b.y, s.y),
                                                    xv.z + fmaf(g.z, b.z, s.z), xv.w + fmaf(g.w, b.w, s.w));
     }
@@ -511,16 +523,18 @@ template <typename T, int C, int MB> int launch_tm(const Stage3Args& a, int j, i
   return BTSBOT_OK;
 }
 
-// Tile shapes: 32-alert fc1 tiles / 32-channel fc2 tiles; at 640 channels (16-bit modes) 64 alerts / 64 channels -- 160
-// workgroups instead of 320, one round of the chip's 256 CUs with twice the rows per filter fragment: 19 -> 16.7 / 14.7 us per
-// launch at 1024 alerts.  (Measured and NOT taken at 512 channels for the 2048-alert chunks of a large call, 512 -> 256
-// workgroups: 2.255 against 2.265 ms per 8192 alerts in bf16, 2.09 against 2.07 in fp8.  The split mode's fragments are 8
-// registers each: narrow tiles only.)
-template <typename T, int C> int launch_t(const Stage3Args& a, int j, int phase, hipStream_t st) {
+// Tile shapes: 32-alert fc1 tiles / 32-channel fc2 tiles, or wide: 64 alerts / 64 channels.  The handle's schedule picks
+// (schedule.hip, Schedule::s3_wide).  At 640 channels (16-bit modes) wide is 160 workgroups instead of 320, one round of the
+// chip's 256 CUs with twice the rows per filter fragment: 19 -> 16.7 / 14.7 us per launch at 1024 alerts.  At 512 channels a
+// lone forward gains nothing (2048-alert chunks of a large call, 512 -> 256 workgroups: 2.255 against 2.265 ms per 8192 alerts
+// in bf16, 2.09 against 2.07 in fp8); there wide tiles are for forwards that overlap on several streams, where a CU not held
+// is a CU another stream's kernel uses.  (The split mode's fragments are 8 registers each: narrow tiles only.)
+template <typename T, int C> int launch_t(const Stage3Args& a, int j, int phase, bool wide, hipStream_t st) {
   if constexpr (S3M<T>::ESZ <= 2) {
-    static const int forced = switch_int(SW_S3_TILES, 0);   // BTSBOT_AMD_S3_TILES=1 / 2: always narrow / always wide (A/B timing, parity)
-    const bool wide = forced == 2 || (forced != 1 && C == 640 && S3M<T>::ESZ == 2);
     if (wide) return launch_tm<T, C, 2>(a, j, phase, st);
+  } else if (wide) {
+    btsbot_set_error("stage3: the split mode has no wide tiles");
+    return BTSBOT_ERR_INVALID_ARG;
   }
   return launch_tm<T, C, 1>(a, j, phase, st);
 }
@@ -536,16 +550,16 @@ size_t stage3_hfrag_bytes(int prec, int c3, int B) {
   return (size_t)((B + M2 - 1) / M2) * M2 * 4 * c3 * (prec == BTSBOT_F32 || prec == BTSBOT_F16X2 ? 4 : 2);
 }
 
-int launch_stage3(int prec, int c3, const Stage3Args& a, int block, int phase, hipStream_t st) {
+int launch_stage3(int prec, int c3, const Stage3Args& a, int block, int phase, bool wide, hipStream_t st) {
   if (a.B <= 0) return BTSBOT_OK;
-  if (prec == BTSBOT_BF16 && c3 == 512) return launch_t<bf16_t, 512>(a, block, phase, st);
-  if (prec == BTSBOT_F16 && c3 == 512) return launch_t<f16_t, 512>(a, block, phase, st);
-  if (prec == BTSBOT_BF16 && c3 == 640) return launch_t<bf16_t, 640>(a, block, phase, st);
-  if (prec == BTSBOT_F16 && c3 == 640) return launch_t<f16_t, 640>(a, block, phase, st);
-  if (prec == BTSBOT_FP8 && c3 == 512) return launch_t<fp8_t, 512>(a, block, phase, st);
-  if (prec == BTSBOT_FP8 && c3 == 640) return launch_t<fp8_t, 640>(a, block, phase, st);
-  if (prec == BTSBOT_F16X2 && c3 == 512) return launch_t<f16x2_t, 512>(a, block, phase, st);
-  if (prec == BTSBOT_F16X2 && c3 == 640) return launch_t<f16x2_t, 640>(a, block, phase, st);
+  if (prec == BTSBOT_BF16 && c3 == 512) return launch_t<bf16_t, 512>(a, block, phase, wide, st);
+  if (prec == BTSBOT_F16 && c3 == 512) return launch_t<f16_t, 512>(a, block, phase, wide, st);
+  if (prec == BTSBOT_BF16 && c3 == 640) return launch_t<bf16_t, 640>(a, block, phase, wide, st);
+  if (prec == BTSBOT_F16 && c3 == 640) return launch_t<f16_t, 640>(a, block, phase, wide, st);
+  if (prec == BTSBOT_FP8 && c3 == 512) return launch_t<fp8_t, 512>(a, block, phase, wide, st);
+  if (prec == BTSBOT_FP8 && c3 == 640) return launch_t<fp8_t, 640>(a, block, phase, wide, st);
+  if (prec == BTSBOT_F16X2 && c3 == 512) return launch_t<f16x2_t, 512>(a, block, phase, wide, st);
+  if (prec == BTSBOT_F16X2 && c3 == 640) return launch_t<f16x2_t, 640>(a, block, phase, wide, st);
   btsbot_set_error("stage3: precision %d / width %d not supported", prec, c3);
   return BTSBOT_ERR_INVALID_ARG;
 }

@@ -96,7 +96,7 @@ int stage2p_args(const btsbot_ctx* h, bool keep, Stage2pArgs* out) {
   a.ds_wp = IMG(h, d.p_wp);
   a.ds_b = m + d.b;
   a.cw = h->cfg.dims[2];
-  a.alerts_hint = h->s2p_alerts_hint;
+  a.alerts_hint = h->sched.s2p_alerts;
   return BTSBOT_OK;
 }
 

@@ -47,9 +47,10 @@ def _replica(model):
     return twin.to(dev).eval()
 
 
-_S2P_HINT = int(__import__("os").environ.get("BTSBOT_AMD_S2P_HINT", "7"))   # (developer A/B: 4, 5 or 7; 0 = by rounds)
+# (developer A/B: stage2p's alerts per workgroup under overlap, 4, 5 or 7, over the library's choice; 0 or unset = that choice)
+_S2P_HINT = int(__import__("os").environ.get("BTSBOT_AMD_S2P_HINT", "0"))
 if _S2P_HINT not in (0, 4, 5, 7):   # (the library would reject the value and the hint would silently do nothing)
-    raise ValueError(f"BTSBOT_AMD_S2P_HINT={_S2P_HINT}: stage2p keeps 4, 5 or 7 alerts per workgroup (0: its own choice)")
+    raise ValueError(f"BTSBOT_AMD_S2P_HINT={_S2P_HINT}: stage2p keeps 4, 5 or 7 alerts per workgroup (0: the library's choice)")
 
 
 class ScoreStream:
@@ -105,10 +106,14 @@ class ScoreStream:
         m = self.models[k]
         hinted = len(self.models) > 1 and getattr(m, "_handle", None) is not None
         if hinted:
-            # several forwards in flight: the stage-2 kernel keeps 7 alerts per workgroup at every batch size and so
-            # leaves ~40 % of the CUs to the other stream's kernels (+6 % through this loop at 1024 alerts; a lone
-            # model(...) call is 4 % slower that way, so the hint is taken back right after the launches are queued)
-            _lib.check(_lib.lib().btsbot_set_option(m._handle.ptr, b"stage2p_alerts", _S2P_HINT), "btsbot_set_option")
+            # several forwards in flight: the library takes the forms that hold fewer CUs per launch -- the stage-2
+            # kernel keeps 7 alerts per workgroup at every batch size and so leaves ~40 % of the CUs to the other
+            # stream's kernels (+6 % through this loop at 1024 alerts), the 1x1 stage runs on half the workgroups.  A
+            # lone model(...) call is slower that way (stage 2: 4 %), so the hint is taken back right after the
+            # launches are queued
+            _lib.check(_lib.lib().btsbot_set_option(m._handle.ptr, b"forwards_in_flight", 1), "btsbot_set_option")
+            if _S2P_HINT:
+                _lib.check(_lib.lib().btsbot_set_option(m._handle.ptr, b"stage2p_alerts", _S2P_HINT), "btsbot_set_option")
         with torch.cuda.stream(side), torch.no_grad():
             try:
                 if self.embed is None:
@@ -118,7 +123,9 @@ class ScoreStream:
                     out = (logits, emb)
             finally:
                 if hinted:
-                    _lib.lib().btsbot_set_option(m._handle.ptr, b"stage2p_alerts", 0)
+                    _lib.lib().btsbot_set_option(m._handle.ptr, b"forwards_in_flight", 0)
+                    if _S2P_HINT:
+                        _lib.lib().btsbot_set_option(m._handle.ptr, b"stage2p_alerts", 0)
             done = torch.cuda.Event()
             done.record(side)
         return out, done, inputs

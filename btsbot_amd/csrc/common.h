@@ -164,6 +164,57 @@ template <int DEG> __device__ __forceinline__ float gelu_poly(float x) {
   const float e = __builtin_amdgcn_exp2f(gelu_q<DEG>(a));
   return fmaf(-a, e, relu_f(x));
 }
+// gelu_poly<3> of eight values on packed f16, for hidden activations that go to the matrix pipe as an f16 operand
+// (stage0b.hip's bf16 inference form; tools/unit/mlp_occ.hip): value 2 i and 2 i + 1 are rounded to f16 as a pair
+// (v_cvt_pkrtz: towards zero, so a finite input never becomes inf), |x| is a mask, q(a) runs on three v_pk_fma_f16 with
+// the degree-3 coefficients rounded to f16, 2^q is one v_exp_f16 per half, and max(x, 0) - a E is v_pk_max_f16 + one
+// v_pk_fma_f16: 11 instructions per pair, the result IS the operand dword.  Against the erf GELU: max 3.9e-3 / rms
+// 1.2e-3 over |x| <= 8 (tests/test_gpu_stage0_gelu.py), a quarter of gelu_poly<3> rounded to bf16.  Past |x| ~ 9 q
+// overflows to -inf and E = 0: the result is max(x, 0), at most 65504.
+// The four pairs advance together, one step at a time (sched_barrier: hipcc otherwise runs each pair's chain of eight
+// dependent instructions to its end, with an s_nop for the hazard between most of them, to save three registers).
+__device__ __forceinline__ void gelu_pk4(const float (&x)[8], f16x2v (&g)[4]) {
+  const f16x2v c3 = {(_Float16)-0.024772998623334343f, (_Float16)-0.024772998623334343f};
+  const f16x2v c2 = {(_Float16)-0.49926576060257244f, (_Float16)-0.49926576060257244f};
+  const f16x2v c1 = {(_Float16)-1.1287482669759885f, (_Float16)-1.1287482669759885f};
+  const f16x2v c0 = {(_Float16)-1.0036805164077327f, (_Float16)-1.0036805164077327f};
+  const f16x2v z = {(_Float16)0.f, (_Float16)0.f};
+  f16x2v xh[4], a[4], t[4];
+  unsigned e[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) xh[i] = __builtin_bit_cast(f16x2v, __builtin_amdgcn_cvt_pkrtz(x[2 * i], x[2 * i + 1]));
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) a[i] = __builtin_bit_cast(f16x2v, __builtin_bit_cast(unsigned, xh[i]) & 0x7fff7fffu);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) t[i] = __builtin_elementwise_fma(a[i], c3, c2);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) t[i] = __builtin_elementwise_fma(a[i], t[i], c1);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) t[i] = __builtin_elementwise_fma(a[i], t[i], c0);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) xh[i] = __builtin_elementwise_max(xh[i], z);
+  __builtin_amdgcn_sched_barrier(0);
+  // 2^q per half, the second one written into the high half in place: from __builtin_elementwise_exp2 hipcc makes
+  // v_exp_f16 + v_exp_f16_sdwa + v_pack_b32_f16, a slot more per pair.  The compiler's hazard recogniser does not look
+  // inside inline asm: gfx950 wants a wait state between a transcendental or a dst_sel write and a VALU read of the
+  // result.  Three other instructions stand between the two writes of a register (volatile: kept in this order), and
+  // the s_nop stands in front of whichever product hipcc places first.
+#pragma unroll
+  for (int i = 0; i < 4; ++i) asm volatile("v_exp_f16_e32 %0, %1" : "=&v"(e[i]) : "v"(__builtin_bit_cast(unsigned, t[i])));
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    asm volatile("v_exp_f16_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1"
+                 : "+v"(e[i]) : "v"(__builtin_bit_cast(unsigned, t[i])));
+  asm volatile("s_nop 0");
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) g[i] = __builtin_elementwise_fma(-a[i], __builtin_bit_cast(f16x2v, e[i]), xh[i]);
+}
 // d/dx of gelu_poly: with E = 2^q(a), D = E (1 + a ln2 q'(a)):  x > 0: 1 - D,  x < 0: D  (x = 0: 1/2 either way
 // up to the fit error).  The 16-bit training forward applies gelu_poly, so its backward differentiates gelu_poly.
 template <int DEG> __device__ __forceinline__ float gelu_dq(float a);

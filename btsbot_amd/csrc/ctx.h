@@ -20,6 +20,7 @@ struct BlockPk {  // per ConvNeXt block: master offsets + packed offsets (bytes 
   size_t p_s0par = 0;      // stage-0 / stage-1 blocks: parameter image for stage0b.hip / stage1b.hip
   size_t p_s0par_t = 0;    // ... for their keeping forms (training forward): the same image with f16 taps in every mode
   size_t p_fc2g = 0;       // diag(gamma) W2 in the operand type (megakernels fold the layer scale)
+  size_t p_fc2g_h = 0;     // ... in f16, stage-0 blocks of a bf16 / fp8 handle: stage0b.hip's inference form hands fc2 f16 hidden activations
   size_t p_w1p = 0, p_w2p = 0;   // stage2p.hip / stage3.hip: fc1 / gamma * fc2 filters as MFMA A fragments
   size_t p_scales = 0;           // fp8 mode: {S1, 1/S1, S2, 1/S2} of those two
   size_t p_x2_w1 = 0, p_x2_w2g = 0;   // split mode, stages 0-1: fc1 / gamma * fc2 filters, f16 heads (stage0b / stage1b)

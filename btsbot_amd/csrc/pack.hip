@@ -499,6 +499,11 @@ void image_walk(btsbot_ctx* h) {
             [=](hipStream_t st) {
               return launch_rowscale_cast(h->cfg.precision, h->mirror + b->fc2_w, h->mirror + b->gamma, IMG(h, b->p_fc2g), ch, 4 * ch, st);
             });
+        // the same in f16 for stage0b.hip's bf16 inference form (stage 0 of an fp8 handle too), whose hidden type is f16
+        if (i == 0 && sc.stage0 && h->prec_s01() == BTSBOT_BF16)
+          own("p_fc2g_h", &b->p_fc2g_h, wb * 2, F, false, nullptr, [=](hipStream_t st) {
+            return launch_rowscale_cast(BTSBOT_F16, h->mirror + b->fc2_w, h->mirror + b->gamma, IMG(h, b->p_fc2g_h), ch, 4 * ch, st);
+          });
         if (frag) {
           const bool s3 = i == 3;   // (stage 2's two are reserved above, with their table jobs)
           own("p_scales", &b->p_scales, 64, 0, false, nullptr, nullptr);   // fp8 mode: {S1, 1/S1, S2, 1/S2}, written with the two below

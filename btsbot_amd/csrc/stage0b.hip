@@ -126,9 +126,18 @@ __device__ __forceinline__ void regs_to_tap(const f32x16 (&x)[CT], float* tap, i
 // WPS = waves per SIMD the register allocation leaves room for (2: two workgroups per CU, 256 registers; 1: one
 // workgroup per CU with 512 registers -- the split mode's doubled fragments spill at 256)
 // KEEP: the training forward (Stage0Args::keep_*): the same kernel plus the copies the backward reads
-template <typename T, bool X2, int WPS = 2, bool KEEP = false>
+// HT: the type in which the hidden activations (and with them gamma * W2, Stage0Blk::w2g) reach the matrix pipe.  The
+// bf16 inference form takes f16.  Every single-operand inference form with f16 hidden activations -- that one and the f16
+// handle's -- applies the GELU as gelu_pk4() on pairs of neighbouring fc1 accumulator registers: 5.5 issue slots per value
+// against 7.5 (gelu_poly<3> and the rounding to bf16) and 9 (gelu_poly<5>, f16), and for the bf16 handle 11 significant
+// bits of the hidden value against 8.  The keeping forms have HT = T and gelu_for<T>, because the backward
+// differentiates gelu_poly; the split form keeps gelu_poly<5>, whose remainder operand needs the fp32 value.
+template <typename T, bool X2, int WPS = 2, bool KEEP = false, typename HT = T>
 __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
   using frag = typename Mfma<T>::frag;
+  using hfrag = typename Mfma<HT>::frag;
+  constexpr bool PKG = std::is_same<HT, f16_t>::value && !X2 && !KEEP;   // the packed-f16 GELU
+  static_assert(std::is_same<HT, T>::value || PKG, "a hidden type of its own: f16, inference, one operand");
   // the depthwise phase's operand type: the training forward reads map and taps as f16 in the bf16 mode too -- the
   // map is the fp32 residual stream, and its rounding to bf16 in front of 49 products moved a 50-step bf16 training
   // run ten times further from the fp32 recipe than the per-op forward's fp32 convolution (test_16bit_training_follows_
@@ -497,7 +506,8 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
         if (ch == 1 && j == 0) zero_planar();
         const unsigned char* w1s = smem + L::slot(ch % NSLOT);
         const unsigned char* w2s = w1s + 4096;
-        frag a1[4], a2[CT][2], a1l[X2 ? 4 : 1], a2l[X2 ? CT : 1][2];
+        frag a1[4], a1l[X2 ? 4 : 1];
+        hfrag a2[CT][2], a2l[X2 ? CT : 1][2];
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
           a1[ks] = *reinterpret_cast<const frag*>(w1s + lr * 128 + (((ks * 2 + h) ^ ((lr >> 1) & 7)) << 4));
@@ -508,8 +518,8 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
 #pragma unroll
           for (int s2 = 0; s2 < 2; ++s2) {
             const int r = ct * 32 + lr;
-            a2[ct][s2] = *reinterpret_cast<const frag*>(w2s + r * 64 + (((s2 * 2 + h) ^ swz4(r)) << 4));
-            if (X2) a2l[ct][s2] = *reinterpret_cast<const frag*>(w2s + CHUNKB + r * 64 + (((s2 * 2 + h) ^ swz4(r)) << 4));
+            a2[ct][s2] = *reinterpret_cast<const hfrag*>(w2s + r * 64 + (((s2 * 2 + h) ^ swz4(r)) << 4));
+            if (X2) a2l[ct][s2] = *reinterpret_cast<const hfrag*>(w2s + CHUNKB + r * 64 + (((s2 * 2 + h) ^ swz4(r)) << 4));
           }
         // (inline asm: behind a compiler-visible ds_read of anything but the ring hipcc waits vmcnt(0) -- it cannot
         //  tell that the bias words are not an LDS-DMA destination -- and the ring's two chunks in flight are gone)
@@ -548,24 +558,35 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
           // GELU in two halves, each followed by the fc2 MFMAs that consume it
 #pragma unroll
           for (int s2 = 0; s2 < 2; ++s2) {
-            frag hf, hfl;
+            hfrag hf, hfl;
+            if constexpr (PKG) {
+              // registers 8 s2 + 2 i and + 1 are neighbouring k of the fc2 B fragment: the packed result is its dword i
+              float hx[8];
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
+              for (int r = 0; r < 8; ++r) hx[r] = hacc[t][8 * s2 + r];
+              f16x2v g2[4];
+              gelu_pk4(hx, g2);
+              hf = __builtin_shufflevector(__builtin_shufflevector(g2[0], g2[1], 0, 1, 2, 3),
+                                           __builtin_shufflevector(g2[2], g2[3], 0, 1, 2, 3), 0, 1, 2, 3, 4, 5, 6, 7);
+            } else {
+#pragma unroll
+              for (int r = 0; r < 8; ++r) {
 #ifdef S0_EXP_NOGELU
-              const float gv = hacc[t][8 * s2 + r];
+                const float gv = hacc[t][8 * s2 + r];
 #else
-              const float gv = gelu_for<T>(hacc[t][8 * s2 + r]);
+                const float gv = gelu_for<T>(hacc[t][8 * s2 + r]);
 #endif
-              hf[r] = (T)gv;
-              if (X2) hfl[r] = (T)(gv - (float)hf[r]);
+                hf[r] = (HT)gv;
+                if (X2) hfl[r] = (HT)(gv - (float)hf[r]);
+              }
             }
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
               if (X2) {
-                x[t][ct] = Mfma<T>::m32(a2l[ct][s2], hf, x[t][ct]);
-                x[t][ct] = Mfma<T>::m32(a2[ct][s2], hfl, x[t][ct]);
+                x[t][ct] = Mfma<HT>::m32(a2l[ct][s2], hf, x[t][ct]);
+                x[t][ct] = Mfma<HT>::m32(a2[ct][s2], hfl, x[t][ct]);
               }
-              x[t][ct] = Mfma<T>::m32(a2[ct][s2], hf, x[t][ct]);
+              x[t][ct] = Mfma<HT>::m32(a2[ct][s2], hf, x[t][ct]);
             }
           }
         }
@@ -689,8 +710,9 @@ __global__ void pack_s0par_kernel(const float* __restrict__ taps, const float* _
   reinterpret_cast<float*>(out + (X2 ? 2 : 1) * TW_BYTES)[f] = v;
 }
 
-template <typename T, bool X2 = false, int WPS = 2, bool KEEP = false> int launch_stage0b_t(const Stage0Args& a, hipStream_t st) {
-  auto kern = stage0b_kernel<T, X2, WPS, KEEP>;
+template <typename T, bool X2 = false, int WPS = 2, bool KEEP = false, typename HT = T>
+int launch_stage0b_t(const Stage0Args& a, hipStream_t st) {
+  auto kern = stage0b_kernel<T, X2, WPS, KEEP, HT>;
   static DevOnce attr_set;
   // (BTSBOT_AMD_S0_ONE_WG=1: developer probe -- the LDS request padded so that ONE workgroup fits a CU: how the kernel's
   //  time scales from one to two waves per SIMD says what two more would buy)
@@ -753,7 +775,8 @@ bool stage0_supported(int prec, int c0) {
   return (prec == BTSBOT_BF16 || prec == BTSBOT_F16 || prec == BTSBOT_F16X2) && c0 == 64;
 }
 
-// Needs Stage0Blk::par, ::w1 (plain [256][64]) and Stage0Blk::w2g (gamma-scaled [64][256]), 16-bit.
+// Needs Stage0Blk::par, ::w1 (plain [256][64]) and Stage0Blk::w2g (gamma-scaled [64][256]), 16-bit.  The bf16 inference
+// form (also stage 0 of an fp8 handle) reads w2g as f16 (stage_args.hip: p_fc2g_h); its keeping form as bf16.
 int launch_stage0b(int prec, const Stage0Args& a, hipStream_t st) {
   if (a.B <= 0) return BTSBOT_OK;
   if (a.keep_xn[0] != nullptr) {   // the training forward
@@ -767,7 +790,7 @@ int launch_stage0b(int prec, const Stage0Args& a, hipStream_t st) {
     btsbot_set_error("stage0b: the training forward runs in the bf16 / f16 modes, not %d", prec);
     return BTSBOT_ERR_INVALID_ARG;
   }
-  if (prec == BTSBOT_BF16) return launch_stage0b_t<bf16_t>(a, st);
+  if (prec == BTSBOT_BF16) return launch_stage0b_t<bf16_t, false, 2, false, f16_t>(a, st);
   if (prec == BTSBOT_F16) return launch_stage0b_t<f16_t>(a, st);
   if (prec == BTSBOT_F16X2) {
     if (a.ds_w_lo == nullptr || a.stem_w_lo == nullptr || a.blk[0].w1_lo == nullptr || a.blk[0].w2g_lo == nullptr ||

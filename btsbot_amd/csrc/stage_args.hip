@@ -11,7 +11,8 @@
 
 namespace {
 
-int s01_blk(const btsbot_ctx* h, const BlockPk& b, bool keep, Stage0Blk* out) {
+// hid16: stage0b.hip's bf16 inference form takes gamma * W2 as f16 (its hidden type); the keeping form and stage 1 the bf16 image
+int s01_blk(const btsbot_ctx* h, const BlockPk& b, bool keep, bool hid16, Stage0Blk* out) {
   const float* m = h->mirror;
   const bool x2 = h->x2 && !keep;
   Stage0Blk& k = *out;
@@ -24,7 +25,7 @@ int s01_blk(const btsbot_ctx* h, const BlockPk& b, bool keep, Stage0Blk* out) {
   k.gamma = m + b.gamma;
   k.w1 = x2 ? IMG(h, b.p_x2_w1) : IMG(h, b.p_fc1);
   k.par = keep ? IMG(h, b.p_s0par_t) : IMG(h, b.p_s0par);
-  k.w2g = x2 ? IMG(h, b.p_x2_w2g) : IMG(h, b.p_fc2g);
+  k.w2g = x2 ? IMG(h, b.p_x2_w2g) : hid16 ? IMG(h, b.p_fc2g_h) : IMG(h, b.p_fc2g);
   k.w1_lo = x2 ? IMG(h, b.p_x2_w1lo) : nullptr;
   k.w2g_lo = x2 ? IMG(h, b.p_x2_w2glo) : nullptr;
   return BTSBOT_OK;
@@ -44,7 +45,7 @@ int stage0_args(const btsbot_ctx* h, bool keep, Stage0Args* out) {
   a.stem_lnw = m + h->stem_lnw;
   a.stem_lnb = m + h->stem_lnb;
   for (int j = 0; j < 2; ++j) {
-    const int s = s01_blk(h, h->blocks[0][j], keep, &a.blk[j]);
+    const int s = s01_blk(h, h->blocks[0][j], keep, !keep && h->prec_s01() == BTSBOT_BF16, &a.blk[j]);
     if (s != BTSBOT_OK) return s;
   }
   a.ds_lnw = m + d.ln_w;
@@ -61,7 +62,7 @@ int stage1_args(const btsbot_ctx* h, bool keep, Stage1Args* out) {
   Stage1Args& a = *out;
   memset(&a, 0, sizeof(a));
   for (int j = 0; j < 2; ++j) {
-    const int s = s01_blk(h, h->blocks[1][j], keep, &a.blk[j]);
+    const int s = s01_blk(h, h->blocks[1][j], keep, false, &a.blk[j]);
     if (s != BTSBOT_OK) return s;
   }
   a.ds_lnw = m + d.ln_w;

@@ -158,7 +158,13 @@ int btsbot_use_workspace(btsbot_handle h, int max_chunk, void* workspace, int64_
  * torch.sigmoid (architectures.py:166-171,121-122,292-293,367-372; inference_example.py:84-91).
  * `triplets` may be NULL for BTSBOT_UM_NN, `meta` NULL for BTSBOT_CONVNEXT; `scores` may be NULL.
  * training != 0 selects BatchNorm batch statistics + dropout (seeded by dropout_seed) and keeps
- * the activations needed by btsbot_backward(). */
+ * the activations needed by btsbot_backward().
+ * Range, ConvNeXt pico in BTSBOT_BF16 / BTSBOT_FP8 / BTSBOT_F16: stage 0's two blocks hand fc2 their hidden
+ * activations as F16 operands, from a GELU evaluated on packed f16 (DESIGN.md sections 2 and 4a).  A bf16 handle's
+ * stage-0 pre-activations (fc1's output, behind a LayerNorm) therefore have f16 RANGE in inference: beyond +-65504
+ * they saturate (the activation is then max(x, 0), at most 65504; no inf / NaN).  The training forward (below: the
+ * keeping forms, whose own f16 range note concerns the depthwise phase) keeps bf16 hidden activations and
+ * gelu_poly<3>, which its backward differentiates. */
 int btsbot_forward(btsbot_handle h, const float* triplets_nchw, const float* meta,
                    float* logits, float* scores, int batch, int training,
                    uint64_t dropout_seed, void* stream);

@@ -10,14 +10,9 @@
 #include <cstdio>
 #include <cstdlib>
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+#include "../../btsbot_amd/csrc/common.h"   // relu_f(), gelu_pk4(): one definition for the probe and the kernels
 
-__device__ __forceinline__ float relu_f(float x) {
-  const int b = __float_as_int(x);
-  return __int_as_float(b > 0 ? b : 0);
-}
+typedef __attribute__((ext_vector_type(16))) float f32x16;
 __device__ __forceinline__ float gelu3(float x) {
   const float a = __builtin_fabsf(x);
   float t = fmaf(a, -0.024772998623334343f, -0.49926576060257244f);
@@ -98,24 +93,8 @@ __global__ __launch_bounds__(NW * 64, WPS) void mlp_kernel(float* out, int iters
 
 
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
 
-// packed-f16 GELU of two values: q(a) on v_pk_fma_f16, 2^q per half (v_exp_f16), max(x, 0) - a E packed
-__device__ __forceinline__ f16x2 gelu_pk(float x0, float x1) {
-  const f16x2 xh = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(x0, x1));
-  const f16x2 a = __builtin_bit_cast(f16x2, __builtin_bit_cast(unsigned, xh) & 0x7fff7fffu);
-  const f16x2 c3 = {(_Float16)-0.024772998623334343f, (_Float16)-0.024772998623334343f};
-  const f16x2 c2 = {(_Float16)-0.49926576060257244f, (_Float16)-0.49926576060257244f};
-  const f16x2 c1 = {(_Float16)-1.1287482669759885f, (_Float16)-1.1287482669759885f};
-  const f16x2 c0 = {(_Float16)-1.0036805164077327f, (_Float16)-1.0036805164077327f};
-  f16x2 t = a * c3 + c2;
-  t = a * t + c1;
-  t = a * t + c0;
-  const f16x2 e = __builtin_elementwise_exp2(t);   // hipcc: v_exp_f16 per half
-  const f16x2 z = {(_Float16)0.f, (_Float16)0.f};
-  const f16x2 r = __builtin_elementwise_max(xh, z);
-  return r - a * e;
-}
+// (the packed-f16 GELU, gelu_pk4(), is the library's: csrc/common.h)
 
 // The lean loop: one column block per wave; nothing but the accumulators lives across a chunk -- the fc1 B operand is
 // re-read from LDS every chunk, filter fragments are read in groups of four right before their products
@@ -165,11 +144,15 @@ __global__ __launch_bounds__(NW * 64, WPS) void lean_kernel(float* out, int iter
       for (int ct = 0; ct < CT; ++ct) a2[ct] = *reinterpret_cast<const bf16x8*>(base + (KS1 + ct * 2 + s2) * 1024);
       if (PK) {
         f16x8 hf;
+        float hx[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) hx[r] = hacc[8 * s2 + r];
+        f16x2v g2[4];
+        gelu_pk4(hx, g2);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const f16x2 g2 = gelu_pk(hacc[8 * s2 + 2 * r], hacc[8 * s2 + 2 * r + 1]);
-          hf[2 * r] = g2[0];
-          hf[2 * r + 1] = g2[1];
+          hf[2 * r] = g2[r][0];
+          hf[2 * r + 1] = g2[r][1];
         }
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)

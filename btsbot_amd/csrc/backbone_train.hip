@@ -67,8 +67,6 @@ struct BBCache {
   size_t total;
 };
 
-size_t al(size_t n) { return (n + 255) / 256 * 256; }
-
 // carve the cache for a batch of B alerts; base == nullptr only measures
 BBCache carve_bb(const btsbot_ctx* h, unsigned char* base, int B) {
   const btsbot_config& c = h->cfg;
@@ -78,7 +76,7 @@ BBCache carve_bb(const btsbot_ctx* h, unsigned char* base, int B) {
   size_t cur = 0;
   auto take = [&](size_t bytes) {
     unsigned char* p = base ? base + cur : nullptr;
-    cur += al(bytes);
+    cur += align256(bytes);
     return p;
   };
   size_t maxrc = 0, maxc4c = 0, maxpat = 0, maxplanes = 0;
@@ -157,12 +155,6 @@ BBCache carve_bb(const btsbot_ctx* h, unsigned char* base, int B) {
   return k;
 }
 
-#define TRYB(call)                  \
-  do {                              \
-    int _s = (call);                \
-    if (_s != BTSBOT_OK) return _s; \
-  } while (0)
-
 // One 1x1 / downsample product of the training step, out = epi(A W^T): under train_split on split operands -- W's split
 // planes at slot `sw`, a gradient operand A scaled by its amax record, amax_out the record of a gradient it writes
 // (gemm_x2.hip) -- else in the handle's operand type with the packed filter at slot `w`
@@ -225,9 +217,9 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
     // stem + stage 0 + the first downsample as one launch of the inference megakernel's keeping form: every buffer the
     // backward reads of them is written on its way (stage0.h).  It needs this step's operand images at once: the
     // re-pack queued behind the previous optimiser step runs under the mask draws and whatever precedes this call
-    TRYB(pack_sync_early(h, st));
+    TRY(pack_sync_early(h, st));
     Stage0Args a;
-    TRYB(stage0_args(h, true, &a));
+    TRY(stage0_args(h, true, &a));
     a.img = img;
     for (int j = 0; j < 2; ++j) {
       a.keep_d[j] = k.blk[0][j].d;
@@ -240,23 +232,23 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
     a.tap_stage = k.xs[0];
     a.keep_patches = k.patches[1];
     a.B = B;
-    TRYB(launch_stage0b(c.precision, a, st));
+    TRY(launch_stage0b(c.precision, a, st));
   } else if (sc.stem16)
-    TRYB(launch_stem16(c.precision, img, m + h->stem_w, m + h->stem_b, m + h->stem_lnw, m + h->stem_lnb, stage_in(0), B,
+    TRY(launch_stem16(c.precision, img, m + h->stem_w, m + h->stem_b, m + h->stem_lnw, m + h->stem_lnb, stage_in(0), B,
                        c.dims[0], st, k.stem_pre));
   else
-    TRYB(launch_stem(img, m + h->stem_w, m + h->stem_b, m + h->stem_lnw, m + h->stem_lnb, stage_in(0),
+    TRY(launch_stem(img, m + h->stem_w, m + h->stem_b, m + h->stem_lnw, m + h->stem_lnb, stage_in(0),
                      B, c.dims[0], st, k.stem_pre));
-  TRYB(pack_sync(h, st));   // the operand images of this step (packed on the side stream while the stem ran)
+  TRY(pack_sync(h, st));   // the operand images of this step (packed on the side stream while the stem ran)
   // (stage 2's form does not keep the blocks' depthwise outputs, BlkBuf::d)
   const bool s0t = sc.s0_keep, s1t = sc.s1_keep, s2t = sc.s2_kept(B);
   for (int i = s0t ? 1 : 0; i < 4; ++i) {
     const int ch = c.dims[i], hw = STAGE_HW[i], rows = B * hw * hw;
     if (i > 0 && !(i == 3 && s2t) && !(i == 1 && s0t) && !(i == 2 && s1t)) {
       const int cin = c.dims[i - 1];
-      TRYB(launch_ln_patch(c.precision, k.xs[i - 1], m + h->down[i].ln_w, m + h->down[i].ln_b,
+      TRY(launch_ln_patch(c.precision, k.xs[i - 1], m + h->down[i].ln_w, m + h->down[i].ln_b,
                            k.patches[i], B, STAGE_HW[i - 1], cin, st));
-      TRYB(train_gemm(h, EPI_BIAS, k.patches[i], h->down[i].p_w, h->down[i].p_s_w, m + h->down[i].b, nullptr, nullptr,
+      TRY(train_gemm(h, EPI_BIAS, k.patches[i], h->down[i].p_w, h->down[i].p_s_w, m + h->down[i].b, nullptr, nullptr,
                       stage_in(i), rows, ch, 4 * cin, nullptr, nullptr, st));
     }
     const size_t nblk = h->blocks[i].size();
@@ -264,7 +256,7 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
       // stage 1 + the second downsample as one launch of stage1b's keeping form: block 0's input is its x_in, block 1's
       // input the residual copy the kernel parks between the blocks anyway
       Stage1Args a;
-      TRYB(stage1_args(h, true, &a));
+      TRY(stage1_args(h, true, &a));
       a.x_in = stage_in(1);
       for (int j = 0; j < 2; ++j) {
         a.keep_d[j] = k.blk[1][j].d;
@@ -275,7 +267,7 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
       a.tap_stage = k.xs[1];
       a.keep_patches = k.patches[2];
       a.B = B;
-      TRYB(launch_stage1b(c.precision, a, st));
+      TRY(launch_stage1b(c.precision, a, st));
       continue;
     }
     if (i == 2 && s2t) {
@@ -285,7 +277,7 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
       // output is not kept: dw3ln_bwd_kernel recomputes it (block 0's buffer for it takes the copy of the stage input the
       // kernel writes for every block alike).
       Stage2pArgs a;
-      TRYB(stage2p_args(h, true, &a));
+      TRY(stage2p_args(h, true, &a));
       a.x_in = stage_in(2);
       for (size_t j = 0; j < nblk; ++j) {
         const BlkBuf& sb = k.blk[2][j];
@@ -300,25 +292,25 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
       a.B = B;
       a.train = 1;
       a.stamps = h->stamps ? h->stamps + STAMP_S2 : nullptr;   // (tools/stamps_train.py)
-      TRYB(launch_stage2p(c.precision, a, st));
+      TRY(launch_stage2p(c.precision, a, st));
       continue;
     }
     for (size_t j = 0; j < nblk; ++j) {
       const BlockPk& b = h->blocks[i][j];
       const BlkBuf& s = k.blk[i][j];
       float* xout = j + 1 < nblk ? k.blk[i][j + 1].xin : k.xs[i];
-      TRYB(launch_dwconv_ln(c.precision, s.xin, IMG_F32(h, b.p_dw),
+      TRY(launch_dwconv_ln(c.precision, s.xin, IMG_F32(h, b.p_dw),
                             m + b.dw_b, m + b.ln_w, m + b.ln_b, s.xn, B, hw, ch, st, s.d));
       if (s.fpart != nullptr) {
         // the block's backward recomputes fc1 (mlp_bwd.hip): neither the pre-activation nor the GELU output is kept
-        TRYB(launch_fused_mlp(c.precision, ch, s.xn, IMG(h, b.p_fused), m + b.fc1_b, m + b.fc2_b, m + b.gamma, xout,
+        TRY(launch_fused_mlp(c.precision, ch, s.xn, IMG(h, b.p_fused), m + b.fc1_b, m + b.fc2_b, m + b.gamma, xout,
                               rows, st, nullptr, nullptr, nullptr, 0, s.xin));
         continue;
       }
       // (split training: the activations enter the products unscaled, as in inference)
-      TRYB(train_gemm(h, EPI_GELU_SAVE, s.xn, b.p_fc1, b.p_s_fc1, m + b.fc1_b, nullptr, reinterpret_cast<const float*>(s.a), s.h,
+      TRY(train_gemm(h, EPI_GELU_SAVE, s.xn, b.p_fc1, b.p_s_fc1, m + b.fc1_b, nullptr, reinterpret_cast<const float*>(s.a), s.h,
                       rows, 4 * ch, ch, nullptr, nullptr, st));
-      TRYB(train_gemm(h, EPI_RESID, s.h, b.p_fc2, b.p_s_fc2, m + b.fc2_b, m + b.gamma, s.xin, xout, rows, ch, 4 * ch, nullptr,
+      TRY(train_gemm(h, EPI_RESID, s.h, b.p_fc2, b.p_s_fc2, m + b.fc2_b, m + b.gamma, s.xin, xout, rows, ch, 4 * ch, nullptr,
                       nullptr, st));
     }
   }
@@ -341,7 +333,7 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
   const bool s2t = sc.s2_kept(B);
   float* dy = k.dyA;
   float* dxn = k.dyB;
-  TRYB(launch_copy_f32(dy, dfeat, (size_t)B * c.dims[3], st));
+  TRY(launch_copy_f32(dy, dfeat, (size_t)B * c.dims[3], st));
   // Two streams.  `st` carries the chain every block waits on (dy -> da -> dxn -> LayerNorm -> depthwise -> dy of the
   // block before); the filter-gradient GEMMs, their slice reductions and the layer-scale / bias gradients hang off
   // that chain (nothing downstream reads them before the optimiser), so they trail it on `h->side`: in stages 2-3
@@ -358,20 +350,20 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
   Pend pend[8];
   int npend = 0;
   auto fork = [&]() -> int {
-    TRYB(side_fork(h, st, &sd));
+    TRY(side_fork(h, st, &sd));
     for (int q = 0; q < npend; ++q) {
-      if (pend[q].cols == 0) TRYB(launch_dw3_rows(pend[q].part, pend[q].dst, pend[q].rows, sd));
-      else TRYB(launch_colsum(BTSBOT_F32, pend[q].part, pend[q].dst, pend[q].rows, pend[q].cols, sd));
+      if (pend[q].cols == 0) TRY(launch_dw3_rows(pend[q].part, pend[q].dst, pend[q].rows, sd));
+      else TRY(launch_colsum(BTSBOT_F32, pend[q].part, pend[q].dst, pend[q].rows, pend[q].cols, sd));
     }
     npend = 0;
     return BTSBOT_OK;
   };
   auto join = [&]() -> int {
-    if (npend > 0) TRYB(fork());
+    if (npend > 0) TRY(fork());
     return side_join(h, st);
   };
   auto add_pend = [&](const float* part, float* dst, int rows, int cols) -> int {
-    if (npend == (int)(sizeof(pend) / sizeof(pend[0]))) TRYB(fork());
+    if (npend == (int)(sizeof(pend) / sizeof(pend[0]))) TRY(fork());
     pend[npend++] = Pend{part, dst, rows, cols};
     return BTSBOT_OK;
   };
@@ -382,10 +374,10 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
   // here, afterwards every consumer (fc2_grads_kernel, unpack_down_grad_kernel) leaves what it read zero
   {
     float* z0 = k.fS0 != nullptr ? k.fS0 : k.S;
-    TRYB(launch_fill0(z0, (size_t)((k.G + k.g_floats) - z0), st));
+    TRY(launch_fill0(z0, (size_t)((k.G + k.g_floats) - z0), st));
   }
   const bool sp = sc.train_split;
-  if (sp) TRYB(launch_fill0(reinterpret_cast<float*>(k.amax), (size_t)k.namax * AMAX_WORDS, st));
+  if (sp) TRY(launch_fill0(reinterpret_cast<float*>(k.amax), (size_t)k.namax * AMAX_WORDS, st));
   auto amax_rec = [&](int slot) { return k.amax + (size_t)slot * AMAX_WORDS; };
   auto blk_amax = [&](int i, int j) {   // dy slot of block (i, j); its da slot follows
     int b = j;
@@ -394,7 +386,7 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
   };
   // (deterministic mode: the per-GEMM launches with their fixed-order column sums)
   const bool batching = k.gb_floats > 0 && det_alloc(0) == nullptr;
-  if (batching) TRYB(launch_fill0(k.gb0, k.gb_floats, st));
+  if (batching) TRY(launch_fill0(k.gb0, k.gb_floats, st));
   // operand-type buffer the consumer after block (i, j) reads its dy from: the block before, else the downsample
   auto next_dyT = [&](int i, int j) -> void* {
     if (j > 0) return k.blk[i][j - 1].dyT;
@@ -405,7 +397,7 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
   // (no fork of its own: it reads the caller's triplets, which the forward already read on this stream, and the side
   //  stream has the head's backward in front of it, queued behind a fork a few launches ago)
   if (sc.side_stream && h->side != nullptr) sd = h->side;
-  TRYB(launch_stem_im2col(prec, img, k.stem_patches, B, sd));
+  TRY(launch_stem_im2col(prec, img, k.stem_patches, B, sd));
   bool dyT_ready = false;
   for (int i = 3; i >= 0; --i) {
     const int ch = c.dims[i], hw = STAGE_HW[i], rows = B * hw * hw, H = 4 * ch;
@@ -419,9 +411,9 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
       unsigned* am_dy = sp ? amax_rec(blk_amax(i, j)) : nullptr;
       unsigned* am_da = sp ? amax_rec(blk_amax(i, j) + 1) : nullptr;
       if (sp)   // (split training: the fp32 copy also records dy's largest magnitude)
-        TRYB(launch_copy_amax(dy, reinterpret_cast<float*>(s.dyT), (long)rows * ch, am_dy, st));
+        TRY(launch_copy_amax(dy, reinterpret_cast<float*>(s.dyT), (long)rows * ch, am_dy, st));
       else if (!dyT_ready)
-        TRYB(launch_scale_cast(prec, dy, nullptr, s.dyT, (long)rows * ch, ch, st));
+        TRY(launch_scale_cast(prec, dy, nullptr, s.dyT, (long)rows * ch, ch, st));
       dyT_ready = false;
       WgradReduceJob red[2];
       const bool adjacent = b.dw_b == b.dw_w + 49 * (int64_t)ch && b.ln_w == b.dw_b + ch && b.ln_b == b.ln_w + ch;
@@ -439,47 +431,47 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
       }
       if (s.fpart != nullptr) {
         // ---- da, dxn = da W1 and both filter gradients of the MLP in one launch (a recomputed from xn; da, g only on chip)
-        TRYB(launch_mlp_bwd(prec, ch, s.xn, s.dyT, IMG(h, b.p_fc1), IMG(h, b.p_fc2t), m + b.fc1_b, dxn, s.fpart,
+        TRY(launch_mlp_bwd(prec, ch, s.xn, s.dyT, IMG(h, b.p_fc1), IMG(h, b.p_fc2t), m + b.fc1_b, dxn, s.fpart,
                             k.G, s.fS, grads + b.fc1_w, grads + b.fc1_b, rows, st, red));
-        TRYB(fork());
+        TRY(fork());
       } else if (sc.s2mlp && b.p_w1tp != 0 && s2mlp_bwd_supported(prec, ch)) {
         // ---- 256 channels: da = (dy (diag(gamma) W2)) * gelu'(a) and dxn = da W1 in one launch (s2mlp_bwd.hip)
-        TRYB(launch_s2mlp_bwd(prec, s.dyT, s.a, IMG(h, b.p_w2tp), IMG(h, b.p_w1tp), s.da, dxn, rows, st));
-        if (!batched || sc.fork_per_block) TRYB(fork());
+        TRY(launch_s2mlp_bwd(prec, s.dyT, s.a, IMG(h, b.p_w2tp), IMG(h, b.p_w1tp), s.da, dxn, rows, st));
+        if (!batched || sc.fork_per_block) TRY(fork());
       } else {
         // ---- da = (dy (diag(gamma) W2)) * gelu'(a)     (gamma is folded into the packed W2^T; split training: dy, da
         //      scaled by their own powers of two)
-        TRYB(train_gemm(h, EPI_DGELU, s.dyT, b.p_fc2t, b.p_s_fc2t, nullptr, nullptr, reinterpret_cast<const float*>(s.a), s.da,
+        TRY(train_gemm(h, EPI_DGELU, s.dyT, b.p_fc2t, b.p_s_fc2t, nullptr, nullptr, reinterpret_cast<const float*>(s.a), s.da,
                         rows, H, ch, am_dy, am_da, st));
         // the side stream may start once da exists; its work is queued below, behind the chain's (a block whose GEMMs wait
         // for the stage's batch has nothing for it yet; split training batches none)
-        if (!batched || sc.fork_per_block) TRYB(fork());
+        if (!batched || sc.fork_per_block) TRY(fork());
         // ---- dxn = da W1, then the LayerNorm backward on the depthwise output d = dwconv(x_in) + bias the forward kept
-        TRYB(train_gemm(h, EPI_PLAIN, s.da, b.p_fc1t, b.p_s_fc1t, nullptr, nullptr, nullptr, dxn, rows, ch, H, am_da, nullptr,
+        TRY(train_gemm(h, EPI_PLAIN, s.da, b.p_fc1t, b.p_s_fc1t, nullptr, nullptr, nullptr, dxn, rows, ch, H, am_da, nullptr,
                         st));
       }
       void* nxt = fold_cast ? next_dyT(i, j) : nullptr;
       // (the partial rows follow the arena's layout of conv_dw.weight | conv_dw.bias | norm.weight | norm.bias)
       if (dw3) {
         // ---- 3x3 maps: the same in their own kernel (d recomputed from x_in; compact rows, reduced by launch_dw3_rows)
-        TRYB(launch_dw3ln_bwd(m + b.dw_b, dxn, m + b.ln_w, s.xin, wdw, dy, nxt, prec, s.dwpart, B, st, planes,
+        TRY(launch_dw3ln_bwd(m + b.dw_b, dxn, m + b.ln_w, s.xin, wdw, dy, nxt, prec, s.dwpart, B, st, planes,
                               (size_t)rows * ch));
-        TRYB(add_pend(s.dwpart, grads + b.dw_w, dw3_rows(B), 0));
+        TRY(add_pend(s.dwpart, grads + b.dw_w, dw3_rows(B), 0));
       } else if (s.dwpart != nullptr && adjacent) {
         // ---- LayerNorm backward, depthwise filter gradient and dx = dy + conv_flipped(dd) in one launch
-        TRYB(launch_dwln_bwd(s.d, dxn, m + b.ln_w, s.xin, wdw, dy, nxt, prec, s.dwpart, B, hw, ch, st, planes, (size_t)rows * ch));
-        TRYB(add_pend(s.dwpart, grads + b.dw_w, dwln_bwd_grid(hw, ch, B), 52 * ch));
+        TRY(launch_dwln_bwd(s.d, dxn, m + b.ln_w, s.xin, wdw, dy, nxt, prec, s.dwpart, B, hw, ch, st, planes, (size_t)rows * ch));
+        TRY(add_pend(s.dwpart, grads + b.dw_w, dwln_bwd_grid(hw, ch, B), 52 * ch));
       } else if (hw == 1 && sc.dwln && ch <= 640) {
         // ---- 1x1 maps: the same three steps per (alert, channel) in one launch
-        TRYB(launch_ln_dw1_bwd(s.d, dxn, m + b.ln_w, s.xin, wdw, dy, nxt, prec, grads + b.ln_w, grads + b.ln_b,
+        TRY(launch_ln_dw1_bwd(s.d, dxn, m + b.ln_w, s.xin, wdw, dy, nxt, prec, grads + b.ln_w, grads + b.ln_b,
                                grads + b.dw_w, grads + b.dw_b, rows, ch, st));
       } else {
-        TRYB(launch_ln_bwd(s.d, dxn, m + b.ln_w, dxn, grads + b.ln_w, grads + b.ln_b, rows, ch, st));
+        TRY(launch_ln_bwd(s.d, dxn, m + b.ln_w, dxn, grads + b.ln_w, grads + b.ln_b, rows, ch, st));
         // ---- depthwise filter gradient.  Stays in the chain: behind a fork of its own (per-block dd buffers) the
         //      step was 0.02-0.06 ms slower, as was a single fork placed here instead of behind da
-        TRYB(launch_dw_wgrad(s.xin, dxn, grads + b.dw_w, grads + b.dw_b, k.dwpart, B, hw, ch, st));
+        TRY(launch_dw_wgrad(s.xin, dxn, grads + b.dw_w, grads + b.dw_b, k.dwpart, B, hw, ch, st));
         // ---- depthwise input gradient: dx = dy + conv_flipped(dd)
-        TRYB(launch_dw_plain(dxn, wdw, 1, nullptr, dy, dy, B, hw, ch, st, nxt, prec));
+        TRY(launch_dw_plain(dxn, wdw, 1, nullptr, dy, dy, B, hw, ch, st, nxt, prec));
       }
       // ---- side: fc2 / layer-scale (S = colsum(dy), G = dy^T h), fc1 (dW1 += da^T xn, db1 += colsum(da)).  Queued
       //      after the chain's launches above (the fork itself sits behind da), so the host's five launches here never
@@ -493,24 +485,24 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
         continue;
       }
       if (s.fpart == nullptr) {
-        TRYB(train_wgrad(h, s.dyT, s.h, am_dy, nullptr, k.G, k.S, rows, ch, H, H, sd, k.wpart, &red[0]));
-        TRYB(train_wgrad(h, s.da, s.xn, am_da, nullptr, grads + b.fc1_w, grads + b.fc1_b, rows, H, ch, ch, sd,
+        TRY(train_wgrad(h, s.dyT, s.h, am_dy, nullptr, k.G, k.S, rows, ch, H, H, sd, k.wpart, &red[0]));
+        TRY(train_wgrad(h, s.da, s.xn, am_da, nullptr, grads + b.fc1_w, grads + b.fc1_b, rows, H, ch, ch, sd,
                          k.wpart + WPART_FLOATS, &red[1]));
       }
-      TRYB(launch_wgrad_reduce(red, 2, sd));
-      TRYB(launch_fc2_grads(k.G, s.fpart != nullptr ? s.fS : k.S, m + b.fc2_w, m + b.fc2_b, m + b.gamma, grads + b.fc2_w,
+      TRY(launch_wgrad_reduce(red, 2, sd));
+      TRY(launch_fc2_grads(k.G, s.fpart != nullptr ? s.fS : k.S, m + b.fc2_w, m + b.fc2_b, m + b.gamma, grads + b.fc2_w,
                             grads + b.fc2_b, grads + b.gamma, ch, H, sd));
       dyT_ready = nxt != nullptr;
     }
     auto stage_batch = [&]() -> int {
       // ---- the stage's filter-gradient GEMMs as one launch + one slice reduction, then the fc2 / layer-scale gradients
       //      of every block from its own G / S (side stream; the chain has passed the stage)
-      TRYB(launch_wgrad16_batched(prec, bj, nbj, k.wpart, 2 * WPART_FLOATS, hw >= 3 ? 576 : 256, sd));
+      TRY(launch_wgrad16_batched(prec, bj, nbj, k.wpart, 2 * WPART_FLOATS, hw >= 3 ? 576 : 256, sd));
       for (int j = (int)h->blocks[i].size() - 1; j >= 0; --j) {
         const BlockPk& b = h->blocks[i][j];
         const BlkBuf& s = k.blk[i][j];
         if (s.Gb == nullptr) continue;
-        TRYB(launch_fc2_grads(s.Gb, s.Sb, m + b.fc2_w, m + b.fc2_b, m + b.gamma, grads + b.fc2_w, grads + b.fc2_b,
+        TRY(launch_fc2_grads(s.Gb, s.Sb, m + b.fc2_w, m + b.fc2_b, m + b.gamma, grads + b.fc2_w, grads + b.fc2_b,
                               grads + b.gamma, ch, H, sd));
       }
       nbj = 0;
@@ -518,8 +510,8 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
     };
     // (with a downsample in front of the stage the batch shares that one's fork)
     if (nbj > 0 && (i == 0 || sc.fork_per_block)) {
-      TRYB(fork());
-      TRYB(stage_batch());
+      TRY(fork());
+      TRY(stage_batch());
     }
     if (i > 0) {
       // ---- downsample backward: y = patches(LN(x_prev)) Wd^T + b
@@ -528,51 +520,51 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
       void* dyT = k.dyT_down[i];
       unsigned* am_dn = sp ? amax_rec(k.namax - 5 + i) : nullptr;
       if (sp)
-        TRYB(launch_copy_amax(dy, reinterpret_cast<float*>(dyT), (long)rows * ch, am_dn, st));
+        TRY(launch_copy_amax(dy, reinterpret_cast<float*>(dyT), (long)rows * ch, am_dn, st));
       else if (!dyT_ready)
-        TRYB(launch_scale_cast(prec, dy, nullptr, dyT, (long)rows * ch, ch, st));
+        TRY(launch_scale_cast(prec, dy, nullptr, dyT, (long)rows * ch, ch, st));
       dyT_ready = false;
-      TRYB(fork());
-      if (nbj > 0) TRYB(stage_batch());
-      TRYB(train_gemm(h, EPI_PLAIN, dyT, h->down[i].p_wt, h->down[i].p_s_wt, nullptr, nullptr, nullptr, k.dpat, rows, 4 * cin,
+      TRY(fork());
+      if (nbj > 0) TRY(stage_batch());
+      TRY(train_gemm(h, EPI_PLAIN, dyT, h->down[i].p_wt, h->down[i].p_s_wt, nullptr, nullptr, nullptr, k.dpat, rows, 4 * cin,
                       ch, am_dn, nullptr, st));
       // LN backward per input pixel (x_prev = stage i-1 output), its incoming gradient gathered from the patch matrix
       // (was an unpatch launch); result is the new dy, in the 16-bit modes also as the operand of stage i-1's last
       // block (was a cast launch)
       void* nxt16 = fold_cast && !h->blocks[i - 1].empty() ? k.blk[i - 1].back().dyT : nullptr;
-      TRYB(launch_ln_bwd(k.xs[i - 1], k.dpat, m + h->down[i].ln_w, dy, grads + h->down[i].ln_w,
+      TRY(launch_ln_bwd(k.xs[i - 1], k.dpat, m + h->down[i].ln_w, dy, grads + h->down[i].ln_w,
                          grads + h->down[i].ln_b, prow, cin, st, nxt16, prec, hwp));
       dyT_ready = nxt16 != nullptr;
       // (side work queued behind the chain's launches, as in the blocks)
-      TRYB(train_wgrad(h, dyT, k.patches[i], am_dn, nullptr, k.G, grads + h->down[i].b, rows, ch, 4 * cin, 4 * cin, sd, k.wpart));
-      TRYB(launch_unpack_down_grad(k.G, grads + h->down[i].w, ch, cin, sd));
+      TRY(train_wgrad(h, dyT, k.patches[i], am_dn, nullptr, k.G, grads + h->down[i].b, rows, ch, 4 * cin, 4 * cin, sd, k.wpart));
+      TRY(launch_unpack_down_grad(k.G, grads + h->down[i].w, ch, cin, sd));
     }
     // every gradient of stages.i.* (and, for i = 3, of the heads) is queued: bucket 3 - i is complete once the
     // side stream has drained what it holds AND seen the chain up to here -- so the event is recorded on the side
     // stream behind a fork, and the chain itself does not wait (a join here stalled it ~17 us twice per step)
     if (i >= 2 && h->n_buckets == 3 && h->bucket_fine) {
-      TRYB(fork());
+      TRY(fork());
       HIP_TRY(hipEventRecord(h->bucket_ev[3 - i], sd));
     }
   }
   // ---- stem: y = LN(patches(img) Ws^T + bs);  dy is d(loss)/d(stem output) [B*225][C0]
   {
     const int c0 = c.dims[0], rows = B * 225;
-    TRYB(launch_ln_bwd(k.stem_pre, dy, m + h->stem_lnw, dxn, grads + h->stem_lnw,
+    TRY(launch_ln_bwd(k.stem_pre, dy, m + h->stem_lnw, dxn, grads + h->stem_lnw,
                        grads + h->stem_lnb, rows, c0, st, fold_cast ? k.dyT_stem : nullptr, prec));
     // (split training: the stem's filter gradient on split operands too -- its fp32 kernel meets through atomics; the
     //  patches are raw pixel values, scaled like the gradient)
     unsigned* am = sp ? amax_rec(k.namax - 5) : nullptr;
     unsigned* am_pat = sp ? amax_rec(k.namax - 1) : nullptr;
     if (sp)
-      TRYB(launch_copy_amax(dxn, reinterpret_cast<float*>(k.dyT_stem), (long)rows * c0, am, st));
+      TRY(launch_copy_amax(dxn, reinterpret_cast<float*>(k.dyT_stem), (long)rows * c0, am, st));
     else if (!fold_cast)
-      TRYB(launch_scale_cast(prec, dxn, nullptr, k.dyT_stem, (long)rows * c0, c0, st));
-    TRYB(fork());
-    if (sp) TRYB(launch_copy_amax(reinterpret_cast<const float*>(k.stem_patches), nullptr, (long)rows * 48, am_pat, sd));
-    TRYB(train_wgrad(h, k.dyT_stem, k.stem_patches, am, am_pat, grads + h->stem_w, grads + h->stem_b, rows, c0, 48, 48, sd, k.wpart));
+      TRY(launch_scale_cast(prec, dxn, nullptr, k.dyT_stem, (long)rows * c0, c0, st));
+    TRY(fork());
+    if (sp) TRY(launch_copy_amax(reinterpret_cast<const float*>(k.stem_patches), nullptr, (long)rows * 48, am_pat, sd));
+    TRY(train_wgrad(h, k.dyT_stem, k.stem_patches, am, am_pat, grads + h->stem_w, grads + h->stem_b, rows, c0, 48, 48, sd, k.wpart));
   }
-  TRYB(join());
+  TRY(join());
   if (h->n_buckets == 3 && h->bucket_fine) HIP_TRY(hipEventRecord(h->bucket_ev[2], st));
   return BTSBOT_OK;
 }

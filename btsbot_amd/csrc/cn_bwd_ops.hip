@@ -7,28 +7,7 @@
 
 namespace {
 
-#define CNT_TRY(call)               \
-  do {                              \
-    int _s = (call);                \
-    if (_s != BTSBOT_OK) return _s; \
-  } while (0)
-
 constexpr size_t LDS_MAX = 160 * 1024;   // dynamic LDS one gfx950 workgroup can ask for
-
-// partial rows of one call: stream-ordered, released behind the work on `st`
-struct CntScratch {
-  hipStream_t st;
-  float* p = nullptr;
-  explicit CntScratch(hipStream_t s) : st(s) {}
-  ~CntScratch() {
-    if (p != nullptr) (void)hipFreeAsync(p, st);
-  }
-  int alloc(size_t floats) {
-    if (hipMallocAsync(reinterpret_cast<void**>(&p), floats * sizeof(float), st) == hipSuccess) return BTSBOT_OK;
-    btsbot_set_error("op_cnt: hipMallocAsync of %zu scratch floats failed", floats);
-    return BTSBOT_ERR_HIP;
-  }
-};
 
 int cnt_bad(const char* who, const char* what) {
   btsbot_set_error("%s: %s", who, what);
@@ -77,14 +56,15 @@ extern "C" int btsbot_op_cnt_dwln_bwd(const float* d, const float* dxn, const fl
     btsbot_set_error("op_cnt_dwln_bwd: no kernel for a %dx%d map of %d channels", HW, HW, C);
     return BTSBOT_ERR_INVALID_ARG;
   }
-  CNT_TRY(cnt_planes("op_cnt_dwln_bwd", B, HW * HW, C, nplanes, pstride));
+  TRY(cnt_planes("op_cnt_dwln_bwd", B, HW * HW, C, nplanes, pstride));
   if (B == 0) return BTSBOT_OK;
   hipStream_t st = (hipStream_t)stream;
   const int rows = dwln_bwd_grid(HW, C, B);
-  CntScratch part(st);
-  CNT_TRY(part.alloc((size_t)rows * 52 * C));
-  CNT_TRY(launch_dwln_bwd(d, dxn, g, xin, w, dy, out16, prec16, part.p, B, HW, C, st, nplanes, (size_t)pstride));
-  return launch_colsum(BTSBOT_F32, part.p, arena, rows, 52 * C, st);
+  StreamScratch part(st, "op_cnt");   // partial rows of this call
+  part.reserve((size_t)rows * 52 * C * 4);
+  TRY(part.alloc());
+  TRY(launch_dwln_bwd(d, dxn, g, xin, w, dy, out16, prec16, part.at<float>(0), B, HW, C, st, nplanes, (size_t)pstride));
+  return launch_colsum(BTSBOT_F32, part.at<float>(0), arena, rows, 52 * C, st);
 }
 
 extern "C" int btsbot_op_cnt_dw3ln_bwd(const float* dwb, const float* dxn, const float* g, const float* xin, const float* w,
@@ -97,14 +77,15 @@ extern "C" int btsbot_op_cnt_dw3ln_bwd(const float* dwb, const float* dxn, const
     btsbot_set_error("op_cnt_dw3ln_bwd: no kernel for a %dx%d map of %d channels (3x3 maps of 256)", HW, HW, C);
     return BTSBOT_ERR_INVALID_ARG;
   }
-  CNT_TRY(cnt_planes("op_cnt_dw3ln_bwd", B, 9, C, nplanes, pstride));
+  TRY(cnt_planes("op_cnt_dw3ln_bwd", B, 9, C, nplanes, pstride));
   if (B == 0) return BTSBOT_OK;
   hipStream_t st = (hipStream_t)stream;
   const int rows = dw3_rows(B);
-  CntScratch part(st);
-  CNT_TRY(part.alloc((size_t)rows * 28 * C));   // compact rows: 25 live taps | bias | LayerNorm weight | bias, per channel
-  CNT_TRY(launch_dw3ln_bwd(dwb, dxn, g, xin, w, dy, out16, prec16, part.p, B, st, nplanes, (size_t)pstride));
-  return launch_dw3_rows(part.p, arena, rows, st);
+  StreamScratch part(st, "op_cnt");   // partial rows of this call
+  part.reserve((size_t)rows * 28 * C * 4);
+  TRY(part.alloc());   // compact rows: 25 live taps | bias | LayerNorm weight | bias, per channel
+  TRY(launch_dw3ln_bwd(dwb, dxn, g, xin, w, dy, out16, prec16, part.at<float>(0), B, st, nplanes, (size_t)pstride));
+  return launch_dw3_rows(part.at<float>(0), arena, rows, st);
 }
 
 extern "C" int btsbot_op_cnt_ln_bwd(const float* d, const float* dxn, const float* g, float* dd, float* dg, float* dbeta,
@@ -141,21 +122,22 @@ extern "C" int btsbot_op_cnt_dw_plain(const float* x, const float* w, int flip, 
   if (x == nullptr || w == nullptr || out == nullptr) return cnt_bad("op_cnt_dw_plain", "null pointer");
   if (!out16_ok(out16, prec16)) return cnt_bad("op_cnt_dw_plain", "out16 needs prec16 = BTSBOT_BF16 or BTSBOT_F16");
   if (flip != 0 && flip != 1) return cnt_bad("op_cnt_dw_plain", "flip is 0 or 1");
-  CNT_TRY(cnt_dw_shape("op_cnt_dw_plain", B, HW, C, ((size_t)HW * HW + 49) * (size_t)(C > 0 ? C : 0) * sizeof(float)));
+  TRY(cnt_dw_shape("op_cnt_dw_plain", B, HW, C, ((size_t)HW * HW + 49) * (size_t)(C > 0 ? C : 0) * sizeof(float)));
   return launch_dw_plain(x, w, flip, bias, addend, out, B, HW, C, (hipStream_t)stream, out16, prec16);
 }
 
 extern "C" int btsbot_op_cnt_dw_wgrad(const float* x, const float* dd, float* dw, float* dbias, int B, int HW, int C,
                                       void* stream) {
   if (x == nullptr || dd == nullptr || dw == nullptr || dbias == nullptr) return cnt_bad("op_cnt_dw_wgrad", "null pointer");
-  CNT_TRY(cnt_dw_shape("op_cnt_dw_wgrad", B, HW, C, 2 * (size_t)HW * HW * (size_t)(C > 0 ? C : 0) * sizeof(float)));
+  TRY(cnt_dw_shape("op_cnt_dw_wgrad", B, HW, C, 2 * (size_t)HW * HW * (size_t)(C > 0 ? C : 0) * sizeof(float)));
   if (dbias != dw + (size_t)49 * C) return cnt_bad("op_cnt_dw_wgrad", "filter and bias gradients must be adjacent (dbias = dw + 49 C)");
   if (B == 0) return BTSBOT_OK;
   hipStream_t st = (hipStream_t)stream;
   // one partial row [C*49 | C] per workgroup (<= 256) and row group (256 / C of them where C < 256)
-  CntScratch part(st);
-  CNT_TRY(part.alloc((size_t)256 * 50 * (C < 256 ? 256 : C)));
-  return launch_dw_wgrad(x, dd, dw, dbias, part.p, B, HW, C, st);
+  StreamScratch part(st, "op_cnt");   // partial rows of this call
+  part.reserve((size_t)256 * 50 * (C < 256 ? 256 : C) * 4);
+  TRY(part.alloc());
+  return launch_dw_wgrad(x, dd, dw, dbias, part.at<float>(0), B, HW, C, st);
 }
 
 extern "C" int btsbot_op_cnt_colsum_f32(const float* in, float* out, int M, int N, void* stream) {

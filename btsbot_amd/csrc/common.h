@@ -122,6 +122,43 @@ void btsbot_set_error(const char* fmt, ...);
     }                                                                                   \
   } while (0)
 
+// status propagation: a btsbot_status other than BTSBOT_OK ends the calling function (or lambda) with it
+#define TRY(call)                   \
+  do {                              \
+    int _s = (call);                \
+    if (_s != BTSBOT_OK) return _s; \
+  } while (0)
+
+// every carved buffer (workspace, operand images, caches, scratch) starts on a 256-byte boundary
+inline size_t align256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+inline size_t bump(size_t& cur, size_t bytes) {
+  const size_t o = cur;
+  cur += align256(bytes);
+  return o;
+}
+
+// one stream-ordered allocation, carved into 256-byte aligned pieces: offsets are reserved first, alloc() makes the one
+// allocation, and it is released behind the work on the same stream when the object goes out of scope (`who` names the
+// entry point in the error text)
+struct StreamScratch {
+  hipStream_t st;
+  const char* who;
+  unsigned char* base = nullptr;
+  size_t total = 0;
+  StreamScratch(hipStream_t s, const char* w) : st(s), who(w) {}
+  StreamScratch(const StreamScratch&) = delete;
+  ~StreamScratch() {
+    if (base != nullptr) (void)hipFreeAsync(base, st);
+  }
+  size_t reserve(size_t bytes) { return bump(total, bytes); }
+  int alloc() {
+    if (hipMallocAsync(reinterpret_cast<void**>(&base), total ? total : 256, st) == hipSuccess) return BTSBOT_OK;
+    btsbot_set_error("%s: hipMallocAsync of %zu scratch bytes failed", who, total);
+    return BTSBOT_ERR_HIP;
+  }
+  template <typename P = void> P* at(size_t off) const { return reinterpret_cast<P*>(base + off); }
+};
+
 // ---------------------------------------------------------------------------------------
 // device math
 // ---------------------------------------------------------------------------------------

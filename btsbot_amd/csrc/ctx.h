@@ -1,4 +1,5 @@
-// Internal: the handle behind btsbot_handle (shared by api.hip and head_train.hip).
+// Internal: the handle behind btsbot_handle, and what the files that work on it (api.hip, forward.hip, train_step.hip,
+// streams.hip, exchange.hip, the schedules and packers) call of each other.
 #pragma once
 #include <functional>
 #include <string>
@@ -56,7 +57,7 @@ constexpr size_t PROF_MAX_LAUNCHES = 16384;
 
 // Regions of the developer timestamp buffer (btsbot_debug_stamps; include/btsbot_hip.h lists them): offsets and sizes in
 // uint64 entries.  Phase clocks come from one workgroup of a launch; a per-workgroup region holds [grid][2] start / end
-// wall clocks and is passed only when the launch's grid fits (stamp_wgt in api.hip).
+// wall clocks and is passed only when the launch's grid fits (stamp_wgt in forward.hip).
 constexpr size_t STAMP_TOTAL = 32 + 16384 + 64 + 2048;       // 18528
 constexpr size_t STAMP_S0 = 0, STAMP_S0_N = 16;               // stage 0 phases (stage0b.hip)
 constexpr size_t STAMP_S1 = 16, STAMP_S1_N = 16;              // stage 1 phases (stage1b.hip)
@@ -228,11 +229,43 @@ struct btsbot_ctx {
 
 // Fork / join of the backward's second stream.  side_fork: work queued on *sd afterwards sees everything queued on
 // `st` so far (*sd = st when the second stream is off); side_join: `st` waits for everything queued on the side.
-int create_side_stream(btsbot_ctx* h, hipStream_t caller);   // api.hip: h->side, on another hardware queue than `caller`
-// api.hip: a new stream measured to run beside every stream of busy[] (else the last candidate, *apart = false + a warning)
+int create_side_stream(btsbot_ctx* h, hipStream_t caller);   // streams.hip: h->side, on another hardware queue than `caller`
+// streams.hip: a new stream measured to run beside every stream of busy[] (else the last candidate, *apart = false + a warning)
 int pick_apart_stream(btsbot_ctx* h, const hipStream_t* busy, int nbusy, const char* role, hipStream_t* out, bool* apart);
 int side_fork(btsbot_ctx* h, hipStream_t st, hipStream_t* sd);
 int side_join(btsbot_ctx* h, hipStream_t st);
+
+// run one launch, bracketed by HIP events on `st` when profiling is on
+template <typename F> static int timed(btsbot_ctx* h, int cat, hipStream_t st, F&& fn) {
+  const bool rec = h->prof_on && h->prof_used < PROF_MAX_LAUNCHES;
+  if (rec) HIP_TRY(hipEventRecord(h->prof_ev[2 * h->prof_used], st));
+  const int s = fn();
+  if (s != BTSBOT_OK) return s;
+  if (rec) {
+    HIP_TRY(hipEventRecord(h->prof_ev[2 * h->prof_used + 1], st));
+    h->prof_cat[h->prof_used++] = cat;
+  }
+  return BTSBOT_OK;
+}
+
+// forward.hip: image branch of one chunk; *feat_out = [nb][dims[3]] fp32 features inside the workspace
+int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float** feat_out);
+
+// the training step's halves (backbone_train.hip, head_train.hip), called by train_step.hip
+size_t train_cache_floats(const btsbot_ctx* h, int M);
+size_t bb_cache_bytes(const btsbot_ctx* h, int B);
+int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t st, float** feat_out);
+int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat, float* grads,
+                            int B, hipStream_t st);
+float* train_cache_feat(btsbot_ctx* h, float* cache, int M);
+int head_train_forward(btsbot_ctx* h, float* cache, const float* meta, float* logits,
+                       float* scores, int M, const uint8_t* meta_mask, const uint8_t* comb_mask,
+                       float* master, hipStream_t st, bool meta_done = false);
+int head_train_meta_forward(btsbot_ctx* h, float* cache, const float* meta, int M, const uint8_t* meta_mask, float* master,
+                            hipStream_t st);
+int head_train_backward(btsbot_ctx* h, float* cache, const float* dlogits, float* grads, int M,
+                        int need_meta, int need_image, float** dfeat_out,
+                        const uint8_t* meta_mask, const uint8_t* comb_mask, hipStream_t st);
 
 // h->extra + slot for a reader or a packer.  An image the layout never reserved ends the calling function (or lambda)
 // with BTSBOT_ERR_STATE and its name, in front of the launch it was meant for.
@@ -246,12 +279,6 @@ int side_join(btsbot_ctx* h, hipStream_t st);
     img_;                                                                                       \
   })
 #define IMG_F32(h, slot) reinterpret_cast<const float*>(IMG(h, slot))
-
-inline size_t bump(size_t& cur, size_t bytes) {
-  const size_t o = cur;
-  cur += (bytes + 255) / 256 * 256;
-  return o;
-}
 
 // pack.hip
 int pack_layout(btsbot_ctx* h);       // lists the images, reserves their slots behind extra_fixed, sets extra_bytes

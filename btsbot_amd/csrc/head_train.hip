@@ -14,12 +14,6 @@
 
 #include "ctx.h"
 
-#define TRY_RET(call)               \
-  do {                              \
-    int _s = (call);                \
-    if (_s != BTSBOT_OK) return _s; \
-  } while (0)
-
 namespace {
 
 constexpr float BN_EPS = 1e-5f, BN_MOM = 0.1f, HN_EPS = 1e-6f;
@@ -455,7 +449,7 @@ int head_train_forward(btsbot_ctx* h, float* cache, const float* meta, float* lo
                        p.z, zd, M);
     LAUNCH_CHECK();
   }
-  if (h->has_meta && !meta_done) TRY_RET(head_train_meta_forward(h, cache, meta, M, meta_mask, master, st));
+  if (h->has_meta && !meta_done) TRY(head_train_meta_forward(h, cache, meta, M, meta_mask, master, st));
   const float* in = p.z;
   int ldi = zd;
   const float ksc = c.comb_dropout < 1.f ? 1.f / (1.f - c.comb_dropout) : 0.f;
@@ -465,7 +459,7 @@ int head_train_forward(btsbot_ctx* h, float* cache, const float* meta, float* lo
     // Dropout sits after the activation of the layer BEFORE the final Linear (architectures.py:162)
     const bool drop = !last && i + 2 == h->n_comb && c.comb_dropout > 0.f;
     if (wide_layer(M, N, K, ldi)) {
-      TRY_RET(launch_gemm(BTSBOT_F32, EPI_BIAS, in, m + h->comb_w[i], m + h->comb_b[i], nullptr, nullptr, p.pre[i], M, N,
+      TRY(launch_gemm(BTSBOT_F32, EPI_BIAS, in, m + h->comb_w[i], m + h->comb_b[i], nullptr, nullptr, p.pre[i], M, N,
                           K, st));
       hipLaunchKernelGGL(act_fwd_kernel, g1((long)M * N), dim3(256), 0, st, p.pre[i], p.actv[i], N, M, N,
                          last ? ACT_NONE : h->act, drop ? comb_mask : nullptr, ksc);
@@ -507,7 +501,7 @@ int head_train_backward(btsbot_ctx* h, float* cache, const float* dlogits, float
     if (i == 0 && !want_dz) break;
     float* din = p.dbuf[i];
     if (wide_layer(M, K, N, N)) {   // din[m][k] = sum_n dout[m][n] Wt[k][n]
-      TRY_RET(launch_gemm(BTSBOT_F32, EPI_PLAIN, dout[i], IMG(h, h->p_comb[i]), nullptr, nullptr, nullptr, din, M, K,
+      TRY(launch_gemm(BTSBOT_F32, EPI_PLAIN, dout[i], IMG(h, h->p_comb[i]), nullptr, nullptr, nullptr, din, M, K,
                           N, st));
     } else {
       hipLaunchKernelGGL(lin_bwd_in_kernel, g1((long)M * K), dim3(256), 0, st, dout[i], m + h->comb_w[i],
@@ -533,10 +527,10 @@ int head_train_backward(btsbot_ctx* h, float* cache, const float* dlogits, float
     LAUNCH_CHECK();
   }
   hipStream_t sd = st;
-  TRY_RET(side_fork(h, st, &sd));
+  TRY(side_fork(h, st, &sd));
   if (need_image && h->has_image) {
     if (h->hn_w >= 0)   // undo the head LayerNorm
-      TRY_RET(launch_ln_bwd(p.feat, dfeat, m + h->hn_w, dfeat, grads + h->hn_w, grads + h->hn_b, M,
+      TRY(launch_ln_bwd(p.feat, dfeat, m + h->hn_w, dfeat, grads + h->hn_w, grads + h->hn_b, M,
                             F, st));
     *dfeat_out = dfeat;
   }
@@ -544,7 +538,7 @@ int head_train_backward(btsbot_ctx* h, float* cache, const float* dlogits, float
     const int N = h->comb_dims[i + 1], K = h->comb_dims[i];
     const float* in = i == 0 ? p.z : p.actv[i - 1];
     const int ldi = i == 0 ? zd : K;
-    TRY_RET(launch_lin_bwd_w(dout[i], in, ldi, grads + h->comb_w[i], grads + h->comb_b[i], M, N, K, sd));
+    TRY(launch_lin_bwd_w(dout[i], in, ldi, grads + h->comb_w[i], grads + h->comb_b[i], M, N, K, sd));
   }
   if (need_meta && h->has_meta) {
     // the metadata features are columns F .. F+f2 of d(z) [M][zd]
@@ -554,7 +548,7 @@ int head_train_backward(btsbot_ctx* h, float* cache, const float* dlogits, float
                        p.a2, da2, M, c.meta_fc2, h->meta_trailing_act ? h->act : ACT_NONE, nullptr,
                        1.f);
     LAUNCH_CHECK();
-    TRY_RET(launch_lin_bwd_w(da2, p.h1, c.meta_fc1, grads + h->m2_w, grads + h->m2_b, M, c.meta_fc2, c.meta_fc1, sd));
+    TRY(launch_lin_bwd_w(da2, p.h1, c.meta_fc1, grads + h->m2_w, grads + h->m2_b, M, c.meta_fc2, c.meta_fc1, sd));
     float* dh1 = const_cast<float*>(dz);     // d(z) is dead once da2 exists
     hipLaunchKernelGGL(lin_bwd_in_kernel, g1((long)M * c.meta_fc1), dim3(256), 0, sd, da2,
                        m + h->m2_w, dh1, c.meta_fc1, M, c.meta_fc2, c.meta_fc1);
@@ -563,7 +557,7 @@ int head_train_backward(btsbot_ctx* h, float* cache, const float* dlogits, float
                        p.a1, dh1, M, c.meta_fc1, h->act, c.meta_dropout > 0.f ? meta_mask : nullptr,
                        ks1);
     LAUNCH_CHECK();
-    TRY_RET(launch_lin_bwd_w(dh1, p.x1, c.n_meta, grads + h->m1_w, grads + h->m1_b, M, c.meta_fc1, c.n_meta, sd));
+    TRY(launch_lin_bwd_w(dh1, p.x1, c.n_meta, grads + h->m1_w, grads + h->m1_b, M, c.meta_fc1, c.n_meta, sd));
     hipLaunchKernelGGL(lin_bwd_in_kernel, g1((long)M * c.n_meta), dim3(256), 0, sd, dh1,
                        m + h->m1_w, da2, c.n_meta, M, c.meta_fc1, c.n_meta);
     LAUNCH_CHECK();

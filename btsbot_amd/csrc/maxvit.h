@@ -6,7 +6,7 @@
 
 struct btsbot_ctx;
 
-// ---- schedule (maxvit.hip), called from api.hip
+// ---- schedule (maxvit.hip), called from api.hip (tables, workspace, free), pack.hip and forward.hip (maxvit_chunk)
 int maxvit_build_tables(btsbot_ctx* h, size_t* extra_cursor);            // parameter table + operand images
 int maxvit_pack(btsbot_ctx* h, hipStream_t st);                          // mirror -> operand images
 size_t maxvit_ws_bytes(const btsbot_ctx* h, int chunk);

@@ -54,20 +54,14 @@ int64_t mv_add(btsbot_ctx* h, const std::string& name, std::initializer_list<int
   return r.off;
 }
 
-size_t mv_bump(size_t& cur, size_t bytes) {
-  const size_t o = cur;
-  cur += (bytes + 255) / 256 * 256;
-  return o;
-}
-
 BnPk add_bn(btsbot_ctx* h, const std::string& p, int n, size_t& cur) {
   BnPk b;
   b.w = mv_add(h, p + "weight", {n});
   b.b = mv_add(h, p + "bias", {n});
   b.rm = mv_add(h, p + "running_mean", {n}, 1);
   b.rv = mv_add(h, p + "running_var", {n}, 1);
-  b.p_scale = mv_bump(cur, (size_t)n * 4);
-  b.p_shift = mv_bump(cur, (size_t)n * 4);
+  b.p_scale = bump(cur, (size_t)n * 4);
+  b.p_shift = bump(cur, (size_t)n * 4);
   return b;
 }
 
@@ -87,24 +81,24 @@ AttnPk add_attn(btsbot_ctx* h, const std::string& p, int c, size_t& cur, int esz
   a.fc1_b = mv_add(h, p + "mlp.fc1.bias", {4 * c});
   a.fc2_w = mv_add(h, p + "mlp.fc2.weight", {c, 4 * c});
   a.fc2_b = mv_add(h, p + "mlp.fc2.bias", {c});
-  a.p_qkv = mv_bump(cur, (size_t)3 * c * c * esz);
-  a.p_proj = mv_bump(cur, (size_t)c * c * esz);
-  a.p_fc1 = mv_bump(cur, (size_t)4 * c * c * esz);
-  a.p_fc2 = mv_bump(cur, (size_t)4 * c * c * esz);
-  a.p_bias = mv_bump(cur, (size_t)heads * 2401 * 4);
-  a.p_bias64 = mv_bump(cur, (size_t)heads * 4096 * 4);
+  a.p_qkv = bump(cur, (size_t)3 * c * c * esz);
+  a.p_proj = bump(cur, (size_t)c * c * esz);
+  a.p_fc1 = bump(cur, (size_t)4 * c * c * esz);
+  a.p_fc2 = bump(cur, (size_t)4 * c * c * esz);
+  a.p_bias = bump(cur, (size_t)heads * 2401 * 4);
+  a.p_bias64 = bump(cur, (size_t)heads * 4096 * 4);
   a.fused = fused_mlp_supported(h->cfg.precision, c);
-  a.p_fused = a.fused ? mv_bump(cur, fused_mlp_packed_bytes(c)) : 0;
+  a.p_fused = a.fused ? bump(cur, fused_mlp_packed_bytes(c)) : 0;
   a.smlp = !a.fused && stage2p_rows_supported(h->cfg.precision, c);
   a.part = mv_part_supported(h->cfg.precision, c);
   if (a.smlp || a.part) {
-    a.p_w1p = mv_bump(cur, (size_t)4 * c * c * esz);
-    a.p_w2p = mv_bump(cur, (size_t)4 * c * c * esz);
+    a.p_w1p = bump(cur, (size_t)4 * c * c * esz);
+    a.p_w2p = bump(cur, (size_t)4 * c * c * esz);
   }
   if (a.part) {
-    a.p_qkvp = mv_bump(cur, (size_t)3 * c * c * esz);
-    a.p_projp = mv_bump(cur, (size_t)c * c * esz);
-    a.p_biasl = mv_bump(cur, (size_t)heads * 4096 * 4);
+    a.p_qkvp = bump(cur, (size_t)3 * c * c * esz);
+    a.p_projp = bump(cur, (size_t)c * c * esz);
+    a.p_biasl = bump(cur, (size_t)heads * 4096 * 4);
   }
   return a;
 }
@@ -120,12 +114,12 @@ int maxvit_build_tables(btsbot_ctx* h, size_t* extra_cursor) {
   mv->stem1_w = mv_add(h, "stem.conv1.weight", {32, 3, 3, 3});
   mv->stem_bn = add_bn(h, "stem.norm1.", 32, cur);
   mv->stem2_w = mv_add(h, "stem.conv2.weight", {64, 32, 3, 3});
-  mv->p_stem1 = mv_bump(cur, (size_t)32 * 32 * esz);
-  mv->p_stem2 = mv_bump(cur, (size_t)64 * 288 * esz);
-  mv->p_zero = mv_bump(cur, 2048 * 4);
-  mv->p_one = mv_bump(cur, 2048 * 4);
+  mv->p_stem1 = bump(cur, (size_t)32 * 32 * esz);
+  mv->p_stem2 = bump(cur, (size_t)64 * 288 * esz);
+  mv->p_zero = bump(cur, 2048 * 4);
+  mv->p_one = bump(cur, 2048 * 4);
   mv->x2 = h->x2;
-  if (mv->x2) mv->p_x2_tmp = mv_bump(cur, (size_t)64 * 288 * 4);
+  if (mv->x2) mv->p_x2_tmp = bump(cur, (size_t)64 * 288 * 4);
   int cin = 64, hw = 112;
   for (int i = 0; i < 4; ++i) {
     for (int j = 0; j < MV_DEPTHS[i]; ++j) {
@@ -141,7 +135,7 @@ int maxvit_build_tables(btsbot_ctx* h, size_t* extra_cursor) {
       const std::string bp(buf), p = bp + "conv.";
       if (b.stride == 2 && b.cin != b.c) {
         b.sc_w = mv_add(h, p + "shortcut.expand.weight", {b.c, b.cin, 1, 1});
-        b.p_sc = mv_bump(cur, (size_t)b.c * b.cin * esz);
+        b.p_sc = bump(cur, (size_t)b.c * b.cin * esz);
       } else {
         b.p_sc = 0;
       }
@@ -157,12 +151,12 @@ int maxvit_build_tables(btsbot_ctx* h, size_t* extra_cursor) {
       b.se2_w = mv_add(h, p + "se.fc2.weight", {b.mid, b.rd, 1, 1});
       b.se2_b = mv_add(h, p + "se.fc2.bias", {b.mid});
       b.c3_w = mv_add(h, p + "conv3_1x1.weight", {b.c, b.mid, 1, 1});
-      b.p_c1 = mv_bump(cur, (size_t)b.mid * b.cin * esz);
-      b.p_c1b = mv_bump(cur, (size_t)b.mid * 4);
-      b.p_dw = mv_bump(cur, (size_t)9 * b.mid * 4);
-      b.p_dwb = mv_bump(cur, (size_t)b.mid * 4);
-      b.p_c3 = mv_bump(cur, (size_t)b.c * b.mid * esz);
-      b.p_se2t = mv_bump(cur, (size_t)b.mid * b.rd * 4);
+      b.p_c1 = bump(cur, (size_t)b.mid * b.cin * esz);
+      b.p_c1b = bump(cur, (size_t)b.mid * 4);
+      b.p_dw = bump(cur, (size_t)9 * b.mid * 4);
+      b.p_dwb = bump(cur, (size_t)b.mid * 4);
+      b.p_c3 = bump(cur, (size_t)b.c * b.mid * esz);
+      b.p_se2t = bump(cur, (size_t)b.mid * b.rd * 4);
       b.attn[0] = add_attn(h, bp + "attn_block.", b.c, cur, esz);
       b.attn[1] = add_attn(h, bp + "attn_grid.", b.c, cur, esz);
       mv->blocks.push_back(b);
@@ -181,12 +175,6 @@ void maxvit_free(btsbot_ctx* h) {
   h->mv = nullptr;
 }
 
-#define MTRY(call)                  \
-  do {                              \
-    int _s = (call);                \
-    if (_s != BTSBOT_OK) return _s; \
-  } while (0)
-
 static int fold_bn(btsbot_ctx* h, const BnPk& b, int n, hipStream_t st) {
   const float* m = h->mirror;
   return launch_bn_fold(m + b.w, m + b.b, m + b.rm, m + b.rv,
@@ -199,8 +187,8 @@ static int fold_bn(btsbot_ctx* h, const BnPk& b, int n, hipStream_t st) {
 static int mv_pack_filter(const MaxVit* mv, int prec, const float* in, const float* rowscale, void* out, int rows,
                           int cols, hipStream_t st) {
   if (mv->x2) {
-    if (rowscale != nullptr) MTRY(launch_rowscale_cast(BTSBOT_F16, in, rowscale, out, rows, cols, st));
-    else MTRY(launch_cast(BTSBOT_F16, in, out, (int64_t)rows * cols, st));
+    if (rowscale != nullptr) TRY(launch_rowscale_cast(BTSBOT_F16, in, rowscale, out, rows, cols, st));
+    else TRY(launch_cast(BTSBOT_F16, in, out, (int64_t)rows * cols, st));
     return launch_rowscale_cast_lo(in, rowscale, reinterpret_cast<f16_t*>(out) + (size_t)rows * cols, rows, cols, st);
   }
   if (rowscale != nullptr) return launch_rowscale_cast(prec, in, rowscale, out, rows, cols, st);
@@ -213,48 +201,48 @@ int maxvit_pack(btsbot_ctx* h, hipStream_t st) {
   const float* m = h->mirror;
   unsigned char* ex = h->extra;
   auto F = [&](size_t off) { return reinterpret_cast<float*>(ex + off); };
-  MTRY(fold_bn(h, mv->stem_bn, 32, st));
+  TRY(fold_bn(h, mv->stem_bn, 32, st));
   if (mv->x2) {   // the stem images in fp32 first (BatchNorm folded, im2col order), then split
     float* tmp = F(mv->p_x2_tmp);
-    MTRY(launch_mv_pack_stem1(BTSBOT_F32, m + mv->stem1_w, F(mv->stem_bn.p_scale), tmp, st));
-    MTRY(mv_pack_filter(mv, prec, tmp, nullptr, ex + mv->p_stem1, 32, 32, st));
-    MTRY(launch_mv_pack_conv3(BTSBOT_F32, m + mv->stem2_w, tmp, 64, 32, st));
-    MTRY(mv_pack_filter(mv, prec, tmp, nullptr, ex + mv->p_stem2, 64, 288, st));
+    TRY(launch_mv_pack_stem1(BTSBOT_F32, m + mv->stem1_w, F(mv->stem_bn.p_scale), tmp, st));
+    TRY(mv_pack_filter(mv, prec, tmp, nullptr, ex + mv->p_stem1, 32, 32, st));
+    TRY(launch_mv_pack_conv3(BTSBOT_F32, m + mv->stem2_w, tmp, 64, 32, st));
+    TRY(mv_pack_filter(mv, prec, tmp, nullptr, ex + mv->p_stem2, 64, 288, st));
   } else {
-    MTRY(launch_mv_pack_stem1(prec, m + mv->stem1_w, F(mv->stem_bn.p_scale), ex + mv->p_stem1, st));
-    MTRY(launch_mv_pack_conv3(prec, m + mv->stem2_w, ex + mv->p_stem2, 64, 32, st));
+    TRY(launch_mv_pack_stem1(prec, m + mv->stem1_w, F(mv->stem_bn.p_scale), ex + mv->p_stem1, st));
+    TRY(launch_mv_pack_conv3(prec, m + mv->stem2_w, ex + mv->p_stem2, 64, 32, st));
   }
-  MTRY(launch_mv_fill(F(mv->p_zero), 0.f, 2048, st));
-  MTRY(launch_mv_fill(F(mv->p_one), 1.f, 2048, st));
+  TRY(launch_mv_fill(F(mv->p_zero), 0.f, 2048, st));
+  TRY(launch_mv_fill(F(mv->p_one), 1.f, 2048, st));
   for (const MvBlock& b : mv->blocks) {
-    if (b.sc_w >= 0) MTRY(mv_pack_filter(mv, prec, m + b.sc_w, nullptr, ex + b.p_sc, b.c, b.cin, st));
-    MTRY(fold_bn(h, b.pre, b.cin, st));
-    MTRY(fold_bn(h, b.n1, b.mid, st));
-    MTRY(fold_bn(h, b.n2, b.mid, st));
+    if (b.sc_w >= 0) TRY(mv_pack_filter(mv, prec, m + b.sc_w, nullptr, ex + b.p_sc, b.c, b.cin, st));
+    TRY(fold_bn(h, b.pre, b.cin, st));
+    TRY(fold_bn(h, b.n1, b.mid, st));
+    TRY(fold_bn(h, b.n2, b.mid, st));
     // conv1_1x1 followed by BN1: W' = diag(s1) W, b' = b s1 + t1
-    MTRY(mv_pack_filter(mv, prec, m + b.c1_w, F(b.n1.p_scale), ex + b.p_c1, b.mid, b.cin, st));
-    MTRY(launch_mv_fold_bias(m + b.c1_b, F(b.n1.p_scale), F(b.n1.p_shift), F(b.p_c1b), b.mid, st));
-    MTRY(launch_mv_pack_dw(m + b.c2_w, F(b.n2.p_scale), F(b.p_dw), b.mid, st));
-    MTRY(launch_mv_fold_bias(m + b.c2_b, F(b.n2.p_scale), F(b.n2.p_shift), F(b.p_dwb), b.mid, st));
-    MTRY(mv_pack_filter(mv, prec, m + b.c3_w, nullptr, ex + b.p_c3, b.c, b.mid, st));
-    MTRY(launch_transpose_f32(m + b.se2_w, F(b.p_se2t), b.mid, b.rd, st));
+    TRY(mv_pack_filter(mv, prec, m + b.c1_w, F(b.n1.p_scale), ex + b.p_c1, b.mid, b.cin, st));
+    TRY(launch_mv_fold_bias(m + b.c1_b, F(b.n1.p_scale), F(b.n1.p_shift), F(b.p_c1b), b.mid, st));
+    TRY(launch_mv_pack_dw(m + b.c2_w, F(b.n2.p_scale), F(b.p_dw), b.mid, st));
+    TRY(launch_mv_fold_bias(m + b.c2_b, F(b.n2.p_scale), F(b.n2.p_shift), F(b.p_dwb), b.mid, st));
+    TRY(mv_pack_filter(mv, prec, m + b.c3_w, nullptr, ex + b.p_c3, b.c, b.mid, st));
+    TRY(launch_transpose_f32(m + b.se2_w, F(b.p_se2t), b.mid, b.rd, st));
     for (const AttnPk& a : b.attn) {
       const int c = b.c;
-      MTRY(mv_pack_filter(mv, prec, m + a.qkv_w, nullptr, ex + a.p_qkv, 3 * c, c, st));
-      MTRY(mv_pack_filter(mv, prec, m + a.proj_w, nullptr, ex + a.p_proj, c, c, st));
-      MTRY(mv_pack_filter(mv, prec, m + a.fc1_w, nullptr, ex + a.p_fc1, 4 * c, c, st));
-      MTRY(mv_pack_filter(mv, prec, m + a.fc2_w, nullptr, ex + a.p_fc2, c, 4 * c, st));
-      MTRY(launch_mv_pack_relbias(m + a.rel, F(a.p_bias), c / 32, st));
-      MTRY(launch_mv_pack_relbias64(m + a.rel, F(a.p_bias64), c / 32, st));
-      if (a.fused) MTRY(launch_pack_fused_mlp(prec, c, m + a.fc1_w, m + a.fc2_w, ex + a.p_fused, st));
+      TRY(mv_pack_filter(mv, prec, m + a.qkv_w, nullptr, ex + a.p_qkv, 3 * c, c, st));
+      TRY(mv_pack_filter(mv, prec, m + a.proj_w, nullptr, ex + a.p_proj, c, c, st));
+      TRY(mv_pack_filter(mv, prec, m + a.fc1_w, nullptr, ex + a.p_fc1, 4 * c, c, st));
+      TRY(mv_pack_filter(mv, prec, m + a.fc2_w, nullptr, ex + a.p_fc2, c, 4 * c, st));
+      TRY(launch_mv_pack_relbias(m + a.rel, F(a.p_bias), c / 32, st));
+      TRY(launch_mv_pack_relbias64(m + a.rel, F(a.p_bias64), c / 32, st));
+      if (a.fused) TRY(launch_pack_fused_mlp(prec, c, m + a.fc1_w, m + a.fc2_w, ex + a.p_fused, st));
       if (a.part) {
-        MTRY(launch_pack_s2p(prec, m + a.qkv_w, nullptr, ex + a.p_qkvp, 3 * c, c, 0, 0, nullptr, st));
-        MTRY(launch_pack_s2p(prec, m + a.proj_w, nullptr, ex + a.p_projp, c, c, 0, 0, nullptr, st));
-        MTRY(launch_mv_pack_relbias_lanes(m + a.rel, F(a.p_biasl), c / 32, st));
+        TRY(launch_pack_s2p(prec, m + a.qkv_w, nullptr, ex + a.p_qkvp, 3 * c, c, 0, 0, nullptr, st));
+        TRY(launch_pack_s2p(prec, m + a.proj_w, nullptr, ex + a.p_projp, c, c, 0, 0, nullptr, st));
+        TRY(launch_mv_pack_relbias_lanes(m + a.rel, F(a.p_biasl), c / 32, st));
       }
       if (a.smlp || a.part) {
-        MTRY(launch_pack_s2p(prec, m + a.fc1_w, nullptr, ex + a.p_w1p, 4 * c, c, 0, 0, nullptr, st));
-        MTRY(launch_pack_s2p(prec, m + a.fc2_w, nullptr, ex + a.p_w2p, c, 4 * c, 0, 0, nullptr, st));
+        TRY(launch_pack_s2p(prec, m + a.fc1_w, nullptr, ex + a.p_w1p, 4 * c, c, 0, 0, nullptr, st));
+        TRY(launch_pack_s2p(prec, m + a.fc2_w, nullptr, ex + a.p_w2p, c, 4 * c, 0, 0, nullptr, st));
       }
     }
   }
@@ -265,11 +253,7 @@ int maxvit_pack(btsbot_ctx* h, hipStream_t st) {
 static void mv_layout(const btsbot_ctx* h, int chunk, MaxVit* out, size_t* total) {
   const size_t esz = (size_t)h->esz(), n = (size_t)chunk;
   size_t cur = 0;
-  auto bump = [&](size_t bytes) {
-    const size_t o = cur;
-    cur += (bytes + 255) / 256 * 256;
-    return o;
-  };
+  auto bump = [&](size_t bytes) { return ::bump(cur, bytes); };
   MaxVit tmp;
   MaxVit* o = out ? out : &tmp;
   o->o_x = bump(n * 12544 * 64 * 4);       // fp32 residual map (stem output is the largest)
@@ -302,18 +286,6 @@ static int mv_gemm(const btsbot_ctx* h, int prec, int epi, const void* X, const 
   return launch_gemm(prec, epi, X, W, bias, gamma, resid, out, M, N, K, st);
 }
 
-template <typename F> static int mv_timed(btsbot_ctx* h, int cat, hipStream_t st, F&& fn) {
-  const bool rec = h->prof_on && h->prof_used < PROF_MAX_LAUNCHES;
-  if (rec) HIP_TRY(hipEventRecord(h->prof_ev[2 * h->prof_used], st));
-  const int s = fn();
-  if (s != BTSBOT_OK) return s;
-  if (rec) {
-    HIP_TRY(hipEventRecord(h->prof_ev[2 * h->prof_used + 1], st));
-    h->prof_cat[h->prof_used++] = cat;
-  }
-  return BTSBOT_OK;
-}
-
 int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float** feat_out) {
   MaxVit* mv = h->mv;
   const Schedule& sc = h->sched;
@@ -342,12 +314,12 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
   // ---- stem: resize + conv3x3 s2 (+BN, SiLU) + conv3x3 s1, both as im2col GEMMs
   const int M0 = nb * 12544;
   if (prec != BTSBOT_F32 && !sc.mv_stem_im2col) {
-    MTRY(mv_timed(h, CAT_MV_STEM, st, [&] {
+    TRY(timed(h, CAT_MV_STEM, st, [&] {
       return launch_mv_stem1(prec, img, ex + mv->p_stem1, F(mv->stem_bn.p_shift), Cc, nb, st);
     }));
   } else {
-    MTRY(mv_timed(h, CAT_MV_STEM, st, [&] { return launch_mv_resize_im2col(prec, img, Bb, nb, st); }));
-    MTRY(mv_timed(h, CAT_MV_G_STEM, st, [&] {
+    TRY(timed(h, CAT_MV_STEM, st, [&] { return launch_mv_resize_im2col(prec, img, Bb, nb, st); }));
+    TRY(timed(h, CAT_MV_G_STEM, st, [&] {
       return mv_gemm(h, prec, EPI_SILU, Bb, ex + mv->p_stem1, F(mv->stem_bn.p_shift), nullptr, nullptr,
                      Cc, M0, 32, 32, st);
     }));
@@ -358,14 +330,14 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
     // (without debug taps nobody needs the fp32 stem map itself: block 0's shortcut only wants its 2x2
     //  average pool, which the kernel then writes straight into the residual buffer x2)
     pool_ready = !h->debug && b0.stride == 2 && b0.sc_w < 0;
-    MTRY(mv_timed(h, CAT_MV_G_STEM, st, [&] {
+    TRY(timed(h, CAT_MV_G_STEM, st, [&] {
       return launch_mv_stem2(prec, Cc, ex + mv->p_stem2, pool_ready ? x2 : x, pool_ready ? 1 : 0, Bb,
                              F(b0.pre.p_scale), F(b0.pre.p_shift), nb, st);
     }));
     xn_ready = true;
   } else {
-    MTRY(mv_timed(h, CAT_MV_STEM, st, [&] { return launch_mv_im2col3(prec, Cc, A, nb, 112, 32, st); }));
-    MTRY(mv_timed(h, CAT_MV_G_STEM, st, [&] {
+    TRY(timed(h, CAT_MV_STEM, st, [&] { return launch_mv_im2col3(prec, Cc, A, nb, 112, 32, st); }));
+    TRY(timed(h, CAT_MV_G_STEM, st, [&] {
       return mv_gemm(h, prec, EPI_BIAS, A, ex + mv->p_stem2, zero, nullptr, nullptr, x, M0, 64, 288,
                      st);
     }));
@@ -383,15 +355,15 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
     float* dst = x;
     if (b.stride == 2) {
       if (b.sc_w >= 0) {
-        MTRY(mv_timed(h, CAT_MV_ELT, st, [&] {
+        TRY(timed(h, CAT_MV_ELT, st, [&] {
           return launch_mv_avgpool2(prec, x, E, 1, nb, b.hin, b.cin, st);
         }));
-        MTRY(mv_timed(h, CAT_MV_G_SC, st, [&] {
+        TRY(timed(h, CAT_MV_G_SC, st, [&] {
           return mv_gemm(h, prec, EPI_BIAS, E, ex + b.p_sc, zero, nullptr, nullptr, x2, Mo, b.c,
                              b.cin, st);
         }));
       } else if (!(bi == 0 && pool_ready)) {
-        MTRY(mv_timed(h, CAT_MV_ELT, st, [&] {
+        TRY(timed(h, CAT_MV_ELT, st, [&] {
           return launch_mv_avgpool2(prec, x, x2, 0, nb, b.hin, b.cin, st);
         }));
       }
@@ -404,7 +376,7 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
     } else if (next_xn_ready) {   // the previous block's last MLP already wrote BN_pre(x) into Cc
       next_xn_ready = false;
     } else {
-      MTRY(mv_timed(h, CAT_MV_ELT, st, [&] {
+      TRY(timed(h, CAT_MV_ELT, st, [&] {
         return launch_mv_bn_cast(prec, x, F(b.pre.p_scale), F(b.pre.p_shift), Cc, (long)Min, b.cin, st);
       }));
     }
@@ -414,33 +386,33 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
     if (front) {
       // wide stages: conv1 + depthwise + pool partials in one kernel, the expanded map stays on-chip
       m2b = A;
-      MTRY(mv_timed(h, CAT_MV_FRONT, st, [&] {
+      TRY(timed(h, CAT_MV_FRONT, st, [&] {
         return launch_mv_mbconv_front(prec, c1_in, ex + b.p_c1, F(b.p_c1b), F(b.p_dw), F(b.p_dwb), m2b, part,
                                       nb, b.hin, b.cin, b.mid, b.stride, st);
       }));
-      MTRY(mv_timed(h, CAT_MV_SE, st, [&] {
+      TRY(timed(h, CAT_MV_SE, st, [&] {
         return launch_mv_se(BTSBOT_F32, part, m + b.se1_w, m + b.se1_b, F(b.p_se2t), m + b.se2_b, gate,
                             sescr, nb, mv_mbconv_front_tiles(b.hin, b.stride), b.mid, b.rd, inv_hw, st);
       }));
     } else {
-    MTRY(mv_timed(h, CAT_MV_G_CONV1, st, [&] {
+    TRY(timed(h, CAT_MV_G_CONV1, st, [&] {
       return mv_gemm(h, prec, EPI_SILU, c1_in, ex + b.p_c1, F(b.p_c1b), nullptr, nullptr, A, Min, b.mid,
                          b.cin, st);
     }));
     if (prec != BTSBOT_F32 && !sc.mv_dw_plain) {
       // depthwise conv with the squeeze-excite pool fused (partial sums per workgroup, no second pass)
-      MTRY(mv_timed(h, CAT_MV_DW, st, [&] {
+      TRY(timed(h, CAT_MV_DW, st, [&] {
         return launch_mv_dw3s(prec, A, F(b.p_dw), F(b.p_dwb), Bb, part, nb, b.hin, b.mid, b.stride, st);
       }));
-      MTRY(mv_timed(h, CAT_MV_SE, st, [&] {
+      TRY(timed(h, CAT_MV_SE, st, [&] {
         return launch_mv_se(BTSBOT_F32, part, m + b.se1_w, m + b.se1_b, F(b.p_se2t), m + b.se2_b, gate,
                             sescr, nb, mv_dw3s_groups(b.hin, b.mid, b.stride), b.mid, b.rd, inv_hw, st);
       }));
     } else {
-      MTRY(mv_timed(h, CAT_MV_DW, st, [&] {
+      TRY(timed(h, CAT_MV_DW, st, [&] {
         return launch_mv_dw3(prec, A, F(b.p_dw), F(b.p_dwb), Bb, nb, b.hin, b.mid, b.stride, st);
       }));
-      MTRY(mv_timed(h, CAT_MV_SE, st, [&] {
+      TRY(timed(h, CAT_MV_SE, st, [&] {
         return launch_mv_se(prec, Bb, m + b.se1_w, m + b.se1_b, F(b.p_se2t), m + b.se2_b, gate, sescr, nb,
                             b.hout * b.hout, b.mid, b.rd, inv_hw, st);
       }));
@@ -455,10 +427,10 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
     bool ln1_done = false, ln1_grid_done = false;
     if (prec != BTSBOT_F32 && !sc.mv_gated_gemm && (size_t)b.c * b.mid * 4 <= (size_t)hw2 * b.mid) {
       // wide stages: per-alert filters W3 diag(g_b) (a fraction of the map's size) + batched LDS-DMA GEMM
-      MTRY(mv_timed(h, CAT_MV_SE, st, [&] {
+      TRY(timed(h, CAT_MV_SE, st, [&] {
         return launch_mv_scale_w(prec, m + b.c3_w, gate, wg, nb, b.c, b.mid, st);
       }));
-      MTRY(mv_timed(h, CAT_MV_G_CONV3, st, [&] {
+      TRY(timed(h, CAT_MV_G_CONV3, st, [&] {
         return launch_gemm2_batched_resid(prec, m2b, wg, zero, one, resid, dst, nb, hw2, b.c, b.mid, st,
                                           ln_fuse ? m + b.attn[0].n1w : nullptr,
                                           ln_fuse ? m + b.attn[0].n1b : nullptr, ln_fuse ? Cc : nullptr);
@@ -466,12 +438,12 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
       ln1_done = ln_fuse;
     } else if (prec != BTSBOT_F32 && !sc.mv_gated_gemm) {
       // narrow stages: the map is small -- gate it in place, then the plain LDS-DMA GEMM
-      MTRY(mv_timed(h, CAT_MV_SE, st, [&] { return launch_mv_gate(prec, m2b, gate, nb, hw2, b.mid, st); }));
-      MTRY(mv_timed(h, CAT_MV_G_CONV3, st, [&] {
+      TRY(timed(h, CAT_MV_SE, st, [&] { return launch_mv_gate(prec, m2b, gate, nb, hw2, b.mid, st); }));
+      TRY(timed(h, CAT_MV_G_CONV3, st, [&] {
         return launch_gemm(prec, EPI_RESID, m2b, ex + b.p_c3, zero, one, resid, dst, Mo, b.c, b.mid, st);
       }));
     } else {
-      MTRY(mv_timed(h, CAT_MV_G_CONV3, st, [&] {
+      TRY(timed(h, CAT_MV_G_CONV3, st, [&] {
         if (sc.maxvit_split)
           return launch_gemm_x2_gated(reinterpret_cast<const float*>(m2b), gate, hw2, ex + b.p_c3, resid, dst, Mo, b.c,
                                       b.mid, st);
@@ -511,42 +483,42 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
           pw.post_b = F(mv->blocks[bi + 1].pre.p_shift);
           pw.post_out = Cc;
         }
-        MTRY(mv_timed(h, CAT_MV_PART, st, [&] { return launch_mv_part(prec, x, pw, nb, b.hout, c, g, st); }));
+        TRY(timed(h, CAT_MV_PART, st, [&] { return launch_mv_part(prec, x, pw, nb, b.hout, c, g, st); }));
         if (pw.post_out != nullptr) next_xn_ready = true;
         continue;
       } else {
       if (!(g == 0 && ln1_done) && !(g == 1 && ln1_grid_done)) {
-        MTRY(mv_timed(h, CAT_MV_LN, st, [&] {
+        TRY(timed(h, CAT_MV_LN, st, [&] {
           return launch_mv_ln(prec, x, m + a.n1w, m + a.n1b, Cc, (long)Mo, c, st);
         }));
       }
       if (!sc.mv_no_attn_block && mv_attn_block_supported(prec, c)) {
         // C = 64: qkv, attention, proj, residual and LN2 in one kernel (qkv never reaches HBM)
-        MTRY(mv_timed(h, CAT_MV_ABLK, st, [&] {
+        TRY(timed(h, CAT_MV_ABLK, st, [&] {
           return launch_mv_attn_block(prec, Cc, x, Cc, ex + a.p_qkv, m + a.qkv_b, ex + a.p_proj, m + a.proj_b,
                                       F(a.p_bias64), m + a.n2w, m + a.n2b, nb, b.hout, c, g, st);
         }));
       } else {
-      MTRY(mv_timed(h, CAT_MV_G_QKV, st, [&] {
+      TRY(timed(h, CAT_MV_G_QKV, st, [&] {
         return mv_gemm(h, prec, EPI_BIAS_T, Cc, ex + a.p_qkv, m + a.qkv_b, nullptr, nullptr, D, Mo,
                            3 * c, c, st);
       }));
-      MTRY(mv_timed(h, CAT_MV_ATTN, st, [&] {
+      TRY(timed(h, CAT_MV_ATTN, st, [&] {
         if (prec != BTSBOT_F32 && !sc.mv_attn_valu)
           return launch_mv_attn_mfma(prec, D, F(a.p_bias64), E, nb, b.hout, c, g, st);
         return launch_mv_attn(prec, D, F(a.p_bias), E, nb, b.hout, c, g, st);
       }));
       if (ln_fuse && gemm2_supported(prec, Mo, c, c)) {   // proj + residual + LN2 in one launch
-        MTRY(mv_timed(h, CAT_MV_G_PROJ, st, [&] {
+        TRY(timed(h, CAT_MV_G_PROJ, st, [&] {
           return launch_gemm2_batched_resid(prec, E, ex + a.p_proj, m + a.proj_b, one, x, x, 1, Mo, c, c, st,
                                             m + a.n2w, m + a.n2b, Cc);
         }));
       } else {
-        MTRY(mv_timed(h, CAT_MV_G_PROJ, st, [&] {
+        TRY(timed(h, CAT_MV_G_PROJ, st, [&] {
           return mv_gemm(h, prec, EPI_RESID, E, ex + a.p_proj, m + a.proj_b, one, x, x, Mo, c, c, st);
         }));
         if (!(a.smlp && !sc.mv_no_smlp))   // (the streamed MLP below normalises its rows itself)
-          MTRY(mv_timed(h, CAT_MV_LN, st, [&] {
+          TRY(timed(h, CAT_MV_LN, st, [&] {
             return launch_mv_ln(prec, x, m + a.n2w, m + a.n2b, Cc, (long)Mo, c, st);
           }));
       }
@@ -568,7 +540,7 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
           pb = F(mv->blocks[bi + 1].pre.p_shift);
           post = 2;
         }
-        MTRY(mv_timed(h, CAT_MV_FUSED, st, [&] {
+        TRY(timed(h, CAT_MV_FUSED, st, [&] {
           return launch_fused_mlp(prec, c, Cc, ex + a.p_fused, m + a.fc1_b, m + a.fc2_b, one, x, Mo, st,
                                   post ? Cc : nullptr, pw, pb, post);
         }));
@@ -589,14 +561,14 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
         sb.gamma = one;
         sb.w1p = ex + a.p_w1p;
         sb.w2p = ex + a.p_w2p;
-        MTRY(mv_timed(h, CAT_MV_SMLP, st, [&] { return launch_stage2p_rows(prec, x, (long)Mo, sb, st); }));
+        TRY(timed(h, CAT_MV_SMLP, st, [&] { return launch_stage2p_rows(prec, x, (long)Mo, sb, st); }));
         continue;
       }
-      MTRY(mv_timed(h, CAT_MV_G_FC1, st, [&] {
+      TRY(timed(h, CAT_MV_G_FC1, st, [&] {
         return mv_gemm(h, prec, EPI_GELU, Cc, ex + a.p_fc1, m + a.fc1_b, nullptr, nullptr, Bb, Mo,
                            4 * c, c, st);
       }));
-      MTRY(mv_timed(h, CAT_MV_G_FC2, st, [&] {
+      TRY(timed(h, CAT_MV_G_FC2, st, [&] {
         return mv_gemm(h, prec, EPI_RESID, Bb, ex + a.p_fc2, m + a.fc2_b, one, x, x, Mo, c, 4 * c,
                        st);
       }));
@@ -611,7 +583,7 @@ int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float*
       jblk = 0;
     }
   }
-  MTRY(mv_timed(h, CAT_MV_LN, st, [&] {
+  TRY(timed(h, CAT_MV_LN, st, [&] {
     return launch_mv_final(x, m + mv->norm_w, m + mv->norm_b, feat, nb, 49, 512, st);
   }));
   *feat_out = feat;

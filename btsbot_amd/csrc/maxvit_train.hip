@@ -23,12 +23,6 @@ namespace {
 
 constexpr float BN_EPS = 1e-5f, BN_MOM = 0.1f;
 
-#define VTRY(call)                  \
-  do {                              \
-    int _s = (call);                \
-    if (_s != BTSBOT_OK) return _s; \
-  } while (0)
-
 inline unsigned nblk(long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + __expf(-x)); }
@@ -677,7 +671,7 @@ int launch_attn_bwd(const float* qkv, const float* table, const float* dout, flo
                     int H, int C, int grid_mode, hipStream_t st) {
   const int heads = C / 32;
   HIP_TRY(hipMemsetAsync(dbias, 0, (size_t)heads * 2401 * 4, st));
-  VTRY(launch_mv_pack_relbias(table, dbias + 16 * 2401, heads, st));
+  TRY(launch_mv_pack_relbias(table, dbias + 16 * 2401, heads, st));
   const long units = (long)B * (H / 7) * (H / 7);
   const long per_head = attn_bwd_groups_per_head(units, heads);
   hipLaunchKernelGGL(mv_attn_bwd_kernel, dim3((unsigned)(per_head * heads)), dim3(64), 0, st, qkv, (const float*)(dbias + 16 * 2401),
@@ -710,7 +704,7 @@ int launch_se_bwd(float* d, const float* a2, const float* pool, const float* rpr
                   const float* w1, const float* w2, float* dw1, float* db1, float* dw2, float* db2, float* dgate, float* dr,
                   float* dpool, float* dgpre, int B, int P, int C, int RD, hipStream_t st) {
   hipLaunchKernelGGL(alert_colsum_kernel, dim3((C + 63) / 64, B), dim3(256), 0, st, (const float*)d, a2, dgate, P, C, 1.0f);
-  VTRY(launch_gate_mul(d, gate, d, B, P, C, st));                                   // d(a2) = d(gated) * g, in place
+  TRY(launch_gate_mul(d, gate, d, B, P, C, st));                                   // d(a2) = d(gated) * g, in place
   hipLaunchKernelGGL(act_bwd_small_kernel, dim3(nblk((long)B * C)), dim3(256), 0, st, (const float*)dgate, gate, dgpre, B * C, 2);
   hipLaunchKernelGGL(lin_bwd_w_small_kernel, dim3(nblk((long)C * RD)), dim3(256), 0, st, (const float*)dgpre, r, dw2, db2, B, RD,
                      C);
@@ -795,7 +789,7 @@ MvtCache carve(const MaxVit* mv, unsigned char* base, int B, int64_t nparams = 0
   size_t cur = 0;
   auto take = [&](size_t floats) {
     float* p = base ? reinterpret_cast<float*>(base + cur) : nullptr;
-    cur += (floats * 4 + 255) / 256 * 256;
+    cur += align256(floats * 4);
     return p;
   };
   const size_t n = (size_t)B, M0 = n * 12544;
@@ -922,7 +916,7 @@ int maxvit_train_forward(btsbot_ctx* h, const float* img, int B, float* master, 
   const int prec = h->cfg.precision;
   const bool lowp = prec == BTSBOT_BF16 || prec == BTSBOT_F16;
   // (16-bit modes) every filter of the parameter mirror in the operand type, one launch; the inputs' copies are kept
-  if (lowp) VTRY(launch_cast(prec, m, k.wall16, h->total_floats, st));
+  if (lowp) TRY(launch_cast(prec, m, k.wall16, h->total_floats, st));
   mv->xkept.clear();
   size_t xcur = 0;   // bytes handed out of xkeep
   auto w16_of = [&](const float* W, int64_t n, const void** out) -> int {
@@ -930,24 +924,24 @@ int maxvit_train_forward(btsbot_ctx* h, const float* img, int B, float* master, 
       *out = reinterpret_cast<const unsigned char*>(k.wall16) + (size_t)(W - m) * 2;
       return BTSBOT_OK;
     }
-    VTRY(launch_cast(prec, W, k.w16, n, st));   // (the stem's packed filters live outside the mirror)
+    TRY(launch_cast(prec, W, k.w16, n, st));   // (the stem's packed filters live outside the mirror)
     *out = k.w16;
     return BTSBOT_OK;
   };
   auto x16_of = [&](const float* X, int64_t n, const void** out) -> int {
     if (X == k.dA || X == k.dB || X == k.dC) {   // scratch maps (rewritten before the backward): cast per call, not kept
-      VTRY(launch_cast(prec, X, k.x16, n, st));
+      TRY(launch_cast(prec, X, k.x16, n, st));
       *out = k.x16;
       return BTSBOT_OK;
     }
-    const size_t bytes = ((size_t)n * 2 + 255) / 256 * 256;
+    const size_t bytes = align256((size_t)n * 2);
     if (xcur + bytes > k.xkeep_floats * 4) {
       btsbot_set_error("maxvit_train_forward: the kept-operand arena is too small");
       return BTSBOT_ERR_STATE;
     }
     void* dst = reinterpret_cast<unsigned char*>(k.xkeep) + xcur;
     xcur += bytes;
-    VTRY(launch_cast(prec, X, dst, n, st));
+    TRY(launch_cast(prec, X, dst, n, st));
     mv->xkept.push_back({X, dst});
     *out = dst;
     return BTSBOT_OK;
@@ -955,27 +949,27 @@ int maxvit_train_forward(btsbot_ctx* h, const float* img, int B, float* master, 
   auto gemm = [&](const float* X, const float* W, const float* bias, float* out, long M, int N, int K) -> int {
     if (!lowp) return launch_gemm(BTSBOT_F32, EPI_BIAS, X, W, bias ? bias : zero, nullptr, nullptr, out, (int)M, N, K, st);
     const void *x16, *w16;
-    VTRY(x16_of(X, (int64_t)M * K, &x16));
-    VTRY(w16_of(W, (int64_t)N * K, &w16));
+    TRY(x16_of(X, (int64_t)M * K, &x16));
+    TRY(w16_of(W, (int64_t)N * K, &w16));
     return launch_gemm(prec, EPI_BIAS, x16, w16, bias ? bias : zero, nullptr, nullptr, out, (int)M, N, K, st);
   };
   auto gemm_resid = [&](const float* X, const float* W, const float* bias, const float* resid, float* out, long M, int N,
                         int K) -> int {
     if (!lowp) return launch_gemm(BTSBOT_F32, EPI_RESID, X, W, bias ? bias : zero, one, resid, out, (int)M, N, K, st);
     const void *x16, *w16;
-    VTRY(x16_of(X, (int64_t)M * K, &x16));
-    VTRY(w16_of(W, (int64_t)N * K, &w16));
+    TRY(x16_of(X, (int64_t)M * K, &x16));
+    TRY(w16_of(W, (int64_t)N * K, &w16));
     return launch_gemm(prec, EPI_RESID, x16, w16, bias ? bias : zero, one, resid, out, (int)M, N, K, st);
   };
   const long M0 = (long)B * 12544;
   // ---- stem: resize + conv 3x3 s2 (im2col GEMM) -> BN + SiLU -> conv 3x3 s1
-  VTRY(launch_mv_pack_stem1(BTSBOT_F32, m + mv->stem1_w, one, k.w1p, st));
-  VTRY(launch_mv_pack_conv3(BTSBOT_F32, m + mv->stem2_w, k.w2p, 64, 32, st));
-  VTRY(launch_mv_resize_im2col(BTSBOT_F32, img, k.col1, B, st));
-  VTRY(gemm(k.col1, k.w1p, nullptr, k.y1, M0, 32, 32));
-  VTRY(bn_train(h, k.y1, mv->stem_bn, k.st_stem, sums_arena, k.a1s, M0, 32, 1, master, st));
-  VTRY(launch_mv_im2col3(BTSBOT_F32, k.a1s, k.dC, B, 112, 32, st));
-  VTRY(gemm(k.dC, k.w2p, nullptr, k.x0, M0, 64, 288));
+  TRY(launch_mv_pack_stem1(BTSBOT_F32, m + mv->stem1_w, one, k.w1p, st));
+  TRY(launch_mv_pack_conv3(BTSBOT_F32, m + mv->stem2_w, k.w2p, 64, 32, st));
+  TRY(launch_mv_resize_im2col(BTSBOT_F32, img, k.col1, B, st));
+  TRY(gemm(k.col1, k.w1p, nullptr, k.y1, M0, 32, 32));
+  TRY(bn_train(h, k.y1, mv->stem_bn, k.st_stem, sums_arena, k.a1s, M0, 32, 1, master, st));
+  TRY(launch_mv_im2col3(BTSBOT_F32, k.a1s, k.dC, B, 112, 32, st));
+  TRY(gemm(k.dC, k.w2p, nullptr, k.x0, M0, 64, 288));
   if (h->debug && h->taps[0]) HIP_TRY(hipMemcpyAsync(h->taps[0], k.x0, (size_t)M0 * 64 * 4, hipMemcpyDeviceToDevice, st));
   int stage = 0, jblk = 0;
   constexpr int DEPTHS[4] = {2, 2, 5, 2};
@@ -987,37 +981,37 @@ int maxvit_train_forward(btsbot_ctx* h, const float* img, int B, float* master, 
     // shortcut: x | avgpool2(x) | avgpool2(x) Wsc^T -- goes straight into y, the projection adds to it
     const float* sc = a.xin;
     if (b.stride == 2) {
-      VTRY(launch_mv_avgpool2(BTSBOT_F32, a.xin, a.pool_in, 0, B, b.hin, b.cin, st));
+      TRY(launch_mv_avgpool2(BTSBOT_F32, a.xin, a.pool_in, 0, B, b.hin, b.cin, st));
       sc = a.pool_in;
       if (b.sc_w >= 0) {
-        VTRY(gemm(a.pool_in, m + b.sc_w, nullptr, a.y, Mo, b.c, b.cin));
+        TRY(gemm(a.pool_in, m + b.sc_w, nullptr, a.y, Mo, b.c, b.cin));
         sc = a.y;
       }
     }
-    VTRY(bn_train(h, a.xin, b.pre, a.st_pre, sums_arena, a.a0, Min, b.cin, 0, master, st));
-    VTRY(gemm(a.a0, m + b.c1_w, m + b.c1_b, a.c1, Min, b.mid, b.cin));
-    VTRY(bn_train(h, a.c1, b.n1, a.st1, sums_arena, a.a1, Min, b.mid, 1, master, st));
-    VTRY(launch_mv_pack_dw(m + b.c2_w, one, k.g9, b.mid, st));
-    VTRY(launch_dw3_fwd(a.a1, k.g9, m + b.c2_b, a.d2, B, b.hin, b.mid, b.stride, st));
-    VTRY(bn_train(h, a.d2, b.n2, a.st2, sums_arena, a.a2, Mo, b.mid, 1, master, st));
+    TRY(bn_train(h, a.xin, b.pre, a.st_pre, sums_arena, a.a0, Min, b.cin, 0, master, st));
+    TRY(gemm(a.a0, m + b.c1_w, m + b.c1_b, a.c1, Min, b.mid, b.cin));
+    TRY(bn_train(h, a.c1, b.n1, a.st1, sums_arena, a.a1, Min, b.mid, 1, master, st));
+    TRY(launch_mv_pack_dw(m + b.c2_w, one, k.g9, b.mid, st));
+    TRY(launch_dw3_fwd(a.a1, k.g9, m + b.c2_b, a.d2, B, b.hin, b.mid, b.stride, st));
+    TRY(bn_train(h, a.d2, b.n2, a.st2, sums_arena, a.a2, Mo, b.mid, 1, master, st));
     // squeeze-excite
-    VTRY(launch_se_fwd(a.a2, m + b.se1_w, m + b.se1_b, m + b.se2_w, m + b.se2_b, a.sepool, a.rpre, a.r, a.g, k.dA, B, hw2, b.mid,
+    TRY(launch_se_fwd(a.a2, m + b.se1_w, m + b.se1_b, m + b.se2_w, m + b.se2_b, a.sepool, a.rpre, a.r, a.g, k.dA, B, hw2, b.mid,
                        b.rd, st));
-    VTRY(gemm_resid(k.dA, m + b.c3_w, nullptr, sc, a.y, Mo, b.c, b.mid));
+    TRY(gemm_resid(k.dA, m + b.c3_w, nullptr, sc, a.y, Mo, b.c, b.mid));
     const float* yin = a.y;
     for (int g = 0; g < 2; ++g) {
       const AttnPk& p = b.attn[g];
       AttnAct& t = a.at[g];
       const int c = b.c;
-      VTRY(launch_mv_ln(BTSBOT_F32, yin, m + p.n1w, m + p.n1b, t.n1, Mo, c, st));
-      VTRY(gemm(t.n1, m + p.qkv_w, m + p.qkv_b, t.qkv, Mo, 3 * c, c));
-      VTRY(launch_mv_pack_relbias(m + p.rel, k.dbias, c / 32, st));
-      VTRY(launch_mv_attn(BTSBOT_F32, t.qkv, k.dbias, t.o, B, b.hout, c, g, st));
-      VTRY(gemm_resid(t.o, m + p.proj_w, m + p.proj_b, yin, t.y1, Mo, c, c));
-      VTRY(launch_mv_ln(BTSBOT_F32, t.y1, m + p.n2w, m + p.n2b, t.n2, Mo, c, st));
-      VTRY(gemm(t.n2, m + p.fc1_w, m + p.fc1_b, t.f1, Mo, 4 * c, c));
-      VTRY(launch_gelu_fwd(t.f1, t.gl, Mo * c, st));
-      VTRY(gemm_resid(t.gl, m + p.fc2_w, m + p.fc2_b, t.y1, t.y2, Mo, c, 4 * c));
+      TRY(launch_mv_ln(BTSBOT_F32, yin, m + p.n1w, m + p.n1b, t.n1, Mo, c, st));
+      TRY(gemm(t.n1, m + p.qkv_w, m + p.qkv_b, t.qkv, Mo, 3 * c, c));
+      TRY(launch_mv_pack_relbias(m + p.rel, k.dbias, c / 32, st));
+      TRY(launch_mv_attn(BTSBOT_F32, t.qkv, k.dbias, t.o, B, b.hout, c, g, st));
+      TRY(gemm_resid(t.o, m + p.proj_w, m + p.proj_b, yin, t.y1, Mo, c, c));
+      TRY(launch_mv_ln(BTSBOT_F32, t.y1, m + p.n2w, m + p.n2b, t.n2, Mo, c, st));
+      TRY(gemm(t.n2, m + p.fc1_w, m + p.fc1_b, t.f1, Mo, 4 * c, c));
+      TRY(launch_gelu_fwd(t.f1, t.gl, Mo * c, st));
+      TRY(gemm_resid(t.gl, m + p.fc2_w, m + p.fc2_b, t.y1, t.y2, Mo, c, 4 * c));
       yin = t.y2;
     }
     ++jblk;
@@ -1029,7 +1023,7 @@ int maxvit_train_forward(btsbot_ctx* h, const float* img, int B, float* master, 
     }
   }
   float* feat = k.dsmall;   // [B][512] (copied out by the caller before the backward reuses the scratch)
-  VTRY(launch_mv_final(k.xfin, m + mv->norm_w, m + mv->norm_b, feat, B, 49, 512, st));
+  TRY(launch_mv_final(k.xfin, m + mv->norm_w, m + mv->norm_b, feat, B, 49, 512, st));
   *feat_out = feat;
   return BTSBOT_OK;
 }
@@ -1050,26 +1044,26 @@ int maxvit_train_backward(btsbot_ctx* h, const float* img, const float* dfeat, f
   int64_t d16_n = 0;
   auto dgrad = [&](const float* dY, const float* W, float* dX, long M, int N, int K) -> int {
     if (lowp) {
-      if (!(d16_src == dY && d16_n == (int64_t)M * N)) VTRY(launch_cast(prec, dY, k.d16, (int64_t)M * N, st));
+      if (!(d16_src == dY && d16_n == (int64_t)M * N)) TRY(launch_cast(prec, dY, k.d16, (int64_t)M * N, st));
       d16_src = nullptr;
-      VTRY(launch_transpose_cast(prec, W, nullptr, k.w16, N, K, st));
+      TRY(launch_transpose_cast(prec, W, nullptr, k.w16, N, K, st));
       return launch_gemm(prec, EPI_BIAS, k.d16, k.w16, zero, nullptr, nullptr, dX, (int)M, K, N, st);
     }
-    VTRY(launch_transpose_f32(W, k.wt, N, K, st));
+    TRY(launch_transpose_f32(W, k.wt, N, K, st));
     return launch_gemm(BTSBOT_F32, EPI_BIAS, dY, k.wt, zero, nullptr, nullptr, dX, (int)M, K, N, st);
   };
   // dW [N][K] += dY^T X, db [N] += column sums of dY
   auto wgrad = [&](const float* dY, const float* X, float* dW, float* db, long M, int N, int K) -> int {
     d16_src = nullptr;
     if (lowp && N % 8 == 0 && K % 8 == 0) {
-      VTRY(launch_cast(prec, dY, k.d16, (int64_t)M * N, st));
+      TRY(launch_cast(prec, dY, k.d16, (int64_t)M * N, st));
       d16_src = dY;
       d16_n = (int64_t)M * N;
       const void* x16 = nullptr;
       for (const auto& e : mv->xkept)   // the forward's copy of this input, if it made one (a buffer is cast where it is
         if (e.first == X) x16 = e.second;   // written last: scratch maps reused by the forward appear once per use -- the last wins)
       if (x16 == nullptr) {
-        VTRY(launch_cast(prec, X, k.x16, (int64_t)M * K, st));
+        TRY(launch_cast(prec, X, k.x16, (int64_t)M * K, st));
         x16 = k.x16;
       }
       return launch_wgrad16(prec, k.d16, x16, dW, db, (int)M, N, K, K, st, k.wpart, MVT_WPART_FLOATS);
@@ -1080,8 +1074,8 @@ int maxvit_train_backward(btsbot_ctx* h, const float* img, const float* dfeat, f
   float* dy = k.dA;         // gradient w.r.t. the current map [rows][C]
   float* dt = k.dB;         // second map
   {
-    VTRY(launch_bcast_set(k.xn_final, dfeat, B, 49, 512, 1.0f / 49.0f, st));
-    VTRY(launch_ln_bwd(k.xfin, k.xn_final, m + mv->norm_w, dy, grads + mv->norm_w, grads + mv->norm_b, (long)B * 49, 512, st));
+    TRY(launch_bcast_set(k.xn_final, dfeat, B, 49, 512, 1.0f / 49.0f, st));
+    TRY(launch_ln_bwd(k.xfin, k.xn_final, m + mv->norm_w, dy, grads + mv->norm_w, grads + mv->norm_b, (long)B * 49, 512, st));
   }
   for (int bi = (int)mv->blocks.size() - 1; bi >= 0; --bi) {
     const MvBlock& b = mv->blocks[bi];
@@ -1094,56 +1088,56 @@ int maxvit_train_backward(btsbot_ctx* h, const float* img, const float* dfeat, f
       AttnAct& t = a.at[g];
       const float* yin = g == 0 ? a.y : a.at[0].y2;
       // y2 = y1 + gl W2^T + b2
-      VTRY(wgrad(dy, t.gl, grads + p.fc2_w, grads + p.fc2_b, Mo, c, 4 * c));
-      VTRY(dgrad(dy, m + p.fc2_w, dt, Mo, c, 4 * c));                       // d(gl) [Mo][4c]
-      VTRY(launch_gelu_bwd(t.f1, dt, Mo * c, st));
-      VTRY(wgrad(dt, t.n2, grads + p.fc1_w, grads + p.fc1_b, Mo, 4 * c, c));
-      VTRY(dgrad(dt, m + p.fc1_w, k.dC, Mo, 4 * c, c));                     // d(n2) [Mo][c]
-      VTRY(launch_ln_bwd(t.y1, k.dC, m + p.n2w, dt, grads + p.n2w, grads + p.n2b, Mo, c, st));
-      VTRY(launch_add(dy, dt, Mo * c / 4, st));   // dy = d(y1)
+      TRY(wgrad(dy, t.gl, grads + p.fc2_w, grads + p.fc2_b, Mo, c, 4 * c));
+      TRY(dgrad(dy, m + p.fc2_w, dt, Mo, c, 4 * c));                       // d(gl) [Mo][4c]
+      TRY(launch_gelu_bwd(t.f1, dt, Mo * c, st));
+      TRY(wgrad(dt, t.n2, grads + p.fc1_w, grads + p.fc1_b, Mo, 4 * c, c));
+      TRY(dgrad(dt, m + p.fc1_w, k.dC, Mo, 4 * c, c));                     // d(n2) [Mo][c]
+      TRY(launch_ln_bwd(t.y1, k.dC, m + p.n2w, dt, grads + p.n2w, grads + p.n2b, Mo, c, st));
+      TRY(launch_add(dy, dt, Mo * c / 4, st));   // dy = d(y1)
       // y1 = yin + o Wp^T + bp
-      VTRY(wgrad(dy, t.o, grads + p.proj_w, grads + p.proj_b, Mo, c, c));
-      VTRY(dgrad(dy, m + p.proj_w, dt, Mo, c, c));                          // d(o) [Mo][c]
-      VTRY(launch_attn_bwd(t.qkv, m + p.rel, dt, k.dC, k.dbias, grads + p.rel, B, b.hout, c, g, st));   // d(qkv) [Mo][3c]
-      VTRY(wgrad(k.dC, t.n1, grads + p.qkv_w, grads + p.qkv_b, Mo, 3 * c, c));
-      VTRY(dgrad(k.dC, m + p.qkv_w, dt, Mo, 3 * c, c));                     // d(n1) [Mo][c]
-      VTRY(launch_ln_bwd(yin, dt, m + p.n1w, k.dC, grads + p.n1w, grads + p.n1b, Mo, c, st));
-      VTRY(launch_add(dy, k.dC, Mo * c / 4, st));   // dy = d(yin)
+      TRY(wgrad(dy, t.o, grads + p.proj_w, grads + p.proj_b, Mo, c, c));
+      TRY(dgrad(dy, m + p.proj_w, dt, Mo, c, c));                          // d(o) [Mo][c]
+      TRY(launch_attn_bwd(t.qkv, m + p.rel, dt, k.dC, k.dbias, grads + p.rel, B, b.hout, c, g, st));   // d(qkv) [Mo][3c]
+      TRY(wgrad(k.dC, t.n1, grads + p.qkv_w, grads + p.qkv_b, Mo, 3 * c, c));
+      TRY(dgrad(k.dC, m + p.qkv_w, dt, Mo, 3 * c, c));                     // d(n1) [Mo][c]
+      TRY(launch_ln_bwd(yin, dt, m + p.n1w, k.dC, grads + p.n1w, grads + p.n1b, Mo, c, st));
+      TRY(launch_add(dy, k.dC, Mo * c / 4, st));   // dy = d(yin)
     }
     // ---- MBConv: y = sc + (a2 * g) W3^T;  dy = d(loss)/d(y) [Mo][c]
     float* dx = dt;           // gradient w.r.t. the block's input [Min][cin], accumulated from three paths
     // a3 = a2 * g (recomputed), d(a3) = dy W3
-    VTRY(launch_gate_mul(a.a2, a.g, k.dC, B, hw2, b.mid, st));
-    VTRY(wgrad(dy, k.dC, grads + b.c3_w, nullptr, Mo, c, b.mid));
-    VTRY(dgrad(dy, m + b.c3_w, k.dC, Mo, c, b.mid));                        // d(a3) [Mo][mid]
+    TRY(launch_gate_mul(a.a2, a.g, k.dC, B, hw2, b.mid, st));
+    TRY(wgrad(dy, k.dC, grads + b.c3_w, nullptr, Mo, c, b.mid));
+    TRY(dgrad(dy, m + b.c3_w, k.dC, Mo, c, b.mid));                        // d(a3) [Mo][mid]
     // squeeze-excite: dg[b][c] = sum_p d(a3) a2; d(a2) = d(a3) g (+ the pooled path below)
     float* dgate = k.dsmall;                    // [B][mid]
     float* dr = k.dsmall + (size_t)B * 2048;    // [B][rd] and scratch
     float* dpool = k.dsmall + (size_t)B * 2048 * 2;
     float* dgpre = k.dsmall + (size_t)B * 2048 * 3;
-    VTRY(launch_se_bwd(k.dC, a.a2, a.sepool, a.rpre, a.r, a.g, m + b.se1_w, m + b.se2_w, grads + b.se1_w, grads + b.se1_b,
+    TRY(launch_se_bwd(k.dC, a.a2, a.sepool, a.rpre, a.r, a.g, m + b.se1_w, m + b.se2_w, grads + b.se1_w, grads + b.se1_b,
                        grads + b.se2_w, grads + b.se2_b, dgate, dr, dpool, dgpre, B, hw2, b.mid, b.rd, st));
     // BN2 + SiLU: d(d2) in place of d(a2)
-    VTRY(bn_train_bwd(h, a.d2, k.dC, b.n2, a.st2, sums_arena, k.dC, grads, Mo, b.mid, 1, 0, st));
+    TRY(bn_train_bwd(h, a.d2, k.dC, b.n2, a.st2, sums_arena, k.dC, grads, Mo, b.mid, 1, 0, st));
     // depthwise 3x3: filter / bias gradients (tap-major, then into the master layout), input gradient d(a1) [Min][mid]
-    VTRY(launch_dw3_bwd_w(a.a1, k.dC, k.g9, grads + b.c2_w, grads + b.c2_b, B, b.hin, b.mid, b.stride, st));
-    VTRY(launch_mv_pack_dw(m + b.c2_w, F(mv->p_one), k.g9, b.mid, st));
-    VTRY(launch_dw3_bwd_in(k.dC, k.g9, dx, B, b.hin, b.mid, b.stride, st));
+    TRY(launch_dw3_bwd_w(a.a1, k.dC, k.g9, grads + b.c2_w, grads + b.c2_b, B, b.hin, b.mid, b.stride, st));
+    TRY(launch_mv_pack_dw(m + b.c2_w, F(mv->p_one), k.g9, b.mid, st));
+    TRY(launch_dw3_bwd_in(k.dC, k.g9, dx, B, b.hin, b.mid, b.stride, st));
     // BN1 + SiLU: d(c1) in place; conv1 1x1
-    VTRY(bn_train_bwd(h, a.c1, dx, b.n1, a.st1, sums_arena, dx, grads, Min, b.mid, 1, 0, st));
-    VTRY(wgrad(dx, a.a0, grads + b.c1_w, grads + b.c1_b, Min, b.mid, b.cin));
-    VTRY(dgrad(dx, m + b.c1_w, k.dC, Min, b.mid, b.cin));                   // d(a0) [Min][cin]
+    TRY(bn_train_bwd(h, a.c1, dx, b.n1, a.st1, sums_arena, dx, grads, Min, b.mid, 1, 0, st));
+    TRY(wgrad(dx, a.a0, grads + b.c1_w, grads + b.c1_b, Min, b.mid, b.cin));
+    TRY(dgrad(dx, m + b.c1_w, k.dC, Min, b.mid, b.cin));                   // d(a0) [Min][cin]
     // pre-norm BatchNorm (no activation): d(xin) = its input gradient ...
-    VTRY(bn_train_bwd(h, a.xin, k.dC, b.pre, a.st_pre, sums_arena, dx, grads, Min, b.cin, 0, 0, st));
+    TRY(bn_train_bwd(h, a.xin, k.dC, b.pre, a.st_pre, sums_arena, dx, grads, Min, b.cin, 0, 0, st));
     // ... plus the shortcut's: dy through identity | avgpool2 | avgpool2 . Wsc
     if (b.stride == 1) {
-      VTRY(launch_add(dx, dy, Min * b.cin / 4, st));
+      TRY(launch_add(dx, dy, Min * b.cin / 4, st));
     } else if (b.sc_w >= 0) {
-      VTRY(wgrad(dy, a.pool_in, grads + b.sc_w, nullptr, Mo, c, b.cin));
-      VTRY(dgrad(dy, m + b.sc_w, k.dC, Mo, c, b.cin));
-      VTRY(launch_avgpool2_bwd(k.dC, dx, B, b.hin, b.cin, 1, st));
+      TRY(wgrad(dy, a.pool_in, grads + b.sc_w, nullptr, Mo, c, b.cin));
+      TRY(dgrad(dy, m + b.sc_w, k.dC, Mo, c, b.cin));
+      TRY(launch_avgpool2_bwd(k.dC, dx, B, b.hin, b.cin, 1, st));
     } else {
-      VTRY(launch_avgpool2_bwd(dy, dx, B, b.hin, b.cin, 1, st));
+      TRY(launch_avgpool2_bwd(dy, dx, B, b.hin, b.cin, 1, st));
     }
     float* tswap = dy;       // dx becomes the next (earlier) block's dy
     dy = dx;
@@ -1152,16 +1146,16 @@ int maxvit_train_backward(btsbot_ctx* h, const float* img, const float* dfeat, f
   // ---- stem: x0 = im2col3(a1s) W2^T;  a1s = silu(BN(y1));  y1 = col1 W1^T
   {
     const long M0 = (long)B * 12544;
-    VTRY(launch_mv_im2col3(BTSBOT_F32, k.a1s, k.dC, B, 112, 32, st));
+    TRY(launch_mv_im2col3(BTSBOT_F32, k.a1s, k.dC, B, 112, 32, st));
     HIP_TRY(hipMemsetAsync(k.gconv, 0, (size_t)64 * 288 * 4, st));
-    VTRY(wgrad(dy, k.dC, k.gconv, nullptr, M0, 64, 288));
-    VTRY(launch_unpack_conv3_grad(k.gconv, grads + mv->stem2_w, 64, 32, 288, st));
-    VTRY(dgrad(dy, k.w2p, k.dC, M0, 64, 288));                              // d(col2) [M0][288]
-    VTRY(launch_col2im3(k.dC, dt, B, 112, 32, st));
-    VTRY(bn_train_bwd(h, k.y1, dt, mv->stem_bn, k.st_stem, sums_arena, dt, grads, M0, 32, 1, 0, st));
+    TRY(wgrad(dy, k.dC, k.gconv, nullptr, M0, 64, 288));
+    TRY(launch_unpack_conv3_grad(k.gconv, grads + mv->stem2_w, 64, 32, 288, st));
+    TRY(dgrad(dy, k.w2p, k.dC, M0, 64, 288));                              // d(col2) [M0][288]
+    TRY(launch_col2im3(k.dC, dt, B, 112, 32, st));
+    TRY(bn_train_bwd(h, k.y1, dt, mv->stem_bn, k.st_stem, sums_arena, dt, grads, M0, 32, 1, 0, st));
     HIP_TRY(hipMemsetAsync(k.gconv, 0, (size_t)32 * 32 * 4, st));
-    VTRY(wgrad(dt, k.col1, k.gconv, nullptr, M0, 32, 32));
-    VTRY(launch_unpack_conv3_grad(k.gconv, grads + mv->stem1_w, 32, 3, 32, st));
+    TRY(wgrad(dt, k.col1, k.gconv, nullptr, M0, 32, 32));
+    TRY(launch_unpack_conv3_grad(k.gconv, grads + mv->stem1_w, 32, 3, 32, st));
   }
   for (int i = 0; i < h->n_buckets; ++i) HIP_TRY(hipEventRecord(h->bucket_ev[i], st));
   return BTSBOT_OK;
@@ -1170,27 +1164,6 @@ int maxvit_train_backward(btsbot_ctx* h, const float* img, const float* dfeat, f
 // ---- op-level entry points (include/btsbot_hip.h, btsbot_op_mvt_*): the launchers above, one kernel group at a time,
 // on the caller's tensors and a stream-ordered scratch
 namespace {
-
-struct MvtScratch {   // (api.hip's OpScratch: offsets reserved first, one allocation, released behind the work on `st`)
-  hipStream_t st;
-  unsigned char* base = nullptr;
-  size_t total = 0;
-  explicit MvtScratch(hipStream_t s) : st(s) {}
-  ~MvtScratch() {
-    if (base != nullptr) (void)hipFreeAsync(base, st);
-  }
-  size_t reserve(size_t floats) {
-    const size_t o = total;
-    total += (floats * 4 + 255) / 256 * 256;
-    return o;
-  }
-  int alloc() {
-    if (hipMallocAsync(reinterpret_cast<void**>(&base), total ? total : 256, st) == hipSuccess) return BTSBOT_OK;
-    btsbot_set_error("op_mvt: hipMallocAsync of %zu scratch bytes failed", total);
-    return BTSBOT_ERR_HIP;
-  }
-  float* at(size_t off) const { return reinterpret_cast<float*>(base + off); }
-};
 
 int mvt_bad(const char* who, const char* what) {
   btsbot_set_error("%s: %s", who, what);
@@ -1206,7 +1179,7 @@ int mvt_dw3_shape(const char* who, int B, int H, int C, int stride) {
 }
 // taps [9][C] of w [C][1][3][3] as the engine packs them (scale = 1)
 int mvt_pack_taps(const float* w, float* ones, float* w9, int C, hipStream_t st) {
-  VTRY(launch_mv_fill(ones, 1.0f, C, st));
+  TRY(launch_mv_fill(ones, 1.0f, C, st));
   return launch_mv_pack_dw(w, ones, w9, C, st);
 }
 
@@ -1234,11 +1207,11 @@ extern "C" int btsbot_op_mvt_bn_fwd(const float* x, const float* w, const float*
     return BTSBOT_ERR_INVALID_ARG;
   }
   hipStream_t st = (hipStream_t)stream;
-  MvtScratch sc(st);
-  const size_t o0 = sc.reserve(2 * (size_t)C), o1 = sc.reserve(2 * (size_t)C);
-  VTRY(sc.alloc());
+  StreamScratch sc(st, "op_mvt");
+  const size_t o0 = sc.reserve(2 * (size_t)C * 4), o1 = sc.reserve(2 * (size_t)C * 4);
+  TRY(sc.alloc());
   HIP_TRY(hipMemsetAsync(sc.base, 0, sc.total, st));
-  return launch_bn_train(x, w, b, stat, sc.at(o0), sc.at(o1), run_mean, run_var, y, (long)M, C, act, st);
+  return launch_bn_train(x, w, b, stat, sc.at<float>(o0), sc.at<float>(o1), run_mean, run_var, y, (long)M, C, act, st);
 }
 
 extern "C" int btsbot_op_mvt_bn_bwd(const float* x, const float* dy, const float* stat, const float* w, const float* b, float* dx,
@@ -1252,49 +1225,49 @@ extern "C" int btsbot_op_mvt_bn_bwd(const float* x, const float* dy, const float
     return BTSBOT_ERR_INVALID_ARG;
   }
   hipStream_t st = (hipStream_t)stream;
-  MvtScratch sc(st);
-  const size_t o = sc.reserve(2 * (size_t)C);
-  VTRY(sc.alloc());
+  StreamScratch sc(st, "op_mvt");
+  const size_t o = sc.reserve(2 * (size_t)C * 4);
+  TRY(sc.alloc());
   HIP_TRY(hipMemsetAsync(sc.base, 0, sc.total, st));
-  return launch_bn_train_bwd(x, dy, stat, w, b, sc.at(o), dx, dw, db, (long)M, C, act, accumulate, st);
+  return launch_bn_train_bwd(x, dy, stat, w, b, sc.at<float>(o), dx, dw, db, (long)M, C, act, accumulate, st);
 }
 
 extern "C" int btsbot_op_mvt_dw3_fwd(const float* in, const float* w, const float* bias, float* out, int B, int H, int C,
                                      int stride, void* stream) {
   if (in == nullptr || w == nullptr || bias == nullptr || out == nullptr) return mvt_bad("op_mvt_dw3_fwd", "null pointer");
-  VTRY(mvt_dw3_shape("op_mvt_dw3_fwd", B, H, C, stride));
+  TRY(mvt_dw3_shape("op_mvt_dw3_fwd", B, H, C, stride));
   if (B == 0) return BTSBOT_OK;
   hipStream_t st = (hipStream_t)stream;
-  MvtScratch sc(st);
-  const size_t o1 = sc.reserve(C), o9 = sc.reserve(9 * (size_t)C);
-  VTRY(sc.alloc());
-  VTRY(mvt_pack_taps(w, sc.at(o1), sc.at(o9), C, st));
-  return launch_dw3_fwd(in, sc.at(o9), bias, out, B, H, C, stride, st);
+  StreamScratch sc(st, "op_mvt");
+  const size_t o1 = sc.reserve(C * 4), o9 = sc.reserve(9 * (size_t)C * 4);
+  TRY(sc.alloc());
+  TRY(mvt_pack_taps(w, sc.at<float>(o1), sc.at<float>(o9), C, st));
+  return launch_dw3_fwd(in, sc.at<float>(o9), bias, out, B, H, C, stride, st);
 }
 
 extern "C" int btsbot_op_mvt_dw3_bwd_in(const float* dout, const float* w, float* din, int B, int H, int C, int stride,
                                         void* stream) {
   if (dout == nullptr || w == nullptr || din == nullptr) return mvt_bad("op_mvt_dw3_bwd_in", "null pointer");
-  VTRY(mvt_dw3_shape("op_mvt_dw3_bwd_in", B, H, C, stride));
+  TRY(mvt_dw3_shape("op_mvt_dw3_bwd_in", B, H, C, stride));
   if (B == 0) return BTSBOT_OK;
   hipStream_t st = (hipStream_t)stream;
-  MvtScratch sc(st);
-  const size_t o1 = sc.reserve(C), o9 = sc.reserve(9 * (size_t)C);
-  VTRY(sc.alloc());
-  VTRY(mvt_pack_taps(w, sc.at(o1), sc.at(o9), C, st));
-  return launch_dw3_bwd_in(dout, sc.at(o9), din, B, H, C, stride, st);
+  StreamScratch sc(st, "op_mvt");
+  const size_t o1 = sc.reserve(C * 4), o9 = sc.reserve(9 * (size_t)C * 4);
+  TRY(sc.alloc());
+  TRY(mvt_pack_taps(w, sc.at<float>(o1), sc.at<float>(o9), C, st));
+  return launch_dw3_bwd_in(dout, sc.at<float>(o9), din, B, H, C, stride, st);
 }
 
 extern "C" int btsbot_op_mvt_dw3_bwd_w(const float* in, const float* dout, float* dw, float* dbias, int B, int H, int C,
                                        int stride, void* stream) {
   if (in == nullptr || dout == nullptr || dw == nullptr || dbias == nullptr) return mvt_bad("op_mvt_dw3_bwd_w", "null pointer");
-  VTRY(mvt_dw3_shape("op_mvt_dw3_bwd_w", B, H, C, stride));
+  TRY(mvt_dw3_shape("op_mvt_dw3_bwd_w", B, H, C, stride));
   if (B == 0) return BTSBOT_OK;
   hipStream_t st = (hipStream_t)stream;
-  MvtScratch sc(st);
-  const size_t o = sc.reserve(10 * (size_t)C);
-  VTRY(sc.alloc());
-  return launch_dw3_bwd_w(in, dout, sc.at(o), dw, dbias, B, H, C, stride, st);
+  StreamScratch sc(st, "op_mvt");
+  const size_t o = sc.reserve(10 * (size_t)C * 4);
+  TRY(sc.alloc());
+  return launch_dw3_bwd_w(in, dout, sc.at<float>(o), dw, dbias, B, H, C, stride, st);
 }
 
 extern "C" int btsbot_op_mvt_attn_bwd(const float* qkv, const float* table, const float* dout, float* dqkv, float* dtable, int B,
@@ -1309,10 +1282,10 @@ extern "C" int btsbot_op_mvt_attn_bwd(const float* qkv, const float* table, cons
   if ((long)B * (H / 7) * (H / 7) > 0x7fffffffL) return mvt_bad("op_mvt_attn_bwd", "too many (alert, partition) units");
   if (B == 0) return BTSBOT_OK;
   hipStream_t st = (hipStream_t)stream;
-  MvtScratch sc(st);
-  const size_t o = sc.reserve((size_t)32 * 2401);
-  VTRY(sc.alloc());
-  return launch_attn_bwd(qkv, table, dout, dqkv, sc.at(o), dtable, B, H, C, grid_mode, st);
+  StreamScratch sc(st, "op_mvt");
+  const size_t o = sc.reserve((size_t)32 * 2401 * 4);
+  TRY(sc.alloc());
+  return launch_attn_bwd(qkv, table, dout, dqkv, sc.at<float>(o), dtable, B, H, C, grid_mode, st);
 }
 
 // (the small dense kernels index [B][C] and [RD][C] with an int)
@@ -1330,7 +1303,7 @@ extern "C" int btsbot_op_mvt_se_fwd(const float* a2, const float* fc1_w, const f
   if (a2 == nullptr || fc1_w == nullptr || fc1_b == nullptr || fc2_w == nullptr || fc2_b == nullptr || pool == nullptr ||
       rpre == nullptr || r == nullptr || gate == nullptr || gated == nullptr)
     return mvt_bad("op_mvt_se_fwd", "null pointer");
-  VTRY(mvt_se_shape("op_mvt_se_fwd", B, P, C, RD));
+  TRY(mvt_se_shape("op_mvt_se_fwd", B, P, C, RD));
   if (B == 0) return BTSBOT_OK;
   return launch_se_fwd(a2, fc1_w, fc1_b, fc2_w, fc2_b, pool, rpre, r, gate, gated, B, P, C, RD, (hipStream_t)stream);
 }
@@ -1342,17 +1315,18 @@ extern "C" int btsbot_op_mvt_se_bwd(const float* d_gated, const float* a2, const
       fc1_w == nullptr || fc2_w == nullptr || d_a2 == nullptr || d_fc1_w == nullptr || d_fc1_b == nullptr || d_fc2_w == nullptr ||
       d_fc2_b == nullptr)
     return mvt_bad("op_mvt_se_bwd", "null pointer");
-  VTRY(mvt_se_shape("op_mvt_se_bwd", B, P, C, RD));
+  TRY(mvt_se_shape("op_mvt_se_bwd", B, P, C, RD));
   if (B == 0) return BTSBOT_OK;
   hipStream_t st = (hipStream_t)stream;
-  MvtScratch sc(st);
+  StreamScratch sc(st, "op_mvt");
   const size_t bc = (size_t)B * C;
-  const size_t o_dgate = sc.reserve(bc), o_dr = sc.reserve((size_t)B * RD), o_dpool = sc.reserve(bc), o_dgpre = sc.reserve(bc);
-  VTRY(sc.alloc());
+  const size_t o_dgate = sc.reserve(bc * 4), o_dr = sc.reserve((size_t)B * RD * 4), o_dpool = sc.reserve(bc * 4),
+               o_dgpre = sc.reserve(bc * 4);
+  TRY(sc.alloc());
   // (the engine's chain runs in place on d(gated))
   if (d_a2 != d_gated) HIP_TRY(hipMemcpyAsync(d_a2, d_gated, (size_t)B * P * C * 4, hipMemcpyDeviceToDevice, st));
-  return launch_se_bwd(d_a2, a2, pool, rpre, r, gate, fc1_w, fc2_w, d_fc1_w, d_fc1_b, d_fc2_w, d_fc2_b, sc.at(o_dgate), sc.at(o_dr),
-                       sc.at(o_dpool), sc.at(o_dgpre), B, P, C, RD, st);
+  return launch_se_bwd(d_a2, a2, pool, rpre, r, gate, fc1_w, fc2_w, d_fc1_w, d_fc1_b, d_fc2_w, d_fc2_b, sc.at<float>(o_dgate), sc.at<float>(o_dr),
+                       sc.at<float>(o_dpool), sc.at<float>(o_dgpre), B, P, C, RD, st);
 }
 
 extern "C" int btsbot_op_mvt_avgpool2_bwd(const float* g, float* dx, int B, int H, int C, int accumulate, void* stream) {

@@ -381,12 +381,6 @@ int launch_pack_down_t(int prec, const float* src, void* dst, int Cout, int Cin,
 // ---------------------------------------------------------------------------------------
 namespace {
 
-#define TRY(call)                   \
-  do {                              \
-    int _s = (call);                \
-    if (_s != BTSBOT_OK) return _s; \
-  } while (0)
-
 // Every packed image of the handle, in the order the packs write them: stem, then per stage the downsample and the
 // blocks, the split-training planes, metadata, fusion, head16.  THE place that decides that an image exists (an entry
 // with bytes) and which packs write it (`when`), from the handle's resolved schedule (schedule.h): a stage kernel's images

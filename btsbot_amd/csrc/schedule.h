@@ -80,7 +80,7 @@ int switch_int(Switch s, int dflt);
 bool switch_set(Switch s);   // present at all, whatever its value
 
 // Which kernel runs what on one handle: the final decisions, each from the handle's configuration, what the kernels
-// support and the switches above.  resolve_schedule() is the only writer; the schedules (api.hip, backbone_train.hip,
+// support and the switches above.  resolve_schedule() is the only writer; the schedules (forward.hip, backbone_train.hip,
 // head_train.hip, maxvit.hip), the workspace / cache layouts and the image list (pack.hip) read these and nothing else.
 // X(field): the on/off decisions, which btsbot_set_option(h, "query_schedule:<field>", 0) reports.
 #define BTSBOT_SCHEDULE_FLAGS(X)                                                                                       \

@@ -1,5 +1,5 @@
 // Argument blocks of the ConvNeXt stage kernels (stage0.h, stage2p.h, stage3.h), shared by the inference forward
-// (api.hip: backbone_chunk) and the training forward (backbone_train.hip): the parameter pointers of every block and
+// (forward.hip: backbone_chunk) and the training forward (backbone_train.hip): the parameter pointers of every block and
 // downsample.  The callers add their buffers, taps, stamps and the keeping form's keep_* / train.  BTSBOT_ERR_STATE:
 // the handle has no such operand image (ctx.h: IMG).
 #include <string.h>

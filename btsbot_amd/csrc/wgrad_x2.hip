@@ -18,12 +18,6 @@
 
 namespace {
 
-#define TRYX(call)                  \
-  do {                              \
-    int _s = (call);                \
-    if (_s != BTSBOT_OK) return _s; \
-  } while (0)
-
 constexpr int TM = 64;   // reduction rows per LDS tile
 
 // 4 fp32 values (times s) -> f16 heads and remainders at row r, 4-column chunk cc of the two images
@@ -221,7 +215,7 @@ int wgrad_x2_launch(const float* D, const float* A, float* out, float* colsum, i
   LAUNCH_CHECK();
   if (cpart != nullptr) {
     const DetOut o{colsum, 1};
-    TRYX(launch_det_reduce(cpart, nsl, N, 1, &o, st));
+    TRY(launch_det_reduce(cpart, nsl, N, 1, &o, st));
   }
   WgradReduceJob job = {part, out, N, K, ldo, gx, gy, two_pass ? nsl : 0, TN, TK};
   if (defer != nullptr) {

@@ -293,6 +293,28 @@ def test_environment_is_read_through_the_switch_table_only():
     assert "getenv(" not in open(os.path.join(_CSRC, "common.h")).read()
 
 
+def test_host_helpers_exist_once_and_every_source_is_built():
+    """Every *.hip of csrc/ is a source of the Makefile; the status-propagating macro is defined in common.h alone; one
+    stream-ordered scratch type (a struct ...Scratch whose destructor calls hipFreeAsync) serves every entry point."""
+    names = sorted(os.listdir(_CSRC))
+    srcs = re.search(r"^SRCS\s*=\s*(.*)$", open(os.path.join(_CSRC, "Makefile")).read(), re.M).group(1).split()
+    hips = [f for f in names if f.endswith(".hip")]
+    assert sorted(srcs) == hips, sorted(set(hips) ^ set(srcs))
+    defines, scratch = [], []
+    for f in names:
+        if not f.endswith((".hip", ".h")):
+            continue
+        text = open(os.path.join(_CSRC, f)).read()
+        defines += [f"{f}: {m}" for m in re.findall(r"#define \w*TRY\w*\(", text)]
+        for m in re.finditer(r"struct (\w*Scratch)\b[^;{]*\{", text):
+            body = text[m.end():text.find("\n};", m.end())]
+            if re.search(r"~%s\(\)[^}]*hipFreeAsync" % m.group(1), body):
+                scratch.append(f"{f}: {m.group(1)}")
+    assert defines and all(d.startswith("common.h: ") for d in defines), defines
+    assert sorted(d.split(": ")[1] for d in defines) == ["#define HIP_TRY(", "#define TRY("], defines
+    assert len(scratch) == 1, scratch
+
+
 def test_every_documented_switch_is_in_the_table():
     """Each BTSBOT_AMD_* name the header, DESIGN.md section 4c's neighbourhood, bench.py, the tests and the tools use is a
     row of the table, or one of the variables Python reads (an explicit list)."""

@@ -42,6 +42,8 @@ from . import diagnostics
 from .diagnostics import alert_histograms, diagnostic_data, diagnostic_fig, draw_diagnostic_fig, roc_points
 from .triggers import TriggerState
 from .features import FeatureState
+from . import neighbors
+from .neighbors import EmbeddingIndex, embedding_neighbors, knn_graph
 from .splits import (SOURCE_SETS, SPLIT_NAMES, create_subset, cut_set_and_assign_splits, cuts_suffix, label_set,
                      merge_sets_across_split, split_labels, subsample_data, subset_mask)
 
@@ -53,6 +55,7 @@ __all__ = [
     "REFERENCE_POLICIES", "policy_eval", "policy_performance", "triggers", "TriggerState",
     "diagnostics", "alert_histograms", "roc_points", "diagnostic_data", "diagnostic_fig", "draw_diagnostic_fig",
     "features", "FeatureState",
+    "neighbors", "EmbeddingIndex", "embedding_neighbors", "knn_graph",
     "splits", "SPLIT_NAMES", "SOURCE_SETS", "label_set", "split_labels", "subset_mask", "cuts_suffix",
     "cut_set_and_assign_splits", "merge_sets_across_split", "create_subset", "subsample_data",
 ]

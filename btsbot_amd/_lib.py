@@ -48,7 +48,10 @@ SYMBOLS = [
     "btsbot_policy_eval", "btsbot_alert_histograms", "btsbot_trigger_reset", "btsbot_trigger_update", "btsbot_trigger_load",
     "btsbot_trigger_rehash", "btsbot_feature_reset", "btsbot_feature_update", "btsbot_feature_load", "btsbot_feature_rehash",
     "btsbot_embed_width", "btsbot_forward_embed",
+    "btsbot_knn_bank_bytes", "btsbot_knn_pack_bank", "btsbot_knn_splits", "btsbot_knn_workspace", "btsbot_knn_query",
 ]
+KNN_METRIC = {"euclidean": 0, "cosine": 1}   # enum btsbot_knn_metric
+KNN_MAX_DIM, KNN_MAX_K, KNN_MAX_SPLITS = 1024, 64, 32
 EMBEDDING = {"features": 0, "hidden": 1}   # enum btsbot_embedding
 # enum btsbot_stamp_status: what btsbot_decode_stamps says of each stamp
 STAMP_STATUS = {"OK": 0, "BAD_GZIP": 1, "BAD_DEFLATE": 2, "TOO_LARGE": 3, "BAD_TRAILER": 4, "BAD_FITS": 5,
@@ -260,6 +263,16 @@ def lib() -> C.CDLL:
     L.btsbot_feature_load.argtypes = [C.POINTER(FeatureTable), i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.btsbot_feature_rehash.restype = i32
     L.btsbot_feature_rehash.argtypes = [C.POINTER(FeatureTable), C.POINTER(FeatureTable), C.c_double, vp]
+    L.btsbot_knn_bank_bytes.restype = i64
+    L.btsbot_knn_bank_bytes.argtypes = [i64, i32]
+    L.btsbot_knn_pack_bank.restype = i32
+    L.btsbot_knn_pack_bank.argtypes = [vp, i64, i64, i32, i32, vp, i64, vp]
+    L.btsbot_knn_splits.restype = i32
+    L.btsbot_knn_splits.argtypes = [i64, i64, i32, i32]
+    L.btsbot_knn_workspace.restype = i64
+    L.btsbot_knn_workspace.argtypes = [i64, i64, i32, i32, i32]
+    L.btsbot_knn_query.restype = i32
+    L.btsbot_knn_query.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, i64, i32, vp, vp, vp, i64, vp]
     L.btsbot_eval_metrics.restype = i32
     L.btsbot_eval_metrics.argtypes = [vp, vp, f32, i64, vp, vp]
     if L.btsbot_abi_version() != ABI_VERSION:

@@ -1,0 +1,594 @@
+// btsbot_knn_*: exact brute-force k-nearest neighbours over embedding rows (gfx950), DESIGN.md section 4m.
+//
+//   idx[q][0..k), dist[q][0..k) = the k bank rows nearest to query row q, ascending by (dist, bank index)
+//
+// Two passes, neither of which writes anything of size Q x N:
+//
+//   selection  grid = query tiles (128 rows) x bank splits.  A workgroup walks its slice of the bank in tiles of 128 rows,
+//              forms the 128 x 128 products on the matrix pipe and keeps each query row's best k (score, index) pairs
+//              in LDS.  score = |b|^2 - 2 q.b (Euclidean; |q|^2 is the same for every candidate of a row) or
+//              -2 q.b / |b| (cosine).  Ties go to the lower bank index.  k candidates per (query, split) to the workspace.
+//   merge      one wave per query: the k best of its splits * k candidates by (score, index) -- the same k whatever the
+//              number of splits --, each one's distance again in the direct form (sum (q_i - b_i)^2, or the fp32 dot and
+//              norms) from the ORIGINAL fp32 rows, sorted by (distance, index).
+//
+// Operands: every row enters the products as an f16 head + f16 remainder of the row scaled by a power of two of its own
+// (its largest magnitude lands in [2^14, 2^15): common.h, split_exp), three v_mfma_f32_16x16x32_f16 per product, small
+// terms first (gemm_x2.hip).  The scale is per ROW, so a row's image depends on nothing but the row: an index built by
+// several adds equals one built at once, and a query's answer does not depend on its neighbours in the batch.  A packed row
+// is one record of 16 + 4 * dp bytes (dp = dim rounded up to 32, zero filled):
+//   float bias, float scale, 8 bytes unused, f16 head[dp], f16 remainder[dp]
+// bank rows: bias = |b|^2 and scale = 2^-e (Euclidean), bias = 0 and scale = 2^-e / |b| (cosine; 0 for a zero row); a row
+// that holds a non-finite value, or whose squared norm is not finite in fp32, has bias = +inf, scale = 0 and a zero image:
+// its score is +inf and +inf is never kept.  Query rows: scale = 2^(1-e) (0 and a zero image for a non-finite row, which
+// the merge answers with idx = -1, dist = NaN).  score = fma(-(acc * qscale), bscale, bias): the two scalings are exact.
+//
+// The GEMM part is gemm_x2.hip's 128 x 128 tile (256 threads = 2 x 2 waves, K tile 64, the same LDS swizzle, the MFMA run
+// "transposed": bank rows = A operand, query rows = B operand) reading both operands already split; the next K tile's
+// (and the next bank tile's first) operands are loaded into registers under the products.  After a tile's products every
+// lane compares its 64 scores with its rows' worst kept score; what passes goes into per-row buckets in the (then idle)
+// operand LDS, and thread q, the owner of row q's list, takes its bucket: see offer().  Nothing here meets through an
+// atomic whose order matters: the bucket slots are handed out by LDS atomics, but a list is the k best of what it was
+// offered whatever the order.  LDS: 64 KB of operands + 1 KB of lists per k, so two workgroups share a CU up to k = 16.
+#include <float.h>
+
+#include "common.h"
+
+namespace {
+
+constexpr int TQ = 128, TB = 128;   // query rows and bank rows per tile
+constexpr int BK = 64;              // K elements per tile
+constexpr int ROWB = 128;           // bytes per LDS row of one plane (64 f16)
+constexpr int GEMM_LDS = 2 * (TQ + TB) * ROWB;   // 64 KB: four operand planes
+constexpr int BCAP = 8;             // candidates a query row's bucket holds per round
+constexpr int HDR = 16;             // bytes in front of a record's head plane
+constexpr int EMPTY = 0x7fffffff;   // index of an empty list entry (score +inf)
+constexpr int MAX_K = 64, MAX_DIM = 1024, MAX_SPLITS = 32;
+enum { MODE_BANK_L2 = 0, MODE_BANK_COS = 1, MODE_QUERY = 2 };
+
+struct Cand {
+  float s;
+  int i;
+};
+
+__host__ __device__ inline int padded_dim(int dim) { return (dim + 31) & ~31; }
+__host__ __device__ inline size_t record_bytes(int dim) { return (size_t)HDR + 4 * (size_t)padded_dim(dim); }
+
+__device__ __forceinline__ bool before(float s1, int i1, float s2, int i2) { return s1 < s2 || (s1 == s2 && i1 < i2); }
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// pack: one wave per row
+__global__ __launch_bounds__(256) void knn_pack_kernel(const float* __restrict__ rows, long n_rows, int dim, int mode,
+                                                       unsigned char* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n_rows) return;
+  const int dp = padded_dim(dim);
+  const float* x = rows + row * dim;
+  float v[MAX_DIM / 64];
+  unsigned amax = 0;
+  bool fin = true;
+  float ss = 0.f;
+#pragma unroll
+  for (int j = 0; j < MAX_DIM / 64; ++j) {
+    const int d = j * 64 + lane;
+    v[j] = d < dim ? x[d] : 0.f;
+    fin = fin && fabsf(v[j]) <= FLT_MAX;   // false for inf and NaN
+    amax = max(amax, __float_as_uint(fabsf(v[j])));
+    ss = fmaf(v[j], v[j], ss);
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) amax = max(amax, (unsigned)__shfl_xor((int)amax, o));
+  fin = __all(fin);
+  ss = wave_sum(ss);
+  const bool ok = fin && ss <= FLT_MAX;
+  int e = 0;
+  const float a = __uint_as_float(amax);
+  if (ok && a > 0.f) {
+    int ex;
+    (void)frexpf(a, &ex);   // a in [2^(ex-1), 2^ex)
+    e = 15 - ex;
+    e = e < -120 ? -120 : e > 120 ? 120 : e;
+  }
+  const float up = ok ? ldexpf(1.f, e) : 0.f;
+  unsigned char* rec = out + (size_t)row * record_bytes(dim);
+  f16_t* hi = reinterpret_cast<f16_t*>(rec + HDR);
+  f16_t* lo = hi + dp;
+#pragma unroll
+  for (int j = 0; j < MAX_DIM / 64; ++j) {
+    const int d = j * 64 + lane;
+    if (d < dp) {
+      f16_t h, l;
+      split_f16(ok ? v[j] * up : 0.f, h, l);
+      hi[d] = h;
+      lo[d] = l;
+    }
+  }
+  if (lane == 0) {
+    float bias = 0.f, scale = 0.f;
+    if (mode == MODE_QUERY) {
+      scale = ok ? ldexpf(1.f, 1 - e) : 0.f;
+    } else if (!ok) {
+      bias = __builtin_inff();
+    } else if (mode == MODE_BANK_L2) {
+      bias = ss;
+      scale = ldexpf(1.f, -e);
+    } else {
+      scale = ss > 0.f ? ldexpf(1.f, -e) / sqrtf(ss) : 0.f;
+    }
+    *reinterpret_cast<float4*>(rec) = make_float4(bias, scale, 0.f, 0.f);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// selection
+__device__ __forceinline__ f32x4 mma_x2(const h2x8& a, const h2x8& b, f32x4 c) {
+  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.lo, b.hi, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.lo, c, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.hi, c, 0, 0, 0);
+}
+
+__device__ __forceinline__ int swz(int row, int chunk) { return row * ROWB + ((chunk ^ ((row >> 1) & 7)) << 4); }
+
+// The barriers behind a tile's products: LDS traffic only, so the next tile's operand loads stay in flight across them
+// (__syncthreads() would wait for them)
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");   // (no LDS read of the next phase moves above the barrier)
+}
+
+// A list is the k best by (score, index) of what it was offered, UNSORTED (the merge ranks by counting), with its worst
+// entry (ts, ti) at position tp: a better candidate replaces the worst, then the worst is looked up again -- k independent
+// LDS reads, where shifting a sorted list was a chain of dependent ones (23 of 51 ms at N = 500,000, D = 528, k = 15).
+__device__ __forceinline__ void offer(Cand* mine, int k, float s, int gb, float& ts, int& ti, int& tp) {
+  if (!before(s, gb, ts, ti)) return;
+  mine[tp] = Cand{s, gb};
+  Cand w = mine[0];
+  int wp = 0;
+#pragma unroll 4
+  for (int j = 1; j < k; ++j) {
+    const Cand o = mine[j];
+    if (before(w.s, w.i, o.s, o.i)) {
+      w = o;
+      wp = j;
+    }
+  }
+  ts = w.s;
+  ti = w.i;
+  tp = wp;
+}
+
+__global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char* __restrict__ qimg,
+                                                            const unsigned char* __restrict__ bimg, long Q, int N,
+                                                            int dim, int k, long self_offset, int tiles_per_split,
+                                                            int splits, Cand* __restrict__ cand) {
+  constexpr int MI = 4, NI = 4;     // 16-row fragments per wave: queries (B operand), bank rows (A operand)
+  constexpr int CH = TQ * 8 / 256;  // 16-byte chunks per thread, plane and K tile (TQ == TB)
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned char* Qh = smem;
+  unsigned char* Ql = Qh + TQ * ROWB;
+  unsigned char* Bh = Ql + TQ * ROWB;
+  unsigned char* Bl = Bh + TB * ROWB;
+  Cand* L = reinterpret_cast<Cand*>(smem + GEMM_LDS);   // [TQ][k] lists
+  // behind a tile's products, over the idle operand planes: the candidate buckets of the tile's query rows, their fill
+  // counts, the rows' worst kept scores and two "candidates left over" flags
+  Cand* bucket = reinterpret_cast<Cand*>(smem);         // [TQ][BCAP] (score, bank row of the tile)
+  int* bcnt = reinterpret_cast<int*>(bucket + TQ * BCAP);
+  float* thr = reinterpret_cast<float*>(bcnt + TQ);
+  int* flag = reinterpret_cast<int*>(thr + TQ);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int lrow = lane & 15, lq = lane >> 4;
+  const int dp = padded_dim(dim);
+  const size_t rec = record_bytes(dim);
+  const long q0 = (long)blockIdx.x * TQ;
+  const int split = blockIdx.y;
+  const int total_tiles = (N + TB - 1) / TB;
+  const int t_begin = (int)min((long)split * tiles_per_split, (long)total_tiles);
+  const int t_end = (int)min((long)(split + 1) * tiles_per_split, (long)total_tiles);
+  const int b_end = (int)min((long)t_end * TB, (long)N);
+  const int nk = (dp + BK - 1) / BK;
+
+  // the thread's own list (threads 0..TQ-1: query row q0 + tid)
+  const bool owner = tid < TQ && q0 + tid < Q;
+  float ts = __builtin_inff();
+  int ti = EMPTY, tp = 0;
+  if (tid < TQ)
+    for (int j = 0; j < k; ++j) L[tid * k + j] = Cand{__builtin_inff(), EMPTY};
+
+  float sq[MI];
+  int selfb[MI];   // the bank row that IS the query row (never a candidate), -1: none
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    const long gq = q0 + wm * 64 + mi * 16 + lrow;
+    sq[mi] = gq < Q ? reinterpret_cast<const float*>(qimg + gq * rec)[1] : 0.f;
+    const long sb = gq + self_offset;
+    selfb[mi] = self_offset >= 0 && sb < N ? (int)sb : -1;
+  }
+
+  uint4 qh[CH], ql[CH], bh[CH], bl[CH];
+  auto gload = [&](int tile, int kt) {
+    const int k0 = kt * BK;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      const int c = tid + i * 256, row = c >> 3, gk = k0 + (c & 7) * 8;
+      const long gq = q0 + row;
+      const long gb = (long)tile * TB + row;
+      const bool kin = gk < dp;   // (dp % 8 == 0: a chunk is wholly inside or wholly outside)
+      const unsigned char* pq = qimg + gq * rec + HDR + gk * 2;
+      const unsigned char* pb = bimg + gb * rec + HDR + gk * 2;
+      const bool okq = kin && gq < Q, okb = kin && gb < N;
+      qh[i] = okq ? *reinterpret_cast<const uint4*>(pq) : make_uint4(0, 0, 0, 0);
+      ql[i] = okq ? *reinterpret_cast<const uint4*>(pq + 2 * dp) : make_uint4(0, 0, 0, 0);
+      bh[i] = okb ? *reinterpret_cast<const uint4*>(pb) : make_uint4(0, 0, 0, 0);
+      bl[i] = okb ? *reinterpret_cast<const uint4*>(pb + 2 * dp) : make_uint4(0, 0, 0, 0);
+    }
+  };
+  auto sstore = [&]() {
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      const int c = tid + i * 256;
+      const int o = swz(c >> 3, c & 7);
+      *reinterpret_cast<uint4*>(Qh + o) = qh[i];
+      *reinterpret_cast<uint4*>(Ql + o) = ql[i];
+      *reinterpret_cast<uint4*>(Bh + o) = bh[i];
+      *reinterpret_cast<uint4*>(Bl + o) = bl[i];
+    }
+  };
+
+  if (t_begin < t_end) gload(t_begin, 0);
+  __syncthreads();   // the lists
+  for (int tile = t_begin; tile < t_end; ++tile) {
+    const int b0 = tile * TB;
+    f32x4 acc[NI][MI];
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    for (int kt = 0; kt < nk; ++kt) {
+      sstore();
+      __syncthreads();
+      if (kt + 1 < nk) gload(tile, kt + 1);
+      else if (tile + 1 < t_end) gload(tile + 1, 0);
+#pragma unroll 1   // (unrolled, the fragments of both halves are loaded up front: 56 registers to scratch)
+      for (int ks = 0; ks < BK / 32; ++ks) {
+        if (kt * BK + ks * 32 < dp) {
+          h2x8 bfr[MI];
+#pragma unroll
+          for (int mi = 0; mi < MI; ++mi) {
+            const int o = swz(wm * 64 + mi * 16 + lrow, ks * 4 + lq);
+            bfr[mi].hi = *reinterpret_cast<const f16x8*>(Qh + o);
+            bfr[mi].lo = *reinterpret_cast<const f16x8*>(Ql + o);
+          }
+#pragma unroll
+          for (int ni = 0; ni < NI; ++ni) {
+            const int o = swz(wn * 64 + ni * 16 + lrow, ks * 4 + lq);
+            h2x8 afr;
+            afr.hi = *reinterpret_cast<const f16x8*>(Bh + o);
+            afr.lo = *reinterpret_cast<const f16x8*>(Bl + o);
+#pragma unroll
+            for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = mma_x2(afr, bfr[mi], acc[ni][mi]);
+          }
+        }
+      }
+      lds_barrier();
+    }
+
+    // ---- the tile's candidates.  The operand planes are idle: the owners publish their worst kept scores there
+    if (tid < TQ) {
+      thr[tid] = owner ? ts : -__builtin_inff();   // (a row past Q never has a candidate)
+      bcnt[tid] = 0;
+    }
+    if (tid < 2) flag[tid] = 0;
+    lds_barrier();
+    // scores, and which of them can enter a list (<=: a tie may still win on the index); the tile's bank biases and
+    // scales: rows b0 + wn * 64 + ni * 16 + lq * 4 + i
+    float t[MI];
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) t[mi] = thr[wm * 64 + mi * 16 + lrow];
+    unsigned long long mask = 0;
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni) {
+      float nb[4], sb[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int b = b0 + wn * 64 + ni * 16 + lq * 4 + i;
+        const float2 h = b < N ? *reinterpret_cast<const float2*>(bimg + (size_t)b * rec)
+                               : make_float2(__builtin_inff(), 0.f);
+        nb[i] = h.x;
+        sb[i] = h.y;
+      }
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int gb = b0 + wn * 64 + ni * 16 + lq * 4 + i;
+          const float s = fmaf(-(acc[ni][mi][i] * sq[mi]), sb[i], nb[i]);
+          acc[ni][mi][i] = s;
+          if (s <= t[mi] && s < __builtin_inff() && gb < b_end && gb != selfb[mi])
+            mask |= 1ull << ((ni * MI + mi) * 4 + i);
+        }
+    }
+    // Rounds of: every lane puts its candidates into their rows' buckets (BCAP each; what finds no room waits for the
+    // next round, unless the row's worst kept score has passed it by then), every owner takes its bucket.  A list does
+    // not depend on the order it is offered its candidates in.
+    for (int rc = 0;; ++rc) {
+      if (mask != 0) {
+        if (rc > 0) {
+#pragma unroll
+          for (int mi = 0; mi < MI; ++mi) t[mi] = thr[wm * 64 + mi * 16 + lrow];
+        }
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+          for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const unsigned long long bit = 1ull << ((ni * MI + mi) * 4 + i);
+              if ((mask & bit) != 0) {
+                const int row = wm * 64 + mi * 16 + lrow;
+                if (!(acc[ni][mi][i] <= t[mi])) {
+                  mask &= ~bit;
+                } else {
+                  const int slot = atomicAdd(&bcnt[row], 1);
+                  if (slot < BCAP) {
+                    bucket[row * BCAP + slot] = Cand{acc[ni][mi][i], wn * 64 + ni * 16 + lq * 4 + i};
+                    mask &= ~bit;
+                  }
+                }
+              }
+            }
+        if (mask != 0) flag[rc & 1] = 1;
+      }
+      if (tid == 0) flag[(rc + 1) & 1] = 0;   // (last read before the previous round's second barrier)
+      lds_barrier();
+      if (owner) {
+        const int n = min(bcnt[tid], BCAP);
+        for (int e = 0; e < n; ++e) {
+          const Cand c = bucket[tid * BCAP + e];
+          offer(L + tid * k, k, c.s, b0 + c.i, ts, ti, tp);
+        }
+        thr[tid] = ts;
+      }
+      if (tid < TQ) bcnt[tid] = 0;
+      const int more = flag[rc & 1];
+      lds_barrier();   // the buckets are free (for the next round, or the next tile's operands); thr is visible
+      if (more == 0) break;
+    }
+  }
+
+  if (owner) {
+    Cand* o = cand + ((q0 + tid) * splits + split) * k;
+    for (int j = 0; j < k; ++j) o[j] = L[tid * k + j];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// merge: one wave per query
+__global__ __launch_bounds__(64) void knn_merge_kernel(const float* __restrict__ queries, const float* __restrict__ bank,
+                                                       const Cand* __restrict__ cand, int dim, int k, int splits,
+                                                       int metric, int64_t* __restrict__ idx, float* __restrict__ dist) {
+  __shared__ Cand pool[MAX_SPLITS * MAX_K];
+  __shared__ int win[MAX_K];
+  __shared__ float wdist[MAX_K];
+  const int lane = threadIdx.x;
+  const long q = blockIdx.x;
+  const float* x = queries + q * dim;
+  int64_t* oi = idx + q * k;
+  float* od = dist + q * k;
+
+  float xv[MAX_DIM / 64];
+  bool fin = true;
+  float qq = 0.f;
+#pragma unroll
+  for (int j = 0; j < MAX_DIM / 64; ++j) {
+    const int d = j * 64 + lane;
+    xv[j] = d < dim ? x[d] : 0.f;
+    fin = fin && fabsf(xv[j]) <= FLT_MAX;
+    qq = fmaf(xv[j], xv[j], qq);
+  }
+  qq = wave_sum(qq);
+  if (!__all(fin) || !(qq <= FLT_MAX)) {   // (the selection saw a zero image for this row)
+    if (lane < k) {
+      oi[lane] = -1;
+      od[lane] = __builtin_nanf("");
+    }
+    return;
+  }
+
+  const int P = splits * k;
+  for (int c = lane; c < P; c += 64) pool[c] = cand[q * P + c];
+  if (lane < MAX_K) win[lane] = EMPTY;
+  __syncthreads();
+  // the k best of the pool by (score, index): entries are distinct, so the ranks are too
+  for (int c = lane; c < P; c += 64) {
+    const Cand me = pool[c];
+    if (me.i == EMPTY) continue;
+    int rank = 0;
+    for (int e = 0; e < P; ++e) {
+      const Cand o = pool[e];
+      rank += before(o.s, o.i, me.s, me.i) ? 1 : 0;
+    }
+    if (rank < k) win[rank] = me.i;
+  }
+  __syncthreads();
+
+  // each winner's distance in the direct form, from the fp32 rows
+  int nwin = 0;
+  for (int j = 0; j < k; ++j) {
+    const int b = win[j];
+    if (b == EMPTY) break;   // (the ranks are dense: winners fill win[] from the front)
+    nwin = j + 1;
+    const float* y = bank + (long)b * dim;
+    float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < MAX_DIM / 64; ++jj) {
+      const int d = jj * 64 + lane;
+      if (d < dim) {
+        const float yv = y[d];
+        if (metric == 0) {
+          const float t = xv[jj] - yv;
+          a0 = fmaf(t, t, a0);
+        } else {
+          a0 = fmaf(xv[jj], yv, a0);
+          a1 = fmaf(yv, yv, a1);
+        }
+      }
+    }
+    a0 = wave_sum(a0);
+    float dj;
+    if (metric == 0) {
+      dj = sqrtf(a0);
+    } else {
+      a1 = wave_sum(a1);
+      const float c = qq > 0.f && a1 > 0.f ? (a0 / sqrtf(qq)) / sqrtf(a1) : 0.f;
+      dj = 1.f - c;
+    }
+    if (lane == 0) wdist[j] = dj;
+  }
+  __syncthreads();
+  if (lane < k) {
+    if (lane < nwin) {
+      const float d = wdist[lane];
+      const int b = win[lane];
+      int rank = 0;
+      for (int e = 0; e < nwin; ++e) rank += before(wdist[e], win[e], d, b) ? 1 : 0;
+      oi[rank] = b;
+      od[rank] = d;
+    } else {
+      oi[lane] = -1;
+      od[lane] = __builtin_inff();
+    }
+  }
+}
+
+int check_shape(const char* who, int64_t n_query, int64_t n_bank, int dim, int k) {
+  if (dim < 1 || dim > MAX_DIM || k < 1 || k > MAX_K || n_query < 0 || n_bank < 0 || n_bank > 0x7fffffffLL ||
+      n_query > 0x7fffffffLL) {
+    btsbot_set_error("%s: need 1 <= dim <= %d, 1 <= k <= %d, 0 <= n_bank, n_query < 2^31 (dim=%d k=%d n_bank=%lld "
+                     "n_query=%lld)", who, MAX_DIM, MAX_K, dim, k, (long long)n_bank, (long long)n_query);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  return BTSBOT_OK;
+}
+
+int auto_splits(int64_t n_query, int64_t n_bank) {
+  const int64_t qt = (n_query + TQ - 1) / TQ, bt = (n_bank + TB - 1) / TB;
+  if (qt < 1 || bt < 1) return 1;
+  // two workgroups per CU (256 CUs) where the bank has the tiles for it
+  int64_t s = (512 + qt - 1) / qt;
+  s = s > bt ? bt : s;
+  s = s > MAX_SPLITS ? MAX_SPLITS : s;
+  return (int)(s < 1 ? 1 : s);
+}
+
+size_t image_bytes(int64_t rows, int dim) { return ((size_t)rows * record_bytes(dim) + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" int64_t btsbot_knn_bank_bytes(int64_t n_bank, int dim) {
+  if (check_shape("btsbot_knn_bank_bytes", 0, n_bank, dim, 1) != BTSBOT_OK) return BTSBOT_ERR_INVALID_ARG;
+  return (int64_t)((size_t)n_bank * record_bytes(dim));
+}
+
+extern "C" int btsbot_knn_pack_bank(const float* rows, int64_t first_row, int64_t n_rows, int dim, int metric,
+                                    void* packed, int64_t n_bank_capacity, void* stream) {
+  const int s = check_shape("btsbot_knn_pack_bank", 0, n_bank_capacity, dim, 1);
+  if (s != BTSBOT_OK) return s;
+  if (metric != BTSBOT_KNN_EUCLIDEAN && metric != BTSBOT_KNN_COSINE) {
+    btsbot_set_error("btsbot_knn_pack_bank: metric %d", metric);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (first_row < 0 || n_rows < 0 || first_row > n_bank_capacity || n_rows > n_bank_capacity - first_row) {
+    btsbot_set_error("btsbot_knn_pack_bank: rows [%lld, %lld + %lld) do not fit a bank of %lld", (long long)first_row,
+                     (long long)first_row, (long long)n_rows, (long long)n_bank_capacity);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (n_rows == 0) return BTSBOT_OK;
+  if (rows == nullptr || packed == nullptr || ((uintptr_t)packed & 15) != 0) {
+    btsbot_set_error("btsbot_knn_pack_bank: NULL rows / packed, or packed not 16-byte aligned");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  unsigned char* out = reinterpret_cast<unsigned char*>(packed) + (size_t)first_row * record_bytes(dim);
+  hipLaunchKernelGGL(knn_pack_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, rows,
+                     (long)n_rows, dim, metric == BTSBOT_KNN_COSINE ? MODE_BANK_COS : MODE_BANK_L2, out);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+extern "C" int btsbot_knn_splits(int64_t n_query, int64_t n_bank, int dim, int k) {
+  const int s = check_shape("btsbot_knn_splits", n_query, n_bank, dim, k);
+  if (s != BTSBOT_OK) return s;
+  return auto_splits(n_query, n_bank);
+}
+
+extern "C" int64_t btsbot_knn_workspace(int64_t n_query, int64_t n_bank, int dim, int k, int splits) {
+  if (check_shape("btsbot_knn_workspace", n_query, n_bank, dim, k) != BTSBOT_OK) return BTSBOT_ERR_INVALID_ARG;
+  if (splits < 0 || splits > MAX_SPLITS) {
+    btsbot_set_error("btsbot_knn_workspace: splits=%d must be 0 (the library's choice) .. %d", splits, MAX_SPLITS);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (splits == 0) splits = auto_splits(n_query, n_bank);
+  return (int64_t)(image_bytes(n_query, dim) + (size_t)n_query * splits * k * sizeof(Cand));
+}
+
+extern "C" int btsbot_knn_query(const float* queries, int64_t n_query, const float* bank, const void* packed,
+                                int64_t n_bank, int dim, int k, int metric, int64_t self_offset, int splits,
+                                int64_t* idx, float* dist, void* workspace, int64_t workspace_bytes, void* stream) {
+  const int s = check_shape("btsbot_knn_query", n_query, n_bank, dim, k);
+  if (s != BTSBOT_OK) return s;
+  if (metric != BTSBOT_KNN_EUCLIDEAN && metric != BTSBOT_KNN_COSINE) {
+    btsbot_set_error("btsbot_knn_query: metric %d", metric);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (splits < 0 || splits > MAX_SPLITS) {
+    btsbot_set_error("btsbot_knn_query: splits=%d must be 0 (the library's choice) .. %d", splits, MAX_SPLITS);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (n_query == 0) return BTSBOT_OK;
+  if (splits == 0) splits = auto_splits(n_query, n_bank);
+  const int64_t need = btsbot_knn_workspace(n_query, n_bank, dim, k, splits);
+  if (queries == nullptr || idx == nullptr || dist == nullptr || workspace == nullptr ||
+      (n_bank > 0 && (bank == nullptr || packed == nullptr))) {
+    btsbot_set_error("btsbot_knn_query: NULL argument");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (workspace_bytes < need || ((uintptr_t)workspace & 15) != 0 || ((uintptr_t)packed & 15) != 0) {
+    btsbot_set_error("btsbot_knn_query: workspace of %lld bytes (need %lld), or workspace / packed not 16-byte aligned",
+                     (long long)workspace_bytes, (long long)need);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* qimg = reinterpret_cast<unsigned char*>(workspace);
+  Cand* cand = reinterpret_cast<Cand*>(qimg + image_bytes(n_query, dim));
+  hipLaunchKernelGGL(knn_pack_kernel, dim3((unsigned)((n_query + 3) / 4)), dim3(256), 0, st, queries, (long)n_query, dim,
+                     (int)MODE_QUERY, qimg);
+  LAUNCH_CHECK();
+
+  const int total_tiles = (int)((n_bank + TB - 1) / TB);
+  const int tps = (total_tiles + splits - 1) / splits;
+  // 64 KB of operands + 1 KB of lists per k: two workgroups per CU up to k = 16
+  static DevOnce attr;
+  if (attr.need()) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_select_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS + TQ * MAX_K * (int)sizeof(Cand)));
+    attr.done();
+  }
+  hipLaunchKernelGGL(knn_select_kernel, dim3((unsigned)((n_query + TQ - 1) / TQ), (unsigned)splits), dim3(256),
+                     GEMM_LDS + TQ * k * (int)sizeof(Cand), st, qimg, reinterpret_cast<const unsigned char*>(packed),
+                     (long)n_query, (int)n_bank, dim, k, (long)self_offset, tps, splits, cand);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)n_query), dim3(64), 0, st, queries, bank, cand, dim, k, splits,
+                     metric, idx, dist);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}

@@ -319,7 +319,10 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
     ``model_dir/best_model.pth`` into ``model``, embed every alert of the test split -- of the validation split when
     there are no test files -- through ``ScoreStream(embed=layer)`` and write ``{stem}.npy`` (fp32 [N, width], rows in
     the candidate file's order) and, when that file has a ``candid`` column, ``{stem}.csv`` with it.  The 2-D
-    projection the reference makes of these rows (UMAP) is the caller's business.  Returns the .npy path."""
+    projection the reference makes of these rows (UMAP) is the caller's business.  With ``config['embedding_neighbors']
+    = k`` also ``{stem}_knn.npz``: ``indices`` int64 [N, k] and ``distances`` fp32 [N, k] of ``knn_graph(rows, k,
+    include_self=True)`` (the layout umap-learn's ``precomputed_knn`` takes) and ``candid`` where the table has it.
+    Returns the .npy path."""
     import numpy as np
     from .data import load_split
     from .pipeline import ScoreStream
@@ -341,6 +344,12 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
     np.save(stem + ".npy", out)
     if "candid" in cand.columns:
         cand[["candid"]].to_csv(stem + ".csv", index=False)
+    k = config.get("embedding_neighbors")
+    if k:   # opt-in: the neighbour search get_torch_embedding runs in front of its UMAP layout
+        from .neighbors import knn_graph
+        idx, dist = knn_graph(torch.from_numpy(out).to(dev), int(k), include_self=True)
+        extra = {"candid": cand["candid"].to_numpy()} if "candid" in cand.columns else {}
+        np.savez(stem + "_knn.npz", indices=idx.cpu().numpy(), distances=dist.cpu().numpy(), **extra)
     return stem + ".npy"
 
 

@@ -819,6 +819,43 @@ int btsbot_feature_load(const btsbot_feature_table* table, int n_records, const 
 int btsbot_feature_rehash(const btsbot_feature_table* src, const btsbot_feature_table* dst, double keep_from_jd,
                           void* stream);
 
+/* ---- embedding neighbours: exact brute-force k-nearest rows of a bank (csrc/knn.hip) ---- */
+
+/* Replaces: the neighbour search of the embedding step (train.py:449-469, get_torch_embedding).  queries fp32
+ * [n_query][dim], bank fp32 [n_bank][dim], row-contiguous device memory; 1 <= dim <= 1024, 1 <= k <= 64, n_bank and
+ * n_query < 2^31 -- BTSBOT_ERR_INVALID_ARG with a message, before any HIP call, otherwise (also: an unknown metric,
+ * splits outside 0..32, a NULL or misaligned pointer, a workspace that is too small).
+ *
+ * The bank is searched through a PACKED image the caller owns: btsbot_knn_bank_bytes(n_bank, dim) bytes, 16-byte
+ * aligned, one record of 16 + 4 * ceil(dim / 32) * 32 bytes per row (bias, scale, the row scaled by a power of two of its
+ * own as f16 head and remainder planes), so the image of rows [0, n) is a prefix of the image of any larger bank and may
+ * be copied into a larger buffer as bytes.  btsbot_knn_pack_bank() writes the records of rows [first_row, first_row +
+ * n_rows) from `rows` (the fp32 rows themselves, [n_rows][dim]) into `packed`, whose capacity in rows is
+ * n_bank_capacity; a record depends on its row and the metric only.  One launch on `stream`.
+ *
+ * btsbot_knn_query(): idx int64 [n_query][k], dist fp32 [n_query][k] = each query's k nearest bank rows, ascending by
+ * (dist as returned, bank index).  dist: BTSBOT_KNN_EUCLIDEAN the Euclidean distance (not squared), BTSBOT_KNN_COSINE
+ * 1 - cos (cos = 0 where a row's norm is 0); both recomputed for the rows returned in the direct form from the fp32
+ * rows (`bank` must be the rows `packed` was made from, packed for the same metric).  A bank row that holds a non-finite
+ * value (or whose squared norm is not finite in fp32) is never returned; a query row that does gets idx = -1, dist = NaN
+ * throughout; where fewer than k rows are eligible the tail is idx = -1, dist = +inf.  self_offset < 0: no exclusion;
+ * otherwise query row i IS bank row i + self_offset and that one row is not a candidate (by position: duplicates are).
+ * The candidates are the k best by (selection score, bank index), the score being |b|^2 - 2 q.b (cosine: -q.b / |b|) on
+ * split f16 operands with fp32 accumulation (an fp32-class product); splits = how many slices of the bank a query tile
+ * is searched in by separate workgroups, 0 = btsbot_knn_splits()'s choice.  A row's answer is bit for bit independent
+ * of splits, of the other rows of the call and of the run.  workspace: btsbot_knn_workspace(...) bytes for the same
+ * arguments, 16-byte aligned, the caller's; scratch afterwards.  Three launches on `stream`; nothing allocates,
+ * synchronises or copies to the host, nothing of size n_query x n_bank is written; n_query == 0 launches nothing. */
+enum btsbot_knn_metric { BTSBOT_KNN_EUCLIDEAN = 0, BTSBOT_KNN_COSINE = 1 };
+int64_t btsbot_knn_bank_bytes(int64_t n_bank, int dim);
+int btsbot_knn_pack_bank(const float* rows, int64_t first_row, int64_t n_rows, int dim, int metric, void* packed,
+                         int64_t n_bank_capacity, void* stream);
+int btsbot_knn_splits(int64_t n_query, int64_t n_bank, int dim, int k);
+int64_t btsbot_knn_workspace(int64_t n_query, int64_t n_bank, int dim, int k, int splits);
+int btsbot_knn_query(const float* queries, int64_t n_query, const float* bank, const void* packed, int64_t n_bank,
+                     int dim, int k, int metric, int64_t self_offset, int splits, int64_t* idx, float* dist,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Replaces: the epoch / validation metrics of val.py:159-168 and train.py:550-558 -- out2[0] += sum_i of
  * BCEWithLogitsLoss(pos_weight) terms over n logits, out2[1] += number of alerts whose sigmoid(z) > 0.5
  * agrees with the label (caller zeroes out2 and divides by n). */

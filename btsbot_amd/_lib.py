@@ -49,7 +49,10 @@ SYMBOLS = [
     "btsbot_trigger_rehash", "btsbot_feature_reset", "btsbot_feature_update", "btsbot_feature_load", "btsbot_feature_rehash",
     "btsbot_embed_width", "btsbot_forward_embed",
     "btsbot_knn_bank_bytes", "btsbot_knn_pack_bank", "btsbot_knn_splits", "btsbot_knn_workspace", "btsbot_knn_query",
+    "btsbot_layout_smooth_knn", "btsbot_layout_symmetrize_workspace", "btsbot_layout_symmetrize", "btsbot_layout_init",
+    "btsbot_layout_epochs",
 ]
+LAYOUT_MAX_K, LAYOUT_MAX_NEGATIVES = 64, 64
 KNN_METRIC = {"euclidean": 0, "cosine": 1}   # enum btsbot_knn_metric
 KNN_MAX_DIM, KNN_MAX_K, KNN_MAX_SPLITS = 1024, 64, 32
 EMBEDDING = {"features": 0, "hidden": 1}   # enum btsbot_embedding
@@ -273,6 +276,16 @@ def lib() -> C.CDLL:
     L.btsbot_knn_workspace.argtypes = [i64, i64, i32, i32, i32]
     L.btsbot_knn_query.restype = i32
     L.btsbot_knn_query.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, i64, i32, vp, vp, vp, i64, vp]
+    L.btsbot_layout_smooth_knn.restype = i32
+    L.btsbot_layout_smooth_knn.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp]
+    L.btsbot_layout_symmetrize_workspace.restype = i64
+    L.btsbot_layout_symmetrize_workspace.argtypes = [i64, i32]
+    L.btsbot_layout_symmetrize.restype = i32
+    L.btsbot_layout_symmetrize.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp, i64, vp]
+    L.btsbot_layout_init.restype = i32
+    L.btsbot_layout_init.argtypes = [vp, i64, C.c_uint64, i32, vp]
+    L.btsbot_layout_epochs.restype = i32
+    L.btsbot_layout_epochs.argtypes = [vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, f32, f32, C.c_uint64, i32, f32, i32, vp]
     L.btsbot_eval_metrics.restype = i32
     L.btsbot_eval_metrics.argtypes = [vp, vp, f32, i64, vp, vp]
     if L.btsbot_abi_version() != ABI_VERSION:

@@ -318,11 +318,12 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
     """The embedding step at the end of a run (train.py:449-469, whose helper module the reference does not ship): load
     ``model_dir/best_model.pth`` into ``model``, embed every alert of the test split -- of the validation split when
     there are no test files -- through ``ScoreStream(embed=layer)`` and write ``{stem}.npy`` (fp32 [N, width], rows in
-    the candidate file's order) and, when that file has a ``candid`` column, ``{stem}.csv`` with it.  The 2-D
-    projection the reference makes of these rows (UMAP) is the caller's business.  With ``config['embedding_neighbors']
-    = k`` also ``{stem}_knn.npz``: ``indices`` int64 [N, k] and ``distances`` fp32 [N, k] of ``knn_graph(rows, k,
+    the candidate file's order) and, when that file has a ``candid`` column, ``{stem}.csv`` with it.  With
+    ``config['embedding_neighbors'] = k`` also ``{stem}_knn.npz``: ``indices`` int64 [N, k] and ``distances`` fp32 [N, k] of ``knn_graph(rows, k,
     include_self=True)`` (the layout umap-learn's ``precomputed_knn`` takes) and ``candid`` where the table has it.
-    Returns the .npy path."""
+    With ``config['embedding_layout']`` (``True``, or a dict of ``embedding_layout`` keyword arguments; ``seed`` defaults
+    to the run's ``random_seed``) also ``{stem}_umap.csv`` with the reference's columns ``umap_emb_1, umap_emb_2,
+    candid`` (train.py:464): the 2-D map of the rows, in the candidate file's order.  Returns the .npy path."""
     import numpy as np
     from .data import load_split
     from .pipeline import ScoreStream
@@ -350,6 +351,17 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
         idx, dist = knn_graph(torch.from_numpy(out).to(dev), int(k), include_self=True)
         extra = {"candid": cand["candid"].to_numpy()} if "candid" in cand.columns else {}
         np.savez(stem + "_knn.npz", indices=idx.cpu().numpy(), distances=dist.cpu().numpy(), **extra)
+    lay = config.get("embedding_layout")
+    if lay:   # opt-in: the UMAP map itself, with the reference's columns (train.py:464)
+        import pandas as pd
+        from .layout import embedding_layout
+        kw = dict(lay) if isinstance(lay, dict) else {}
+        kw.setdefault("seed", int(config.get("random_seed", 0)))
+        y = embedding_layout(torch.from_numpy(out).to(dev), **kw).cpu().numpy()
+        table = {"umap_emb_1": y[:, 0], "umap_emb_2": y[:, 1]}
+        if "candid" in cand.columns:
+            table["candid"] = cand["candid"].to_numpy()
+        pd.DataFrame(table).to_csv(stem + "_umap.csv", index=False)
     return stem + ".npy"
 
 

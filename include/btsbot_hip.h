@@ -856,6 +856,50 @@ int btsbot_knn_query(const float* queries, int64_t n_query, const float* bank, c
                      int dim, int k, int metric, int64_t self_offset, int splits, int64_t* idx, float* dist,
                      void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- embedding layout: a deterministic UMAP map of the kNN graph (csrc/layout.hip) ---- */
+
+/* Replaces: the UMAP layout of the embedding step (train.py:449-469, the umap_emb_1 / umap_emb_2 columns).  Everything
+ * is queued on `stream`; nothing allocates, synchronises or copies to the host.  BTSBOT_ERR_INVALID_ARG for a NULL
+ * pointer, k outside 2..64, 2 n k >= 2^31, a short or misaligned (256 bytes) workspace, an epoch range outside
+ * 1 <= first <= last <= n_epochs, negative_sample_rate outside 0..64.
+ *
+ * btsbot_layout_smooth_knn(): idx int64 [n][k], dist fp32 [n][k] as btsbot_knn_query returns them with the row itself
+ * in column 0 (knn_graph(..., include_self=True)); entries with idx < 0 are absent.  Writes rho [n] (the row's smallest
+ * positive distance over columns 1.., or 0), sigma [n] (umap-learn's smooth_knn_dist bisection with local_connectivity
+ * = bandwidth = 1: at most 64 trips towards sum_j exp(-max(d_j - rho, 0) / sigma) = log2 k, floored at 1e-3 times the
+ * row's mean distance -- of *mean_all, a DEVICE double the caller sets to the mean of all present distances, where rho
+ * is 0; searched in float64, rounded to fp32 once) and memb [n][k], the memberships a_ij = exp(-max(d - rho, 0) /
+ * sigma), 0 in column 0 and for an absent, out-of-range or self entry.  One wave per row, one launch.
+ *
+ * btsbot_layout_symmetrize(): the symmetric CSR graph of those memberships, w_ij = (a_ij + a_ji) - a_ij a_ji in fp32
+ * (a missing direction counts 0), bitwise equal in both slots of an edge.  indptr int64 [n + 1]; indices int32 and
+ * weights fp32 hold 2 n (k - 1) slots of which the first indptr[n] are written, columns ascending inside a row; *w_max
+ * (device) receives the largest weight.  A row must not name a neighbour twice.  workspace:
+ * btsbot_layout_symmetrize_workspace(n, k) bytes.  Three kernels, one radix sort, one scan.
+ *
+ * btsbot_layout_init(): y fp32 [n][2].  mode 0: uniform in [-10, 10); mode 1: adds a jitter in +-1e-4 to what y holds.
+ * Both from the counter hash of (seed, epoch 0, vertex, coordinate).
+ *
+ * btsbot_layout_epochs(): epochs first_epoch..last_epoch of an n_epochs schedule, one launch each.  The first epoch
+ * reads y_a and writes y_b, the next reads y_b and writes y_a, ...: the result is in y_b after an odd number of epochs,
+ * in y_a after an even one.  Epoch e: a slot with r = fp32(w / w_max) fires iff floor(e r) > floor((e - 1) r) (float64);
+ * a firing slot (v, u) adds to v the attractive term 2 clip(-2ab d^(2(b-1)) / (1 + a d^(2b)) (y_v - y_u), +-4) and
+ * negative_sample_rate repulsive terms clip(2b / ((0.001 + d^2)(1 + a d^(2b))) (y_v - y_t), +-4), t = the high word of
+ * (hash >> 32) * n, hash = the splitmix64 counter hash of (seed, e, slot, sample); t == v or a non-finite y_t adds
+ * nothing, d = 0 adds 0 (attractive) or +4 per coordinate (repulsive).  y_new = y_old + learning_rate (1 - (e - 1) /
+ * n_epochs) * sum.  A vertex is written by its own eight lanes in an order fixed by its row: bit for bit reproducible,
+ * whatever `blocks` (the grid; 0 = the library's choice). */
+int btsbot_layout_smooth_knn(const int64_t* idx, const float* dist, int64_t n, int k, const double* mean_all,
+                             float* sigma, float* rho, float* memb, void* stream);
+int64_t btsbot_layout_symmetrize_workspace(int64_t n, int k);
+int btsbot_layout_symmetrize(const int64_t* idx, const float* memb, int64_t n, int k, int64_t* indptr, int32_t* indices,
+                             float* weights, float* w_max, void* workspace, int64_t workspace_bytes, void* stream);
+int btsbot_layout_init(float* y, int64_t n, uint64_t seed, int mode, void* stream);
+int btsbot_layout_epochs(const int64_t* indptr, const int32_t* indices, const float* weights, const float* w_max,
+                         int64_t n, float* y_a, float* y_b, int n_epochs, int first_epoch, int last_epoch, float a,
+                         float b, uint64_t seed, int negative_sample_rate, float learning_rate, int blocks,
+                         void* stream);
+
 /* Replaces: the epoch / validation metrics of val.py:159-168 and train.py:550-558 -- out2[0] += sum_i of
  * BCEWithLogitsLoss(pos_weight) terms over n logits, out2[1] += number of alerts whose sigmoid(z) > 0.5
  * agrees with the label (caller zeroes out2 and divides by n). */

@@ -239,9 +239,11 @@ def prep_triplets(raw: torch.Tensor, shapes: Optional[torch.Tensor] = None,
 # the columns of alert_features(), in its output order
 CUSTOM_COLS = ("peakmag", "maxmag", "peakmag_so_far", "maxmag_so_far", "age", "days_since_peak", "days_to_peak",
                "nnotdet")
-# alerts per LDS tile of btsbot_alert_features (TILE in csrc/alert_features.hip): objects of up to 64 alerts take one
-# wave, up to FEATURE_TILE one workgroup with the object resident in LDS, larger ones stream through the tile
-FEATURE_TILE = 1024
+# alerts per LDS tile of the per-object kernels btsbot_alert_features, btsbot_split_labels and btsbot_policy_eval (TILE in
+# csrc/object_walk.h): objects of up to 64 alerts take one wave, up to OBJECT_TILE one workgroup with the object
+# resident in LDS, larger ones stream through the tile
+OBJECT_TILE = 1024
+FEATURE_TILE = OBJECT_TILE
 _FEATURE_INPUTS = ("jd", "magpsf", "jdstarthist", "ncovhist", "ndethist")
 
 
@@ -265,6 +267,36 @@ def _group_by_object(object_id: torch.Tensor,
     return perm.to(torch.int32), offsets.to(torch.int32)
 
 
+def _check_table(where: str, object_id: torch.Tensor, **cols) -> int:
+    """The number of alerts n, after the checks every per-object wrapper makes: object_id on the GPU (``where`` names
+    the caller, ``module.function``), one-dimensional and of an integer type, every column (None: absent) of shape [n]."""
+    if object_id.device.type != "cuda":
+        raise RuntimeError(f"btsbot_amd.{where} runs on the GPU; there is no CPU fallback (object_id is on "
+                           f"{object_id.device})")
+    if object_id.dim() != 1:
+        raise ValueError(f"object_id must be one-dimensional, got {tuple(object_id.shape)}")
+    n = object_id.shape[0]
+    for name, t in cols.items():
+        if t is not None and (t.dim() != 1 or t.shape[0] != n):
+            raise ValueError(f"{name} must be [{n}], got {tuple(t.shape)}")
+    if object_id.dtype.is_floating_point or object_id.dtype == torch.bool:
+        raise ValueError(f"object_id must be an integer tensor, got {object_id.dtype}")
+    return n
+
+
+def _launch_grouped(symbol: str, grouping: Tuple[torch.Tensor, torch.Tensor], n: int, *args) -> None:
+    """One launch of a per-object kernel (csrc/object_walk.h) on the current stream of the grouping's device:
+    ``symbol(perm, seg_offsets, n, n, *args, stream)`` with ``grouping`` = ``_group_by_object``'s result -- n alerts in n
+    possibly empty objects.  Tensors among ``args`` go as their device pointers.  No host synchronisation."""
+    def ptr(a):
+        return C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a
+
+    dev = grouping[0].device
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(getattr(_lib.lib(), symbol)(*map(ptr, grouping), n, n, *map(ptr, args), C.c_void_p(st)), symbol)
+
+
 def alert_features(object_id: torch.Tensor, jd: torch.Tensor, magpsf: torch.Tensor, jdstarthist: torch.Tensor,
                    ncovhist: torch.Tensor, ndethist: torch.Tensor) -> torch.Tensor:
     """CUSTOM_COLS of N alerts as float32 [N, 8] on the inputs' device, rows in input order.
@@ -276,30 +308,15 @@ def alert_features(object_id: torch.Tensor, jd: torch.Tensor, magpsf: torch.Tens
     earliest alert of P(i) at peakmag_so_far; nnotdet = ncovhist - ndethist.  NaN magpsf are skipped (all NaN: NaN); a
     NaN jdstarthist gives NaN age and days_to_peak.  jd must be finite (not checked: that would be a host sync).
     Everything is compared and subtracted in float64 and rounded to float32 once.  No host synchronisation."""
-    if object_id.device.type != "cuda":
-        raise RuntimeError("btsbot_amd.alert_utils.alert_features runs on the GPU; there is no CPU "
-                           f"fallback (object_id is on {object_id.device})")
+    n = _check_table("alert_utils.alert_features", object_id, jd=jd, magpsf=magpsf, jdstarthist=jdstarthist,
+                     ncovhist=ncovhist, ndethist=ndethist)
     dev = object_id.device
-    n = object_id.shape[0]
-    cols = (jd, magpsf, jdstarthist, ncovhist, ndethist)
-    for name, t in zip(("object_id",) + _FEATURE_INPUTS, (object_id,) + cols):
-        if t.dim() != 1 or t.shape[0] != n:
-            raise ValueError(f"{name} must be [{n}], got {tuple(t.shape)}")
-    if object_id.dtype.is_floating_point or object_id.dtype == torch.bool:
-        raise ValueError(f"object_id must be an integer tensor, got {object_id.dtype}")
-    jd, magpsf, jdstarthist = (t.to(device=dev, dtype=torch.float64).contiguous() for t in cols[:3])
-    ncovhist, ndethist = (t.to(device=dev, dtype=torch.int32).contiguous() for t in cols[3:])
+    jd, magpsf, jdstarthist = (t.to(device=dev, dtype=torch.float64).contiguous() for t in (jd, magpsf, jdstarthist))
+    ncovhist, ndethist = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (ncovhist, ndethist))
     out = torch.empty((n, 8), dtype=torch.float32, device=dev)
-    if n == 0:
-        return out
-    perm, offsets = _group_by_object(object_id)
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(_lib.lib().btsbot_alert_features(
-            C.c_void_p(perm.data_ptr()), C.c_void_p(offsets.data_ptr()), n, n,
-            C.c_void_p(jd.data_ptr()), C.c_void_p(magpsf.data_ptr()), C.c_void_p(jdstarthist.data_ptr()),
-            C.c_void_p(ncovhist.data_ptr()), C.c_void_p(ndethist.data_ptr()), C.c_void_p(out.data_ptr()),
-            C.c_void_p(st)), "btsbot_alert_features")
+    if n:
+        _launch_grouped("btsbot_alert_features", _group_by_object(object_id), n,
+                        jd, magpsf, jdstarthist, ncovhist, ndethist, out)
     return out
 
 

@@ -18,7 +18,6 @@
 
 namespace {
 
-using object_walk::OBJ_PER_WG;
 using object_walk::WG;
 
 struct Inputs {
@@ -82,22 +81,18 @@ __global__ __launch_bounds__(WG) void alert_features_kernel(Inputs in, const int
 extern "C" int btsbot_alert_features(const int32_t* perm, const int32_t* seg_offsets, int n_alerts, int n_objects,
                                      const double* jd, const double* magpsf, const double* jdstarthist,
                                      const int32_t* ncovhist, const int32_t* ndethist, float* out8, void* stream) {
-  if (perm == nullptr || seg_offsets == nullptr || jd == nullptr || magpsf == nullptr || jdstarthist == nullptr ||
-      ncovhist == nullptr || ndethist == nullptr || out8 == nullptr || n_alerts < 0 || n_objects < 0) {
-    btsbot_set_error("alert_features: NULL argument or negative n_alerts / n_objects");
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if (n_alerts == 0) return BTSBOT_OK;
-  if (((uintptr_t)out8 & 15) != 0) {
+  TRY(object_walk::check_args("alert_features",
+                              perm != nullptr && seg_offsets != nullptr && jd != nullptr && magpsf != nullptr &&
+                                  jdstarthist != nullptr && ncovhist != nullptr && ndethist != nullptr && out8 != nullptr,
+                              n_alerts, n_objects));
+  if (n_alerts > 0 && ((uintptr_t)out8 & 15) != 0) {   // (an empty batch returns BTSBOT_OK whatever out8 is)
     btsbot_set_error("alert_features: out8 must be 16-byte aligned");
     return BTSBOT_ERR_INVALID_ARG;
   }
-  if (n_objects == 0) {
-    btsbot_set_error("alert_features: %d alerts in 0 objects", n_alerts);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
+  unsigned blocks;
+  TRY(object_walk::grid("alert_features", n_alerts, n_objects, &blocks));
+  if (blocks == 0) return BTSBOT_OK;
   const Inputs in{perm, jd, magpsf, jdstarthist, ncovhist, ndethist, out8, n_alerts};
-  const unsigned blocks = (unsigned)(((long)n_objects + OBJ_PER_WG - 1) / OBJ_PER_WG);
   hipLaunchKernelGGL(alert_features_kernel, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, in, seg_offsets,
                      n_objects);
   LAUNCH_CHECK();

@@ -11,27 +11,23 @@
 // obj_info keeps what the object filter and the peak-magnitude bins need: the number of alerts, the label of the
 // first alert in input order, min magpsf over O (NaN: no magnitude at all).
 //
-// Every alert counts over the alerts of its own object -- n^2 compare-and-selects per object, the valid bits of up to
-// 16 policies riding along as one mask per alert; no sort, no atomics, one writer per output element.  The earliest
-// firing alert is a (jd, index) min-reduction: per thread over its own alerts, across lanes with shuffles, across the
-// four waves through LDS.  A workgroup of four waves owns four consecutive objects and picks a form per object:
-//   n <= 64         one wave, one alert per lane; the object's (jd, magpsf, index, mask) go round as readlane broadcasts
-//   n <= TILE       the workgroup stages the object in LDS once; each thread counts its alerts over the tile (every lane
-//                   reads the same LDS address: a broadcast, no bank conflicts)
-//   n >  TILE       the same inner loop, 256 alerts at a time, the object streamed through the LDS tile once per batch
-// The three forms run the same take() on the same (jd, index) order, so they give identical results.
+// Every alert counts over the alerts of its own object in the three forms of object_walk.h (one wave; the object
+// resident in LDS; the object streamed through the LDS tile), the valid bits of up to 16 policies riding along as the
+// walk's payload word: one mask per alert.  The result is per object, so the walk runs with a reducer: the earliest
+// firing alert is a (jd, index) min-reduction -- per thread over its own alerts, across lanes with shuffles, across the
+// four waves through LDS -- beside a running min magpsf over the object.
 //
 // LDS per workgroup: 1024 x (8 + 8 + 4 + 4) B tile + 4 x 16 x (8 + 4) B of wave minima = 25,344 B, so six workgroups
 // (24 waves) fit the 160 KiB of a CU.
-#include "common.h"
+#include "object_walk.h"
 
 #include <climits>
 #include <cmath>
 
 namespace {
 
-constexpr int TILE = 1024;   // alerts per LDS tile (val.POLICY_TILE)
-constexpr int WG = 256, OBJ_PER_WG = WG / 64;
+using object_walk::OBJ_PER_WG;
+using object_walk::WG;
 constexpr int MAXP = 16;     // policies per launch
 
 struct Policies {
@@ -40,7 +36,7 @@ struct Policies {
   int n;
 };
 
-struct Inputs {
+struct Args {
   const int32_t* perm;
   const double* jd;
   const double* mag;
@@ -50,6 +46,21 @@ struct Inputs {
   double* trig;
   double* info;
   int n_alerts;
+  Policies pol;
+};
+
+// the walk's inputs for a kernel of up to NP policies: every alert carries the mask of the policies it is valid for (an
+// invalid slot: 0, it changes no count and never fires)
+template <int NP>
+struct Inputs : Args {
+  using Word = unsigned;
+  __device__ __forceinline__ Word word(int a, double amag) const {
+    const double score = (double)raw[a];
+    Word mask = 0;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) mask |= (unsigned)(q < pol.n && score > pol.thr[q] && amag < pol.cut[q]) << q;
+    return mask;
+  }
 };
 
 // what one alert knows about the alerts of its object up to and including itself
@@ -72,31 +83,57 @@ struct Acc {
   }
 };
 
-// the (jd, index)-earliest alert seen firing so far, per policy; a == INT_MAX: none
+__device__ __forceinline__ void store_policy(const Args& in, long obj, int q, double bjd, int ba) {
+  const bool fired = ba != INT_MAX;
+  const long e = obj * in.pol.n + q;
+  in.pred[e] = fired ? 1 : 0;
+  in.trig[2 * e] = fired ? bjd : -1.0;
+  in.trig[2 * e + 1] = fired ? in.mag[ba] : -1.0;
+}
+
+// n alerts starting at grouped position s: (n, label of the first alert in input order, min magpsf)
+__device__ __forceinline__ void store_info(const Args& in, long obj, int s, int n, double lo) {
+  double lab = -1.0;
+  if (n > 0) {
+    const int a = in.perm[s];   // the stable grouping keeps input order: the run's head is the first alert
+    if ((unsigned)a < (unsigned)in.n_alerts) lab = (double)in.label[a];
+  }
+  in.info[3 * obj] = (double)n;
+  in.info[3 * obj + 1] = lab;
+  in.info[3 * obj + 2] = lo;
+}
+
+// the walk's reducer: the (jd, index)-earliest alert seen firing so far, per policy (a == INT_MAX: none), and min
+// magpsf over the object
 template <int NP>
 struct Best {
   double jd[NP];
   int a[NP];
+  double lo;
   __device__ void init() {
+    lo = __builtin_nan("");
+    // lo stays in vector registers: in the one-wave form it is uniform, and for a scalar pair hipcc 7.2 can emit the NaN
+    // as one s_mov_b64 with a 64-bit literal, which gfx950 cannot encode -- the object file then holds its low half, 0
+    asm volatile("" : "+v"(lo));
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
       jd[q] = __builtin_inf();
       a[q] = INT_MAX;
     }
   }
+  __device__ __forceinline__ void slot(double, double kmag, int) { lo = (kmag == kmag && !(lo <= kmag)) ? kmag : lo; }
   __device__ __forceinline__ void offer(int q, double ojd, int oa) {
     if (oa != INT_MAX && (a[q] == INT_MAX || ojd < jd[q] || (ojd == jd[q] && oa < a[q]))) {
       jd[q] = ojd;
       a[q] = oa;
     }
   }
-  // an own alert whose counts are complete
-  __device__ __forceinline__ void alert_done(const Policies& pol, const Acc<NP>& c, double myjd, int mya) {
+  __device__ __forceinline__ void alert_done(const Inputs<NP>& in, const Acc<NP>& c, double myjd, int mya) {
     if (mya < 0) return;
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
-      const double g = pol.gate[q];
-      if (q < pol.n && c.cnt[q] >= pol.k[q] && (g != g || c.sp <= g)) offer(q, myjd, mya);
+      const double g = in.pol.gate[q];
+      if (q < in.pol.n && c.cnt[q] >= in.pol.k[q] && (g != g || c.sp <= g)) offer(q, myjd, mya);
     }
   }
   __device__ __forceinline__ void wave_min() {   // afterwards every lane holds the wave's earliest
@@ -110,181 +147,31 @@ struct Best {
       }
     }
   }
-};
-
-__device__ __forceinline__ void store_policy(const Inputs& in, const Policies& pol, long obj, int q, double bjd, int ba) {
-  const bool fired = ba != INT_MAX;
-  const long e = obj * pol.n + q;
-  in.pred[e] = fired ? 1 : 0;
-  in.trig[2 * e] = fired ? bjd : -1.0;
-  in.trig[2 * e + 1] = fired ? in.mag[ba] : -1.0;
-}
-
-// n alerts starting at grouped position s: (n, label of the first alert in input order, min magpsf)
-__device__ __forceinline__ void store_info(const Inputs& in, long obj, int s, int n, double lo) {
-  double lab = -1.0;
-  if (n > 0) {
-    const int a = in.perm[s];   // the stable grouping keeps input order: the run's head is the first alert
-    if ((unsigned)a < (unsigned)in.n_alerts) lab = (double)in.label[a];
-  }
-  in.info[3 * obj] = (double)n;
-  in.info[3 * obj + 1] = lab;
-  in.info[3 * obj + 2] = lo;
-}
-
-// alert p of the grouped order: its index (-1: p is outside the object, or perm holds no valid alert there), jd, magpsf
-// and the mask of the policies it is valid for.  An invalid slot reads as (jd = +inf, magpsf = NaN, mask = 0): it changes
-// no count and never fires.
-template <int NP>
-__device__ __forceinline__ int load_alert(const Inputs& in, const Policies& pol, int p, bool inside, double& jd,
-                                          double& mag, unsigned& mask) {
-  int a = -1;
-  jd = __builtin_inf();
-  mag = __builtin_nan("");
-  mask = 0;
-  if (inside) {
-    a = in.perm[p];
-    if ((unsigned)a < (unsigned)in.n_alerts) {
-      jd = in.jd[a];
-      mag = in.mag[a];
-      const double score = (double)in.raw[a];
+  __device__ __forceinline__ void finish_wave(const Inputs<NP>& in, long obj, int s, int n) {
+    wave_min();
+    if ((threadIdx.x & 63) == 0) {
 #pragma unroll
       for (int q = 0; q < NP; ++q)
-        mask |= (unsigned)(q < pol.n && score > pol.thr[q] && mag < pol.cut[q]) << q;
-    } else {
-      a = -1;
+        if (q < in.pol.n) store_policy(in, obj, q, jd[q], a[q]);
+      store_info(in, obj, s, n, lo);
     }
   }
-  return a;
-}
-
-template <int NP>
-__global__ __launch_bounds__(WG) void policy_eval_kernel(Inputs in, Policies pol, const int32_t* __restrict__ seg_offsets,
-                                                         int n_objects) {
-  __shared__ double s_jd[TILE], s_mag[TILE];
-  __shared__ int s_a[TILE];
-  __shared__ unsigned s_mask[TILE];
-  __shared__ double s_bjd[OBJ_PER_WG][MAXP];
-  __shared__ int s_ba[OBJ_PER_WG][MAXP];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long obj0 = (long)blockIdx.x * OBJ_PER_WG;
-
-  // the five offsets of this workgroup's objects (objects past n_objects: empty), clamped to the batch
-  int off[OBJ_PER_WG + 1];
-#pragma unroll
-  for (int q = 0; q <= OBJ_PER_WG; ++q) {
-    const long o = obj0 + q < n_objects ? obj0 + q : n_objects;
-    const int v = seg_offsets[o];
-    off[q] = v < 0 ? 0 : v > in.n_alerts ? in.n_alerts : v;
-  }
-
-  // ---- one wave per object, n <= 64 (n == 0: an empty object still gets its "never" row)
-  {
-    int s = off[0], e = off[1];
-#pragma unroll
-    for (int q = 1; q < OBJ_PER_WG; ++q)
-      if (wave == q) { s = off[q]; e = off[q + 1]; }
-    const int n = e - s;
-    if (obj0 + wave < n_objects && n >= 0 && n <= 64) {
-      double myjd, mymag;
-      unsigned mymask;
-      const int mya = load_alert<NP>(in, pol, s + lane, lane < n, myjd, mymag, mymask);
-      Acc<NP> c;
-      c.init();
-      double lo = __builtin_nan("");
-      for (int k = 0; k < n; ++k) {
-        const double kmag = lane_bcast(mymag, k);
-        lo = (kmag == kmag && !(lo <= kmag)) ? kmag : lo;
-        c.take(lane_bcast(myjd, k), kmag, __builtin_amdgcn_readlane(mya, k),
-               (unsigned)__builtin_amdgcn_readlane((int)mymask, k), myjd, mya);
-      }
-      Best<NP> b;
-      b.init();
-      b.alert_done(pol, c, myjd, mya);
-      b.wave_min();
-      if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < NP; ++q)
-          if (q < pol.n) store_policy(in, pol, obj0 + wave, q, b.jd[q], b.a[q]);
-        store_info(in, obj0 + wave, s, n, lo);
-      }
-    }
-  }
-
-  // ---- one workgroup per object, n > 64 (every condition below is uniform over the workgroup)
-  for (int q = 0; q < OBJ_PER_WG; ++q) {
-    const int s = off[q], n = off[q + 1] - s;
-    if (n <= 64) continue;
-    Best<NP> b;
-    b.init();
-    double lo = __builtin_nan("");                                  // complete after any one pass over the object
-    for (int b0 = 0; b0 < n; b0 += (n <= TILE ? n : WG)) {          // n <= TILE: one pass, the tile staged once
-      const int bn = n <= TILE ? n : (n - b0 < WG ? n - b0 : WG);   // this pass's own alerts: [b0, b0 + bn)
-      constexpr int OWN = TILE / WG;                                // own alerts per thread in the one-pass form
-      double myjd[OWN];
-      int mya[OWN];
-      Acc<NP> c[OWN];
-#pragma unroll
-      for (int r = 0; r < OWN; ++r) c[r].init();
-      for (int t0 = 0; t0 < n; t0 += TILE) {
-        const int tn = n - t0 < TILE ? n - t0 : TILE;
-        __syncthreads();                                            // the tile's previous readers are done
-        for (int i = threadIdx.x; i < tn; i += WG) {
-          double jd, mag;
-          unsigned mask;
-          s_a[i] = load_alert<NP>(in, pol, s + t0 + i, true, jd, mag, mask);
-          s_jd[i] = jd;
-          s_mag[i] = mag;
-          s_mask[i] = mask;
-        }
-        __syncthreads();
-        if (n <= TILE) {
-          // own alerts threadIdx.x + r * WG: they are in the tile already
-#pragma unroll
-          for (int r = 0; r < OWN; ++r) {
-            const int i = threadIdx.x + r * WG;
-            mya[r] = i < n ? s_a[i] : -1;
-            myjd[r] = i < n ? s_jd[i] : __builtin_inf();
-          }
-          for (int k = 0; k < tn; ++k) {
-            const double kjd = s_jd[k], kmag = s_mag[k];
-            const int ka = s_a[k];
-            const unsigned km = s_mask[k];
-            lo = (kmag == kmag && !(lo <= kmag)) ? kmag : lo;
-#pragma unroll
-            for (int r = 0; r < OWN; ++r) c[r].take(kjd, kmag, ka, km, myjd[r], mya[r]);
-          }
-        } else {
-          if (t0 == 0) {
-            double mag;
-            unsigned mask;
-            mya[0] = load_alert<NP>(in, pol, s + b0 + threadIdx.x, (int)threadIdx.x < bn, myjd[0], mag, mask);
-          }
-          for (int k = 0; k < tn; ++k) {
-            const double kmag = s_mag[k];
-            if (b0 == 0) lo = (kmag == kmag && !(lo <= kmag)) ? kmag : lo;
-            c[0].take(s_jd[k], kmag, s_a[k], s_mask[k], myjd[0], mya[0]);
-          }
-        }
-      }
-      if (n <= TILE) {
-#pragma unroll
-        for (int r = 0; r < OWN; ++r) b.alert_done(pol, c[r], myjd[r], mya[r]);
-      } else {
-        b.alert_done(pol, c[0], myjd[0], mya[0]);
-      }
-    }
-    // the object's earliest firing alert: lanes, then the four waves through LDS, policy p written by thread p
-    b.wave_min();
-    if (lane == 0) {
+  // lanes, then the four waves through LDS, policy p written by thread p.  Nothing writes s_bjd / s_ba again before the
+  // next object's first barrier (object_walk.h).
+  __device__ __forceinline__ void finish_workgroup(const Inputs<NP>& in, long obj, int s, int n) {
+    __shared__ double s_bjd[OBJ_PER_WG][MAXP];
+    __shared__ int s_ba[OBJ_PER_WG][MAXP];
+    const int wave = threadIdx.x >> 6;
+    wave_min();
+    if ((threadIdx.x & 63) == 0) {
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
-        s_bjd[wave][p] = b.jd[p];
-        s_ba[wave][p] = b.a[p];
+        s_bjd[wave][p] = jd[p];
+        s_ba[wave][p] = a[p];
       }
     }
     __syncthreads();
-    if ((int)threadIdx.x < pol.n) {
+    if ((int)threadIdx.x < in.pol.n) {
       const int p = threadIdx.x;
       double bjd = s_bjd[0][p];
       int ba = s_ba[0][p];
@@ -296,11 +183,16 @@ __global__ __launch_bounds__(WG) void policy_eval_kernel(Inputs in, Policies pol
           ba = oa;
         }
       }
-      store_policy(in, pol, obj0 + q, p, bjd, ba);
+      store_policy(in, obj, p, bjd, ba);
     }
-    if (threadIdx.x == 0) store_info(in, obj0 + q, s, n, lo);
-    // (the next object's first barrier comes before anything writes s_bjd / s_ba again)
+    if (threadIdx.x == 0) store_info(in, obj, s, n, lo);
   }
+};
+
+template <int NP>
+__global__ __launch_bounds__(WG) void policy_eval_kernel(Inputs<NP> in, const int32_t* __restrict__ seg_offsets,
+                                                         int n_objects) {
+  object_walk::walk<Acc<NP>, Best<NP>>(in, seg_offsets, n_objects);
 }
 
 }  // namespace
@@ -309,17 +201,17 @@ extern "C" int btsbot_policy_eval(const int32_t* perm, const int32_t* seg_offset
                                   const double* jd, const double* magpsf, const float* raw_pred, const int32_t* label,
                                   const double* policies, int n_policies, int32_t* obj_pred, double* obj_trigger,
                                   double* obj_info, void* stream) {
-  if (perm == nullptr || seg_offsets == nullptr || jd == nullptr || magpsf == nullptr || raw_pred == nullptr ||
-      label == nullptr || policies == nullptr || obj_pred == nullptr || obj_trigger == nullptr || obj_info == nullptr ||
-      n_alerts < 0 || n_objects < 0) {
-    btsbot_set_error("policy_eval: NULL argument or negative n_alerts / n_objects");
-    return BTSBOT_ERR_INVALID_ARG;
-  }
+  TRY(object_walk::check_args("policy_eval",
+                              perm != nullptr && seg_offsets != nullptr && jd != nullptr && magpsf != nullptr &&
+                                  raw_pred != nullptr && label != nullptr && policies != nullptr && obj_pred != nullptr &&
+                                  obj_trigger != nullptr && obj_info != nullptr,
+                              n_alerts, n_objects));
   if (n_policies < 1 || n_policies > MAXP) {
     btsbot_set_error("policy_eval: n_policies must be 1..%d per launch, got %d", MAXP, n_policies);
     return BTSBOT_ERR_INVALID_ARG;
   }
-  Policies pol;
+  Args in{perm, jd, magpsf, raw_pred, label, obj_pred, obj_trigger, obj_info, n_alerts, {}};
+  Policies& pol = in.pol;
   pol.n = n_policies;
   for (int q = 0; q < MAXP; ++q) {
     const bool used = q < n_policies;
@@ -333,19 +225,15 @@ extern "C" int btsbot_policy_eval(const int32_t* perm, const int32_t* seg_offset
     pol.gate[q] = used ? policies[4 * q + 3] : 0.0;
     pol.k[q] = k > (double)INT_MAX ? INT_MAX : (int)k;   // (more than any object can hold: never fires)
   }
-  if (n_alerts == 0) return BTSBOT_OK;
-  if (n_objects == 0) {
-    btsbot_set_error("policy_eval: %d alerts in 0 objects", n_alerts);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  const Inputs in{perm, jd, magpsf, raw_pred, label, obj_pred, obj_trigger, obj_info, n_alerts};
-  const unsigned blocks = (unsigned)(((long)n_objects + OBJ_PER_WG - 1) / OBJ_PER_WG);
+  unsigned blocks;
+  TRY(object_walk::grid("policy_eval", n_alerts, n_objects, &blocks));
+  if (blocks == 0) return BTSBOT_OK;
   if (n_policies <= 4)
-    hipLaunchKernelGGL(policy_eval_kernel<4>, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, in, pol, seg_offsets,
+    hipLaunchKernelGGL(policy_eval_kernel<4>, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, Inputs<4>{in}, seg_offsets,
                        n_objects);
   else
-    hipLaunchKernelGGL(policy_eval_kernel<MAXP>, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, in, pol, seg_offsets,
-                       n_objects);
+    hipLaunchKernelGGL(policy_eval_kernel<MAXP>, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, Inputs<MAXP>{in},
+                       seg_offsets, n_objects);
   LAUNCH_CHECK();
   return BTSBOT_OK;
 }

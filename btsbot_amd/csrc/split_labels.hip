@@ -21,7 +21,6 @@
 
 namespace {
 
-using object_walk::OBJ_PER_WG;
 using object_walk::WG;
 
 struct Inputs {
@@ -82,19 +81,15 @@ extern "C" int btsbot_split_labels(const int32_t* perm, const int32_t* seg_offse
                                    const double* jd, const double* magpsf, int32_t* pos, int32_t* size,
                                    int32_t* first_row, int32_t* later, uint8_t* is_rise, double* peakmag,
                                    void* stream) {
-  if (perm == nullptr || seg_offsets == nullptr || jd == nullptr || magpsf == nullptr || pos == nullptr ||
-      size == nullptr || first_row == nullptr || later == nullptr || is_rise == nullptr || peakmag == nullptr ||
-      n_alerts < 0 || n_objects < 0) {
-    btsbot_set_error("split_labels: NULL argument or negative n_alerts / n_objects");
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if (n_alerts == 0) return BTSBOT_OK;
-  if (n_objects == 0) {
-    btsbot_set_error("split_labels: %d alerts in 0 objects", n_alerts);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
+  TRY(object_walk::check_args("split_labels",
+                              perm != nullptr && seg_offsets != nullptr && jd != nullptr && magpsf != nullptr &&
+                                  pos != nullptr && size != nullptr && first_row != nullptr && later != nullptr &&
+                                  is_rise != nullptr && peakmag != nullptr,
+                              n_alerts, n_objects));
+  unsigned blocks;
+  TRY(object_walk::grid("split_labels", n_alerts, n_objects, &blocks));
+  if (blocks == 0) return BTSBOT_OK;
   const Inputs in{perm, jd, magpsf, pos, size, first_row, later, is_rise, peakmag, n_alerts};
-  const unsigned blocks = (unsigned)(((long)n_objects + OBJ_PER_WG - 1) / OBJ_PER_WG);
   hipLaunchKernelGGL(split_labels_kernel, dim3(blocks), dim3(WG), 0, (hipStream_t)stream, in, seg_offsets, n_objects);
   LAUNCH_CHECK();
   return BTSBOT_OK;

@@ -27,7 +27,6 @@ everywhere in this package.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import os
 from typing import Optional, Sequence
@@ -35,28 +34,12 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib
-from .alert_utils import _group_by_object, object_keys
+from .alert_utils import _check_table, _group_by_object, _launch_grouped, object_keys
 
 SPLIT_NAMES = ("train", "val", "test")                                     # the codes of label_set()["split"]
 SOURCE_SETS = ("trues", "dims", "vars", "rejects", "junk", "extIas")       # the codes of subset_mask's source_set
 NON_SN_TYPES = ("AGN", "AGN?", "bogus", "bogus?", "duplicate", "nova", "rock", "star", "varstar", "QSO", "CV", "CV?",
                 "CLAGN", "Blazar")
-
-
-def _check_table(where: str, object_id: torch.Tensor, **cols) -> int:
-    if object_id.device.type != "cuda":
-        raise RuntimeError(f"btsbot_amd.splits.{where} runs on the GPU; there is no CPU fallback (object_id is on "
-                           f"{object_id.device})")
-    if object_id.dim() != 1:
-        raise ValueError(f"object_id must be one-dimensional, got {tuple(object_id.shape)}")
-    n = object_id.shape[0]
-    for name, t in cols.items():
-        if t is not None and (t.dim() != 1 or t.shape[0] != n):
-            raise ValueError(f"{name} must be [{n}], got {tuple(t.shape)}")
-    if object_id.dtype.is_floating_point or object_id.dtype == torch.bool:
-        raise ValueError(f"object_id must be an integer tensor, got {object_id.dtype}")
-    return n
 
 
 def split_labels(object_id: torch.Tensor, jd: torch.Tensor, magpsf: torch.Tensor) -> dict:
@@ -68,20 +51,14 @@ def split_labels(object_id: torch.Tensor, jd: torch.Tensor, magpsf: torch.Tensor
     among themselves go by row --, per object a permutation of 0 .. size - 1;  is_rise bool: jd[i] <= the jd of the
     lowest row at the object's minimum non-NaN magpsf (false on an object without one);  peakmag float64: that minimum,
     NaN if none.  No host synchronisation."""
-    n = _check_table("split_labels", object_id, jd=jd, magpsf=magpsf)
+    n = _check_table("splits.split_labels", object_id, jd=jd, magpsf=magpsf)
     dev = object_id.device
     jd, magpsf = (t.to(device=dev, dtype=torch.float64).contiguous() for t in (jd, magpsf))
     i32 = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4)]
     rise = torch.empty(n, dtype=torch.uint8, device=dev)
     peak = torch.empty(n, dtype=torch.float64, device=dev)
     if n:
-        perm, offsets = _group_by_object(object_id)
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(_lib.lib().btsbot_split_labels(
-                C.c_void_p(perm.data_ptr()), C.c_void_p(offsets.data_ptr()), n, n, C.c_void_p(jd.data_ptr()),
-                C.c_void_p(magpsf.data_ptr()), *(C.c_void_p(t.data_ptr()) for t in i32), C.c_void_p(rise.data_ptr()),
-                C.c_void_p(peak.data_ptr()), C.c_void_p(st)), "btsbot_split_labels")
+        _launch_grouped("btsbot_split_labels", _group_by_object(object_id), n, jd, magpsf, *i32, rise, peak)
     return {"pos": i32[0], "size": i32[1], "first_row": i32[2], "later": i32[3], "is_rise": rise.bool(), "peakmag": peak}
 
 
@@ -98,7 +75,7 @@ def label_set(object_id: torch.Tensor, jd: torch.Tensor, magpsf: torch.Tensor, p
 
     One host read: the number of objects and the distinct object sizes, which size the two draws; the permutations of
     the distinct sizes go back as one table and N, split are gathers.  Raises on CPU tensors: there is no CPU path."""
-    n = _check_table("label_set", object_id, jd=jd, magpsf=magpsf, peakmag=peakmag)
+    n = _check_table("splits.label_set", object_id, jd=jd, magpsf=magpsf, peakmag=peakmag)
     fractions = [float(f) for f in fractions]
     if len(fractions) != len(SPLIT_NAMES) or min(fractions) < 0 or abs(sum(fractions) - 1.0) > 1e-8:
         raise ValueError(f"fractions must be {len(SPLIT_NAMES)} non-negative numbers summing to 1, got {fractions}")

@@ -24,7 +24,7 @@ from typing import Dict, Mapping, Optional, Tuple
 import torch
 
 from . import _lib
-from .alert_utils import _group_by_object
+from .alert_utils import OBJECT_TILE, _check_table, _group_by_object, _launch_grouped
 from .data import DeviceDataset
 
 
@@ -142,9 +142,7 @@ def run_val(config: dict, model_dir: str, model_filename: str, bts_weight: float
 # name -> (score threshold, magnitude cut, count, peak gate or None): the four policies the reference logs
 REFERENCE_POLICIES = {"bts_p1": (0.5, 19.0, 2, None), "bts_p2": (0.5, 19.0, 2, 18.5),
                       "prod_p1": (0.85, 19.0, 1, None), "prod_p2": (0.85, 19.0, 1, 18.5)}
-# alerts per LDS tile of btsbot_policy_eval (TILE in csrc/policy_eval.hip): objects of up to 64 alerts take one wave, up
-# to POLICY_TILE one workgroup with the object resident in LDS, larger ones stream through the tile
-POLICY_TILE = 1024
+POLICY_TILE = OBJECT_TILE                                          # btsbot_policy_eval runs the shared per-object walk
 POLICIES_PER_LAUNCH = 16
 PEAKMAG_BINS = (17.0, 17.25, 17.5, 17.75, 18.0, 18.25, 18.5)       # np.arange(17.0, 18.75, 0.25)
 JAN1_2021_JD = 2459215.5                                           # scanners' times before it are not trusted
@@ -166,20 +164,12 @@ def _policy_table(policies: Mapping) -> torch.Tensor:
 def _policy_slots(object_id, jd, magpsf, label, raw_preds, policies: Mapping) -> Dict[str, torch.Tensor]:
     """The kernel over n object slots (objects in ascending id order first, then empty slots with n_alerts = 0), without
     a host synchronisation.  ``first`` is the index of each object's first alert in input order (n for an empty slot)."""
-    cols = (jd, magpsf, label, raw_preds)
-    for name, t in zip(("object_id", "jd", "magpsf", "label", "raw_preds"), (object_id,) + cols):
+    cols = dict(jd=jd, magpsf=magpsf, label=label, raw_preds=raw_preds)
+    for name, t in dict(object_id=object_id, **cols).items():
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
-    if object_id.device.type != "cuda":
-        raise RuntimeError("btsbot_amd.val.policy_eval runs on the GPU; there is no CPU "
-                           f"fallback (object_id is on {object_id.device})")
+    n = _check_table("val.policy_eval", object_id, **cols)
     dev = object_id.device
-    n = object_id.shape[0] if object_id.dim() == 1 else -1
-    for name, t in zip(("object_id", "jd", "magpsf", "label", "raw_preds"), (object_id,) + cols):
-        if t.dim() != 1 or t.shape[0] != n:
-            raise ValueError(f"{name} must be [{max(n, 0)}], got {tuple(t.shape)}")
-    if object_id.dtype.is_floating_point or object_id.dtype == torch.bool:
-        raise ValueError(f"object_id must be an integer tensor, got {object_id.dtype}")
     table = _policy_table(policies)
     npol = table.shape[0]
     jd, magpsf = (t.to(device=dev, dtype=torch.float64).contiguous() for t in (jd, magpsf))
@@ -192,23 +182,17 @@ def _policy_slots(object_id, jd, magpsf, label, raw_preds, policies: Mapping) ->
     if n:
         perm, offsets = _group_by_object(object_id)
         first = torch.cat([perm.to(torch.int64), torch.full((1,), n, dtype=torch.int64, device=dev)])[offsets[:-1].long()]
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream(dev).cuda_stream
-            for p0 in range(0, npol, POLICIES_PER_LAUNCH):
-                chunk = table[p0:p0 + POLICIES_PER_LAUNCH].contiguous()
-                m = chunk.shape[0]
-                whole = m == npol                      # one launch: write in place; a sweep: per-chunk buffers, copied in
-                cp = pred if whole else torch.empty((n, m), dtype=torch.int32, device=dev)
-                ct = trig if whole else torch.empty((n, m, 2), dtype=torch.float64, device=dev)
-                _lib.check(_lib.lib().btsbot_policy_eval(
-                    C.c_void_p(perm.data_ptr()), C.c_void_p(offsets.data_ptr()), n, n,
-                    C.c_void_p(jd.data_ptr()), C.c_void_p(magpsf.data_ptr()), C.c_void_p(raw.data_ptr()),
-                    C.c_void_p(lab.data_ptr()), C.cast(C.c_void_p(chunk.data_ptr()), C.POINTER(C.c_double)), m,
-                    C.c_void_p(cp.data_ptr()), C.c_void_p(ct.data_ptr()), C.c_void_p(info.data_ptr()),
-                    C.c_void_p(st)), "btsbot_policy_eval")
-                if not whole:
-                    pred[:, p0:p0 + m] = cp
-                    trig[:, p0:p0 + m] = ct
+        for p0 in range(0, npol, POLICIES_PER_LAUNCH):
+            chunk = table[p0:p0 + POLICIES_PER_LAUNCH].contiguous()    # (a host array: it travels as kernel arguments)
+            m = chunk.shape[0]
+            whole = m == npol                      # one launch: write in place; a sweep: per-chunk buffers, copied in
+            cp = pred if whole else torch.empty((n, m), dtype=torch.int32, device=dev)
+            ct = trig if whole else torch.empty((n, m, 2), dtype=torch.float64, device=dev)
+            _launch_grouped("btsbot_policy_eval", (perm, offsets), n, jd, magpsf, raw, lab,
+                            C.cast(C.c_void_p(chunk.data_ptr()), C.POINTER(C.c_double)), m, cp, ct, info)
+            if not whole:
+                pred[:, p0:p0 + m] = cp
+                trig[:, p0:p0 + m] = ct
     return {"first": first, "n_alerts": info[:, 0].to(torch.int64), "label": info[:, 1].to(torch.int64),
             "min_magpsf": info[:, 2], "pred": pred, "trigger_jd": trig[:, :, 0], "trigger_mag": trig[:, :, 1]}
 

@@ -89,17 +89,21 @@ def test_golden_fixture(cuda):
     _check(cuda, rows)
 
 
-def test_size_boundaries(cuda):
-    """Objects of 1, 2, 3, 63, 64, 65, T - 1, T, T + 1 and 2 T + 7 alerts in one shuffled batch: each of the three kernel
-    forms (one wave; one workgroup over an LDS tile; an object streamed through the tile) and each hand-over between
-    them, with an object that never fires, one that fires at the first possible alert and one that fires at its last
-    alert in every form."""
+def _boundary_batch():
     from btsbot_amd.val import POLICY_TILE as T
     rng = np.random.default_rng(11)
     plan = [(1, "random"), (2, "first"), (3, "last"), (63, "never"), (64, "first"), (65, "never"), (T - 1, "first"),
             (T, "last"), (T + 1, "never"), (2 * T + 7, "first"), (T + 9, "last"), (40, "last"), (17, "random"),
             (90, "random"), (2, "never"), (2, "last")]
-    case = _cat([_object(100 + 3 * k, n, rng, sc, label=k % 2) for k, (n, sc) in enumerate(plan)], rng)
+    return plan, _cat([_object(100 + 3 * k, n, rng, sc, label=k % 2) for k, (n, sc) in enumerate(plan)], rng)
+
+
+def test_size_boundaries(cuda):
+    """Objects of 1, 2, 3, 63, 64, 65, T - 1, T, T + 1 and 2 T + 7 alerts in one shuffled batch: each of the three kernel
+    forms (one wave; one workgroup over an LDS tile; an object streamed through the tile) and each hand-over between
+    them, with an object that never fires, one that fires at the first possible alert and one that fires at its last
+    alert in every form."""
+    plan, case = _boundary_batch()
     got = _check(cuda, case)
     assert list(got["n_alerts"]) == [n for n, _ in plan]
     for k, (n, sc) in enumerate(plan):
@@ -110,6 +114,19 @@ def test_size_boundaries(cuda):
             assert got["pred"][k].all() and list(got["trigger_jd"][k]) == [np.sort(jd)[1]] * 2 + [jd.min()] * 2
         elif sc == "last" and n >= 2:
             assert got["pred"][k].all() and (got["trigger_jd"][k] == jd.max()).all() and (got["trigger_mag"][k] == 18.45).all()
+
+
+def test_size_boundaries_sixteen_policies(cuda):
+    """The same batch under 16 distinct policies (thr, cut, k = 1..3, with and without a gate), against the restatement:
+    more than four policies select the wide kernel, which the sweep test otherwise compares only with the kernel's own
+    single-policy calls.  Objects of 65, T - 1, T, T + 1, 2 T + 7 and T + 9 alerts lie in adjacent slots of a workgroup:
+    each hands the LDS tile and the wave minima over to the next."""
+    _, case = _boundary_batch()
+    pols = {f"p{i}": (0.08 + 0.055 * i, (19.0, 18.9, 18.7)[i % 3], 1 + (i // 2) % 3, None if i % 2 else 18.3 + 0.04 * i)
+            for i in range(16)}
+    assert len({p[0] for p in pols.values()}) == 16 and {p[2] for p in pols.values()} == {1, 2, 3}
+    got = _check(cuda, case, pols)
+    assert got["pred"].any(axis=0).all() and not got["pred"].all(axis=0).any()     # every policy fires somewhere, none everywhere
 
 
 def test_hand_over_across_waves_and_tiles(cuda):

@@ -45,7 +45,8 @@ from .features import FeatureState
 from . import neighbors
 from .neighbors import EmbeddingIndex, embedding_neighbors, knn_graph
 from . import layout
-from .layout import FuzzyGraph, embedding_layout, find_ab_params, fuzzy_graph, optimize_layout
+from .layout import (EmbeddingMap, FuzzyGraph, embedding_layout, find_ab_params, fuzzy_graph, layout_transform,
+                     optimize_layout, query_memberships)
 from .splits import (SOURCE_SETS, SPLIT_NAMES, create_subset, cut_set_and_assign_splits, cuts_suffix, label_set,
                      merge_sets_across_split, split_labels, subsample_data, subset_mask)
 
@@ -59,6 +60,7 @@ __all__ = [
     "features", "FeatureState",
     "neighbors", "EmbeddingIndex", "embedding_neighbors", "knn_graph",
     "layout", "FuzzyGraph", "fuzzy_graph", "optimize_layout", "embedding_layout", "find_ab_params",
+    "EmbeddingMap", "layout_transform", "query_memberships",
     "splits", "SPLIT_NAMES", "SOURCE_SETS", "label_set", "split_labels", "subset_mask", "cuts_suffix",
     "cut_set_and_assign_splits", "merge_sets_across_split", "create_subset", "subsample_data",
 ]

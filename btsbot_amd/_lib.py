@@ -50,7 +50,7 @@ SYMBOLS = [
     "btsbot_embed_width", "btsbot_forward_embed",
     "btsbot_knn_bank_bytes", "btsbot_knn_pack_bank", "btsbot_knn_splits", "btsbot_knn_workspace", "btsbot_knn_query",
     "btsbot_layout_smooth_knn", "btsbot_layout_symmetrize_workspace", "btsbot_layout_symmetrize", "btsbot_layout_init",
-    "btsbot_layout_epochs",
+    "btsbot_layout_epochs", "btsbot_layout_smooth_knn_query", "btsbot_layout_transform",
 ]
 LAYOUT_MAX_K, LAYOUT_MAX_NEGATIVES = 64, 64
 KNN_METRIC = {"euclidean": 0, "cosine": 1}   # enum btsbot_knn_metric
@@ -286,6 +286,11 @@ def lib() -> C.CDLL:
     L.btsbot_layout_init.argtypes = [vp, i64, C.c_uint64, i32, vp]
     L.btsbot_layout_epochs.restype = i32
     L.btsbot_layout_epochs.argtypes = [vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, f32, f32, C.c_uint64, i32, f32, i32, vp]
+    L.btsbot_layout_smooth_knn_query.restype = i32
+    L.btsbot_layout_smooth_knn_query.argtypes = [vp, vp, i64, i32, vp, vp, vp]
+    L.btsbot_layout_transform.restype = i32
+    L.btsbot_layout_transform.argtypes = [vp, vp, vp, i64, i64, i32, vp, vp, i32, i32, i32, f32, f32, C.c_uint64, i32, f32, i32,
+                                          vp]
     L.btsbot_eval_metrics.restype = i32
     L.btsbot_eval_metrics.argtypes = [vp, vp, f32, i64, vp, vp]
     if L.btsbot_abi_version() != ABI_VERSION:

@@ -19,6 +19,10 @@
 //              partial sums meet in a fixed butterfly: the summation order of a vertex depends on its row alone, never
 //              on the grid or the run.
 //              Negative samples come from a counter hash of (seed, epoch, slot, s); there is no RNG state.
+//
+//   kNN of new rows in a bank (btsbot_knn_query, no self) -> smooth_knn_query: sigma, memberships w_j (rho = 0)
+//                                                         -> transform: positions of the new rows on the FIXED map of
+//                                                            the bank, every epoch of the schedule in one launch (4o)
 #include <hipcub/hipcub.hpp>
 
 #include "common.h"
@@ -29,6 +33,7 @@ constexpr int MAX_K = 64, MAX_NSR = 64;
 constexpr int G = 8;                 // lanes per vertex in the epoch kernel
 constexpr int LONG_ROW = 128;        // a row of more slots than this is walked by the whole workgroup
 constexpr int EPOCH_MAX_BLOCKS = 16384;
+constexpr int TRANSFORM_MAX_BLOCKS = 65536;   // of one wave (8 queries) each
 
 __host__ __device__ inline uint64_t mix64(uint64_t x) {   // splitmix64: the state step and the finaliser
   x += 0x9e3779b97f4a7c15ULL;
@@ -50,6 +55,25 @@ __device__ __forceinline__ float wave_min_f32(float v) {
   return v;
 }
 
+// umap's bisection for sigma over one wave's row (lane = column): sum over the neighbours of exp(-max(x, 0) / sigma) =
+// target.  The trips and branches are the same in every lane (psum is a wave sum).
+__device__ __forceinline__ double bisect_sigma(bool nb, double x, double target) {
+  double lo = 0.0, hi = __builtin_inf(), mid = 1.0;
+  for (int trip = 0; trip < 64; ++trip) {
+    const double psum = wave_sum_f64(nb ? (x > 0.0 ? exp(-(x / mid)) : 1.0) : 0.0);
+    if (fabs(psum - target) < 1e-5) break;
+    if (psum > target) {
+      hi = mid;
+      mid = (lo + hi) / 2.0;
+    } else {
+      lo = mid;
+      if (hi == __builtin_inf()) mid *= 2.0;
+      else mid = (lo + hi) / 2.0;
+    }
+  }
+  return mid;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // smooth_knn: one wave per row
 __global__ __launch_bounds__(256) void layout_smooth_knn_kernel(const int64_t* __restrict__ idx, const float* __restrict__ dist,
@@ -69,19 +93,7 @@ __global__ __launch_bounds__(256) void layout_smooth_knn_kernel(const int64_t* _
   const float r32 = wave_min_f32(nb && d32 > 0.f ? d32 : __builtin_inff());
   const double rh = r32 == __builtin_inff() ? 0.0 : (double)r32;
   const double x = d - rh;
-  double lo = 0.0, hi = __builtin_inf(), mid = 1.0;
-  for (int trip = 0; trip < 64; ++trip) {
-    const double psum = wave_sum_f64(nb ? (x > 0.0 ? exp(-(x / mid)) : 1.0) : 0.0);
-    if (fabs(psum - target) < 1e-5) break;
-    if (psum > target) {
-      hi = mid;
-      mid = (lo + hi) / 2.0;
-    } else {
-      lo = mid;
-      if (hi == __builtin_inf()) mid *= 2.0;
-      else mid = (lo + hi) / 2.0;
-    }
-  }
+  double mid = bisect_sigma(nb, x, target);
   const double cnt = wave_sum_f64(present ? 1.0 : 0.0);
   const double mean_row = cnt > 0.0 ? wave_sum_f64(present ? d : 0.0) / cnt : 0.0;
   const double floor_s = 1e-3 * (rh > 0.0 ? mean_row : *mean_all);
@@ -96,6 +108,27 @@ __global__ __launch_bounds__(256) void layout_smooth_knn_kernel(const int64_t* _
     if (nb && j < n && j != row) a = x > 0.0 ? (float)exp(-(x / (double)s32)) : 1.f;
     memb[row * k + lane] = a;
   }
+}
+
+// The query side (umap-learn's transform: rows that are NOT in the bank): no self column, rho = 0, and the floor of sigma
+// is 1e-3 x the mean of the row's OWN present distances -- nothing here depends on the other rows of the call.
+__global__ __launch_bounds__(256) void layout_smooth_knn_query_kernel(const int64_t* __restrict__ idx,
+                                                                      const float* __restrict__ dist, long n, int k,
+                                                                      double target, float* __restrict__ sigma,
+                                                                      float* __restrict__ memb) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;
+  const bool in_row = lane < k;
+  const bool nb = in_row && idx[row * k + lane] >= 0;
+  const double x = nb ? (double)dist[row * k + lane] : 0.0;
+  double mid = bisect_sigma(nb, x, target);
+  const double cnt = wave_sum_f64(nb ? 1.0 : 0.0);
+  const double floor_s = cnt > 0.0 ? 1e-3 * (wave_sum_f64(x) / cnt) : 0.0;
+  if (mid < floor_s) mid = floor_s;
+  const float s32 = (float)mid;
+  if (lane == 0) sigma[row] = s32;
+  if (in_row) memb[row * k + lane] = nb ? (x > 0.0 ? (float)exp(-(x / (double)s32)) : 1.f) : 0.f;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -295,6 +328,129 @@ __global__ __launch_bounds__(256) void layout_epoch_kernel(const EpochArgs A) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// transform: new rows placed on the fixed map of a bank
+struct TransformArgs {
+  const int64_t* idx;   // [q][k] rows of the bank, -1 = absent
+  const float* w;       // [q][k] memberships
+  const float2* bank;   // [n_bank] map positions, fixed
+  const float2* yin;    // [q]; may be yout
+  float2* yout;         // [q]
+  long q;
+  uint32_t n_bank;
+  int k, n_epochs, first, last, nsr;
+  float a, b, lr;
+  uint64_t seed;
+};
+
+// the start: the mean of the neighbours' positions weighted by the memberships, float64 in slot order, rounded once
+__global__ __launch_bounds__(256) void layout_transform_init_kernel(const TransformArgs A) {
+  const long q = (long)blockIdx.x * 256 + threadIdx.x;
+  if (q >= A.q) return;
+  double sw = 0.0, sx = 0.0, sy = 0.0;
+  for (int j = 0; j < A.k; ++j) {
+    const int64_t u = A.idx[q * A.k + j];
+    if (u < 0 || u >= (int64_t)A.n_bank) continue;
+    const double wj = A.w[q * A.k + j];
+    const float2 yu = A.bank[u];
+    sw = __dadd_rn(sw, wj);
+    sx = __dadd_rn(sx, __dmul_rn(wj, (double)yu.x));
+    sy = __dadd_rn(sy, __dmul_rn(wj, (double)yu.y));
+  }
+  A.yout[q] = make_float2((float)(sx / sw), (float)(sy / sw));   // no slot present: 0 / 0 = NaN
+}
+
+// A group of G = 8 lanes owns one query for the whole schedule.  Lane l holds the slots l, l + 8, ... (S of them at
+// most) in registers: the neighbour's fixed position and r = fp32(w / w_rowmax).  With the bank fixed a query depends on
+// nothing but its own row, so the epochs first..last run here back to back: the position stays in registers, only the
+// negative samples are gathered, and the one store is lane 0's after the last epoch.  No LDS, no barrier, no atomic.
+// The sum order of an epoch (lane: slots in order, per firing slot the attractive term then the samples in order; then a
+// 3-step xor butterfly, which leaves the same bits in all eight lanes) is a function of the row alone.
+template <int S>
+__global__ __launch_bounds__(64) void layout_transform_kernel(const TransformArgs A) {
+  constexpr int GPB = 64 / G;
+  const int lane = threadIdx.x % G, grp = threadIdx.x / G;
+  const float a = A.a, b = A.b;
+  const int k = A.k;
+  for (long q0 = (long)blockIdx.x * GPB; q0 < A.q; q0 += (long)gridDim.x * GPB) {
+    const long q = q0 + grp;
+    if (q >= A.q) continue;   // a whole group leaves together; the butterfly never crosses groups
+    const int64_t* ri = A.idx + q * k;
+    const float* rw = A.w + q * k;
+    // rowkey: what makes the samples of a row a function of the row alone
+    uint64_t key = 0;
+    float wmax = 0.f;
+    for (int j = 0; j < k; ++j) {
+      const float wj = rw[j];
+      key = mix64(key + (((uint64_t)(uint32_t)ri[j] << 32) | (uint64_t)__float_as_uint(wj)));
+      wmax = fmaxf(wmax, wj);
+    }
+    float2 yn[S];
+    float r[S];
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+      const int j = lane + G * i;
+      const int64_t u = j < k ? ri[j] : -1;
+      const bool present = u >= 0 && u < (int64_t)A.n_bank;
+      yn[i] = present ? A.bank[u] : make_float2(0.f, 0.f);
+      r[i] = present ? __fdiv_rn(rw[j], wmax) : 0.f;   // w_rowmax = 0: NaN, which never fires
+    }
+    float2 y = A.yin[q];
+    for (int n = A.first; n <= A.last; ++n) {
+      const uint64_t base = hash_base(A.seed, (uint64_t)n) + key + 64ULL * (uint64_t)lane;
+      float sx = 0.f, sy = 0.f;
+#pragma unroll
+      for (int i = 0; i < S; ++i) {
+        const double rd = (double)r[i];
+        if (!(floor((double)n * rd) > floor((double)(n - 1) * rd))) continue;
+        {
+          // one end moves only: no factor 2
+          const float dx = y.x - yn[i].x, dy = y.y - yn[i].y;
+          const float d2 = dx * dx + dy * dy;
+          if (d2 > 0.f) {
+            const float L = log2f(d2);
+            const float c = -2.f * a * b * exp2f((b - 1.f) * L) / (1.f + a * exp2f(b * L));
+            sx += clip4(c * dx);
+            sy += clip4(c * dy);
+          }
+        }
+        const uint64_t h0 = base + 64ULL * (uint64_t)(G * i);
+        for (int s0 = 0; s0 < A.nsr; s0 += 8) {
+          float2 yt[8];
+#pragma unroll
+          for (int s = 0; s < 8; ++s) {   // the gathers of up to eight samples are in flight together
+            yt[s] = make_float2(__builtin_nanf(""), 0.f);
+            if (s0 + s < A.nsr) yt[s] = A.bank[__umulhi((uint32_t)(mix64(h0 + (uint64_t)(s0 + s)) >> 32), A.n_bank)];
+          }
+#pragma unroll
+          for (int s = 0; s < 8; ++s) {
+            if (!(isfinite(yt[s].x) && isfinite(yt[s].y))) continue;
+            const float dx = y.x - yt[s].x, dy = y.y - yt[s].y;
+            const float d2 = dx * dx + dy * dy;
+            if (d2 > 0.f) {
+              const float c = 2.f * b / ((0.001f + d2) * (1.f + a * exp2f(b * log2f(d2))));
+              sx += clip4(c * dx);
+              sy += clip4(c * dy);
+            } else {
+              sx += 4.f;
+              sy += 4.f;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int o = G / 2; o >= 1; o >>= 1) {
+        sx += __shfl_xor(sx, o);
+        sy += __shfl_xor(sy, o);
+      }
+      // umap-learn's transform starts at initial_alpha / 4
+      const float alpha = (float)((double)A.lr / 4.0 * (1.0 - (double)(n - 1) / (double)A.n_epochs));
+      y = make_float2(__fmaf_rn(alpha, sx, y.x), __fmaf_rn(alpha, sy, y.y));
+    }
+    if (lane == 0) A.yout[q] = y;
+  }
+}
+
 int check_graph_shape(const char* who, int64_t n, int k) {
   if (n < 0 || k < 2 || k > MAX_K || 2 * n * (int64_t)k >= 0x7fffffffLL) {
     btsbot_set_error("%s: need n >= 0, 2 <= k <= %d and 2 n k < 2^31 (n=%lld k=%d)", who, MAX_K, (long long)n, k);
@@ -346,6 +502,85 @@ extern "C" int btsbot_layout_smooth_knn(const int64_t* idx, const float* dist, i
   }
   hipLaunchKernelGGL(layout_smooth_knn_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, idx, dist,
                      (long)n, k, log2((double)k), mean_all, sigma, rho, memb);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+extern "C" int btsbot_layout_smooth_knn_query(const int64_t* idx, const float* dist, int64_t q, int k, float* sigma,
+                                              float* w, void* stream) {
+  TRY(check_graph_shape("btsbot_layout_smooth_knn_query", q, k));
+  if (q == 0) return BTSBOT_OK;
+  if (idx == nullptr || dist == nullptr || sigma == nullptr || w == nullptr) {
+    btsbot_set_error("btsbot_layout_smooth_knn_query: NULL argument");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  hipLaunchKernelGGL(layout_smooth_knn_query_kernel, dim3((unsigned)((q + 3) / 4)), dim3(256), 0, (hipStream_t)stream, idx,
+                     dist, (long)q, k, log2((double)k), sigma, w);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+extern "C" int btsbot_layout_transform(const int64_t* idx, const float* w, const float* bank_y, int64_t n_bank, int64_t q,
+                                       int k, const float* y0, float* yout, int n_epochs, int first_epoch, int last_epoch,
+                                       float a, float b, uint64_t seed, int negative_sample_rate, float learning_rate,
+                                       int blocks, void* stream) {
+  TRY(check_graph_shape("btsbot_layout_transform", q, k));
+  const bool start_only = first_epoch == 1 && last_epoch == 0 && y0 == nullptr;   // the weighted-mean start, no epoch
+  if (n_bank < 0 || n_bank > 0x7fffffffLL || n_epochs < 1 || first_epoch < 1 || last_epoch > n_epochs ||
+      (first_epoch > last_epoch && !start_only) || negative_sample_rate < 0 || negative_sample_rate > MAX_NSR ||
+      blocks < 0) {
+    btsbot_set_error("btsbot_layout_transform: need 0 <= n_bank < 2^31, 1 <= first_epoch <= last_epoch <= n_epochs (or "
+                     "epochs 1..0 without y0: the start alone), 0 <= negative_sample_rate <= %d, blocks >= 0 (n_bank=%lld "
+                     "epochs %d..%d of %d, rate %d, blocks %d)", MAX_NSR, (long long)n_bank, first_epoch, last_epoch,
+                     n_epochs, negative_sample_rate, blocks);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (first_epoch > 1 && y0 == nullptr) {
+    btsbot_set_error("btsbot_layout_transform: first_epoch = %d needs y0, the positions after epoch %d", first_epoch,
+                     first_epoch - 1);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (q == 0) return BTSBOT_OK;
+  if (n_bank == 0) {
+    btsbot_set_error("btsbot_layout_transform: the bank is empty (q=%lld)", (long long)q);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (idx == nullptr || w == nullptr || bank_y == nullptr || yout == nullptr || ((uintptr_t)bank_y & 7) != 0 ||
+      ((uintptr_t)yout & 7) != 0 || ((uintptr_t)y0 & 7) != 0) {
+    btsbot_set_error("btsbot_layout_transform: NULL argument, or positions not 8-byte aligned");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  TransformArgs A;
+  A.idx = idx;
+  A.w = w;
+  A.bank = reinterpret_cast<const float2*>(bank_y);
+  A.yin = reinterpret_cast<const float2*>(y0 != nullptr ? y0 : yout);
+  A.yout = reinterpret_cast<float2*>(yout);
+  A.q = (long)q;
+  A.n_bank = (uint32_t)n_bank;
+  A.k = k;
+  A.n_epochs = n_epochs;
+  A.first = first_epoch;
+  A.last = last_epoch;
+  A.nsr = negative_sample_rate;
+  A.a = a;
+  A.b = b;
+  A.lr = learning_rate;
+  A.seed = seed;
+  hipStream_t st = (hipStream_t)stream;
+  if (y0 == nullptr) {
+    hipLaunchKernelGGL(layout_transform_init_kernel, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, st, A);
+    LAUNCH_CHECK();
+  }
+  if (start_only) return BTSBOT_OK;
+  constexpr int GPB = 64 / G;
+  long grid = (q + GPB - 1) / GPB;
+  if (blocks > 0) grid = grid < blocks ? grid : blocks;
+  else if (grid > TRANSFORM_MAX_BLOCKS) grid = TRANSFORM_MAX_BLOCKS;
+  const dim3 g((unsigned)grid), t(64);
+  if (k <= 2 * G) hipLaunchKernelGGL(layout_transform_kernel<2>, g, t, 0, st, A);
+  else if (k <= 4 * G) hipLaunchKernelGGL(layout_transform_kernel<4>, g, t, 0, st, A);
+  else hipLaunchKernelGGL(layout_transform_kernel<8>, g, t, 0, st, A);
   LAUNCH_CHECK();
   return BTSBOT_OK;
 }

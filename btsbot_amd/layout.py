@@ -15,6 +15,14 @@ and writes new ones, a vertex is moved by its own lanes only and negative sample
 input gives the same map bit for bit, whatever the grid or the run -- which also means the result is not umap-learn's
 (whose sequential, racy updates cannot be reproduced).  Nothing synchronises with the host except the one read of the
 D x D covariance ``init="pca"`` needs; the work is queued on the current stream.  There is no CPU fallback.
+
+New rows are placed on a map that stays fixed (umap-learn's ``transform``):
+
+    m = EmbeddingMap(bank)                                      # index + embedding_layout; or .from_positions(bank, y)
+    y_new = m.transform(queries)                                # float32 [Q, 2]; m.extend(rows) also adds them
+    idx, dist = index.query(queries, 15)
+    w, sigma = query_memberships(idx, dist)
+    y_new = layout_transform(idx, dist, bank_y, 100, a=a, b=b)  # every epoch of the schedule in one launch
 """
 from __future__ import annotations
 
@@ -294,3 +302,125 @@ def embedding_layout(emb: torch.Tensor, n_neighbors: int = 15, min_dist: float =
             return y0
         return optimize_layout(g, y0, epochs, a, b, seed=seed, negative_sample_rate=negative_sample_rate,
                                learning_rate=learning_rate)
+
+
+# ---- new rows on an existing map
+def query_memberships(idx: torch.Tensor, dist: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The memberships of ``EmbeddingIndex.query(queries, k)``'s ``idx`` int64 [Q, k] and ``dist`` float32 [Q, k] (2 <= k
+    <= 64; rows that are NOT in the bank, so there is no self column): umap-learn's ``smooth_knn_dist`` as its
+    ``transform`` calls it (``rho = 0``), ``w = exp(-d / sigma)``; 0 where ``idx = -1``.  Returns ``(w [Q, k], sigma
+    [Q])``, float32.  A row's result depends on that row alone."""
+    n, k = _check_knn(idx, dist)
+    dev = idx.device
+    idx, dist = idx.contiguous(), dist.contiguous()
+    with torch.cuda.device(dev):
+        sigma = torch.empty(n, dtype=torch.float32, device=dev)
+        w = torch.empty((n, k), dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().btsbot_layout_smooth_knn_query(_ptr(idx), _ptr(dist), n, k, _ptr(sigma), _ptr(w), _stream(dev)),
+                   "btsbot_layout_smooth_knn_query")
+    return w, sigma
+
+
+def _positions(t, name: str, rows: Optional[int], dev) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 2 or (rows is not None and t.shape[0] != rows):
+        raise ValueError(f"{name} must be float32 [{'N' if rows is None else rows}, 2], got {t.dtype} {tuple(t.shape)}")
+    _on_gpu(t, name, dev)
+    return t.detach().contiguous()
+
+
+def layout_transform(idx: torch.Tensor, dist: torch.Tensor, bank_y: torch.Tensor, n_epochs: int = 100, *, a: float,
+                     b: float, seed: int = 0, negative_sample_rate: int = 5, learning_rate: float = 1.0,
+                     y0: Optional[torch.Tensor] = None, first_epoch: int = 1, last_epoch: Optional[int] = None,
+                     blocks: int = 0) -> torch.Tensor:
+    """Positions float32 [Q, 2] of Q new rows on the map ``bank_y`` float32 [N, 2], which stays fixed: umap-learn's
+    ``transform``.  ``idx``, ``dist``: the rows' neighbours in the bank (``EmbeddingIndex.query``).  A row starts at the
+    mean of its neighbours' positions weighted by ``query_memberships`` and runs epochs ``first_epoch..last_epoch``
+    (default: all) of an ``n_epochs`` schedule at a quarter of ``learning_rate``, the whole schedule in one launch.  With
+    ``y0`` float32 [Q, 2] (not modified) the rows start there instead, so the schedule can be stepped: ``first_epoch > 1``
+    needs it.  ``last_epoch=0`` (with ``first_epoch=1`` and no ``y0``) returns the start alone.  A row's position depends
+    on that row alone -- not on the other rows of the call, on ``blocks`` (the grid; 0: the library's choice) or on the
+    run; a row without neighbours (a non-finite query) gets NaN."""
+    n, k = _check_knn(idx, dist)
+    start_only = last_epoch == 0 and first_epoch == 1 and y0 is None and not isinstance(last_epoch, bool)
+    last = 0 if start_only else _check_epoch_args(n_epochs, seed, negative_sample_rate, learning_rate, first_epoch, last_epoch)
+    if start_only:
+        _check_epoch_args(n_epochs, seed, negative_sample_rate, learning_rate, 1, None)
+    _int(blocks, "blocks", 0, (1 << 31) - 1)
+    if not (float(a) > 0 and float(b) > 0):
+        raise ValueError(f"a and b must be positive, got a={a!r} b={b!r}")
+    dev = idx.device
+    bank_y = _positions(bank_y, "bank_y", None, dev)
+    if y0 is not None:
+        y0 = _positions(y0, "y0", n, dev)
+    elif first_epoch > 1:
+        raise ValueError(f"first_epoch = {first_epoch} needs y0, the positions after epoch {first_epoch - 1}")
+    n_bank = int(bank_y.shape[0])
+    if n and not n_bank:
+        raise ValueError("bank_y is empty: there is no map to place the rows on")
+    w, _sigma = query_memberships(idx, dist)
+    idx = idx.contiguous()
+    with torch.cuda.device(dev):
+        y = torch.empty((n, 2), dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().btsbot_layout_transform(_ptr(idx), _ptr(w), _ptr(bank_y), n_bank, n, k, _ptr(y0) if y0 is not None
+                                                      else C.c_void_p(0), _ptr(y), n_epochs, first_epoch, last, float(a),
+                                                      float(b), seed & _U64, negative_sample_rate, float(learning_rate),
+                                                      blocks, _stream(dev)), "btsbot_layout_transform")
+    return y
+
+
+class EmbeddingMap:
+    """A bank of embedding rows (an ``EmbeddingIndex``) with its 2-D map, and the placement of new rows on it.
+
+        m = EmbeddingMap(bank)                          # embedding_layout of the bank
+        m = EmbeddingMap.from_positions(bank, y)        # a map made earlier
+        y_new = m.transform(queries)                    # the map does not move
+        m.extend(rows)                                  # transform, then the rows join the bank at those positions
+
+    ``n_neighbors`` counts the row itself in the fit (as ``embedding_layout``) and is the number of bank rows a new row is
+    attached to in ``transform`` (as umap-learn).  ``transform`` runs 100 epochs whatever the number of rows
+    (``n_epochs=None``), so that a row's position does not depend on the size of the call.  Calls on one map must be
+    ordered by the caller's streams."""
+
+    def __init__(self, bank: torch.Tensor, n_neighbors: int = 15, min_dist: float = 0.1, spread: float = 1.0,
+                 n_epochs: Optional[int] = None, init="pca", seed: int = 0, metric: str = "euclidean"):
+        from .neighbors import EmbeddingIndex, _self_first_graph
+        _int(n_neighbors, "n_neighbors", 2, _lib.LAYOUT_MAX_K)
+        self.a, self.b = find_ab_params(spread, min_dist)
+        self.n_neighbors = n_neighbors
+        self.index = EmbeddingIndex(bank, metric)
+        self.embedding_ = embedding_layout(self.index.bank, n_neighbors, min_dist, spread, n_epochs, init, seed, metric,
+                                           knn=_self_first_graph(self.index, n_neighbors))
+
+    @classmethod
+    def from_positions(cls, bank_or_index, y: torch.Tensor, n_neighbors: int = 15, min_dist: float = 0.1,
+                       spread: float = 1.0) -> "EmbeddingMap":
+        """The map ``y`` float32 [N, 2] of ``bank_or_index`` (rows [N, D], packed here, or an ``EmbeddingIndex``, used
+        as it is), laid out earlier -- ``embedding_layout``'s result or a run's ``_umap.csv``."""
+        from .neighbors import EmbeddingIndex
+        _int(n_neighbors, "n_neighbors", 2, _lib.LAYOUT_MAX_K)
+        m = cls.__new__(cls)
+        m.a, m.b = find_ab_params(spread, min_dist)
+        m.n_neighbors = n_neighbors
+        m.index = bank_or_index if isinstance(bank_or_index, EmbeddingIndex) else EmbeddingIndex(bank_or_index)
+        m.embedding_ = _positions(y, "y", len(m.index), m.index.device).clone()
+        return m
+
+    def __len__(self) -> int:
+        return len(self.index)
+
+    def transform(self, queries: torch.Tensor, n_epochs: Optional[int] = None, seed: int = 0) -> torch.Tensor:
+        """Positions float32 [Q, 2] of ``queries`` [Q, D] on the map (``layout_transform`` of their ``n_neighbors``
+        nearest bank rows); a row that holds a non-finite value gets NaN."""
+        epochs = 100 if n_epochs is None else _int(n_epochs, "n_epochs", 1, (1 << 31) - 1)
+        idx, dist = self.index.query(queries, self.n_neighbors)
+        return layout_transform(idx, dist, self.embedding_, epochs, a=self.a, b=self.b, seed=seed)
+
+    def extend(self, rows: torch.Tensor, n_epochs: Optional[int] = None, seed: int = 0) -> torch.Tensor:
+        """``transform(rows)``, after which the rows join the bank at those positions (and are neighbours and samples
+        of later calls); returns the new positions."""
+        y = self.transform(rows, n_epochs, seed)
+        self.index.add(rows)
+        self.embedding_ = torch.cat([self.embedding_, y])
+        return y

@@ -177,6 +177,12 @@ def knn_graph(emb: torch.Tensor, k: int, include_self: bool = True, metric: str 
     index = EmbeddingIndex(rows, metric)
     if not include_self:
         return index.query(rows, k, splits=splits, self_offset=0)
+    return _self_first_graph(index, k, splits)
+
+
+def _self_first_graph(index: EmbeddingIndex, k: int, splits: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``knn_graph(index.bank, k, include_self=True)`` from an index already packed."""
+    rows = index.bank
     n = int(rows.shape[0])
     idx = torch.empty((n, k), dtype=torch.int64, device=rows.device)
     dist = torch.empty((n, k), dtype=torch.float32, device=rows.device)

@@ -900,6 +900,35 @@ int btsbot_layout_epochs(const int64_t* indptr, const int32_t* indices, const fl
                          float b, uint64_t seed, int negative_sample_rate, float learning_rate, int blocks,
                          void* stream);
 
+/* ---- new rows on an existing map: umap-learn's transform (csrc/layout.hip) ---- */
+
+/* Both are queued on `stream`; nothing allocates, synchronises or copies to the host.  A row's result is a function of
+ * that row of idx / dist (and of the bank's positions) alone: it does not depend, bit for bit, on the other rows of the
+ * call, on `blocks` or on the run.  BTSBOT_ERR_INVALID_ARG for a NULL pointer, k outside 2..64, 2 q k >= 2^31, an epoch
+ * range outside 1 <= first <= last <= n_epochs, first > 1 without y0, negative_sample_rate outside 0..64, an empty bank.
+ * q = 0 succeeds without a launch.
+ *
+ * btsbot_layout_smooth_knn_query(): idx int64 [q][k], dist fp32 [q][k] as btsbot_knn_query returns them for rows that
+ * are NOT in the bank: there is no self column, every entry with idx >= 0 is a neighbour.  Writes sigma [q] (the
+ * bisection of btsbot_layout_smooth_knn with rho = 0, floored at 1e-3 times the mean of the row's own present
+ * distances; float64, rounded to fp32 once) and w [q][k] = exp(-d / sigma) (1 at d = 0, 0 where idx < 0).
+ *
+ * btsbot_layout_transform(): epochs first_epoch..last_epoch of an n_epochs schedule for q new points against the FIXED
+ * positions bank_y fp32 [n_bank][2], in ONE launch; yout fp32 [q][2].  y0 (fp32 [q][2], may be yout) holds the positions
+ * the first epoch starts from; y0 = NULL (first_epoch = 1 only): the start is sum_j w_j Y[idx_j] / sum_j w_j (float64 in
+ * slot order, rounded once; NaN where no slot is present), from a launch of its own, and first_epoch = 1, last_epoch = 0
+ * then returns that start alone.  Epoch e: slot j with r = fp32(w_j / max_j w_j) fires iff floor(e r) > floor((e - 1) r)
+ * (float64) and adds clip(-2ab d^(2(b-1)) / (1 + a d^(2b)) (y - Y[idx_j]), +-4) -- no factor 2: the bank does not move
+ * -- and negative_sample_rate terms clip(2b / ((0.001 + d^2)(1 + a d^(2b))) (y - Y_t), +-4), t = the high word of
+ * (hash >> 32) * n_bank, hash = mix64(mix64(seed ^ mix64(e)) + rowkey + 64 j + s), rowkey = the fold key <- mix64(key +
+ * ((uint32(idx_j) << 32) | bits(w_j))) over the row's slots from key = 0; a non-finite Y_t adds nothing.  y <- fma(alpha_e,
+ * sum, y), alpha_e = fp32(learning_rate / 4 (1 - (e - 1) / n_epochs)).  idx entries outside 0..n_bank-1 are absent. */
+int btsbot_layout_smooth_knn_query(const int64_t* idx, const float* dist, int64_t q, int k, float* sigma, float* w,
+                                   void* stream);
+int btsbot_layout_transform(const int64_t* idx, const float* w, const float* bank_y, int64_t n_bank, int64_t q, int k,
+                            const float* y0, float* yout, int n_epochs, int first_epoch, int last_epoch, float a, float b,
+                            uint64_t seed, int negative_sample_rate, float learning_rate, int blocks, void* stream);
+
 /* Replaces: the epoch / validation metrics of val.py:159-168 and train.py:550-558 -- out2[0] += sum_i of
  * BCEWithLogitsLoss(pos_weight) terms over n logits, out2[1] += number of alerts whose sigmoid(z) > 0.5
  * agrees with the label (caller zeroes out2 and divides by n). */

@@ -49,12 +49,15 @@ SYMBOLS = [
     "btsbot_trigger_rehash", "btsbot_feature_reset", "btsbot_feature_update", "btsbot_feature_load", "btsbot_feature_rehash",
     "btsbot_embed_width", "btsbot_forward_embed",
     "btsbot_knn_bank_bytes", "btsbot_knn_pack_bank", "btsbot_knn_splits", "btsbot_knn_workspace", "btsbot_knn_query",
+    "btsbot_knn_workspace_grouped", "btsbot_knn_query_grouped",
     "btsbot_layout_smooth_knn", "btsbot_layout_symmetrize_workspace", "btsbot_layout_symmetrize", "btsbot_layout_init",
     "btsbot_layout_epochs", "btsbot_layout_smooth_knn_query", "btsbot_layout_transform",
 ]
 LAYOUT_MAX_K, LAYOUT_MAX_NEGATIVES = 64, 64
 KNN_METRIC = {"euclidean": 0, "cosine": 1}   # enum btsbot_knn_metric
 KNN_MAX_DIM, KNN_MAX_K, KNN_MAX_SPLITS = 1024, 64, 32
+KNN_EXCLUDE_SAME, KNN_ONE_PER_GROUP = 1, 2   # enum btsbot_knn_flags
+KNN_MAX_K_ONE_PER_GROUP = 32                 # k's cap under KNN_ONE_PER_GROUP
 EMBEDDING = {"features": 0, "hidden": 1}   # enum btsbot_embedding
 # enum btsbot_stamp_status: what btsbot_decode_stamps says of each stamp
 STAMP_STATUS = {"OK": 0, "BAD_GZIP": 1, "BAD_DEFLATE": 2, "TOO_LARGE": 3, "BAD_TRAILER": 4, "BAD_FITS": 5,
@@ -276,6 +279,10 @@ def lib() -> C.CDLL:
     L.btsbot_knn_workspace.argtypes = [i64, i64, i32, i32, i32]
     L.btsbot_knn_query.restype = i32
     L.btsbot_knn_query.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, i64, i32, vp, vp, vp, i64, vp]
+    L.btsbot_knn_workspace_grouped.restype = i64
+    L.btsbot_knn_workspace_grouped.argtypes = [i64, i64, i32, i32, i32, i32]
+    L.btsbot_knn_query_grouped.restype = i32
+    L.btsbot_knn_query_grouped.argtypes = L.btsbot_knn_query.argtypes + [vp, vp, i32]
     L.btsbot_layout_smooth_knn.restype = i32
     L.btsbot_layout_smooth_knn.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp]
     L.btsbot_layout_symmetrize_workspace.restype = i64

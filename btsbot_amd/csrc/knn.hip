@@ -30,6 +30,33 @@
 // operand LDS, and thread q, the owner of row q's list, takes its bucket: see offer().  Nothing here meets through an
 // atomic whose order matters: the bucket slots are handed out by LDS atomics, but a list is the k best of what it was
 // offered whatever the order.  LDS: 64 KB of operands + 1 KB of lists per k, so two workgroups share a CU up to k = 16.
+//
+// Groups (btsbot_knn_query_grouped).  A row may carry a group, any int64 (an alert's object).  Both kernels are templates
+// on the group mode GM; GM = 0 is the code above, unchanged, and is what btsbot_knn_query launches.
+//   GM & 1, exclude   a bank row of the query row's group is never a candidate: one more term in the mask that decides
+//                     which of a lane's 64 scores may be offered.  The query groups of the lane's four rows stay in
+//                     registers; the tile's 128 bank groups are loaded under the products (one per thread) and put into
+//                     the idle operand LDS behind them, from where a fragment's four are read inside the ni loop.
+//   GM & 2, one per group   a list holds at most one entry per group, the group's best by (score, index).  The groups of
+//                     the entries, in full -- 64 bits decide equality, there is no tag --, do NOT live in LDS: 8 more
+//                     bytes per entry there leave one workgroup per CU from k = 9 on, and that alone cost 1.8 x at
+//                     k = 15 (measured).  They live in the workspace, a [k][128] block per workgroup that
+//                     only its owner threads read and write, each its own column: an offer that passes the pre-filter
+//                     reads k of them, coalesced over the owners, from L2.  k <= 32 in this mode: the merge keeps the
+//                     groups of its splits * k pool entries on chip (8 KB at 32 x 32) and its per-lane mask of losers
+//                     has 16 bits in use.
+// Why a list is still independent of the order of its offers.  Let S be the set offered so far and B(S) the best row of
+// every group in S.  Invariant: the list is the k best of B(S).  Offer c of group g.  (a) g has an entry e in the list:
+// e is g's best in S; c before e -> c replaces e in place (it is before e, so it stays among the k best), else B(S)
+// and the list stay.  (b) g has no entry: g's best in S, if any, is not before the list's worst w (it was refused or
+// evicted by k better groups, and lists only improve).  c before w -> c is g's new best and enters for w; the old best
+// of g leaves B(S) unnoticed; otherwise the k best of B do not change.  No row ever has to come BACK: B(S) loses a row
+// only to a better row of the same group.  So the list is a function of S alone, and the pre-filter s <= thr stays valid:
+// a candidate not before the worst of k distinct groups' bests is not before its own group's entry either.
+// The merge then keeps, of a query's splits * k pool entries, those with no pool entry of their group before them, and
+// ranks among these: a group's best over the whole bank is its best split-best, and a row that is not its group's best
+// has k groups' bests of one split before it, each represented in the pool by a kept entry no worse -- rank >= k.  The
+// answer is the same whatever `splits` is.
 #include <float.h>
 
 #include "common.h"
@@ -45,6 +72,9 @@ constexpr int HDR = 16;             // bytes in front of a record's head plane
 constexpr int EMPTY = 0x7fffffff;   // index of an empty list entry (score +inf)
 constexpr int MAX_K = 64, MAX_DIM = 1024, MAX_SPLITS = 32;
 enum { MODE_BANK_L2 = 0, MODE_BANK_COS = 1, MODE_QUERY = 2 };
+enum { GM_EXCLUDE = BTSBOT_KNN_EXCLUDE_SAME, GM_ONE = BTSBOT_KNN_ONE_PER_GROUP };   // group mode bits (template GM)
+constexpr int MAX_K_ONE = 32;       // k's cap with one entry per group: the merge's pool carries its groups on chip
+constexpr int TG_OFF = 16 * 1024;   // the tile's bank groups in the idle operand LDS, behind buckets, counts and flags
 
 struct Cand {
   float s;
@@ -165,10 +195,47 @@ __device__ __forceinline__ void offer(Cand* mine, int k, float s, int gb, float&
   tp = wp;
 }
 
+// One entry per group (the header's argument): mg[j * TQ] is the group of mine[j], in the workspace (the owner's own
+// column of its workgroup's [k][TQ] block: coalesced over the owners).  An entry of the candidate's group decides
+// alone -- the better of the two stays in its place --; without one the candidate is offered as above.
+__device__ __forceinline__ void offer_one(Cand* mine, long long* mg, int k, float s, int gb, long long g, float& ts,
+                                          int& ti, int& tp) {
+  if (!before(s, gb, ts, ti)) return;
+  int at = -1;
+#pragma unroll 4
+  for (int j = 0; j < k; ++j)
+    if (mg[j * TQ] == g && mine[j].i != EMPTY) at = j;   // (at most one entry matches; an empty entry has no group)
+  if (at >= 0) {
+    const Cand e = mine[at];
+    if (!before(s, gb, e.s, e.i)) return;
+  } else {
+    at = tp;
+  }
+  mine[at] = Cand{s, gb};
+  mg[at * TQ] = g;
+  Cand w = mine[0];
+  int wp = 0;
+#pragma unroll 4
+  for (int j = 1; j < k; ++j) {
+    const Cand o = mine[j];
+    if (before(w.s, w.i, o.s, o.i)) {
+      w = o;
+      wp = j;
+    }
+  }
+  ts = w.s;
+  ti = w.i;
+  tp = wp;
+}
+
+template <int GM>
 __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char* __restrict__ qimg,
                                                             const unsigned char* __restrict__ bimg, long Q, int N,
                                                             int dim, int k, long self_offset, int tiles_per_split,
-                                                            int splits, Cand* __restrict__ cand) {
+                                                            int splits, Cand* __restrict__ cand,
+                                                            const long long* __restrict__ qgrp,
+                                                            const long long* __restrict__ bgrp,
+                                                            long long* __restrict__ lgrp) {
   constexpr int MI = 4, NI = 4;     // 16-row fragments per wave: queries (B operand), bank rows (A operand)
   constexpr int CH = TQ * 8 / 256;  // 16-byte chunks per thread, plane and K tile (TQ == TB)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -183,6 +250,9 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
   int* bcnt = reinterpret_cast<int*>(bucket + TQ * BCAP);
   float* thr = reinterpret_cast<float*>(bcnt + TQ);
   int* flag = reinterpret_cast<int*>(thr + TQ);
+  // GM & GM_ONE: the groups of this thread's list entries, entry j at LG[j * TQ]
+  long long* LG = lgrp + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * (size_t)k * TQ + threadIdx.x;
+  long long* tg = reinterpret_cast<long long*>(smem + TG_OFF);       // GM != 0: [TB] the tile's bank groups
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
@@ -212,6 +282,14 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
     sq[mi] = gq < Q ? reinterpret_cast<const float*>(qimg + gq * rec)[1] : 0.f;
     const long sb = gq + self_offset;
     selfb[mi] = self_offset >= 0 && sb < N ? (int)sb : -1;
+  }
+  long long qg[MI];   // GM & GM_EXCLUDE: the groups of the lane's four query rows
+  if constexpr ((GM & GM_EXCLUDE) != 0) {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+      const long gq = q0 + wm * 64 + mi * 16 + lrow;
+      qg[mi] = gq < Q ? qgrp[gq] : 0;   // (a row past Q never has a candidate)
+    }
   }
 
   uint4 qh[CH], ql[CH], bh[CH], bl[CH];
@@ -248,6 +326,10 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
   __syncthreads();   // the lists
   for (int tile = t_begin; tile < t_end; ++tile) {
     const int b0 = tile * TB;
+    long long gt = 0;   // GM != 0: bank row b0 + tid's group, in flight under the products
+    if constexpr (GM != 0) {
+      if (tid < TB && (long)b0 + tid < N) gt = bgrp[(long)b0 + tid];
+    }
     f32x4 acc[NI][MI];
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni)
@@ -287,6 +369,7 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
     if (tid < TQ) {
       thr[tid] = owner ? ts : -__builtin_inff();   // (a row past Q never has a candidate)
       bcnt[tid] = 0;
+      if constexpr (GM != 0) tg[tid] = gt;
     }
     if (tid < 2) flag[tid] = 0;
     lds_barrier();
@@ -307,6 +390,11 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
         nb[i] = h.x;
         sb[i] = h.y;
       }
+      long long bg[4];   // GM & GM_EXCLUDE: the fragment's bank groups
+      if constexpr ((GM & GM_EXCLUDE) != 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) bg[i] = tg[wn * 64 + ni * 16 + lq * 4 + i];
+      }
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -314,8 +402,9 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
           const int gb = b0 + wn * 64 + ni * 16 + lq * 4 + i;
           const float s = fmaf(-(acc[ni][mi][i] * sq[mi]), sb[i], nb[i]);
           acc[ni][mi][i] = s;
-          if (s <= t[mi] && s < __builtin_inff() && gb < b_end && gb != selfb[mi])
-            mask |= 1ull << ((ni * MI + mi) * 4 + i);
+          bool in = s <= t[mi] && s < __builtin_inff() && gb < b_end && gb != selfb[mi];
+          if constexpr ((GM & GM_EXCLUDE) != 0) in = in && bg[i] != qg[mi];
+          if (in) mask |= 1ull << ((ni * MI + mi) * 4 + i);
         }
     }
     // Rounds of: every lane puts its candidates into their rows' buckets (BCAP each; what finds no room waits for the
@@ -355,7 +444,8 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
         const int n = min(bcnt[tid], BCAP);
         for (int e = 0; e < n; ++e) {
           const Cand c = bucket[tid * BCAP + e];
-          offer(L + tid * k, k, c.s, b0 + c.i, ts, ti, tp);
+          if constexpr ((GM & GM_ONE) != 0) offer_one(L + tid * k, LG, k, c.s, b0 + c.i, tg[c.i], ts, ti, tp);
+          else offer(L + tid * k, k, c.s, b0 + c.i, ts, ti, tp);
         }
         thr[tid] = ts;
       }
@@ -374,9 +464,11 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
 
 // ---------------------------------------------------------------------------------------------------------------------
 // merge: one wave per query
+template <int GM>
 __global__ __launch_bounds__(64) void knn_merge_kernel(const float* __restrict__ queries, const float* __restrict__ bank,
                                                        const Cand* __restrict__ cand, int dim, int k, int splits,
-                                                       int metric, int64_t* __restrict__ idx, float* __restrict__ dist) {
+                                                       int metric, int64_t* __restrict__ idx, float* __restrict__ dist,
+                                                       const long long* __restrict__ bgrp) {
   __shared__ Cand pool[MAX_SPLITS * MAX_K];
   __shared__ int win[MAX_K];
   __shared__ float wdist[MAX_K];
@@ -409,6 +501,32 @@ __global__ __launch_bounds__(64) void knn_merge_kernel(const float* __restrict__
   for (int c = lane; c < P; c += 64) pool[c] = cand[q * P + c];
   if (lane < MAX_K) win[lane] = EMPTY;
   __syncthreads();
+  if constexpr ((GM & GM_ONE) != 0) {
+    // one per group: an entry counts only if no pool entry of its group is before it (the splits' bests of one group
+    // meet here); the others become empty, and the ranks below are counted among the rest
+    __shared__ long long pgrp[MAX_SPLITS * MAX_K_ONE];
+    for (int c = lane; c < P; c += 64) {
+      const int b = pool[c].i;
+      pgrp[c] = b != EMPTY ? bgrp[b] : 0;
+    }
+    __syncthreads();
+    unsigned lose = 0;   // bit j: entry lane + 64 j (P <= 32 * 32: at most 16 per lane)
+    for (int c = lane, j = 0; c < P; c += 64, ++j) {
+      const Cand me = pool[c];
+      if (me.i == EMPTY) continue;
+      const long long g = pgrp[c];
+      bool l = false;
+      for (int e = 0; e < P; ++e) {
+        const Cand o = pool[e];
+        l = l || (o.i != EMPTY && pgrp[e] == g && before(o.s, o.i, me.s, me.i));
+      }
+      lose |= l ? 1u << j : 0u;
+    }
+    __syncthreads();
+    for (int c = lane, j = 0; c < P; c += 64, ++j)
+      if ((lose >> j & 1u) != 0) pool[c] = Cand{__builtin_inff(), EMPTY};
+    __syncthreads();
+  }
   // the k best of the pool by (score, index): entries are distinct, so the ranks are too
   for (int c = lane; c < P; c += 64) {
     const Cand me = pool[c];
@@ -541,54 +659,116 @@ extern "C" int64_t btsbot_knn_workspace(int64_t n_query, int64_t n_bank, int dim
   return (int64_t)(image_bytes(n_query, dim) + (size_t)n_query * splits * k * sizeof(Cand));
 }
 
-extern "C" int btsbot_knn_query(const float* queries, int64_t n_query, const float* bank, const void* packed,
-                                int64_t n_bank, int dim, int k, int metric, int64_t self_offset, int splits,
-                                int64_t* idx, float* dist, void* workspace, int64_t workspace_bytes, void* stream) {
-  const int s = check_shape("btsbot_knn_query", n_query, n_bank, dim, k);
-  if (s != BTSBOT_OK) return s;
-  if (metric != BTSBOT_KNN_EUCLIDEAN && metric != BTSBOT_KNN_COSINE) {
-    btsbot_set_error("btsbot_knn_query: metric %d", metric);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if (splits < 0 || splits > MAX_SPLITS) {
-    btsbot_set_error("btsbot_knn_query: splits=%d must be 0 (the library's choice) .. %d", splits, MAX_SPLITS);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if (n_query == 0) return BTSBOT_OK;
+// With one entry per group the groups of the list entries follow the candidates: [query tiles][splits][k][TQ] int64
+extern "C" int64_t btsbot_knn_workspace_grouped(int64_t n_query, int64_t n_bank, int dim, int k, int splits, int flags) {
+  const int64_t base = btsbot_knn_workspace(n_query, n_bank, dim, k, splits);
+  if (base < 0 || (flags & GM_ONE) == 0) return base;
   if (splits == 0) splits = auto_splits(n_query, n_bank);
-  const int64_t need = btsbot_knn_workspace(n_query, n_bank, dim, k, splits);
-  if (queries == nullptr || idx == nullptr || dist == nullptr || workspace == nullptr ||
-      (n_bank > 0 && (bank == nullptr || packed == nullptr))) {
-    btsbot_set_error("btsbot_knn_query: NULL argument");
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if (workspace_bytes < need || ((uintptr_t)workspace & 15) != 0 || ((uintptr_t)packed & 15) != 0) {
-    btsbot_set_error("btsbot_knn_query: workspace of %lld bytes (need %lld), or workspace / packed not 16-byte aligned",
-                     (long long)workspace_bytes, (long long)need);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  unsigned char* qimg = reinterpret_cast<unsigned char*>(workspace);
-  Cand* cand = reinterpret_cast<Cand*>(qimg + image_bytes(n_query, dim));
+  return base + (int64_t)(((size_t)n_query + TQ - 1) / TQ * TQ * splits * k * sizeof(long long));
+}
+
+namespace {
+
+// The launches of btsbot_knn_query (GM = 0) and btsbot_knn_query_grouped, one instantiation per group mode
+template <int GM>
+int launch_query(const float* queries, int64_t n_query, const float* bank, const unsigned char* packed, int64_t n_bank,
+                 int dim, int k, int metric, int64_t self_offset, int splits, int64_t* idx, float* dist,
+                 unsigned char* qimg, Cand* cand, const long long* qgrp, const long long* bgrp, hipStream_t st) {
+  // (the candidates end on a multiple of 8 bytes behind the 256-byte aligned query image)
+  long long* lgrp = reinterpret_cast<long long*>(cand + (size_t)n_query * splits * k);
   hipLaunchKernelGGL(knn_pack_kernel, dim3((unsigned)((n_query + 3) / 4)), dim3(256), 0, st, queries, (long)n_query, dim,
                      (int)MODE_QUERY, qimg);
   LAUNCH_CHECK();
 
   const int total_tiles = (int)((n_bank + TB - 1) / TB);
   const int tps = (total_tiles + splits - 1) / splits;
-  // 64 KB of operands + 1 KB of lists per k: two workgroups per CU up to k = 16
+  // 64 KB of operands + 1 KB of lists per k: two workgroups per CU up to k = 16, in every group mode
   static DevOnce attr;
   if (attr.need()) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_select_kernel),
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_select_kernel<GM>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS + TQ * MAX_K * (int)sizeof(Cand)));
     attr.done();
   }
-  hipLaunchKernelGGL(knn_select_kernel, dim3((unsigned)((n_query + TQ - 1) / TQ), (unsigned)splits), dim3(256),
-                     GEMM_LDS + TQ * k * (int)sizeof(Cand), st, qimg, reinterpret_cast<const unsigned char*>(packed),
-                     (long)n_query, (int)n_bank, dim, k, (long)self_offset, tps, splits, cand);
+  hipLaunchKernelGGL(knn_select_kernel<GM>, dim3((unsigned)((n_query + TQ - 1) / TQ), (unsigned)splits), dim3(256),
+                     GEMM_LDS + TQ * k * (int)sizeof(Cand), st, qimg, packed, (long)n_query, (int)n_bank, dim, k, (long)self_offset,
+                     tps, splits, cand, qgrp, bgrp, lgrp);
   LAUNCH_CHECK();
-  hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)n_query), dim3(64), 0, st, queries, bank, cand, dim, k, splits,
-                     metric, idx, dist);
+  hipLaunchKernelGGL(knn_merge_kernel<(GM & GM_ONE)>, dim3((unsigned)n_query), dim3(64), 0, st, queries, bank,
+                     (const Cand*)cand, dim, k, splits, metric, idx, dist, bgrp);
   LAUNCH_CHECK();
   return BTSBOT_OK;
+}
+
+int query_checked(const char* who, const float* queries, int64_t n_query, const float* bank, const void* packed,
+                  int64_t n_bank, int dim, int k, int metric, int64_t self_offset, int splits, int64_t* idx, float* dist,
+                  void* workspace, int64_t workspace_bytes, const int64_t* query_group, const int64_t* bank_group,
+                  int flags, void* stream) {
+  const int s = check_shape(who, n_query, n_bank, dim, k);
+  if (s != BTSBOT_OK) return s;
+  if (metric != BTSBOT_KNN_EUCLIDEAN && metric != BTSBOT_KNN_COSINE) {
+    btsbot_set_error("%s: metric %d", who, metric);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (splits < 0 || splits > MAX_SPLITS) {
+    btsbot_set_error("%s: splits=%d must be 0 (the library's choice) .. %d", who, splits, MAX_SPLITS);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if ((flags & ~(GM_EXCLUDE | GM_ONE)) != 0) {
+    btsbot_set_error("%s: flags=%d holds bits other than BTSBOT_KNN_EXCLUDE_SAME | BTSBOT_KNN_ONE_PER_GROUP", who, flags);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if ((flags & GM_ONE) != 0 && k > MAX_K_ONE) {
+    btsbot_set_error("%s: k=%d, but BTSBOT_KNN_ONE_PER_GROUP holds k <= %d (the merge keeps its pool's groups on chip)", who, k,
+                     MAX_K_ONE);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (n_query == 0) return BTSBOT_OK;
+  if (splits == 0) splits = auto_splits(n_query, n_bank);
+  const int64_t need = btsbot_knn_workspace_grouped(n_query, n_bank, dim, k, splits, flags);
+  if (queries == nullptr || idx == nullptr || dist == nullptr || workspace == nullptr ||
+      (n_bank > 0 && (bank == nullptr || packed == nullptr))) {
+    btsbot_set_error("%s: NULL argument", who);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (((flags & GM_EXCLUDE) != 0 && query_group == nullptr) || (flags != 0 && n_bank > 0 && bank_group == nullptr)) {
+    btsbot_set_error("%s: flags=%d need bank_group (and BTSBOT_KNN_EXCLUDE_SAME query_group), got NULL", who, flags);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (workspace_bytes < need || ((uintptr_t)workspace & 15) != 0 || ((uintptr_t)packed & 15) != 0) {
+    btsbot_set_error("%s: workspace of %lld bytes (need %lld), or workspace / packed not 16-byte aligned", who,
+                     (long long)workspace_bytes, (long long)need);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* qimg = reinterpret_cast<unsigned char*>(workspace);
+  Cand* cand = reinterpret_cast<Cand*>(qimg + image_bytes(n_query, dim));
+  const unsigned char* pk = reinterpret_cast<const unsigned char*>(packed);
+  const long long* qg = reinterpret_cast<const long long*>(query_group);
+  const long long* bg = reinterpret_cast<const long long*>(bank_group);
+#define KNN_GO(GM) \
+  launch_query<GM>(queries, n_query, bank, pk, n_bank, dim, k, metric, self_offset, splits, idx, dist, qimg, cand, qg, bg, st)
+  switch (flags) {
+    case 0: return KNN_GO(0);
+    case GM_EXCLUDE: return KNN_GO(GM_EXCLUDE);
+    case GM_ONE: return KNN_GO(GM_ONE);
+    default: return KNN_GO(GM_EXCLUDE | GM_ONE);
+  }
+#undef KNN_GO
+}
+
+}  // namespace
+
+extern "C" int btsbot_knn_query(const float* queries, int64_t n_query, const float* bank, const void* packed,
+                                int64_t n_bank, int dim, int k, int metric, int64_t self_offset, int splits,
+                                int64_t* idx, float* dist, void* workspace, int64_t workspace_bytes, void* stream) {
+  return query_checked("btsbot_knn_query", queries, n_query, bank, packed, n_bank, dim, k, metric, self_offset, splits,
+                       idx, dist, workspace, workspace_bytes, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int btsbot_knn_query_grouped(const float* queries, int64_t n_query, const float* bank, const void* packed,
+                                        int64_t n_bank, int dim, int k, int metric, int64_t self_offset, int splits,
+                                        int64_t* idx, float* dist, void* workspace, int64_t workspace_bytes,
+                                        void* stream, const int64_t* query_group, const int64_t* bank_group, int flags) {
+  return query_checked("btsbot_knn_query_grouped", queries, n_query, bank, packed, n_bank, dim, k, metric, self_offset,
+                       splits, idx, dist, workspace, workspace_bytes, query_group, bank_group, flags, stream);
 }

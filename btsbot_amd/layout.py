@@ -268,14 +268,17 @@ def _initial_positions(rows: torch.Tensor, finite: torch.Tensor, init, seed: int
 def embedding_layout(emb: torch.Tensor, n_neighbors: int = 15, min_dist: float = 0.1, spread: float = 1.0,
                      n_epochs: Optional[int] = None, init="pca", seed: int = 0, metric: str = "euclidean",
                      negative_sample_rate: int = 5, learning_rate: float = 1.0,
-                     knn: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
+                     knn: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, *,
+                     groups: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The 2-D UMAP map of the rows of ``emb`` [N, D]: ``knn_graph`` (``n_neighbors`` columns, the row itself included,
     as umap-learn counts them) -> ``fuzzy_graph`` -> initial positions -> ``optimize_layout``; float32 [N, 2].
 
     n_epochs=None: 500 for N <= 10,000 and 200 otherwise, as umap-learn.  init: "pca" (the two leading principal
     directions scaled to max |y| = 10 plus a jitter of 1e-4), "random" (uniform in [-10, 10)) or a float32 [N, 2]
     tensor.  knn=(idx, dist): a neighbour graph already made (``knn_graph(emb, n_neighbors, include_self=True)``).  A
-    row that holds a non-finite value has no edges and a NaN position."""
+    row that holds a non-finite value has no edges and a NaN position.  groups: int64 [N], the rows' objects: the graph
+    is ``knn_graph(emb, n_neighbors, groups=groups, group_mode="exclude")`` -- the row itself, then rows of OTHER
+    objects --, so the map is no picture of object identity (not together with ``knn``)."""
     from .neighbors import METRICS, _rows, knn_graph
     _int(n_neighbors, "n_neighbors", 2, _lib.LAYOUT_MAX_K)
     if metric not in METRICS:
@@ -287,13 +290,15 @@ def embedding_layout(emb: torch.Tensor, n_neighbors: int = 15, min_dist: float =
     a, b = find_ab_params(spread, min_dist)
     if knn is not None and not (isinstance(knn, (tuple, list)) and len(knn) == 2):
         raise ValueError("knn must be the pair (idx, dist) of knn_graph(emb, n_neighbors, include_self=True)")
+    if knn is not None and groups is not None:
+        raise ValueError("groups shape the neighbour graph: give them to knn_graph(..., groups=...), not beside knn=")
     rows = _rows(emb, "emb")
     n = int(rows.shape[0])
     epochs = n_epochs if n_epochs is not None else (500 if n <= 10000 else 200)
     _check_epoch_args(epochs, seed, negative_sample_rate, learning_rate, 1, None)
     with torch.cuda.device(rows.device):
         if knn is None:
-            knn = knn_graph(rows, n_neighbors, include_self=True, metric=metric)
+            knn = knn_graph(rows, n_neighbors, include_self=True, metric=metric, groups=groups, group_mode="exclude")
         elif isinstance(knn[0], torch.Tensor) and knn[0].shape[0] != n:
             raise ValueError(f"knn has {knn[0].shape[0]} rows, emb {n}")
         g = fuzzy_graph(*knn)

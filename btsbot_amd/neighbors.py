@@ -15,6 +15,21 @@ fewer than ``k`` bank rows are eligible the tail is ``idx = -1, dist = +inf``; a
 never returned; a query row that does gets ``idx = -1, dist = NaN`` throughout.  A row's answer does not depend, bit for
 bit, on the other rows of the call, on ``splits`` or on the run.  Nothing here synchronises with the host; the work is
 queued on the current stream.  There is no CPU fallback.
+
+Rows that belong together.  A row is one alert, and the alerts of one object are near-copies of each other, so the search
+can be told which rows belong together: a *group* is an int64 per row, any value (``alert_utils.object_keys``).
+
+    index = EmbeddingIndex(bank, groups=obj)                     # one group per bank row; add(rows, groups=...)
+    idx, dist = index.query(q, k, query_groups=obj_q, exclude_same_group=True)   # never a row of the query's own group
+    idx, dist = index.query(q, k, one_per_group=True)            # the k nearest GROUPS, each by its nearest row
+    idx, dist = knn_graph(emb, k, groups=obj, group_mode="exclude")              # self first, then rows of OTHER groups
+    score = neighbor_vote(idx, dist, labels)                     # the positive fraction among a row's neighbours
+
+``exclude_same_group`` removes every bank row whose group equals the query row's; ``one_per_group`` keeps of each group
+only its nearest row (by the ranking of the candidates: selection score, then index) and answers with the ``k`` nearest
+groups, ordered by (dist, index) of these rows; it holds ``k <= 32``.  Both may be combined.  A non-finite bank row is
+never a group's representative.  Both happen inside the selection kernel: the answer is exact however many alerts an
+object has, and keeps every property above (``splits``, batch cuts, runs, incremental ``add``).
 """
 from __future__ import annotations
 
@@ -62,14 +77,43 @@ def _metric(metric) -> int:
     return _lib.KNN_METRIC[metric]
 
 
+def _groups(g, name: str, rows: int, device) -> torch.Tensor:
+    """One int64 group per row, [rows] on ``device``, contiguous.  ValueError otherwise: nothing is converted, a group
+    is an identity and a silent cast could merge two."""
+    if not isinstance(g, torch.Tensor) or g.dtype != torch.int64:
+        raise ValueError(f"{name} must be an int64 torch.Tensor, got "
+                         f"{g.dtype if isinstance(g, torch.Tensor) else type(g).__name__}")
+    if g.device != device:
+        raise ValueError(f"{name} is on {g.device}, its rows on {device}")
+    if g.dim() != 1 or g.shape[0] != rows:
+        raise ValueError(f"{name} must hold one group per row, [{rows}], got {tuple(g.shape)}")
+    return g.detach().contiguous()
+
+
+def _check_group_args(k: int, has_groups: bool, query_groups, exclude_same_group, one_per_group) -> int:
+    """The flags of btsbot_knn_query_grouped; ValueError for a combination that cannot be answered."""
+    if not isinstance(exclude_same_group, bool) or not isinstance(one_per_group, bool):
+        raise ValueError("exclude_same_group and one_per_group must be bools")
+    if (exclude_same_group or one_per_group) and not has_groups:
+        raise ValueError("exclude_same_group / one_per_group need an index built with groups=...")
+    if exclude_same_group and query_groups is None:
+        raise ValueError("exclude_same_group needs query_groups (one int64 group per query row)")
+    if one_per_group and k > _lib.KNN_MAX_K_ONE_PER_GROUP:
+        raise ValueError(f"one_per_group holds k <= {_lib.KNN_MAX_K_ONE_PER_GROUP}, got k = {k}")
+    return (_lib.KNN_EXCLUDE_SAME if exclude_same_group else 0) | (_lib.KNN_ONE_PER_GROUP if one_per_group else 0)
+
+
 class EmbeddingIndex:
     """A bank of embedding rows on one GPU with its packed operand image (norms, per-row scales, f16 head and remainder
     planes), built once and extended by ``add``.  A row's image depends on the row alone, so an index built by several
     ``add`` calls answers bit for bit like one built at once.
 
+    groups: one int64 group per bank row (an alert's object), or None.  An index with groups takes them with every
+    ``add`` and can answer ``query(..., exclude_same_group=True)`` and ``query(..., one_per_group=True)``.
+
     Calls on one index must be ordered by the caller's streams."""
 
-    def __init__(self, bank: torch.Tensor, metric: str = "euclidean"):
+    def __init__(self, bank: torch.Tensor, metric: str = "euclidean", *, groups: Optional[torch.Tensor] = None):
         self._metric_id = _metric(metric)
         self.metric = metric
         rows = _rows(bank, "bank")
@@ -79,7 +123,8 @@ class EmbeddingIndex:
         self._cap = 0
         self._bank = rows.new_empty((0, self.dim))
         self._packed = torch.empty(0, dtype=torch.uint8, device=self.device)
-        self.add(rows)
+        self._groups = None if groups is None else torch.empty(0, dtype=torch.int64, device=self.device)
+        self.add(rows, groups=groups)
 
     def __len__(self) -> int:
         return self._n
@@ -89,20 +134,30 @@ class EmbeddingIndex:
         """The fp32 rows held, [len, D] (a view of the index's storage)."""
         return self._bank[:self._n]
 
+    @property
+    def groups(self) -> Optional[torch.Tensor]:
+        """The rows' groups, int64 [len] (a view of the index's storage), or None for an index without groups."""
+        return None if self._groups is None else self._groups[:self._n]
+
     def _stream(self) -> C.c_void_p:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _record_bytes(self) -> int:
         return int(_lib.lib().btsbot_knn_bank_bytes(1, self.dim))
 
-    def add(self, rows: torch.Tensor) -> "EmbeddingIndex":
-        """Appends ``rows`` [n, D]; only they are packed (what is held already moves as bytes when the storage grows)."""
+    def add(self, rows: torch.Tensor, *, groups: Optional[torch.Tensor] = None) -> "EmbeddingIndex":
+        """Appends ``rows`` [n, D]; only they are packed (what is held already moves as bytes when the storage grows).
+        groups: int64 [n], required if and only if the index was built with groups."""
         rows = _rows(rows, "rows", self.device)
         if rows.shape[1] != self.dim:
             raise ValueError(f"rows: D = {rows.shape[1]}, the index holds D = {self.dim}")
         n = int(rows.shape[0])
         if self._n + n >= 1 << 31:
             raise ValueError(f"an index holds at most 2^31 - 1 rows ({self._n} + {n})")
+        if (groups is None) != (self._groups is None):
+            raise ValueError("add(rows, groups=...) takes groups if and only if the index was built with groups")
+        if groups is not None:
+            groups = _groups(groups, "groups", n, self.device)
         if n == 0:
             return self
         L = _lib.lib()
@@ -114,74 +169,113 @@ class EmbeddingIndex:
                 packed = torch.empty(cap * rec, dtype=torch.uint8, device=self.device)
                 bank[:self._n].copy_(self._bank[:self._n])
                 packed[:self._n * rec].copy_(self._packed[:self._n * rec])
+                if self._groups is not None:
+                    grp = torch.empty(cap, dtype=torch.int64, device=self.device)
+                    grp[:self._n].copy_(self._groups[:self._n])
+                    self._groups = grp
                 self._bank, self._packed, self._cap = bank, packed, cap
             new = self._bank[self._n:self._n + n]
             new.copy_(rows)
+            if groups is not None:
+                self._groups[self._n:self._n + n].copy_(groups)
             _lib.check(L.btsbot_knn_pack_bank(_ptr(new), self._n, n, self.dim, self._metric_id, _ptr(self._packed),
                                               self._cap, self._stream()), "btsbot_knn_pack_bank")
         self._n += n
         return self
 
-    def query(self, queries: torch.Tensor, k: int, *, splits: int = 0,
+    def query(self, queries: torch.Tensor, k: int, *, query_groups: Optional[torch.Tensor] = None,
+              exclude_same_group: bool = False, one_per_group: bool = False, splits: int = 0,
               self_offset: int = -1) -> Tuple[torch.Tensor, torch.Tensor]:
         """``idx`` int64 [Q, k] and ``dist`` float32 [Q, k] of each query row's ``k`` nearest rows of the index.
         splits: bank slices searched by separate workgroups (0: the library's choice; the answer does not depend on it).
-        self_offset >= 0: query row i is row i + self_offset of the index and is not its own candidate."""
+        self_offset >= 0: query row i is row i + self_offset of the index and is not its own candidate.
+        query_groups: int64 [Q], the query rows' groups.  exclude_same_group: no row of the query row's own group.
+        one_per_group: at most one row per group, its nearest; the ``k`` nearest groups (``k <= 32``)."""
         _check_k(k, splits)
+        flags = _check_group_args(k, self._groups is not None, query_groups, exclude_same_group, one_per_group)
         q = _rows(queries, "queries", self.device)
         if q.shape[1] != self.dim:
             raise ValueError(f"queries: D = {q.shape[1]}, the index holds D = {self.dim}")
         if not isinstance(self_offset, int):
             raise ValueError(f"self_offset must be an int, got {self_offset!r}")
         nq = int(q.shape[0])
+        if query_groups is not None:
+            query_groups = _groups(query_groups, "query_groups", nq, self.device)
         idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         dist = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         if nq == 0:
             return idx, dist
         L = _lib.lib()
-        need = int(L.btsbot_knn_workspace(nq, self._n, self.dim, k, splits))
+        need = int(L.btsbot_knn_workspace_grouped(nq, self._n, self.dim, k, splits, flags))
         if need < 0:
-            _lib.check(need, "btsbot_knn_workspace")
+            _lib.check(need, "btsbot_knn_workspace_grouped")
         with torch.cuda.device(self.device):
             ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
-            _lib.check(L.btsbot_knn_query(_ptr(q), nq, _ptr(self._bank), _ptr(self._packed), self._n, self.dim, k,
-                                          self._metric_id, self_offset, splits, _ptr(idx), _ptr(dist), _ptr(ws), need,
-                                          self._stream()), "btsbot_knn_query")
+            args = (_ptr(q), nq, _ptr(self._bank), _ptr(self._packed), self._n, self.dim, k, self._metric_id,
+                    self_offset, splits, _ptr(idx), _ptr(dist), _ptr(ws), need, self._stream())
+            if flags == 0:
+                _lib.check(L.btsbot_knn_query(*args), "btsbot_knn_query")
+            else:
+                _lib.check(L.btsbot_knn_query_grouped(*args, _ptr(query_groups), _ptr(self._groups), flags),
+                           "btsbot_knn_query_grouped")
         return idx, dist
 
 
 def embedding_neighbors(queries: torch.Tensor, bank: torch.Tensor, k: int, metric: str = "euclidean", *,
+                        bank_groups: Optional[torch.Tensor] = None, query_groups: Optional[torch.Tensor] = None,
+                        exclude_same_group: bool = False, one_per_group: bool = False,
                         splits: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """The ``k`` nearest rows of ``bank`` [N, D] for every row of ``queries`` [Q, D]: ``idx`` int64 [Q, k], ``dist``
     float32 [Q, k] (see the module text).  Packs the bank for this one call; keep an ``EmbeddingIndex`` to query a bank
-    more than once."""
+    more than once.  bank_groups / query_groups / exclude_same_group / one_per_group: as ``EmbeddingIndex(groups=...)``
+    and its ``query``."""
     _check_k(k, splits)
     _metric(metric)
+    _check_group_args(k, bank_groups is not None, query_groups, exclude_same_group, one_per_group)
     q = _rows(queries, "queries")
     b = _rows(bank, "bank", q.device)
     if q.shape[1] != b.shape[1]:
         raise ValueError(f"queries have D = {q.shape[1]}, the bank D = {b.shape[1]}")
-    return EmbeddingIndex(b, metric).query(q, k, splits=splits)
+    return EmbeddingIndex(b, metric, groups=bank_groups).query(
+        q, k, query_groups=query_groups, exclude_same_group=exclude_same_group, one_per_group=one_per_group, splits=splits)
+
+
+GROUP_MODES = ("exclude", "distinct", "exclude+distinct")
 
 
 def knn_graph(emb: torch.Tensor, k: int, include_self: bool = True, metric: str = "euclidean", *,
+              groups: Optional[torch.Tensor] = None, group_mode: str = "exclude",
               splits: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """Every row of ``emb`` [N, D] among the others: ``idx`` int64 [N, k], ``dist`` float32 [N, k].
 
     include_self=True: the row itself first at distance 0, then its ``k - 1`` nearest others -- the layout pynndescent
     and umap-learn's ``precomputed_knn`` use.  include_self=False: ``k`` others.  A row is excluded by position, not by
-    value: its duplicates are legitimate neighbours at distance 0."""
+    value: its duplicates are legitimate neighbours at distance 0.
+
+    groups: int64 [N], the rows' groups (objects); a row's own group is its query group.  group_mode: ``"exclude"`` the
+    others are rows of OTHER groups only; ``"distinct"`` the others hold at most one row per group (the row's own group
+    may be among them, by another of its rows); ``"exclude+distinct"`` both.  The row itself stays in column 0 under
+    include_self=True in every mode."""
     _check_k(k, splits)
     _metric(metric)
+    if group_mode not in GROUP_MODES:
+        raise ValueError(f"group_mode must be one of {GROUP_MODES}, got {group_mode!r}")
     rows = _rows(emb, "emb")
-    index = EmbeddingIndex(rows, metric)
+    if groups is None:
+        kw = {}
+    else:
+        groups = _groups(groups, "groups", int(rows.shape[0]), rows.device)
+        kw = dict(query_groups=groups, exclude_same_group="exclude" in group_mode, one_per_group="distinct" in group_mode)
+        _check_group_args(k - 1 if include_self else k, True, groups, kw["exclude_same_group"], kw["one_per_group"])
+    index = EmbeddingIndex(rows, metric, groups=groups)
     if not include_self:
-        return index.query(rows, k, splits=splits, self_offset=0)
-    return _self_first_graph(index, k, splits)
+        return index.query(rows, k, splits=splits, self_offset=0, **kw)
+    return _self_first_graph(index, k, splits, **kw)
 
 
-def _self_first_graph(index: EmbeddingIndex, k: int, splits: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
-    """``knn_graph(index.bank, k, include_self=True)`` from an index already packed."""
+def _self_first_graph(index: EmbeddingIndex, k: int, splits: int = 0, **kw) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``knn_graph(index.bank, k, include_self=True)`` from an index already packed (kw: the group arguments of
+    ``query``)."""
     rows = index.bank
     n = int(rows.shape[0])
     idx = torch.empty((n, k), dtype=torch.int64, device=rows.device)
@@ -190,5 +284,36 @@ def _self_first_graph(index: EmbeddingIndex, k: int, splits: int = 0) -> Tuple[t
     idx[:, 0] = torch.where(finite, torch.arange(n, device=rows.device), torch.full_like(idx[:, 0], -1))
     dist[:, 0] = torch.where(finite, torch.zeros_like(dist[:, 0]), torch.full_like(dist[:, 0], float("nan")))
     if k > 1:
-        idx[:, 1:], dist[:, 1:] = index.query(rows, k - 1, splits=splits, self_offset=0)
+        idx[:, 1:], dist[:, 1:] = index.query(rows, k - 1, splits=splits, self_offset=0, **kw)
     return idx, dist
+
+
+def neighbor_vote(idx: torch.Tensor, dist: torch.Tensor, labels: torch.Tensor, weights: str = "uniform") -> torch.Tensor:
+    """The kNN score of every row, float32 [Q]: the positive fraction (``labels`` [N], non-zero = positive, indexed by
+    ``idx``) among the row's valid neighbours (``idx >= 0``), or with ``weights="distance"`` the ``1 / dist``-weighted
+    fraction, where a neighbour at distance 0 takes the whole vote (several: they share it).  NaN where a row has no valid
+    neighbour.  With ``knn_graph(emb, k, include_self=False, groups=obj, group_mode="exclude")`` this is the
+    leave-one-object-out kNN score of an embedding.  Torch operations on the tensors' device; nothing is synchronised."""
+    if weights not in ("uniform", "distance"):
+        raise ValueError(f'weights must be "uniform" or "distance", got {weights!r}')
+    if idx.dim() != 2 or idx.shape != dist.shape or idx.dtype != torch.int64 or not dist.is_floating_point():
+        raise ValueError(f"idx must be int64 [Q, k] and dist floating point of the same shape, got {idx.dtype} "
+                         f"{tuple(idx.shape)} and {dist.dtype} {tuple(dist.shape)}")
+    if labels.dim() != 1:
+        raise ValueError(f"labels must be [N], got {tuple(labels.shape)}")
+    valid = idx >= 0
+    if labels.shape[0] == 0:
+        pos = torch.zeros_like(valid)
+    else:
+        pos = (labels[idx.clamp(min=0)] != 0) & valid
+    if weights == "uniform":
+        w = valid.to(torch.float32)
+    else:
+        # 1 / dist up to a factor per row, the row's smallest distance: no weight overflows for a tiny distance
+        d = torch.where(valid, dist.to(torch.float32), torch.full_like(dist, float("inf"), dtype=torch.float32))
+        dmin = d.min(dim=1, keepdim=True).values if d.shape[1] else d.new_zeros((d.shape[0], 1))
+        zero = valid & (d == 0)
+        w = torch.where(dmin == 0, zero.to(torch.float32), torch.where(valid, dmin / d, torch.zeros_like(d)))
+    den = w.sum(dim=1)
+    num = (w * pos.to(torch.float32)).sum(dim=1)
+    return torch.where(den > 0, num / den.clamp(min=torch.finfo(torch.float32).tiny), torch.full_like(den, float("nan")))

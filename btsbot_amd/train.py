@@ -320,7 +320,10 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
     there are no test files -- through ``ScoreStream(embed=layer)`` and write ``{stem}.npy`` (fp32 [N, width], rows in
     the candidate file's order) and, when that file has a ``candid`` column, ``{stem}.csv`` with it.  With
     ``config['embedding_neighbors'] = k`` also ``{stem}_knn.npz``: ``indices`` int64 [N, k] and ``distances`` fp32 [N, k] of ``knn_graph(rows, k,
-    include_self=True)`` (the layout umap-learn's ``precomputed_knn`` takes) and ``candid`` where the table has it.
+    include_self=True)`` (the layout umap-learn's ``precomputed_knn`` takes) and ``candid`` where the table has it; with
+    the dict ``{"k": 15, "group_by": "objectId", "mode": "exclude"}`` the graph of ``knn_graph(..., groups=ids,
+    group_mode=mode)``, ``ids = alert_utils.object_keys`` of that column (an error names a column the table lacks), and
+    ``groups`` = these ids in the file.  ``config['embedding_layout']`` takes ``"group_by"`` likewise (``groups=ids``).
     With ``config['embedding_layout']`` (``True``, or a dict of ``embedding_layout`` keyword arguments; ``seed`` defaults
     to the run's ``random_seed``) also ``{stem}_umap.csv`` with the reference's columns ``umap_emb_1, umap_emb_2,
     candid`` (train.py:464): the 2-D map of the rows, in the candidate file's order.  Returns the .npy path."""
@@ -345,11 +348,29 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
     np.save(stem + ".npy", out)
     if "candid" in cand.columns:
         cand[["candid"]].to_csv(stem + ".csv", index=False)
+    def group_ids(column, key):
+        """int64 ids of the candidate table's ``column`` (alert_utils.object_keys) on ``dev``"""
+        from .alert_utils import object_keys
+        if column not in cand.columns:
+            raise KeyError(f"config[{key!r}]['group_by'] = {column!r}: the candidate table has no such column "
+                           f"(it has {list(cand.columns)})")
+        return torch.from_numpy(object_keys(cand[column].to_numpy())).to(dev)
+
     k = config.get("embedding_neighbors")
     if k:   # opt-in: the neighbour search get_torch_embedding runs in front of its UMAP layout
         from .neighbors import knn_graph
-        idx, dist = knn_graph(torch.from_numpy(out).to(dev), int(k), include_self=True)
-        extra = {"candid": cand["candid"].to_numpy()} if "candid" in cand.columns else {}
+        kw, extra = {}, {}
+        if isinstance(k, dict):   # {"k": 15, "group_by": "objectId", "mode": "exclude"}: neighbours by source
+            unknown = set(k) - {"k", "group_by", "mode"}
+            if unknown or "k" not in k:
+                raise ValueError(f"config['embedding_neighbors'] takes the keys k, group_by and mode, got {sorted(k)}")
+            if k.get("group_by") is not None:
+                kw = dict(groups=group_ids(k["group_by"], "embedding_neighbors"), group_mode=k.get("mode", "exclude"))
+                extra["groups"] = kw["groups"].cpu().numpy()
+            k = k["k"]
+        idx, dist = knn_graph(torch.from_numpy(out).to(dev), int(k), include_self=True, **kw)
+        if "candid" in cand.columns:
+            extra["candid"] = cand["candid"].to_numpy()
         np.savez(stem + "_knn.npz", indices=idx.cpu().numpy(), distances=dist.cpu().numpy(), **extra)
     lay = config.get("embedding_layout")
     if lay:   # opt-in: the UMAP map itself, with the reference's columns (train.py:464)
@@ -357,6 +378,9 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
         from .layout import embedding_layout
         kw = dict(lay) if isinstance(lay, dict) else {}
         kw.setdefault("seed", int(config.get("random_seed", 0)))
+        if kw.get("group_by") is not None:   # the map of the graph without the row's own object
+            kw["groups"] = group_ids(kw["group_by"], "embedding_layout")
+        kw.pop("group_by", None)
         y = embedding_layout(torch.from_numpy(out).to(dev), **kw).cpu().numpy()
         table = {"umap_emb_1": y[:, 0], "umap_emb_2": y[:, 1]}
         if "candid" in cand.columns:

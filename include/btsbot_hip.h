@@ -845,8 +845,26 @@ int btsbot_feature_rehash(const btsbot_feature_table* src, const btsbot_feature_
  * is searched in by separate workgroups, 0 = btsbot_knn_splits()'s choice.  A row's answer is bit for bit independent
  * of splits, of the other rows of the call and of the run.  workspace: btsbot_knn_workspace(...) bytes for the same
  * arguments, 16-byte aligned, the caller's; scratch afterwards.  Three launches on `stream`; nothing allocates,
- * synchronises or copies to the host, nothing of size n_query x n_bank is written; n_query == 0 launches nothing. */
+ * synchronises or copies to the host, nothing of size n_query x n_bank is written; n_query == 0 launches nothing.
+ *
+ * btsbot_knn_query_grouped(): btsbot_knn_query with rows that belong together.  bank_group int64 [n_bank] and query_group
+ * int64 [n_query] (device memory) give every row a group, any value, negative included -- an alert's object; all 64 bits
+ * decide equality.  flags:
+ *   BTSBOT_KNN_EXCLUDE_SAME   a bank row whose group equals the query row's is never a candidate (self_offset still
+ *                             works beside it); needs query_group and bank_group
+ *   BTSBOT_KNN_ONE_PER_GROUP  the answer holds at most one row per group, the group's nearest by (selection score, bank
+ *                             index) -- the ranking of the candidates --, and is the k nearest GROUPS, ordered by (dist,
+ *                             index) of these representatives; needs bank_group (query_group may be NULL), and k <= 32
+ *                             (the merge keeps the groups of its splits * k candidates on chip).  A non-finite bank row
+ *                             is never a representative; a group whose rows are all non-finite does not exist.
+ * Both may be set.  Fewer than k eligible rows / groups: the tail is idx = -1, dist = +inf; a non-finite query row: -1 /
+ * NaN.  flags = 0 (groups may be NULL) answers exactly as btsbot_knn_query, with the same kernels.  The workspace is
+ * btsbot_knn_workspace_grouped(..., flags) bytes -- btsbot_knn_workspace()'s plus, under BTSBOT_KNN_ONE_PER_GROUP, 8
+ * bytes per candidate for the groups of the list entries (ceil(n_query / 128) * 128 * splits * k of them) --; three launches; the answer is bit for bit independent of splits, of
+ * the other rows of the call and of the run.  BTSBOT_ERR_INVALID_ARG also for unknown flag bits, a group array a flag
+ * needs being NULL, and k > 32 with BTSBOT_KNN_ONE_PER_GROUP. */
 enum btsbot_knn_metric { BTSBOT_KNN_EUCLIDEAN = 0, BTSBOT_KNN_COSINE = 1 };
+enum btsbot_knn_flags { BTSBOT_KNN_EXCLUDE_SAME = 1, BTSBOT_KNN_ONE_PER_GROUP = 2 };
 int64_t btsbot_knn_bank_bytes(int64_t n_bank, int dim);
 int btsbot_knn_pack_bank(const float* rows, int64_t first_row, int64_t n_rows, int dim, int metric, void* packed,
                          int64_t n_bank_capacity, void* stream);
@@ -855,6 +873,11 @@ int64_t btsbot_knn_workspace(int64_t n_query, int64_t n_bank, int dim, int k, in
 int btsbot_knn_query(const float* queries, int64_t n_query, const float* bank, const void* packed, int64_t n_bank,
                      int dim, int k, int metric, int64_t self_offset, int splits, int64_t* idx, float* dist,
                      void* workspace, int64_t workspace_bytes, void* stream);
+int64_t btsbot_knn_workspace_grouped(int64_t n_query, int64_t n_bank, int dim, int k, int splits, int flags);
+int btsbot_knn_query_grouped(const float* queries, int64_t n_query, const float* bank, const void* packed,
+                             int64_t n_bank, int dim, int k, int metric, int64_t self_offset, int splits, int64_t* idx,
+                             float* dist, void* workspace, int64_t workspace_bytes, void* stream,
+                             const int64_t* query_group, const int64_t* bank_group, int flags);
 
 /* ---- embedding layout: a deterministic UMAP map of the kNN graph (csrc/layout.hip) ---- */
 

@@ -50,6 +50,8 @@ SYMBOLS = [
     "btsbot_embed_width", "btsbot_forward_embed",
     "btsbot_knn_bank_bytes", "btsbot_knn_pack_bank", "btsbot_knn_splits", "btsbot_knn_workspace", "btsbot_knn_query",
     "btsbot_knn_workspace_grouped", "btsbot_knn_query_grouped",
+    "btsbot_knn_radius_workspace", "btsbot_knn_radius_count", "btsbot_knn_radius_fill",
+    "btsbot_graph_components", "btsbot_dbscan_labels",
     "btsbot_layout_smooth_knn", "btsbot_layout_symmetrize_workspace", "btsbot_layout_symmetrize", "btsbot_layout_init",
     "btsbot_layout_epochs", "btsbot_layout_smooth_knn_query", "btsbot_layout_transform",
 ]
@@ -283,6 +285,17 @@ def lib() -> C.CDLL:
     L.btsbot_knn_workspace_grouped.argtypes = [i64, i64, i32, i32, i32, i32]
     L.btsbot_knn_query_grouped.restype = i32
     L.btsbot_knn_query_grouped.argtypes = L.btsbot_knn_query.argtypes + [vp, vp, i32]
+    L.btsbot_knn_radius_workspace.restype = i64
+    L.btsbot_knn_radius_workspace.argtypes = [i64, i32]
+    L.btsbot_knn_radius_count.restype = i32
+    L.btsbot_knn_radius_count.argtypes = [vp, i64, vp, i64, i32, i32, vp, i64, i32, vp, vp, i32, vp, vp, i64, vp]
+    L.btsbot_knn_radius_fill.restype = i32
+    L.btsbot_knn_radius_fill.argtypes = [vp, i64, vp, vp, i64, i32, i32, vp, i64, i32, vp, vp, i32, vp, vp, i64, vp, vp, vp,
+                                         vp, vp, i64, vp]
+    L.btsbot_graph_components.restype = i32
+    L.btsbot_graph_components.argtypes = [vp, vp, vp, i64, vp, vp, vp]
+    L.btsbot_dbscan_labels.restype = i32
+    L.btsbot_dbscan_labels.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp]
     L.btsbot_layout_smooth_knn.restype = i32
     L.btsbot_layout_smooth_knn.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp]
     L.btsbot_layout_symmetrize_workspace.restype = i64

@@ -17,7 +17,8 @@
 // terms first (gemm_x2.hip).  The scale is per ROW, so a row's image depends on nothing but the row: an index built by
 // several adds equals one built at once, and a query's answer does not depend on its neighbours in the batch.  A packed row
 // is one record of 16 + 4 * dp bytes (dp = dim rounded up to 32, zero filled):
-//   float bias, float scale, 8 bytes unused, f16 head[dp], f16 remainder[dp]
+//   float bias, float scale, 8 bytes (bank rows: unused; query rows: |q|^2 and 1 / (2 |q|), for the radius passes),
+//   f16 head[dp], f16 remainder[dp]
 // bank rows: bias = |b|^2 and scale = 2^-e (Euclidean), bias = 0 and scale = 2^-e / |b| (cosine; 0 for a zero row); a row
 // that holds a non-finite value, or whose squared norm is not finite in fp32, has bias = +inf, scale = 0 and a zero image:
 // its score is +inf and +inf is never kept.  Query rows: scale = 2^(1-e) (0 and a zero image for a non-finite row, which
@@ -57,6 +58,10 @@
 // ranks among these: a group's best over the whole bank is its best split-best, and a row that is not its group's best
 // has k groups' bests of one split before it, each represented in the pool by a kept entry no worse -- rank >= k.  The
 // answer is the same whatever `splits` is.
+//
+// Radius search (btsbot_knn_radius_*): the same grid and tile walk with the epilogue "admit if
+// within r" -- see knn_radius_kernel -- and direct_distance(), the one function that computes a returned distance, for
+// the merge's winners and for every radius candidate alike.
 #include <float.h>
 
 #include "common.h"
@@ -141,9 +146,11 @@ __global__ __launch_bounds__(256) void knn_pack_kernel(const float* __restrict__
     }
   }
   if (lane == 0) {
-    float bias = 0.f, scale = 0.f;
+    float bias = 0.f, scale = 0.f, qq = 0.f, qinv = 0.f;   // qq, qinv: query records only (the radius passes)
     if (mode == MODE_QUERY) {
       scale = ok ? ldexpf(1.f, 1 - e) : 0.f;
+      qq = ok ? ss : 0.f;
+      qinv = ok && ss > 0.f ? 0.5f / sqrtf(ss) : 0.f;
     } else if (!ok) {
       bias = __builtin_inff();
     } else if (mode == MODE_BANK_L2) {
@@ -152,7 +159,7 @@ __global__ __launch_bounds__(256) void knn_pack_kernel(const float* __restrict__
     } else {
       scale = ss > 0.f ? ldexpf(1.f, -e) / sqrtf(ss) : 0.f;
     }
-    *reinterpret_cast<float4*>(rec) = make_float4(bias, scale, 0.f, 0.f);
+    *reinterpret_cast<float4*>(rec) = make_float4(bias, scale, qq, qinv);
   }
 }
 
@@ -173,6 +180,112 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");   // (no LDS read of the next phase moves above the barrier)
 }
+
+// A workgroup's walk over its bank tiles, the selection kernel's statements as a struct for the radius kernels (the
+// selection keeps its own text, see there): the operand registers of the K tile in flight (loaded under the products of
+// the one before) and the 128 x 128 x dp products of one bank tile.
+// products() leaves behind an lds_barrier: the operand planes are idle and may be used by the caller's epilogue, which
+// must end with a barrier of its own if it writes there.
+struct TileWalk {
+  static constexpr int MI = 4, NI = 4;     // 16-row fragments per wave: queries (B operand), bank rows (A operand)
+  static constexpr int CH = TQ * 8 / 256;  // 16-byte chunks per thread, plane and K tile (TQ == TB)
+  const unsigned char* qimg;
+  const unsigned char* bimg;
+  unsigned char* smem;
+  long Q, q0;
+  int N, dp, nk, tid;
+  size_t rec;
+  uint4 qh[CH], ql[CH], bh[CH], bl[CH];
+
+  __device__ __forceinline__ void init(const unsigned char* qi, const unsigned char* bi, unsigned char* lds, long nq,
+                                       long first_q, int nb, int dim) {
+    qimg = qi;
+    bimg = bi;
+    smem = lds;
+    Q = nq;
+    q0 = first_q;
+    N = nb;
+    dp = padded_dim(dim);
+    nk = (dp + BK - 1) / BK;
+    tid = threadIdx.x;
+    rec = record_bytes(dim);
+  }
+  __device__ __forceinline__ void gload(int tile, int kt) {
+    const int k0 = kt * BK;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      const int c = tid + i * 256, row = c >> 3, gk = k0 + (c & 7) * 8;
+      const long gq = q0 + row;
+      const long gb = (long)tile * TB + row;
+      const bool kin = gk < dp;   // (dp % 8 == 0: a chunk is wholly inside or wholly outside)
+      const unsigned char* pq = qimg + gq * rec + HDR + gk * 2;
+      const unsigned char* pb = bimg + gb * rec + HDR + gk * 2;
+      const bool okq = kin && gq < Q, okb = kin && gb < N;
+      qh[i] = okq ? *reinterpret_cast<const uint4*>(pq) : make_uint4(0, 0, 0, 0);
+      ql[i] = okq ? *reinterpret_cast<const uint4*>(pq + 2 * dp) : make_uint4(0, 0, 0, 0);
+      bh[i] = okb ? *reinterpret_cast<const uint4*>(pb) : make_uint4(0, 0, 0, 0);
+      bl[i] = okb ? *reinterpret_cast<const uint4*>(pb + 2 * dp) : make_uint4(0, 0, 0, 0);
+    }
+  }
+  __device__ __forceinline__ void sstore() {
+    unsigned char* Qh = smem;
+    unsigned char* Ql = Qh + TQ * ROWB;
+    unsigned char* Bh = Ql + TQ * ROWB;
+    unsigned char* Bl = Bh + TB * ROWB;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      const int c = tid + i * 256;
+      const int o = swz(c >> 3, c & 7);
+      *reinterpret_cast<uint4*>(Qh + o) = qh[i];
+      *reinterpret_cast<uint4*>(Ql + o) = ql[i];
+      *reinterpret_cast<uint4*>(Bh + o) = bh[i];
+      *reinterpret_cast<uint4*>(Bl + o) = bl[i];
+    }
+  }
+  // acc[ni][mi] = the products of bank tile `tile` (gload(tile, 0) has been issued); loads the next tile's first operands
+  __device__ __forceinline__ void products(f32x4 (&acc)[NI][MI], int tile, int t_end) {
+    const unsigned char* Qh = smem;
+    const unsigned char* Ql = Qh + TQ * ROWB;
+    const unsigned char* Bh = Ql + TQ * ROWB;
+    const unsigned char* Bl = Bh + TB * ROWB;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int lrow = lane & 15, lq = lane >> 4;
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    for (int kt = 0; kt < nk; ++kt) {
+      sstore();
+      __syncthreads();
+      if (kt + 1 < nk) gload(tile, kt + 1);
+      else if (tile + 1 < t_end) gload(tile + 1, 0);
+#pragma unroll 1   // (unrolled, the fragments of both halves are loaded up front: 56 registers to scratch)
+      for (int ks = 0; ks < BK / 32; ++ks) {
+        if (kt * BK + ks * 32 < dp) {
+          h2x8 bfr[MI];
+#pragma unroll
+          for (int mi = 0; mi < MI; ++mi) {
+            const int o = swz(wm * 64 + mi * 16 + lrow, ks * 4 + lq);
+            bfr[mi].hi = *reinterpret_cast<const f16x8*>(Qh + o);
+            bfr[mi].lo = *reinterpret_cast<const f16x8*>(Ql + o);
+          }
+#pragma unroll
+          for (int ni = 0; ni < NI; ++ni) {
+            const int o = swz(wn * 64 + ni * 16 + lrow, ks * 4 + lq);
+            h2x8 afr;
+            afr.hi = *reinterpret_cast<const f16x8*>(Bh + o);
+            afr.lo = *reinterpret_cast<const f16x8*>(Bl + o);
+#pragma unroll
+            for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = mma_x2(afr, bfr[mi], acc[ni][mi]);
+          }
+        }
+      }
+      lds_barrier();
+    }
+  }
+};
 
 // A list is the k best by (score, index) of what it was offered, UNSORTED (the merge ranks by counting), with its worst
 // entry (ts, ti) at position tp: a better candidate replaces the worst, then the worst is looked up again -- k independent
@@ -292,6 +405,9 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
     }
   }
 
+  // (the operand loads and the products below are TileWalk's, kept in this kernel's own text: routed through the
+  //  struct the same statements allocate registers differently -- scratch 172 -> 156, 280 -> 288 bytes -- and this
+  //  kernel's figures are held fixed)
   uint4 qh[CH], ql[CH], bh[CH], bl[CH];
   auto gload = [&](int tile, int kt) {
     const int k0 = kt * BK;
@@ -463,6 +579,52 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// The distance the library returns, in the direct form from the fp32 rows, by one wave: xv = the query row (element
+// j * 64 + lane in xv[j], zero past dim), qq = its squared norm (wave_sum of the lanes' fma chains), y = the bank row.
+// Lane-strided fma chains, the fixed butterfly, a correctly rounded sqrtf.  The merge applies it to the rows it returns
+// and the radius search decides membership by it: one function, so the two agree bit for bit.
+__device__ __forceinline__ float direct_distance(const float (&xv)[MAX_DIM / 64], float qq, const float* __restrict__ y,
+                                                 int dim, int metric, int lane) {
+  float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+  for (int jj = 0; jj < MAX_DIM / 64; ++jj) {
+    const int d = jj * 64 + lane;
+    if (d < dim) {
+      const float yv = y[d];
+      if (metric == 0) {
+        const float t = xv[jj] - yv;
+        a0 = fmaf(t, t, a0);
+      } else {
+        a0 = fmaf(xv[jj], yv, a0);
+        a1 = fmaf(yv, yv, a1);
+      }
+    }
+  }
+  a0 = wave_sum(a0);
+  if (metric == 0) return sqrtf(a0);
+  a1 = wave_sum(a1);
+  const float c = qq > 0.f && a1 > 0.f ? (a0 / sqrtf(qq)) / sqrtf(a1) : 0.f;
+  return 1.f - c;
+}
+
+// the query row of a wave as direct_distance takes it; false for a row that holds a non-finite value or whose squared
+// norm is not finite (the selection saw a zero image for it)
+__device__ __forceinline__ bool load_query_row(const float* __restrict__ x, int dim, int lane, float (&xv)[MAX_DIM / 64],
+                                               float& qq) {
+  bool fin = true;
+  qq = 0.f;
+#pragma unroll
+  for (int j = 0; j < MAX_DIM / 64; ++j) {
+    const int d = j * 64 + lane;
+    xv[j] = d < dim ? x[d] : 0.f;
+    fin = fin && fabsf(xv[j]) <= FLT_MAX;
+    qq = fmaf(xv[j], xv[j], qq);
+  }
+  qq = wave_sum(qq);
+  return __all(fin) && qq <= FLT_MAX;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // merge: one wave per query
 template <int GM>
 __global__ __launch_bounds__(64) void knn_merge_kernel(const float* __restrict__ queries, const float* __restrict__ bank,
@@ -479,17 +641,8 @@ __global__ __launch_bounds__(64) void knn_merge_kernel(const float* __restrict__
   float* od = dist + q * k;
 
   float xv[MAX_DIM / 64];
-  bool fin = true;
-  float qq = 0.f;
-#pragma unroll
-  for (int j = 0; j < MAX_DIM / 64; ++j) {
-    const int d = j * 64 + lane;
-    xv[j] = d < dim ? x[d] : 0.f;
-    fin = fin && fabsf(xv[j]) <= FLT_MAX;
-    qq = fmaf(xv[j], xv[j], qq);
-  }
-  qq = wave_sum(qq);
-  if (!__all(fin) || !(qq <= FLT_MAX)) {   // (the selection saw a zero image for this row)
+  float qq;
+  if (!load_query_row(x, dim, lane, xv, qq)) {   // (the selection saw a zero image for this row)
     if (lane < k) {
       oi[lane] = -1;
       od[lane] = __builtin_nanf("");
@@ -546,31 +699,7 @@ __global__ __launch_bounds__(64) void knn_merge_kernel(const float* __restrict__
     const int b = win[j];
     if (b == EMPTY) break;   // (the ranks are dense: winners fill win[] from the front)
     nwin = j + 1;
-    const float* y = bank + (long)b * dim;
-    float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-    for (int jj = 0; jj < MAX_DIM / 64; ++jj) {
-      const int d = jj * 64 + lane;
-      if (d < dim) {
-        const float yv = y[d];
-        if (metric == 0) {
-          const float t = xv[jj] - yv;
-          a0 = fmaf(t, t, a0);
-        } else {
-          a0 = fmaf(xv[jj], yv, a0);
-          a1 = fmaf(yv, yv, a1);
-        }
-      }
-    }
-    a0 = wave_sum(a0);
-    float dj;
-    if (metric == 0) {
-      dj = sqrtf(a0);
-    } else {
-      a1 = wave_sum(a1);
-      const float c = qq > 0.f && a1 > 0.f ? (a0 / sqrtf(qq)) / sqrtf(a1) : 0.f;
-      dj = 1.f - c;
-    }
+    const float dj = direct_distance(xv, qq, bank + (long)b * dim, dim, metric, lane);
     if (lane == 0) wdist[j] = dj;
   }
   __syncthreads();
@@ -585,6 +714,178 @@ __global__ __launch_bounds__(64) void knn_merge_kernel(const float* __restrict__
     } else {
       oi[lane] = -1;
       od[lane] = __builtin_inff();
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// radius search (btsbot_knn_radius_*): the selection's grid and tile walk with a second epilogue,
+// "admit if within r" in place of "keep the best k".  A pair is a CANDIDATE when its GEMM-form value
+//   Euclidean  g = score + |q|^2            <= lim = r^2 * rel + ctau * (|q|^2 + |b|^2)
+//   cosine     g = 1 + score / (2 |q|)      <= lim = r + ctau
+// (rel = 1 + 4 (D + 4) u, ctau = 8 (D + 8) u; cosine ctau = 16 (D + 8) u: the margin of 4p, which covers the error
+// bounds of this form and of the direct form) -- a superset of the members, decided by the same expression in both
+// instantiations.  FILL = false counts a (query, split)'s candidates; FILL = true writes their bank rows into the region
+// the scan of the counts gave it, slots handed out by an LDS cursor per query row (the order inside a region is no
+// one's business: the lists are sorted afterwards), each slot checked against the region's size.  No list of fixed
+// size, nothing of size Q x N.  knn_radius_verify_kernel then applies direct_distance to every candidate.
+template <bool FILL, bool EXCL>
+__global__ __launch_bounds__(256, 2) void knn_radius_kernel(const unsigned char* __restrict__ qimg,
+                                                            const unsigned char* __restrict__ bimg, long Q, int N,
+                                                            int dim, int metric, const float* __restrict__ radius,
+                                                            float rel, float ctau, long self_offset,
+                                                            int tiles_per_split, int splits,
+                                                            const long long* __restrict__ qgrp,
+                                                            const long long* __restrict__ bgrp, int* counts,
+                                                            const long long* __restrict__ offsets,
+                                                            int* __restrict__ cand, long long n_cand,
+                                                            int* __restrict__ err) {
+  constexpr int MI = TileWalk::MI, NI = TileWalk::NI;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  int* rowcnt = reinterpret_cast<int*>(smem + GEMM_LDS);          // [TQ] candidates so far (FILL: the row's cursor)
+  int* rowcap = rowcnt + TQ;                                      // [TQ] FILL: the size of the row's region
+  long long* rowbase = reinterpret_cast<long long*>(rowcap + TQ); // [TQ] FILL: where it starts in cand
+  long long* tg = reinterpret_cast<long long*>(smem);             // EXCL: [TB] the tile's bank groups (idle operand LDS)
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int lrow = lane & 15, lq = lane >> 4;
+  const size_t rec = record_bytes(dim);
+  const long q0 = (long)blockIdx.x * TQ;
+  const int split = blockIdx.y;
+  const int total_tiles = (N + TB - 1) / TB;
+  const int t_begin = (int)min((long)split * tiles_per_split, (long)total_tiles);
+  const int t_end = (int)min((long)(split + 1) * tiles_per_split, (long)total_tiles);
+  const int b_end = (int)min((long)t_end * TB, (long)N);
+
+  if (tid < TQ) {
+    rowcnt[tid] = 0;
+    if constexpr (FILL) {
+      const bool in = q0 + tid < Q;
+      rowcap[tid] = in ? counts[(q0 + tid) * splits + split] : 0;
+      rowbase[tid] = in ? offsets[(q0 + tid) * splits + split] : 0;
+    }
+  }
+
+  float sq[MI], qq[MI], qinv[MI], lim[MI];   // the query record's scale, |q|^2, 1 / (2 |q|); r^2 * rel (cosine: r + ctau)
+  int selfb[MI];                             // the bank row that IS the query row (never a candidate), -1: none
+  long long qg[MI];                          // EXCL: the groups of the lane's four query rows
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    const long gq = q0 + wm * 64 + mi * 16 + lrow;
+    const float4 h = gq < Q ? *reinterpret_cast<const float4*>(qimg + gq * rec) : make_float4(0.f, 0.f, 0.f, 0.f);
+    sq[mi] = h.y;
+    qq[mi] = h.z;
+    qinv[mi] = h.w;
+    const float r = gq < Q ? radius[gq] : -1.f;
+    // a row past Q, a non-finite query row (scale 0) and a negative or NaN radius admit nothing
+    lim[mi] = h.y != 0.f && r >= 0.f ? (metric == 0 ? (r * r) * rel : r + ctau) : -__builtin_inff();
+    const long sb = gq + self_offset;
+    selfb[mi] = self_offset >= 0 && sb < N ? (int)sb : -1;
+    if constexpr (EXCL) qg[mi] = gq < Q ? qgrp[gq] : 0;
+  }
+
+  int n[MI] = {0, 0, 0, 0};
+  bool past = false;
+  TileWalk w;
+  w.init(qimg, bimg, smem, Q, q0, N, dim);
+  if (t_begin < t_end) w.gload(t_begin, 0);
+  __syncthreads();   // the rows' counters and regions
+  for (int tile = t_begin; tile < t_end; ++tile) {
+    const int b0 = tile * TB;
+    long long gt = 0;   // EXCL: bank row b0 + tid's group, in flight under the products
+    if constexpr (EXCL) {
+      if (tid < TB && (long)b0 + tid < N) gt = bgrp[(long)b0 + tid];
+    }
+    f32x4 acc[NI][MI];
+    w.products(acc, tile, t_end);
+    if constexpr (EXCL) {
+      if (tid < TB) tg[tid] = gt;
+      lds_barrier();
+    }
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni) {
+      float nb[4], sb[4];   // the fragment's bank biases and scales: rows b0 + wn * 64 + ni * 16 + lq * 4 + i
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int b = b0 + wn * 64 + ni * 16 + lq * 4 + i;
+        const float2 h = b < N ? *reinterpret_cast<const float2*>(bimg + (size_t)b * rec)
+                               : make_float2(__builtin_inff(), 0.f);
+        nb[i] = h.x;
+        sb[i] = h.y;
+      }
+      long long bg[4];
+      if constexpr (EXCL) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) bg[i] = tg[wn * 64 + ni * 16 + lq * 4 + i];
+      }
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int gb = b0 + wn * 64 + ni * 16 + lq * 4 + i;
+          const float s = fmaf(-(acc[ni][mi][i] * sq[mi]), sb[i], nb[i]);
+          float g, l;
+          if (metric == 0) {
+            g = s + qq[mi];
+            l = fmaf(ctau, qq[mi] + nb[i], lim[mi]);
+          } else {
+            g = fmaf(s, qinv[mi], 1.f);
+            l = lim[mi];
+          }
+          bool in = g <= l && s < __builtin_inff() && gb < b_end && gb != selfb[mi];
+          if constexpr (EXCL) in = in && bg[i] != qg[mi];
+          if (in) {
+            if constexpr (FILL) {
+              const int row = wm * 64 + mi * 16 + lrow;
+              const int slot = atomicAdd(&rowcnt[row], 1);
+              const long long at = rowbase[row] + slot;
+              if (slot < rowcap[row] && at >= 0 && at < n_cand) cand[at] = gb;
+              else past = true;   // (never, while counts / offsets are the count pass's: the same arithmetic)
+            } else {
+              ++n[mi];
+            }
+          }
+        }
+    }
+    if constexpr (EXCL) lds_barrier();   // the groups are read: the next tile's operands may land there
+  }
+
+  if constexpr (FILL) {
+    if (past) *err = 1;
+  } else {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+      if (n[mi] != 0) atomicAdd(&rowcnt[wm * 64 + mi * 16 + lrow], n[mi]);
+    __syncthreads();
+    if (tid < TQ && q0 + tid < Q) counts[(q0 + tid) * splits + split] = rowcnt[tid];
+  }
+}
+
+// one wave per candidate in turn: grid (query, Y), wave y takes the query's candidates y, y + Y, ...
+__global__ __launch_bounds__(64) void knn_radius_verify_kernel(const float* __restrict__ queries,
+                                                               const float* __restrict__ bank,
+                                                               const float* __restrict__ radius,
+                                                               const long long* __restrict__ offsets, int splits,
+                                                               const int* __restrict__ cand, int N, int dim, int metric,
+                                                               float* __restrict__ dist,
+                                                               unsigned char* __restrict__ keep) {
+  const int lane = threadIdx.x;
+  const long q = blockIdx.x;
+  const long long c1 = offsets[(q + 1) * splits];
+  long long c = offsets[q * splits] + blockIdx.y;
+  if (c >= c1) return;
+  float xv[MAX_DIM / 64];
+  float qq;
+  const bool ok = load_query_row(queries + q * dim, dim, lane, xv, qq);   // (a row that is not has no candidates)
+  const float r = radius[q];
+  for (; c < c1; c += gridDim.y) {
+    const int b = cand[c];
+    const bool have = b >= 0 && b < N;   // (a slot the fill did not reach: it raised the error flag)
+    const float d = have ? direct_distance(xv, qq, bank + (long)b * dim, dim, metric, lane) : __builtin_nanf("");
+    if (lane == 0) {
+      dist[c] = d;
+      keep[c] = ok && have && d <= r ? 1 : 0;
     }
   }
 }
@@ -771,4 +1072,145 @@ extern "C" int btsbot_knn_query_grouped(const float* queries, int64_t n_query, c
                                         void* stream, const int64_t* query_group, const int64_t* bank_group, int flags) {
   return query_checked("btsbot_knn_query_grouped", queries, n_query, bank, packed, n_bank, dim, k, metric, self_offset,
                        splits, idx, dist, workspace, workspace_bytes, query_group, bank_group, flags, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// radius search: the entry points
+namespace {
+
+struct RadiusArgs {
+  const float* queries;
+  int64_t n_query;
+  const void* packed;
+  int64_t n_bank;
+  int dim, metric;
+  const float* radius;
+  int64_t self_offset;
+  int splits;
+  const int64_t* query_group;
+  const int64_t* bank_group;
+  int flags;
+  void* workspace;
+  int64_t workspace_bytes;
+};
+
+int radius_checked(const char* who, const RadiusArgs& a) {
+  TRY(check_shape(who, a.n_query, a.n_bank, a.dim, 1));
+  if (a.metric != BTSBOT_KNN_EUCLIDEAN && a.metric != BTSBOT_KNN_COSINE) {
+    btsbot_set_error("%s: metric %d", who, a.metric);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (a.splits < 1 || a.splits > MAX_SPLITS) {
+    btsbot_set_error("%s: splits=%d must be 1 .. %d", who, a.splits, MAX_SPLITS);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if ((a.flags & ~GM_EXCLUDE) != 0) {
+    btsbot_set_error("%s: flags=%d, only 0 and BTSBOT_KNN_EXCLUDE_SAME are radius modes", who, a.flags);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (a.n_query == 0) return BTSBOT_OK;
+  if (a.queries == nullptr || a.radius == nullptr || a.workspace == nullptr || (a.n_bank > 0 && a.packed == nullptr)) {
+    btsbot_set_error("%s: NULL argument", who);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (a.flags != 0 && (a.query_group == nullptr || (a.n_bank > 0 && a.bank_group == nullptr))) {
+    btsbot_set_error("%s: BTSBOT_KNN_EXCLUDE_SAME needs query_group and bank_group, got NULL", who);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  const int64_t need = (int64_t)image_bytes(a.n_query, a.dim);
+  if (a.workspace_bytes < need || ((uintptr_t)a.workspace & 15) != 0 || ((uintptr_t)a.packed & 15) != 0) {
+    btsbot_set_error("%s: workspace of %lld bytes (need %lld), or workspace / packed not 16-byte aligned", who,
+                     (long long)a.workspace_bytes, (long long)need);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  return BTSBOT_OK;
+}
+
+// query pack + one tile pass (FILL = false: counts are written; true: counts and offsets are read, cand is written)
+template <bool FILL, bool EXCL>
+int launch_radius(const RadiusArgs& a, int* counts, const int64_t* offsets, int* cand, int64_t n_cand, int* err,
+                  hipStream_t st) {
+  unsigned char* qimg = reinterpret_cast<unsigned char*>(a.workspace);
+  hipLaunchKernelGGL(knn_pack_kernel, dim3((unsigned)((a.n_query + 3) / 4)), dim3(256), 0, st, a.queries, (long)a.n_query,
+                     a.dim, (int)MODE_QUERY, qimg);
+  LAUNCH_CHECK();
+  constexpr int LDS = GEMM_LDS + TQ * 16;   // operands + per query row: counter, region size, region start
+  static DevOnce attr;
+  if (attr.need()) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_radius_kernel<FILL, EXCL>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+    attr.done();
+  }
+  // the margin of DESIGN.md 4p; u = 2^-24
+  const float u = 5.9604644775390625e-8f;
+  const bool cosine = a.metric == BTSBOT_KNN_COSINE;
+  const float rel = 1.f + 4.f * (float)(a.dim + 4) * u;
+  const float ctau = (cosine ? 16.f : 8.f) * (float)(a.dim + 8) * u;
+  const int total_tiles = (int)((a.n_bank + TB - 1) / TB);
+  const int tps = (total_tiles + a.splits - 1) / a.splits;
+  hipLaunchKernelGGL((knn_radius_kernel<FILL, EXCL>), dim3((unsigned)((a.n_query + TQ - 1) / TQ), (unsigned)a.splits),
+                     dim3(256), LDS, st, (const unsigned char*)qimg, reinterpret_cast<const unsigned char*>(a.packed),
+                     (long)a.n_query, (int)a.n_bank, a.dim, a.metric, a.radius, rel, ctau, (long)a.self_offset, tps,
+                     a.splits, reinterpret_cast<const long long*>(a.query_group),
+                     reinterpret_cast<const long long*>(a.bank_group), counts,
+                     reinterpret_cast<const long long*>(offsets), cand, (long long)n_cand, err);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t btsbot_knn_radius_workspace(int64_t n_query, int dim) {
+  if (check_shape("btsbot_knn_radius_workspace", n_query, 0, dim, 1) != BTSBOT_OK) return BTSBOT_ERR_INVALID_ARG;
+  return (int64_t)image_bytes(n_query, dim);
+}
+
+extern "C" int btsbot_knn_radius_count(const float* queries, int64_t n_query, const void* packed, int64_t n_bank, int dim,
+                                       int metric, const float* radius, int64_t self_offset, int splits,
+                                       const int64_t* query_group, const int64_t* bank_group, int flags, int32_t* counts,
+                                       void* workspace, int64_t workspace_bytes, void* stream) {
+  const RadiusArgs a{queries, n_query, packed, n_bank, dim, metric, radius, self_offset, splits, query_group, bank_group,
+                     flags, workspace, workspace_bytes};
+  TRY(radius_checked("btsbot_knn_radius_count", a));
+  if (n_query == 0) return BTSBOT_OK;
+  if (counts == nullptr) {
+    btsbot_set_error("btsbot_knn_radius_count: NULL counts");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  return flags != 0 ? launch_radius<false, true>(a, counts, nullptr, nullptr, 0, nullptr, st)
+                    : launch_radius<false, false>(a, counts, nullptr, nullptr, 0, nullptr, st);
+}
+
+extern "C" int btsbot_knn_radius_fill(const float* queries, int64_t n_query, const float* bank, const void* packed,
+                                      int64_t n_bank, int dim, int metric, const float* radius, int64_t self_offset,
+                                      int splits, const int64_t* query_group, const int64_t* bank_group, int flags,
+                                      const int32_t* counts, const int64_t* offsets, int64_t n_cand, int32_t* cand,
+                                      float* dist, uint8_t* keep, int32_t* error_flag, void* workspace,
+                                      int64_t workspace_bytes, void* stream) {
+  const RadiusArgs a{queries, n_query, packed, n_bank, dim, metric, radius, self_offset, splits, query_group, bank_group,
+                     flags, workspace, workspace_bytes};
+  TRY(radius_checked("btsbot_knn_radius_fill", a));
+  if (n_cand < 0) {
+    btsbot_set_error("btsbot_knn_radius_fill: n_cand=%lld", (long long)n_cand);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (n_query == 0 || n_cand == 0) return BTSBOT_OK;
+  if (bank == nullptr || counts == nullptr || offsets == nullptr || cand == nullptr || dist == nullptr || keep == nullptr ||
+      error_flag == nullptr) {
+    btsbot_set_error("btsbot_knn_radius_fill: NULL argument");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  int* cnt = const_cast<int*>(counts);   // (read only by the FILL instantiation)
+  TRY(flags != 0 ? (launch_radius<true, true>(a, cnt, offsets, cand, n_cand, error_flag, st))
+                 : (launch_radius<true, false>(a, cnt, offsets, cand, n_cand, error_flag, st)));
+  // enough waves per query that a crowded row does not serialise: its candidates are shared out over Y waves
+  const int64_t per = (n_cand + n_query - 1) / n_query;
+  const unsigned Y = (unsigned)(per <= 32 ? 1 : per >= 32 * 64 ? 64 : (per + 31) / 32);
+  hipLaunchKernelGGL(knn_radius_verify_kernel, dim3((unsigned)n_query, Y), dim3(64), 0, st, queries, bank, radius,
+                     reinterpret_cast<const long long*>(offsets), splits, (const int*)cand, (int)n_bank, dim, metric, dist,
+                     keep);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
 }

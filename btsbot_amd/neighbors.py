@@ -30,6 +30,26 @@ only its nearest row (by the ranking of the candidates: selection score, then in
 groups, ordered by (dist, index) of these rows; it holds ``k <= 32``.  Both may be combined.  A non-finite bank row is
 never a group's representative.  Both happen inside the selection kernel: the answer is exact however many alerts an
 object has, and keeps every property above (``splits``, batch cuts, runs, incremental ``add``).
+
+Everything within r.  The second question of an archive: not the k nearest, all rows within ``r``.
+
+    indptr, indices, dist = index.radius(queries, r)             # a CSR: int64 [Q + 1], int64 [T], float32 [T]
+    counts = index.count_within(queries, r)                      # int64 [Q] == indptr.diff(); 0 is novelty
+    indptr, indices, dist = radius_neighbors(queries, bank, r)   # packs the bank for this one call
+    indptr, indices, dist = radius_graph(emb, r, include_self=True)
+
+Bank row b is in query row q's list if and only if b is eligible (finite, not the position ``self_offset`` masks, not of
+q's group under ``exclude_same_group``) and the direct-form fp32 distance -- the device function ``query`` applies to the
+rows it returns -- is ``<= r``, compared in fp32.  Hence ``dist`` is bit-identical to ``query``'s for the same pair; the
+rows of ``query(q, k)`` with ``dist <= r`` are the head of the list sorted by (dist, index); identical rows are at exactly
+0 and ``r = 0`` returns the duplicates; a non-finite query row has an empty list; and a row's list does not depend, bit
+for bit, on the other rows of the call, on ``splits``, on the run or on how the index was built.  ``r`` is a float
+(rounded to fp32 once) or a float tensor [Q] of per-row radii; negative or NaN is a ``ValueError``, ``+inf`` returns every
+finite eligible row; for the cosine metric it is in ``1 - cos``.  Two tile passes count and write the candidates -- pairs
+whose GEMM-form value is within ``r^2`` plus a margin that covers the error of both forms --, a third kernel computes
+their direct-form distances, torch compacts and orders; nothing of size Q x N is written, the host is read twice (to
+size the candidates, then the lists).  The margin grows with ``|q|^2 + |b|^2``: centre the rows (``rows - rows.mean(0)``),
+or data far from the origin relative to its spread verifies most pairs -- exactly, and slowly.
 """
 from __future__ import annotations
 
@@ -219,6 +239,179 @@ class EmbeddingIndex:
                 _lib.check(L.btsbot_knn_query_grouped(*args, _ptr(query_groups), _ptr(self._groups), flags),
                            "btsbot_knn_query_grouped")
         return idx, dist
+
+    def radius(self, queries: torch.Tensor, r, *, query_groups: Optional[torch.Tensor] = None,
+               exclude_same_group: bool = False, self_offset: int = -1, sort: str = "index", splits: int = 0,
+               max_total: Optional[int] = None,
+               stats: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Every row of the index within ``r`` of each query row, as a CSR: ``indptr`` int64 [Q + 1], ``indices`` int64
+        [T], ``dist`` float32 [T] (see the module text).  r: a float, or a float tensor [Q] of per-row radii.
+        sort: ``"index"`` orders a row's list by bank index, ``"distance"`` by (dist, index).  max_total: ValueError
+        (naming the total) instead of lists longer than this in all.  stats: a dict that receives ``candidates`` (the
+        pairs whose distance was computed in the direct form), ``total`` and ``error_flag`` (the fill kernel's bounds
+        check; 0, or the call raises).  The other arguments are ``query``'s.  Two host reads: the number of
+        candidates, then the total, each to allocate."""
+        _check_radius_args(r, int(queries.shape[0]) if isinstance(queries, torch.Tensor) and queries.dim() == 2 else None,
+                           sort, splits, max_total)
+        flags = _check_group_args(1, self._groups is not None, query_groups, exclude_same_group, False)
+        q = _rows(queries, "queries", self.device)
+        if q.shape[1] != self.dim:
+            raise ValueError(f"queries: D = {q.shape[1]}, the index holds D = {self.dim}")
+        if not isinstance(self_offset, int):
+            raise ValueError(f"self_offset must be an int, got {self_offset!r}")
+        nq, n, dev = int(q.shape[0]), self._n, self.device
+        if query_groups is not None:
+            query_groups = _groups(query_groups, "query_groups", nq, dev)
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            if isinstance(r, torch.Tensor):
+                if r.device != dev:
+                    raise ValueError(f"r is on {r.device}, the index on {dev}")
+                rad = r.detach().to(torch.float32).contiguous()
+                bad = (~(rad >= 0)).any().to(torch.int64)
+            else:
+                rad = torch.full((nq,), float(r), dtype=torch.float32, device=dev)   # rounded to fp32 once
+                bad = torch.zeros((), dtype=torch.int64, device=dev)
+            if splits == 0:
+                splits = max(1, int(L.btsbot_knn_splits(max(nq, 1), n, self.dim, 1)))
+            counts = torch.zeros((nq, splits), dtype=torch.int32, device=dev)
+            need = int(L.btsbot_knn_radius_workspace(nq, self.dim))
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+            head = (_ptr(q), nq)
+            tail = (_ptr(self._packed), n, self.dim, self._metric_id, _ptr(rad), self_offset, splits,
+                    _ptr(query_groups) if flags else None, _ptr(self._groups) if flags else None, flags)
+            if nq and n:
+                _lib.check(L.btsbot_knn_radius_count(*head, *tail, _ptr(counts), _ptr(ws), need, self._stream()),
+                           "btsbot_knn_radius_count")
+            offsets = torch.zeros(nq * splits + 1, dtype=torch.int64, device=dev)
+            offsets[1:] = torch.cumsum(counts.view(-1), 0, dtype=torch.int64)
+            n_cand, bad = torch.stack([offsets[-1], bad]).tolist()          # the host read that sizes the candidates
+            if bad:
+                raise ValueError("r must be >= 0 in every row (and not NaN)")
+            cand = torch.zeros(n_cand, dtype=torch.int32, device=dev)
+            cdist = torch.empty(n_cand, dtype=torch.float32, device=dev)
+            keep = torch.zeros(n_cand, dtype=torch.uint8, device=dev)
+            err = torch.zeros(1, dtype=torch.int32, device=dev)
+            if n_cand:
+                _lib.check(L.btsbot_knn_radius_fill(*head, _ptr(self._bank), *tail, _ptr(counts), _ptr(offsets), n_cand,
+                                                    _ptr(cand), _ptr(cdist), _ptr(keep), _ptr(err), _ptr(ws), need,
+                                                    self._stream()), "btsbot_knn_radius_fill")
+            row_off = offsets[::splits]                                       # [Q + 1]: a row's candidates are contiguous
+            kept = torch.cat([offsets.new_zeros(1), torch.cumsum(keep, 0, dtype=torch.int64)])
+            indptr = kept[row_off]
+            total, flag = torch.stack([indptr[-1], err[0].to(torch.int64)]).tolist()   # the read that sizes the lists
+            if stats is not None:
+                stats.update(candidates=int(n_cand), total=int(total), error_flag=int(flag))
+            if flag:
+                raise RuntimeError("btsbot_knn_radius_fill: a candidate fell past the end of its region (the count and "
+                                   "the fill pass disagree); the lists are not returned")
+            if max_total is not None and total > max_total:
+                raise ValueError(f"the lists hold T = {total} entries, more than max_total = {max_total}")
+            rows = torch.repeat_interleave(torch.arange(nq, device=dev), row_off.diff(), output_size=n_cand)
+            order = _csr_order(rows, cand.to(torch.int64), cdist, max(n, 1), sort, keep=keep, total=total)
+            return indptr, cand[order].to(torch.int64), cdist[order]
+
+    def count_within(self, queries: torch.Tensor, r, **kw) -> torch.Tensor:
+        """int64 [Q]: how many rows of the index lie within ``r`` of each query row -- exact, the ``indptr.diff()`` of
+        ``radius`` with the same arguments (it goes through the lists; 0 is novelty, thousands a crowded region)."""
+        return self.radius(queries, r, **kw)[0].diff()
+
+
+SORTS = ("index", "distance")
+
+
+def _check_radius_args(r, n_query, sort, splits, max_total) -> None:
+    """ValueError for what ``radius`` cannot answer, before anything touches the device."""
+    if isinstance(r, torch.Tensor):
+        if not r.is_floating_point() or r.dim() != 1 or (n_query is not None and r.shape[0] != n_query):
+            raise ValueError(f"r as a tensor holds one float radius per query row, [{n_query}], got {r.dtype} "
+                             f"{tuple(r.shape)}")
+        if r.device.type == "cpu" and not bool((r >= 0).all()):
+            raise ValueError("r must be >= 0 in every row (and not NaN)")
+    elif isinstance(r, bool) or not isinstance(r, (int, float)) or not r >= 0:
+        raise ValueError(f"r must be a float >= 0 (and not NaN) or a tensor of them, got {r!r}")
+    if sort not in SORTS:
+        raise ValueError(f"sort must be one of {SORTS}, got {sort!r}")
+    if not isinstance(splits, int) or isinstance(splits, bool) or not 0 <= splits <= _lib.KNN_MAX_SPLITS:
+        raise ValueError(f"splits must be an int in 0..{_lib.KNN_MAX_SPLITS} (0: the library's choice), got {splits!r}")
+    if max_total is not None and (isinstance(max_total, bool) or not isinstance(max_total, int) or max_total < 0):
+        raise ValueError(f"max_total must be None or an int >= 0, got {max_total!r}")
+
+
+def _float_order(dist: torch.Tensor) -> torch.Tensor:
+    """int64 in [0, 2^32) that orders like the fp32 values (negative ones included: 1 - cos may round below 0)"""
+    b = dist.view(torch.int32).to(torch.int64)
+    ub = b & 0xFFFFFFFF
+    return torch.where(b < 0, 0xFFFFFFFF - ub, ub + 0x80000000)
+
+
+def _csr_order(rows, idx, dist, n_bank: int, sort: str, keep=None, total=None) -> torch.Tensor:
+    """The permutation that drops the entries ``keep`` rejects (``total`` stay) and orders the rest by row, then by
+    ``sort``: one sort by (row, index) does both, a second, stable one by (row, dist) gives the distance order."""
+    key = rows * n_bank + idx
+    if keep is not None:
+        key = torch.where(keep != 0, key, torch.full_like(key, torch.iinfo(torch.int64).max))
+    order = torch.sort(key).indices
+    if total is not None:
+        order = order[:total]
+    if sort == "distance":
+        order = order[torch.sort((rows[order] << 32) | _float_order(dist[order]), stable=True).indices]
+    return order
+
+
+def radius_neighbors(queries: torch.Tensor, bank: torch.Tensor, r, metric: str = "euclidean", *,
+                     bank_groups: Optional[torch.Tensor] = None, query_groups: Optional[torch.Tensor] = None,
+                     exclude_same_group: bool = False, sort: str = "index", splits: int = 0,
+                     max_total: Optional[int] = None,
+                     stats: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Every row of ``bank`` [N, D] within ``r`` of each row of ``queries`` [Q, D], as the CSR ``EmbeddingIndex.radius``
+    returns.  Packs the bank for this one call."""
+    _metric(metric)
+    _check_radius_args(r, int(queries.shape[0]) if isinstance(queries, torch.Tensor) and queries.dim() == 2 else None,
+                       sort, splits, max_total)
+    _check_group_args(1, bank_groups is not None, query_groups, exclude_same_group, False)
+    q = _rows(queries, "queries")
+    b = _rows(bank, "bank", q.device)
+    if q.shape[1] != b.shape[1]:
+        raise ValueError(f"queries have D = {q.shape[1]}, the bank D = {b.shape[1]}")
+    return EmbeddingIndex(b, metric, groups=bank_groups).radius(
+        q, r, query_groups=query_groups, exclude_same_group=exclude_same_group, sort=sort, splits=splits,
+        max_total=max_total, stats=stats)
+
+
+def radius_graph(emb: torch.Tensor, r, include_self: bool = True, metric: str = "euclidean", *,
+                 groups: Optional[torch.Tensor] = None, group_mode: str = "exclude", sort: str = "index",
+                 splits: int = 0, max_total: Optional[int] = None,
+                 stats: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Every row of ``emb`` [N, D] among the others within ``r``: the CSR of ``EmbeddingIndex.radius`` with N rows.
+    include_self=True: a finite row is in its own list at distance 0 (DBSCAN counts it); False: it is not, by
+    position -- its duplicates are.  groups / group_mode="exclude": the others are rows of OTHER groups only (the row
+    itself stays under include_self=True).  A non-finite row has an empty list."""
+    _metric(metric)
+    if group_mode != "exclude":
+        raise ValueError(f'radius lists know group_mode="exclude" only, got {group_mode!r}')
+    _check_radius_args(r, int(emb.shape[0]) if isinstance(emb, torch.Tensor) and emb.dim() == 2 else None, sort, splits,
+                       max_total)
+    rows = _rows(emb, "emb")
+    n = int(rows.shape[0])
+    kw = dict(sort=sort, splits=splits, max_total=max_total, stats=stats)
+    if groups is not None:
+        groups = _groups(groups, "groups", n, rows.device)
+        kw.update(query_groups=groups, exclude_same_group=True)
+    index = EmbeddingIndex(rows, metric, groups=groups)
+    if include_self and groups is None and metric == "euclidean":
+        return index.radius(rows, r, **kw)         # the row itself is a bank row at exactly 0
+    indptr, indices, dist = index.radius(rows, r, self_offset=0, **kw)
+    if not include_self:
+        return indptr, indices, dist
+    # the row itself, by position, at distance 0
+    finite = torch.isfinite(rows).all(dim=1) & torch.isfinite((rows * rows).sum(dim=1))
+    own = finite.nonzero().view(-1)
+    at = torch.repeat_interleave(torch.arange(n, device=rows.device), indptr.diff(), output_size=int(indices.shape[0]))
+    at, indices, dist = torch.cat([at, own]), torch.cat([indices, own]), torch.cat([dist, dist.new_zeros(own.shape[0])])
+    order = _csr_order(at, indices, dist, max(n, 1), sort)
+    indptr = indptr + torch.cat([indptr.new_zeros(1), torch.cumsum(finite, 0, dtype=torch.int64)])
+    return indptr, indices[order], dist[order]
 
 
 def embedding_neighbors(queries: torch.Tensor, bank: torch.Tensor, k: int, metric: str = "euclidean", *,

@@ -879,6 +879,59 @@ int btsbot_knn_query_grouped(const float* queries, int64_t n_query, const float*
                              float* dist, void* workspace, int64_t workspace_bytes, void* stream,
                              const int64_t* query_group, const int64_t* bank_group, int flags);
 
+/* ---- everything within r: radius search over the same packed bank (csrc/knn.hip) ---- */
+
+/* Bank row b belongs to query row q's list if and only if b is eligible (finite, not the row self_offset masks, not of
+ * q's group under BTSBOT_KNN_EXCLUDE_SAME) and the direct-form fp32 distance -- the function btsbot_knn_query applies to
+ * the rows it returns -- is <= radius[q], compared in fp32.  Two tile passes over the grid of btsbot_knn_query's
+ * selection (query tiles of 128 x splits) find the CANDIDATES, a superset: pairs whose GEMM-form value from the split
+ * f16 products is within radius^2 plus a margin that covers the error bounds of both forms; a third
+ * kernel computes every candidate's direct-form distance and marks the members.  Nothing of size n_query x n_bank is
+ * written.  queries, bank, packed, dim, metric, self_offset, query_group / bank_group: as btsbot_knn_query_grouped;
+ * flags: 0 or BTSBOT_KNN_EXCLUDE_SAME.  radius: fp32 [n_query] device memory, one per query row (a negative or NaN
+ * radius admits nothing).  splits: 1..32, the same value in both calls.  workspace: btsbot_knn_radius_workspace(n_query,
+ * dim) bytes, 16-byte aligned (the packed query rows; scratch afterwards).
+ *
+ * btsbot_knn_radius_count(): counts int32 [n_query][splits] = the candidates of each query row in each bank slice.
+ * Two launches (query pack, count).  The caller forms offsets int64 [n_query * splits + 1], the exclusive scan of counts
+ * with the total last, and reads the total n_cand to allocate.
+ *
+ * btsbot_knn_radius_fill(): the same walk with the same arithmetic writes the candidates' bank rows into cand int32
+ * [n_cand] (query q's are cand[offsets[q * splits] .. offsets[(q + 1) * splits]), in no particular order inside a
+ * slice), then dist fp32 [n_cand] = each candidate's direct-form distance and keep uint8 [n_cand] = dist <= radius[q].
+ * The fill checks every slot against its region: a candidate past the end of its region is not written and sets
+ * *error_flag (int32, device memory, zeroed by the caller) to 1 -- it cannot happen while counts and offsets are those
+ * of the count call.  Three launches (query pack, fill, verify); n_cand == 0 launches nothing.
+ * BTSBOT_ERR_INVALID_ARG with a message, before any HIP call, for the shapes btsbot_knn_query refuses, splits outside
+ * 1..32, flags other than 0 / BTSBOT_KNN_EXCLUDE_SAME, a NULL pointer that is needed, a short or misaligned workspace. */
+int64_t btsbot_knn_radius_workspace(int64_t n_query, int dim);
+int btsbot_knn_radius_count(const float* queries, int64_t n_query, const void* packed, int64_t n_bank, int dim,
+                            int metric, const float* radius, int64_t self_offset, int splits,
+                            const int64_t* query_group, const int64_t* bank_group, int flags, int32_t* counts,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int btsbot_knn_radius_fill(const float* queries, int64_t n_query, const float* bank, const void* packed, int64_t n_bank,
+                           int dim, int metric, const float* radius, int64_t self_offset, int splits,
+                           const int64_t* query_group, const int64_t* bank_group, int flags, const int32_t* counts,
+                           const int64_t* offsets, int64_t n_cand, int32_t* cand, float* dist, uint8_t* keep,
+                           int32_t* error_flag, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- connected components of a CSR graph and the DBSCAN labelling rule (csrc/components.hip) ---- */
+
+/* btsbot_graph_components(): indptr int64 [n + 1], indices int64 [indptr[n]] (values in [0, n)), mask uint8 [n] or
+ * NULL (every row passes).  root int64 [n] = the smallest row index of the row's connected component in the graph
+ * restricted to rows and edges whose both ends pass mask, an edge in either direction joining; -1 where mask is 0.
+ * Lock-free union-find on parent int32 [n] (scratch, the caller's): the larger root is hooked under the smaller, so the
+ * result is a function of the graph alone.  Three launches on `stream` (initialise, hook, flatten), no host read.
+ *
+ * btsbot_dbscan_labels(): core uint8 [n]; root as btsbot_graph_components(mask = core) returns it; cluster int64 [n] =
+ * at a core row that is its own root the cluster's number (the others are not read).  labels int64 [n]: a core row
+ * takes cluster[root[row]], a non-core row the smallest cluster[root[j]] over its core neighbours j, or -1 without one.
+ * One launch.  Both: n < 2^31; BTSBOT_ERR_INVALID_ARG for a NULL pointer or n outside 0 .. 2^31 - 1. */
+int btsbot_graph_components(const int64_t* indptr, const int64_t* indices, const uint8_t* mask, int64_t n,
+                            int32_t* parent, int64_t* root, void* stream);
+int btsbot_dbscan_labels(const int64_t* indptr, const int64_t* indices, const uint8_t* core, const int64_t* root,
+                         const int64_t* cluster, int64_t n, int64_t* labels, void* stream);
+
 /* ---- embedding layout: a deterministic UMAP map of the kNN graph (csrc/layout.hip) ---- */
 
 /* Replaces: the UMAP layout of the embedding step (train.py:449-469, the umap_emb_1 / umap_emb_2 columns).  Everything

@@ -45,6 +45,8 @@ from .features import FeatureState
 from . import neighbors
 from .neighbors import (EmbeddingIndex, embedding_neighbors, knn_graph, neighbor_vote, radius_graph,
                         radius_neighbors)
+from . import mapindex
+from .mapindex import MapIndex
 from . import clusters
 from .clusters import dbscan, graph_components
 from . import layout
@@ -62,7 +64,7 @@ __all__ = [
     "diagnostics", "alert_histograms", "roc_points", "diagnostic_data", "diagnostic_fig", "draw_diagnostic_fig",
     "features", "FeatureState",
     "neighbors", "EmbeddingIndex", "embedding_neighbors", "knn_graph", "neighbor_vote",
-    "radius_neighbors", "radius_graph", "clusters", "graph_components", "dbscan",
+    "radius_neighbors", "radius_graph", "clusters", "graph_components", "dbscan", "mapindex", "MapIndex",
     "layout", "FuzzyGraph", "fuzzy_graph", "optimize_layout", "embedding_layout", "find_ab_params",
     "EmbeddingMap", "layout_transform", "query_memberships",
     "splits", "SPLIT_NAMES", "SOURCE_SETS", "label_set", "split_labels", "subset_mask", "cuts_suffix",

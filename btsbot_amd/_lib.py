@@ -52,6 +52,7 @@ SYMBOLS = [
     "btsbot_knn_workspace_grouped", "btsbot_knn_query_grouped",
     "btsbot_knn_radius_workspace", "btsbot_knn_radius_count", "btsbot_knn_radius_fill",
     "btsbot_graph_components", "btsbot_dbscan_labels",
+    "btsbot_grid_finite", "btsbot_grid_cells", "btsbot_grid_radius_count", "btsbot_grid_radius_fill", "btsbot_grid_knn",
     "btsbot_layout_smooth_knn", "btsbot_layout_symmetrize_workspace", "btsbot_layout_symmetrize", "btsbot_layout_init",
     "btsbot_layout_epochs", "btsbot_layout_smooth_knn_query", "btsbot_layout_transform",
 ]
@@ -60,6 +61,8 @@ KNN_METRIC = {"euclidean": 0, "cosine": 1}   # enum btsbot_knn_metric
 KNN_MAX_DIM, KNN_MAX_K, KNN_MAX_SPLITS = 1024, 64, 32
 KNN_EXCLUDE_SAME, KNN_ONE_PER_GROUP = 1, 2   # enum btsbot_knn_flags
 KNN_MAX_K_ONE_PER_GROUP = 32                 # k's cap under KNN_ONE_PER_GROUP
+GRID_MAX_CELLS, GRID_MAX_K = 4096, 64         # csrc/grid.hip
+GRID_LANES = (0, 1, 4, 8, 16, 32, 64)        # lanes per query row of btsbot_grid_radius_* (0: the library's choice)
 EMBEDDING = {"features": 0, "hidden": 1}   # enum btsbot_embedding
 # enum btsbot_stamp_status: what btsbot_decode_stamps says of each stamp
 STAMP_STATUS = {"OK": 0, "BAD_GZIP": 1, "BAD_DEFLATE": 2, "TOO_LARGE": 3, "BAD_TRAILER": 4, "BAD_FITS": 5,
@@ -296,6 +299,17 @@ def lib() -> C.CDLL:
     L.btsbot_graph_components.argtypes = [vp, vp, vp, i64, vp, vp, vp]
     L.btsbot_dbscan_labels.restype = i32
     L.btsbot_dbscan_labels.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp]
+    L.btsbot_grid_finite.restype = i32
+    L.btsbot_grid_finite.argtypes = [vp, i64, vp, vp]
+    L.btsbot_grid_cells.restype = i32
+    L.btsbot_grid_cells.argtypes = [vp, i64, vp, i32, vp, vp, vp]
+    grid = [vp, i32, vp, vp, vp, vp, i64, i64, vp, i32]   # geom, cells, cell_start, points, rows, groups, n_bank, self, qgroups, flags
+    L.btsbot_grid_radius_count.restype = i32
+    L.btsbot_grid_radius_count.argtypes = [vp, i64, vp] + grid + [i32, vp, vp, vp]
+    L.btsbot_grid_radius_fill.restype = i32
+    L.btsbot_grid_radius_fill.argtypes = [vp, i64, vp] + grid + [i32, vp, i64, vp, vp, vp, vp]
+    L.btsbot_grid_knn.restype = i32
+    L.btsbot_grid_knn.argtypes = [vp, i64, i32] + grid + [vp, vp, vp]
     L.btsbot_layout_smooth_knn.restype = i32
     L.btsbot_layout_smooth_knn.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp]
     L.btsbot_layout_symmetrize_workspace.restype = i64

@@ -15,6 +15,7 @@ With ``groups=obj`` (one int64 per row, an alert's object) a row's density is th
 rows within ``eps`` -- otherwise one object with fifty epochs is a cluster of its own --; everything else is unchanged.
 A non-finite row has no neighbours, not even itself: label -1, not core.  The components and the labelling are HIP
 kernels (csrc/components.hip); counting and numbering are torch operations on the same device.
+``method="grid"`` takes the graph of a 2-D map from ``mapindex.MapIndex`` (section 4q): the same graph, the same labels.
 There is no CPU fallback.
 """
 from __future__ import annotations
@@ -25,7 +26,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .neighbors import _groups, _metric, _ptr, _rows, radius_graph
+from .mapindex import check_grid_method
+from .neighbors import _check_method, _groups, _metric, _ptr, _rows, radius_graph
 
 
 def _csr(indptr, indices, n: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, int]:
@@ -69,11 +71,16 @@ def graph_components(indptr: torch.Tensor, indices: torch.Tensor, mask: Optional
 
 def dbscan(emb: torch.Tensor, eps: float, min_samples: int = 5, metric: str = "euclidean", *,
            groups: Optional[torch.Tensor] = None,
-           graph: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+           graph: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+           method: str = "tiles") -> Tuple[torch.Tensor, torch.Tensor]:
     """``labels`` int64 [N] (-1: noise) and ``core`` bool [N] of the rows of ``emb`` [N, D]: sklearn's DBSCAN (see the
     module text).  groups: int64 [N]; a row's density is then the number of distinct groups within ``eps``.
-    graph: ``(indptr, indices)`` of ``radius_graph(emb, eps, include_self=True)``, to reuse one."""
+    graph: ``(indptr, indices)`` of ``radius_graph(emb, eps, include_self=True)``, to reuse one.
+    method: ``radius_graph``'s, ``"tiles"`` or, for a 2-D map, ``"grid"``: the same graph, hence the same labels."""
     _metric(metric)
+    _check_method(method)
+    if method == "grid":
+        check_grid_method(int(emb.shape[1]) if isinstance(emb, torch.Tensor) and emb.dim() == 2 else None, metric)
     if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not eps >= 0:
         raise ValueError(f"eps must be a float >= 0, got {eps!r}")
     if isinstance(min_samples, bool) or not isinstance(min_samples, int) or min_samples < 1:
@@ -83,7 +90,7 @@ def dbscan(emb: torch.Tensor, eps: float, min_samples: int = 5, metric: str = "e
     if groups is not None:
         groups = _groups(groups, "groups", n, dev)
     if graph is None:
-        indptr, indices, _dist = radius_graph(rows, float(eps), include_self=True, metric=metric)
+        indptr, indices, _dist = radius_graph(rows, float(eps), include_self=True, metric=metric, method=method)
     else:
         indptr, indices, _n = _csr(graph[0], graph[1], n)
         if indptr.device != dev:

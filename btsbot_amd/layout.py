@@ -382,6 +382,7 @@ class EmbeddingMap:
         m = EmbeddingMap.from_positions(bank, y)        # a map made earlier
         y_new = m.transform(queries)                    # the map does not move
         m.extend(rows)                                  # transform, then the rows join the bank at those positions
+        mi = m.map_index()                              # a MapIndex over embedding_: neighbours ON the map
 
     ``n_neighbors`` counts the row itself in the fit (as ``embedding_layout``) and is the number of bank rows a new row is
     attached to in ``transform`` (as umap-learn).  ``transform`` runs 100 epochs whatever the number of rows
@@ -428,4 +429,15 @@ class EmbeddingMap:
         y = self.transform(rows, n_epochs, seed)
         self.index.add(rows)
         self.embedding_ = torch.cat([self.embedding_, y])
+        self._map_index = None
         return y
+
+    def map_index(self):
+        """A ``MapIndex`` over ``embedding_`` -- radius, count and k-nearest questions about the MAP positions --,
+        built at the first call and kept until ``extend`` moves on (or ``embedding_`` is replaced)."""
+        from .mapindex import MapIndex
+        cached = getattr(self, "_map_index", None)
+        if cached is None or cached[0] is not self.embedding_:
+            cached = (self.embedding_, MapIndex(self.embedding_))
+            self._map_index = cached
+        return cached[1]

@@ -50,6 +50,11 @@ whose GEMM-form value is within ``r^2`` plus a margin that covers the error of b
 their direct-form distances, torch compacts and orders; nothing of size Q x N is written, the host is read twice (to
 size the candidates, then the lists).  The margin grows with ``|q|^2 + |b|^2``: centre the rows (``rows - rows.mean(0)``),
 or data far from the origin relative to its spread verifies most pairs -- exactly, and slowly.
+
+On a 2-D map.  ``radius_graph`` and ``knn_graph`` take ``method="grid"`` for 2-D rows and the
+euclidean metric: ``mapindex.MapIndex`` answers from a uniform grid in time linear in the rows plus the output, with the
+same membership, ordering and distances (the radius lists are bit-identical).  The default, ``"tiles"``, is the path
+described above.
 """
 from __future__ import annotations
 
@@ -381,24 +386,36 @@ def radius_neighbors(queries: torch.Tensor, bank: torch.Tensor, r, metric: str =
 
 def radius_graph(emb: torch.Tensor, r, include_self: bool = True, metric: str = "euclidean", *,
                  groups: Optional[torch.Tensor] = None, group_mode: str = "exclude", sort: str = "index",
-                 splits: int = 0, max_total: Optional[int] = None,
-                 stats: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                 splits: int = 0, max_total: Optional[int] = None, stats: Optional[dict] = None,
+                 method: str = "tiles") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Every row of ``emb`` [N, D] among the others within ``r``: the CSR of ``EmbeddingIndex.radius`` with N rows.
     include_self=True: a finite row is in its own list at distance 0 (DBSCAN counts it); False: it is not, by
     position -- its duplicates are.  groups / group_mode="exclude": the others are rows of OTHER groups only (the row
-    itself stays under include_self=True).  A non-finite row has an empty list."""
+    itself stays under include_self=True).  A non-finite row has an empty list.
+    method: ``"tiles"`` (``EmbeddingIndex``) or, for a 2-D ``emb`` and the euclidean metric, ``"grid"`` (``MapIndex``:
+    the same lists bit for bit, in time linear in N plus the edges; ``splits`` has no part in it, ``stats`` receives
+    ``visited`` in place of ``candidates``)."""
     _metric(metric)
+    _check_method(method)
     if group_mode != "exclude":
         raise ValueError(f'radius lists know group_mode="exclude" only, got {group_mode!r}')
     _check_radius_args(r, int(emb.shape[0]) if isinstance(emb, torch.Tensor) and emb.dim() == 2 else None, sort, splits,
                        max_total)
+    if method == "grid":
+        from .mapindex import check_grid_method
+        check_grid_method(int(emb.shape[1]) if isinstance(emb, torch.Tensor) and emb.dim() == 2 else None, metric)
     rows = _rows(emb, "emb")
     n = int(rows.shape[0])
     kw = dict(sort=sort, splits=splits, max_total=max_total, stats=stats)
     if groups is not None:
         groups = _groups(groups, "groups", n, rows.device)
         kw.update(query_groups=groups, exclude_same_group=True)
-    index = EmbeddingIndex(rows, metric, groups=groups)
+    if method == "grid":
+        from .mapindex import MapIndex
+        del kw["splits"]
+        index = MapIndex(rows, groups=groups)
+    else:
+        index = EmbeddingIndex(rows, metric, groups=groups)
     if include_self and groups is None and metric == "euclidean":
         return index.radius(rows, r, **kw)         # the row itself is a bank row at exactly 0
     indptr, indices, dist = index.radius(rows, r, self_offset=0, **kw)
@@ -434,11 +451,17 @@ def embedding_neighbors(queries: torch.Tensor, bank: torch.Tensor, k: int, metri
 
 
 GROUP_MODES = ("exclude", "distinct", "exclude+distinct")
+METHODS = ("tiles", "grid")
+
+
+def _check_method(method) -> None:
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, got {method!r}")
 
 
 def knn_graph(emb: torch.Tensor, k: int, include_self: bool = True, metric: str = "euclidean", *,
               groups: Optional[torch.Tensor] = None, group_mode: str = "exclude",
-              splits: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+              splits: int = 0, method: str = "tiles") -> Tuple[torch.Tensor, torch.Tensor]:
     """Every row of ``emb`` [N, D] among the others: ``idx`` int64 [N, k], ``dist`` float32 [N, k].
 
     include_self=True: the row itself first at distance 0, then its ``k - 1`` nearest others -- the layout pynndescent
@@ -448,11 +471,18 @@ def knn_graph(emb: torch.Tensor, k: int, include_self: bool = True, metric: str 
     groups: int64 [N], the rows' groups (objects); a row's own group is its query group.  group_mode: ``"exclude"`` the
     others are rows of OTHER groups only; ``"distinct"`` the others hold at most one row per group (the row's own group
     may be among them, by another of its rows); ``"exclude+distinct"`` both.  The row itself stays in column 0 under
-    include_self=True in every mode."""
+    include_self=True in every mode.
+    method: ``"tiles"`` (``EmbeddingIndex``) or, for a 2-D ``emb``, the euclidean metric and group_mode ``"exclude"``,
+    ``"grid"`` (``MapIndex``: the k smallest by (dist, index) of the direct-form distance, in time linear in N)."""
     _check_k(k, splits)
     _metric(metric)
+    _check_method(method)
     if group_mode not in GROUP_MODES:
         raise ValueError(f"group_mode must be one of {GROUP_MODES}, got {group_mode!r}")
+    if method == "grid":
+        from .mapindex import check_grid_method
+        check_grid_method(int(emb.shape[1]) if isinstance(emb, torch.Tensor) and emb.dim() == 2 else None, metric,
+                          group_mode=group_mode)
     rows = _rows(emb, "emb")
     if groups is None:
         kw = {}
@@ -460,16 +490,27 @@ def knn_graph(emb: torch.Tensor, k: int, include_self: bool = True, metric: str 
         groups = _groups(groups, "groups", int(rows.shape[0]), rows.device)
         kw = dict(query_groups=groups, exclude_same_group="exclude" in group_mode, one_per_group="distinct" in group_mode)
         _check_group_args(k - 1 if include_self else k, True, groups, kw["exclude_same_group"], kw["one_per_group"])
+    if method == "grid":
+        from .mapindex import MapIndex
+        index = MapIndex(rows, groups=groups)
+        kw.pop("one_per_group", None)
+        if not include_self:
+            return index.query(rows, k, self_offset=0, **kw)
+        return _self_first_graph(index, k, None, **kw)
     index = EmbeddingIndex(rows, metric, groups=groups)
     if not include_self:
         return index.query(rows, k, splits=splits, self_offset=0, **kw)
     return _self_first_graph(index, k, splits, **kw)
 
 
-def _self_first_graph(index: EmbeddingIndex, k: int, splits: int = 0, **kw) -> Tuple[torch.Tensor, torch.Tensor]:
+def _self_first_graph(index, k: int, splits: Optional[int] = 0, **kw) -> Tuple[torch.Tensor, torch.Tensor]:
     """``knn_graph(index.bank, k, include_self=True)`` from an index already packed (kw: the group arguments of
-    ``query``)."""
-    rows = index.bank
+    ``query``).  splits=None: a ``MapIndex``, which has none."""
+    if splits is None:
+        rows = index.points
+    else:
+        rows = index.bank
+        kw["splits"] = splits
     n = int(rows.shape[0])
     idx = torch.empty((n, k), dtype=torch.int64, device=rows.device)
     dist = torch.empty((n, k), dtype=torch.float32, device=rows.device)
@@ -477,7 +518,7 @@ def _self_first_graph(index: EmbeddingIndex, k: int, splits: int = 0, **kw) -> T
     idx[:, 0] = torch.where(finite, torch.arange(n, device=rows.device), torch.full_like(idx[:, 0], -1))
     dist[:, 0] = torch.where(finite, torch.zeros_like(dist[:, 0]), torch.full_like(dist[:, 0], float("nan")))
     if k > 1:
-        idx[:, 1:], dist[:, 1:] = index.query(rows, k - 1, splits=splits, self_offset=0, **kw)
+        idx[:, 1:], dist[:, 1:] = index.query(rows, k - 1, self_offset=0, **kw)
     return idx, dist
 
 

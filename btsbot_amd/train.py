@@ -327,7 +327,8 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
     With ``config['embedding_layout']`` (``True``, or a dict of ``embedding_layout`` keyword arguments; ``seed`` defaults
     to the run's ``random_seed``) also ``{stem}_umap.csv`` with the reference's columns ``umap_emb_1, umap_emb_2,
     candid`` (train.py:464): the 2-D map of the rows, in the candidate file's order.  With
-    ``config['embedding_clusters'] = {"eps": ..., "min_samples": 5, "on": "map" | "embedding"}`` the DBSCAN labels
+    ``config['embedding_clusters'] = {"eps": ..., "min_samples": 5, "on": "map" | "embedding", "method": "tiles" |
+    "grid"}`` (``"grid"``: the 2-D map only, the same labels in time linear in the rows) the DBSCAN labels
     (``clusters.dbscan``; -1 = noise) of the map, as a ``cluster`` column of ``{stem}_umap.csv``, or of the embedding
     rows, as ``{stem}_clusters.npy`` (int64 [N]).  Returns the .npy path."""
     import numpy as np
@@ -379,16 +380,18 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
     clu = config.get("embedding_clusters")
     if clu:   # opt-in: DBSCAN of the map (a `cluster` column of the map's table) or of the rows ({stem}_clusters.npy)
         from .clusters import dbscan
-        unknown = set(clu) - {"eps", "min_samples", "on"} if isinstance(clu, dict) else {"?"}
-        if unknown or "eps" not in clu or clu.get("on", "map") not in ("map", "embedding"):
-            raise ValueError("config['embedding_clusters'] is a dict with the keys eps, min_samples and on "
-                             f"('map' or 'embedding'), got {clu!r}")
-        clu = dict(eps=float(clu["eps"]), min_samples=int(clu.get("min_samples", 5)), on=clu.get("on", "map"))
+        unknown = set(clu) - {"eps", "min_samples", "on", "method"} if isinstance(clu, dict) else {"?"}
+        if (unknown or "eps" not in clu or clu.get("on", "map") not in ("map", "embedding")
+                or clu.get("method", "tiles") not in ("tiles", "grid")):
+            raise ValueError("config['embedding_clusters'] is a dict with the keys eps, min_samples, on "
+                             f"('map' or 'embedding') and method ('tiles' or 'grid'), got {clu!r}")
+        clu = dict(eps=float(clu["eps"]), min_samples=int(clu.get("min_samples", 5)), on=clu.get("on", "map"),
+                   method=clu.get("method", "tiles"))
         if clu["on"] == "map" and not lay:
             raise ValueError("config['embedding_clusters'] with on='map' clusters the map of config['embedding_layout'], "
                              "which is not set")
         if clu["on"] == "embedding":
-            labels, _core = dbscan(torch.from_numpy(out).to(dev), clu["eps"], clu["min_samples"])
+            labels, _core = dbscan(torch.from_numpy(out).to(dev), clu["eps"], clu["min_samples"], method=clu["method"])
             np.save(stem + "_clusters.npy", labels.cpu().numpy())
     if lay:   # opt-in: the UMAP map itself, with the reference's columns (train.py:464)
         import pandas as pd
@@ -404,7 +407,7 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
         if "candid" in cand.columns:
             table["candid"] = cand["candid"].to_numpy()
         if clu and clu["on"] == "map":
-            labels, _core = dbscan(y_dev, clu["eps"], clu["min_samples"])
+            labels, _core = dbscan(y_dev, clu["eps"], clu["min_samples"], method=clu["method"])
             table["cluster"] = labels.cpu().numpy()
         pd.DataFrame(table).to_csv(stem + "_umap.csv", index=False)
     return stem + ".npy"

@@ -932,6 +932,57 @@ int btsbot_graph_components(const int64_t* indptr, const int64_t* indices, const
 int btsbot_dbscan_labels(const int64_t* indptr, const int64_t* indices, const uint8_t* core, const int64_t* root,
                          const int64_t* cluster, int64_t n, int64_t* labels, void* stream);
 
+/* ---- exact neighbour search on 2-D maps by a uniform grid (csrc/grid.hip) ---- */
+
+/* The radius and k-nearest questions of btsbot_knn_radius_* / btsbot_knn_query for fp32 points in the plane, answered
+ * in time linear in the points plus the output.  Membership, ranking and the returned distance are those of the tile
+ * path at D = 2, bit for bit: a bank row is eligible if it is finite (both coordinates finite and
+ * fl(fl(x x) + fl(y y)) <= FLT_MAX), is not row q + self_offset (self_offset >= 0) and, under BTSBOT_KNN_EXCLUDE_SAME,
+ * is not of q's group (64 bits); the distance is sqrtf(fl(fl(t0 t0) + fl(t1 t1))), t = q - b, never contracted; a
+ * member has distance <= radius[q] in fp32.  The grid only says which pairs are looked at, and provably looks at every
+ * member, so no answer depends on `cells`.
+ *
+ * Build.  btsbot_grid_finite(): finite uint8 [n] by the rule above.  The caller reduces bbox fp32 [4] = {min x, min y,
+ * max x, max y} over the finite rows (+inf / -inf without one), on the device.  btsbot_grid_cells(): writes geom fp32
+ * [4] = {x0, y0, inv_hx, inv_hy} (inv_h = cells / extent, 0 for an extent that is not positive and finite) and cell
+ * int32 [n] = cy * cells + cx with c(x) = clamp(floor(fl(fl(x - x0) * inv_h)), 0, cells - 1), or cells * cells for a
+ * row that is not finite.  The caller sorts the rows by cell (stably) and hands every query call: cell_start int32
+ * [cells * cells + 1] (cell_start[c] = the first sorted position whose cell is >= c), sorted_points fp32 [n_bank][2],
+ * sorted_rows int32 [n_bank] (the points' original rows) and, for BTSBOT_KNN_EXCLUDE_SAME, sorted_group int64 [n_bank],
+ * all in cell order.  1 <= cells <= 4096; n < 2^31.
+ *
+ * btsbot_grid_radius_count(): counts int64 [n_query] = the members of each query row; visited int64 [n_query] (may be
+ * NULL) = the pairs whose distance was computed.  One launch, no host read.  A non-finite query row, or one whose
+ * radius is negative or NaN, has none.  lanes: the lanes that share a query row, 0 (the library's choice, 16), 1, 4, 8,
+ * 16, 32 or 64; the answer does not depend on it.
+ * btsbot_grid_radius_fill(): indptr int64 [n_query + 1] = the exclusive scan of counts, total = indptr[n_query].  The
+ * same walk writes query row q's members into cand int32 [total] (original rows) and dist fp32 [total] at indptr[q] ..,
+ * in the order of the walk (the caller sorts).  A member past indptr[q + 1] is not written and sets *error_flag (int32,
+ * device memory, zeroed by the caller) to 1 -- it cannot happen while indptr is the scan of the count call.
+ * btsbot_grid_knn(): idx int64 [n_query][k], dist fp32 [n_query][k]: the k smallest eligible rows by (distance, row);
+ * fewer than k eligible: the tail is -1 / +inf; a non-finite query row: -1 / NaN.  1 <= k <= 64.  One launch, no host
+ * read, no workspace.
+ * BTSBOT_ERR_INVALID_ARG with a message, before any HIP call, for sizes out of range, cells outside 1..4096, flags other
+ * than 0 / BTSBOT_KNN_EXCLUDE_SAME, a group array the flag needs being NULL, lanes not listed above, k outside 1..64 and
+ * a NULL pointer that is needed. */
+int btsbot_grid_finite(const float* points, int64_t n, uint8_t* finite, void* stream);
+int btsbot_grid_cells(const float* points, int64_t n, const float* bbox, int cells, float* geom, int32_t* cell,
+                      void* stream);
+int btsbot_grid_radius_count(const float* queries, int64_t n_query, const float* radius, const float* geom, int cells,
+                             const int32_t* cell_start, const float* sorted_points, const int32_t* sorted_rows,
+                             const int64_t* sorted_group, int64_t n_bank, int64_t self_offset,
+                             const int64_t* query_group, int flags, int lanes, int64_t* counts, int64_t* visited,
+                             void* stream);
+int btsbot_grid_radius_fill(const float* queries, int64_t n_query, const float* radius, const float* geom, int cells,
+                            const int32_t* cell_start, const float* sorted_points, const int32_t* sorted_rows,
+                            const int64_t* sorted_group, int64_t n_bank, int64_t self_offset,
+                            const int64_t* query_group, int flags, int lanes, const int64_t* indptr, int64_t total,
+                            int32_t* cand, float* dist, int32_t* error_flag, void* stream);
+int btsbot_grid_knn(const float* queries, int64_t n_query, int k, const float* geom, int cells,
+                    const int32_t* cell_start, const float* sorted_points, const int32_t* sorted_rows,
+                    const int64_t* sorted_group, int64_t n_bank, int64_t self_offset, const int64_t* query_group,
+                    int flags, int64_t* idx, float* dist, void* stream);
+
 /* ---- embedding layout: a deterministic UMAP map of the kNN graph (csrc/layout.hip) ---- */
 
 /* Replaces: the UMAP layout of the embedding step (train.py:449-469, the umap_emb_1 / umap_emb_2 columns).  Everything

@@ -43,12 +43,14 @@ from .diagnostics import alert_histograms, diagnostic_data, diagnostic_fig, draw
 from .triggers import TriggerState
 from .features import FeatureState
 from . import neighbors
-from .neighbors import (EmbeddingIndex, embedding_neighbors, knn_graph, neighbor_vote, radius_graph,
+from .neighbors import (EmbeddingIndex, embedding_neighbors, knn_graph, neighbor_ranks, neighbor_vote, radius_graph,
                         radius_neighbors)
 from . import mapindex
 from .mapindex import MapIndex
 from . import clusters
 from .clusters import dbscan, graph_components
+from . import quality
+from .quality import continuity, map_quality, trustworthiness
 from . import layout
 from .layout import (EmbeddingMap, FuzzyGraph, embedding_layout, find_ab_params, fuzzy_graph, layout_transform,
                      optimize_layout, query_memberships)
@@ -64,7 +66,8 @@ __all__ = [
     "diagnostics", "alert_histograms", "roc_points", "diagnostic_data", "diagnostic_fig", "draw_diagnostic_fig",
     "features", "FeatureState",
     "neighbors", "EmbeddingIndex", "embedding_neighbors", "knn_graph", "neighbor_vote",
-    "radius_neighbors", "radius_graph", "clusters", "graph_components", "dbscan", "mapindex", "MapIndex",
+    "radius_neighbors", "radius_graph", "neighbor_ranks", "quality", "trustworthiness", "continuity", "map_quality",
+    "clusters", "graph_components", "dbscan", "mapindex", "MapIndex",
     "layout", "FuzzyGraph", "fuzzy_graph", "optimize_layout", "embedding_layout", "find_ab_params",
     "EmbeddingMap", "layout_transform", "query_memberships",
     "splits", "SPLIT_NAMES", "SOURCE_SETS", "label_set", "split_labels", "subset_mask", "cuts_suffix",

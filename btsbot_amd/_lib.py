@@ -51,6 +51,7 @@ SYMBOLS = [
     "btsbot_knn_bank_bytes", "btsbot_knn_pack_bank", "btsbot_knn_splits", "btsbot_knn_workspace", "btsbot_knn_query",
     "btsbot_knn_workspace_grouped", "btsbot_knn_query_grouped",
     "btsbot_knn_radius_workspace", "btsbot_knn_radius_count", "btsbot_knn_radius_fill",
+    "btsbot_knn_rank_workspace", "btsbot_knn_rank_count", "btsbot_knn_rank_fill",
     "btsbot_graph_components", "btsbot_dbscan_labels",
     "btsbot_grid_finite", "btsbot_grid_cells", "btsbot_grid_radius_count", "btsbot_grid_radius_fill", "btsbot_grid_knn",
     "btsbot_layout_smooth_knn", "btsbot_layout_symmetrize_workspace", "btsbot_layout_symmetrize", "btsbot_layout_init",
@@ -295,6 +296,13 @@ def lib() -> C.CDLL:
     L.btsbot_knn_radius_fill.restype = i32
     L.btsbot_knn_radius_fill.argtypes = [vp, i64, vp, vp, i64, i32, i32, vp, i64, i32, vp, vp, i32, vp, vp, i64, vp, vp, vp,
                                          vp, vp, i64, vp]
+    L.btsbot_knn_rank_workspace.restype = i64
+    L.btsbot_knn_rank_workspace.argtypes = [i64, i32, i32]
+    rank_head = [vp, i64, vp, vp, i64, i32, i32, vp, i32, i64, i32, vp, vp, i32]
+    L.btsbot_knn_rank_count.restype = i32
+    L.btsbot_knn_rank_count.argtypes = rank_head + [vp, vp, vp, vp, i64, vp]
+    L.btsbot_knn_rank_fill.restype = i32
+    L.btsbot_knn_rank_fill.argtypes = rank_head + [vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
     L.btsbot_graph_components.restype = i32
     L.btsbot_graph_components.argtypes = [vp, vp, vp, i64, vp, vp, vp]
     L.btsbot_dbscan_labels.restype = i32

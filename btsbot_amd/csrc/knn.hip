@@ -62,6 +62,9 @@
 // Radius search (btsbot_knn_radius_*): the same grid and tile walk with the epilogue "admit if
 // within r" -- see knn_radius_kernel -- and direct_distance(), the one function that computes a returned distance, for
 // the merge's winners and for every radius candidate alike.
+//
+// Neighbour ranks (btsbot_knn_rank_*): the same walk with a third epilogue, "count if surely before
+// the target, hand to the direct form if within the margin" -- see knn_rank_kernel.
 #include <float.h>
 
 #include "common.h"
@@ -890,6 +893,308 @@ __global__ __launch_bounds__(64) void knn_radius_verify_kernel(const float* __re
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// neighbour ranks (btsbot_knn_rank_*): rank[q][c] = the number of eligible bank rows b with
+// (direct_distance(q, b), b) before (dist[q][c], targets[q][c]).  The margin of 4p read from both sides: with
+// r = dist[q][c] a pair's GEMM-form value g decides
+//   g <  lo_c = r^2 * relm - ctau * (|q|^2 + |b|^2)   (cosine: r - ctau)    surely before: the direct form is < r, strictly
+//   g <= hi_c = r^2 * rel  + ctau * (|q|^2 + |b|^2)   (cosine: r + ctau)    the band: the direct form decides
+// and nothing otherwise (relm = 1 - 4 (D + 4) u; rel and ctau are the radius search's).  The thresholds kernel leaves
+// thr[q][c] = (r^2 * relm, r^2 * rel) (cosine: (r - ctau, r + ctau)) and rowlim[q] = the largest second component.
+//
+// thresholds: one wave per query row, its targets in turn.  dist[q][c] by direct_distance; rank[q][c] = 0, or -1 where
+// the target is out of range, not eligible for q, or q is not finite: such a column has thr = (-inf, -inf) and takes no
+// part in rowlim, so the tile pass adds nothing to it.
+__global__ __launch_bounds__(64) void knn_rank_thresh_kernel(const float* __restrict__ queries,
+                                                             const float* __restrict__ bank,
+                                                             const unsigned char* __restrict__ bimg, long N, int dim,
+                                                             int metric, const long long* __restrict__ targets, int t,
+                                                             long self_offset, const long long* __restrict__ qgrp,
+                                                             const long long* __restrict__ bgrp, float rel, float relm,
+                                                             float ctau, float* __restrict__ dist, int* __restrict__ rank,
+                                                             float2* __restrict__ thr, float* __restrict__ rowlim) {
+  const int lane = threadIdx.x;
+  const long q = blockIdx.x;
+  float xv[MAX_DIM / 64];
+  float qq;
+  const bool qok = load_query_row(queries + q * dim, dim, lane, xv, qq);
+  const size_t rec = record_bytes(dim);
+  const float ninf = -__builtin_inff();
+  float widest = ninf;
+  for (int c = 0; c < t; ++c) {
+    const long long b = targets[q * t + c];
+    const bool in = b >= 0 && b < N;
+    // (a bank row is finite exactly when its record's bias is: what the tile pass sees as score < inf)
+    const bool fin = in && qok && reinterpret_cast<const float*>(bimg + (size_t)b * rec)[0] < __builtin_inff();
+    const float d = fin ? direct_distance(xv, qq, bank + b * dim, dim, metric, lane) : __builtin_nanf("");
+    bool el = fin && !(self_offset >= 0 && b == q + self_offset);
+    if (el && qgrp != nullptr) el = bgrp[b] != qgrp[q];
+    float lo = ninf, hi = ninf;
+    if (el) {
+      if (metric == 0) {
+        hi = (d * d) * rel;
+        lo = (d * d) * relm;
+      } else {
+        hi = d + ctau;
+        lo = d - ctau;
+      }
+      if (!(fabsf(d) <= FLT_MAX)) lo = ninf;   // (an overflowed distance ties with its like: all of it is band)
+      widest = fmaxf(widest, hi);
+    }
+    if (lane == 0) {
+      dist[q * t + c] = d;
+      rank[q * t + c] = el ? 0 : -1;
+      thr[q * t + c] = make_float2(lo, hi);
+    }
+  }
+  if (lane == 0) rowlim[q] = widest;
+}
+
+// The tile pass: knn_radius_kernel's walk and pre-filter (one compare of g with the row's widest limit; most of the
+// bank ends there), then, for a score that passes, the row's t thresholds from L2.  FILL = false adds the surely-before
+// pairs to sure[row][c] in LDS (one global integer atomic per workgroup, row and column at the end) and counts the
+// (query, split)'s band pairs -- a pair is ONE band entry however many columns it is in the band of; FILL = true writes
+// the band pairs as (bank row, 64-bit mask of these columns) into the region the scan of the counts gave them, every
+// slot checked as in the radius fill.  Only integer additions meet across workgroups.
+// The scores that pass are few per lane but, in a crowded region, some lane of a wave passes at most of the 64 unrolled
+// sites, and a t-step loop run there for the whole wave costs several times the products (measured).  So a
+// site only QUEUES its score -- (row, bank row of the tile, g, the margin's scale) in the idle operand LDS -- and after
+// the tile all 256 threads share the queue's (score, column) compares, one each, then its entries.  What finds no room
+// in the queue is compared on the spot, by the same expressions.
+struct RankEnt {
+  int rowgb;          // query row of the tile * TB + bank row of the tile
+  float g, x;         // the GEMM-form value, |q|^2 + |b|^2 (cosine: 0)
+  unsigned mlo, mhi;  // the band mask, met by LDS atomic ORs
+};
+constexpr int RANK_QCAP = 2048;      // queue entries: 40 KB of the 64 KB operand planes, behind the tile's bank groups
+constexpr int RANK_QOFF = 2048;
+
+template <bool FILL, bool EXCL>
+__global__ __launch_bounds__(256, 2) void knn_rank_kernel(const unsigned char* __restrict__ qimg,
+                                                          const unsigned char* __restrict__ bimg, long Q, int N, int dim,
+                                                          int metric, int t, const float2* __restrict__ thr,
+                                                          const float* __restrict__ rowlim, float ctau, long self_offset,
+                                                          int tiles_per_split, int splits,
+                                                          const long long* __restrict__ qgrp,
+                                                          const long long* __restrict__ bgrp, int* __restrict__ rank,
+                                                          int* counts, const long long* __restrict__ offsets,
+                                                          int* __restrict__ cand, unsigned long long* __restrict__ cmask,
+                                                          long long n_band, int* __restrict__ err) {
+  constexpr int MI = TileWalk::MI, NI = TileWalk::NI;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  int* rowcnt = reinterpret_cast<int*>(smem + GEMM_LDS);          // [TQ] band pairs so far (FILL: the row's cursor)
+  int* rowcap = rowcnt + TQ;                                      // [TQ] FILL: the size of the row's region
+  long long* rowbase = reinterpret_cast<long long*>(rowcap + TQ); // [TQ] FILL: where it starts in cand / cmask
+  int* qn = reinterpret_cast<int*>(rowbase + TQ);                 // the queue's fill count (16 bytes kept for it)
+  int* sure = qn + 4;                                             // [TQ][t] count pass: the surely-before pairs
+  long long* tg = reinterpret_cast<long long*>(smem);             // EXCL: [TB] the tile's bank groups (idle operand LDS)
+  RankEnt* ent = reinterpret_cast<RankEnt*>(smem + RANK_QOFF);    // [RANK_QCAP] the tile's queue (idle operand LDS)
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int lrow = lane & 15, lq = lane >> 4;
+  const size_t rec = record_bytes(dim);
+  const long q0 = (long)blockIdx.x * TQ;
+  const int split = blockIdx.y;
+  const int total_tiles = (N + TB - 1) / TB;
+  const int t_begin = (int)min((long)split * tiles_per_split, (long)total_tiles);
+  const int t_end = (int)min((long)(split + 1) * tiles_per_split, (long)total_tiles);
+  const int b_end = (int)min((long)t_end * TB, (long)N);
+
+  if (tid < TQ) {
+    rowcnt[tid] = 0;
+    if constexpr (FILL) {
+      const bool in = q0 + tid < Q;
+      rowcap[tid] = in ? counts[(q0 + tid) * splits + split] : 0;
+      rowbase[tid] = in ? offsets[(q0 + tid) * splits + split] : 0;
+    }
+  }
+  if (tid == 0) *qn = 0;
+  if constexpr (!FILL)
+    for (int i = tid; i < TQ * t; i += 256) sure[i] = 0;
+
+  float sq[MI], qq[MI], qinv[MI], lim[MI];   // the query record's scale, |q|^2, 1 / (2 |q|); the row's widest limit
+  int selfb[MI];                             // the bank row that IS the query row (never counted), -1: none
+  long long qg[MI];                          // EXCL: the groups of the lane's four query rows
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    const long gq = q0 + wm * 64 + mi * 16 + lrow;
+    const float4 h = gq < Q ? *reinterpret_cast<const float4*>(qimg + gq * rec) : make_float4(0.f, 0.f, 0.f, 0.f);
+    sq[mi] = h.y;
+    qq[mi] = h.z;
+    qinv[mi] = h.w;
+    // a row past Q, a non-finite query row and a row without a valid target pass nothing
+    lim[mi] = gq < Q && h.y != 0.f ? rowlim[gq] : -__builtin_inff();
+    const long sb = gq + self_offset;
+    selfb[mi] = self_offset >= 0 && sb < N ? (int)sb : -1;
+    if constexpr (EXCL) qg[mi] = gq < Q ? qgrp[gq] : 0;
+  }
+
+  int n[MI] = {0, 0, 0, 0};
+  bool past = false;
+  TileWalk w;
+  w.init(qimg, bimg, smem, Q, q0, N, dim);
+  if (t_begin < t_end) w.gload(t_begin, 0);
+  __syncthreads();   // the rows' counters and regions
+  for (int tile = t_begin; tile < t_end; ++tile) {
+    const int b0 = tile * TB;
+    long long gt = 0;   // EXCL: bank row b0 + tid's group, in flight under the products
+    if constexpr (EXCL) {
+      if (tid < TB && (long)b0 + tid < N) gt = bgrp[(long)b0 + tid];
+    }
+    f32x4 acc[NI][MI];
+    w.products(acc, tile, t_end);
+    if constexpr (EXCL) {
+      if (tid < TB) tg[tid] = gt;
+      lds_barrier();
+    }
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni) {
+      float nb[4], sb[4];   // the fragment's bank biases and scales: rows b0 + wn * 64 + ni * 16 + lq * 4 + i
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int b = b0 + wn * 64 + ni * 16 + lq * 4 + i;
+        const float2 h = b < N ? *reinterpret_cast<const float2*>(bimg + (size_t)b * rec)
+                               : make_float2(__builtin_inff(), 0.f);
+        nb[i] = h.x;
+        sb[i] = h.y;
+      }
+      long long bg[4];
+      if constexpr (EXCL) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) bg[i] = tg[wn * 64 + ni * 16 + lq * 4 + i];
+      }
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int gb = b0 + wn * 64 + ni * 16 + lq * 4 + i;
+          const float s = fmaf(-(acc[ni][mi][i] * sq[mi]), sb[i], nb[i]);
+          float g, x;   // x: what the margin's tau part scales with (cosine: its tau is in the thresholds)
+          if (metric == 0) {
+            g = s + qq[mi];
+            x = qq[mi] + nb[i];
+          } else {
+            g = fmaf(s, qinv[mi], 1.f);
+            x = 0.f;
+          }
+          const float l = fmaf(ctau, x, lim[mi]);
+          bool in = g <= l && s < __builtin_inff() && gb < b_end && gb != selfb[mi];
+          if constexpr (EXCL) in = in && bg[i] != qg[mi];
+          if (in) {
+            const int row = wm * 64 + mi * 16 + lrow;
+            const int slot = atomicAdd(qn, 1);
+            if (slot < RANK_QCAP) {
+              ent[slot] = RankEnt{row * TB + (gb - b0), g, x, 0u, 0u};
+              continue;
+            }
+            const float2* th = thr + (q0 + row) * t;
+            unsigned long long band = 0;
+#pragma unroll 1
+            for (int c = 0; c < t; ++c) {
+              const float2 lh = th[c];
+              if (g < fmaf(-ctau, x, lh.x)) {
+                if constexpr (!FILL) atomicAdd(&sure[row * t + c], 1);
+              } else if (g <= fmaf(ctau, x, lh.y)) {
+                band |= 1ull << c;
+              }
+            }
+            if (band != 0) {
+              if constexpr (FILL) {
+                const int slot = atomicAdd(&rowcnt[row], 1);
+                const long long at = rowbase[row] + slot;
+                if (slot < rowcap[row] && at >= 0 && at < n_band) {
+                  cand[at] = gb;
+                  cmask[at] = band;
+                } else {
+                  past = true;   // (never, while counts / offsets are the count pass's: the same arithmetic)
+                }
+              } else {
+                ++n[mi];
+              }
+            }
+          }
+        }
+    }
+    lds_barrier();   // the queue is complete (and the groups are read)
+    const int nq = min(*qn, RANK_QCAP);
+    for (int w = tid; w < nq * t; w += 256) {   // one (score, column) compare per thread and step
+      const int e = w / t, c = w - e * t;
+      const int row = ent[e].rowgb / TB;
+      const float g = ent[e].g, x = ent[e].x;
+      const float2 lh = thr[(q0 + row) * t + c];
+      if (g < fmaf(-ctau, x, lh.x)) {
+        if constexpr (!FILL) atomicAdd(&sure[row * t + c], 1);
+      } else if (g <= fmaf(ctau, x, lh.y)) {
+        atomicOr(c < 32 ? &ent[e].mlo : &ent[e].mhi, 1u << (c & 31));
+      }
+    }
+    lds_barrier();   // the masks are complete
+    for (int e = tid; e < nq; e += 256) {
+      const unsigned long long band = (unsigned long long)ent[e].mhi << 32 | ent[e].mlo;
+      if (band == 0) continue;
+      const int row = ent[e].rowgb / TB;
+      const int slot = atomicAdd(&rowcnt[row], 1);
+      if constexpr (FILL) {
+        const long long at = rowbase[row] + slot;
+        if (slot < rowcap[row] && at >= 0 && at < n_band) {
+          cand[at] = b0 + ent[e].rowgb % TB;
+          cmask[at] = band;
+        } else {
+          past = true;
+        }
+      }
+    }
+    lds_barrier();   // the queue is read: the next tile's operands may land there
+    if (tid == 0) *qn = 0;   // (the next tile's first push is behind the barriers of its products)
+  }
+
+  if constexpr (FILL) {
+    if (past) *err = 1;
+  } else {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+      if (n[mi] != 0) atomicAdd(&rowcnt[wm * 64 + mi * 16 + lrow], n[mi]);
+    __syncthreads();
+    if (tid < TQ && q0 + tid < Q) counts[(q0 + tid) * splits + split] = rowcnt[tid];
+    for (int i = tid; i < TQ * t; i += 256) {
+      const int v = sure[i];
+      if (v != 0) atomicAdd(&rank[q0 * t + i], v);   // (row q0 + i / t, column i % t; a row past Q has none)
+    }
+  }
+}
+
+// one wave per band entry in turn (the radius verify's grid): the pair's direct-form distance once, then lane c adds
+// before((d, b), (dist[q][c], targets[q][c])) to rank[q][c] for the columns of the entry's mask
+__global__ __launch_bounds__(64) void knn_rank_verify_kernel(const float* __restrict__ queries,
+                                                             const float* __restrict__ bank,
+                                                             const long long* __restrict__ targets, int t,
+                                                             const float* __restrict__ dist,
+                                                             const long long* __restrict__ offsets, int splits,
+                                                             const int* __restrict__ cand,
+                                                             const unsigned long long* __restrict__ cmask, int N,
+                                                             int dim, int metric, int* __restrict__ rank) {
+  const int lane = threadIdx.x;
+  const long q = blockIdx.x;
+  const long long c1 = offsets[(q + 1) * splits];
+  long long c = offsets[q * splits] + blockIdx.y;
+  if (c >= c1) return;
+  float xv[MAX_DIM / 64];
+  float qq;
+  (void)load_query_row(queries + q * dim, dim, lane, xv, qq);   // (a row that is not finite has no band entries)
+  const bool col = lane < t;
+  const float dc = col ? dist[q * t + lane] : 0.f;
+  const long long tc = col ? targets[q * t + lane] : 0;
+  int add = 0;
+  for (; c < c1; c += gridDim.y) {
+    const int b = cand[c];
+    if (b < 0 || b >= N) continue;   // (a slot the fill did not reach: it raised the error flag)
+    const float d = direct_distance(xv, qq, bank + (long)b * dim, dim, metric, lane);
+    if (col && (cmask[c] >> lane & 1ull) != 0 && before(d, b, dc, (int)tc)) ++add;
+  }
+  if (add != 0) atomicAdd(&rank[q * t + lane], add);
+}
+
 int check_shape(const char* who, int64_t n_query, int64_t n_bank, int dim, int k) {
   if (dim < 1 || dim > MAX_DIM || k < 1 || k > MAX_K || n_query < 0 || n_bank < 0 || n_bank > 0x7fffffffLL ||
       n_query > 0x7fffffffLL) {
@@ -1211,6 +1516,185 @@ extern "C" int btsbot_knn_radius_fill(const float* queries, int64_t n_query, con
   hipLaunchKernelGGL(knn_radius_verify_kernel, dim3((unsigned)n_query, Y), dim3(64), 0, st, queries, bank, radius,
                      reinterpret_cast<const long long*>(offsets), splits, (const int*)cand, (int)n_bank, dim, metric, dist,
                      keep);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// neighbour ranks: the entry points
+namespace {
+
+struct RankArgs {
+  const float* queries;
+  int64_t n_query;
+  const float* bank;
+  const void* packed;
+  int64_t n_bank;
+  int dim, metric;
+  const int64_t* targets;
+  int n_targets;
+  int64_t self_offset;
+  int splits;
+  const int64_t* query_group;
+  const int64_t* bank_group;
+  int flags;
+  void* workspace;
+  int64_t workspace_bytes;
+};
+
+// the workspace: the packed query rows, thr float2 [n_query][n_targets], rowlim float [n_query]
+size_t rank_thr_bytes(int64_t n_query, int n_targets) {
+  return ((size_t)n_query * n_targets * sizeof(float2) + 255) & ~(size_t)255;
+}
+
+int rank_checked(const char* who, const RankArgs& a) {
+  TRY(check_shape(who, a.n_query, a.n_bank, a.dim, a.n_targets));   // (1 <= n_targets <= 64 is k's range)
+  if (a.metric != BTSBOT_KNN_EUCLIDEAN && a.metric != BTSBOT_KNN_COSINE) {
+    btsbot_set_error("%s: metric %d", who, a.metric);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (a.splits < 1 || a.splits > MAX_SPLITS) {
+    btsbot_set_error("%s: splits=%d must be 1 .. %d", who, a.splits, MAX_SPLITS);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if ((a.flags & ~GM_EXCLUDE) != 0) {
+    btsbot_set_error("%s: flags=%d, only 0 and BTSBOT_KNN_EXCLUDE_SAME are rank modes", who, a.flags);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (a.n_query == 0) return BTSBOT_OK;
+  if (a.queries == nullptr || a.targets == nullptr || a.workspace == nullptr ||
+      (a.n_bank > 0 && (a.bank == nullptr || a.packed == nullptr))) {
+    btsbot_set_error("%s: NULL argument", who);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (a.flags != 0 && (a.query_group == nullptr || (a.n_bank > 0 && a.bank_group == nullptr))) {
+    btsbot_set_error("%s: BTSBOT_KNN_EXCLUDE_SAME needs query_group and bank_group, got NULL", who);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  const int64_t need = btsbot_knn_rank_workspace(a.n_query, a.dim, a.n_targets);
+  if (a.workspace_bytes < need || ((uintptr_t)a.workspace & 15) != 0 || ((uintptr_t)a.packed & 15) != 0) {
+    btsbot_set_error("%s: workspace of %lld bytes (need %lld), or workspace / packed not 16-byte aligned", who,
+                     (long long)a.workspace_bytes, (long long)need);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  return BTSBOT_OK;
+}
+
+// the margin of DESIGN.md 4p / 4r; u = 2^-24
+struct RankMargin {
+  float rel, relm, ctau;
+  RankMargin(int dim, int metric) {
+    const float u = 5.9604644775390625e-8f;
+    rel = 1.f + 4.f * (float)(dim + 4) * u;
+    relm = 1.f - 4.f * (float)(dim + 4) * u;
+    ctau = (metric == BTSBOT_KNN_COSINE ? 16.f : 8.f) * (float)(dim + 8) * u;
+  }
+};
+
+template <bool FILL, bool EXCL>
+int launch_rank(const RankArgs& a, int* rank, int* counts, const int64_t* offsets, int* cand, uint64_t* cmask,
+                int64_t n_band, int* err, hipStream_t st) {
+  unsigned char* qimg = reinterpret_cast<unsigned char*>(a.workspace);
+  const float2* thr = reinterpret_cast<const float2*>(qimg + image_bytes(a.n_query, a.dim));
+  const float* rowlim = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(thr) +
+                                                       rank_thr_bytes(a.n_query, a.n_targets));
+  // operands + per query row: counter, region size, region start; the queue's count; the count pass: + its
+  // n_targets sure counts per row
+  const int lds = GEMM_LDS + TQ * 16 + 16 + (FILL ? 0 : TQ * a.n_targets * (int)sizeof(int));
+  static DevOnce attr;
+  if (attr.need()) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_rank_kernel<FILL, EXCL>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                GEMM_LDS + TQ * 16 + 16 + (FILL ? 0 : TQ * MAX_K * (int)sizeof(int))));
+    attr.done();
+  }
+  const RankMargin m(a.dim, a.metric);
+  const int total_tiles = (int)((a.n_bank + TB - 1) / TB);
+  const int tps = (total_tiles + a.splits - 1) / a.splits;
+  hipLaunchKernelGGL((knn_rank_kernel<FILL, EXCL>), dim3((unsigned)((a.n_query + TQ - 1) / TQ), (unsigned)a.splits),
+                     dim3(256), lds, st, (const unsigned char*)qimg, reinterpret_cast<const unsigned char*>(a.packed),
+                     (long)a.n_query, (int)a.n_bank, a.dim, a.metric, a.n_targets, thr, rowlim, m.ctau,
+                     (long)a.self_offset, tps, a.splits, reinterpret_cast<const long long*>(a.query_group),
+                     reinterpret_cast<const long long*>(a.bank_group), rank, counts,
+                     reinterpret_cast<const long long*>(offsets), cand, reinterpret_cast<unsigned long long*>(cmask),
+                     (long long)n_band, err);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t btsbot_knn_rank_workspace(int64_t n_query, int dim, int n_targets) {
+  if (check_shape("btsbot_knn_rank_workspace", n_query, 0, dim, n_targets) != BTSBOT_OK) return BTSBOT_ERR_INVALID_ARG;
+  return (int64_t)(image_bytes(n_query, dim) + rank_thr_bytes(n_query, n_targets) + (size_t)n_query * sizeof(float));
+}
+
+extern "C" int btsbot_knn_rank_count(const float* queries, int64_t n_query, const float* bank, const void* packed,
+                                     int64_t n_bank, int dim, int metric, const int64_t* targets, int n_targets,
+                                     int64_t self_offset, int splits, const int64_t* query_group,
+                                     const int64_t* bank_group, int flags, float* dist, int32_t* rank, int32_t* counts,
+                                     void* workspace, int64_t workspace_bytes, void* stream) {
+  const RankArgs a{queries, n_query, bank, packed, n_bank, dim, metric, targets, n_targets, self_offset, splits,
+                   query_group, bank_group, flags, workspace, workspace_bytes};
+  TRY(rank_checked("btsbot_knn_rank_count", a));
+  if (n_query == 0) return BTSBOT_OK;
+  if (dist == nullptr || rank == nullptr || counts == nullptr) {
+    btsbot_set_error("btsbot_knn_rank_count: NULL dist / rank / counts");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* qimg = reinterpret_cast<unsigned char*>(workspace);
+  float2* thr = reinterpret_cast<float2*>(qimg + image_bytes(n_query, dim));
+  float* rowlim = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(thr) + rank_thr_bytes(n_query, n_targets));
+  hipLaunchKernelGGL(knn_pack_kernel, dim3((unsigned)((n_query + 3) / 4)), dim3(256), 0, st, queries, (long)n_query, dim,
+                     (int)MODE_QUERY, qimg);
+  LAUNCH_CHECK();
+  const RankMargin m(dim, metric);
+  hipLaunchKernelGGL(knn_rank_thresh_kernel, dim3((unsigned)n_query), dim3(64), 0, st, queries, bank,
+                     reinterpret_cast<const unsigned char*>(packed), (long)n_bank, dim, metric,
+                     reinterpret_cast<const long long*>(targets), n_targets, (long)self_offset,
+                     flags != 0 ? reinterpret_cast<const long long*>(query_group) : nullptr,
+                     reinterpret_cast<const long long*>(bank_group), m.rel, m.relm, m.ctau, dist, rank, thr, rowlim);
+  LAUNCH_CHECK();
+  if (n_bank == 0) {   // every target is out of range: rank -1, dist NaN, no band
+    HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_query * splits * sizeof(int), st));
+    return BTSBOT_OK;
+  }
+  return flags != 0 ? launch_rank<false, true>(a, rank, counts, nullptr, nullptr, nullptr, 0, nullptr, st)
+                    : launch_rank<false, false>(a, rank, counts, nullptr, nullptr, nullptr, 0, nullptr, st);
+}
+
+extern "C" int btsbot_knn_rank_fill(const float* queries, int64_t n_query, const float* bank, const void* packed,
+                                    int64_t n_bank, int dim, int metric, const int64_t* targets, int n_targets,
+                                    int64_t self_offset, int splits, const int64_t* query_group,
+                                    const int64_t* bank_group, int flags, const float* dist, int32_t* rank,
+                                    const int32_t* counts, const int64_t* offsets, int64_t n_band, int32_t* cand,
+                                    uint64_t* cand_mask, int32_t* error_flag, void* workspace, int64_t workspace_bytes,
+                                    void* stream) {
+  const RankArgs a{queries, n_query, bank, packed, n_bank, dim, metric, targets, n_targets, self_offset, splits,
+                   query_group, bank_group, flags, workspace, workspace_bytes};
+  TRY(rank_checked("btsbot_knn_rank_fill", a));
+  if (n_band < 0) {
+    btsbot_set_error("btsbot_knn_rank_fill: n_band=%lld", (long long)n_band);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (n_query == 0 || n_band == 0 || n_bank == 0) return BTSBOT_OK;
+  if (dist == nullptr || rank == nullptr || counts == nullptr || offsets == nullptr || cand == nullptr ||
+      cand_mask == nullptr || error_flag == nullptr) {
+    btsbot_set_error("btsbot_knn_rank_fill: NULL argument");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  int* cnt = const_cast<int*>(counts);   // (read only by the FILL instantiation)
+  TRY(flags != 0 ? (launch_rank<true, true>(a, rank, cnt, offsets, cand, cand_mask, n_band, error_flag, st))
+                 : (launch_rank<true, false>(a, rank, cnt, offsets, cand, cand_mask, n_band, error_flag, st)));
+  // enough waves per query that a crowded row does not serialise, as the radius verify
+  const int64_t per = (n_band + n_query - 1) / n_query;
+  const unsigned Y = (unsigned)(per <= 32 ? 1 : per >= 32 * 64 ? 64 : (per + 31) / 32);
+  hipLaunchKernelGGL(knn_rank_verify_kernel, dim3((unsigned)n_query, Y), dim3(64), 0, st, queries, bank,
+                     reinterpret_cast<const long long*>(targets), n_targets, dist,
+                     reinterpret_cast<const long long*>(offsets), splits, (const int*)cand,
+                     reinterpret_cast<const unsigned long long*>(cand_mask), (int)n_bank, dim, metric, rank);
   LAUNCH_CHECK();
   return BTSBOT_OK;
 }

@@ -432,6 +432,13 @@ class EmbeddingMap:
         self._map_index = None
         return y
 
+    def quality(self, n_neighbors: Optional[int] = None, rows: Optional[torch.Tensor] = None) -> dict:
+        """``quality.map_quality`` of ``embedding_`` against the bank it maps: trustworthiness, continuity and
+        neighbour recall at ``n_neighbors`` (default: the map's own), judged from ``rows`` (default: every row)."""
+        from .quality import map_quality
+        k = self.n_neighbors if n_neighbors is None else n_neighbors
+        return map_quality(self.index.bank, self.embedding_, k, metric=self.index.metric, rows=rows)
+
     def map_index(self):
         """A ``MapIndex`` over ``embedding_`` -- radius, count and k-nearest questions about the MAP positions --,
         built at the first call and kept until ``extend`` moves on (or ``embedding_`` is replaced)."""

@@ -51,6 +51,17 @@ their direct-form distances, torch compacts and orders; nothing of size Q x N is
 size the candidates, then the lists).  The margin grows with ``|q|^2 + |b|^2``: centre the rows (``rows - rows.mean(0)``),
 or data far from the origin relative to its spread verifies most pairs -- exactly, and slowly.
 
+Where a row stands.  The third question: not which rows are near, but how near a GIVEN row is.
+
+    rank, dist = index.rank_of(queries, targets)                 # int64 [Q, t], float32 [Q, t] for targets int64 [Q, t]
+    rank, dist = neighbor_ranks(queries, bank, targets)          # packs the bank for this one call
+
+``rank[q, c]`` is the number of eligible bank rows b with (direct-form distance, b) before (``dist[q, c]``,
+``targets[q, c]``): 0-based, without a cap, the position of the target in ``radius(q, dist[:, c], sort="distance")``
+with the same switches, bit for bit.  The tile walk counts the pairs that are surely before -- below the target's
+distance by more than the margin of both forms -- and hands the pairs inside the margin to the direct form; two host
+reads (the number of these band pairs, the fill's error flag).  ``quality.trustworthiness`` is built on it.
+
 On a 2-D map.  ``radius_graph`` and ``knn_graph`` take ``method="grid"`` for 2-D rows and the
 euclidean metric: ``mapindex.MapIndex`` answers from a uniform grid in time linear in the rows plus the output, with the
 same membership, ordering and distances (the radius lists are bit-identical).  The default, ``"tiles"``, is the path
@@ -316,6 +327,76 @@ class EmbeddingIndex:
             order = _csr_order(rows, cand.to(torch.int64), cdist, max(n, 1), sort, keep=keep, total=total)
             return indptr, cand[order].to(torch.int64), cdist[order]
 
+    def rank_of(self, queries: torch.Tensor, targets: torch.Tensor, *, query_groups: Optional[torch.Tensor] = None,
+                exclude_same_group: bool = False, one_per_group: bool = False, self_offset: int = -1, splits: int = 0,
+                max_band: Optional[int] = None, stats: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Where given rows of the index stand in each query row's neighbour ordering: ``rank``
+        int64 [Q, t] and ``dist`` float32 [Q, t] for ``targets`` int64 [Q, t], bank row numbers, 1 <= t <= 64.
+        ``dist[q, c]`` is the direct-form distance to row ``targets[q, c]``, the bits ``query`` and ``radius`` return
+        for that pair; ``rank[q, c]`` is the number of eligible rows b with (distance, b) before (``dist[q, c]``,
+        ``targets[q, c]``): 0-based, the position of the target in ``radius(q, dist[:, c], sort="distance")`` with the
+        same switches, bit for bit.  ``rank = -1`` where the target is < 0 or >= len(index), is not eligible for the
+        row (non-finite, the masked self, the row's own group under ``exclude_same_group``) or the query row is
+        non-finite; ``dist`` is NaN where the target is out of range or either row is non-finite.  There is no cap on
+        the rank.  max_band: ValueError (naming the total) instead of more than this many band pairs, the pairs whose
+        order against a target only the direct form can decide.  stats: receives ``band`` and ``error_flag``.  The
+        other arguments are ``radius``'s; ``one_per_group`` is not a rank mode.  Two host reads: the number of band
+        pairs, to allocate them, and the fill's error flag."""
+        _check_rank_args(targets, int(queries.shape[0]) if isinstance(queries, torch.Tensor) and queries.dim() == 2
+                         else None, splits, max_band, one_per_group)
+        flags = _check_group_args(1, self._groups is not None, query_groups, exclude_same_group, False)
+        q = _rows(queries, "queries", self.device)
+        if q.shape[1] != self.dim:
+            raise ValueError(f"queries: D = {q.shape[1]}, the index holds D = {self.dim}")
+        if not isinstance(self_offset, int):
+            raise ValueError(f"self_offset must be an int, got {self_offset!r}")
+        if targets.device != self.device:
+            raise ValueError(f"targets is on {targets.device}, the index on {self.device}")
+        nq, n, dev, t = int(q.shape[0]), self._n, self.device, int(targets.shape[1])
+        if query_groups is not None:
+            query_groups = _groups(query_groups, "query_groups", nq, dev)
+        tg = targets.detach().contiguous()
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            dist = torch.full((nq, t), float("nan"), dtype=torch.float32, device=dev)
+            rank = torch.full((nq, t), -1, dtype=torch.int32, device=dev)
+            if stats is not None:
+                stats.update(band=0, error_flag=0)
+            if nq == 0:
+                return rank.to(torch.int64), dist
+            if splits == 0:
+                splits = max(1, int(L.btsbot_knn_splits(nq, n, self.dim, 1)))
+            counts = torch.zeros((nq, splits), dtype=torch.int32, device=dev)
+            need = int(L.btsbot_knn_rank_workspace(nq, self.dim, t))
+            if need < 0:
+                _lib.check(need, "btsbot_knn_rank_workspace")
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+            head = (_ptr(q), nq, _ptr(self._bank), _ptr(self._packed), n, self.dim, self._metric_id, _ptr(tg), t,
+                    self_offset, splits, _ptr(query_groups) if flags else None, _ptr(self._groups) if flags else None,
+                    flags)
+            _lib.check(L.btsbot_knn_rank_count(*head, _ptr(dist), _ptr(rank), _ptr(counts), _ptr(ws), need,
+                                               self._stream()), "btsbot_knn_rank_count")
+            offsets = torch.zeros(nq * splits + 1, dtype=torch.int64, device=dev)
+            offsets[1:] = torch.cumsum(counts.view(-1), 0, dtype=torch.int64)
+            n_band = int(offsets[-1])                                       # the host read that sizes the band pairs
+            if max_band is not None and n_band > max_band:
+                raise ValueError(f"the band holds {n_band} pairs, more than max_band = {max_band}")
+            flag = 0
+            if n_band:
+                cand = torch.full((n_band,), -1, dtype=torch.int32, device=dev)
+                cmask = torch.zeros(n_band, dtype=torch.int64, device=dev)
+                err = torch.zeros(1, dtype=torch.int32, device=dev)
+                _lib.check(L.btsbot_knn_rank_fill(*head, _ptr(dist), _ptr(rank), _ptr(counts), _ptr(offsets), n_band,
+                                                  _ptr(cand), _ptr(cmask), _ptr(err), _ptr(ws), need, self._stream()),
+                           "btsbot_knn_rank_fill")
+                flag = int(err[0])                                          # the second read: the fill's bounds check
+            if stats is not None:
+                stats.update(band=n_band, error_flag=flag)
+            if flag:
+                raise RuntimeError("btsbot_knn_rank_fill: a band pair fell past the end of its region (the count and "
+                                   "the fill pass disagree); the ranks are not returned")
+            return rank.to(torch.int64), dist
+
     def count_within(self, queries: torch.Tensor, r, **kw) -> torch.Tensor:
         """int64 [Q]: how many rows of the index lie within ``r`` of each query row -- exact, the ``indptr.diff()`` of
         ``radius`` with the same arguments (it goes through the lists; 0 is novelty, thousands a crowded region)."""
@@ -341,6 +422,42 @@ def _check_radius_args(r, n_query, sort, splits, max_total) -> None:
         raise ValueError(f"splits must be an int in 0..{_lib.KNN_MAX_SPLITS} (0: the library's choice), got {splits!r}")
     if max_total is not None and (isinstance(max_total, bool) or not isinstance(max_total, int) or max_total < 0):
         raise ValueError(f"max_total must be None or an int >= 0, got {max_total!r}")
+
+
+def _check_rank_args(targets, n_query, splits, max_band, one_per_group=False) -> None:
+    """ValueError for what ``rank_of`` cannot answer, before anything touches the device."""
+    if one_per_group:
+        raise ValueError("one_per_group is not a rank mode (a rank counts rows, not groups)")
+    if not isinstance(targets, torch.Tensor) or targets.dtype != torch.int64:
+        raise ValueError(f"targets must be an int64 torch.Tensor [Q, t] of bank row numbers, got "
+                         f"{targets.dtype if isinstance(targets, torch.Tensor) else type(targets).__name__}")
+    if targets.dim() != 2 or not 1 <= targets.shape[1] <= _lib.KNN_MAX_K or \
+            (n_query is not None and targets.shape[0] != n_query):
+        raise ValueError(f"targets must be [Q = {n_query}, t] with 1 <= t <= {_lib.KNN_MAX_K}, got {tuple(targets.shape)}")
+    if not isinstance(splits, int) or isinstance(splits, bool) or not 0 <= splits <= _lib.KNN_MAX_SPLITS:
+        raise ValueError(f"splits must be an int in 0..{_lib.KNN_MAX_SPLITS} (0: the library's choice), got {splits!r}")
+    if max_band is not None and (isinstance(max_band, bool) or not isinstance(max_band, int) or max_band < 0):
+        raise ValueError(f"max_band must be None or an int >= 0, got {max_band!r}")
+
+
+def neighbor_ranks(queries: torch.Tensor, bank: torch.Tensor, targets: torch.Tensor, metric: str = "euclidean", *,
+                   bank_groups: Optional[torch.Tensor] = None, query_groups: Optional[torch.Tensor] = None,
+                   exclude_same_group: bool = False, self_offset: int = -1, splits: int = 0,
+                   max_band: Optional[int] = None, stats: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``rank`` int64 [Q, t] and ``dist`` float32 [Q, t] of the rows ``targets`` [Q, t] of ``bank`` [N, D] in the
+    neighbour ordering of each row of ``queries`` [Q, D], as ``EmbeddingIndex.rank_of`` returns them.  Packs the bank for
+    this one call."""
+    _metric(metric)
+    _check_rank_args(targets, int(queries.shape[0]) if isinstance(queries, torch.Tensor) and queries.dim() == 2 else None,
+                     splits, max_band)
+    _check_group_args(1, bank_groups is not None, query_groups, exclude_same_group, False)
+    q = _rows(queries, "queries")
+    b = _rows(bank, "bank", q.device)
+    if q.shape[1] != b.shape[1]:
+        raise ValueError(f"queries have D = {q.shape[1]}, the bank D = {b.shape[1]}")
+    return EmbeddingIndex(b, metric, groups=bank_groups).rank_of(
+        q, targets, query_groups=query_groups, exclude_same_group=exclude_same_group, self_offset=self_offset,
+        splits=splits, max_band=max_band, stats=stats)
 
 
 def _float_order(dist: torch.Tensor) -> torch.Tensor:

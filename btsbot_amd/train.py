@@ -330,7 +330,9 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
     ``config['embedding_clusters'] = {"eps": ..., "min_samples": 5, "on": "map" | "embedding", "method": "tiles" |
     "grid"}`` (``"grid"``: the 2-D map only, the same labels in time linear in the rows) the DBSCAN labels
     (``clusters.dbscan``; -1 = noise) of the map, as a ``cluster`` column of ``{stem}_umap.csv``, or of the embedding
-    rows, as ``{stem}_clusters.npy`` (int64 [N]).  Returns the .npy path."""
+    rows, as ``{stem}_clusters.npy`` (int64 [N]).  ``config['embedding_layout']`` also takes ``"quality": True | k``:
+    ``write_map_quality`` leaves ``{stem}_umap_quality.json``, the map's trustworthiness, continuity and neighbour recall
+    at ``k`` (``True``: the layout's ``n_neighbors``).  Returns the .npy path."""
     import numpy as np
     from .data import load_split
     from .pipeline import ScoreStream
@@ -401,7 +403,11 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
         if kw.get("group_by") is not None:   # the map of the graph without the row's own object
             kw["groups"] = group_ids(kw["group_by"], "embedding_layout")
         kw.pop("group_by", None)
-        y_dev = embedding_layout(torch.from_numpy(out).to(dev), **kw)
+        quality = kw.pop("quality", None)   # True | k: judge the map (not an embedding_layout argument)
+        emb_dev = torch.from_numpy(out).to(dev)
+        y_dev = embedding_layout(emb_dev, **kw)
+        if quality:
+            write_map_quality(stem, emb_dev, y_dev, quality, kw)
         y = y_dev.cpu().numpy()
         table = {"umap_emb_1": y[:, 0], "umap_emb_2": y[:, 1]}
         if "candid" in cand.columns:
@@ -411,6 +417,23 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
             table["cluster"] = labels.cpu().numpy()
         pd.DataFrame(table).to_csv(stem + "_umap.csv", index=False)
     return stem + ".npy"
+
+
+def write_map_quality(stem: str, emb, y, quality=True, layout_kw: Optional[dict] = None) -> str:
+    """``quality.map_quality`` of the map ``y`` of the rows ``emb`` as ``{stem}_umap_quality.json``.  quality: ``True``
+    (k = the layout's ``n_neighbors``, 15 by default) or k; layout_kw: the keyword arguments the map was laid out with,
+    of which ``n_neighbors``, ``metric`` and ``groups`` are read.  Returns the path."""
+    import json
+    from . import quality as Q
+    kw = layout_kw or {}
+    k = kw.get("n_neighbors", 15) if quality is True else quality
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise ValueError(f"config['embedding_layout']['quality'] must be True or an int k, got {quality!r}")
+    res = Q.map_quality(emb, y, k, metric=kw.get("metric", "euclidean"), groups=kw.get("groups"))
+    path = stem + "_umap_quality.json"
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+    return path
 
 
 def run_training(config: dict, data_base_dir: str = "", run_name: str = "testing", device="cuda",

@@ -49,6 +49,9 @@ def main():
     purity = float((labels[idx[:, 1:].cpu().numpy()] == labels[:, None]).mean())
     print(f"{args.n} rows of width {emb.shape[1]} -> map of extent x [{y[:, 0].min():.1f}, {y[:, 0].max():.1f}], "
           f"y [{y[:, 1].min():.1f}, {y[:, 1].max():.1f}]; 5-neighbour label purity in the map {purity:.3f}")
+    q = btsbot_amd.map_quality(emb, torch.from_numpy(y).to(dev), 15)
+    print(f"map quality at k = {q['k']} over {q['rows']} rows: trustworthiness {q['trustworthiness']:.4f}, continuity "
+          f"{q['continuity']:.4f}, neighbour recall {q['neighbor_recall']:.3f}")
     if args.csv:
         import pandas as pd
         pd.DataFrame({"umap_emb_1": y[:, 0], "umap_emb_2": y[:, 1], "label": labels}).to_csv(args.csv, index=False)

@@ -915,6 +915,50 @@ int btsbot_knn_radius_fill(const float* queries, int64_t n_query, const float* b
                            const int64_t* offsets, int64_t n_cand, int32_t* cand, float* dist, uint8_t* keep,
                            int32_t* error_flag, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- neighbour ranks: where does a given bank row stand in a query row's ordering (csrc/knn.hip) ---- */
+
+/* targets int64 [n_query][n_targets] (device memory, 1 <= n_targets <= 64) names bank rows.  For every (q, c):
+ *   dist[q][c] = the direct-form fp32 distance of query row q and bank row targets[q][c] -- the bits btsbot_knn_query and
+ *                btsbot_knn_radius_fill return for that pair; NaN where the target is < 0 or >= n_bank or either row
+ *                holds a non-finite value;
+ *   rank[q][c] = the number of bank rows b, eligible for q as in btsbot_knn_radius_* (finite, not the row self_offset
+ *                masks, not of q's group under BTSBOT_KNN_EXCLUDE_SAME), whose (direct-form distance, b) is before
+ *                (dist[q][c], targets[q][c]): distance first, then index, both sides fp32 direct form.  0-based; the
+ *                target does not count against itself.  -1 where the target is out of range or not eligible for q, or
+ *                query row q is not finite.
+ * Hence rank[q][c] is the position of targets[q][c] in q's list of btsbot_knn_radius_* at radius dist[q][c], ordered by
+ * (dist, index), bit for bit.  A (q, c) answer does not depend on the other rows or columns, on splits or on the run;
+ * only integer additions meet across workgroups.  queries, bank, packed, dim, metric, self_offset, query_group /
+ * bank_group: as btsbot_knn_query_grouped; flags: 0 or BTSBOT_KNN_EXCLUDE_SAME; splits: 1..32, the same in both calls.
+ * workspace: btsbot_knn_rank_workspace(n_query, dim, n_targets) bytes, 16-byte aligned, the SAME memory in both calls and
+ * untouched between them (the packed query rows and the thresholds of the count call).
+ *
+ * btsbot_knn_rank_count(): writes dist, initialises rank (int32 [n_query][n_targets]: 0, or -1) and adds to it the pairs
+ * that are surely before -- whose GEMM-form value is below dist^2 less the two-sided margin of DESIGN.md 4r --;
+ * counts int32 [n_query][splits] = the BAND pairs of each query row in each bank slice, those the margin cannot decide
+ * for at least one column.  Three launches (query pack, thresholds, tile pass).  The caller forms offsets int64
+ * [n_query * splits + 1], the exclusive scan of counts with the total last, and reads the total n_band to allocate.
+ *
+ * btsbot_knn_rank_fill(): the same walk writes each band pair as cand int32 [n_band] (the bank row) and cand_mask
+ * uint64 [n_band] (bit c: the pair is in column c's band), every slot checked against its region (*error_flag, int32,
+ * zeroed by the caller, is set to 1 otherwise -- it cannot happen while counts and offsets are the count call's); then
+ * one wave per band pair computes the direct-form distance once and adds 1 to rank[q][c] for every masked column the
+ * pair is before.  Two launches; n_band == 0 launches nothing and rank is final after the count call.
+ * BTSBOT_ERR_INVALID_ARG with a message, before any HIP call, for the shapes btsbot_knn_query refuses (n_targets in k's
+ * place), splits outside 1..32, flags other than 0 / BTSBOT_KNN_EXCLUDE_SAME (BTSBOT_KNN_ONE_PER_GROUP is not a rank
+ * mode), a NULL pointer that is needed, a short or misaligned workspace. */
+int64_t btsbot_knn_rank_workspace(int64_t n_query, int dim, int n_targets);
+int btsbot_knn_rank_count(const float* queries, int64_t n_query, const float* bank, const void* packed, int64_t n_bank,
+                          int dim, int metric, const int64_t* targets, int n_targets, int64_t self_offset, int splits,
+                          const int64_t* query_group, const int64_t* bank_group, int flags, float* dist, int32_t* rank,
+                          int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
+int btsbot_knn_rank_fill(const float* queries, int64_t n_query, const float* bank, const void* packed, int64_t n_bank,
+                         int dim, int metric, const int64_t* targets, int n_targets, int64_t self_offset, int splits,
+                         const int64_t* query_group, const int64_t* bank_group, int flags, const float* dist,
+                         int32_t* rank, const int32_t* counts, const int64_t* offsets, int64_t n_band, int32_t* cand,
+                         uint64_t* cand_mask, int32_t* error_flag, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
 /* ---- connected components of a CSR graph and the DBSCAN labelling rule (csrc/components.hip) ---- */
 
 /* btsbot_graph_components(): indptr int64 [n + 1], indices int64 [indptr[n]] (values in [0, n)), mask uint8 [n] or

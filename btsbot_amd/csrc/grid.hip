@@ -1,7 +1,7 @@
 // btsbot_grid_*: exact radius and k-nearest search over 2-D fp32 points on a uniform grid (gfx950), DESIGN.md section 4q.
 //
 // The grid only prunes, it never decides.  Every kernel here computes a pair's distance with grid_distance() -- the value
-// direct_distance() of knn.hip gives at D = 2: sqrtf(fl(fl(t0 t0) + fl(t1 t1))), t = q - b, nothing contracted -- and
+// direct_distance() of knn_tile.h gives at D = 2: sqrtf(fl(fl(t0 t0) + fl(t1 t1))), t = q - b, nothing contracted -- and
 // decides membership and rank by it alone; the cells say which pairs are looked at.  That no member is missed rests on
 // three facts (4q holds the proof):
 //   * cell_of() is a monotone function of the coordinate: fl(x - x0), fl(. * inv_h) with inv_h >= 0, floor and clamp are

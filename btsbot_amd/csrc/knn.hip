@@ -59,46 +59,16 @@
 // has k groups' bests of one split before it, each represented in the pool by a kept entry no worse -- rank >= k.  The
 // answer is the same whatever `splits` is.
 //
-// Radius search (btsbot_knn_radius_*): the same grid and tile walk with the epilogue "admit if
-// within r" -- see knn_radius_kernel -- and direct_distance(), the one function that computes a returned distance, for
-// the merge's winners and for every radius candidate alike.
-//
-// Neighbour ranks (btsbot_knn_rank_*): the same walk with a third epilogue, "count if surely before
-// the target, hand to the direct form if within the margin" -- see knn_rank_kernel.
-#include <float.h>
-
-#include "common.h"
+// knn_tile.h holds what this file shares with the radius search (knn_radius.hip) and the neighbour ranks
+// (knn_rank.hip): the record, the tile walk, direct_distance() -- the one function that computes a returned distance --
+// and the host helpers defined at the end of this file.
+#include "knn_tile.h"
 
 namespace {
 
-constexpr int TQ = 128, TB = 128;   // query rows and bank rows per tile
-constexpr int BK = 64;              // K elements per tile
-constexpr int ROWB = 128;           // bytes per LDS row of one plane (64 f16)
-constexpr int GEMM_LDS = 2 * (TQ + TB) * ROWB;   // 64 KB: four operand planes
 constexpr int BCAP = 8;             // candidates a query row's bucket holds per round
-constexpr int HDR = 16;             // bytes in front of a record's head plane
-constexpr int EMPTY = 0x7fffffff;   // index of an empty list entry (score +inf)
-constexpr int MAX_K = 64, MAX_DIM = 1024, MAX_SPLITS = 32;
 enum { MODE_BANK_L2 = 0, MODE_BANK_COS = 1, MODE_QUERY = 2 };
-enum { GM_EXCLUDE = BTSBOT_KNN_EXCLUDE_SAME, GM_ONE = BTSBOT_KNN_ONE_PER_GROUP };   // group mode bits (template GM)
-constexpr int MAX_K_ONE = 32;       // k's cap with one entry per group: the merge's pool carries its groups on chip
 constexpr int TG_OFF = 16 * 1024;   // the tile's bank groups in the idle operand LDS, behind buckets, counts and flags
-
-struct Cand {
-  float s;
-  int i;
-};
-
-__host__ __device__ inline int padded_dim(int dim) { return (dim + 31) & ~31; }
-__host__ __device__ inline size_t record_bytes(int dim) { return (size_t)HDR + 4 * (size_t)padded_dim(dim); }
-
-__device__ __forceinline__ bool before(float s1, int i1, float s2, int i2) { return s1 < s2 || (s1 == s2 && i1 < i2); }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // pack: one wave per row
@@ -168,128 +138,6 @@ __global__ __launch_bounds__(256) void knn_pack_kernel(const float* __restrict__
 
 // ---------------------------------------------------------------------------------------------------------------------
 // selection
-__device__ __forceinline__ f32x4 mma_x2(const h2x8& a, const h2x8& b, f32x4 c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.lo, b.hi, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.lo, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, b.hi, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ int swz(int row, int chunk) { return row * ROWB + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-// The barriers behind a tile's products: LDS traffic only, so the next tile's operand loads stay in flight across them
-// (__syncthreads() would wait for them)
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");   // (no LDS read of the next phase moves above the barrier)
-}
-
-// A workgroup's walk over its bank tiles, the selection kernel's statements as a struct for the radius kernels (the
-// selection keeps its own text, see there): the operand registers of the K tile in flight (loaded under the products of
-// the one before) and the 128 x 128 x dp products of one bank tile.
-// products() leaves behind an lds_barrier: the operand planes are idle and may be used by the caller's epilogue, which
-// must end with a barrier of its own if it writes there.
-struct TileWalk {
-  static constexpr int MI = 4, NI = 4;     // 16-row fragments per wave: queries (B operand), bank rows (A operand)
-  static constexpr int CH = TQ * 8 / 256;  // 16-byte chunks per thread, plane and K tile (TQ == TB)
-  const unsigned char* qimg;
-  const unsigned char* bimg;
-  unsigned char* smem;
-  long Q, q0;
-  int N, dp, nk, tid;
-  size_t rec;
-  uint4 qh[CH], ql[CH], bh[CH], bl[CH];
-
-  __device__ __forceinline__ void init(const unsigned char* qi, const unsigned char* bi, unsigned char* lds, long nq,
-                                       long first_q, int nb, int dim) {
-    qimg = qi;
-    bimg = bi;
-    smem = lds;
-    Q = nq;
-    q0 = first_q;
-    N = nb;
-    dp = padded_dim(dim);
-    nk = (dp + BK - 1) / BK;
-    tid = threadIdx.x;
-    rec = record_bytes(dim);
-  }
-  __device__ __forceinline__ void gload(int tile, int kt) {
-    const int k0 = kt * BK;
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const int c = tid + i * 256, row = c >> 3, gk = k0 + (c & 7) * 8;
-      const long gq = q0 + row;
-      const long gb = (long)tile * TB + row;
-      const bool kin = gk < dp;   // (dp % 8 == 0: a chunk is wholly inside or wholly outside)
-      const unsigned char* pq = qimg + gq * rec + HDR + gk * 2;
-      const unsigned char* pb = bimg + gb * rec + HDR + gk * 2;
-      const bool okq = kin && gq < Q, okb = kin && gb < N;
-      qh[i] = okq ? *reinterpret_cast<const uint4*>(pq) : make_uint4(0, 0, 0, 0);
-      ql[i] = okq ? *reinterpret_cast<const uint4*>(pq + 2 * dp) : make_uint4(0, 0, 0, 0);
-      bh[i] = okb ? *reinterpret_cast<const uint4*>(pb) : make_uint4(0, 0, 0, 0);
-      bl[i] = okb ? *reinterpret_cast<const uint4*>(pb + 2 * dp) : make_uint4(0, 0, 0, 0);
-    }
-  }
-  __device__ __forceinline__ void sstore() {
-    unsigned char* Qh = smem;
-    unsigned char* Ql = Qh + TQ * ROWB;
-    unsigned char* Bh = Ql + TQ * ROWB;
-    unsigned char* Bl = Bh + TB * ROWB;
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const int c = tid + i * 256;
-      const int o = swz(c >> 3, c & 7);
-      *reinterpret_cast<uint4*>(Qh + o) = qh[i];
-      *reinterpret_cast<uint4*>(Ql + o) = ql[i];
-      *reinterpret_cast<uint4*>(Bh + o) = bh[i];
-      *reinterpret_cast<uint4*>(Bl + o) = bl[i];
-    }
-  }
-  // acc[ni][mi] = the products of bank tile `tile` (gload(tile, 0) has been issued); loads the next tile's first operands
-  __device__ __forceinline__ void products(f32x4 (&acc)[NI][MI], int tile, int t_end) {
-    const unsigned char* Qh = smem;
-    const unsigned char* Ql = Qh + TQ * ROWB;
-    const unsigned char* Bh = Ql + TQ * ROWB;
-    const unsigned char* Bl = Bh + TB * ROWB;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int lrow = lane & 15, lq = lane >> 4;
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int kt = 0; kt < nk; ++kt) {
-      sstore();
-      __syncthreads();
-      if (kt + 1 < nk) gload(tile, kt + 1);
-      else if (tile + 1 < t_end) gload(tile + 1, 0);
-#pragma unroll 1   // (unrolled, the fragments of both halves are loaded up front: 56 registers to scratch)
-      for (int ks = 0; ks < BK / 32; ++ks) {
-        if (kt * BK + ks * 32 < dp) {
-          h2x8 bfr[MI];
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi) {
-            const int o = swz(wm * 64 + mi * 16 + lrow, ks * 4 + lq);
-            bfr[mi].hi = *reinterpret_cast<const f16x8*>(Qh + o);
-            bfr[mi].lo = *reinterpret_cast<const f16x8*>(Ql + o);
-          }
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni) {
-            const int o = swz(wn * 64 + ni * 16 + lrow, ks * 4 + lq);
-            h2x8 afr;
-            afr.hi = *reinterpret_cast<const f16x8*>(Bh + o);
-            afr.lo = *reinterpret_cast<const f16x8*>(Bl + o);
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = mma_x2(afr, bfr[mi], acc[ni][mi]);
-          }
-        }
-      }
-      lds_barrier();
-    }
-  }
-};
-
 // A list is the k best by (score, index) of what it was offered, UNSORTED (the merge ranks by counting), with its worst
 // entry (ts, ti) at position tp: a better candidate replaces the worst, then the worst is looked up again -- k independent
 // LDS reads, where shifting a sorted list was a chain of dependent ones (23 of 51 ms at N = 500,000, D = 528, k = 15).
@@ -352,8 +200,7 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
                                                             const long long* __restrict__ qgrp,
                                                             const long long* __restrict__ bgrp,
                                                             long long* __restrict__ lgrp) {
-  constexpr int MI = 4, NI = 4;     // 16-row fragments per wave: queries (B operand), bank rows (A operand)
-  constexpr int CH = TQ * 8 / 256;  // 16-byte chunks per thread, plane and K tile (TQ == TB)
+  constexpr int MI = TileWalk::MI, NI = TileWalk::NI;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* Qh = smem;
   unsigned char* Ql = Qh + TQ * ROWB;
@@ -370,18 +217,22 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
   long long* LG = lgrp + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * (size_t)k * TQ + threadIdx.x;
   long long* tg = reinterpret_cast<long long*>(smem + TG_OFF);       // GM != 0: [TB] the tile's bank groups
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int lrow = lane & 15, lq = lane >> 4;
+  const int tid = threadIdx.x;
+  const LanePos p;
   const int dp = padded_dim(dim);
   const size_t rec = record_bytes(dim);
   const long q0 = (long)blockIdx.x * TQ;
-  const int split = blockIdx.y;
-  const int total_tiles = (N + TB - 1) / TB;
-  const int t_begin = (int)min((long)split * tiles_per_split, (long)total_tiles);
-  const int t_end = (int)min((long)(split + 1) * tiles_per_split, (long)total_tiles);
-  const int b_end = (int)min((long)t_end * TB, (long)N);
+  const SplitRange sr(N, tiles_per_split);
   const int nk = (dp + BK - 1) / BK;
+
+  // This kernel shares LanePos, SplitRange, the operand loads and their LDS store (tile_gload, tile_sstore),
+  // load_tile_group and tile_score with the radius and rank passes, and keeps its own text of the rest of a tile pass --
+  // the query rows' header, the product loop, the fragment's biases, scales and groups, the eligibility term (QueryRows,
+  // TileWalk::products, frag_bias_scale, frag_groups, eligible) -- because each of these moves its allocation.  Scratch
+  // bytes per lane for GM = 0 / 1 / 2 / 3: this text 172 / 280 / 184 / 316, as ever.  All of it on the shared pieces:
+  // 144 / 200 / 160 / 212, every one lower, and 2 % slower (42.1 against 41.3 ms per query call at N = 1,000,000,
+  // Q = 8,192, D = 528, k = 15, twice each).  The product loop shared too: 156 / 288 / 176 / 292; the plain struct: 156 /
+  // 288 / 180 / 300 -- both above 280 for GM = 1.  DESIGN.md 4s.
 
   // the thread's own list (threads 0..TQ-1: query row q0 + tid)
   const bool owner = tid < TQ && q0 + tid < Q;
@@ -394,7 +245,7 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
   int selfb[MI];   // the bank row that IS the query row (never a candidate), -1: none
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi) {
-    const long gq = q0 + wm * 64 + mi * 16 + lrow;
+    const long gq = p.gq(q0, mi);
     sq[mi] = gq < Q ? reinterpret_cast<const float*>(qimg + gq * rec)[1] : 0.f;
     const long sb = gq + self_offset;
     selfb[mi] = self_offset >= 0 && sb < N ? (int)sb : -1;
@@ -403,52 +254,21 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
   if constexpr ((GM & GM_EXCLUDE) != 0) {
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
-      const long gq = q0 + wm * 64 + mi * 16 + lrow;
+      const long gq = p.gq(q0, mi);
       qg[mi] = gq < Q ? qgrp[gq] : 0;   // (a row past Q never has a candidate)
     }
   }
 
-  // (the operand loads and the products below are TileWalk's, kept in this kernel's own text: routed through the
-  //  struct the same statements allocate registers differently -- scratch 172 -> 156, 280 -> 288 bytes -- and this
-  //  kernel's figures are held fixed)
   uint4 qh[CH], ql[CH], bh[CH], bl[CH];
-  auto gload = [&](int tile, int kt) {
-    const int k0 = kt * BK;
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const int c = tid + i * 256, row = c >> 3, gk = k0 + (c & 7) * 8;
-      const long gq = q0 + row;
-      const long gb = (long)tile * TB + row;
-      const bool kin = gk < dp;   // (dp % 8 == 0: a chunk is wholly inside or wholly outside)
-      const unsigned char* pq = qimg + gq * rec + HDR + gk * 2;
-      const unsigned char* pb = bimg + gb * rec + HDR + gk * 2;
-      const bool okq = kin && gq < Q, okb = kin && gb < N;
-      qh[i] = okq ? *reinterpret_cast<const uint4*>(pq) : make_uint4(0, 0, 0, 0);
-      ql[i] = okq ? *reinterpret_cast<const uint4*>(pq + 2 * dp) : make_uint4(0, 0, 0, 0);
-      bh[i] = okb ? *reinterpret_cast<const uint4*>(pb) : make_uint4(0, 0, 0, 0);
-      bl[i] = okb ? *reinterpret_cast<const uint4*>(pb + 2 * dp) : make_uint4(0, 0, 0, 0);
-    }
-  };
-  auto sstore = [&]() {
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const int c = tid + i * 256;
-      const int o = swz(c >> 3, c & 7);
-      *reinterpret_cast<uint4*>(Qh + o) = qh[i];
-      *reinterpret_cast<uint4*>(Ql + o) = ql[i];
-      *reinterpret_cast<uint4*>(Bh + o) = bh[i];
-      *reinterpret_cast<uint4*>(Bl + o) = bl[i];
-    }
-  };
+  auto gload = [&](int tile, int kt) { tile_gload(qh, ql, bh, bl, qimg, bimg, Q, q0, N, dp, rec, tid, tile, kt); };
+  auto sstore = [&]() { tile_sstore(smem, qh, ql, bh, bl, tid); };
 
-  if (t_begin < t_end) gload(t_begin, 0);
+  if (sr.t_begin < sr.t_end) gload(sr.t_begin, 0);
   __syncthreads();   // the lists
-  for (int tile = t_begin; tile < t_end; ++tile) {
+  for (int tile = sr.t_begin; tile < sr.t_end; ++tile) {
     const int b0 = tile * TB;
     long long gt = 0;   // GM != 0: bank row b0 + tid's group, in flight under the products
-    if constexpr (GM != 0) {
-      if (tid < TB && (long)b0 + tid < N) gt = bgrp[(long)b0 + tid];
-    }
+    if constexpr (GM != 0) gt = load_tile_group(bgrp, b0, N);
     f32x4 acc[NI][MI];
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni)
@@ -459,20 +279,20 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
       sstore();
       __syncthreads();
       if (kt + 1 < nk) gload(tile, kt + 1);
-      else if (tile + 1 < t_end) gload(tile + 1, 0);
+      else if (tile + 1 < sr.t_end) gload(tile + 1, 0);
 #pragma unroll 1   // (unrolled, the fragments of both halves are loaded up front: 56 registers to scratch)
       for (int ks = 0; ks < BK / 32; ++ks) {
         if (kt * BK + ks * 32 < dp) {
           h2x8 bfr[MI];
 #pragma unroll
           for (int mi = 0; mi < MI; ++mi) {
-            const int o = swz(wm * 64 + mi * 16 + lrow, ks * 4 + lq);
+            const int o = swz(p.qrow(mi), ks * 4 + p.lq);
             bfr[mi].hi = *reinterpret_cast<const f16x8*>(Qh + o);
             bfr[mi].lo = *reinterpret_cast<const f16x8*>(Ql + o);
           }
 #pragma unroll
           for (int ni = 0; ni < NI; ++ni) {
-            const int o = swz(wn * 64 + ni * 16 + lrow, ks * 4 + lq);
+            const int o = swz(p.wn * 64 + ni * 16 + p.lrow, ks * 4 + p.lq);
             h2x8 afr;
             afr.hi = *reinterpret_cast<const f16x8*>(Bh + o);
             afr.lo = *reinterpret_cast<const f16x8*>(Bl + o);
@@ -492,18 +312,18 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
     }
     if (tid < 2) flag[tid] = 0;
     lds_barrier();
-    // scores, and which of them can enter a list (<=: a tie may still win on the index); the tile's bank biases and
-    // scales: rows b0 + wn * 64 + ni * 16 + lq * 4 + i
+    // scores, and which of them can enter a list (<=: a tie may still win on the index); the fragment's bank biases
+    // and scales
     float t[MI];
 #pragma unroll
-    for (int mi = 0; mi < MI; ++mi) t[mi] = thr[wm * 64 + mi * 16 + lrow];
+    for (int mi = 0; mi < MI; ++mi) t[mi] = thr[p.qrow(mi)];
     unsigned long long mask = 0;
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
       float nb[4], sb[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int b = b0 + wn * 64 + ni * 16 + lq * 4 + i;
+        const int b = p.gb(b0, ni, i);
         const float2 h = b < N ? *reinterpret_cast<const float2*>(bimg + (size_t)b * rec)
                                : make_float2(__builtin_inff(), 0.f);
         nb[i] = h.x;
@@ -512,16 +332,16 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
       long long bg[4];   // GM & GM_EXCLUDE: the fragment's bank groups
       if constexpr ((GM & GM_EXCLUDE) != 0) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) bg[i] = tg[wn * 64 + ni * 16 + lq * 4 + i];
+        for (int i = 0; i < 4; ++i) bg[i] = tg[p.wn * 64 + ni * 16 + p.lq * 4 + i];   // (p.brow(ni, i), spelt out)
       }
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const int gb = b0 + wn * 64 + ni * 16 + lq * 4 + i;
-          const float s = fmaf(-(acc[ni][mi][i] * sq[mi]), sb[i], nb[i]);
+          const int gb = p.gb(b0, ni, i);
+          const float s = tile_score(acc[ni][mi][i], sq[mi], sb[i], nb[i]);
           acc[ni][mi][i] = s;
-          bool in = s <= t[mi] && s < __builtin_inff() && gb < b_end && gb != selfb[mi];
+          bool in = s <= t[mi] && s < __builtin_inff() && gb < sr.b_end && gb != selfb[mi];
           if constexpr ((GM & GM_EXCLUDE) != 0) in = in && bg[i] != qg[mi];
           if (in) mask |= 1ull << ((ni * MI + mi) * 4 + i);
         }
@@ -533,7 +353,7 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
       if (mask != 0) {
         if (rc > 0) {
 #pragma unroll
-          for (int mi = 0; mi < MI; ++mi) t[mi] = thr[wm * 64 + mi * 16 + lrow];
+          for (int mi = 0; mi < MI; ++mi) t[mi] = thr[p.qrow(mi)];
         }
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
@@ -543,13 +363,13 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
             for (int i = 0; i < 4; ++i) {
               const unsigned long long bit = 1ull << ((ni * MI + mi) * 4 + i);
               if ((mask & bit) != 0) {
-                const int row = wm * 64 + mi * 16 + lrow;
+                const int row = p.qrow(mi);
                 if (!(acc[ni][mi][i] <= t[mi])) {
                   mask &= ~bit;
                 } else {
                   const int slot = atomicAdd(&bcnt[row], 1);
                   if (slot < BCAP) {
-                    bucket[row * BCAP + slot] = Cand{acc[ni][mi][i], wn * 64 + ni * 16 + lq * 4 + i};
+                    bucket[row * BCAP + slot] = Cand{acc[ni][mi][i], p.brow(ni, i)};
                     mask &= ~bit;
                   }
                 }
@@ -576,55 +396,9 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
   }
 
   if (owner) {
-    Cand* o = cand + ((q0 + tid) * splits + split) * k;
+    Cand* o = cand + ((q0 + tid) * splits + sr.split) * k;
     for (int j = 0; j < k; ++j) o[j] = L[tid * k + j];
   }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The distance the library returns, in the direct form from the fp32 rows, by one wave: xv = the query row (element
-// j * 64 + lane in xv[j], zero past dim), qq = its squared norm (wave_sum of the lanes' fma chains), y = the bank row.
-// Lane-strided fma chains, the fixed butterfly, a correctly rounded sqrtf.  The merge applies it to the rows it returns
-// and the radius search decides membership by it: one function, so the two agree bit for bit.
-__device__ __forceinline__ float direct_distance(const float (&xv)[MAX_DIM / 64], float qq, const float* __restrict__ y,
-                                                 int dim, int metric, int lane) {
-  float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-  for (int jj = 0; jj < MAX_DIM / 64; ++jj) {
-    const int d = jj * 64 + lane;
-    if (d < dim) {
-      const float yv = y[d];
-      if (metric == 0) {
-        const float t = xv[jj] - yv;
-        a0 = fmaf(t, t, a0);
-      } else {
-        a0 = fmaf(xv[jj], yv, a0);
-        a1 = fmaf(yv, yv, a1);
-      }
-    }
-  }
-  a0 = wave_sum(a0);
-  if (metric == 0) return sqrtf(a0);
-  a1 = wave_sum(a1);
-  const float c = qq > 0.f && a1 > 0.f ? (a0 / sqrtf(qq)) / sqrtf(a1) : 0.f;
-  return 1.f - c;
-}
-
-// the query row of a wave as direct_distance takes it; false for a row that holds a non-finite value or whose squared
-// norm is not finite (the selection saw a zero image for it)
-__device__ __forceinline__ bool load_query_row(const float* __restrict__ x, int dim, int lane, float (&xv)[MAX_DIM / 64],
-                                               float& qq) {
-  bool fin = true;
-  qq = 0.f;
-#pragma unroll
-  for (int j = 0; j < MAX_DIM / 64; ++j) {
-    const int d = j * 64 + lane;
-    xv[j] = d < dim ? x[d] : 0.f;
-    fin = fin && fabsf(xv[j]) <= FLT_MAX;
-    qq = fmaf(xv[j], xv[j], qq);
-  }
-  qq = wave_sum(qq);
-  return __all(fin) && qq <= FLT_MAX;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -721,479 +495,30 @@ __global__ __launch_bounds__(64) void knn_merge_kernel(const float* __restrict__
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// radius search (btsbot_knn_radius_*): the selection's grid and tile walk with a second epilogue,
-// "admit if within r" in place of "keep the best k".  A pair is a CANDIDATE when its GEMM-form value
-//   Euclidean  g = score + |q|^2            <= lim = r^2 * rel + ctau * (|q|^2 + |b|^2)
-//   cosine     g = 1 + score / (2 |q|)      <= lim = r + ctau
-// (rel = 1 + 4 (D + 4) u, ctau = 8 (D + 8) u; cosine ctau = 16 (D + 8) u: the margin of 4p, which covers the error
-// bounds of this form and of the direct form) -- a superset of the members, decided by the same expression in both
-// instantiations.  FILL = false counts a (query, split)'s candidates; FILL = true writes their bank rows into the region
-// the scan of the counts gave it, slots handed out by an LDS cursor per query row (the order inside a region is no
-// one's business: the lists are sorted afterwards), each slot checked against the region's size.  No list of fixed
-// size, nothing of size Q x N.  knn_radius_verify_kernel then applies direct_distance to every candidate.
-template <bool FILL, bool EXCL>
-__global__ __launch_bounds__(256, 2) void knn_radius_kernel(const unsigned char* __restrict__ qimg,
-                                                            const unsigned char* __restrict__ bimg, long Q, int N,
-                                                            int dim, int metric, const float* __restrict__ radius,
-                                                            float rel, float ctau, long self_offset,
-                                                            int tiles_per_split, int splits,
-                                                            const long long* __restrict__ qgrp,
-                                                            const long long* __restrict__ bgrp, int* counts,
-                                                            const long long* __restrict__ offsets,
-                                                            int* __restrict__ cand, long long n_cand,
-                                                            int* __restrict__ err) {
-  constexpr int MI = TileWalk::MI, NI = TileWalk::NI;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  int* rowcnt = reinterpret_cast<int*>(smem + GEMM_LDS);          // [TQ] candidates so far (FILL: the row's cursor)
-  int* rowcap = rowcnt + TQ;                                      // [TQ] FILL: the size of the row's region
-  long long* rowbase = reinterpret_cast<long long*>(rowcap + TQ); // [TQ] FILL: where it starts in cand
-  long long* tg = reinterpret_cast<long long*>(smem);             // EXCL: [TB] the tile's bank groups (idle operand LDS)
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int lrow = lane & 15, lq = lane >> 4;
-  const size_t rec = record_bytes(dim);
-  const long q0 = (long)blockIdx.x * TQ;
-  const int split = blockIdx.y;
-  const int total_tiles = (N + TB - 1) / TB;
-  const int t_begin = (int)min((long)split * tiles_per_split, (long)total_tiles);
-  const int t_end = (int)min((long)(split + 1) * tiles_per_split, (long)total_tiles);
-  const int b_end = (int)min((long)t_end * TB, (long)N);
-
-  if (tid < TQ) {
-    rowcnt[tid] = 0;
-    if constexpr (FILL) {
-      const bool in = q0 + tid < Q;
-      rowcap[tid] = in ? counts[(q0 + tid) * splits + split] : 0;
-      rowbase[tid] = in ? offsets[(q0 + tid) * splits + split] : 0;
-    }
-  }
-
-  float sq[MI], qq[MI], qinv[MI], lim[MI];   // the query record's scale, |q|^2, 1 / (2 |q|); r^2 * rel (cosine: r + ctau)
-  int selfb[MI];                             // the bank row that IS the query row (never a candidate), -1: none
-  long long qg[MI];                          // EXCL: the groups of the lane's four query rows
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi) {
-    const long gq = q0 + wm * 64 + mi * 16 + lrow;
-    const float4 h = gq < Q ? *reinterpret_cast<const float4*>(qimg + gq * rec) : make_float4(0.f, 0.f, 0.f, 0.f);
-    sq[mi] = h.y;
-    qq[mi] = h.z;
-    qinv[mi] = h.w;
-    const float r = gq < Q ? radius[gq] : -1.f;
-    // a row past Q, a non-finite query row (scale 0) and a negative or NaN radius admit nothing
-    lim[mi] = h.y != 0.f && r >= 0.f ? (metric == 0 ? (r * r) * rel : r + ctau) : -__builtin_inff();
-    const long sb = gq + self_offset;
-    selfb[mi] = self_offset >= 0 && sb < N ? (int)sb : -1;
-    if constexpr (EXCL) qg[mi] = gq < Q ? qgrp[gq] : 0;
-  }
-
-  int n[MI] = {0, 0, 0, 0};
-  bool past = false;
-  TileWalk w;
-  w.init(qimg, bimg, smem, Q, q0, N, dim);
-  if (t_begin < t_end) w.gload(t_begin, 0);
-  __syncthreads();   // the rows' counters and regions
-  for (int tile = t_begin; tile < t_end; ++tile) {
-    const int b0 = tile * TB;
-    long long gt = 0;   // EXCL: bank row b0 + tid's group, in flight under the products
-    if constexpr (EXCL) {
-      if (tid < TB && (long)b0 + tid < N) gt = bgrp[(long)b0 + tid];
-    }
-    f32x4 acc[NI][MI];
-    w.products(acc, tile, t_end);
-    if constexpr (EXCL) {
-      if (tid < TB) tg[tid] = gt;
-      lds_barrier();
-    }
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni) {
-      float nb[4], sb[4];   // the fragment's bank biases and scales: rows b0 + wn * 64 + ni * 16 + lq * 4 + i
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int b = b0 + wn * 64 + ni * 16 + lq * 4 + i;
-        const float2 h = b < N ? *reinterpret_cast<const float2*>(bimg + (size_t)b * rec)
-                               : make_float2(__builtin_inff(), 0.f);
-        nb[i] = h.x;
-        sb[i] = h.y;
-      }
-      long long bg[4];
-      if constexpr (EXCL) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) bg[i] = tg[wn * 64 + ni * 16 + lq * 4 + i];
-      }
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int gb = b0 + wn * 64 + ni * 16 + lq * 4 + i;
-          const float s = fmaf(-(acc[ni][mi][i] * sq[mi]), sb[i], nb[i]);
-          float g, l;
-          if (metric == 0) {
-            g = s + qq[mi];
-            l = fmaf(ctau, qq[mi] + nb[i], lim[mi]);
-          } else {
-            g = fmaf(s, qinv[mi], 1.f);
-            l = lim[mi];
-          }
-          bool in = g <= l && s < __builtin_inff() && gb < b_end && gb != selfb[mi];
-          if constexpr (EXCL) in = in && bg[i] != qg[mi];
-          if (in) {
-            if constexpr (FILL) {
-              const int row = wm * 64 + mi * 16 + lrow;
-              const int slot = atomicAdd(&rowcnt[row], 1);
-              const long long at = rowbase[row] + slot;
-              if (slot < rowcap[row] && at >= 0 && at < n_cand) cand[at] = gb;
-              else past = true;   // (never, while counts / offsets are the count pass's: the same arithmetic)
-            } else {
-              ++n[mi];
-            }
-          }
-        }
-    }
-    if constexpr (EXCL) lds_barrier();   // the groups are read: the next tile's operands may land there
-  }
-
-  if constexpr (FILL) {
-    if (past) *err = 1;
-  } else {
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-      if (n[mi] != 0) atomicAdd(&rowcnt[wm * 64 + mi * 16 + lrow], n[mi]);
-    __syncthreads();
-    if (tid < TQ && q0 + tid < Q) counts[(q0 + tid) * splits + split] = rowcnt[tid];
-  }
+int auto_splits(int64_t n_query, int64_t n_bank) {
+  // (no sum that could overflow: the callers' shape checks may still be ahead)
+  const int64_t qt = n_query / TQ + (n_query % TQ != 0), bt = n_bank / TB + (n_bank % TB != 0);
+  if (qt < 1 || bt < 1) return 1;
+  // two workgroups per CU (256 CUs) where the bank has the tiles for it
+  int64_t s = (512 + qt - 1) / qt;
+  s = s > bt ? bt : s;
+  s = s > MAX_SPLITS ? MAX_SPLITS : s;
+  return (int)(s < 1 ? 1 : s);
 }
 
-// one wave per candidate in turn: grid (query, Y), wave y takes the query's candidates y, y + Y, ...
-__global__ __launch_bounds__(64) void knn_radius_verify_kernel(const float* __restrict__ queries,
-                                                               const float* __restrict__ bank,
-                                                               const float* __restrict__ radius,
-                                                               const long long* __restrict__ offsets, int splits,
-                                                               const int* __restrict__ cand, int N, int dim, int metric,
-                                                               float* __restrict__ dist,
-                                                               unsigned char* __restrict__ keep) {
-  const int lane = threadIdx.x;
-  const long q = blockIdx.x;
-  const long long c1 = offsets[(q + 1) * splits];
-  long long c = offsets[q * splits] + blockIdx.y;
-  if (c >= c1) return;
-  float xv[MAX_DIM / 64];
-  float qq;
-  const bool ok = load_query_row(queries + q * dim, dim, lane, xv, qq);   // (a row that is not has no candidates)
-  const float r = radius[q];
-  for (; c < c1; c += gridDim.y) {
-    const int b = cand[c];
-    const bool have = b >= 0 && b < N;   // (a slot the fill did not reach: it raised the error flag)
-    const float d = have ? direct_distance(xv, qq, bank + (long)b * dim, dim, metric, lane) : __builtin_nanf("");
-    if (lane == 0) {
-      dist[c] = d;
-      keep[c] = ok && have && d <= r ? 1 : 0;
-    }
-  }
+// what the query keeps behind the packed query rows: k candidates per (query, split) and, with one entry per group, the
+// groups of the list entries, [query tiles][splits][k][TQ] int64
+size_t query_extra_bytes(int64_t n_query, int k, int splits, int flags) {
+  const size_t cands = (size_t)n_query * splits * k * sizeof(Cand);
+  if ((flags & GM_ONE) == 0) return cands;
+  return cands + ((size_t)n_query + TQ - 1) / TQ * TQ * splits * k * sizeof(long long);
 }
+
+}  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
-// neighbour ranks (btsbot_knn_rank_*): rank[q][c] = the number of eligible bank rows b with
-// (direct_distance(q, b), b) before (dist[q][c], targets[q][c]).  The margin of 4p read from both sides: with
-// r = dist[q][c] a pair's GEMM-form value g decides
-//   g <  lo_c = r^2 * relm - ctau * (|q|^2 + |b|^2)   (cosine: r - ctau)    surely before: the direct form is < r, strictly
-//   g <= hi_c = r^2 * rel  + ctau * (|q|^2 + |b|^2)   (cosine: r + ctau)    the band: the direct form decides
-// and nothing otherwise (relm = 1 - 4 (D + 4) u; rel and ctau are the radius search's).  The thresholds kernel leaves
-// thr[q][c] = (r^2 * relm, r^2 * rel) (cosine: (r - ctau, r + ctau)) and rowlim[q] = the largest second component.
-//
-// thresholds: one wave per query row, its targets in turn.  dist[q][c] by direct_distance; rank[q][c] = 0, or -1 where
-// the target is out of range, not eligible for q, or q is not finite: such a column has thr = (-inf, -inf) and takes no
-// part in rowlim, so the tile pass adds nothing to it.
-__global__ __launch_bounds__(64) void knn_rank_thresh_kernel(const float* __restrict__ queries,
-                                                             const float* __restrict__ bank,
-                                                             const unsigned char* __restrict__ bimg, long N, int dim,
-                                                             int metric, const long long* __restrict__ targets, int t,
-                                                             long self_offset, const long long* __restrict__ qgrp,
-                                                             const long long* __restrict__ bgrp, float rel, float relm,
-                                                             float ctau, float* __restrict__ dist, int* __restrict__ rank,
-                                                             float2* __restrict__ thr, float* __restrict__ rowlim) {
-  const int lane = threadIdx.x;
-  const long q = blockIdx.x;
-  float xv[MAX_DIM / 64];
-  float qq;
-  const bool qok = load_query_row(queries + q * dim, dim, lane, xv, qq);
-  const size_t rec = record_bytes(dim);
-  const float ninf = -__builtin_inff();
-  float widest = ninf;
-  for (int c = 0; c < t; ++c) {
-    const long long b = targets[q * t + c];
-    const bool in = b >= 0 && b < N;
-    // (a bank row is finite exactly when its record's bias is: what the tile pass sees as score < inf)
-    const bool fin = in && qok && reinterpret_cast<const float*>(bimg + (size_t)b * rec)[0] < __builtin_inff();
-    const float d = fin ? direct_distance(xv, qq, bank + b * dim, dim, metric, lane) : __builtin_nanf("");
-    bool el = fin && !(self_offset >= 0 && b == q + self_offset);
-    if (el && qgrp != nullptr) el = bgrp[b] != qgrp[q];
-    float lo = ninf, hi = ninf;
-    if (el) {
-      if (metric == 0) {
-        hi = (d * d) * rel;
-        lo = (d * d) * relm;
-      } else {
-        hi = d + ctau;
-        lo = d - ctau;
-      }
-      if (!(fabsf(d) <= FLT_MAX)) lo = ninf;   // (an overflowed distance ties with its like: all of it is band)
-      widest = fmaxf(widest, hi);
-    }
-    if (lane == 0) {
-      dist[q * t + c] = d;
-      rank[q * t + c] = el ? 0 : -1;
-      thr[q * t + c] = make_float2(lo, hi);
-    }
-  }
-  if (lane == 0) rowlim[q] = widest;
-}
-
-// The tile pass: knn_radius_kernel's walk and pre-filter (one compare of g with the row's widest limit; most of the
-// bank ends there), then, for a score that passes, the row's t thresholds from L2.  FILL = false adds the surely-before
-// pairs to sure[row][c] in LDS (one global integer atomic per workgroup, row and column at the end) and counts the
-// (query, split)'s band pairs -- a pair is ONE band entry however many columns it is in the band of; FILL = true writes
-// the band pairs as (bank row, 64-bit mask of these columns) into the region the scan of the counts gave them, every
-// slot checked as in the radius fill.  Only integer additions meet across workgroups.
-// The scores that pass are few per lane but, in a crowded region, some lane of a wave passes at most of the 64 unrolled
-// sites, and a t-step loop run there for the whole wave costs several times the products (measured).  So a
-// site only QUEUES its score -- (row, bank row of the tile, g, the margin's scale) in the idle operand LDS -- and after
-// the tile all 256 threads share the queue's (score, column) compares, one each, then its entries.  What finds no room
-// in the queue is compared on the spot, by the same expressions.
-struct RankEnt {
-  int rowgb;          // query row of the tile * TB + bank row of the tile
-  float g, x;         // the GEMM-form value, |q|^2 + |b|^2 (cosine: 0)
-  unsigned mlo, mhi;  // the band mask, met by LDS atomic ORs
-};
-constexpr int RANK_QCAP = 2048;      // queue entries: 40 KB of the 64 KB operand planes, behind the tile's bank groups
-constexpr int RANK_QOFF = 2048;
-
-template <bool FILL, bool EXCL>
-__global__ __launch_bounds__(256, 2) void knn_rank_kernel(const unsigned char* __restrict__ qimg,
-                                                          const unsigned char* __restrict__ bimg, long Q, int N, int dim,
-                                                          int metric, int t, const float2* __restrict__ thr,
-                                                          const float* __restrict__ rowlim, float ctau, long self_offset,
-                                                          int tiles_per_split, int splits,
-                                                          const long long* __restrict__ qgrp,
-                                                          const long long* __restrict__ bgrp, int* __restrict__ rank,
-                                                          int* counts, const long long* __restrict__ offsets,
-                                                          int* __restrict__ cand, unsigned long long* __restrict__ cmask,
-                                                          long long n_band, int* __restrict__ err) {
-  constexpr int MI = TileWalk::MI, NI = TileWalk::NI;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  int* rowcnt = reinterpret_cast<int*>(smem + GEMM_LDS);          // [TQ] band pairs so far (FILL: the row's cursor)
-  int* rowcap = rowcnt + TQ;                                      // [TQ] FILL: the size of the row's region
-  long long* rowbase = reinterpret_cast<long long*>(rowcap + TQ); // [TQ] FILL: where it starts in cand / cmask
-  int* qn = reinterpret_cast<int*>(rowbase + TQ);                 // the queue's fill count (16 bytes kept for it)
-  int* sure = qn + 4;                                             // [TQ][t] count pass: the surely-before pairs
-  long long* tg = reinterpret_cast<long long*>(smem);             // EXCL: [TB] the tile's bank groups (idle operand LDS)
-  RankEnt* ent = reinterpret_cast<RankEnt*>(smem + RANK_QOFF);    // [RANK_QCAP] the tile's queue (idle operand LDS)
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int lrow = lane & 15, lq = lane >> 4;
-  const size_t rec = record_bytes(dim);
-  const long q0 = (long)blockIdx.x * TQ;
-  const int split = blockIdx.y;
-  const int total_tiles = (N + TB - 1) / TB;
-  const int t_begin = (int)min((long)split * tiles_per_split, (long)total_tiles);
-  const int t_end = (int)min((long)(split + 1) * tiles_per_split, (long)total_tiles);
-  const int b_end = (int)min((long)t_end * TB, (long)N);
-
-  if (tid < TQ) {
-    rowcnt[tid] = 0;
-    if constexpr (FILL) {
-      const bool in = q0 + tid < Q;
-      rowcap[tid] = in ? counts[(q0 + tid) * splits + split] : 0;
-      rowbase[tid] = in ? offsets[(q0 + tid) * splits + split] : 0;
-    }
-  }
-  if (tid == 0) *qn = 0;
-  if constexpr (!FILL)
-    for (int i = tid; i < TQ * t; i += 256) sure[i] = 0;
-
-  float sq[MI], qq[MI], qinv[MI], lim[MI];   // the query record's scale, |q|^2, 1 / (2 |q|); the row's widest limit
-  int selfb[MI];                             // the bank row that IS the query row (never counted), -1: none
-  long long qg[MI];                          // EXCL: the groups of the lane's four query rows
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi) {
-    const long gq = q0 + wm * 64 + mi * 16 + lrow;
-    const float4 h = gq < Q ? *reinterpret_cast<const float4*>(qimg + gq * rec) : make_float4(0.f, 0.f, 0.f, 0.f);
-    sq[mi] = h.y;
-    qq[mi] = h.z;
-    qinv[mi] = h.w;
-    // a row past Q, a non-finite query row and a row without a valid target pass nothing
-    lim[mi] = gq < Q && h.y != 0.f ? rowlim[gq] : -__builtin_inff();
-    const long sb = gq + self_offset;
-    selfb[mi] = self_offset >= 0 && sb < N ? (int)sb : -1;
-    if constexpr (EXCL) qg[mi] = gq < Q ? qgrp[gq] : 0;
-  }
-
-  int n[MI] = {0, 0, 0, 0};
-  bool past = false;
-  TileWalk w;
-  w.init(qimg, bimg, smem, Q, q0, N, dim);
-  if (t_begin < t_end) w.gload(t_begin, 0);
-  __syncthreads();   // the rows' counters and regions
-  for (int tile = t_begin; tile < t_end; ++tile) {
-    const int b0 = tile * TB;
-    long long gt = 0;   // EXCL: bank row b0 + tid's group, in flight under the products
-    if constexpr (EXCL) {
-      if (tid < TB && (long)b0 + tid < N) gt = bgrp[(long)b0 + tid];
-    }
-    f32x4 acc[NI][MI];
-    w.products(acc, tile, t_end);
-    if constexpr (EXCL) {
-      if (tid < TB) tg[tid] = gt;
-      lds_barrier();
-    }
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni) {
-      float nb[4], sb[4];   // the fragment's bank biases and scales: rows b0 + wn * 64 + ni * 16 + lq * 4 + i
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int b = b0 + wn * 64 + ni * 16 + lq * 4 + i;
-        const float2 h = b < N ? *reinterpret_cast<const float2*>(bimg + (size_t)b * rec)
-                               : make_float2(__builtin_inff(), 0.f);
-        nb[i] = h.x;
-        sb[i] = h.y;
-      }
-      long long bg[4];
-      if constexpr (EXCL) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) bg[i] = tg[wn * 64 + ni * 16 + lq * 4 + i];
-      }
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int gb = b0 + wn * 64 + ni * 16 + lq * 4 + i;
-          const float s = fmaf(-(acc[ni][mi][i] * sq[mi]), sb[i], nb[i]);
-          float g, x;   // x: what the margin's tau part scales with (cosine: its tau is in the thresholds)
-          if (metric == 0) {
-            g = s + qq[mi];
-            x = qq[mi] + nb[i];
-          } else {
-            g = fmaf(s, qinv[mi], 1.f);
-            x = 0.f;
-          }
-          const float l = fmaf(ctau, x, lim[mi]);
-          bool in = g <= l && s < __builtin_inff() && gb < b_end && gb != selfb[mi];
-          if constexpr (EXCL) in = in && bg[i] != qg[mi];
-          if (in) {
-            const int row = wm * 64 + mi * 16 + lrow;
-            const int slot = atomicAdd(qn, 1);
-            if (slot < RANK_QCAP) {
-              ent[slot] = RankEnt{row * TB + (gb - b0), g, x, 0u, 0u};
-              continue;
-            }
-            const float2* th = thr + (q0 + row) * t;
-            unsigned long long band = 0;
-#pragma unroll 1
-            for (int c = 0; c < t; ++c) {
-              const float2 lh = th[c];
-              if (g < fmaf(-ctau, x, lh.x)) {
-                if constexpr (!FILL) atomicAdd(&sure[row * t + c], 1);
-              } else if (g <= fmaf(ctau, x, lh.y)) {
-                band |= 1ull << c;
-              }
-            }
-            if (band != 0) {
-              if constexpr (FILL) {
-                const int slot = atomicAdd(&rowcnt[row], 1);
-                const long long at = rowbase[row] + slot;
-                if (slot < rowcap[row] && at >= 0 && at < n_band) {
-                  cand[at] = gb;
-                  cmask[at] = band;
-                } else {
-                  past = true;   // (never, while counts / offsets are the count pass's: the same arithmetic)
-                }
-              } else {
-                ++n[mi];
-              }
-            }
-          }
-        }
-    }
-    lds_barrier();   // the queue is complete (and the groups are read)
-    const int nq = min(*qn, RANK_QCAP);
-    for (int w = tid; w < nq * t; w += 256) {   // one (score, column) compare per thread and step
-      const int e = w / t, c = w - e * t;
-      const int row = ent[e].rowgb / TB;
-      const float g = ent[e].g, x = ent[e].x;
-      const float2 lh = thr[(q0 + row) * t + c];
-      if (g < fmaf(-ctau, x, lh.x)) {
-        if constexpr (!FILL) atomicAdd(&sure[row * t + c], 1);
-      } else if (g <= fmaf(ctau, x, lh.y)) {
-        atomicOr(c < 32 ? &ent[e].mlo : &ent[e].mhi, 1u << (c & 31));
-      }
-    }
-    lds_barrier();   // the masks are complete
-    for (int e = tid; e < nq; e += 256) {
-      const unsigned long long band = (unsigned long long)ent[e].mhi << 32 | ent[e].mlo;
-      if (band == 0) continue;
-      const int row = ent[e].rowgb / TB;
-      const int slot = atomicAdd(&rowcnt[row], 1);
-      if constexpr (FILL) {
-        const long long at = rowbase[row] + slot;
-        if (slot < rowcap[row] && at >= 0 && at < n_band) {
-          cand[at] = b0 + ent[e].rowgb % TB;
-          cmask[at] = band;
-        } else {
-          past = true;
-        }
-      }
-    }
-    lds_barrier();   // the queue is read: the next tile's operands may land there
-    if (tid == 0) *qn = 0;   // (the next tile's first push is behind the barriers of its products)
-  }
-
-  if constexpr (FILL) {
-    if (past) *err = 1;
-  } else {
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-      if (n[mi] != 0) atomicAdd(&rowcnt[wm * 64 + mi * 16 + lrow], n[mi]);
-    __syncthreads();
-    if (tid < TQ && q0 + tid < Q) counts[(q0 + tid) * splits + split] = rowcnt[tid];
-    for (int i = tid; i < TQ * t; i += 256) {
-      const int v = sure[i];
-      if (v != 0) atomicAdd(&rank[q0 * t + i], v);   // (row q0 + i / t, column i % t; a row past Q has none)
-    }
-  }
-}
-
-// one wave per band entry in turn (the radius verify's grid): the pair's direct-form distance once, then lane c adds
-// before((d, b), (dist[q][c], targets[q][c])) to rank[q][c] for the columns of the entry's mask
-__global__ __launch_bounds__(64) void knn_rank_verify_kernel(const float* __restrict__ queries,
-                                                             const float* __restrict__ bank,
-                                                             const long long* __restrict__ targets, int t,
-                                                             const float* __restrict__ dist,
-                                                             const long long* __restrict__ offsets, int splits,
-                                                             const int* __restrict__ cand,
-                                                             const unsigned long long* __restrict__ cmask, int N,
-                                                             int dim, int metric, int* __restrict__ rank) {
-  const int lane = threadIdx.x;
-  const long q = blockIdx.x;
-  const long long c1 = offsets[(q + 1) * splits];
-  long long c = offsets[q * splits] + blockIdx.y;
-  if (c >= c1) return;
-  float xv[MAX_DIM / 64];
-  float qq;
-  (void)load_query_row(queries + q * dim, dim, lane, xv, qq);   // (a row that is not finite has no band entries)
-  const bool col = lane < t;
-  const float dc = col ? dist[q * t + lane] : 0.f;
-  const long long tc = col ? targets[q * t + lane] : 0;
-  int add = 0;
-  for (; c < c1; c += gridDim.y) {
-    const int b = cand[c];
-    if (b < 0 || b >= N) continue;   // (a slot the fill did not reach: it raised the error flag)
-    const float d = direct_distance(xv, qq, bank + (long)b * dim, dim, metric, lane);
-    if (col && (cmask[c] >> lane & 1ull) != 0 && before(d, b, dc, (int)tc)) ++add;
-  }
-  if (add != 0) atomicAdd(&rank[q * t + lane], add);
-}
+// the host helpers every search kind shares (knn_tile.h)
+namespace knn {
 
 int check_shape(const char* who, int64_t n_query, int64_t n_bank, int dim, int k) {
   if (dim < 1 || dim > MAX_DIM || k < 1 || k > MAX_K || n_query < 0 || n_bank < 0 || n_bank > 0x7fffffffLL ||
@@ -1205,28 +530,86 @@ int check_shape(const char* who, int64_t n_query, int64_t n_bank, int dim, int k
   return BTSBOT_OK;
 }
 
-int auto_splits(int64_t n_query, int64_t n_bank) {
-  const int64_t qt = (n_query + TQ - 1) / TQ, bt = (n_bank + TB - 1) / TB;
-  if (qt < 1 || bt < 1) return 1;
-  // two workgroups per CU (256 CUs) where the bank has the tiles for it
-  int64_t s = (512 + qt - 1) / qt;
-  s = s > bt ? bt : s;
-  s = s > MAX_SPLITS ? MAX_SPLITS : s;
-  return (int)(s < 1 ? 1 : s);
-}
-
 size_t image_bytes(int64_t rows, int dim) { return ((size_t)rows * record_bytes(dim) + 255) & ~(size_t)255; }
 
-}  // namespace
+int check_search(const char* who, const SearchArgs& a) {
+  TRY(check_shape(who, a.n_query, a.n_bank, a.dim, a.k));
+  if (a.metric != BTSBOT_KNN_EUCLIDEAN && a.metric != BTSBOT_KNN_COSINE) {
+    btsbot_set_error("%s: metric %d", who, a.metric);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (a.splits < a.min_splits || a.splits > MAX_SPLITS) {
+    if (a.min_splits == 0) btsbot_set_error("%s: splits=%d must be 0 (the library's choice) .. %d", who, a.splits, MAX_SPLITS);
+    else btsbot_set_error("%s: splits=%d must be 1 .. %d", who, a.splits, MAX_SPLITS);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if ((a.flags & ~a.flag_mask) != 0) {
+    if (a.mode_word == nullptr)
+      btsbot_set_error("%s: flags=%d holds bits other than BTSBOT_KNN_EXCLUDE_SAME | BTSBOT_KNN_ONE_PER_GROUP", who, a.flags);
+    else
+      btsbot_set_error("%s: flags=%d, only 0 and BTSBOT_KNN_EXCLUDE_SAME are %s modes", who, a.flags, a.mode_word);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if ((a.flags & GM_ONE) != 0 && a.k > MAX_K_ONE) {
+    btsbot_set_error("%s: k=%d, but BTSBOT_KNN_ONE_PER_GROUP holds k <= %d (the merge keeps its pool's groups on chip)", who,
+                     a.k, MAX_K_ONE);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (a.n_query == 0) return BTSBOT_OK;
+  if (a.null_arg) {
+    btsbot_set_error("%s: NULL argument", who);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (((a.flags & GM_EXCLUDE) != 0 && a.query_group == nullptr) ||
+      (a.flags != 0 && a.n_bank > 0 && a.bank_group == nullptr)) {
+    if (a.mode_word == nullptr)
+      btsbot_set_error("%s: flags=%d need bank_group (and BTSBOT_KNN_EXCLUDE_SAME query_group), got NULL", who, a.flags);
+    else
+      btsbot_set_error("%s: BTSBOT_KNN_EXCLUDE_SAME needs query_group and bank_group, got NULL", who);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  const int64_t need = (int64_t)(image_bytes(a.n_query, a.dim) + a.extra_bytes);
+  if (a.workspace_bytes < need || ((uintptr_t)a.workspace & 15) != 0 || ((uintptr_t)a.packed & 15) != 0) {
+    btsbot_set_error("%s: workspace of %lld bytes (need %lld), or workspace / packed not 16-byte aligned", who,
+                     (long long)a.workspace_bytes, (long long)need);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  return BTSBOT_OK;
+}
+
+Margin margin(int dim, int metric) {
+  const float u = 5.9604644775390625e-8f;
+  return Margin{1.f + 4.f * (float)(dim + 4) * u, 1.f - 4.f * (float)(dim + 4) * u,
+                (metric == BTSBOT_KNN_COSINE ? 16.f : 8.f) * (float)(dim + 8) * u};
+}
+
+TileGrid tile_grid(int64_t n_query, int64_t n_bank, int splits) {
+  const int total_tiles = (int)((n_bank + TB - 1) / TB);
+  return TileGrid{(total_tiles + splits - 1) / splits, dim3((unsigned)((n_query + TQ - 1) / TQ), (unsigned)splits)};
+}
+
+unsigned verify_waves(int64_t n, int64_t n_query) {
+  const int64_t per = (n + n_query - 1) / n_query;
+  return (unsigned)(per <= 32 ? 1 : per >= 32 * 64 ? 64 : (per + 31) / 32);
+}
+
+int pack_queries(const float* queries, int64_t n_query, int dim, unsigned char* qimg, hipStream_t st) {
+  hipLaunchKernelGGL(knn_pack_kernel, dim3((unsigned)((n_query + 3) / 4)), dim3(256), 0, st, queries, (long)n_query, dim,
+                     (int)MODE_QUERY, qimg);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+}  // namespace knn
 
 extern "C" int64_t btsbot_knn_bank_bytes(int64_t n_bank, int dim) {
-  if (check_shape("btsbot_knn_bank_bytes", 0, n_bank, dim, 1) != BTSBOT_OK) return BTSBOT_ERR_INVALID_ARG;
+  if (knn::check_shape("btsbot_knn_bank_bytes", 0, n_bank, dim, 1) != BTSBOT_OK) return BTSBOT_ERR_INVALID_ARG;
   return (int64_t)((size_t)n_bank * record_bytes(dim));
 }
 
 extern "C" int btsbot_knn_pack_bank(const float* rows, int64_t first_row, int64_t n_rows, int dim, int metric,
                                     void* packed, int64_t n_bank_capacity, void* stream) {
-  const int s = check_shape("btsbot_knn_pack_bank", 0, n_bank_capacity, dim, 1);
+  const int s = knn::check_shape("btsbot_knn_pack_bank", 0, n_bank_capacity, dim, 1);
   if (s != BTSBOT_OK) return s;
   if (metric != BTSBOT_KNN_EUCLIDEAN && metric != BTSBOT_KNN_COSINE) {
     btsbot_set_error("btsbot_knn_pack_bank: metric %d", metric);
@@ -1250,27 +633,23 @@ extern "C" int btsbot_knn_pack_bank(const float* rows, int64_t first_row, int64_
 }
 
 extern "C" int btsbot_knn_splits(int64_t n_query, int64_t n_bank, int dim, int k) {
-  const int s = check_shape("btsbot_knn_splits", n_query, n_bank, dim, k);
+  const int s = knn::check_shape("btsbot_knn_splits", n_query, n_bank, dim, k);
   if (s != BTSBOT_OK) return s;
   return auto_splits(n_query, n_bank);
 }
 
-extern "C" int64_t btsbot_knn_workspace(int64_t n_query, int64_t n_bank, int dim, int k, int splits) {
-  if (check_shape("btsbot_knn_workspace", n_query, n_bank, dim, k) != BTSBOT_OK) return BTSBOT_ERR_INVALID_ARG;
+extern "C" int64_t btsbot_knn_workspace_grouped(int64_t n_query, int64_t n_bank, int dim, int k, int splits, int flags) {
+  if (knn::check_shape("btsbot_knn_workspace", n_query, n_bank, dim, k) != BTSBOT_OK) return BTSBOT_ERR_INVALID_ARG;
   if (splits < 0 || splits > MAX_SPLITS) {
     btsbot_set_error("btsbot_knn_workspace: splits=%d must be 0 (the library's choice) .. %d", splits, MAX_SPLITS);
     return BTSBOT_ERR_INVALID_ARG;
   }
   if (splits == 0) splits = auto_splits(n_query, n_bank);
-  return (int64_t)(image_bytes(n_query, dim) + (size_t)n_query * splits * k * sizeof(Cand));
+  return (int64_t)(knn::image_bytes(n_query, dim) + query_extra_bytes(n_query, k, splits, flags));
 }
 
-// With one entry per group the groups of the list entries follow the candidates: [query tiles][splits][k][TQ] int64
-extern "C" int64_t btsbot_knn_workspace_grouped(int64_t n_query, int64_t n_bank, int dim, int k, int splits, int flags) {
-  const int64_t base = btsbot_knn_workspace(n_query, n_bank, dim, k, splits);
-  if (base < 0 || (flags & GM_ONE) == 0) return base;
-  if (splits == 0) splits = auto_splits(n_query, n_bank);
-  return base + (int64_t)(((size_t)n_query + TQ - 1) / TQ * TQ * splits * k * sizeof(long long));
+extern "C" int64_t btsbot_knn_workspace(int64_t n_query, int64_t n_bank, int dim, int k, int splits) {
+  return btsbot_knn_workspace_grouped(n_query, n_bank, dim, k, splits, 0);
 }
 
 namespace {
@@ -1282,12 +661,8 @@ int launch_query(const float* queries, int64_t n_query, const float* bank, const
                  unsigned char* qimg, Cand* cand, const long long* qgrp, const long long* bgrp, hipStream_t st) {
   // (the candidates end on a multiple of 8 bytes behind the 256-byte aligned query image)
   long long* lgrp = reinterpret_cast<long long*>(cand + (size_t)n_query * splits * k);
-  hipLaunchKernelGGL(knn_pack_kernel, dim3((unsigned)((n_query + 3) / 4)), dim3(256), 0, st, queries, (long)n_query, dim,
-                     (int)MODE_QUERY, qimg);
-  LAUNCH_CHECK();
-
-  const int total_tiles = (int)((n_bank + TB - 1) / TB);
-  const int tps = (total_tiles + splits - 1) / splits;
+  TRY(knn::pack_queries(queries, n_query, dim, qimg, st));
+  const knn::TileGrid tg = knn::tile_grid(n_query, n_bank, splits);
   // 64 KB of operands + 1 KB of lists per k: two workgroups per CU up to k = 16, in every group mode
   static DevOnce attr;
   if (attr.need()) {
@@ -1295,9 +670,9 @@ int launch_query(const float* queries, int64_t n_query, const float* bank, const
                                 hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS + TQ * MAX_K * (int)sizeof(Cand)));
     attr.done();
   }
-  hipLaunchKernelGGL(knn_select_kernel<GM>, dim3((unsigned)((n_query + TQ - 1) / TQ), (unsigned)splits), dim3(256),
-                     GEMM_LDS + TQ * k * (int)sizeof(Cand), st, qimg, packed, (long)n_query, (int)n_bank, dim, k, (long)self_offset,
-                     tps, splits, cand, qgrp, bgrp, lgrp);
+  hipLaunchKernelGGL(knn_select_kernel<GM>, tg.grid, dim3(256), GEMM_LDS + TQ * k * (int)sizeof(Cand), st, qimg, packed,
+                     (long)n_query, (int)n_bank, dim, k, (long)self_offset, tg.tiles_per_split, splits, cand, qgrp, bgrp,
+                     lgrp);
   LAUNCH_CHECK();
   hipLaunchKernelGGL(knn_merge_kernel<(GM & GM_ONE)>, dim3((unsigned)n_query), dim3(64), 0, st, queries, bank,
                      (const Cand*)cand, dim, k, splits, metric, idx, dist, bgrp);
@@ -1309,45 +684,17 @@ int query_checked(const char* who, const float* queries, int64_t n_query, const 
                   int64_t n_bank, int dim, int k, int metric, int64_t self_offset, int splits, int64_t* idx, float* dist,
                   void* workspace, int64_t workspace_bytes, const int64_t* query_group, const int64_t* bank_group,
                   int flags, void* stream) {
-  const int s = check_shape(who, n_query, n_bank, dim, k);
-  if (s != BTSBOT_OK) return s;
-  if (metric != BTSBOT_KNN_EUCLIDEAN && metric != BTSBOT_KNN_COSINE) {
-    btsbot_set_error("%s: metric %d", who, metric);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if (splits < 0 || splits > MAX_SPLITS) {
-    btsbot_set_error("%s: splits=%d must be 0 (the library's choice) .. %d", who, splits, MAX_SPLITS);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if ((flags & ~(GM_EXCLUDE | GM_ONE)) != 0) {
-    btsbot_set_error("%s: flags=%d holds bits other than BTSBOT_KNN_EXCLUDE_SAME | BTSBOT_KNN_ONE_PER_GROUP", who, flags);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if ((flags & GM_ONE) != 0 && k > MAX_K_ONE) {
-    btsbot_set_error("%s: k=%d, but BTSBOT_KNN_ONE_PER_GROUP holds k <= %d (the merge keeps its pool's groups on chip)", who, k,
-                     MAX_K_ONE);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
+  const bool null_arg = queries == nullptr || idx == nullptr || dist == nullptr || workspace == nullptr ||
+                        (n_bank > 0 && (bank == nullptr || packed == nullptr));
+  const int sp = splits == 0 ? auto_splits(n_query, n_bank) : splits;
+  TRY(knn::check_search(who, knn::SearchArgs{n_query, n_bank, dim, k, metric, splits, 0, flags, GM_EXCLUDE | GM_ONE,
+                                             nullptr, null_arg, query_group, bank_group, packed, workspace,
+                                             workspace_bytes, query_extra_bytes(n_query, k, sp, flags)}));
   if (n_query == 0) return BTSBOT_OK;
-  if (splits == 0) splits = auto_splits(n_query, n_bank);
-  const int64_t need = btsbot_knn_workspace_grouped(n_query, n_bank, dim, k, splits, flags);
-  if (queries == nullptr || idx == nullptr || dist == nullptr || workspace == nullptr ||
-      (n_bank > 0 && (bank == nullptr || packed == nullptr))) {
-    btsbot_set_error("%s: NULL argument", who);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if (((flags & GM_EXCLUDE) != 0 && query_group == nullptr) || (flags != 0 && n_bank > 0 && bank_group == nullptr)) {
-    btsbot_set_error("%s: flags=%d need bank_group (and BTSBOT_KNN_EXCLUDE_SAME query_group), got NULL", who, flags);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if (workspace_bytes < need || ((uintptr_t)workspace & 15) != 0 || ((uintptr_t)packed & 15) != 0) {
-    btsbot_set_error("%s: workspace of %lld bytes (need %lld), or workspace / packed not 16-byte aligned", who,
-                     (long long)workspace_bytes, (long long)need);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
+  splits = sp;
   hipStream_t st = (hipStream_t)stream;
   unsigned char* qimg = reinterpret_cast<unsigned char*>(workspace);
-  Cand* cand = reinterpret_cast<Cand*>(qimg + image_bytes(n_query, dim));
+  Cand* cand = reinterpret_cast<Cand*>(qimg + knn::image_bytes(n_query, dim));
   const unsigned char* pk = reinterpret_cast<const unsigned char*>(packed);
   const long long* qg = reinterpret_cast<const long long*>(query_group);
   const long long* bg = reinterpret_cast<const long long*>(bank_group);
@@ -1377,324 +724,4 @@ extern "C" int btsbot_knn_query_grouped(const float* queries, int64_t n_query, c
                                         void* stream, const int64_t* query_group, const int64_t* bank_group, int flags) {
   return query_checked("btsbot_knn_query_grouped", queries, n_query, bank, packed, n_bank, dim, k, metric, self_offset,
                        splits, idx, dist, workspace, workspace_bytes, query_group, bank_group, flags, stream);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// radius search: the entry points
-namespace {
-
-struct RadiusArgs {
-  const float* queries;
-  int64_t n_query;
-  const void* packed;
-  int64_t n_bank;
-  int dim, metric;
-  const float* radius;
-  int64_t self_offset;
-  int splits;
-  const int64_t* query_group;
-  const int64_t* bank_group;
-  int flags;
-  void* workspace;
-  int64_t workspace_bytes;
-};
-
-int radius_checked(const char* who, const RadiusArgs& a) {
-  TRY(check_shape(who, a.n_query, a.n_bank, a.dim, 1));
-  if (a.metric != BTSBOT_KNN_EUCLIDEAN && a.metric != BTSBOT_KNN_COSINE) {
-    btsbot_set_error("%s: metric %d", who, a.metric);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if (a.splits < 1 || a.splits > MAX_SPLITS) {
-    btsbot_set_error("%s: splits=%d must be 1 .. %d", who, a.splits, MAX_SPLITS);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if ((a.flags & ~GM_EXCLUDE) != 0) {
-    btsbot_set_error("%s: flags=%d, only 0 and BTSBOT_KNN_EXCLUDE_SAME are radius modes", who, a.flags);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if (a.n_query == 0) return BTSBOT_OK;
-  if (a.queries == nullptr || a.radius == nullptr || a.workspace == nullptr || (a.n_bank > 0 && a.packed == nullptr)) {
-    btsbot_set_error("%s: NULL argument", who);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if (a.flags != 0 && (a.query_group == nullptr || (a.n_bank > 0 && a.bank_group == nullptr))) {
-    btsbot_set_error("%s: BTSBOT_KNN_EXCLUDE_SAME needs query_group and bank_group, got NULL", who);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  const int64_t need = (int64_t)image_bytes(a.n_query, a.dim);
-  if (a.workspace_bytes < need || ((uintptr_t)a.workspace & 15) != 0 || ((uintptr_t)a.packed & 15) != 0) {
-    btsbot_set_error("%s: workspace of %lld bytes (need %lld), or workspace / packed not 16-byte aligned", who,
-                     (long long)a.workspace_bytes, (long long)need);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  return BTSBOT_OK;
-}
-
-// query pack + one tile pass (FILL = false: counts are written; true: counts and offsets are read, cand is written)
-template <bool FILL, bool EXCL>
-int launch_radius(const RadiusArgs& a, int* counts, const int64_t* offsets, int* cand, int64_t n_cand, int* err,
-                  hipStream_t st) {
-  unsigned char* qimg = reinterpret_cast<unsigned char*>(a.workspace);
-  hipLaunchKernelGGL(knn_pack_kernel, dim3((unsigned)((a.n_query + 3) / 4)), dim3(256), 0, st, a.queries, (long)a.n_query,
-                     a.dim, (int)MODE_QUERY, qimg);
-  LAUNCH_CHECK();
-  constexpr int LDS = GEMM_LDS + TQ * 16;   // operands + per query row: counter, region size, region start
-  static DevOnce attr;
-  if (attr.need()) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_radius_kernel<FILL, EXCL>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    attr.done();
-  }
-  // the margin of DESIGN.md 4p; u = 2^-24
-  const float u = 5.9604644775390625e-8f;
-  const bool cosine = a.metric == BTSBOT_KNN_COSINE;
-  const float rel = 1.f + 4.f * (float)(a.dim + 4) * u;
-  const float ctau = (cosine ? 16.f : 8.f) * (float)(a.dim + 8) * u;
-  const int total_tiles = (int)((a.n_bank + TB - 1) / TB);
-  const int tps = (total_tiles + a.splits - 1) / a.splits;
-  hipLaunchKernelGGL((knn_radius_kernel<FILL, EXCL>), dim3((unsigned)((a.n_query + TQ - 1) / TQ), (unsigned)a.splits),
-                     dim3(256), LDS, st, (const unsigned char*)qimg, reinterpret_cast<const unsigned char*>(a.packed),
-                     (long)a.n_query, (int)a.n_bank, a.dim, a.metric, a.radius, rel, ctau, (long)a.self_offset, tps,
-                     a.splits, reinterpret_cast<const long long*>(a.query_group),
-                     reinterpret_cast<const long long*>(a.bank_group), counts,
-                     reinterpret_cast<const long long*>(offsets), cand, (long long)n_cand, err);
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
-}
-
-}  // namespace
-
-extern "C" int64_t btsbot_knn_radius_workspace(int64_t n_query, int dim) {
-  if (check_shape("btsbot_knn_radius_workspace", n_query, 0, dim, 1) != BTSBOT_OK) return BTSBOT_ERR_INVALID_ARG;
-  return (int64_t)image_bytes(n_query, dim);
-}
-
-extern "C" int btsbot_knn_radius_count(const float* queries, int64_t n_query, const void* packed, int64_t n_bank, int dim,
-                                       int metric, const float* radius, int64_t self_offset, int splits,
-                                       const int64_t* query_group, const int64_t* bank_group, int flags, int32_t* counts,
-                                       void* workspace, int64_t workspace_bytes, void* stream) {
-  const RadiusArgs a{queries, n_query, packed, n_bank, dim, metric, radius, self_offset, splits, query_group, bank_group,
-                     flags, workspace, workspace_bytes};
-  TRY(radius_checked("btsbot_knn_radius_count", a));
-  if (n_query == 0) return BTSBOT_OK;
-  if (counts == nullptr) {
-    btsbot_set_error("btsbot_knn_radius_count: NULL counts");
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  return flags != 0 ? launch_radius<false, true>(a, counts, nullptr, nullptr, 0, nullptr, st)
-                    : launch_radius<false, false>(a, counts, nullptr, nullptr, 0, nullptr, st);
-}
-
-extern "C" int btsbot_knn_radius_fill(const float* queries, int64_t n_query, const float* bank, const void* packed,
-                                      int64_t n_bank, int dim, int metric, const float* radius, int64_t self_offset,
-                                      int splits, const int64_t* query_group, const int64_t* bank_group, int flags,
-                                      const int32_t* counts, const int64_t* offsets, int64_t n_cand, int32_t* cand,
-                                      float* dist, uint8_t* keep, int32_t* error_flag, void* workspace,
-                                      int64_t workspace_bytes, void* stream) {
-  const RadiusArgs a{queries, n_query, packed, n_bank, dim, metric, radius, self_offset, splits, query_group, bank_group,
-                     flags, workspace, workspace_bytes};
-  TRY(radius_checked("btsbot_knn_radius_fill", a));
-  if (n_cand < 0) {
-    btsbot_set_error("btsbot_knn_radius_fill: n_cand=%lld", (long long)n_cand);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if (n_query == 0 || n_cand == 0) return BTSBOT_OK;
-  if (bank == nullptr || counts == nullptr || offsets == nullptr || cand == nullptr || dist == nullptr || keep == nullptr ||
-      error_flag == nullptr) {
-    btsbot_set_error("btsbot_knn_radius_fill: NULL argument");
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  int* cnt = const_cast<int*>(counts);   // (read only by the FILL instantiation)
-  TRY(flags != 0 ? (launch_radius<true, true>(a, cnt, offsets, cand, n_cand, error_flag, st))
-                 : (launch_radius<true, false>(a, cnt, offsets, cand, n_cand, error_flag, st)));
-  // enough waves per query that a crowded row does not serialise: its candidates are shared out over Y waves
-  const int64_t per = (n_cand + n_query - 1) / n_query;
-  const unsigned Y = (unsigned)(per <= 32 ? 1 : per >= 32 * 64 ? 64 : (per + 31) / 32);
-  hipLaunchKernelGGL(knn_radius_verify_kernel, dim3((unsigned)n_query, Y), dim3(64), 0, st, queries, bank, radius,
-                     reinterpret_cast<const long long*>(offsets), splits, (const int*)cand, (int)n_bank, dim, metric, dist,
-                     keep);
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// neighbour ranks: the entry points
-namespace {
-
-struct RankArgs {
-  const float* queries;
-  int64_t n_query;
-  const float* bank;
-  const void* packed;
-  int64_t n_bank;
-  int dim, metric;
-  const int64_t* targets;
-  int n_targets;
-  int64_t self_offset;
-  int splits;
-  const int64_t* query_group;
-  const int64_t* bank_group;
-  int flags;
-  void* workspace;
-  int64_t workspace_bytes;
-};
-
-// the workspace: the packed query rows, thr float2 [n_query][n_targets], rowlim float [n_query]
-size_t rank_thr_bytes(int64_t n_query, int n_targets) {
-  return ((size_t)n_query * n_targets * sizeof(float2) + 255) & ~(size_t)255;
-}
-
-int rank_checked(const char* who, const RankArgs& a) {
-  TRY(check_shape(who, a.n_query, a.n_bank, a.dim, a.n_targets));   // (1 <= n_targets <= 64 is k's range)
-  if (a.metric != BTSBOT_KNN_EUCLIDEAN && a.metric != BTSBOT_KNN_COSINE) {
-    btsbot_set_error("%s: metric %d", who, a.metric);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if (a.splits < 1 || a.splits > MAX_SPLITS) {
-    btsbot_set_error("%s: splits=%d must be 1 .. %d", who, a.splits, MAX_SPLITS);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if ((a.flags & ~GM_EXCLUDE) != 0) {
-    btsbot_set_error("%s: flags=%d, only 0 and BTSBOT_KNN_EXCLUDE_SAME are rank modes", who, a.flags);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if (a.n_query == 0) return BTSBOT_OK;
-  if (a.queries == nullptr || a.targets == nullptr || a.workspace == nullptr ||
-      (a.n_bank > 0 && (a.bank == nullptr || a.packed == nullptr))) {
-    btsbot_set_error("%s: NULL argument", who);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if (a.flags != 0 && (a.query_group == nullptr || (a.n_bank > 0 && a.bank_group == nullptr))) {
-    btsbot_set_error("%s: BTSBOT_KNN_EXCLUDE_SAME needs query_group and bank_group, got NULL", who);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  const int64_t need = btsbot_knn_rank_workspace(a.n_query, a.dim, a.n_targets);
-  if (a.workspace_bytes < need || ((uintptr_t)a.workspace & 15) != 0 || ((uintptr_t)a.packed & 15) != 0) {
-    btsbot_set_error("%s: workspace of %lld bytes (need %lld), or workspace / packed not 16-byte aligned", who,
-                     (long long)a.workspace_bytes, (long long)need);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  return BTSBOT_OK;
-}
-
-// the margin of DESIGN.md 4p / 4r; u = 2^-24
-struct RankMargin {
-  float rel, relm, ctau;
-  RankMargin(int dim, int metric) {
-    const float u = 5.9604644775390625e-8f;
-    rel = 1.f + 4.f * (float)(dim + 4) * u;
-    relm = 1.f - 4.f * (float)(dim + 4) * u;
-    ctau = (metric == BTSBOT_KNN_COSINE ? 16.f : 8.f) * (float)(dim + 8) * u;
-  }
-};
-
-template <bool FILL, bool EXCL>
-int launch_rank(const RankArgs& a, int* rank, int* counts, const int64_t* offsets, int* cand, uint64_t* cmask,
-                int64_t n_band, int* err, hipStream_t st) {
-  unsigned char* qimg = reinterpret_cast<unsigned char*>(a.workspace);
-  const float2* thr = reinterpret_cast<const float2*>(qimg + image_bytes(a.n_query, a.dim));
-  const float* rowlim = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(thr) +
-                                                       rank_thr_bytes(a.n_query, a.n_targets));
-  // operands + per query row: counter, region size, region start; the queue's count; the count pass: + its
-  // n_targets sure counts per row
-  const int lds = GEMM_LDS + TQ * 16 + 16 + (FILL ? 0 : TQ * a.n_targets * (int)sizeof(int));
-  static DevOnce attr;
-  if (attr.need()) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_rank_kernel<FILL, EXCL>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                GEMM_LDS + TQ * 16 + 16 + (FILL ? 0 : TQ * MAX_K * (int)sizeof(int))));
-    attr.done();
-  }
-  const RankMargin m(a.dim, a.metric);
-  const int total_tiles = (int)((a.n_bank + TB - 1) / TB);
-  const int tps = (total_tiles + a.splits - 1) / a.splits;
-  hipLaunchKernelGGL((knn_rank_kernel<FILL, EXCL>), dim3((unsigned)((a.n_query + TQ - 1) / TQ), (unsigned)a.splits),
-                     dim3(256), lds, st, (const unsigned char*)qimg, reinterpret_cast<const unsigned char*>(a.packed),
-                     (long)a.n_query, (int)a.n_bank, a.dim, a.metric, a.n_targets, thr, rowlim, m.ctau,
-                     (long)a.self_offset, tps, a.splits, reinterpret_cast<const long long*>(a.query_group),
-                     reinterpret_cast<const long long*>(a.bank_group), rank, counts,
-                     reinterpret_cast<const long long*>(offsets), cand, reinterpret_cast<unsigned long long*>(cmask),
-                     (long long)n_band, err);
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
-}
-
-}  // namespace
-
-extern "C" int64_t btsbot_knn_rank_workspace(int64_t n_query, int dim, int n_targets) {
-  if (check_shape("btsbot_knn_rank_workspace", n_query, 0, dim, n_targets) != BTSBOT_OK) return BTSBOT_ERR_INVALID_ARG;
-  return (int64_t)(image_bytes(n_query, dim) + rank_thr_bytes(n_query, n_targets) + (size_t)n_query * sizeof(float));
-}
-
-extern "C" int btsbot_knn_rank_count(const float* queries, int64_t n_query, const float* bank, const void* packed,
-                                     int64_t n_bank, int dim, int metric, const int64_t* targets, int n_targets,
-                                     int64_t self_offset, int splits, const int64_t* query_group,
-                                     const int64_t* bank_group, int flags, float* dist, int32_t* rank, int32_t* counts,
-                                     void* workspace, int64_t workspace_bytes, void* stream) {
-  const RankArgs a{queries, n_query, bank, packed, n_bank, dim, metric, targets, n_targets, self_offset, splits,
-                   query_group, bank_group, flags, workspace, workspace_bytes};
-  TRY(rank_checked("btsbot_knn_rank_count", a));
-  if (n_query == 0) return BTSBOT_OK;
-  if (dist == nullptr || rank == nullptr || counts == nullptr) {
-    btsbot_set_error("btsbot_knn_rank_count: NULL dist / rank / counts");
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  unsigned char* qimg = reinterpret_cast<unsigned char*>(workspace);
-  float2* thr = reinterpret_cast<float2*>(qimg + image_bytes(n_query, dim));
-  float* rowlim = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(thr) + rank_thr_bytes(n_query, n_targets));
-  hipLaunchKernelGGL(knn_pack_kernel, dim3((unsigned)((n_query + 3) / 4)), dim3(256), 0, st, queries, (long)n_query, dim,
-                     (int)MODE_QUERY, qimg);
-  LAUNCH_CHECK();
-  const RankMargin m(dim, metric);
-  hipLaunchKernelGGL(knn_rank_thresh_kernel, dim3((unsigned)n_query), dim3(64), 0, st, queries, bank,
-                     reinterpret_cast<const unsigned char*>(packed), (long)n_bank, dim, metric,
-                     reinterpret_cast<const long long*>(targets), n_targets, (long)self_offset,
-                     flags != 0 ? reinterpret_cast<const long long*>(query_group) : nullptr,
-                     reinterpret_cast<const long long*>(bank_group), m.rel, m.relm, m.ctau, dist, rank, thr, rowlim);
-  LAUNCH_CHECK();
-  if (n_bank == 0) {   // every target is out of range: rank -1, dist NaN, no band
-    HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_query * splits * sizeof(int), st));
-    return BTSBOT_OK;
-  }
-  return flags != 0 ? launch_rank<false, true>(a, rank, counts, nullptr, nullptr, nullptr, 0, nullptr, st)
-                    : launch_rank<false, false>(a, rank, counts, nullptr, nullptr, nullptr, 0, nullptr, st);
-}
-
-extern "C" int btsbot_knn_rank_fill(const float* queries, int64_t n_query, const float* bank, const void* packed,
-                                    int64_t n_bank, int dim, int metric, const int64_t* targets, int n_targets,
-                                    int64_t self_offset, int splits, const int64_t* query_group,
-                                    const int64_t* bank_group, int flags, const float* dist, int32_t* rank,
-                                    const int32_t* counts, const int64_t* offsets, int64_t n_band, int32_t* cand,
-                                    uint64_t* cand_mask, int32_t* error_flag, void* workspace, int64_t workspace_bytes,
-                                    void* stream) {
-  const RankArgs a{queries, n_query, bank, packed, n_bank, dim, metric, targets, n_targets, self_offset, splits,
-                   query_group, bank_group, flags, workspace, workspace_bytes};
-  TRY(rank_checked("btsbot_knn_rank_fill", a));
-  if (n_band < 0) {
-    btsbot_set_error("btsbot_knn_rank_fill: n_band=%lld", (long long)n_band);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  if (n_query == 0 || n_band == 0 || n_bank == 0) return BTSBOT_OK;
-  if (dist == nullptr || rank == nullptr || counts == nullptr || offsets == nullptr || cand == nullptr ||
-      cand_mask == nullptr || error_flag == nullptr) {
-    btsbot_set_error("btsbot_knn_rank_fill: NULL argument");
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  int* cnt = const_cast<int*>(counts);   // (read only by the FILL instantiation)
-  TRY(flags != 0 ? (launch_rank<true, true>(a, rank, cnt, offsets, cand, cand_mask, n_band, error_flag, st))
-                 : (launch_rank<true, false>(a, rank, cnt, offsets, cand, cand_mask, n_band, error_flag, st)));
-  // enough waves per query that a crowded row does not serialise, as the radius verify
-  const int64_t per = (n_band + n_query - 1) / n_query;
-  const unsigned Y = (unsigned)(per <= 32 ? 1 : per >= 32 * 64 ? 64 : (per + 31) / 32);
-  hipLaunchKernelGGL(knn_rank_verify_kernel, dim3((unsigned)n_query, Y), dim3(64), 0, st, queries, bank,
-                     reinterpret_cast<const long long*>(targets), n_targets, dist,
-                     reinterpret_cast<const long long*>(offsets), splits, (const int*)cand,
-                     reinterpret_cast<const unsigned long long*>(cand_mask), (int)n_bank, dim, metric, rank);
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
 }

@@ -1,7 +1,7 @@
 """Similar alerts: exact k-nearest neighbours over embedding rows, on the device.
 
 ``model.embed(...)`` and ``ScoreStream(embed=...)`` hand out a learned vector per alert; this module answers "which rows
-of an archive lie nearest to these" without ever forming the [Q, N] distance matrix (csrc/knn.hip):
+of an archive lie nearest to these" without ever forming the [Q, N] distance matrix (csrc/knn*.hip):
 
     idx, dist = embedding_neighbors(queries, bank, k)            # int64 [Q, k], float32 [Q, k]
     index = EmbeddingIndex(bank)                                 # packs the bank once
@@ -100,11 +100,39 @@ def _rows(t, name: str, device=None) -> torch.Tensor:
     return t.detach().to(torch.float32).contiguous()
 
 
+def _n_rows_or_none(x) -> Optional[int]:
+    return int(x.shape[0]) if isinstance(x, torch.Tensor) and x.dim() == 2 else None
+
+
+def _same_dim(queries, bank) -> Tuple[torch.Tensor, torch.Tensor]:
+    q = _rows(queries, "queries")
+    b = _rows(bank, "bank", q.device)
+    if q.shape[1] != b.shape[1]:
+        raise ValueError(f"queries have D = {q.shape[1]}, the bank D = {b.shape[1]}")
+    return q, b
+
+
+def _check_splits(splits) -> None:
+    if not isinstance(splits, int) or isinstance(splits, bool) or not 0 <= splits <= _lib.KNN_MAX_SPLITS:
+        raise ValueError(f"splits must be an int in 0..{_lib.KNN_MAX_SPLITS} (0: the library's choice), got {splits!r}")
+
+
+def _check_cap(name: str, v) -> None:
+    if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 0):
+        raise ValueError(f"{name} must be None or an int >= 0, got {v!r}")
+
+
 def _check_k(k, splits) -> None:
     if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= _lib.KNN_MAX_K:
         raise ValueError(f"k must be an int in 1..{_lib.KNN_MAX_K}, got {k!r}")
-    if not isinstance(splits, int) or isinstance(splits, bool) or not 0 <= splits <= _lib.KNN_MAX_SPLITS:
-        raise ValueError(f"splits must be an int in 0..{_lib.KNN_MAX_SPLITS} (0: the library's choice), got {splits!r}")
+    _check_splits(splits)
+
+
+def _scan_counts(counts: torch.Tensor) -> torch.Tensor:
+    """int64 [counts.numel() + 1]: where each (query, split)'s region starts, and the total at the end."""
+    offsets = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=counts.device)
+    offsets[1:] = torch.cumsum(counts.view(-1), 0, dtype=torch.int64)
+    return offsets
 
 
 def _metric(metric) -> int:
@@ -219,6 +247,24 @@ class EmbeddingIndex:
         self._n += n
         return self
 
+    def _prelude(self, queries, k, splits, query_groups, exclude_same_group, one_per_group, self_offset, targets=None):
+        """The common arguments of ``query``, ``radius`` and ``rank_of``, checked in their order: ``(flags, q, nq,
+        query_groups, splits)``, with ``splits == 0`` resolved to the library's choice."""
+        flags = _check_group_args(k, self._groups is not None, query_groups, exclude_same_group, one_per_group)
+        q = _rows(queries, "queries", self.device)
+        if q.shape[1] != self.dim:
+            raise ValueError(f"queries: D = {q.shape[1]}, the index holds D = {self.dim}")
+        if not isinstance(self_offset, int):
+            raise ValueError(f"self_offset must be an int, got {self_offset!r}")
+        if targets is not None and targets.device != self.device:
+            raise ValueError(f"targets is on {targets.device}, the index on {self.device}")
+        nq = int(q.shape[0])
+        if query_groups is not None:
+            query_groups = _groups(query_groups, "query_groups", nq, self.device)
+        if splits == 0:
+            splits = max(1, int(_lib.lib().btsbot_knn_splits(max(nq, 1), self._n, self.dim, 1)))
+        return flags, q, nq, query_groups, splits
+
     def query(self, queries: torch.Tensor, k: int, *, query_groups: Optional[torch.Tensor] = None,
               exclude_same_group: bool = False, one_per_group: bool = False, splits: int = 0,
               self_offset: int = -1) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -228,15 +274,8 @@ class EmbeddingIndex:
         query_groups: int64 [Q], the query rows' groups.  exclude_same_group: no row of the query row's own group.
         one_per_group: at most one row per group, its nearest; the ``k`` nearest groups (``k <= 32``)."""
         _check_k(k, splits)
-        flags = _check_group_args(k, self._groups is not None, query_groups, exclude_same_group, one_per_group)
-        q = _rows(queries, "queries", self.device)
-        if q.shape[1] != self.dim:
-            raise ValueError(f"queries: D = {q.shape[1]}, the index holds D = {self.dim}")
-        if not isinstance(self_offset, int):
-            raise ValueError(f"self_offset must be an int, got {self_offset!r}")
-        nq = int(q.shape[0])
-        if query_groups is not None:
-            query_groups = _groups(query_groups, "query_groups", nq, self.device)
+        flags, q, nq, query_groups, splits = self._prelude(queries, k, splits, query_groups, exclude_same_group,
+                                                           one_per_group, self_offset)
         idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         dist = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         if nq == 0:
@@ -267,18 +306,10 @@ class EmbeddingIndex:
         pairs whose distance was computed in the direct form), ``total`` and ``error_flag`` (the fill kernel's bounds
         check; 0, or the call raises).  The other arguments are ``query``'s.  Two host reads: the number of
         candidates, then the total, each to allocate."""
-        _check_radius_args(r, int(queries.shape[0]) if isinstance(queries, torch.Tensor) and queries.dim() == 2 else None,
-                           sort, splits, max_total)
-        flags = _check_group_args(1, self._groups is not None, query_groups, exclude_same_group, False)
-        q = _rows(queries, "queries", self.device)
-        if q.shape[1] != self.dim:
-            raise ValueError(f"queries: D = {q.shape[1]}, the index holds D = {self.dim}")
-        if not isinstance(self_offset, int):
-            raise ValueError(f"self_offset must be an int, got {self_offset!r}")
-        nq, n, dev = int(q.shape[0]), self._n, self.device
-        if query_groups is not None:
-            query_groups = _groups(query_groups, "query_groups", nq, dev)
-        L = _lib.lib()
+        _check_radius_args(r, _n_rows_or_none(queries), sort, splits, max_total)
+        flags, q, nq, query_groups, splits = self._prelude(queries, 1, splits, query_groups, exclude_same_group, False,
+                                                           self_offset)
+        n, dev, L = self._n, self.device, _lib.lib()
         with torch.cuda.device(dev):
             if isinstance(r, torch.Tensor):
                 if r.device != dev:
@@ -288,8 +319,6 @@ class EmbeddingIndex:
             else:
                 rad = torch.full((nq,), float(r), dtype=torch.float32, device=dev)   # rounded to fp32 once
                 bad = torch.zeros((), dtype=torch.int64, device=dev)
-            if splits == 0:
-                splits = max(1, int(L.btsbot_knn_splits(max(nq, 1), n, self.dim, 1)))
             counts = torch.zeros((nq, splits), dtype=torch.int32, device=dev)
             need = int(L.btsbot_knn_radius_workspace(nq, self.dim))
             ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
@@ -299,8 +328,7 @@ class EmbeddingIndex:
             if nq and n:
                 _lib.check(L.btsbot_knn_radius_count(*head, *tail, _ptr(counts), _ptr(ws), need, self._stream()),
                            "btsbot_knn_radius_count")
-            offsets = torch.zeros(nq * splits + 1, dtype=torch.int64, device=dev)
-            offsets[1:] = torch.cumsum(counts.view(-1), 0, dtype=torch.int64)
+            offsets = _scan_counts(counts)
             n_cand, bad = torch.stack([offsets[-1], bad]).tolist()          # the host read that sizes the candidates
             if bad:
                 raise ValueError("r must be >= 0 in every row (and not NaN)")
@@ -342,21 +370,11 @@ class EmbeddingIndex:
         order against a target only the direct form can decide.  stats: receives ``band`` and ``error_flag``.  The
         other arguments are ``radius``'s; ``one_per_group`` is not a rank mode.  Two host reads: the number of band
         pairs, to allocate them, and the fill's error flag."""
-        _check_rank_args(targets, int(queries.shape[0]) if isinstance(queries, torch.Tensor) and queries.dim() == 2
-                         else None, splits, max_band, one_per_group)
-        flags = _check_group_args(1, self._groups is not None, query_groups, exclude_same_group, False)
-        q = _rows(queries, "queries", self.device)
-        if q.shape[1] != self.dim:
-            raise ValueError(f"queries: D = {q.shape[1]}, the index holds D = {self.dim}")
-        if not isinstance(self_offset, int):
-            raise ValueError(f"self_offset must be an int, got {self_offset!r}")
-        if targets.device != self.device:
-            raise ValueError(f"targets is on {targets.device}, the index on {self.device}")
-        nq, n, dev, t = int(q.shape[0]), self._n, self.device, int(targets.shape[1])
-        if query_groups is not None:
-            query_groups = _groups(query_groups, "query_groups", nq, dev)
+        _check_rank_args(targets, _n_rows_or_none(queries), splits, max_band, one_per_group)
+        flags, q, nq, query_groups, splits = self._prelude(queries, 1, splits, query_groups, exclude_same_group, False,
+                                                           self_offset, targets=targets)
+        n, dev, t, L = self._n, self.device, int(targets.shape[1]), _lib.lib()
         tg = targets.detach().contiguous()
-        L = _lib.lib()
         with torch.cuda.device(dev):
             dist = torch.full((nq, t), float("nan"), dtype=torch.float32, device=dev)
             rank = torch.full((nq, t), -1, dtype=torch.int32, device=dev)
@@ -364,8 +382,6 @@ class EmbeddingIndex:
                 stats.update(band=0, error_flag=0)
             if nq == 0:
                 return rank.to(torch.int64), dist
-            if splits == 0:
-                splits = max(1, int(L.btsbot_knn_splits(nq, n, self.dim, 1)))
             counts = torch.zeros((nq, splits), dtype=torch.int32, device=dev)
             need = int(L.btsbot_knn_rank_workspace(nq, self.dim, t))
             if need < 0:
@@ -376,8 +392,7 @@ class EmbeddingIndex:
                     flags)
             _lib.check(L.btsbot_knn_rank_count(*head, _ptr(dist), _ptr(rank), _ptr(counts), _ptr(ws), need,
                                                self._stream()), "btsbot_knn_rank_count")
-            offsets = torch.zeros(nq * splits + 1, dtype=torch.int64, device=dev)
-            offsets[1:] = torch.cumsum(counts.view(-1), 0, dtype=torch.int64)
+            offsets = _scan_counts(counts)
             n_band = int(offsets[-1])                                       # the host read that sizes the band pairs
             if max_band is not None and n_band > max_band:
                 raise ValueError(f"the band holds {n_band} pairs, more than max_band = {max_band}")
@@ -418,10 +433,8 @@ def _check_radius_args(r, n_query, sort, splits, max_total) -> None:
         raise ValueError(f"r must be a float >= 0 (and not NaN) or a tensor of them, got {r!r}")
     if sort not in SORTS:
         raise ValueError(f"sort must be one of {SORTS}, got {sort!r}")
-    if not isinstance(splits, int) or isinstance(splits, bool) or not 0 <= splits <= _lib.KNN_MAX_SPLITS:
-        raise ValueError(f"splits must be an int in 0..{_lib.KNN_MAX_SPLITS} (0: the library's choice), got {splits!r}")
-    if max_total is not None and (isinstance(max_total, bool) or not isinstance(max_total, int) or max_total < 0):
-        raise ValueError(f"max_total must be None or an int >= 0, got {max_total!r}")
+    _check_splits(splits)
+    _check_cap("max_total", max_total)
 
 
 def _check_rank_args(targets, n_query, splits, max_band, one_per_group=False) -> None:
@@ -434,10 +447,8 @@ def _check_rank_args(targets, n_query, splits, max_band, one_per_group=False) ->
     if targets.dim() != 2 or not 1 <= targets.shape[1] <= _lib.KNN_MAX_K or \
             (n_query is not None and targets.shape[0] != n_query):
         raise ValueError(f"targets must be [Q = {n_query}, t] with 1 <= t <= {_lib.KNN_MAX_K}, got {tuple(targets.shape)}")
-    if not isinstance(splits, int) or isinstance(splits, bool) or not 0 <= splits <= _lib.KNN_MAX_SPLITS:
-        raise ValueError(f"splits must be an int in 0..{_lib.KNN_MAX_SPLITS} (0: the library's choice), got {splits!r}")
-    if max_band is not None and (isinstance(max_band, bool) or not isinstance(max_band, int) or max_band < 0):
-        raise ValueError(f"max_band must be None or an int >= 0, got {max_band!r}")
+    _check_splits(splits)
+    _check_cap("max_band", max_band)
 
 
 def neighbor_ranks(queries: torch.Tensor, bank: torch.Tensor, targets: torch.Tensor, metric: str = "euclidean", *,
@@ -448,13 +459,9 @@ def neighbor_ranks(queries: torch.Tensor, bank: torch.Tensor, targets: torch.Ten
     neighbour ordering of each row of ``queries`` [Q, D], as ``EmbeddingIndex.rank_of`` returns them.  Packs the bank for
     this one call."""
     _metric(metric)
-    _check_rank_args(targets, int(queries.shape[0]) if isinstance(queries, torch.Tensor) and queries.dim() == 2 else None,
-                     splits, max_band)
+    _check_rank_args(targets, _n_rows_or_none(queries), splits, max_band)
     _check_group_args(1, bank_groups is not None, query_groups, exclude_same_group, False)
-    q = _rows(queries, "queries")
-    b = _rows(bank, "bank", q.device)
-    if q.shape[1] != b.shape[1]:
-        raise ValueError(f"queries have D = {q.shape[1]}, the bank D = {b.shape[1]}")
+    q, b = _same_dim(queries, bank)
     return EmbeddingIndex(b, metric, groups=bank_groups).rank_of(
         q, targets, query_groups=query_groups, exclude_same_group=exclude_same_group, self_offset=self_offset,
         splits=splits, max_band=max_band, stats=stats)
@@ -489,13 +496,9 @@ def radius_neighbors(queries: torch.Tensor, bank: torch.Tensor, r, metric: str =
     """Every row of ``bank`` [N, D] within ``r`` of each row of ``queries`` [Q, D], as the CSR ``EmbeddingIndex.radius``
     returns.  Packs the bank for this one call."""
     _metric(metric)
-    _check_radius_args(r, int(queries.shape[0]) if isinstance(queries, torch.Tensor) and queries.dim() == 2 else None,
-                       sort, splits, max_total)
+    _check_radius_args(r, _n_rows_or_none(queries), sort, splits, max_total)
     _check_group_args(1, bank_groups is not None, query_groups, exclude_same_group, False)
-    q = _rows(queries, "queries")
-    b = _rows(bank, "bank", q.device)
-    if q.shape[1] != b.shape[1]:
-        raise ValueError(f"queries have D = {q.shape[1]}, the bank D = {b.shape[1]}")
+    q, b = _same_dim(queries, bank)
     return EmbeddingIndex(b, metric, groups=bank_groups).radius(
         q, r, query_groups=query_groups, exclude_same_group=exclude_same_group, sort=sort, splits=splits,
         max_total=max_total, stats=stats)
@@ -516,8 +519,7 @@ def radius_graph(emb: torch.Tensor, r, include_self: bool = True, metric: str = 
     _check_method(method)
     if group_mode != "exclude":
         raise ValueError(f'radius lists know group_mode="exclude" only, got {group_mode!r}')
-    _check_radius_args(r, int(emb.shape[0]) if isinstance(emb, torch.Tensor) and emb.dim() == 2 else None, sort, splits,
-                       max_total)
+    _check_radius_args(r, _n_rows_or_none(emb), sort, splits, max_total)
     if method == "grid":
         from .mapindex import check_grid_method
         check_grid_method(int(emb.shape[1]) if isinstance(emb, torch.Tensor) and emb.dim() == 2 else None, metric)
@@ -559,10 +561,7 @@ def embedding_neighbors(queries: torch.Tensor, bank: torch.Tensor, k: int, metri
     _check_k(k, splits)
     _metric(metric)
     _check_group_args(k, bank_groups is not None, query_groups, exclude_same_group, one_per_group)
-    q = _rows(queries, "queries")
-    b = _rows(bank, "bank", q.device)
-    if q.shape[1] != b.shape[1]:
-        raise ValueError(f"queries have D = {q.shape[1]}, the bank D = {b.shape[1]}")
+    q, b = _same_dim(queries, bank)
     return EmbeddingIndex(b, metric, groups=bank_groups).query(
         q, k, query_groups=query_groups, exclude_same_group=exclude_same_group, one_per_group=one_per_group, splits=splits)
 

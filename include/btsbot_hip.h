@@ -879,7 +879,7 @@ int btsbot_knn_query_grouped(const float* queries, int64_t n_query, const float*
                              float* dist, void* workspace, int64_t workspace_bytes, void* stream,
                              const int64_t* query_group, const int64_t* bank_group, int flags);
 
-/* ---- everything within r: radius search over the same packed bank (csrc/knn.hip) ---- */
+/* ---- everything within r: radius search over the same packed bank (csrc/knn_radius.hip) ---- */
 
 /* Bank row b belongs to query row q's list if and only if b is eligible (finite, not the row self_offset masks, not of
  * q's group under BTSBOT_KNN_EXCLUDE_SAME) and the direct-form fp32 distance -- the function btsbot_knn_query applies to
@@ -915,7 +915,7 @@ int btsbot_knn_radius_fill(const float* queries, int64_t n_query, const float* b
                            const int64_t* offsets, int64_t n_cand, int32_t* cand, float* dist, uint8_t* keep,
                            int32_t* error_flag, void* workspace, int64_t workspace_bytes, void* stream);
 
-/* ---- neighbour ranks: where does a given bank row stand in a query row's ordering (csrc/knn.hip) ---- */
+/* ---- neighbour ranks: where does a given bank row stand in a query row's ordering (csrc/knn_rank.hip) ---- */
 
 /* targets int64 [n_query][n_targets] (device memory, 1 <= n_targets <= 64) names bank rows.  For every (q, c):
  *   dist[q][c] = the direct-form fp32 distance of query row q and bank row targets[q][c] -- the bits btsbot_knn_query and

@@ -1,7 +1,7 @@
 """What the MapIndex tests share (no GPU): the three rules of csrc/grid.hip in numpy float32, one
 rounded operation at a time, the brute-force answers they define, and the seeded sets.
 
-  distance    sqrt(fl(fl(t0 t0) + fl(t1 t1))), t = q - b: what direct_distance of csrc/knn.hip gives at D = 2
+  distance    sqrt(fl(fl(t0 t0) + fl(t1 t1))), t = q - b: what direct_distance of csrc/knn_tile.h gives at D = 2
   finite row  both coordinates finite and fl(fl(x x) + fl(y y)) <= FLT_MAX
   cells       c(x) = clamp(floor(fl(fl(x - x0) * inv_h)), 0, G - 1), a monotone function of x; a query with radius r walks
               c(lo) .. c(hi), lo = down(fl(x - R)), hi = up(fl(x + R)), R = up(fl(max(r, 2^-60) * (1 + 16 u)))

@@ -18,7 +18,7 @@ import numpy as np
 import knn_ref as R
 
 U, TILE = R.U, R.TILE
-MAX_K_ONE = 32   # k's cap under one_per_group (csrc/knn.hip, MAX_K_ONE)
+MAX_K_ONE = 32   # k's cap under one_per_group (csrc/knn_tile.h, MAX_K_ONE)
 MODES = {"exclude": (True, False), "distinct": (False, True), "exclude+distinct": (True, True)}   # (exclude, one)
 PATTERNS = ("runs", "mod3", "mod40", "one", "distinct", "runs_hi32", "mod40_hi32", "negative")
 

@@ -18,7 +18,7 @@ exact on integer rows.  The distances of the RETURNED rows (clause 2, r_j) are f
 import numpy as np
 
 U = 2.0 ** -24
-TILE = 128   # the kernel's bank tile (csrc/knn.hip)
+TILE = 128   # the kernel's bank tile (csrc/knn_tile.h)
 
 # (Q, N, D, k, splits): a covering subset of Q {1, 63, 65, 130} x N {1, 7, 127, 128, 129, 1000, 4099} x
 # D {1, 5, 31, 32, 33, 528, 1024} x k {1, 15, 64} (k > N included) x splits {1, 2, 7, 0}

@@ -1,6 +1,6 @@
-// The host-side argument checks of btsbot_knn_rank_workspace / _count / _fill (btsbot_amd/csrc/knn.hip) as a stand-alone
-// program for a run under the host sanitizers, on a machine without a GPU: every call below is refused, or has nothing
-// to do, before the first HIP call.
+// The host-side argument checks of btsbot_knn_rank_workspace / _count / _fill (btsbot_amd/csrc/knn_rank.hip, with the
+// shared checker of knn.hip) as a stand-alone program for a run under the host sanitizers, on a machine without a GPU:
+// every call below is refused, or has nothing to do, before the first HIP call.
 //
 //   hipcc -std=c++17 -O1 -g --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined
 //       -Xarch_host -fno-sanitize-recover=all -o tools/unit/knn_rank_args_check tools/unit/knn_rank_args_check.hip
@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "../../btsbot_amd/csrc/knn.hip"
+#include "../../btsbot_amd/csrc/knn_rank.hip"
 
 static char g_err[512];
 void btsbot_set_error(const char* fmt, ...) {

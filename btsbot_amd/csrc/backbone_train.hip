@@ -1,5 +1,5 @@
 // Training-mode schedule of the ConvNeXt image branch: a forward that keeps what the backward
-// needs, and the backward itself (kernels in backward.hip / dwln_bwd.hip / wgrad.hip / gemm2.hip / convnext.hip).
+// needs, and the backward itself (kernels in ln_dw_bwd.hip / dwln_bwd.hip / wgrad.hip / wgrad_f32.hip / gemm2.hip / convnext.hip).
 //
 // Replaces, for the timm backbone reached at /root/reference/btsbot/architectures.py:108,132, what
 // torch autograd does between model(...) (train.py:510) and loss.backward() (train.py:526).
@@ -13,7 +13,7 @@
 // Split training (BTSBOT_F16X2 + "train_split", fp32 schedule otherwise): the blocks' fc1 / fc2 products and the
 // downsamples' -- forward, input gradients and filter gradients -- on split operands (gemm_x2.hip, wgrad_x2.hip).  The
 // gradient operands (dy of a block or downsample, da) carry the largest magnitude the kernel that wrote them recorded;
-// the products scale them by a power of two from it before the split (common.h: split_exp).
+// the products scale them by a power of two from it before the split (device_math.h: split_exp).
 #include <string.h>
 
 #include "ctx.h"

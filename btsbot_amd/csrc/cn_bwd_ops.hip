@@ -1,5 +1,5 @@
 // Op-level entry points of the ConvNeXt training step's LayerNorm / depthwise backward (include/btsbot_hip.h,
-// btsbot_op_cnt_*): the launchers of dwln_bwd.hip and backward.hip one at a time, on the caller's tensors and stream,
+// btsbot_op_cnt_*): the launchers of dwln_bwd.hip and ln_dw_bwd.hip one at a time, on the caller's tensors and stream,
 // for the per-kernel tests.  Nothing here is on the product path: backbone_train_backward calls the same launchers.
 // Every entry point checks its arguments before it allocates or launches anything; what its launcher has no kernel for
 // comes back as BTSBOT_ERR_INVALID_ARG with a message.
@@ -25,7 +25,7 @@ int cnt_planes(const char* who, int B, int P, int C, int nplanes, int64_t pstrid
   return BTSBOT_OK;
 }
 
-// the depthwise kernels of backward.hip: a map side they are instantiated for, 16-byte pixel rows, maps that fit LDS
+// the depthwise kernels of ln_dw_bwd.hip: a map side they are instantiated for, 16-byte pixel rows, maps that fit LDS
 int cnt_dw_shape(const char* who, int B, int HW, int C, size_t lds) {
   if (B < 0 || (HW != 15 && HW != 7 && HW != 3 && HW != 1) || C < 4 || C % 4 != 0 || lds > LDS_MAX) {
     btsbot_set_error("%s: bad shape B=%d HW=%d C=%d (HW 15, 7, 3 or 1; C a multiple of 4; %zu bytes of LDS, at most %zu)", who,

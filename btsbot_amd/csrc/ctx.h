@@ -91,7 +91,7 @@ struct ImageEntry {
   unsigned when;          // which packs write it (0: reserved only, e.g. the dgrad transposes before btsbot_reserve_train)
   bool early;             // training re-pack: stage0b_kernel's keeping form reads it -- written in front of pack_early_ev
   const size_t* reads;    // the packed image it is made from, listed in front of it (nullptr: made from the mirror)
-  int op;                 // >= 0: a PackJob of the batch table (common.h: PACK_*), src / scale = master offsets (-1: none)
+  int op;                 // >= 0: a PackJob of the batch table (launchers.h: PACK_*), src / scale = master offsets (-1: none)
   int64_t src, scale;
   int R, Cc;
   long split_n;           // > 0: the f16 head + remainder planes of the split_n floats of *reads (SplitJob)

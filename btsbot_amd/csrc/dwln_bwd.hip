@@ -7,7 +7,7 @@
 //     dW[c][t] += sum_p dd[p][c] x_in[p + delta_t][c],   db[c] += sum_p dd[p][c]      (depthwise filter / bias)
 //     dy  = dy + conv(dd, flipped taps)        (gradient w.r.t. the block input, joins the residual path)
 //
-// Unfused (ln_bwd_kernel -> dw_wgrad_kernel -> dw_plain_kernel, backward.hip) dd makes a round trip through HBM and is
+// Unfused (ln_bwd_kernel -> dw_wgrad_kernel -> dw_plain_kernel, ln_dw_bwd.hip) dd makes a round trip through HBM and is
 // read twice, and stages 2-3 pay three launch latencies for 9 MB tensors.  Here dd exists only in LDS:
 // a workgroup takes `ga` alerts one after the other (3x3 maps: four per pass); per alert it stages x_in, runs the LayerNorm backward over the
 // map's pixels (C/4 lanes per pixel, float4 pieces, result straight into LDS), then every thread = (channel, row group)

@@ -8,7 +8,7 @@
 // v_mfma_f32_16x16x32_f16 with fp32 accumulation, small terms first: an fp32-class result at the
 // f16 matrix rate.  The epilogues are the fp32 ones of gemm.hip (exact erf GELU, expf SiLU), output always fp32.
 // Training (btsbot_set_option "train_split"): the forward's GELU_SAVE and the input-gradient products' DGELU / PLAIN.
-// Their X is a gradient there: it enters scaled by 2^e (common.h: split_exp of its largest magnitude) so that its heads
+// Their X is a gradient there: it enters scaled by 2^e (device_math.h: split_exp of its largest magnitude) so that its heads
 // stay normal f16 values, and the epilogue multiplies the accumulator by 2^-e; DGELU also reports its output's largest
 // magnitude, the scale of the products that read it next.
 //

@@ -4,7 +4,7 @@
 struct H16Layer {
   const void* w;        // [hi | lo][row tile of 32][k-step][lane 64][8] A fragments (launch_pack_h16)
   const float* bias;    // [N]
-  int K, N, act;        // act: ACT_NONE / ACT_GELU / ACT_RELU (common.h)
+  int K, N, act;        // act: ACT_NONE / ACT_GELU / ACT_RELU (launchers.h)
 };
 
 struct H16Step {        // one layer of the chain; buffers: 0 = z (concat row), 1 = t0, 2 = t1
@@ -26,7 +26,7 @@ struct Head16Args {
   H16Layer comb[3];
   float* logits;
   float* scores;        // may be nullptr
-  float* features;      // embedding outputs as in HeadArgs (common.h): [B][feat_dim + m2.N] fp32, or nullptr
+  float* features;      // embedding outputs as in HeadArgs (launchers.h): [B][feat_dim + m2.N] fp32, or nullptr
   float* hidden;        // [B][comb[n_layers - 1].K] fp32, or nullptr
   int B;
   unsigned long long* stamps;     // optional: workgroup 0 / thread 0 stores the shader clock per phase

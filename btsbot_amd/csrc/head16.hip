@@ -47,7 +47,7 @@ template <typename T> __device__ __forceinline__ void split_store(unsigned char*
   *reinterpret_cast<T*>(lo) = (T)(v - (float)h);
 }
 
-// GELU here = gelu_poly<5> (|error| < 5e-7, common.h): erff costs ~45 instructions per value, ~3k cycles per layer
+// GELU here = gelu_poly<5> (|error| < 5e-7, device_math.h): erff costs ~45 instructions per value, ~3k cycles per layer
 __device__ __forceinline__ float head_act(float x, int act) {
   if (act == ACT_GELU) return gelu_poly<5>(x);
   if (act == ACT_RELU) return relu_f(x);

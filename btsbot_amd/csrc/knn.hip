@@ -13,7 +13,7 @@
 //              norms) from the ORIGINAL fp32 rows, sorted by (distance, index).
 //
 // Operands: every row enters the products as an f16 head + f16 remainder of the row scaled by a power of two of its own
-// (its largest magnitude lands in [2^14, 2^15): common.h, split_exp), three v_mfma_f32_16x16x32_f16 per product, small
+// (its largest magnitude lands in [2^14, 2^15): device_math.h, split_exp), three v_mfma_f32_16x16x32_f16 per product, small
 // terms first (gemm_x2.hip).  The scale is per ROW, so a row's image depends on nothing but the row: an index built by
 // several adds equals one built at once, and a query's answer does not depend on its neighbours in the batch.  A packed row
 // is one record of 16 + 4 * dp bytes (dp = dim rounded up to 32, zero filled):

@@ -1,264 +1,17 @@
-// Backward kernels of the ConvNeXt image branch (gfx950).  Replaces the autograd graph that
-// loss.backward() walks at /root/reference/btsbot/train.py:526 for timm's ConvNeXt blocks:
+// LayerNorm and depthwise backward of the ConvNeXt image branch, one launch per step (gfx950), and the fc2 / layer-scale
+// gradients.  Of the block
 //
 //   y = x + gamma * fc2(gelu(fc1(LN(dwconv(x)))))
 //
-// Given dy: G = dy^T h (wgrad GEMM) -> dW2 = gamma (.) G, dgamma = <W2, G> + b2 * colsum(dy);
-// dh = (gamma (.) dy) W2, da = dh * gelu'(a) (dgrad GEMM epilogue); dW1 = da^T xn; dxn = da W1;
-// LayerNorm backward on the recomputed depthwise output; depthwise dgrad = the same depthwise
-// kernel with the 7x7 filter flipped; depthwise wgrad = per-tap correlation reduced over pixels
-// and alerts.  Reductions over the batch use fp32 atomics into the (pre-zeroed) gradient arena.
-#include <stdlib.h>
-
-#include "mfma.h"
+// given G = dy^T h (the filter-gradient GEMM in front): dW2 = gamma (.) G, dgamma = <W2, G> + b2 * colsum(dy)
+// (fc2_grads_kernel); LayerNorm backward on the depthwise output (ln_bwd_kernel, ln_bwd_narrow_kernel); depthwise dgrad =
+// the same depthwise kernel with the 7x7 filter flipped (dw_plain_kernel); depthwise wgrad = per-tap correlation reduced
+// over pixels and alerts (dw_wgrad_kernel); on 1x1 maps the three as one kernel (ln_dw1_bwd_kernel).  Reductions over the
+// batch use fp32 atomics into the (pre-zeroed) gradient arena, or det_reduce.hip's partial rows.  dwln_bwd.hip fuses the
+// three steps for the larger maps; cn_bwd_ops.hip exposes these launchers one at a time.
+#include "common.h"
 
 namespace {
-
-
-template <typename T> struct Mw : Mfma<T> { static constexpr int KR = 32; };   // reduction depth per MFMA
-template <> struct Mw<float> : Mfma<float> { static constexpr int KR = 4; };
-
-// ---------------------------------------------------------------------------------------
-// wgrad: out[n][k] += sum_m D[m][n] * A[m][k]   (D: [M][N], A: [M][K], both row-major, type T)
-// Workgroup = 64x64 output tile x one slice of M; 4 waves in 2x2, each a 32x32 sub-tile.
-// Both operands are "reduction-major" in memory, so fragments are gathered from row-major LDS
-// tiles with strided 16-bit reads (lane (i, g) takes rows 8g..8g+7 of column i).
-// ---------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void wgrad_kernel(const T* __restrict__ D,
-                                                    const T* __restrict__ A,
-                                                    float* __restrict__ out, int M, int N, int K,
-                                                    int ldo, int mslice) {
-  using MM = Mw<T>;
-  using frag = typename MM::frag;
-  constexpr int TM = 64;                 // rows of the reduction dimension per LDS tile
-  constexpr int PITCH = 64 + 8;          // elements per LDS row (padded)
-  __shared__ T Ds[TM * PITCH];
-  __shared__ T As[TM * PITCH];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wn = wave >> 1, wk = wave & 1;
-  const int n0 = blockIdx.x * 64, k0 = blockIdx.y * 64;
-  const int mbeg = blockIdx.z * mslice, mend = min(M, mbeg + mslice);
-  const int li = lane & 15, lg = lane >> 4;
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  for (int m0 = mbeg; m0 < mend; m0 += TM) {
-    // stage [64 m][64 n] of D and [64 m][64 k] of A (zero-filled at the edges)
-    for (int i = tid; i < TM * 64; i += 256) {
-      const int r = i >> 6, c = i & 63;
-      const int m = m0 + r;
-      Ds[r * PITCH + c] = (m < mend && n0 + c < N) ? D[(size_t)m * N + n0 + c] : (T)0.f;
-      As[r * PITCH + c] = (m < mend && k0 + c < K) ? A[(size_t)m * K + k0 + c] : (T)0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int ms = 0; ms < TM; ms += MM::KR) {
-      frag af[2], bf[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const int cn = wn * 32 + t * 16 + li, ck = wk * 32 + t * 16 + li;
-        if constexpr (MM::KR == 32) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            af[t][e] = Ds[(ms + 8 * lg + e) * PITCH + cn];
-            bf[t][e] = As[(ms + 8 * lg + e) * PITCH + ck];
-          }
-        } else {
-          af[t] = Ds[(ms + lg) * PITCH + cn];
-          bf[t] = As[(ms + lg) * PITCH + ck];
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = MM::m16(af[i], bf[j], acc[i][j]);
-    }
-    __syncthreads();
-  }
-  // C/D layout: col = lane&15 -> k, row = 4*(lane>>4)+r -> n
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = n0 + wn * 32 + i * 16 + lg * 4 + r;
-        const int k = k0 + wk * 32 + j * 16 + li;
-        if (n < N && k < K) atomicAdd(out + (size_t)n * ldo + k, acc[i][j][r]);
-      }
-}
-
-// The same product for fp32 operands at the matrix pipe's fp32 rate (v_mfma_f32_32x32x2_f32: 256 FLOP per clock and CU).
-// The kernel above stages 64 x 64 tiles element by element under a bounds test and ran the fp32 mode's 28 filter-gradient
-// GEMMs per training step at 24 TFLOP/s -- 5.7 ms of a 10.5 ms step, on the side stream that bounds it.  Here: TN x TK
-// output tile (64 or 128 each: one wave per 64 x 64), both operands in 16-row stages through LDS as 16-byte pieces, the
-// next stage's loads in flight under the current stage's products (registers -> the other LDS buffer, one barrier per
-// stage).  Both operands are reduction-major in memory, which is what the 32x32x2 fragments want: lane l reads element
-// [m + (l >> 5)][base + (l & 31)] -- 32 consecutive floats per half wave.  N % TN == K % TK == 0 (the launcher picks).
-template <int TN, int TK>
-__global__ __launch_bounds__(64 * (TN / 64) * (TK / 64)) void wgrad_f32_kernel(const float* __restrict__ D,
-                                                                                const float* __restrict__ A,
-                                                                                float* __restrict__ out, int M, int N, int K,
-                                                                                int ldo, int mslice, float* __restrict__ cs) {
-  // cs != nullptr: cs[n] += sum_m D[m][n] as well (the bias gradient beside the filter gradient): the workgroups of the
-  // first k-tile column add up the D rows they stage anyway -- was a launch of its own reading D once more (fp32 mode:
-  // 32 launches, 1.9 ms of kernel time per training step)
-  constexpr int WK = TK / 64, NTH = 64 * (TN / 64) * WK, TM = 16;
-  constexpr int DV = TM * TN / 4, AV = TM * TK / 4;                 // 16-byte pieces per stage
-  constexpr int DPT = (DV + NTH - 1) / NTH, APT = (AV + NTH - 1) / NTH;
-  static_assert(DV % NTH == 0 && AV % NTH == 0, "whole pieces per thread");
-  __shared__ __attribute__((aligned(16))) float Ds[2][TM * TN];
-  __shared__ __attribute__((aligned(16))) float As[2][TM * TK];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wn = wave / WK, wk = wave - wn * WK;
-  const int n0 = blockIdx.x * TN, k0 = blockIdx.y * TK;
-  const int mbeg = blockIdx.z * mslice, mend = min(M, mbeg + mslice);
-  const int l31 = lane & 31, lh = lane >> 5;
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  float4 dr[DPT], ar[APT];
-  const bool do_cs = cs != nullptr && blockIdx.y == 0;   // (uniform)
-  float4 csum = make_float4(0.f, 0.f, 0.f, 0.f);         // this thread's columns 4 (tid % (TN / 4)) .. + 3, its rows
-  static_assert(NTH % (TN / 4) == 0, "a thread's pieces share their columns");
-  auto fetch = [&](int m0) {
-#pragma unroll
-    for (int u = 0; u < DPT; ++u) {
-      const int i = tid + u * NTH, r = i / (TN / 4), c = i - r * (TN / 4);
-      dr[u] = m0 + r < mend ? *reinterpret_cast<const float4*>(D + (size_t)(m0 + r) * N + n0 + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int u = 0; u < APT; ++u) {
-      const int i = tid + u * NTH, r = i / (TK / 4), c = i - r * (TK / 4);
-      ar[u] = m0 + r < mend ? *reinterpret_cast<const float4*>(A + (size_t)(m0 + r) * K + k0 + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  auto park = [&](int buf) {
-#pragma unroll
-    for (int u = 0; u < DPT; ++u) {
-      reinterpret_cast<float4*>(Ds[buf])[tid + u * NTH] = dr[u];
-      if (do_cs) {
-        csum.x += dr[u].x;
-        csum.y += dr[u].y;
-        csum.z += dr[u].z;
-        csum.w += dr[u].w;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < APT; ++u) reinterpret_cast<float4*>(As[buf])[tid + u * NTH] = ar[u];
-  };
-  if (mbeg < mend) {
-    fetch(mbeg);
-    park(0);
-  }
-  __syncthreads();
-  int buf = 0;
-  for (int m0 = mbeg; m0 < mend; m0 += TM) {
-    const bool more = m0 + TM < mend;   // (uniform)
-    if (more) fetch(m0 + TM);
-    const float* ds = Ds[buf] + wn * 64 + l31;
-    const float* as = As[buf] + wk * 64 + l31;
-#pragma unroll
-    for (int ms = 0; ms < TM; ms += 2) {
-      float af[2], bf[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        af[t] = ds[(ms + lh) * TN + 32 * t];
-        bf[t] = as[(ms + lh) * TK + 32 * t];
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bf[j], acc[i][j], 0, 0, 0);
-    }
-    if (more) park(buf ^ 1);
-    __syncthreads();
-    buf ^= 1;
-  }
-  // C/D layout of 32x32: column (lane & 31) -> k, register r -> row (r & 3) + 8 (r >> 2) + 4 (lane >> 5) -> n
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int n = n0 + wn * 64 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const int k = k0 + wk * 64 + 32 * j + l31;
-        atomicAdd(out + (size_t)n * ldo + k, acc[i][j][r]);
-      }
-  if (do_cs) {   // the row groups' column sums meet in LDS (the operand stages are dead: the loop ended on a barrier)
-    constexpr int CG = TN / 4, RG = NTH / CG;
-    float4* red = reinterpret_cast<float4*>(Ds[0]);
-    static_assert(RG * CG * 16 <= (int)sizeof(Ds), "the partial sums fit the D stages");
-    red[tid] = csum;   // [row group = tid / CG][column group = tid % CG]
-    __syncthreads();
-    if (tid < CG) {
-      float4 t = red[tid];
-#pragma unroll
-      for (int g = 1; g < RG; ++g) {
-        const float4 e = red[g * CG + tid];
-        t.x += e.x;
-        t.y += e.y;
-        t.z += e.z;
-        t.w += e.w;
-      }
-      float* d = cs + n0 + 4 * tid;
-      atomicAdd(d, t.x);
-      atomicAdd(d + 1, t.y);
-      atomicAdd(d + 2, t.z);
-      atomicAdd(d + 3, t.w);
-    }
-  }
-}
-
-// out[n] += sum_m in[m][n].  Block = 64 columns x 4 row groups over one slice of M; the row groups
-// meet in LDS so that every column costs ONE atomic per block (same-address atomics serialise).
-template <typename T>
-__global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ in, float* out, int M,
-                                                     int N, int mslice, float* part) {
-  __shared__ float sh[4][64];
-  const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
-  const int n = blockIdx.x * 64 + cl;
-  const int mbeg = blockIdx.y * mslice, mend = min(M, mbeg + mslice);
-  float s0 = 0.f, s1 = 0.f;
-  if (n < N) {
-    int m = mbeg + rg;
-    for (; m + 4 < mend; m += 8) {
-      s0 += (float)in[(size_t)m * N + n];
-      s1 += (float)in[(size_t)(m + 4) * N + n];
-    }
-    if (m < mend) s0 += (float)in[(size_t)m * N + n];
-  }
-  sh[rg][cl] = s0 + s1;
-  __syncthreads();
-  if (rg == 0 && n < N) det_add(out + n, sh[0][cl] + sh[1][cl] + sh[2][cl] + sh[3][cl], part, (size_t)blockIdx.y * N + n);
-}
-
-// out[m][c] = (T)(in[m][c] * scale[c])   (scale may be null)
-template <typename T>
-__global__ __launch_bounds__(256) void scale_cast_kernel(const float* __restrict__ in,
-                                                         const float* __restrict__ scale,
-                                                         T* __restrict__ out, long n, int C) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
-    out[i] = (T)(in[i] * (scale != nullptr ? scale[i % C] : 1.f));
-}
-
-// out[r][c] = (T)(in[r][c] * rowscale[r])
-template <typename T>
-__global__ __launch_bounds__(256) void rowscale_cast_kernel(const float* __restrict__ in,
-                                                            const float* __restrict__ rowscale,
-                                                            T* __restrict__ out, long n, int cols) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
-    out[i] = (T)(in[i] * rowscale[i / cols]);
-}
 
 // fc2 weight/scale gradients from G = dy^T h:  dW2[c][k] = gamma[c] G[c][k];
 // dgamma[c] = sum_k W2[c][k] G[c][k] + b2[c] S[c];  db2[c] = gamma[c] S[c]    (S = colsum(dy))
@@ -688,271 +441,7 @@ __global__ __launch_bounds__(256) void dw_wgrad_kernel(const float* __restrict__
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void stem_im2col_kernel(const float* __restrict__ img,
-                                                          T* __restrict__ patches, int B) {
-  const long n = (long)B * 225 * 48;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const int k = (int)(i % 48);
-    const long r = i / 48;
-    const int p = (int)(r % 225), b = (int)(r / 225);
-    const int ci = k >> 4, ky = (k >> 2) & 3, kx = k & 3;
-    const int py = p / 15, px = p - py * 15;
-    patches[i] = (T)img[((size_t)b * 3 + ci) * 3969 + (4 * py + ky) * 63 + 4 * px + kx];
-  }
-}
-
-inline int gridn(long n) {
-  long b = (n + 255) / 256;
-  return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
-}
-
-template <typename T>
-int wgrad_t(const void* D, const void* A, float* out, int M, int N, int K, int ldo,
-            hipStream_t st) {
-  // slices of the reduction: enough workgroups to fill the chip, at least 512 rows each
-  const int tiles = ((N + 63) / 64) * ((K + 63) / 64);
-  int nsl = (1024 + tiles - 1) / tiles;
-  if (nsl > (M + 511) / 512) nsl = (M + 511) / 512;
-  if (nsl < 1) nsl = 1;
-  int mslice = ((M + nsl - 1) / nsl + 63) / 64 * 64;
-  nsl = (M + mslice - 1) / mslice;
-  dim3 grid((N + 63) / 64, (K + 63) / 64, nsl);
-  hipLaunchKernelGGL(wgrad_kernel<T>, grid, dim3(256), 0, st, reinterpret_cast<const T*>(D),
-                     reinterpret_cast<const T*>(A), out, M, N, K, ldo, mslice);
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
-}
-
-template <int TN, int TK>
-int wgrad_f32_launch(const float* D, const float* A, float* out, int M, int N, int K, int ldo, hipStream_t st, float* cs) {
-  // slices of the reduction: ~768 workgroups (two or three per CU), at least 256 rows each
-  const int tiles = (N / TN) * (K / TK);
-  int nsl = (768 + tiles - 1) / tiles;
-  if (nsl > (M + 255) / 256) nsl = (M + 255) / 256;
-  if (nsl < 1) nsl = 1;
-  const int mslice = ((M + nsl - 1) / nsl + 15) / 16 * 16;
-  nsl = (M + mslice - 1) / mslice;
-  hipLaunchKernelGGL((wgrad_f32_kernel<TN, TK>), dim3(N / TN, K / TK, nsl), dim3(64 * (TN / 64) * (TK / 64)), 0, st, D, A, out, M, N,
-                     K, ldo, mslice, cs);
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
-}
-
-// fp32: the matrix-pipe kernel where the shapes allow it; *cs_done says whether the column sums went along
-int wgrad_f32(const void* Dv, const void* Av, float* out, int M, int N, int K, int ldo, hipStream_t st, float* cs, bool* cs_done) {
-  const float* D = reinterpret_cast<const float*>(Dv);
-  const float* A = reinterpret_cast<const float*>(Av);
-  if (cs_done != nullptr) *cs_done = false;
-  static const bool old_form = switch_on(SW_WGRAD_F32_OLD);   // 1: the 64 x 64 kernel for every shape (A/B timing, parity)
-  const bool aligned = ((reinterpret_cast<uintptr_t>(D) | reinterpret_cast<uintptr_t>(A)) & 15) == 0;
-  if (!old_form && aligned && N % 64 == 0 && K % 64 == 0) {
-    // (deterministic mode: the column sums keep their own launch with its fixed-order reduction)
-    float* csk = cs != nullptr && cs_done != nullptr && det_alloc(0) == nullptr ? cs : nullptr;
-    if (csk != nullptr) *cs_done = true;
-    const bool n128 = N % 128 == 0, k128 = K % 128 == 0;
-    if (n128 && k128) return wgrad_f32_launch<128, 128>(D, A, out, M, N, K, ldo, st, csk);
-    if (n128) return wgrad_f32_launch<128, 64>(D, A, out, M, N, K, ldo, st, csk);
-    if (k128) return wgrad_f32_launch<64, 128>(D, A, out, M, N, K, ldo, st, csk);
-    return wgrad_f32_launch<64, 64>(D, A, out, M, N, K, ldo, st, csk);
-  }
-  const int tiles = ((N + 63) / 64) * ((K + 63) / 64);
-  int nsl = (1024 + tiles - 1) / tiles;
-  if (nsl > (M + 511) / 512) nsl = (M + 511) / 512;
-  if (nsl < 1) nsl = 1;
-  int mslice = ((M + nsl - 1) / nsl + 63) / 64 * 64;
-  nsl = (M + mslice - 1) / mslice;
-  dim3 grid((N + 63) / 64, (K + 63) / 64, nsl);
-  hipLaunchKernelGGL(wgrad_kernel<float>, grid, dim3(256), 0, st, D, A, out, M, N, K, ldo, mslice);
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
-}
-template <>
-int wgrad_t<float>(const void* D, const void* A, float* out, int M, int N, int K, int ldo, hipStream_t st) {
-  return wgrad_f32(D, A, out, M, N, K, ldo, st, nullptr, nullptr);
-}
-
-template <typename T>
-int colsum_t(const void* in, float* out, int M, int N, hipStream_t st) {
-  const int nb = (N + 63) / 64;
-  int nsl = (768 + nb - 1) / nb;                 // ~768 blocks in flight
-  if (nsl > 64) nsl = 64;                        // ... but at most 64 atomics per column
-  if (nsl > (M + 63) / 64) nsl = (M + 63) / 64;
-  if (nsl < 1) nsl = 1;
-  const int mslice = (M + nsl - 1) / nsl;
-  dim3 grid(nb, (M + mslice - 1) / mslice);
-  float* part = det_alloc((size_t)grid.y * N);
-  hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(256), 0, st, reinterpret_cast<const T*>(in), out,
-                     M, N, mslice, part);
-  LAUNCH_CHECK();
-  if (part != nullptr) {
-    const DetOut o{out, 1};
-    return launch_det_reduce(part, (int)grid.y, N, 1, &o, st);
-  }
-  return BTSBOT_OK;
-}
-
 }  // namespace
-
-#define BY_PREC(prec, CALL_F32, CALL_BF16, CALL_F16)            \
-  switch (prec) {                                               \
-    case BTSBOT_F32: return CALL_F32;                           \
-    case BTSBOT_BF16: return CALL_BF16;                         \
-    case BTSBOT_F16: return CALL_F16;                           \
-  }                                                             \
-  btsbot_set_error("backward: bad precision %d", prec);         \
-  return BTSBOT_ERR_INVALID_ARG;
-
-// fp32 operands: filter gradient and (cs != nullptr) the column sums of D, in one launch where the matrix-pipe kernel applies
-int launch_wgrad_cs_f32(const float* D, const float* A, float* out, float* cs, int M, int N, int K, int ldo, hipStream_t st) {
-  if (M <= 0) return BTSBOT_OK;
-  bool done = false;
-  const int rc = wgrad_f32(D, A, out, M, N, K, ldo, st, cs, &done);
-  if (rc != BTSBOT_OK || cs == nullptr || done) return rc;
-  return launch_colsum(BTSBOT_F32, D, cs, M, N, st);
-}
-
-int launch_wgrad(int prec, const void* D, const void* A, float* out, int M, int N, int K, int ldo,
-                 hipStream_t st) {
-  if (M <= 0) return BTSBOT_OK;
-  BY_PREC(prec, wgrad_t<float>(D, A, out, M, N, K, ldo, st),
-          wgrad_t<bf16_t>(D, A, out, M, N, K, ldo, st), wgrad_t<f16_t>(D, A, out, M, N, K, ldo, st))
-}
-
-// ---- deterministic mode: the scratch of the running backward call (thread-local: launchers run on the caller's thread)
-namespace {
-thread_local float* g_det_base = nullptr;
-thread_local size_t g_det_cap = 0, g_det_used = 0;
-thread_local bool g_det_short = false;   // a request did not fit the scratch: that reduction fell back to atomics
-
-// 32 columns x 8 row groups per workgroup: group q adds rows q, q + 8, ... in order, the groups meet in LDS in order
-__global__ __launch_bounds__(256) void det_reduce_kernel(const float* __restrict__ part, int nrows, int C, int W,
-                                                         DetOut o0, DetOut o1, DetOut o2, DetOut o3) {
-  __shared__ float sh[8][32];
-  const int cl = threadIdx.x & 31, q = threadIdx.x >> 5;
-  const int col = blockIdx.x * 32 + cl;
-  float s = 0.f;
-  if (col < W)
-    for (int r = q; r < nrows; r += 8) s += part[(size_t)r * W + col];
-  sh[q][cl] = s;
-  __syncthreads();
-  if (q == 0 && col < W) {
-    float t = sh[0][cl];
-#pragma unroll
-    for (int i = 1; i < 8; ++i) t += sh[i][cl];
-    const int o = col / C, c = col - o * C;
-    const DetOut d = o == 0 ? o0 : o == 1 ? o1 : o == 2 ? o2 : o3;
-    d.ptr[(size_t)c * d.stride] += t;
-  }
-}
-}  // namespace
-
-void det_begin(float* base, size_t floats) {
-  g_det_base = base;
-  g_det_cap = base != nullptr ? floats : 0;
-  g_det_used = 0;
-}
-void det_end() { det_begin(nullptr, 0); }
-bool det_fell_short() {   // since the last call: did any reduction of this thread's backward not fit the scratch?
-  const bool v = g_det_short;
-  g_det_short = false;
-  return v;
-}
-float* det_alloc(size_t floats) {
-  if (g_det_base == nullptr) return nullptr;
-  if (g_det_used + floats > g_det_cap) {
-    g_det_short = true;
-    return nullptr;
-  }
-  float* p = g_det_base + g_det_used;
-  g_det_used += (floats + 63) / 64 * 64;
-  return p;
-}
-int launch_det_reduce(const float* part, int nrows, int C, int nout, const DetOut* outs, hipStream_t st) {
-  if (nout < 1 || nout > 4) {
-    btsbot_set_error("det_reduce: %d outputs", nout);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  const int W = nout * C;
-  DetOut o[4] = {outs[0], outs[0], outs[0], outs[0]};
-  for (int i = 0; i < nout; ++i) o[i] = outs[i];
-  hipLaunchKernelGGL(det_reduce_kernel, dim3((W + 31) / 32), dim3(256), 0, st, part, nrows, C, W, o[0], o[1], o[2], o[3]);
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
-}
-
-int launch_colsum(int prec, const void* in, float* out, int M, int N, hipStream_t st) {
-  if (M <= 0) return BTSBOT_OK;
-  BY_PREC(prec, colsum_t<float>(in, out, M, N, st), colsum_t<bf16_t>(in, out, M, N, st),
-          colsum_t<f16_t>(in, out, M, N, st))
-}
-
-int launch_scale_cast(int prec, const float* in, const float* scale, void* out, long n, int C,
-                      hipStream_t st) {
-  if (n <= 0) return BTSBOT_OK;
-  switch (prec) {
-    case BTSBOT_F32:
-      hipLaunchKernelGGL(scale_cast_kernel<float>, dim3(gridn(n)), dim3(256), 0, st, in, scale,
-                         reinterpret_cast<float*>(out), n, C);
-      break;
-    case BTSBOT_BF16:
-      hipLaunchKernelGGL(scale_cast_kernel<bf16_t>, dim3(gridn(n)), dim3(256), 0, st, in, scale,
-                         reinterpret_cast<bf16_t*>(out), n, C);
-      break;
-    case BTSBOT_F16:
-      hipLaunchKernelGGL(scale_cast_kernel<f16_t>, dim3(gridn(n)), dim3(256), 0, st, in, scale,
-                         reinterpret_cast<f16_t*>(out), n, C);
-      break;
-    default:
-      btsbot_set_error("scale_cast: bad precision %d", prec);
-      return BTSBOT_ERR_INVALID_ARG;
-  }
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
-}
-
-__global__ __launch_bounds__(256) void rowscale_cast_lo_kernel(const float* __restrict__ in, const float* __restrict__ rowscale,
-                                                              f16_t* __restrict__ out, long n, int cols) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float v = rowscale != nullptr ? in[i] * rowscale[i / cols] : in[i];
-  const f16_t hi = (f16_t)v;
-  out[i] = (f16_t)(v - (float)hi);
-}
-
-int launch_rowscale_cast_lo(const float* in, const float* rowscale, void* out, int rows, int cols, hipStream_t st) {
-  const long n = (long)rows * cols;
-  if (n <= 0) return BTSBOT_OK;
-  hipLaunchKernelGGL(rowscale_cast_lo_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in, rowscale,
-                     reinterpret_cast<f16_t*>(out), n, cols);
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
-}
-
-int launch_rowscale_cast(int prec, const float* in, const float* rowscale, void* out, int rows,
-                         int cols, hipStream_t st) {
-  const long n = (long)rows * cols;
-  if (n <= 0) return BTSBOT_OK;
-  switch (prec) {
-    case BTSBOT_F32:
-      hipLaunchKernelGGL(rowscale_cast_kernel<float>, dim3(gridn(n)), dim3(256), 0, st, in, rowscale,
-                         reinterpret_cast<float*>(out), n, cols);
-      break;
-    case BTSBOT_BF16:
-      hipLaunchKernelGGL(rowscale_cast_kernel<bf16_t>, dim3(gridn(n)), dim3(256), 0, st, in, rowscale,
-                         reinterpret_cast<bf16_t*>(out), n, cols);
-      break;
-    case BTSBOT_F16:
-      hipLaunchKernelGGL(rowscale_cast_kernel<f16_t>, dim3(gridn(n)), dim3(256), 0, st, in, rowscale,
-                         reinterpret_cast<f16_t*>(out), n, cols);
-      break;
-    default:
-      btsbot_set_error("rowscale_cast: bad precision %d", prec);
-      return BTSBOT_ERR_INVALID_ARG;
-  }
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
-}
 
 int launch_fc2_grads(float* G, float* S, const float* w2, const float* b2,
                      const float* gamma, float* dW2, float* db2, float* dgamma, int C, int H,
@@ -1217,29 +706,5 @@ int launch_dw_wgrad(const float* x, const float* dd, float* dw, float* dbias, fl
   }
 #undef DWW
   LAUNCH_CHECK();
-  return colsum_t<float>(partials, dw, grid * (C < 256 ? 256 / C : 1), 50 * C, st);
-}
-
-int launch_stem_im2col(int prec, const float* img, void* patches, int B, hipStream_t st) {
-  const long n = (long)B * 225 * 48;
-  if (n <= 0) return BTSBOT_OK;
-  switch (prec) {
-    case BTSBOT_F32:
-      hipLaunchKernelGGL(stem_im2col_kernel<float>, dim3(gridn(n)), dim3(256), 0, st, img,
-                         reinterpret_cast<float*>(patches), B);
-      break;
-    case BTSBOT_BF16:
-      hipLaunchKernelGGL(stem_im2col_kernel<bf16_t>, dim3(gridn(n)), dim3(256), 0, st, img,
-                         reinterpret_cast<bf16_t*>(patches), B);
-      break;
-    case BTSBOT_F16:
-      hipLaunchKernelGGL(stem_im2col_kernel<f16_t>, dim3(gridn(n)), dim3(256), 0, st, img,
-                         reinterpret_cast<f16_t*>(patches), B);
-      break;
-    default:
-      btsbot_set_error("stem_im2col: bad precision %d", prec);
-      return BTSBOT_ERR_INVALID_ARG;
-  }
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
+  return launch_colsum(BTSBOT_F32, partials, dw, grid * (C < 256 ? 256 / C : 1), 50 * C, st);
 }

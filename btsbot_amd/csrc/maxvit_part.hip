@@ -38,7 +38,7 @@ namespace {
 constexpr int NB = 4;
 
 // sum over the wave's four 16-lane rows (the lanes that share lane & 15); every lane ends with the total.  The rows meet
-// through v_permlane16_swap / v_permlane32_swap as in common.h's wave_sum (inline asm for the reason given there).
+// through v_permlane16_swap / v_permlane32_swap as in device_math.h's wave_sum (inline asm for the reason given there).
 __device__ __forceinline__ float rows_sum(float v) {
   float w = v;
   asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(v), "+v"(w));

@@ -7,7 +7,7 @@
 //
 // An fp32 engine of its own, whatever the handle's operand mode: activations are fp32 NHWC rows [B*H*H][C]; every
 // 1x1 convolution / Linear runs on the exact-fp32 MFMA GEMM (gemm.hip), its input gradient on the same GEMM against
-// the transposed filter, its filter gradient on backward.hip's split-K GEMM; what has no GEMM shape (BatchNorm
+// the transposed filter, its filter gradient on wgrad_f32.hip's split-K GEMM; what has no GEMM shape (BatchNorm
 // statistics, depthwise 3x3, squeeze-excite, attention inside a 49-token partition) is a small kernel here.  It is
 // correctness-first -- one launch per layer, every intermediate through HBM (~110 MB of cache per alert) -- and
 // says so in DESIGN.md: configs[2], the training benchmark, is ConvNeXt.

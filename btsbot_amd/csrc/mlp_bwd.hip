@@ -64,7 +64,7 @@ template <typename T> struct MB : MfmaRaw<T> {
   static __device__ __forceinline__ short cvt(float v) { return __builtin_bit_cast(short, (T)v); }
 };
 
-// gelu_poly and its derivative from one exponential (common.h: gelu_poly / gelu_poly_grad)
+// gelu_poly and its derivative from one exponential (device_math.h: gelu_poly / gelu_poly_grad)
 template <int DEG> __device__ __forceinline__ void gelu_both(float x, float& g, float& gp) {
   const float a = __builtin_fabsf(x);
   const float e = __builtin_amdgcn_exp2f(gelu_q<DEG>(a));

@@ -1,7 +1,7 @@
 // The packed operand images of a ConvNeXt / metadata / fusion handle (btsbot_ctx::extra): image_walk() is the one list of
 // them, pack_layout() reserves their slots, pack_params() writes them (btsbot_pack_params / btsbot_pack_params_train).
-// Also the generic packing kernels: casts, transposes, the downsample re-orderings and the job table that runs them as
-// one launch.  The packers tied to one stage kernel's fragment layout live in that kernel's file.
+// Also the generic packing kernels: casts (plain, scaled per column or row, the stem's im2col), transposes, the downsample
+// re-orderings and the job table that runs them as one launch.  The packers tied to one stage kernel's fragment layout live in that kernel's file.
 // (A MaxViT image branch lays out and packs its own images: maxvit.hip.)
 #include "ctx.h"
 #include "head16.h"
@@ -116,7 +116,7 @@ __global__ void bn_fold_kernel(const float* w, const float* b, const float* rm, 
   }
 }
 
-// the five element maps above behind one launch: see PackJob in common.h
+// the five element maps above behind one launch: see PackJob in launchers.h
 template <typename T>
 __global__ __launch_bounds__(256) void pack_jobs_kernel(const PackJob* __restrict__ jobs, int njobs) {
   int lo = 0, hi = njobs - 1;
@@ -212,10 +212,65 @@ __global__ __launch_bounds__(256) void pack_jobs_kernel(const PackJob* __restric
   }
 }
 
+// ---- operand casts of the training step and of the packs with a scale folded in
+
+// out[m][c] = (T)(in[m][c] * scale[c])   (scale may be null)
+template <typename T>
+__global__ __launch_bounds__(256) void scale_cast_kernel(const float* __restrict__ in,
+                                                         const float* __restrict__ scale,
+                                                         T* __restrict__ out, long n, int C) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
+    out[i] = (T)(in[i] * (scale != nullptr ? scale[i % C] : 1.f));
+}
+
+// out[r][c] = (T)(in[r][c] * rowscale[r])
+template <typename T>
+__global__ __launch_bounds__(256) void rowscale_cast_kernel(const float* __restrict__ in,
+                                                            const float* __restrict__ rowscale,
+                                                            T* __restrict__ out, long n, int cols) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
+    out[i] = (T)(in[i] * rowscale[i / cols]);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void stem_im2col_kernel(const float* __restrict__ img,
+                                                          T* __restrict__ patches, int B) {
+  const long n = (long)B * 225 * 48;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const int k = (int)(i % 48);
+    const long r = i / 48;
+    const int p = (int)(r % 225), b = (int)(r / 225);
+    const int ci = k >> 4, ky = (k >> 2) & 3, kx = k & 3;
+    const int py = p / 15, px = p - py * 15;
+    patches[i] = (T)img[((size_t)b * 3 + ci) * 3969 + (4 * py + ky) * 63 + 4 * px + kx];
+  }
+}
+
 inline int nblocks(int64_t n) {
   int64_t b = (n + 255) / 256;
   return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
 }
+inline int gridn(long n) {   // (the casts above)
+  long b = (n + 255) / 256;
+  return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
+}
+
+// The by-precision ladder of the launchers below: launch(T* out) runs with `out` in the operand type of `prec`, and the
+// launch is checked; any other `prec` is the error "<who>: bad precision".
+template <typename Launch>
+int by_prec(int prec, const char* who, void* out, Launch launch) {
+  switch (prec) {
+    case BTSBOT_F32: launch(reinterpret_cast<float*>(out)); break;
+    case BTSBOT_BF16: launch(reinterpret_cast<bf16_t*>(out)); break;
+    case BTSBOT_F16: launch(reinterpret_cast<f16_t*>(out)); break;
+    default:
+      btsbot_set_error("%s: bad precision %d", who, prec);
+      return BTSBOT_ERR_INVALID_ARG;
+  }
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+template <typename P> using pointee = typename std::remove_pointer<P>::type;
 
 }  // namespace
 
@@ -227,22 +282,9 @@ int pack_job_blocks(const PackJob& j) {
 
 int launch_pack_jobs(int prec, const PackJob* dev_jobs, int njobs, int total_blocks, hipStream_t st) {
   if (njobs <= 0) return BTSBOT_OK;
-  switch (prec) {
-    case BTSBOT_F32:
-      hipLaunchKernelGGL(pack_jobs_kernel<float>, dim3(total_blocks), dim3(256), 0, st, dev_jobs, njobs);
-      break;
-    case BTSBOT_BF16:
-      hipLaunchKernelGGL(pack_jobs_kernel<bf16_t>, dim3(total_blocks), dim3(256), 0, st, dev_jobs, njobs);
-      break;
-    case BTSBOT_F16:
-      hipLaunchKernelGGL(pack_jobs_kernel<f16_t>, dim3(total_blocks), dim3(256), 0, st, dev_jobs, njobs);
-      break;
-    default:
-      btsbot_set_error("pack_jobs: bad precision %d", prec);
-      return BTSBOT_ERR_INVALID_ARG;
-  }
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
+  return by_prec(prec, "pack_jobs", nullptr, [&](auto* d) {   // (every job brings its own destination)
+    hipLaunchKernelGGL(pack_jobs_kernel<pointee<decltype(d)>>, dim3(total_blocks), dim3(256), 0, st, dev_jobs, njobs);
+  });
 }
 
 int launch_cast(int prec, const float* src, void* dst, int64_t n, hipStream_t st) {
@@ -284,25 +326,9 @@ int launch_transpose_f32(const float* src, float* dst, int R, int Cc, hipStream_
 
 int launch_pack_down(int prec, const float* src, void* dst, int Cout, int Cin, hipStream_t st) {
   const int64_t n = (int64_t)Cout * Cin * 4;
-  switch (prec) {
-    case BTSBOT_F32:
-      hipLaunchKernelGGL(pack_down_kernel<float>, dim3(nblocks(n)), dim3(256), 0, st, src,
-                         reinterpret_cast<float*>(dst), Cout, Cin);
-      break;
-    case BTSBOT_BF16:
-      hipLaunchKernelGGL(pack_down_kernel<bf16_t>, dim3(nblocks(n)), dim3(256), 0, st, src,
-                         reinterpret_cast<bf16_t*>(dst), Cout, Cin);
-      break;
-    case BTSBOT_F16:
-      hipLaunchKernelGGL(pack_down_kernel<f16_t>, dim3(nblocks(n)), dim3(256), 0, st, src,
-                         reinterpret_cast<f16_t*>(dst), Cout, Cin);
-      break;
-    default:
-      btsbot_set_error("pack_down: bad precision %d", prec);
-      return BTSBOT_ERR_INVALID_ARG;
-  }
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
+  return by_prec(prec, "pack_down", dst, [&](auto* d) {
+    hipLaunchKernelGGL(pack_down_kernel<pointee<decltype(d)>>, dim3(nblocks(n)), dim3(256), 0, st, src, d, Cout, Cin);
+  });
 }
 
 int launch_pack_down_split(const float* src, void* hi, void* lo, int Cout, int Cin, hipStream_t st) {
@@ -325,25 +351,52 @@ int launch_bn_fold(const float* w, const float* b, const float* rm, const float*
 int launch_transpose_cast(int prec, const float* src, const float* rowscale, void* dst, int R, int Cc,
                           hipStream_t st) {
   const int64_t n = (int64_t)R * Cc;
-  switch (prec) {
-    case BTSBOT_F32:
-      hipLaunchKernelGGL(transpose_cast_kernel<float>, dim3(nblocks(n)), dim3(256), 0, st, src,
-                         rowscale, reinterpret_cast<float*>(dst), R, Cc);
-      break;
-    case BTSBOT_BF16:
-      hipLaunchKernelGGL(transpose_cast_kernel<bf16_t>, dim3(nblocks(n)), dim3(256), 0, st, src,
-                         rowscale, reinterpret_cast<bf16_t*>(dst), R, Cc);
-      break;
-    case BTSBOT_F16:
-      hipLaunchKernelGGL(transpose_cast_kernel<f16_t>, dim3(nblocks(n)), dim3(256), 0, st, src,
-                         rowscale, reinterpret_cast<f16_t*>(dst), R, Cc);
-      break;
-    default:
-      btsbot_set_error("transpose_cast: bad precision %d", prec);
-      return BTSBOT_ERR_INVALID_ARG;
-  }
+  return by_prec(prec, "transpose_cast", dst, [&](auto* d) {
+    hipLaunchKernelGGL(transpose_cast_kernel<pointee<decltype(d)>>, dim3(nblocks(n)), dim3(256), 0, st, src, rowscale, d, R, Cc);
+  });
+}
+
+int launch_scale_cast(int prec, const float* in, const float* scale, void* out, long n, int C,
+                      hipStream_t st) {
+  if (n <= 0) return BTSBOT_OK;
+  return by_prec(prec, "scale_cast", out, [&](auto* o) {
+    hipLaunchKernelGGL(scale_cast_kernel<pointee<decltype(o)>>, dim3(gridn(n)), dim3(256), 0, st, in, scale, o, n, C);
+  });
+}
+
+int launch_rowscale_cast(int prec, const float* in, const float* rowscale, void* out, int rows,
+                         int cols, hipStream_t st) {
+  const long n = (long)rows * cols;
+  if (n <= 0) return BTSBOT_OK;
+  return by_prec(prec, "rowscale_cast", out, [&](auto* o) {
+    hipLaunchKernelGGL(rowscale_cast_kernel<pointee<decltype(o)>>, dim3(gridn(n)), dim3(256), 0, st, in, rowscale, o, n, cols);
+  });
+}
+
+__global__ __launch_bounds__(256) void rowscale_cast_lo_kernel(const float* __restrict__ in, const float* __restrict__ rowscale,
+                                                              f16_t* __restrict__ out, long n, int cols) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float v = rowscale != nullptr ? in[i] * rowscale[i / cols] : in[i];
+  const f16_t hi = (f16_t)v;
+  out[i] = (f16_t)(v - (float)hi);
+}
+
+int launch_rowscale_cast_lo(const float* in, const float* rowscale, void* out, int rows, int cols, hipStream_t st) {
+  const long n = (long)rows * cols;
+  if (n <= 0) return BTSBOT_OK;
+  hipLaunchKernelGGL(rowscale_cast_lo_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in, rowscale,
+                     reinterpret_cast<f16_t*>(out), n, cols);
   LAUNCH_CHECK();
   return BTSBOT_OK;
+}
+
+int launch_stem_im2col(int prec, const float* img, void* patches, int B, hipStream_t st) {
+  const long n = (long)B * 225 * 48;
+  if (n <= 0) return BTSBOT_OK;
+  return by_prec(prec, "stem_im2col", patches, [&](auto* p) {
+    hipLaunchKernelGGL(stem_im2col_kernel<pointee<decltype(p)>>, dim3(gridn(n)), dim3(256), 0, st, img, p, B);
+  });
 }
 
 int launch_unpack_down_grad(float* Gd, float* dst, int Cout, int Cin, hipStream_t st) {
@@ -355,25 +408,9 @@ int launch_unpack_down_grad(float* Gd, float* dst, int Cout, int Cin, hipStream_
 
 int launch_pack_down_t(int prec, const float* src, void* dst, int Cout, int Cin, hipStream_t st) {
   const int64_t n = (int64_t)Cout * Cin * 4;
-  switch (prec) {
-    case BTSBOT_F32:
-      hipLaunchKernelGGL(pack_down_t_kernel<float>, dim3(nblocks(n)), dim3(256), 0, st, src,
-                         reinterpret_cast<float*>(dst), Cout, Cin);
-      break;
-    case BTSBOT_BF16:
-      hipLaunchKernelGGL(pack_down_t_kernel<bf16_t>, dim3(nblocks(n)), dim3(256), 0, st, src,
-                         reinterpret_cast<bf16_t*>(dst), Cout, Cin);
-      break;
-    case BTSBOT_F16:
-      hipLaunchKernelGGL(pack_down_t_kernel<f16_t>, dim3(nblocks(n)), dim3(256), 0, st, src,
-                         reinterpret_cast<f16_t*>(dst), Cout, Cin);
-      break;
-    default:
-      btsbot_set_error("pack_down_t: bad precision %d", prec);
-      return BTSBOT_ERR_INVALID_ARG;
-  }
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
+  return by_prec(prec, "pack_down_t", dst, [&](auto* d) {
+    hipLaunchKernelGGL(pack_down_t_kernel<pointee<decltype(d)>>, dim3(nblocks(n)), dim3(256), 0, st, src, d, Cout, Cin);
+  });
 }
 
 // ---------------------------------------------------------------------------------------

@@ -14,7 +14,7 @@ extern "C" int btsbot_reserve_train(btsbot_handle h, int max_batch, int with_ima
   // (MaxViT: with_image_grads = 1 trains the branch -- BatchNorm2d batch statistics, maxvit_train.hip; = 0 serves heads
   //  over a frozen, eval-mode branch with the inference kernels)
   const bool want_bb = with_image_grads && h->has_image;
-  if (h->sched.deterministic) {   // partial rows of the batch reductions (common.h: det_add), sized by the batch: 256 KB per alert,
+  if (h->sched.deterministic) {   // partial rows of the batch reductions (device_math.h: det_add), sized by the batch: 256 KB per alert,
     const size_t want = std::max((size_t)16 << 20, (size_t)max_batch << 16);   // at least 64 MB (what a step of <= 256 alerts takes)
     if (h->det_scratch == nullptr || h->det_floats < want) {
       HIP_TRY(hipDeviceSynchronize());

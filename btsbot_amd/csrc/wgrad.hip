@@ -14,7 +14,7 @@
 // buffer, one barrier per 64-row tile: with 32-row tiles a tile's 8 MFMAs per wave hid a quarter of the load
 // latency, 64 rows took the isolated backward from 3.68 to 3.58 ms).  Slices leave as dense partial tiles which
 // wgrad_reduce_kernel adds in a fixed order (or, without scratch, meet in the output through fp32 atomics).
-// Replaces (with backward.hip) what autograd does for nn.Linear / 1x1 Conv2d weight gradients at
+// Replaces (with wgrad_f32.hip) what autograd does for nn.Linear / 1x1 Conv2d weight gradients at
 // /root/reference/btsbot/train.py:526.
 #include <stdlib.h>
 

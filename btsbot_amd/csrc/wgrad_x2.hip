@@ -4,7 +4,7 @@
 //
 // D = gradient w.r.t. the layer output [M pixels][N], A = the layer input [M][K], both fp32 and pixel-major (the
 // reduction index outermost), as the fp32 training schedule keeps them.  wgrad.hip's form for 16-bit operands with the
-// split of gemm_x2.hip in front: the fp32 tiles are read global -> registers as 16-byte vectors, D scaled by 2^e (common.h:
+// split of gemm_x2.hip in front: the fp32 tiles are read global -> registers as 16-byte vectors, D scaled by 2^e (device_math.h:
 // split_exp of its largest magnitude -- gradients are small and their heads would be f16 subnormals), split into f16
 // head and remainder images in LDS and read back with ds_read_b64_tr_b16, the transposing LDS read that hands a lane
 // eight reduction-consecutive values of one output row / column.  Each product is lo*hi + hi*lo + hi*hi on

@@ -491,7 +491,7 @@ int btsbot_op_mvt_gelu_fwd(const float* pre, float* out, int64_t n, void* stream
 int btsbot_op_mvt_gelu_bwd(const float* pre, float* d, int64_t n, void* stream);
 int btsbot_op_mvt_bcast_set(const float* v, float* d, int B, int P, int C, float scale, void* stream);
 
-/* The LayerNorm / depthwise backward kernels of the ConvNeXt TRAINING step (dwln_bwd.hip, backward.hip) one at a time.
+/* The LayerNorm / depthwise backward kernels of the ConvNeXt TRAINING step (dwln_bwd.hip, ln_dw_bwd.hip) one at a time.
  * Everything is fp32; activations are NHWC rows [B][HW*HW][C]; w = the depthwise taps [49][C] (tap-major, as the
  * engine packs conv_dw.weight); the LayerNorm eps is 1e-6.  Every call runs the launcher the training engine itself
  * runs (same kernels, same grid arithmetic) on the caller's stream, with a stream-ordered scratch of its own for the

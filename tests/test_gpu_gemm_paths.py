@@ -30,9 +30,9 @@ SUB = {"f32": 0.0, "bf16": 0.0, "f16": 2.0 ** -25}
 EPIS = ("gelu", "resid", "bias", "silu", "bias_t", "gelu_save", "dgelu", "plain")
 T_OUT = ("gelu", "silu", "bias_t", "gelu_save", "dgelu")     # outputs of the operand type; the others are fp32
 L_GELU, L_SILU = 1.13, 1.1            # max |gelu'| = 1.1289 (both fits match it), max |silu'| = 1.0998
-SILU_REL = 4e-6                       # silu_fast / silu_f: ~1e-6 relative claimed (common.h), held at 4x
+SILU_REL = 4e-6                       # silu_fast / silu_f: ~1e-6 relative claimed (device_math.h), held at 4x
 
-# ---- float64 ports of common.h's GELU for the 16-bit modes (gelu_q<3/5>, gelu_poly, gelu_dq, gelu_poly_grad)
+# ---- float64 ports of device_math.h's GELU for the 16-bit modes (gelu_q<3/5>, gelu_poly, gelu_dq, gelu_poly_grad)
 GELU_Q = {3: (-1.0036805164077327, -1.1287482669759885, -0.49926576060257244, -0.024772998623334343),
           5: (-1.000039487932206, -1.1507770495088248, -0.46001256950698816, -0.05181158088529847,
               0.007079169600613161, -0.0004726569791655389)}
@@ -365,6 +365,56 @@ def test_wgrad16_against_float64(cuda, prec, nk):
     print(f"[wgrad16 {prec} {N}x{K}] err/bound " + " ".join(f"{k}={v:.3g}" for k, v in worst.items()))
 
 
+# ---- fp32 filter gradient: one (N, K) per dispatch branch of wgrad_f32 (wgrad_f32.hip); `off`: d starts one float into
+# a larger buffer, so the 16-byte alignment test sends a 64-multiple shape to the fallback kernel
+WGRAD32_NK = [
+    (128, 128, 0),    # 128x128 tile
+    (128, 64, 0),     # 128x64 tile
+    (64, 128, 0),     # 64x128 tile
+    (64, 64, 0),      # 64x64 tile
+    (192, 192, 0),    # 64x64, several tiles
+    (64, 48, 0),      # fallback, the stem's K
+    (80, 320, 0),     # fallback, nano's widths
+    (64, 64, 1),      # fallback through the alignment test
+]
+# a sub-tile, both sides of the 16-row rounding, both sides of the 256-row minimum slice, several slices with a ragged last
+WGRAD32_M = (1, 15, 17, 255, 257, 1100)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nk", WGRAD32_NK, ids=[f"{n}x{k}" + ("-unaligned" if o else "") for n, k, o in WGRAD32_NK])
+def test_wgrad_f32_against_float64(cuda, nk):
+    """ops.wgrad on fp32 operands (the matrix-pipe kernel per tile shape, the 64x64 fallback kernel): out and colsum
+    accumulate onto non-zero starting values; colsum given (summed in the kernel on the matrix-pipe path, by the column
+    sum launch behind the fallback) and None.  Bound: the any-order fp32 sum of M products and of the starting value,
+    (M + 2) 2^-24 (|out0| + |D|^T |A|) and (M + 2) 2^-24 (|cs0| + sum |D|) -- whatever order the slices' atomics land in."""
+    N, K, off = nk
+    worst = {}
+    for M in WGRAD32_M:
+        g = torch.Generator(device=cuda).manual_seed(M + 7 * N + K + off)
+        dbuf = torch.randn(M * N + off, generator=g, device=cuda)
+        d = dbuf[off:].view(M, N)
+        a = torch.randn(M, K, generator=g, device=cuda)
+        out0 = torch.randn(N, K, generator=g, device=cuda)
+        cs0 = torch.randn(N, generator=g, device=cuda)
+        d64, a64 = d.double(), a.double()
+        ref = out0.double() + d64.t() @ a64
+        bound = (M + 2) * EPS * (out0.double().abs() + d64.abs().t() @ a64.abs())
+        for with_cs in (True, False):
+            obuf, out = _guarded(N * K, torch.float32, cuda, fill=out0)
+            cbuf, cs = _guarded(N, torch.float32, cuda, fill=cs0)
+            ops.wgrad(d, a, out=out.view(N, K), colsum=cs if with_cs else None, precision="f32")
+            tag = f"M={M}" + ("" if with_cs else " no-cs")
+            _check(f"out {tag}", out.view(N, K), ref, bound, worst)
+            if with_cs:
+                _check(f"colsum {tag}", cs, cs0.double() + d64.sum(0), (M + 2) * EPS * (cs0.double().abs() + d64.abs().sum(0)),
+                       worst)
+            assert _intact(obuf, N * K) and _intact(cbuf, N), f"{tag}: guard bytes changed"
+            del obuf, cbuf
+        del dbuf, d, a, d64, a64, ref, bound
+    print(f"[wgrad f32 {N}x{K}{' unaligned' if off else ''}] err/bound " + " ".join(f"{k}={v:.3g}" for k, v in worst.items()))
+
+
 @pytest.mark.gpu
 def test_wgrad16_refuses_what_it_cannot_run(cuda):
     d = torch.zeros(16, 24, dtype=torch.float16, device=cuda)
@@ -489,18 +539,19 @@ def test_gemm_resid_ln_against_float64(cuda, prec, case):
 @pytest.mark.gpu
 def test_process_wide_switches_in_a_child_process(cuda):
     """The switches read once per process -- BTSBOT_AMD_GEMM2_NO_PREFETCH (gemm2's RESID / DGELU epilogues load inside
-    their store loop), BTSBOT_AMD_GEMM2_NO_1SLOT (K = 64 runs the 2- / 3-slot rings) and BTSBOT_AMD_WGRAD_ATOMIC (the
-    filter-gradient slices meet through atomics) -- in ONE child running the gemm2 paths, the resid+LN form and the
-    f16 filter gradients."""
+    their store loop), BTSBOT_AMD_GEMM2_NO_1SLOT (K = 64 runs the 2- / 3-slot rings), BTSBOT_AMD_WGRAD_ATOMIC (the
+    filter-gradient slices meet through atomics) and BTSBOT_AMD_WGRAD_F32_OLD (the fp32 filter gradient's 64x64
+    fallback kernel for every shape) -- in ONE child running the gemm2 paths, the resid+LN form and the f16 and fp32
+    filter gradients."""
     import subprocess
     import sys
     if os.environ.get("BTSBOT_AMD_TEST_CHILD") == "1":
         pytest.skip("already the child")
     env = dict(os.environ, BTSBOT_AMD_TEST_CHILD="1", BTSBOT_AMD_GEMM2_NO_PREFETCH="1",
-               BTSBOT_AMD_GEMM2_NO_1SLOT="1", BTSBOT_AMD_WGRAD_ATOMIC="1")
+               BTSBOT_AMD_GEMM2_NO_1SLOT="1", BTSBOT_AMD_WGRAD_ATOMIC="1", BTSBOT_AMD_WGRAD_F32_OLD="1")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     pick = ("(tile_path_epilogues and (s1 or s2 or s3)) or resid_ln or "
-            "(wgrad16_against and f16 and not bf16)")
+            "(wgrad16_against and f16 and not bf16) or wgrad_f32_against")
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", "-k", pick,
                         "tests/test_gpu_gemm_paths.py"], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]

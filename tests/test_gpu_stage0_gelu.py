@@ -1,5 +1,5 @@
 """stage0b's bf16 inference form (btsbot_amd/csrc/stage0b.hip; stage 0 of an fp8 handle runs it too) hands fc2 its hidden
-activations as f16, from a GELU evaluated on packed f16 (csrc/common.h: gelu_pk), against an f16 image of gamma * W2.
+activations as f16, from a GELU evaluated on packed f16 (csrc/device_math.h: gelu_pk), against an f16 image of gamma * W2.
 
 (The f16 handle's inference form applies the same GELU; its rows are held by tests/test_gpu_stage0_ln.py and
 tests/test_gpu_parity.py at their unchanged bounds.)

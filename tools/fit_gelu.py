@@ -1,4 +1,4 @@
-"""Fit of the one-transcendental GELU of the 16-bit modes (btsbot_amd/csrc/common.h, gelu_poly):
+"""Fit of the one-transcendental GELU of the 16-bit modes (btsbot_amd/csrc/device_math.h, gelu_poly):
     gelu(x) = max(x, 0) - |x| 2^q(|x|),   q ~ log2 Phi(-a)
 minimising the largest |error| of gelu itself over [-12, 12].  Prints the coefficients per degree."""
 import numpy as np

@@ -2,7 +2,7 @@
 minimax exponent on v_pk_fma_f16, 2^q on v_exp_f16, max(x, 0) - |x| 2^q packed -- against what the f16 mode ships
 (degree-5 exponent in fp32, ONE rounding to f16 on the way to the fc2 operand).  Error of the hidden activation that
 reaches the matrix pipe, |x| <= 4, against the exact erf GELU.
-(Since built: csrc/common.h gelu_pk4, stage0b.hip's inference forms.  The kernel rounds the pair towards zero
+(Since built: csrc/device_math.h gelu_pk4, stage0b.hip's inference forms.  The kernel rounds the pair towards zero
 (v_cvt_pkrtz), this script to nearest; tests/test_gpu_stage0_gelu.py holds the emulation of what ships.)"""
 import math
 import numpy as np

@@ -94,7 +94,7 @@ __global__ __launch_bounds__(NW * 64, WPS) void mlp_kernel(float* out, int iters
 
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 
-// (the packed-f16 GELU, gelu_pk4(), is the library's: csrc/common.h)
+// (the packed-f16 GELU, gelu_pk4(), is the library's: csrc/device_math.h)
 
 // The lean loop: one column block per wave; nothing but the accumulators lives across a chunk -- the fc1 B operand is
 // re-read from LDS every chunk, filter fragments are read in groups of four right before their products

@@ -1,4 +1,4 @@
-// Unit check of common.h's cross-lane reductions on the device.
+// Unit check of device_math.h's cross-lane reductions on the device.
 #include "../../btsbot_amd/csrc/common.h"
 #include <cstdio>
 #include <vector>

@@ -51,6 +51,8 @@ from . import clusters
 from .clusters import dbscan, graph_components
 from . import quality
 from .quality import continuity, map_quality, trustworthiness
+from . import novelty
+from .novelty import NoveltyModel, kth_neighbor_distance, local_outlier_factor
 from . import layout
 from .layout import (EmbeddingMap, FuzzyGraph, embedding_layout, find_ab_params, fuzzy_graph, layout_transform,
                      optimize_layout, query_memberships)
@@ -68,6 +70,7 @@ __all__ = [
     "neighbors", "EmbeddingIndex", "embedding_neighbors", "knn_graph", "neighbor_vote",
     "radius_neighbors", "radius_graph", "neighbor_ranks", "quality", "trustworthiness", "continuity", "map_quality",
     "clusters", "graph_components", "dbscan", "mapindex", "MapIndex",
+    "novelty", "NoveltyModel", "local_outlier_factor", "kth_neighbor_distance",
     "layout", "FuzzyGraph", "fuzzy_graph", "optimize_layout", "embedding_layout", "find_ab_params",
     "EmbeddingMap", "layout_transform", "query_memberships",
     "splits", "SPLIT_NAMES", "SOURCE_SETS", "label_set", "split_labels", "subset_mask", "cuts_suffix",

@@ -56,7 +56,9 @@ SYMBOLS = [
     "btsbot_grid_finite", "btsbot_grid_cells", "btsbot_grid_radius_count", "btsbot_grid_radius_fill", "btsbot_grid_knn",
     "btsbot_layout_smooth_knn", "btsbot_layout_symmetrize_workspace", "btsbot_layout_symmetrize", "btsbot_layout_init",
     "btsbot_layout_epochs", "btsbot_layout_smooth_knn_query", "btsbot_layout_transform",
+    "btsbot_lof_fit", "btsbot_lof_score",
 ]
+LOF_MAX_K = 64                               # csrc/lof.hip
 LAYOUT_MAX_K, LAYOUT_MAX_NEGATIVES = 64, 64
 KNN_METRIC = {"euclidean": 0, "cosine": 1}   # enum btsbot_knn_metric
 KNN_MAX_DIM, KNN_MAX_K, KNN_MAX_SPLITS = 1024, 64, 32
@@ -333,6 +335,10 @@ def lib() -> C.CDLL:
     L.btsbot_layout_transform.restype = i32
     L.btsbot_layout_transform.argtypes = [vp, vp, vp, i64, i64, i32, vp, vp, i32, i32, i32, f32, f32, C.c_uint64, i32, f32, i32,
                                           vp]
+    L.btsbot_lof_fit.restype = i32
+    L.btsbot_lof_fit.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
+    L.btsbot_lof_score.restype = i32
+    L.btsbot_lof_score.argtypes = [vp, vp, i64, i32, vp, vp, i64, vp, vp, vp]
     L.btsbot_eval_metrics.restype = i32
     L.btsbot_eval_metrics.argtypes = [vp, vp, f32, i64, vp, vp]
     if L.btsbot_abi_version() != ABI_VERSION:

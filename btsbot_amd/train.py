@@ -324,6 +324,8 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
     the dict ``{"k": 15, "group_by": "objectId", "mode": "exclude"}`` the graph of ``knn_graph(..., groups=ids,
     group_mode=mode)``, ``ids = alert_utils.object_keys`` of that column (an error names a column the table lacks), and
     ``groups`` = these ids in the file.  ``config['embedding_layout']`` takes ``"group_by"`` likewise (``groups=ids``).
+    With ``config['embedding_novelty'] = k`` (or the same dict form) also ``{stem}_lof.npy``: float64 [N], the local
+    outlier factor of every row among the others (``novelty.local_outlier_factor(rows, k, groups=ids, group_mode=mode)``).
     With ``config['embedding_layout']`` (``True``, or a dict of ``embedding_layout`` keyword arguments; ``seed`` defaults
     to the run's ``random_seed``) also ``{stem}_umap.csv`` with the reference's columns ``umap_emb_1, umap_emb_2,
     candid`` (train.py:464): the 2-D map of the rows, in the candidate file's order.  With
@@ -378,6 +380,19 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
         if "candid" in cand.columns:
             extra["candid"] = cand["candid"].to_numpy()
         np.savez(stem + "_knn.npz", indices=idx.cpu().numpy(), distances=dist.cpu().numpy(), **extra)
+    nov = config.get("embedding_novelty")
+    if nov:   # opt-in: the local outlier factor of every row among the others ({stem}_lof.npy)
+        from .novelty import local_outlier_factor
+        kw = {}
+        if isinstance(nov, dict):   # {"k": 20, "group_by": "objectId", "mode": "exclude"}: a row's own object left out
+            unknown = set(nov) - {"k", "group_by", "mode"}
+            if unknown or "k" not in nov:
+                raise ValueError(f"config['embedding_novelty'] takes the keys k, group_by and mode, got {sorted(nov)}")
+            if nov.get("group_by") is not None:
+                kw = dict(groups=group_ids(nov["group_by"], "embedding_novelty"), group_mode=nov.get("mode", "exclude"))
+            nov = nov["k"]
+        lof = local_outlier_factor(torch.from_numpy(out).to(dev), int(nov), **kw)
+        np.save(stem + "_lof.npy", lof.cpu().numpy())
     lay = config.get("embedding_layout")
     clu = config.get("embedding_clusters")
     if clu:   # opt-in: DBSCAN of the map (a `cluster` column of the map's table) or of the rows ({stem}_clusters.npy)

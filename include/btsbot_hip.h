@@ -1100,6 +1100,37 @@ int btsbot_layout_transform(const int64_t* idx, const float* w, const float* ban
                             const float* y0, float* yout, int n_epochs, int first_epoch, int last_epoch, float a, float b,
                             uint64_t seed, int negative_sample_rate, float learning_rate, int blocks, void* stream);
 
+/* ---- local outlier factor on a kNN graph: novelty scores (csrc/lof.hip) ---- */
+
+/* Both are queued on `stream`; nothing allocates, synchronises or copies to the host.  An entry (row, c) is PRESENT when
+ * 0 <= idx[row][c] < n; a -1 tail is no entry and an index out of range is treated the same.  m(row) is the number of
+ * present entries.  All arithmetic is float64 on the fp32 distances converted once:
+ *   kdist(i)    = dist of row i's last present column                                      NaN when m = 0
+ *   reach(i, c) = fmax(dist[i][c], kdist(idx[i][c]))       (a NaN kdist leaves dist)
+ *   lrd(i)      = 1 / (sum_c reach(i, c) / m + 1e-10)      (scikit-learn's constant)       NaN when m = 0
+ *   lof(i)      = (sum_c lrd(idx[i][c]) / lrd(i)) / m      (each quotient formed first)    NaN when m = 0
+ * A sum runs over W slots, W = 16, 32 or 64 the smallest that holds k: slot c holds column c's term where the entry is
+ * present and +0.0 otherwise, then for o = W/2, ..., 1 every slot c takes v[c] + v[c ^ o]; the sum is slot 0.  The order
+ * depends on the row's own columns and k alone, so a row's result does not depend, bit for bit, on the other rows of the
+ * call, on the grid or on the run.  No fused multiply-add, IEEE divisions.
+ *
+ * btsbot_lof_fit(): idx int64 [n][k], dist fp32 [n][k] as btsbot_knn_query returns them for every bank row among the
+ * OTHERS (self_offset = 0; knn_graph(..., include_self=False)).  Writes kdist, lrd and lof, float64 [n] each; lof may be
+ * NULL (two launches instead of three).
+ *
+ * btsbot_lof_score(): idx / dist [q][k] of NEW rows against a fitted bank of n rows (no self column), bank_kdist and
+ * bank_lrd float64 [n] as btsbot_lof_fit wrote them.  The two formulas with kdist and lrd of the neighbours read from
+ * the bank's arrays (the new row has no kdist of its own); writes lof and, unless NULL, lrd, float64 [q] each.  One
+ * launch.
+ *
+ * BTSBOT_ERR_INVALID_ARG with a message, before any HIP call, for k outside 1..64, n or q outside 0..2^31 - 1, a NULL
+ * pointer (but the optional output; the bank's arrays where n = 0) or a misaligned one.  btsbot_lof_fit with n = 0 and
+ * btsbot_lof_score with q = 0 succeed without a launch; btsbot_lof_score with n = 0 writes NaN. */
+int btsbot_lof_fit(const int64_t* idx, const float* dist, int64_t n, int k, double* kdist, double* lrd, double* lof,
+                   void* stream);
+int btsbot_lof_score(const int64_t* idx, const float* dist, int64_t q, int k, const double* bank_kdist,
+                     const double* bank_lrd, int64_t n, double* lrd, double* lof, void* stream);
+
 /* Replaces: the epoch / validation metrics of val.py:159-168 and train.py:550-558 -- out2[0] += sum_i of
  * BCEWithLogitsLoss(pos_weight) terms over n logits, out2[1] += number of alerts whose sigmoid(z) > 0.5
  * agrees with the label (caller zeroes out2 and divides by n). */

@@ -1,0 +1,343 @@
+"""Clusters of any density: HDBSCAN on the exact searches, the spanning tree on the device.
+
+``dbscan(emb, eps)`` needs a radius nobody knows in advance, and one radius cannot serve an archive whose clumps differ
+in density by orders of magnitude.  HDBSCAN (Campello et al. 2013; scikit-learn's ``HDBSCAN``) takes ``min_cluster_size``
+alone (csrc/mst.hip, csrc/hdbscan_tree.hip):
+
+    labels, prob = hdbscan(emb, min_cluster_size=5)              # int64 [N] (-1: noise), float64 [N]
+    mst = mutual_reachability_mst(emb_or_index, min_samples)     # .edges int64 [n - 1, 2], .weights f32, .core f32 [N]
+    tree = ClusterTree(mst)                                      # one tree, any parameters afterwards
+    labels, prob = tree.labels(min_cluster_size, method="eom")
+    labels = tree.cut(eps, min_cluster_size=1)                   # DBSCAN* at any eps from the same tree
+
+``core(i)`` is the distance from row i to its ``(min_samples - 1)``-th nearest other finite row (scikit-learn's rule: its
+neighbour call counts the row itself) -- ``knn_graph(emb, min_samples - 1, include_self=False)``'s last column, 0 for
+``min_samples = 1`` --, ``w(a, b) = max(d(a, b), core(a), core(b))`` in fp32 on the direct-form distances ``query``,
+``radius`` and ``rank_of`` return, and the tree is a minimum spanning tree of the complete graph on the finite rows under
+``w``.  It is built by Boruvka rounds: every row asks the grouped k-nearest search for its ``search_k`` nearest rows of
+OTHER components (the row's component is its group), an offer kernel picks the lightest and decides whether the list
+proves it the lightest of all, the rows it does not are asked again by ``radius`` at the weight found, and every
+component's lightest offer is hooked by a lock-free union.  Nothing of size N x N is formed.  Which of several equally
+light edges the tree holds may differ between runs; its sorted weights, and everything derived, may not.
+
+The hierarchy (``btsbot_hdbscan_tree``, host C++ in the same library) is TIE-INVARIANT: all edges of one weight are
+applied at once and every set of components they join becomes one node with two or more children.  Mutual-reachability
+weights tie by construction (``w = core(a)`` for many edges of ``a``), and scikit-learn's binary dendrogram depends on
+the order tied edges arrive in: its labels can change when the rows are merely permuted.  Here labels and probabilities
+are a function of the rows alone -- not of their order, ``search_k``, ``splits``, the method or the run.  Two more stated
+departures: ``lambda = 1 / w`` at ``w = 0`` is the tree's largest finite lambda (scikit-learn: infinite stabilities), and
+clusters are numbered by their smallest row (``dbscan``'s rule).
+
+With ``groups=obj`` a row's density is counted in OTHER objects' alerts (``group_mode="exclude"``, as ``dbscan(groups=)``
+and the LOF); edges still join all finite rows.  A non-finite row has no core distance and no edge: label -1,
+probability 0.  ``method="grid"`` takes the searches of a 2-D map from ``MapIndex``.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import copy
+import ctypes as C
+import math
+import time
+from typing import Optional, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _lib
+from .mapindex import MapIndex, check_grid_method
+from .neighbors import EmbeddingIndex, _check_method, _check_splits, _groups, _metric, _ptr, _rows
+
+__all__ = ["hdbscan", "mutual_reachability_mst", "MutualReachabilityMST", "ClusterTree"]
+
+SELECTION_METHODS = tuple(_lib.HDBSCAN_METHOD)
+U = 2.0 ** -24
+
+
+def _check_int(name: str, v, lo: int, hi: Optional[int] = None) -> None:
+    if isinstance(v, bool) or not isinstance(v, int) or v < lo or (hi is not None and v > hi):
+        raise ValueError(f"{name} must be an int {'>= ' + str(lo) if hi is None else f'in {lo}..{hi}'}, got {v!r}")
+
+
+def _check_selection(min_cluster_size, method, allow_single_cluster) -> None:
+    _check_int("min_cluster_size", min_cluster_size, 2)
+    if method not in SELECTION_METHODS:
+        raise ValueError(f"cluster_selection_method must be one of {SELECTION_METHODS}, got {method!r}")
+    if not isinstance(allow_single_cluster, bool):
+        raise ValueError(f"allow_single_cluster must be a bool, got {allow_single_cluster!r}")
+
+
+def _check_mst_args(min_samples, search_k, splits, stats) -> None:
+    _check_int("min_samples", min_samples, 1, _lib.KNN_MAX_K + 1)   # the core graph holds min_samples - 1 columns
+    _check_int("search_k", search_k, 1, _lib.MST_MAX_K)
+    _check_splits(splits)
+    if stats is not None and not isinstance(stats, dict):
+        raise ValueError(f"stats must be None or a dict, got {type(stats).__name__}")
+
+
+def _stream(dev) -> C.c_void_p:
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+class MutualReachabilityMST:
+    """``edges`` int64 [n_finite - 1, 2] (lo, hi), ``weights`` float32 [n_finite - 1] in the order the rounds found
+    them, ``core`` float32 [N] (NaN for a non-finite row), ``n`` = N."""
+
+    def __init__(self, edges: torch.Tensor, weights: torch.Tensor, core: torch.Tensor):
+        self.edges, self.weights, self.core = edges, weights, core
+        self.n = int(core.shape[0])
+        self.device = core.device
+
+    def __len__(self) -> int:
+        return int(self.weights.shape[0])
+
+
+def _comp_view(index, comp: torch.Tensor):
+    """A shallow copy of ``index`` whose groups are ``comp``: the searches exclude a row's own component.  The index
+    itself, its rows and its own groups are not touched."""
+    view = copy.copy(index)
+    view._groups = comp
+    if isinstance(index, MapIndex):
+        view._sorted_groups = comp[index._sorted_rows.to(torch.int64)].contiguous()
+    return view
+
+
+def _slack(index) -> Tuple[Optional[torch.Tensor], int, float]:
+    """(slack [N] or None, squared?, rel) of ``btsbot_mst_offer_knn``: how far below the last listed distance a row the
+    list does not hold may lie.  The grid ranks by the returned distance itself: nothing.  The tile search ranks its
+    candidates by the expansion form and guarantees the j-th returned squared distance within tau = 8 (D + 2) u (|q|^2 +
+    max |b|^2) of the j-th best (cosine: 8 (D + 2) u on 1 - cos; tests/knn_ref.py clause 3); the direct form the lists
+    carry is within (D + 4) u relative of the truth at both ends."""
+    if isinstance(index, MapIndex):
+        return None, 0, 0.0
+    d = index.dim
+    rel = 4 * (d + 4) * U
+    rows = index.bank
+    if index.metric == "cosine":
+        return torch.full((len(index),), 8 * (d + 2) * U, dtype=torch.float32, device=index.device), 0, rel
+    sq = (rows.to(torch.float64) ** 2).sum(dim=1)
+    sq = torch.where(torch.isfinite(sq), sq, torch.zeros_like(sq))
+    tau = 8 * (d + 2 if d >= 4 else d + 6) * U * (sq + sq.max() if len(index) else sq)
+    return (tau * (1 + 2.0 ** -20)).to(torch.float32), 1, rel
+
+
+def mutual_reachability_mst(emb_or_index: Union[torch.Tensor, EmbeddingIndex, MapIndex], min_samples: int = 5,
+                            groups: Optional[torch.Tensor] = None, method: str = "tiles", search_k: int = 8,
+                            stats: Optional[dict] = None, *, metric: str = "euclidean",
+                            splits: int = 0) -> MutualReachabilityMST:
+    """A minimum spanning tree of the mutual-reachability graph of the finite rows (see the module text).
+
+    emb_or_index: rows float [N, D] (an index is built on them: ``EmbeddingIndex``, or ``MapIndex`` with
+    ``method="grid"``, 2-D and euclidean only), an ``EmbeddingIndex`` or a ``MapIndex``.  An index brings its own metric
+    and groups: ``groups=`` next to an index is a ``ValueError``.  groups: int64 [N]; core distances are then counted in
+    rows of OTHER groups.  search_k: the list length of a round's search, 1..64 (no answer depends on it; 1 sends every
+    row that is not inside a full list's reach through the radius tier).  splits: ``EmbeddingIndex.query``'s.
+    stats: a dict that receives ``rounds``, ``n_finite`` and per round the lists ``components`` (at its start),
+    ``unresolved`` (rows sent to the radius tier) and ``radius_total`` (entries of their lists); a dict that comes with
+    ``{"time": True}`` also receives ``ms_search``, ``ms_offer``, ``ms_radius`` and ``ms_merge`` per round (the device
+    is synchronised around every step then: tools/hdbscan_bench.py).
+    Fewer finite rows than ``max(min_samples, 2)`` is a ``ValueError``; more than ``ceil(log2 n_finite) + 1`` rounds a
+    ``RuntimeError``.  Host reads per round: the unresolved rows, the radius search's own, the number of components."""
+    _check_mst_args(min_samples, search_k, splits, stats)
+    _check_method(method)
+    if isinstance(emb_or_index, (EmbeddingIndex, MapIndex)):
+        index = emb_or_index
+        if groups is not None:
+            raise ValueError("groups= next to an index: the tree uses the index's own groups (build the index with "
+                             "groups=...)" + ("" if index.groups is None else "; this one already has them"))
+        index_metric = getattr(index, "metric", "euclidean")
+        if metric != index_metric:
+            raise ValueError(f"metric = {metric!r}, the index holds {index_metric!r}")
+    else:
+        _metric(metric)
+        if method == "grid":
+            check_grid_method(int(emb_or_index.shape[1]) if isinstance(emb_or_index, torch.Tensor)
+                              and emb_or_index.dim() == 2 else None, metric)
+        if groups is not None and (not isinstance(groups, torch.Tensor) or groups.dtype != torch.int64):
+            raise ValueError("groups must be an int64 torch.Tensor, got "
+                             f"{groups.dtype if isinstance(groups, torch.Tensor) else type(groups).__name__}")
+        rows = _rows(emb_or_index, "emb")
+        if groups is not None:
+            groups = _groups(groups, "groups", int(rows.shape[0]), rows.device)
+        index = MapIndex(rows, groups=groups) if method == "grid" else EmbeddingIndex(rows, metric, groups=groups)
+    grid = isinstance(index, MapIndex)
+    if grid and splits:
+        raise ValueError("a MapIndex has no splits")
+    rows = index.points if grid else index.bank
+    n, dev, L = len(index), index.device, _lib.lib()
+    skw = {} if grid else {"splits": splits}
+    with torch.cuda.device(dev):
+        comp = torch.arange(n, dtype=torch.int64, device=dev)
+        # the finite rows are those a search answers; core distances from the graph among the others
+        gkw = {} if index.groups is None else dict(query_groups=index.groups, exclude_same_group=True)
+        probe = index.query(rows, max(min_samples - 1, 1), self_offset=0, **gkw, **skw)[1]
+        finite = ~torch.isnan(probe[:, 0]) if n else torch.zeros(0, dtype=torch.bool, device=dev)
+        if min_samples > 1:
+            core = probe[:, -1].contiguous()
+        else:
+            core = torch.where(finite, torch.zeros_like(probe[:, 0]), torch.full_like(probe[:, 0], float("nan")))
+            if index.groups is not None:   # (with groups the probe left the own object out; finiteness is the row's own)
+                finite = ~torch.isnan(index.query(rows, 1, self_offset=0, **skw)[1][:, 0])
+                core = torch.where(finite, torch.zeros_like(core), torch.full_like(core, float("nan")))
+        n_finite = int(finite.sum()) if n else 0
+        if n_finite < max(min_samples, 2):
+            raise ValueError(f"{n_finite} finite rows, fewer than max(min_samples, 2) = {max(min_samples, 2)}")
+        slack, squared, rel = _slack(index)
+        parent = torch.arange(n, dtype=torch.int32, device=dev)
+        comp_w = torch.empty(n, dtype=torch.int32, device=dev)
+        comp_edge = torch.empty(n, dtype=torch.int64, device=dev)
+        edges = torch.zeros((n, 2), dtype=torch.int64, device=dev)
+        weights = torch.zeros(n, dtype=torch.float32, device=dev)
+        cursor = torch.zeros(1, dtype=torch.int32, device=dev)
+        best_w = torch.empty(n, dtype=torch.float32, device=dev)
+        best_j = torch.empty(n, dtype=torch.int32, device=dev)
+        unres = torch.empty(n, dtype=torch.uint8, device=dev)
+        max_rounds = math.ceil(math.log2(n_finite)) + 1
+        log = dict(rounds=0, n_finite=n_finite, components=[], unresolved=[], radius_total=[])
+        timed = bool(stats and stats.get("time"))
+        if timed:
+            log.update(ms_search=[], ms_offer=[], ms_radius=[], ms_merge=[])
+
+        def lap(key, since):
+            """appends the milliseconds of a step to the log (a timed call only)"""
+            if not timed:
+                return 0.0
+            torch.cuda.synchronize(dev)
+            now = time.perf_counter()
+            if key is not None:
+                log[key].append((now - since) * 1e3)
+            return now
+        components = n_finite
+        while components > 1:
+            if log["rounds"] == max_rounds:
+                raise RuntimeError(f"the spanning tree is not complete after {max_rounds} rounds ({components} components "
+                                   f"of {n_finite} finite rows are left): every round at least halves them")
+            view = _comp_view(index, comp)
+            t0 = lap(None, 0.0)
+            idx, dist = view.query(rows, search_k, query_groups=comp, exclude_same_group=True, **skw)
+            t0 = lap("ms_search", t0)
+            _lib.check(L.btsbot_mst_offer_knn(_ptr(idx), _ptr(dist), n, search_k, _ptr(core), _ptr(slack), squared, rel,
+                                              _ptr(best_w), _ptr(best_j), _ptr(unres), _stream(dev)),
+                       "btsbot_mst_offer_knn")
+            todo = unres.nonzero().view(-1)                       # a host read: the rows of the radius tier
+            t0 = lap("ms_offer", t0)
+            total = 0
+            if todo.numel():
+                st = {}
+                indptr, indices, rdist = view.radius(rows[todo], best_w[todo], query_groups=comp[todo],
+                                                     exclude_same_group=True, stats=st, **skw)
+                total = st["total"]
+                _lib.check(L.btsbot_mst_offer_csr(_ptr(indptr), _ptr(indices), _ptr(rdist), _ptr(todo), int(todo.numel()),
+                                                  n, _ptr(core), _ptr(best_w), _ptr(best_j), _stream(dev)),
+                           "btsbot_mst_offer_csr")
+            t0 = lap("ms_radius", t0)
+            _lib.check(L.btsbot_mst_merge(_ptr(best_w), _ptr(best_j), n, _ptr(comp), _ptr(parent), _ptr(comp_w),
+                                          _ptr(comp_edge), _ptr(edges), _ptr(weights), n, _ptr(cursor), _stream(dev)),
+                       "btsbot_mst_merge")
+            log["rounds"] += 1
+            log["components"].append(components)
+            log["unresolved"].append(int(todo.numel()))
+            log["radius_total"].append(int(total))
+            left = n_finite - int(cursor.item())                  # the round's one read of its own: the components left
+            lap("ms_merge", t0)
+            if left >= components:
+                raise RuntimeError(f"round {log['rounds']} joined nothing: {components} components are left")
+            components = left
+        if stats is not None:
+            stats.update(log)
+        m = n_finite - 1
+        return MutualReachabilityMST(edges[:m].contiguous(), weights[:m].contiguous(), core)
+
+
+def _tree_host(edges: np.ndarray, weights: np.ndarray, n: int, min_cluster_size: int, method: str = "eom",
+               allow_single_cluster: bool = False):
+    """``btsbot_hdbscan_tree`` on host arrays: (labels int64 [n], prob float64 [n], (parent, child, lambda, size))."""
+    _check_selection(min_cluster_size, method, allow_single_cluster)
+    edges = np.ascontiguousarray(edges, dtype=np.int64).reshape(-1, 2)
+    weights = np.ascontiguousarray(weights, dtype=np.float32)
+    if edges.shape[0] != weights.shape[0]:
+        raise ValueError(f"{edges.shape[0]} edges, {weights.shape[0]} weights")
+    labels, prob = np.empty(n, np.int64), np.empty(n, np.float64)
+    cap = 2 * n
+    cp, cc, cs = (np.empty(cap, np.int64) for _ in range(3))
+    cl = np.empty(cap, np.float64)
+    count = C.c_int64(0)
+
+    def p(a):
+        return C.c_void_p(a.ctypes.data)
+
+    _lib.check(_lib.lib().btsbot_hdbscan_tree(p(edges), p(weights), edges.shape[0], n, min_cluster_size,
+                                              _lib.HDBSCAN_METHOD[method], int(allow_single_cluster), p(labels), p(prob),
+                                              p(cp), p(cc), p(cl), p(cs), cap, C.byref(count)), "btsbot_hdbscan_tree")
+    m = count.value
+    return labels, prob, (cp[:m].copy(), cc[:m].copy(), cl[:m].copy(), cs[:m].copy())
+
+
+class ClusterTree:
+    """The hierarchy of one spanning tree, asked with any parameters afterwards: ``labels`` runs the host pass of the
+    library (O(n log n), no GPU call), ``cut`` the component kernels on the tree's device."""
+
+    def __init__(self, mst: MutualReachabilityMST):
+        if not all(isinstance(getattr(mst, a, None), torch.Tensor) for a in ("edges", "weights", "core")):
+            raise ValueError("ClusterTree takes what mutual_reachability_mst returns (edges, weights, core)")
+        self.mst = mst
+        self.n = int(mst.core.shape[0])
+        self.device = mst.core.device
+        self._edges = mst.edges.detach().cpu().numpy()
+        self._weights = mst.weights.detach().cpu().numpy()
+        self.condensed = None
+
+    def labels(self, min_cluster_size: int = 5, method: str = "eom",
+               allow_single_cluster: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``labels`` int64 [N] (-1: noise) and ``prob`` float64 [N] on the tree's device; ``self.condensed`` then holds
+        the condensed tree (parent, child, lambda, size) as numpy arrays."""
+        lab, prob, self.condensed = _tree_host(self._edges, self._weights, self.n, min_cluster_size, method,
+                                               allow_single_cluster)
+        return torch.from_numpy(lab).to(self.device), torch.from_numpy(prob).to(self.device)
+
+    def cut(self, eps: float, min_cluster_size: int = 1) -> torch.Tensor:
+        """DBSCAN* at ``eps``: int64 [N], the components of the tree's edges with ``w <= eps`` among the rows with
+        ``core <= eps``, numbered 0, 1, ... by their smallest row; components smaller than ``min_cluster_size`` and every
+        other row are -1.  On ``dbscan(emb, eps, min_samples)``'s core rows these are its labels."""
+        if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not eps >= 0:
+            raise ValueError(f"eps must be a float >= 0, got {eps!r}")
+        _check_int("min_cluster_size", min_cluster_size, 1)
+        from .clusters import graph_components
+        dev, n = self.device, self.n
+        if dev.type != "cuda":
+            raise RuntimeError(f"ClusterTree.cut runs on the GPU; there is no CPU fallback (the tree is on {dev})")
+        with torch.cuda.device(dev):
+            eps32 = torch.tensor(float(eps), dtype=torch.float32, device=dev)   # rounded to fp32 once
+            keep = self.mst.weights <= eps32
+            src, dst = self.mst.edges[keep, 0], self.mst.edges[keep, 1]
+            order = torch.sort(src).indices
+            indptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            indptr[1:] = torch.cumsum(torch.bincount(src, minlength=n), 0)
+            mask = self.mst.core <= eps32
+            root = graph_components(indptr, dst[order].contiguous(), mask)
+            size = torch.bincount(root[mask], minlength=n)
+            is_root = mask & (root == torch.arange(n, device=dev)) & (size >= min_cluster_size)
+            number = torch.cumsum(is_root, 0, dtype=torch.int64) - 1
+            ok = mask & is_root[root.clamp(min=0)]
+            return torch.where(ok, number[root.clamp(min=0)], torch.full_like(root, -1))
+
+
+def hdbscan(emb: torch.Tensor, min_cluster_size: int = 5, min_samples: Optional[int] = None, metric: str = "euclidean", *,
+            cluster_selection_method: str = "eom", allow_single_cluster: bool = False,
+            groups: Optional[torch.Tensor] = None, method: str = "tiles", search_k: int = 8, splits: int = 0,
+            return_tree: bool = False):
+    """``labels`` int64 [N] (-1: noise) and ``prob`` float64 [N], the membership strength, of the rows of ``emb`` [N, D]
+    (see the module text).  min_samples: None = ``min_cluster_size``.  cluster_selection_method: ``"eom"`` or
+    ``"leaf"``.  groups: int64 [N], an alert's object: densities are counted in other objects' alerts.  method:
+    ``"tiles"`` or, for a 2-D map, ``"grid"``.  return_tree: also the ``ClusterTree``."""
+    _check_selection(min_cluster_size, cluster_selection_method, allow_single_cluster)
+    if min_samples is None:
+        min_samples = min_cluster_size
+    _check_mst_args(min_samples, search_k, splits, None)
+    _metric(metric)
+    _check_method(method)
+    if isinstance(emb, (EmbeddingIndex, MapIndex)):
+        raise ValueError("hdbscan takes rows; build the tree of an index with mutual_reachability_mst")
+    mst = mutual_reachability_mst(emb, min_samples, groups, method, search_k, metric=metric, splits=splits)
+    tree = ClusterTree(mst)
+    labels, prob = tree.labels(min_cluster_size, cluster_selection_method, allow_single_cluster)
+    return (labels, prob, tree) if return_tree else (labels, prob)

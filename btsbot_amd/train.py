@@ -313,6 +313,35 @@ def policy_summary(cand, raw_preds, labels, device="cuda") -> dict:
                               torch.as_tensor(raw_preds.astype(np.float32)).to(dev), **extra)
 
 
+def cluster_config(clu) -> dict:
+    """``config['embedding_clusters']`` checked and completed.  ``"algorithm": "dbscan"`` (the default) takes ``eps``
+    (required), ``min_samples`` (5); ``"hdbscan"`` takes ``min_cluster_size`` (5) and ``min_samples`` (None: the same)
+    and no ``eps``; both take ``on`` (``"map"`` or ``"embedding"``) and ``method`` (``"tiles"`` or ``"grid"``)."""
+    algorithm = clu.get("algorithm", "dbscan") if isinstance(clu, dict) else None
+    own = {"dbscan": {"eps", "min_samples"}, "hdbscan": {"min_cluster_size", "min_samples"}}.get(algorithm, set())
+    unknown = set(clu) - own - {"algorithm", "on", "method"} if isinstance(clu, dict) else {"?"}
+    if (unknown or algorithm not in ("dbscan", "hdbscan") or (algorithm == "dbscan" and "eps" not in clu)
+            or clu.get("on", "map") not in ("map", "embedding") or clu.get("method", "tiles") not in ("tiles", "grid")):
+        raise ValueError("config['embedding_clusters'] is a dict with the keys eps, min_samples, on "
+                         "('map' or 'embedding') and method ('tiles' or 'grid') -- or, with algorithm = 'hdbscan', "
+                         f"min_cluster_size and min_samples in place of eps --, got {clu!r}")
+    tail = dict(on=clu.get("on", "map"), method=clu.get("method", "tiles"))
+    if algorithm == "dbscan":
+        return dict(algorithm=algorithm, eps=float(clu["eps"]), min_samples=int(clu.get("min_samples", 5)), **tail)
+    ms = clu.get("min_samples")
+    return dict(algorithm=algorithm, min_cluster_size=int(clu.get("min_cluster_size", 5)),
+                min_samples=None if ms is None else int(ms), **tail)
+
+
+def _cluster_rows(rows, clu: dict):
+    """(labels, membership probabilities or None) of ``rows`` by a checked ``cluster_config``"""
+    if clu["algorithm"] == "hdbscan":
+        from .hdbscan import hdbscan
+        return hdbscan(rows, clu["min_cluster_size"], clu["min_samples"], method=clu["method"])
+    from .clusters import dbscan
+    return dbscan(rows, clu["eps"], clu["min_samples"], method=clu["method"])[0], None
+
+
 def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, stem: str, batch_size: int = 1024,
                      device="cuda", layer: str = "features") -> str:
     """The embedding step at the end of a run (train.py:449-469, whose helper module the reference does not ship): load
@@ -332,7 +361,9 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
     ``config['embedding_clusters'] = {"eps": ..., "min_samples": 5, "on": "map" | "embedding", "method": "tiles" |
     "grid"}`` (``"grid"``: the 2-D map only, the same labels in time linear in the rows) the DBSCAN labels
     (``clusters.dbscan``; -1 = noise) of the map, as a ``cluster`` column of ``{stem}_umap.csv``, or of the embedding
-    rows, as ``{stem}_clusters.npy`` (int64 [N]).  ``config['embedding_layout']`` also takes ``"quality": True | k``:
+    rows, as ``{stem}_clusters.npy`` (int64 [N]).  With ``"algorithm": "hdbscan"`` in that dict (``min_cluster_size``,
+    ``min_samples`` in place of ``eps``; ``cluster_config``) the labels are ``hdbscan.hdbscan``'s and the membership
+    strengths are left as ``{stem}_cluster_prob.npy`` (float64 [N]).  ``config['embedding_layout']`` also takes ``"quality": True | k``:
     ``write_map_quality`` leaves ``{stem}_umap_quality.json``, the map's trustworthiness, continuity and neighbour recall
     at ``k`` (``True``: the layout's ``n_neighbors``).  Returns the .npy path."""
     import numpy as np
@@ -395,21 +426,16 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
         np.save(stem + "_lof.npy", lof.cpu().numpy())
     lay = config.get("embedding_layout")
     clu = config.get("embedding_clusters")
-    if clu:   # opt-in: DBSCAN of the map (a `cluster` column of the map's table) or of the rows ({stem}_clusters.npy)
-        from .clusters import dbscan
-        unknown = set(clu) - {"eps", "min_samples", "on", "method"} if isinstance(clu, dict) else {"?"}
-        if (unknown or "eps" not in clu or clu.get("on", "map") not in ("map", "embedding")
-                or clu.get("method", "tiles") not in ("tiles", "grid")):
-            raise ValueError("config['embedding_clusters'] is a dict with the keys eps, min_samples, on "
-                             f"('map' or 'embedding') and method ('tiles' or 'grid'), got {clu!r}")
-        clu = dict(eps=float(clu["eps"]), min_samples=int(clu.get("min_samples", 5)), on=clu.get("on", "map"),
-                   method=clu.get("method", "tiles"))
+    if clu:   # opt-in: DBSCAN or HDBSCAN of the map (a `cluster` column of its table) or of the rows ({stem}_clusters.npy)
+        clu = cluster_config(clu)
         if clu["on"] == "map" and not lay:
             raise ValueError("config['embedding_clusters'] with on='map' clusters the map of config['embedding_layout'], "
                              "which is not set")
         if clu["on"] == "embedding":
-            labels, _core = dbscan(torch.from_numpy(out).to(dev), clu["eps"], clu["min_samples"], method=clu["method"])
+            labels, prob = _cluster_rows(torch.from_numpy(out).to(dev), clu)
             np.save(stem + "_clusters.npy", labels.cpu().numpy())
+            if prob is not None:
+                np.save(stem + "_cluster_prob.npy", prob.cpu().numpy())
     if lay:   # opt-in: the UMAP map itself, with the reference's columns (train.py:464)
         import pandas as pd
         from .layout import embedding_layout
@@ -428,8 +454,10 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
         if "candid" in cand.columns:
             table["candid"] = cand["candid"].to_numpy()
         if clu and clu["on"] == "map":
-            labels, _core = dbscan(y_dev, clu["eps"], clu["min_samples"], method=clu["method"])
+            labels, prob = _cluster_rows(y_dev, clu)
             table["cluster"] = labels.cpu().numpy()
+            if prob is not None:
+                np.save(stem + "_cluster_prob.npy", prob.cpu().numpy())
         pd.DataFrame(table).to_csv(stem + "_umap.csv", index=False)
     return stem + ".npy"
 

@@ -1131,6 +1131,70 @@ int btsbot_lof_fit(const int64_t* idx, const float* dist, int64_t n, int k, doub
 int btsbot_lof_score(const int64_t* idx, const float* dist, int64_t q, int k, const double* bank_kdist,
                      const double* bank_lrd, int64_t n, double* lrd, double* lof, void* stream);
 
+/* ---- HDBSCAN: the mutual-reachability spanning tree and its hierarchy (csrc/mst.hip, csrc/hdbscan_tree.hip) ---- */
+
+/* The minimum spanning tree of the complete graph on the finite rows under w(a, b) = max(d(a, b), core(a), core(b), 0) in
+ * fp32, by Boruvka rounds.  A round's searches are btsbot_knn_query_grouped / btsbot_grid_knn and btsbot_knn_radius_* /
+ * btsbot_grid_radius_* with comp int64 [n] -- the row's current component, its smallest row -- as the group of both sides
+ * under BTSBOT_KNN_EXCLUDE_SAME; these three calls stand between them.  All are queued on `stream`; nothing allocates,
+ * synchronises or copies to the host.
+ *
+ * btsbot_mst_offer_knn(): idx int64 [n][k], dist fp32 [n][k]: every row's k nearest rows of other components, ordered by
+ * distance; core fp32 [n].  best_w fp32 [n], best_j int32 [n]: the row's lightest entry by (w, index); -1 / +inf where the
+ * list is empty (a non-finite row; the last component).  unresolved uint8 [n] = 0 where the list proves the offer the
+ * lightest edge that leaves the row: the list is not full, or best_w <= max(floor, core(row)), floor = (1 - rel) *
+ * (slack_is_squared ? sqrt(max(d_last^2 - slack[row], 0)) : d_last - slack[row]) in float64, a lower bound of the distance
+ * of every row the list does not hold (slack fp32 [n] or NULL = 0; a search that ranks by the returned distance itself
+ * passes NULL and rel = 0).  1 where it does not: every lighter edge then lies within the radius best_w.  1 <= k <= 64,
+ * 0 <= rel < 1.  One launch, W = 16, 32 or 64 lanes per row.
+ *
+ * btsbot_mst_offer_csr(): indptr int64 [m + 1], indices int64, dist fp32: the radius lists (rows of other components
+ * within best_w) of the m rows `rows` int64 [m]; lowers (best_w, best_j) of these rows to the lightest entry by (w, index).
+ * One launch, one wave per row.
+ *
+ * btsbot_mst_merge(): every component (comp[i], in [0, n)) takes the lightest offer of its rows -- atomicMin on the
+ * weight's bits into comp_w uint32 [n], then on (lo << 32 | hi) among the rows at that weight into comp_edge uint64 [n],
+ * both scratch --, its edge is united lock-free on parent int32 [n] (parent[i] = comp[i] on entry, a root is hooked under
+ * the smaller root); an edge that joins two trees is appended at (*cursor)++ to edges int64 [edge_capacity][2] (lo, hi)
+ * and weights fp32 [edge_capacity], an edge whose ends are joined already is dropped; then comp and parent are relabelled
+ * to the roots.  *cursor (int32, device memory, zero before the first round) counts the edges of all rounds: the
+ * components left are the finite rows less *cursor.  Which of several equally light edges a component takes may differ
+ * between runs; the sorted weights may not.  Six launches.
+ * All three: BTSBOT_ERR_INVALID_ARG for n or m outside 0 .. 2^31 - 1, k or rel out of range, a NULL pointer that is
+ * needed; n == 0 launches nothing. */
+int btsbot_mst_offer_knn(const int64_t* idx, const float* dist, int64_t n, int k, const float* core, const float* slack,
+                         int slack_is_squared, float rel, float* best_w, int32_t* best_j, uint8_t* unresolved,
+                         void* stream);
+int btsbot_mst_offer_csr(const int64_t* indptr, const int64_t* indices, const float* dist, const int64_t* rows, int64_t m,
+                         int64_t n, const float* core, float* best_w, int32_t* best_j, void* stream);
+int btsbot_mst_merge(const float* best_w, const int32_t* best_j, int64_t n, int64_t* comp, int32_t* parent,
+                     uint32_t* comp_w, uint64_t* comp_edge, int64_t* edges, float* weights, int64_t edge_capacity,
+                     int32_t* cursor, void* stream);
+
+/* btsbot_hdbscan_tree(): HOST arrays in, host arrays out; no stream, no GPU call -- it runs on a machine without one.
+ * edges int64 [n_edges][2] and weights fp32 [n_edges] (>= 0, +inf allowed): a spanning tree of the rows it names, rows in
+ * [0, n); a row no edge names is noise.  The hierarchy is tie-invariant: all edges of one weight are applied at once and
+ * every set of old components they join becomes one node with two or more children, so the answer is a function of the
+ * components of "edges with w <= t" for every t -- the same for every edge order and every minimum spanning tree.
+ * lambda = 1 / w in float64 (w = 0: the largest lambda of a positive weight of the tree, 1 without one).  Condensed tree,
+ * top-down: at a node of cluster c a child of size >= min_cluster_size is real; two or more real children start new
+ * clusters born at the node's lambda, exactly one continues c, the rows of the others fall out of c there.  Clusters
+ * are numbered n, n + 1, ... by (smallest row, size descending); the entries (parent cluster, child row or cluster,
+ * lambda, size) are sorted by (parent, child).  stability(c) = (sum over its rows of lambda - birth(c)) + (sum over its
+ * child clusters of size * (lambda - birth(c))), float64, each sum sequential in entry order.  BTSBOT_HDBSCAN_EOM: bottom-up,
+ * the children replace c only if their summed selected stability is strictly greater; BTSBOT_HDBSCAN_LEAF: the clusters
+ * without child clusters; the root only with allow_single_cluster.  labels int64 [n]: the nearest selected
+ * ancestor-or-self of the cluster the row fell out of, numbered 0, 1, ... by smallest row, or -1; prob float64 [n] =
+ * min(lambda_row, m) / m with m the largest lambda of the selected cluster's own entries (1 where m = 0; 0 for noise).
+ * The condensed arrays may all be NULL; *n_cond receives the number of entries (at most 2 n).
+ * BTSBOT_ERR_INVALID_ARG for n >= 2^30, n_edges >= n, min_cluster_size < 2, an unknown method, an edge out of range or a
+ * self-loop, a negative or NaN weight, edges that are no spanning tree of their rows, a short condensed capacity. */
+enum btsbot_hdbscan_method { BTSBOT_HDBSCAN_EOM = 0, BTSBOT_HDBSCAN_LEAF = 1 };
+int btsbot_hdbscan_tree(const int64_t* edges, const float* weights, int64_t n_edges, int64_t n, int min_cluster_size,
+                        int method, int allow_single_cluster, int64_t* labels, double* prob, int64_t* cond_parent,
+                        int64_t* cond_child, double* cond_lambda, int64_t* cond_size, int64_t cond_capacity,
+                        int64_t* n_cond);
+
 /* Replaces: the epoch / validation metrics of val.py:159-168 and train.py:550-558 -- out2[0] += sum_i of
  * BCEWithLogitsLoss(pos_weight) terms over n logits, out2[1] += number of alerts whose sigmoid(z) > 0.5
  * agrees with the label (caller zeroes out2 and divides by n). */

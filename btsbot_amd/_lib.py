@@ -41,6 +41,8 @@ SYMBOLS = [
     "btsbot_op_cnt_dwln_bwd_rows", "btsbot_op_cnt_dw3ln_bwd_rows", "btsbot_op_cnt_dwln_bwd", "btsbot_op_cnt_dw3ln_bwd",
     "btsbot_op_cnt_ln_bwd", "btsbot_op_cnt_ln_dw1_bwd", "btsbot_op_cnt_dw_plain", "btsbot_op_cnt_dw_wgrad",
     "btsbot_op_cnt_colsum_f32",
+    "btsbot_op_cnt_mlp_bwd_planes", "btsbot_op_cnt_mlp_bwd_slices", "btsbot_op_cnt_s2mlp_bwd_rows", "btsbot_op_cnt_mlp_bwd",
+    "btsbot_op_cnt_s2mlp_bwd", "btsbot_op_cnt_fused_mlp", "btsbot_op_cnt_fc2_grads",
     "btsbot_reserve_train", "btsbot_forward_train", "btsbot_backward", "btsbot_debug_stamps",
     "btsbot_grad_buckets", "btsbot_wait_grad_bucket", "btsbot_allreduce_grads", "btsbot_use_workspace", "btsbot_set_option",
     "btsbot_augment", "btsbot_eval_metrics", "btsbot_prep_triplets", "btsbot_alert_features",
@@ -220,7 +222,10 @@ def lib() -> C.CDLL:
                        ("ln_bwd", [vp] * 6 + [i64, i32, vp, i32, i32, vp]),
                        ("ln_dw1_bwd", [vp] * 7 + [i32] + [vp] * 4 + [i64, i32, vp]),
                        ("dw_plain", [vp, vp, i32, vp, vp, vp, vp] + [i32] * 4 + [vp]),
-                       ("dw_wgrad", [vp] * 4 + [i32] * 3 + [vp]), ("colsum_f32", [vp, vp, i32, i32, vp])):
+                       ("dw_wgrad", [vp] * 4 + [i32] * 3 + [vp]), ("colsum_f32", [vp, vp, i32, i32, vp]),
+                       ("mlp_bwd_planes", [i32]), ("mlp_bwd_slices", [i32, i32]), ("s2mlp_bwd_rows", []),
+                       ("mlp_bwd", [i32, i32] + [vp] * 10 + [i32, i32, vp]), ("s2mlp_bwd", [i32, i32] + [vp] * 6 + [i32, vp]),
+                       ("fused_mlp", [i32, i32] + [vp] * 8 + [i32, vp]), ("fc2_grads", [vp] * 8 + [i32, i32, vp])):
         fn = getattr(L, "btsbot_op_cnt_" + name)
         fn.restype = i32
         fn.argtypes = args

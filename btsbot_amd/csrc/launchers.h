@@ -319,6 +319,7 @@ int launch_mlp_bwd(int prec, int C, const void* xn, const void* dy, const void* 
 // gelu'(a) [R][1024] (operand type) and dxn = W1^T da [R][256] (fp32); w2tp / w1tp = launch_pack_frag16 of the 16-bit
 // dgrad transposes (diag(gamma) W2)^T [1024][256] and W1^T [256][1024]
 bool s2mlp_bwd_supported(int prec, int C);
+int s2mlp_bwd_rows();   // pixel rows per workgroup (<= 48): da is stored in whole workgroups of them
 int launch_pack_frag16(const void* src, void* dst, int rows, int K, hipStream_t st);
 int launch_s2mlp_bwd(int prec, const void* dy, const void* a, const void* w2tp, const void* w1tp, void* da, float* dxn, int R,
                      hipStream_t st);

@@ -230,6 +230,14 @@ __global__ void pack_frag16_kernel(const unsigned short* __restrict__ src, unsig
 
 bool s2mlp_bwd_supported(int prec, int C_) { return (prec == BTSBOT_BF16 || prec == BTSBOT_F16) && C_ == C; }
 
+int s2mlp_bwd_rows() {
+  static const int rw = [] {
+    const int v = switch_int(SW_S2MLP_ROWS, 0);   // tuning knob: pixel rows per workgroup (<= 48)
+    return v >= 16 && v <= NCOL ? v : 45;
+  }();
+  return rw;
+}
+
 int launch_pack_frag16(const void* src, void* dst, int rows, int K, hipStream_t st) {
   const long total = (long)rows * K;
   hipLaunchKernelGGL(pack_frag16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
@@ -247,10 +255,7 @@ int launch_s2mlp_bwd(int prec, const void* dy, const void* a, const void* w2tp, 
     btsbot_set_error("s2mlp_bwd: precision %d is not bf16 / f16", prec);
     return BTSBOT_ERR_INVALID_ARG;
   }
-  static const int rw = [] {
-    const int v = switch_int(SW_S2MLP_ROWS, 0);   // tuning knob: pixel rows per workgroup (<= 48)
-    return v >= 16 && v <= NCOL ? v : 45;
-  }();
+  const int rw = s2mlp_bwd_rows();
   S2MlpBwdArgs g{dy, a, w2tp, w1tp, da, dxn, R, rw};
   const int grid = (R + rw - 1) / rw;
   static DevOnce attr;

@@ -577,3 +577,74 @@ def cnt_colsum_f32(rows, out):
     _f32t(rows), _f32t(out, (N,))
     _cnt("colsum_f32", rows, _p(rows), _p(out), M, N)
     return out
+
+
+# ---- the MLP half of the ConvNeXt 16-bit training step one launcher at a time (btsbot_op_cnt_*, cn_mlp_ops.hip).
+# Operand tensors are bf16 or f16 (that picks the kernels), biases / gamma / gradients fp32.  Every output is the
+# caller's tensor; include/btsbot_hip.h states which are added to and which written.
+def _t16(t, shape):
+    assert t.dtype in (torch.bfloat16, torch.float16) and t.is_contiguous() and tuple(t.shape) == tuple(shape), \
+        (t.dtype, tuple(t.shape), tuple(shape))
+    return _lib.PRECISION["bf16" if t.dtype == torch.bfloat16 else "f16"]
+
+
+def cnt_mlp_bwd_planes(C):
+    """Addend planes of cnt_mlp_bwd's dxn."""
+    return _lib.check(_lib.lib().btsbot_op_cnt_mlp_bwd_planes(C), "btsbot_op_cnt_mlp_bwd_planes")
+
+
+def cnt_mlp_bwd_slices(C, R):
+    """Workgroups along the rows of one mlp_bwd launch: workgroup i walks the 64-row tiles i, i + slices, ..."""
+    return _lib.check(_lib.lib().btsbot_op_cnt_mlp_bwd_slices(C, R), "btsbot_op_cnt_mlp_bwd_slices")
+
+
+def cnt_s2mlp_bwd_rows():
+    """Rows per workgroup of s2mlp_bwd."""
+    return _lib.check(_lib.lib().btsbot_op_cnt_s2mlp_bwd_rows(), "btsbot_op_cnt_s2mlp_bwd_rows")
+
+
+def cnt_mlp_bwd(xn, dy, w1, w2g, b1, dxn, G, S, dW1, db1, deterministic=False):
+    """xn, dy [R, C]; w1 [4C, C]; w2g = (diag(gamma) W2)^T [4C, C]; dxn [planes, R, C] = ; G [C, 4C], S [C], dW1 [4C, C],
+    db1 [4C] += ."""
+    R, Cc = xn.shape
+    prec = _t16(xn, (R, Cc))
+    assert _t16(dy, (R, Cc)) == prec and _t16(w1, (4 * Cc, Cc)) == prec and _t16(w2g, (4 * Cc, Cc)) == prec
+    planes = cnt_mlp_bwd_planes(Cc)
+    _f32t(b1, (4 * Cc,)), _f32t(dxn, numel=planes * R * Cc), _f32t(G, (Cc, 4 * Cc)), _f32t(S, (Cc,))
+    _f32t(dW1, (4 * Cc, Cc)), _f32t(db1, (4 * Cc,))
+    _cnt("mlp_bwd", xn, prec, Cc, _p(xn), _p(dy), _p(w1), _p(w2g), _p(b1), _p(dxn), _p(G), _p(S), _p(dW1), _p(db1), R,
+         int(bool(deterministic)))
+    return dxn
+
+
+def cnt_s2mlp_bwd(dy, a, w2gt, w1t, da, dxn):
+    """dy [R, 256]; a [R, 1024]; w2gt = (diag(gamma) W2)^T [1024, 256]; w1t = W1^T [256, 1024]; da [R + 48, 1024] = (the
+    operand type); dxn [R, 256] fp32 = ."""
+    R = dy.shape[0]
+    prec = _t16(dy, (R, 256))
+    assert _t16(a, (R, 1024)) == prec and _t16(w2gt, (1024, 256)) == prec and _t16(w1t, (256, 1024)) == prec
+    assert _t16(da, (R + 48, 1024)) == prec
+    _f32t(dxn, (R, 256))
+    _cnt("s2mlp_bwd", dy, prec, 256, _p(dy), _p(a), _p(w2gt), _p(w1t), _p(da), _p(dxn), R)
+    return da, dxn
+
+
+def cnt_fused_mlp(xn, w1, w2, b1, b2, gamma, x, xres=None):
+    """xn [M, C] (bf16 / f16); w1 [4C, C], w2 [C, 4C] fp32 masters; x [M, C] = xres + gamma (W2 gelu(W1 xn + b1) + b2),
+    xres None: x itself (in place)."""
+    M, Cc = xn.shape
+    prec = _t16(xn, (M, Cc))
+    _f32t(w1, (4 * Cc, Cc)), _f32t(w2, (Cc, 4 * Cc)), _f32t(b1, (4 * Cc,)), _f32t(b2, (Cc,)), _f32t(gamma, (Cc,))
+    _f32t(x, (M, Cc))
+    assert xres is None or _f32t(xres, (M, Cc)) is xres
+    _cnt("fused_mlp", xn, prec, Cc, _p(xn), _p(w1), _p(w2), _p(b1), _p(b2), _p(gamma), _p(xres), _p(x), M)
+    return x
+
+
+def cnt_fc2_grads(G, S, w2, b2, gamma, dW2, db2, dgamma):
+    """G, w2, dW2 [C, H]; S, b2, gamma, db2, dgamma [C]; dW2, db2, dgamma = ; G and S are left zero."""
+    Cc, H = G.shape
+    _f32t(G), _f32t(S, (Cc,)), _f32t(w2, (Cc, H)), _f32t(b2, (Cc,)), _f32t(gamma, (Cc,)), _f32t(dW2, (Cc, H))
+    _f32t(db2, (Cc,)), _f32t(dgamma, (Cc,))
+    _cnt("fc2_grads", G, _p(G), _p(S), _p(w2), _p(b2), _p(gamma), _p(dW2), _p(db2), _p(dgamma), Cc, H)
+    return dW2, db2, dgamma

@@ -540,6 +540,46 @@ int btsbot_op_cnt_dw_wgrad(const float* x, const float* dd, float* dw, float* db
 /* out [N] += the column sums of in [M][N] (fp32): what folds partial rows into the arena. */
 int btsbot_op_cnt_colsum_f32(const float* in, float* out, int M, int N, void* stream);
 
+/* The MLP half of the ConvNeXt 16-bit TRAINING step (mlp_bwd.hip, s2mlp_bwd.hip, fused_mlp.hip, fc2_grads_kernel of
+ * ln_dw_bwd.hip) one launcher at a time (cn_mlp_ops.hip).  prec = BTSBOT_BF16 or BTSBOT_F16 (the "operand type"); biases,
+ * gamma and every gradient are fp32.  Same rules as above: the engine's own launchers on the caller's stream, scratch of
+ * the call's own, every argument checked before anything is allocated or launched (a null pointer, a negative row
+ * count, another prec or a width the launcher has no kernel for: BTSBOT_ERR_INVALID_ARG with a message); zero rows
+ * return BTSBOT_OK and touch nothing.
+ *
+ * The launchers' own figures: addend planes of dxn (1 at C = 64, 4 at C = 128), workgroups along the rows of one
+ * mlp_bwd launch (= slices of its partial filter-gradient tiles; a workgroup walks row tiles of 64 in steps of that
+ * count), and the rows per workgroup of s2mlp_bwd. */
+int btsbot_op_cnt_mlp_bwd_planes(int C);
+int btsbot_op_cnt_mlp_bwd_slices(int C, int R);
+int btsbot_op_cnt_s2mlp_bwd_rows(void);
+/* Backward of a block's MLP y = x + gamma (W2 gelu(W1 xn + b1) + b2) at C = 64 or 128 in one kernel, then the slice
+ * reduction of its partial tiles.  xn, dy [R][C], w1 [4C][C], w2g = (diag(gamma) W2)^T [4C][C]: operand type; b1 [4C].
+ *   dxn  =  planes x [R][C] addend planes, R * C floats apart; plane s = da[:, slice s] W1[slice s]   (written)
+ *   G [C][4C] += dy^T g;   S [C] += colsum(dy);   dW1 [4C][C] += da^T xn;   db1 [4C] += colsum(da)
+ * deterministic != 0: db1 and S go through partial rows added in a fixed order (scratch sized from the slice count);
+ * BTSBOT_ERR_STATE if that scratch fell short. */
+int btsbot_op_cnt_mlp_bwd(int prec, int C, const void* xn, const void* dy, const void* w1, const void* w2g, const float* b1,
+                          float* dxn, float* G, float* S, float* dW1, float* db1, int R, int deterministic, void* stream);
+/* The input-gradient half of a 256-channel block's MLP backward (C = 256: the only width with a kernel).  dy [R][256], a [R][1024] (the kept fc1 pre-activation),
+ * w2gt = (diag(gamma) W2)^T [1024][256], w1t = W1^T [256][1024]: operand type, row-major (packed into MFMA fragments in
+ * scratch here).
+ *   da  [R + 48][1024] operand type =  (dy (gamma W2)) * gelu'(a): rows 0 .. R-1; the last workgroup also writes its dead
+ *       rows R .. ceil(R / rows) * rows - 1 (zeros); nothing behind them is touched                        (written)
+ *   dxn [R][256] fp32 = da W1                                                                               (written) */
+int btsbot_op_cnt_s2mlp_bwd(int prec, int C, const void* dy, const void* a, const void* w2gt, const void* w1t, void* da,
+                            float* dxn, int R, void* stream);
+/* The training forward of a block's MLP at C = 64, 80, 128 or 160: xn [M][C] operand type; w1 [4C][C], w2 [C][4C] the
+ * fp32 masters (packed in scratch here); b1 [4C], b2, gamma [C].
+ *   x [M][C] fp32 = xres + gamma (W2 gelu(W1 xn + b1) + b2)        (written; xres NULL or == x: in place) */
+int btsbot_op_cnt_fused_mlp(int prec, int C, const void* xn, const float* w1, const float* w2, const float* b1,
+                            const float* b2, const float* gamma, const float* xres, float* x, int M, void* stream);
+/* fc2 / layer-scale gradients from G [C][H] = dy^T g and S [C] = colsum(dy) (C, H >= 1):
+ *   dW2 [C][H] = gamma G;   db2 [C] = gamma S;   dgamma [C] = <W2, G> rows + b2 S       (all three written)
+ *   G and S are read once and LEFT ZERO (they are the next block's accumulators). */
+int btsbot_op_cnt_fc2_grads(float* G, float* S, const float* w2, const float* b2, const float* gamma, float* dW2, float* db2,
+                            float* dgamma, int C, int H, void* stream);
+
 /* Measurement aid with no reference counterpart (bench.py's roofline leg): when on, every kernel
  * launch of forward() is bracketed by two HIP events recorded on the launch stream;
  * profile_collect() waits for them and returns, per kernel family (profile_category_name), the

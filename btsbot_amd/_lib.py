@@ -60,9 +60,10 @@ SYMBOLS = [
     "btsbot_layout_epochs", "btsbot_layout_smooth_knn_query", "btsbot_layout_transform",
     "btsbot_lof_fit", "btsbot_lof_score",
     "btsbot_mst_offer_knn", "btsbot_mst_offer_csr", "btsbot_mst_merge", "btsbot_hdbscan_tree",
+    "btsbot_hdbscan_model", "btsbot_cluster_offer_knn", "btsbot_cluster_offer_csr", "btsbot_cluster_assign",
 ]
 LOF_MAX_K = 64                               # csrc/lof.hip
-MST_MAX_K = 64                               # csrc/mst.hip: search_k
+MST_MAX_K = 64                               # csrc/mst.hip, csrc/hdbscan_predict.hip: search_k
 HDBSCAN_METHOD = {"eom": 0, "leaf": 1}       # enum btsbot_hdbscan_method
 LAYOUT_MAX_K, LAYOUT_MAX_NEGATIVES = 64, 64
 KNN_METRIC = {"euclidean": 0, "cosine": 1}   # enum btsbot_knn_metric
@@ -355,6 +356,14 @@ def lib() -> C.CDLL:
     L.btsbot_mst_merge.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp]
     L.btsbot_hdbscan_tree.restype = i32
     L.btsbot_hdbscan_tree.argtypes = [vp, vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]
+    L.btsbot_hdbscan_model.restype = i32
+    L.btsbot_hdbscan_model.argtypes = [vp, vp, i64, i64, i32, i32, i32] + [vp] * 8 + [i64, vp, vp]
+    L.btsbot_cluster_offer_knn.restype = i32
+    L.btsbot_cluster_offer_knn.argtypes = [vp, vp, i64, i32, i64, i32, vp, vp, i32, f32, vp, vp, vp, vp, vp]
+    L.btsbot_cluster_offer_csr.restype = i32
+    L.btsbot_cluster_offer_csr.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]
+    L.btsbot_cluster_assign.restype = i32
+    L.btsbot_cluster_assign.argtypes = [vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, C.c_double] + [vp] * 7
     L.btsbot_eval_metrics.restype = i32
     L.btsbot_eval_metrics.argtypes = [vp, vp, f32, i64, vp, vp]
     if L.btsbot_abi_version() != ABI_VERSION:

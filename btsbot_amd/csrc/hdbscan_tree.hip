@@ -1,6 +1,6 @@
-// btsbot_hdbscan_tree: the HDBSCAN hierarchy, condensed tree, stabilities and selection from a spanning tree of the
-// mutual-reachability graph.  Host only: no stream, no GPU call, nothing of common.h (DESIGN.md section 4v;
-// tests/hdbscan_ref.py is the float64 restatement, tests/test_hdbscan_host.py compares the two exactly).
+// btsbot_hdbscan_tree, btsbot_hdbscan_model: the HDBSCAN hierarchy, condensed tree, stabilities and selection from a
+// spanning tree of the mutual-reachability graph.  Host only: no stream, no GPU call, nothing of common.h (DESIGN.md
+// section 4v; tests/hdbscan_ref.py is the float64 restatement, tests/test_hdbscan_host.py compares the two exactly).
 //
 //   1 sort the edges by weight
 //   2 the TIE-INVARIANT dendrogram: all edges of one weight are applied at once, every set of old components they join
@@ -11,10 +11,14 @@
 //   4 canonical numbering: clusters by (smallest row, size descending), entries by (parent, child)
 //   5 stabilities in that order, the selection bottom-up, labels and probabilities
 // O(n log n): two sorts, a union-find, and passes over O(n) nodes.
+// btsbot_hdbscan_model is the same pass (one function, tree_pass) handing out the tables a prediction walks -- per row
+// the cluster it fell out of and its lambda, per cluster parent, birth, label, the strength's denominator and the largest
+// lambda of its subtree -- and the GLOSH score of the fitted rows (tests/hdbscan_predict_ref.py).
 #include <stdarg.h>
 #include <stdint.h>
 
 #include <algorithm>
+#include <limits>
 #include <numeric>
 #include <vector>
 
@@ -47,13 +51,20 @@ struct Entry {
   int64_t size;
 };
 
-}  // namespace
+// what btsbot_hdbscan_model hands out of the pass: per row the cluster it fell out of and the lambda, per cluster (in
+// the canonical numbering less n) its parent, birth, the label and largest lambda of its nearest selected
+// ancestor-or-self, and the largest lambda of its subtree
+struct Tables {
+  std::vector<int32_t> fell, parent, label;
+  std::vector<double> lam_row, birth, max_lambda, death;
+  double lam_zero = 1.0;
+};
 
-extern "C" int btsbot_hdbscan_tree(const int64_t* edges, const float* weights, int64_t n_edges, int64_t n,
-                                   int min_cluster_size, int method, int allow_single_cluster, int64_t* labels,
-                                   double* prob, int64_t* cond_parent, int64_t* cond_child, double* cond_lambda,
-                                   int64_t* cond_size, int64_t cond_capacity, int64_t* n_cond) {
-  const char* who = "btsbot_hdbscan_tree";
+// the whole pass; `out` (or nullptr) receives the tables
+int tree_pass(const char* who, const int64_t* edges, const float* weights, int64_t n_edges, int64_t n,
+              int min_cluster_size, int method, int allow_single_cluster, int64_t* labels, double* prob,
+              int64_t* cond_parent, int64_t* cond_child, double* cond_lambda, int64_t* cond_size,
+              int64_t cond_capacity, int64_t* n_cond, Tables* out) {
   if (n < 0 || n > 0x7fffffffLL / 2 || n_edges < 0 || n_edges >= std::max<int64_t>(n, 1) || min_cluster_size < 2 ||
       (method != BTSBOT_HDBSCAN_EOM && method != BTSBOT_HDBSCAN_LEAF)) {
     btsbot_set_error("%s: need 0 <= n < 2^30, 0 <= n_edges < n, min_cluster_size >= 2 and a known method (n=%lld "
@@ -71,6 +82,10 @@ extern "C" int btsbot_hdbscan_tree(const int64_t* edges, const float* weights, i
     prob[i] = 0.0;
   }
   *n_cond = 0;
+  if (out != nullptr) {
+    out->fell.assign((size_t)n, -1);
+    out->lam_row.assign((size_t)n, 0.0);
+  }
   if (n_edges == 0) return BTSBOT_OK;
   for (int64_t e = 0; e < n_edges; ++e) {
     const int64_t a = edges[2 * e], b = edges[2 * e + 1];
@@ -289,5 +304,82 @@ extern "C" int btsbot_hdbscan_tree(const int64_t* edges, const float* weights, i
     labels[r] = number[s];
     prob[r] = max_lam[s] == 0.0 ? 1.0 : std::min(lam_row[r], max_lam[s]) / max_lam[s];
   }
+  if (out != nullptr) {
+    out->lam_zero = lam_zero;
+    out->label.assign((size_t)nc, -1);
+    out->max_lambda.assign((size_t)nc, 0.0);
+    out->death = max_lam;
+    for (int32_t c = 0; c < nc; ++c)
+      if (sel[c] >= 0) {
+        out->label[c] = number[sel[c]];
+        out->max_lambda[c] = max_lam[sel[c]];
+      }
+    for (int32_t c = nc - 1; c > 0; --c)   // (a parent stands before its children)
+      out->death[par[c]] = std::max(out->death[par[c]], out->death[c]);
+    out->fell = std::move(fell);
+    out->lam_row = std::move(lam_row);
+    out->parent = std::move(par);
+    out->birth = std::move(birth);
+  }
+  return BTSBOT_OK;
+}
+
+}  // namespace
+
+extern "C" int btsbot_hdbscan_tree(const int64_t* edges, const float* weights, int64_t n_edges, int64_t n,
+                                   int min_cluster_size, int method, int allow_single_cluster, int64_t* labels,
+                                   double* prob, int64_t* cond_parent, int64_t* cond_child, double* cond_lambda,
+                                   int64_t* cond_size, int64_t cond_capacity, int64_t* n_cond) {
+  return tree_pass("btsbot_hdbscan_tree", edges, weights, n_edges, n, min_cluster_size, method, allow_single_cluster,
+                   labels, prob, cond_parent, cond_child, cond_lambda, cond_size, cond_capacity, n_cond, nullptr);
+}
+
+extern "C" int btsbot_hdbscan_model(const int64_t* edges, const float* weights, int64_t n_edges, int64_t n,
+                                    int min_cluster_size, int method, int allow_single_cluster, int32_t* row_cluster,
+                                    double* row_lambda, double* outlier, int32_t* parent, double* birth, int32_t* label,
+                                    double* max_lambda, double* death, int64_t cluster_capacity, int64_t* n_clusters,
+                                    double* lam_zero) {
+  const char* who = "btsbot_hdbscan_model";
+  if (n_clusters == nullptr || lam_zero == nullptr || cluster_capacity < 0 ||
+      (n > 0 && (row_cluster == nullptr || row_lambda == nullptr || outlier == nullptr))) {
+    btsbot_set_error("%s: NULL argument, or a negative cluster_capacity", who);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  *n_clusters = 0;
+  *lam_zero = 1.0;
+  if (n < 0 || n > 0x7fffffffLL / 2) {   // (before anything of size n is allocated; the pass checks the rest)
+    btsbot_set_error("%s: need 0 <= n < 2^30 (n=%lld)", who, (long long)n);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  std::vector<int64_t> labels((size_t)n);
+  std::vector<double> prob(labels.size());
+  int64_t n_cond = 0;
+  Tables t;
+  const int rc = tree_pass(who, edges, weights, n_edges, n, min_cluster_size, method, allow_single_cluster, labels.data(),
+                           prob.data(), nullptr, nullptr, nullptr, nullptr, 0, &n_cond, &t);
+  if (rc != BTSBOT_OK) return rc;
+  const int64_t nc = (int64_t)t.parent.size();
+  if (nc > cluster_capacity || (nc > 0 && (parent == nullptr || birth == nullptr || label == nullptr ||
+                                           max_lambda == nullptr || death == nullptr))) {
+    btsbot_set_error("%s: the tree holds %lld clusters; the five cluster arrays need that capacity (got %lld; at most "
+                     "max(n - 1, 1) are ever needed)", who, (long long)nc, (long long)cluster_capacity);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  for (int64_t c = 0; c < nc; ++c) {
+    parent[c] = t.parent[c];
+    birth[c] = t.birth[c];
+    label[c] = t.label[c];
+    max_lambda[c] = t.max_lambda[c];
+    death[c] = t.death[c];
+  }
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (int64_t r = 0; r < n; ++r) {
+    const int32_t c = t.fell[r];
+    row_cluster[r] = c;
+    row_lambda[r] = t.lam_row[r];
+    outlier[r] = c < 0 ? nan : (t.death[c] == 0.0 ? 0.0 : 1.0 - t.lam_row[r] / t.death[c]);
+  }
+  *n_clusters = nc;
+  *lam_zero = t.lam_zero;
   return BTSBOT_OK;
 }

@@ -19,35 +19,15 @@
 //               relabel comp[i] = the root of i, then parent[i] = comp[i]: the smallest row of the component
 // W lanes hold a row of a list, as in csrc/lof.hip.  Plain C++ atomics only.
 #include "common.h"
+#include "mst_key.h"
 
 namespace {
 
 constexpr int MST_MAX_K = 64;
 constexpr int WG = 256;
-constexpr unsigned long long NO_KEY = ~0ull;
-
-__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int o, int w) {
-  const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)(v & 0xffffffffull), o, w);
-  const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o, w);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
-template <int W>
-__device__ __forceinline__ unsigned long long group_min_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = W / 2; o >= 1; o >>= 1) {
-    const unsigned long long t = shfl_xor_u64(v, o, W);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-
-// (w, j) as one key: the bits of a float >= 0 (+inf included) order like the value
-__device__ __forceinline__ unsigned long long offer_key(float d, float core_row, float core_j, long j) {
-  float w = fmaxf(d, fmaxf(core_row, core_j));
-  w = w > 0.0f ? w : 0.0f;   // (1 - cos may round below 0; -0 would not order by its bits)
-  return ((unsigned long long)__float_as_uint(w) << 32) | (unsigned)j;
-}
+using offer::NO_KEY;
+using offer::group_min_u64;
+using offer::offer_key;
 
 template <int W>
 __global__ __launch_bounds__(WG) void mst_offer_knn_kernel(const int64_t* __restrict__ idx, const float* __restrict__ dist,

@@ -9,6 +9,9 @@ alone (csrc/mst.hip, csrc/hdbscan_tree.hip):
     tree = ClusterTree(mst)                                      # one tree, any parameters afterwards
     labels, prob = tree.labels(min_cluster_size, method="eom")
     labels = tree.cut(eps, min_cluster_size=1)                   # DBSCAN* at any eps from the same tree
+    glosh = tree.outlier_scores(min_cluster_size)                # float64 [N]: GLOSH, 0 in a cluster's core, -> 1 far out
+    m = ClusterModel(bank_or_index, min_cluster_size=5)          # the fit, kept to answer NEW rows
+    labels, prob = m.predict(queries)                            # int64 [Q], float64 [Q]; return_details=True: a dict too
 
 ``core(i)`` is the distance from row i to its ``(min_samples - 1)``-th nearest other finite row (scikit-learn's rule: its
 neighbour call counts the row itself) -- ``knn_graph(emb, min_samples - 1, include_self=False)``'s last column, 0 for
@@ -31,6 +34,22 @@ clusters are numbered by their smallest row (``dbscan``'s rule).
 With ``groups=obj`` a row's density is counted in OTHER objects' alerts (``group_mode="exclude"``, as ``dbscan(groups=)``
 and the LOF); edges still join all finite rows.  A non-finite row has no core distance and no edge: label -1,
 probability 0.  ``method="grid"`` takes the searches of a 2-D map from ``MapIndex``.  There is no CPU fallback.
+
+New rows (csrc/hdbscan_predict.hip).  ``ClusterModel.predict`` answers a row ``q`` that was not
+fitted from ONE neighbour search.  ``core(q)`` is the distance to its ``(min_samples - 1)``-th nearest eligible bank row
+-- the value it would have as a row of the bank; the bank's own core distances do not move --, ``w(q, b) = max(dist(q, b),
+core(q), core(b))`` in fp32, and the *nearest mutual-reachability neighbour* is the eligible bank row with the smallest
+``(w, b)`` among ALL of them: the offer kernel takes it from the list of ``max(search_k, min_samples - 1, 1)`` rows where
+the list proves it (the list is not full, or ``w`` is STRICTLY below what a row outside the list can have), the other rows
+are asked again by ``radius`` at the weight found.  ``lambda_q = 1 / w`` in float64; from the cluster the neighbour fell
+out of the row climbs, if the neighbour left it later than ``lambda_q``, to the cluster alive at ``lambda_q`` (a cluster
+born AT ``lambda_q`` is left: everything that joins at one weight joins the parent); the label is that cluster's, the
+strength ``min(lambda_q, m) / m`` as for a fitted row, the GLOSH score ``1 - min(lambda_q, death) / death`` with ``death``
+the largest lambda below the cluster.  Fewer than ``min_samples - 1`` eligible rows: label -1, strength 0, score 1; a
+non-finite row: -1, 0, NaN.  Every step is one correctly rounded operation on the search's fp32 distances, so a row's
+answer does not depend, bit for bit, on the other rows of the call, on ``search_k``, ``splits``, the method or the run.
+Departures from the ``hdbscan`` library's ``approximate_predict``: the exact nearest neighbour instead of the best of
+``2 * min_samples``, this library's core-distance rule, the multiway tree, and ``lam_zero`` at ``w = 0``.
 """
 from __future__ import annotations
 
@@ -47,7 +66,7 @@ from . import _lib
 from .mapindex import MapIndex, check_grid_method
 from .neighbors import EmbeddingIndex, _check_method, _check_splits, _groups, _metric, _ptr, _rows
 
-__all__ = ["hdbscan", "mutual_reachability_mst", "MutualReachabilityMST", "ClusterTree"]
+__all__ = ["hdbscan", "mutual_reachability_mst", "MutualReachabilityMST", "ClusterTree", "ClusterModel"]
 
 SELECTION_METHODS = tuple(_lib.HDBSCAN_METHOD)
 U = 2.0 ** -24
@@ -120,6 +139,32 @@ def _slack(index) -> Tuple[Optional[torch.Tensor], int, float]:
     return (tau * (1 + 2.0 ** -20)).to(torch.float32), 1, rel
 
 
+def _index_of(emb_or_index, groups, method: str, metric: str, what: str = "tree"):
+    """The index ``mutual_reachability_mst`` and ``ClusterModel`` search: the one given (it brings its own metric and
+    groups), or one built on the rows -- a ``MapIndex`` with ``method="grid"``."""
+    if isinstance(emb_or_index, (EmbeddingIndex, MapIndex)):
+        index = emb_or_index
+        if groups is not None:
+            raise ValueError("groups= next to an index: the " + what + " uses the index's own groups (build the index with "
+                             "groups=...)" + ("" if index.groups is None else "; this one already has them"))
+        index_metric = getattr(index, "metric", "euclidean")
+        if metric != index_metric:
+            raise ValueError(f"metric = {metric!r}, the index holds {index_metric!r}")
+    else:
+        _metric(metric)
+        if method == "grid":
+            check_grid_method(int(emb_or_index.shape[1]) if isinstance(emb_or_index, torch.Tensor)
+                              and emb_or_index.dim() == 2 else None, metric)
+        if groups is not None and (not isinstance(groups, torch.Tensor) or groups.dtype != torch.int64):
+            raise ValueError("groups must be an int64 torch.Tensor, got "
+                             f"{groups.dtype if isinstance(groups, torch.Tensor) else type(groups).__name__}")
+        rows = _rows(emb_or_index, "emb")
+        if groups is not None:
+            groups = _groups(groups, "groups", int(rows.shape[0]), rows.device)
+        index = MapIndex(rows, groups=groups) if method == "grid" else EmbeddingIndex(rows, metric, groups=groups)
+    return index
+
+
 def mutual_reachability_mst(emb_or_index: Union[torch.Tensor, EmbeddingIndex, MapIndex], min_samples: int = 5,
                             groups: Optional[torch.Tensor] = None, method: str = "tiles", search_k: int = 8,
                             stats: Optional[dict] = None, *, metric: str = "euclidean",
@@ -139,26 +184,7 @@ def mutual_reachability_mst(emb_or_index: Union[torch.Tensor, EmbeddingIndex, Ma
     ``RuntimeError``.  Host reads per round: the unresolved rows, the radius search's own, the number of components."""
     _check_mst_args(min_samples, search_k, splits, stats)
     _check_method(method)
-    if isinstance(emb_or_index, (EmbeddingIndex, MapIndex)):
-        index = emb_or_index
-        if groups is not None:
-            raise ValueError("groups= next to an index: the tree uses the index's own groups (build the index with "
-                             "groups=...)" + ("" if index.groups is None else "; this one already has them"))
-        index_metric = getattr(index, "metric", "euclidean")
-        if metric != index_metric:
-            raise ValueError(f"metric = {metric!r}, the index holds {index_metric!r}")
-    else:
-        _metric(metric)
-        if method == "grid":
-            check_grid_method(int(emb_or_index.shape[1]) if isinstance(emb_or_index, torch.Tensor)
-                              and emb_or_index.dim() == 2 else None, metric)
-        if groups is not None and (not isinstance(groups, torch.Tensor) or groups.dtype != torch.int64):
-            raise ValueError("groups must be an int64 torch.Tensor, got "
-                             f"{groups.dtype if isinstance(groups, torch.Tensor) else type(groups).__name__}")
-        rows = _rows(emb_or_index, "emb")
-        if groups is not None:
-            groups = _groups(groups, "groups", int(rows.shape[0]), rows.device)
-        index = MapIndex(rows, groups=groups) if method == "grid" else EmbeddingIndex(rows, metric, groups=groups)
+    index = _index_of(emb_or_index, groups, method, metric)
     grid = isinstance(index, MapIndex)
     if grid and splits:
         raise ValueError("a MapIndex has no splits")
@@ -272,6 +298,31 @@ def _tree_host(edges: np.ndarray, weights: np.ndarray, n: int, min_cluster_size:
     return labels, prob, (cp[:m].copy(), cc[:m].copy(), cl[:m].copy(), cs[:m].copy())
 
 
+def _model_host(edges: np.ndarray, weights: np.ndarray, n: int, min_cluster_size: int, method: str = "eom",
+                allow_single_cluster: bool = False) -> dict:
+    """``btsbot_hdbscan_model`` on host arrays: the tables of a fitted tree as numpy arrays -- ``row_cluster`` int32 [n],
+    ``row_lambda`` and ``outlier`` float64 [n]; ``parent`` int32, ``birth`` float64, ``label`` int32, ``max_lambda`` and
+    ``death`` float64 [nc] -- and ``lam_zero``, a float."""
+    _check_selection(min_cluster_size, method, allow_single_cluster)
+    edges = np.ascontiguousarray(edges, dtype=np.int64).reshape(-1, 2)
+    weights = np.ascontiguousarray(weights, dtype=np.float32)
+    if edges.shape[0] != weights.shape[0]:
+        raise ValueError(f"{edges.shape[0]} edges, {weights.shape[0]} weights")
+    cap = max(n - 1, 1)
+    t = dict(row_cluster=np.empty(n, np.int32), row_lambda=np.empty(n, np.float64), outlier=np.empty(n, np.float64),
+             parent=np.empty(cap, np.int32), birth=np.empty(cap, np.float64), label=np.empty(cap, np.int32),
+             max_lambda=np.empty(cap, np.float64), death=np.empty(cap, np.float64))
+    nc, lam_zero = C.c_int64(0), C.c_double(0.0)
+    _lib.check(_lib.lib().btsbot_hdbscan_model(C.c_void_p(edges.ctypes.data), C.c_void_p(weights.ctypes.data),
+                                               edges.shape[0], n, min_cluster_size, _lib.HDBSCAN_METHOD[method],
+                                               int(allow_single_cluster), *(C.c_void_p(a.ctypes.data) for a in t.values()),
+                                               cap, C.byref(nc), C.byref(lam_zero)), "btsbot_hdbscan_model")
+    for name in ("parent", "birth", "label", "max_lambda", "death"):
+        t[name] = t[name][:nc.value].copy()
+    t["lam_zero"] = lam_zero.value
+    return t
+
+
 class ClusterTree:
     """The hierarchy of one spanning tree, asked with any parameters afterwards: ``labels`` runs the host pass of the
     library (O(n log n), no GPU call), ``cut`` the component kernels on the tree's device."""
@@ -293,6 +344,14 @@ class ClusterTree:
         lab, prob, self.condensed = _tree_host(self._edges, self._weights, self.n, min_cluster_size, method,
                                                allow_single_cluster)
         return torch.from_numpy(lab).to(self.device), torch.from_numpy(prob).to(self.device)
+
+    def outlier_scores(self, min_cluster_size: int = 5) -> torch.Tensor:
+        """GLOSH (Campello et al. 2015) of the fitted rows, float64 [N] on the tree's device: ``1 - lambda_row / death``
+        with ``death`` the largest lambda at which any row leaves the subtree of the cluster the row fell out of -- 0 for
+        the rows that stay to the end, towards 1 for a row that leaves long before; 0 where that ``death`` is 0, NaN for a
+        non-finite row.  The score does not depend on which clusters are selected.  The host pass, no GPU call."""
+        t = _model_host(self._edges, self._weights, self.n, min_cluster_size)
+        return torch.from_numpy(t["outlier"]).to(self.device)
 
     def cut(self, eps: float, min_cluster_size: int = 1) -> torch.Tensor:
         """DBSCAN* at ``eps``: int64 [N], the components of the tree's edges with ``w <= eps`` among the rows with
@@ -341,3 +400,159 @@ def hdbscan(emb: torch.Tensor, min_cluster_size: int = 5, min_samples: Optional[
     tree = ClusterTree(mst)
     labels, prob = tree.labels(min_cluster_size, cluster_selection_method, allow_single_cluster)
     return (labels, prob, tree) if return_tree else (labels, prob)
+
+
+def _query_slack(index, queries: torch.Tensor, bank_sq_max: Optional[torch.Tensor]):
+    """``_slack`` for NEW rows: (slack [Q] or None, squared?, rel) of ``btsbot_cluster_offer_knn``.  The tile search's
+    bound is tau = 8 (D + 2, or D + 6 below D = 4) u (|q|^2 + max |b|^2) with the QUERY's own |q|^2."""
+    if isinstance(index, MapIndex):
+        return None, 0, 0.0
+    d = index.dim
+    rel = 4 * (d + 4) * U
+    if index.metric == "cosine":
+        return torch.full((int(queries.shape[0]),), 8 * (d + 2) * U, dtype=torch.float32, device=index.device), 0, rel
+    sq = (queries.to(torch.float64) ** 2).sum(dim=1)
+    sq = torch.where(torch.isfinite(sq), sq, torch.zeros_like(sq))
+    tau = 8 * (d + 2 if d >= 4 else d + 6) * U * (sq + bank_sq_max)
+    return (tau * (1 + 2.0 ** -20)).to(torch.float32), 1, rel
+
+
+class ClusterModel:
+    """The HDBSCAN fit of a bank, kept to assign new rows to its clusters (see the module text).
+
+    bank_or_index: rows float [N, D] (an index is built on them, with ``groups``: an ``EmbeddingIndex``, or a ``MapIndex``
+    with ``method="grid"``), an ``EmbeddingIndex`` or a ``MapIndex``.  An index brings its own metric and groups:
+    ``groups=`` next to an index is a ``ValueError``.  The other arguments are ``hdbscan``'s; ``search_k`` and ``splits``
+    are those of the fit's rounds.  ``labels`` int64, ``prob`` and ``outlier_scores`` float64 [N] are the fit -- ``labels``
+    and ``prob`` are ``hdbscan``'s, ``outlier_scores`` is ``tree.outlier_scores(min_cluster_size)`` --, ``tree``, ``mst``
+    and ``index`` what it was made of.  The tables ``predict`` walks live on the index's device.
+
+    The fit does not follow ``index.add``; ``refit()`` recomputes it, and ``predict`` refuses an index that has grown
+    since.  Calls on one model must be ordered by the caller's streams.  There is no CPU fallback."""
+
+    def __init__(self, bank_or_index: Union[torch.Tensor, EmbeddingIndex, MapIndex], min_cluster_size: int = 5,
+                 min_samples: Optional[int] = None, metric: str = "euclidean", *, cluster_selection_method: str = "eom",
+                 allow_single_cluster: bool = False, groups: Optional[torch.Tensor] = None, method: str = "tiles",
+                 search_k: int = 8, splits: int = 0):
+        _check_selection(min_cluster_size, cluster_selection_method, allow_single_cluster)
+        if min_samples is None:
+            min_samples = min_cluster_size
+        _check_mst_args(min_samples, search_k, splits, None)
+        _check_method(method)
+        self.index = _index_of(bank_or_index, groups, method, metric, "model")
+        if isinstance(self.index, MapIndex) and splits:
+            raise ValueError("a MapIndex has no splits")
+        self.min_cluster_size, self.min_samples = min_cluster_size, min_samples
+        self.cluster_selection_method, self.allow_single_cluster = cluster_selection_method, allow_single_cluster
+        self.metric = getattr(self.index, "metric", "euclidean")
+        self.search_k, self.splits = search_k, splits
+        self.device = self.index.device
+        self.refit()
+
+    def __len__(self) -> int:
+        """The rows the fit covers."""
+        return int(self.labels.shape[0])
+
+    def refit(self) -> "ClusterModel":
+        """Fits the rows the index holds now (after ``index.add``): the spanning tree's rounds, the host pass, and the
+        copy of its tables to the device."""
+        dev = self.device
+        self.mst = mutual_reachability_mst(self.index, self.min_samples, search_k=self.search_k, metric=self.metric,
+                                           splits=self.splits)
+        self.tree = ClusterTree(self.mst)
+        self.labels, self.prob = self.tree.labels(self.min_cluster_size, self.cluster_selection_method,
+                                                  self.allow_single_cluster)
+        t = _model_host(self.tree._edges, self.tree._weights, self.tree.n, self.min_cluster_size,
+                        self.cluster_selection_method, self.allow_single_cluster)
+        self.lam_zero = t.pop("lam_zero")
+        self.tables = {k: torch.from_numpy(v).to(dev) for k, v in t.items()}
+        self.outlier_scores = self.tables["outlier"]
+        self._bank_sq_max = None
+        if isinstance(self.index, EmbeddingIndex) and self.metric == "euclidean":
+            sq = (self.index.bank.to(torch.float64) ** 2).sum(dim=1)
+            self._bank_sq_max = torch.where(torch.isfinite(sq), sq, torch.zeros_like(sq)).max()
+        return self
+
+    def _offer(self, idx: torch.Tensor, dist: torch.Tensor, q: torch.Tensor):
+        """btsbot_cluster_offer_knn on the lists of the rows ``q``: (core_q, best_w, best_j, unresolved)"""
+        nq, k, dev = int(idx.shape[0]), int(idx.shape[1]), self.device
+        slack, squared, rel = _query_slack(self.index, q, self._bank_sq_max)
+        core_q = torch.empty(nq, dtype=torch.float32, device=dev)
+        best_w = torch.empty(nq, dtype=torch.float32, device=dev)
+        best_j = torch.empty(nq, dtype=torch.int32, device=dev)
+        unres = torch.empty(nq, dtype=torch.uint8, device=dev)
+        _lib.check(_lib.lib().btsbot_cluster_offer_knn(_ptr(idx), _ptr(dist), nq, k, len(self), self.min_samples,
+                                                       _ptr(self.mst.core), _ptr(slack), squared, rel, _ptr(core_q),
+                                                       _ptr(best_w), _ptr(best_j), _ptr(unres), _stream(dev)),
+                   "btsbot_cluster_offer_knn")
+        return core_q, best_w, best_j, unres
+
+    def _assign(self, best_w: torch.Tensor, best_j: torch.Tensor):
+        """btsbot_cluster_assign: (labels, prob, outlier, lambda, cluster, neighbor) of the rows' neighbours"""
+        nq, dev, t = int(best_w.shape[0]), self.device, self.tables
+        labels, cluster, neighbor = (torch.empty(nq, dtype=torch.int64, device=dev) for _ in range(3))
+        prob, outlier, lam = (torch.empty(nq, dtype=torch.float64, device=dev) for _ in range(3))
+        _lib.check(_lib.lib().btsbot_cluster_assign(_ptr(best_w), _ptr(best_j), nq, len(self), _ptr(t["row_cluster"]),
+                                                    _ptr(t["row_lambda"]), int(t["parent"].shape[0]), _ptr(t["parent"]),
+                                                    _ptr(t["birth"]), _ptr(t["label"]), _ptr(t["max_lambda"]),
+                                                    _ptr(t["death"]), self.lam_zero, _ptr(labels), _ptr(prob),
+                                                    _ptr(outlier), _ptr(lam), _ptr(cluster), _ptr(neighbor), _stream(dev)),
+                   "btsbot_cluster_assign")
+        return labels, prob, outlier, lam, cluster, neighbor
+
+    def predict(self, queries: torch.Tensor, query_groups: Optional[torch.Tensor] = None, exclude_same_group: bool = False,
+                search_k: Optional[int] = None, stats: Optional[dict] = None, *, return_details: bool = False,
+                splits: Optional[int] = None):
+        """``labels`` int64 [Q] (-1: noise) and ``prob`` float64 [Q] of NEW rows ``queries`` [Q, D] against the fitted
+        clusters; with ``return_details`` also a dict of ``neighbor`` int64 (the nearest mutual-reachability neighbour,
+        -1 without one), ``lambda`` float64, ``outlier`` float64 (GLOSH) and ``cluster`` int64 (the condensed tree's
+        cluster less N, -1 without one), [Q] each.  query_groups / exclude_same_group: as ``EmbeddingIndex.query`` --
+        leave out the rows of the query's own object, from the row's density and from its neighbours.  search_k: the
+        list length, 1..64; None = ``min(64, max(8, 2 * min_samples))``; the list holds ``max(search_k, min_samples - 1,
+        1)`` rows and no answer depends on it.  splits: ``EmbeddingIndex.query``'s (None: the model's).  stats: a dict
+        that receives ``unresolved`` (rows sent to the radius tier) and ``radius_total`` (entries of their lists).  One
+        host read, the unresolved rows, and the radius search's own when there are any."""
+        if len(self.index) != len(self):
+            raise RuntimeError(f"the index holds {len(self.index)} rows, the fit {len(self)}: a fit does not follow "
+                               "index.add -- call refit()")
+        ms = self.min_samples
+        if search_k is None:
+            search_k = min(_lib.MST_MAX_K, max(8, 2 * ms))
+        if splits is None:
+            splits = self.splits
+        _check_mst_args(ms, search_k, splits, stats)
+        if not isinstance(return_details, bool):
+            raise ValueError(f"return_details must be a bool, got {return_details!r}")
+        index, dev, L = self.index, self.device, _lib.lib()
+        grid = isinstance(index, MapIndex)
+        if grid and splits:
+            raise ValueError("a MapIndex has no splits")
+        k = max(search_k, ms - 1, 1)
+        kw = dict(query_groups=query_groups, exclude_same_group=exclude_same_group)
+        if not grid:
+            kw["splits"] = splits
+        idx, dist = index.query(queries, k, **kw)
+        nq, n = int(idx.shape[0]), len(self)
+        with torch.cuda.device(dev):
+            q = queries.detach().to(torch.float32).contiguous()
+            core_q, best_w, best_j, unres = self._offer(idx, dist, q)
+            todo = unres.nonzero().view(-1)                       # the host read: the rows of the radius tier
+            total = 0
+            if todo.numel():
+                st = {}
+                rkw = dict(exclude_same_group=exclude_same_group, stats=st)
+                if query_groups is not None:
+                    rkw["query_groups"] = query_groups[todo]
+                if not grid:
+                    rkw["splits"] = splits
+                indptr, indices, rdist = index.radius(q[todo], best_w[todo], **rkw)
+                total = st["total"]
+                _lib.check(L.btsbot_cluster_offer_csr(_ptr(indptr), _ptr(indices), _ptr(rdist), _ptr(todo),
+                                                      int(todo.numel()), nq, n, _ptr(self.mst.core), _ptr(core_q),
+                                                      _ptr(best_w), _ptr(best_j), _stream(dev)), "btsbot_cluster_offer_csr")
+            labels, prob, outlier, lam, cluster, neighbor = self._assign(best_w, best_j)
+        if stats is not None:
+            stats.update(unresolved=int(todo.numel()), radius_total=int(total))
+        if return_details:
+            return labels, prob, {"neighbor": neighbor, "lambda": lam, "outlier": outlier, "cluster": cluster}
+        return labels, prob

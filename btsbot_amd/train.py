@@ -316,30 +316,39 @@ def policy_summary(cand, raw_preds, labels, device="cuda") -> dict:
 def cluster_config(clu) -> dict:
     """``config['embedding_clusters']`` checked and completed.  ``"algorithm": "dbscan"`` (the default) takes ``eps``
     (required), ``min_samples`` (5); ``"hdbscan"`` takes ``min_cluster_size`` (5) and ``min_samples`` (None: the same)
-    and no ``eps``; both take ``on`` (``"map"`` or ``"embedding"``) and ``method`` (``"tiles"`` or ``"grid"``)."""
+    and no ``eps``, and ``outlier_scores`` (a bool; the result holds the key only when it is given and true); both take
+    ``on`` (``"map"`` or ``"embedding"``) and ``method`` (``"tiles"`` or ``"grid"``)."""
     algorithm = clu.get("algorithm", "dbscan") if isinstance(clu, dict) else None
-    own = {"dbscan": {"eps", "min_samples"}, "hdbscan": {"min_cluster_size", "min_samples"}}.get(algorithm, set())
+    own = {"dbscan": {"eps", "min_samples"},
+           "hdbscan": {"min_cluster_size", "min_samples", "outlier_scores"}}.get(algorithm, set())
     unknown = set(clu) - own - {"algorithm", "on", "method"} if isinstance(clu, dict) else {"?"}
     if (unknown or algorithm not in ("dbscan", "hdbscan") or (algorithm == "dbscan" and "eps" not in clu)
+            or not isinstance(clu.get("outlier_scores", False), bool)
             or clu.get("on", "map") not in ("map", "embedding") or clu.get("method", "tiles") not in ("tiles", "grid")):
         raise ValueError("config['embedding_clusters'] is a dict with the keys eps, min_samples, on "
                          "('map' or 'embedding') and method ('tiles' or 'grid') -- or, with algorithm = 'hdbscan', "
-                         f"min_cluster_size and min_samples in place of eps --, got {clu!r}")
+                         "min_cluster_size, min_samples and outlier_scores (a bool) in place of eps --, "
+                         f"got {clu!r}")
     tail = dict(on=clu.get("on", "map"), method=clu.get("method", "tiles"))
     if algorithm == "dbscan":
         return dict(algorithm=algorithm, eps=float(clu["eps"]), min_samples=int(clu.get("min_samples", 5)), **tail)
     ms = clu.get("min_samples")
+    if clu.get("outlier_scores"):
+        tail["outlier_scores"] = True
     return dict(algorithm=algorithm, min_cluster_size=int(clu.get("min_cluster_size", 5)),
                 min_samples=None if ms is None else int(ms), **tail)
 
 
 def _cluster_rows(rows, clu: dict):
-    """(labels, membership probabilities or None) of ``rows`` by a checked ``cluster_config``"""
+    """(labels, membership probabilities or None, GLOSH outlier scores or None) of ``rows`` by a checked
+    ``cluster_config``"""
     if clu["algorithm"] == "hdbscan":
         from .hdbscan import hdbscan
-        return hdbscan(rows, clu["min_cluster_size"], clu["min_samples"], method=clu["method"])
+        labels, prob, tree = hdbscan(rows, clu["min_cluster_size"], clu["min_samples"], method=clu["method"],
+                                     return_tree=True)
+        return labels, prob, tree.outlier_scores(clu["min_cluster_size"]) if clu.get("outlier_scores") else None
     from .clusters import dbscan
-    return dbscan(rows, clu["eps"], clu["min_samples"], method=clu["method"])[0], None
+    return dbscan(rows, clu["eps"], clu["min_samples"], method=clu["method"])[0], None, None
 
 
 def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, stem: str, batch_size: int = 1024,
@@ -363,7 +372,8 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
     (``clusters.dbscan``; -1 = noise) of the map, as a ``cluster`` column of ``{stem}_umap.csv``, or of the embedding
     rows, as ``{stem}_clusters.npy`` (int64 [N]).  With ``"algorithm": "hdbscan"`` in that dict (``min_cluster_size``,
     ``min_samples`` in place of ``eps``; ``cluster_config``) the labels are ``hdbscan.hdbscan``'s and the membership
-    strengths are left as ``{stem}_cluster_prob.npy`` (float64 [N]).  ``config['embedding_layout']`` also takes ``"quality": True | k``:
+    strengths are left as ``{stem}_cluster_prob.npy`` (float64 [N]), and with ``"outlier_scores": True`` next to it the
+    GLOSH scores as ``{stem}_cluster_outlier.npy`` (float64 [N]).  ``config['embedding_layout']`` also takes ``"quality": True | k``:
     ``write_map_quality`` leaves ``{stem}_umap_quality.json``, the map's trustworthiness, continuity and neighbour recall
     at ``k`` (``True``: the layout's ``n_neighbors``).  Returns the .npy path."""
     import numpy as np
@@ -432,10 +442,12 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
             raise ValueError("config['embedding_clusters'] with on='map' clusters the map of config['embedding_layout'], "
                              "which is not set")
         if clu["on"] == "embedding":
-            labels, prob = _cluster_rows(torch.from_numpy(out).to(dev), clu)
+            labels, prob, glosh = _cluster_rows(torch.from_numpy(out).to(dev), clu)
             np.save(stem + "_clusters.npy", labels.cpu().numpy())
             if prob is not None:
                 np.save(stem + "_cluster_prob.npy", prob.cpu().numpy())
+            if glosh is not None:
+                np.save(stem + "_cluster_outlier.npy", glosh.cpu().numpy())
     if lay:   # opt-in: the UMAP map itself, with the reference's columns (train.py:464)
         import pandas as pd
         from .layout import embedding_layout
@@ -454,10 +466,12 @@ def write_embeddings(model, config: dict, data_base_dir: str, model_dir: str, st
         if "candid" in cand.columns:
             table["candid"] = cand["candid"].to_numpy()
         if clu and clu["on"] == "map":
-            labels, prob = _cluster_rows(y_dev, clu)
+            labels, prob, glosh = _cluster_rows(y_dev, clu)
             table["cluster"] = labels.cpu().numpy()
             if prob is not None:
                 np.save(stem + "_cluster_prob.npy", prob.cpu().numpy())
+            if glosh is not None:
+                np.save(stem + "_cluster_outlier.npy", glosh.cpu().numpy())
         pd.DataFrame(table).to_csv(stem + "_umap.csv", index=False)
     return stem + ".npy"
 

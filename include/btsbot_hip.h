@@ -1235,6 +1235,64 @@ int btsbot_hdbscan_tree(const int64_t* edges, const float* weights, int64_t n_ed
                         int64_t* cond_child, double* cond_lambda, int64_t* cond_size, int64_t cond_capacity,
                         int64_t* n_cond);
 
+/* ---- HDBSCAN for new rows: the tables of a fitted tree and the prediction (csrc/hdbscan_tree.hip,
+ *      csrc/hdbscan_predict.hip) ---- */
+
+/* btsbot_hdbscan_model(): the same pass as btsbot_hdbscan_tree() on the same inputs (HOST arrays, no GPU call, the same
+ * errors), handing out the tables a prediction walks.  Clusters are in the canonical numbering less n: ids 0 ..
+ * *n_clusters - 1, cluster c is condensed id n + c, the root is 0, a parent stands before its children.
+ * Per row [n]: row_cluster int32, the cluster the row fell out of (-1: a row without an entry); row_lambda float64, the
+ * lambda it fell out at (0 without an entry); outlier float64, the GLOSH score 1 - row_lambda / death[row_cluster] (0 where
+ * that death is 0, NaN for a row without an entry).  Per cluster [cluster_capacity >= *n_clusters; max(n - 1, 1) always
+ * suffices]: parent int32 (-1: the root); birth float64; label int32, the label of the nearest selected ancestor-or-self
+ * (-1 without one); max_lambda float64, the largest lambda of that selected cluster's own entries (0 where label is -1):
+ * labels[r] = label[row_cluster[r]] and prob[r] = min(row_lambda[r], m) / m with m = max_lambda[row_cluster[r]] (1 where
+ * m = 0, 0 where the label is -1) are btsbot_hdbscan_tree()'s, bit for bit; death float64, the largest lambda of any entry
+ * in the cluster's subtree.  *lam_zero: the lambda that stands for w = 0 (1 without a positive weight). */
+int btsbot_hdbscan_model(const int64_t* edges, const float* weights, int64_t n_edges, int64_t n, int min_cluster_size,
+                         int method, int allow_single_cluster, int32_t* row_cluster, double* row_lambda, double* outlier,
+                         int32_t* parent, double* birth, int32_t* label, double* max_lambda, double* death,
+                         int64_t cluster_capacity, int64_t* n_clusters, double* lam_zero);
+
+/* The cluster of NEW rows against a fitted tree, after idx int64 [n_query][k], dist fp32 [n_query][k] =
+ * btsbot_knn_query*() / btsbot_grid_knn() of the rows against the bank with k >= max(min_samples - 1, 1).  core fp32 [n]:
+ * the bank's core distances (btsbot_mst_*'s).  All three are queued on `stream`; nothing allocates, synchronises or copies
+ * to the host.
+ *
+ * btsbot_cluster_offer_knn(): core_q fp32 [n_query]: the row's own core distance, column min_samples - 2 of its list (0 for
+ * min_samples = 1, +inf where that column is absent, NaN for a non-finite row: dist NaN throughout).  best_w fp32, best_j
+ * int32 [n_query]: the entry with the smallest (w, index), w = max(dist, core_q, core[index], 0) in fp32; -1 / +inf where
+ * the list is empty or core_q is +inf, -1 / NaN for a non-finite row.  unresolved uint8 [n_query] = 0 where the list proves
+ * that no bank row has a smaller (w, index): the list is not full, or best_w < floor -- STRICTLY; a row the list does not
+ * hold may tie a weight at a smaller index, and two rows of one weight can lie in different clusters --, floor as in
+ * btsbot_mst_offer_knn() with slack fp32 [n_query] per QUERY row.  1 where it does not: every row with a smaller (w,
+ * index) then lies within the radius best_w.  One launch, W = 16, 32 or 64 lanes per row.
+ *
+ * btsbot_cluster_offer_csr(): indptr int64 [m + 1], indices int64, dist fp32: the radius lists (bank rows within best_w)
+ * of the m query rows `rows` int64 [m]; lowers (best_w, best_j) of these rows to the smallest (w, index).  One launch,
+ * one wave per row.
+ *
+ * btsbot_cluster_assign(): with b = best_j and lambda = 1 / (double) best_w (lam_zero at 0): c = row_cluster[b]; if
+ * row_lambda[b] > lambda, while parent[c] >= 0 and birth[c] >= lambda: c = parent[c].  out_label int64 = label[c];
+ * out_prob float64 = min(lambda, max_lambda[c]) / max_lambda[c] (1 where that is 0, 0 where the label is -1);
+ * out_outlier float64 = 1 - min(lambda, death[c]) / death[c] (0 where death[c] is 0); out_lambda float64; out_cluster
+ * int64 = c; out_neighbor int64 = b.  A row without a neighbour: -1, 0, 1, 0, -1, -1; a non-finite row: -1, 0, NaN, NaN,
+ * -1, -1.  Each operation is one correctly rounded IEEE operation, none contracted.  The tables are
+ * btsbot_hdbscan_model()'s, in device memory.  One launch, one lane per row.
+ * All three: BTSBOT_ERR_INVALID_ARG for a size outside 0 .. 2^31 - 1, k outside 1..64, min_samples outside 1..k + 1, rel
+ * outside [0, 1), lam_zero <= 0, a NULL pointer that is needed; n_query == 0 launches nothing. */
+int btsbot_cluster_offer_knn(const int64_t* idx, const float* dist, int64_t n_query, int k, int64_t n, int min_samples,
+                             const float* core, const float* slack, int slack_is_squared, float rel, float* core_q,
+                             float* best_w, int32_t* best_j, uint8_t* unresolved, void* stream);
+int btsbot_cluster_offer_csr(const int64_t* indptr, const int64_t* indices, const float* dist, const int64_t* rows,
+                             int64_t m, int64_t n_query, int64_t n, const float* core, const float* core_q, float* best_w,
+                             int32_t* best_j, void* stream);
+int btsbot_cluster_assign(const float* best_w, const int32_t* best_j, int64_t n_query, int64_t n,
+                          const int32_t* row_cluster, const double* row_lambda, int64_t n_clusters, const int32_t* parent,
+                          const double* birth, const int32_t* label, const double* max_lambda, const double* death,
+                          double lam_zero, int64_t* out_label, double* out_prob, double* out_outlier, double* out_lambda,
+                          int64_t* out_cluster, int64_t* out_neighbor, void* stream);
+
 /* Replaces: the epoch / validation metrics of val.py:159-168 and train.py:550-558 -- out2[0] += sum_i of
  * BCEWithLogitsLoss(pos_weight) terms over n logits, out2[1] += number of alerts whose sigmoid(z) > 0.5
  * agrees with the label (caller zeroes out2 and divides by n). */

@@ -267,7 +267,7 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
       a.tap_stage = k.xs[1];
       a.keep_patches = k.patches[2];
       a.B = B;
-      TRY(launch_stage1b(c.precision, a, st));
+      TRY(launch_stage1b(c.precision, a, false, st));
       continue;
     }
     if (i == 2 && s2t) {

@@ -81,7 +81,7 @@ int backbone_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, floa
         a.stamps = h->stamps ? h->stamps + STAMP_S1 : nullptr;
         a.wgt = stamp_wgt(h, STAMP_S1_WG, STAMP_S1_MAX_WG, (nb + 1) / 2);
         TRY(timed(h, CAT_STAGE1, st, [&] {
-          return launch_stage1b(h->prec_s01(), a, st);
+          return launch_stage1b(h->prec_s01(), a, sc.s1_g5, st);
         }));
         float* t = x;
         x = x2;

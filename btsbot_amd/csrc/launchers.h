@@ -125,7 +125,7 @@ int launch_pack_s0par(int prec, const float* taps, const float* dw_b, const floa
 // ---- stage1b.hip
 struct Stage1Args;
 bool stage1_supported(int prec, int c1, int c2);   // stage1b.hip
-int launch_stage1b(int prec, const Stage1Args& a, hipStream_t st);   // stage1b.hip
+int launch_stage1b(int prec, const Stage1Args& a, bool g5, hipStream_t st);   // stage1b.hip
 size_t s1par_bytes();
 int launch_pack_frag32(int prec, const float* src, void* dst, int cout, int cin, hipStream_t st);   // stage1b.hip
 int launch_pack_s1par(int prec, const float* taps, const float* dw_b, const float* ln_w,

@@ -89,6 +89,7 @@ bool switch_set(Switch s);   // present at all, whatever its value
   X(stage1)       /* stage 1 + second downsample as one kernel (stage1b.hip) */                                        \
   X(stage2p)      /* stage 2 + last downsample as one persistent kernel (stage2p.hip) */                               \
   X(stage3)       /* the 1x1 stage as two fragment-streaming launches per block (stage3.hip) */                        \
+  X(s1_g5)        /* stage1b on five alerts per 512-thread workgroup: 205 of them at 1024 alerts (options below) */    \
   X(s2p_g7)       /* stage2p keeps 7 alerts per workgroup at every batch size (options below) */                       \
   X(s3_wide)      /* stage3.hip on 64-alert fc1 / 64-channel fc2 tiles: half the workgroups (options below) */         \
   X(head16)       /* the head on the matrix pipe (head16.hip); off: the fp32 head (head.hip) */                        \
@@ -122,6 +123,7 @@ bool switch_set(Switch s);   // present at all, whatever its value
 //   "train_split"        0 | 1        train_split
 //   "stage2p_alerts"     0, 4, 5, 7   s2p_alerts (0: forwards_in_flight's choice, else the kernel's by rounds), s2p_g7
 //   "forwards_in_flight" 0 | 1        other forwards run beside this handle's: forms that hold fewer CUs per launch --
+//                                     s1_g5 in the bf16 / f16 / fp8 modes (same bits as the two-alert form);
 //                                     s2p_alerts = 7 unless "stage2p_alerts" is given; s3_wide at 512 channels in the
 //                                     bf16 / f16 / fp8 modes (split operands: 8 registers per fragment, narrow only)
 struct Schedule {

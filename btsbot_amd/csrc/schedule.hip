@@ -84,6 +84,9 @@ void resolve_schedule(btsbot_ctx* h) {
     s.stage1 = !on(SW_NO_STAGE1) && stage1_supported(h->prec_s01(), c.dims[1], c.dims[2]) && c.depths[1] == 2;
     s.stage2p = !on(SW_NO_STAGE2) && stage2p_supported(h->prec_tail(), c.dims[2], c.dims[3], c.depths[2]);
     s.stage3 = !on(SW_NO_S3) && stage3_supported(h->prec_tail(), c.dims[3], c.depths[3]);
+    // stage 1 on five alerts per workgroup while other forwards are in flight: its launch is 3 us longer than the
+    // two-alert form's and holds 205 CUs instead of 256 at 1024 alerts (the split mode's two planar images hold two alerts)
+    s.s1_g5 = s.stage1 && h->opt_forwards_in_flight && (h->prec_s01() == BTSBOT_BF16 || h->prec_s01() == BTSBOT_F16);
     // stage 2's alerts per workgroup: the caller's number wins, then the overlap hint (7: 147 workgroups at 1024 alerts,
     // the other streams' kernels take the remaining CUs), else the kernel's own choice by rounds
     s.s2p_alerts = h->s2p_alerts_hint != 0 ? h->s2p_alerts_hint : h->opt_forwards_in_flight ? 7 : 0;

@@ -48,7 +48,7 @@ struct Stage0Args {
 };
 
 
-// Stage-1 megakernel (stage1b.hip): two alerts per workgroup, C = 128.
+// Stage-1 megakernel (stage1b.hip): two alerts per workgroup, or five while forwards overlap (Schedule::s1_g5), C = 128.
 struct Stage1Args {
   const float* x_in;      // [B][49][128] f32 (stage-0 output after its downsample)
   Stage0Blk blk[2];       // dw_w is [49][128]

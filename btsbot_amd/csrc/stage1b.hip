@@ -1,6 +1,20 @@
-// Stage-1 megakernel (gfx950): TWO alerts' 7x7x128 maps per 256-thread workgroup, two workgroups per CU:
+// Stage-1 megakernel (gfx950): G alerts' 7x7x128 maps per workgroup:
 //
 //   2 x [ dwconv 7x7 + LN -> fc1 -> GELU -> fc2 -> layer-scale -> +x ]  ->  LN + conv 2x2 s2 (128 -> 256)
+//
+// Two forms of one template (S1L<G, X2> holds what follows G):
+//   G = 5  inference in the bf16 / f16 modes (stage 1 of an fp8 handle too) while other forwards are in flight
+//          (Schedule::s1_g5): 512 threads, the 245 pixels on 245 of 8 x 32 pixel slots, one workgroup per CU (132,944 B
+//          of LDS), ceil(B / 5) workgroups: 205 CUs at 1024 alerts, the others are the other streams'.  A wave
+//          takes ONE group of 16 channels over all five alerts in the depthwise phase (its 21 tap fragments loaded once),
+//          2 of a filter chunk's 16 pieces (waves 0-3 W1, waves 4-7 W2) and one 32-channel tile of the downsample over both
+//          32-column blocks of the 45 output pixels, so a downsample filter fragment is loaded once per workgroup.
+//   G = 2  a lone forward (its launch is 3 us shorter and a lone forward has no use for idle CUs), the keeping forms
+//          (training forward) and the split mode: 256 threads, 98 pixels on 4 x 32 slots, two workgroups per CU (split
+//          mode: one).  Two planar images of five alerts do not fit LDS, and the backward's buffers hold what the keeping
+//          forms keep.  The text below describes this form; where G = 5 differs it says so.
+// Every sum runs in the same order in both forms and in every workgroup (no chunk rotation by workgroup index), so an
+// alert's bits depend neither on G nor on its place in the batch: hinted and plain forwards give the same logits.
 //
 // (timm ConvNeXt stages[1].blocks / stages[2].downsample, reached from
 // /root/reference/btsbot/architectures.py:108,132).  HBM sees [49][128] f32 in and [9][256] f32
@@ -13,7 +27,8 @@
 //     consecutive rows read with one ds_read_b64 from a planar image [alert][x quad][row][channel][4 x]: the
 //     channel-minor order with a 136-entry row pitch makes the 8 blocks x 4 rows of a half wave hit 32 different
 //     8-byte bank slots.  Rows outside the map are one shared zero row (per-lane row offsets), column 7 of
-//     the second quad is kept zero.  Wave = 2 channel groups x both alerts: 224 MFMAs, 88 reads per block
+//     the second quad is kept zero.  Wave = 2 channel groups x both alerts: 224 MFMAs, 88 reads per block (G = 5: one
+//     group x five alerts: 280 MFMAs, 110 reads, no second set of taps to fetch in the middle of the phase)
 //     (the VALU form this replaces: 25k cycles per block, 2 x 49 x 7 FMAs per lane plus conversions);
 //   * LayerNorm: ONE transpose -- behind a barrier that ends every wave's reads of the planar image the depthwise outputs
 //     (lane = channel, registers = pixels) go to LDS as fp32 [98 px][128 ch] with a 528-byte pitch (row p starts at bank
@@ -21,37 +36,40 @@
 //     registers (two-pass fp32 statistics, one __shfl_xor(.., 32) per sum), rounds once to the operand type and holds the
 //     MLP's B operand xf (stage0b.hip).  The image lies in bytes that are dead in that phase: ring slots 0, 1
 //     [0, 32768) and the head of the planar image [32768, 51744).  Every ring slot but W2 slot 0 lies inside it, so
-//     the first filter chunks are requested behind the barrier that ends the row reads, under the LayerNorm arithmetic;
+//     the first filter chunks are requested behind the barrier that ends the row reads, under the LayerNorm arithmetic
+//     (G = 5: [245 px], 129,360 B over ring slots 0, 1, the whole planar image and 9,552 B behind it; every ring slot
+//     lies inside it);
 //   * pointwise filters: chunks of 32 hidden units (8 KB of W1 rows + 8 KB of gamma*W2 columns) through two
-//     3-slot LDS-DMA rings straight from the plain row-major filters (waves 0, 1 load W1, waves 2, 3 load W2); the
+//     3-slot LDS-DMA rings straight from the plain row-major filters (waves 0, 1 load W1, waves 2, 3 load W2; G = 5:
+//     waves 0-3 and 4-7, two pieces each); the
 //     per-lane source address applies the bank swizzles and the bit-2/bit-3 row swap that makes the fc1 accumulator
 //     the fc2 B operand in plain k order (stage0b.hip); fc2 accumulates into the residual registers.  The rings
 //     live in the planar image's and the fp32 LN image's bytes (dead by then).  The chunk loop is software-pipelined
 //     inside the wave: W1 fragments and the fc1 bias of chunk ch+1 are in registers before step ch starts, its fc1
 //     MFMAs issue between the GELUs of chunk ch, chunk ch's fc2 MFMAs between the second half's GELUs.
 //
-// LDS (bytes; split mode in brackets):
-//   [0, 32768)             ring slots 0, 1: W2 slots 1, 2 | the last downsample's 16-bit map(s)
-//   [32768, 67584)         planar image  [.. 102400): two]; its head doubles as W1 slots 0, 1, 2 and W2 slot 0 (4 x 8 KB
-//                          [4 x 16 KB])
-//   [0, 51744)             fp32 LN image [98][528 B], over both of the above
+// LDS (bytes; split mode in brackets, G = 5 in braces):
+//   [0, 32768)             ring slots 0, 1: W2 slots 1, 2 | the last downsample's 16-bit map(s) {[0, 66640): the map
+//                          runs on into the planar image, dead by then}
+//   [32768, 67584)         planar image  [.. 102400): two] {.. 119808): five alerts}; its head doubles as W1 slots 0, 1, 2
+//                          and W2 slot 0 (4 x 8 KB [4 x 16 KB])
+//   [0, 51744)             fp32 LN image [98][528 B], over both of the above {[0, 129360): [245][528 B]}
 //   [102400, 135168)       split mode only: W2 slots 1, 2
-//   OFF_B1   67584 [135168]  fc1 bias [512] | gamma*b2 [128], fp32
-//   OFF_LNW  70144 [137728]  LN weight [128] | LN bias [128], fp32;  end 71168 [138752]
+//   OFF_B1   67584 [135168] {129360}  fc1 bias [512] | gamma*b2 [128], fp32
+//   OFF_LNW  70144 [137728] {131920}  LN weight [128] | LN bias [128], fp32;  end 71168 [138752] {132944}
 #include "stage0.h"
 #include "stage_regs.h"
 #include <type_traits>
 
 namespace {
 
-constexpr int C = 128, HW = 7, PA = 49, G = 2, NPX = G * PA, CT = 4, HID = 512, KS1 = 8;
+constexpr int C = 128, HW = 7, PA = 49, CT = 4, HID = 512, KS1 = 8;
 constexpr int CN = 256, PO = 9;                   // downsample: output channels, pixels per alert
 constexpr int PITCH = 2 * C + 16;                 // [pixel][channel] image: 272 bytes per pixel row
 static_assert(C == StageRegs<CT>::C && PITCH == StageRegs<CT>::PITCH, "ln_regs / regs_to_map derive both from CT");
-constexpr int MAPB = NPX * PITCH;                 // 26656: lives in ring slots 0..1
 constexpr int CHUNKB = 16384, HALFB = CHUNKB / 2, NCH = HID / 32, NSLOT = 3;
 // planar image of the depthwise phase: [alert][x quad 0..1][row 0..6, 7 = zeros][channel, pitch 136][4 x]
-constexpr int PL_ROW = 136 * 8, PL_XQ = 8 * PL_ROW, PL_AL = 2 * PL_XQ, PLB = G * PL_AL;   // 1088, 8704, 17408, 34816
+constexpr int PL_ROW = 136 * 8, PL_XQ = 8 * PL_ROW, PL_AL = 2 * PL_XQ;   // 1088, 8704, 17408 per alert
 constexpr int OFF_PL = 2 * CHUNKB;                // ring slots 0, 1 | planar image (its first 32 KB: W1 slots 0..2, W2 slot 0)
 // Split mode (X2): a second planar image behind the first (the remainders of the map the depthwise phase reads), ring slots of
 // twice the size (a filter piece's remainders 8 KB behind its heads): the W1 slots and W2 slot 0 (64 KB) lie in the two
@@ -60,17 +78,33 @@ constexpr int OFF_PL = 2 * CHUNKB;                // ring slots 0, 1 | planar im
 // the head of the planar image -- all dead between the depthwise phase and the MLP.  Pitch 132 words: row p starts at
 // bank 4 p, a lane's 16-byte reads of its own row are conflict-free.
 constexpr int LNP = 4 * C + 16;                   // 528
-template <bool X2> struct S1L {
+// G = alerts per workgroup: 2 on four waves (the keeping and split forms), 5 on eight waves (inference: 245 of the 256
+// pixel slots live, one workgroup per CU).  What follows G: the waves, the channel groups a wave takes in the depthwise
+// phase, its pieces of a filter chunk, its output tiles and the 32-column blocks of the downsample, and the LDS layout.
+template <int G, bool X2> struct S1L {
+  static_assert(G == 2 || (G == 5 && !X2), "two planar images of five alerts do not fit LDS");
+  static constexpr int NW = G == 2 ? 4 : 8, NT = 64 * NW;       // waves, threads
+  static constexpr int NPX = G * PA;                            // 98 of 128 / 245 of 256 pixel slots
+  static constexpr int NG = 8 / NW;                             // depthwise: channel groups (of 16) per wave
+  static constexpr int NPIECE = 16 / NW;                        // 1 KiB pieces of a filter chunk per wave
+  static constexpr int NCB = (G * PO + 31) / 32;                // downsample: 32-column blocks of output pixels
+  static constexpr int MAPB = NPX * PITCH;                      // 26656 / 66640: the downsample's 16-bit map, from byte 0
+  static constexpr int PLB = G * PL_AL;                         // 34816 / 87040
   static constexpr int PLANES = X2 ? 2 : 1;
   static constexpr int SLB = X2 ? 2 * HALFB : HALFB;            // bytes of a W1 / W2 ring slot
   static constexpr int OFF_W2X = OFF_PL + PLANES * PLB;         // X2 only: W2 slots 1, 2
-  static constexpr int OFF_B1 = OFF_W2X + (X2 ? 2 * SLB : 0);   // 512 floats fc1 bias + 128 floats gamma*b2
+  static constexpr int LNB = NPX * LNP;                         // 51744 / 129360: the fp32 LayerNorm image, from byte 0
+  // 512 floats fc1 bias + 128 floats gamma*b2: behind the planar images (G = 2) resp. behind the fp32 image, which is
+  // longer than ring slots 0, 1 + the planar image at G = 5
+  static constexpr int OFF_B1 = OFF_W2X + (X2 ? 2 * SLB : 0) > LNB ? OFF_W2X + (X2 ? 2 * SLB : 0) : LNB;
   static constexpr int OFF_LNW = OFF_B1 + (HID + C) * 4;        // LayerNorm weight [128] | bias [128], fp32
-  static constexpr int LDS_BYTES = OFF_LNW + 2 * C * 4;         // 71168: two workgroups per CU / 138752
+  static constexpr int LDS_BYTES = OFF_LNW + 2 * C * 4;         // 71168: two workgroups per CU / 138752 / G = 5: 132944
   static_assert(4 * SLB <= PLANES * PLB, "W1 slots + W2 slot 0 inside the planar images");
-  static_assert(NPX * LNP <= OFF_PL + PLB && NPX * LNP <= OFF_B1, "the fp32 image lies in ring slots 0, 1 + the planar image");
+  static_assert(LNB <= OFF_B1 && OFF_B1 % 16 == 0, "the fp32 image ends in front of the bias words");
+  static_assert((X2 ? 2 : 1) * MAPB <= OFF_B1, "the [pixel][channel] image(s) in front of the bias words");
 };
-static_assert(MAPB <= 2 * CHUNKB && S1L<false>::LDS_BYTES <= 75264 && S1L<true>::LDS_BYTES <= 160 * 1024, "LDS layout");
+static_assert(S1L<2, false>::LDS_BYTES <= 75264 && S1L<2, true>::LDS_BYTES <= 160 * 1024 && S1L<5, false>::LDS_BYTES <= 160 * 1024,
+              "LDS layout");
 // per-block parameter image in HBM (launch_pack_s1par): Toeplitz taps in the operand type
 //   [r = ky * 3 + (rb + 1)][channel][i][k] = W[channel][ky][4 rb + k - i + 3]   (0 outside the 7 taps)
 // then fp32: dw bias [128] | LN weight [128] | LN bias [128]
@@ -91,9 +125,9 @@ constexpr int PARB_X2 = 2 * TW_BYTES + 3 * C * 4;
 // (LOPLANE > 0: also the values' f16 remainders, LOPLANE bytes behind -- split mode)
 // (SAT: the value is clamped to the f16 range first -- the keeping forms run their depthwise phase on f16 operands in
 //  every mode, and a bf16 handle's residual stream may exceed 65504: saturate instead of inf -> NaN through the LayerNorm)
-template <typename T, int LOPLANE = 0, bool SAT = false>
+template <typename T, int G, int LOPLANE = 0, bool SAT = false>
 __device__ __forceinline__ void regs_to_planar(const f32x16 (&x)[CT], unsigned char* pl, int p, int h) {
-  const int al = p >= PA ? 1 : 0, pp = p - al * PA;
+  const int al = G == 2 ? (p >= PA ? 1 : 0) : p / PA, pp = p - al * PA;
   const int y = pp / HW, xx = pp - y * HW;
   unsigned char* dst = pl + al * PL_AL + (xx >> 2) * PL_XQ + y * PL_ROW + (xx & 3) * 2 + h * 32;
 #pragma unroll
@@ -111,8 +145,8 @@ __device__ __forceinline__ void regs_to_planar(const f32x16 (&x)[CT], unsigned c
 // WPS = waves per SIMD the register allocation leaves room for (2: two workgroups per CU, 256 registers; 1: one
 // workgroup per CU with 512 registers -- the split mode's doubled fragments spill at 256)
 // KEEP: the training forward (Stage1Args::keep_*): the same kernel plus the copies the backward reads
-template <typename T, bool X2, int WPS = 2, bool KEEP = false>
-__global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
+template <typename T, bool X2, int WPS = 2, bool KEEP = false, int G = 2>
+__global__ __launch_bounds__((S1L<G, X2>::NT), WPS) void stage1b_kernel(Stage1Args a) {
   using frag = typename Mfma<T>::frag;
   // the depthwise phase's operand type: the training forward reads map and taps as f16 in the bf16 mode too -- the
   // map is the fp32 residual stream, and its rounding to bf16 in front of 49 products moved a 50-step bf16 training
@@ -123,8 +157,9 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* pl = smem + OFF_PL;                 // planar image; its first 24 KB double as the W1 ring
   unsigned char* stg = smem;                         // the last downsample's 16-bit image [98][PITCH] in ring slots 0..1
-  using L = S1L<X2>;
-  constexpr int SLB = L::SLB;
+  using L = S1L<G, X2>;
+  static_assert(G == 2 || !KEEP, "the keeping forms hold two alerts");
+  constexpr int SLB = L::SLB, NW = L::NW, NT = L::NT, NPX = L::NPX, NG = L::NG, NPIECE = L::NPIECE, PLB = L::PLB, MAPB = L::MAPB;
   constexpr int PLO = X2 ? PLB : 0;                  // split mode: the planar image of the remainders
   float* b1s = reinterpret_cast<float*>(smem + L::OFF_B1);
   float* b2s = b1s + HID;
@@ -138,7 +173,7 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lr = lane & 31, h = lane >> 5;
-  const bool w1wave = wave < 2;
+  const bool w1wave = wave < NW / 2;
   const int a0 = blockIdx.x * G;
   const int nal = min(G, a.B - a0);
   const int p = wave * 32 + lr;                      // this lane's pixel slot (MFMA phases)
@@ -153,11 +188,11 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
 #pragma unroll
     for (int pn = 0; pn < L::PLANES; ++pn) {
       unsigned char* pb = pl + pn * PLB;
-      for (int i = tid; i < 4 * PL_ROW / 16; i += 256) {
+      for (int i = tid; i < 2 * G * PL_ROW / 16; i += NT) {
         const int blk = i / (PL_ROW / 16), o = i - blk * (PL_ROW / 16);
         *reinterpret_cast<uint4*>(pb + (blk >> 1) * PL_AL + (blk & 1) * PL_XQ + 7 * PL_ROW + o * 16) = make_uint4(0u, 0u, 0u, 0u);
       }
-      for (int i = tid; i < G * HW * C; i += 256) {
+      for (int i = tid; i < G * HW * C; i += NT) {
         const int al = i / (HW * C), r = (i / C) % HW, c = i % C;
         *reinterpret_cast<unsigned short*>(pb + al * PL_AL + PL_XQ + r * PL_ROW + c * 8 + 6) = 0;
       }
@@ -184,12 +219,11 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
   {
     f32x16 x0[CT];
     load_x(xsrc, x0);
-    if (inmap) regs_to_planar<DT, PLO, KEEP && !std::is_same<T, f16_t>::value>(x0, pl, p, h);
+    if (inmap) regs_to_planar<DT, G, PLO, KEEP && !std::is_same<T, f16_t>::value>(x0, pl, p, h);
   }
   SC_STAMP(1);
 
   f32x16 x[CT];   // (written in full at the start of every MLP: dead through the depthwise phases)
-  const int rot = (blockIdx.x * 5 + (blockIdx.x >> 4)) & (NCH - 1);   // chunk rotation, see issue()
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const Stage0Blk& bk = a.blk[j];
@@ -202,9 +236,10 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
     const int dj = ln & 3, db = ln >> 2;
     // ---- ordinary loads first (vmcnt retires in order: a load younger than a DMA would wait for it): fc1 bias,
     //      gamma*b2, the first channel group's Toeplitz taps and both groups' per-channel scalars
-    const float b1v0 = bk.b1[tid], b1v1 = bk.b1[256 + tid];
+    // (eight waves: thread tid holds fc1 bias tid alone, and the threads past 256 re-read the LN words of tid - 256)
+    const float b1v0 = bk.b1[tid], b1v1 = NT == 256 ? bk.b1[256 + tid] : 0.f;
     const float b2v = bk.gamma[tid & (C - 1)] * bk.b2[tid & (C - 1)];
-    const uint2* twsrc = reinterpret_cast<const uint2*>(bk.par) + (2 * wave) * 64 + ln;
+    const uint2* twsrc = reinterpret_cast<const uint2*>(bk.par) + (NG * wave) * 64 + ln;
     frag4 tw[TW_R], twl[X2 ? TW_R : 1];
 #pragma unroll
     for (int r = 0; r < TW_R; ++r) tw[r] = __builtin_bit_cast(frag4, twsrc[r * 512]);
@@ -213,27 +248,27 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
       for (int r = 0; r < TW_R; ++r) twl[r] = __builtin_bit_cast(frag4, twsrc[TW_BYTES / 8 + r * 512]);
     }
     const float* pf = reinterpret_cast<const float*>(bk.par + (X2 ? 2 : 1) * TW_BYTES);
-    float dwbias[2];
+    float dwbias[NG];
 #pragma unroll
-    for (int gi = 0; gi < 2; ++gi) dwbias[gi] = pf[16 * (2 * wave + gi) + db];
-    const float lnv = pf[C + tid];   // LN weight [128] | LN bias [128]
+    for (int gi = 0; gi < NG; ++gi) dwbias[gi] = pf[16 * (NG * wave + gi) + db];
+    const float lnv = pf[C + (NT == 256 ? tid : tid & 255)];   // LN weight [128] | LN bias [128]
     SC_STAMP(2 + 5 * j);
     __syncthreads();   // planar image complete (input / previous MLP + zero pads); ring slots 0, 1 free
     b1s[tid] = b1v0;
-    b1s[256 + tid] = b1v1;
+    if (NT == 256) b1s[256 + tid] = b1v1;
     if (tid < C) b2s[tid] = b2v;
-    lnws[tid] = lnv;
+    if (NT == 256 || tid < 2 * C) lnws[tid] = lnv;
 
-    // ---- pointwise filters: chunk = 32 hidden units = 16 pieces of 1 KiB, 4 per wave.
+    // ---- pointwise filters: chunk = 32 hidden units = 16 pieces of 1 KiB, NPIECE = 4 (2: eight waves) per wave.
     //      pieces 0..7 : W1 rows (LDS row m <- hidden unit 32*ch + swap23(m)), 256-byte rows,
     //                    16-byte chunk c of row m at position c ^ (m & 15)
     //      pieces 8..15: gamma*W2 columns 32*ch .. +31 of the 128 channel rows, 64-byte rows,
     //                    chunk c of row r at position c ^ F[(r >> 2) & 3]
-    const unsigned char* wsrc[4];
-    const unsigned char* wsrcl[4];   // split mode: the same pieces of the remainder images, 8 KB further into the slot
+    const unsigned char* wsrc[NPIECE];
+    const unsigned char* wsrcl[NPIECE];   // split mode: the same pieces of the remainder images, 8 KB further into the slot
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int pc = wave * 4 + i;
+    for (int i = 0; i < NPIECE; ++i) {
+      const int pc = wave * NPIECE + i;
       if (pc < 8) {
         const int m = pc * 4 + (lane >> 4);
         const int hid = (m & ~12) | ((m & 4) << 1) | ((m & 8) >> 1);   // swap bits 2 and 3
@@ -249,31 +284,33 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
     }
     // chunk k adds 32 W1 rows (8192 B) resp. 32 W2 columns (64 B)
     const int wstep0 = w1wave ? 32 * C * 2 : 64;
-    // (every workgroup walks the 16 chunks in its own rotation -- fc2 sums over the hidden units,
-    //  so the order is free -- which keeps the 512 workgroups off the same L2 lines)
-    // waves 0, 1 load the W1 half of chunk k into W1 slot k % 3, waves 2, 3 the W2 half into W2 slot k % 3
+    // (every workgroup walks the 16 chunks in the same order, so an alert's fc2 sum does not depend on where it sits
+    //  in a batch or on G; a rotation by workgroup index, meant to keep the workgroups off the same L2 lines, measured
+    //  nothing: DESIGN.md section 4a)
+    // the first half of the waves loads the W1 half of chunk k into W1 slot k % 3, the second half the W2 half into
+    // W2 slot k % 3: NPIECE consecutive pieces each
     auto issue = [&](int k) {
-      unsigned char* dst = (w1wave ? w1slot(k % NSLOT) : w2slot(k % NSLOT)) + (wave & 1) * 4096;
+      unsigned char* dst = (w1wave ? w1slot(k % NSLOT) : w2slot(k % NSLOT)) + (wave & (NW / 2 - 1)) * (NPIECE * 1024);
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
-        __builtin_amdgcn_global_load_lds((gptr_t)(wsrc[i] + (size_t)((k + rot) & (NCH - 1)) * wstep0),
+      for (int i = 0; i < NPIECE; ++i)
+        __builtin_amdgcn_global_load_lds((gptr_t)(wsrc[i] + (size_t)(k & (NCH - 1)) * wstep0),
                                          (lptr_t)(dst + i * 1024), 16, 0, 0);
       if (X2) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-          __builtin_amdgcn_global_load_lds((gptr_t)(wsrcl[i] + (size_t)((k + rot) & (NCH - 1)) * wstep0),
+        for (int i = 0; i < NPIECE; ++i)
+          __builtin_amdgcn_global_load_lds((gptr_t)(wsrcl[i] + (size_t)(k & (NCH - 1)) * wstep0),
                                            (lptr_t)(dst + HALFB + i * 1024), 16, 0, 0);
       }
     };
-    // one of the four pieces (the chunk loop spreads them over its MFMAs: four LDS-DMAs back to back held the wave
+    // one of the wave's pieces (the chunk loop spreads them over its MFMAs: four LDS-DMAs back to back held the wave
     // for 230-420 cycles at the vector-memory port, a fifth of a step)
     auto issue_piece = [&](int k, int i) {   // (split mode: pieces 4..7 are the remainders)
-      unsigned char* dst = (w1wave ? w1slot(k % NSLOT) : w2slot(k % NSLOT)) + (wave & 1) * 4096;
+      unsigned char* dst = (w1wave ? w1slot(k % NSLOT) : w2slot(k % NSLOT)) + (wave & (NW / 2 - 1)) * (NPIECE * 1024);
       if (X2 && i >= 4)
-        __builtin_amdgcn_global_load_lds((gptr_t)(wsrcl[i & 3] + (size_t)((k + rot) & (NCH - 1)) * wstep0),
+        __builtin_amdgcn_global_load_lds((gptr_t)(wsrcl[i & 3] + (size_t)(k & (NCH - 1)) * wstep0),
                                          (lptr_t)(dst + HALFB + (i & 3) * 1024), 16, 0, 0);
       else
-        __builtin_amdgcn_global_load_lds((gptr_t)(wsrc[i] + (size_t)((k + rot) & (NCH - 1)) * wstep0),
+        __builtin_amdgcn_global_load_lds((gptr_t)(wsrc[i] + (size_t)(k & (NCH - 1)) * wstep0),
                                          (lptr_t)(dst + i * 1024), 16, 0, 0);
     };
     SC_STAMP(3 + 5 * j);
@@ -288,10 +325,10 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
       const int r = sx + dj - 3;
       rofs[sx] = ((unsigned)r < (unsigned)HW ? r : 7) * PL_ROW;
     }
-    float v[2][2][16];   // [group][alert][yb * 8 + xb * 4 + i]
+    float v[NG][G][16];   // [group][alert][yb * 8 + xb * 4 + i]
 #pragma unroll
-    for (int gi = 0; gi < 2; ++gi) {
-      if (gi == 1) {   // the second group's taps into the same registers (their last use is behind us)
+    for (int gi = 0; gi < NG; ++gi) {
+      if (gi == 1) {   // (four waves) the second group's taps into the same registers (their last use is behind us)
 #pragma unroll
         for (int r = 0; r < TW_R; ++r) tw[r] = __builtin_bit_cast(frag4, twsrc[r * 512 + 64]);
         if (X2) {
@@ -308,7 +345,7 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
         for (int yb = 0; yb < 2; ++yb)
 #pragma unroll
           for (int xb = 0; xb < 2; ++xb) acc[al][yb][xb] = f32x4{dwbias[gi], dwbias[gi], dwbias[gi], dwbias[gi]};
-      const unsigned char* lb = pl + (16 * (2 * wave + gi) + db) * 8;
+      const unsigned char* lb = pl + (16 * (NG * wave + gi) + db) * 8;
       frag4 bq[2][G][2], bql[X2 ? 2 : 1][G][X2 ? 2 : 1];
       auto read_step = [&](int sx, int buf) {
 #pragma unroll
@@ -372,11 +409,11 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
     if (KEEP && a.keep_d[j] != nullptr) {   // the depthwise output before the LayerNorm: lane = (channel of the group, row j of
                                              // the quad) (nullptr: the backward recomputes it, dwln_bwd.hip)
 #pragma unroll
-      for (int gi = 0; gi < 2; ++gi)
+      for (int gi = 0; gi < NG; ++gi)
 #pragma unroll
         for (int al = 0; al < G; ++al) {
           if (al >= nal) continue;
-          float* dst = a.keep_d[j] + (size_t)(a0 + al) * PA * C + 16 * (2 * wave + gi) + db;
+          float* dst = a.keep_d[j] + (size_t)(a0 + al) * PA * C + 16 * (NG * wave + gi) + db;
 #pragma unroll
           for (int yb = 0; yb < 2; ++yb)
 #pragma unroll
@@ -395,9 +432,9 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
     //      [pixel][channel] image, which overlays the planar image that other waves may still be reading
     __syncthreads();   // nobody reads the planar image any more
     {
-      unsigned char* dst = smem + dj * (HW * LNP) + (32 * wave + db) * 4;
+      unsigned char* dst = smem + dj * (HW * LNP) + (16 * NG * wave + db) * 4;
 #pragma unroll
-      for (int gi = 0; gi < 2; ++gi)
+      for (int gi = 0; gi < NG; ++gi)
 #pragma unroll
         for (int al = 0; al < G; ++al)
 #pragma unroll
@@ -491,7 +528,7 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
       // read of float type hipcc waits vmcnt(0) while an LDS-DMA is in flight -- its type-based alias test takes the
       // DMA for a possible writer of those words -- and the chunks this ring keeps ahead are drained.)
       auto bias_acc = [&](int k, f32x16& acc) {
-        const float* bp = b1s + ((k + rot) & (NCH - 1)) * 32 + 8 * h;
+        const float* bp = b1s + (k & (NCH - 1)) * 32 + 8 * h;
 #pragma unroll
         for (int qd = 0; qd < 4; ++qd) {
           const f32x4 bv = __builtin_bit_cast(f32x4, *reinterpret_cast<const bf16x8*>(bp + 4 * (qd & 1) + 16 * (qd >> 1)));
@@ -521,10 +558,12 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
       frag a1[KS1];
       {   // prologue: chunk 0's fc1, then the operands of step 0
         // VM order of a wave: W1 waves W1(0), W1(1), W1(2), 16 loads of x; W2 waves W2(0), W2(1), x: chunk 0 has landed
-        // once no more than W2(1) + x are out.  (Whatever else the wave issues behind chunk 0 -- the keeping forms' 8
+        // once no more than W2(1) + x are out.  A group W(k) is the wave's NPIECE requests (4 on four waves, 2 on
+        // eight; split mode: twice that, heads and remainders), so the count is NPIECE + 16 = 20 / 18 / split 24.
+        // (Whatever else the wave issues behind chunk 0 -- the keeping forms' 8
         // keep_xn stores, a spill store of hipcc's -- counts in vmcnt on gfx9 as well and is younger than chunk 0, so it
         // only makes this wait stricter: the count is an upper bound and must not be tightened to the loads listed here.)
-        wait_vm<(X2 ? 8 : 4) + 16>();
+        wait_vm<(X2 ? 2 : 1) * NPIECE + 16>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         bias_acc(0, hacc[0]);
@@ -566,8 +605,9 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
       auto step = [&](auto last_c, int ch, f32x16& hc, f32x16& hn) {
         constexpr bool LAST = decltype(last_c)::value;
         LS(0);
-        // VM order of a wave: W1 waves W1(0..ch+3), W2 waves W2(0..ch+1); both need all but their youngest group
-        wait_vm<X2 ? 8 : 4>();
+        // VM order of a wave: W1 waves W1(0..ch+3), W2 waves W2(0..ch+1), each group in piece order (step ch - 1 issued
+        // its kdma group's pieces one by one, nothing else); both need all but their youngest group of NPIECE (x 2: split)
+        wait_vm<(X2 ? 2 : 1) * NPIECE>();
         LS(1);
         // raw barrier: __syncthreads() would also wait vmcnt(0) while an LDS-DMA is in flight
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // every LDS read of the last step is home
@@ -606,7 +646,7 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
 #endif
 #ifndef S1_EXP_NODMA
           if (X2) issue_piece(kdma, r);
-          else if (r & 1) issue_piece(kdma, r >> 1);
+          else if (r % (8 / NPIECE) == 8 / NPIECE - 1) issue_piece(kdma, r / (8 / NPIECE));   // r = 1, 3, 5, 7 / 3, 7
 #endif
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -669,7 +709,7 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
       if (j == 0) {      // next block's depthwise operand; chunk 15 (W1 slot 0 = the planar image's first 8 KB) must be read out first
         __syncthreads();
         zero_pads();
-        if (inmap) regs_to_planar<DT, PLO, KEEP && !std::is_same<T, f16_t>::value>(x, pl, p, h);
+        if (inmap) regs_to_planar<DT, G, PLO, KEEP && !std::is_same<T, f16_t>::value>(x, pl, p, h);
         if (live) {
 #pragma unroll
           for (int ct = 0; ct < CT; ++ct)
@@ -692,22 +732,22 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
             make_float4(x[ct][4 * qd], x[ct][4 * qd + 1], x[ct][4 * qd + 2], x[ct][4 * qd + 3]);
   }
 
-  // ---- downsample: LN + conv 2x2 s2 (128 -> 256): 18 output pixels x 256 channels, K = 512
+  // ---- downsample: LN + conv 2x2 s2 (128 -> 256): 9 G output pixels x 256 channels, K = 512
   {
-    __syncthreads();   // every wave is out of the MLP: ring slots 0..1 take the LN image
+    __syncthreads();   // every wave is out of the MLP: the ring and planar bytes from 0 take the LN image
     {
       f32x16 xn[CT];
       ln_regs(x, a.ds_lnw, a.ds_lnb, h, xn);
       if (inmap) regs_to_map<T, X2 ? MAPB : 0>(xn, stg, p, h);   // (split: the remainder image behind it, dead bytes too)
     }
-    static_assert(2 * MAPB <= L::OFF_B1, "two [pixel][channel] images in front of the bias words");
-    // this wave's output tiles wave, wave + 4 (32 channels each) x 32 k-steps: 64 filter fragments packed as
-    // MFMA A operands (1 KiB each, launch_pack_frag32), a ring of 16 in flight
-    constexpr int KSD = 4 * C / 16, RING = X2 ? 8 : 16, NSTEP = 2 * KSD;
+    // this wave's output tiles wave, wave + 4 (32 channels each; eight waves: tile wave alone) x 32 k-steps: 64 (32)
+    // filter fragments packed as MFMA A operands (1 KiB each, launch_pack_frag32), a ring of 16 in flight; a fragment
+    // serves every 32-column block of output pixels (eight waves: 45 pixels on two), so the workgroup loads it once
+    constexpr int KSD = 4 * C / 16, RING = X2 ? 8 : 16, NSTEP = NG * KSD, NCB = L::NCB;
     // (split: a packed fragment is 2 KiB, the heads' 1 KiB then the remainders')
     const frag* wsrc = reinterpret_cast<const frag*>(a.ds_w) + lane;
     auto fsrc = [&](int stp) {
-      return wsrc + (size_t)((wave + 4 * (stp >> 5)) * KSD + (stp & (KSD - 1))) * (X2 ? 128 : 64);
+      return wsrc + (size_t)((wave + NW * (stp >> 5)) * KSD + (stp & (KSD - 1))) * (X2 ? 128 : 64);
     };
     frag wq[RING], wql[X2 ? RING : 1];
 #pragma unroll
@@ -718,7 +758,7 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
     __syncthreads();
     if (KEEP) {   // the downsample's patch rows [output pixel][q = 2 ky + kx][128] = LayerNorm'd pixels (2 oy + ky, 2 ox + kx)
       unsigned char* dst = reinterpret_cast<unsigned char*>(a.keep_patches) + (size_t)a0 * PO * 4 * C * 2;
-      for (int i = tid; i < nal * PO * 4 * 16; i += 256) {
+      for (int i = tid; i < nal * PO * 4 * 16; i += NT) {
         const int c16 = i & 15, q = (i >> 4) & 3, o2 = i >> 6;
         const int g2 = o2 / PO, oo2 = o2 - g2 * PO;
         const int pin2 = g2 * PA + (2 * (oo2 / 3) + (q >> 1)) * HW + 2 * (oo2 % 3) + (q & 1);
@@ -727,12 +767,16 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
       }
     }
     SC_STAMP(12);
-    const int o = lr;                                // output pixel slot: 18 of 32 used
-    const bool olive = o < nal * PO;
-    const int oc = o < G * PO ? o : 0;
-    const int g = oc / PO, oo = oc - g * PO;
-    const int oy = oo / 3, ox = oo - oy * 3;
-    f32x16 acc;
+    // output pixel slots o = 32 cb + lr: 18 of 32 / 45 of 64 used; pin0 = the input pixel under tap 0
+    int pin0[NCB];
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb) {
+      const int o = cb * 32 + lr, oc = o < G * PO ? o : 0;
+      const int g = oc / PO, oo = oc - g * PO;
+      const int oy = oo / 3, ox = oo - oy * 3;
+      pin0[cb] = g * PA + 2 * oy * HW + 2 * ox;
+    }
+    f32x16 acc[NCB];
     constexpr int RPT = KSD / RING;   // ring rounds per output tile
 #ifdef S1_EXP_NODS
 #pragma unroll 1
@@ -741,40 +785,51 @@ __global__ __launch_bounds__(256, WPS) void stage1b_kernel(Stage1Args a) {
 #pragma unroll 1
     for (int rd = 0; rd < NSTEP / RING; ++rd) {
 #endif
-      const int cot = wave + 4 * (rd / RPT);
+      const int cot = wave + NW * (rd / RPT);
       if (rd % RPT == 0) {
 #pragma unroll
         for (int qd = 0; qd < 4; ++qd) {
           const float4 bv = *reinterpret_cast<const float4*>(a.ds_b + cot * 32 + 8 * qd + 4 * h);
-          acc[4 * qd + 0] = bv.x;
-          acc[4 * qd + 1] = bv.y;
-          acc[4 * qd + 2] = bv.z;
-          acc[4 * qd + 3] = bv.w;
+#pragma unroll
+          for (int cb = 0; cb < NCB; ++cb) {
+            acc[cb][4 * qd + 0] = bv.x;
+            acc[cb][4 * qd + 1] = bv.y;
+            acc[cb][4 * qd + 2] = bv.z;
+            acc[cb][4 * qd + 3] = bv.w;
+          }
         }
       }
 #pragma unroll
       for (int i = 0; i < RING; ++i) {
         const int stp = rd * RING + i, ks = stp & (KSD - 1);
         const int q = ks >> 3;                     // tap (ky*2 + kx): 8 k-steps of 16 channels each
-        const int pin = g * PA + (2 * oy + (q >> 1)) * HW + 2 * ox + (q & 1);
-        const frag bf = *reinterpret_cast<const frag*>(stg + pin * PITCH + (ks & 7) * 32 + h * 16);
-        if (X2) {
-          const frag bfl = *reinterpret_cast<const frag*>(stg + MAPB + pin * PITCH + (ks & 7) * 32 + h * 16);
-          acc = Mfma<T>::m32(wql[i], bf, acc);
-          acc = Mfma<T>::m32(wq[i], bfl, acc);
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb) {
+          const int pin = pin0[cb] + (q >> 1) * HW + (q & 1);
+          const frag bf = *reinterpret_cast<const frag*>(stg + pin * PITCH + (ks & 7) * 32 + h * 16);
+          if (X2) {
+            const frag bfl = *reinterpret_cast<const frag*>(stg + MAPB + pin * PITCH + (ks & 7) * 32 + h * 16);
+            acc[cb] = Mfma<T>::m32(wql[i], bf, acc[cb]);
+            acc[cb] = Mfma<T>::m32(wq[i], bfl, acc[cb]);
+          }
+          acc[cb] = Mfma<T>::m32(wq[i], bf, acc[cb]);
         }
-        acc = Mfma<T>::m32(wq[i], bf, acc);
         if (stp + RING < NSTEP) {
           wq[i] = *fsrc(stp + RING);
           if (X2) wql[i] = fsrc(stp + RING)[64];
         }
       }
-      if (rd % RPT == RPT - 1 && olive) {
-        float* dst = a.out + ((size_t)a0 * PO + o) * CN + cot * 32 + 4 * h;
+      if (rd % RPT == RPT - 1) {
 #pragma unroll
-        for (int qd = 0; qd < 4; ++qd)
-          *reinterpret_cast<float4*>(dst + 8 * qd) =
-              make_float4(acc[4 * qd], acc[4 * qd + 1], acc[4 * qd + 2], acc[4 * qd + 3]);
+        for (int cb = 0; cb < NCB; ++cb) {
+          const int o = cb * 32 + lr;
+          if (o >= nal * PO) continue;
+          float* dst = a.out + ((size_t)a0 * PO + o) * CN + cot * 32 + 4 * h;
+#pragma unroll
+          for (int qd = 0; qd < 4; ++qd)
+            *reinterpret_cast<float4*>(dst + 8 * qd) =
+                make_float4(acc[cb][4 * qd], acc[cb][4 * qd + 1], acc[cb][4 * qd + 2], acc[cb][4 * qd + 3]);
+        }
       }
     }
     SC_STAMP(13);
@@ -829,18 +884,20 @@ __global__ void pack_frag32_kernel(const float* __restrict__ w, T* __restrict__ 
   }
 }
 
-template <typename T, bool X2 = false, int WPS = 2, bool KEEP = false> int launch_stage1b_t(const Stage1Args& a, hipStream_t st) {
-  auto kern = stage1b_kernel<T, X2, WPS, KEEP>;
+template <typename T, bool X2 = false, int WPS = 2, bool KEEP = false, int G = 2>
+int launch_stage1b_t(const Stage1Args& a, hipStream_t st) {
+  auto kern = stage1b_kernel<T, X2, WPS, KEEP, G>;
+  using L = S1L<G, X2>;
   static DevOnce attr_set;
-  // (BTSBOT_AMD_S1_ONE_WG=1: the same probe as stage0b.hip's)
-  static const int pad = switch_on(SW_S1_ONE_WG) && !X2 ? 90 * 1024 - S1L<X2>::LDS_BYTES : 0;
-  const int LDS_BYTES = S1L<X2>::LDS_BYTES + pad;
+  // (BTSBOT_AMD_S1_ONE_WG=1: the same probe as stage0b.hip's; the forms that hold a CU alone have nothing to pad)
+  static const int pad = switch_on(SW_S1_ONE_WG) && !X2 && G == 2 ? 90 * 1024 - L::LDS_BYTES : 0;
+  const int LDS_BYTES = L::LDS_BYTES + pad;
   if (attr_set.need()) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
     attr_set.done();
   }
-  hipLaunchKernelGGL(kern, dim3((a.B + G - 1) / G), dim3(256), LDS_BYTES, st, a);
+  hipLaunchKernelGGL(kern, dim3((a.B + G - 1) / G), dim3(L::NT), LDS_BYTES, st, a);
   LAUNCH_CHECK();
   return BTSBOT_OK;
 }
@@ -922,7 +979,7 @@ bool stage1_supported(int prec, int c1, int c2) {
 
 // Needs Stage0Blk::par (launch_pack_s1par), ::w1 (plain [512][128]) and Stage0Blk::w2g (gamma-scaled [128][512]), 16-bit,
 // and Stage1Args::ds_w as MFMA fragments (launch_pack_frag32).
-int launch_stage1b(int prec, const Stage1Args& a, hipStream_t st) {
+int launch_stage1b(int prec, const Stage1Args& a, bool g5, hipStream_t st) {
   if (a.B <= 0) return BTSBOT_OK;
   if (a.keep_xn[0] != nullptr) {   // the training forward
     if ((a.keep_d[0] == nullptr) != (a.keep_d[1] == nullptr) || a.keep_xn[1] == nullptr || a.keep_patches == nullptr ||
@@ -934,6 +991,12 @@ int launch_stage1b(int prec, const Stage1Args& a, hipStream_t st) {
     if (prec == BTSBOT_F16) return launch_stage1b_t<f16_t, false, 2, true>(a, st);
     btsbot_set_error("stage1b: the training forward runs in the bf16 / f16 modes, not %d", prec);
     return BTSBOT_ERR_INVALID_ARG;
+  }
+  // inference: five alerts per workgroup where the schedule asks for it (Schedule::s1_g5: other forwards in flight),
+  // else two; the same bits either way
+  if (g5) {
+    if (prec == BTSBOT_BF16) return launch_stage1b_t<bf16_t, false, 2, false, 5>(a, st);
+    if (prec == BTSBOT_F16) return launch_stage1b_t<f16_t, false, 2, false, 5>(a, st);
   }
   if (prec == BTSBOT_BF16) return launch_stage1b_t<bf16_t>(a, st);
   if (prec == BTSBOT_F16) return launch_stage1b_t<f16_t>(a, st);

@@ -271,10 +271,10 @@ int btsbot_allreduce_grads(btsbot_handle h, void* nccl_comm, float* grads, int n
  *   the kernel then leaves ~40 % of the CUs to the other stream at 1024 alerts); 4: always.
  *   "forwards_in_flight": 1 = other forwards run beside this handle's on other streams (a scoring loop sets it around
  *   each forward it queues and clears it behind it): the schedule then takes the forms that hold fewer CUs per launch --
- *   stage 2 with 7 alerts per workgroup unless "stage2p_alerts" says otherwise, and at 512 channels the 1x1 stage on
+ *   stage 1 with 5 alerts per workgroup (bf16, f16 and fp8 handles), stage 2 with 7 alerts per workgroup unless "stage2p_alerts" says otherwise, and at 512 channels the 1x1 stage on
  *   64-alert / 64-channel tiles (half the workgroups; bf16, f16 and fp8 handles -- f32 and BTSBOT_F16X2 handles accept
  *   the option and keep their tiles).  0 (default): the forms that are fastest for a lone forward.  Reported by
- *   "query_schedule:s2p_g7" and "query_schedule:s3_wide".
+ *   "query_schedule:s1_g5", "query_schedule:s2p_g7" and "query_schedule:s3_wide".
  *   "exchange": form of btsbot_allreduce_grads' collectives -- 0 (default) all-reduce, 1 reduce-scatter + all-gather.
  *   "deterministic" (also BTSBOT_AMD_DETERMINISTIC=1 at btsbot_create; set before btsbot_reserve_train): 1 = the batch
  *   reductions of the ConvNeXt training step that meet through fp32 atomics (LayerNorm / depthwise parameter gradients,

@@ -12,6 +12,10 @@ kind, cfg = CONFIGS["mm_pico"]
 m = build_model(kind, cfg, seeded_state(kind, cfg, seed=3), dev, os.environ.get("PREC", "bf16"))
 img, meta, _ = synthetic_batch(B, seed=2)
 img, meta = img.to(dev), meta.to(dev)
+run_model(kind, m, img, meta)
+HINT = os.environ.get("S1_HINT", "0") == "1"   # the overlap hint: stage1b on five alerts per workgroup (and its companions)
+if HINT:
+    _lib.check(_lib.lib().btsbot_set_option(m._handle.ptr, b"forwards_in_flight", 1), "btsbot_set_option")
 for _ in range(3):
     run_model(kind, m, img, meta)
 buf = torch.zeros(32 + 16384 + 64 + 2048, dtype=torch.int64, device=dev)
@@ -28,7 +32,7 @@ for base, tag in ((0, "stage0"), (16, "stage1")):
 
 print("   stage0 b0 LN detail: barrier + transposing fp32 stores", t[14] - t[4], " barrier", t[15] - t[14], " row reads + LayerNorm in registers", t[5] - t[15])
 import numpy as np
-for off, tag, n in ((32, "stage0", B), (32 + 8192, "stage1", (B + 1) // 2)):
+for off, tag, n in ((32, "stage0", B), (32 + 8192, "stage1", (B + 4) // 5 if HINT else (B + 1) // 2)):   # stage1b: five alerts per workgroup under the hint
     w = np.array(t[off:off + 2 * n]).reshape(n, 2)
     t0 = w[:, 0].min()
     dur = (w[:, 1] - w[:, 0]) / 100.0

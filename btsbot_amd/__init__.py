@@ -51,6 +51,8 @@ from . import clusters
 from .clusters import dbscan, graph_components
 from . import quality
 from .quality import continuity, map_quality, trustworthiness
+from . import graph
+from .graph import KnnGraph
 from . import novelty
 from .novelty import NoveltyModel, kth_neighbor_distance, local_outlier_factor
 # (the function takes the package attribute ``hdbscan``; the module is ``from btsbot_amd.hdbscan import ...``)
@@ -72,6 +74,7 @@ __all__ = [
     "neighbors", "EmbeddingIndex", "embedding_neighbors", "knn_graph", "neighbor_vote",
     "radius_neighbors", "radius_graph", "neighbor_ranks", "quality", "trustworthiness", "continuity", "map_quality",
     "clusters", "graph_components", "dbscan", "mapindex", "MapIndex",
+    "graph", "KnnGraph",
     "novelty", "NoveltyModel", "local_outlier_factor", "kth_neighbor_distance",
     "hdbscan", "mutual_reachability_mst", "MutualReachabilityMST", "ClusterTree", "ClusterModel",
     "layout", "FuzzyGraph", "fuzzy_graph", "optimize_layout", "embedding_layout", "find_ab_params",

@@ -59,6 +59,7 @@ SYMBOLS = [
     "btsbot_layout_smooth_knn", "btsbot_layout_symmetrize_workspace", "btsbot_layout_symmetrize", "btsbot_layout_init",
     "btsbot_layout_epochs", "btsbot_layout_smooth_knn_query", "btsbot_layout_transform",
     "btsbot_lof_fit", "btsbot_lof_score",
+    "btsbot_knn_graph_merge",
     "btsbot_mst_offer_knn", "btsbot_mst_offer_csr", "btsbot_mst_merge", "btsbot_hdbscan_tree",
     "btsbot_hdbscan_model", "btsbot_cluster_offer_knn", "btsbot_cluster_offer_csr", "btsbot_cluster_assign",
 ]
@@ -70,6 +71,7 @@ KNN_METRIC = {"euclidean": 0, "cosine": 1}   # enum btsbot_knn_metric
 KNN_MAX_DIM, KNN_MAX_K, KNN_MAX_SPLITS = 1024, 64, 32
 KNN_EXCLUDE_SAME, KNN_ONE_PER_GROUP = 1, 2   # enum btsbot_knn_flags
 KNN_MAX_K_ONE_PER_GROUP = 32                 # k's cap under KNN_ONE_PER_GROUP
+KNN_GRAPH_DISTINCT = 1                       # enum btsbot_knn_graph_flags (csrc/knn_graph.hip)
 GRID_MAX_CELLS, GRID_MAX_K = 4096, 64         # csrc/grid.hip
 GRID_LANES = (0, 1, 4, 8, 16, 32, 64)        # lanes per query row of btsbot_grid_radius_* (0: the library's choice)
 EMBEDDING = {"features": 0, "hidden": 1}   # enum btsbot_embedding
@@ -348,6 +350,8 @@ def lib() -> C.CDLL:
     L.btsbot_lof_fit.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
     L.btsbot_lof_score.restype = i32
     L.btsbot_lof_score.argtypes = [vp, vp, i64, i32, vp, vp, i64, vp, vp, vp]
+    L.btsbot_knn_graph_merge.restype = i32
+    L.btsbot_knn_graph_merge.argtypes = [vp, vp, i64, i32, i64, vp, vp, vp, i64, vp, i64, i32, vp, i64, vp, vp, vp]
     L.btsbot_mst_offer_knn.restype = i32
     L.btsbot_mst_offer_knn.argtypes = [vp, vp, i64, i32, vp, vp, i32, f32, vp, vp, vp, vp]
     L.btsbot_mst_offer_csr.restype = i32

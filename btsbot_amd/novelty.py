@@ -27,8 +27,14 @@ row, ``alert_utils.object_keys``) the fit leaves a row's own object out of its n
 does the same for new alerts of objects the archive knows.
 
 Fit and score read nothing from the host and are queued on the current stream; only ``threshold`` reads.  There is no CPU
-fallback.  A fit does NOT follow ``index.add``: ``refit()`` recomputes it for the rows the index holds now, and ``score``
-refuses an index that has grown since.
+fallback.  A fit does NOT follow ``index.add`` by itself: ``refit()`` recomputes it for the rows the index holds now, and
+``score`` refuses an index that has grown since.
+
+Following the archive.  ``NoveltyModel(index, 20, keep_graph=True)`` keeps the neighbour graph of the fit
+(``model.graph``, a ``graph.KnnGraph``), and ``model.update()`` after ``index.add`` brings graph and
+fit to the rows the index holds now at the cost of the new rows: ``graph.update()`` and ``btsbot_lof_fit`` over all rows.
+``update`` reads the host where ``radius`` does.  A graph kept elsewhere serves the same way:
+``local_outlier_factor(None, k, knn=(g.idx, g.dist))`` and ``fuzzy_graph(*g.self_first())`` take it as it is.
 """
 from __future__ import annotations
 
@@ -38,6 +44,7 @@ from typing import Optional, Tuple, Union
 import torch
 
 from . import _lib
+from .graph import KnnGraph
 from .mapindex import MapIndex
 from .neighbors import GROUP_MODES, EmbeddingIndex, _ptr, knn_graph
 
@@ -133,13 +140,21 @@ class NoveltyModel:
     group_mode: how the FIT treats the groups, as ``knn_graph`` (``"exclude"``: a row's neighbours are rows of other
     groups only).  ``kdist``, ``lrd`` and ``lof`` are float64 [N].
 
-    The fit does not follow ``index.add``; ``refit()`` recomputes it.  Calls on one model must be ordered by the
+    The fit does not follow ``index.add``; ``refit()`` recomputes it.  keep_graph=True (an ``EmbeddingIndex`` or rows;
+    a ``MapIndex`` is a ``ValueError``): the model keeps ``graph``, the ``KnnGraph`` of ``n_neighbors`` columns the fit
+    is computed on (``n_neighbors <= 32`` in the ``"distinct"`` modes); ``refit()`` rebuilds it, and ``update()`` follows
+    ``index.add`` at the cost of the new rows.  The default keeps nothing.  Calls on one model must be ordered by the
     caller's streams."""
 
     def __init__(self, bank_or_index: Union[torch.Tensor, EmbeddingIndex, MapIndex], n_neighbors: int = 20,
-                 metric: str = "euclidean", *, groups: Optional[torch.Tensor] = None, group_mode: str = "exclude"):
+                 metric: str = "euclidean", *, groups: Optional[torch.Tensor] = None, group_mode: str = "exclude",
+                 keep_graph: bool = False):
         _check_n_neighbors(n_neighbors)
         _check_group_mode(group_mode)
+        if not isinstance(keep_graph, bool):
+            raise ValueError(f"keep_graph must be a bool, got {keep_graph!r}")
+        if keep_graph and isinstance(bank_or_index, MapIndex):
+            raise ValueError("keep_graph=True needs an EmbeddingIndex: a MapIndex has no add to follow")
         if isinstance(bank_or_index, (EmbeddingIndex, MapIndex)):
             index = bank_or_index
             if groups is not None:
@@ -157,7 +172,12 @@ class NoveltyModel:
         self.metric = getattr(index, "metric", "euclidean")
         self.group_mode = group_mode
         self.device = index.device
-        self.refit()
+        self.graph = None
+        if keep_graph:
+            self.graph = KnnGraph(index, n_neighbors, self.metric, group_mode=group_mode)
+            self.kdist, self.lrd, self.lof = _fit(self.graph.idx, self.graph.dist)
+        else:
+            self.refit()
 
     def __len__(self) -> int:
         """The rows the fit covers."""
@@ -167,7 +187,12 @@ class NoveltyModel:
         return self.index.points if isinstance(self.index, MapIndex) else self.index.bank
 
     def refit(self) -> "NoveltyModel":
-        """Fits the rows the index holds now (after ``index.add``): one neighbour search and three launches."""
+        """Fits the rows the index holds now (after ``index.add``): one neighbour search and three launches.  A kept
+        graph is rebuilt."""
+        if self.graph is not None:
+            self.graph.rebuild()
+            self.kdist, self.lrd, self.lof = _fit(self.graph.idx, self.graph.dist)
+            return self
         kw = {}
         if self.index.groups is not None:
             kw = dict(query_groups=self.index.groups, exclude_same_group="exclude" in self.group_mode)
@@ -175,6 +200,18 @@ class NoveltyModel:
                 kw["one_per_group"] = "distinct" in self.group_mode
         idx, dist = self.index.query(self._rows(), self.n_neighbors, self_offset=0, **kw)
         self.kdist, self.lrd, self.lof = _fit(idx, dist)
+        return self
+
+    def update(self, stats: Optional[dict] = None) -> "NoveltyModel":
+        """Follows ``index.add`` at the cost of the new rows (``keep_graph=True`` only): ``graph.update(stats)``, then
+        ``btsbot_lof_fit`` over all rows -- the fit is three launches whatever the archive holds, so it is not made
+        incremental.  ``kdist``, ``lrd`` and ``lof`` are those of the updated graph, whose promise is ``KnnGraph``'s.
+        Reads the host where ``radius`` does."""
+        if getattr(self, "graph", None) is None:
+            raise RuntimeError("update() needs the model's neighbour graph: build the model with keep_graph=True (or "
+                               "call refit(), which searches every pair again)")
+        self.graph.update(stats)
+        self.kdist, self.lrd, self.lof = _fit(self.graph.idx, self.graph.dist)
         return self
 
     def score(self, queries: torch.Tensor, *, query_groups: Optional[torch.Tensor] = None,
@@ -186,7 +223,8 @@ class NoveltyModel:
         without an eligible neighbour.  Nothing is read from the host."""
         if len(self.index) != len(self):
             raise RuntimeError(f"the index holds {len(self.index)} rows, the fit {len(self)}: a fit does not follow "
-                               "index.add -- call refit()")
+                               "index.add -- call refit()" + (" or update()" if self.graph is not None else
+                                                             " (a model built with keep_graph=True has update())"))
         kw = dict(query_groups=query_groups, exclude_same_group=exclude_same_group)
         if isinstance(self.index, MapIndex):
             if one_per_group:

@@ -1171,6 +1171,37 @@ int btsbot_lof_fit(const int64_t* idx, const float* dist, int64_t n, int k, doub
 int btsbot_lof_score(const int64_t* idx, const float* dist, int64_t q, int k, const double* bank_kdist,
                      const double* bank_lrd, int64_t n, double* lrd, double* lof, void* stream);
 
+/* ---- a kNN graph kept current under add: the merge of offers into the lists (csrc/knn_graph.hip) ---- */
+
+/* Flags of btsbot_knn_graph_merge. */
+enum btsbot_knn_graph_flags { BTSBOT_KNN_GRAPH_DISTINCT = 1 };
+
+/* Merges, in place, offers into the neighbour lists of n_old rows.  idx int64 / dist fp32 hold row a's list at
+ * [a * stride .. a * stride + k): present entries (idx >= 0) first, ordered by (dist, idx), then a -1 / +inf tail -- the
+ * lists btsbot_knn_query writes.  The offers are a CSR: indptr int64 [n_old + 1] (n_offers = indptr[n_old]), offer_idx
+ * int64 and offer_dist fp32 [n_offers], a row's offers ordered by (dist, idx); every offer index must be larger than
+ * every index of the lists (new rows: an old entry wins a tie in dist) and not occur in them.  Row a's list becomes the
+ * first k of the merge by (dist, idx) of its present entries and its offers, the tail -1 / +inf.  Under
+ * BTSBOT_KNN_GRAPH_DISTINCT (k <= 32) an entry is emitted only if its group -- groups int64 [n_groups], read at the
+ * entry's index, all 64 bits -- differs from every entry emitted before it.  A list of a row whose dist[0] is NaN (a
+ * non-finite row) and a row whose indptr range is empty or does not lie inside [0, n_offers] is left as it is.
+ *
+ * rows: NULL, every row a in [0, n_old) is visited, one wave each, and a row without offers ends after its two indptr
+ * reads; or int64 [n_rows], the rows to visit (distinct, in [0, n_old); others are skipped).  changed_rows: NULL or uint8
+ * [n_old], set to 1 for every row whose list changed (never cleared here); changed_count: NULL or one int32 the number of
+ * changed rows is ADDED to.  The merge itself uses no atomic: a row is read whole by its wave before it is written, and
+ * its result is a function of its own list and offers.  Work per row: k + the offers that can matter (the first k in the
+ * plain mode; in the distinct mode the walk ends at k emitted groups).  Queued on `stream`; nothing allocates,
+ * synchronises or copies to the host.
+ *
+ * BTSBOT_ERR_INVALID_ARG with a message, before any HIP call, for k outside 1..64 (1..32 under DISTINCT), stride < k,
+ * n_old, n_rows or n_offers outside 0..2^31 - 1, unknown flags, DISTINCT without groups, a NULL or misaligned pointer
+ * (but the optional ones).  n_old = 0, n_offers = 0 or rows given with n_rows = 0 succeed without a launch. */
+int btsbot_knn_graph_merge(int64_t* idx, float* dist, int64_t stride, int k, int64_t n_old, const int64_t* indptr,
+                           const int64_t* offer_idx, const float* offer_dist, int64_t n_offers, const int64_t* groups,
+                           int64_t n_groups, int flags, const int64_t* rows, int64_t n_rows, uint8_t* changed_rows,
+                           int32_t* changed_count, void* stream);
+
 /* ---- HDBSCAN: the mutual-reachability spanning tree and its hierarchy (csrc/mst.hip, csrc/hdbscan_tree.hip) ---- */
 
 /* The minimum spanning tree of the complete graph on the finite rows under w(a, b) = max(d(a, b), core(a), core(b), 0) in

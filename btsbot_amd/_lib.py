@@ -64,7 +64,7 @@ SYMBOLS = [
     "btsbot_hdbscan_model", "btsbot_cluster_offer_knn", "btsbot_cluster_offer_csr", "btsbot_cluster_assign",
 ]
 LOF_MAX_K = 64                               # csrc/lof.hip
-MST_MAX_K = 64                               # csrc/mst.hip, csrc/hdbscan_predict.hip: search_k
+MST_MAX_K = 64                               # csrc/mr_offer.hip: search_k
 HDBSCAN_METHOD = {"eom": 0, "leaf": 1}       # enum btsbot_hdbscan_method
 LAYOUT_MAX_K, LAYOUT_MAX_NEGATIVES = 64, 64
 KNN_METRIC = {"euclidean": 0, "cosine": 1}   # enum btsbot_knn_metric
@@ -381,6 +381,17 @@ def check(status: int, what: str) -> int:
         msg = lib().btsbot_last_error().decode("utf-8", "replace")
         raise BtsbotHipError(f"{what} failed ({status}): {msg}")
     return status
+
+
+def ptr(t) -> C.c_void_p:
+    """The device pointer of a tensor as a C argument; NULL for ``None`` and for a tensor without elements."""
+    return C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
+
+
+def stream(device) -> C.c_void_p:
+    """The caller's current stream on ``device`` as a C argument."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def make_config(wiring: str, precision: str, depths, dims, head_norm: bool, n_meta: int,

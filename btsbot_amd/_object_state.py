@@ -12,14 +12,11 @@ from typing import Callable, Dict, Mapping, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr, stream as _stream
 from .alert_utils import _group_by_object
 
 RESERVED_ID = -(1 << 63)          # BTSBOT_TRIGGER_FREE: the free-slot marker, the one id a state cannot hold
 _COUNTERS = ("objects", "taken", "dropped", "late")
-
-
-def _ptr(t: torch.Tensor) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr())
 
 
 def _check_capacity(capacity) -> None:
@@ -71,13 +68,10 @@ class ObjectState:
     def _installed(self):
         return self.capacity, [getattr(self, name) for name in self._ARRAYS], self._table
 
-    def _stream(self) -> C.c_void_p:
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _call(self, symbol: str, *args) -> None:
         """symbol(table, *args, stream) on the state's device."""
         with torch.cuda.device(self.device):
-            _lib.check(getattr(_lib.lib(), symbol)(C.byref(self._table), *args, self._stream()), symbol)
+            _lib.check(getattr(_lib.lib(), symbol)(C.byref(self._table), *args, _stream(self.device)), symbol)
 
     def reset(self) -> None:
         """Forget every object and zero the counters (one launch, no host synchronisation)."""
@@ -128,7 +122,7 @@ class ObjectState:
         it).  No host synchronisation."""
         old = self._installed()
         arrays, table = self._allocate(capacity)
-        L, stream = _lib.lib(), self._stream()
+        L, stream = _lib.lib(), _stream(self.device)
         with torch.cuda.device(self.device):
             _lib.check(getattr(L, self._RESET)(C.byref(table), stream), self._RESET)
             _lib.check(getattr(L, self._REHASH)(C.byref(old[2]), C.byref(table), C.c_double(keep_from), stream),

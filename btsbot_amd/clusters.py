@@ -20,14 +20,14 @@ There is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Tuple
 
 import torch
 
 from . import _lib
 from .mapindex import check_grid_method
-from .neighbors import _check_method, _groups, _metric, _ptr, _rows, radius_graph
+from ._lib import ptr as _ptr, stream as _stream
+from .neighbors import _check_method, _groups, _metric, _rows, radius_graph
 
 
 def _csr(indptr, indices, n: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, int]:
@@ -42,10 +42,6 @@ def _csr(indptr, indices, n: Optional[int] = None) -> Tuple[torch.Tensor, torch.
     if indices.device != indptr.device:
         raise ValueError(f"indices is on {indices.device}, indptr on {indptr.device}")
     return indptr.contiguous(), indices.contiguous(), int(indptr.shape[0]) - 1
-
-
-def _stream(device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def graph_components(indptr: torch.Tensor, indices: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -15,7 +15,7 @@
 // Labels: one wave per row.  A core row takes its component's number; any other row the smallest number among its core
 // neighbours (clusters are numbered in the order of their smallest core row, so that is the component with the smallest
 // root), or -1 -- sklearn.cluster.DBSCAN's labels, made independent of the visiting order.
-#include "common.h"
+#include "list_row.h"
 
 namespace {
 
@@ -96,19 +96,13 @@ __global__ __launch_bounds__(256) void dbscan_label_kernel(const long long* __re
   if (lane == 0) labels[u] = best == 0x7fffffffffffffffLL ? -1 : best;
 }
 
-int check_n(const char* who, int64_t n) {
-  if (n < 0 || n > 0x7fffffffLL) {
-    btsbot_set_error("%s: n=%lld must be in 0 .. 2^31 - 1", who, (long long)n);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
-  return BTSBOT_OK;
-}
+using list_row::check_count;
 
 }  // namespace
 
 extern "C" int btsbot_graph_components(const int64_t* indptr, const int64_t* indices, const uint8_t* mask, int64_t n,
                                        int32_t* parent, int64_t* root, void* stream) {
-  TRY(check_n("btsbot_graph_components", n));
+  TRY(check_count("btsbot_graph_components", "n", n));
   if (n == 0) return BTSBOT_OK;
   if (indptr == nullptr || parent == nullptr || root == nullptr) {
     btsbot_set_error("btsbot_graph_components: NULL argument");
@@ -130,7 +124,7 @@ extern "C" int btsbot_graph_components(const int64_t* indptr, const int64_t* ind
 extern "C" int btsbot_dbscan_labels(const int64_t* indptr, const int64_t* indices, const uint8_t* core,
                                     const int64_t* root, const int64_t* cluster, int64_t n, int64_t* labels,
                                     void* stream) {
-  TRY(check_n("btsbot_dbscan_labels", n));
+  TRY(check_count("btsbot_dbscan_labels", "n", n));
   if (n == 0) return BTSBOT_OK;
   if (indptr == nullptr || core == nullptr || root == nullptr || cluster == nullptr || labels == nullptr) {
     btsbot_set_error("btsbot_dbscan_labels: NULL argument");

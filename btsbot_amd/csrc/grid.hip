@@ -22,7 +22,7 @@
 // until k eligible rows were seen, then the safe range of their k-th distance is walked without the square.
 #include <float.h>
 
-#include "common.h"
+#include "list_row.h"
 
 namespace {
 
@@ -404,10 +404,7 @@ int launch_radius_lanes(int lanes, const char* who, const GridView& g, const flo
 }  // namespace
 
 extern "C" int btsbot_grid_finite(const float* points, int64_t n, uint8_t* finite, void* stream) {
-  if (n < 0 || n > 0x7fffffffLL) {
-    btsbot_set_error("btsbot_grid_finite: n=%lld must be in 0 .. 2^31 - 1", (long long)n);
-    return BTSBOT_ERR_INVALID_ARG;
-  }
+  TRY(list_row::check_count("btsbot_grid_finite", "n", n));
   if (n == 0) return BTSBOT_OK;
   if (points == nullptr || finite == nullptr) {
     btsbot_set_error("btsbot_grid_finite: NULL argument");

@@ -18,7 +18,7 @@
 //             first offer whose place is >= k (every later one lies behind it).  Work: k + the offers that enter.
 //   DISTINCT  a two-pointer walk over (list, offers) in merged order, the offers fetched 64 at a time; lane e keeps the
 //             e-th emitted entry and one ballot answers "group seen before".  It ends at k emitted groups.
-#include "common.h"
+#include "list_row.h"
 
 namespace {
 
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(WG) void knn_graph_merge_kernel(int64_t* __restrict
   }
 }
 
-bool misaligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+using list_row::misaligned;
 
 }  // namespace
 

@@ -11,43 +11,26 @@
 //   lrd(i)       1 / (sum_c reach(i, c) / m + 1e-10)         (scikit-learn's constant)         NaN when m = 0
 //   lof(i)       (sum_c lrd(idx[i][c]) / lrd(i)) / m         (each quotient formed first)      NaN when m = 0
 //
-// Lanes.  A row is held by a group of W lanes, lane c its column c: W = 16, 32 or 64, the smallest that holds k, so that
-// at the usual k = 15..20 a wave carries four or two rows and not one (4u has the times of both forms).
+// Lanes.  A row is held by a group of W lanes, lane c its column c (csrc/list_row.h): W = 16, 32 or 64, the smallest that
+// holds k, so that at the usual k = 15..20 a wave carries four or two rows and not one (4u has the times of both forms).
 //
-// The order of a row's sum -- the one thing a float64 restatement has to copy (tests/lof_ref.py, tree_sum):
+// The order of a row's sum (list_row::group_sum) -- the one thing a float64 restatement has to copy (tests/lof_ref.py,
+// tree_sum):
 //   slots v[0..W), v[c] = the term of column c where the entry is present, +0.0 everywhere else (c >= k, absent);
 //   for o = W/2, W/4, ..., 1:  v[c] <- v[c] + v[c ^ o] for every c at once;   the sum is v[0].
 // It depends on the row's own columns and on k (through W) alone: not on the grid, the run, the other rows of the call or
 // where the row stands in its workgroup.  (A slot of +0.0 adds exactly, so W = 64 gives the bits of the smaller W for every
 // sum that is not a zero; BTSBOT_LOF_LANES=64 at compile time is the one-wave-per-row form, kept to time it.)
 // Nothing here is a product followed by a sum, and the contraction is switched off all the same; the divisions are IEEE.
-#include "common.h"
+#include "list_row.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int LOF_MAX_K = 64;
-constexpr int WG = 256;
+using namespace list_row;
 
-template <int W>
-__device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-  for (int o = W / 2; o >= 1; o >>= 1) v = v + __shfl_xor(v, o, W);
-  return v;
-}
-template <int W>
-__device__ __forceinline__ int group_sum_i(int v) {
-#pragma unroll
-  for (int o = W / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o, W);
-  return v;
-}
-template <int W>
-__device__ __forceinline__ int group_max_i(int v) {
-#pragma unroll
-  for (int o = W / 2; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o, W));
-  return v;
-}
+constexpr int LOF_MAX_K = 64;
 
 // what lane c of a row's group holds: its entry, whether it is present, and m
 struct Entry {
@@ -71,8 +54,8 @@ __device__ __forceinline__ Entry load_entry(const int64_t* __restrict__ idx, con
 template <int W>
 __global__ __launch_bounds__(WG) void lof_kdist_kernel(const int64_t* __restrict__ idx, const float* __restrict__ dist, long n,
                                                       int k, double* __restrict__ kdist) {
-  const int c = threadIdx.x % W;
-  const long row = (long)blockIdx.x * (WG / W) + threadIdx.x / W;
+  const int c = lane_col<W>();
+  const long row = lane_row<W>();
   if (row >= n) return;   // (a whole group leaves together)
   const Entry e = load_entry<W>(idx, dist, row, k, c, n);
   const int last = group_max_i<W>(e.present ? c : -1);
@@ -86,8 +69,8 @@ __global__ __launch_bounds__(WG) void lof_kernel(const int64_t* __restrict__ idx
                                                 int k, const double* __restrict__ bank_kdist,
                                                 const double* __restrict__ bank_lrd, long n, double* __restrict__ lrd,
                                                 double* __restrict__ lof) {
-  const int c = threadIdx.x % W;
-  const long row = (long)blockIdx.x * (WG / W) + threadIdx.x / W;
+  const int c = lane_col<W>();
+  const long row = lane_row<W>();
   if (row >= rows) return;
   const Entry e = load_entry<W>(idx, dist, row, k, c, n);
   const double nan = __builtin_nan("");
@@ -108,12 +91,13 @@ __global__ __launch_bounds__(WG) void lof_kernel(const int64_t* __restrict__ idx
   }
 }
 
-int lanes_for(int k) {
+// (BTSBOT_LOF_LANES=64 at compile time: one wave per row at every k, the form 4u times this one against)
+int lof_lanes(int k) {
 #ifdef BTSBOT_LOF_LANES
   static_assert(BTSBOT_LOF_LANES == 64, "only the whole wave holds every k");
   return BTSBOT_LOF_LANES;
 #else
-  return k <= 16 ? 16 : k <= 32 ? 32 : 64;
+  return lanes_for(k);
 #endif
 }
 
@@ -126,12 +110,10 @@ int check_lof_shape(const char* who, int64_t rows, int k, int64_t n) {
   return BTSBOT_OK;
 }
 
-bool misaligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 template <int W>
 void launch_fit(const int64_t* idx, const float* dist, long n, int k, double* kdist, double* lrd, double* lof,
                 hipStream_t s) {
-  const dim3 grid((unsigned)((n + WG / W - 1) / (WG / W)));
+  const dim3 grid = row_grid(n, W);
   hipLaunchKernelGGL(lof_kdist_kernel<W>, grid, dim3(WG), 0, s, idx, dist, n, k, kdist);
   hipLaunchKernelGGL((lof_kernel<W, 0>), grid, dim3(WG), 0, s, idx, dist, n, k, (const double*)kdist, (const double*)nullptr, n,
                      lrd, (double*)nullptr);
@@ -143,8 +125,7 @@ void launch_fit(const int64_t* idx, const float* dist, long n, int k, double* kd
 template <int W>
 void launch_score(const int64_t* idx, const float* dist, long q, int k, const double* bank_kdist, const double* bank_lrd,
                   long n, double* lrd, double* lof, hipStream_t s) {
-  const dim3 grid((unsigned)((q + WG / W - 1) / (WG / W)));
-  hipLaunchKernelGGL((lof_kernel<W, 2>), grid, dim3(WG), 0, s, idx, dist, q, k, bank_kdist, bank_lrd, n, lrd, lof);
+  hipLaunchKernelGGL((lof_kernel<W, 2>), row_grid(q, W), dim3(WG), 0, s, idx, dist, q, k, bank_kdist, bank_lrd, n, lrd, lof);
 }
 
 }  // namespace
@@ -162,11 +143,7 @@ extern "C" int btsbot_lof_fit(const int64_t* idx, const float* dist, int64_t n, 
     return BTSBOT_ERR_INVALID_ARG;
   }
   const hipStream_t s = (hipStream_t)stream;
-  switch (lanes_for(k)) {
-    case 16: launch_fit<16>(idx, dist, (long)n, k, kdist, lrd, lof, s); break;
-    case 32: launch_fit<32>(idx, dist, (long)n, k, kdist, lrd, lof, s); break;
-    default: launch_fit<64>(idx, dist, (long)n, k, kdist, lrd, lof, s); break;
-  }
+  for_lanes(lof_lanes(k), [&](auto w) { launch_fit<decltype(w)::value>(idx, dist, (long)n, k, kdist, lrd, lof, s); });
   LAUNCH_CHECK();
   return BTSBOT_OK;
 }
@@ -186,11 +163,9 @@ extern "C" int btsbot_lof_score(const int64_t* idx, const float* dist, int64_t q
     return BTSBOT_ERR_INVALID_ARG;
   }
   const hipStream_t s = (hipStream_t)stream;
-  switch (lanes_for(k)) {
-    case 16: launch_score<16>(idx, dist, (long)q, k, bank_kdist, bank_lrd, (long)n, lrd, lof, s); break;
-    case 32: launch_score<32>(idx, dist, (long)q, k, bank_kdist, bank_lrd, (long)n, lrd, lof, s); break;
-    default: launch_score<64>(idx, dist, (long)q, k, bank_kdist, bank_lrd, (long)n, lrd, lof, s); break;
-  }
+  for_lanes(lof_lanes(k), [&](auto w) {
+    launch_score<decltype(w)::value>(idx, dist, (long)q, k, bank_kdist, bank_lrd, (long)n, lrd, lof, s);
+  });
   LAUNCH_CHECK();
   return BTSBOT_OK;
 }

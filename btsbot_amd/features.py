@@ -23,7 +23,8 @@ from typing import Dict, Mapping
 import torch
 
 from . import _lib
-from ._object_state import RESERVED_ID, ObjectState, _ptr   # noqa: F401  (RESERVED_ID: part of this module's names)
+from ._lib import ptr as _ptr
+from ._object_state import RESERVED_ID, ObjectState   # noqa: F401  (RESERVED_ID: part of this module's names)
 from .alert_utils import _FEATURE_INPUTS
 
 _RECORD = ("object_id", "n_alerts", "first_jd", "last_jd", "peakmag", "peak_jd", "maxmag")

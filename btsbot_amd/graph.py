@@ -37,14 +37,14 @@ the rest is queued on the current stream.  There is no CPU fallback.  Rows canno
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Tuple, Union
 
 import torch
 
 from . import _lib
 from .mapindex import MapIndex
-from .neighbors import GROUP_MODES, EmbeddingIndex, _check_group_args, _check_k, _metric, _ptr
+from ._lib import ptr as _ptr, stream as _stream
+from .neighbors import GROUP_MODES, EmbeddingIndex, _check_group_args, _check_k, _metric
 
 __all__ = ["KnnGraph"]
 
@@ -167,7 +167,7 @@ class KnnGraph:
             _ptr(self._idx), _ptr(self._dist), self.k, self.k, n0, _ptr(indptr), _ptr(off_idx), _ptr(off_dist),
             int(off_idx.shape[0]), _ptr(groups), 0 if groups is None else int(groups.shape[0]),
             _lib.KNN_GRAPH_DISTINCT if self._distinct else 0, _ptr(rows), 0 if rows is None else int(rows.shape[0]),
-            None, _ptr(changed_count), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+            None, _ptr(changed_count), _stream(self.device)),
             "btsbot_knn_graph_merge")
 
     def update(self, stats: Optional[dict] = None) -> "KnnGraph":

@@ -2,7 +2,7 @@
 
 ``dbscan(emb, eps)`` needs a radius nobody knows in advance, and one radius cannot serve an archive whose clumps differ
 in density by orders of magnitude.  HDBSCAN (Campello et al. 2013; scikit-learn's ``HDBSCAN``) takes ``min_cluster_size``
-alone (csrc/mst.hip, csrc/hdbscan_tree.hip):
+alone (csrc/mr_offer.hip, csrc/mst.hip, csrc/hdbscan_tree.hip):
 
     labels, prob = hdbscan(emb, min_cluster_size=5)              # int64 [N] (-1: noise), float64 [N]
     mst = mutual_reachability_mst(emb_or_index, min_samples)     # .edges int64 [n - 1, 2], .weights f32, .core f32 [N]
@@ -35,7 +35,8 @@ With ``groups=obj`` a row's density is counted in OTHER objects' alerts (``group
 and the LOF); edges still join all finite rows.  A non-finite row has no core distance and no edge: label -1,
 probability 0.  ``method="grid"`` takes the searches of a 2-D map from ``MapIndex``.  There is no CPU fallback.
 
-New rows (csrc/hdbscan_predict.hip).  ``ClusterModel.predict`` answers a row ``q`` that was not
+New rows (csrc/mr_offer.hip, csrc/hdbscan_predict.hip).
+``ClusterModel.predict`` answers a row ``q`` that was not
 fitted from ONE neighbour search.  ``core(q)`` is the distance to its ``(min_samples - 1)``-th nearest eligible bank row
 -- the value it would have as a row of the bank; the bank's own core distances do not move --, ``w(q, b) = max(dist(q, b),
 core(q), core(b))`` in fp32, and the *nearest mutual-reachability neighbour* is the eligible bank row with the smallest
@@ -63,8 +64,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr, stream as _stream
 from .mapindex import MapIndex, check_grid_method
-from .neighbors import EmbeddingIndex, _check_method, _check_splits, _groups, _metric, _ptr, _rows
+from .neighbors import EmbeddingIndex, _check_method, _check_splits, _groups, _metric, _rows
 
 __all__ = ["hdbscan", "mutual_reachability_mst", "MutualReachabilityMST", "ClusterTree", "ClusterModel"]
 
@@ -93,10 +95,6 @@ def _check_mst_args(min_samples, search_k, splits, stats) -> None:
         raise ValueError(f"stats must be None or a dict, got {type(stats).__name__}")
 
 
-def _stream(dev) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 class MutualReachabilityMST:
     """``edges`` int64 [n_finite - 1, 2] (lo, hi), ``weights`` float32 [n_finite - 1] in the order the rounds found
     them, ``core`` float32 [N] (NaN for a non-finite row), ``n`` = N."""
@@ -120,23 +118,42 @@ def _comp_view(index, comp: torch.Tensor):
     return view
 
 
-def _slack(index) -> Tuple[Optional[torch.Tensor], int, float]:
-    """(slack [N] or None, squared?, rel) of ``btsbot_mst_offer_knn``: how far below the last listed distance a row the
-    list does not hold may lie.  The grid ranks by the returned distance itself: nothing.  The tile search ranks its
-    candidates by the expansion form and guarantees the j-th returned squared distance within tau = 8 (D + 2) u (|q|^2 +
-    max |b|^2) of the j-th best (cosine: 8 (D + 2) u on 1 - cos; tests/knn_ref.py clause 3); the direct form the lists
-    carry is within (D + 4) u relative of the truth at both ends."""
+def _sq_norms(rows: torch.Tensor) -> torch.Tensor:
+    """float64 [rows]: |row|^2, 0 for a non-finite row"""
+    sq = (rows.to(torch.float64) ** 2).sum(dim=1)
+    return torch.where(torch.isfinite(sq), sq, torch.zeros_like(sq))
+
+
+def _slack(index, rows: torch.Tensor, bank_sq_max: Optional[torch.Tensor] = None):
+    """(slack [rows] or None, squared?, rel) of ``btsbot_mst_offer_knn`` and ``btsbot_cluster_offer_knn``: how far below
+    the last listed distance a row the list of ``rows[i]`` does not hold may lie.  The grid ranks by the returned distance
+    itself: nothing.  The tile search ranks its candidates by the expansion form and guarantees the j-th returned squared
+    distance within tau = 8 (D + 2, or D + 6 below D = 4) u (|q|^2 + max |b|^2) of the j-th best, with the row's own
+    |q|^2 (cosine: 8 (D + 2) u on 1 - cos; tests/knn_ref.py clause 3); the direct form the lists carry is within (D + 4) u
+    relative of the truth at both ends.  bank_sq_max: max |b|^2 of the bank; None: ``rows`` ARE the bank."""
     if isinstance(index, MapIndex):
         return None, 0, 0.0
     d = index.dim
     rel = 4 * (d + 4) * U
-    rows = index.bank
     if index.metric == "cosine":
-        return torch.full((len(index),), 8 * (d + 2) * U, dtype=torch.float32, device=index.device), 0, rel
-    sq = (rows.to(torch.float64) ** 2).sum(dim=1)
-    sq = torch.where(torch.isfinite(sq), sq, torch.zeros_like(sq))
-    tau = 8 * (d + 2 if d >= 4 else d + 6) * U * (sq + sq.max() if len(index) else sq)
+        return torch.full((int(rows.shape[0]),), 8 * (d + 2) * U, dtype=torch.float32, device=index.device), 0, rel
+    sq = _sq_norms(rows)
+    if bank_sq_max is None:
+        bank_sq_max = sq.max() if sq.numel() else 0.0
+    tau = 8 * (d + 2 if d >= 4 else d + 6) * U * (sq + bank_sq_max)
     return (tau * (1 + 2.0 ** -20)).to(torch.float32), 1, rel
+
+
+def _radius_tier(index, rows: torch.Tensor, todo: torch.Tensor, best_w: torch.Tensor, query_groups, exclude_same_group,
+                 skw: dict):
+    """The second tier of an offer: ``radius`` around the unresolved rows ``todo`` at the weight their lists found, which
+    contains the answer.  (indptr, indices, rdist, total) -- the caller's ``offer_csr`` takes the minimum over them.
+    query_groups: of all ``rows``, or None.  skw: the search's own keywords (``splits``)."""
+    st = {}
+    asked, radius = rows[todo], best_w[todo]
+    gkw = {} if query_groups is None else dict(query_groups=query_groups[todo])
+    indptr, indices, rdist = index.radius(asked, radius, exclude_same_group=exclude_same_group, stats=st, **gkw, **skw)
+    return indptr, indices, rdist, st["total"]
 
 
 def _index_of(emb_or_index, groups, method: str, metric: str, what: str = "tree"):
@@ -207,7 +224,7 @@ def mutual_reachability_mst(emb_or_index: Union[torch.Tensor, EmbeddingIndex, Ma
         n_finite = int(finite.sum()) if n else 0
         if n_finite < max(min_samples, 2):
             raise ValueError(f"{n_finite} finite rows, fewer than max(min_samples, 2) = {max(min_samples, 2)}")
-        slack, squared, rel = _slack(index)
+        slack, squared, rel = _slack(index, rows)
         parent = torch.arange(n, dtype=torch.int32, device=dev)
         comp_w = torch.empty(n, dtype=torch.int32, device=dev)
         comp_edge = torch.empty(n, dtype=torch.int64, device=dev)
@@ -248,10 +265,7 @@ def mutual_reachability_mst(emb_or_index: Union[torch.Tensor, EmbeddingIndex, Ma
             t0 = lap("ms_offer", t0)
             total = 0
             if todo.numel():
-                st = {}
-                indptr, indices, rdist = view.radius(rows[todo], best_w[todo], query_groups=comp[todo],
-                                                     exclude_same_group=True, stats=st, **skw)
-                total = st["total"]
+                indptr, indices, rdist, total = _radius_tier(view, rows, todo, best_w, comp, True, skw)
                 _lib.check(L.btsbot_mst_offer_csr(_ptr(indptr), _ptr(indices), _ptr(rdist), _ptr(todo), int(todo.numel()),
                                                   n, _ptr(core), _ptr(best_w), _ptr(best_j), _stream(dev)),
                            "btsbot_mst_offer_csr")
@@ -274,14 +288,20 @@ def mutual_reachability_mst(emb_or_index: Union[torch.Tensor, EmbeddingIndex, Ma
         return MutualReachabilityMST(edges[:m].contiguous(), weights[:m].contiguous(), core)
 
 
-def _tree_host(edges: np.ndarray, weights: np.ndarray, n: int, min_cluster_size: int, method: str = "eom",
-               allow_single_cluster: bool = False):
-    """``btsbot_hdbscan_tree`` on host arrays: (labels int64 [n], prob float64 [n], (parent, child, lambda, size))."""
+def _host_edges(edges, weights, min_cluster_size, method, allow_single_cluster) -> Tuple[np.ndarray, np.ndarray]:
+    """What the host passes take: the selection checked, ``edges`` int64 [m, 2] and ``weights`` float32 [m], contiguous."""
     _check_selection(min_cluster_size, method, allow_single_cluster)
     edges = np.ascontiguousarray(edges, dtype=np.int64).reshape(-1, 2)
     weights = np.ascontiguousarray(weights, dtype=np.float32)
     if edges.shape[0] != weights.shape[0]:
         raise ValueError(f"{edges.shape[0]} edges, {weights.shape[0]} weights")
+    return edges, weights
+
+
+def _tree_host(edges: np.ndarray, weights: np.ndarray, n: int, min_cluster_size: int, method: str = "eom",
+               allow_single_cluster: bool = False):
+    """``btsbot_hdbscan_tree`` on host arrays: (labels int64 [n], prob float64 [n], (parent, child, lambda, size))."""
+    edges, weights = _host_edges(edges, weights, min_cluster_size, method, allow_single_cluster)
     labels, prob = np.empty(n, np.int64), np.empty(n, np.float64)
     cap = 2 * n
     cp, cc, cs = (np.empty(cap, np.int64) for _ in range(3))
@@ -303,11 +323,7 @@ def _model_host(edges: np.ndarray, weights: np.ndarray, n: int, min_cluster_size
     """``btsbot_hdbscan_model`` on host arrays: the tables of a fitted tree as numpy arrays -- ``row_cluster`` int32 [n],
     ``row_lambda`` and ``outlier`` float64 [n]; ``parent`` int32, ``birth`` float64, ``label`` int32, ``max_lambda`` and
     ``death`` float64 [nc] -- and ``lam_zero``, a float."""
-    _check_selection(min_cluster_size, method, allow_single_cluster)
-    edges = np.ascontiguousarray(edges, dtype=np.int64).reshape(-1, 2)
-    weights = np.ascontiguousarray(weights, dtype=np.float32)
-    if edges.shape[0] != weights.shape[0]:
-        raise ValueError(f"{edges.shape[0]} edges, {weights.shape[0]} weights")
+    edges, weights = _host_edges(edges, weights, min_cluster_size, method, allow_single_cluster)
     cap = max(n - 1, 1)
     t = dict(row_cluster=np.empty(n, np.int32), row_lambda=np.empty(n, np.float64), outlier=np.empty(n, np.float64),
              parent=np.empty(cap, np.int32), birth=np.empty(cap, np.float64), label=np.empty(cap, np.int32),
@@ -402,21 +418,6 @@ def hdbscan(emb: torch.Tensor, min_cluster_size: int = 5, min_samples: Optional[
     return (labels, prob, tree) if return_tree else (labels, prob)
 
 
-def _query_slack(index, queries: torch.Tensor, bank_sq_max: Optional[torch.Tensor]):
-    """``_slack`` for NEW rows: (slack [Q] or None, squared?, rel) of ``btsbot_cluster_offer_knn``.  The tile search's
-    bound is tau = 8 (D + 2, or D + 6 below D = 4) u (|q|^2 + max |b|^2) with the QUERY's own |q|^2."""
-    if isinstance(index, MapIndex):
-        return None, 0, 0.0
-    d = index.dim
-    rel = 4 * (d + 4) * U
-    if index.metric == "cosine":
-        return torch.full((int(queries.shape[0]),), 8 * (d + 2) * U, dtype=torch.float32, device=index.device), 0, rel
-    sq = (queries.to(torch.float64) ** 2).sum(dim=1)
-    sq = torch.where(torch.isfinite(sq), sq, torch.zeros_like(sq))
-    tau = 8 * (d + 2 if d >= 4 else d + 6) * U * (sq + bank_sq_max)
-    return (tau * (1 + 2.0 ** -20)).to(torch.float32), 1, rel
-
-
 class ClusterModel:
     """The HDBSCAN fit of a bank, kept to assign new rows to its clusters (see the module text).
 
@@ -469,14 +470,13 @@ class ClusterModel:
         self.outlier_scores = self.tables["outlier"]
         self._bank_sq_max = None
         if isinstance(self.index, EmbeddingIndex) and self.metric == "euclidean":
-            sq = (self.index.bank.to(torch.float64) ** 2).sum(dim=1)
-            self._bank_sq_max = torch.where(torch.isfinite(sq), sq, torch.zeros_like(sq)).max()
+            self._bank_sq_max = _sq_norms(self.index.bank).max()
         return self
 
     def _offer(self, idx: torch.Tensor, dist: torch.Tensor, q: torch.Tensor):
         """btsbot_cluster_offer_knn on the lists of the rows ``q``: (core_q, best_w, best_j, unresolved)"""
         nq, k, dev = int(idx.shape[0]), int(idx.shape[1]), self.device
-        slack, squared, rel = _query_slack(self.index, q, self._bank_sq_max)
+        slack, squared, rel = _slack(self.index, q, self._bank_sq_max)
         core_q = torch.empty(nq, dtype=torch.float32, device=dev)
         best_w = torch.empty(nq, dtype=torch.float32, device=dev)
         best_j = torch.empty(nq, dtype=torch.int32, device=dev)
@@ -528,10 +528,8 @@ class ClusterModel:
         if grid and splits:
             raise ValueError("a MapIndex has no splits")
         k = max(search_k, ms - 1, 1)
-        kw = dict(query_groups=query_groups, exclude_same_group=exclude_same_group)
-        if not grid:
-            kw["splits"] = splits
-        idx, dist = index.query(queries, k, **kw)
+        skw = {} if grid else {"splits": splits}
+        idx, dist = index.query(queries, k, query_groups=query_groups, exclude_same_group=exclude_same_group, **skw)
         nq, n = int(idx.shape[0]), len(self)
         with torch.cuda.device(dev):
             q = queries.detach().to(torch.float32).contiguous()
@@ -539,14 +537,7 @@ class ClusterModel:
             todo = unres.nonzero().view(-1)                       # the host read: the rows of the radius tier
             total = 0
             if todo.numel():
-                st = {}
-                rkw = dict(exclude_same_group=exclude_same_group, stats=st)
-                if query_groups is not None:
-                    rkw["query_groups"] = query_groups[todo]
-                if not grid:
-                    rkw["splits"] = splits
-                indptr, indices, rdist = index.radius(q[todo], best_w[todo], **rkw)
-                total = st["total"]
+                indptr, indices, rdist, total = _radius_tier(index, q, todo, best_w, query_groups, exclude_same_group, skw)
                 _lib.check(L.btsbot_cluster_offer_csr(_ptr(indptr), _ptr(indices), _ptr(rdist), _ptr(todo),
                                                       int(todo.numel()), nq, n, _ptr(self.mst.core), _ptr(core_q),
                                                       _ptr(best_w), _ptr(best_j), _stream(dev)), "btsbot_cluster_offer_csr")

@@ -33,16 +33,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr, stream as _stream
 
 _U64 = (1 << 64) - 1
-
-
-def _ptr(t: torch.Tensor) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr() if t.numel() else 0)
-
-
-def _stream(dev) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _int(v, name: str, lo: int, hi: Optional[int] = None) -> int:

@@ -30,7 +30,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .neighbors import _check_group_args, _check_radius_args, _csr_order, _groups, _ptr
+from ._lib import ptr as _ptr, stream as _stream
+from .neighbors import _check_group_args, _check_radius_args, _csr_order, _groups
 
 POINTS_PER_CELL = 2      # the default resolution aims at this many points per cell on uniform data
 DEFAULT_MAX_CELLS = 2048  # ... with at most this many cells per axis (cell_start: 16 MiB)
@@ -103,7 +104,7 @@ class MapIndex:
         inf = float("inf")
         with torch.cuda.device(dev):
             finite = torch.empty(n, dtype=torch.uint8, device=dev)
-            _lib.check(L.btsbot_grid_finite(_ptr(pts), n, _ptr(finite), self._stream()), "btsbot_grid_finite")
+            _lib.check(L.btsbot_grid_finite(_ptr(pts), n, _ptr(finite), _stream(self.device)), "btsbot_grid_finite")
             if n:
                 fin = finite.view(torch.bool)[:, None]
                 bbox = torch.cat([torch.where(fin, pts, pts.new_full((), inf)).amin(dim=0),
@@ -113,7 +114,7 @@ class MapIndex:
             self._geom = torch.empty(4, dtype=torch.float32, device=dev)
             cell = torch.empty(n, dtype=torch.int32, device=dev)
             _lib.check(L.btsbot_grid_cells(_ptr(pts), n, C.c_void_p(bbox.data_ptr()), G, C.c_void_p(self._geom.data_ptr()),
-                                           _ptr(cell), self._stream()), "btsbot_grid_cells")
+                                           _ptr(cell), _stream(self.device)), "btsbot_grid_cells")
             cell, order = torch.sort(cell, stable=True)
             self._cell_start = torch.searchsorted(cell, torch.arange(G * G + 1, dtype=torch.int32, device=dev)
                                                   ).to(torch.int32).contiguous()
@@ -133,9 +134,6 @@ class MapIndex:
     def groups(self) -> Optional[torch.Tensor]:
         """The points' groups, int64 [len], or None."""
         return self._groups
-
-    def _stream(self) -> C.c_void_p:
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _grid_args(self, self_offset: int, query_groups, flags: int):
         return (C.c_void_p(self._geom.data_ptr()), self.cells, C.c_void_p(self._cell_start.data_ptr()),
@@ -165,7 +163,7 @@ class MapIndex:
         counts = torch.zeros(nq, dtype=torch.int64, device=self.device)
         vis = torch.zeros(nq, dtype=torch.int64, device=self.device) if visited else None
         _lib.check(_lib.lib().btsbot_grid_radius_count(_ptr(q), nq, _ptr(rad), *grid, self._lanes, _ptr(counts), _ptr(vis),
-                                                       self._stream()), "btsbot_grid_radius_count")
+                                                       _stream(self.device)), "btsbot_grid_radius_count")
         return counts, vis
 
     def radius(self, queries: torch.Tensor, r, *, query_groups: Optional[torch.Tensor] = None,
@@ -202,7 +200,7 @@ class MapIndex:
             dist = torch.empty(total, dtype=torch.float32, device=dev)
             err = torch.zeros(1, dtype=torch.int32, device=dev)
             _lib.check(L.btsbot_grid_radius_fill(_ptr(q), nq, _ptr(rad), *grid, self._lanes, _ptr(indptr), total,
-                                                 _ptr(cand), _ptr(dist), C.c_void_p(err.data_ptr()), self._stream()),
+                                                 _ptr(cand), _ptr(dist), C.c_void_p(err.data_ptr()), _stream(self.device)),
                        "btsbot_grid_radius_fill")
             rows = torch.repeat_interleave(torch.arange(nq, device=dev), counts, output_size=total)
             order = _csr_order(rows, cand.to(torch.int64), dist, max(self._n, 1), sort)
@@ -239,5 +237,5 @@ class MapIndex:
         dist = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().btsbot_grid_knn(_ptr(q), nq, k, *self._grid_args(self_offset, query_groups, flags),
-                                                  _ptr(idx), _ptr(dist), self._stream()), "btsbot_grid_knn")
+                                                  _ptr(idx), _ptr(dist), _stream(self.device)), "btsbot_grid_knn")
         return idx, dist

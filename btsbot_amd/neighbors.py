@@ -69,18 +69,14 @@ described above.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Tuple
 
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr, stream as _stream
 
 METRICS = tuple(_lib.KNN_METRIC)
-
-
-def _ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
 
 
 def _rows(t, name: str, device=None) -> torch.Tensor:
@@ -203,9 +199,6 @@ class EmbeddingIndex:
         """The rows' groups, int64 [len] (a view of the index's storage), or None for an index without groups."""
         return None if self._groups is None else self._groups[:self._n]
 
-    def _stream(self) -> C.c_void_p:
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _record_bytes(self) -> int:
         return int(_lib.lib().btsbot_knn_bank_bytes(1, self.dim))
 
@@ -243,7 +236,7 @@ class EmbeddingIndex:
             if groups is not None:
                 self._groups[self._n:self._n + n].copy_(groups)
             _lib.check(L.btsbot_knn_pack_bank(_ptr(new), self._n, n, self.dim, self._metric_id, _ptr(self._packed),
-                                              self._cap, self._stream()), "btsbot_knn_pack_bank")
+                                              self._cap, _stream(self.device)), "btsbot_knn_pack_bank")
         self._n += n
         return self
 
@@ -287,7 +280,7 @@ class EmbeddingIndex:
         with torch.cuda.device(self.device):
             ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
             args = (_ptr(q), nq, _ptr(self._bank), _ptr(self._packed), self._n, self.dim, k, self._metric_id,
-                    self_offset, splits, _ptr(idx), _ptr(dist), _ptr(ws), need, self._stream())
+                    self_offset, splits, _ptr(idx), _ptr(dist), _ptr(ws), need, _stream(self.device))
             if flags == 0:
                 _lib.check(L.btsbot_knn_query(*args), "btsbot_knn_query")
             else:
@@ -326,7 +319,7 @@ class EmbeddingIndex:
             tail = (_ptr(self._packed), n, self.dim, self._metric_id, _ptr(rad), self_offset, splits,
                     _ptr(query_groups) if flags else None, _ptr(self._groups) if flags else None, flags)
             if nq and n:
-                _lib.check(L.btsbot_knn_radius_count(*head, *tail, _ptr(counts), _ptr(ws), need, self._stream()),
+                _lib.check(L.btsbot_knn_radius_count(*head, *tail, _ptr(counts), _ptr(ws), need, _stream(self.device)),
                            "btsbot_knn_radius_count")
             offsets = _scan_counts(counts)
             n_cand, bad = torch.stack([offsets[-1], bad]).tolist()          # the host read that sizes the candidates
@@ -339,7 +332,7 @@ class EmbeddingIndex:
             if n_cand:
                 _lib.check(L.btsbot_knn_radius_fill(*head, _ptr(self._bank), *tail, _ptr(counts), _ptr(offsets), n_cand,
                                                     _ptr(cand), _ptr(cdist), _ptr(keep), _ptr(err), _ptr(ws), need,
-                                                    self._stream()), "btsbot_knn_radius_fill")
+                                                    _stream(self.device)), "btsbot_knn_radius_fill")
             row_off = offsets[::splits]                                       # [Q + 1]: a row's candidates are contiguous
             kept = torch.cat([offsets.new_zeros(1), torch.cumsum(keep, 0, dtype=torch.int64)])
             indptr = kept[row_off]
@@ -391,7 +384,7 @@ class EmbeddingIndex:
                     self_offset, splits, _ptr(query_groups) if flags else None, _ptr(self._groups) if flags else None,
                     flags)
             _lib.check(L.btsbot_knn_rank_count(*head, _ptr(dist), _ptr(rank), _ptr(counts), _ptr(ws), need,
-                                               self._stream()), "btsbot_knn_rank_count")
+                                               _stream(self.device)), "btsbot_knn_rank_count")
             offsets = _scan_counts(counts)
             n_band = int(offsets[-1])                                       # the host read that sizes the band pairs
             if max_band is not None and n_band > max_band:
@@ -402,7 +395,7 @@ class EmbeddingIndex:
                 cmask = torch.zeros(n_band, dtype=torch.int64, device=dev)
                 err = torch.zeros(1, dtype=torch.int32, device=dev)
                 _lib.check(L.btsbot_knn_rank_fill(*head, _ptr(dist), _ptr(rank), _ptr(counts), _ptr(offsets), n_band,
-                                                  _ptr(cand), _ptr(cmask), _ptr(err), _ptr(ws), need, self._stream()),
+                                                  _ptr(cand), _ptr(cmask), _ptr(err), _ptr(ws), need, _stream(self.device)),
                            "btsbot_knn_rank_fill")
                 flag = int(err[0])                                          # the second read: the fill's bounds check
             if stats is not None:

@@ -38,7 +38,6 @@ fit to the rows the index holds now at the cost of the new rows: ``graph.update(
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Tuple, Union
 
 import torch
@@ -46,7 +45,8 @@ import torch
 from . import _lib
 from .graph import KnnGraph
 from .mapindex import MapIndex
-from .neighbors import GROUP_MODES, EmbeddingIndex, _ptr, knn_graph
+from ._lib import ptr as _ptr, stream as _stream
+from .neighbors import GROUP_MODES, EmbeddingIndex, knn_graph
 
 __all__ = ["NoveltyModel", "local_outlier_factor", "kth_neighbor_distance"]
 
@@ -75,10 +75,6 @@ def _graph(idx, dist, name: str = "knn") -> Tuple[torch.Tensor, torch.Tensor]:
     if not 1 <= idx.shape[1] <= _lib.LOF_MAX_K:
         raise ValueError(f"{name}: k must be in 1..{_lib.LOF_MAX_K}, got {idx.shape[1]}")
     return idx.detach().contiguous(), dist.detach().contiguous()
-
-
-def _stream(dev) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _fit(idx: torch.Tensor, dist: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

@@ -21,7 +21,8 @@ from typing import Dict, Mapping
 import torch
 
 from . import _lib
-from ._object_state import RESERVED_ID, ObjectState, _ptr   # noqa: F401  (RESERVED_ID: part of this module's names)
+from ._lib import ptr as _ptr
+from ._object_state import RESERVED_ID, ObjectState   # noqa: F401  (RESERVED_ID: part of this module's names)
 from .val import POLICIES_PER_LAUNCH, REFERENCE_POLICIES, _policy_table
 
 _RECORD = ("object_id", "n_alerts", "min_magpsf", "last_jd", "count", "trigger_jd", "trigger_mag")

@@ -1202,7 +1202,8 @@ int btsbot_knn_graph_merge(int64_t* idx, float* dist, int64_t stride, int k, int
                            int64_t n_groups, int flags, const int64_t* rows, int64_t n_rows, uint8_t* changed_rows,
                            int32_t* changed_count, void* stream);
 
-/* ---- HDBSCAN: the mutual-reachability spanning tree and its hierarchy (csrc/mst.hip, csrc/hdbscan_tree.hip) ---- */
+/* ---- HDBSCAN: the mutual-reachability spanning tree and its hierarchy (csrc/mr_offer.hip, csrc/mst.hip,
+ *      csrc/hdbscan_tree.hip) ---- */
 
 /* The minimum spanning tree of the complete graph on the finite rows under w(a, b) = max(d(a, b), core(a), core(b), 0) in
  * fp32, by Boruvka rounds.  A round's searches are btsbot_knn_query_grouped / btsbot_grid_knn and btsbot_knn_radius_* /
@@ -1267,7 +1268,7 @@ int btsbot_hdbscan_tree(const int64_t* edges, const float* weights, int64_t n_ed
                         int64_t* n_cond);
 
 /* ---- HDBSCAN for new rows: the tables of a fitted tree and the prediction (csrc/hdbscan_tree.hip,
- *      csrc/hdbscan_predict.hip) ---- */
+ *      csrc/mr_offer.hip, csrc/hdbscan_predict.hip) ---- */
 
 /* btsbot_hdbscan_model(): the same pass as btsbot_hdbscan_tree() on the same inputs (HOST arrays, no GPU call, the same
  * errors), handing out the tables a prediction walks.  Clusters are in the canonical numbering less n: ids 0 ..

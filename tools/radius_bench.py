@@ -87,7 +87,7 @@ def count_pass(index, q, r):
 
     def go():
         _lib.check(L.btsbot_knn_radius_count(p(q), nq, p(index._packed), n, index.dim, index._metric_id, p(rad), -1, splits,
-                                             None, None, 0, p(counts), p(ws), need, index._stream()), "count")
+                                             None, None, 0, p(counts), p(ws), need, _lib.stream(index.device)), "count")
     return go
 
 

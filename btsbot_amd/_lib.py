@@ -59,7 +59,7 @@ SYMBOLS = [
     "btsbot_layout_smooth_knn", "btsbot_layout_symmetrize_workspace", "btsbot_layout_symmetrize", "btsbot_layout_init",
     "btsbot_layout_epochs", "btsbot_layout_smooth_knn_query", "btsbot_layout_transform",
     "btsbot_lof_fit", "btsbot_lof_score",
-    "btsbot_knn_graph_merge",
+    "btsbot_knn_graph_merge", "btsbot_knn_graph_compact",
     "btsbot_mst_offer_knn", "btsbot_mst_offer_csr", "btsbot_mst_merge", "btsbot_hdbscan_tree",
     "btsbot_hdbscan_model", "btsbot_cluster_offer_knn", "btsbot_cluster_offer_csr", "btsbot_cluster_assign",
 ]
@@ -352,6 +352,8 @@ def lib() -> C.CDLL:
     L.btsbot_lof_score.argtypes = [vp, vp, i64, i32, vp, vp, i64, vp, vp, vp]
     L.btsbot_knn_graph_merge.restype = i32
     L.btsbot_knn_graph_merge.argtypes = [vp, vp, i64, i32, i64, vp, vp, vp, i64, vp, i64, i32, vp, i64, vp, vp, vp]
+    L.btsbot_knn_graph_compact.restype = i32
+    L.btsbot_knn_graph_compact.argtypes = [vp, vp, i64, i32, i64, vp, vp, vp, i64, i64, i32, vp, vp, vp]
     L.btsbot_mst_offer_knn.restype = i32
     L.btsbot_mst_offer_knn.argtypes = [vp, vp, i64, i32, vp, vp, i32, f32, vp, vp, vp, vp]
     L.btsbot_mst_offer_csr.restype = i32

@@ -1,5 +1,5 @@
 // btsbot_knn_graph_merge: offers of new rows merged into the neighbour lists of old rows, in place (gfx950), DESIGN.md
-// section 4x.
+// section 4x.  btsbot_knn_graph_compact, the lists after rows were removed, is at the end of the file (section 4y).
 //
 // A list is what btsbot_knn_query writes: k slots, the present entries (idx >= 0) first, ordered by (dist, idx), then a
 // -1 / +inf tail.  A row's offers are a slice of a CSR, ordered by (dist, idx) too, and every offer index is larger than
@@ -141,6 +141,77 @@ __global__ __launch_bounds__(WG) void knn_graph_merge_kernel(int64_t* __restrict
 
 using list_row::misaligned;
 
+// ---- btsbot_knn_graph_compact: the lists of the surviving rows, renumbered, out of place.
+//
+// W lanes hold old row a, lane c its column c (list_row.h).  A streaming pass, 12 k bytes per row in and out, with one
+// 8-byte gather per entry into new_of_old, which stays in L2 at a million rows.  The lanes of a removed row leave after
+// their one (broadcast) read of new_of_old[a]; the others read the row whole, map every present entry through new_of_old,
+// and one ballot over the row's lanes gives a surviving entry its new column: the survivors before it.  Input and output
+// do not overlap (the entry refuses it), so a row is its group's to write in any order; lane c also writes the tail slot
+// c where c is past the survivors.  The two counters take at most two atomics per wave, from its first active lane.
+template <int W>
+__global__ __launch_bounds__(list_row::WG) void knn_graph_compact_kernel(
+    const int64_t* __restrict__ idx, const float* __restrict__ dist, long stride, int k, long n_old,
+    const int64_t* __restrict__ new_of_old, int64_t* __restrict__ out_idx, float* __restrict__ out_dist, long out_stride,
+    long n_new, bool distinct, uint8_t* __restrict__ damaged, int32_t* __restrict__ counts) {
+  const int c = list_row::lane_col<W>();
+  const long a = list_row::lane_row<W>();
+  if (a >= n_old) return;   // (a whole group leaves together throughout)
+  const long j = (long)new_of_old[a];
+  if (j < 0 || j >= n_new) return;
+  const bool in_row = c < k;
+  const float inf = __builtin_inff();
+  const int64_t e = in_row ? idx[a * stride + c] : -1;
+  const float d = in_row ? dist[a * stride + c] : inf;
+  int64_t* const oi = out_idx + j * out_stride;
+  float* const od = out_dist + j * out_stride;
+  const float d0 = __shfl(d, 0, W);
+  if (d0 != d0) {   // a non-finite row: copied as it stands
+    if (in_row) {
+      oi[c] = e;
+      od[c] = d;
+    }
+    if (c == 0) damaged[j] = 0;
+    return;
+  }
+  const bool present = e >= 0;
+  const int64_t m = (present && e < n_old) ? new_of_old[e] : -1;   // (an entry out of range is never a subscript)
+  const bool survives = m >= 0;
+  const int base = (threadIdx.x % WAVE) & ~(W - 1);   // where the group's lanes stand in the wave's ballot
+  const unsigned long long ones = W == 64 ? ~0ull : ((1ull << (W % 64)) - 1);
+  const unsigned long long dropped_wave = __ballot(present && !survives);
+  const unsigned long long kept_mask = (__ballot(survives) >> base) & ones;
+  const unsigned long long present_mask = (__ballot(present) >> base) & ones;
+  const bool any_dropped = ((dropped_wave >> base) & ones) != 0;
+  const int kept = __popcll(kept_mask);
+  const bool full = ((present_mask >> (k - 1)) & 1ull) != 0;
+  const bool dam = any_dropped && (full || distinct);
+  if (survives) {
+    const int at = __popcll(kept_mask & ((1ull << c) - 1));
+    oi[at] = m;
+    od[at] = d;
+  }
+  if (in_row && c >= kept) {
+    oi[c] = -1;
+    od[c] = inf;
+  }
+  if (c == 0) damaged[j] = dam ? 1 : 0;
+  if (counts != nullptr) {
+    const unsigned long long active = __ballot(true);
+    const unsigned long long dam_wave = __ballot(c == 0 && dam);
+    if ((int)(threadIdx.x % WAVE) == __ffsll((long long)active) - 1) {
+      if (dam_wave != 0) atomicAdd(counts, __popcll(dam_wave));
+      if (dropped_wave != 0) atomicAdd(counts + 1, __popcll(dropped_wave));
+    }
+  }
+}
+
+// [p, p + bytes) and [q, q + bytes_q) share a byte
+inline bool overlap(const void* p, int64_t bytes, const void* q, int64_t bytes_q) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return a < b + (uintptr_t)bytes_q && b < a + (uintptr_t)bytes;
+}
+
 }  // namespace
 
 extern "C" int btsbot_knn_graph_merge(int64_t* idx, float* dist, int64_t stride, int k, int64_t n_old, const int64_t* indptr,
@@ -191,6 +262,60 @@ extern "C" int btsbot_knn_graph_merge(int64_t* idx, float* dist, int64_t stride,
     hipLaunchKernelGGL(knn_graph_merge_kernel<false>, grid, dim3(WG), 0, s, idx, dist, (long)stride, k, (long)n_old, indptr,
                        offer_idx, offer_dist, (long)n_offers, groups, (long)n_groups, rows, (long)n_rows, changed_rows,
                        changed_count);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+extern "C" int btsbot_knn_graph_compact(const int64_t* idx, const float* dist, int64_t stride, int k, int64_t n_old,
+                                        const int64_t* new_of_old, int64_t* out_idx, float* out_dist, int64_t out_stride,
+                                        int64_t n_new, int flags, uint8_t* damaged, int32_t* counts, void* stream) {
+  const char* who = "btsbot_knn_graph_compact";
+  const bool distinct = (flags & BTSBOT_KNN_GRAPH_DISTINCT) != 0;
+  if ((flags & ~BTSBOT_KNN_GRAPH_DISTINCT) != 0) {
+    btsbot_set_error("%s: unknown flags %d", who, flags);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  const int max_k = distinct ? GM_MAX_K_DISTINCT : GM_MAX_K;
+  if (k < 1 || k > max_k || stride < k || out_stride < k) {
+    btsbot_set_error("%s: need 1 <= k <= %d%s, stride >= k and out_stride >= k (k=%d stride=%lld out_stride=%lld)", who, max_k,
+                     distinct ? " (the distinct mode)" : "", k, (long long)stride, (long long)out_stride);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  TRY(list_row::check_count(who, "n_old", n_old));
+  TRY(list_row::check_count(who, "n_new", n_new));
+  if (n_new > n_old) {
+    btsbot_set_error("%s: n_new=%lld survivors of n_old=%lld rows", who, (long long)n_new, (long long)n_old);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (n_old == 0 || n_new == 0) return BTSBOT_OK;
+  if (idx == nullptr || dist == nullptr || new_of_old == nullptr || out_idx == nullptr || out_dist == nullptr ||
+      damaged == nullptr) {
+    btsbot_set_error("%s: NULL argument (only counts may be NULL)", who);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (misaligned(idx, 8) || misaligned(dist, 4) || misaligned(new_of_old, 8) || misaligned(out_idx, 8) ||
+      misaligned(out_dist, 4) || misaligned(counts, 4)) {
+    btsbot_set_error("%s: misaligned argument (int64 arrays: 8 bytes; dist, out_dist, counts: 4)", who);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  const int64_t in_slots = (n_old - 1) * stride + k, out_slots = (n_new - 1) * out_stride + k;
+  const void* const in_p[3] = {idx, dist, new_of_old};
+  const int64_t in_b[3] = {in_slots * 8, in_slots * 4, n_old * 8};
+  const void* const out_p[3] = {out_idx, out_dist, damaged};
+  const int64_t out_b[3] = {out_slots * 8, out_slots * 4, n_new};
+  for (int i = 0; i < 3; ++i)
+    for (int o = 0; o < 3; ++o)
+      if (overlap(in_p[i], in_b[i], out_p[o], out_b[o])) {
+        btsbot_set_error("%s: an output array overlaps an input array (the lists are compacted out of place)", who);
+        return BTSBOT_ERR_INVALID_ARG;
+      }
+  const hipStream_t s = (hipStream_t)stream;
+  list_row::for_lanes(list_row::lanes_for(k), [&](auto w) {
+    constexpr int W = decltype(w)::value;
+    hipLaunchKernelGGL(knn_graph_compact_kernel<W>, list_row::row_grid((long)n_old, W), dim3(list_row::WG), 0, s, idx, dist,
+                       (long)stride, k, (long)n_old, new_of_old, out_idx, out_dist, (long)out_stride, (long)n_new, distinct,
+                       damaged, counts);
+  });
   LAUNCH_CHECK();
   return BTSBOT_OK;
 }

@@ -66,7 +66,7 @@ import torch
 from . import _lib
 from ._lib import ptr as _ptr, stream as _stream
 from .mapindex import MapIndex, check_grid_method
-from .neighbors import EmbeddingIndex, _check_method, _check_splits, _groups, _metric, _rows
+from .neighbors import EmbeddingIndex, _check_method, _check_splits, _groups, _metric, _rows, _stale_fit
 
 __all__ = ["hdbscan", "mutual_reachability_mst", "MutualReachabilityMST", "ClusterTree", "ClusterModel"]
 
@@ -428,8 +428,8 @@ class ClusterModel:
     and ``prob`` are ``hdbscan``'s, ``outlier_scores`` is ``tree.outlier_scores(min_cluster_size)`` --, ``tree``, ``mst``
     and ``index`` what it was made of.  The tables ``predict`` walks live on the index's device.
 
-    The fit does not follow ``index.add``; ``refit()`` recomputes it, and ``predict`` refuses an index that has grown
-    since.  Calls on one model must be ordered by the caller's streams.  There is no CPU fallback."""
+    The fit does not follow ``index.add`` or ``index.remove``; ``refit()`` recomputes it, and ``predict`` refuses an index
+    that has grown since or that rows were removed from (``index.generation``).  Calls on one model must be ordered by the caller's streams.  There is no CPU fallback."""
 
     def __init__(self, bank_or_index: Union[torch.Tensor, EmbeddingIndex, MapIndex], min_cluster_size: int = 5,
                  min_samples: Optional[int] = None, metric: str = "euclidean", *, cluster_selection_method: str = "eom",
@@ -471,6 +471,7 @@ class ClusterModel:
         self._bank_sq_max = None
         if isinstance(self.index, EmbeddingIndex) and self.metric == "euclidean":
             self._bank_sq_max = _sq_norms(self.index.bank).max()
+        self._generation = getattr(self.index, "generation", 0)
         return self
 
     def _offer(self, idx: torch.Tensor, dist: torch.Tensor, q: torch.Tensor):
@@ -512,9 +513,9 @@ class ClusterModel:
         1)`` rows and no answer depends on it.  splits: ``EmbeddingIndex.query``'s (None: the model's).  stats: a dict
         that receives ``unresolved`` (rows sent to the radius tier) and ``radius_total`` (entries of their lists).  One
         host read, the unresolved rows, and the radius search's own when there are any."""
-        if len(self.index) != len(self):
-            raise RuntimeError(f"the index holds {len(self.index)} rows, the fit {len(self)}: a fit does not follow "
-                               "index.add -- call refit()")
+        stale = _stale_fit(self.index, len(self), self._generation)
+        if stale is not None:
+            raise RuntimeError(stale + " -- call refit()")
         ms = self.min_samples
         if search_k is None:
             search_k = min(_lib.MST_MAX_K, max(8, 2 * ms))

@@ -375,6 +375,7 @@ class EmbeddingMap:
         m = EmbeddingMap.from_positions(bank, y)        # a map made earlier
         y_new = m.transform(queries)                    # the map does not move
         m.extend(rows)                                  # transform, then the rows join the bank at those positions
+        kept = m.remove(which)                          # rows leave the bank and the map; the survivors do not move
         mi = m.map_index()                              # a MapIndex over embedding_: neighbours ON the map
 
     ``n_neighbors`` counts the row itself in the fit (as ``embedding_layout``) and is the number of bank rows a new row is
@@ -424,6 +425,16 @@ class EmbeddingMap:
         self.embedding_ = torch.cat([self.embedding_, y])
         self._map_index = None
         return y
+
+    def remove(self, which: torch.Tensor) -> torch.Tensor:
+        """Removes rows from the bank and from the map (``EmbeddingIndex.remove``; ``which``: a bool [len] mask or int64
+        row numbers) and returns ``kept`` int64, the old row number of every survivor.  ``embedding_`` becomes
+        ``embedding_[kept]``: the survivors' positions do not move, and ``transform`` then attaches new rows to
+        survivors only.  The cached ``MapIndex`` is dropped."""
+        kept = self.index.remove(which)
+        self.embedding_ = self.embedding_[kept]
+        self._map_index = None
+        return kept
 
     def quality(self, n_neighbors: Optional[int] = None, rows: Optional[torch.Tensor] = None) -> dict:
         """``quality.map_quality`` of ``embedding_`` against the bank it maps: trustworthiness, continuity and

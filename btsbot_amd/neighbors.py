@@ -6,6 +6,7 @@ of an archive lie nearest to these" without ever forming the [Q, N] distance mat
     idx, dist = embedding_neighbors(queries, bank, k)            # int64 [Q, k], float32 [Q, k]
     index = EmbeddingIndex(bank)                                 # packs the bank once
     index.add(more_rows)                                         # packs only the new rows
+    kept = index.remove(mask_or_rows)                            # stable compaction; side = side[kept] stays aligned
     idx, dist = index.query(queries, k)
     idx, dist = knn_graph(emb, k)                                # every row among the others (self first, distance 0)
 
@@ -168,6 +169,13 @@ class EmbeddingIndex:
     planes), built once and extended by ``add``.  A row's image depends on the row alone, so an index built by several
     ``add`` calls answers bit for bit like one built at once.
 
+    Rows leave by ``remove`` (a stable compaction: the survivors keep their order and move as bytes -- the fp32 rows, the
+    packed records, the groups, the ids).  After any mix of ``add`` and ``remove`` the index answers ``query``, ``radius``,
+    ``count_within`` and ``rank_of`` bit for bit like ``EmbeddingIndex(index.bank.clone(), metric, groups=index.groups)``
+    built at once.  ``ids`` int64 [len], ascending, is every row's permanent number -- the rows ever added before it,
+    never reused --, ``locate(ids)`` the current row of an id, and ``generation`` the number of ``remove`` calls that
+    removed at least one row: what a ``KnnGraph`` or a fit compares to see that rows have left.
+
     groups: one int64 group per bank row (an alert's object), or None.  An index with groups takes them with every
     ``add`` and can answer ``query(..., exclude_same_group=True)`` and ``query(..., one_per_group=True)``.
 
@@ -184,6 +192,9 @@ class EmbeddingIndex:
         self._bank = rows.new_empty((0, self.dim))
         self._packed = torch.empty(0, dtype=torch.uint8, device=self.device)
         self._groups = None if groups is None else torch.empty(0, dtype=torch.int64, device=self.device)
+        self._ids = torch.empty(0, dtype=torch.int64, device=self.device)
+        self._next_id = 0
+        self.generation = 0
         self.add(rows, groups=groups)
 
     def __len__(self) -> int:
@@ -198,6 +209,12 @@ class EmbeddingIndex:
     def groups(self) -> Optional[torch.Tensor]:
         """The rows' groups, int64 [len] (a view of the index's storage), or None for an index without groups."""
         return None if self._groups is None else self._groups[:self._n]
+
+    @property
+    def ids(self) -> torch.Tensor:
+        """The rows' permanent numbers, int64 [len], ascending (a view of the index's storage): a row's id is the
+        number of rows ever added before it, and is never reused."""
+        return self._ids[:self._n]
 
     def _record_bytes(self) -> int:
         return int(_lib.lib().btsbot_knn_bank_bytes(1, self.dim))
@@ -230,15 +247,84 @@ class EmbeddingIndex:
                     grp = torch.empty(cap, dtype=torch.int64, device=self.device)
                     grp[:self._n].copy_(self._groups[:self._n])
                     self._groups = grp
+                ids = torch.empty(cap, dtype=torch.int64, device=self.device)
+                ids[:self._n].copy_(self._ids[:self._n])
+                self._ids = ids
                 self._bank, self._packed, self._cap = bank, packed, cap
             new = self._bank[self._n:self._n + n]
             new.copy_(rows)
             if groups is not None:
                 self._groups[self._n:self._n + n].copy_(groups)
+            torch.arange(self._next_id, self._next_id + n, out=self._ids[self._n:self._n + n])
             _lib.check(L.btsbot_knn_pack_bank(_ptr(new), self._n, n, self.dim, self._metric_id, _ptr(self._packed),
                                               self._cap, _stream(self.device)), "btsbot_knn_pack_bank")
         self._n += n
+        self._next_id += n
         return self
+
+    def remove(self, which: torch.Tensor) -> torch.Tensor:
+        """Removes rows and returns ``kept`` int64 [len after], ascending: the OLD row number of every surviving row, so
+        that ``side = side[kept]`` keeps any per-row array of the caller aligned.  which: bool [len] (True: remove) or
+        int64 [m] row numbers (any order, repeats allowed).  A stable compaction out of place into fresh storage, which
+        is then swapped in: the survivors keep their order, their ids and their bytes (rows, packed records, groups).
+        Removing nothing returns ``arange(len)`` and leaves ``generation`` as it is.  One host read: the survivor count
+        and the range check of int64 rows.  A wrong dtype, device or mask length and a row out of range are a
+        ``ValueError``, and the index stays as it was."""
+        n, dev = self._n, self.device
+        if not isinstance(which, torch.Tensor) or which.dtype not in (torch.bool, torch.int64):
+            raise ValueError("which must be a bool [len] mask (True: remove) or int64 row numbers, got "
+                             f"{which.dtype if isinstance(which, torch.Tensor) else type(which).__name__}")
+        if which.device != dev:
+            raise ValueError(f"which is on {which.device}, the index on {dev}")
+        if which.dim() != 1 or (which.dtype == torch.bool and which.shape[0] != n):
+            raise ValueError(f"which must be a bool mask [{n}] or int64 [m], got {which.dtype} {tuple(which.shape)}")
+        if dev.type != "cuda":
+            raise RuntimeError(f"btsbot_amd.neighbors runs on the GPU; there is no CPU fallback (which is on {dev})")
+        with torch.cuda.device(dev):
+            if which.dtype == torch.bool:
+                keep = ~which
+                bad = torch.zeros((), dtype=torch.int64, device=dev)
+            else:
+                bad = ((which < 0) | (which >= n)).any().to(torch.int64)
+                keep = torch.ones(n + 1, dtype=torch.bool, device=dev)        # (slot n takes the rows out of range)
+                keep[torch.where((which < 0) | (which >= n), torch.full_like(which, n), which)] = False
+                keep = keep[:n]
+            at = torch.cumsum(keep, 0, dtype=torch.int64)
+            s, bad = torch.stack([at[-1] if n else bad.new_zeros(()), bad]).tolist()      # the one host read
+            if bad:
+                raise ValueError(f"which names a row outside 0..{n - 1}")
+            rows = torch.arange(n, device=dev)
+            if s == n:
+                return rows
+            # the survivors' old numbers without a second read: row a goes to slot at[a] - 1, a removed one to slot s
+            kept = torch.empty(s + 1, dtype=torch.int64, device=dev)
+            kept.scatter_(0, torch.where(keep, at - 1, torch.full_like(at, s)), rows)
+            kept = kept[:s].contiguous()
+            rec = self._record_bytes()
+            bank = self._bank[:n].index_select(0, kept)
+            packed = self._packed[:n * rec].view(n, rec).index_select(0, kept).view(-1)
+            ids = self._ids[:n].index_select(0, kept)
+            if self._groups is not None:
+                self._groups = self._groups[:n].index_select(0, kept)
+            self._bank, self._packed, self._ids, self._cap, self._n = bank, packed, ids, s, s
+        self.generation += 1
+        return kept
+
+    def locate(self, ids: torch.Tensor) -> torch.Tensor:
+        """int64, the shape of ``ids``: the current row of each permanent id, -1 where it is gone (or was never given).
+        ``torch.searchsorted`` on ``index.ids``; nothing is read from the host."""
+        if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64:
+            raise ValueError("ids must be an int64 torch.Tensor, got "
+                             f"{ids.dtype if isinstance(ids, torch.Tensor) else type(ids).__name__}")
+        if ids.device != self.device:
+            raise ValueError(f"ids is on {ids.device}, the index on {self.device}")
+        if self.device.type != "cuda":
+            raise RuntimeError(f"btsbot_amd.neighbors runs on the GPU; there is no CPU fallback (ids is on {ids.device})")
+        if self._n == 0:
+            return torch.full_like(ids, -1)
+        own = self.ids
+        pos = torch.searchsorted(own, ids.contiguous()).clamp(max=self._n - 1)
+        return torch.where(own[pos] == ids, pos, torch.full_like(pos, -1))
 
     def _prelude(self, queries, k, splits, query_groups, exclude_same_group, one_per_group, self_offset, targets=None):
         """The common arguments of ``query``, ``radius`` and ``rank_of``, checked in their order: ``(flags, q, nq,
@@ -260,15 +346,25 @@ class EmbeddingIndex:
 
     def query(self, queries: torch.Tensor, k: int, *, query_groups: Optional[torch.Tensor] = None,
               exclude_same_group: bool = False, one_per_group: bool = False, splits: int = 0,
-              self_offset: int = -1) -> Tuple[torch.Tensor, torch.Tensor]:
+              self_offset: int = -1, self_rows: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """``idx`` int64 [Q, k] and ``dist`` float32 [Q, k] of each query row's ``k`` nearest rows of the index.
         splits: bank slices searched by separate workgroups (0: the library's choice; the answer does not depend on it).
         self_offset >= 0: query row i is row i + self_offset of the index and is not its own candidate.
+        self_rows: int64 [Q], query row i is row ``self_rows[i]`` of the index -- scattered rows, where ``self_offset``
+        masks a run -- and is not its own candidate: on an index without groups the search runs with the row numbers as
+        the groups of both sides (all 64 bits decide, so exactly the row itself is excluded); on an index with groups it
+        needs ``exclude_same_group=True``, under which the row's own group covers the row.  Not beside ``self_offset``.
         query_groups: int64 [Q], the query rows' groups.  exclude_same_group: no row of the query row's own group.
         one_per_group: at most one row per group, its nearest; the ``k`` nearest groups (``k <= 32``)."""
         _check_k(k, splits)
+        _check_self_rows(self_rows, _n_rows_or_none(queries), self_offset, self._groups is not None, exclude_same_group,
+                         self.device)
         flags, q, nq, query_groups, splits = self._prelude(queries, k, splits, query_groups, exclude_same_group,
                                                            one_per_group, self_offset)
+        bank_groups = self._groups
+        if self_rows is not None and self._groups is None:
+            flags, query_groups = _lib.KNN_EXCLUDE_SAME, self_rows.detach().contiguous()
+            bank_groups = torch.arange(self._n, device=self.device)
         idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         dist = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         if nq == 0:
@@ -284,7 +380,7 @@ class EmbeddingIndex:
             if flags == 0:
                 _lib.check(L.btsbot_knn_query(*args), "btsbot_knn_query")
             else:
-                _lib.check(L.btsbot_knn_query_grouped(*args, _ptr(query_groups), _ptr(self._groups), flags),
+                _lib.check(L.btsbot_knn_query_grouped(*args, _ptr(query_groups), _ptr(bank_groups), flags),
                            "btsbot_knn_query_grouped")
         return idx, dist
 
@@ -409,6 +505,36 @@ class EmbeddingIndex:
         """int64 [Q]: how many rows of the index lie within ``r`` of each query row -- exact, the ``indptr.diff()`` of
         ``radius`` with the same arguments (it goes through the lists; 0 is novelty, thousands a crowded region)."""
         return self.radius(queries, r, **kw)[0].diff()
+
+
+def _check_self_rows(self_rows, n_query, self_offset, has_groups: bool, exclude_same_group, device) -> None:
+    """ValueError for a ``self_rows`` that ``query`` cannot honour, before anything touches the device."""
+    if self_rows is None:
+        return
+    if not isinstance(self_rows, torch.Tensor) or self_rows.dtype != torch.int64:
+        raise ValueError("self_rows must be an int64 torch.Tensor [Q] of bank row numbers, got "
+                         f"{self_rows.dtype if isinstance(self_rows, torch.Tensor) else type(self_rows).__name__}")
+    if self_rows.dim() != 1 or (n_query is not None and self_rows.shape[0] != n_query):
+        raise ValueError(f"self_rows must hold one bank row per query row, [{n_query}], got {tuple(self_rows.shape)}")
+    if isinstance(self_offset, int) and self_offset >= 0:
+        raise ValueError("self_rows and self_offset >= 0 both say which bank row a query row is: give one")
+    if has_groups and exclude_same_group is not True:
+        raise ValueError("self_rows on an index with groups needs exclude_same_group=True (the row's own group then "
+                         "covers the row; the group switches have no way to mask one row and keep its group)")
+    if self_rows.device != device:
+        raise ValueError(f"self_rows is on {self_rows.device}, the index on {device}")
+
+
+def _stale_fit(index, n_fit: int, generation: int) -> Optional[str]:
+    """None, or why a fit of ``n_fit`` rows made at ``generation`` no longer describes ``index`` (the head of the
+    RuntimeError of ``NoveltyModel.score`` and ``ClusterModel.predict``)."""
+    if len(index) != n_fit:
+        return f"the index holds {len(index)} rows, the fit {n_fit}: a fit does not follow index.add"
+    now = getattr(index, "generation", 0)
+    if now != generation:
+        return (f"rows were removed from the index since the fit (generation {generation} -> {now}): a fit does not "
+                "follow index.remove")
+    return None
 
 
 SORTS = ("index", "distance")

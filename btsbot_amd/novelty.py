@@ -27,12 +27,14 @@ row, ``alert_utils.object_keys``) the fit leaves a row's own object out of its n
 does the same for new alerts of objects the archive knows.
 
 Fit and score read nothing from the host and are queued on the current stream; only ``threshold`` reads.  There is no CPU
-fallback.  A fit does NOT follow ``index.add`` by itself: ``refit()`` recomputes it for the rows the index holds now, and
-``score`` refuses an index that has grown since.
+fallback.  A fit does NOT follow ``index.add`` or ``index.remove`` by itself: ``refit()`` recomputes it for the rows the
+index holds now, and ``score`` refuses an index that has grown since, or that rows were removed from (it compares
+``index.generation``: after ``remove`` and ``add`` the lengths can coincide).
 
 Following the archive.  ``NoveltyModel(index, 20, keep_graph=True)`` keeps the neighbour graph of the fit
-(``model.graph``, a ``graph.KnnGraph``), and ``model.update()`` after ``index.add`` brings graph and
-fit to the rows the index holds now at the cost of the new rows: ``graph.update()`` and ``btsbot_lof_fit`` over all rows.
+(``model.graph``, a ``graph.KnnGraph``, DESIGN.md sections 4x and 4y), and ``model.update()`` after ``index.add`` and
+``index.remove`` brings graph and fit to the rows the index holds now at the cost of the new rows and of the rows whose list
+lost an entry: ``graph.update()`` and ``btsbot_lof_fit`` over all rows.
 ``update`` reads the host where ``radius`` does.  A graph kept elsewhere serves the same way:
 ``local_outlier_factor(None, k, knn=(g.idx, g.dist))`` and ``fuzzy_graph(*g.self_first())`` take it as it is.
 """
@@ -46,7 +48,7 @@ from . import _lib
 from .graph import KnnGraph
 from .mapindex import MapIndex
 from ._lib import ptr as _ptr, stream as _stream
-from .neighbors import GROUP_MODES, EmbeddingIndex, knn_graph
+from .neighbors import GROUP_MODES, EmbeddingIndex, _stale_fit, knn_graph
 
 __all__ = ["NoveltyModel", "local_outlier_factor", "kth_neighbor_distance"]
 
@@ -136,10 +138,10 @@ class NoveltyModel:
     group_mode: how the FIT treats the groups, as ``knn_graph`` (``"exclude"``: a row's neighbours are rows of other
     groups only).  ``kdist``, ``lrd`` and ``lof`` are float64 [N].
 
-    The fit does not follow ``index.add``; ``refit()`` recomputes it.  keep_graph=True (an ``EmbeddingIndex`` or rows;
+    The fit does not follow ``index.add`` or ``index.remove``; ``refit()`` recomputes it.  keep_graph=True (an ``EmbeddingIndex`` or rows;
     a ``MapIndex`` is a ``ValueError``): the model keeps ``graph``, the ``KnnGraph`` of ``n_neighbors`` columns the fit
     is computed on (``n_neighbors <= 32`` in the ``"distinct"`` modes); ``refit()`` rebuilds it, and ``update()`` follows
-    ``index.add`` at the cost of the new rows.  The default keeps nothing.  Calls on one model must be ordered by the
+    ``index.add`` and ``index.remove`` at the cost of the new and the damaged rows.  The default keeps nothing.  Calls on one model must be ordered by the
     caller's streams."""
 
     def __init__(self, bank_or_index: Union[torch.Tensor, EmbeddingIndex, MapIndex], n_neighbors: int = 20,
@@ -171,7 +173,7 @@ class NoveltyModel:
         self.graph = None
         if keep_graph:
             self.graph = KnnGraph(index, n_neighbors, self.metric, group_mode=group_mode)
-            self.kdist, self.lrd, self.lof = _fit(self.graph.idx, self.graph.dist)
+            self._set_fit(_fit(self.graph.idx, self.graph.dist))
         else:
             self.refit()
 
@@ -187,7 +189,7 @@ class NoveltyModel:
         graph is rebuilt."""
         if self.graph is not None:
             self.graph.rebuild()
-            self.kdist, self.lrd, self.lof = _fit(self.graph.idx, self.graph.dist)
+            self._set_fit(_fit(self.graph.idx, self.graph.dist))
             return self
         kw = {}
         if self.index.groups is not None:
@@ -195,11 +197,15 @@ class NoveltyModel:
             if not isinstance(self.index, MapIndex):
                 kw["one_per_group"] = "distinct" in self.group_mode
         idx, dist = self.index.query(self._rows(), self.n_neighbors, self_offset=0, **kw)
-        self.kdist, self.lrd, self.lof = _fit(idx, dist)
+        self._set_fit(_fit(idx, dist))
         return self
 
+    def _set_fit(self, fit) -> None:
+        self.kdist, self.lrd, self.lof = fit
+        self._generation = getattr(self.index, "generation", 0)
+
     def update(self, stats: Optional[dict] = None) -> "NoveltyModel":
-        """Follows ``index.add`` at the cost of the new rows (``keep_graph=True`` only): ``graph.update(stats)``, then
+        """Follows ``index.add`` and ``index.remove`` at the cost of the new and the damaged rows (``keep_graph=True`` only): ``graph.update(stats)``, then
         ``btsbot_lof_fit`` over all rows -- the fit is three launches whatever the archive holds, so it is not made
         incremental.  ``kdist``, ``lrd`` and ``lof`` are those of the updated graph, whose promise is ``KnnGraph``'s.
         Reads the host where ``radius`` does."""
@@ -207,7 +213,7 @@ class NoveltyModel:
             raise RuntimeError("update() needs the model's neighbour graph: build the model with keep_graph=True (or "
                                "call refit(), which searches every pair again)")
         self.graph.update(stats)
-        self.kdist, self.lrd, self.lof = _fit(self.graph.idx, self.graph.dist)
+        self._set_fit(_fit(self.graph.idx, self.graph.dist))
         return self
 
     def score(self, queries: torch.Tensor, *, query_groups: Optional[torch.Tensor] = None,
@@ -217,9 +223,9 @@ class NoveltyModel:
         identical to a bank row finds it at distance 0.  query_groups / exclude_same_group / one_per_group: as
         ``EmbeddingIndex.query`` -- leave out the rows of the query's own object.  NaN for a non-finite row and for a row
         without an eligible neighbour.  Nothing is read from the host."""
-        if len(self.index) != len(self):
-            raise RuntimeError(f"the index holds {len(self.index)} rows, the fit {len(self)}: a fit does not follow "
-                               "index.add -- call refit()" + (" or update()" if self.graph is not None else
+        stale = _stale_fit(self.index, len(self), self._generation)
+        if stale is not None:
+            raise RuntimeError(stale + " -- call refit()" + (" or update()" if self.graph is not None else
                                                              " (a model built with keep_graph=True has update())"))
         kw = dict(query_groups=query_groups, exclude_same_group=exclude_same_group)
         if isinstance(self.index, MapIndex):

@@ -1171,7 +1171,8 @@ int btsbot_lof_fit(const int64_t* idx, const float* dist, int64_t n, int k, doub
 int btsbot_lof_score(const int64_t* idx, const float* dist, int64_t q, int k, const double* bank_kdist,
                      const double* bank_lrd, int64_t n, double* lrd, double* lof, void* stream);
 
-/* ---- a kNN graph kept current under add: the merge of offers into the lists (csrc/knn_graph.hip) ---- */
+/* ---- a kNN graph kept current under add and remove: the merge of offers into the lists and their compaction
+ *      (csrc/knn_graph.hip) ---- */
 
 /* Flags of btsbot_knn_graph_merge. */
 enum btsbot_knn_graph_flags { BTSBOT_KNN_GRAPH_DISTINCT = 1 };
@@ -1201,6 +1202,32 @@ int btsbot_knn_graph_merge(int64_t* idx, float* dist, int64_t stride, int k, int
                            const int64_t* offer_idx, const float* offer_dist, int64_t n_offers, const int64_t* groups,
                            int64_t n_groups, int flags, const int64_t* rows, int64_t n_rows, uint8_t* changed_rows,
                            int32_t* changed_count, void* stream);
+
+/* Compacts the neighbour lists of n_old rows after rows were removed, out of place.  idx / dist: the lists
+ * as above, row a at [a * stride .. a * stride + k).  new_of_old int64 [n_old]: the row's new number, -1 (any negative)
+ * for a removed row; ascending over the survivors and < n_new.  An old row a with j = new_of_old[a] in [0, n_new) has its
+ * list written to out_idx / out_dist at [j * out_stride .. j * out_stride + k): its present entries whose row survived,
+ * renumbered through new_of_old, in their order (new_of_old is monotone, so (dist, index) order is kept), with the dist
+ * bits they had, then a -1 / +inf tail.  An entry outside [0, n_old) is never a subscript: it is dropped and counts as
+ * removed.  A row whose dist[0] is NaN (a non-finite row) is copied as it stands.  damaged uint8 [n_new] is written for
+ * every surviving row: 1 iff at least one present entry was dropped and either the list was full (idx[k - 1] >= 0) or
+ * BTSBOT_KNN_GRAPH_DISTINCT is set -- the rows whose list has to be searched again; a list with a free slot held every
+ * eligible row, so what is left of it is complete (not so under DISTINCT, where a further row of a dropped entry's group
+ * may surface); 0 for a NaN row.  counts: NULL, or int32 [2] to which the damaged rows and the entries dropped (of all
+ * surviving rows but the NaN ones) are ADDED, at most two atomics per wave.
+ *
+ * One launch.  W lanes hold a row, lane c its column c, W = 16, 32 or 64 the smallest that holds k; the row is read whole
+ * before anything is written, one ballot gives every surviving entry its new column, no atomic touches a list, and the
+ * lanes of a removed row leave after their one read of new_of_old.  Rows of the output that no survivor maps to are not
+ * written.  Queued on `stream`; nothing allocates, synchronises or copies to the host.
+ *
+ * BTSBOT_ERR_INVALID_ARG with a message, before any HIP call, for flags other than 0 / BTSBOT_KNN_GRAPH_DISTINCT, k
+ * outside 1..64 (1..32 under DISTINCT), stride < k or out_stride < k, n_old or n_new outside 0..2^31 - 1, n_new > n_old, a
+ * NULL or misaligned pointer (but counts), and an output array that overlaps an input array.  n_old = 0 or n_new = 0
+ * succeed without a launch. */
+int btsbot_knn_graph_compact(const int64_t* idx, const float* dist, int64_t stride, int k, int64_t n_old,
+                             const int64_t* new_of_old, int64_t* out_idx, float* out_dist, int64_t out_stride,
+                             int64_t n_new, int flags, uint8_t* damaged, int32_t* counts, void* stream);
 
 /* ---- HDBSCAN: the mutual-reachability spanning tree and its hierarchy (csrc/mr_offer.hip, csrc/mst.hip,
  *      csrc/hdbscan_tree.hip) ---- */

@@ -43,6 +43,10 @@ SYMBOLS = [
     "btsbot_op_cnt_colsum_f32",
     "btsbot_op_cnt_mlp_bwd_planes", "btsbot_op_cnt_mlp_bwd_slices", "btsbot_op_cnt_s2mlp_bwd_rows", "btsbot_op_cnt_mlp_bwd",
     "btsbot_op_cnt_s2mlp_bwd", "btsbot_op_cnt_fused_mlp", "btsbot_op_cnt_fc2_grads",
+    "btsbot_op_head16_supported", "btsbot_op_head",
+    "btsbot_op_ht_lin_is_wide", "btsbot_op_ht_lin_fwd", "btsbot_op_ht_act_bwd", "btsbot_op_ht_lin_bwd_in",
+    "btsbot_op_ht_lin_bwd_w_kind", "btsbot_op_ht_lin_bwd_w", "btsbot_op_ht_bn_fwd", "btsbot_op_ht_bn_bwd",
+    "btsbot_op_ht_feat_rows", "btsbot_op_ht_logits", "btsbot_op_ht_copy_cols",
     "btsbot_reserve_train", "btsbot_forward_train", "btsbot_backward", "btsbot_debug_stamps",
     "btsbot_grad_buckets", "btsbot_wait_grad_bucket", "btsbot_allreduce_grads", "btsbot_use_workspace", "btsbot_set_option",
     "btsbot_augment", "btsbot_eval_metrics", "btsbot_prep_triplets", "btsbot_alert_features",
@@ -230,6 +234,22 @@ def lib() -> C.CDLL:
                        ("mlp_bwd", [i32, i32] + [vp] * 10 + [i32, i32, vp]), ("s2mlp_bwd", [i32, i32] + [vp] * 6 + [i32, vp]),
                        ("fused_mlp", [i32, i32] + [vp] * 8 + [i32, vp]), ("fc2_grads", [vp] * 8 + [i32, i32, vp])):
         fn = getattr(L, "btsbot_op_cnt_" + name)
+        fn.restype = i32
+        fn.argtypes = args
+    L.btsbot_op_head16_supported.restype = i32
+    L.btsbot_op_head16_supported.argtypes = [i32] * 6 + [C.POINTER(i32)]
+    L.btsbot_op_head.restype = i32
+    L.btsbot_op_head.argtypes = ([i32, vp, i32, vp, vp, vp, i32] + [vp] * 6 + [i32, vp, vp, i32, i32, i32, C.POINTER(i32),
+                                 C.POINTER(vp), C.POINTER(vp), i32] + [vp] * 4 + [i32, vp])
+    for name, args in (("lin_is_wide", [i32] * 4),
+                       ("lin_fwd", [vp, i32, vp, vp, vp, vp] + [i32] * 5 + [vp, f32, vp]),
+                       ("act_bwd", [vp, i32, vp, vp, i32, i32, i32, vp, f32, vp]),
+                       ("lin_bwd_in", [vp, vp, vp] + [i32] * 4 + [vp]), ("lin_bwd_w_kind", [vp, i32, vp, i32, i32]),
+                       ("lin_bwd_w", [vp, vp, i32, vp, vp, i32, i32, i32, vp]),
+                       ("bn_fwd", [vp, i32, i32] + [vp] * 8), ("bn_bwd", [vp, i32, i32] + [vp] * 6),
+                       ("feat_rows", [vp, i32, vp, vp, vp, i32, i32, vp]), ("logits", [vp, vp, vp, i32, vp]),
+                       ("copy_cols", [vp, i32, vp, i32, i32, i32, vp])):
+        fn = getattr(L, "btsbot_op_ht_" + name)
         fn.restype = i32
         fn.argtypes = args
     L.btsbot_debug_stamps.restype = i32

@@ -237,6 +237,12 @@ int launch_head(const HeadArgs& a, hipStream_t st) {
     btsbot_set_error("head: feature width %d above 768", a.feat_dim);
     return BTSBOT_ERR_INVALID_ARG;
   }
+  int widest = a.f1 > a.f2 ? a.f1 : a.f2;   // (f2 lands in z, so maxw does not see it)
+  widest = widest > maxw ? widest : maxw;
+  if (widest > PARTN) {   // dense_t's `part` holds PARTN rows
+    btsbot_set_error("head: layer width %d above %d", widest, PARTN);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
   if (lds > 150 * 1024) {
     btsbot_set_error("head: layer widths too large for one workgroup (%zu bytes of LDS)", lds);
     return BTSBOT_ERR_INVALID_ARG;

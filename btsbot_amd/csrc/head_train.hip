@@ -209,20 +209,6 @@ __global__ __launch_bounds__(256) void lin_bwd_w4_kernel(const float* __restrict
   }
 }
 
-static int launch_lin_bwd_w(const float* dpre, const float* in, int ldi, float* dw, float* db, int M, int N, int K,
-                            hipStream_t st) {
-  const bool vec = K % 4 == 0 && ldi % 4 == 0 && (((uintptr_t)in | (uintptr_t)dw) & 15) == 0;
-  if (vec)
-    hipLaunchKernelGGL(lin_bwd_w4_kernel, dim3(N * ((K + 63) / 64)), dim3(256), 0, st, dpre, in, ldi, dw, db, M, N, K);
-  else if ((long)N * (K + 1) <= 8192)
-    hipLaunchKernelGGL((lin_bwd_w_kernel<4, 64>), dim3(((long)N * (K + 1) + 3) / 4), dim3(256), 0, st, dpre, in, ldi,
-                       dw, db, M, N, K);
-  else
-    hipLaunchKernelGGL((lin_bwd_w_kernel<16, 16>), dim3(((long)N * (K + 1) + 15) / 16), dim3(256), 0, st, dpre, in,
-                       ldi, dw, db, M, N, K);
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
-}
 
 // BatchNorm1d, training: one workgroup per feature j.  Biased variance normalises, unbiased
 // variance goes into running_var (torch semantics), momentum 0.1.
@@ -346,6 +332,116 @@ inline dim3 g1(long n) { return dim3((unsigned)((n + 255) / 256)); }
 }  // namespace
 
 // ---------------------------------------------------------------------------------------
+// One launcher per kernel (launchers.h): the schedules below and the op entry points (head_ops.hip) share the grids.
+// ---------------------------------------------------------------------------------------
+bool head_train_lin_is_wide(int M, int N, int K, int ldi) { return wide_layer(M, N, K, ldi); }
+
+int launch_ht_lin_fwd(const float* in, int ldi, const float* wt, const float* bias, float* pre, float* outa, int ldo, int M,
+                      int N, int K, int act, const uint8_t* mask, float keep_scale, hipStream_t st) {
+  hipLaunchKernelGGL(lin_fwd_kernel, g1((long)M * N), dim3(256), 0, st, in, ldi, wt, bias, pre, outa, ldo, M, N, K, act, mask,
+                     keep_scale);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+int launch_ht_act_fwd(const float* pre, float* outa, int ldo, int M, int N, int act, const uint8_t* mask, float keep_scale,
+                      hipStream_t st) {
+  hipLaunchKernelGGL(act_fwd_kernel, g1((long)M * N), dim3(256), 0, st, pre, outa, ldo, M, N, act, mask, keep_scale);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+// A fusion layer's forward: the MFMA GEMM into `pre` + the activation kernel where wide_layer says so (w: the filter as
+// stored, [N][K]; pre must exist then), the per-output kernel otherwise (wt: the packed transpose [K][N]).
+int launch_ht_layer_fwd(const float* in, int ldi, const float* w, const float* wt, const float* bias, float* pre, float* outa,
+                        int ldo, int M, int N, int K, int act, const uint8_t* mask, float keep_scale, hipStream_t st) {
+  if (wide_layer(M, N, K, ldi)) {
+    TRY(launch_gemm(BTSBOT_F32, EPI_BIAS, in, w, bias, nullptr, nullptr, pre, M, N, K, st));
+    return launch_ht_act_fwd(pre, outa, ldo, M, N, act, mask, keep_scale, st);
+  }
+  return launch_ht_lin_fwd(in, ldi, wt, bias, pre, outa, ldo, M, N, K, act, mask, keep_scale, st);
+}
+
+int launch_ht_act_bwd(const float* dout, int ldd, const float* pre, float* dpre, int M, int N, int act, const uint8_t* mask,
+                      float keep_scale, hipStream_t st) {
+  hipLaunchKernelGGL(act_bwd_kernel, g1((long)M * N), dim3(256), 0, st, dout, ldd, pre, dpre, M, N, act, mask, keep_scale);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+int launch_ht_lin_bwd_in(const float* dpre, const float* w, float* din, int ldi, int M, int N, int K, hipStream_t st) {
+  hipLaunchKernelGGL(lin_bwd_in_kernel, g1((long)M * K), dim3(256), 0, st, dpre, w, din, ldi, M, N, K);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+// A fusion layer's input gradient din [M][K] = dpre [M][N] . w [N][K]: the MFMA GEMM on the packed transpose wt [K][N]
+// where wide_layer says so, the per-output kernel on w otherwise.
+int launch_ht_layer_bwd_in(const float* dpre, const float* w, const float* wt, float* din, int M, int N, int K,
+                           hipStream_t st) {
+  if (wide_layer(M, K, N, N)) {   // din[m][k] = sum_n dout[m][n] Wt[k][n]
+    TRY(launch_gemm(BTSBOT_F32, EPI_PLAIN, dpre, wt, nullptr, nullptr, nullptr, din, M, K, N, st));
+    LAUNCH_CHECK();
+    return BTSBOT_OK;
+  }
+  return launch_ht_lin_bwd_in(dpre, w, din, K, M, N, K, st);
+}
+
+// 0: lin_bwd_w4_kernel, 1: lin_bwd_w_kernel<4, 64>, 2: lin_bwd_w_kernel<16, 16>
+int head_train_lin_bwd_w_kind(const float* in, int ldi, const float* dw, int N, int K) {
+  const bool vec = K % 4 == 0 && ldi % 4 == 0 && (((uintptr_t)in | (uintptr_t)dw) & 15) == 0;
+  return vec ? 0 : (long)N * (K + 1) <= 8192 ? 1 : 2;
+}
+
+int launch_ht_lin_bwd_w(const float* dpre, const float* in, int ldi, float* dw, float* db, int M, int N, int K,
+                        hipStream_t st) {
+  const int kind = head_train_lin_bwd_w_kind(in, ldi, dw, N, K);
+  if (kind == 0)
+    hipLaunchKernelGGL(lin_bwd_w4_kernel, dim3(N * ((K + 63) / 64)), dim3(256), 0, st, dpre, in, ldi, dw, db, M, N, K);
+  else if (kind == 1)
+    hipLaunchKernelGGL((lin_bwd_w_kernel<4, 64>), dim3(((long)N * (K + 1) + 3) / 4), dim3(256), 0, st, dpre, in, ldi,
+                       dw, db, M, N, K);
+  else
+    hipLaunchKernelGGL((lin_bwd_w_kernel<16, 16>), dim3(((long)N * (K + 1) + 15) / 16), dim3(256), 0, st, dpre, in,
+                       ldi, dw, db, M, N, K);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+int launch_ht_bn_fwd(const float* x, int M, int n, const float* w, const float* b, float* run_mean, float* run_var,
+                     float* xhat, float* out, float* rstd, hipStream_t st) {
+  hipLaunchKernelGGL(bn_train_fwd_kernel, dim3(n), dim3(256), 0, st, x, M, n, w, b, run_mean, run_var, xhat, out, rstd);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+int launch_ht_bn_bwd(const float* dy, int M, int n, const float* w, const float* xhat, const float* rstd, float* dw,
+                     float* db, hipStream_t st) {
+  hipLaunchKernelGGL(bn_train_bwd_kernel, dim3(n), dim3(256), 0, st, dy, M, n, w, xhat, rstd, dw, db);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+int launch_ht_feat_rows(const float* feat, int F, const float* hw, const float* hb, float* z, int ldz, int M,
+                        hipStream_t st) {
+  hipLaunchKernelGGL(feat_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, st, feat, F, hw, hb, z, ldz, M);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+int launch_ht_logits(const float* in, float* logits, float* scores, int M, hipStream_t st) {
+  hipLaunchKernelGGL(logits_kernel, g1(M), dim3(256), 0, st, in, logits, scores, M);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+int launch_ht_copy_cols(float* dst, int ldd, const float* src, int lds, int cols, int M, hipStream_t st) {
+  hipLaunchKernelGGL(copy_cols_kernel, g1((long)M * cols), dim3(256), 0, st, dst, ldd, src, lds, cols, M);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // cache layout (floats) for a batch of M alerts
 // ---------------------------------------------------------------------------------------
 // Row width of the three backward scratch buffers: the widest tensor any of them ever holds -- d(z) of the
@@ -416,22 +512,13 @@ int head_train_meta_forward(btsbot_ctx* h, float* cache, const float* meta, int 
   TrainPtrs p = carve(h, cache, M);
   const int F = h->has_image ? c.dims[3] : 0;
   const int zd = h->comb_dims[0];
-  hipLaunchKernelGGL(bn_train_fwd_kernel, dim3(c.n_meta), dim3(256), 0, st, meta, M, c.n_meta,
-                     m + h->bn_w, m + h->bn_b, master ? master + h->bn_rm : nullptr,
-                     master ? master + h->bn_rv : nullptr, p.xhat, p.x1, p.bn_rstd);
-  LAUNCH_CHECK();
+  TRY(launch_ht_bn_fwd(meta, M, c.n_meta, m + h->bn_w, m + h->bn_b, master ? master + h->bn_rm : nullptr,
+                       master ? master + h->bn_rv : nullptr, p.xhat, p.x1, p.bn_rstd, st));
   const float ks1 = c.meta_dropout < 1.f ? 1.f / (1.f - c.meta_dropout) : 0.f;
-  hipLaunchKernelGGL(lin_fwd_kernel, g1((long)M * c.meta_fc1), dim3(256), 0, st, p.x1, c.n_meta,
-                     IMG_F32(h, h->p_m1), m + h->m1_b, p.a1, p.h1,
-                     c.meta_fc1, M, c.meta_fc1, c.n_meta, h->act,
-                     c.meta_dropout > 0.f ? meta_mask : nullptr, ks1);
-  LAUNCH_CHECK();
-  hipLaunchKernelGGL(lin_fwd_kernel, g1((long)M * c.meta_fc2), dim3(256), 0, st, p.h1,
-                     c.meta_fc1, IMG_F32(h, h->p_m2), m + h->m2_b,
-                     p.a2, p.z + F, zd, M, c.meta_fc2, c.meta_fc1,
-                     h->meta_trailing_act ? h->act : ACT_NONE, nullptr, 1.f);
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
+  TRY(launch_ht_lin_fwd(p.x1, c.n_meta, IMG_F32(h, h->p_m1), m + h->m1_b, p.a1, p.h1, c.meta_fc1, M, c.meta_fc1, c.n_meta,
+                        h->act, c.meta_dropout > 0.f ? meta_mask : nullptr, ks1, st));
+  return launch_ht_lin_fwd(p.h1, c.meta_fc1, IMG_F32(h, h->p_m2), m + h->m2_b, p.a2, p.z + F, zd, M, c.meta_fc2, c.meta_fc1,
+                           h->meta_trailing_act ? h->act : ACT_NONE, nullptr, 1.f, st);
 }
 
 // Forward of the heads in training mode.  feat: [M][F] backbone features (already in the cache).
@@ -444,10 +531,8 @@ int head_train_forward(btsbot_ctx* h, float* cache, const float* meta, float* lo
   const int F = h->has_image ? c.dims[3] : 0;
   const int zd = h->comb_dims[0];
   if (h->has_image) {
-    hipLaunchKernelGGL(feat_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, st, p.feat, F,
-                       h->hn_w >= 0 ? m + h->hn_w : nullptr, h->hn_b >= 0 ? m + h->hn_b : nullptr,
-                       p.z, zd, M);
-    LAUNCH_CHECK();
+    TRY(launch_ht_feat_rows(p.feat, F, h->hn_w >= 0 ? m + h->hn_w : nullptr, h->hn_b >= 0 ? m + h->hn_b : nullptr, p.z, zd,
+                            M, st));
   }
   if (h->has_meta && !meta_done) TRY(head_train_meta_forward(h, cache, meta, M, meta_mask, master, st));
   const float* in = p.z;
@@ -458,24 +543,12 @@ int head_train_forward(btsbot_ctx* h, float* cache, const float* meta, float* lo
     const bool last = i + 1 == h->n_comb;
     // Dropout sits after the activation of the layer BEFORE the final Linear (architectures.py:162)
     const bool drop = !last && i + 2 == h->n_comb && c.comb_dropout > 0.f;
-    if (wide_layer(M, N, K, ldi)) {
-      TRY(launch_gemm(BTSBOT_F32, EPI_BIAS, in, m + h->comb_w[i], m + h->comb_b[i], nullptr, nullptr, p.pre[i], M, N,
-                          K, st));
-      hipLaunchKernelGGL(act_fwd_kernel, g1((long)M * N), dim3(256), 0, st, p.pre[i], p.actv[i], N, M, N,
-                         last ? ACT_NONE : h->act, drop ? comb_mask : nullptr, ksc);
-    } else {
-      hipLaunchKernelGGL(lin_fwd_kernel, g1((long)M * N), dim3(256), 0, st, in, ldi,
-                         IMG_F32(h, h->p_comb[i]), m + h->comb_b[i],
-                         p.pre[i], p.actv[i], N, M, N, K, last ? ACT_NONE : h->act,
-                         drop ? comb_mask : nullptr, ksc);
-    }
-    LAUNCH_CHECK();
+    TRY(launch_ht_layer_fwd(in, ldi, m + h->comb_w[i], IMG_F32(h, h->p_comb[i]), m + h->comb_b[i], p.pre[i], p.actv[i], N, M,
+                            N, K, last ? ACT_NONE : h->act, drop ? comb_mask : nullptr, ksc, st));
     in = p.actv[i];
     ldi = N;
   }
-  hipLaunchKernelGGL(logits_kernel, g1(M), dim3(256), 0, st, in, logits, scores, M);
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
+  return launch_ht_logits(in, logits, scores, M, st);
 }
 
 // Backward of the heads.  Writes d(loss)/d(param) for the fusion head (always) and the metadata
@@ -500,19 +573,10 @@ int head_train_backward(btsbot_ctx* h, float* cache, const float* dlogits, float
     const int N = h->comb_dims[i + 1], K = h->comb_dims[i];
     if (i == 0 && !want_dz) break;
     float* din = p.dbuf[i];
-    if (wide_layer(M, K, N, N)) {   // din[m][k] = sum_n dout[m][n] Wt[k][n]
-      TRY(launch_gemm(BTSBOT_F32, EPI_PLAIN, dout[i], IMG(h, h->p_comb[i]), nullptr, nullptr, nullptr, din, M, K,
-                          N, st));
-    } else {
-      hipLaunchKernelGGL(lin_bwd_in_kernel, g1((long)M * K), dim3(256), 0, st, dout[i], m + h->comb_w[i],
-                         din, K, M, N, K);
-    }
-    LAUNCH_CHECK();
+    TRY(launch_ht_layer_bwd_in(dout[i], m + h->comb_w[i], IMG_F32(h, h->p_comb[i]), din, M, N, K, st));
     if (i > 0) {   // through dropout + activation of layer i-1
       const bool drop = i + 1 == h->n_comb && c.comb_dropout > 0.f;
-      hipLaunchKernelGGL(act_bwd_kernel, g1((long)M * K), dim3(256), 0, st, din, K, p.pre[i - 1],
-                         din, M, K, h->act, drop ? comb_mask : nullptr, ksc);
-      LAUNCH_CHECK();
+      TRY(launch_ht_act_bwd(din, K, p.pre[i - 1], din, M, K, h->act, drop ? comb_mask : nullptr, ksc, st));
       dout[i - 1] = din;
     } else {
       dz = din;
@@ -522,10 +586,7 @@ int head_train_backward(btsbot_ctx* h, float* cache, const float* dlogits, float
   if (need_image && h->has_image)
     // d(z)[:, 0:F] is the gradient of the (head-normalised) image feature; pulled out of the concat layout
     // (the metadata backward below recycles d(z))
-  {
-    hipLaunchKernelGGL(copy_cols_kernel, g1((long)M * F), dim3(256), 0, st, dfeat, F, dz, zd, F, M);
-    LAUNCH_CHECK();
-  }
+    TRY(launch_ht_copy_cols(dfeat, F, dz, zd, F, M, st));
   hipStream_t sd = st;
   TRY(side_fork(h, st, &sd));
   if (need_image && h->has_image) {
@@ -538,32 +599,21 @@ int head_train_backward(btsbot_ctx* h, float* cache, const float* dlogits, float
     const int N = h->comb_dims[i + 1], K = h->comb_dims[i];
     const float* in = i == 0 ? p.z : p.actv[i - 1];
     const int ldi = i == 0 ? zd : K;
-    TRY(launch_lin_bwd_w(dout[i], in, ldi, grads + h->comb_w[i], grads + h->comb_b[i], M, N, K, sd));
+    TRY(launch_ht_lin_bwd_w(dout[i], in, ldi, grads + h->comb_w[i], grads + h->comb_b[i], M, N, K, sd));
   }
   if (need_meta && h->has_meta) {
     // the metadata features are columns F .. F+f2 of d(z) [M][zd]
     const float ks1 = c.meta_dropout < 1.f ? 1.f / (1.f - c.meta_dropout) : 0.f;
     float* da2 = p.dbuf[4];
-    hipLaunchKernelGGL(act_bwd_kernel, g1((long)M * c.meta_fc2), dim3(256), 0, sd, dz + F, zd,
-                       p.a2, da2, M, c.meta_fc2, h->meta_trailing_act ? h->act : ACT_NONE, nullptr,
-                       1.f);
-    LAUNCH_CHECK();
-    TRY(launch_lin_bwd_w(da2, p.h1, c.meta_fc1, grads + h->m2_w, grads + h->m2_b, M, c.meta_fc2, c.meta_fc1, sd));
+    TRY(launch_ht_act_bwd(dz + F, zd, p.a2, da2, M, c.meta_fc2, h->meta_trailing_act ? h->act : ACT_NONE, nullptr, 1.f, sd));
+    TRY(launch_ht_lin_bwd_w(da2, p.h1, c.meta_fc1, grads + h->m2_w, grads + h->m2_b, M, c.meta_fc2, c.meta_fc1, sd));
     float* dh1 = const_cast<float*>(dz);     // d(z) is dead once da2 exists
-    hipLaunchKernelGGL(lin_bwd_in_kernel, g1((long)M * c.meta_fc1), dim3(256), 0, sd, da2,
-                       m + h->m2_w, dh1, c.meta_fc1, M, c.meta_fc2, c.meta_fc1);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(act_bwd_kernel, g1((long)M * c.meta_fc1), dim3(256), 0, sd, dh1, c.meta_fc1,
-                       p.a1, dh1, M, c.meta_fc1, h->act, c.meta_dropout > 0.f ? meta_mask : nullptr,
-                       ks1);
-    LAUNCH_CHECK();
-    TRY(launch_lin_bwd_w(dh1, p.x1, c.n_meta, grads + h->m1_w, grads + h->m1_b, M, c.meta_fc1, c.n_meta, sd));
-    hipLaunchKernelGGL(lin_bwd_in_kernel, g1((long)M * c.n_meta), dim3(256), 0, sd, dh1,
-                       m + h->m1_w, da2, c.n_meta, M, c.meta_fc1, c.n_meta);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_train_bwd_kernel, dim3(c.n_meta), dim3(256), 0, sd, da2, M, c.n_meta,
-                       m + h->bn_w, p.xhat, p.bn_rstd, grads + h->bn_w, grads + h->bn_b);
-    LAUNCH_CHECK();
+    TRY(launch_ht_lin_bwd_in(da2, m + h->m2_w, dh1, c.meta_fc1, M, c.meta_fc2, c.meta_fc1, sd));
+    TRY(launch_ht_act_bwd(dh1, c.meta_fc1, p.a1, dh1, M, c.meta_fc1, h->act, c.meta_dropout > 0.f ? meta_mask : nullptr, ks1,
+                          sd));
+    TRY(launch_ht_lin_bwd_w(dh1, p.x1, c.n_meta, grads + h->m1_w, grads + h->m1_b, M, c.meta_fc1, c.n_meta, sd));
+    TRY(launch_ht_lin_bwd_in(dh1, m + h->m1_w, da2, c.n_meta, M, c.meta_fc1, c.n_meta, sd));
+    TRY(launch_ht_bn_bwd(da2, M, c.n_meta, m + h->bn_w, p.xhat, p.bn_rstd, grads + h->bn_w, grads + h->bn_b, sd));
   }
   return BTSBOT_OK;
 }

@@ -212,6 +212,41 @@ struct HeadArgs {
 };
 int launch_head(const HeadArgs& a, hipStream_t st);
 
+// ---- head_train.hip: the training heads' kernels (fp32), one launcher each; the schedules of head_train.hip and the op
+// entry points of head_ops.hip go through these and nothing else
+// pre [M][N] (may be nullptr) = bias + in [M][ldi] . wt [K][N];  outa [M][ldo] = dropout(act(pre)), mask [M][N] or nullptr
+int launch_ht_lin_fwd(const float* in, int ldi, const float* wt, const float* bias, float* pre, float* outa, int ldo, int M,
+                      int N, int K, int act, const uint8_t* mask, float keep_scale, hipStream_t st);
+int launch_ht_act_fwd(const float* pre, float* outa, int ldo, int M, int N, int act, const uint8_t* mask, float keep_scale,
+                      hipStream_t st);
+// a fusion layer's forward: head_train_lin_is_wide(M, N, K, ldi) ? launch_gemm on w [N][K] into pre (which must exist) +
+// launch_ht_act_fwd : launch_ht_lin_fwd on wt [K][N]
+bool head_train_lin_is_wide(int M, int N, int K, int ldi);
+int launch_ht_layer_fwd(const float* in, int ldi, const float* w, const float* wt, const float* bias, float* pre, float* outa,
+                        int ldo, int M, int N, int K, int act, const uint8_t* mask, float keep_scale, hipStream_t st);
+// dpre [M][N] = dout [M][ldd] * act'(pre) * mask * keep_scale   (in place allowed)
+int launch_ht_act_bwd(const float* dout, int ldd, const float* pre, float* dpre, int M, int N, int act, const uint8_t* mask,
+                      float keep_scale, hipStream_t st);
+// din [M][ldi] (columns 0 .. K) = dpre [M][N] . w [N][K]
+int launch_ht_lin_bwd_in(const float* dpre, const float* w, float* din, int ldi, int M, int N, int K, hipStream_t st);
+// a fusion layer's input gradient, din [M][K]: head_train_lin_is_wide(M, K, N, N) ? launch_gemm on wt [K][N] : the above
+int launch_ht_layer_bwd_in(const float* dpre, const float* w, const float* wt, float* din, int M, int N, int K,
+                           hipStream_t st);
+// dw [N][K] = dpre^T in, db [N] = colsum(dpre) (written); which kernel: 0 lin_bwd_w4, 1 lin_bwd_w<4, 64>, 2 lin_bwd_w<16, 16>
+int head_train_lin_bwd_w_kind(const float* in, int ldi, const float* dw, int N, int K);
+int launch_ht_lin_bwd_w(const float* dpre, const float* in, int ldi, float* dw, float* db, int M, int N, int K,
+                        hipStream_t st);
+// BatchNorm1d on batch statistics over x [M][n]; run_mean / run_var (nullptr: none) updated with momentum 0.1
+int launch_ht_bn_fwd(const float* x, int M, int n, const float* w, const float* b, float* run_mean, float* run_var,
+                     float* xhat, float* out, float* rstd, hipStream_t st);
+int launch_ht_bn_bwd(const float* dy, int M, int n, const float* w, const float* xhat, const float* rstd, float* dw,
+                     float* db, hipStream_t st);
+// z [M][ldz] (columns 0 .. F) = feat [M][F], through the head LayerNorm where hw != nullptr
+int launch_ht_feat_rows(const float* feat, int F, const float* hw, const float* hb, float* z, int ldz, int M,
+                        hipStream_t st);
+int launch_ht_logits(const float* in, float* logits, float* scores, int M, hipStream_t st);   // scores may be nullptr
+int launch_ht_copy_cols(float* dst, int ldd, const float* src, int lds, int cols, int M, hipStream_t st);
+
 // ---- wgrad.hip
 // slice reduction of a filter-gradient GEMM (wgrad.hip), described so that two of them can share a launch
 struct WgradReduceJob {

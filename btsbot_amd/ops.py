@@ -648,3 +648,170 @@ def cnt_fc2_grads(G, S, w2, b2, gamma, dW2, db2, dgamma):
     _f32t(db2, (Cc,)), _f32t(dgamma, (Cc,))
     _cnt("fc2_grads", G, _p(G), _p(S), _p(w2), _p(b2), _p(gamma), _p(dW2), _p(db2), _p(dgamma), Cc, H)
     return dW2, db2, dgamma
+
+
+# ---- the classifier heads on given rows (btsbot_op_head*, btsbot_op_ht_*, head_ops.hip).  Parameters are fp32 in
+# state-dict layout.  Row tensors may be views with a row stride (ld) wider than their width; every output is the
+# caller's tensor.
+_ACT = {"none": 0, "gelu": 1, "relu": 2}
+
+
+def _rows(t, width=None):
+    """(M, width, ld) of an fp32 row tensor / view with unit column stride."""
+    assert t.dtype == torch.float32 and t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1), (t.dtype, t.shape, t.stride())
+    assert width is None or t.shape[1] == width, (tuple(t.shape), width)
+    return t.shape[0], t.shape[1], (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
+
+
+def _ht(name, t, *args):
+    with torch.cuda.device(t.device):
+        return _lib.check(getattr(_lib.lib(), "btsbot_op_ht_" + name)(*args, _stream(t)), "btsbot_op_ht_" + name)
+
+
+def _head_dims(dims):
+    return (C.c_int * len(dims))(*[int(d) for d in dims])
+
+
+def head16_supported(precision, feat_dim, n_meta, f1, f2, dims):
+    """head16.hip's own predicate for these widths (dims: the fusion MLP's widths, input first)."""
+    return bool(_lib.lib().btsbot_op_head16_supported(_lib.PRECISION[precision], feat_dim, n_meta, f1, f2, len(dims) - 1,
+                                                      _head_dims(dims)))
+
+
+def head(precision, logits, feat=None, hn=None, meta=None, bn=None, m1=None, m2=None, meta_trailing_act=False, comb=(),
+         act="gelu", scores=None, features=None, hidden=None):
+    """The whole inference head: precision 'f32' (head.hip) or 'bf16' / 'f16' (head16.hip; widths it has no kernel for
+    raise, nothing is written).  feat [B, F]; hn = (weight, bias) of the head LayerNorm; meta [B, n_meta] with bn =
+    (weight, bias, running_mean, running_var), m1 = (weight [f1, n_meta], bias), m2 = (weight [f2, f1], bias); comb =
+    ((weight, bias), ...) the fusion Linears, the last one [1, .].  logits [B] = ; scores [B], features [B * (F + f2)],
+    hidden [B * comb[-1].in] = where given."""
+    B = logits.numel()
+    F = feat.shape[1] if feat is not None else 0
+    n_meta = meta.shape[1] if meta is not None else 0
+    f1 = m1[0].shape[0] if meta is not None else 0
+    f2 = m2[0].shape[0] if meta is not None else 0
+    for t in (feat, meta) + tuple(hn or ()) + tuple(bn or ()) + tuple(m1 or ()) + tuple(m2 or ()) + tuple(x for l in comb for x in l):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    if feat is not None:
+        assert feat.shape[0] == B
+    if meta is not None:
+        assert meta.shape[0] == B and m1[0].shape == (f1, n_meta) and m2[0].shape == (f2, f1) and all(t.shape == (n_meta,) for t in bn)
+    dims = [comb[0][0].shape[1]] + [w.shape[0] for w, _ in comb]
+    for i, (w, b) in enumerate(comb):
+        assert w.shape == (dims[i + 1], dims[i]) and b.shape == (dims[i + 1],)
+    for t, n in ((logits, B), (scores, B), (features, B * dims[0]), (hidden, B * dims[-2])):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n), n
+    vp = C.c_void_p
+    cw = (vp * 3)(*[w.data_ptr() for w, _ in comb])
+    cb = (vp * 3)(*[b.data_ptr() for _, b in comb])
+    hn = hn or (None, None)
+    bn = bn or (None,) * 4
+    m1 = m1 or (None, None)
+    m2 = m2 or (None, None)
+    with torch.cuda.device(logits.device):
+        _lib.check(_lib.lib().btsbot_op_head(
+            _lib.PRECISION[precision], _p(feat), F, _p(hn[0]), _p(hn[1]), _p(meta), n_meta, _p(bn[0]), _p(bn[1]), _p(bn[2]),
+            _p(bn[3]), _p(m1[0]), _p(m1[1]), f1, _p(m2[0]), _p(m2[1]), f2, int(bool(meta_trailing_act)), len(comb),
+            _head_dims(dims), cw, cb, _ACT[act], _p(logits), _p(scores), _p(features), _p(hidden), B, _stream(logits)),
+            "btsbot_op_head")
+    return logits
+
+
+def ht_lin_is_wide(M, N, K, ldi):
+    """Whether a training fusion layer of this shape goes through the MFMA GEMM (head_train.hip's own decision)."""
+    return bool(_lib.check(_lib.lib().btsbot_op_ht_lin_is_wide(M, N, K, ldi), "btsbot_op_ht_lin_is_wide"))
+
+
+def ht_lin_fwd(x, w, bias, outa, pre=None, act="none", mask=None, keep_scale=1.0):
+    """x [M, K] (ld), w [N, K], bias [N]; pre [M, N] = bias + x w^T where given; outa [M, N] (ld) = dropout(act(pre))."""
+    M, K, ldi = _rows(x)
+    N = w.shape[0]
+    _f32t(w, (N, K)), _f32t(bias, (N,))
+    _, _, ldo = _rows(outa, N)
+    assert outa.shape[0] == M and (pre is None or _f32t(pre, (M, N)) is pre)
+    assert mask is None or (mask.dtype == torch.uint8 and mask.is_contiguous() and tuple(mask.shape) == (M, N))
+    _ht("lin_fwd", x, _p(x), ldi, _p(w), _p(bias), _p(pre), _p(outa), ldo, M, N, K, _ACT[act], _p(mask), float(keep_scale))
+    return outa
+
+
+def ht_act_bwd(dout, pre, dpre, act="none", mask=None, keep_scale=1.0):
+    """dpre [M, N] = dout [M, N] (ld) * act'(pre [M, N]) * mask * keep_scale; dpre may share dout's memory."""
+    M, N, ldd = _rows(dout)
+    _f32t(pre, (M, N)), _f32t(dpre, (M, N))
+    assert mask is None or (mask.dtype == torch.uint8 and mask.is_contiguous() and tuple(mask.shape) == (M, N))
+    _ht("act_bwd", pre, _p(dout), ldd, _p(pre), _p(dpre), M, N, _ACT[act], _p(mask), float(keep_scale))
+    return dpre
+
+
+def ht_lin_bwd_in(dpre, w, din):
+    """din [M, K] (ld) = dpre [M, N] w [N, K]."""
+    M, N = dpre.shape
+    K = w.shape[1]
+    _f32t(dpre), _f32t(w, (N, K))
+    _, _, ldi = _rows(din, K)
+    assert din.shape[0] == M
+    _ht("lin_bwd_in", dpre, _p(dpre), _p(w), _p(din), ldi, M, N, K)
+    return din
+
+
+def ht_lin_bwd_w_kind(x, dw):
+    """Which kernel ht_lin_bwd_w(., x, dw, .) takes: 0 lin_bwd_w4, 1 lin_bwd_w<4, 64>, 2 lin_bwd_w<16, 16>."""
+    _, K, ldi = _rows(x)
+    return _lib.check(_lib.lib().btsbot_op_ht_lin_bwd_w_kind(_p(x), ldi, _p(dw), dw.shape[0], K), "btsbot_op_ht_lin_bwd_w_kind")
+
+
+def ht_lin_bwd_w(dpre, x, dw, db):
+    """dw [N, K] = dpre [M, N]^T x [M, K] (ld); db [N] = colsum(dpre)."""
+    M, N = dpre.shape
+    _, K, ldi = _rows(x)
+    assert x.shape[0] == M
+    _f32t(dpre), _f32t(dw, (N, K)), _f32t(db, (N,))
+    _ht("lin_bwd_w", dpre, _p(dpre), _p(x), ldi, _p(dw), _p(db), M, N, K)
+    return dw, db
+
+
+def ht_bn_fwd(x, w, b, xhat, out, rstd, run_mean=None, run_var=None):
+    """BatchNorm1d on batch statistics: x, xhat, out [M, n]; w, b, rstd, run_mean, run_var [n]."""
+    M, n = x.shape
+    _f32t(x), _f32t(w, (n,)), _f32t(b, (n,)), _f32t(xhat, (M, n)), _f32t(out, (M, n)), _f32t(rstd, (n,))
+    for t in (run_mean, run_var):
+        assert t is None or _f32t(t, (n,)) is t
+    _ht("bn_fwd", x, _p(x), M, n, _p(w), _p(b), _p(run_mean), _p(run_var), _p(xhat), _p(out), _p(rstd))
+    return xhat, out, rstd
+
+
+def ht_bn_bwd(dy, w, xhat, rstd, dw, db):
+    """dw [n] = sum dy xhat; db [n] = sum dy."""
+    M, n = dy.shape
+    _f32t(dy), _f32t(w, (n,)), _f32t(xhat, (M, n)), _f32t(rstd, (n,)), _f32t(dw, (n,)), _f32t(db, (n,))
+    _ht("bn_bwd", dy, _p(dy), M, n, _p(w), _p(xhat), _p(rstd), _p(dw), _p(db))
+    return dw, db
+
+
+def ht_feat_rows(feat, z, hn=None):
+    """z [M, F] (ld) = feat [M, F], through LayerNorm(eps 1e-6) with hn = (weight, bias) where given."""
+    M, F = feat.shape
+    _f32t(feat)
+    _, _, ldz = _rows(z, F)
+    assert z.shape[0] == M
+    hn = hn or (None, None)
+    _ht("feat_rows", feat, _p(feat), F, _p(hn[0]), _p(hn[1]), _p(z), ldz, M)
+    return z
+
+
+def ht_logits(x, logits, scores=None):
+    """logits [M] = x [M]; scores [M] = sigmoid(x) where given."""
+    M = x.numel()
+    _f32t(x), _f32t(logits, numel=M)
+    assert scores is None or _f32t(scores, numel=M) is scores
+    _ht("logits", x, _p(x), _p(logits), _p(scores), M)
+    return logits
+
+
+def ht_copy_cols(dst, src):
+    """dst [M, cols] (ld) = src [M, cols] (ld)."""
+    M, cols, lds = _rows(src)
+    _, _, ldd = _rows(dst, cols)
+    assert dst.shape[0] == M
+    _ht("copy_cols", src, _p(dst), ldd, _p(src), lds, cols, M)
+    return dst

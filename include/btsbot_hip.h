@@ -580,6 +580,60 @@ int btsbot_op_cnt_fused_mlp(int prec, int C, const void* xn, const float* w1, co
 int btsbot_op_cnt_fc2_grads(float* G, float* S, const float* w2, const float* b2, const float* gamma, float* dW2, float* db2,
                             float* dgamma, int C, int H, void* stream);
 
+/* The classifier heads on given rows (head_ops.hip), for the per-kernel tests.  Parameters are fp32 in state-dict layout
+ * (a Linear's weight [out][in]); the operand images a handle keeps packed are built in the call's own scratch by the
+ * launchers the handle uses.  Same rules as above: arguments checked before anything is allocated or launched.
+ *
+ * btsbot_op_head: the whole inference head.  feat [B][feat_dim] or NULL (feat_dim 0); hn_w / hn_b [feat_dim] the head
+ * LayerNorm, or both NULL; meta [B][n_meta] or NULL (n_meta 0) with the BatchNorm1d four [n_meta], m1_w [f1][n_meta],
+ * m1_b [f1], m2_w [f2][f1], m2_b [f2]; meta_trailing_act: the activation behind the second metadata Linear; the fusion
+ * MLP: n_layers <= 3, dims[n_layers + 1] (host; dims[0] = feat_dim + f2, dims[n_layers] = 1), comb_w[i] [dims[i+1]][dims[i]],
+ * comb_b[i] (host arrays of device pointers); act = 1 (GELU) or 2 (ReLU).
+ *   logits [B] (written); scores [B], features [B][dims[0]], hidden [B][dims[n_layers - 1]]: written, each may be NULL.
+ * prec BTSBOT_F32 runs head.hip's kernel, BTSBOT_BF16 / BTSBOT_F16 head16.hip's; widths head16 has no kernel for
+ * (btsbot_op_head16_supported() == 0) are BTSBOT_ERR_INVALID_ARG with the cause in the message and nothing written --
+ * never the fp32 kernel in its place. */
+int btsbot_op_head16_supported(int prec, int feat_dim, int n_meta, int f1, int f2, int n_layers, const int* dims);
+int btsbot_op_head(int prec, const float* feat, int feat_dim, const float* hn_w, const float* hn_b, const float* meta,
+                   int n_meta, const float* bn_w, const float* bn_b, const float* bn_rm, const float* bn_rv,
+                   const float* m1_w, const float* m1_b, int f1, const float* m2_w, const float* m2_b, int f2,
+                   int meta_trailing_act, int n_layers, const int* dims, const float* const* comb_w,
+                   const float* const* comb_b, int act, float* logits, float* scores, float* features, float* hidden, int B,
+                   void* stream);
+/* The training heads' kernels (head_train.hip, fp32) one launcher at a time.  act: 0 none, 1 GELU, 2 ReLU; mask [M][N]
+ * bytes (0: dropped) or NULL.
+ *   lin_fwd:    pre [M][N] (NULL: not kept) = bias + in [M][ldi] w [N][K]^T;  outa [M][ldo] = dropout(act(pre)) -- as a fusion
+ *               layer's forward runs it: the fp32 MFMA GEMM + activation kernel where btsbot_op_ht_lin_is_wide(M, N, K, ldi),
+ *               the per-output kernel otherwise
+ *   act_bwd:    dpre [M][N] = dout [M][ldd] * act'(pre) * mask * keep_scale      (dpre may be dout)
+ *   lin_bwd_in: din [M][ldi] (columns 0 .. K) = dpre [M][N] w [N][K]; ldi == K takes a fusion layer's decision,
+ *               btsbot_op_ht_lin_is_wide(M, K, N, N); ldi > K the per-output kernel
+ *   lin_bwd_w:  dw [N][K] = dpre^T in [M][ldi], db [N] = colsum(dpre) (written); btsbot_op_ht_lin_bwd_w_kind says which
+ *               kernel a call takes: 0 lin_bwd_w4, 1 lin_bwd_w<4, 64>, 2 lin_bwd_w<16, 16>
+ *   bn_fwd:     BatchNorm1d on the batch statistics of x [M][n]: xhat, out [M][n], rstd [n] written; run_mean / run_var
+ *               [n] updated (momentum 0.1, unbiased variance) or both NULL
+ *   bn_bwd:     dw [n] = sum dy xhat, db [n] = sum dy
+ *   feat_rows:  z [M][ldz] (columns 0 .. F) = feat [M][F], through LayerNorm (eps 1e-6) where hw / hb are given
+ *   logits:     logits [M] = in [M]; scores = sigmoid (NULL: not written)
+ *   copy_cols:  dst [M][ldd] (columns 0 .. cols) = src [M][lds] */
+int btsbot_op_ht_lin_is_wide(int M, int N, int K, int ldi);
+int btsbot_op_ht_lin_fwd(const float* in, int ldi, const float* w, const float* bias, float* pre, float* outa, int ldo, int M,
+                         int N, int K, int act, const uint8_t* mask, float keep_scale, void* stream);
+int btsbot_op_ht_act_bwd(const float* dout, int ldd, const float* pre, float* dpre, int M, int N, int act,
+                         const uint8_t* mask, float keep_scale, void* stream);
+int btsbot_op_ht_lin_bwd_in(const float* dpre, const float* w, float* din, int ldi, int M, int N, int K, void* stream);
+int btsbot_op_ht_lin_bwd_w_kind(const float* in, int ldi, const float* dw, int N, int K);
+int btsbot_op_ht_lin_bwd_w(const float* dpre, const float* in, int ldi, float* dw, float* db, int M, int N, int K,
+                           void* stream);
+int btsbot_op_ht_bn_fwd(const float* x, int M, int n, const float* w, const float* b, float* run_mean, float* run_var,
+                        float* xhat, float* out, float* rstd, void* stream);
+int btsbot_op_ht_bn_bwd(const float* dy, int M, int n, const float* w, const float* xhat, const float* rstd, float* dw,
+                        float* db, void* stream);
+int btsbot_op_ht_feat_rows(const float* feat, int F, const float* hw, const float* hb, float* z, int ldz, int M,
+                           void* stream);
+int btsbot_op_ht_logits(const float* in, float* logits, float* scores, int M, void* stream);
+int btsbot_op_ht_copy_cols(float* dst, int ldd, const float* src, int lds, int cols, int M, void* stream);
+
 /* Measurement aid with no reference counterpart (bench.py's roofline leg): when on, every kernel
  * launch of forward() is bracketed by two HIP events recorded on the launch stream;
  * profile_collect() waits for them and returns, per kernel family (profile_category_name), the

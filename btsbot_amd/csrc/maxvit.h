@@ -12,8 +12,9 @@ int maxvit_pack(btsbot_ctx* h, hipStream_t st);                          // mirr
 size_t maxvit_ws_bytes(const btsbot_ctx* h, int chunk);
 int maxvit_chunk(btsbot_ctx* h, const float* img, int nb, hipStream_t st, float** feat_out);
 void maxvit_free(btsbot_ctx* h);
-// ---- training of the branch (maxvit_train.hip): BatchNorm2d batch statistics forward, backward of every layer; an
-//      fp32 engine whatever the handle's operand mode.  cache = h->bbcache, sized by maxvit_train_cache_bytes(B)
+// ---- training of the branch (maxvit_train.hip, the engine; its kernels: maxvit_train_kernels.hip, below): BatchNorm2d
+//      batch statistics forward, backward of every layer; an fp32 engine whatever the handle's operand mode.
+//      cache = h->bbcache, sized by maxvit_train_cache_bytes(B)
 size_t maxvit_train_cache_bytes(const btsbot_ctx* h, int B);
 int maxvit_train_forward(btsbot_ctx* h, const float* img, int B, float* master_arena, hipStream_t st, float** feat_out);
 int maxvit_train_backward(btsbot_ctx* h, const float* img, const float* dfeat, float* grads, int B, hipStream_t st);
@@ -122,3 +123,45 @@ int launch_mv_pack_dw(const float* w, const float* scale, float* out, int C, hip
 // relative position table [169][heads] -> bias_t [heads][49][49] (key-major, see launch_mv_attn)
 int launch_mv_pack_relbias(const float* table, float* out, int heads, hipStream_t st);
 int launch_mv_fill(float* out, float v, int n, hipStream_t st);
+
+// ---- training kernels (maxvit_train_kernels.hip): everything fp32, on plain pointers and sizes
+// row blocks (gridDim.y) of the BatchNorm reductions over M rows, and of dw3_bwd_w over npix output pixels
+unsigned bn_row_blocks(long M);
+unsigned dw3_bwd_w_row_blocks(long npix);
+// attention backward: workgroups per head for `units` (alert, partition) pairs
+long attn_bwd_groups_per_head(long units, int heads);
+// BatchNorm2d, training mode: batch statistics of x [M][C] into stat (mean | rstd), running statistics updated (or
+// nullptr), y = act(...);  sums0 / sums: two zeroed slots of 2C floats
+int launch_bn_train(const float* x, const float* w, const float* b, float* stat, float* sums0, float* sums, float* run_mean,
+                    float* run_var, float* y, long M, int C, int act, hipStream_t st);
+// ... and its backward: dy = gradient w.r.t. the layer's output (behind the activation), dx (+)= gradient w.r.t. x (dx may
+// be dy), dw / db += ;  sums: one zeroed slot
+int launch_bn_train_bwd(const float* x, const float* dy, const float* stat, const float* w, const float* b, float* sums,
+                        float* dx, float* dw, float* db, long M, int C, int act, int accumulate, hipStream_t st);
+// depthwise 3x3 on packed taps w9 [9][C] (launch_mv_pack_dw)
+int launch_dw3_fwd(const float* in, const float* w9, const float* bias, float* out, int B, int H, int C, int s, hipStream_t st);
+int launch_dw3_bwd_in(const float* dout, const float* w9, float* din, int B, int H, int C, int s, hipStream_t st);
+// filter / bias gradients: tap-major into the scratch g9 [10][C] (zeroed here), then added into the master layout dw [C][1][3][3]
+int launch_dw3_bwd_w(const float* in, const float* dout, float* g9, float* dw, float* dbias, int B, int H, int C, int s,
+                     hipStream_t st);
+// attention backward of one layer: dqkv written, dtable [169][heads] += ;  dbias: scratch [32][2401], the gradient of the
+// bias [heads <= 16][49][49] in its first half, the bias image bias_t in its second
+int launch_attn_bwd(const float* qkv, const float* table, const float* dout, float* dqkv, float* dbias, float* dtable, int B,
+                    int H, int C, int grid_mode, hipStream_t st);
+// y[b][p][c] = a[b][p][c] * g[b][c]   (y may be a)
+int launch_gate_mul(const float* a, const float* g, float* y, int B, int P, int C, hipStream_t st);
+// squeeze-excite of a2 [B][P][C]: pool = mean_p a2, r = silu(rpre = fc1 pool), gate = sigmoid(fc2 r), gated = a2 * gate
+int launch_se_fwd(const float* a2, const float* w1, const float* b1, const float* w2, const float* b2, float* pool, float* rpre,
+                  float* r, float* gate, float* gated, int B, int P, int C, int RD, hipStream_t st);
+// ... and its backward, in place: d [B][P][C] holds d(gated) and leaves as d(a2);  dg[b][c] = sum_p d(gated) a2,
+// d(a2) = d(gated) g + the pooled path;  dw1 / db1 / dw2 / db2 += ;  dgate, dpool, dgpre [B][C] and dr [B][RD]: scratch
+int launch_se_bwd(float* d, const float* a2, const float* pool, const float* rpre, const float* r, const float* gate,
+                  const float* w1, const float* w2, float* dw1, float* db1, float* dw2, float* db2, float* dgate, float* dr,
+                  float* dpool, float* dgpre, int B, int P, int C, int RD, hipStream_t st);
+int launch_bcast_set(float* d, const float* v, int B, int P, int C, float scale, hipStream_t st);
+int launch_avgpool2_bwd(const float* g, float* dx, int B, int H, int C, int accumulate, hipStream_t st);
+int launch_add(float* a, const float* b, long n4, hipStream_t st);   // a += b, n4 = count / 4
+int launch_gelu_fwd(const float* pre, float* out, long n4, hipStream_t st);
+int launch_gelu_bwd(const float* pre, float* d, long n4, hipStream_t st);
+int launch_col2im3(const float* dcol, float* din, int B, int H, int C, hipStream_t st);
+int launch_unpack_conv3_grad(const float* gp, float* g, int O, int C, int ldp, hipStream_t st);

@@ -1,4 +1,5 @@
-// Internal: parameter / operand tables of the MaxViT image branch (maxvit.hip builds them; maxvit_train.hip reads them).
+// Internal: parameter / operand tables of the MaxViT image branch (maxvit.hip builds them; the training engine,
+// maxvit_train.hip, reads them).
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -39,7 +40,8 @@ struct MaxVit {
   std::vector<MvBlock> blocks;
   // workspace offsets (bytes) for the current reservation
   size_t o_x, o_x2, o_a, o_b, o_c, o_d, o_e, o_gate, o_feat, o_part, o_sescr, o_wg;
-  // training, 16-bit modes: (fp32 GEMM input of the forward, its kept 16-bit copy) in call order (maxvit_train.hip)
+  // training, 16-bit modes: (fp32 GEMM input of the forward, its kept 16-bit copy) in call order; it outlives the forward
+  // for the backward, and only MvtOperands (maxvit_train.hip) touches it
   std::vector<std::pair<const float*, void*>> xkept;
 };
 

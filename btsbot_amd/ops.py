@@ -305,7 +305,7 @@ def mv_stem(img, conv1_w, bn_scale, bn_shift, conv2_w, precision="bf16", pooled=
     return out if pre is None else (out, xn)
 
 
-# ---- the MaxViT TRAINING kernels one at a time (btsbot_op_mvt_*, maxvit_train.hip): everything fp32; outputs given by
+# ---- the MaxViT TRAINING kernels one at a time (btsbot_op_mvt_*, maxvit_train_ops.hip): everything fp32; outputs given by
 # the caller are used as they are ("+=" ones are added to), the others are allocated here
 def _f32t(t, shape=None, numel=None):
     assert t.dtype == torch.float32 and t.is_contiguous(), "fp32 contiguous tensors"

@@ -440,7 +440,7 @@ int btsbot_op_mv_stem(int prec, const float* img, const float* conv1_w, const fl
                       const float* conv2_w, float* out, int pooled, void* xn, const float* pre_scale,
                       const float* pre_shift, int B, void* stream);
 
-/* The MaxViT TRAINING kernels (maxvit_train.hip) one at a time.  Everything is fp32; parameters are in the state-dict
+/* The MaxViT TRAINING kernels (maxvit_train_kernels.hip; these entry points: maxvit_train_ops.hip) one at a time.  Everything is fp32; parameters are in the state-dict
  * layout; activations are NHWC rows.  Every call runs the launcher the training engine itself runs (same kernels, same
  * grid arithmetic) on a stream-ordered scratch of its own.  "+=" outputs are added to, the others written.  What a
  * kernel cannot run (a null pointer, C not a multiple of 4, H not a multiple of 7 for attention or of the stride,

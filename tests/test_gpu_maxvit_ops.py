@@ -59,7 +59,7 @@ MBConv pieces:
 
 Out of scope: the elementwise kernels (mv_ln, mv_avgpool2, mv_gate, mv_scale_w, mv_bn_cast, mv_im2col3, mv_final,
 mv_resize_im2col) -- the fp32 stage taps of test_gpu_parity.py pin them at 1e-4 and they have no index map of their
-own.  The training kernels of maxvit_train.hip have test_gpu_maxvit_train_ops.py.
+own.  The training kernels of maxvit_train_kernels.hip have test_gpu_maxvit_train_ops.py.
 """
 import pytest
 import torch

@@ -1,4 +1,5 @@
-"""The MaxViT training kernels of maxvit_train.hip one at a time (btsbot_op_mvt_*) against plain float64 references.
+"""The MaxViT training kernels of maxvit_train_kernels.hip one at a time (btsbot_op_mvt_*, the entry points of
+maxvit_train_ops.hip) against plain float64 references.
 
 Conventions are test_gpu_gemm_paths.py's and test_gpu_maxvit_ops.py's: everything is fp32, references are float64 torch
 on the device (F.batch_norm(training=True), F.conv2d(groups=C), an explicit softmax attention over part_rows; backwards

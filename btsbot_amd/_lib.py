@@ -44,6 +44,8 @@ SYMBOLS = [
     "btsbot_op_cnt_mlp_bwd_planes", "btsbot_op_cnt_mlp_bwd_slices", "btsbot_op_cnt_s2mlp_bwd_rows", "btsbot_op_cnt_mlp_bwd",
     "btsbot_op_cnt_s2mlp_bwd", "btsbot_op_cnt_fused_mlp", "btsbot_op_cnt_fc2_grads",
     "btsbot_op_head16_supported", "btsbot_op_head",
+    "btsbot_op_cn_stage3_supported", "btsbot_op_cn_stage3_hfrag_bytes", "btsbot_op_cn_stage3", "btsbot_op_cn_pack_s3",
+    "btsbot_op_cn_fp8_scale",
     "btsbot_op_ht_lin_is_wide", "btsbot_op_ht_lin_fwd", "btsbot_op_ht_act_bwd", "btsbot_op_ht_lin_bwd_in",
     "btsbot_op_ht_lin_bwd_w_kind", "btsbot_op_ht_lin_bwd_w", "btsbot_op_ht_bn_fwd", "btsbot_op_ht_bn_bwd",
     "btsbot_op_ht_feat_rows", "btsbot_op_ht_logits", "btsbot_op_ht_copy_cols",
@@ -241,6 +243,16 @@ def lib() -> C.CDLL:
     L.btsbot_op_head.restype = i32
     L.btsbot_op_head.argtypes = ([i32, vp, i32, vp, vp, vp, i32] + [vp] * 6 + [i32, vp, vp, i32, i32, i32, C.POINTER(i32),
                                  C.POINTER(vp), C.POINTER(vp), i32] + [vp] * 4 + [i32, vp])
+    L.btsbot_op_cn_stage3_supported.restype = i32
+    L.btsbot_op_cn_stage3_supported.argtypes = [i32] * 3
+    L.btsbot_op_cn_stage3_hfrag_bytes.restype = i64
+    L.btsbot_op_cn_stage3_hfrag_bytes.argtypes = [i32] * 3
+    L.btsbot_op_cn_stage3.restype = i32
+    L.btsbot_op_cn_stage3.argtypes = [i32] * 4 + [vp, i32] + [C.POINTER(vp)] * 9 + [vp]
+    L.btsbot_op_cn_pack_s3.restype = i32
+    L.btsbot_op_cn_pack_s3.argtypes = [i32, vp, vp, i32, i32, i32, vp, vp, vp]
+    L.btsbot_op_cn_fp8_scale.restype = i32
+    L.btsbot_op_cn_fp8_scale.argtypes = [vp, vp, i64, i32, vp, vp]
     for name, args in (("lin_is_wide", [i32] * 4),
                        ("lin_fwd", [vp, i32, vp, vp, vp, vp] + [i32] * 5 + [vp, f32, vp]),
                        ("act_bwd", [vp, i32, vp, vp, i32, i32, i32, vp, f32, vp]),

@@ -3,6 +3,7 @@
 #include <string.h>
 
 #include "maxvit.h"
+#include "stage3.h"
 
 extern "C" int btsbot_op_gemm(int prec, int epi, const void* X, const void* W, const float* bias,
                               const float* gamma, const float* resid, void* out, int M, int N,
@@ -408,4 +409,126 @@ extern "C" int btsbot_op_mv_stem(int prec, const float* img, const float* conv1_
   TRY(launch_mv_stem1(prec, img, sc.at(o_w1), bn_shift, sc.at(o_mid), B, st));
   TRY(launch_mv_pack_conv3(prec, conv2_w, sc.at(o_w2), 64, 32, st));
   return launch_mv_stem2(prec, sc.at(o_mid), sc.at(o_w2), out, pooled, xn, pre_scale, pre_shift, B, st);
+}
+
+// ---- ConvNeXt stage 3 (stage3.hip) alone: `depth` blocks in place on the caller's rows, and its packers on the caller's
+// buffers.  Parameters come in the state-dict layout (fp32); the operand images are built in a stream-ordered scratch by
+// the launchers the handle uses (pack.hip's calls for a stage-3 block, stage_args.hip's pointers into them).
+namespace {
+
+int s3_op_bad(const char* who, const char* what) {
+  btsbot_set_error("%s: %s", who, what);
+  return BTSBOT_ERR_INVALID_ARG;
+}
+bool s3_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+bool s3_frag_prec(int prec) { return prec == BTSBOT_BF16 || prec == BTSBOT_F16 || prec == BTSBOT_FP8 || prec == BTSBOT_F16X2; }
+size_t s3_esz(int prec) { return prec == BTSBOT_FP8 ? 1 : prec == BTSBOT_F16X2 ? 4 : 2; }
+
+}  // namespace
+
+extern "C" int btsbot_op_cn_stage3_supported(int prec, int c3, int depth) { return stage3_supported(prec, c3, depth) ? 1 : 0; }
+
+extern "C" int64_t btsbot_op_cn_stage3_hfrag_bytes(int prec, int c3, int B) {
+  if (!s3_frag_prec(prec) || c3 < 1 || B < 0) {
+    btsbot_set_error("op_cn_stage3_hfrag_bytes: bad argument prec=%d c3=%d B=%d", prec, c3, B);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  return (int64_t)stage3_hfrag_bytes(prec, c3, B);
+}
+
+extern "C" int btsbot_op_cn_stage3(int prec, int c3, int depth, int wide, float* x, int B, const float* const* dw_w,
+                                   const float* const* dw_b, const float* const* ln_w, const float* const* ln_b,
+                                   const float* const* fc1_w, const float* const* fc1_b, const float* const* fc2_w,
+                                   const float* const* fc2_b, const float* const* gamma, void* stream) {
+  const char* who = "op_cn_stage3";
+  if (!stage3_supported(prec, c3, depth)) {
+    btsbot_set_error("op_cn_stage3: unsupported (prec %d, width %d, depth %d): BTSBOT_BF16 / F16 / FP8 / F16X2, 512 or 640 "
+                     "channels, 1 to %d blocks", prec, c3, depth, S3_MAX_DEPTH);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (wide != 0 && wide != 1) return s3_op_bad(who, "wide must be 0 or 1");
+  if (wide && prec == BTSBOT_F16X2) return s3_op_bad(who, "the split mode has no wide tiles");
+  if (B < 0) return s3_op_bad(who, "negative row count");
+  const float* const* lists[9] = {dw_w, dw_b, ln_w, ln_b, fc1_w, fc1_b, fc2_w, fc2_b, gamma};
+  if (x == nullptr) return s3_op_bad(who, "null pointer");
+  for (const float* const* l : lists) {
+    if (l == nullptr) return s3_op_bad(who, "null pointer");
+    for (int j = 0; j < depth; ++j)
+      if (l[j] == nullptr) return s3_op_bad(who, "null pointer");
+  }
+  if (!s3_al16(x)) return s3_op_bad(who, "x must be 16-byte aligned");
+  for (int j = 0; j < depth; ++j)
+    if (!s3_al16(dw_b[j]) || !s3_al16(ln_w[j]) || !s3_al16(ln_b[j]) || !s3_al16(fc1_b[j]) || !s3_al16(fc2_b[j]) ||
+        !s3_al16(gamma[j]))
+      return s3_op_bad(who, "the parameter vectors must be 16-byte aligned");
+  if (B == 0) return BTSBOT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int ch = c3;
+  const size_t wb = (size_t)4 * ch * ch * s3_esz(prec), hbytes = stage3_hfrag_bytes(prec, ch, B);
+  StreamScratch sc(st, who);   // per block: tap-major taps | fc1 fragments | gamma * fc2 fragments | scales; then hfrag
+  size_t o_dw[S3_MAX_DEPTH], o_w1[S3_MAX_DEPTH], o_w2[S3_MAX_DEPTH], o_sc[S3_MAX_DEPTH];
+  for (int j = 0; j < depth; ++j) {
+    o_dw[j] = sc.reserve((size_t)49 * ch * 4);
+    o_w1[j] = sc.reserve(wb);
+    o_w2[j] = sc.reserve(wb);
+    o_sc[j] = sc.reserve(64);
+  }
+  const size_t o_h = sc.reserve(hbytes);
+  TRY(sc.alloc());
+  Stage3Args a;
+  memset(&a, 0, sizeof(a));
+  a.x = x;
+  a.depth = depth;
+  a.hfrag = sc.at(o_h);
+  a.B = B;
+  a.stamps = nullptr;
+  for (int j = 0; j < depth; ++j) {
+    float* scales = sc.at<float>(o_sc[j]);
+    TRY(launch_transpose_f32(dw_w[j], sc.at<float>(o_dw[j]), ch, 49, st));   // (pack.hip's p_dw: tap-major [49][C])
+    TRY(launch_pack_s3(prec, fc1_w[j], nullptr, sc.at(o_w1[j]), 4 * ch, ch, 1, scales, st));
+    TRY(launch_pack_s3(prec, fc2_w[j], gamma[j], sc.at(o_w2[j]), ch, 4 * ch, 0, scales + 2, st));
+    Stage3Blk& k = a.blk[j];
+    k.dw_c = sc.at<float>(o_dw[j]) + 24 * ch;   // the centre row (stage_args.hip)
+    k.dw_b = dw_b[j];
+    k.ln_w = ln_w[j];
+    k.ln_b = ln_b[j];
+    k.w1p = sc.at(o_w1[j]);
+    k.b1 = fc1_b[j];
+    k.w2p = sc.at(o_w2[j]);
+    k.b2 = fc2_b[j];
+    k.gamma = gamma[j];
+    k.scales = prec == BTSBOT_FP8 ? scales : nullptr;
+  }
+  // 0xFF bytes are NaN in bf16, f16 and e4m3: a block of hfrag that no fc1 tile wrote shows if it reaches a live row
+  HIP_TRY(hipMemsetAsync(a.hfrag, 0xFF, hbytes, st));
+  for (int j = 0; j < depth; ++j) {
+    TRY(launch_stage3(prec, ch, a, j, 0, wide != 0, st));
+    TRY(launch_stage3(prec, ch, a, j, 1, wide != 0, st));
+  }
+  return BTSBOT_OK;
+}
+
+extern "C" int btsbot_op_cn_pack_s3(int prec, const float* src, const float* rowscale, int rows, int K, int swap23, void* dst,
+                                    float* scale, void* stream) {
+  const char* who = "op_cn_pack_s3";
+  if (src == nullptr || dst == nullptr) return s3_op_bad(who, "null pointer");
+  if (!s3_frag_prec(prec)) return s3_op_bad(who, "precision must be bf16, f16, fp8 or f16x2");
+  if (prec == BTSBOT_FP8 && scale == nullptr) return s3_op_bad(who, "the fp8 mode needs a scale slot");
+  const int kstep = prec == BTSBOT_FP8 ? 64 : 16;
+  if (rows < 32 || rows % 32 != 0 || K < kstep || K % kstep != 0 || (long)rows * K >= (1L << 31)) {
+    btsbot_set_error("op_cn_pack_s3: bad shape rows=%d K=%d (rows a multiple of 32, K of %d)", rows, K, kstep);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (swap23 != 0 && swap23 != 1) return s3_op_bad(who, "swap23 must be 0 or 1");
+  return launch_pack_s3(prec, src, rowscale, dst, rows, K, swap23, scale, (hipStream_t)stream);
+}
+
+extern "C" int btsbot_op_cn_fp8_scale(const float* src, const float* rowscale, int64_t n, int K, float* scale, void* stream) {
+  const char* who = "op_cn_fp8_scale";
+  if (src == nullptr || scale == nullptr) return s3_op_bad(who, "null pointer");
+  if (n < 1 || K < 1 || (rowscale != nullptr && n % K != 0)) {
+    btsbot_set_error("op_cn_fp8_scale: bad shape n=%ld K=%d (n >= 1; whole rows of K where rowscale is given)", (long)n, K);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  return launch_fp8_scale(src, rowscale, (long)n, K, scale, (hipStream_t)stream);
 }

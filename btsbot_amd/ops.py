@@ -815,3 +815,59 @@ def ht_copy_cols(dst, src):
     assert dst.shape[0] == M
     _ht("copy_cols", src, _p(dst), ldd, _p(src), lds, cols, M)
     return dst
+
+
+# ---- ConvNeXt stage 3 alone (btsbot_op_cn_*, infer_ops.hip / stage3.hip).  Argument checks are the library's: these
+# wrappers pass what they are given (None as a null pointer), so the refusals can be asked for.
+S3_PARAMS = ("dw_w", "dw_b", "ln_w", "ln_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "gamma")
+_S3_ESZ = {"bf16": 2, "f16": 2, "fp8": 1, "f16x2": 4}
+
+
+def cn_stage3_supported(precision, c3, depth):
+    """stage3.hip's own predicate."""
+    return bool(_lib.lib().btsbot_op_cn_stage3_supported(_lib.PRECISION[precision], c3, depth))
+
+
+def cn_stage3_hfrag_bytes(precision, c3, B):
+    """Bytes of the hidden-activation scratch a stage-3 call of B rows uses."""
+    return _lib.check(_lib.lib().btsbot_op_cn_stage3_hfrag_bytes(_lib.PRECISION[precision], c3, B),
+                      "btsbot_op_cn_stage3_hfrag_bytes")
+
+
+def cn_stage3(precision, x, blocks, wide=False, B=None, c3=None):
+    """`len(blocks)` ConvNeXt blocks on 1x1 maps, in place on x [B, c3] (fp32).  blocks: one dict per block with the fp32
+    tensors of S3_PARAMS in state-dict layout (dw_w [C, 1, 7, 7], fc1_w [4C, C], fc2_w [C, 4C]).  B / c3 default to x's
+    shape (a flat view of a larger buffer passes them)."""
+    if B is None:
+        B, c3 = x.shape
+    lists = [(C.c_void_p * max(len(blocks), 1))(*[(b[k].data_ptr() if b[k] is not None else 0) for b in blocks])
+             for k in S3_PARAMS]
+    on = x if x is not None else next(t for b in blocks for t in b.values() if t is not None)
+    with torch.cuda.device(on.device):
+        _lib.check(_lib.lib().btsbot_op_cn_stage3(_lib.PRECISION[precision], c3, len(blocks), int(wide), _p(x), B, *lists,
+                                                  _stream(on)), "btsbot_op_cn_stage3")
+    return x
+
+
+def cn_pack_s3(precision, src, rowscale=None, swap23=False, dst=None, scale=None):
+    """stage 3's fragment packer: src [rows, K] fp32 (x rowscale [rows]) -> dst, a uint8 tensor of rows * K operand values
+    (made when None); fp8: scale [2] fp32 receives {S, 1/S} (made when None).  Returns (dst, scale)."""
+    rows, K = src.shape
+    if dst is None:
+        dst = torch.empty(rows * K * _S3_ESZ[precision], dtype=torch.uint8, device=src.device)
+    if scale is None and precision == "fp8":
+        scale = torch.empty(2, dtype=torch.float32, device=src.device)
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.lib().btsbot_op_cn_pack_s3(_lib.PRECISION[precision], _p(src), _p(rowscale), rows, K, int(swap23),
+                                                   _p(dst), _p(scale), _stream(src)), "btsbot_op_cn_pack_s3")
+    return dst, scale
+
+
+def cn_fp8_scale(src, rowscale=None, K=1, scale=None):
+    """scale [2] = {S, 1/S}: S the power of two that puts max |src[i] * rowscale[i // K]| into (120, 240]."""
+    if scale is None:
+        scale = torch.empty(2, dtype=torch.float32, device=src.device)
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.lib().btsbot_op_cn_fp8_scale(_p(src), _p(rowscale), src.numel(), K, _p(scale), _stream(src)),
+                   "btsbot_op_cn_fp8_scale")
+    return scale

@@ -634,6 +634,32 @@ int btsbot_op_ht_feat_rows(const float* feat, int F, const float* hw, const floa
 int btsbot_op_ht_logits(const float* in, float* logits, float* scores, int M, void* stream);
 int btsbot_op_ht_copy_cols(float* dst, int ldd, const float* src, int lds, int cols, int M, void* stream);
 
+/* ConvNeXt stage 3 alone (stage3.hip: 1x1 maps, s3_fc1 / s3_fc2), for the per-kernel tests (infer_ops.hip).
+ * btsbot_op_cn_stage3 runs `depth` blocks
+ *     x += gamma * fc2( GELU( fc1( LN( dw_c * x + dw_b ) ) ) )          (dw_c = the 7x7 depthwise filter's centre tap)
+ * in place on x [B][c3] (fp32).  Every parameter is a host array of `depth` device pointers, fp32 in state-dict layout:
+ * dw_w [C][1][7][7], dw_b, ln_w, ln_b [C], fc1_w [4C][C], fc1_b [4C], fc2_w [C][4C], fc2_b, gamma [C].  The operand
+ * images (tap-major taps, the fc1 / gamma * fc2 fragments, the fp8 scales) are built in the call's scratch by the
+ * launchers the handle uses; the hidden-activation scratch of btsbot_op_cn_stage3_hfrag_bytes() bytes starts as 0xFF
+ * bytes (NaN in bf16, f16 and e4m3).  wide: 64-alert / 64-channel tiles.  BTSBOT_ERR_INVALID_ARG with a message, nothing
+ * launched: what btsbot_op_cn_stage3_supported() refuses (prec BF16 / F16 / FP8 / F16X2, c3 512 / 640, depth 1..4),
+ * wide with BTSBOT_F16X2, a null pointer, x or a parameter vector not 16-byte aligned.  B == 0: BTSBOT_OK, nothing touched.
+ * btsbot_op_cn_pack_s3: fp32 src [rows][K] (x rowscale[row], or NULL) -> stage 3's A fragments in dst (rows * K values of
+ *   2 / 2 / 1 / 4 bytes in BF16 / F16 / FP8 / F16X2; rows a multiple of 32, K of 16 -- 64 in fp8); swap23: tile row r
+ *   holds source row (r with bits 2 and 3 exchanged).  fp8: scale [2] (device) receives {S, 1/S}, the values are packed
+ *   times S, and swap23 == 0 orders k as s3_fc1 writes the hidden units (fc2's filter).
+ * btsbot_op_cn_fp8_scale: scale [2] (device) <- {S, 1/S}, S the power of two with 120 < S max|src[i] rowscale[i / K]| <= 240
+ *   ({1, 1} when that maximum is 0); src [n], rowscale [n / K] or NULL. */
+int btsbot_op_cn_stage3_supported(int prec, int c3, int depth);
+int64_t btsbot_op_cn_stage3_hfrag_bytes(int prec, int c3, int B);
+int btsbot_op_cn_stage3(int prec, int c3, int depth, int wide, float* x, int B, const float* const* dw_w,
+                        const float* const* dw_b, const float* const* ln_w, const float* const* ln_b,
+                        const float* const* fc1_w, const float* const* fc1_b, const float* const* fc2_w,
+                        const float* const* fc2_b, const float* const* gamma, void* stream);
+int btsbot_op_cn_pack_s3(int prec, const float* src, const float* rowscale, int rows, int K, int swap23, void* dst,
+                         float* scale, void* stream);
+int btsbot_op_cn_fp8_scale(const float* src, const float* rowscale, int64_t n, int K, float* scale, void* stream);
+
 /* Measurement aid with no reference counterpart (bench.py's roofline leg): when on, every kernel
  * launch of forward() is bracketed by two HIP events recorded on the launch stream;
  * profile_collect() waits for them and returns, per kernel family (profile_category_name), the

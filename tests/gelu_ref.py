@@ -6,14 +6,18 @@ import math
 import torch
 
 EPS = 2.0 ** -24
-U = {"f32": 0.0, "bf16": 2.0 ** -8, "f16": 2.0 ** -11}
-SUB = {"f32": 0.0, "bf16": 0.0, "f16": 2.0 ** -25}
+# one rounding to the format: U relative, SUB the floor below its smallest normal.  "f16x2" = f16 head + f16 remainder (the
+# remainder of a value is rounded once more: 2^-11 of 2^-11; its floor is f16's subnormal spacing / 2); "fp8" = OCP e4m3
+# (3 mantissa bits; smallest subnormal 2^-9, so half a step is 2^-10; largest finite value 448)
+U = {"f32": 0.0, "bf16": 2.0 ** -8, "f16": 2.0 ** -11, "f16x2": 2.0 ** -22, "fp8": 2.0 ** -4}
+SUB = {"f32": 0.0, "bf16": 0.0, "f16": 2.0 ** -25, "f16x2": 2.0 ** -25, "fp8": 2.0 ** -10}
 L_GELU = 1.13                         # max |gelu'| = 1.1289 (both fits match it)
 
 GELU_Q = {3: (-1.0036805164077327, -1.1287482669759885, -0.49926576060257244, -0.024772998623334343),
           5: (-1.000039487932206, -1.1507770495088248, -0.46001256950698816, -0.05181158088529847,
               0.007079169600613161, -0.0004726569791655389)}
-GELU_DEG = {"bf16": 3, "f16": 5}
+# (GeluDeg's primary template is 5: the split mode takes it; GeluOf<fp8_t> is bf16)
+GELU_DEG = {"bf16": 3, "f16": 5, "f16x2": 5, "fp8": 3}
 LN2 = math.log(2.0)
 
 

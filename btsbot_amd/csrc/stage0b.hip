@@ -61,7 +61,7 @@ constexpr int LNIMGB = P * LNP;                   // 61200
 static_assert(LNIMGB % 16 == 0 && PLB + CHUNKB <= LNIMGB, "ring slot 2 inside the image's tail, behind the planar image");
 // LDS layout: the image region (planar image, fp32 image, the downsample's 16-bit map: never live together), ring
 // slots 0 and 1 behind it, slot 2 over the fp32 image's tail at byte 51200 (zero_planar() never touches it), then the
-// block's fp32 words.  Split mode (X2): a second planar image behind the first (the f16 remainders of the map the
+// block's fp32 words and the downsample's (kernel-lifetime constants, fetched once in the prologue).  Split mode (X2): a second planar image behind the first (the f16 remainders of the map the
 // depthwise phase reads; the fp32 image fits inside the two) and chunks of twice the size (the filters' remainders
 // behind their heads), all three slots behind the images -- 153,344 bytes, one workgroup per CU.
 template <bool X2> struct S0L {
@@ -70,7 +70,10 @@ template <bool X2> struct S0L {
   static constexpr int OFF_RING = X2 ? PLANES * PLB : LNIMGB;
   static constexpr int OFF_SLOT2 = X2 ? OFF_RING + 2 * CHB : PLB;
   static constexpr int OFF_B1 = OFF_RING + (X2 ? NSLOT : 2) * CHB;   // 256 + 3 x 64 floats: this block's fc1 bias, gamma*b2, LN weight, LN bias
-  static constexpr int LDS_BYTES = OFF_B1 + (HID + 3 * C) * 4;       // 79376 (two workgroups per CU) / 153344
+  // kernel-lifetime constants, fp32: the downsample's LN weight [64] | LN bias [64] | conv bias [128], then the stem's
+  // bias [64] | LN weight [64] | LN bias [64]
+  static constexpr int OFF_DSC = OFF_B1 + (HID + 3 * C) * 4;
+  static constexpr int LDS_BYTES = OFF_DSC + 7 * C * 4;              // 81168 (two workgroups per CU) / 155136
   static __device__ __forceinline__ int slot(int s) { return s == 2 ? OFF_SLOT2 : OFF_RING + s * CHB; }
 };
 static_assert(S0L<false>::LDS_BYTES <= 81920, "two workgroups per CU");
@@ -153,6 +156,7 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
   float* b2s = b1s + HID;
   float* lnws = b2s + C;         // this block's LayerNorm weight and bias
   float* lnbs = lnws + C;
+  float* dscs = reinterpret_cast<float*>(smem + L::OFF_DSC);   // ds_lnw | ds_lnb | ds_b | stem_b | stem_lnw | stem_lnb
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 31, h = lane >> 5;
@@ -168,6 +172,43 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
   const int dj = lane & 3, dch = wave * 16 + (lane >> 2);
 
   SB_STAMP(0);
+  // ---- the vector-memory queue returns in order, so what the first products need is requested first: both column
+  //      blocks' image rows (2 x 3 channels x 2 rows of 4 pixels, unaligned 16-byte loads), whose HBM latency then runs
+  //      under the zero fill below instead of behind a block's 43 KB of taps
+  f4u iq[2][3][2];
+  {
+    const float* src = a.img + (size_t)alert * 3 * 63 * 63;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int pc = live[t] ? pix[t] : 0;
+      const int py = pc / HW, px = pc - py * HW;
+#pragma unroll
+      for (int ci = 0; ci < 3; ++ci) {     // k-step = input channel: k = ci*16 + ky*4 + kx
+        const float* r0 = src + (ci * 63 + 4 * py + 2 * h) * 63 + 4 * px;
+        iq[t][ci][0] = *reinterpret_cast<const f4u*>(r0);
+        iq[t][ci][1] = *reinterpret_cast<const f4u*>(r0 + 63);
+      }
+    }
+  }
+  // the kernel-lifetime constants, the same for every workgroup: the downsample's LayerNorm weight and bias and its
+  // conv bias (one float per lane), the stem's bias and LayerNorm weight and bias (waves 0-2); in LDS before the first
+  // barrier.  Neither the stem nor the tail then waits for a parameter behind other requests.
+  const float dscv = tid < C ? a.ds_lnw[tid] : tid < 2 * C ? a.ds_lnb[tid - C] : a.ds_b[tid - 2 * C];
+  const float stcv = tid < C ? a.stem_b[tid] : tid < 2 * C ? a.stem_lnw[tid - C] : tid < 3 * C ? a.stem_lnb[tid - 2 * C] : 0.f;
+  // the stem's filter fragments
+  frag saf[3][CT], safl[X2 ? 3 : 1][CT];
+  {
+    const T* sw = reinterpret_cast<const T*>(a.stem_w);
+#pragma unroll
+    for (int ci = 0; ci < 3; ++ci)
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) {
+        saf[ci][ct] = *reinterpret_cast<const frag*>(sw + (ct * 32 + lr) * 48 + ci * 16 + h * 8);
+        if (X2)
+          safl[ci][ct] = *reinterpret_cast<const frag*>(reinterpret_cast<const T*>(a.stem_w_lo) + (ct * 32 + lr) * 48 + ci * 16 + h * 8);
+      }
+  }
+  __builtin_amdgcn_sched_barrier(0);
   // a block's Toeplitz taps (16 channels x 4 rows x 21 fragments per wave, lane-linear 8-byte loads) and its
   // per-lane scalars: requested one phase ahead of the depthwise convolution that needs them
   frag4 tw[TW_R], twl[X2 ? TW_R : 1];
@@ -193,41 +234,32 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
     for (int i = tid; i < L::PLANES * PLB / 16; i += 256) reinterpret_cast<uint4*>(pl)[i] = make_uint4(0u, 0u, 0u, 0u);
   };
   zero_planar();
+  dscs[tid] = dscv;
+  if (tid < 3 * C) dscs[4 * C + tid] = stcv;
   __syncthreads();
 
   // ============================ stem: conv 4x4 s4 + LN =====================================
+  // (operands requested in the prologue; bias and LayerNorm parameters are words of LDS: one counted wait per column
+  //  block for its image rows, none for a parameter)
   f32x16 x[2][CT];
   {
-    const float* src = a.img + (size_t)alert * 3 * 63 * 63;
-    const T* sw = reinterpret_cast<const T*>(a.stem_w);
-    frag af[3][CT], afl[X2 ? 3 : 1][CT];
-#pragma unroll
-    for (int ci = 0; ci < 3; ++ci)
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct) {
-        af[ci][ct] = *reinterpret_cast<const frag*>(sw + (ct * 32 + lr) * 48 + ci * 16 + h * 8);
-        if (X2)
-          afl[ci][ct] = *reinterpret_cast<const frag*>(reinterpret_cast<const T*>(a.stem_w_lo) + (ct * 32 + lr) * 48 + ci * 16 + h * 8);
-      }
+    const float* stbs = dscs + 4 * C;   // stem bias | LN weight | LN bias
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      const int pc = live[t] ? pix[t] : 0;
-      const int py = pc / HW, px = pc - py * HW;
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
         for (int qd = 0; qd < 4; ++qd) {
-          const float4 bv = *reinterpret_cast<const float4*>(a.stem_b + ct * 32 + 8 * qd + 4 * h);
-          x[t][ct][4 * qd + 0] = bv.x;
-          x[t][ct][4 * qd + 1] = bv.y;
-          x[t][ct][4 * qd + 2] = bv.z;
-          x[t][ct][4 * qd + 3] = bv.w;
+          const f32x4 bv = lds_f32x4(stbs + ct * 32 + 8 * qd + 4 * h);
+          x[t][ct][4 * qd + 0] = bv[0];
+          x[t][ct][4 * qd + 1] = bv[1];
+          x[t][ct][4 * qd + 2] = bv[2];
+          x[t][ct][4 * qd + 3] = bv[3];
         }
 #pragma unroll
       for (int ci = 0; ci < 3; ++ci) {     // k-step = input channel: k = ci*16 + ky*4 + kx
-        const float* r0 = src + (ci * 63 + 4 * py + 2 * h) * 63 + 4 * px;
-        const f4u v0 = *reinterpret_cast<const f4u*>(r0);
-        const f4u v1 = *reinterpret_cast<const f4u*>(r0 + 63);
+        const f4u v0 = iq[t][ci][0];
+        const f4u v1 = iq[t][ci][1];
         frag bf, bfl;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -241,14 +273,14 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
           if (X2) {
-            x[t][ct] = Mfma<T>::m32(afl[ci][ct], bf, x[t][ct]);
-            x[t][ct] = Mfma<T>::m32(af[ci][ct], bfl, x[t][ct]);
+            x[t][ct] = Mfma<T>::m32(safl[ci][ct], bf, x[t][ct]);
+            x[t][ct] = Mfma<T>::m32(saf[ci][ct], bfl, x[t][ct]);
           }
-          x[t][ct] = Mfma<T>::m32(af[ci][ct], bf, x[t][ct]);
+          x[t][ct] = Mfma<T>::m32(saf[ci][ct], bf, x[t][ct]);
         }
       }
       if (KEEP && live[t]) regs_to_tap(x[t], a.keep_stem_pre + ((size_t)alert * P + pix[t]) * C, h);
-      ln_regs(x[t], a.stem_lnw, a.stem_lnb, h, x[t]);
+      ln_regs<true>(x[t], stbs + C, stbs + 2 * C, h, x[t]);
       if (live[t]) regs_to_planar<DT, PLO, KEEP && !std::is_same<T, f16_t>::value>(x[t], pl, pix[t], h);
       if (a.tap_stem != nullptr && live[t])
         regs_to_tap(x[t], a.tap_stem + ((size_t)alert * P + pix[t]) * C, h);
@@ -621,10 +653,15 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
     //  other waves may still be reading, lie at or behind byte 51200)
     constexpr int MAPB = 256 * PITCH;   // split mode: the remainder image follows (into the second planar image's bytes)
     static_assert(MAPB <= PLB && 2 * MAPB <= S0L<true>::OFF_RING, "the 16-bit [pixel][channel] image(s) in front of every ring slot");
+    // (the lane id is laundered: hipcc otherwise computes the constants' LDS addresses in the prologue and keeps them
+    //  through the whole kernel, in a register the inference forms do not have)
+    int lt = tid;
+    asm volatile("" : "+v"(lt));
+    const int ht = (lt >> 5) & 1, lrt = lt & 31;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       f32x16 xn[CT];
-      ln_regs(x[t], a.ds_lnw, a.ds_lnb, h, xn);
+      ln_regs<true>(x[t], dscs, dscs + C, ht, xn);   // (weights from LDS: no wait behind the 16 fragments above)
       regs_to_map<T, X2 ? MAPB : 0>(xn, map, pix[t], h);
     }
     if (X2) {
@@ -632,7 +669,9 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks) afl[ks] = *reinterpret_cast<const frag*>(dwl + ks * 16);
     }
-    __syncthreads();
+    // raw barrier: the map is complete once everybody's LDS stores are; __syncthreads() would wait for the filter too
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
     if (KEEP) {   // the downsample's patch rows [output pixel][q = 2 ky + kx][64] = LayerNorm'd pixels (2 oy + ky, 2 ox + kx)
       unsigned char* dst = reinterpret_cast<unsigned char*>(a.keep_patches) + (size_t)alert * 49 * 4 * C * 2;
       for (int i = tid; i < 49 * 4 * 8; i += 256) {
@@ -643,39 +682,67 @@ __global__ __launch_bounds__(256, WPS) void stage0b_kernel(Stage0Args a) {
       }
     }
     SB_STAMP(12);
+    // Both column blocks' 16-step chains interleaved (two independent accumulators, each in its k order); the B fragments
+    // are read two steps ahead of their products into four rotating register sets (read directly in front of its
+    // product, each of the 32 products waited for an LDS round trip: stage2p.hip, part 4); the bias is a word of LDS,
+    // so the only waits for vector memory are hipcc's counted ones for af.
+    const unsigned char* bsrc[2];
+    f32x16 acc[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      const int o = t * 32 + lr;
-      const bool olive = o < 49;
-      const int oc = olive ? o : 0;
+      const int o = t * 32 + lrt, oc = o < 49 ? o : 0;
       const int oy = oc / 7, ox = oc - oy * 7;
-      f32x16 acc;
+      bsrc[t] = map + (2 * oy * HW + 2 * ox) * PITCH + ht * 16;
+    }
 #pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const float4 bv = *reinterpret_cast<const float4*>(a.ds_b + wave * 32 + 8 * qd + 4 * h);
-        acc[4 * qd + 0] = bv.x;
-        acc[4 * qd + 1] = bv.y;
-        acc[4 * qd + 2] = bv.z;
-        acc[4 * qd + 3] = bv.w;
+    for (int qd = 0; qd < 4; ++qd) {
+      const f32x4 bv = lds_f32x4(dscs + 2 * C + wave * 32 + 8 * qd + 4 * ht);
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[t][4 * qd + e] = bv[e];
+    }
+    frag bq[4][2], bql[X2 ? 4 : 1][X2 ? 2 : 1];
+    auto read_b = [&](int ks, int set) {
+      const int q = ks >> 2;
+      const int ofs = ((q >> 1) * HW + (q & 1)) * PITCH + (ks & 3) * 32;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        bq[set][t] = *reinterpret_cast<const frag*>(bsrc[t] + ofs);
+        if (X2) bql[X2 ? set : 0][X2 ? t : 0] = *reinterpret_cast<const frag*>(bsrc[t] + MAPB + ofs);
       }
+    };
+    read_b(0, 0);
+    read_b(1, 1);
 #pragma unroll
-      for (int ks = 0; ks < 16; ++ks) {
-        const int q = ks >> 2;
-        const int pin = (2 * oy + (q >> 1)) * HW + 2 * ox + (q & 1);
-        const frag bf = *reinterpret_cast<const frag*>(map + pin * PITCH + (ks & 3) * 32 + h * 16);
+    for (int ks = 0; ks < 16; ++ks) {
+      // (touching this step's fragments makes hipcc wait for them here, in front of the next request)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        asm volatile("" : "+v"(bq[ks & 3][t]));
+        if (X2) asm volatile("" : "+v"(bql[X2 ? ks & 3 : 0][X2 ? t : 0]));
+      }
+      if (ks + 2 < 16) read_b(ks + 2, (ks + 2) & 3);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
         if (X2) {
-          const frag bfl = *reinterpret_cast<const frag*>(map + MAPB + pin * PITCH + (ks & 3) * 32 + h * 16);
-          acc = Mfma<T>::m32(afl[ks], bf, acc);
-          acc = Mfma<T>::m32(af[ks], bfl, acc);
+          acc[t] = Mfma<T>::m32(afl[ks], bq[ks & 3][t], acc[t]);
+          acc[t] = Mfma<T>::m32(af[ks], bql[X2 ? ks & 3 : 0][X2 ? t : 0], acc[t]);
         }
-        acc = Mfma<T>::m32(af[ks], bf, acc);
+        acc[t] = Mfma<T>::m32(af[ks], bq[ks & 3][t], acc[t]);
       }
-      if (olive) {
-        float* dst = a.out + ((size_t)alert * 49 + o) * 128 + wave * 32 + 4 * h;
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int o = t * 32 + lrt;
+      if (o < 49) {
+        float* dst = a.out + ((size_t)alert * 49 + o) * 128 + wave * 32 + 4 * ht;
 #pragma unroll
         for (int qd = 0; qd < 4; ++qd)
           *reinterpret_cast<float4*>(dst + 8 * qd) =
-              make_float4(acc[4 * qd], acc[4 * qd + 1], acc[4 * qd + 2], acc[4 * qd + 3]);
+              make_float4(acc[t][4 * qd], acc[t][4 * qd + 1], acc[t][4 * qd + 2], acc[t][4 * qd + 3]);
       }
     }
     SB_STAMP(13);

@@ -4,7 +4,7 @@
 //
 // Two forms of one template (S1L<G, X2> holds what follows G):
 //   G = 5  inference in the bf16 / f16 modes (stage 1 of an fp8 handle too) while other forwards are in flight
-//          (Schedule::s1_g5): 512 threads, the 245 pixels on 245 of 8 x 32 pixel slots, one workgroup per CU (132,944 B
+//          (Schedule::s1_g5): 512 threads, the 245 pixels on 245 of 8 x 32 pixel slots, one workgroup per CU (134,992 B
 //          of LDS), ceil(B / 5) workgroups: 205 CUs at 1024 alerts, the others are the other streams'.  A wave
 //          takes ONE group of 16 channels over all five alerts in the depthwise phase (its 21 tap fragments loaded once),
 //          2 of a filter chunk's 16 pieces (waves 0-3 W1, waves 4-7 W2) and one 32-channel tile of the downsample over both
@@ -56,7 +56,9 @@
 //   [0, 51744)             fp32 LN image [98][528 B], over both of the above {[0, 129360): [245][528 B]}
 //   [102400, 135168)       split mode only: W2 slots 1, 2
 //   OFF_B1   67584 [135168] {129360}  fc1 bias [512] | gamma*b2 [128], fp32
-//   OFF_LNW  70144 [137728] {131920}  LN weight [128] | LN bias [128], fp32;  end 71168 [138752] {132944}
+//   OFF_LNW  70144 [137728] {131920}  LN weight [128] | LN bias [128], fp32
+//   OFF_DSC  71168 [138752] {132944}  the downsample's LN weight [128] | LN bias [128] | conv bias [256], fp32: the same for
+//                          every workgroup and block, fetched once in the prologue;  end 73216 [140800] {134992}
 #include "stage0.h"
 #include "stage_regs.h"
 #include <type_traits>
@@ -98,7 +100,8 @@ template <int G, bool X2> struct S1L {
   // longer than ring slots 0, 1 + the planar image at G = 5
   static constexpr int OFF_B1 = OFF_W2X + (X2 ? 2 * SLB : 0) > LNB ? OFF_W2X + (X2 ? 2 * SLB : 0) : LNB;
   static constexpr int OFF_LNW = OFF_B1 + (HID + C) * 4;        // LayerNorm weight [128] | bias [128], fp32
-  static constexpr int LDS_BYTES = OFF_LNW + 2 * C * 4;         // 71168: two workgroups per CU / 138752 / G = 5: 132944
+  static constexpr int OFF_DSC = OFF_LNW + 2 * C * 4;           // the downsample's LN weight [128] | LN bias [128] | bias [256], fp32
+  static constexpr int LDS_BYTES = OFF_DSC + (2 * C + CN) * 4;  // 73216: two workgroups per CU / 140800 / G = 5: 134992
   static_assert(4 * SLB <= PLANES * PLB, "W1 slots + W2 slot 0 inside the planar images");
   static_assert(LNB <= OFF_B1 && OFF_B1 % 16 == 0, "the fp32 image ends in front of the bias words");
   static_assert((X2 ? 2 : 1) * MAPB <= OFF_B1, "the [pixel][channel] image(s) in front of the bias words");
@@ -165,6 +168,7 @@ __global__ __launch_bounds__((S1L<G, X2>::NT), WPS) void stage1b_kernel(Stage1Ar
   float* b2s = b1s + HID;
   float* lnws = reinterpret_cast<float*>(smem + L::OFF_LNW);
   float* lnbs = lnws + C;
+  float* dscs = reinterpret_cast<float*>(smem + L::OFF_DSC);   // kernel-lifetime constants: ds_lnw | ds_lnb | ds_b
   // filter rings, 3 slots of 8 KB each (split mode: 16 KB, the remainders behind the heads): the W1 slots and W2 slot 0
   // lie in the planar image(s), W2 slots 1, 2 in ring slots 0, 1 (split mode: in a region of their own); all but W2
   // slot 0 overlap the fp32 LayerNorm image, so the first request follows the barrier that ends its row reads
@@ -198,6 +202,15 @@ __global__ __launch_bounds__((S1L<G, X2>::NT), WPS) void stage1b_kernel(Stage1Ar
       }
     }
   };
+  // the downsample's LayerNorm weight and bias and its conv bias: one float per lane (two on four waves), in LDS before
+  // block 0's first barrier -- no ordinary load may be outstanding once the filter rings run (vmcnt retires in order)
+  constexpr int NDSC = (2 * C + CN) / NT;
+  float dscv[NDSC];
+#pragma unroll
+  for (int i = 0; i < NDSC; ++i) {
+    const int f = tid + i * NT;   // (wave-uniform choice: the three vectors are multiples of 64 floats)
+    dscv[i] = f < C ? a.ds_lnw[f] : f < 2 * C ? a.ds_lnb[f - C] : a.ds_b[f - 2 * C];
+  }
   zero_pads();
   // ---- the residual stream does NOT stay in registers through the depthwise phase (64 registers next to that
   //      phase's 64 outputs and 42 tap registers spill): it is re-read at the start of each MLP, from the stage
@@ -221,6 +234,8 @@ __global__ __launch_bounds__((S1L<G, X2>::NT), WPS) void stage1b_kernel(Stage1Ar
     load_x(xsrc, x0);
     if (inmap) regs_to_planar<DT, G, PLO, KEEP && !std::is_same<T, f16_t>::value>(x0, pl, p, h);
   }
+#pragma unroll
+  for (int i = 0; i < NDSC; ++i) dscs[tid + i * NT] = dscv[i];
   SC_STAMP(1);
 
   f32x16 x[CT];   // (written in full at the start of every MLP: dead through the depthwise phases)
@@ -735,11 +750,6 @@ __global__ __launch_bounds__((S1L<G, X2>::NT), WPS) void stage1b_kernel(Stage1Ar
   // ---- downsample: LN + conv 2x2 s2 (128 -> 256): 9 G output pixels x 256 channels, K = 512
   {
     __syncthreads();   // every wave is out of the MLP: the ring and planar bytes from 0 take the LN image
-    {
-      f32x16 xn[CT];
-      ln_regs(x, a.ds_lnw, a.ds_lnb, h, xn);
-      if (inmap) regs_to_map<T, X2 ? MAPB : 0>(xn, stg, p, h);   // (split: the remainder image behind it, dead bytes too)
-    }
     // this wave's output tiles wave, wave + 4 (32 channels each; eight waves: tile wave alone) x 32 k-steps: 64 (32)
     // filter fragments packed as MFMA A operands (1 KiB each, launch_pack_frag32), a ring of 16 in flight; a fragment
     // serves every 32-column block of output pixels (eight waves: 45 pixels on two), so the workgroup loads it once
@@ -749,13 +759,27 @@ __global__ __launch_bounds__((S1L<G, X2>::NT), WPS) void stage1b_kernel(Stage1Ar
     auto fsrc = [&](int stp) {
       return wsrc + (size_t)((wave + NW * (stp >> 5)) * KSD + (stp & (KSD - 1))) * (X2 ? 128 : 64);
     };
+    // the ring's first round is requested in front of the LayerNorm, whose weights are words of LDS: its L2 latency
+    // passes under the arithmetic, and nothing below waits for a vector-memory load before the first product
     frag wq[RING], wql[X2 ? RING : 1];
 #pragma unroll
     for (int i = 0; i < RING; ++i) {
       wq[i] = *fsrc(i);
       if (X2) wql[i] = fsrc(i)[64];
     }
-    __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);
+    // (in place: x is dead behind it, and a second set of 64 registers beside the ring's 64 spills in the f16 forms.
+    //  Every column block goes to the map as soon as it is normalised.  The pixel slots beyond the image store too, into
+    //  the rows behind the map -- dead bytes in front of the bias words -- which spares the phase four branches; not in
+    //  the split form, where those rows are the first of the remainder image.)
+    static_assert(NW * 32 * PITCH <= L::OFF_B1, "the rows of the slots beyond the image lie in dead bytes");
+    ln_regs<true>(x, dscs, dscs + C, h, x, [&](int ct) {
+      if (X2 && !inmap) return;
+      regs_to_map_ct<T, X2 ? MAPB : 0>(x, stg, p, h, ct);   // (split: the remainder image behind it, dead bytes too)
+    });
+    // raw barrier: the map is complete once everybody's LDS stores are; __syncthreads() would wait for the ring as well
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
     if (KEEP) {   // the downsample's patch rows [output pixel][q = 2 ky + kx][128] = LayerNorm'd pixels (2 oy + ky, 2 ox + kx)
       unsigned char* dst = reinterpret_cast<unsigned char*>(a.keep_patches) + (size_t)a0 * PO * 4 * C * 2;
       for (int i = tid; i < nal * PO * 4 * 16; i += NT) {
@@ -767,57 +791,70 @@ __global__ __launch_bounds__((S1L<G, X2>::NT), WPS) void stage1b_kernel(Stage1Ar
       }
     }
     SC_STAMP(12);
-    // output pixel slots o = 32 cb + lr: 18 of 32 / 45 of 64 used; pin0 = the input pixel under tap 0
-    int pin0[NCB];
+    // output pixel slots o = 32 cb + lr: 18 of 32 / 45 of 64 used; bsrc = this lane's half of the input pixel under tap 0
+    const unsigned char* bsrc[NCB];
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
       const int o = cb * 32 + lr, oc = o < G * PO ? o : 0;
       const int g = oc / PO, oo = oc - g * PO;
       const int oy = oo / 3, ox = oo - oy * 3;
-      pin0[cb] = g * PA + 2 * oy * HW + 2 * ox;
+      bsrc[cb] = stg + (g * PA + 2 * oy * HW + 2 * ox) * PITCH + h * 16;
     }
     f32x16 acc[NCB];
-    constexpr int RPT = KSD / RING;   // ring rounds per output tile
-#ifdef S1_EXP_NODS
-#pragma unroll 1
-    for (int rd = 0; rd < 0; ++rd) {
-#else
-#pragma unroll 1
-    for (int rd = 0; rd < NSTEP / RING; ++rd) {
-#endif
+    constexpr int RPT = KSD / RING, NRD = NSTEP / RING;   // ring rounds per output tile, rounds in all
+    static_assert(RING % 8 == 0 && KSD % RING == 0, "a round stays inside a tile and starts at a tap's first k-step");
+    // B fragments of step stp (k-step ks of its tile: tap q = ks >> 3 = (ky*2 + kx), 8 k-steps of 16 channels each), read
+    // two steps ahead of their products into four rotating register sets (RING is a multiple of 4: the rotation carries
+    // over the rounds): read and used in the same step, every product waited for an LDS round trip (stage2p.hip, part 4)
+    frag bq[4][NCB], bql[X2 ? 4 : 1][X2 ? NCB : 1];
+    auto read_b = [&](int stp, int set) {
+      const int ks = stp & (KSD - 1), q = ks >> 3;
+      const int ofs = ((q >> 1) * HW + (q & 1)) * PITCH + (ks & 7) * 32;
+#pragma unroll
+      for (int cb = 0; cb < NCB; ++cb) {
+        bq[set][cb] = *reinterpret_cast<const frag*>(bsrc[cb] + ofs);
+        if (X2) bql[X2 ? set : 0][X2 ? cb : 0] = *reinterpret_cast<const frag*>(bsrc[cb] + MAPB + ofs);
+      }
+    };
+    // one ring round: RING k-steps of tile cot.  The refills are unconditional; the last round (LAST) has none and reads
+    // no fragment past the end.  The tile's bias is a word of LDS: no wait for vector memory but hipcc's counted ones for wq.
+    auto round = [&](auto last_c, int rd) {
+      constexpr bool LAST = decltype(last_c)::value;
       const int cot = wave + NW * (rd / RPT);
       if (rd % RPT == 0) {
 #pragma unroll
         for (int qd = 0; qd < 4; ++qd) {
-          const float4 bv = *reinterpret_cast<const float4*>(a.ds_b + cot * 32 + 8 * qd + 4 * h);
+          const f32x4 bv = lds_f32x4(dscs + 2 * C + cot * 32 + 8 * qd + 4 * h);
 #pragma unroll
-          for (int cb = 0; cb < NCB; ++cb) {
-            acc[cb][4 * qd + 0] = bv.x;
-            acc[cb][4 * qd + 1] = bv.y;
-            acc[cb][4 * qd + 2] = bv.z;
-            acc[cb][4 * qd + 3] = bv.w;
-          }
+          for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[cb][4 * qd + e] = bv[e];
         }
       }
 #pragma unroll
       for (int i = 0; i < RING; ++i) {
-        const int stp = rd * RING + i, ks = stp & (KSD - 1);
-        const int q = ks >> 3;                     // tap (ky*2 + kx): 8 k-steps of 16 channels each
+        const int stp = rd * RING + i;
+        // (touching this step's fragments makes hipcc wait for them here, in front of the next request)
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
-          const int pin = pin0[cb] + (q >> 1) * HW + (q & 1);
-          const frag bf = *reinterpret_cast<const frag*>(stg + pin * PITCH + (ks & 7) * 32 + h * 16);
-          if (X2) {
-            const frag bfl = *reinterpret_cast<const frag*>(stg + MAPB + pin * PITCH + (ks & 7) * 32 + h * 16);
-            acc[cb] = Mfma<T>::m32(wql[i], bf, acc[cb]);
-            acc[cb] = Mfma<T>::m32(wq[i], bfl, acc[cb]);
-          }
-          acc[cb] = Mfma<T>::m32(wq[i], bf, acc[cb]);
+          asm volatile("" : "+v"(bq[i & 3][cb]));
+          if (X2) asm volatile("" : "+v"(bql[X2 ? i & 3 : 0][X2 ? cb : 0]));
         }
-        if (stp + RING < NSTEP) {
+        if (!LAST || i + 2 < RING) read_b(stp + 2, (i + 2) & 3);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb) {
+          if (X2) {
+            acc[cb] = Mfma<T>::m32(wql[i], bq[i & 3][cb], acc[cb]);
+            acc[cb] = Mfma<T>::m32(wq[i], bql[X2 ? i & 3 : 0][X2 ? cb : 0], acc[cb]);
+          }
+          acc[cb] = Mfma<T>::m32(wq[i], bq[i & 3][cb], acc[cb]);
+        }
+        if (!LAST) {
           wq[i] = *fsrc(stp + RING);
           if (X2) wql[i] = fsrc(stp + RING)[64];
         }
+        __builtin_amdgcn_sched_barrier(0);
       }
       if (rd % RPT == RPT - 1) {
 #pragma unroll
@@ -831,7 +868,14 @@ __global__ __launch_bounds__((S1L<G, X2>::NT), WPS) void stage1b_kernel(Stage1Ar
                 make_float4(acc[cb][4 * qd], acc[cb][4 * qd + 1], acc[cb][4 * qd + 2], acc[cb][4 * qd + 3]);
         }
       }
-    }
+    };
+#ifndef S1_EXP_NODS
+    read_b(0, 0);
+    read_b(1, 1);
+#pragma unroll 1
+    for (int rd = 0; rd < NRD - 1; ++rd) round(std::false_type{}, rd);
+    round(std::true_type{}, NRD - 1);
+#endif
     SC_STAMP(13);
   }
 }

@@ -1,6 +1,7 @@
 """Developer timing: per-kernel average launch time (HIP events recorded by the library on the launch stream) of the
 bf16 forward at B alerts, plus the score error against the oracle on 64 alerts (a wrong variant shows up at once).
-BTSBOT_AMD_LIB=<path> times another build of the library (tools/build_variant.sh)."""
+BTSBOT_AMD_LIB=<path> times another build of the library (tools/build_variant.sh); S1_HINT=1 sets the overlap hint by hand
+(stage1b on five alerts per workgroup and its companions, as tools/stamps.py)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -20,6 +21,9 @@ with torch.no_grad():
     ref = O.forward(kind, sd, cfg, img[:64], meta[:64])
 img, meta = img.to(dev), meta.to(dev)
 m = build_model(kind, cfg, sd, dev, prec)
+if os.environ.get("S1_HINT", "0") == "1":
+    from btsbot_amd import _lib
+    _lib.check(_lib.lib().btsbot_set_option(m._handle.ptr, b"forwards_in_flight", 1), "btsbot_set_option")
 out = run_model(kind, m, img, meta)
 err = (torch.sigmoid(out[:64].cpu()) - torch.sigmoid(ref)).abs().max().item()
 t_end = time.perf_counter() + 0.5

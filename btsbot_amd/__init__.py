@@ -57,6 +57,8 @@ from . import novelty
 from .novelty import NoveltyModel, kth_neighbor_distance, local_outlier_factor
 # (the function takes the package attribute ``hdbscan``; the module is ``from btsbot_amd.hdbscan import ...``)
 from .hdbscan import ClusterModel, ClusterTree, MutualReachabilityMST, hdbscan, mutual_reachability_mst
+from . import attribution
+from .attribution import saliency
 from . import layout
 from .layout import (EmbeddingMap, FuzzyGraph, embedding_layout, find_ab_params, fuzzy_graph, layout_transform,
                      optimize_layout, query_memberships)
@@ -77,6 +79,7 @@ __all__ = [
     "graph", "KnnGraph",
     "novelty", "NoveltyModel", "local_outlier_factor", "kth_neighbor_distance",
     "hdbscan", "mutual_reachability_mst", "MutualReachabilityMST", "ClusterTree", "ClusterModel",
+    "attribution", "saliency",
     "layout", "FuzzyGraph", "fuzzy_graph", "optimize_layout", "embedding_layout", "find_ab_params",
     "EmbeddingMap", "layout_transform", "query_memberships",
     "splits", "SPLIT_NAMES", "SOURCE_SETS", "label_set", "split_labels", "subset_mask", "cuts_suffix",

@@ -40,7 +40,7 @@ SYMBOLS = [
     "btsbot_op_mvt_gelu_bwd", "btsbot_op_mvt_bcast_set",
     "btsbot_op_cnt_dwln_bwd_rows", "btsbot_op_cnt_dw3ln_bwd_rows", "btsbot_op_cnt_dwln_bwd", "btsbot_op_cnt_dw3ln_bwd",
     "btsbot_op_cnt_ln_bwd", "btsbot_op_cnt_ln_dw1_bwd", "btsbot_op_cnt_dw_plain", "btsbot_op_cnt_dw_wgrad",
-    "btsbot_op_cnt_colsum_f32",
+    "btsbot_op_cnt_colsum_f32", "btsbot_op_cnt_stem_dgrad",
     "btsbot_op_cnt_mlp_bwd_planes", "btsbot_op_cnt_mlp_bwd_slices", "btsbot_op_cnt_s2mlp_bwd_rows", "btsbot_op_cnt_mlp_bwd",
     "btsbot_op_cnt_s2mlp_bwd", "btsbot_op_cnt_fused_mlp", "btsbot_op_cnt_fc2_grads",
     "btsbot_op_head16_supported", "btsbot_op_head",
@@ -49,7 +49,9 @@ SYMBOLS = [
     "btsbot_op_ht_lin_is_wide", "btsbot_op_ht_lin_fwd", "btsbot_op_ht_act_bwd", "btsbot_op_ht_lin_bwd_in",
     "btsbot_op_ht_lin_bwd_w_kind", "btsbot_op_ht_lin_bwd_w", "btsbot_op_ht_bn_fwd", "btsbot_op_ht_bn_bwd",
     "btsbot_op_ht_feat_rows", "btsbot_op_ht_logits", "btsbot_op_ht_copy_cols",
+    "btsbot_op_ht_bn_eval_fwd", "btsbot_op_ht_bn_bwd_in",
     "btsbot_reserve_train", "btsbot_forward_train", "btsbot_backward", "btsbot_debug_stamps",
+    "btsbot_forward_keep_eval", "btsbot_backward_inputs",
     "btsbot_grad_buckets", "btsbot_wait_grad_bucket", "btsbot_allreduce_grads", "btsbot_use_workspace", "btsbot_set_option",
     "btsbot_augment", "btsbot_eval_metrics", "btsbot_prep_triplets", "btsbot_alert_features",
     "btsbot_split_labels", "btsbot_decode_stamps_workspace", "btsbot_decode_stamps",
@@ -232,6 +234,7 @@ def lib() -> C.CDLL:
                        ("ln_dw1_bwd", [vp] * 7 + [i32] + [vp] * 4 + [i64, i32, vp]),
                        ("dw_plain", [vp, vp, i32, vp, vp, vp, vp] + [i32] * 4 + [vp]),
                        ("dw_wgrad", [vp] * 4 + [i32] * 3 + [vp]), ("colsum_f32", [vp, vp, i32, i32, vp]),
+                       ("stem_dgrad", [vp, vp, vp, i32, i32, vp]),
                        ("mlp_bwd_planes", [i32]), ("mlp_bwd_slices", [i32, i32]), ("s2mlp_bwd_rows", []),
                        ("mlp_bwd", [i32, i32] + [vp] * 10 + [i32, i32, vp]), ("s2mlp_bwd", [i32, i32] + [vp] * 6 + [i32, vp]),
                        ("fused_mlp", [i32, i32] + [vp] * 8 + [i32, vp]), ("fc2_grads", [vp] * 8 + [i32, i32, vp])):
@@ -259,6 +262,7 @@ def lib() -> C.CDLL:
                        ("lin_bwd_in", [vp, vp, vp] + [i32] * 4 + [vp]), ("lin_bwd_w_kind", [vp, i32, vp, i32, i32]),
                        ("lin_bwd_w", [vp, vp, i32, vp, vp, i32, i32, i32, vp]),
                        ("bn_fwd", [vp, i32, i32] + [vp] * 8), ("bn_bwd", [vp, i32, i32] + [vp] * 6),
+                       ("bn_eval_fwd", [vp, i32, i32] + [vp] * 8), ("bn_bwd_in", [vp, i32, i32] + [vp] * 6 + [i32, vp]),
                        ("feat_rows", [vp, i32, vp, vp, vp, i32, i32, vp]), ("logits", [vp, vp, vp, i32, vp]),
                        ("copy_cols", [vp, i32, vp, i32, i32, i32, vp])):
         fn = getattr(L, "btsbot_op_ht_" + name)
@@ -272,6 +276,10 @@ def lib() -> C.CDLL:
     L.btsbot_forward_train.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp]
     L.btsbot_backward.restype = i32
     L.btsbot_backward.argtypes = [vp, vp, vp, i32, i32, vp]
+    L.btsbot_forward_keep_eval.restype = i32
+    L.btsbot_forward_keep_eval.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
+    L.btsbot_backward_inputs.restype = i32
+    L.btsbot_backward_inputs.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
     L.btsbot_grad_buckets.restype = i32
     L.btsbot_grad_buckets.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(i64)]
     L.btsbot_wait_grad_bucket.restype = i32

@@ -318,6 +318,9 @@ class _HipModel(nn.Module):
         if batch == 0:
             empty = torch.empty(0, 1, dtype=torch.float32, device=dev)
             return (empty, empty.clone()) if want_scores else empty
+        if any(self._input_grads(image, meta)):
+            logits = self._run_eval_grad(image, meta)
+            return (logits, torch.sigmoid(logits)) if want_scores else logits
         with torch.cuda.device(dev):
             L, stream = self._prepare(dev, batch)
             logits = torch.empty(batch, dtype=torch.float32, device=dev)
@@ -433,16 +436,112 @@ class _HipModel(nn.Module):
         comb, metag, imageg = self._slot_groups()
         grad_on = torch.is_grad_enabled()
         trainable = [g for g in imageg + metag + comb if g[0].requires_grad] if grad_on else []
-        keep_image = grad_on and any(t.requires_grad for t, *_ in imageg)
+        in_grads = self._input_grads(image, meta)
+        # (a frozen image branch still hands gradients through to its input)
+        keep_image = grad_on and (any(t.requires_grad for t, *_ in imageg) or in_grads[0])
         ref = image if image is not None else meta
         batch, dev = ref.shape[0], ref.device
         if batch < 1:
             raise ValueError("btsbot_amd: training-mode forward needs a non-empty batch")
         masks = self._dropout_masks(batch, dev)
-        if not trainable:
+        if not trainable and not any(in_grads):
             return self._forward_train_raw(image, meta, masks)
-        return _TrainFn.apply(self, image, meta, masks, (trainable, keep_image),
+        return _TrainFn.apply(self, image, meta, masks, (trainable, keep_image, in_grads, False),
                               *[g[0] for g in trainable])
+
+    def _input_grads(self, image, meta):
+        """(image, metadata): which inputs take part in autograd -- grad mode on and the tensor requires grad.  The
+        MaxViT wirings have no input gradient: their inputs never take part."""
+        if not torch.is_grad_enabled() or getattr(self, "_inference_only", False):
+            return (False, False)
+        return (image is not None and image.requires_grad, meta is not None and meta.requires_grad)
+
+    def _run_eval_grad(self, image, meta):
+        """model.eval() forward with an input that requires grad: the eval-form keeping forward
+        (``btsbot_forward_keep_eval``: running statistics, no dropout, nothing written to the arena) behind the same
+        autograd node as the training forward.  Only the inputs are autograd participants here: no parameter receives
+        a ``.grad``.  The logits come from the keeping kernels: in the 16-bit modes those are the training-form
+        forwards, which agree with ``btsbot_forward``'s logits to the mode's parity tolerance, not to the bit (f32:
+        same arithmetic per op, different fusion).  Without an input that requires grad, or under ``no_grad``, eval
+        calls take ``btsbot_forward`` untouched."""
+        in_grads = self._input_grads(image, meta)
+        return _TrainFn.apply(self, image, meta, (None, None), ([], in_grads[0], in_grads, True))
+
+    def metadata_running_mean(self) -> torch.Tensor:
+        """The metadata BatchNorm1d's ``running_mean`` [n_meta]: the metadata row the branch maps to its bias, and the
+        default integrated-gradients baseline (``btsbot_amd.attribution``)."""
+        for (canon, *_), t in zip(self._table_rows, self._tensor_list()):
+            if canon == "meta.0.running_mean":
+                return t.detach()
+        raise ValueError(f"btsbot_amd.{type(self).__name__}: this wiring has no metadata branch")
+
+    def _reserve_train(self, L, stream, batch: int, keep_image: bool):
+        if batch > self._reserved_train or (keep_image and not self._reserved_image):
+            _lib.check(L.btsbot_reserve_train(self._handle.ptr, max(batch, self._reserved_train),
+                                              int(keep_image or self._reserved_image)),
+                       "btsbot_reserve_train")
+            self._reserved_train = max(batch, self._reserved_train)
+            if keep_image and not self._reserved_image:
+                self._reserved_image = True
+                # the dgrad operand images are packed from now on
+                _lib.check(L.btsbot_pack_params(self._handle.ptr,
+                                                C.c_void_p(self._arena.data_ptr()),
+                                                C.c_void_p(stream)), "btsbot_pack_params")
+
+    def _forward_keep_eval_raw(self, image, meta, keep_image: bool):
+        """btsbot_forward_keep_eval on a whole batch; returns logits [B, 1].  Writes nothing into the arena."""
+        ref = image if image is not None else meta
+        batch, dev = ref.shape[0], ref.device
+        with torch.cuda.device(dev):
+            L, stream = self._prepare(dev, batch)
+            self._reserve_train(L, stream, batch, keep_image)
+            logits = torch.empty(batch, dtype=torch.float32, device=dev)
+            _lib.check(L.btsbot_forward_keep_eval(
+                self._handle.ptr,
+                C.c_void_p(image.data_ptr() if image is not None else 0),
+                C.c_void_p(meta.data_ptr() if meta is not None else 0),
+                C.c_void_p(logits.data_ptr()), C.c_void_p(0), batch, int(keep_image), C.c_void_p(stream)),
+                "btsbot_forward_keep_eval")
+        return logits.view(batch, 1)
+
+    def input_gradients(self, *inputs, target: str = "logit", batch_size: int = 1024, **kw_inputs):
+        """``(d_image [B,3,63,63], d_meta [B,n_meta])``: the gradient of every alert's logit (``target="logit"``) or
+        score (``target="score"``: the logit's gradient times ``s (1 - s)``) with respect to its own inputs, ``None``
+        for an input the wiring lacks.  Takes the inputs ``forward`` takes.  Eval mode only (RuntimeError otherwise,
+        as ``embed``): rows are independent there, so the batch is walked in chunks of ``batch_size`` (the kept
+        activations cost about 2.8 MB per alert).  Runs ``btsbot_forward_keep_eval`` + ``btsbot_backward_inputs``
+        outside autograd; touches no parameter's ``.grad``.  MaxViT wirings: NotImplementedError."""
+        if getattr(self, "_inference_only", False):
+            raise NotImplementedError(f"btsbot_amd.{type(self).__name__}: input gradients of the MaxViT wirings are "
+                                      "not built (DESIGN.md section 8)")
+        if target not in ("logit", "score"):
+            raise ValueError(f"btsbot_amd: input_gradients target must be 'logit' or 'score', got {target!r}")
+        if int(batch_size) < 1:
+            raise ValueError("btsbot_amd: input_gradients needs batch_size >= 1")
+        if self.training:
+            raise RuntimeError("btsbot_amd: input_gradients() is defined in eval mode only (BatchNorm batch statistics "
+                               "couple the alerts of a batch and dropout makes the map depend on the draw); call "
+                               "model.eval() first")
+        image, meta = self._bind_inputs(inputs, kw_inputs)
+        image, meta, batch, dev = self._check_inputs(image.detach() if image is not None else None,
+                                                     meta.detach() if meta is not None else None)
+        d_img = torch.empty_like(image) if image is not None else None
+        d_meta = torch.empty_like(meta) if meta is not None else None
+        with torch.no_grad():
+            for b0 in range(0, batch, int(batch_size)):
+                b1 = min(batch, b0 + int(batch_size))
+                ci = image[b0:b1] if image is not None else None
+                cm = meta[b0:b1] if meta is not None else None
+                logits = self._forward_keep_eval_raw(ci, cm, keep_image=ci is not None)
+                if target == "score":
+                    sc = torch.sigmoid(logits)
+                    seed = sc * (1.0 - sc)
+                else:
+                    seed = torch.ones_like(logits)
+                self._backward_raw(seed, False, ci is not None,
+                                   d_image=d_img[b0:b1] if d_img is not None else None,
+                                   d_meta=d_meta[b0:b1] if d_meta is not None else None)
+        return d_img, d_meta
 
     def _image_bn_modules(self):
         """Modules of the image branch that own BatchNorm running statistics (MaxViT's BatchNorm2d)."""
@@ -491,17 +590,7 @@ class _HipModel(nn.Module):
         batch, dev = ref.shape[0], ref.device
         with torch.cuda.device(dev):
             L, stream = self._prepare(dev, batch, train_only=keep_image and self._reserved_image)
-            if batch > self._reserved_train or (keep_image and not self._reserved_image):
-                _lib.check(L.btsbot_reserve_train(self._handle.ptr, max(batch, self._reserved_train),
-                                                  int(keep_image or self._reserved_image)),
-                           "btsbot_reserve_train")
-                self._reserved_train = max(batch, self._reserved_train)
-                if keep_image and not self._reserved_image:
-                    self._reserved_image = True
-                    # the dgrad operand images are packed from now on
-                    _lib.check(L.btsbot_pack_params(self._handle.ptr,
-                                                    C.c_void_p(self._arena.data_ptr()),
-                                                    C.c_void_p(stream)), "btsbot_pack_params")
+            self._reserve_train(L, stream, batch, keep_image)
             logits = torch.empty(batch, dtype=torch.float32, device=dev)
             self._live_masks = masks          # must outlive btsbot_backward
             _lib.check(L.btsbot_forward_train(
@@ -521,17 +610,29 @@ class _HipModel(nn.Module):
         return logits.view(batch, 1)
 
     def _backward_raw(self, dlogits: torch.Tensor, need_meta: bool,
-                      need_image: bool = False) -> torch.Tensor:
-        """d(loss)/d(param) into the flat gradient arena (master-arena layout); returns the arena."""
+                      need_image: bool = False, d_image: Optional[torch.Tensor] = None,
+                      d_meta: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """d(loss)/d(param) into the flat gradient arena (master-arena layout); returns the arena.  d_image / d_meta
+        (contiguous fp32, the inputs' shapes): also d(loss)/d(input), written in full (btsbot_backward_inputs)."""
         dev = self._arena.device
         if getattr(self, "_grad_arena", None) is None or self._grad_arena.device != dev:
             object.__setattr__(self, "_grad_arena", torch.zeros_like(self._arena))
         dl = dlogits.reshape(-1).to(torch.float32).contiguous()
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(_lib.lib().btsbot_backward(
-                self._handle.ptr, C.c_void_p(dl.data_ptr()), C.c_void_p(self._grad_arena.data_ptr()),
-                int(need_meta), int(need_image), C.c_void_p(stream)), "btsbot_backward")
+            if d_image is None and d_meta is None:
+                _lib.check(_lib.lib().btsbot_backward(
+                    self._handle.ptr, C.c_void_p(dl.data_ptr()), C.c_void_p(self._grad_arena.data_ptr()),
+                    int(need_meta), int(need_image), C.c_void_p(stream)), "btsbot_backward")
+            else:
+                for t in (d_image, d_meta):
+                    assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.device == dev)
+                _lib.check(_lib.lib().btsbot_backward_inputs(
+                    self._handle.ptr, C.c_void_p(dl.data_ptr()), C.c_void_p(self._grad_arena.data_ptr()),
+                    int(need_meta), int(need_image),
+                    C.c_void_p(d_image.data_ptr() if d_image is not None else 0),
+                    C.c_void_p(d_meta.data_ptr() if d_meta is not None else 0), C.c_void_p(stream)),
+                    "btsbot_backward_inputs")
         return self._grad_arena
 
     def _grad_buckets(self):
@@ -575,15 +676,20 @@ class _HipModel(nn.Module):
 
 
 class _TrainFn(torch.autograd.Function):
-    """Autograd node around btsbot_forward_train / btsbot_backward (train.py:510,526)."""
+    """Autograd node around btsbot_forward_train (or, in eval mode, btsbot_forward_keep_eval) and btsbot_backward /
+    btsbot_backward_inputs (train.py:510,526).  plan = (trainable parameter slots, keep_image, (image, metadata) input
+    takes part in autograd, eval form)."""
 
     @staticmethod
     def forward(ctx, model, image, meta, masks, plan, *params):
-        trainable, keep_image = plan
+        trainable, keep_image, in_grads, eval_form = plan
         ctx.model = model
         ctx.trainable = trainable
         ctx.keep_image = keep_image
+        ctx.in_grads = in_grads
         ctx.inputs = (image, meta, masks)   # the C side re-reads them in backward: keep them alive
+        if eval_form:
+            return model._forward_keep_eval_raw(image, meta, keep_image)
         return model._forward_train_raw(image, meta, masks, keep_image)
 
     @staticmethod
@@ -592,9 +698,12 @@ class _TrainFn(torch.autograd.Function):
         _comb, metag, _img = model._slot_groups()
         meta_ids = {id(t) for t, *_ in metag}
         need_meta = any(id(t) in meta_ids for t, *_ in trainable)
-        arena = model._backward_raw(dlogits, need_meta, ctx.keep_image)
+        image, meta, _masks = ctx.inputs
+        d_image = torch.empty_like(image) if ctx.in_grads[0] and ctx.needs_input_grad[1] else None
+        d_meta = torch.empty_like(meta) if ctx.in_grads[1] and ctx.needs_input_grad[2] else None
+        arena = model._backward_raw(dlogits, need_meta, ctx.keep_image, d_image, d_meta)
         grads = [arena[off:off + numel].view(shape).clone() for _t, off, numel, shape in trainable]
-        return (None, None, None, None, None, *grads)
+        return (None, d_image, d_meta, None, None, *grads)
 
 
 def _backbone_key_map(bprefix: str, head_norm_key: str, meta_prefix: str, comb_keys):

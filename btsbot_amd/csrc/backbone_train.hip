@@ -323,8 +323,9 @@ int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t s
 // (before the head LayerNorm, which the caller has already differentiated).  Gradients are
 // ACCUMULATED (atomics) into `grads` (master-arena layout): the caller zeroes the image-branch
 // range first.
+// d_img (or nullptr): [B][3][63][63], the gradient w.r.t. the triplets -- one more launch at the end of the chain.
 int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat, float* grads,
-                            int B, hipStream_t st) {
+                            int B, hipStream_t st, float* d_img) {
   const btsbot_config& c = h->cfg;
   const float* m = h->mirror;
   const int prec = c.precision;
@@ -566,5 +567,8 @@ int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat,
   }
   TRY(join());
   if (h->n_buckets == 3 && h->bucket_fine) HIP_TRY(hipEventRecord(h->bucket_ev[2], st));
+  // ---- the triplets' gradient from dxn (still in place: nothing behind the stem's LayerNorm backward writes it) and the
+  //      fp32 filter of the mirror, in every precision mode
+  if (d_img != nullptr) TRY(launch_stem_dgrad(dxn, m + h->stem_w, d_img, B, c.dims[0], st));
   return BTSBOT_OK;
 }

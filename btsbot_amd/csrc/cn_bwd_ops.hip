@@ -1,5 +1,5 @@
 // Op-level entry points of the ConvNeXt training step's LayerNorm / depthwise backward (include/btsbot_hip.h,
-// btsbot_op_cnt_*): the launchers of dwln_bwd.hip and ln_dw_bwd.hip one at a time, on the caller's tensors and stream,
+// btsbot_op_cnt_*): the launchers of dwln_bwd.hip, ln_dw_bwd.hip and stem_dgrad.hip one at a time, on the caller's tensors and stream,
 // for the per-kernel tests.  Nothing here is on the product path: backbone_train_backward calls the same launchers.
 // Every entry point checks its arguments before it allocates or launches anything; what its launcher has no kernel for
 // comes back as BTSBOT_ERR_INVALID_ARG with a message.
@@ -147,4 +147,13 @@ extern "C" int btsbot_op_cnt_colsum_f32(const float* in, float* out, int M, int 
     return BTSBOT_ERR_INVALID_ARG;
   }
   return launch_colsum(BTSBOT_F32, in, out, M, N, (hipStream_t)stream);
+}
+
+extern "C" int btsbot_op_cnt_stem_dgrad(const float* dxn, const float* w, float* dimg, int B, int C0, void* stream) {
+  if (dxn == nullptr || w == nullptr || dimg == nullptr) return cnt_bad("op_cnt_stem_dgrad", "null pointer");
+  if (B < 0 || B > (1 << 17) || (C0 != 64 && C0 != 80)) {
+    btsbot_set_error("op_cnt_stem_dgrad: bad shape B=%d C0=%d (0 <= B <= 131072; C0 64 or 80)", B, C0);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  return launch_stem_dgrad(dxn, w, dimg, B, C0, (hipStream_t)stream);
 }

@@ -186,6 +186,7 @@ struct btsbot_ctx {
   int tcache_batch = 0, train_batch = 0;
   const uint8_t* t_meta_mask = nullptr;
   const uint8_t* t_comb_mask = nullptr;
+  bool t_eval = false;        // the last keeping forward was the eval form (btsbot_forward_keep_eval)
 
   // gradient buckets in the order btsbot_backward() completes them (btsbot_grad_buckets / btsbot_wait_grad_bucket)
   int n_buckets = 0;
@@ -256,16 +257,17 @@ size_t train_cache_floats(const btsbot_ctx* h, int M);
 size_t bb_cache_bytes(const btsbot_ctx* h, int B);
 int backbone_train_forward(btsbot_ctx* h, const float* img, int B, hipStream_t st, float** feat_out);
 int backbone_train_backward(btsbot_ctx* h, const float* img, const float* dfeat, float* grads,
-                            int B, hipStream_t st);
+                            int B, hipStream_t st, float* d_img = nullptr);
 float* train_cache_feat(btsbot_ctx* h, float* cache, int M);
 int head_train_forward(btsbot_ctx* h, float* cache, const float* meta, float* logits,
                        float* scores, int M, const uint8_t* meta_mask, const uint8_t* comb_mask,
-                       float* master, hipStream_t st, bool meta_done = false);
+                       float* master, hipStream_t st, bool meta_done = false, bool eval = false);
 int head_train_meta_forward(btsbot_ctx* h, float* cache, const float* meta, int M, const uint8_t* meta_mask, float* master,
-                            hipStream_t st);
+                            hipStream_t st, bool eval = false);
 int head_train_backward(btsbot_ctx* h, float* cache, const float* dlogits, float* grads, int M,
                         int need_meta, int need_image, float** dfeat_out,
-                        const uint8_t* meta_mask, const uint8_t* comb_mask, hipStream_t st);
+                        const uint8_t* meta_mask, const uint8_t* comb_mask, hipStream_t st, float* d_meta = nullptr,
+                        bool eval = false);
 
 // h->extra + slot for a reader or a packer.  An image the layout never reserved ends the calling function (or lambda)
 // with BTSBOT_ERR_STATE and its name, in front of the launch it was meant for.

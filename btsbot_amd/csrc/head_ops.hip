@@ -253,6 +253,25 @@ extern "C" int btsbot_op_ht_bn_bwd(const float* dy, int M, int n, const float* w
   return launch_ht_bn_bwd(dy, M, n, w, xhat, rstd, dw, db, (hipStream_t)stream);
 }
 
+extern "C" int btsbot_op_ht_bn_eval_fwd(const float* x, int M, int n, const float* w, const float* b, const float* run_mean,
+                                        const float* run_var, float* xhat, float* out, float* rstd, void* stream) {
+  const char* who = "op_ht_bn_eval_fwd";
+  if (x == nullptr || w == nullptr || b == nullptr || run_mean == nullptr || run_var == nullptr || xhat == nullptr ||
+      out == nullptr || rstd == nullptr)
+    return head_bad(who, "null pointer");
+  if (!fits(M, n)) return head_bad(who, "bad shape (M, n >= 1)");
+  return launch_ht_bn_eval_fwd(x, M, n, w, b, run_mean, run_var, xhat, out, rstd, (hipStream_t)stream);
+}
+
+extern "C" int btsbot_op_ht_bn_bwd_in(const float* dy, int M, int n, const float* w, const float* xhat, const float* rstd,
+                                      const float* sum_dy, const float* sum_dyx, float* dx, int eval, void* stream) {
+  const char* who = "op_ht_bn_bwd_in";
+  if (dy == nullptr || w == nullptr || xhat == nullptr || rstd == nullptr || dx == nullptr) return head_bad(who, "null pointer");
+  if (!eval && (sum_dy == nullptr || sum_dyx == nullptr)) return head_bad(who, "the batch-statistics form reads both column sums");
+  if (!fits(M, n)) return head_bad(who, "bad shape (M, n >= 1)");
+  return launch_ht_bn_bwd_in(dy, M, n, w, xhat, rstd, sum_dy, sum_dyx, dx, eval ? 1 : 0, (hipStream_t)stream);
+}
+
 extern "C" int btsbot_op_ht_feat_rows(const float* feat, int F, const float* hw, const float* hb, float* z, int ldz, int M,
                                       void* stream) {
   const char* who = "op_ht_feat_rows";

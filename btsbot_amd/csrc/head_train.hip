@@ -280,7 +280,42 @@ __global__ __launch_bounds__(256) void bn_train_bwd_kernel(const float* __restri
     dw[j] = sh[4] + sh[5] + sh[6] + sh[7];
   }
   (void)w;
-  (void)rstd;   // dx of the metadata INPUT is never needed (the inputs are data)
+  (void)rstd;   // dx of the metadata INPUT: bn_bwd_in_kernel, behind this one, on these two sums (only when asked for)
+}
+
+// BatchNorm1d, eval: out = (x - running_mean) * rsqrt(running_var + eps) * w + b.  xhat and rstd are kept like the
+// training form's, so the same backward kernels follow it.  Nothing is reduced over the batch: one thread per element.
+__global__ __launch_bounds__(256) void bn_eval_fwd_kernel(const float* __restrict__ x, int M, int n,
+                                                          const float* __restrict__ w, const float* __restrict__ b,
+                                                          const float* __restrict__ rm, const float* __restrict__ rv,
+                                                          float* __restrict__ xhat, float* __restrict__ out,
+                                                          float* __restrict__ rstd_out) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= M * n) return;
+  const int j = idx % n;
+  const float rstd = rsqrtf(rv[j] + BN_EPS);
+  const float xh = (x[idx] - rm[j]) * rstd;
+  xhat[idx] = xh;
+  out[idx] = xh * w[j] + b[j];
+  if (idx < n) rstd_out[j] = rstd;
+}
+
+// The BatchNorm's input gradient, behind bn_train_bwd_kernel (whose two column sums it reads in the batch form).
+// eval: the statistics are constants, dx = dy * w * rstd.  Batch statistics: the formula above that kernel.
+__global__ __launch_bounds__(256) void bn_bwd_in_kernel(const float* __restrict__ dy, int M, int n,
+                                                        const float* __restrict__ w, const float* __restrict__ xhat,
+                                                        const float* __restrict__ rstd, const float* __restrict__ sum_dy,
+                                                        const float* __restrict__ sum_dyx, float* __restrict__ dx, int eval) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= M * n) return;
+  const int j = idx % n;
+  const float g = w[j] * rstd[j];
+  if (eval) {
+    dx[idx] = dy[idx] * g;
+    return;
+  }
+  const float fm = (float)M;
+  dx[idx] = (g / fm) * (fm * dy[idx] - sum_dy[j] - xhat[idx] * sum_dyx[j]);
 }
 
 // rows of feat -> (optional LayerNorm) -> z[:, 0:F]
@@ -422,6 +457,20 @@ int launch_ht_bn_bwd(const float* dy, int M, int n, const float* w, const float*
   return BTSBOT_OK;
 }
 
+int launch_ht_bn_eval_fwd(const float* x, int M, int n, const float* w, const float* b, const float* run_mean,
+                          const float* run_var, float* xhat, float* out, float* rstd, hipStream_t st) {
+  hipLaunchKernelGGL(bn_eval_fwd_kernel, g1((long)M * n), dim3(256), 0, st, x, M, n, w, b, run_mean, run_var, xhat, out, rstd);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+int launch_ht_bn_bwd_in(const float* dy, int M, int n, const float* w, const float* xhat, const float* rstd,
+                        const float* sum_dy, const float* sum_dyx, float* dx, int eval, hipStream_t st) {
+  hipLaunchKernelGGL(bn_bwd_in_kernel, g1((long)M * n), dim3(256), 0, st, dy, M, n, w, xhat, rstd, sum_dy, sum_dyx, dx, eval);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
 int launch_ht_feat_rows(const float* feat, int F, const float* hw, const float* hb, float* z, int ldz, int M,
                         hipStream_t st) {
   hipLaunchKernelGGL(feat_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, st, feat, F, hw, hb, z, ldz, M);
@@ -505,15 +554,22 @@ static TrainPtrs carve(const btsbot_ctx* h, float* base, int M) {
 // The metadata branch's training forward (BatchNorm1d batch statistics -> fc1 -> act -> dropout -> fc2 (-> act)) into the
 // cache and columns F.. of the concatenated fusion input z.  It reads nothing of the image branch: btsbot_forward_train
 // queues it on the side stream, beside the backbone, and head_train_forward(meta_done = true) picks up behind a join.
+// eval: the eval form (running statistics from the mirror, dropout the identity, `master` and the mask unused).
 int head_train_meta_forward(btsbot_ctx* h, float* cache, const float* meta, int M, const uint8_t* meta_mask, float* master,
-                            hipStream_t st) {
+                            hipStream_t st, bool eval) {
   const btsbot_config& c = h->cfg;
   const float* m = h->mirror;
   TrainPtrs p = carve(h, cache, M);
   const int F = h->has_image ? c.dims[3] : 0;
   const int zd = h->comb_dims[0];
-  TRY(launch_ht_bn_fwd(meta, M, c.n_meta, m + h->bn_w, m + h->bn_b, master ? master + h->bn_rm : nullptr,
-                       master ? master + h->bn_rv : nullptr, p.xhat, p.x1, p.bn_rstd, st));
+  if (eval) {
+    TRY(launch_ht_bn_eval_fwd(meta, M, c.n_meta, m + h->bn_w, m + h->bn_b, m + h->bn_rm, m + h->bn_rv, p.xhat, p.x1,
+                              p.bn_rstd, st));
+    meta_mask = nullptr;
+  } else {
+    TRY(launch_ht_bn_fwd(meta, M, c.n_meta, m + h->bn_w, m + h->bn_b, master ? master + h->bn_rm : nullptr,
+                         master ? master + h->bn_rv : nullptr, p.xhat, p.x1, p.bn_rstd, st));
+  }
   const float ks1 = c.meta_dropout < 1.f ? 1.f / (1.f - c.meta_dropout) : 0.f;
   TRY(launch_ht_lin_fwd(p.x1, c.n_meta, IMG_F32(h, h->p_m1), m + h->m1_b, p.a1, p.h1, c.meta_fc1, M, c.meta_fc1, c.n_meta,
                         h->act, c.meta_dropout > 0.f ? meta_mask : nullptr, ks1, st));
@@ -524,7 +580,7 @@ int head_train_meta_forward(btsbot_ctx* h, float* cache, const float* meta, int 
 // Forward of the heads in training mode.  feat: [M][F] backbone features (already in the cache).
 int head_train_forward(btsbot_ctx* h, float* cache, const float* meta, float* logits,
                        float* scores, int M, const uint8_t* meta_mask, const uint8_t* comb_mask,
-                       float* master, hipStream_t st, bool meta_done) {
+                       float* master, hipStream_t st, bool meta_done, bool eval) {
   const btsbot_config& c = h->cfg;
   const float* m = h->mirror;
   TrainPtrs p = carve(h, cache, M);
@@ -534,7 +590,8 @@ int head_train_forward(btsbot_ctx* h, float* cache, const float* meta, float* lo
     TRY(launch_ht_feat_rows(p.feat, F, h->hn_w >= 0 ? m + h->hn_w : nullptr, h->hn_b >= 0 ? m + h->hn_b : nullptr, p.z, zd,
                             M, st));
   }
-  if (h->has_meta && !meta_done) TRY(head_train_meta_forward(h, cache, meta, M, meta_mask, master, st));
+  if (h->has_meta && !meta_done) TRY(head_train_meta_forward(h, cache, meta, M, meta_mask, master, st, eval));
+  if (eval) comb_mask = nullptr;   // dropout is the identity (scale 1): the activation kernels take no mask
   const float* in = p.z;
   int ldi = zd;
   const float ksc = c.comb_dropout < 1.f ? 1.f / (1.f - c.comb_dropout) : 0.f;
@@ -557,8 +614,11 @@ int head_train_forward(btsbot_ctx* h, float* cache, const float* meta, float* lo
 // backward read what that chain leaves behind (one gradient buffer per layer) and run on `sd` behind side_fork().
 int head_train_backward(btsbot_ctx* h, float* cache, const float* dlogits, float* grads, int M,
                         int need_meta, int need_image, float** dfeat_out,
-                        const uint8_t* meta_mask, const uint8_t* comb_mask, hipStream_t st) {
+                        const uint8_t* meta_mask, const uint8_t* comb_mask, hipStream_t st, float* d_meta, bool eval) {
   const btsbot_config& c = h->cfg;
+  // the metadata input's gradient hangs off the end of the metadata branch's backward: that chain then runs whether or
+  // not the caller asked for the branch's parameter gradients (which it writes on its way)
+  if (d_meta != nullptr) need_meta = 1;
   const float* m = h->mirror;
   TrainPtrs p = carve(h, cache, M);
   const int F = h->has_image ? c.dims[3] : 0;
@@ -614,6 +674,9 @@ int head_train_backward(btsbot_ctx* h, float* cache, const float* dlogits, float
     TRY(launch_ht_lin_bwd_w(dh1, p.x1, c.n_meta, grads + h->m1_w, grads + h->m1_b, M, c.meta_fc1, c.n_meta, sd));
     TRY(launch_ht_lin_bwd_in(dh1, m + h->m1_w, da2, c.n_meta, M, c.meta_fc1, c.n_meta, sd));
     TRY(launch_ht_bn_bwd(da2, M, c.n_meta, m + h->bn_w, p.xhat, p.bn_rstd, grads + h->bn_w, grads + h->bn_b, sd));
+    if (d_meta != nullptr)
+      TRY(launch_ht_bn_bwd_in(da2, M, c.n_meta, m + h->bn_w, p.xhat, p.bn_rstd, grads + h->bn_b, grads + h->bn_w, d_meta,
+                              eval ? 1 : 0, sd));
   }
   return BTSBOT_OK;
 }

@@ -241,6 +241,14 @@ int launch_ht_bn_fwd(const float* x, int M, int n, const float* w, const float* 
                      float* xhat, float* out, float* rstd, hipStream_t st);
 int launch_ht_bn_bwd(const float* dy, int M, int n, const float* w, const float* xhat, const float* rstd, float* dw,
                      float* db, hipStream_t st);
+// BatchNorm1d on running statistics: out = (x - rm) * rsqrt(rv + eps) * w + b; xhat and rstd [n] kept as by the above
+int launch_ht_bn_eval_fwd(const float* x, int M, int n, const float* w, const float* b, const float* run_mean,
+                          const float* run_var, float* xhat, float* out, float* rstd, hipStream_t st);
+// the BatchNorm's input gradient dx [M][n].  eval != 0: dx = dy w rstd (running statistics are constants); else the
+// batch-statistics form dx = (w rstd / M) (M dy - sum_dy - xhat sum_dyx) on the two column sums launch_ht_bn_bwd left
+// (its db and dw); they are not read in the eval form
+int launch_ht_bn_bwd_in(const float* dy, int M, int n, const float* w, const float* xhat, const float* rstd,
+                        const float* sum_dy, const float* sum_dyx, float* dx, int eval, hipStream_t st);
 // z [M][ldz] (columns 0 .. F) = feat [M][F], through the head LayerNorm where hw != nullptr
 int launch_ht_feat_rows(const float* feat, int F, const float* hw, const float* hb, float* z, int ldz, int M,
                         hipStream_t st);
@@ -336,6 +344,12 @@ int dw3_rows(int B);
 int launch_dw3ln_bwd(const float* dwb, const float* dxn, const float* g, const float* xin, const float* w, float* dy,
                      void* out16, int prec16, float* partials, int B, hipStream_t st, int nplanes = 1, size_t pstride = 0);
 int launch_dw3_rows(const float* partials, float* out, int nrows, hipStream_t st);
+
+// ---- stem_dgrad.hip
+// dimg [B][3][63][63] = the input gradient of the patch stem from dxn [B*225][C0] (fp32, behind the stem convolution) and
+// the filter w [C0][48] (fp32, state-dict layout); every element written once, rows / columns 60..62 as +0.0f.  C0 64 or 80
+int stem_dgrad_grid(int B);
+int launch_stem_dgrad(const float* dxn, const float* w, float* dimg, int B, int C0, hipStream_t st);
 
 // ---- mlp_bwd.hip
 // backward of a block's MLP as one kernel (mlp_bwd.hip): 16-bit modes, C in {64, 128}

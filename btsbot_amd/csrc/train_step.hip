@@ -49,13 +49,17 @@ extern "C" int btsbot_reserve_train(btsbot_handle h, int max_batch, int with_ima
   return BTSBOT_OK;
 }
 
-extern "C" int btsbot_forward_train(btsbot_handle h, const float* triplets, const float* meta,
-                                    float* logits, float* scores, int batch,
-                                    const uint8_t* meta_mask, const uint8_t* comb_mask,
-                                    float* master_arena, int keep_image_activations,
-                                    void* stream) {
+// The keeping forward in its two forms.  eval: BatchNorm1d on running statistics, dropout the identity, no arena
+// (btsbot_forward_keep_eval); otherwise btsbot_forward_train as it always was.
+static int forward_keep(btsbot_handle h, const float* triplets, const float* meta, float* logits, float* scores, int batch,
+                        const uint8_t* meta_mask, const uint8_t* comb_mask, float* master_arena, int keep_image_activations,
+                        void* stream, bool eval) {
   if (h == nullptr || logits == nullptr || batch < 1) {
     btsbot_set_error("forward_train: NULL handle/logits or empty batch");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (eval && h->is_maxvit) {
+    btsbot_set_error("forward_keep_eval: the MaxViT wirings have no eval-form keeping forward");
     return BTSBOT_ERR_INVALID_ARG;
   }
   if (!h->packed || h->ws == nullptr || h->tcache == nullptr || batch > h->tcache_batch) {
@@ -67,11 +71,11 @@ extern "C" int btsbot_forward_train(btsbot_handle h, const float* triplets, cons
     return BTSBOT_ERR_INVALID_ARG;
   }
   const btsbot_config& c = h->cfg;
-  if (h->has_meta && ((c.meta_dropout > 0.f && meta_mask == nullptr) || c.meta_dropout >= 1.f)) {
+  if (!eval && h->has_meta && ((c.meta_dropout > 0.f && meta_mask == nullptr) || c.meta_dropout >= 1.f)) {
     btsbot_set_error("forward_train: metadata dropout %.3f needs a keep-mask", c.meta_dropout);
     return BTSBOT_ERR_INVALID_ARG;
   }
-  if (h->n_comb > 1 && ((c.comb_dropout > 0.f && comb_mask == nullptr) || c.comb_dropout >= 1.f)) {
+  if (!eval && h->n_comb > 1 && ((c.comb_dropout > 0.f && comb_mask == nullptr) || c.comb_dropout >= 1.f)) {
     btsbot_set_error("forward_train: head dropout %.3f needs a keep-mask", c.comb_dropout);
     return BTSBOT_ERR_INVALID_ARG;
   }
@@ -103,7 +107,7 @@ extern "C" int btsbot_forward_train(btsbot_handle h, const float* triplets, cons
       hipStream_t sd = st;
       if (h->has_meta && h->side != nullptr && h->sched.meta_side) {
         TRY(side_fork(h, st, &sd));
-        TRY(head_train_meta_forward(h, h->tcache, meta, batch, meta_mask, master_arena, sd));
+        TRY(head_train_meta_forward(h, h->tcache, meta, batch, meta_mask, master_arena, sd, eval));
         meta_on_side = sd != st;
         h->meta_join_pending = meta_on_side;   // (cleared by the next side_join(): the forward's wait for the re-pack, as a rule)
         meta_done = true;
@@ -126,19 +130,48 @@ extern "C" int btsbot_forward_train(btsbot_handle h, const float* triplets, cons
     }
   }
   TRY(head_train_forward(h, h->tcache, meta, logits, scores, batch, meta_mask, comb_mask,
-                         master_arena, st, meta_done));
+                         master_arena, st, meta_done, eval));
   h->train_batch = batch;
-  h->t_meta_mask = meta_mask;
-  h->t_comb_mask = comb_mask;
+  h->t_meta_mask = eval ? nullptr : meta_mask;
+  h->t_comb_mask = eval ? nullptr : comb_mask;
+  h->t_eval = eval;
   return BTSBOT_OK;
+}
+
+extern "C" int btsbot_forward_train(btsbot_handle h, const float* triplets, const float* meta,
+                                    float* logits, float* scores, int batch,
+                                    const uint8_t* meta_mask, const uint8_t* comb_mask,
+                                    float* master_arena, int keep_image_activations,
+                                    void* stream) {
+  return forward_keep(h, triplets, meta, logits, scores, batch, meta_mask, comb_mask, master_arena, keep_image_activations,
+                      stream, false);
+}
+
+extern "C" int btsbot_forward_keep_eval(btsbot_handle h, const float* triplets, const float* meta, float* logits,
+                                        float* scores, int batch, int keep_image_activations, void* stream) {
+  return forward_keep(h, triplets, meta, logits, scores, batch, nullptr, nullptr, nullptr, keep_image_activations, stream, true);
 }
 
 extern "C" int btsbot_backward(btsbot_handle h, const float* dlogits, float* grad_arena,
                                int need_meta_grads, int need_image_grads, void* stream) {
+  return btsbot_backward_inputs(h, dlogits, grad_arena, need_meta_grads, need_image_grads, nullptr, nullptr, stream);
+}
+
+extern "C" int btsbot_backward_inputs(btsbot_handle h, const float* dlogits, float* grad_arena, int need_meta_grads,
+                                      int need_image_grads, float* d_triplets, float* d_meta, void* stream) {
   if (h == nullptr || dlogits == nullptr || grad_arena == nullptr) {
     btsbot_set_error("backward: NULL argument");
     return BTSBOT_ERR_INVALID_ARG;
   }
+  if ((d_triplets != nullptr || d_meta != nullptr) && h->is_maxvit) {
+    btsbot_set_error("backward_inputs: input gradients of the MaxViT wirings are not built");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if ((d_triplets != nullptr && !h->has_image) || (d_meta != nullptr && !h->has_meta)) {
+    btsbot_set_error("backward_inputs: this wiring has no %s input", d_triplets != nullptr && !h->has_image ? "image" : "metadata");
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (d_triplets != nullptr) need_image_grads = 1;   // the triplets' gradient is the end of the image branch's backward
   if (h->train_batch < 1) {
     btsbot_set_error("backward: no training-mode forward has been run on this handle");
     return BTSBOT_ERR_STATE;
@@ -186,13 +219,13 @@ extern "C" int btsbot_backward(btsbot_handle h, const float* dlogits, float* gra
   h->bucket_fine = h->bucket_waits_seen || !need_img || h->is_maxvit;
   float* dfeat = nullptr;
   TRY(head_train_backward(h, h->tcache, dlogits, grad_arena, h->train_batch, need_meta_grads,
-                          need_img, &dfeat, h->t_meta_mask, h->t_comb_mask, st));
+                          need_img, &dfeat, h->t_meta_mask, h->t_comb_mask, st, d_meta, h->t_eval));
   if (need_img) {
     if (h->is_maxvit) {
       TRY(side_join(h, st));
       TRY(maxvit_train_backward(h, h->t_img, dfeat, grad_arena, h->train_batch, st));   // records the bucket event
     } else {
-      TRY(backbone_train_backward(h, h->t_img, dfeat, grad_arena, h->train_batch, st));   // records the bucket events
+      TRY(backbone_train_backward(h, h->t_img, dfeat, grad_arena, h->train_batch, st, d_triplets));   // records the bucket events
     }
   } else {
     TRY(side_join(h, st));

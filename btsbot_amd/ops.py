@@ -579,6 +579,18 @@ def cnt_colsum_f32(rows, out):
     return out
 
 
+def cnt_stem_dgrad(dxn, w, out=None):
+    """The patch stem's input gradient: dxn [B, 15, 15, C0] (or [B*225, C0]), w [C0, 3, 4, 4] -> [B, 3, 63, 63], every
+    element written (rows / columns 60..62 as zeros).  C0 64 or 80."""
+    C0 = w.shape[0]
+    _f32t(w, (C0, 3, 4, 4)), _f32t(dxn)
+    assert dxn.shape[-1] == C0 and dxn.numel() % (225 * C0) == 0, tuple(dxn.shape)
+    B = dxn.numel() // (225 * C0)
+    out = _new(out, (B, 3, 63, 63), dxn)
+    _cnt("stem_dgrad", dxn, _p(dxn), _p(w), _p(out), B, C0)
+    return out.view(B, 3, 63, 63)
+
+
 # ---- the MLP half of the ConvNeXt 16-bit training step one launcher at a time (btsbot_op_cnt_*, cn_mlp_ops.hip).
 # Operand tensors are bf16 or f16 (that picks the kernels), biases / gamma / gradients fp32.  Every output is the
 # caller's tensor; include/btsbot_hip.h states which are added to and which written.
@@ -786,6 +798,27 @@ def ht_bn_bwd(dy, w, xhat, rstd, dw, db):
     _f32t(dy), _f32t(w, (n,)), _f32t(xhat, (M, n)), _f32t(rstd, (n,)), _f32t(dw, (n,)), _f32t(db, (n,))
     _ht("bn_bwd", dy, _p(dy), M, n, _p(w), _p(xhat), _p(rstd), _p(dw), _p(db))
     return dw, db
+
+
+def ht_bn_eval_fwd(x, w, b, run_mean, run_var, xhat, out, rstd):
+    """BatchNorm1d on running statistics: x, xhat, out [M, n]; w, b, run_mean, run_var, rstd [n]."""
+    M, n = x.shape
+    _f32t(x), _f32t(xhat, (M, n)), _f32t(out, (M, n))
+    for t in (w, b, run_mean, run_var, rstd):
+        _f32t(t, (n,))
+    _ht("bn_eval_fwd", x, _p(x), M, n, _p(w), _p(b), _p(run_mean), _p(run_var), _p(xhat), _p(out), _p(rstd))
+    return xhat, out, rstd
+
+
+def ht_bn_bwd_in(dy, w, xhat, rstd, dx, sum_dy=None, sum_dyx=None, eval=False):
+    """The BatchNorm's input gradient dx [M, n].  eval: dy * w * rstd; otherwise the batch-statistics form on the two
+    column sums ht_bn_bwd leaves (its db and dw)."""
+    M, n = dy.shape
+    _f32t(dy), _f32t(w, (n,)), _f32t(xhat, (M, n)), _f32t(rstd, (n,)), _f32t(dx, (M, n))
+    for t in (sum_dy, sum_dyx):
+        assert t is None or _f32t(t, (n,)) is t
+    _ht("bn_bwd_in", dy, _p(dy), M, n, _p(w), _p(xhat), _p(rstd), _p(sum_dy), _p(sum_dyx), _p(dx), int(bool(eval)))
+    return dx
 
 
 def ht_feat_rows(feat, z, hn=None):

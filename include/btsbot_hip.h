@@ -229,6 +229,31 @@ int btsbot_forward_train(btsbot_handle h, const float* triplets_nchw, const floa
 int btsbot_backward(btsbot_handle h, const float* dlogits, float* grad_arena, int need_meta_grads,
                     int need_image_grads, void* stream);
 
+/* Input gradients (saliency, SmoothGrad, integrated gradients on a deployed model): what
+ * image_input.requires_grad_() ... logits.sum().backward() leaves on the inputs of the stock nn.Module classes.
+ * ConvNeXt wirings and BTSBOT_UM_NN; the MaxViT wirings are refused (BTSBOT_ERR_INVALID_ARG).
+ * btsbot_forward_keep_eval: btsbot_forward_train in EVAL form -- the metadata BatchNorm1d uses its running statistics
+ * (read from the packed mirror: pack first, as for btsbot_forward), dropout is the identity with scale 1 (no masks),
+ * nothing in any arena is written.  Activations are kept exactly as by btsbot_forward_train (same cache, same
+ * btsbot_reserve_train, keep_image_activations as there), so btsbot_backward / btsbot_backward_inputs may follow and
+ * differentiate THIS forward: the BatchNorm backward then treats the statistics as constants and an alert's gradient
+ * does not depend on the other alerts of the call.  In the 16-bit modes the image branch runs the training-form
+ * kernels: the logits agree with btsbot_forward's to the mode's parity tolerance, not to the bit.
+ * btsbot_backward_inputs: btsbot_backward that also returns d(loss)/d(input): d_triplets [batch][3][63][63] fp32 (the
+ * layout of triplets_nchw) and d_meta [batch][n_meta] fp32, device buffers, either may be NULL; with both NULL this IS
+ * btsbot_backward (same launches, order and streams).  Every element of both is written exactly once (rows / columns
+ * 60..62 of the triplets, which the 4x4 / stride-4 stem never reads, as +0.0f): no clearing by the caller, no atomic on the
+ * chain that produces them -- two identical calls give identical bits.  Both are ordered on `stream` like every
+ * gradient.  A non-NULL d_triplets implies need_image_grads (BTSBOT_ERR_STATE unless the forward kept the image
+ * activations); a non-NULL d_meta runs the metadata branch's backward whatever need_meta_grads says.  Parameter
+ * gradients are still written to grad_arena on the way.  BTSBOT_ERR_INVALID_ARG for a pointer whose input the wiring
+ * does not have.  Behind btsbot_forward_train the gradients are those of the batch-statistics form (the metadata rows
+ * couple through the batch mean and variance). */
+int btsbot_forward_keep_eval(btsbot_handle h, const float* triplets_nchw, const float* meta, float* logits,
+                             float* scores, int batch, int keep_image_activations, void* stream);
+int btsbot_backward_inputs(btsbot_handle h, const float* dlogits, float* grad_arena, int need_meta_grads,
+                           int need_image_grads, float* d_triplets, float* d_meta, void* stream);
+
 /* Replaces the gradient reduction of torch.nn.DataParallel (train.py:238-240; SURVEY.md section 8b's
  * btsbot_allreduce_grads) -- split in two, because the communicator belongs to the host's process group
  * (torch.distributed over RCCL), not to this library: the library says WHICH parts of the gradient arena
@@ -539,6 +564,10 @@ int btsbot_op_cnt_dw_plain(const float* x, const float* w, int flip, const float
 int btsbot_op_cnt_dw_wgrad(const float* x, const float* dd, float* dw, float* dbias, int B, int HW, int C, void* stream);
 /* out [N] += the column sums of in [M][N] (fp32): what folds partial rows into the arena. */
 int btsbot_op_cnt_colsum_f32(const float* in, float* out, int M, int N, void* stream);
+/* The patch stem's input gradient (stem_dgrad.hip), what btsbot_backward_inputs runs last for d_triplets:
+ * dimg [B][3][63][63] (written, every element once; rows / columns 60..62 = +0.0f) from dxn [B*225][C0] and the filter
+ * w [C0][3][4][4], both fp32 and 16-byte aligned; C0 = 64 or 80. */
+int btsbot_op_cnt_stem_dgrad(const float* dxn, const float* w, float* dimg, int B, int C0, void* stream);
 
 /* The MLP half of the ConvNeXt 16-bit TRAINING step (mlp_bwd.hip, s2mlp_bwd.hip, fused_mlp.hip, fc2_grads_kernel of
  * ln_dw_bwd.hip) one launcher at a time (cn_mlp_ops.hip).  prec = BTSBOT_BF16 or BTSBOT_F16 (the "operand type"); biases,
@@ -613,6 +642,10 @@ int btsbot_op_head(int prec, const float* feat, int feat_dim, const float* hn_w,
  *   bn_fwd:     BatchNorm1d on the batch statistics of x [M][n]: xhat, out [M][n], rstd [n] written; run_mean / run_var
  *               [n] updated (momentum 0.1, unbiased variance) or both NULL
  *   bn_bwd:     dw [n] = sum dy xhat, db [n] = sum dy
+ *   bn_eval_fwd: BatchNorm1d on the running statistics run_mean / run_var [n] (read only): xhat, out, rstd as bn_fwd
+ *   bn_bwd_in:  the BatchNorm's input gradient dx [M][n] (written).  eval != 0: dx = dy w rstd; eval == 0: the batch-
+ *               statistics form (w rstd / M) (M dy - sum_dy - xhat sum_dyx) on bn_bwd's two sums (db, dw), which the eval
+ *               form does not read (they may be NULL there)
  *   feat_rows:  z [M][ldz] (columns 0 .. F) = feat [M][F], through LayerNorm (eps 1e-6) where hw / hb are given
  *   logits:     logits [M] = in [M]; scores = sigmoid (NULL: not written)
  *   copy_cols:  dst [M][ldd] (columns 0 .. cols) = src [M][lds] */
@@ -629,6 +662,10 @@ int btsbot_op_ht_bn_fwd(const float* x, int M, int n, const float* w, const floa
                         float* xhat, float* out, float* rstd, void* stream);
 int btsbot_op_ht_bn_bwd(const float* dy, int M, int n, const float* w, const float* xhat, const float* rstd, float* dw,
                         float* db, void* stream);
+int btsbot_op_ht_bn_eval_fwd(const float* x, int M, int n, const float* w, const float* b, const float* run_mean,
+                             const float* run_var, float* xhat, float* out, float* rstd, void* stream);
+int btsbot_op_ht_bn_bwd_in(const float* dy, int M, int n, const float* w, const float* xhat, const float* rstd,
+                           const float* sum_dy, const float* sum_dyx, float* dx, int eval, void* stream);
 int btsbot_op_ht_feat_rows(const float* feat, int F, const float* hw, const float* hb, float* z, int ldz, int M,
                            void* stream);
 int btsbot_op_ht_logits(const float* in, float* logits, float* scores, int M, void* stream);

@@ -46,6 +46,8 @@ SYMBOLS = [
     "btsbot_op_head16_supported", "btsbot_op_head",
     "btsbot_op_cn_stage3_supported", "btsbot_op_cn_stage3_hfrag_bytes", "btsbot_op_cn_stage3", "btsbot_op_cn_pack_s3",
     "btsbot_op_cn_fp8_scale",
+    "btsbot_op_cn_stage2_supported", "btsbot_op_cn_stage2_alerts", "btsbot_op_cn_stage2", "btsbot_op_cn_stage2_rows",
+    "btsbot_op_cn_pack_s2p",
     "btsbot_op_ht_lin_is_wide", "btsbot_op_ht_lin_fwd", "btsbot_op_ht_act_bwd", "btsbot_op_ht_lin_bwd_in",
     "btsbot_op_ht_lin_bwd_w_kind", "btsbot_op_ht_lin_bwd_w", "btsbot_op_ht_bn_fwd", "btsbot_op_ht_bn_bwd",
     "btsbot_op_ht_feat_rows", "btsbot_op_ht_logits", "btsbot_op_ht_copy_cols",
@@ -254,6 +256,16 @@ def lib() -> C.CDLL:
     L.btsbot_op_cn_stage3.argtypes = [i32] * 4 + [vp, i32] + [C.POINTER(vp)] * 9 + [vp]
     L.btsbot_op_cn_pack_s3.restype = i32
     L.btsbot_op_cn_pack_s3.argtypes = [i32, vp, vp, i32, i32, i32, vp, vp, vp]
+    L.btsbot_op_cn_stage2_supported.restype = i32
+    L.btsbot_op_cn_stage2_supported.argtypes = [i32] * 3
+    L.btsbot_op_cn_stage2_alerts.restype = i32
+    L.btsbot_op_cn_stage2_alerts.argtypes = [i32] * 2
+    L.btsbot_op_cn_stage2.restype = i32
+    L.btsbot_op_cn_stage2.argtypes = [i32] * 4 + [vp, i32] + [C.POINTER(vp)] * 9 + [vp] * 6 + [C.POINTER(vp)] * 4 + [vp, vp]
+    L.btsbot_op_cn_stage2_rows.restype = i32
+    L.btsbot_op_cn_stage2_rows.argtypes = [i32, vp, i64] + [vp] * 8
+    L.btsbot_op_cn_pack_s2p.restype = i32
+    L.btsbot_op_cn_pack_s2p.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.btsbot_op_cn_fp8_scale.restype = i32
     L.btsbot_op_cn_fp8_scale.argtypes = [vp, vp, i64, i32, vp, vp]
     for name, args in (("lin_is_wide", [i32] * 4),

@@ -3,6 +3,7 @@
 #include <string.h>
 
 #include "maxvit.h"
+#include "stage2p.h"
 #include "stage3.h"
 
 extern "C" int btsbot_op_gemm(int prec, int epi, const void* X, const void* W, const float* bias,
@@ -531,4 +532,163 @@ extern "C" int btsbot_op_cn_fp8_scale(const float* src, const float* rowscale, i
     return BTSBOT_ERR_INVALID_ARG;
   }
   return launch_fp8_scale(src, rowscale, (long)n, K, scale, (hipStream_t)stream);
+}
+
+// ---- ConvNeXt stage 2 (+ stages[3].downsample) alone: stage2p_kernel in every form it is launched in, on the caller's
+// buffers.  Parameters in state-dict layout (fp32); the operand images are built in a stream-ordered scratch by the calls
+// pack.hip makes for a stage-2 block and the downsample behind it (stage_args.hip's pointers into them).
+extern "C" int btsbot_op_cn_stage2_supported(int prec, int cw, int depth) { return stage2p_supported(prec, cw, 2 * cw, depth) ? 1 : 0; }
+
+extern "C" int btsbot_op_cn_stage2_alerts(int B, int hint) {
+  if (B < 0 || (hint != 0 && hint != 4 && hint != 5 && hint != 7)) {
+    btsbot_set_error("op_cn_stage2_alerts: bad argument B=%d hint=%d (hint 0, 4, 5 or 7)", B, hint);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  return stage2p_alerts_per_workgroup(B, hint);
+}
+
+extern "C" int btsbot_op_cn_stage2(int prec, int cw, int depth, int alerts_hint, const float* x_in, int B,
+                                   const float* const* dw_w, const float* const* dw_b, const float* const* ln_w,
+                                   const float* const* ln_b, const float* const* fc1_w, const float* const* fc1_b,
+                                   const float* const* fc2_w, const float* const* fc2_b, const float* const* gamma,
+                                   const float* ds_ln_w, const float* ds_ln_b, const float* ds_w, const float* ds_b, float* out,
+                                   float* tap_stage, float* const* keep_xin, void* const* keep_xn, void* const* keep_a,
+                                   void* const* keep_hh, void* ds_patches, void* stream) {
+  const char* who = "op_cn_stage2";
+  if (!stage2p_supported(prec, cw, 2 * cw, depth)) {
+    btsbot_set_error("op_cn_stage2: unsupported (prec %d, width %d, depth %d): BTSBOT_BF16 / F16 / FP8 / F16X2 at 256 channels, "
+                     "BF16 / F16 at 320, 1 to %d blocks", prec, cw, depth, S2P_MAX_DEPTH);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (alerts_hint != 0 && alerts_hint != 4 && alerts_hint != 5 && alerts_hint != 7)
+    return s3_op_bad(who, "alerts_hint must be 0, 4, 5 or 7");
+  if (B < 0) return s3_op_bad(who, "negative alert count");
+  const int nkeep = (keep_xin != nullptr) + (keep_xn != nullptr) + (keep_a != nullptr) + (keep_hh != nullptr) + (ds_patches != nullptr);
+  if (nkeep != 0 && nkeep != 5) return s3_op_bad(who, "the keep buffers (xin, xn, a, hh, ds_patches) are given all or none");
+  const bool train = nkeep == 5;
+  if (train && (cw != 256 || (prec != BTSBOT_BF16 && prec != BTSBOT_F16)))
+    return s3_op_bad(who, "the keeping form runs in the bf16 / f16 modes at 256 channels");
+  if (train && tap_stage == nullptr) return s3_op_bad(who, "the keeping form needs tap_stage (the stage output)");
+  const float* const* lists[9] = {dw_w, dw_b, ln_w, ln_b, fc1_w, fc1_b, fc2_w, fc2_b, gamma};
+  if (x_in == nullptr || out == nullptr || ds_ln_w == nullptr || ds_ln_b == nullptr || ds_w == nullptr || ds_b == nullptr)
+    return s3_op_bad(who, "null pointer");
+  for (const float* const* l : lists) {
+    if (l == nullptr) return s3_op_bad(who, "null pointer");
+    for (int j = 0; j < depth; ++j)
+      if (l[j] == nullptr) return s3_op_bad(who, "null pointer");
+  }
+  if (train)
+    for (int j = 0; j < depth; ++j)
+      if (keep_xin[j] == nullptr || keep_xn[j] == nullptr || keep_a[j] == nullptr || keep_hh[j] == nullptr)
+        return s3_op_bad(who, "null pointer");
+  if (!s3_al16(x_in) || !s3_al16(out) || !s3_al16(tap_stage)) return s3_op_bad(who, "x_in, out and tap_stage must be 16-byte aligned");
+  if (!s3_al16(ds_ln_w) || !s3_al16(ds_ln_b) || !s3_al16(ds_b)) return s3_op_bad(who, "the parameter vectors must be 16-byte aligned");
+  for (int j = 0; j < depth; ++j)
+    if (!s3_al16(dw_b[j]) || !s3_al16(ln_w[j]) || !s3_al16(ln_b[j]) || !s3_al16(fc1_b[j]) || !s3_al16(fc2_b[j]) ||
+        !s3_al16(gamma[j]))
+      return s3_op_bad(who, "the parameter vectors must be 16-byte aligned");
+  if (train) {
+    if (!s3_al16(ds_patches)) return s3_op_bad(who, "the keep buffers must be 16-byte aligned");
+    for (int j = 0; j < depth; ++j)
+      if (!s3_al16(keep_xin[j]) || !s3_al16(keep_xn[j]) || !s3_al16(keep_a[j]) || !s3_al16(keep_hh[j]))
+        return s3_op_bad(who, "the keep buffers must be 16-byte aligned");
+  }
+  if (B == 0) return BTSBOT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int precd = prec == BTSBOT_FP8 ? BTSBOT_BF16 : prec;   // (prec_down3: the downsample keeps 16-bit operands)
+  const size_t wb = (size_t)4 * cw * cw * s3_esz(prec), wdb = (size_t)8 * cw * cw * s3_esz(precd);
+  StreamScratch sc(st, who);   // per block: tap-major taps | fc1 fragments | gamma * fc2 fragments | scales; then the downsample's
+  size_t o_dw[S2P_MAX_DEPTH], o_w1[S2P_MAX_DEPTH], o_w2[S2P_MAX_DEPTH], o_sc[S2P_MAX_DEPTH];
+  for (int j = 0; j < depth; ++j) {
+    o_dw[j] = sc.reserve((size_t)49 * cw * 4);
+    o_w1[j] = sc.reserve(wb);
+    o_w2[j] = sc.reserve(wb);
+    o_sc[j] = sc.reserve(64);
+  }
+  const size_t o_ds = sc.reserve(wdb);
+  TRY(sc.alloc());
+  Stage2pArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x_in = x_in;
+  a.depth = depth;
+  a.ds_lnw = ds_ln_w;
+  a.ds_lnb = ds_ln_b;
+  a.ds_wp = sc.at(o_ds);
+  a.ds_b = ds_b;
+  a.out = out;
+  a.tap_stage = tap_stage;
+  a.B = B;
+  a.cw = cw;
+  a.alerts_hint = alerts_hint;
+  a.train = train ? 1 : 0;
+  a.ds_patches = ds_patches;
+  for (int j = 0; j < depth; ++j) {
+    float* scales = sc.at<float>(o_sc[j]);
+    TRY(launch_transpose_f32(dw_w[j], sc.at<float>(o_dw[j]), cw, 49, st));   // (pack.hip's p_dw: tap-major [49][C])
+    TRY(launch_pack_s2p(prec, fc1_w[j], nullptr, sc.at(o_w1[j]), 4 * cw, cw, 0, 0, scales, st));
+    TRY(launch_pack_s2p(prec, fc2_w[j], gamma[j], sc.at(o_w2[j]), cw, 4 * cw, 0, 0, scales + 2, st));
+    Stage2pBlk& k = a.blk[j];
+    k.dw_w = sc.at<float>(o_dw[j]);
+    k.dw_b = dw_b[j];
+    k.ln_w = ln_w[j];
+    k.ln_b = ln_b[j];
+    k.b1 = fc1_b[j];
+    k.b2 = fc2_b[j];
+    k.gamma = gamma[j];
+    k.w1p = sc.at(o_w1[j]);
+    k.w2p = sc.at(o_w2[j]);
+    k.scales = prec == BTSBOT_FP8 ? scales : nullptr;
+    if (train) a.keep[j] = Stage2pKeep{keep_xin[j], keep_xn[j], keep_a[j], keep_hh[j]};
+  }
+  TRY(launch_pack_s2p(precd, ds_w, nullptr, sc.at(o_ds), 2 * cw, 4 * cw, 1, cw, nullptr, st));
+  return launch_stage2p(prec, a, st);
+}
+
+extern "C" int btsbot_op_cn_stage2_rows(int prec, float* x, int64_t rows, const float* ln_w, const float* ln_b,
+                                        const float* fc1_w, const float* fc1_b, const float* fc2_w, const float* fc2_b,
+                                        const float* gamma, void* stream) {
+  const char* who = "op_cn_stage2_rows";
+  if (!stage2p_rows_supported(prec, 256)) return s3_op_bad(who, "unsupported: the row-tile form runs in the bf16 / f16 modes");
+  if (rows < 0 || rows > 0x7fffffffL / 256) return s3_op_bad(who, "bad row count");
+  if (x == nullptr || ln_w == nullptr || ln_b == nullptr || fc1_w == nullptr || fc1_b == nullptr || fc2_w == nullptr ||
+      fc2_b == nullptr || gamma == nullptr)
+    return s3_op_bad(who, "null pointer");
+  if (!s3_al16(x)) return s3_op_bad(who, "x must be 16-byte aligned");
+  if (!s3_al16(ln_w) || !s3_al16(ln_b) || !s3_al16(fc1_b) || !s3_al16(fc2_b) || !s3_al16(gamma))
+    return s3_op_bad(who, "the parameter vectors must be 16-byte aligned");
+  if (rows == 0) return BTSBOT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int c = 256;
+  const size_t wb = (size_t)4 * c * c * 2;
+  StreamScratch sc(st, who);   // fc1 fragments | gamma * fc2 fragments
+  const size_t o_w1 = sc.reserve(wb), o_w2 = sc.reserve(wb);
+  TRY(sc.alloc());
+  TRY(launch_pack_s2p(prec, fc1_w, nullptr, sc.at(o_w1), 4 * c, c, 0, 0, nullptr, st));
+  TRY(launch_pack_s2p(prec, fc2_w, gamma, sc.at(o_w2), c, 4 * c, 0, 0, nullptr, st));
+  Stage2pBlk sb;
+  memset(&sb, 0, sizeof(sb));
+  sb.ln_w = ln_w;
+  sb.ln_b = ln_b;
+  sb.b1 = fc1_b;
+  sb.b2 = fc2_b;
+  sb.gamma = gamma;
+  sb.w1p = sc.at(o_w1);
+  sb.w2p = sc.at(o_w2);
+  return launch_stage2p_rows(prec, x, (long)rows, sb, st);
+}
+
+extern "C" int btsbot_op_cn_pack_s2p(int prec, const float* src, const float* rowscale, int rows, int K, int reorder_down,
+                                     int cin, void* dst, float* scale, void* stream) {
+  const char* who = "op_cn_pack_s2p";
+  if (src == nullptr || dst == nullptr) return s3_op_bad(who, "null pointer");
+  if (!s3_frag_prec(prec)) return s3_op_bad(who, "precision must be bf16, f16, fp8 or f16x2");
+  if (prec == BTSBOT_FP8 && scale == nullptr) return s3_op_bad(who, "the fp8 mode needs a scale slot");
+  const int kstep = prec == BTSBOT_FP8 ? 128 : 32;
+  if (rows < 16 || rows % 16 != 0 || K < kstep || K % kstep != 0 || (long)rows * K >= (1L << 31)) {
+    btsbot_set_error("op_cn_pack_s2p: bad shape rows=%d K=%d (rows a multiple of 16, K of %d)", rows, K, kstep);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if (reorder_down != 0 && reorder_down != 1) return s3_op_bad(who, "reorder_down must be 0 or 1");
+  if (reorder_down && (cin < 1 || K != 4 * cin)) return s3_op_bad(who, "reorder_down: K must be 4 cin");
+  return launch_pack_s2p(prec, src, rowscale, dst, rows, K, reorder_down, cin, scale, (hipStream_t)stream);
 }

@@ -136,6 +136,8 @@ int launch_pack_s1par(int prec, const float* taps, const float* dw_b, const floa
 struct Stage2pArgs;
 bool stage2p_supported(int prec, int c2, int c3, int depth);
 int launch_stage2p(int prec, const Stage2pArgs& a, hipStream_t st);
+// alerts resident per workgroup (4, 5 or 7) of a call of B alerts with Stage2pArgs::alerts_hint = hint (256 channels)
+int stage2p_alerts_per_workgroup(int B, int hint);
 // the kernel's row-tile form (stage2p.hip, ROWS): x [rows][256] fp32 += W2 gelu(W1 LN(x) + b1) + b2 in place -- the MLP half
 // of a MaxViT partition-attention layer at 256 channels.  blk: ln_w / ln_b = norm2, b1 / b2 the Linear biases, gamma = ones,
 // w1p / w2p = launch_pack_s2p fragments of fc1 [1024][256] / fc2 [256][1024]; dw_* unused

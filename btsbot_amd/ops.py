@@ -904,3 +904,70 @@ def cn_fp8_scale(src, rowscale=None, K=1, scale=None):
         _lib.check(_lib.lib().btsbot_op_cn_fp8_scale(_p(src), _p(rowscale), src.numel(), K, _p(scale), _stream(src)),
                    "btsbot_op_cn_fp8_scale")
     return scale
+
+
+# ---- ConvNeXt stage 2 alone (btsbot_op_cn_stage2*, infer_ops.hip / stage2p.hip).  As above: the checks are the library's.
+S2_DOWN = ("ds_ln_w", "ds_ln_b", "ds_w", "ds_b")
+S2_KEEP = ("xin", "xn", "a", "hh")
+
+
+def cn_stage2_supported(precision, cw, depth):
+    """stage2p.hip's own predicate (the stage's width cw, the next stage's being 2 cw)."""
+    return bool(_lib.lib().btsbot_op_cn_stage2_supported(_lib.PRECISION[precision], cw, depth))
+
+
+def cn_stage2_alerts(B, hint=0):
+    """Alerts resident per workgroup (4, 5 or 7) that a 256-channel call of B alerts with this hint runs with."""
+    return _lib.check(_lib.lib().btsbot_op_cn_stage2_alerts(B, hint), "btsbot_op_cn_stage2_alerts")
+
+
+def cn_stage2(precision, x_in, blocks, down, out, tap_stage=None, alerts_hint=0, keep=None, ds_patches=None, B=None, cw=None):
+    """`len(blocks)` ConvNeXt blocks on 3x3 maps x_in [B, 9, cw] (fp32) and the downsample behind them: out [B, 2 cw],
+    tap_stage [B, 9, cw] (optional) the stage output.  blocks: as cn_stage3; down: a dict of S2_DOWN (ds_w [2 cw, cw, 2, 2]).
+    keep: None, or a dict of S2_KEEP, each a list of one tensor per block (a list or a tensor may be None: the refusals),
+    with ds_patches: the keeping form, every buffer with room for B + 9 alerts.  B / cw default to x_in's shape."""
+    if B is None:
+        B, _, cw = x_in.shape
+    lists = [(C.c_void_p * max(len(blocks), 1))(*[(b[k].data_ptr() if b[k] is not None else 0) for b in blocks])
+             for k in S3_PARAMS]
+    if keep is None:
+        klists = [None] * 4
+    else:
+        klists = [None if keep[k] is None else
+                  (C.c_void_p * max(len(keep[k]), 1))(*[(t.data_ptr() if t is not None else 0) for t in keep[k]]) for k in S2_KEEP]
+    on = out if out is not None else x_in
+    with torch.cuda.device(on.device):
+        _lib.check(_lib.lib().btsbot_op_cn_stage2(_lib.PRECISION[precision], cw, len(blocks), alerts_hint, _p(x_in), B, *lists,
+                                                  *[_p(down[k]) for k in S2_DOWN], _p(out), _p(tap_stage), *klists,
+                                                  _p(ds_patches), _stream(on)), "btsbot_op_cn_stage2")
+    return out
+
+
+def cn_stage2_rows(precision, x, block, rows=None):
+    """stage2p's row-tile form in place on x [rows, 256] (fp32): x += gamma (fc2 gelu(fc1 LN(x) + fc1_b) + fc2_b); block: a
+    dict with ln_w, ln_b, fc1_w, fc1_b, fc2_w, fc2_b, gamma."""
+    if rows is None:
+        rows = x.shape[0]
+    on = x if x is not None else block["ln_w"]
+    with torch.cuda.device(on.device):
+        _lib.check(_lib.lib().btsbot_op_cn_stage2_rows(_lib.PRECISION[precision], _p(x), rows,
+                                                       *[_p(block[k]) for k in S3_PARAMS[2:]], _stream(on)),
+                   "btsbot_op_cn_stage2_rows")
+    return x
+
+
+def cn_pack_s2p(precision, src, rowscale=None, reorder_down=False, cin=0, dst=None, scale=None, rows=None, K=None):
+    """stage 2's fragment packer: src [rows, K] fp32 (x rowscale [rows]; reorder_down: a downsample filter [rows, cin, 2, 2],
+    K = 4 cin) -> dst, a uint8 tensor of rows * K operand values (made when None); fp8: scale [2] fp32 receives {S, 1/S}
+    (made when None).  Returns (dst, scale)."""
+    if rows is None:
+        rows = src.shape[0]
+        K = src.numel() // rows
+    if dst is None:
+        dst = torch.empty(rows * K * _S3_ESZ[precision], dtype=torch.uint8, device=src.device)
+    if scale is None and precision == "fp8":
+        scale = torch.empty(2, dtype=torch.float32, device=src.device)
+    with torch.cuda.device(dst.device):
+        _lib.check(_lib.lib().btsbot_op_cn_pack_s2p(_lib.PRECISION[precision], _p(src), _p(rowscale), rows, K, int(reorder_down),
+                                                    cin, _p(dst), _p(scale), _stream(dst)), "btsbot_op_cn_pack_s2p")
+    return dst, scale

@@ -697,6 +697,43 @@ int btsbot_op_cn_pack_s3(int prec, const float* src, const float* rowscale, int 
                          float* scale, void* stream);
 int btsbot_op_cn_fp8_scale(const float* src, const float* rowscale, int64_t n, int K, float* scale, void* stream);
 
+/* ConvNeXt stage 2 alone (stage2p.hip: 3x3 maps, one persistent launch), for the per-kernel tests (infer_ops.hip).
+ * btsbot_op_cn_stage2 runs `depth` blocks
+ *     x += gamma * fc2( GELU( fc1( LN( dwconv7x7(x) + dw_b ) ) ) )
+ * on x_in [B][9][cw] (fp32, pixel-major 3x3 maps) and then stages[3].downsample (LayerNorm + conv 2x2 stride 2 on pixels
+ * 0, 1, 3, 4): out [B][2 cw]; tap_stage (optional) [B][9][cw] receives the stage output in front of the downsample.  The
+ * nine per-block parameters are host arrays of `depth` device pointers as in btsbot_op_cn_stage3; ds_ln_w / ds_ln_b [cw],
+ * ds_w [2 cw][cw][2][2], ds_b [2 cw].  The operand images (tap-major taps, fc1 / gamma * fc2 fragments, fp8 scales, the
+ * downsample's fragments -- bf16 in the fp8 mode) are built in the call's scratch by the launchers the handle uses.
+ * alerts_hint: 0 (the library picks) or 4 / 5 / 7 alerts per workgroup (320 channels always run 5, BTSBOT_F16X2 runs 5 for
+ * 7); btsbot_op_cn_stage2_alerts(B, hint) returns the library's choice at 256 channels.
+ * The keeping form (the training forward) runs when keep_xin / keep_xn / keep_a / keep_hh (host arrays of `depth` device
+ * pointers) and ds_patches are given, all or none: per block the input map fp32 [(B + 9) * 9][cw], the LayerNorm output
+ * [(B + 9) * 9][cw], the rounded fc1 pre-activation and its GELU [(B + 9) * 9][4 cw] in the operand type, and ds_patches
+ * [(B + 9)][4 cw]; every buffer has room for B + 9 alerts (the kernel stores padding rows unconditionally).
+ * BTSBOT_ERR_INVALID_ARG with a message, nothing launched: what btsbot_op_cn_stage2_supported() refuses (BF16 / F16 / FP8 /
+ * F16X2 at 256 channels, BF16 / F16 at 320, depth 1..8), another alerts_hint, the keeping form outside BF16 / F16 at 256
+ * channels or without tap_stage, keep buffers given in part, a null pointer, x_in / out / tap_stage / a parameter vector /
+ * a keep buffer not 16-byte aligned, B < 0.  B == 0: BTSBOT_OK, nothing touched.
+ * btsbot_op_cn_stage2_rows: the kernel's row-tile form (the MLP half of a MaxViT partition layer at 256 channels, BF16 /
+ *   F16): x [rows][256] += gamma * (fc2 GELU(fc1 LN(x) + fc1_b) + fc2_b) in place, 64 rows per workgroup.
+ * btsbot_op_cn_pack_s2p: fp32 src [rows][K] (x rowscale[row], or NULL) -> stage 2's A fragments in dst (rows * K values of
+ *   2 / 2 / 1 / 4 bytes in BF16 / F16 / FP8 / F16X2; rows a multiple of 16, K of 32 -- 128 in fp8); reorder_down: src is a
+ *   downsample filter [rows][cin][2][2] read as k = (2 ky + kx) cin + c, K = 4 cin.  fp8: scale [2] (device) receives
+ *   {S, 1/S} and the values are packed times S. */
+int btsbot_op_cn_stage2_supported(int prec, int cw, int depth);
+int btsbot_op_cn_stage2_alerts(int B, int hint);
+int btsbot_op_cn_stage2(int prec, int cw, int depth, int alerts_hint, const float* x_in, int B, const float* const* dw_w,
+                        const float* const* dw_b, const float* const* ln_w, const float* const* ln_b,
+                        const float* const* fc1_w, const float* const* fc1_b, const float* const* fc2_w,
+                        const float* const* fc2_b, const float* const* gamma, const float* ds_ln_w, const float* ds_ln_b,
+                        const float* ds_w, const float* ds_b, float* out, float* tap_stage, float* const* keep_xin,
+                        void* const* keep_xn, void* const* keep_a, void* const* keep_hh, void* ds_patches, void* stream);
+int btsbot_op_cn_stage2_rows(int prec, float* x, int64_t rows, const float* ln_w, const float* ln_b, const float* fc1_w,
+                             const float* fc1_b, const float* fc2_w, const float* fc2_b, const float* gamma, void* stream);
+int btsbot_op_cn_pack_s2p(int prec, const float* src, const float* rowscale, int rows, int K, int reorder_down, int cin,
+                          void* dst, float* scale, void* stream);
+
 /* Measurement aid with no reference counterpart (bench.py's roofline leg): when on, every kernel
  * launch of forward() is bracketed by two HIP events recorded on the launch stream;
  * profile_collect() waits for them and returns, per kernel family (profile_category_name), the

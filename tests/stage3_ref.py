@@ -167,17 +167,18 @@ def dense_blocks(C, gammas, seed):
     return out
 
 
-def spot_maps(C):
+def spot_maps(C, step=333):
     """-> (c1 [4C], c2 [4C] (-1: none), hid [C][4]): the channels hidden unit h reads, the hidden units channel c reads.
     3, 7 and 333 are odd and no multiple of 5: h -> 3 h + 1 and h -> 7 h + 5 pass through every channel four times, and
     n -> 333 n + 17 is a bijection of the 4C hidden units.  A channel's four are 333 apart: more than a K slice (256 / 320),
-    three steps less than seven slices, and 13 mod 16 and mod 64 -- four slices, four k positions"""
+    three steps less than seven slices, and 13 mod 16 and mod 64 -- four slices, four k positions.  step: another odd
+    multiplier prime to 4C in place of 333 (stage2_ref.py: chunks of 128 hidden units)"""
     H = 4 * C
     h = torch.arange(H)
     c1 = (3 * h + 1) % C
     c2 = (7 * h + 5) % C
     c2 = torch.where((h % 2 == 1) & (c2 != c1), c2, torch.full_like(c2, -1))
-    hid = ((333 * torch.arange(H) + 17) % H).view(C, 4)
+    hid = ((step * torch.arange(H) + 17) % H).view(C, 4)
     return c1, c2, hid
 
 
@@ -187,11 +188,11 @@ def _mag(i, span):
     return (1.0 + (i % 7).to(F32) / 8.0) * 2.0 ** -((i // 7) % span).to(F32)
 
 
-def spot_blocks(C, depth, seed):
+def spot_blocks(C, depth, seed, step=333):
     """sparse filters (see the module docstring); gamma a power of two other than 1, biases of the size of the products"""
     g = torch.Generator().manual_seed(seed)
     H = 4 * C
-    c1, c2, hid = spot_maps(C)
+    c1, c2, hid = spot_maps(C, step)
     h = torch.arange(H)
     out = []
     for j in range(depth):

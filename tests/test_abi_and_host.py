@@ -34,6 +34,38 @@ def test_library_exports_every_declared_symbol():
     assert _lib.lib().btsbot_abi_version() == 1
 
 
+def test_stage2_entry_points_check_their_arguments_on_the_host():
+    """btsbot_op_cn_stage2 / _rows / _pack_s2p refuse a bad call before anything is launched, so the refusals can be asked
+    for without a GPU; btsbot_op_cn_stage2_alerts is stage2p_alerts_per_workgroup"""
+    L, vp = _lib.lib(), ctypes.c_void_p
+    bf16 = _lib.PRECISION["bf16"]
+
+    def refused(rc, word):
+        assert rc == _lib.ERR_INVALID_ARG and word in L.btsbot_last_error().decode(), (rc, word, L.btsbot_last_error())
+
+    assert L.btsbot_op_cn_stage2_supported(bf16, 256, 6) == 1 and L.btsbot_op_cn_stage2_supported(bf16, 320, 8) == 1
+    assert L.btsbot_op_cn_stage2_supported(_lib.PRECISION["fp8"], 320, 8) == 0 and L.btsbot_op_cn_stage2_supported(bf16, 256, 9) == 0
+    if "BTSBOT_AMD_S2P_G" not in os.environ:      # (the developer switch overrides hint and batch size alike)
+        assert [L.btsbot_op_cn_stage2_alerts(1024, h) for h in (0, 4, 5, 7)] == [5, 4, 5, 7]
+        assert L.btsbot_op_cn_stage2_alerts(4096, 0) == 7     # 586 workgroups of 7: three rounds of 256; 820 of 5: four
+    refused(L.btsbot_op_cn_stage2_alerts(8, 6), "hint")
+    lists = [(vp * 1)(0) for _ in range(9)]
+    none4 = [ctypes.cast(None, ctypes.POINTER(vp))] * 4
+    call = lambda prec, cw, depth, hint, B: L.btsbot_op_cn_stage2(prec, cw, depth, hint, vp(0), B, *lists, *[vp(0)] * 6, *none4,   # noqa: E731
+                                                                   vp(0), vp(0))
+    refused(call(0, 256, 1, 0, 1), "unsupported")
+    refused(call(bf16, 384, 1, 0, 1), "unsupported")
+    refused(call(bf16, 256, 9, 0, 1), "unsupported")
+    refused(call(bf16, 256, 1, 6, 1), "alerts_hint")
+    refused(call(bf16, 256, 1, 0, -1), "negative alert count")
+    refused(call(bf16, 256, 1, 0, 1), "null pointer")
+    refused(L.btsbot_op_cn_stage2_rows(_lib.PRECISION["fp8"], vp(0), 1, *[vp(0)] * 7, vp(0)), "unsupported")
+    refused(L.btsbot_op_cn_stage2_rows(bf16, vp(0), 1, *[vp(0)] * 7, vp(0)), "null pointer")
+    refused(L.btsbot_op_cn_pack_s2p(bf16, vp(16), vp(0), 24, 64, 0, 0, vp(16), vp(0), vp(0)), "bad shape")
+    refused(L.btsbot_op_cn_pack_s2p(_lib.PRECISION["fp8"], vp(16), vp(0), 16, 64, 0, 0, vp(16), vp(16), vp(0)), "bad shape")
+    refused(L.btsbot_op_cn_pack_s2p(bf16, vp(16), vp(0), 16, 64, 1, 8, vp(16), vp(0), vp(0)), "K must be 4 cin")
+
+
 @pytest.mark.parametrize("name", list(CONFIGS))
 def test_state_dict_layout_matches_reference(name):
     kind, cfg = CONFIGS[name]

@@ -45,6 +45,8 @@ from .features import FeatureState
 from . import neighbors
 from .neighbors import (EmbeddingIndex, embedding_neighbors, knn_graph, neighbor_ranks, neighbor_vote, radius_graph,
                         radius_neighbors)
+from . import ivf
+from .ivf import IvfIndex, KMeansFit, kmeans
 from . import mapindex
 from .mapindex import MapIndex
 from . import clusters
@@ -77,6 +79,7 @@ __all__ = [
     "radius_neighbors", "radius_graph", "neighbor_ranks", "quality", "trustworthiness", "continuity", "map_quality",
     "clusters", "graph_components", "dbscan", "mapindex", "MapIndex",
     "graph", "KnnGraph",
+    "ivf", "IvfIndex", "KMeansFit", "kmeans",
     "novelty", "NoveltyModel", "local_outlier_factor", "kth_neighbor_distance",
     "hdbscan", "mutual_reachability_mst", "MutualReachabilityMST", "ClusterTree", "ClusterModel",
     "attribution", "saliency",

@@ -70,6 +70,8 @@ SYMBOLS = [
     "btsbot_layout_epochs", "btsbot_layout_smooth_knn_query", "btsbot_layout_transform",
     "btsbot_lof_fit", "btsbot_lof_score",
     "btsbot_knn_graph_merge", "btsbot_knn_graph_compact",
+    "btsbot_kmeans_workspace", "btsbot_kmeans_update", "btsbot_ivf_list_rows", "btsbot_ivf_layout", "btsbot_ivf_workspace",
+    "btsbot_ivf_query",
     "btsbot_mst_offer_knn", "btsbot_mst_offer_csr", "btsbot_mst_merge", "btsbot_hdbscan_tree",
     "btsbot_hdbscan_model", "btsbot_cluster_offer_knn", "btsbot_cluster_offer_csr", "btsbot_cluster_assign",
 ]
@@ -82,6 +84,8 @@ KNN_MAX_DIM, KNN_MAX_K, KNN_MAX_SPLITS = 1024, 64, 32
 KNN_EXCLUDE_SAME, KNN_ONE_PER_GROUP = 1, 2   # enum btsbot_knn_flags
 KNN_MAX_K_ONE_PER_GROUP = 32                 # k's cap under KNN_ONE_PER_GROUP
 KNN_GRAPH_DISTINCT = 1                       # enum btsbot_knn_graph_flags (csrc/knn_graph.hip)
+IVF_MAX_LISTS, IVF_MAX_NPROBE = 65536, 32    # csrc/ivf.hip (nprobe's cap is the merge's KNN_MAX_SPLITS)
+KMEANS_CHUNK = 64                            # csrc/ivf.hip: rows per partial sum of btsbot_kmeans_update
 GRID_MAX_CELLS, GRID_MAX_K = 4096, 64         # csrc/grid.hip
 GRID_LANES = (0, 1, 4, 8, 16, 32, 64)        # lanes per query row of btsbot_grid_radius_* (0: the library's choice)
 EMBEDDING = {"features": 0, "hidden": 1}   # enum btsbot_embedding
@@ -406,6 +410,18 @@ def lib() -> C.CDLL:
     L.btsbot_knn_graph_merge.argtypes = [vp, vp, i64, i32, i64, vp, vp, vp, i64, vp, i64, i32, vp, i64, vp, vp, vp]
     L.btsbot_knn_graph_compact.restype = i32
     L.btsbot_knn_graph_compact.argtypes = [vp, vp, i64, i32, i64, vp, vp, vp, i64, i64, i32, vp, vp, vp]
+    L.btsbot_kmeans_workspace.restype = i64
+    L.btsbot_kmeans_workspace.argtypes = [i64, i32, i32]
+    L.btsbot_kmeans_update.restype = i32
+    L.btsbot_kmeans_update.argtypes = [vp, i64, i32, vp, vp, i32, vp, vp, vp, i64, vp]
+    L.btsbot_ivf_list_rows.restype = i64
+    L.btsbot_ivf_list_rows.argtypes = [i64, i32]
+    L.btsbot_ivf_layout.restype = i32
+    L.btsbot_ivf_layout.argtypes = [vp, i64, i32, vp, vp, i32, vp, i64, vp, vp, vp, vp, vp, i64, vp]
+    L.btsbot_ivf_workspace.restype = i64
+    L.btsbot_ivf_workspace.argtypes = [i64, i32, i32, i32, i32]
+    L.btsbot_ivf_query.restype = i32
+    L.btsbot_ivf_query.argtypes = [vp, i64, vp, i64, i32, i32, vp, i32, vp, vp, i64, vp, vp, vp, i32, vp, vp, vp, i64, vp]
     L.btsbot_mst_offer_knn.restype = i32
     L.btsbot_mst_offer_knn.argtypes = [vp, vp, i64, i32, vp, vp, i32, f32, vp, vp, vp, vp]
     L.btsbot_mst_offer_csr.restype = i32

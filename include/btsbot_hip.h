@@ -1383,6 +1383,56 @@ int btsbot_knn_graph_compact(const int64_t* idx, const float* dist, int64_t stri
                              const int64_t* new_of_old, int64_t* out_idx, float* out_dist, int64_t out_stride,
                              int64_t n_new, int flags, uint8_t* damaged, int32_t* counts, void* stream);
 
+/* ---- The partitioned index: k-means on the device and a probed nearest-row search (csrc/ivf.hip) ----
+ *
+ * The rows of a bank are cut into lists around centroids; a query searches only the lists it is told to probe.  The
+ * answer of btsbot_ivf_query() is exactly btsbot_knn_query()'s (euclidean) over the finite rows of the probed lists:
+ * the same selection scores, the same merge by (score, row), the same direct-form fp32 distance, ordered by (dist,
+ * ORIGINAL row number).  Which lists are probed is the caller's (btsbot_knn_query() of the queries against the
+ * centroids); it is the only approximation.  All pointers are device memory; n_clusters / n_lists in 1 .. 65,536.
+ *
+ * btsbot_kmeans_update(): centroids[c] = the mean of the rows with labels[row] == c, for every cluster with at least one
+ * row; an empty cluster's centroid is not written.  counts int64 [n_clusters] receives every cluster's size.  labels
+ * int64 [n_rows] in -1 .. n_clusters - 1 (negative: the row enters no sum); order int64 [n_rows] = the row numbers
+ * sorted stably by label (rows of equal label ascending; any stable sort).  Deterministic, no atomic on a sum: the rows
+ * of a cluster, in ascending row order, are cut into chunks of 64 counted from the cluster's first row, pass 1 adds a
+ * chunk's rows one after the other per column, pass 2 adds the cluster's partial sums in chunk order and divides by
+ * the count.  A centroid's bits depend on its cluster's rows alone -- not on the grid, the run or the other clusters.
+ * One read of the fp32 rows.  workspace: btsbot_kmeans_workspace() bytes, 16-byte aligned; four launches and a memset.
+ *
+ * btsbot_ivf_layout(): the list-ordered operand image.  packed: the bank's records (btsbot_knn_pack_bank, euclidean);
+ * labels / order as above (a row of negative label is in no list).  list_packed receives n_list_rows =
+ * btsbot_ivf_list_rows(n_bank, n_lists) records, an upper bound that needs no host read: every list starts on a 128-row
+ * boundary, its rows in ascending row number, padded with the record of a non-finite row (never a candidate).
+ * row_of int32 [n_list_rows]: the bank row at a position, -1 for padding; pos_of int32 [n_bank]: a row's position, -1 for
+ * a row in no list; list_sizes int64 [n_lists]; list_tile int32 [n_lists + 1]: list l holds the 128-row tiles
+ * list_tile[l] .. list_tile[l + 1].  workspace: 2 * align256(4 * (n_lists + 1)) bytes.
+ *
+ * btsbot_ivf_query(): idx int64 [n_query][k] (original row numbers), dist fp32 [n_query][k].  probes int64
+ * [n_query][nprobe], 1 <= nprobe <= min(n_lists, 32), distinct per row; a value outside 0 .. n_lists - 1 contributes
+ * nothing.  self_rows: NULL, or int64 [n_query]: query row i IS bank row self_rows[i] and that one row is not a
+ * candidate (by position: duplicates are).  Fewer than k rows in the probed lists: the tail is idx = -1, dist = +inf; a
+ * non-finite query row: -1 / NaN.  One work item is one list and at most 128 of the queries that probe it; the items
+ * are built on the device and the grid is the upper bound ceil(n_query * nprobe / 128) + n_lists: no host read.  A
+ * row's answer is bit for bit independent of the other rows of the call and of the run.  workspace:
+ * btsbot_ivf_workspace() bytes -- the packed image of the query rows, n_query * nprobe * k candidates of 8 bytes, 4
+ * bytes per (query, probe) pair and 12 per list --, 16-byte aligned.  Seven launches and two memsets on `stream`.
+ * BTSBOT_ERR_INVALID_ARG with a message, before any HIP call, for a shape out of range, n_query * nprobe >= 2^31, a
+ * NULL or misaligned pointer, a workspace too small. */
+int64_t btsbot_kmeans_workspace(int64_t n_rows, int dim, int n_clusters);
+int btsbot_kmeans_update(const float* rows, int64_t n_rows, int dim, const int64_t* labels, const int64_t* order,
+                         int n_clusters, float* centroids, int64_t* counts, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+int64_t btsbot_ivf_list_rows(int64_t n_bank, int n_lists);
+int btsbot_ivf_layout(const void* packed, int64_t n_bank, int dim, const int64_t* labels, const int64_t* order,
+                      int n_lists, void* list_packed, int64_t n_list_rows, int32_t* row_of, int32_t* pos_of,
+                      int64_t* list_sizes, int32_t* list_tile, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t btsbot_ivf_workspace(int64_t n_query, int dim, int k, int nprobe, int n_lists);
+int btsbot_ivf_query(const float* queries, int64_t n_query, const float* bank, int64_t n_bank, int dim, int k,
+                     const int64_t* probes, int nprobe, const int64_t* self_rows, const void* list_packed,
+                     int64_t n_list_rows, const int32_t* row_of, const int32_t* pos_of, const int32_t* list_tile,
+                     int n_lists, int64_t* idx, float* dist, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- HDBSCAN: the mutual-reachability spanning tree and its hierarchy (csrc/mr_offer.hip, csrc/mst.hip,
  *      csrc/hdbscan_tree.hip) ---- */
 

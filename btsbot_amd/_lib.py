@@ -71,7 +71,7 @@ SYMBOLS = [
     "btsbot_lof_fit", "btsbot_lof_score",
     "btsbot_knn_graph_merge", "btsbot_knn_graph_compact",
     "btsbot_kmeans_workspace", "btsbot_kmeans_update", "btsbot_ivf_list_rows", "btsbot_ivf_layout", "btsbot_ivf_workspace",
-    "btsbot_ivf_query",
+    "btsbot_ivf_query", "btsbot_ivf_layout_groups", "btsbot_ivf_workspace_grouped", "btsbot_ivf_query_grouped",
     "btsbot_mst_offer_knn", "btsbot_mst_offer_csr", "btsbot_mst_merge", "btsbot_hdbscan_tree",
     "btsbot_hdbscan_model", "btsbot_cluster_offer_knn", "btsbot_cluster_offer_csr", "btsbot_cluster_assign",
 ]
@@ -422,6 +422,12 @@ def lib() -> C.CDLL:
     L.btsbot_ivf_workspace.argtypes = [i64, i32, i32, i32, i32]
     L.btsbot_ivf_query.restype = i32
     L.btsbot_ivf_query.argtypes = [vp, i64, vp, i64, i32, i32, vp, i32, vp, vp, i64, vp, vp, vp, i32, vp, vp, vp, i64, vp]
+    L.btsbot_ivf_layout_groups.restype = i32
+    L.btsbot_ivf_layout_groups.argtypes = [vp, i64, i32, vp, i64, vp, vp]
+    L.btsbot_ivf_workspace_grouped.restype = i64
+    L.btsbot_ivf_workspace_grouped.argtypes = [i64, i32, i32, i32, i32, i32]
+    L.btsbot_ivf_query_grouped.restype = i32
+    L.btsbot_ivf_query_grouped.argtypes = L.btsbot_ivf_query.argtypes + [vp, vp, i32]
     L.btsbot_mst_offer_knn.restype = i32
     L.btsbot_mst_offer_knn.argtypes = [vp, vp, i64, i32, vp, vp, i32, f32, vp, vp, vp, vp]
     L.btsbot_mst_offer_csr.restype = i32

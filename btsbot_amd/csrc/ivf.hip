@@ -23,6 +23,38 @@
 // The only atomics are integer counters: the histogram, and the slot a pair takes inside its list's run of pairs.  Which
 // slot -- hence which item and which tile row -- a pair gets differs from run to run; its partial list does not, because a
 // score depends on its two records alone and a list is the k best of what it was offered whatever the order (knn.hip).
+//
+// Groups (btsbot_ivf_query_grouped).  A row may carry a group, any int64 (an alert's object), and the probed search takes
+// the two switches of btsbot_knn_query_grouped with the same contract over the rows of the probed lists.  Both kernels
+// are templates on the group mode GM, as knn.hip's are; GM = 0 is the text above, unchanged, and is what btsbot_ivf_query
+// launches.  The selection's indices are positions of the list image, so the groups are banked in list order:
+// btsbot_ivf_layout_groups gathers list_group[position] = bank_group[row_of[position]] (0 at a padding position, whose
+// score is +inf and which is therefore never offered: its group is never read as a candidate's), 8 bytes per row next to
+// a record of 2.1 KB.  A tile's 128 groups are requested under the products, one per thread, and parked in the idle
+// operand LDS at TG_OFF (load_tile_group, knn_tile.h), exactly as knn.hip does it.
+//   GM & 1, exclude   the query groups of a lane's four tile rows sit in registers, taken from query_group[pair /
+//                     nprobe] through the item's row map; one more term in the mask of what may be offered.  self_rows
+//                     stays the position compare it is and combines with every mode.
+//   GM & 2, one per group   offer_one (knn_tile.h).  The groups of the list entries live in the workspace, not in LDS
+//                     (knn.hip says why), as lg[j * pairs + slot], an int64 [k][n_query * nprobe] array, 8 k bytes per
+//                     (query, probe) pair -- 7.9 MB at Q = 8,192, nprobe = 8, k = 15 --: slot = first + tile row is the
+//                     pair's place in its list's run of pairs, unique and below n_query * nprobe, so an entry is only
+//                     ever touched by the slot's owner thread and the owners of an item read and write neighbouring
+//                     words.  No host read and no n_lists term: a block per work item would be [items][k][128] over the
+//                     grid's upper bound, about 1 GiB at 65,536 lists and k = 15.  k <= 32 in this mode (MAX_K_ONE).
+// Order-independence in the listed pass.  Inside one list the positions ascend with the original row number, so "a
+// group's best by (score, position)" is its best by (score, row), and knn.hip's argument -- the list is the k best of
+// B(S), the best row of every group offered so far, whatever the order of the offers -- holds per work item as written.
+// Which slot a pair takes still differs from run to run; its list does not.
+// The merge.  A group's rows may lie in several probed lists, so this is where they meet.  After the pool's positions
+// are mapped to original rows, GM & 2 drops every pool entry that has an entry of its own group before it by (score,
+// row) and ranks among the rest (keep_group_bests, knn_tile.h, shared with knn_merge_kernel).  This is knn.hip's split
+// argument with "list" for "split": a group's best over the probed lists is the best of its list-bests; it is in its
+// list's k unless k other groups' bests of that list are before it, and then it is not among the k best groups overall
+// either.  A row that is not its group's best over the probed lists either loses to its group's entry in the pool, or
+// its group's best was pushed out of a list by k groups' bests, each represented in the pool by a kept entry no worse
+// -- rank >= k.  The pool is nprobe * k <= 32 * 32 entries and their 8 KB of groups, on chip.
+// New code here has no inline assembly; the only atomics are the integer LDS and global counters named above.
 #include "knn_tile.h"
 
 namespace {
@@ -207,6 +239,16 @@ __global__ __launch_bounds__(256) void ivf_gather_kernel(const unsigned char* __
   }
 }
 
+// the groups in list order: position p holds the group of bank row row_of[p], 0 at a padding position
+__global__ __launch_bounds__(256) void ivf_gather_groups_kernel(const long long* __restrict__ bank_group,
+                                                                const int* __restrict__ row_of, long n_list_rows,
+                                                                long n_bank, long long* __restrict__ list_group) {
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= n_list_rows) return;
+  const int r = row_of[p];
+  list_group[p] = r >= 0 && r < n_bank ? bank_group[r] : 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // query: the (query, probe) pairs into their lists' runs
 __global__ __launch_bounds__(256) void ivf_fill_kernel(const long long* __restrict__ probes, long n_pairs, int n_lists,
@@ -221,29 +263,12 @@ __global__ __launch_bounds__(256) void ivf_fill_kernel(const long long* __restri
   if (at < n_pairs) pair_at[at] = (int)i;
 }
 
-// a list is the k best by (score, index) of what it was offered, unsorted, its worst entry at tp (knn.hip, offer())
-__device__ __forceinline__ void ivf_offer(Cand* mine, int k, float s, int gb, float& ts, int& ti, int& tp) {
-  if (!before(s, gb, ts, ti)) return;
-  mine[tp] = Cand{s, gb};
-  Cand w = mine[0];
-  int wp = 0;
-#pragma unroll 4
-  for (int j = 1; j < k; ++j) {
-    const Cand o = mine[j];
-    if (before(w.s, w.i, o.s, o.i)) {
-      w = o;
-      wp = j;
-    }
-  }
-  ts = w.s;
-  ti = w.i;
-  tp = wp;
-}
-
 // The listed selection.  Item blockIdx.x = list l and the pairs pair_at[first .. first + nq) that probe it; tile row r is
 // query pair_at[first + r] / nprobe.  The list's tiles [tstart[l], tstart[l + 1]) of the list image are walked as
 // knn_select_kernel walks a split; an index is a POSITION of the list image (ascending in the row number inside a list).
-// cand[pair][k] receives the row's list.
+// cand[pair][k] receives the row's list.  GM != 0: qgrp = the query rows' groups, lgrp = the groups in list order; GM & 2:
+// lg = the groups of the list entries, entry j of the pair at slot s at lg[j * lg_stride + s], lg_stride = Q * nprobe.
+template <int GM>
 __global__ __launch_bounds__(256, 2) void ivf_select_kernel(const unsigned char* __restrict__ qimg,
                                                             const unsigned char* __restrict__ limg, long n_list_rows,
                                                             int dim, int k, int nprobe, int n_lists, long n_bank,
@@ -252,7 +277,10 @@ __global__ __launch_bounds__(256, 2) void ivf_select_kernel(const unsigned char*
                                                             const int* __restrict__ pair_at,
                                                             const int* __restrict__ tstart,
                                                             const long long* __restrict__ self_rows,
-                                                            const int* __restrict__ pos_of, Cand* __restrict__ cand) {
+                                                            const int* __restrict__ pos_of, Cand* __restrict__ cand,
+                                                            const long long* __restrict__ qgrp,
+                                                            const long long* __restrict__ lgrp,
+                                                            long long* __restrict__ lg, long lg_stride) {
   constexpr int MI = TileWalk::MI, NI = TileWalk::NI;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int w = blockIdx.x;
@@ -267,6 +295,7 @@ __global__ __launch_bounds__(256, 2) void ivf_select_kernel(const unsigned char*
   int* bcnt = reinterpret_cast<int*>(bucket + TQ * BCAP);
   float* thr = reinterpret_cast<float*>(bcnt + TQ);
   int* flag = reinterpret_cast<int*>(thr + TQ);
+  long long* tg = reinterpret_cast<long long*>(smem + TG_OFF);   // GM != 0: [TB] the tile's groups
 
   const int tid = threadIdx.x;
   const LanePos p;
@@ -305,6 +334,16 @@ __global__ __launch_bounds__(256, 2) void ivf_select_kernel(const unsigned char*
       }
     }
   }
+  long long qg[MI];   // GM & GM_EXCLUDE: the groups of the lane's four tile rows
+  if constexpr ((GM & GM_EXCLUDE) != 0) {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+      const int pr = qpair[p.qrow(mi)];
+      qg[mi] = pr >= 0 ? qgrp[pr / nprobe] : 0;   // (a row past the item's end never has a candidate)
+    }
+  }
+  // GM & GM_ONE: the groups of this thread's list entries (an owner's slot first + tid is below lg_stride)
+  long long* LG = lg + ((long)first + tid);
   long qoff[CH];   // the records of the rows this thread loads chunks of, -1: none
 #pragma unroll
   for (int i = 0; i < CH; ++i) {
@@ -333,6 +372,8 @@ __global__ __launch_bounds__(256, 2) void ivf_select_kernel(const unsigned char*
   if (t_begin < t_end) gload(t_begin, 0);
   for (int tile = t_begin; tile < t_end; ++tile) {
     const int b0 = tile * TB;
+    long long gt = 0;   // GM != 0: the group at position b0 + tid, in flight under the products
+    if constexpr (GM != 0) gt = load_tile_group(lgrp, b0, (int)n_list_rows);
     f32x4 acc[NI][MI];
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni)
@@ -372,6 +413,7 @@ __global__ __launch_bounds__(256, 2) void ivf_select_kernel(const unsigned char*
     if (tid < TQ) {
       thr[tid] = owner ? ts : -__builtin_inff();   // (a row past the item's end never has a candidate)
       bcnt[tid] = 0;
+      if constexpr (GM != 0) tg[tid] = gt;
     }
     if (tid < 2) flag[tid] = 0;
     lds_barrier();
@@ -388,6 +430,11 @@ __global__ __launch_bounds__(256, 2) void ivf_select_kernel(const unsigned char*
         nb[i] = h.x;
         sb[i] = h.y;
       }
+      long long bg[4];   // GM & GM_EXCLUDE: the fragment's groups
+      if constexpr ((GM & GM_EXCLUDE) != 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) bg[i] = tg[p.wn * 64 + ni * 16 + p.lq * 4 + i];   // (p.brow(ni, i), as knn.hip)
+      }
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -395,7 +442,8 @@ __global__ __launch_bounds__(256, 2) void ivf_select_kernel(const unsigned char*
           const int gb = p.gb(b0, ni, i);
           const float s = tile_score(acc[ni][mi][i], sq[mi], sb[i], nb[i]);
           acc[ni][mi][i] = s;
-          const bool in = s <= t[mi] && s < __builtin_inff() && gb != selfb[mi];
+          bool in = s <= t[mi] && s < __builtin_inff() && gb != selfb[mi];
+          if constexpr ((GM & GM_EXCLUDE) != 0) in = in && bg[i] != qg[mi];
           if (in) mask |= 1ull << ((ni * MI + mi) * 4 + i);
         }
     }
@@ -433,7 +481,8 @@ __global__ __launch_bounds__(256, 2) void ivf_select_kernel(const unsigned char*
         const int n = min(bcnt[tid], BCAP);
         for (int e = 0; e < n; ++e) {
           const Cand c = bucket[tid * BCAP + e];
-          ivf_offer(L + tid * k, k, c.s, b0 + c.i, ts, ti, tp);
+          if constexpr ((GM & GM_ONE) != 0) offer_one(L + tid * k, LG, lg_stride, k, c.s, b0 + c.i, tg[c.i], ts, ti, tp);
+          else offer(L + tid * k, k, c.s, b0 + c.i, ts, ti, tp);
         }
         thr[tid] = ts;
       }
@@ -453,12 +502,15 @@ __global__ __launch_bounds__(256, 2) void ivf_select_kernel(const unsigned char*
 // merge, one wave per query (knn_merge_kernel): the pool is the query's nprobe * k candidates, their positions mapped to
 // original row numbers before any comparison; the k best by (score, row), each one's distance in the direct form from
 // the fp32 rows by direct_distance() -- the function btsbot_knn_query applies --, ordered by (dist, row).  A probe outside
-// 0 .. n_lists - 1 has no item and contributes nothing.
+// 0 .. n_lists - 1 has no item and contributes nothing.  GM & GM_ONE (the header's argument): the entries' groups are read
+// at their positions, lgrp, and only a group's best entry by (score, row) is ranked.
+template <int GM>
 __global__ __launch_bounds__(64) void ivf_merge_kernel(const float* __restrict__ queries, const float* __restrict__ bank,
                                                        long n_bank, const Cand* __restrict__ cand,
                                                        const long long* __restrict__ probes, int n_lists,
                                                        const int* __restrict__ row_of, long n_list_rows, int dim, int k,
-                                                       int nprobe, int64_t* __restrict__ idx, float* __restrict__ dist) {
+                                                       int nprobe, int64_t* __restrict__ idx, float* __restrict__ dist,
+                                                       const long long* __restrict__ lgrp) {
   __shared__ Cand pool[MAX_SPLITS * MAX_K];
   __shared__ int win[MAX_K];
   __shared__ float wdist[MAX_K];
@@ -493,6 +545,13 @@ __global__ __launch_bounds__(64) void ivf_merge_kernel(const float* __restrict__
   }
   if (lane < MAX_K) win[lane] = EMPTY;
   __syncthreads();
+  if constexpr ((GM & GM_ONE) != 0) {
+    // one per group: the groups of the entries that stand (their positions are in range), then only the groups' bests
+    __shared__ long long pgrp[MAX_SPLITS * MAX_K_ONE];
+    for (int c = lane; c < P; c += 64) pgrp[c] = pool[c].i != EMPTY ? lgrp[cand[q * P + c].i] : 0;
+    __syncthreads();
+    keep_group_bests(pool, pgrp, P, lane);
+  }
   // a row lies in one list: the entries are distinct, so the ranks are too
   for (int c = lane; c < P; c += 64) {
     const Cand me = pool[c];
@@ -531,8 +590,8 @@ __global__ __launch_bounds__(64) void ivf_merge_kernel(const float* __restrict__
 }
 
 struct IvfWs {
-  size_t qimg, cand, pair_at, cnt, pstart, istart, total;
-  IvfWs(int64_t n_query, int dim, int k, int nprobe, int n_lists) {
+  size_t qimg, cand, pair_at, cnt, pstart, istart, lg, total;
+  IvfWs(int64_t n_query, int dim, int k, int nprobe, int n_lists, int flags = 0) {
     const size_t pairs = (size_t)n_query * nprobe;
     const size_t bins = align256(((size_t)n_lists + 1) * sizeof(int));
     qimg = 0;
@@ -541,7 +600,8 @@ struct IvfWs {
     cnt = pair_at + align256(pairs * sizeof(int));
     pstart = cnt + bins;
     istart = pstart + bins;
-    total = istart + bins;
+    lg = istart + bins;   // GM_ONE: the groups of the list entries, int64 [k][pairs]
+    total = lg + ((flags & GM_ONE) != 0 ? align256(pairs * k * sizeof(long long)) : 0);
   }
 };
 
@@ -562,6 +622,20 @@ int check_probe_shape(const char* who, int64_t n_query, int dim, int k, int npro
   }
   if (n_query * nprobe > 0x7fffffffLL) {
     btsbot_set_error("%s: n_query * nprobe = %lld must be below 2^31", who, (long long)(n_query * nprobe));
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  return BTSBOT_OK;
+}
+
+// the group switches of the probed query, as knn::check_search holds them for the exact one
+int check_group_flags(const char* who, int flags, int k) {
+  if ((flags & ~(GM_EXCLUDE | GM_ONE)) != 0) {
+    btsbot_set_error("%s: flags=%d holds bits other than BTSBOT_KNN_EXCLUDE_SAME | BTSBOT_KNN_ONE_PER_GROUP", who, flags);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  if ((flags & GM_ONE) != 0 && k > MAX_K_ONE) {
+    btsbot_set_error("%s: k=%d, but BTSBOT_KNN_ONE_PER_GROUP holds k <= %d (the merge keeps its pool's groups on chip)", who,
+                     k, MAX_K_ONE);
     return BTSBOT_ERR_INVALID_ARG;
   }
   return BTSBOT_OK;
@@ -689,19 +763,118 @@ extern "C" int btsbot_ivf_layout(const void* packed, int64_t n_bank, int dim, co
   return BTSBOT_OK;
 }
 
-extern "C" int64_t btsbot_ivf_workspace(int64_t n_query, int dim, int k, int nprobe, int n_lists) {
-  if (check_probe_shape("btsbot_ivf_workspace", n_query, dim, k, nprobe, n_lists) != BTSBOT_OK)
+extern "C" int btsbot_ivf_layout_groups(const int64_t* bank_group, int64_t n_bank, int n_lists, const int32_t* row_of,
+                                        int64_t n_list_rows, int64_t* list_group, void* stream) {
+  const char* who = "btsbot_ivf_layout_groups";
+  TRY(knn::check_shape(who, 0, n_bank, 1, 1));
+  TRY(check_lists(who, n_lists));
+  if (n_list_rows != btsbot_ivf_list_rows(n_bank, n_lists)) {
+    btsbot_set_error("%s: n_list_rows=%lld is not btsbot_ivf_list_rows(n_bank, n_lists)", who, (long long)n_list_rows);
     return BTSBOT_ERR_INVALID_ARG;
-  return (int64_t)IvfWs(n_query, dim, k, nprobe, n_lists).total;
+  }
+  if (row_of == nullptr || list_group == nullptr || (n_bank > 0 && bank_group == nullptr)) {
+    btsbot_set_error("%s: NULL bank_group, row_of or list_group", who);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  hipLaunchKernelGGL(ivf_gather_groups_kernel, dim3((unsigned)((n_list_rows + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, reinterpret_cast<const long long*>(bank_group), (const int*)row_of,
+                     (long)n_list_rows, (long)n_bank, reinterpret_cast<long long*>(list_group));
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
 }
 
-extern "C" int btsbot_ivf_query(const float* queries, int64_t n_query, const float* bank, int64_t n_bank, int dim, int k,
-                                const int64_t* probes, int nprobe, const int64_t* self_rows, const void* list_packed,
-                                int64_t n_list_rows, const int32_t* row_of, const int32_t* pos_of,
-                                const int32_t* list_tile, int n_lists, int64_t* idx, float* dist, void* workspace,
-                                int64_t workspace_bytes, void* stream) {
-  const char* who = "btsbot_ivf_query";
+extern "C" int64_t btsbot_ivf_workspace_grouped(int64_t n_query, int dim, int k, int nprobe, int n_lists, int flags) {
+  const char* who = flags == 0 ? "btsbot_ivf_workspace" : "btsbot_ivf_workspace_grouped";
+  if (check_probe_shape(who, n_query, dim, k, nprobe, n_lists) != BTSBOT_OK ||
+      check_group_flags(who, flags, k) != BTSBOT_OK)
+    return BTSBOT_ERR_INVALID_ARG;
+  return (int64_t)IvfWs(n_query, dim, k, nprobe, n_lists, flags).total;
+}
+
+extern "C" int64_t btsbot_ivf_workspace(int64_t n_query, int dim, int k, int nprobe, int n_lists) {
+  return btsbot_ivf_workspace_grouped(n_query, dim, k, nprobe, n_lists, 0);
+}
+
+namespace {
+
+// what btsbot_ivf_query and btsbot_ivf_query_grouped were given, behind their checks
+struct IvfQuery {
+  const float* queries;
+  int64_t n_query;
+  const float* bank;
+  int64_t n_bank;
+  int dim, k;
+  const long long* probes;
+  int nprobe;
+  const long long* self_rows;
+  const unsigned char* list_packed;
+  int64_t n_list_rows;
+  const int *row_of, *pos_of, *list_tile;
+  int n_lists;
+  int64_t* idx;
+  float* dist;
+  unsigned char* base;
+  const long long *qgrp, *lgrp;
+  hipStream_t st;
+};
+
+// The launches of btsbot_ivf_query (GM = 0) and btsbot_ivf_query_grouped, one instantiation per group mode
+template <int GM>
+int launch_query(const IvfQuery& a) {
+  const IvfWs ws(a.n_query, a.dim, a.k, a.nprobe, a.n_lists, GM);
+  hipStream_t st = a.st;
+  unsigned char* qimg = a.base + ws.qimg;
+  Cand* cand = reinterpret_cast<Cand*>(a.base + ws.cand);
+  int* pair_at = reinterpret_cast<int*>(a.base + ws.pair_at);
+  int* cnt = reinterpret_cast<int*>(a.base + ws.cnt);
+  int* pstart = reinterpret_cast<int*>(a.base + ws.pstart);
+  int* istart = reinterpret_cast<int*>(a.base + ws.istart);
+  long long* lg = reinterpret_cast<long long*>(a.base + ws.lg);
+  const int k = a.k, n_lists = a.n_lists;
+  const long n_pairs = (long)(a.n_query * a.nprobe);
+  const long long* pr = a.probes;
+  const unsigned pair_blocks = (unsigned)((n_pairs + 255) / 256);
+
+  TRY(knn::pack_queries(a.queries, a.n_query, a.dim, qimg, st));
+  HIP_TRY(hipMemsetAsync(cnt, 0, ((size_t)n_lists + 1) * sizeof(int), st));
+  hipLaunchKernelGGL(hist_kernel, dim3(pair_blocks), dim3(256), 0, st, pr, n_pairs, n_lists, cnt);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SCAN_T), 0, st, (const int*)cnt, n_lists, TQ, pstart, istart,
+                     (long long*)nullptr);
+  LAUNCH_CHECK();
+  HIP_TRY(hipMemsetAsync(cnt, 0, ((size_t)n_lists + 1) * sizeof(int), st));   // now the lists' fill cursors
+  hipLaunchKernelGGL(ivf_fill_kernel, dim3(pair_blocks), dim3(256), 0, st, pr, n_pairs, n_lists, (const int*)pstart, cnt,
+                     pair_at);
+  LAUNCH_CHECK();
+  // 64 KB of operands + 1 KB of lists per k + the tile's row map: two workgroups per CU up to k = 15, in every group mode
+  const int lds_max = GEMM_LDS + TQ * MAX_K * (int)sizeof(Cand) + TQ * (int)sizeof(int);
+  static DevOnce attr;
+  if (attr.need()) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(ivf_select_kernel<GM>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+    attr.done();
+  }
+  const unsigned items = (unsigned)((n_pairs + TQ - 1) / TQ + n_lists);
+  hipLaunchKernelGGL(ivf_select_kernel<GM>, dim3(items), dim3(256),
+                     GEMM_LDS + TQ * k * (int)sizeof(Cand) + TQ * (int)sizeof(int), st, (const unsigned char*)qimg,
+                     a.list_packed, (long)a.n_list_rows, a.dim, k, a.nprobe, n_lists, (long)a.n_bank, (const int*)pstart,
+                     (const int*)istart, (const int*)pair_at, a.list_tile, a.self_rows, a.pos_of, cand, a.qgrp, a.lgrp, lg,
+                     n_pairs);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(ivf_merge_kernel<(GM & GM_ONE)>, dim3((unsigned)a.n_query), dim3(64), 0, st, a.queries, a.bank,
+                     (long)a.n_bank, (const Cand*)cand, pr, n_lists, a.row_of, (long)a.n_list_rows, a.dim, k, a.nprobe,
+                     a.idx, a.dist, a.lgrp);
+  LAUNCH_CHECK();
+  return BTSBOT_OK;
+}
+
+int query_checked(const char* who, const float* queries, int64_t n_query, const float* bank, int64_t n_bank, int dim, int k,
+                  const int64_t* probes, int nprobe, const int64_t* self_rows, const void* list_packed,
+                  int64_t n_list_rows, const int32_t* row_of, const int32_t* pos_of, const int32_t* list_tile, int n_lists,
+                  int64_t* idx, float* dist, void* workspace, int64_t workspace_bytes, void* stream,
+                  const int64_t* query_group, const int64_t* list_group, int flags) {
   TRY(check_probe_shape(who, n_query, dim, k, nprobe, n_lists));
+  TRY(check_group_flags(who, flags, k));
   TRY(knn::check_shape(who, 0, n_bank, dim, 1));
   if (n_list_rows != btsbot_ivf_list_rows(n_bank, n_lists)) {
     btsbot_set_error("%s: n_list_rows=%lld is not btsbot_ivf_list_rows(n_bank, n_lists)", who, (long long)n_list_rows);
@@ -714,52 +887,48 @@ extern "C" int btsbot_ivf_query(const float* queries, int64_t n_query, const flo
     btsbot_set_error("%s: NULL argument", who);
     return BTSBOT_ERR_INVALID_ARG;
   }
-  const IvfWs ws(n_query, dim, k, nprobe, n_lists);
+  if (((flags & GM_EXCLUDE) != 0 && query_group == nullptr) || (flags != 0 && list_group == nullptr)) {
+    btsbot_set_error("%s: flags=%d need list_group (and BTSBOT_KNN_EXCLUDE_SAME query_group), got NULL", who, flags);
+    return BTSBOT_ERR_INVALID_ARG;
+  }
+  const IvfWs ws(n_query, dim, k, nprobe, n_lists, flags);
   if (workspace_bytes < (int64_t)ws.total || ((uintptr_t)workspace & 15) != 0 || ((uintptr_t)list_packed & 15) != 0) {
     btsbot_set_error("%s: workspace of %lld bytes (need %lld), or workspace / list_packed not 16-byte aligned", who,
                      (long long)workspace_bytes, (long long)ws.total);
     return BTSBOT_ERR_INVALID_ARG;
   }
-  hipStream_t st = (hipStream_t)stream;
-  unsigned char* base = reinterpret_cast<unsigned char*>(workspace);
-  unsigned char* qimg = base + ws.qimg;
-  Cand* cand = reinterpret_cast<Cand*>(base + ws.cand);
-  int* pair_at = reinterpret_cast<int*>(base + ws.pair_at);
-  int* cnt = reinterpret_cast<int*>(base + ws.cnt);
-  int* pstart = reinterpret_cast<int*>(base + ws.pstart);
-  int* istart = reinterpret_cast<int*>(base + ws.istart);
-  const long n_pairs = (long)(n_query * nprobe);
-  const long long* pr = reinterpret_cast<const long long*>(probes);
-  const unsigned pair_blocks = (unsigned)((n_pairs + 255) / 256);
-
-  TRY(knn::pack_queries(queries, n_query, dim, qimg, st));
-  HIP_TRY(hipMemsetAsync(cnt, 0, ((size_t)n_lists + 1) * sizeof(int), st));
-  hipLaunchKernelGGL(hist_kernel, dim3(pair_blocks), dim3(256), 0, st, pr, n_pairs, n_lists, cnt);
-  LAUNCH_CHECK();
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SCAN_T), 0, st, (const int*)cnt, n_lists, TQ, pstart, istart,
-                     (long long*)nullptr);
-  LAUNCH_CHECK();
-  HIP_TRY(hipMemsetAsync(cnt, 0, ((size_t)n_lists + 1) * sizeof(int), st));   // now the lists' fill cursors
-  hipLaunchKernelGGL(ivf_fill_kernel, dim3(pair_blocks), dim3(256), 0, st, pr, n_pairs, n_lists, (const int*)pstart, cnt,
-                     pair_at);
-  LAUNCH_CHECK();
-  // 64 KB of operands + 1 KB of lists per k + the tile's row map: two workgroups per CU up to k = 15
-  const int lds_max = GEMM_LDS + TQ * MAX_K * (int)sizeof(Cand) + TQ * (int)sizeof(int);
-  static DevOnce attr;
-  if (attr.need()) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(ivf_select_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    attr.done();
+  const IvfQuery a{queries, n_query, bank, n_bank, dim, k, reinterpret_cast<const long long*>(probes), nprobe,
+                   reinterpret_cast<const long long*>(self_rows), reinterpret_cast<const unsigned char*>(list_packed),
+                   n_list_rows, row_of, pos_of, list_tile, n_lists, idx, dist, reinterpret_cast<unsigned char*>(workspace),
+                   reinterpret_cast<const long long*>(query_group), reinterpret_cast<const long long*>(list_group),
+                   (hipStream_t)stream};
+  switch (flags) {
+    case 0: return launch_query<0>(a);
+    case GM_EXCLUDE: return launch_query<GM_EXCLUDE>(a);
+    case GM_ONE: return launch_query<GM_ONE>(a);
+    default: return launch_query<(GM_EXCLUDE | GM_ONE)>(a);
   }
-  const unsigned items = (unsigned)((n_pairs + TQ - 1) / TQ + n_lists);
-  hipLaunchKernelGGL(ivf_select_kernel, dim3(items), dim3(256),
-                     GEMM_LDS + TQ * k * (int)sizeof(Cand) + TQ * (int)sizeof(int), st, (const unsigned char*)qimg,
-                     reinterpret_cast<const unsigned char*>(list_packed), (long)n_list_rows, dim, k, nprobe, n_lists,
-                     (long)n_bank, (const int*)pstart, (const int*)istart, (const int*)pair_at, (const int*)list_tile,
-                     reinterpret_cast<const long long*>(self_rows), (const int*)pos_of, cand);
-  LAUNCH_CHECK();
-  hipLaunchKernelGGL(ivf_merge_kernel, dim3((unsigned)n_query), dim3(64), 0, st, queries, bank, (long)n_bank,
-                     (const Cand*)cand, pr, n_lists, (const int*)row_of, (long)n_list_rows, dim, k, nprobe, idx, dist);
-  LAUNCH_CHECK();
-  return BTSBOT_OK;
+}
+
+}  // namespace
+
+extern "C" int btsbot_ivf_query(const float* queries, int64_t n_query, const float* bank, int64_t n_bank, int dim, int k,
+                                const int64_t* probes, int nprobe, const int64_t* self_rows, const void* list_packed,
+                                int64_t n_list_rows, const int32_t* row_of, const int32_t* pos_of,
+                                const int32_t* list_tile, int n_lists, int64_t* idx, float* dist, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+  return query_checked("btsbot_ivf_query", queries, n_query, bank, n_bank, dim, k, probes, nprobe, self_rows, list_packed,
+                       n_list_rows, row_of, pos_of, list_tile, n_lists, idx, dist, workspace, workspace_bytes, stream,
+                       nullptr, nullptr, 0);
+}
+
+extern "C" int btsbot_ivf_query_grouped(const float* queries, int64_t n_query, const float* bank, int64_t n_bank, int dim,
+                                        int k, const int64_t* probes, int nprobe, const int64_t* self_rows,
+                                        const void* list_packed, int64_t n_list_rows, const int32_t* row_of,
+                                        const int32_t* pos_of, const int32_t* list_tile, int n_lists, int64_t* idx,
+                                        float* dist, void* workspace, int64_t workspace_bytes, void* stream,
+                                        const int64_t* query_group, const int64_t* list_group, int flags) {
+  return query_checked("btsbot_ivf_query_grouped", queries, n_query, bank, n_bank, dim, k, probes, nprobe, self_rows,
+                       list_packed, n_list_rows, row_of, pos_of, list_tile, n_lists, idx, dist, workspace, workspace_bytes,
+                       stream, query_group, list_group, flags);
 }

@@ -68,7 +68,6 @@ namespace {
 
 constexpr int BCAP = 8;             // candidates a query row's bucket holds per round
 enum { MODE_BANK_L2 = 0, MODE_BANK_COS = 1, MODE_QUERY = 2 };
-constexpr int TG_OFF = 16 * 1024;   // the tile's bank groups in the idle operand LDS, behind buckets, counts and flags
 
 // ---------------------------------------------------------------------------------------------------------------------
 // pack: one wave per row
@@ -137,61 +136,7 @@ __global__ __launch_bounds__(256) void knn_pack_kernel(const float* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// selection
-// A list is the k best by (score, index) of what it was offered, UNSORTED (the merge ranks by counting), with its worst
-// entry (ts, ti) at position tp: a better candidate replaces the worst, then the worst is looked up again -- k independent
-// LDS reads, where shifting a sorted list was a chain of dependent ones (23 of 51 ms at N = 500,000, D = 528, k = 15).
-__device__ __forceinline__ void offer(Cand* mine, int k, float s, int gb, float& ts, int& ti, int& tp) {
-  if (!before(s, gb, ts, ti)) return;
-  mine[tp] = Cand{s, gb};
-  Cand w = mine[0];
-  int wp = 0;
-#pragma unroll 4
-  for (int j = 1; j < k; ++j) {
-    const Cand o = mine[j];
-    if (before(w.s, w.i, o.s, o.i)) {
-      w = o;
-      wp = j;
-    }
-  }
-  ts = w.s;
-  ti = w.i;
-  tp = wp;
-}
-
-// One entry per group (the header's argument): mg[j * TQ] is the group of mine[j], in the workspace (the owner's own
-// column of its workgroup's [k][TQ] block: coalesced over the owners).  An entry of the candidate's group decides
-// alone -- the better of the two stays in its place --; without one the candidate is offered as above.
-__device__ __forceinline__ void offer_one(Cand* mine, long long* mg, int k, float s, int gb, long long g, float& ts,
-                                          int& ti, int& tp) {
-  if (!before(s, gb, ts, ti)) return;
-  int at = -1;
-#pragma unroll 4
-  for (int j = 0; j < k; ++j)
-    if (mg[j * TQ] == g && mine[j].i != EMPTY) at = j;   // (at most one entry matches; an empty entry has no group)
-  if (at >= 0) {
-    const Cand e = mine[at];
-    if (!before(s, gb, e.s, e.i)) return;
-  } else {
-    at = tp;
-  }
-  mine[at] = Cand{s, gb};
-  mg[at * TQ] = g;
-  Cand w = mine[0];
-  int wp = 0;
-#pragma unroll 4
-  for (int j = 1; j < k; ++j) {
-    const Cand o = mine[j];
-    if (before(w.s, w.i, o.s, o.i)) {
-      w = o;
-      wp = j;
-    }
-  }
-  ts = w.s;
-  ti = w.i;
-  tp = wp;
-}
-
+// selection: the lists and their offers (offer, offer_one) are knn_tile.h's, shared with the listed pass of ivf.hip
 template <int GM>
 __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char* __restrict__ qimg,
                                                             const unsigned char* __restrict__ bimg, long Q, int N,
@@ -383,7 +328,7 @@ __global__ __launch_bounds__(256, 2) void knn_select_kernel(const unsigned char*
         const int n = min(bcnt[tid], BCAP);
         for (int e = 0; e < n; ++e) {
           const Cand c = bucket[tid * BCAP + e];
-          if constexpr ((GM & GM_ONE) != 0) offer_one(L + tid * k, LG, k, c.s, b0 + c.i, tg[c.i], ts, ti, tp);
+          if constexpr ((GM & GM_ONE) != 0) offer_one(L + tid * k, LG, TQ, k, c.s, b0 + c.i, tg[c.i], ts, ti, tp);
           else offer(L + tid * k, k, c.s, b0 + c.i, ts, ti, tp);
         }
         thr[tid] = ts;
@@ -440,22 +385,7 @@ __global__ __launch_bounds__(64) void knn_merge_kernel(const float* __restrict__
       pgrp[c] = b != EMPTY ? bgrp[b] : 0;
     }
     __syncthreads();
-    unsigned lose = 0;   // bit j: entry lane + 64 j (P <= 32 * 32: at most 16 per lane)
-    for (int c = lane, j = 0; c < P; c += 64, ++j) {
-      const Cand me = pool[c];
-      if (me.i == EMPTY) continue;
-      const long long g = pgrp[c];
-      bool l = false;
-      for (int e = 0; e < P; ++e) {
-        const Cand o = pool[e];
-        l = l || (o.i != EMPTY && pgrp[e] == g && before(o.s, o.i, me.s, me.i));
-      }
-      lose |= l ? 1u << j : 0u;
-    }
-    __syncthreads();
-    for (int c = lane, j = 0; c < P; c += 64, ++j)
-      if ((lose >> j & 1u) != 0) pool[c] = Cand{__builtin_inff(), EMPTY};
-    __syncthreads();
+    keep_group_bests(pool, pgrp, P, lane);
   }
   // the k best of the pool by (score, index): entries are distinct, so the ranks are too
   for (int c = lane; c < P; c += 64) {

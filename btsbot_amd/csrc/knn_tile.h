@@ -266,6 +266,88 @@ __device__ __forceinline__ void frag_bias_scale(const unsigned char* bimg, size_
 
 __device__ __forceinline__ float tile_score(float acc, float sq, float sb, float nb) { return fmaf(-(acc * sq), sb, nb); }
 
+// ---- the selection's lists (knn.hip, ivf.hip)
+constexpr int TG_OFF = 16 * 1024;   // the tile's bank groups in the idle operand LDS, behind buckets, counts and flags
+
+// A list is the k best by (score, index) of what it was offered, UNSORTED (the merge ranks by counting), with its worst
+// entry (ts, ti) at position tp: a better candidate replaces the worst, then the worst is looked up again -- k independent
+// LDS reads, where shifting a sorted list was a chain of dependent ones (23 of 51 ms at N = 500,000, D = 528, k = 15).
+__device__ __forceinline__ void offer(Cand* mine, int k, float s, int gb, float& ts, int& ti, int& tp) {
+  if (!before(s, gb, ts, ti)) return;
+  mine[tp] = Cand{s, gb};
+  Cand w = mine[0];
+  int wp = 0;
+#pragma unroll 4
+  for (int j = 1; j < k; ++j) {
+    const Cand o = mine[j];
+    if (before(w.s, w.i, o.s, o.i)) {
+      w = o;
+      wp = j;
+    }
+  }
+  ts = w.s;
+  ti = w.i;
+  tp = wp;
+}
+
+// One entry per group (knn.hip's header has the argument): mg[j * stride] is the group of mine[j], in the workspace,
+// the owner's own column of a [k][stride] block -- coalesced over the owners.  An entry of the candidate's group decides
+// alone -- the better of the two stays in its place --; without one the candidate is offered as above.  Stride: int for
+// the exact search's constant TQ (its index arithmetic, hence its allocation, as it was), long for the listed pass.
+template <typename Stride>
+__device__ __forceinline__ void offer_one(Cand* mine, long long* mg, Stride stride, int k, float s, int gb, long long g,
+                                          float& ts, int& ti, int& tp) {
+  if (!before(s, gb, ts, ti)) return;
+  int at = -1;
+#pragma unroll 4
+  for (int j = 0; j < k; ++j)
+    if (mg[j * stride] == g && mine[j].i != EMPTY) at = j;   // (at most one entry matches; an empty entry has no group)
+  if (at >= 0) {
+    const Cand e = mine[at];
+    if (!before(s, gb, e.s, e.i)) return;
+  } else {
+    at = tp;
+  }
+  mine[at] = Cand{s, gb};
+  mg[at * stride] = g;
+  Cand w = mine[0];
+  int wp = 0;
+#pragma unroll 4
+  for (int j = 1; j < k; ++j) {
+    const Cand o = mine[j];
+    if (before(w.s, w.i, o.s, o.i)) {
+      w = o;
+      wp = j;
+    }
+  }
+  ts = w.s;
+  ti = w.i;
+  tp = wp;
+}
+
+// The merges' one-per-group step, by one wave: pool[0..P) are a query's candidates and pgrp[c] the group of pool[c]
+// (both in LDS and visible).  An entry counts only if no pool entry of its group is before it by (score, index) -- the
+// bests of one group from the several splits, or probed lists, meet here --; the others become empty.  P <= 32 * 32: at
+// most 16 entries per lane.  Ends with a barrier: the pool is ready to be ranked.
+__device__ __forceinline__ void keep_group_bests(Cand* pool, const long long* pgrp, int P, int lane) {
+  unsigned lose = 0;   // bit j: entry lane + 64 j
+  for (int c = lane, j = 0; c < P; c += 64, ++j) {
+    const Cand me = pool[c];
+    if (me.i == EMPTY) continue;
+    const long long g = pgrp[c];
+    bool l = false;
+    for (int e = 0; e < P; ++e) {
+      const Cand o = pool[e];
+      l = l || (o.i != EMPTY && pgrp[e] == g && before(o.s, o.i, me.s, me.i));
+    }
+    lose |= l ? 1u << j : 0u;
+  }
+  __syncthreads();
+  for (int c = lane, j = 0; c < P; c += 64, ++j)
+    if ((lose >> j & 1u) != 0) pool[c] = Cand{__builtin_inff(), EMPTY};
+  __syncthreads();
+}
+
 // `near`, the kind's own test of the pair, and: may bank row gb be a candidate of this query row at all -- finite, inside
 // the split, not the row itself and (EXCL) not of its group.  (One chain, the kind's test first, as the kernels had it:
 // with that test outside the radius count pass is 6 % slower)

@@ -5,11 +5,15 @@ centroids and searches, for every query row, only the lists of its ``nprobe`` ne
 section 4ab):
 
     fit = kmeans(emb, n_clusters, n_iter=10, init="random", seed=0)    # fit.centroids, .labels, .counts, .inertia, .n_iter
-    ivf = IvfIndex(bank, n_lists=None, centroids=None, n_iter=10, seed=0)
+    ivf = IvfIndex(bank, n_lists=None, centroids=None, n_iter=10, seed=0, groups=None)
     idx, dist = ivf.query(queries, k, nprobe=8)                        # int64 [Q, k] ORIGINAL row numbers, float32 [Q, k]
     lists = ivf.probes(queries, nprobe)                                # int64 [Q, nprobe]
     idx, dist = ivf.knn_graph(k, include_self=True, nprobe=8)          # knn_graph's layout
     ivf.add(rows); kept = ivf.remove(which); ivf.refit(n_iter=10)
+    ivf = IvfIndex(bank, n_lists, groups=obj)                          # int64 [N]: ivf.groups; ivf.add(rows, groups=obj_new)
+    idx, dist = ivf.query(q, k, nprobe, query_groups=obj_q, exclude_same_group=True)    # no row of the query's own object
+    idx, dist = ivf.query(q, k, nprobe, one_per_group=True)                             # the k nearest OBJECTS
+    idx, dist = ivf.knn_graph(k, nprobe=8, group_mode="exclude")       # or "distinct", "exclude+distinct"
 
 What an answer is.  With ``allowed(q)`` = the finite bank rows whose label is in ``probes(q)``, minus ``self_rows[q]``, the
 answer of ``query`` is exactly the k-nearest answer over ``allowed(q)``: the selection scores, the merge and the returned
@@ -19,6 +23,18 @@ direct-form fp32 distances are those of ``EmbeddingIndex.query`` (``dist[q, j]``
 looked at is the only approximation; it is measured as recall and never hidden in the distances.  A row's answer does not
 depend, bit for bit, on the other rows of the call, on the run, or on how the index was grown (``add`` in pieces against
 built at once on the same centroids).
+
+By source.  An index built with ``groups`` (one int64 per row, an alert's object) answers the two switches of
+``EmbeddingIndex.query`` with the same contract over the probed lists.  Under ``exclude_same_group`` ``allowed(q)`` is
+further restricted to the rows of another group than ``query_groups[q]``, and the answer is exactly
+``EmbeddingIndex.query``'s grouped answer over ``allowed(q)``.  Under ``one_per_group`` (``k <= 32``) it is the k nearest
+groups present in ``allowed(q)``, each by its best row by (score, row) -- a group whose rows lie in several probed lists
+meets in the merge and is returned once.  ``self_rows`` stays a compare of positions and combines with every mode.
+Distances are ``direct_distance()``'s, the bits of ``ivf.index.query`` for the same pair; the answer is ordered by (dist,
+original row); the tail is ``-1 / +inf`` where fewer rows -- or groups -- are eligible and ``-1 / NaN`` for a non-finite
+query row.  With ``nprobe == n_lists`` the answer is ``ivf.index.query(...)`` with the same switches, bit for bit, and a
+row's answer still does not depend on the other rows of the call, on the run, or on whether the index was grown by ``add``.
+Nothing is over-fetched and filtered: both switches act inside the selection kernel and its merge.
 
 k-means.  ``init="random"`` takes ``n_clusters`` distinct finite rows by a permutation drawn from
 ``torch.Generator().manual_seed(seed)`` on the host (FAISS's rule); a float32 ``[n_clusters, D]`` tensor is taken as the
@@ -30,7 +46,8 @@ the last iteration the rows are assigned once more: ``labels``, ``counts`` and `
 
 The price of the lists is a second packed image in list order: every list starts on a 128-row tile boundary and is padded
 with the record of a non-finite row, ``record_bytes`` per row (2.1 GB at 10^6 x 528) plus up to 128 padding records per
-list.  Only the euclidean metric is built; ``IvfIndex`` takes no groups.  There is no CPU fallback.
+list, and with groups 8 bytes per position for the groups in list order.  Only the euclidean metric is built.  There is no
+CPU fallback.
 """
 from __future__ import annotations
 
@@ -40,7 +57,7 @@ import torch
 
 from . import _lib
 from ._lib import ptr as _ptr, stream as _stream
-from .neighbors import EmbeddingIndex, _check_k, _n_rows_or_none, _rows
+from .neighbors import GROUP_MODES, EmbeddingIndex, _check_group_args, _check_k, _groups, _n_rows_or_none, _rows
 
 GRAPH_CHUNK = 65536   # rows per query call of IvfIndex.knn_graph
 
@@ -186,10 +203,13 @@ class IvfIndex:
 
     n_lists: None is ``round(sqrt(N))``, clipped to 1 .. 65,536.  centroids: a finite float32 ``[n_lists, D]`` tensor
     skips the fit (checking that it is finite is the one host read of the construction).  n_iter, seed: the fit's, from
-    ``init="random"``.  Calls on one index must be ordered by the caller's streams."""
+    ``init="random"``.  groups: one int64 group per bank row (an alert's object), or None; they are kept by ``.index``
+    (``ivf.groups`` is ``ivf.index.groups``, and ``ivf.index.query(..., exclude_same_group=True)`` works as ever) and, in
+    list order, next to the list image.  An index with groups takes them with every ``add``.  Calls on one index must be
+    ordered by the caller's streams."""
 
     def __init__(self, bank: torch.Tensor, n_lists: Optional[int] = None, *, centroids: Optional[torch.Tensor] = None,
-                 n_iter: int = 10, seed: int = 0, metric: str = "euclidean"):
+                 n_iter: int = 10, seed: int = 0, metric: str = "euclidean", groups: Optional[torch.Tensor] = None):
         _check_metric(metric)
         if n_lists is not None:
             _check_count("n_lists", n_lists, 1, _lib.IVF_MAX_LISTS)
@@ -197,11 +217,13 @@ class IvfIndex:
         _check_seed(seed)
         if centroids is not None:
             _check_centroids(centroids, "centroids", None, n_clusters=n_lists)
+        if groups is not None and _n_rows_or_none(bank) is not None:
+            groups = _groups(groups, "groups", int(bank.shape[0]), bank.device)
         rows = _rows(bank, "bank")
         if centroids is not None:
             _check_centroids(centroids, "centroids", int(rows.shape[1]), rows.device)
         self.metric = metric
-        self.index = EmbeddingIndex(rows)
+        self.index = EmbeddingIndex(rows, groups=groups)
         self.device, self.dim = self.index.device, self.index.dim
         with torch.cuda.device(self.device):
             if centroids is not None:
@@ -221,6 +243,11 @@ class IvfIndex:
         return len(self.index)
 
     @property
+    def groups(self) -> Optional[torch.Tensor]:
+        """The rows' groups, int64 [len] (``index.groups``), or None for an index without groups."""
+        return self.index.groups
+
+    @property
     def n_lists(self) -> int:
         return int(self.centroids.shape[0])
 
@@ -229,7 +256,8 @@ class IvfIndex:
         self._cindex = EmbeddingIndex(c)
 
     def _layout(self) -> None:
-        """The list image, the row maps and the list sizes from ``self.labels`` (``btsbot_ivf_layout``)."""
+        """The list image, the row maps and the list sizes from ``self.labels`` (``btsbot_ivf_layout``) and, on an index
+        with groups, the groups in list order (``btsbot_ivf_layout_groups``)."""
         L, dev, n, nl = _lib.lib(), self.device, len(self.index), self.n_lists
         rec = self.index._record_bytes()
         rows = int(L.btsbot_ivf_list_rows(n, nl))
@@ -248,6 +276,11 @@ class IvfIndex:
                                            _ptr(self._list_packed), rows, _ptr(self._row_of), _ptr(self._pos_of),
                                            _ptr(self.list_sizes), _ptr(self._list_tile), _ptr(ws), need, _stream(dev)),
                        "btsbot_ivf_layout")
+            self._list_groups = None
+            if self.index.groups is not None:
+                self._list_groups = torch.empty(rows, dtype=torch.int64, device=dev)
+                _lib.check(L.btsbot_ivf_layout_groups(_ptr(self.index.groups), n, nl, _ptr(self._row_of), rows,
+                                                      _ptr(self._list_groups), _stream(dev)), "btsbot_ivf_layout_groups")
         self._list_rows = rows
 
     def lists(self) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -258,12 +291,15 @@ class IvfIndex:
         return indptr, self._row_of[self._row_of >= 0].to(torch.int64)
 
     # ---- growth
-    def add(self, rows: torch.Tensor) -> "IvfIndex":
-        """``index.add(rows)``; the new rows' labels come from the FIXED centroids, then the lists are laid out again."""
+    def add(self, rows: torch.Tensor, *, groups: Optional[torch.Tensor] = None) -> "IvfIndex":
+        """``index.add(rows, groups=groups)``; the new rows' labels come from the FIXED centroids, then the lists are laid
+        out again.  groups: int64 [n], required if and only if the index was built with groups."""
+        if (groups is None) != (self.index.groups is None):
+            raise ValueError("add(rows, groups=...) takes groups if and only if the index was built with groups")
         rows = _rows(rows, "rows", self.device)
         if rows.shape[1] != self.dim:
             raise ValueError(f"rows: D = {rows.shape[1]}, the index holds D = {self.dim}")
-        self.index.add(rows)
+        self.index.add(rows, groups=groups)
         if rows.shape[0]:
             with torch.cuda.device(self.device):
                 self.labels = torch.cat([self.labels, _assign(self.centroids, rows)[0]])
@@ -271,7 +307,8 @@ class IvfIndex:
         return self
 
     def remove(self, which: torch.Tensor) -> torch.Tensor:
-        """``index.remove(which)``: returns ``kept``; ``labels`` becomes ``labels[kept]`` and the lists are laid out again."""
+        """``index.remove(which)``: returns ``kept``; ``labels`` becomes ``labels[kept]`` (the groups follow inside
+        ``index``) and the lists are laid out again."""
         n = len(self.index)
         kept = self.index.remove(which)
         if int(kept.shape[0]) != n:
@@ -313,13 +350,23 @@ class IvfIndex:
         self._check_nprobe(nprobe)
         return self._cindex.query(self._queries(queries), nprobe)[0]
 
-    def query(self, queries: torch.Tensor, k: int, nprobe: int = 8,
-              self_rows: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def query(self, queries: torch.Tensor, k: int, nprobe: int = 8, self_rows: Optional[torch.Tensor] = None, *,
+              query_groups: Optional[torch.Tensor] = None, exclude_same_group: bool = False,
+              one_per_group: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """``idx`` int64 [Q, k] (ORIGINAL row numbers) and ``dist`` float32 [Q, k]: each query row's ``k`` nearest rows
         among the lists of its ``nprobe`` nearest centroids (see the module text).  self_rows: int64 [Q], query row i is
-        bank row ``self_rows[i]`` and is excluded by position, so its duplicates stay legitimate neighbours."""
+        bank row ``self_rows[i]`` and is excluded by position, so its duplicates stay legitimate neighbours; it combines
+        with both switches.  query_groups: int64 [Q], the query rows' groups.  exclude_same_group: no row of the query
+        row's own group.  one_per_group: at most one row per group, its nearest; the ``k`` nearest groups (``k <= 32``).
+        Both need an index built with ``groups``."""
         _check_k(k, 0)
         self._check_nprobe(nprobe)
+        flags = 0
+        if query_groups is not None or exclude_same_group is not False or one_per_group is not False:
+            flags = _check_group_args(k, self.index.groups is not None, query_groups, exclude_same_group, one_per_group)
+            nq = _n_rows_or_none(queries)
+            if query_groups is not None and nq is not None:
+                query_groups = _groups(query_groups, "query_groups", nq, self.device)
         if self_rows is not None:
             nq = _n_rows_or_none(queries)
             if not isinstance(self_rows, torch.Tensor) or self_rows.dtype != torch.int64:
@@ -336,26 +383,42 @@ class IvfIndex:
         if nq == 0:
             return idx, dist
         L = _lib.lib()
-        need = int(L.btsbot_ivf_workspace(nq, self.dim, k, nprobe, self.n_lists))
+        need = int(L.btsbot_ivf_workspace_grouped(nq, self.dim, k, nprobe, self.n_lists, flags))
         if need < 0:
-            _lib.check(need, "btsbot_ivf_workspace")
+            _lib.check(need, "btsbot_ivf_workspace_grouped")
         with torch.cuda.device(dev):
             probes = self._cindex.query(q, nprobe)[0]
             ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
             sr = None if self_rows is None else self_rows.detach().contiguous()
-            _lib.check(L.btsbot_ivf_query(_ptr(q), nq, _ptr(self.index._bank), n, self.dim, k, _ptr(probes), nprobe,
-                                          _ptr(sr), _ptr(self._list_packed), self._list_rows, _ptr(self._row_of),
-                                          _ptr(self._pos_of), _ptr(self._list_tile), self.n_lists, _ptr(idx), _ptr(dist),
-                                          _ptr(ws), need, _stream(dev)), "btsbot_ivf_query")
+            args = (_ptr(q), nq, _ptr(self.index._bank), n, self.dim, k, _ptr(probes), nprobe, _ptr(sr),
+                    _ptr(self._list_packed), self._list_rows, _ptr(self._row_of), _ptr(self._pos_of), _ptr(self._list_tile),
+                    self.n_lists, _ptr(idx), _ptr(dist), _ptr(ws), need, _stream(dev))
+            if flags == 0:
+                _lib.check(L.btsbot_ivf_query(*args), "btsbot_ivf_query")
+            else:
+                _lib.check(L.btsbot_ivf_query_grouped(*args, _ptr(query_groups), _ptr(self._list_groups), flags),
+                           "btsbot_ivf_query_grouped")
         return idx, dist
 
-    def knn_graph(self, k: int, include_self: bool = True, nprobe: int = 8) -> Tuple[torch.Tensor, torch.Tensor]:
+    def knn_graph(self, k: int, include_self: bool = True, nprobe: int = 8,
+                  group_mode: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Every row of the index among the others, in ``neighbors.knn_graph``'s layout: ``idx`` int64 [N, k], ``dist``
         float32 [N, k].  include_self=True: the row itself first at distance 0 (-1 / NaN for a non-finite row), then its
         ``k - 1`` nearest others among its probed lists; False: ``k`` others.  A row is excluded by position: its
-        duplicates are legitimate neighbours.  The rows are asked in chunks."""
+        duplicates are legitimate neighbours.  group_mode (an index with groups; a row's own group is its query group):
+        ``"exclude"`` the others are rows of OTHER groups only, ``"distinct"`` at most one row per group,
+        ``"exclude+distinct"`` both, as ``neighbors.knn_graph``; None: no groups are read.  The rows are asked in chunks."""
         _check_k(k, 0)
         self._check_nprobe(nprobe)
+        kw = {}
+        if group_mode is not None:
+            if group_mode not in GROUP_MODES:
+                raise ValueError(f"group_mode must be None or one of {GROUP_MODES}, got {group_mode!r}")
+            groups = self.index.groups
+            if groups is None:
+                raise ValueError("group_mode needs an index built with groups=...")
+            kw = dict(exclude_same_group="exclude" in group_mode, one_per_group="distinct" in group_mode)
+            _check_group_args(k - 1 if include_self else k, True, groups, kw["exclude_same_group"], kw["one_per_group"])
         rows, dev = self.index.bank, self.device
         n = int(rows.shape[0])
         idx = torch.empty((n, k), dtype=torch.int64, device=dev)
@@ -369,6 +432,8 @@ class IvfIndex:
         if k > first:
             for a in range(0, n, GRAPH_CHUNK):
                 b = min(n, a + GRAPH_CHUNK)
-                i, d = self.query(rows[a:b], k - first, nprobe, self_rows=torch.arange(a, b, device=dev))
+                if kw:
+                    kw["query_groups"] = groups[a:b]
+                i, d = self.query(rows[a:b], k - first, nprobe, self_rows=torch.arange(a, b, device=dev), **kw)
                 idx[a:b, first:], dist[a:b, first:] = i, d
         return idx, dist

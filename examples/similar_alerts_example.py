@@ -10,7 +10,12 @@ its nearest alert, their distances and the distance-weighted vote of their label
 model's own score.  Without the two switches the answer would be the other epochs of the alert's own source.  Nothing of
 size night x archive is ever formed.
 
+With ``--ivf N_LISTS`` the labelled archive is a ``btsbot.IvfIndex(..., groups=ids)`` -- the index for archives too large
+for the linear search -- asked with the same two switches over the lists of each alert's ``--nprobe`` nearest centroids,
+and the recall of its sources against the exact grouped answer of the same run is printed.
+
     python examples/similar_alerts_example.py [--archive 4096] [--night 512] [--k 7] [--epochs 4] [--metric cosine]
+                                              [--ivf N_LISTS] [--nprobe 8]
 """
 import argparse
 import os
@@ -35,7 +40,11 @@ def main():
     p.add_argument("--precision", type=str, default="f16", choices=["f32", "bf16", "f16", "f16x2"])
     p.add_argument("--batch", type=int, default=256, help="alerts per forward")
     p.add_argument("--show", type=int, default=8, help="alerts printed")
+    p.add_argument("--ivf", type=int, default=0, metavar="N_LISTS", help="ask an IvfIndex of this many lists (0: the exact search)")
+    p.add_argument("--nprobe", type=int, default=8, help="lists searched per alert with --ivf")
     args = p.parse_args()
+    if args.ivf and args.metric != "euclidean":
+        p.error("--ivf is built for --metric euclidean only")
     dev = torch.device("cuda:0")
     model = seeded_model(args.precision).to(dev).eval()
 
@@ -56,15 +65,26 @@ def main():
             index = btsbot.EmbeddingIndex(emb, args.metric, groups=g) if index is None else index.add(emb, groups=g)
     print(f"archive: {len(index)} alerts of {len(source)} sources, {int(labels.sum())} alerts labelled real, "
           f"embedding width {index.dim}")
+    ivf = None
+    if args.ivf:
+        ivf = btsbot.IvfIndex(index.bank, args.ivf, groups=index.groups)
+        nprobe = min(args.nprobe, ivf.n_lists)
+        print(f"ivf: {ivf.n_lists} lists, the largest of {int(ivf.list_sizes.max())} alerts; {nprobe} probed per alert")
 
     images, meta, truth = synthetic_batch(args.night, seed=12)
     own = source[torch.arange(args.night, device=dev) % len(source)]               # tonight's alerts: archive sources
     shown = 0
-    agree = total = 0
+    agree = total = found = asked = 0
     with torch.no_grad():
         for logits, emb in stream.map(batches(images, meta)):
-            idx, dist = index.query(emb, args.k, query_groups=own[total:total + emb.shape[0]], exclude_same_group=True,
-                                    one_per_group=True)
+            kw = dict(query_groups=own[total:total + emb.shape[0]], exclude_same_group=True, one_per_group=True)
+            idx, dist = index.query(emb, args.k, **kw)
+            if ivf is not None:
+                exact = idx
+                idx, dist = ivf.query(emb, args.k, nprobe, **kw)
+                hit = (groups[idx.clamp(min=0)][:, :, None] == groups[exact.clamp(min=0)][:, None, :]) & (idx >= 0)[:, :, None]
+                found += int((hit.any(dim=1) & (exact >= 0)).sum())
+                asked += int((exact >= 0).sum())
             majority = btsbot.neighbor_vote(idx, dist, labels, weights="distance") > 0.5
             score = torch.sigmoid(logits).reshape(-1)
             agree += int((majority == (score > 0.5)).sum())
@@ -76,6 +96,8 @@ def main():
                       f"weighted label {'real' if bool(majority[r]) else 'bogus'}")
                 shown += 1
     print(f"{total} alerts of the night: the nearest sources' weighted label agrees with the model's own call on {agree}")
+    if ivf is not None:
+        print(f"ivf: {found} of the {asked} sources of the exact grouped answer found ({found / max(asked, 1):.4f} recall)")
     del truth
 
 

@@ -1418,7 +1418,22 @@ int btsbot_knn_graph_compact(const int64_t* idx, const float* dist, int64_t stri
  * btsbot_ivf_workspace() bytes -- the packed image of the query rows, n_query * nprobe * k candidates of 8 bytes, 4
  * bytes per (query, probe) pair and 12 per list --, 16-byte aligned.  Seven launches and two memsets on `stream`.
  * BTSBOT_ERR_INVALID_ARG with a message, before any HIP call, for a shape out of range, n_query * nprobe >= 2^31, a
- * NULL or misaligned pointer, a workspace too small. */
+ * NULL or misaligned pointer, a workspace too small.
+ *
+ * Groups: btsbot_ivf_query_grouped() is btsbot_ivf_query() with the two switches of btsbot_knn_query_grouped() and the
+ * same contract over the rows of the probed lists.  flags: BTSBOT_KNN_EXCLUDE_SAME, BTSBOT_KNN_ONE_PER_GROUP, both, or 0
+ * (btsbot_ivf_query() itself: the groups are not read).  query_group int64 [n_query] (needed by EXCLUDE_SAME);
+ * list_group int64 [n_list_rows]: the rows' groups in LIST order, made by btsbot_ivf_layout_groups(bank_group int64
+ * [n_bank], ..., row_of, n_list_rows, list_group) after btsbot_ivf_layout() -- list_group[p] = bank_group[row_of[p]], 0
+ * at a padding position (never a candidate); one launch.  EXCLUDE_SAME: no row of the query row's own group is a
+ * candidate.  ONE_PER_GROUP (k <= 32): the k nearest groups among the eligible rows of the probed lists, each by its
+ * best row by (score, original row) -- a group whose rows lie in several probed lists is met in the merge and returned
+ * once.  self_rows stays a compare of positions and combines with every mode.  Distances, ordering, tails and the
+ * independence of a row's answer from the call and the run are btsbot_ivf_query()'s; with every list probed the answer
+ * is btsbot_knn_query_grouped()'s, bit for bit.  workspace: btsbot_ivf_workspace_grouped() bytes, which under
+ * ONE_PER_GROUP adds the groups of the list entries, int64 [k][n_query * nprobe] (8 k bytes per pair; no n_lists term
+ * and no host read).  BTSBOT_ERR_INVALID_ARG with a message for flags with other bits, k > 32 under ONE_PER_GROUP, and
+ * a NULL query_group / list_group where the flags need them. */
 int64_t btsbot_kmeans_workspace(int64_t n_rows, int dim, int n_clusters);
 int btsbot_kmeans_update(const float* rows, int64_t n_rows, int dim, const int64_t* labels, const int64_t* order,
                          int n_clusters, float* centroids, int64_t* counts, void* workspace, int64_t workspace_bytes,
@@ -1432,6 +1447,15 @@ int btsbot_ivf_query(const float* queries, int64_t n_query, const float* bank, i
                      const int64_t* probes, int nprobe, const int64_t* self_rows, const void* list_packed,
                      int64_t n_list_rows, const int32_t* row_of, const int32_t* pos_of, const int32_t* list_tile,
                      int n_lists, int64_t* idx, float* dist, void* workspace, int64_t workspace_bytes, void* stream);
+int btsbot_ivf_layout_groups(const int64_t* bank_group, int64_t n_bank, int n_lists, const int32_t* row_of,
+                             int64_t n_list_rows, int64_t* list_group, void* stream);
+int64_t btsbot_ivf_workspace_grouped(int64_t n_query, int dim, int k, int nprobe, int n_lists, int flags);
+int btsbot_ivf_query_grouped(const float* queries, int64_t n_query, const float* bank, int64_t n_bank, int dim, int k,
+                             const int64_t* probes, int nprobe, const int64_t* self_rows, const void* list_packed,
+                             int64_t n_list_rows, const int32_t* row_of, const int32_t* pos_of,
+                             const int32_t* list_tile, int n_lists, int64_t* idx, float* dist, void* workspace,
+                             int64_t workspace_bytes, void* stream, const int64_t* query_group,
+                             const int64_t* list_group, int flags);
 
 /* ---- HDBSCAN: the mutual-reachability spanning tree and its hierarchy (csrc/mr_offer.hip, csrc/mst.hip,
  *      csrc/hdbscan_tree.hip) ---- */
